@@ -16,6 +16,11 @@ libcrt.so, the compact RGB8 tile buffers are all-gathered over RCCL and de-inter
 The total work is fixed as N grows ("strong" scaling).  One frame at a time (ms_per_step is a frame's latency);
 --frames-in-flight 2 overlaps consecutive frames (an option, see its help text).
 
+A plain run sets up, warms up, times --steps frames and prints the JSON line (with --dump-outputs DIR it first writes the
+last timed frame, see dump_outputs).  Everything else below -- the device BVH set-up record, the roofline and contract
+figures, parity, cpu_baseline, the all-rays-traced and other-mode frames, the C3 and mesh-size sub-records -- runs
+only with --full.
+
 A ray is one closest-hit query of the reference (DeviceBVH::intersect): primary, bounce, shadow and specular-probe
 rays; the count is deterministic given (scene, config, seed) and comes from the kernel's counters.
 
@@ -93,8 +98,14 @@ def parse_args():
                     help="exact (default): provably the reference's frame; fast: + distance pruning (measured rate of lost rays, include/crt.h)")
     ap.add_argument("--engine", default="procs", choices=["procs", "multi"],
                     help="procs: one process per GPU, torch.distributed over RCCL; multi: one process, crt_multi_render")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c3", action="store_true", help="skip the veach-mis 800x600 spp=1024 sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: device BVH set-up, "
+                         "roofline / contract figures, parity against the CPU oracle, cpu_baseline, the all-rays-traced and other-mode "
+                         "frames, the C3 and mesh-size sub-records (each --no-* option below drops one of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed frame as DIR/<name>.npy (float32 image, float64 ray counts; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity gate")
+    ap.add_argument("--no-c3", action="store_true", help="--full: skip the veach-mis 800x600 spp=1024 sub-record")
     ap.add_argument("--cpu-spp", type=int, default=8)
     ap.add_argument("--frames-in-flight", type=int, default=1, choices=[1, 2],
                     help="1 (default): one frame at a time, ms_per_step is a frame's latency.  2: frames are pipelined over two device "
@@ -103,7 +114,7 @@ def parse_args():
                          "share of C2 at 1 / 2 / 4 / 8 ranks (tools/pipeline_probe.py), but k_accumulate of frame i then waits for "
                          "kernel i+1 (no free VGPRs) and a frame's latency doubles -- an option, not the reported number")
     ap.add_argument("--save-png", default=None)
-    ap.add_argument("--no-large-scene", action="store_true", help="skip the large-mesh sub-record (a 126 000-triangle variant of the scene, and the stand-in under the large-mesh layout)")
+    ap.add_argument("--no-large-scene", action="store_true", help="--full: skip the large-mesh sub-record (a 126 000-triangle variant of the scene, and the stand-in under the large-mesh layout)")
     a = ap.parse_args()
     w = WORKLOADS[a.workload or "c2"]
     explicit = any(v is not None for v in (a.scene, a.width, a.height, a.spp))
@@ -312,6 +323,33 @@ def device_identity(torch, device):
     return int.from_bytes(h[:8], "little") >> 1, src
 
 
+DUMP_IMAGE_LIMIT = 48 << 20   # bytes of float32 image per dump; the whole dump stays below 64 MB
+
+
+def dump_outputs(out_dir, image, rays, rays_untraced):
+    """--dump-outputs: what a caller of the timed path receives for its last frame, written as out_dir/<name>.npy.
+      image.npy   (H, W, 3) float32, the RGB8 frame (values 0 .. 255)
+      rays.npy    (2,) float64, the frame's ray count and its untraced share (rays_per_frame, rays_untraced_per_frame)
+    A frame whose float32 image exceeds DUMP_IMAGE_LIMIT is written as a fixed sample of its pixels instead (numpy seed 0):
+      image_sample.npy (n, 3) float32 and image_sample_pixels.npy (n,) float64, their row-major pixel indices.
+    Returns the names written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rgb = np.asarray(image, dtype=np.float32)
+    h, w, c = rgb.shape
+    out = {"rays": np.array([rays, rays_untraced], dtype=np.float64)}
+    if rgb.nbytes <= DUMP_IMAGE_LIMIT:
+        out["image"] = rgb
+    else:
+        n = DUMP_IMAGE_LIMIT // (4 * c + 8)
+        pick = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        out["image_sample"] = rgb.reshape(h * w, c)[pick]
+        out["image_sample_pixels"] = pick.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
+
+
 def main_rank(args):
     import numpy as np
     import torch
@@ -387,9 +425,11 @@ def main_rank(args):
                              gather=crt.GATHER_COPY if one_device else (crt.GATHER_RCCL if args.gpus > 1 else crt.GATHER_AUTO))
         mr.seed = args.seed
         mr.traversal = trav
-    render = crt.Render(scene, args.spp, task.P_RR, task.light_sample_n, device=local_rank)
-    render.seed = args.seed
-    render.traversal = trav
+    render = None   # (--engine multi steps on mr; this single-device handle is then only needed by the --full legs)
+    if not multi or args.full:
+        render = crt.Render(scene, args.spp, task.P_RR, task.light_sample_n, device=local_rank)
+        render.seed = args.seed
+        render.traversal = trav
     pipelined = args.frames_in_flight > 1 and not multi
     render2 = None
     if pipelined:
@@ -397,21 +437,22 @@ def main_rank(args):
         render2.seed = args.seed
         render2.traversal = trav
 
-    if rank == 0:
+    if rank == 0 and render is not None:
+        ai = render.accel_info()
+        setup.update({"sah_tree": {"on_device": bool(ai["sah_on_device"]), "ms": round(ai["sah_ms"], 2), "device_ms": round(ai["sah_device_ms"], 2),
+                                   "leaves": ai["n_leaves"], "nodes4": ai["n_nodes4"]},
+                      # the HIP runtime's one-off start in this process (context, code objects), paid by whatever touches the device first:
+                      # timed by itself (crt_accel_info.runtime_init_ms); rounds 1-3 booked it on the SAH build ("147 ms")
+                      "runtime_init_ms": round(ai["runtime_init_ms"], 2)})
+    if rank == 0 and args.full:
         # scene set-up on the device (not part of a step): the reference BVH (byte-identical to the host build above) and the SAH tree of
         # the FAST traversal, both built on the GPU -- crt_host_scene_set_bvh_device / crt_scene_create
         s2 = crt.Scene.from_task(task, args.width, args.height, bvh_device=local_rank)
         s2 = crt.Scene.from_task(task, args.width, args.height, bvh_device=local_rank)  # (second build: code objects loaded)
         same = s2.nodes().tobytes() == scene.nodes().tobytes() and s2.triangles().tobytes() == scene.triangles().tobytes()
         bi = s2.bvh_build_info
-        ai = render.accel_info()
-        setup.update({"bvh_device": {"total_ms": round(bi["total_ms"], 2), "level_loop_ms": round(bi["device_ms"], 2), "host_sorts": bi["host_sorts"],
-                                     "host_triangles": bi["host_triangles"], "byte_identical_to_host_build": bool(same)},
-                      "sah_tree": {"on_device": bool(ai["sah_on_device"]), "ms": round(ai["sah_ms"], 2), "device_ms": round(ai["sah_device_ms"], 2),
-                                   "leaves": ai["n_leaves"], "nodes4": ai["n_nodes4"]},
-                      # the HIP runtime's one-off start in this process (context, code objects), paid by whatever touches the device first:
-                      # timed by itself (crt_accel_info.runtime_init_ms); rounds 1-3 booked it on the SAH build ("147 ms")
-                      "runtime_init_ms": round(ai["runtime_init_ms"], 2)})
+        setup["bvh_device"] = {"total_ms": round(bi["total_ms"], 2), "level_loop_ms": round(bi["device_ms"], 2), "host_sorts": bi["host_sorts"],
+                               "host_triangles": bi["host_triangles"], "byte_identical_to_host_build": bool(same)}
         s2.free()
 
     def step():
@@ -504,10 +545,22 @@ def main_rank(args):
     mrays = (rays_frame - untraced_frame) * args.steps / elapsed / 1e6
     n_gpus = args.gpus
     single = n_gpus == 1
+    multi_info = dict(mr.info) if multi else None   # (of the timed frames)
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        if multi:
+            # the timed steps leave the frame on rank 0's device: the same frame (fixed seed and inputs) is rendered once more, to the host
+            frame = mr.run_view(eye, inv_view, fov, want_mean=False, width=args.width, height=args.height)
+        else:
+            frame = img.cpu().numpy()
+        dumped = dump_outputs(args.dump_outputs, frame, rays_frame, untraced_frame)
 
     if rank == 0:
         wl = args.workload_id          # "c2" .. "c5" when the run is exactly that BASELINE configuration, else None
         c2 = wl == "c2"
+        roofline = exact_vs_reference = fast_vs_reference = None
+    if rank == 0 and args.full:
         # ---- contract figure: bytes per ray from the counting kernels on a spp=8 slice of the same frame; the same two renders
         #      give the FAST == REFERENCE cross-check (every pixel of the slice, float bits) ----
         def visit_bytes(st, node_bytes=64.0):
@@ -590,10 +643,11 @@ def main_rank(args):
         else:
             roofline["note"] = pmc_note
 
+    if rank == 0:
         # ---- the same frame with every next-event sample traced (CRT_FLAG_TRACE_ALL): the default path answers the samples whose
         #      contribution is exactly zero without traversal (same frame bit for bit; they still count as rays of the reference) ----
         all_traced = None
-        if single and not multi:
+        if args.full and single and not multi:
             render.set_spp(args.spp)
             render.extra_flags = crt.FLAG_TRACE_ALL
             step()
@@ -610,7 +664,7 @@ def main_rank(args):
         #      CRT_TRAVERSAL_EXACT (default; provably the reference's frame; docs/experiments.md 4.3) against CRT_TRAVERSAL_FAST (+ distance pruning) ----
         other_mode = None
         other_name = None
-        if single and not multi and trav in (crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
+        if args.full and single and not multi and trav in (crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
             other = crt.TRAVERSAL_EXACT if trav == crt.TRAVERSAL_FAST else crt.TRAVERSAL_FAST
             other_name = "exact_mode" if other == crt.TRAVERSAL_EXACT else "fast_mode"
             render.set_spp(args.spp)
@@ -632,7 +686,7 @@ def main_rank(args):
 
         # ---- C3 (veach-mis 800x600 spp=1024: divergence stress) timed by the same run ----
         c3 = None
-        if single and c2 and not multi and not args.no_c3:
+        if args.full and single and c2 and not multi and not args.no_c3:
             t3 = crt.Task(os.path.join(ROOT, "scenes", "veach-mis", "config.json"), base_dir=ROOT)
             s3 = crt.Scene.from_task(t3, 800, 600)
             r3 = crt.Render(s3, 1024, t3.P_RR, t3.light_sample_n, device=local_rank)
@@ -689,7 +743,7 @@ def main_rank(args):
         #      mesh got in rounds 1-3), and a 102 412-triangle variant of the scene (scenes/gen_cornell_box.py --detail 6,5), same
         #      camera, same spp ----
         large = None
-        if single and c2 and not multi and not args.no_large_scene:
+        if args.full and single and c2 and not multi and not args.no_large_scene:
             def timed_frames(rr, n=3):
                 render_sharded(rr, eye, inv_view, fov, args.width, args.height, 0, 1, device)
                 torch.cuda.synchronize(device)
@@ -749,7 +803,7 @@ def main_rank(args):
         #      thread; the GPU renders the same frame; every pixel is compared ----
         cpu = None
         parity = None
-        if single and not args.no_cpu_baseline:
+        if args.full and single and not args.no_cpu_baseline:
             import oracle_lib as O
             osc = O.OracleScene(task.OBJ_paths, task.bvh_thresh_n)
             c0 = time.perf_counter()
@@ -783,8 +837,8 @@ def main_rank(args):
         rccl_ranks = 0
         rccl_evidence = None
         if multi:
-            rccl_ranks = int(mr.info["rccl_ranks"])   # ncclCommCount of the communicator crt_multi_render gathers on (0: peer copies)
-            rccl_evidence = {"source": "ncclCommCount (crt_multi_info.rccl_ranks)", "fallback_reason": mr.info.get("fallback_reason") or None}
+            rccl_ranks = int(multi_info["rccl_ranks"])   # ncclCommCount of the communicator crt_multi_render gathers on (0: peer copies)
+            rccl_evidence = {"source": "ncclCommCount (crt_multi_info.rccl_ranks)", "fallback_reason": multi_info.get("fallback_reason") or None}
         elif world > 1 and backend == "nccl":
             rccl_ranks = int(collective_proof["ranks_counted_by_all_reduce"])
             rccl_evidence = dict(collective_proof, source="sum of a device tensor of ones all-reduced over the RCCL process group (torch exposes no ncclCommCount); "
@@ -792,7 +846,7 @@ def main_rank(args):
         line = {
             "metric": "Mrays/sec", "value": round(mrays, 2), "unit": "Mrays/s", "n_gpus": n_gpus, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "%s %dx%d spp=%d P_RR=%g light_sample_n=%d (stand-in cornell-box.obj, 40972 triangles)"
                                    % (args.scene, args.width, args.height, args.spp, float(task.P_RR), task.light_sample_n)
                        if args.scene == "cornell-box" else
@@ -802,7 +856,7 @@ def main_rank(args):
                        "engine": "one process, crt_multi_render" if multi else "one process per GPU, torch.distributed",
                        "untraced_samples": "next-event samples whose contribution is exactly zero are answered without traversal "
                                            "(frame bit-identical, still counted as rays of the reference): %.1f%% of the rays%s; "
-                                           "`all_rays_traced` times the same frame with every one of them traced"
+                                           "`all_rays_traced` (--full) times the same frame with every one of them traced"
                                            % (100.0 * untraced_frame / max(1.0, rays_frame), "")},
             "value_definition": "rays TRACED per second (reference rays minus the zero-contribution next-event samples answered without traversal); "
                                 "`value_reference_rays` divides the reference's own ray count by the same time; ms_per_step is the figure that compares across implementations",
@@ -837,6 +891,7 @@ def main_rank(args):
             "roofline": roofline,
             "exact_vs_reference": exact_vs_reference,
             "fast_vs_reference": fast_vs_reference,
+            "dumped_outputs": dumped,
         }
         if n_gpus > 1:
             # what a rank's step is made of: its kernel (min / max over the ranks: the interleaved tiles balance the load, the spread
@@ -855,7 +910,7 @@ def main_rank(args):
             except Exception:
                 pass
         if multi:
-            line["multi_info"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in mr.info.items()}
+            line["multi_info"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in multi_info.items()}
         if parity is not None:
             line["parity"] = parity
         if c3 is not None:
@@ -865,7 +920,8 @@ def main_rank(args):
         if cpu is not None:
             line["cpu_baseline"] = cpu
         print(json.dumps(line), flush=True)
-    render.free()
+    if render is not None:
+        render.free()
     if render2 is not None:
         render2.free()
     if mr is not None:
@@ -879,6 +935,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be positive")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be positive and --warmup not negative")
     if args.engine == "procs" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     main_rank(args)

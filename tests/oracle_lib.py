@@ -1,6 +1,6 @@
 """ctypes binding of oracle/liboracle.so -- test infrastructure only.
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
+Only tests/, __graft_entry__.smoke() and bench.py --full's cpu_baseline leg import this.
 """
 import ctypes as C
 import os

@@ -229,6 +229,31 @@ def test_bench_workload_aliases_are_the_baseline_configurations(monkeypatch):
     assert bench.parse_args().workload_id == "c3"
 
 
+def test_bench_dump_outputs_are_float_arrays_within_the_size_limit(tmp_path, monkeypatch):
+    """--dump-outputs writes float32 / float64 .npy files; an image above the limit becomes a fixed sample of its pixels, the same on
+    every run, and the whole dump stays under 64 MB.  A plain run is the default: --full is off."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse_args()
+    assert a.full is False and a.dump_outputs is None
+    rng = np.random.default_rng(1)
+    small = rng.integers(0, 256, (152, 200, 3), dtype=np.uint8)
+    assert bench.dump_outputs(str(tmp_path / "s"), small, 123.0, 4.0) == ["image", "rays"]
+    img, rays = np.load(tmp_path / "s" / "image.npy"), np.load(tmp_path / "s" / "rays.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, small.astype(np.float32))
+    assert rays.dtype == np.float64 and rays.tolist() == [123.0, 4.0]
+    big = rng.integers(0, 256, (2160, 3840, 3), dtype=np.uint8)
+    for d in ("b1", "b2"):
+        assert bench.dump_outputs(str(tmp_path / d), big, 1.0, 0.0) == ["image_sample", "image_sample_pixels", "rays"]
+    total = sum(os.path.getsize(tmp_path / "b1" / f) for f in os.listdir(tmp_path / "b1"))
+    assert total <= 64 * 1024 * 1024
+    px, smp = np.load(tmp_path / "b1" / "image_sample_pixels.npy"), np.load(tmp_path / "b1" / "image_sample.npy")
+    assert px.dtype == np.float64 and smp.dtype == np.float32 and len(px) == len(smp) > 1000000
+    assert np.array_equal(smp, big.reshape(-1, 3)[px.astype(np.int64)].astype(np.float32))
+    for f in ("image_sample.npy", "image_sample_pixels.npy"):
+        assert np.array_equal(np.load(tmp_path / "b1" / f), np.load(tmp_path / "b2" / f))
+
+
 def test_header_constants_match_the_python_mirror():
     """include/crt.h is the contract: the enum values the Python mirror passes must be the header's, and the default traversal mode
     (a zeroed crt_params) must be the provably exact one."""
@@ -258,14 +283,11 @@ def test_header_constants_match_the_python_mirror():
 
 def test_the_documented_reference_side_binding_compiles(tmp_path):
     """INTEGRATION.md section 2 shows the `Render` class a maintainer of the reference would drop in (talking to libcrt.so through
-    include/crt.h).  The code block is extracted and type-checked here -- against include/crt.h, the reference's vendored Eigen and
-    test-only declarations of the Scene / BVH / Triangle / Material / Object getters it calls (tests/shim_decls/Scene.h) -- with the
-    calls src/main.cu makes (main.cu:282, 368-377), so that a change of a struct in crt.h cannot silently break the documented binding."""
-    import shutil
+    include/crt.h).  The code block is extracted and type-checked here -- against include/crt.h and test-only declarations of the
+    Eigen types (tests/shim_decls/Eigen/Dense) and of the Scene / BVH / Triangle / Material / Object getters it calls
+    (tests/shim_decls/Scene.h) -- with the calls src/main.cu makes (main.cu:282, 368-377), so that a change of a struct in crt.h cannot
+    silently break the documented binding."""
     import subprocess
-    eigen = "/root/reference/include"
-    if not os.path.isdir(os.path.join(eigen, "Eigen")) or not shutil.which("g++"):
-        pytest.skip("needs the reference's vendored Eigen (/root/reference) and g++")
     text = open(os.path.join(util.ROOT, "INTEGRATION.md")).read()
     sect = text[text.index("## 2. Reference-side shim"):]
     code = sect[sect.index("```cpp") + 6:]
@@ -286,6 +308,6 @@ int use(Scene* scene, Eigen::Vector3f eye, Eigen::Matrix3f inv_view, float fov_y
 }
 ''')
     cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror=narrowing", "-I", os.path.join(util.ROOT, "include"),
-           "-I", os.path.join(util.ROOT, "tests", "shim_decls"), "-I", eigen, str(tmp_path / "main.cpp")]
+           "-I", os.path.join(util.ROOT, "tests", "shim_decls"), str(tmp_path / "main.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]

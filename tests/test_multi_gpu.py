@@ -125,7 +125,7 @@ def test_bench_started_plainly_starts_its_own_ranks(single, tmp_path):
     on the one GPU, gathering over gloo); the line must carry the whole frame's rays and the one-device image."""
     from PIL import Image
     png = str(tmp_path / "two.png")
-    line = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "4", "--width", "200", "--height", "152", "--no-cpu-baseline",
+    line = _bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--spp", "4", "--width", "200", "--height", "152", "--full", "--no-cpu-baseline",
                    "--save-png", png], {"CRT_BENCH_ONE_DEVICE": "1"})
     assert line["n_gpus"] == 2 and line["collective"]["launched_by"].startswith("bench.py")
     assert line["collective"]["backend"] == "gloo" and line["collective"]["rccl_ranks"] == 0
@@ -231,7 +231,7 @@ def test_bench_multi_engine_one_process(single):
 def test_bench_default_line_has_parity_and_bounded_roofline():
     """The single-GPU line on a reduced workload: same-run parity gate against the oracle (all pixels), FAST == REFERENCE
     slice, and every priced bound's fraction <= 1 when PMC counters of this code are present."""
-    line = _bench(["--steps", "1", "--warmup", "1", "--spp", "8", "--width", "160", "--height", "120", "--cpu-spp", "2", "--no-c3"], {})
+    line = _bench(["--steps", "1", "--warmup", "1", "--spp", "8", "--width", "160", "--height", "120", "--cpu-spp", "2", "--no-c3", "--full"], {})
     p = line["parity"]
     assert p["pixels_gt_1e-5"] == 0 and p["pixels_differ_f32_bits"] == 0 and p["rgb8_mismatch"] == 0 and p["rays_equal"]
     assert line["fast_vs_reference"]["pixels_differ_f32_bits"] == 0
@@ -239,6 +239,28 @@ def test_bench_default_line_has_parity_and_bounded_roofline():
     rf = line["roofline"]
     assert rf["frac"] is None or rf["frac"] <= 1.0  # (PMC passes exist for the C2 workload only: null here)
     assert rf["contract_frac"] > 0 and "contract_note" in rf
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_frame(single, tmp_path):
+    """A plain run (no --full) times exactly --steps frames, carries none of the --full records, and --dump-outputs writes the timed
+    frame: the one-device image as float32 and the frame's ray counts.  --engine multi dumps the same frame."""
+    eye, iv, fov = util.camera("cornell-box")
+    one = single["cornell-box"]
+    one.set_spp(4)
+    one.traversal = crt.TRAVERSAL_EXACT
+    rgb = one.run_view(eye, iv, fov, width=200, height=152).copy()
+    rays = [one.stats["rays"], one.stats["rays_untraced"]]
+    args = ["--steps", "3", "--warmup", "1", "--spp", "4", "--width", "200", "--height", "152"]
+    for extra, env in (([], {}), (["--gpus", "2", "--engine", "multi"], {"CRT_BENCH_ONE_DEVICE": "1"})):
+        out = tmp_path / ("dump_%d" % len(extra))
+        line = _bench(args + extra + ["--dump-outputs", str(out)], env)
+        assert line["steps"] == 3 and line["full"] is False and line["ms_per_step"] > 0
+        assert line["roofline"] is None and line["all_rays_traced"] is None and "parity" not in line and "cpu_baseline" not in line
+        assert line["dumped_outputs"] == ["image", "rays"] and sorted(os.listdir(out)) == ["image.npy", "rays.npy"]
+        img = np.load(out / "image.npy")
+        assert img.dtype == np.float32 and np.array_equal(img, rgb.astype(np.float32)), extra
+        r = np.load(out / "rays.npy")
+        assert r.dtype == np.float64 and r.tolist() == rays and line["rays_per_frame"] == rays[0], extra
 
 
 def test_cli_multi_device(tmp_path):

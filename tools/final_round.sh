@@ -22,7 +22,8 @@ for wl in c2 c3 c4 c5; do
 done
 cat gpurun_out/$tag/share_probe.jsonl
 python3 tools/share_model.py gpurun_out/$tag/share_probe.jsonl > gpurun_out/$tag/share_model.json && cp gpurun_out/$tag/share_model.json profiles/share_model.json
-timeout -k 10 600 python3 bench.py > gpurun_out/$tag/bench.log 2>&1 || { echo "bench failed"; tail -20 gpurun_out/$tag/bench.log; exit 7; }
-tail -1 gpurun_out/$tag/bench.log | cut -c1-400
+mkdir -p logs   # (the round's bench line: --full, roofline and sub-records included; tools/keep_profiles.sh keeps it)
+timeout -k 10 600 python3 bench.py --full > logs/${tag}_bench.log 2>&1 || { echo "bench failed"; tail -20 logs/${tag}_bench.log; exit 7; }
+tail -1 logs/${tag}_bench.log | cut -c1-400
 CRT_BENCH_ONE_DEVICE=1 timeout -k 10 300 python3 bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --no-c3 > gpurun_out/$tag/bench_2ranks_one_device.log 2>&1 || { echo "2-rank rehearsal failed"; tail -20 gpurun_out/$tag/bench_2ranks_one_device.log; exit 8; }
 tail -1 gpurun_out/$tag/bench_2ranks_one_device.log | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('2 ranks on one device:', d['ms_per_step'], d.get('per_rank'))"

@@ -17,7 +17,7 @@ cp $src/profiles_$tag/c3_summary.json $dst/c3_pmc_summary.json
 cp $src/profiles_$tag/stats_summary.json $dst/bench_stats_summary.json
 cp $src/profiles_$tag/bench_line.json $dst/bench_line_profiled.json
 f=$(ls $src/profiles_$tag/stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $dst/bench_kernel_stats.csv
-grep -h '"metric"' $src/$tag/bench.log | tail -1 > $dst/bench_line.json
+grep -h '"metric"' logs/${tag}_bench.log | tail -1 > $dst/bench_line.json   # (the --full line tools/final_round.sh wrote)
 grep -h '"metric"' $src/$tag/bench_2ranks_one_device.log | tail -1 > $dst/bench_line_2ranks_one_device.json
 tail -3 $src/$tag/tests.log > $dst/gpu_tests_tail.txt
 ls -la $dst
