@@ -106,6 +106,15 @@ class AccelInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TreeScalars(C.Structure):
+    _fields_ = [("root_fast", C.c_int32), ("root_exact", C.c_int32), ("root3_fast", C.c_int32), ("root3_exact", C.c_int32), ("root4", C.c_int32),
+                ("root4i", C.c_int32), ("n_mixed4i", C.c_uint32), ("empty4_off", C.c_uint32), ("empty4i_off", C.c_uint32), ("coord_max", C.c_float),
+                ("stack_cap", C.c_uint32), ("node4i_f4", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class Task(C.Structure):
     _fields_ = [("n_objs", C.c_uint32), ("obj_path", (C.c_char * 512) * 8), ("mtl_dir", (C.c_char * 512) * 8),
                 ("lookat", C.c_float * 3), ("up", C.c_float * 3), ("eye_pos", C.c_float * 3), ("fov_y", C.c_float),
@@ -125,7 +134,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
            "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
-           "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_host_scene_create", "crt_host_scene_destroy",
+           "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png"]
 
@@ -174,6 +183,7 @@ def lib():
     L.crt_device_math.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crt_device_philox.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crt_device_rcp_check.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.crt_scene_export.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.crt_host_scene_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.crt_host_scene_destroy.argtypes = [C.c_void_p]
     L.crt_host_scene_add_obj.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]

@@ -188,6 +188,30 @@ class Render:
         capi.check(capi.lib().crt_scene_accel_info(self._h, C.byref(a)), "crt_scene_accel_info")
         return a.as_dict()
 
+    # crt_scene_export's arrays (include/crt.h) and their element types: float4 rows as (n, 4) float32, int32 tables flat
+    EXPORT_ARRAYS = {"nodes": np.float32, "nodes3": np.float32, "nodes4": np.float32, "nodes4i": np.float32, "leaf_geo": np.float32,
+                     "leaf_geo_i": np.float32, "rec_map": np.int32, "tri_geo": np.float32, "leaf_count": np.int32, "tri_nm": np.float32}
+
+    def export_trees(self):
+        """Test hook: the traversal trees of this handle as the kernels read them, copied from device memory (crt_scene_export).
+        Returns a dict of numpy arrays (float4 rows as (n, 4) float32, an absent array with 0 rows) and the crt_tree_scalars."""
+        h = self._handle("export_trees")
+        L = capi.lib()
+        out = {}
+        for name, dt in self.EXPORT_ARRAYS.items():
+            n = C.c_size_t()
+            capi.check(L.crt_scene_export(h, name.encode(), None, 0, C.byref(n)), "crt_scene_export")
+            a = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
+            if n.value:
+                capi.check(L.crt_scene_export(h, name.encode(), capi.ptr(a), a.nbytes, C.byref(n)), "crt_scene_export")
+            out[name] = a.reshape(-1, 4) if dt is np.float32 else a
+        s = capi.TreeScalars()
+        n = C.c_size_t()
+        capi.check(L.crt_scene_export(h, b"scalars", C.byref(s), C.sizeof(s), C.byref(n)), "crt_scene_export")
+        assert n.value == C.sizeof(s)
+        out.update(s.as_dict())
+        return out
+
     def set_spp(self, spp):
         self.spp = int(spp)
 

@@ -44,7 +44,16 @@ namespace crtaccel {
 struct Box {
     float lo[3], hi[3];
     void reset() { for (int a = 0; a < 3; a++) { lo[a] = FLT_MAX; hi[a] = -FLT_MAX; } }
-    void grow(const Box& b) { for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], b.lo[a]); hi[a] = std::max(hi[a], b.hi[a]); } }
+    // union in the order of the device builder's integer keys (crt_accel_build.hip: a_ord), in which -0.0 < +0.0: the two builders'
+    // boxes agree in the sign of a zero plane too, whatever order the leaves come in (std::min / std::max keep the first of two equal zeros)
+    static bool ord_lt(float x, float y) { return x < y || (x == y && std::signbit(x) && !std::signbit(y)); }
+    void grow(const Box& b)
+    {
+        for (int a = 0; a < 3; a++) {
+            if (ord_lt(b.lo[a], lo[a])) lo[a] = b.lo[a];
+            if (ord_lt(hi[a], b.hi[a])) hi[a] = b.hi[a];
+        }
+    }
     double half_area() const
     {
         double dx = (double)hi[0] - lo[0], dy = (double)hi[1] - lo[1], dz = (double)hi[2] - lo[2];
@@ -52,6 +61,12 @@ struct Box {
         return dx * dy + dy * dz + dz * dx;
     }
 };
+
+// The bin of a leaf: t = (centroid - lowest centroid) * NB / extent, truncated and clamped to [0, NB - 1].  A centroid extent below about
+// NB / FLT_MAX (denormal centroids) makes the scale +inf and t +inf -- or NaN for the lowest centroid, 0 * inf -- and a plain (int) of
+// those is undefined (x86 gives INT_MIN: the whole range in bin 0).  Saturating, as the device's conversion does (crt_accel_build.hip):
+// NaN -> 0, +inf -> NB - 1, so that both builders bin such a range alike.
+inline int sah_bin(float t, int nb) { return t >= (float)(nb - 1) ? nb - 1 : (t > 0.0f ? (int)t : 0); }
 
 struct Prim {          // one reference leaf
     Box box;           // its box exactly as the reference stores it (DeviceBVHNode AA/BB)
@@ -111,7 +126,7 @@ inline int build_sah(std::vector<Prim>& prims, std::vector<Node>& nodes, int32_t
             const float scale = (float)NB / ext;
             for (int i = b; i < e; i++) {
                 float c = 0.5f * (prims[i].box.lo[a] + prims[i].box.hi[a]);
-                int k = std::min(NB - 1, std::max(0, (int)((c - clo[a]) * scale)));
+                int k = sah_bin((c - clo[a]) * scale, NB);
                 bb[k].grow(prims[i].box);
                 bc[k]++;
             }
@@ -141,7 +156,7 @@ inline int build_sah(std::vector<Prim>& prims, std::vector<Node>& nodes, int32_t
             const float scale = (float)NB / (chi[a] - clo[a]);
             auto it = std::partition(prims.begin() + b, prims.begin() + e, [&](const Prim& p) {
                 float c = 0.5f * (p.box.lo[a] + p.box.hi[a]);
-                int k = std::min(NB - 1, std::max(0, (int)((c - clo[a]) * scale)));
+                int k = sah_bin((c - clo[a]) * scale, NB);
                 return k <= best_split;
             });
             mid = (int)(it - prims.begin());
@@ -589,6 +604,32 @@ inline int optimize_sah(std::vector<Node>& nodes, int passes, int n_threads = 0)
 // The same tree built on the current HIP device (crt_accel_build.hip): node for node the tree of build_sah, except where a range is
 // split "by index" (coinciding centroids).  Returns the depth, or -1 if the device build could not run (use build_sah then).
 int build_sah_device(const std::vector<Prim>& prims, std::vector<Node>& nodes, int32_t& root_ref, float* device_ms, uint32_t* index_splits = nullptr);
+
+// The nearest float <= f (up = false) or >= f (up = true) whose low 12 mantissa bits are `chunk` (< 4096): how crt_render.hip's
+// nodes4i hides child indices in the planes of an inner child, moving them outwards only.  A magnitude below the smallest one with these
+// bits crosses zero to the smallest magnitude of the other sign (a denormal).  ok = false (f returned) when f is not finite or no finite
+// value has those bits on that side; ok is left alone otherwise.  (tests/test_with_bits.py checks it on the CPU.)
+inline float with_bits(float f, uint32_t chunk, bool up, bool& ok)
+{
+    auto raw = [](float x) { uint32_t u; std::memcpy(&u, &x, 4); return u; };
+    auto unraw = [](uint32_t u) { float x; std::memcpy(&x, &u, 4); return x; };
+    if (!(std::fabs(f) <= FLT_MAX)) { ok = false; return f; }
+    const uint32_t r = raw(f);
+    const bool neg = (r >> 31) != 0;
+    uint32_t m = r & 0x7fffffffu; // magnitude: grows with |f|
+    const bool grow = neg ? !up : up; // does the magnitude have to grow?
+    uint32_t c = (m & ~0xfffu) | chunk;
+    if (grow) { if (c < m) c += 0x1000u; }
+    else if (c > m) {
+        if (c >= 0x1000u) c -= 0x1000u;
+        else { // |f| below the smallest magnitude with these bits: cross zero -- the smallest magnitude of the other sign
+            const uint32_t other = chunk | (neg ? 0u : 0x80000000u);
+            return unraw(other);
+        }
+    }
+    if (c >= 0x7f800000u) { ok = false; return f; }
+    return unraw(c | (neg ? 0x80000000u : 0u));
+}
 
 } // namespace crtaccel
 #endif

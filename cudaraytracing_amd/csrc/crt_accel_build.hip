@@ -45,6 +45,8 @@ __device__ inline uint32_t a_ord(float f)
 __device__ inline float a_unord(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 #define SAH_NB 32
+// crt_accel.h: sah_bin -- the same saturating bin, spelled out instead of left to the conversion of an out-of-range float
+__device__ inline int d_bin(float t) { return t >= (float)(SAH_NB - 1) ? SAH_NB - 1 : (t > 0.0f ? (int)t : 0); }
 
 struct DSeg {
     int32_t b, e, node, depth;
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(256) void k_sah_level(const DSeg* segs, const uint3
                 const float ext = chi[a] - clo[a];
                 if (!(ext > 0.0f)) continue;
                 const float scale = (float)SAH_NB / ext;
-                const int k = min(SAH_NB - 1, max(0, (int)((c[a] - clo[a]) * scale)));
+                const int k = d_bin((c[a] - clo[a]) * scale);
                 atomicAdd(&s_cnt[a][k], 1u);
                 for (int q = 0; q < 3; q++) { atomicMin(&s_blo[a][k][q], a_ord(l3[q])); atomicMax(&s_bhi[a][k][q], a_ord(h3[q])); }
             }
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(256) void k_sah_level(const DSeg* segs, const uint3
                     if (axis >= 0) {
                         const float cl = axis == 0 ? lo.x : (axis == 1 ? lo.y : lo.z), ch = axis == 0 ? hi.x : (axis == 1 ? hi.y : hi.z);
                         const float c = 0.5f * (cl + ch);
-                        const int k = min(SAH_NB - 1, max(0, (int)((c - clo[axis]) * scale)));
+                        const int k = d_bin((c - clo[axis]) * scale);
                         left = k <= split;
                     } else left = i < mid;
                 }

@@ -1153,28 +1153,9 @@ int crt_scene_create(const crt_scene_desc* d, int device, crt_scene** out)
                     }
                 }
             }
-            auto raw = [](float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; };
-            auto unraw = [](uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; };
             bool ok = true;
-            // the nearest value <= f (down) / >= f (up) whose low 12 bits are `chunk`
-            auto with_bits = [&](float f, uint32_t chunk, bool up) -> float {
-                if (!(std::fabs(f) <= FLT_MAX)) { ok = false; return f; }
-                const uint32_t r = raw(f);
-                const bool neg = (r >> 31) != 0;
-                uint32_t m = r & 0x7fffffffu; // magnitude: grows with |f|
-                const bool grow = neg ? !up : up; // does the magnitude have to grow?
-                uint32_t c = (m & ~0xfffu) | chunk;
-                if (grow) { if (c < m) c += 0x1000u; }
-                else if (c > m) {
-                    if (c >= 0x1000u) c -= 0x1000u;
-                    else { // |f| below the smallest magnitude with these bits: cross zero -- the smallest magnitude of the other sign
-                        const uint32_t other = chunk | (neg ? 0u : 0x80000000u);
-                        return unraw(other);
-                    }
-                }
-                if (c >= 0x7f800000u) { ok = false; return f; }
-                return unraw(c | (neg ? 0x80000000u : 0u));
-            };
+            // the nearest value <= f (down) / >= f (up) whose low 12 bits are `chunk` (crt_accel.h)
+            auto with_bits = [&](float f, uint32_t chunk, bool up) -> float { return crtaccel::with_bits(f, chunk, up, ok); };
             std::vector<float4> n4i((n4 + 1) * (size_t)NODE4I_F4, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
             const size_t n_rec_i = (n4 + 1) * 4;
             std::vector<float4> lgi(n_rec_i * 5, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
@@ -1291,6 +1272,56 @@ int crt_scene_accel_info(crt_scene* sc, crt_accel_info* out)
     if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, "crt_scene_accel_info: null argument");
     *out = sc->accel;
     return CRT_OK;
+}
+
+int crt_scene_export(crt_scene* sc, const char* name, void* dst, size_t capacity, size_t* bytes)
+{
+    if (!bytes) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: null bytes");
+    static const char* names[] = {"nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo", "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", "scalars"};
+    int id = -1;
+    for (int i = 0; name && i < 11; i++)
+        if (std::strcmp(name, names[i]) == 0) id = i;
+    if (id < 0) return fail(CRT_ERR_INVALID_ARG, std::string("crt_scene_export: unknown array ") + (name ? name : "(null)"));
+    if (!sc) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: null scene");
+    if (id == 10) {
+        crt_tree_scalars s;
+        std::memset(&s, 0, sizeof(s));
+        s.root_fast = sc->dev.root_fast; s.root_exact = sc->dev.root_exact; s.root3_fast = sc->dev.root3_fast; s.root3_exact = sc->dev.root3_exact;
+        s.root4 = sc->dev.root4; s.root4i = sc->impl_ok ? sc->dev.root4i : 0;
+        s.n_mixed4i = sc->impl_ok ? sc->dev.n_mixed4i : 0; s.empty4_off = sc->dev.empty4_off; s.empty4i_off = sc->impl_ok ? sc->dev.empty4i_off : 0;
+        s.coord_max = sc->dev.coord_max; s.stack_cap = (uint32_t)sc->stack_cap; s.node4i_f4 = NODE4I_F4;
+        *bytes = sizeof(s);
+        if (!dst) return CRT_OK;
+        if (capacity < sizeof(s)) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: capacity below the size");
+        std::memcpy(dst, &s, sizeof(s));
+        return CRT_OK;
+    }
+    // the device arrays themselves (DevBuf::n: the uploaded count -- an empty upload allocates one unused element, reported as 0)
+    const bool leaf_root = sc->dev.root_fast < 0, impl = sc->impl_ok;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (id) {
+    case 0: src = sc->nodes.p; n = leaf_root ? 0 : sc->nodes.n * sizeof(float4); break;
+    case 1: src = sc->nodes3.p; n = leaf_root ? 0 : sc->nodes3.n * sizeof(float4); break;
+    case 2: src = sc->nodes4.p; n = sc->nodes4.n * sizeof(float4); break;
+    case 3: src = sc->nodes4i.p; n = impl ? sc->nodes4i.n * sizeof(float4) : 0; break;
+    case 4: src = sc->leaf_geo.p; n = sc->leaf_geo.n * sizeof(float4); break;
+    case 5: src = sc->leaf_geo_i.p; n = impl ? sc->leaf_geo_i.n * sizeof(float4) : 0; break;
+    case 6: src = sc->rec_map.p; n = impl ? sc->rec_map.n * sizeof(int32_t) : 0; break;
+    case 7: src = sc->tri_geo.p; n = sc->tri_geo.n * sizeof(float4); break;
+    case 8: src = sc->leaf_count.p; n = sc->leaf_count.n * sizeof(int32_t); break;
+    default: src = sc->tri_nm.p; n = sc->tri_nm.n * sizeof(float4); break;
+    }
+    *bytes = n;
+    if (!dst || n == 0) return CRT_OK;
+    if (capacity < n) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: capacity below the size");
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        HIP_CHECK(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
 }
 
 int crt_scene_destroy(crt_scene* sc)

@@ -314,6 +314,20 @@ int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32
  * number of inputs INSIDE the guarded range (2^-126 <= |x| < 2^126) whose bits differ (must be 0), and in *outside the
  * number of inputs outside the range that differ (those take the division itself).  A few milliseconds. */
 int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside);
+/* Test-only export of the traversal trees a scene handle holds, copied from DEVICE memory (what the kernels read; layouts:
+ * csrc/crt_device.h, csrc/crt_render.hip).  `name` is one of the arrays "nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo",
+ * "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", or "scalars" (one crt_tree_scalars).  *bytes receives the array's
+ * size (0 for an array the scene does not have: "nodes" / "nodes3" when the tree is one leaf, the nodes4i set when layout_caps
+ * bit 3 is clear); dst == NULL asks for the size only.  An unknown name, a null `bytes`, a null scene or a capacity below the size
+ * is CRT_ERR_INVALID_ARG (the name and `bytes` are checked first, so a null scene reports those). */
+typedef struct {
+    int32_t root_fast, root_exact, root3_fast, root3_exact, root4, root4i;
+    uint32_t n_mixed4i, empty4_off, empty4i_off; /* empty*_off: byte offsets of the node of four empty slots */
+    float coord_max;
+    uint32_t stack_cap;                          /* traversal stack entries per ray the scene was sized for */
+    uint32_t node4i_f4;                          /* float4 per node of nodes4i (NODE4I_F4) */
+} crt_tree_scalars;
+int crt_scene_export(crt_scene* scene, const char* name, void* dst, size_t capacity, size_t* bytes);
 
 /* ------------------------------------------------------------------------
  * Host layer: scene ingestion and BVH build on the CPU (north star: "C++ host

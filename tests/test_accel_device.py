@@ -11,8 +11,10 @@ import pytest
 
 import cudaraytracing_amd as crt
 import oracle_lib as O
+import tree_check as TC
 import util
 from test_gpu_parity import _write_box_scene, _write_soup_scene
+from test_tree_invariants import write_signed_zero_scene
 
 pytestmark = pytest.mark.gpu
 REPORT = os.path.join(util.ROOT, "gpurun_out", "sah_build_report.jsonl")
@@ -27,6 +29,24 @@ def _pair(scene, spp, p_rr, lsn, monkeypatch):
     monkeypatch.delenv("CRT_SAH_HOST", raising=False)
     dev.free()
     return dev2, host
+
+
+TREE_ARRAYS = ("nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo_i", "rec_map")
+
+
+def _checked_export(r, scene):
+    """The trees of a handle (Render.export_trees), after tests/tree_check.py found no violation in them."""
+    ex = r.export_trees()
+    v = TC.check_trees(ex, r.accel_info(), scene.nodes(), scene.root, scene.triangles())
+    assert v == [], v
+    return ex
+
+
+def _same_trees(a, b):
+    for k in TREE_ARRAYS:
+        assert a[k].tobytes() == b[k].tobytes(), k
+    for k in ("root4", "root4i", "n_mixed4i", "coord_max", "stack_cap"):
+        assert a[k] == b[k], k
 
 
 def _report(name, a, b):
@@ -52,7 +72,10 @@ def test_device_tree_is_the_host_tree_on_the_benchmark_scenes(name, monkeypatch)
         rb = host.run_view(eye, iv, fov, stats=True, width=160, height=120)
         assert np.array_equal(ra, rb) and np.array_equal(util.bits(dev.mean_buffer), util.bits(host.mean_buffer))
         assert a["index_splits"] == b["index_splits"]
-        if a["index_splits"] == 0:  # no range of coinciding leaf centroids: the device tree IS the host tree
+        scene = util.host_scene(name)
+        ea, eb = _checked_export(dev, scene), _checked_export(host, scene)
+        if a["index_splits"] == 0:  # no range of coinciding leaf centroids: the device tree IS the host tree, byte for byte
+            _same_trees(ea, eb)
             for k in ("rays", "inner_pops", "leaf_pops", "tri_tests", "hits", "stack_max"):
                 assert dev.stats[k] == host.stats[k], k
         else:                       # (veach-mis holds coincident triangles: the equal leaves may sit on different sides)
@@ -101,6 +124,29 @@ def test_soup_with_duplicates_matches_the_oracle(tmp_path, monkeypatch):
         for r in (dev, host):
             rgb = r.run_view(eye, iv, fov)
             assert np.array_equal(util.bits(r.mean_buffer), util.bits(omean)) and np.array_equal(rgb, orgb) and r.stats["rays"] == st["rays"]
+    finally:
+        dev.free()
+        host.free()
+
+
+def test_device_tree_is_the_host_tree_with_planes_at_signed_zeros(tmp_path, monkeypatch):
+    """Box planes at +0.0, -0.0 and denormals.  The device builder's integer keys order -0.0 below +0.0, so the host builder's unions must
+    too (crt_accel.h: Box::grow) -- otherwise a box over both zeros differs in the sign bit alone.  A denormal centroid extent makes the
+    bin scale +inf; both builders bin with the same saturating conversion (crt_accel.h: sah_bin) -- the host's plain (int) of +inf put the
+    whole range in bin 0 where the device split it."""
+    obj, mtl = write_signed_zero_scene(str(tmp_path))
+    scene = crt.Scene(32, 24)
+    scene.add_obj(obj, mtl)
+    scene.set_BVH(2)
+    dev, host = _pair(scene, 1, 0.6, 1, monkeypatch)
+    try:
+        a, b = dev.accel_info(), host.accel_info()
+        assert a["sah_on_device"] == 1 and b["sah_on_device"] == 0 and a["index_splits"] == b["index_splits"] == 0
+        ea, eb = _checked_export(dev, scene), _checked_export(host, scene)
+        lo = ea["nodes"][:, :3]
+        assert ((lo == 0) & np.signbit(lo)).any() and ((lo == 0) & ~np.signbit(lo)).any()
+        assert ((np.abs(lo) > 0) & (np.abs(lo) < np.finfo(np.float32).tiny)).any()
+        _same_trees(ea, eb)
     finally:
         dev.free()
         host.free()
@@ -156,7 +202,7 @@ def test_tree_set_up_hooks_change_the_tree_and_not_the_frame(name, monkeypatch):
     """Round 6: the children of a four-wide node are ordered by occupancy, and the re-insertion pass runs in blocks on several threads
     (tests/test_sah_opt.py checks the pass on the CPU).  Every hook of the set-up gives another tree over the SAME leaves: the frame, the
     ray count and the closest hits of random rays stay the oracle's in both exact-by-construction modes and in FAST; the batched pass
-    gives the same tree on one thread as on many (here: the same number of four-wide nodes and the same depths)."""
+    gives the same tree on one thread as on many, byte for byte; every hook's tree passes tests/tree_check.py."""
     t = util.task(name)
     eye, iv, fov = util.camera(name)
     osc = util.oracle_scene(name)
@@ -176,11 +222,9 @@ def test_tree_set_up_hooks_change_the_tree_and_not_the_frame(name, monkeypatch):
                 rgb = r.run_view(eye, iv, fov, stats=True, width=96, height=72)
                 assert np.array_equal(rgb, orgb) and np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), (hook, mode)
                 assert r.stats["rays"] == st["rays"], (hook, mode)
-                if mode == crt.TRAVERSAL_EXACT:
-                    a = r.accel_info()
-                    seen[hook] = (a["n_nodes4"], a["depth2"], a["depth4"])  # (visit counts of any-hit rays depend on the waves' timing: not compared)
+            seen[hook] = _checked_export(r, util.host_scene(name))  # (visit counts of any-hit rays depend on the waves' timing: not compared)
             tri, tt = r.intersect(o, d, traversal=crt.TRAVERSAL_EXACT)
             assert np.array_equal(tri, otri) and np.array_equal(util.bits(tt), util.bits(ot)), hook
         finally:
             r.free()
-    assert seen["default"] == seen["re-insertion pass: one thread"], seen
+    _same_trees(seen["default"], seen["re-insertion pass: one thread"])  # the batched pass: the same tree on one thread as on many

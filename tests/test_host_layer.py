@@ -162,6 +162,17 @@ def test_device_entry_points_validate_arguments_without_a_gpu():
     assert lib.crt_scene_create(C.byref(d), 0, C.byref(h)) == -1
     assert lib.crt_render(None, None, None, None, None, None) == -1
     assert b"null" in lib.crt_last_error()
+    # the test-only tree export: every argument is checked before the scene is touched
+    nb = C.c_size_t(7)
+    assert lib.crt_scene_export(None, b"nodes4", None, 0, C.byref(nb)) == -1
+    assert b"null scene" in lib.crt_last_error() and nb.value == 7
+    assert lib.crt_scene_export(None, b"nodes4", None, 0, None) == -1
+    assert b"null bytes" in lib.crt_last_error()
+    for bad in (b"nodes5", b"", b"NODES4", b"scalar"):
+        assert lib.crt_scene_export(None, bad, None, 0, C.byref(nb)) == -1
+        assert b"unknown array" in lib.crt_last_error(), bad
+    assert lib.crt_scene_export(None, None, None, 0, C.byref(nb)) == -1
+    assert b"unknown array" in lib.crt_last_error()
 
 
 def test_cornell_generator_reproduces_committed_obj(tmp_path):
