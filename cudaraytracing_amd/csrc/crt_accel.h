@@ -355,9 +355,6 @@ inline int optimize_sah_serial(std::vector<Node>& nodes, int passes)
 // search sees every earlier move), but one of the same quality: summed inner area 1.7009e7 -> see tests/test_sah_opt.py, and the frame times
 // of docs/experiments.md 6.10.  (Round 5's form reproduced the serial pass exactly by recording what every search read and repeating the
 // stale ones: the bookkeeping cost as much as the searches, 21 ms on eight threads against 32 serial.)
-#ifndef CRT_SAH_HEAD
-#define CRT_SAH_HEAD 64
-#endif
 inline int optimize_sah(std::vector<Node>& nodes, int passes, int n_threads = 0)
 {
     const int A = (int)nodes.size();
@@ -512,7 +509,7 @@ inline int optimize_sah(std::vector<Node>& nodes, int passes, int n_threads = 0)
     };
     // blocks of 64, 128, ... 2048 nodes (constants: the tree that comes out must not depend on the machine): the large nodes at the head of the
     // list are where the moves are and where one move changes what the next should do
-    const int HEAD = CRT_SAH_HEAD, BLOCK0 = 8, BLOCK = 2048;
+    const int HEAD = 64, BLOCK0 = 8, BLOCK = 2048;
     std::vector<int> found((size_t)BLOCK);
     for (int pass = 0; pass < passes; pass++) {
         // largest first; one 64-bit key per node (the area as a float, inverted, above the id) so that the sort compares integers

@@ -21,9 +21,7 @@ struct MParams {
     int32_t logic_min, leaf_min;
 };
 
-#ifndef POOL_LV
 #define POOL_LV 4 /* 32-bit traversal stack levels kept in LDS per ray (twice as many of 16 bits, Pool3LdsT); deeper levels spill to global memory */
-#endif
 
 // --------------------------------------- megakernel, queued sub-phases ----
 // Its predecessor k_mega2 (wave-private LDS pool, rays regrouped by phase with ballot / prefix rank / ds_permute, one logic
@@ -76,25 +74,10 @@ struct MParams {
 #define RF_HASHIT 0x20000000u  /* closest-hit ray: a hit is recorded (T = its distance) */
 #define RF_SKIP 0x40000000u    /* (NewRay only) next-event sample with a zero contribution: answered without traversal */
 #define RF_QUERY 0x80000000u   /* crt_intersect: a bare closest-hit query; its result goes straight back to LC */
-#ifndef CRT_RING_MODE
-#define CRT_RING_MODE 2 /* 2: the rings are STACKS -- a batch is the newest ids, one scalar per ring, no wrap (round 5: C2 -1.3 %, veach-mis -1.1 % on top of
-                           the mask form of the inner step); 0: FIFO rings that wrap by compare (rounds 2 - 4); 1: FIFO rings of 256 entries, wrap by mask,
-                           146 rays per wave (measured: +0.5 % / +0.1 % against 0 -- the smaller pool costs what the mask saves) (crt_mega3.hip: ring_wrap) */
-#endif
-#ifndef POOL3_P
-#if CRT_RING_MODE == 1
-#define POOL3_P 154
-#else
 #define POOL3_P 164         /* 164 x 56 B + rings = 10 004 B: 16 waves per CU (measured with the 16-bit stack layout: 148 rays x 64 B records
                                with 1/d and six levels 102.5 ms, 176 x 52 B with six levels 100.2, 164 x 56 B with eight levels 98.8, 156 x 60 B with
                                ten 100.0) */
-#endif
-#endif
-#if CRT_RING_MODE == 1
-#define POOL3_QCAP 256
-#else
 #define POOL3_QCAP ((POOL3_P + 3) & ~3) /* ring capacity (any number >= POOL3_P: indices wrap by compare, not by mask); ids fit a byte */
-#endif
 static_assert(POOL3_P <= 256, "ray ids of a pool must fit a byte (ring entries are uint8_t)");
 static_assert(POOL3_QCAP >= POOL3_P, "a ring must hold every ray of the pool");
 #define CRT_MEGA3_MAX_STACK 255 /* the traversal stack depth is kept in 8 bits of the record's word D */
@@ -102,9 +85,7 @@ static_assert(POOL3_QCAP >= POOL3_P, "a ring must hold every ray of the pool");
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-#ifndef CRT_WAVES
 #define CRT_WAVES 4   /* waves per SIMD the kernel is compiled for; the LDS footprint of a pool must allow it (160 KiB per CU) */
-#endif
 // R16: the traversal stack holds 16-bit node refs, twice as many levels in the same bytes (scenes whose 4-wide tree and leaf records
 // number at most 32 768 each: crt_scene::ref16_ok).  The levels beyond LDS cost a wave-uniform branch with 64-bit address arithmetic,
 // global stores and -- in the pop -- an exposed global load whenever ANY ray of a batch is that deep, which with three levels is
@@ -152,17 +133,9 @@ template <bool R16_, bool RING_>
 struct Pool4LdsT {
     static constexpr bool R16 = R16_;
     static constexpr bool DEC = true;
-#ifdef POOL4_P
-    static constexpr int P = POOL4_P;
-#else
-    static constexpr int P = CRT_RING_MODE == 1 ? (RING_ ? 140 : 146) : (RING_ ? 148 : 152);
-#endif
-    static constexpr int QCAP = CRT_RING_MODE == 1 ? 256 : (P + 3) & ~3;
-#ifdef POOL4_LV
-    static constexpr int LV = R16_ ? POOL4_LV : POOL4_LV / 2;
-#else
+    static constexpr int P = RING_ ? 148 : 152;
+    static constexpr int QCAP = (P + 3) & ~3;
     static constexpr int LV = R16_ ? 6 : 3;
-#endif
     typedef typename std::conditional<R16_, short, int>::type stk_t;
     float4 A[P];                 // origin.xyz, the distance an accepted hit must stay below by more than EPSILON: the light's for an any-hit ray, +inf otherwise
     float4 B[P];                 // direction.xyz, bits(current node ref)

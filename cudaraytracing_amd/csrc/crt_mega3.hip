@@ -10,9 +10,6 @@
 
 namespace crtk {
 
-#ifndef CRT_X_SLIGHT
-#define CRT_X_SLIGHT 1 /* 0: the light table through vector loads only (A/B) */
-#endif
 struct NewRay {
     F3 o, d;
     float tl;
@@ -32,21 +29,7 @@ __device__ __forceinline__ int smax(const int a, const int b)
     return r;
 }
 
-// Ring index in [0, 2 * QCAP) -> [0, QCAP).
-// (CRT_RING_MODE 1: rings of 256 entries, the wrap is a mask; 2: the rings are stacks -- a batch is the NEWEST ids, no head, no tail, no wrap)
-template <int QCAP>
-__device__ __forceinline__ uint32_t ring_wrap(const uint32_t x)
-{
-#if CRT_RING_MODE == 1
-    static_assert(QCAP == 256, "CRT_RING_MODE 1: rings of 256 entries");
-    return x & 255u;
-#elif CRT_RING_MODE == 2
-    return x;
-#else
-    return min(x, x - (uint32_t)QCAP);
-#endif
-}
-#if CRT_RING_MODE == 2
+// The rings are stacks: a batch is the NEWEST ids, no head, no tail, no wrap.
 // (the count doubles as the place of the next id, i.e. as the addend of v_mbcnt, a vector operand: handed over as a scalar COPY, or the
 // compiler moves the count itself into a vector register, where the scheduler's scalar maxima cannot reach it)
 __device__ __forceinline__ uint32_t scalar_copy(int x) { asm volatile("" : "+s"(x)); return (uint32_t)x; }
@@ -54,17 +37,6 @@ __device__ __forceinline__ uint32_t scalar_copy(int x) { asm volatile("" : "+s"(
 #define RQ_PUSH_ADV(p_, n_) { qn[p_] += (n_); }
 #define RQ_POP_BASE(p_, take_) ((uint32_t)(qn[p_] - (take_)))
 #define RQ_POP_ADV(p_, take_) { qn[p_] -= (take_); }
-#else
-#define RQ_PUSH_BASE(p_) ((uint32_t)qt[p_])
-#if CRT_RING_MODE == 1
-#define RQ_PUSH_ADV(p_, n_) { qn[p_] += (n_); qt[p_] = (qt[p_] + (n_)) & 255; }
-#define RQ_POP_ADV(p_, take_) { qh[p_] = (qh[p_] + (take_)) & 255; qn[p_] -= (take_); }
-#else
-#define RQ_PUSH_ADV(p_, n_) { qn[p_] += (n_); qt[p_] += (n_); if (qt[p_] >= QCAP) qt[p_] -= QCAP; }
-#define RQ_POP_ADV(p_, take_) { qh[p_] += (take_); if (qh[p_] >= QCAP) qh[p_] -= QCAP; qn[p_] -= (take_); }
-#endif
-#define RQ_POP_BASE(p_, take_) ((uint32_t)qh[p_])
-#endif
 
 // Where a ray goes once its traversal is over: a next-event sample to LA (LB after the last one of its vertex), a probe
 // or a closest-hit ray that found a surface to LA, a closest-hit ray that found nothing to LC.
@@ -247,7 +219,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
     // there, is needed as "is +inf" only (shadow_blocked) and is a bit of the state word.  REFERENCE compares the limit with the nearest
     // hit's distance and keeps the round-5 planes.  (docs/experiments.md 6.12: the store of the vertex position that went with it was the
     // gain, C2 75.8 -> 73.6 ms; this one is level in time and takes 6.7 % off the bytes written.)
-    constexpr bool TRI_CC = CRT_X_NOVN && MODE != 1;
+    constexpr bool TRI_CC = MODE != 1;
     const float4 la = gld(&pl.la[g]);
     const uint4 idv = load_path_id<RING, !TRI_CC>(P, g);
     const float4 cc = gld(&pl.cc[g]); // pending next-event contribution; .w = bits(triangle of the vertex the samples belong to) (REFERENCE: distance to the light sample)
@@ -256,11 +228,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
     // (a path's first visit -- its camera ray found vertex 0 -- has no vertex in the planes yet: cc.w is what the slot's last path left, or
     // never written; the speculative row is then row 0 and is not used)
     const uint32_t vtri_old = TRI_CC ? ((st & 0xfffu) == ((uint32_t)ST_HIT << 8) ? 0u : __float_as_uint(cc.w)) : idv.w;
-#if CRT_X_NOVN
     const float4 vn = gld(&sc.tri_nm[vtri_old]); // (normal, material) of the vertex in the planes: from its triangle
-#else
-    const float4 vn = gld(&pl.vn[g]);
-#endif
     const float res_t = qa.w;
     const int res_tri = __float_as_int(qb.w);
     const float4 gq_hit = gld(&sc.tri_nm[res_tri >= 0 ? res_tri : 0]);
@@ -282,7 +250,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
     // (The eight rows of a light of <= 2 triangles -- the quad of a Cornell box -- fetched the same way and picked per lane: C2 level, and
     // veach-mis, which does not take that path, +1.2 % from the second copy of the set-up code; not kept.)
     if (n_nee > 0) {
-        if (CRT_X_SLIGHT && sc.n_lights == 1) {
+        if (sc.n_lights == 1) {
             const crt_u4v_ l0_ = *(const __attribute__((address_space(4))) crt_u4v_*)tb.lights;
             lg_next = make_uint4(l0_.x, l0_.y, l0_.z, l0_.w);
         } else lg_next = gld(&tb.lights[fast_div(q_next < n_nee ? q_next : 0u, P.lsn_div.m, P.lsn_div.sh)]);
@@ -372,11 +340,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
         if (TNM_SPECULAR(tnm_cur)) gst_rec(&pl.rec_b[(size_t)s.depth * pl.n + g], make_float4(s.rd.x, s.rd.y, s.rd.z, 0.0f));
         // (round 6: the vertex position is not written to the vx plane any more -- LB takes it from the slot's ray record, which is a
         // next-event ray of this vertex or, for a vertex without one, is given the position below.  The plane lives on for the probe rays.)
-#if CRT_X_NOVN
         if (!TRI_CC) store_path_tri(P, g, s.vtri);
-#else
-        gst(&pl.vn[g], make_float4(s.nrm.x, s.nrm.y, s.nrm.z, __uint_as_float(s.mat)));
-#endif
         if (TNM_EMITTER(tnm_cur)) { // emitter: the path ends here (Render.cuh:210); TRI_CC: LC finds the emitter's triangle in la.x
             gst(&pl.la[g], make_float4(TRI_CC ? __uint_as_float(s.vtri) : 0.0f, 0.0f, 0.0f, __uint_as_float(s.depth | ((uint32_t)ST_FIN << 8) | (1u << 16))));
             return PH3_LC;
@@ -399,9 +363,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
     // The next sample of such a lane is set up right here while enough lanes of the batch need it (setup_shadow is the most
     // expensive section of the phase and the others wait); the last few stragglers are instead handed to start_ray as
     // "answered" (RF_SKIP) and go back to the ring of their consumer, which adds the zero contribution.
-#ifndef LA_LOOP_MIN
-#define LA_LOOP_MIN 16
-#endif
+    constexpr int LA_LOOP_MIN = 16;
     const float4 m0 = m0_cur;
     bool skip;
     for (bool first = true;; first = false) {
@@ -432,7 +394,7 @@ template <int MODE, bool RING = false>
 __device__ __forceinline__ uint32_t logic_B(const LParams& P, const uint32_t g, const float4 qa, const float4 qb, NewRay& nr)
 {
     const Pool& pl = P.pool;
-    constexpr bool TRI_CC = CRT_X_NOVN && MODE != 1; // (see logic_A)
+    constexpr bool TRI_CC = MODE != 1; // (see logic_A)
     const float4 la = gld(&pl.la[g]);
     const uint4 idv = load_path_id<RING, !TRI_CC>(P, g);
     const float4 cc = gld(&pl.cc[g]); // (with the other planes, not after the stage is known: one round trip less, see logic_A)
@@ -456,11 +418,7 @@ __device__ __forceinline__ uint32_t logic_B(const LParams& P, const uint32_t g, 
         return PH3_LC;
     }
     // the vertex: the origin of the slot's last ray -- a next-event ray starts at its vertex (setup_shadow_lg) -- or what LA's caller put there
-#if CRT_X_NOVN
     const float4 vn = gld(&P.sc.tri_nm[TRI_CC ? __float_as_uint(cc.w) : idv.w]);
-#else
-    const float4 vn = gld(&pl.vn[g]);
-#endif
     const float4 vx = qa;
     gst_rec(&pl.rec_a[(size_t)depth * pl.n + g], make_float4(Ld.x, Ld.y, Ld.z, vn.w)); // the vertex's record: L_dir and its material (with the row's flag bits)
     const F3 ndir = unit3(sample_hemisphere(f3(vn.x, vn.y, vn.z), rng_uniform(rb.y), rng_uniform(rb.z)));
@@ -480,7 +438,7 @@ enum { LC_DEAD = 0, LC_RAY = 1, LC_WAIT = 2 };
 template <int MODE, bool RING>
 __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb, const uint32_t g, PathCounters& cnt, NewRay& nr, uint32_t& fin_key)
 {
-    constexpr bool TRI_CC = CRT_X_NOVN && MODE != 1; // (see logic_A: an emitter's triangle arrives in la.x)
+    constexpr bool TRI_CC = MODE != 1; // (see logic_A: an emitter's triangle arrives in la.x)
     const Pool& pl = P.pool;
     const float4 la = gld(&pl.la[g]);
     const uint4 idv = load_path_id<RING, !TRI_CC>(P, g); // (with la, not after the stage is known: one round trip less, see logic_A)
@@ -509,11 +467,7 @@ __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb
         if (stage == ST_HIT) deepest = (int)depth - 1; // the ray that looked for vertex `depth` missed (Render.cuh:210)
         else if ((st >> 16) & 1u) {
             emissive = true;
-#if CRT_X_NOVN
             const float4 m2 = mat_row(tb, TNM_MAT(__float_as_uint(gld(&P.sc.tri_nm[TRI_CC ? __float_as_uint(la.x) : idv.w]).w)), 2);
-#else
-            const float4 m2 = mat_row(tb, __float_as_uint(gld(&pl.vn[g]).w), 2);
-#endif
             ke = f3(m2.x, m2.y, m2.z);
         }
         const F3 L = finish_path_m3(P, tb, g, deepest, emissive, ke, stage == ST_FIN && !emissive, f3(la.x, la.y, la.z));
@@ -552,11 +506,7 @@ __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb
                 // (agent-scope load, as k_order_items' stores: with plain accesses the FIRST frame of a render created after other renders of
                 // the process came out with 10 - 400 work items of the 589 824 of a 96 x 64 x 96 frame never run -- their list entries read as
                 // what an earlier kernel had left at the address -- in half of the runs once the launches' timing had changed; docs/experiments.md 6)
-#if defined(CRT_HANDOFF_PLAIN) || defined(CRT_HANDOFF_PLAIN_LOAD) /* experiment builds only (tools/handoff_ab.sh): the accesses as they were */
-                if (item >= wlo_) item = ((CRT_GAS const unsigned int*)P.item_list)[sh_ * P.order_window + (item - wlo_)];
-#else
                 if (item >= wlo_) item = __hip_atomic_load((CRT_GAS const unsigned int*)&P.item_list[sh_ * P.order_window + (item - wlo_)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
             }
         }
         bool valid; uint32_t pi, pj, pixel_index, k;
@@ -983,13 +933,6 @@ __device__ __forceinline__ wmask visit_front(const DevScene& sc, const MParams3&
         const F3 inv = inv3_exact(dir);
         R.ixy = v2(inv.x, inv.y); R.iz.x = inv.z;
     }
-#ifdef CRT_X_EXTRA_VALU /* sensitivity experiment (round 6): N more vector instructions per visit (independent v_add_f32 on a scratch register) */
-    {
-        float xv_ = dir.x;
-        for (int k_ = 0; k_ < CRT_X_EXTRA_VALU; k_++) asm volatile("v_add_f32 %0, %0, %1" : "+v"(xv_) : "v"(dir.y));
-        asm volatile("" :: "v"(xv_));
-    }
-#endif
     float t0, t1, t2, t3;
     int r0, r1, r2, r3;            // the children's refs (an inner child: its node)
     wmask N0, N1, N2, N3;          // the child is a leaf (or an empty slot, which is never hit)
@@ -1154,9 +1097,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
     int n_exact = 0; // rays on the reference-arithmetic path (RF_EXACT) that are in the traversal phases of this pool
 
     // ring state: wave-uniform scalars
-    int qn[PH3_N], qh[PH3_N], qt[PH3_N]; // entries, head, tail (head and tail in [0, QCAP))
+    int qn[PH3_N]; // entries
 #pragma unroll
-    for (int p = 0; p < PH3_N; p++) { qn[p] = 0; qh[p] = 0; qt[p] = 0; }
+    for (int p = 0; p < PH3_N; p++) qn[p] = 0;
     uint32_t dg_b[5] = {0, 0, 0, 0, 0}, dg_l[5] = {0, 0, 0, 0, 0}; // STATS: batches and rays per phase
     uint32_t dg_sp[6] = {0, 0, 0, 0, 0, 0};                         // STATS, per lane: inner steps that leave the stack deeper than 1 .. 6 entries
     uint32_t dg_ov[2] = {0, 0};                                     // STATS, per lane (DEC): visits taken back because the leaf queue was full (first visit: voided lanes; second visit: bailed, counted by its lanes)
@@ -1175,12 +1118,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
 #define STAMP(k_)
 #define STAMP_OTHER()
 #endif
-#ifdef CRT_HANDOFF_INV /* experiment builds only: what a dispatch's agent-scope acquire does, by hand (vector L1 and the non-local lines of L2) */
-    asm volatile("buffer_inv sc1" ::: "memory");
-#endif
-#ifdef CRT_HANDOFF_INV_SYS
-    asm volatile("buffer_inv sc0 sc1" ::: "memory");
-#endif
     if (commit_ring && lane == 0) S.waitq = 0u;
     // every ray of the pool starts in LC with a path in stage NEW
     {
@@ -1192,8 +1129,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
             pl.la[base + i] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)ST_NEW << 8));
         }
         qn[PH3_LC] = n_valid;
-        qt[PH3_LC] = n_valid >= QCAP ? n_valid - QCAP : n_valid;
-        (void)qh; (void)qt;
     }
 
 // appends the processed rays (lane active = `on`, ray `id`) to the ring of their new phase
@@ -1204,7 +1139,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
         if (m) {                                                                                                           \
             /* slot = tail + number of lanes below this one that go the same way: the tail rides in as mbcnt's addend */      \
             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, RQ_PUSH_BASE(p))); \
-            if (mine) S.rq(p)[ring_wrap<QCAP>(slot)] = (uint8_t)id;                                                            \
+            if (mine) S.rq(p)[slot] = (uint8_t)id;                                                                             \
             const int add = (int)__popcll(m);                                                                              \
             RQ_PUSH_ADV(p, add)                                                                                            \
         }                                                                                                                  \
@@ -1212,12 +1147,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
 // after a traversal step: a ray goes on to an inner node or a leaf, or it is finished -- only then (one wave-uniform test
 // for the three logic rings together) is its route worked out from the flag bits of its record
 #define PUSH_TRAV() { if (on) nph = t_done ? route_done<QUERY>(t_flags) : (t_ref >= 0 ? PH3_INNER : PH3_LEAF); PUSH3() }
-// takes the (up to) 64 oldest rays of ring p
+// takes the (up to) 64 newest rays of ring p
 #define POP3(p)                                                                                                            \
     const int take = min(64, qn[p]);                                                                                       \
     if (STATS) { dg_b[p]++; dg_l[p] += (uint32_t)take; }                                                                   \
     const bool on = lane < take;                                                                                           \
-    const uint32_t id = S.rq(p)[ring_wrap<QCAP>(RQ_POP_BASE(p, take) + (uint32_t)lane)];                                       \
+    const uint32_t id = S.rq(p)[RQ_POP_BASE(p, take) + (uint32_t)lane];                                                        \
     RQ_POP_ADV(p, take)                                                                                                    \
     const uint32_t g = base + id;                                                                                          \
     uint32_t nph = PH3_NONE;
@@ -1251,11 +1186,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
             // key = batch size * 8 + phase number (the phase numbers are the tie-break order)
             const int kC = min(qn[PH3_LC], 64) * 8 + PH3_LC, kA = min(qn[PH3_LA], 64) * 8 + PH3_LA, kB = min(qn[PH3_LB], 64) * 8 + PH3_LB;
             // (DEC: the leaf queue counts entries, not rays; with 64 or more it is the fullest there can be and wins over the inner ring)
-#ifndef LEAFQ_FIRST
 #define LEAFQ_FIRST 48 /* DEC: with this many entries the leaf queue goes before everything else: the queue is emptied early and stays far from full
                           (when inner batches were still cut to a quarter of its free entries: C2 93.9 -> 92.1 ms, veach-mis spp 256 90.6 -> 89.4;
                           40 / 56 / 32: 91.9 / 92.9 / 92.0 and 89.6 / 89.5 / 90.8; with full batches 32 / 40 / 56 against 48: within 0.5 %) */
-#endif
             // (an inner step starts with fewer than LEAFQ_FIRST entries in the queue -- from that many on the leaf step goes first, here and
             // in the alternating loop -- and must find room for a reference-arithmetic batch, 64 entries appended outside the counted
             // ones, plus four entries, the least a 4-wide visit needs to keep one lane: otherwise it would take every lane back, for ever)
@@ -1391,7 +1324,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
         const unsigned long long m_ = __builtin_amdgcn_ballot_w64(mine_);                                                  \
         if (m_) {                                                                                                          \
             const uint32_t slot_ = __builtin_amdgcn_mbcnt_hi((uint32_t)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m_, RQ_PUSH_BASE(p_))); \
-            if (mine_) S.rq(p_)[ring_wrap<QCAP>(slot_)] = (uint8_t)id;                                                     \
+            if (mine_) S.rq(p_)[slot_] = (uint8_t)id;                                                                      \
             const int add_ = (int)__popcll(m_);                                                                            \
             RQ_PUSH_ADV(p_, add_)                                                                                          \
         }                                                                                                                  \
@@ -1412,7 +1345,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
             const wmask ON = bal(lane < take);
             // (a lane beyond the batch reads an entry of the ring that is not part of it -- a ray id of this pool all the same, or the
             // ring's initial bytes: the id is forced into the pool)
-            const uint32_t id_raw = S.rq(PH3_INNER)[ring_wrap<QCAP>(RQ_POP_BASE(PH3_INNER, take) + (uint32_t)lane)];
+            const uint32_t id_raw = S.rq(PH3_INNER)[RQ_POP_BASE(PH3_INNER, take) + (uint32_t)lane];
             RQ_POP_ADV(PH3_INNER, take)
             const uint32_t id = lanes(ON) ? id_raw : 0u;
             const uint32_t g = base + id;
@@ -1445,17 +1378,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
                     Visit4 V1, V2;
                     const wmask EN1 = GO & ~EX;
                     node_load<IMPL>(sc, ref, EN1, dir, V1);
-#ifdef CRT_X_EXTRA_LOADS /* sensitivity experiment (round 6): N more loads per first visit from the node's own line, issued with the others, consumed at the end of the step */
-                    float xl_[CRT_X_EXTRA_LOADS];
-                    for (int k_ = 0; k_ < CRT_X_EXTRA_LOADS; k_++) {
-                        uint32_t off_ = lanes(EN1) ? (uint32_t)ref * (IMPL ? (uint32_t)(NODE4I_F4 * 16) : 128u) : 0u;
-                        asm volatile("" : "+v"(off_));
-#if defined(CRT_X_EXTRA_UNIFORM)
-                        off_ &= 0u; /* every lane the same address */
-#endif
-                        xl_[k_] = *(const float*)(((const char*)(IMPL ? sc.nodes4i : sc.nodes4) + off_) + 80);
-                    }
-#endif
                     const int top1 = stack_top_ahead(S, id, sp, LDS3::LV);
                     DONE |= visit_front<STATS, LDS3, 1, IMPL>(sc, M3, g, dir, R, V1, top1, ref, sp, tc, max_sp, lq_t, added, ANY, n_leaf, EN1, lq_free, nullptr, &VOID);
                     if (STATS && lanes(EN1 & VOID)) dg_ov[0]++;
@@ -1465,10 +1387,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
                     // them the visit is dropped.  C2 82.7 -> 81.7 ms, veach-mis spp 256
                     // 81.8 -> 80.3 (40 .. 52: the same; 16 / 32: 82.6 / 82.1 and 80.8 / 80.6; as a loop, or three / four visits: worse).
                     // Round 6: its node is fetched BEFORE the first visit's appends and pushes are written (node_load / visit_back).
-#ifndef CRT_VISIT2_MIN
-#define CRT_VISIT2_MIN 44
-#endif
-                    constexpr int VISIT2_MIN = CRT_VISIT2_MIN;
+                    constexpr int VISIT2_MIN = 44;
                     const wmask EN2 = ON & ~DONE;
                     const bool second = !MAY_EXACT && (int)__popcll(EN2) >= VISIT2_MIN;
                     if (second) node_load<IMPL>(sc, ref, EN2, dir, V2);
@@ -1482,9 +1401,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
                         if (!bailed) visit_back(S, M3, id, g, V2);
                         if (STATS && bailed && lanes(EN2)) dg_ov[1]++;
                     }
-#ifdef CRT_X_EXTRA_LOADS
-                    for (int k_ = 0; k_ < CRT_X_EXTRA_LOADS; k_++) asm volatile("" :: "v"(xl_[k_]));
-#endif
                 }
                 if (MAY_EXACT) {
                     const wmask GX = GO & EX;
@@ -1518,7 +1434,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
             const wmask MC = ON & ~DONE;
             if (MC) {
                 const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(MC >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)MC, RQ_PUSH_BASE(PH3_INNER)));
-                if (lanes(MC)) S.rq(PH3_INNER)[ring_wrap<QCAP>(slot)] = (uint8_t)id;
+                if (lanes(MC)) S.rq(PH3_INNER)[slot] = (uint8_t)id;
                 const int c = (int)__popcll(MC);
                 RQ_PUSH_ADV(PH3_INNER, c)
             }
@@ -1608,10 +1524,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
         // 89.5 -> 84.8 (32 / 52: the same).  Not taken: staying on the SAME ring while it holds another full batch (92.9 / 86.7); one chained
         // step only, each arm compiled twice (92.1 / 86.0); the same preference expressed in the scheduler's keys (no gain); a short-cut in
         // front of the scheduler (93.6 / 88.7).
-#ifndef CRT_CHAIN_MIN
-#define CRT_CHAIN_MIN 44
-#endif
-        constexpr int CHAIN_MIN = CRT_CHAIN_MIN;
+        constexpr int CHAIN_MIN = 44;
         auto logic_waits = [&]() __attribute__((always_inline)) {
             if constexpr (STATS) return max(max(qn[PH3_LA], qn[PH3_LB]), qn[PH3_LC]) >= 64; // (the counting kernels' cursors may live in vector registers)
             else return smax(smax(qn[PH3_LA], qn[PH3_LB]), qn[PH3_LC]) >= 64;
@@ -1709,9 +1622,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
             const int src_h = held ? wh : (int)RQ_POP_BASE(PH3_LC, take);
             if (STATS) { dg_b[PH3_LC]++; dg_l[PH3_LC] += (uint32_t)take; }
             const bool on = lane < take;
-            // (the parking ring of the commit ring is a FIFO whatever CRT_RING_MODE says: its wrap is by compare)
+            // (the parking ring of the commit ring is a FIFO: its wrap is by compare)
             const uint32_t pop_i = (uint32_t)(src_h + lane);
-            const uint32_t id = held ? S.rq(PH3_WAIT)[min(pop_i, pop_i - (uint32_t)QCAP)] : S.rq(PH3_LC)[ring_wrap<QCAP>(pop_i)];
+            const uint32_t id = held ? S.rq(PH3_WAIT)[min(pop_i, pop_i - (uint32_t)QCAP)] : S.rq(PH3_LC)[pop_i];
             if (held) {
                 int nh = src_h + take;
                 if (nh >= QCAP) nh -= QCAP;
@@ -1857,13 +1770,8 @@ __global__ __launch_bounds__(64) void k_order_items(const LParams P, uint32_t* l
         const unsigned long long m_on = __ballot(on_j), m_off = __ballot(ex_j && !on_j);
         const unsigned long long below = (1ull << lane) - 1ull;
         const uint32_t i = b + j * 64u + lane;
-#if defined(CRT_HANDOFF_PLAIN) || defined(CRT_HANDOFF_PLAIN_STORE)
-        if (on_j) out[base_on + (uint32_t)__popcll(m_on & below)] = i;
-        else if (ex_j) out[wn - 1u - (base_off + (uint32_t)__popcll(m_off & below))] = i;
-#else
         if (on_j) __hip_atomic_store(&out[base_on + (uint32_t)__popcll(m_on & below)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         else if (ex_j) __hip_atomic_store(&out[wn - 1u - (base_off + (uint32_t)__popcll(m_off & below))], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
         base_on += (unsigned int)__popcll(m_on);
         base_off += (unsigned int)__popcll(m_off);
     }

@@ -413,17 +413,13 @@ __device__ __forceinline__ void setup_shadow(const LParams& P, const Tables<LDS_
 // needed (two multiply-shift divisions and the tile arithmetic).  Against keeping (pixel, sample, item) as 16 B, measured on C2 with
 // one --pmc pass per counter: memory-side traffic 431.7 -> 382.7 GB per launch, L2 miss rate 0.495 -> 0.467, vector instructions
 // + 1.2 %, frame 96.7 -> 95.5 ms (profiles/r03_traffic_id_plane.txt).  (The wavefront pipeline keeps the 16-byte entries.)
-// CRT_X_NOVN (round 5; 0 = the round-4 layout): k_mega3 keeps no `vn` plane (normal, material of the current vertex:
+// Round 5: k_mega3 keeps no `vn` plane (normal, material of the current vertex:
 // 16 B read in every LA and LB visit, written at every vertex) -- both are a function of the vertex's triangle, which travels in the second
 // word of an 8-byte id plane, and come from the L2-resident 16 B / triangle table tri_nm, one dependent load later.  Measured (C2, one
 // box): L2 <-> fabric traffic 348.6 -> 320.0 GB per frame (-8.2 %), L2 miss rate 0.475 -> 0.449, frame 78.0 -> 77.2 ms; veach-mis spp 256
 // 77.9 -> 77.5 ms.  (The wavefront pipeline keeps its vn plane.)
-#ifndef CRT_X_NOVN
-#define CRT_X_NOVN 1
-#endif
 // Round 6: in every mode but CRT_TRAVERSAL_REFERENCE the triangle rides in the w word of the cc plane instead -- written
 // with every next-event sample anyway -- and the id plane is read as the work item alone (TRI = false); see logic_A.
-#if CRT_X_NOVN
 template <bool RING = false, bool TRI = true>
 __device__ __forceinline__ uint4 load_path_id(const LParams& P, const uint32_t g)
 {
@@ -448,22 +444,6 @@ __device__ __forceinline__ void store_path_tri(const LParams& P, const uint32_t 
 {
     *(CRT_GAS uint32_t*)((uint32_t*)((uint2*)P.pool.id + g) + 1) = tri;
 }
-#else
-template <bool RING = false, bool TRI = true>
-__device__ __forceinline__ uint4 load_path_id(const LParams& P, const uint32_t g)
-{
-    const uint32_t item = gld((const uint32_t*)P.pool.id + g);
-    uint32_t pixel_index, k, pi, pj;
-    bool valid;
-    decode_item<RING>(P, item, pixel_index, k, valid, pi, pj);
-    return make_uint4(pixel_index, k, item, 0u);
-}
-template <bool TRI = true>
-__device__ __forceinline__ void store_path_id(const LParams& P, const uint32_t g, const uint32_t item)
-{
-    *(CRT_GAS uint32_t*)((uint32_t*)P.pool.id + g) = item;
-}
-#endif
 
 // Backward recursion over the vertex records, deepest first: Render.cuh:238-326.
 template <bool LDS_TABLES>
@@ -482,9 +462,7 @@ __device__ __forceinline__ F3 finish_path(const LParams& P, const Tables<LDS_TAB
     // The recursion is a serial chain, but its loads are not: the records (and material rows) of CRT_FINISH_PF vertices are
     // fetched together, so a chunk costs two memory round trips instead of two per vertex (lanes with fewer vertices re-read
     // vertex 0 and skip the arithmetic).
-#ifndef CRT_FINISH_PF
 #define CRT_FINISH_PF 4
-#endif
     for (int v = deepest - 1; v >= 0; v -= CRT_FINISH_PF) {
         float4 a[CRT_FINISH_PF], fm[CRT_FINISH_PF];
         uint32_t mat[CRT_FINISH_PF];

@@ -457,9 +457,6 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
                 lanes = blocks * pool_p; // pool slots
             }
             sc->p_vx.ensure(lanes); sc->p_la.ensure(lanes); sc->p_cc.ensure(lanes); sc->p_id.ensure(lanes);
-#if !CRT_X_NOVN
-            sc->p_vn.ensure(lanes); // (round 5: k_mega3 reads normal and material from tri_nm through the triangle in its 8-byte id plane, crt_path.h)
-#endif
             sc->p_rec_a.ensure((size_t)lanes * CRT_BOUNCE_STACK_SIZE);
             sc->p_rec_b.ensure((size_t)lanes * CRT_BOUNCE_STACK_SIZE);
             // (16-bit layout: a ray on the reference-arithmetic path keeps its whole stack in the global area)

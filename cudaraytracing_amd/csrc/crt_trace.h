@@ -59,9 +59,7 @@ __device__ __forceinline__ bool slab_test(float4 lo, float4 hi, const RayT& r, b
 // margin histogram of tools/margin_hist.py shows a tail ~ s^-0.7 on veach-mis (factor 1e-3: a fifth of the events for +8.5 % frame
 // time) and no tail at all on cornell-box.  DESIGN.md section 4; docs/experiments.md 4.3 has the numbers; include/crt.h states the contract; the lost
 // rays are known answers in tests/test_adversarial_traversal.py.  Rays with a zero direction component get an infinite bound.
-#ifndef CRT_PRUNE_REL
 #define CRT_PRUNE_REL 1.0e-4f
-#endif
 __device__ __forceinline__ float prune_bound(float t, const F3 o, const F3 inv)
 {
     const float reach = fmaxf(fmaxf(absf(o.x), absf(o.y)), absf(o.z)) + absf(t);

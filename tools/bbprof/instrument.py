@@ -73,7 +73,7 @@ def main():
             return "vmem"
         if mn.startswith("ds_"):
             return "lds"
-        if mn.startswith(("s_load", "s_store", "s_memtime", "s_memrealtime", "s_dcache", "s_buffer_load", "s_atc")):
+        if mn.startswith(("s_load", "s_memtime", "s_memrealtime", "s_dcache", "s_buffer_load", "s_atc")):
             return "smem"
         if mn.startswith(("s_waitcnt", "s_nop", "s_sleep", "s_barrier", "s_endpgm", "s_sethalt", "s_setprio", "s_trap", "s_inst_prefetch", "s_code_end")):
             return "ctl"
