@@ -174,6 +174,7 @@ class Render:
         self.frame_buffer = None
         self.mean_buffer = None
         self.stats = None
+        self.aov_info = None
 
     def _handle(self, what):
         """The crt_scene* of this renderer; raises when there is none (freed, or a MultiRender, whose handle is a crt_multi*)."""
@@ -309,6 +310,45 @@ class Render:
             self.stats = st.as_dict()
         return self.stats
 
+    def run_view_aov(self, eye_pos, inv_view_mat, fovY, want=tuple(capi.AOV_BUFFERS), width=None, height=None):
+        """First-hit AOVs of the frame run_view draws with the same camera and settings (crt_render_aov): per pixel, the spp camera
+        rays of the frame's paths traced for their closest hit.  Returns {name: array} for the names in `want` (albedo, normal:
+        (H, W, 3) float32; depth, coverage: (H, W) float32; tri, material: (H, W) int32); self.aov_info gets rays, chunks, total_ms."""
+        h_ = self._handle("run_view_aov")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        w, h = prm.width, prm.height
+        out, bufs = {}, capi.AovBuffers()
+        for name in want:
+            ch, dt = capi.AOV_BUFFERS[name]
+            out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
+            setattr(bufs, name, out[name].ctypes.data)
+        info = capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov(h_, C.byref(cam), C.byref(prm), C.byref(bufs), C.byref(info)), "crt_render_aov")
+        self.aov_info = info.as_dict()
+        return out
+
+    def run_view_aov_device(self, eye_pos, inv_view_mat, fovY, ptrs, stream=None, rank=0, world=1, tiled=False, want_info=True,
+                            width=None, height=None):
+        """Enqueues the AOV pass with outputs in device memory: ptrs = {name: raw device pointer} (row-major W x H, or the shard's
+        compact tiles with tiled / world > 1, as run_view_device).  With want_info the call synchronizes the stream and sets
+        self.aov_info."""
+        h_ = self._handle("run_view_aov_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
+        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        bufs = capi.AovBuffers()
+        for name, p in ptrs.items():
+            if name not in capi.AOV_BUFFERS:
+                raise ValueError("unknown AOV buffer %r" % name)
+            setattr(bufs, name, int(p) if p else None)
+        info = capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov_device(h_, C.byref(cam), C.byref(prm), C.byref(bufs), C.c_void_p(stream) if stream else None,
+                                                    C.byref(info) if want_info else None), "crt_render_aov_device")
+        if want_info:
+            self.aov_info = info.as_dict()
+        return self.aov_info if want_info else None
+
     def intersect(self, origins, dirs, traversal=None):
         self._handle("intersect")
         o = np.ascontiguousarray(origins, dtype=np.float32)
@@ -416,6 +456,12 @@ class MultiRender(Render):
     def run_view_device(self, *a, **k):
         raise NotImplementedError("MultiRender owns its device buffers (crt_multi_frame_device)")
 
+    def run_view_aov(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov)")
+
+    def run_view_aov_device(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_device)")
+
     def intersect(self, *a, **k):
         raise NotImplementedError("crt_intersect is a single-device interface")
 
@@ -439,6 +485,16 @@ def image_load(path):
     a = np.zeros((y.value, x.value, comp.value), dtype=np.uint8)
     capi.check(capi.lib().crt_image_load(os.fsencode(path), C.byref(x), C.byref(y), C.byref(comp), capi.ptr(a), a.size), "crt_image_load")
     return x.value, y.value, comp.value, a
+
+
+def write_pfm(path, data):
+    """Writes a (H, W) or (H, W, 3) float array as a Portable Float Map (crt_write_pfm: "Pf" / "PF", little-endian, rows bottom to
+    top in the file; row 0 of `data` is the image top)."""
+    a = np.ascontiguousarray(data, dtype=np.float32)
+    if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+        raise ValueError("write_pfm needs an (H, W) or (H, W, 3) array, got %r" % (a.shape,))
+    ch = 1 if a.ndim == 2 else a.shape[2]
+    capi.check(capi.lib().crt_write_pfm(os.fsencode(path), a.shape[1], a.shape[0], ch, capi.ptr(a)), "crt_write_pfm")
 
 
 def shard_slots(width, height, rank, world):

@@ -6,7 +6,9 @@
 //
 //   crt_cli <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
-//           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy]
+//           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
+// --aov PREFIX also writes the first-hit AOVs of the frame (crt_render_aov, one device): PREFIX_albedo.png (8-bit, 255 x clamp(a, 0, 1)
+// truncated, no gamma), PREFIX_normal.png (255 x clamp((n + 1) / 2, 0, 1)) and PREFIX_depth.pfm (floats).
 // --gpus N renders on devices 0..N-1 of this node in one process (crt_multi: interleaved pixel tiles, one RCCL all-gather);
 // --devices names the device of every rank explicitly (a repeated index puts two ranks on one GPU: --gather copy only).
 #include "crt_host.hpp"
@@ -24,13 +26,13 @@ int main(int argc, char** argv)
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
-                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy]\n", argv[0]);
+                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n", argv[0]);
         return 2;
     }
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".";
+        std::string out = "out.png", base_dir = ".", aov;
         uint64_t seed = 0;
         int device = 0;
         bool reference = false, exact = false, fast = false, bounded = false;
@@ -70,6 +72,7 @@ int main(int argc, char** argv)
                 else throw crt::Error(CRT_ERR_INVALID_ARG, "--gather must be auto, rccl or copy");
             }
             else if (a == "--base-dir") { need(i, 1); base_dir = argv[++i]; }
+            else if (a == "--aov") { need(i, 1); aov = argv[++i]; }
             else if (a == "--reference") reference = true;
             else if (a == "--exact") exact = true;
             else if (a == "--fast") fast = true;
@@ -86,6 +89,7 @@ int main(int argc, char** argv)
         std::printf("triangles: %zu, BVH nodes: %zu, lights: %zu\n", scene.get_triangles().size(), scene.get_bvh().get_nodes_size(),
                     scene.get_light_objs().size());
         const bool multi = !devices.empty();
+        if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
         crt::Render render_one_or_many = multi ? crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, devices, gather)
                                                : crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, device);
         crt::Render& render = render_one_or_many;
@@ -110,6 +114,26 @@ int main(int argc, char** argv)
         }
         render.save_frame_buffer(out.c_str());
         std::printf("%s\n", out.c_str());
+        if (!aov.empty()) {
+            render.run_aov(task.eye_pos, inv_view, fov_y);
+            const crt_aov_info& ai = render.last_aov_info();
+            std::printf("aov: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
+            const size_t n = (size_t)task.width * task.height;
+            // (float arithmetic throughout; to_u8 truncates as the frame's tone map does)
+            auto to_u8 = [](float v) -> uint8_t { return !(v == v) || v <= 0.0f ? 0 : v >= 255.0f ? 255 : (uint8_t)v; };
+            auto unit_clamp = [](float v) { return v < 0.0f ? 0.0f : v > 1.0f ? 1.0f : v; };
+            std::vector<uint8_t> albedo(3 * n), normal(3 * n);
+            for (size_t k = 0; k < 3 * n; k++) {
+                albedo[k] = to_u8(255.0f * unit_clamp(render.get_albedo_buffer()[k]));
+                normal[k] = to_u8(255.0f * unit_clamp((render.get_normal_buffer()[k] + 1.0f) / 2.0f));
+            }
+            const std::string pa = aov + "_albedo.png", pn = aov + "_normal.png", pd = aov + "_depth.pfm";
+            int rc = crt_write_png(pa.c_str(), task.width, task.height, albedo.data());
+            if (rc == CRT_OK) rc = crt_write_png(pn.c_str(), task.width, task.height, normal.data());
+            if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_depth_buffer());
+            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the AOV files failed: ") + crt_last_error());
+            std::printf("%s\n%s\n%s\n", pa.c_str(), pn.c_str(), pd.c_str());
+        }
         render.free();
         return 0;
     } catch (const crt::Error& e) {

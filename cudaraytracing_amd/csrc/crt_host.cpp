@@ -677,6 +677,27 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view failed: ") + crt_last_error());
 }
 
+void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov: the AOV pass is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov after free()");
+    crt_camera cam;
+    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
+    cam.fov_y = fovY;
+    crt_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_;
+    const size_t n = scene_->get_pixels();
+    albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f);
+    crt_aov_buffers out{};
+    out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data();
+    const int rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
+}
+
 void Render::save_frame_buffer(const char* save_path) const
 {
     int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), frame_buffer_.data());
@@ -882,6 +903,24 @@ int crt_write_png(const char* path, uint32_t width, uint32_t height, const uint8
     size_t w = std::fwrite(png.data(), 1, png.size(), f);
     std::fclose(f);
     if (w != png.size()) { g_last_error = std::string("short write: ") + path; return CRT_ERR_IO; }
+    return CRT_OK;
+}
+
+int crt_write_pfm(const char* path, uint32_t width, uint32_t height, uint32_t channels, const float* data)
+{
+    if (!path || !data || width == 0 || height == 0 || (channels != 1 && channels != 3)) { g_last_error = "crt_write_pfm: bad arguments"; return CRT_ERR_INVALID_ARG; }
+    static_assert(sizeof(float) == 4, "PFM samples are 32-bit floats");
+    const uint32_t probe = 1;
+    if (*(const uint8_t*)&probe != 1) { g_last_error = "crt_write_pfm: big-endian host"; return CRT_ERR_UNSUPPORTED; } // (scale -1.0 says little-endian)
+    const std::string header = std::string(channels == 3 ? "PF" : "Pf") + "\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
+    FILE* f = std::fopen(path, "wb");
+    if (!f) { g_last_error = std::string("cannot open for writing: ") + path; return CRT_ERR_IO; }
+    bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
+    const size_t row = (size_t)width * channels;
+    for (uint32_t y = height; ok && y-- > 0;) // bottom row first
+        ok = std::fwrite(data + (size_t)y * row, sizeof(float), row, f) == row;
+    ok = std::fclose(f) == 0 && ok;
+    if (!ok) { g_last_error = std::string("short write: ") + path; return CRT_ERR_IO; }
     return CRT_OK;
 }
 

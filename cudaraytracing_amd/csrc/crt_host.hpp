@@ -214,6 +214,12 @@ public:
     Render& operator=(const Render&) = delete;
     // run_view(eye_pos, inv_view_mat, fovY): inv_view column-major, fovY in radians
     void run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY);
+    // first-hit albedo, normal and depth of the frame run_view draws with the same camera and settings (crt_render_aov); one device only
+    void run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY);
+    const float* get_albedo_buffer() const { return albedo_buffer_.data(); } // W x H x 3, row 0 = image top
+    const float* get_normal_buffer() const { return normal_buffer_.data(); } // W x H x 3
+    const float* get_depth_buffer() const { return depth_buffer_.data(); }   // W x H
+    const crt_aov_info& last_aov_info() const { return aov_info_; }
     void free();
     void save_frame_buffer(const char* save_path) const;
     unsigned char* get_frame_buffer() const { return const_cast<unsigned char*>(frame_buffer_.data()); }
@@ -244,7 +250,9 @@ private:
     std::vector<crt_stats> rank_stats_;
     std::vector<unsigned char> frame_buffer_;
     std::vector<float> mean_buffer_;
+    std::vector<float> albedo_buffer_, normal_buffer_, depth_buffer_;
     crt_stats stats_{};
+    crt_aov_info aov_info_{};
 };
 
 } // namespace crt

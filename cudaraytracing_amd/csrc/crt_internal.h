@@ -94,5 +94,35 @@ void launch_math(int fn, uint32_t n, const float* a, const float* b, float* out)
 void launch_philox(uint32_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out);
 void launch_rcp_check(unsigned long long* counts);
 
+// first-hit AOV pass (crt_aov.hip; host side: crt_render_aov in crt_render.hip).  One chunk = samples [sample_begin, sample_begin + n_samples)
+// of every pixel slot of the shard; query ray / result item = sample offset in the chunk x nslots + slot.
+struct AovParams {
+    // the camera, as LParams holds it (camera_dir)
+    float eye[3];
+    float inv_view[9];
+    float scale, ar;
+    uint32_t width, height;
+    uint64_t seed;
+    // the shard's pixel slots (slot_to_pixel)
+    uint32_t rank, world, tiles_x, n_tiles, nslots;
+    FastDiv tiles_x_div;
+    uint32_t spp, sample_begin, n_samples;
+    uint32_t first_chunk, last_chunk, tiled_output;
+    Pool pool;               // k_aov_rays: the query pool (ro, rd, res)
+    const float* res;        // k_aov_resolve: (t, bits(triangle or -1)) of item i at res[i * res_stride]
+    uint32_t res_stride;     // floats per item: 4 (k_mega3 query form, L) or 2 (k_trace, the pool's res plane)
+    const float4* tri_nm;    // scene: normal.xyz, bits(material word) per triangle
+    const float4* mats;      // scene: 3 rows per material, row 1 = kd.xyz
+    float4* acc;             // [nslots][3] running sums across chunks: (albedo.xyz, depth), (normal.xyz, bits(hits)), (bits(tri_0), bits(m_0), -, -)
+    float* albedo;           // outputs (any may be null): row-major W x H, or nslots with tiled_output
+    float* normal;
+    float* depth;
+    float* coverage;
+    int32_t* tri;
+    int32_t* material;
+};
+void launch_aov_rays(const AovParams& A, hipStream_t st);
+void launch_aov_resolve(const AovParams& A, hipStream_t st);
+
 } // namespace crtk
 #endif

@@ -521,13 +521,7 @@ __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb
         }
         cnt.paths++;
         if (!waiting) store_path_id<!TRI_CC>(P, g, item);
-        const U4 rj = rng_draw(P.seed, pixel_index, k, 0, RNG_JITTER, 0);
-        const float x = (2 * ((int)pi + rng_uniform(rj.x)) / P.width - 1) * P.scale * P.ar;
-        const float y = (1 - 2 * ((int)pj + rng_uniform(rj.y)) / P.height) * P.scale;
-        const F3 cd = unit3(f3(-x, y, 1));
-        const F3 wd = f3(P.inv_view[0] * cd.x + (P.inv_view[3] * cd.y + P.inv_view[6] * cd.z),
-                         P.inv_view[1] * cd.x + (P.inv_view[4] * cd.y + P.inv_view[7] * cd.z),
-                         P.inv_view[2] * cd.x + (P.inv_view[5] * cd.y + P.inv_view[8] * cd.z));
+        const F3 wd = camera_dir(P, pixel_index, k, pi, pj);
         gst(&pl.la[g], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)ST_HIT << 8)));
         nr.o = f3(P.eye[0], P.eye[1], P.eye[2]); nr.d = unit3(wd); /* Ray.cuh:13 */ nr.tl = 0.0f; nr.kind = RAY_CLOSEST; nr.flags = 0;
         return LC_RAY;

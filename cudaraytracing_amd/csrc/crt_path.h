@@ -2,7 +2,7 @@
 // code of crt_render.hip), work-item cursors, the path logic both pipelines are made of (next-event set-up, backward recursion:
 // include/Render.cuh:199-326), the commit ring of CRT_FLAG_BOUNDED_RADIANCE, and the short exact reciprocal.
 // Included by crt_mega3.hip (the megakernel), crt_wavefront.hip (the fallback pipeline), crt_frame.hip (frame kernels, test
-// kernels) and crt_render.hip (host).
+// kernels), crt_aov.hip (the AOV pass) and crt_render.hip (host).
 #ifndef CRT_PATH_H
 #define CRT_PATH_H
 #include "../../include/crt.h"
@@ -232,6 +232,24 @@ __device__ __forceinline__ void decode_item(const LParams& P, uint32_t item, uin
     k = P.sample_begin + s;
     valid = (!RING || slot < P.nslots) && slot_to_pixel(slot, P.rank, P.world, P.n_tiles, P.tiles_x, P.tiles_x_div, P.width, P.height, pi, pj);
     pixel_index = pj * P.width + pi; // Render.cuh:336
+}
+
+// The camera ray of sample k of pixel (pi, pj) (Render.cuh:344-347): the jitter draws, the point on the image plane and the inverse view.
+// Returns the direction Render.cuh hands to Ray's constructor; the caller makes the ray's unit direction of it with unit3 (Ray.cuh:13)
+// and takes the eye as origin.  The one definition of a primary ray: k_mega3 (logic_C), k_logic (phase 5) and the AOV pass (k_aov_rays)
+// call it.  CP: a parameter block with seed, width, height, scale, ar and inv_view (LParams, AovParams), scale / ar as camera_scale_ar
+// (crt_render.hip) sets them.
+template <class CP>
+__device__ __forceinline__ F3 camera_dir(const CP& P, const uint32_t pixel_index, const uint32_t k, const uint32_t pi, const uint32_t pj)
+{
+    const U4 rj = rng_draw(P.seed, pixel_index, k, 0, RNG_JITTER, 0);
+    const float x = (2 * ((int)pi + rng_uniform(rj.x)) / P.width - 1) * P.scale * P.ar;
+    const float y = (1 - 2 * ((int)pj + rng_uniform(rj.y)) / P.height) * P.scale;
+    const F3 cd = unit3(f3(-x, y, 1));
+    const F3 wd = f3(P.inv_view[0] * cd.x + (P.inv_view[3] * cd.y + P.inv_view[6] * cd.z),
+                     P.inv_view[1] * cd.x + (P.inv_view[4] * cd.y + P.inv_view[7] * cd.z),
+                     P.inv_view[2] * cd.x + (P.inv_view[5] * cd.y + P.inv_view[8] * cd.z));
+    return wd;
 }
 
 // ---- commit ring: the frame's sum c += L_k / spp in sample order (Render.cuh:348) INSIDE the launch, with storage for a window of

@@ -1,6 +1,7 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- host side of the device layer of libcrt.so: scene upload (the flat HBM layouts of crt_device.h, the two trees,
-// the 4-wide collapse), the launch logic of a frame, and the C ABI of include/crt.h (crt_scene_create, crt_render*, crt_preview*,
-// crt_intersect, crt_device_*).  The kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip.
+// the 4-wide collapse), the launch logic of a frame and of the AOV pass, and the C ABI of include/crt.h (crt_scene_create, crt_render*,
+// crt_preview*, crt_render_aov*, crt_intersect, crt_device_*).  The kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip,
+// crt_aov.hip.
 #include "crt_internal.h"
 
 #include <algorithm>
@@ -37,6 +38,7 @@ struct crt_scene {
     uint32_t n_mats = 0;
     DevBuf<float2> p_res;
     DevBuf<float> accum;
+    DevBuf<float4> aov_acc;                   // AOV pass: running sums of the pixel slots between its chunks (crt_render_aov)
     DevBuf<unsigned long long> counters;      // [CNT_SHARDS][CNT_STRIDE]
     DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
     DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)
@@ -309,6 +311,14 @@ static bool use_impl(const crt_scene* sc, bool dec, bool r16)
 // variables lower the limits so that the tests can force each fallback on a small scene.
 uint32_t choose_pipeline(const crt_scene* sc);
 
+// The camera's half-height at distance 1 and aspect ratio (Render.cuh:338-339), as the camera rays of a frame (camera_dir) and of the AOV
+// pass take them
+void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale, float& ar)
+{
+    scale = det_tanf(cam->fov_y / 2);
+    ar = (float)prm->width / (float)prm->height;
+}
+
 const uint64_t kMaxChunkItems = 1ull << 30; // paths per chunk (17 GB of per-path radiance: sized for 288 GB of HBM, every launch ends with a 2 ms tail)
 
 struct TraceSetup {
@@ -348,6 +358,55 @@ void launch_trace_pass(crt_scene* sc, const TraceSetup& S, hipStream_t st)
 {
     HIP_CHECK(hipMemsetAsync(S.T.slot_next, 0, (size_t)SLOT_SHARDS * SLOT_STRIDE * sizeof(unsigned int), st));
     launch_trace(S.mode_id, S.T, S.blocks, S.lds, st);
+}
+
+// Traces the n query rays in the handle's query pool (p_ro / p_rd, p_res primed: the form k_fill_rays writes) on stream st with the
+// traversal phases of the render kernel itself -- k_mega3 in query form (work item = ray), or k_trace on the fallback pipeline -- and
+// leaves the answers on the device: (t or FLT_MAX, bits(triangle or -1)) of ray i at the returned pointer + i * stride floats (L, stride
+// 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV pass.
+const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride)
+{
+    if (choose_pipeline(sc) == 4) {
+        const bool reference = traversal == CRT_TRAVERSAL_REFERENCE;
+        int per_cu = 1;
+        const bool exact = traversal == CRT_TRAVERSAL_EXACT;
+        const int mode3 = reference ? 1 : exact ? 2 : 0;
+        const bool dec = use_dec(sc, mode3);
+        const bool r16 = use_ref16(sc, mode3, dec);
+        const Mega3Kernel kern3 = mega3_kernel(mode3, false, false, true, r16, false, dec, use_impl(sc, dec, r16));
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern3, 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        const uint32_t pool_p = mega3_pool_p(dec, false);
+        const uint32_t blocks = std::min<uint32_t>((n + pool_p - 1) / pool_p, (uint32_t)(sc->n_cus * per_cu));
+        const uint32_t lanes = blocks * pool_p;
+        sc->p_la.ensure(lanes); sc->p_id.ensure(lanes); sc->L.ensure(n);
+        sc->spill[0].ensure((size_t)(r16 ? std::max(1, sc->stack_cap) : std::max(1, sc->stack_cap - mega3_lds_levels(dec, r16))) * lanes);
+        MParams3 M3;
+        std::memset(&M3, 0, sizeof(M3));
+        LParams& P = M3.M.P;
+        P.sc = sc->dev;
+        P.pool.la = sc->p_la.p; P.pool.id = sc->p_id.p; P.pool.n = lanes;
+        P.n_items = n;
+        P.items_per_shard = ((n + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
+        P.item_next = sc->item_next.p; P.L = sc->L.p; P.counters = sc->counters.p;
+        P.q_o = sc->p_ro.p; P.q_d = sc->p_rd.p;
+        P.nslots = 1; P.nslots_div = make_fastdiv(1); P.tiles_x = 1; P.tiles_x_div = make_fastdiv(1); P.lsn_div = make_fastdiv(1);
+        M3.M.sc = sc->dev; M3.M.counters = sc->counters.p; M3.M.spill_stride = lanes; M3.M.stack_cap = mega3_lds_levels(dec, r16);
+        M3.spill = (int*)sc->spill[0].p;
+        M3.force_exact = force_exact ? 1u : 0u;
+        HIP_CHECK(hipMemsetAsync(sc->item_next.p, 0, (size_t)ITEM_SHARDS * ITEM_STRIDE * sizeof(unsigned int), st));
+        hipLaunchKernelGGL(kern3, dim3(blocks), dim3(64), 0, st, M3);
+        HIP_CHECK(hipGetLastError());
+        stride = 4;
+        return (const float*)sc->L.p;
+    }
+    Pool pool;
+    std::memset(&pool, 0, sizeof(pool));
+    pool.ro = sc->p_ro.p; pool.rd = sc->p_rd.p; pool.res = sc->p_res.p; pool.n = n;
+    TraceSetup TS = make_trace_setup(sc, pool, traversal, false);
+    launch_trace_pass(sc, TS, st);
+    HIP_CHECK(hipGetLastError());
+    stride = 2;
+    return (const float*)sc->p_res.p;
 }
 
 // Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
@@ -472,8 +531,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
             P.sc = sc->dev; P.pool = pool;
             std::memcpy(P.eye, cam->eye, sizeof(P.eye));
             std::memcpy(P.inv_view, cam->inv_view, sizeof(P.inv_view));
-            P.scale = det_tanf(cam->fov_y / 2);                       // Render.cuh:338
-            P.ar = (float)prm->width / (float)prm->height;            // Render.cuh:339
+            camera_scale_ar(cam, prm, P.scale, P.ar);
             P.width = prm->width; P.height = prm->height;
             P.p_rr = prm->p_rr; P.lsn = prm->light_sample_n; P.seed = prm->seed;
             P.rank = prm->rank; P.world = prm->world; P.tiles_x = sh.tiles_x; P.n_tiles = sh.n_tiles;
@@ -626,8 +684,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         P.sc = sc->dev;
         std::memcpy(P.eye, cam->eye, sizeof(P.eye));
         std::memcpy(P.inv_view, cam->inv_view, sizeof(P.inv_view));
-        P.scale = det_tanf(cam->fov_y / 2);                       // Render.cuh:338
-        P.ar = (float)prm->width / (float)prm->height;            // Render.cuh:339
+        camera_scale_ar(cam, prm, P.scale, P.ar);
         P.width = prm->width; P.height = prm->height;
         P.p_rr = prm->p_rr; P.lsn = prm->light_sample_n; P.seed = prm->seed;
         P.rank = prm->rank; P.world = prm->world; P.tiles_x = sh.tiles_x; P.n_tiles = sh.n_tiles;
@@ -745,6 +802,92 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
             stats->logic_ms = (float)logic_ms;
             stats->total_ms = total;
             stats->kernel_launches = trace_launches;
+        }
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+// The first-hit AOV pass (crt_render_aov): the camera rays of samples 0 .. spp-1 of every pixel slot of the shard, in chunks of whole
+// samples of at most kAovChunkRays rays (32 B of query pool + 16 B of results per ray: 1.6 GB), each traced by trace_queries and folded
+// into the per-slot running sums in sample order (k_aov_resolve).  Uses the handle's query pool and trace buffers, as crt_intersect does;
+// the accumulator of a progressive render (accum, acc) is not touched.
+const uint32_t kAovChunkRays = 1u << 25;
+
+// Argument checks of both forms, before any device call
+int aov_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out)
+{
+    if (!sc || !cam || !prm || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: null argument");
+    if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->tri && !out->material)
+        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: no output buffer");
+    if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: width, height and spp must be positive");
+    if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: need rank < world");
+    if (prm->traversal != CRT_TRAVERSAL_FAST && prm->traversal != CRT_TRAVERSAL_REFERENCE && prm->traversal != CRT_TRAVERSAL_EXACT)
+        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: unknown traversal mode");
+    if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: world > 1 needs CRT_FLAG_TILED_OUTPUT");
+    if ((uint64_t)prm->width * prm->height > 0xffffffffull) return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov: more than 2^32 pixels");
+    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
+        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov: more than 2^31 pixel slots in a shard");
+    return CRT_OK;
+}
+
+int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out, hipStream_t st, crt_aov_info* info)
+{
+    const int rc = aov_check(sc, cam, prm, out);
+    if (rc != CRT_OK) return rc;
+    const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
+    const Shard sh = make_shard(prm->width, prm->height, prm->world);
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
+        const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
+        sc->p_ro.ensure(max_rays); sc->p_rd.ensure(max_rays); sc->p_res.ensure(max_rays);
+        sc->aov_acc.ensure((size_t)sh.nslots * 3);
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (info) {
+            while (sc->ev.size() < (size_t)(4 * kMaxBatch + 4)) {
+                hipEvent_t e;
+                HIP_CHECK(hipEventCreate(&e));
+                sc->ev.push_back(e);
+            }
+            e0 = sc->ev[0]; e1 = sc->ev[1];
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        AovParams A;
+        std::memset(&A, 0, sizeof(A));
+        std::memcpy(A.eye, cam->eye, sizeof(A.eye));
+        std::memcpy(A.inv_view, cam->inv_view, sizeof(A.inv_view));
+        camera_scale_ar(cam, prm, A.scale, A.ar);
+        A.width = prm->width; A.height = prm->height; A.seed = prm->seed;
+        A.rank = prm->rank; A.world = prm->world; A.tiles_x = sh.tiles_x; A.n_tiles = sh.n_tiles; A.nslots = sh.nslots;
+        A.tiles_x_div = make_fastdiv(sh.tiles_x);
+        A.spp = prm->spp; A.tiled_output = tiled ? 1u : 0u;
+        A.pool.ro = sc->p_ro.p; A.pool.rd = sc->p_rd.p; A.pool.res = sc->p_res.p;
+        A.tri_nm = sc->dev.tri_nm; A.mats = sc->dev.mats; A.acc = sc->aov_acc.p;
+        A.albedo = out->albedo; A.normal = out->normal; A.depth = out->depth; A.coverage = out->coverage; A.tri = out->tri; A.material = out->material;
+        const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
+        uint64_t rays = 0;
+        uint32_t chunks = 0;
+        for (uint32_t s0 = 0; s0 < prm->spp; s0 += chunk) {
+            const uint32_t ns = std::min(chunk, prm->spp - s0);
+            const uint32_t n = ns * sh.nslots;
+            A.sample_begin = s0; A.n_samples = ns; A.pool.n = n;
+            A.first_chunk = s0 == 0; A.last_chunk = s0 + ns == prm->spp;
+            launch_aov_rays(A, st);
+            HIP_CHECK(hipGetLastError());
+            A.res = trace_queries(sc, n, prm->traversal, force_exact, st, A.res_stride);
+            launch_aov_resolve(A, st);
+            HIP_CHECK(hipGetLastError());
+            rays += n;
+            chunks++;
+        }
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            std::memset(info, 0, sizeof(*info));
+            info->rays = rays; info->chunks = chunks;
+            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
         }
         return CRT_OK;
     } catch (const HipFail& f) {
@@ -1492,58 +1635,54 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
         pool.ro = sc->p_ro.p; pool.rd = sc->p_rd.p; pool.res = sc->p_res.p; pool.n = n;
         launch_fill_rays(pool, n, o.p, d.p, raw_dir, any_hit ? lim.p : (const float*)nullptr);
         HIP_CHECK(hipGetLastError());
-        if (choose_pipeline(sc) == 4) {
-            // the rays walk the traversal phases of the render kernel itself (k_mega3 in query form: work item = ray)
-            const bool reference = traversal == CRT_TRAVERSAL_REFERENCE;
-            int per_cu = 1;
-            const bool exact = traversal == CRT_TRAVERSAL_EXACT;
-            const int mode3 = reference ? 1 : exact ? 2 : 0;
-            const bool dec = use_dec(sc, mode3);
-            const bool r16 = use_ref16(sc, mode3, dec);
-            const Mega3Kernel kern3 = mega3_kernel(mode3, false, false, true, r16, false, dec, use_impl(sc, dec, r16));
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern3, 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-            const uint32_t pool_p = mega3_pool_p(dec, false);
-            const uint32_t blocks = std::min<uint32_t>((n + pool_p - 1) / pool_p, (uint32_t)(sc->n_cus * per_cu));
-            const uint32_t lanes = blocks * pool_p;
-            sc->p_la.ensure(lanes); sc->p_id.ensure(lanes); sc->L.ensure(n);
-            sc->spill[0].ensure((size_t)(r16 ? std::max(1, sc->stack_cap) : std::max(1, sc->stack_cap - mega3_lds_levels(dec, r16))) * lanes);
-            MParams3 M3;
-            std::memset(&M3, 0, sizeof(M3));
-            LParams& P = M3.M.P;
-            P.sc = sc->dev;
-            P.pool.la = sc->p_la.p; P.pool.id = sc->p_id.p; P.pool.n = lanes;
-            P.n_items = n;
-            P.items_per_shard = ((n + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
-            P.item_next = sc->item_next.p; P.L = sc->L.p; P.counters = sc->counters.p;
-            P.q_o = sc->p_ro.p; P.q_d = sc->p_rd.p;
-            P.nslots = 1; P.nslots_div = make_fastdiv(1); P.tiles_x = 1; P.tiles_x_div = make_fastdiv(1); P.lsn_div = make_fastdiv(1);
-            M3.M.sc = sc->dev; M3.M.counters = sc->counters.p; M3.M.spill_stride = lanes; M3.M.stack_cap = mega3_lds_levels(dec, r16);
-            M3.spill = (int*)sc->spill[0].p;
-            M3.force_exact = force_exact ? 1u : 0u;
-            HIP_CHECK(hipMemsetAsync(sc->item_next.p, 0, (size_t)ITEM_SHARDS * ITEM_STRIDE * sizeof(unsigned int), nullptr));
-            hipLaunchKernelGGL(kern3, dim3(blocks), dim3(64), 0, nullptr, M3);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipDeviceSynchronize());
-            std::vector<float4> res(n);
-            HIP_CHECK(hipMemcpy(res.data(), sc->L.p, n * sizeof(float4), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < n; i++) {
-                int32_t tri;
-                std::memcpy(&tri, &res[i].y, 4);
-                answer(i, res[i].x, tri);
-            }
-            return CRT_OK;
-        }
-        TraceSetup TS = make_trace_setup(sc, pool, traversal, false);
-        launch_trace_pass(sc, TS, nullptr);
-        HIP_CHECK(hipGetLastError());
+        uint32_t stride = 0;
+        const float* d_res = trace_queries(sc, n, traversal, force_exact, nullptr, stride);
         HIP_CHECK(hipDeviceSynchronize());
-        std::vector<float2> res(n);
-        HIP_CHECK(hipMemcpy(res.data(), sc->p_res.p, n * sizeof(float2), hipMemcpyDeviceToHost));
+        std::vector<float> res((size_t)n * stride);
+        HIP_CHECK(hipMemcpy(res.data(), d_res, res.size() * sizeof(float), hipMemcpyDeviceToHost));
         for (uint32_t i = 0; i < n; i++) {
             int32_t tri;
-            std::memcpy(&tri, &res[i].y, 4);
-            answer(i, res[i].x, tri);
+            std::memcpy(&tri, &res[(size_t)i * stride + 1], 4);
+            answer(i, res[(size_t)i * stride], tri);
         }
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_render_aov_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_out, void* stream, crt_aov_info* info)
+{
+    return aov_impl(sc, cam, prm, dev_out, (hipStream_t)stream, info);
+}
+
+int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* host_out, crt_aov_info* info)
+{
+    const int rc0 = aov_check(sc, cam, prm, host_out);
+    if (rc0 != CRT_OK) return rc0;
+    const crt_aov_buffers& h = *host_out;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
+        const uint64_t npix = tiled ? make_shard(prm->width, prm->height, prm->world).nslots : (uint64_t)prm->width * prm->height;
+        DevBuf<float> d3[2], d1[2];
+        DevBuf<int32_t> di[2];
+        crt_aov_buffers d{};
+        if (h.albedo) { d3[0].alloc(npix * 3); d.albedo = d3[0].p; }
+        if (h.normal) { d3[1].alloc(npix * 3); d.normal = d3[1].p; }
+        if (h.depth) { d1[0].alloc(npix); d.depth = d1[0].p; }
+        if (h.coverage) { d1[1].alloc(npix); d.coverage = d1[1].p; }
+        if (h.tri) { di[0].alloc(npix); d.tri = di[0].p; }
+        if (h.material) { di[1].alloc(npix); d.material = di[1].p; }
+        const int rc = aov_impl(sc, cam, prm, &d, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        if (h.albedo) HIP_CHECK(hipMemcpy(h.albedo, d.albedo, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (h.normal) HIP_CHECK(hipMemcpy(h.normal, d.normal, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (h.depth) HIP_CHECK(hipMemcpy(h.depth, d.depth, npix * sizeof(float), hipMemcpyDeviceToHost));
+        if (h.coverage) HIP_CHECK(hipMemcpy(h.coverage, d.coverage, npix * sizeof(float), hipMemcpyDeviceToHost));
+        if (h.tri) HIP_CHECK(hipMemcpy(h.tri, d.tri, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (h.material) HIP_CHECK(hipMemcpy(h.material, d.material, npix * sizeof(int32_t), hipMemcpyDeviceToHost));
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);

@@ -161,15 +161,8 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
             if (!valid) continue; // padding slot of a ragged tile: take another item
             cnt.paths++;
             pl.id[slot] = make_uint4(s.pixel_index, s.k, s.item, 0u);
-            U4 rj = rng_draw(P.seed, s.pixel_index, s.k, 0, RNG_JITTER, 0);
-            float x = (2 * ((int)pi + rng_uniform(rj.x)) / P.width - 1) * P.scale * P.ar;
-            float y = (1 - 2 * ((int)pj + rng_uniform(rj.y)) / P.height) * P.scale;
-            F3 cd = unit3(f3(-x, y, 1));
-            F3 wd = f3(P.inv_view[0] * cd.x + (P.inv_view[3] * cd.y + P.inv_view[6] * cd.z),
-                       P.inv_view[1] * cd.x + (P.inv_view[4] * cd.y + P.inv_view[7] * cd.z),
-                       P.inv_view[2] * cd.x + (P.inv_view[5] * cd.y + P.inv_view[8] * cd.z));
             s.ro = f3(P.eye[0], P.eye[1], P.eye[2]);
-            s.rd = unit3(wd); // Ray.cuh:13
+            s.rd = unit3(camera_dir(P, s.pixel_index, s.k, pi, pj)); // Ray.cuh:13
             s.tl = 0.0f; s.kind = RAY_CLOSEST;
             s.depth = 0; s.stage = ST_HIT; s.q = 0;
             cnt.rays++;

@@ -253,6 +253,37 @@ int crt_render_range_device(crt_scene* scene, const crt_camera* cam, const crt_p
 int crt_preview(crt_scene* scene, uint8_t* out_rgb, float* out_mean, uint32_t* samples_done);
 int crt_preview_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_stream, uint32_t* samples_done);
 
+/* First-hit auxiliary buffers (AOVs: the guides of a denoiser, depth and coverage for compositing, IDs for masks), aligned sample for
+ * sample with the frame crt_render draws with the same camera / params.  Per pixel, the S = params->spp camera rays of samples
+ * k = 0 .. S-1 -- the primary rays of the frame's paths: same seed, jitter draws and arithmetic -- are traced for their closest hit
+ * with params->traversal (EXACT, REFERENCE or FAST, as crt_intersect).  tri_k = the triangle sample k hits (BVH order), m_k its
+ * crt_triangle.material, t_k the hit distance along the unit direction, n_hit the number of samples that hit:
+ *   albedo   3 floats  a = a + kd(m_k) / S over the samples that hit, in sample order, from +0.0f (a miss adds nothing); kd = crt_material.kd
+ *   normal   3 floats  the same with the triangle's stored normal (crt_triangle.normal; not renormalised, not flipped)
+ *   depth    float     d = d + t_k over the hits in sample order, then d / (float)n_hit; 0.0f if n_hit = 0
+ *   coverage float     (float)n_hit / (float)S
+ *   tri      int32     tri_0 of sample 0, -1 if it missed
+ *   material int32     m_0 of sample 0, -1 if it missed
+ * IEEE divisions, no reciprocal multiply, no FMA.  Pixel order as crt_render's out_mean: row-major, or the compact 8x8 tiles of shard
+ * rank / world with CRT_FLAG_TILED_OUTPUT (padding slots: 0 and -1).  Ignored: p_rr, light_sample_n, CRT_FLAG_STATS, _TRACE_ALL and
+ * _BOUNDED_RADIANCE.  Any buffer may be NULL, not all six.  A null pointer, six NULL buffers, spp 0 or a size of 0 is
+ * CRT_ERR_INVALID_ARG, checked before any device call.  The rays are traced in chunks of whole samples of at most 2^25 rays (48 B each
+ * of the handle's query pool), so a pass never needs the frame's per-path storage.
+ * The AOV calls leave a progressive render in flight on the handle as it is: ranges with AOV calls in between give the one-shot frame.
+ * Render and AOV calls on one handle share its work buffers: calls with device outputs must be ordered by using one stream. */
+typedef struct { float* albedo; float* normal; float* depth; float* coverage; int32_t* tri; int32_t* material; } crt_aov_buffers;
+typedef struct {
+    uint64_t rays;     /* camera rays traced: spp x the shard's pixel slots (padding slots of ragged tiles included) */
+    uint32_t chunks;   /* trace launches (chunks of whole samples) */
+    float total_ms;    /* HIP-event time of the pass on its stream */
+} crt_aov_info;
+/* host_out: host buffers (W*H or slots elements of 3 or 1 values each); info optional */
+int crt_render_aov(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* host_out, crt_aov_info* info);
+/* dev_out: device buffers on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing, unless
+ * info != NULL (the call then synchronizes the stream to read the timer) */
+int crt_render_aov_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* dev_out,
+                          void* hip_stream, crt_aov_info* info);
+
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
  * (config_CUDA, src/main.cu:92-105); a crt_multi holds one device replica of the scene per entry of
@@ -400,6 +431,10 @@ int crt_image_load(const char* path, int32_t* x, int32_t* y, int32_t* comp, uint
 
 /* stb-free PNG writer used by Render::save_frame_buffer's replacement (Render.cuh:489-493) */
 int crt_write_png(const char* path, uint32_t width, uint32_t height, const uint8_t* rgb);
+/* Portable Float Map of width x height pixels of `channels` (1: "Pf", 3: "PF") floats, row 0 of `data` = image top: header
+ * "P?\n<width> <height>\n-1.0\n" (scale -1.0 = little-endian), then the rows bottom to top, as the format stores them.  The AOV
+ * buffers' depth / coverage (1 channel) or albedo / normal (3 channels). */
+int crt_write_pfm(const char* path, uint32_t width, uint32_t height, uint32_t channels, const float* data);
 
 #ifdef __cplusplus
 }

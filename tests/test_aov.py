@@ -1,0 +1,413 @@
+"""First-hit AOV pass (crt_render_aov / crt_render_aov_device, include/crt.h; Render.run_view_aov in Python; crt_cli --aov) and the
+PFM writer.
+
+The expected buffers come from the oracle: orc_render with p_rr = 0 under the ray log; the closest-hit rays that leave the eye are
+the primary rays of the frame's paths, logged pixel by pixel, sample by sample.  Their hits are folded in numpy float32 exactly as
+the contract says (a = a + kd / S over the hits in sample order, ...), and every buffer must match bit for bit.
+"""
+import ctypes as C
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import util
+
+NAMES = ("albedo", "normal", "depth", "coverage", "tri", "material")
+AOV_EXPORTS = ("crt_render_aov", "crt_render_aov_device", "crt_write_pfm")
+
+
+def read_pfm(path):
+    """(header lines, array with row 0 = image top) of a little-endian PFM, read with numpy alone."""
+    raw = open(path, "rb").read()
+    parts = raw.split(b"\n", 3)
+    kind, dims, scale, body = parts
+    w, h = (int(v) for v in dims.split())
+    ch = {b"PF": 3, b"Pf": 1}[kind]
+    a = np.frombuffer(body, dtype="<f4")
+    assert a.size == w * h * ch
+    a = a.reshape((h, w, ch) if ch == 3 else (h, w))
+    return (kind, dims, scale), np.ascontiguousarray(a[::-1])
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_aov_entry_points_are_exported():
+    lib = capi.lib()
+    for name in AOV_EXPORTS:
+        assert name in capi.EXPORTS
+        getattr(lib, name)
+    assert hasattr(crt, "write_pfm")
+
+
+def test_aov_arguments_are_checked_before_any_device_call():
+    """Every invalid call is CRT_ERR_INVALID_ARG, also on a machine without a GPU: the arguments are checked first.  A non-null
+    scene here is a dummy that must never be dereferenced."""
+    lib = capi.lib()
+    dummy = C.create_string_buffer(256)
+    sc = C.cast(dummy, C.c_void_p)
+    cam = capi.Camera()
+    good = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+    buf = np.zeros(64 * 48 * 3, dtype=np.float32)
+    bufs = capi.AovBuffers()
+    bufs.albedo = buf.ctypes.data
+    none = capi.AovBuffers()
+
+    def both(scene, camera, prm, b):
+        r1 = lib.crt_render_aov(scene, camera, prm, b, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_render_aov_device(scene, camera, prm, b, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == capi.ERR_INVALID_ARG, (r1, r2, e1, e2)
+        return e1
+
+    assert b"null" in both(None, C.byref(cam), C.byref(good), C.byref(bufs))
+    assert b"null" in both(sc, None, C.byref(good), C.byref(bufs))
+    assert b"null" in both(sc, C.byref(cam), None, C.byref(bufs))
+    assert b"null" in both(sc, C.byref(cam), C.byref(good), None)
+    assert b"no output" in both(sc, C.byref(cam), C.byref(good), C.byref(none))
+    for field, value in (("spp", 0), ("width", 0), ("height", 0)):
+        p = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+        setattr(p, field, value)
+        both(sc, C.byref(cam), C.byref(p), C.byref(bufs))
+    bad_shard = capi.Params(64, 48, 4, 0.6, 1, 0, 3, 3, capi.TRAVERSAL_EXACT, capi.FLAG_TILED_OUTPUT)
+    both(sc, C.byref(cam), C.byref(bad_shard), C.byref(bufs))
+    untiled = capi.Params(64, 48, 4, 0.6, 1, 0, 1, 3, capi.TRAVERSAL_EXACT, 0)
+    both(sc, C.byref(cam), C.byref(untiled), C.byref(bufs))
+    bad_mode = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, 7, 0)
+    both(sc, C.byref(cam), C.byref(bad_mode), C.byref(bufs))
+
+
+def test_write_pfm_round_trips(tmp_path):
+    rng = np.random.default_rng(5)
+    one = (rng.normal(size=(5, 7)) * 1e3).astype(np.float32)
+    one[0, 0], one[4, 6], one[2, 3] = np.inf, -0.0, np.float32(1e-42)
+    three = rng.normal(size=(4, 6, 3)).astype(np.float32)
+    lib = capi.lib()
+    for a, kind in ((one, b"Pf"), (three, b"PF")):
+        path = str(tmp_path / ("x%s.pfm" % kind.decode()))
+        ch = 1 if a.ndim == 2 else 3
+        capi.check(lib.crt_write_pfm(path.encode(), a.shape[1], a.shape[0], ch, capi.ptr(a)), "crt_write_pfm")
+        raw = open(path, "rb").read()
+        assert raw.startswith(kind + b"\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
+        hdr, back = read_pfm(path)
+        assert hdr == (kind, b"%d %d" % (a.shape[1], a.shape[0]), b"-1.0")
+        assert np.array_equal(back.view(np.uint32), a.view(np.uint32))
+        # bottom-up rows: the file's first row is the image's last
+        first = np.frombuffer(raw[len(raw) - a.nbytes:][:a.shape[1] * ch * 4], dtype="<f4")
+        assert np.array_equal(first.view(np.uint32), a[-1].reshape(-1).view(np.uint32))
+        path2 = str(tmp_path / "api.pfm")
+        crt.write_pfm(path2, a)
+        assert open(path2, "rb").read() == raw
+    assert lib.crt_write_pfm(str(tmp_path / "y.pfm").encode(), 7, 5, 2, capi.ptr(one)) == capi.ERR_INVALID_ARG
+    assert lib.crt_write_pfm(str(tmp_path / "y.pfm").encode(), 0, 5, 1, capi.ptr(one)) == capi.ERR_INVALID_ARG
+    assert lib.crt_write_pfm(None, 7, 5, 1, capi.ptr(one)) == capi.ERR_INVALID_ARG
+    assert lib.crt_write_pfm(str(tmp_path / "no" / "such" / "dir.pfm").encode(), 7, 5, 1, capi.ptr(one)) == -5
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in ("cornell-box", "veach-mis"):
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+def primary_rays(name, width, height, spp, crop=None, seed=0):
+    """The oracle's primary rays of a render (crop of a width x height frame): (origins, directions, t, tri) as (pixels, spp, ...)
+    arrays in pixel order, then sample order."""
+    sc = util.oracle_scene(name)
+    t = util.task(name)
+    eye, iv, fov = util.camera(name)
+    L = O.lib()
+    L.orc_ray_log_begin.restype = None
+    L.orc_ray_log_end.restype = C.c_uint64
+    L.orc_ray_log_end.argtypes = [C.c_void_p, C.c_uint64]
+    L.orc_ray_log_begin()
+    sc.render(eye, iv, fov, width, height, spp, 0.0, t.light_sample_n, seed=seed, crop=crop)
+    n = int(L.orc_ray_log_end(None, 0))
+    log = np.zeros((n, 10), dtype=np.float32)
+    L.orc_ray_log_end(log.ctypes.data_as(C.c_void_p), n)
+    eye32 = np.asarray(eye, dtype=np.float32)
+    keep = np.isnan(log[:, 8]) & np.all(log[:, 0:3].view(np.uint32) == eye32.view(np.uint32), axis=1)
+    prim = log[keep]
+    cw, ch = (crop[2], crop[3]) if crop else (width, height)
+    assert prim.shape[0] == cw * ch * spp
+    # (pixel, sample) order: with p_rr = 0 each path is its camera ray and that vertex's next-event samples, so the camera rays are
+    # the log's closest-hit rays from the eye, one path after the other
+    p = cw * ch
+    return (prim[:, 0:3].reshape(p, spp, 3), prim[:, 3:6].reshape(p, spp, 3), prim[:, 6].reshape(p, spp),
+            prim[:, 7].astype(np.int32).reshape(p, spp), (ch, cw))
+
+
+def expected_aov(name, width, height, spp, crop=None, seed=0):
+    """The contract of include/crt.h, restated in numpy float32 on the oracle's primary rays."""
+    _, _, t, tri, (ch, cw) = primary_rays(name, width, height, spp, crop, seed)
+    tris = util.oracle_scene(name).tris()
+    mat = util.host_scene(name).triangles()["material"].astype(np.int32)
+    p = tri.shape[0]
+    a = np.zeros((p, 3), dtype=np.float32)
+    nrm = np.zeros((p, 3), dtype=np.float32)
+    d = np.zeros(p, dtype=np.float32)
+    hits = np.zeros(p, dtype=np.int64)
+    fs = np.float32(spp)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        for k in range(spp):
+            hit = tri[:, k] >= 0
+            ti = np.where(hit, tri[:, k], 0)
+            a = np.where(hit[:, None], a + tris["kd"][ti].astype(np.float32) / fs, a)
+            nrm = np.where(hit[:, None], nrm + tris["normal"][ti].astype(np.float32) / fs, nrm)
+            d = np.where(hit, d + t[:, k], d)
+            hits += hit
+        depth = np.where(hits > 0, d / hits.astype(np.float32), np.float32(0.0)).astype(np.float32)
+    cov = (hits.astype(np.float32) / fs).astype(np.float32)
+    tri0 = tri[:, 0]
+    mat0 = np.where(tri0 >= 0, mat[np.maximum(tri0, 0)], -1).astype(np.int32)
+    return {"albedo": a.reshape(ch, cw, 3), "normal": nrm.reshape(ch, cw, 3), "depth": depth.reshape(ch, cw),
+            "coverage": cov.reshape(ch, cw), "tri": tri0.reshape(ch, cw), "material": mat0.reshape(ch, cw)}
+
+
+def assert_same(got, want, where=""):
+    for n in NAMES:
+        if n not in want:
+            continue
+        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
+        assert g.shape == w.shape, (n, g.shape, w.shape)
+        if g.dtype == np.float32:
+            same = g.view(np.uint32) == w.view(np.uint32)
+        else:
+            same = g == w
+        assert same.all(), "%s %s: %d of %d values differ" % (where, n, int((~same).sum()), same.size)
+
+
+def run_aov(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0):
+    eye, iv, fov = util.camera(name)
+    r.set_spp(spp)
+    r.seed = seed
+    r.traversal = traversal
+    try:
+        return r.run_view_aov(eye, iv, fov, width=width, height=height)
+    finally:
+        r.traversal = crt.TRAVERSAL_EXACT
+        r.seed = 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_aov_small_frames_match_oracle(renders, name):
+    got = run_aov(renders[name], name, 4, 64, 48)
+    assert renders[name].aov_info["chunks"] == 1 and renders[name].aov_info["rays"] == 64 * 48 * 4
+    want = expected_aov(name, 64, 48, 4)
+    assert_same(got, want, name)
+    assert (got["tri"] >= 0).any() and (got["coverage"] > 0).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,x0,y0", [("cornell-box", 388, 0), ("veach-mis", 400, 40)])
+def test_aov_crop_of_full_camera_in_chunks(renders, name, x0, y0):
+    """800 x 600 at spp 160: 7.7e7 camera rays, more than the 2^25-ray budget of a chunk, so the running sums cross chunks."""
+    spp = 160
+    got = run_aov(renders[name], name, spp)
+    info = renders[name].aov_info
+    assert info["chunks"] >= 2 and info["rays"] == 800 * 600 * spp, info
+    want = expected_aov(name, 800, 600, spp, crop=(x0, y0, 24, 16))
+    crop = {n: got[n][y0:y0 + 16, x0:x0 + 24] for n in NAMES}
+    assert_same(crop, want, name)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_aov_spp1_equals_intersect_on_the_logged_primary_rays(renders, name):
+    r = renders[name]
+    got = run_aov(r, name, 1, 64, 48)
+    o, d, _, _, _ = primary_rays(name, 64, 48, 1)
+    tri, t = r.intersect(o.reshape(-1, 3), d.reshape(-1, 3), traversal=crt.TRAVERSAL_EXACT | crt.INTERSECT_RAW_DIRECTIONS)
+    assert np.array_equal(got["tri"].reshape(-1), tri)
+    depth = np.where(tri >= 0, t, np.float32(0.0)).astype(np.float32)
+    assert np.array_equal(got["depth"].reshape(-1).view(np.uint32), depth.view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_aov_traversal_modes_agree(renders, name):
+    base = run_aov(renders[name], name, 4, 64, 48, seed=3)
+    for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST):
+        assert_same(run_aov(renders[name], name, 4, 64, 48, traversal=mode, seed=3), base, "%s mode %d" % (name, mode))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("var,value", [("CRT_PIPELINE", "2"), ("CRT_DEC", "0"), ("CRT_IMPL", "0"), ("CRT_REF16", "0")])
+def test_aov_kernel_variants_agree(renders, var, value, monkeypatch):
+    base = {n: run_aov(renders[n], n, 4, 64, 48) for n in renders}
+    monkeypatch.setenv(var, value)
+    for n in renders:
+        assert_same(run_aov(renders[n], n, 4, 64, 48), base[n], "%s %s=%s" % (n, var, value))
+
+
+@pytest.mark.gpu
+def test_aov_tiled_shards_deinterleave_to_row_major(renders):
+    from cudaraytracing_amd.distributed import untile_numpy
+    name, w, h, world, spp = "veach-mis", 100, 70, 3, 2
+    r = renders[name]
+    full = run_aov(r, name, spp, w, h)
+    eye, iv, fov = util.camera(name)
+    cam = r._cam(eye, iv, fov)
+    shards = {n: [] for n in NAMES}
+    for rank in range(world):
+        slots = crt.shard_slots(w, h, rank, world)
+        bufs, arrs = capi.AovBuffers(), {}
+        for n in NAMES:
+            ch, dt = capi.AOV_BUFFERS[n]
+            arrs[n] = np.full((slots, ch), 7, dtype=dt)  # (padding slots must come back as 0 / -1)
+            setattr(bufs, n, arrs[n].ctypes.data)
+        prm = r._params(rank=rank, world=world, flags=capi.FLAG_TILED_OUTPUT, width=w, height=h)
+        info = capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov(r._h, C.byref(cam), C.byref(prm), C.byref(bufs), C.byref(info)), "crt_render_aov")
+        assert info.rays == slots * spp and info.chunks == 1
+        for n in NAMES:
+            shards[n].append(arrs[n])
+    for n in NAMES:
+        img = untile_numpy(np.stack(shards[n]), w, h)
+        img = img if capi.AOV_BUFFERS[n][0] == 3 else img[:, :, 0]
+        assert_same({n: img}, {n: full[n]}, "tiled")
+        # padding slots: every slot of the gathered tiles that is no pixel
+        tx, ty = (w + 7) // 8, (h + 7) // 8
+        g = np.stack(shards[n])
+        lt = g.shape[1] // 64
+        for rank in range(world):
+            for s in range(g.shape[1]):
+                tile = (s // 64) * world + rank
+                i, j = (tile % tx) * 8 + (s % 64) % 8, (tile // tx) * 8 + (s % 64) // 8
+                if tile >= tx * ty or i >= w or j >= h:
+                    assert np.all(g[rank, s] == (-1 if n in ("tri", "material") else 0)), (n, rank, s)
+        assert lt * world >= tx * ty
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pipeline", ["4", "2"])
+def test_aov_calls_between_progressive_ranges(renders, pipeline, monkeypatch):
+    monkeypatch.setenv("CRT_PIPELINE", pipeline)
+    name = "cornell-box"
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    r.set_spp(4)
+    one = r.run_view(eye, iv, fov, width=64, height=48).copy()
+    one_mean = r.mean_buffer.copy()
+    aov = r.run_view_aov(eye, iv, fov, width=64, height=48)
+    assert r.run_view_range(eye, iv, fov, 0, 1, width=64, height=48) is None
+    assert_same(r.run_view_aov(eye, iv, fov, width=64, height=48), aov, "after range 0")
+    _, _, done = r.preview(width=64, height=48)
+    assert done == 1
+    assert r.run_view_range(eye, iv, fov, 1, 2, width=64, height=48) is None
+    r.run_view_aov(eye, iv, fov, width=32, height=24)  # another size in between
+    rgb = r.run_view_range(eye, iv, fov, 3, 1, width=64, height=48)
+    assert np.array_equal(rgb, one)
+    assert np.array_equal(r.mean_buffer.view(np.uint32), one_mean.view(np.uint32))
+
+
+def hip_runtime():
+    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
+    capi.lib()
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    H = C.CDLL(path)
+    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    H.hipFree.argtypes = [C.c_void_p]
+    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    H.hipStreamSynchronize.argtypes = [C.c_void_p]
+    H.hipStreamDestroy.argtypes = [C.c_void_p]
+    return H
+
+
+@pytest.mark.gpu
+def test_aov_device_form_on_a_stream_matches_host_form(renders):
+    name, w, h = "veach-mis", 80, 56
+    r = renders[name]
+    want = run_aov(r, name, 3, w, h)
+    eye, iv, fov = util.camera(name)
+    H = hip_runtime()
+    ptrs, sizes = {}, {}
+    stream = C.c_void_p()
+    try:
+        for n in NAMES:
+            sizes[n] = w * h * capi.AOV_BUFFERS[n][0] * 4
+            p = C.c_void_p()
+            assert H.hipMalloc(C.byref(p), sizes[n]) == 0
+            ptrs[n] = p.value
+            assert H.hipMemset(p, 0x55, sizes[n]) == 0  # (every value must be written by the pass)
+        assert H.hipStreamCreate(C.byref(stream)) == 0
+        assert r.run_view_aov_device(eye, iv, fov, ptrs, stream=stream.value, want_info=False, width=w, height=h) is None
+        assert H.hipStreamSynchronize(stream) == 0
+
+        def fetch(names):
+            out = {}
+            for n in names:
+                ch, dt = capi.AOV_BUFFERS[n]
+                a = np.zeros((h, w, ch) if ch == 3 else (h, w), dtype=dt)
+                assert H.hipMemcpy(a.ctypes.data, ptrs[n], sizes[n], 2) == 0  # hipMemcpyDeviceToHost
+                out[n] = a
+            return out
+
+        assert_same(fetch(NAMES), want, "device form")
+        # a subset of the buffers, with the pass's timer (the call synchronizes the stream)
+        assert H.hipMemset(C.c_void_p(ptrs["depth"]), 0, sizes["depth"]) == 0
+        info = r.run_view_aov_device(eye, iv, fov, {"depth": ptrs["depth"]}, stream=stream.value, width=w, height=h)
+        assert info["chunks"] == 1 and info["rays"] == w * h * 3 and info["total_ms"] > 0
+        assert_same(fetch(["depth"]), {"depth": want["depth"]}, "subset")
+    finally:
+        if stream.value:
+            H.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+def to_u8(v):
+    v = np.asarray(v, dtype=np.float32)
+    out = np.where(np.isnan(v) | (v <= 0), 0, np.where(v >= 255, 255, np.trunc(np.nan_to_num(v))))
+    return out.astype(np.uint8)
+
+
+@pytest.mark.gpu
+def test_cli_writes_aov_files(renders, tmp_path):
+    from PIL import Image
+    from cudaraytracing_amd import build as b
+    cli = b.build_cli()
+    prefix = str(tmp_path / "veach")
+    cfg = util.SCENES["veach-mis"]
+    res = subprocess.run([cli, cfg, "-o", prefix + ".png", "--spp", "2", "--width", "96", "--height", "72", "--seed", "42", "--base-dir", util.ROOT,
+                          "--aov", prefix], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    got = run_aov(renders["veach-mis"], "veach-mis", 2, 96, 72, seed=42)
+    one, two = np.float32(1.0), np.float32(2.0)
+    alb = to_u8(np.float32(255.0) * np.clip(got["albedo"], np.float32(0), np.float32(1)))
+    nrm = to_u8(np.float32(255.0) * np.clip((got["normal"] + one) / two, np.float32(0), np.float32(1)))
+    assert np.array_equal(np.asarray(Image.open(prefix + "_albedo.png")), alb)
+    assert np.array_equal(np.asarray(Image.open(prefix + "_normal.png")), nrm)
+    hdr, depth = read_pfm(prefix + "_depth.pfm")
+    assert hdr[0] == b"Pf" and hdr[2] == b"-1.0"
+    assert np.array_equal(depth.view(np.uint32), got["depth"].view(np.uint32))
+    bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--aov", prefix], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--aov" in bad.stderr
+
+
+@pytest.mark.gpu
+def test_multi_render_has_no_aov_pass():
+    m = crt.MultiRender(util.host_scene("cornell-box"), 2, devices=(0,), gather=crt.GATHER_COPY)
+    try:
+        eye, iv, fov = util.camera("cornell-box")
+        with pytest.raises(NotImplementedError):
+            m.run_view_aov(eye, iv, fov)
+        with pytest.raises(NotImplementedError):
+            m.run_view_aov_device(eye, iv, fov, {})
+    finally:
+        m.free()
