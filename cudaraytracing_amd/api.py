@@ -175,6 +175,8 @@ class Render:
         self.mean_buffer = None
         self.stats = None
         self.aov_info = None
+        self.aov_buffers = None
+        self.denoise_info = None
 
     def _handle(self, what):
         """The crt_scene* of this renderer; raises when there is none (freed, or a MultiRender, whose handle is a crt_multi*)."""
@@ -349,6 +351,19 @@ class Render:
             self.aov_info = info.as_dict()
         return self.aov_info if want_info else None
 
+    def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
+                          sigma_depth=None, width=None, height=None):
+        """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
+        run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
+        self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info."""
+        self._handle("run_view_denoised")
+        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height)
+        self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        rgb, mean, self.denoise_info = denoise(self.mean_buffer, iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal,
+                                               sigma_albedo=sigma_albedo, sigma_depth=sigma_depth, device=self.device, return_info=True,
+                                               **self.aov_buffers)
+        return rgb, mean
+
     def intersect(self, origins, dirs, traversal=None):
         self._handle("intersect")
         o = np.ascontiguousarray(origins, dtype=np.float32)
@@ -462,6 +477,9 @@ class MultiRender(Render):
     def run_view_aov_device(self, *a, **k):
         raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_device)")
 
+    def run_view_denoised(self, *a, **k):
+        raise NotImplementedError("the denoiser is a single-device interface (crt_denoise): gather the frame first")
+
     def intersect(self, *a, **k):
         raise NotImplementedError("crt_intersect is a single-device interface")
 
@@ -495,6 +513,72 @@ def write_pfm(path, data):
         raise ValueError("write_pfm needs an (H, W) or (H, W, 3) array, got %r" % (a.shape,))
     ch = 1 if a.ndim == 2 else a.shape[2]
     capi.check(capi.lib().crt_write_pfm(os.fsencode(path), a.shape[1], a.shape[0], ch, capi.ptr(a)), "crt_write_pfm")
+
+
+def denoise_defaults():
+    """crt_denoise_defaults as a dict: iterations and the four sigmas."""
+    p = capi.DenoiseParams()
+    capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
+    return {n: getattr(p, n) for n, _ in p._fields_ if n not in ("width", "height")}
+
+
+def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth):
+    p = capi.DenoiseParams()
+    capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
+    p.width, p.height = int(width), int(height)
+    for name, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo),
+                    ("sigma_depth", sigma_depth)):
+        if v is not None:
+            setattr(p, name, int(v) if name == "iterations" else float(v))
+    return p
+
+
+def denoise_scratch_bytes(width, height):
+    n = C.c_uint64()
+    capi.check(capi.lib().crt_denoise_scratch_bytes(width, height, C.byref(n)), "crt_denoise_scratch_bytes")
+    return int(n.value)
+
+
+def denoise(color, albedo=None, normal=None, depth=None, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
+            sigma_depth=None, device=0, want_rgb=True, return_info=False):
+    """AOV-guided edge-avoiding a-trous filter (crt_denoise, contract: include/crt.h) of an (H, W, 3) float32 image of pre-tone-map
+    radiance; albedo, normal (H, W, 3) and depth (H, W) are optional guides, None settings take crt_denoise_defaults.  Returns
+    (rgb, mean): the RGB8 tone map (None without want_rgb) and the filtered radiance; with return_info also the crt_denoise_info dict."""
+    c = np.ascontiguousarray(color, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise needs an (H, W, 3) colour image, got %r" % (c.shape,))
+    h, w = c.shape[:2]
+    inputs, keep = capi.DenoiseInputs(), [c]
+    inputs.color = c.ctypes.data
+    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("denoise: %s has shape %r, expected %r" % (name, a.shape, shape))
+        keep.append(a)
+        setattr(inputs, name, a.ctypes.data)
+    prm = _denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
+    mean = np.zeros((h, w, 3), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), C.byref(info)), "crt_denoise")
+    return (rgb, mean, info.as_dict()) if return_info else (rgb, mean)
+
+
+def denoise_device(width, height, color_ptr, out_mean_ptr, out_rgb_ptr, scratch_ptr, scratch_bytes, albedo_ptr=None, normal_ptr=None,
+                   depth_ptr=None, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None, sigma_depth=None, device=0,
+                   stream=None, want_info=True):
+    """Enqueues the filter with everything in device memory (raw device pointers, crt_denoise_device); the caller owns the scratch
+    (denoise_scratch_bytes).  With want_info the call synchronizes the stream and returns the crt_denoise_info dict, else None."""
+    inputs = capi.DenoiseInputs(color_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
+    prm = _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
+                                             C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None, C.c_void_p(scratch_ptr) if scratch_ptr else None,
+                                             int(scratch_bytes), C.c_void_p(stream) if stream else None,
+                                             C.byref(info) if want_info else None), "crt_denoise_device")
+    return info.as_dict() if want_info else None
 
 
 def shard_slots(width, height, rank, world):

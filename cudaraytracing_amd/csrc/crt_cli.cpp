@@ -7,6 +7,10 @@
 //   crt_cli <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
+//           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d]
+// --denoise PATH renders as usual, then filters the frame with the AOV-guided a-trous denoiser (crt_denoise, one device) and writes the
+// result as a PNG to PATH; -o and --aov outputs are unchanged by it.  --denoise-iterations (1 .. 5) and --denoise-sigma (colour, normal,
+// albedo, depth) override crt_denoise_defaults.
 // --aov PREFIX also writes the first-hit AOVs of the frame (crt_render_aov, one device): PREFIX_albedo.png (8-bit, 255 x clamp(a, 0, 1)
 // truncated, no gamma), PREFIX_normal.png (255 x clamp((n + 1) / 2, 0, 1)) and PREFIX_depth.pfm (floats).
 // --gpus N renders on devices 0..N-1 of this node in one process (crt_multi: interleaved pixel tiles, one RCCL all-gather);
@@ -26,13 +30,16 @@ int main(int argc, char** argv)
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
-                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n", argv[0]);
+                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
+                             "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d]\n", argv[0]);
         return 2;
     }
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov;
+        std::string out = "out.png", base_dir = ".", aov, denoise;
+        crt_denoise_params dn;
+        crt_denoise_defaults(&dn);
         uint64_t seed = 0;
         int device = 0;
         bool reference = false, exact = false, fast = false, bounded = false;
@@ -73,6 +80,19 @@ int main(int argc, char** argv)
             }
             else if (a == "--base-dir") { need(i, 1); base_dir = argv[++i]; }
             else if (a == "--aov") { need(i, 1); aov = argv[++i]; }
+            else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
+            else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); }
+            else if (a == "--denoise-sigma") {
+                need(i, 1);
+                float* dst[4] = {&dn.sigma_color, &dn.sigma_normal, &dn.sigma_albedo, &dn.sigma_depth};
+                const char* q = argv[++i];
+                for (int k = 0; k < 4; k++) {
+                    char* end = nullptr;
+                    *dst[k] = std::strtof(q, &end);
+                    if (end == q || (k < 3 ? *end != ',' : *end != 0)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-sigma needs four comma-separated values: colour,normal,albedo,depth");
+                    q = end + 1;
+                }
+            }
             else if (a == "--reference") reference = true;
             else if (a == "--exact") exact = true;
             else if (a == "--fast") fast = true;
@@ -90,6 +110,7 @@ int main(int argc, char** argv)
                     scene.get_light_objs().size());
         const bool multi = !devices.empty();
         if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
+        if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
         crt::Render render_one_or_many = multi ? crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, devices, gather)
                                                : crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, device);
         crt::Render& render = render_one_or_many;
@@ -114,8 +135,8 @@ int main(int argc, char** argv)
         }
         render.save_frame_buffer(out.c_str());
         std::printf("%s\n", out.c_str());
+        if (!aov.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
         if (!aov.empty()) {
-            render.run_aov(task.eye_pos, inv_view, fov_y);
             const crt_aov_info& ai = render.last_aov_info();
             std::printf("aov: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
             const size_t n = (size_t)task.width * task.height;
@@ -133,6 +154,13 @@ int main(int argc, char** argv)
             if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_depth_buffer());
             if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the AOV files failed: ") + crt_last_error());
             std::printf("%s\n%s\n%s\n", pa.c_str(), pn.c_str(), pd.c_str());
+        }
+        if (!denoise.empty()) {
+            render.run_denoise(dn);
+            const crt_denoise_info& di = render.last_denoise_info();
+            std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);
+            render.save_denoised_buffer(denoise.c_str());
+            std::printf("%s\n", denoise.c_str());
         }
         render.free();
         return 0;

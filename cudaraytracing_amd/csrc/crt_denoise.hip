@@ -1,0 +1,263 @@
+// cudaraytracing_amd/csrc/crt_denoise.hip -- the AOV-guided edge-avoiding a-trous filter (crt_denoise / crt_denoise_device, contract:
+// include/crt.h): kernels and host code.  An image operation without a scene handle.
+//
+// One call = k_denoise_pack (colour and guides into four float4 planes of the caller's scratch: a colour ping-pong pair, (normal.xyz,
+// depth) and (albedo.xyz, 0) -- three 16-byte loads per tap, coalesced along a row whatever the spacing) and one filter launch per pass.
+// A pass is one thread per pixel, 25 taps in the contract's order, every tap read from global memory through the caches; the last pass
+// writes out_mean and the tone-mapped RGB8 itself.  (A form that staged the tile and its halo in LDS for spacing 1 and 2 was measured and
+// dropped: the pass is bound by vector-ALU issue, not by its loads -- docs/experiments.md, "The a-trous denoiser".)
+#include "crt_internal.h"
+
+#include <cstring>
+#include <string>
+
+namespace crtk {
+
+struct DnParams {
+    uint32_t width, height, tiles_x;
+    float sig2_c, sig2_n, sig2_a, sigma_d;   // sig * sig of the pass, sigma_normal^2, sigma_albedo^2 (1 for a NULL guide: 0 / 1 = +0), sigma_depth
+    const float4* c_in;                       // c_i: (r, g, b, -)
+    const float4* g0;                         // (normal.xyz, depth); zeros for NULL guides
+    const float4* g1;                         // (albedo.xyz, 0)
+    float4* c_out;                            // c_{i+1}; not written by the last pass
+    float* out_mean;                          // last pass only (either may be null)
+    uint8_t* out_rgb;
+    uint32_t last;
+};
+
+struct DnPack {
+    uint64_t npix;
+    const float* color; const float* albedo; const float* normal; const float* depth;
+    float4* c0; float4* g0; float4* g1;
+};
+
+__global__ __launch_bounds__(256) void k_denoise_pack(const DnPack K)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= K.npix) return;
+    K.c0[p] = make_float4(K.color[p * 3], K.color[p * 3 + 1], K.color[p * 3 + 2], 0.0f);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (K.normal) { g.x = K.normal[p * 3]; g.y = K.normal[p * 3 + 1]; g.z = K.normal[p * 3 + 2]; }
+    if (K.depth) g.w = K.depth[p];
+    if (K.albedo) { a.x = K.albedo[p * 3]; a.y = K.albedo[p * 3 + 1]; a.z = K.albedo[p * 3 + 2]; }
+    K.g0[p] = g;
+    K.g1[p] = a;
+}
+
+struct DnSum { float x, y, z, den; };
+
+// one tap of the contract (include/crt.h), operation by operation; hw = h[dy+2] * h[dx+2]
+__device__ __forceinline__ void dn_tap(const DnParams& P, const float4 cp, const float4 gp, const float4 ap, const float4 cq, const float4 gq,
+                                       const float4 aq, const float hw, DnSum& s)
+{
+    const float dcx = cp.x - cq.x, dcy = cp.y - cq.y, dcz = cp.z - cq.z;
+    const float e_c = (dcx * dcx + dcy * dcy + dcz * dcz) / P.sig2_c;
+    const float dnx = gp.x - gq.x, dny = gp.y - gq.y, dnz = gp.z - gq.z;
+    const float e_n = (dnx * dnx + dny * dny + dnz * dnz) / P.sig2_n;
+    const float dax = ap.x - aq.x, day = ap.y - aq.y, daz = ap.z - aq.z;
+    const float e_a = (dax * dax + day * day + daz * daz) / P.sig2_a;
+    const float m = gp.w > gq.w ? gp.w : gq.w;
+    const float r = (gp.w - gq.w) / (P.sigma_d * m);
+    const float e_d = m > 0.0f ? r * r : 0.0f;
+    const float w = hw * det_expf(-(((e_c + e_n) + e_a) + e_d));
+    s.x = s.x + cq.x * w;
+    s.y = s.y + cq.y * w;
+    s.z = s.z + cq.z * w;
+    s.den = s.den + w;
+}
+
+__device__ __forceinline__ float dn_h(const int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
+
+__device__ __forceinline__ void dn_write(const DnParams& P, const size_t p, const DnSum& s)
+{
+    const float cx = s.x / s.den, cy = s.y / s.den, cz = s.z / s.den;
+    if (!P.last) { P.c_out[p] = make_float4(cx, cy, cz, 0.0f); return; }
+    if (P.out_mean) { P.out_mean[p * 3] = cx; P.out_mean[p * 3 + 1] = cy; P.out_mean[p * 3 + 2] = cz; }
+    if (P.out_rgb) { P.out_rgb[p * 3] = tonemap(cx); P.out_rgb[p * 3 + 1] = tonemap(cy); P.out_rgb[p * 3 + 2] = tonemap(cz); }
+}
+
+// Block = 64 x 4 pixels, a wave = 64 consecutive pixels of one row.
+__global__ __launch_bounds__(256) void k_denoise_pass(const DnParams P, const int step)
+{
+    const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
+    const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
+    const int W = (int)P.width, H = (int)P.height;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * P.width + (size_t)x;
+    const float4 cp = P.c_in[p], gp = P.g0[p], ap = P.g1[p];
+    DnSum s = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * step;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * step;
+            if (qx < 0 || qx >= W) continue;
+            const size_t q = (size_t)qy * P.width + (size_t)qx;
+            dn_tap(P, cp, gp, ap, P.c_in[q], P.g0[q], P.g1[q], dn_h(dy) * dn_h(dx), s);
+        }
+    }
+    dn_write(P, p, s);
+}
+
+} // namespace crtk
+
+using namespace crtk;
+
+namespace {
+
+int fail(int status, const std::string& msg)
+{
+    crt_set_last_error_(msg.c_str());
+    return status;
+}
+int fail_hip(const HipFail& f) { return fail(CRT_ERR_HIP, std::string(f.what) + ": " + hipGetErrorString(f.e)); }
+
+const uint32_t kMaxSide = 1u << 24;
+bool sigma_ok(float s) { return s > 0.0f; } // (false for NaN)
+
+// Argument checks of both forms, before any device call
+int denoise_check(const char* who, const crt_denoise_params* prm, const crt_denoise_inputs* in, const void* out_mean, const void* out_rgb)
+{
+    const std::string w(who);
+    if (!prm || !in) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
+    if (!in->color) return fail(CRT_ERR_INVALID_ARG, w + ": null colour buffer");
+    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (prm->iterations < 1 || prm->iterations > 5) return fail(CRT_ERR_INVALID_ARG, w + ": iterations must be 1 .. 5");
+    if (!sigma_ok(prm->sigma_color) || !sigma_ok(prm->sigma_normal) || !sigma_ok(prm->sigma_albedo) || !sigma_ok(prm->sigma_depth))
+        return fail(CRT_ERR_INVALID_ARG, w + ": every sigma must be > 0 (+inf switches a term off)");
+    if (!out_mean && !out_rgb) return fail(CRT_ERR_INVALID_ARG, w + ": no output buffer");
+    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
+    if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
+    return CRT_OK;
+}
+
+uint64_t scratch_bytes_of(uint32_t width, uint32_t height) { return (uint64_t)width * height * 4u * sizeof(float4); }
+
+int denoise_impl(int device, const crt_denoise_params* prm, const crt_denoise_inputs* in, void* d_out_mean, void* d_out_rgb, void* d_scratch,
+                 uint64_t scratch_bytes, hipStream_t st, crt_denoise_info* info)
+{
+    const int rc = denoise_check("crt_denoise_device", prm, in, d_out_mean, d_out_rgb);
+    if (rc != CRT_OK) return rc;
+    if (!d_scratch) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: null scratch buffer");
+    if (scratch_bytes < scratch_bytes_of(prm->width, prm->height))
+        return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: scratch buffer too small (crt_denoise_scratch_bytes)");
+    if ((uintptr_t)d_scratch % sizeof(float4) != 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: scratch buffer not 16-byte aligned");
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: device index out of range");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int status = CRT_OK;
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        if (info) {
+            HIP_CHECK(hipEventCreate(&e0));
+            HIP_CHECK(hipEventCreate(&e1));
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        const uint64_t npix = (uint64_t)prm->width * prm->height;
+        float4* plane = (float4*)d_scratch;
+        float4* c[2] = {plane, plane + npix};
+        DnPack K;
+        K.npix = npix;
+        K.color = in->color; K.albedo = in->albedo; K.normal = in->normal; K.depth = in->depth;
+        K.c0 = c[0]; K.g0 = plane + 2 * npix; K.g1 = plane + 3 * npix;
+        hipLaunchKernelGGL(k_denoise_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, K);
+        HIP_CHECK(hipGetLastError());
+        DnParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.width = prm->width; P.height = prm->height;
+        P.sig2_n = in->normal ? prm->sigma_normal * prm->sigma_normal : 1.0f;
+        P.sig2_a = in->albedo ? prm->sigma_albedo * prm->sigma_albedo : 1.0f;
+        P.sigma_d = prm->sigma_depth;
+        P.g0 = K.g0; P.g1 = K.g1;
+        P.tiles_x = (prm->width + 63) / 64;
+        for (uint32_t i = 0; i < prm->iterations; i++) {
+            const float sig = prm->sigma_color / (float)(1 << i);
+            P.sig2_c = sig * sig;
+            P.c_in = c[i & 1]; P.c_out = c[(i + 1) & 1];
+            P.last = i + 1 == prm->iterations;
+            P.out_mean = P.last ? (float*)d_out_mean : nullptr;
+            P.out_rgb = P.last ? (uint8_t*)d_out_rgb : nullptr;
+            hipLaunchKernelGGL(k_denoise_pass, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P, 1 << i);
+            HIP_CHECK(hipGetLastError());
+        }
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            std::memset(info, 0, sizeof(*info));
+            info->passes = prm->iterations;
+            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
+        }
+    } catch (const HipFail& f) {
+        status = fail_hip(f);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return status;
+}
+
+} // namespace
+
+extern "C" {
+
+int crt_denoise_defaults(crt_denoise_params* prm)
+{
+    if (!prm) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_defaults: null argument");
+    std::memset(prm, 0, sizeof(*prm));
+    prm->iterations = 3;
+    prm->sigma_color = 4.0f; prm->sigma_normal = 0.5f; prm->sigma_albedo = 0.1f; prm->sigma_depth = 0.05f;
+    return CRT_OK;
+}
+
+int crt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes)
+{
+    if (!bytes || width == 0 || height == 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_scratch_bytes: bad arguments");
+    *bytes = scratch_bytes_of(width, height);
+    return CRT_OK;
+}
+
+int crt_denoise_device(int device, const crt_denoise_params* prm, const crt_denoise_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
+                       void* d_scratch, uint64_t scratch_bytes, void* stream, crt_denoise_info* info)
+{
+    return denoise_impl(device, prm, dev_in, d_out_mean, d_out_rgb, d_scratch, scratch_bytes, (hipStream_t)stream, info);
+}
+
+int crt_denoise(int device, const crt_denoise_params* prm, const crt_denoise_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                crt_denoise_info* info)
+{
+    const int rc0 = denoise_check("crt_denoise", prm, host_in, out_mean, out_rgb);
+    if (rc0 != CRT_OK) return rc0;
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise: device index out of range");
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t npix = (uint64_t)prm->width * prm->height;
+        DevBuf<float> d_color, d_albedo, d_normal, d_depth, d_mean;
+        DevBuf<uint8_t> d_rgb;
+        DevBuf<float4> d_scratch;
+        crt_denoise_inputs d{};
+        auto up = [&](DevBuf<float>& b, const float* h, uint64_t n) -> const float* {
+            if (!h) return nullptr;
+            b.alloc(n);
+            HIP_CHECK(hipMemcpy(b.p, h, n * sizeof(float), hipMemcpyHostToDevice));
+            return b.p;
+        };
+        d.color = up(d_color, host_in->color, npix * 3);
+        d.albedo = up(d_albedo, host_in->albedo, npix * 3);
+        d.normal = up(d_normal, host_in->normal, npix * 3);
+        d.depth = up(d_depth, host_in->depth, npix);
+        if (out_mean) d_mean.alloc(npix * 3);
+        if (out_rgb) d_rgb.alloc(npix * 3);
+        d_scratch.alloc(npix * 4);
+        const int rc = denoise_impl(device, prm, &d, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr, d_scratch.p,
+                                    npix * 4 * sizeof(float4), nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out_mean) HIP_CHECK(hipMemcpy(out_mean, d_mean.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, d_rgb.p, npix * 3, hipMemcpyDeviceToHost));
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+} // extern "C"

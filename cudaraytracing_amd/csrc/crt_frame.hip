@@ -4,20 +4,6 @@
 
 namespace crtk {
 
-__device__ __forceinline__ uint8_t to_u8(float v)
-{
-    if (!(v == v)) return 0;
-    if (v <= 0.0f) return 0;
-    if (v >= 255.0f) return 255;
-    return (uint8_t)v; // truncation (Render.cuh:350)
-}
-// reference: Global.h:121-124 then Render.cuh:350
-__device__ __forceinline__ uint8_t tonemap(float c)
-{
-    float cl = maxf_ref(0.0f, minf_ref(1.0f, c));
-    return to_u8(255 * det_powf(cl, 0.6f));
-}
-
 __device__ __forceinline__ FastDiv make_fastdiv_dev(uint32_t d)
 {
     // k_accumulate runs once per pixel: derive the magic on the fly (same formula as make_fastdiv)

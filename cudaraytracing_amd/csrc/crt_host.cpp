@@ -604,7 +604,7 @@ void load_task_scene(const crt_task& task, Scene& scene, const std::string& base
 
 // ------------------------------------------------------------------ Render --
 Render::Render(Scene* scene, unsigned spp, float P_RR, unsigned light_sample_n, int device)
-    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR)
+    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR), device_(device)
 {
     if (!scene) throw Error(CRT_ERR_INVALID_ARG, "Render: null scene");
     const crt_scene_desc& d = scene->flat();
@@ -696,6 +696,29 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data();
     const int rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
+}
+
+void Render::run_denoise(const crt_denoise_params& prm)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise: the denoiser is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise after free()");
+    const size_t n = scene_->get_pixels();
+    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
+        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise needs run_view and run_aov of this frame size first");
+    crt_denoise_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    crt_denoise_inputs in{};
+    in.color = mean_buffer_.data(); in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    const int rc = crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), &denoise_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise failed: ") + crt_last_error());
+}
+
+void Render::save_denoised_buffer(const char* save_path) const
+{
+    if (denoised_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_denoised_buffer before run_denoise");
+    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), denoised_buffer_.data());
+    if (rc != CRT_OK) throw Error(rc, std::string("save_denoised_buffer failed: ") + crt_last_error());
 }
 
 void Render::save_frame_buffer(const char* save_path) const

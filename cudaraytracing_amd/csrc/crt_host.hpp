@@ -220,6 +220,13 @@ public:
     const float* get_normal_buffer() const { return normal_buffer_.data(); } // W x H x 3
     const float* get_depth_buffer() const { return depth_buffer_.data(); }   // W x H
     const crt_aov_info& last_aov_info() const { return aov_info_; }
+    // the frame of the last run_view filtered by crt_denoise with the albedo, normal and depth of the last run_aov as guides (call both
+    // first, with the same camera); prm: crt_denoise_defaults with overrides, its width and height are set here; one device only
+    void run_denoise(const crt_denoise_params& prm);
+    const unsigned char* get_denoised_buffer() const { return denoised_buffer_.data(); } // W x H x 3 RGB8
+    const float* get_denoised_mean_buffer() const { return denoised_mean_buffer_.data(); } // W x H x 3
+    const crt_denoise_info& last_denoise_info() const { return denoise_info_; }
+    void save_denoised_buffer(const char* save_path) const;
     void free();
     void save_frame_buffer(const char* save_path) const;
     unsigned char* get_frame_buffer() const { return const_cast<unsigned char*>(frame_buffer_.data()); }
@@ -251,6 +258,10 @@ private:
     std::vector<unsigned char> frame_buffer_;
     std::vector<float> mean_buffer_;
     std::vector<float> albedo_buffer_, normal_buffer_, depth_buffer_;
+    std::vector<unsigned char> denoised_buffer_;
+    std::vector<float> denoised_mean_buffer_;
+    int device_ = 0;
+    crt_denoise_info denoise_info_{};
     crt_stats stats_{};
     crt_aov_info aov_info_{};
 };

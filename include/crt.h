@@ -284,6 +284,54 @@ int crt_render_aov(crt_scene* scene, const crt_camera* cam, const crt_params* pa
 int crt_render_aov_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* dev_out,
                           void* hip_stream, crt_aov_info* info);
 
+/* AOV-guided edge-avoiding denoiser: an a-trous ("with holes") wavelet filter with edge-stopping weights on colour, normal, albedo and
+ * depth (Dammertz et al. 2010), run as `iterations` passes over a frame's pre-tone-map mean radiance (out_mean of crt_render), guided by
+ * the buffers crt_render_aov returns.  An image operation: no scene handle.  Row-major images of width x height; color, albedo, normal
+ * 3 floats per pixel, depth 1 float per pixel.  c_0 = color.  Pass i = 0 .. iterations-1 has tap spacing s = 2^i and computes c_{i+1}
+ * from c_i.  For pixel p = (x, y) the 25 taps q = (x + dx*s, y + dy*s) are visited with dy = -2..2 outer, dx = -2..2 inner; a tap outside
+ * the image is skipped (nothing is added for it).  With h = {1/16, 1/4, 3/8, 1/4, 1/16} (exact in fp32):
+ *   sig  = sigma_color / (float)(1 << i)
+ *   dc   = c_i(p) - c_i(q)            e_c = (dc.x*dc.x + dc.y*dc.y + dc.z*dc.z) / (sig * sig)
+ *   dn   = normal(p) - normal(q)      e_n = (dn.x*dn.x + dn.y*dn.y + dn.z*dn.z) / (sigma_normal * sigma_normal)
+ *   da   = albedo(p) - albedo(q)      e_a = (da.x*da.x + da.y*da.y + da.z*da.z) / (sigma_albedo * sigma_albedo)
+ *   m    = depth(p) > depth(q) ? depth(p) : depth(q)
+ *   r    = (depth(p) - depth(q)) / (sigma_depth * m)      e_d = m > 0 ? r * r : 0      (relative depth; depth 0 = a miss)
+ *   w    = (h[dy+2] * h[dx+2]) * exp(-(((e_c + e_n) + e_a) + e_d))                     (exp: det_expf of csrc/crt_detmath.h)
+ *   num  = num + c_i(q) * w   (per channel)               den = den + w
+ *   c_{i+1}(p) = num / den    (per channel)
+ * num and den start at +0.0f; sums are left to right as written; every * + - / is one IEEE fp32 operation (no FMA, no reciprocal
+ * multiply).  A guide pointer that is NULL makes its term +0.0f (color is required).  iterations is 1 .. 5.  Each sigma must be > 0 and
+ * not NaN; +inf is allowed and switches its term off.  Non-finite inputs are not special-cased: the arithmetic above defines the result
+ * (exp(NaN) is NaN, exp(x < -87) is exactly 0).  Outputs: c_iterations as out_mean (3 floats per pixel) and / or its RGB8 tone map
+ * out_rgb (3 bytes per pixel: the bits crt_render writes for that mean); either may be NULL, not both.
+ * crt_denoise_defaults fills iterations 3, sigma_color 4, sigma_normal 0.5, sigma_albedo 0.1, sigma_depth 0.05 (width and height 0):
+ * the best of a small sweep on 160x120 spp 8 frames of the two shipped scenes and nothing larger.
+ * A null pointer, a size of 0, iterations outside 1 .. 5, a sigma that is not > 0, two NULL outputs or a scratch buffer that is missing,
+ * too small or not 16-byte aligned is CRT_ERR_INVALID_ARG, checked before any device call.  (A side longer than 2^24 pixels:
+ * CRT_ERR_UNSUPPORTED.) */
+typedef struct {
+    uint32_t width, height;
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_albedo, sigma_depth;
+} crt_denoise_params;
+typedef struct { const float* color; const float* albedo; const float* normal; const float* depth; } crt_denoise_inputs;
+typedef struct {
+    float total_ms;    /* HIP-event time of the call's kernels on its stream */
+    uint32_t passes;   /* filter passes that ran (= iterations) */
+} crt_denoise_info;
+int crt_denoise_defaults(crt_denoise_params* params);
+/* bytes of device scratch crt_denoise_device needs for a width x height image: 64 B per pixel (the colour ping-pong pair and the two
+ * packed guide planes, 16 B per pixel each) */
+int crt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_denoise(int device, const crt_denoise_params* params, const crt_denoise_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                crt_denoise_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then synchronizes the stream to read the timer).  The caller owns d_scratch (scratch_bytes >= crt_denoise_scratch_bytes),
+ * so frames can be pipelined without allocation.  Outputs must not overlap inputs or scratch. */
+int crt_denoise_device(int device, const crt_denoise_params* params, const crt_denoise_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
+                       void* d_scratch, uint64_t scratch_bytes, void* hip_stream, crt_denoise_info* info);
+
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
  * (config_CUDA, src/main.cu:92-105); a crt_multi holds one device replica of the scene per entry of
