@@ -17,6 +17,7 @@ FLAG_TILED_OUTPUT = 2
 FLAG_FORCE_EXACT = 4
 FLAG_TRACE_ALL = 8
 FLAG_BOUNDED_RADIANCE = 16
+FLAG_VARIANCE = 32
 GATHER_AUTO, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 INTERSECT_RAW_DIRECTIONS, INTERSECT_FORCE_EXACT, INTERSECT_VISIBILITY = 0x100, 0x200, 0x400
 TILE = 8
@@ -136,6 +137,10 @@ class DenoiseInputs(C.Structure):
     _fields_ = [("color", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
 
 
+class DenoiseVarInputs(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("variance", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
 class DenoiseInfo(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("passes", C.c_uint32)]
 
@@ -165,7 +170,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
-           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_multi_create", "crt_multi_destroy",
+           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
@@ -207,6 +212,8 @@ def lib():
     L.crt_radiance_storage.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     L.crt_preview.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.crt_preview_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.crt_variance.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.crt_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.crt_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovInfo)]
     L.crt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.c_void_p,
                                         C.POINTER(AovInfo)]
@@ -215,6 +222,11 @@ def lib():
     L.crt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.POINTER(DenoiseInfo)]
     L.crt_denoise_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                      C.c_void_p, C.POINTER(DenoiseInfo)]
+    L.crt_denoise_var_defaults.argtypes = [C.POINTER(DenoiseParams)]
+    L.crt_denoise_var.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(DenoiseInfo)]
+    L.crt_denoise_var_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(DenoiseInfo)]
     L.crt_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.crt_multi_destroy.argtypes = [C.c_void_p]
     L.crt_multi_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats),

@@ -177,6 +177,7 @@ class Render:
         self.aov_info = None
         self.aov_buffers = None
         self.denoise_info = None
+        self.variance_buffer = None
 
     def _handle(self, what):
         """The crt_scene* of this renderer; raises when there is none (freed, or a MultiRender, whose handle is a crt_multi*)."""
@@ -235,12 +236,14 @@ class Render:
         return capi.Params(width or self.scene.width, height or self.scene.height, self.spp, float(self.P_RR),
                            self.light_sample_n, self.seed, rank, world, self.traversal, flags)
 
-    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None):
-        """Renders the whole frame; returns the RGB8 frame buffer (H, W, 3)."""
+    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False):
+        """Renders the whole frame; returns the RGB8 frame buffer (H, W, 3).  want_variance: render with FLAG_VARIANCE (the frame is
+        the same bits) and leave the per-pixel variance of the mean, (H, W, 3) float32 (crt_variance), in self.variance_buffer."""
         if not self._h:
             raise RuntimeError("Render.run_view after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | self.extra_flags, width=width, height=height)
+        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags,
+                           width=width, height=height)
         w, h = prm.width, prm.height
         rgb = np.zeros((h, w, 3), dtype=np.uint8)
         mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
@@ -248,16 +251,28 @@ class Render:
         capi.check(capi.lib().crt_render(self._h, C.byref(cam), C.byref(prm), capi.ptr(rgb), capi.ptr(mean),
                                          C.byref(st)), "crt_render")
         self.frame_buffer, self.mean_buffer, self.stats = rgb, mean, st.as_dict()
+        self.variance_buffer = self.variance(width=w, height=h)[0] if want_variance else None
         return rgb
 
-    def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None):
+    def variance(self, width=None, height=None):
+        """(var (H, W, 3) float32, samples done) of crt_variance: the estimated variance of the mean the frame -- or, between the ranges
+        of a progressive render, the preview -- shows, from the sums a render with want_variance keeps on the handle.  Reads only."""
+        h_ = self._handle("variance")
+        w, h = width or self.scene.width, height or self.scene.height
+        var = np.zeros((h, w, 3), dtype=np.float32)
+        done = C.c_uint32(0)
+        capi.check(capi.lib().crt_variance(h_, capi.ptr(var), C.byref(done)), "crt_variance")
+        return var, int(done.value)
+
+    def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
+                       want_variance=False):
         """Progressive rendering: adds samples [sample_begin, sample_begin + sample_count) of the spp samples per pixel to the
         accumulator of the device scene; ranges go in ascending order from 0.  Returns the RGB8 frame once the range that ends
         at spp has been rendered (bit-identical to run_view), None before."""
         if not self._h:
             raise RuntimeError("Render.run_view_range after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        prm = self._params(flags=(capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags, width=width, height=height)
         w, h = prm.width, prm.height
         last = sample_begin + sample_count == self.spp
         rgb = np.zeros((h, w, 3), dtype=np.uint8) if last else None
@@ -352,13 +367,19 @@ class Render:
         return self.aov_info if want_info else None
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
-                          sigma_depth=None, width=None, height=None):
+                          sigma_depth=None, width=None, height=None, variance_guided=False):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
-        self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info."""
+        self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
+        variance_guided: render with want_variance and filter with crt_denoise_var (its own defaults) and self.variance_buffer."""
         self._handle("run_view_denoised")
-        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height)
+        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=variance_guided)
         self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        if variance_guided:
+            rgb, mean, self.denoise_info = denoise_var(self.mean_buffer, self.variance_buffer, iterations=iterations, sigma_color=sigma_color,
+                                                       sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
+                                                       device=self.device, return_info=True, **self.aov_buffers)
+            return rgb, mean
         rgb, mean, self.denoise_info = denoise(self.mean_buffer, iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal,
                                                sigma_albedo=sigma_albedo, sigma_depth=sigma_depth, device=self.device, return_info=True,
                                                **self.aov_buffers)
@@ -434,7 +455,9 @@ class MultiRender(Render):
         self.rank_stats = None
         self.info = None
 
-    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, to_host=True):
+    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, to_host=True, want_variance=False):
+        if want_variance:
+            raise NotImplementedError("the variance buffer is a single-device interface (crt_variance): there is no gather for it")
         if not self._mh:
             raise RuntimeError("MultiRender.run_view after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
@@ -464,6 +487,9 @@ class MultiRender(Render):
 
     def preview(self, *a, **k):
         raise NotImplementedError("previews are a single-device interface (crt_preview)")
+
+    def variance(self, *a, **k):
+        raise NotImplementedError("the variance buffer is a single-device interface (crt_variance)")
 
     def accel_info(self):
         raise NotImplementedError("crt_scene_accel_info is a single-device interface")
@@ -522,9 +548,19 @@ def denoise_defaults():
     return {n: getattr(p, n) for n, _ in p._fields_ if n not in ("width", "height")}
 
 
-def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth):
+def denoise_var_defaults():
+    """crt_denoise_var_defaults as a dict: iterations and the four sigmas of the variance-guided filter."""
     p = capi.DenoiseParams()
-    capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
+    capi.check(capi.lib().crt_denoise_var_defaults(C.byref(p)), "crt_denoise_var_defaults")
+    return {n: getattr(p, n) for n, _ in p._fields_ if n not in ("width", "height")}
+
+
+def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=False):
+    p = capi.DenoiseParams()
+    if var:
+        capi.check(capi.lib().crt_denoise_var_defaults(C.byref(p)), "crt_denoise_var_defaults")
+    else:
+        capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
     p.width, p.height = int(width), int(height)
     for name, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo),
                     ("sigma_depth", sigma_depth)):
@@ -578,6 +614,55 @@ def denoise_device(width, height, color_ptr, out_mean_ptr, out_rgb_ptr, scratch_
                                              C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None, C.c_void_p(scratch_ptr) if scratch_ptr else None,
                                              int(scratch_bytes), C.c_void_p(stream) if stream else None,
                                              C.byref(info) if want_info else None), "crt_denoise_device")
+    return info.as_dict() if want_info else None
+
+
+def denoise_var(color, variance, albedo=None, normal=None, depth=None, iterations=None, sigma_color=None, sigma_normal=None,
+                sigma_albedo=None, sigma_depth=None, device=0, want_rgb=True, want_variance=False, return_info=False):
+    """Variance-guided form of the filter (crt_denoise_var, contract: include/crt.h): `variance` is the (H, W, 3) buffer of
+    Render.variance(); None settings take crt_denoise_var_defaults.  Returns (rgb, mean), with want_variance (rgb, mean, var) -- var
+    (H, W) float32, the filter's estimate of the noise left -- and with return_info also the crt_denoise_info dict."""
+    c = np.ascontiguousarray(color, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_var needs an (H, W, 3) colour image, got %r" % (c.shape,))
+    if variance is None:
+        raise ValueError("denoise_var needs the variance buffer (Render.variance)")
+    h, w = c.shape[:2]
+    inputs, keep = capi.DenoiseVarInputs(), [c]
+    inputs.color = c.ctypes.data
+    for name, a, shape in (("variance", variance, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("denoise_var: %s has shape %r, expected %r" % (name, a.shape, shape))
+        keep.append(a)
+        setattr(inputs, name, a.ctypes.data)
+    prm = _denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=True)
+    mean = np.zeros((h, w, 3), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    var = np.zeros((h, w), dtype=np.float32) if want_variance else None
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise_var(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(var), C.byref(info)),
+               "crt_denoise_var")
+    out = (rgb, mean, var) if want_variance else (rgb, mean)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out_rgb_ptr, out_variance_ptr, scratch_ptr, scratch_bytes,
+                       albedo_ptr=None, normal_ptr=None, depth_ptr=None, iterations=None, sigma_color=None, sigma_normal=None,
+                       sigma_albedo=None, sigma_depth=None, device=0, stream=None, want_info=True):
+    """Enqueues the variance-guided filter with everything in device memory (raw device pointers, crt_denoise_var_device); the scratch
+    is that of denoise_device (denoise_scratch_bytes).  With want_info the call synchronizes the stream and returns the info dict."""
+    inputs = capi.DenoiseVarInputs(color_ptr or None, variance_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
+    prm = _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=True)
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise_var_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
+                                                 C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None,
+                                                 C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
+                                                 C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
+                                                 C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
+               "crt_denoise_var_device")
     return info.as_dict() if want_info else None
 
 

@@ -7,7 +7,10 @@
 //   crt_cli <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
-//           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d]
+//           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
+// --variance PATH renders with CRT_FLAG_VARIANCE (the frame is the same bits) and writes the per-pixel variance of the mean
+// (crt_variance, one device) as a 3-channel PFM.  --denoise-variance makes --denoise use the variance-guided filter (crt_denoise_var,
+// its own defaults; --denoise-iterations / --denoise-sigma override them as well).
 // --denoise PATH renders as usual, then filters the frame with the AOV-guided a-trous denoiser (crt_denoise, one device) and writes the
 // result as a PNG to PATH; -o and --aov outputs are unchanged by it.  --denoise-iterations (1 .. 5) and --denoise-sigma (colour, normal,
 // albedo, depth) override crt_denoise_defaults.
@@ -31,15 +34,16 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
-                             "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d]\n", argv[0]);
+                             "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n", argv[0]);
         return 2;
     }
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, denoise;
-        crt_denoise_params dn;
-        crt_denoise_defaults(&dn);
+        std::string out = "out.png", base_dir = ".", aov, denoise, variance;
+        crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
+        std::memset(&dn, 0, sizeof(dn));
+        bool dn_iterations = false, dn_sigma = false, denoise_var = false;
         uint64_t seed = 0;
         int device = 0;
         bool reference = false, exact = false, fast = false, bounded = false;
@@ -81,9 +85,12 @@ int main(int argc, char** argv)
             else if (a == "--base-dir") { need(i, 1); base_dir = argv[++i]; }
             else if (a == "--aov") { need(i, 1); aov = argv[++i]; }
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
-            else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); }
+            else if (a == "--denoise-variance") denoise_var = true;
+            else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
+            else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
+                dn_sigma = true;
                 float* dst[4] = {&dn.sigma_color, &dn.sigma_normal, &dn.sigma_albedo, &dn.sigma_depth};
                 const char* q = argv[++i];
                 for (int k = 0; k < 4; k++) {
@@ -111,12 +118,23 @@ int main(int argc, char** argv)
         const bool multi = !devices.empty();
         if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
         if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
+        if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
+        if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
+        if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
+        const bool want_var = !variance.empty() || denoise_var;
+        {
+            crt_denoise_params d;
+            if (denoise_var) crt_denoise_var_defaults(&d); else crt_denoise_defaults(&d);
+            if (dn_iterations) d.iterations = dn.iterations;
+            if (dn_sigma) { d.sigma_color = dn.sigma_color; d.sigma_normal = dn.sigma_normal; d.sigma_albedo = dn.sigma_albedo; d.sigma_depth = dn.sigma_depth; }
+            dn = d;
+        }
         crt::Render render_one_or_many = multi ? crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, devices, gather)
                                                : crt::Render(&scene, task.spp, task.p_rr, task.light_sample_n, device);
         crt::Render& render = render_one_or_many;
         render.set_seed(seed);
         render.set_traversal(reference ? CRT_TRAVERSAL_REFERENCE : (fast && !exact) ? CRT_TRAVERSAL_FAST : CRT_TRAVERSAL_EXACT);
-        if (bounded) render.set_flags(CRT_FLAG_BOUNDED_RADIANCE);
+        render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u));
         float inv_view[9];
         crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
         float fov_y = task.fov_y * (float)M_PI / 180; // src/main.cu:278
@@ -135,6 +153,11 @@ int main(int argc, char** argv)
         }
         render.save_frame_buffer(out.c_str());
         std::printf("%s\n", out.c_str());
+        if (!variance.empty()) {
+            const int rc = crt_write_pfm(variance.c_str(), task.width, task.height, 3, render.variance());
+            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the variance file failed: ") + crt_last_error());
+            std::printf("%s\n", variance.c_str());
+        }
         if (!aov.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
         if (!aov.empty()) {
             const crt_aov_info& ai = render.last_aov_info();
@@ -156,7 +179,7 @@ int main(int argc, char** argv)
             std::printf("%s\n%s\n%s\n", pa.c_str(), pn.c_str(), pd.c_str());
         }
         if (!denoise.empty()) {
-            render.run_denoise(dn);
+            if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
             const crt_denoise_info& di = render.last_denoise_info();
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);
             render.save_denoised_buffer(denoise.c_str());

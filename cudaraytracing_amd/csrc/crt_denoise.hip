@@ -1,5 +1,5 @@
 // cudaraytracing_amd/csrc/crt_denoise.hip -- the AOV-guided edge-avoiding a-trous filter (crt_denoise / crt_denoise_device, contract:
-// include/crt.h): kernels and host code.  An image operation without a scene handle.
+// include/crt.h) and its variance-guided form (crt_denoise_var / crt_denoise_var_device): kernels and host code.  An image operation without a scene handle.
 //
 // One call = k_denoise_pack (colour and guides into four float4 planes of the caller's scratch: a colour ping-pong pair, (normal.xyz,
 // depth) and (albedo.xyz, 0) -- three 16-byte loads per tap, coalesced along a row whatever the spacing) and one filter launch per pass.
@@ -9,6 +9,7 @@
 #include "crt_internal.h"
 
 #include <cstring>
+#include <limits>
 #include <string>
 
 namespace crtk {
@@ -101,6 +102,93 @@ __global__ __launch_bounds__(256) void k_denoise_pass(const DnParams P, const in
     dn_write(P, p, s);
 }
 
+// ---- variance-guided form (crt_denoise_var, contract: include/crt.h) ----
+// The same planes; the scalar variance v_i rides in the .w of the colour ping-pong pair.  A pass adds, per pixel, nine 4-byte loads for
+// g(p) (the .w of the pixels around p: lines the spacing-1 taps touch anyway) and a multiply-add pair per tap.  No LDS staging, as the
+// plain pass: it sits at the vector-ALU issue rate (docs/experiments.md, "The variance-guided filter").
+struct DnVarPack {
+    DnPack K;
+    const float* variance;
+};
+
+__global__ __launch_bounds__(256) void k_denoise_var_pack(const DnVarPack V)
+{
+    const DnPack& K = V.K;
+    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= K.npix) return;
+    const float v0 = (V.variance[p * 3] + V.variance[p * 3 + 1]) + V.variance[p * 3 + 2];
+    K.c0[p] = make_float4(K.color[p * 3], K.color[p * 3 + 1], K.color[p * 3 + 2], v0);
+    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (K.normal) { g.x = K.normal[p * 3]; g.y = K.normal[p * 3 + 1]; g.z = K.normal[p * 3 + 2]; }
+    if (K.depth) g.w = K.depth[p];
+    if (K.albedo) { a.x = K.albedo[p * 3]; a.y = K.albedo[p * 3 + 1]; a.z = K.albedo[p * 3 + 2]; }
+    K.g0[p] = g;
+    K.g1[p] = a;
+}
+
+__device__ __forceinline__ float dn_k(const int d) { return d == 0 ? 0.5f : 0.25f; }
+
+// P.sig2_c = sigma_color * sigma_color (the same in every pass); out_var: v_iterations of the last pass (may be null)
+__global__ __launch_bounds__(256) void k_denoise_var_pass(const DnParams P, const int step, float* const out_var)
+{
+    const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
+    const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
+    const int W = (int)P.width, H = (int)P.height;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * P.width + (size_t)x;
+    // g(p): the 3x3 Gaussian of v_i at spacing 1, whatever the spacing of the pass
+    float gn = 0.0f, gd = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int ty = y + dy;
+        if (ty < 0 || ty >= H) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int tx = x + dx;
+            if (tx < 0 || tx >= W) continue;
+            const float k = dn_k(dy) * dn_k(dx);
+            gn = gn + k * P.c_in[(size_t)ty * P.width + (size_t)tx].w;
+            gd = gd + k;
+        }
+    }
+    const float n_c = P.sig2_c * (gn / gd) + 1e-10f;
+    const float4 cp = P.c_in[p], gp = P.g0[p], ap = P.g1[p];
+    DnSum s = {0.0f, 0.0f, 0.0f, 0.0f};
+    float vnum = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+        const int qy = y + dy * step;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int qx = x + dx * step;
+            if (qx < 0 || qx >= W) continue;
+            const size_t q = (size_t)qy * P.width + (size_t)qx;
+            const float4 cq = P.c_in[q], gq = P.g0[q], aq = P.g1[q];
+            const float dcx = cp.x - cq.x, dcy = cp.y - cq.y, dcz = cp.z - cq.z;
+            const float e_c = (dcx * dcx + dcy * dcy + dcz * dcz) / n_c;
+            const float dnx = gp.x - gq.x, dny = gp.y - gq.y, dnz = gp.z - gq.z;
+            const float e_n = (dnx * dnx + dny * dny + dnz * dnz) / P.sig2_n;
+            const float dax = ap.x - aq.x, day = ap.y - aq.y, daz = ap.z - aq.z;
+            const float e_a = (dax * dax + day * day + daz * daz) / P.sig2_a;
+            const float m = gp.w > gq.w ? gp.w : gq.w;
+            const float r = (gp.w - gq.w) / (P.sigma_d * m);
+            const float e_d = m > 0.0f ? r * r : 0.0f;
+            const float w = (dn_h(dy) * dn_h(dx)) * det_expf(-(((e_c + e_n) + e_a) + e_d));
+            s.x = s.x + cq.x * w;
+            s.y = s.y + cq.y * w;
+            s.z = s.z + cq.z * w;
+            s.den = s.den + w;
+            vnum = vnum + cq.w * (w * w);
+        }
+    }
+    const float cx = s.x / s.den, cy = s.y / s.den, cz = s.z / s.den, v = vnum / (s.den * s.den);
+    if (!P.last) { P.c_out[p] = make_float4(cx, cy, cz, v); return; }
+    if (P.out_mean) { P.out_mean[p * 3] = cx; P.out_mean[p * 3 + 1] = cy; P.out_mean[p * 3 + 2] = cz; }
+    if (P.out_rgb) { P.out_rgb[p * 3] = tonemap(cx); P.out_rgb[p * 3 + 1] = tonemap(cy); P.out_rgb[p * 3 + 2] = tonemap(cz); }
+    if (out_var) out_var[p] = v;
+}
+
 } // namespace crtk
 
 using namespace crtk;
@@ -135,16 +223,33 @@ int denoise_check(const char* who, const crt_denoise_params* prm, const crt_deno
 
 uint64_t scratch_bytes_of(uint32_t width, uint32_t height) { return (uint64_t)width * height * 4u * sizeof(float4); }
 
-int denoise_impl(int device, const crt_denoise_params* prm, const crt_denoise_inputs* in, void* d_out_mean, void* d_out_rgb, void* d_scratch,
-                 uint64_t scratch_bytes, hipStream_t st, crt_denoise_info* info)
+// The extra checks of the variance-guided form (after denoise_check on the fields the two forms share)
+int denoise_var_check(const char* who, const crt_denoise_params* prm, const crt_denoise_var_inputs* in, const void* out_mean, const void* out_rgb)
 {
-    const int rc = denoise_check("crt_denoise_device", prm, in, d_out_mean, d_out_rgb);
+    const std::string w(who);
+    if (!prm || !in) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
+    const crt_denoise_inputs plain = {in->color, in->albedo, in->normal, in->depth};
+    const int rc = denoise_check(who, prm, &plain, out_mean, out_rgb);
     if (rc != CRT_OK) return rc;
-    if (!d_scratch) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: null scratch buffer");
+    if (!in->variance) return fail(CRT_ERR_INVALID_ARG, w + ": null variance buffer");
+    if (!(prm->sigma_color < std::numeric_limits<float>::infinity()))
+        return fail(CRT_ERR_INVALID_ARG, w + ": sigma_color must be finite (inf x a variance of 0 is NaN; crt_denoise drops the colour term)");
+    return CRT_OK;
+}
+
+// Both forms of the filter on device buffers: d_variance == nullptr is crt_denoise_device (the caller has checked the arguments that
+// the two forms do not share); otherwise the variance-guided passes, d_out_var optional.
+int denoise_impl(const char* who, int device, const crt_denoise_params* prm, const crt_denoise_inputs* in, const float* d_variance, void* d_out_mean,
+                 void* d_out_rgb, float* d_out_var, void* d_scratch, uint64_t scratch_bytes, hipStream_t st, crt_denoise_info* info)
+{
+    const std::string w(who);
+    const int rc = denoise_check(who, prm, in, d_out_mean, d_out_rgb);
+    if (rc != CRT_OK) return rc;
+    if (!d_scratch) return fail(CRT_ERR_INVALID_ARG, w + ": null scratch buffer");
     if (scratch_bytes < scratch_bytes_of(prm->width, prm->height))
-        return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: scratch buffer too small (crt_denoise_scratch_bytes)");
-    if ((uintptr_t)d_scratch % sizeof(float4) != 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: scratch buffer not 16-byte aligned");
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_device: device index out of range");
+        return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer too small (crt_denoise_scratch_bytes)");
+    if ((uintptr_t)d_scratch % sizeof(float4) != 0) return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer not 16-byte aligned");
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, w + ": device index out of range");
     hipEvent_t e0 = nullptr, e1 = nullptr;
     int status = CRT_OK;
     try {
@@ -161,7 +266,13 @@ int denoise_impl(int device, const crt_denoise_params* prm, const crt_denoise_in
         K.npix = npix;
         K.color = in->color; K.albedo = in->albedo; K.normal = in->normal; K.depth = in->depth;
         K.c0 = c[0]; K.g0 = plane + 2 * npix; K.g1 = plane + 3 * npix;
-        hipLaunchKernelGGL(k_denoise_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, K);
+        if (d_variance) {
+            DnVarPack V;
+            V.K = K; V.variance = d_variance;
+            hipLaunchKernelGGL(k_denoise_var_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, V);
+        } else {
+            hipLaunchKernelGGL(k_denoise_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, K);
+        }
         HIP_CHECK(hipGetLastError());
         DnParams P;
         std::memset(&P, 0, sizeof(P));
@@ -178,7 +289,12 @@ int denoise_impl(int device, const crt_denoise_params* prm, const crt_denoise_in
             P.last = i + 1 == prm->iterations;
             P.out_mean = P.last ? (float*)d_out_mean : nullptr;
             P.out_rgb = P.last ? (uint8_t*)d_out_rgb : nullptr;
-            hipLaunchKernelGGL(k_denoise_pass, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P, 1 << i);
+            if (d_variance) {
+                P.sig2_c = prm->sigma_color * prm->sigma_color; // (no halving per pass: the filtered variance shrinks instead)
+                hipLaunchKernelGGL(k_denoise_var_pass, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P, 1 << i, P.last ? d_out_var : (float*)nullptr);
+            } else {
+                hipLaunchKernelGGL(k_denoise_pass, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P, 1 << i);
+            }
             HIP_CHECK(hipGetLastError());
         }
         if (info) {
@@ -219,7 +335,7 @@ int crt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes)
 int crt_denoise_device(int device, const crt_denoise_params* prm, const crt_denoise_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
                        void* d_scratch, uint64_t scratch_bytes, void* stream, crt_denoise_info* info)
 {
-    return denoise_impl(device, prm, dev_in, d_out_mean, d_out_rgb, d_scratch, scratch_bytes, (hipStream_t)stream, info);
+    return denoise_impl("crt_denoise_device", device, prm, dev_in, nullptr, d_out_mean, d_out_rgb, nullptr, d_scratch, scratch_bytes, (hipStream_t)stream, info);
 }
 
 int crt_denoise(int device, const crt_denoise_params* prm, const crt_denoise_inputs* host_in, float* out_mean, uint8_t* out_rgb,
@@ -248,12 +364,72 @@ int crt_denoise(int device, const crt_denoise_params* prm, const crt_denoise_inp
         if (out_mean) d_mean.alloc(npix * 3);
         if (out_rgb) d_rgb.alloc(npix * 3);
         d_scratch.alloc(npix * 4);
-        const int rc = denoise_impl(device, prm, &d, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr, d_scratch.p,
-                                    npix * 4 * sizeof(float4), nullptr, info);
+        const int rc = denoise_impl("crt_denoise_device", device, prm, &d, nullptr, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr, nullptr,
+                                    d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
         if (out_mean) HIP_CHECK(hipMemcpy(out_mean, d_mean.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
         if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, d_rgb.p, npix * 3, hipMemcpyDeviceToHost));
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_denoise_var_defaults(crt_denoise_params* prm)
+{
+    if (!prm) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_var_defaults: null argument");
+    std::memset(prm, 0, sizeof(*prm));
+    prm->iterations = 3;
+    prm->sigma_color = 6.0f; prm->sigma_normal = 0.5f; prm->sigma_albedo = 0.1f; prm->sigma_depth = 0.05f;
+    return CRT_OK;
+}
+
+int crt_denoise_var_device(int device, const crt_denoise_params* prm, const crt_denoise_var_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
+                           void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* stream, crt_denoise_info* info)
+{
+    const int rc = denoise_var_check("crt_denoise_var_device", prm, dev_in, d_out_mean, d_out_rgb);
+    if (rc != CRT_OK) return rc;
+    const crt_denoise_inputs plain = {dev_in->color, dev_in->albedo, dev_in->normal, dev_in->depth};
+    return denoise_impl("crt_denoise_var_device", device, prm, &plain, dev_in->variance, d_out_mean, d_out_rgb, (float*)d_out_variance, d_scratch,
+                        scratch_bytes, (hipStream_t)stream, info);
+}
+
+int crt_denoise_var(int device, const crt_denoise_params* prm, const crt_denoise_var_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                    float* out_variance, crt_denoise_info* info)
+{
+    const int rc0 = denoise_var_check("crt_denoise_var", prm, host_in, out_mean, out_rgb);
+    if (rc0 != CRT_OK) return rc0;
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_var: device index out of range");
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t npix = (uint64_t)prm->width * prm->height;
+        DevBuf<float> d_color, d_var, d_albedo, d_normal, d_depth, d_mean, d_ovar;
+        DevBuf<uint8_t> d_rgb;
+        DevBuf<float4> d_scratch;
+        crt_denoise_var_inputs d{};
+        auto up = [&](DevBuf<float>& b, const float* h, uint64_t n) -> const float* {
+            if (!h) return nullptr;
+            b.alloc(n);
+            HIP_CHECK(hipMemcpy(b.p, h, n * sizeof(float), hipMemcpyHostToDevice));
+            return b.p;
+        };
+        d.color = up(d_color, host_in->color, npix * 3);
+        d.variance = up(d_var, host_in->variance, npix * 3);
+        d.albedo = up(d_albedo, host_in->albedo, npix * 3);
+        d.normal = up(d_normal, host_in->normal, npix * 3);
+        d.depth = up(d_depth, host_in->depth, npix);
+        if (out_mean) d_mean.alloc(npix * 3);
+        if (out_rgb) d_rgb.alloc(npix * 3);
+        if (out_variance) d_ovar.alloc(npix);
+        d_scratch.alloc(npix * 4);
+        const int rc = crt_denoise_var_device(device, prm, &d, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr,
+                                              out_variance ? d_ovar.p : nullptr, d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        if (out_mean) HIP_CHECK(hipMemcpy(out_mean, d_mean.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, d_rgb.p, npix * 3, hipMemcpyDeviceToHost));
+        if (out_variance) HIP_CHECK(hipMemcpy(out_variance, d_ovar.p, npix * sizeof(float), hipMemcpyDeviceToHost));
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);

@@ -658,7 +658,8 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     std::memset(&p, 0, sizeof(p));
     p.width = scene_->get_width(); p.height = scene_->get_height();
     p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE);
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE);
+    variance_buffer_.clear();
     int rc;
     if (multi_) {
         rc = crt_multi_render(multi_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), rank_stats_.data(), &multi_info_);
@@ -712,6 +713,36 @@ void Render::run_denoise(const crt_denoise_params& prm)
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
     const int rc = crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), &denoise_info_);
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise failed: ") + crt_last_error());
+}
+
+const float* Render::variance()
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::variance: the variance buffer is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::variance after free()");
+    if (variance_buffer_.empty()) {
+        std::vector<float> v(3 * scene_->get_pixels(), 0.0f);
+        const int rc = crt_variance(device_scene_, v.data(), nullptr);
+        if (rc != CRT_OK) throw Error(rc, std::string("Render::variance failed: ") + crt_last_error());
+        variance_buffer_.swap(v);
+    }
+    return variance_buffer_.data();
+}
+
+void Render::run_denoise_var(const crt_denoise_params& prm)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise_var: the denoiser is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var after free()");
+    const size_t n = scene_->get_pixels();
+    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
+        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var needs run_view and run_aov of this frame size first");
+    crt_denoise_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    crt_denoise_var_inputs in{};
+    in.color = mean_buffer_.data(); in.variance = variance();
+    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), nullptr, &denoise_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise_var failed: ") + crt_last_error());
 }
 
 void Render::save_denoised_buffer(const char* save_path) const

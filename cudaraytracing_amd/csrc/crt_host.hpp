@@ -223,6 +223,12 @@ public:
     // the frame of the last run_view filtered by crt_denoise with the albedo, normal and depth of the last run_aov as guides (call both
     // first, with the same camera); prm: crt_denoise_defaults with overrides, its width and height are set here; one device only
     void run_denoise(const crt_denoise_params& prm);
+    // the same with the variance-guided filter (crt_denoise_var; prm: crt_denoise_var_defaults with overrides): the last run_view must
+    // have had CRT_FLAG_VARIANCE (set_flags)
+    void run_denoise_var(const crt_denoise_params& prm);
+    // per-pixel variance of the mean of the last run_view (crt_variance; needs set_flags(CRT_FLAG_VARIANCE) before it): W x H x 3,
+    // fetched from the device on the first call after a frame; one device only
+    const float* variance();
     const unsigned char* get_denoised_buffer() const { return denoised_buffer_.data(); } // W x H x 3 RGB8
     const float* get_denoised_mean_buffer() const { return denoised_mean_buffer_.data(); } // W x H x 3
     const crt_denoise_info& last_denoise_info() const { return denoise_info_; }
@@ -236,7 +242,7 @@ public:
     void set_light_sample_n(const int& n) { light_sample_n_ = (unsigned)n; }
     void set_seed(uint64_t s) { seed_ = s; }
     void set_traversal(uint32_t t) { traversal_ = t; }
-    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE
+    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE, CRT_FLAG_VARIANCE
     void set_width(const unsigned& w);
     void set_height(const unsigned& h);
     const crt_stats& last_stats() const { return stats_; }
@@ -260,6 +266,7 @@ private:
     std::vector<float> albedo_buffer_, normal_buffer_, depth_buffer_;
     std::vector<unsigned char> denoised_buffer_;
     std::vector<float> denoised_mean_buffer_;
+    std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame
     int device_ = 0;
     crt_denoise_info denoise_info_{};
     crt_stats stats_{};

@@ -103,6 +103,8 @@ int trace_blocks_per_cu(int mode_id, size_t lds);
 void launch_trace(int mode_id, const TParams& T, uint32_t blocks, size_t lds, hipStream_t st);
 // frame and test kernels (crt_frame.hip)
 void launch_accumulate(const AParams& A, hipStream_t st);
+void launch_accumulate_var(const AParams& A, float* qacc, hipStream_t st); // CRT_FLAG_VARIANCE: c and the sum of squares q (3 planes of nslots)
+void launch_variance(const AParams& A, const float* qacc, float fn, float fs, hipStream_t st); // crt_variance: A.accum, qacc -> A.out_mean
 void launch_preview(const AParams& A, float scale, hipStream_t st);
 void launch_fill_rays(const Pool& pool, uint32_t n, const float* o, const float* d, bool raw_dir, const float* limits);
 void launch_math(int fn, uint32_t n, const float* a, const float* b, float* out);

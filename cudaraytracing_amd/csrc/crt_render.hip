@@ -1,6 +1,6 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- host side of the device layer of libcrt.so: scene upload (the flat HBM layouts of crt_device.h, the two trees,
 // the 4-wide collapse), the launch logic of a frame and of the AOV pass, and the C ABI of include/crt.h (crt_scene_create, crt_render*,
-// crt_preview*, crt_render_aov*, crt_intersect, crt_device_*).  The kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip,
+// crt_preview*, crt_variance*, crt_render_aov*, crt_intersect, crt_device_*).  The kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip,
 // crt_aov.hip.
 #include "crt_internal.h"
 
@@ -62,6 +62,10 @@ struct crt_scene {
     crt_accel_info accel{};
     // progressive render in flight: what the accumulator holds (crt_preview)
     struct { uint32_t samples = 0, spp = 0, width = 0, height = 0, rank = 0, world = 1, tiled = 0; } acc;
+    // CRT_FLAG_VARIANCE: the sum of squares beside accum (3 planes of nslots, allocated when the flag is first used) and what the two
+    // sums hold (crt_variance): samples so far of the frame the flag has been on for since sample 0; valid = the last render call had it
+    DevBuf<float> accum_q;
+    struct { uint32_t samples = 0, spp = 0, width = 0, height = 0, rank = 0, world = 1, tiled = 0; bool valid = false; } var;
     std::vector<hipEvent_t> ev;
     ~crt_scene()
     {
@@ -427,6 +431,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         return fail(CRT_ERR_INVALID_ARG, "crt_render: unknown traversal mode");
     const bool want_stats = (prm->flags & CRT_FLAG_STATS) != 0;
     const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
+    const bool want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
     if (prm->world > 1 && !tiled) return fail(CRT_ERR_INVALID_ARG, "crt_render: world > 1 needs CRT_FLAG_TILED_OUTPUT");
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
     try {
@@ -442,7 +447,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         // the rest of the pool.
         RingPlan ring;
         std::memset(&ring, 0, sizeof(ring));
-        if (pipeline == 4 && !want_stats) {
+        if (pipeline == 4 && !want_stats && !want_var) { // (CRT_FLAG_VARIANCE squares the per-path radiance, which the ring does not keep)
             // cursor shards: the commits of a shard are a serial chain (one wave, a memory round trip per 256 pixel slots), so a ring
             // launch has more and smaller shards than the 64 of a launch without: about 1 024 pixel slots each, at most 1 024 shards
             uint32_t shards = ITEM_SHARDS;
@@ -471,6 +476,20 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         sc->last_radiance_bytes = cap * sizeof(float4);
         sc->last_ring_samples = ring.samples;
         sc->accum.ensure_uncached((size_t)sh.nslots * 3); // (always uncached: a progressive render may switch between launches with and without the ring)
+        // the variance sums: valid from a range that starts at sample 0 with the flag, through ranges that continue that frame with it
+        const bool var_frame = want_var && (s_begin == 0 || (sc->var.valid && sc->var.samples == s_begin && sc->var.spp == prm->spp && sc->var.width == prm->width &&
+                                                             sc->var.height == prm->height && sc->var.rank == prm->rank && sc->var.world == prm->world));
+        sc->var.valid = false;
+        if (want_var) sc->accum_q.ensure_uncached((size_t)sh.nslots * 3);
+        auto accumulate = [&](const AParams& A, uint32_t samples_done) {
+            if (want_var) launch_accumulate_var(A, sc->accum_q.p, st);
+            else launch_accumulate(A, st);
+            HIP_CHECK(hipGetLastError());
+            if (!var_frame) return;
+            sc->var.valid = true;
+            sc->var.samples = samples_done; sc->var.spp = prm->spp; sc->var.width = prm->width; sc->var.height = prm->height;
+            sc->var.rank = prm->rank; sc->var.world = prm->world; sc->var.tiled = tiled ? 1u : 0u;
+        };
         const bool timing = stats != nullptr;
         if (timing && sc->ev.size() < (size_t)(4 * kMaxBatch + 4)) {
             while (sc->ev.size() < (size_t)(4 * kMaxBatch + 4)) {
@@ -627,10 +646,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
                 A.chunk_samples = ns;
                 A.first_chunk = s0 == 0; A.last_chunk = s0 + ns >= prm->spp;
                 if (ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
-                if (!ring.samples || A.last_chunk) {
-                    launch_accumulate(A, st);
-                    HIP_CHECK(hipGetLastError());
-                }
+                if (!ring.samples || A.last_chunk) accumulate(A, s0 + ns);
                 sc->acc.samples = A.last_chunk ? 0u : s0 + ns; sc->acc.spp = prm->spp; sc->acc.width = prm->width; sc->acc.height = prm->height;
                 sc->acc.rank = prm->rank; sc->acc.world = prm->world; sc->acc.tiled = tiled ? 1u : 0u;
             }
@@ -781,8 +797,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
             }
             A.chunk_samples = ns;
             A.first_chunk = s0 == 0; A.last_chunk = s0 + ns >= prm->spp;
-            launch_accumulate(A, st);
-            HIP_CHECK(hipGetLastError());
+            accumulate(A, s0 + ns);
             sc->acc.samples = A.last_chunk ? 0u : s0 + ns; sc->acc.spp = prm->spp; sc->acc.width = prm->width; sc->acc.height = prm->height;
             sc->acc.rank = prm->rank; sc->acc.world = prm->world; sc->acc.tiled = tiled ? 1u : 0u;
         }
@@ -1553,6 +1568,57 @@ int crt_radiance_storage(crt_scene* sc, uint64_t* bytes, uint32_t* ring_samples)
     *bytes = sc->last_radiance_bytes;
     if (ring_samples) *ring_samples = sc->last_ring_samples;
     return CRT_OK;
+}
+
+// Argument checks of both forms of crt_variance, before any device call
+static int variance_check(const crt_scene* sc, const void* out)
+{
+    if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, "crt_variance: null argument");
+    if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, "crt_variance: no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
+    if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, "crt_variance: fewer than 2 samples accumulated (one sample has no variance)");
+    return CRT_OK;
+}
+
+int crt_variance_device(crt_scene* sc, void* d_var, void* stream, uint32_t* samples_done)
+{
+    const int rc = variance_check(sc, d_var);
+    if (rc != CRT_OK) return rc;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        Shard sh = make_shard(sc->var.width, sc->var.height, sc->var.world);
+        AParams A;
+        std::memset(&A, 0, sizeof(A));
+        A.width = sc->var.width; A.height = sc->var.height; A.spp = sc->var.spp;
+        A.rank = sc->var.rank; A.world = sc->var.world; A.tiles_x = sh.tiles_x; A.n_tiles = sh.n_tiles;
+        A.nslots = sh.nslots; A.tiled_output = sc->var.tiled;
+        A.accum = sc->accum.p;
+        A.out_mean = (float*)d_var;
+        launch_variance(A, sc->accum_q.p, (float)sc->var.samples, (float)sc->var.spp, (hipStream_t)stream);
+        HIP_CHECK(hipGetLastError());
+        if (samples_done) *samples_done = sc->var.samples;
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_variance(crt_scene* sc, float* out_var, uint32_t* samples_done)
+{
+    const int rc0 = variance_check(sc, out_var);
+    if (rc0 != CRT_OK) return rc0;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = sc->var.tiled ? make_shard(sc->var.width, sc->var.height, sc->var.world).nslots : (uint64_t)sc->var.width * sc->var.height;
+        DevBuf<float> d_var;
+        d_var.alloc(npix * 3);
+        const int rc = crt_variance_device(sc, d_var.p, nullptr, samples_done);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out_var, d_var.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
 }
 
 int crt_preview_device(crt_scene* sc, void* d_rgb, void* d_mean, void* stream, uint32_t* samples_done)

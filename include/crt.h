@@ -128,13 +128,18 @@ enum {
                                     zero (crt_stats.rays_untraced stays 0); same frame, for measuring the traversal alone */
     CRT_FLAG_FORCE_EXACT = 4u,   /* test hook: treat every ray of CRT_TRAVERSAL_FAST as one with non-finite operands (reference
                                     box arithmetic on the reference topology, still pruned / any-hit); results are unchanged */
-    CRT_FLAG_BOUNDED_RADIANCE = 16u /* keep the radiance of a WINDOW of samples instead of one value per path: the frame's sum c += L_k / spp
+    CRT_FLAG_BOUNDED_RADIANCE = 16u, /* keep the radiance of a WINDOW of samples instead of one value per path: the frame's sum c += L_k / spp
                                     (Render.cuh:348) is made in sample order inside the launch ("commit ring", docs/experiments.md section 9), the
                                     whole sample range is one launch whatever its size, and the handle needs 16 B x pixels x 32 ... 64
                                     samples (245 MB for 800x600) instead of 16 B per path (3.9 GB for 800x600 spp 512; 17 GB per 2^30 paths).
                                     Same bits.  Costs time (800x600 spp 512: 167 ms instead of 93): off by default -- memory is what this
                                     device has plenty of.  Ignored with CRT_FLAG_STATS, by the fallback pipeline, and when the sample range
-                                    is no longer than the window */
+                                    is no longer than the window, and switched off for the call by CRT_FLAG_VARIANCE (the ring keeps
+                                    no per-path radiance to square: crt_radiance_storage then reports ring_samples = 0) */
+    CRT_FLAG_VARIANCE = 32u      /* keep, beside the frame's sum, the per-pixel sum of squares of the samples on the scene handle:
+                                    crt_variance reads the variance of the frame's mean from it.  The frame is bit for bit the frame without
+                                    the flag.  Switches the commit ring of CRT_FLAG_BOUNDED_RADIANCE (and of the CRT_COMMIT_RING_LOG2 test
+                                    hook) off for the call, as CRT_FLAG_STATS does.  Cleared by crt_multi_render (no gather for the buffer) */
 };
 
 typedef struct {
@@ -253,6 +258,35 @@ int crt_render_range_device(crt_scene* scene, const crt_camera* cam, const crt_p
 int crt_preview(crt_scene* scene, uint8_t* out_rgb, float* out_mean, uint32_t* samples_done);
 int crt_preview_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_stream, uint32_t* samples_done);
 
+/* Per-pixel variance of the frame (CRT_FLAG_VARIANCE).  With the flag, crt_render, crt_render_device, crt_render_range and
+ * crt_render_range_device keep, beside the frame's sum c, a second sum q per pixel slot and channel on the scene handle.  With
+ * S = params->spp and x_k = L_k / (float)S (the quotient the frame adds, Render.cuh:348):
+ *   c = c + x_k            (the frame; unchanged)
+ *   q = q + x_k * x_k      from +0.0f, in sample order k = 0, 1, ...; one IEEE fp32 multiply and one add, no FMA
+ * across chunks and progressive ranges exactly as c is carried.  crt_variance writes 3 floats per pixel in the layout of the render's
+ * out_mean (row-major, or the compact tiles of the shard with CRT_FLAG_TILED_OUTPUT; padding slots +0.0f).  With n = samples accumulated
+ * so far (n = S after the range that ends at spp; the buffer stays readable until the next render call on the handle), per channel:
+ *   fn = (float)n;  fs = (float)S
+ *   d  = fn * q - c * c;          d = d < 0.0f ? 0.0f : d        (NaN stays NaN)
+ *   r  = fs / fn                                                  (exactly 1 for a finished frame)
+ *   var = ((r * r) * d) / (fn - 1.0f)
+ * every * - / one IEEE fp32 operation, no FMA, no reciprocal multiply.  This is the unbiased sample variance of the pixel's n radiance
+ * samples divided by n: the estimated variance of the mean that the frame (or, mid-flight, crt_preview's accum * S / n) shows -- what a
+ * progressive caller needs to decide when to stop, and what crt_denoise_var takes.  It only reads the handle's sums: calling it between
+ * ranges changes no later result.  *samples_done (optional) receives n.
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null scene or buffer; no render with the flag on the handle yet; the last
+ * render (or any range of the frame in flight, from sample 0 on) was submitted without the flag; n < 2 (a finished spp 1 frame
+ * included: one sample has no variance).
+ * Precision: a sum of squares, not Welford's update -- both carry two values per channel across chunks, this one adds one multiply and
+ * one add per sample to a pass that is bound by reading 16 B per path, and keeps c the frame's own bits.  The sum of squares loses
+ * accuracy where variance / mean^2 approaches n x 2^-24; a Welford form would not.  Measured against the float64 sample variance of the
+ * same samples on 64x48 spp 8 and 32x24 spp 512 frames of the two shipped scenes: largest relative error 3.44e-6 / 2.75e-6 at spp 8 and
+ * 2.68e-6 / 3.46e-6 at spp 512 (cornell-box / veach-mis), 99th percentile below 2.3e-6, smallest variance / mean^2 met 4.4e-4; every
+ * value whose float64 variance is 0 came out exactly +0 and none came out negative (docs/experiments.md, "The variance buffer"). */
+int crt_variance(crt_scene* scene, float* out_var, uint32_t* samples_done);
+/* d_var: a device buffer on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
+int crt_variance_device(crt_scene* scene, void* d_var, void* hip_stream, uint32_t* samples_done);
+
 /* First-hit auxiliary buffers (AOVs: the guides of a denoiser, depth and coverage for compositing, IDs for masks), aligned sample for
  * sample with the frame crt_render draws with the same camera / params.  Per pixel, the S = params->spp camera rays of samples
  * k = 0 .. S-1 -- the primary rays of the frame's paths: same seed, jitter draws and arithmetic -- are traced for their closest hit
@@ -331,6 +365,35 @@ int crt_denoise(int device, const crt_denoise_params* params, const crt_denoise_
  * so frames can be pipelined without allocation.  Outputs must not overlap inputs or scratch. */
 int crt_denoise_device(int device, const crt_denoise_params* params, const crt_denoise_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
                        void* d_scratch, uint64_t scratch_bytes, void* hip_stream, crt_denoise_info* info);
+
+/* Variance-guided form of the filter (the spatial half of SVGF, Schied et al. 2017): the colour tolerance of a pixel is set by how noisy
+ * the renderer says its neighbourhood is, not by one sigma_color for the whole frame, and the variance is filtered along with the colour
+ * so that later passes see what noise is left.  `variance` is what crt_variance returns (3 floats per pixel) and is required; albedo,
+ * normal and depth may be NULL as in crt_denoise.  c_0 = color, v_0(p) = (variance(p).x + variance(p).y) + variance(p).z.  Pass
+ * i = 0 .. iterations-1, tap spacing s = 2^i:
+ *   g(p):  3x3 taps t = (x + dx, y + dy) at spacing 1 in EVERY pass, dy = -1..1 outer, dx = -1..1 inner, k = {1/4, 1/2, 1/4}, a tap
+ *          outside the image is skipped:   gn = gn + (k[dy+1] * k[dx+1]) * v_i(t);   gd = gd + (k[dy+1] * k[dx+1]);   g = gn / gd
+ *   n_c  = (sigma_color * sigma_color) * g(p) + 1e-10f                 (no halving of sigma_color per pass: v_i shrinks instead)
+ *   e_c  = (dc.x*dc.x + dc.y*dc.y + dc.z*dc.z) / n_c                   dc = c_i(p) - c_i(q)
+ *   e_n, e_a, e_d, h, the 25 taps q, their order and the border rule: exactly as crt_denoise
+ *   w    = (h[dy+2] * h[dx+2]) * exp(-(((e_c + e_n) + e_a) + e_d))     (det_expf)
+ *   num  = num + c_i(q) * w      den = den + w      vnum = vnum + v_i(q) * (w * w)
+ *   c_{i+1}(p) = num / den       v_{i+1}(p) = vnum / (den * den)
+ * all sums from +0.0f, left to right as written, one IEEE fp32 operation per * + - /, no FMA.  Outputs: c_iterations as out_mean and /
+ * or its tone map out_rgb (not both NULL), and optionally v_iterations as out_variance (1 float per pixel: the filter's own estimate of
+ * the noise that is left).  Scratch: the same 64 B per pixel (crt_denoise_scratch_bytes); the scalar variance rides in the .w of the
+ * colour planes.  Argument checks as crt_denoise, plus: a null `variance` and a sigma_color of +inf are CRT_ERR_INVALID_ARG (inf x 0
+ * would make every weight NaN; to drop the colour term use crt_denoise).  Non-finite or negative variance values are not special-cased.
+ * crt_denoise_var_defaults fills iterations 3, sigma_color 6, sigma_normal 0.5, sigma_albedo 0.1, sigma_depth 0.05: on the 160x120 spp 8
+ * frames crt_denoise's defaults were chosen on, the error against a converged frame falls from 169.3 to 159.9 (cornell-box) and from
+ * 149.6 to 112.1 (veach-mis) (docs/experiments.md, "The variance-guided filter"). */
+typedef struct { const float* color; const float* variance; const float* albedo; const float* normal; const float* depth; } crt_denoise_var_inputs;
+int crt_denoise_var_defaults(crt_denoise_params* params);
+int crt_denoise_var(int device, const crt_denoise_params* params, const crt_denoise_var_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                    float* out_variance, crt_denoise_info* info);
+int crt_denoise_var_device(int device, const crt_denoise_params* params, const crt_denoise_var_inputs* dev_in, void* d_out_mean,
+                           void* d_out_rgb, void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream,
+                           crt_denoise_info* info);
 
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there

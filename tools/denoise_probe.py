@@ -4,8 +4,10 @@
 Inputs: a cornell-box frame of --spp samples and its AOVs at that size, rendered here.  Prints ms per call (median and best), ms per
 pass (the call's time over its passes: the pack kernel is in it), and the cache-side byte rate -- (25 taps x 40 B + 12 B) per pixel and
 pass over the time -- next to the rate of the compulsory 52 B per pixel and pass.  One JSON line per figure on stderr, one JSON document on stdout.
+--variance also times the variance-guided form (crt_denoise_var_device, with the frame's crt_variance buffer and the filtered variance
+written) in the same run, the two forms' calls taking turns, and prints its figures and the ratio to the plain form.
 
-  python tools/denoise_probe.py [--sizes 800x600,3840x2160] [--iterations 3,5] [--calls 50] [--warmup 5] [--spp 4]
+  python tools/denoise_probe.py [--sizes 800x600,3840x2160] [--iterations 3,5] [--calls 50] [--warmup 5] [--spp 4] [--variance]
 """
 import argparse
 import ctypes as C
@@ -42,6 +44,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--scene", default="cornell-box")
+    ap.add_argument("--variance", action="store_true", help="time crt_denoise_var_device beside crt_denoise_device")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
@@ -53,12 +56,15 @@ def main():
     for size in a.sizes.split(","):
         w, h = (int(v) for v in size.split("x"))
         r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
-        r.run_view(t.eye_pos, iv, fov)
+        r.run_view(t.eye_pos, iv, fov, want_variance=a.variance)
         host = dict(r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth")), color=r.mean_buffer)
+        if a.variance:
+            host["variance"] = r.variance_buffer
         r.free()
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
         ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_mean", w * h * 12), ("out_rgb", w * h * 3), ("scratch", scratch_bytes)]:
+        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_mean", w * h * 12), ("out_rgb", w * h * 3), ("out_var", w * h * 4),
+                                                                                    ("scratch", scratch_bytes)]:
             p = C.c_void_p()
             if H.hipMalloc(C.byref(p), nbytes) != 0:
                 raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
@@ -72,14 +78,28 @@ def main():
                                       albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"],
                                       iterations=iterations)["total_ms"]
 
+        def call_var(iterations):
+            return crt.denoise_var_device(w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["out_var"], ptrs["scratch"],
+                                          scratch_bytes, albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"],
+                                          iterations=iterations)["total_ms"]
+
         for it in [int(v) for v in a.iterations.split(",")]:
-            ms = [call(it) for _ in range(a.warmup + a.calls)][a.warmup:]
+            ms, ms_var = [], []
+            for _ in range(a.warmup + a.calls):
+                ms.append(call(it))
+                if a.variance:
+                    ms_var.append(call_var(it))
+            ms, ms_var = ms[a.warmup:], ms_var[a.warmup:]
             med, best = statistics.median(ms), min(ms)
             per_pass = med / it
             run = {"width": w, "height": h, "iterations": it, "ms_per_call_median": round(med, 4), "ms_per_call_best": round(best, 4),
                    "ms_per_pass": round(per_pass, 4),
                    "cache_side_TB_per_s": round(CACHE_SIDE_BYTES * w * h / (per_pass * 1e-3) / 1e12, 3),
                    "compulsory_TB_per_s": round(COMPULSORY_BYTES * w * h / (per_pass * 1e-3) / 1e12, 4)}
+            if a.variance:
+                med_var = statistics.median(ms_var)
+                run.update({"var_ms_per_call_median": round(med_var, 4), "var_ms_per_call_best": round(min(ms_var), 4),
+                            "var_ms_per_pass": round(med_var / it, 4), "var_over_plain": round(med_var / med, 4)})
             out["runs"].append(run)
             print(json.dumps(run), file=sys.stderr, flush=True)
         for p in ptrs.values():
