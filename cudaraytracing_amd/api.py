@@ -265,14 +265,16 @@ class Render:
         return var, int(done.value)
 
     def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
-                       want_variance=False):
+                       want_variance=False, stats=False):
         """Progressive rendering: adds samples [sample_begin, sample_begin + sample_count) of the spp samples per pixel to the
         accumulator of the device scene; ranges go in ascending order from 0.  Returns the RGB8 frame once the range that ends
-        at spp has been rendered (bit-identical to run_view), None before."""
+        at spp has been rendered (bit-identical to run_view), None before.  A range with sample_begin > 0 that does not continue
+        the frame in flight on the handle (samples so far, spp, size) raises CrtError."""
         if not self._h:
             raise RuntimeError("Render.run_view_range after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=(capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags, width=width, height=height)
+        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags,
+                           width=width, height=height)
         w, h = prm.width, prm.height
         last = sample_begin + sample_count == self.spp
         rgb = np.zeros((h, w, 3), dtype=np.uint8) if last else None

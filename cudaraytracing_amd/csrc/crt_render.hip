@@ -413,6 +413,14 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
     return (const float*)sc->p_res.p;
 }
 
+// Whether a range that begins at sample s_begin > 0 continues the frame `f` records (crt_scene::acc for the sum c, crt_scene::var for
+// the sum of squares q): the samples before it are in the sums, and spp, size, shard and layout are the frame's.
+template <class Frame> static bool continues_frame(const Frame& f, const crt_params* prm, uint32_t s_begin, bool tiled)
+{
+    return f.samples == s_begin && f.spp == prm->spp && f.width == prm->width && f.height == prm->height && f.rank == prm->rank &&
+           f.world == prm->world && f.tiled == (tiled ? 1u : 0u);
+}
+
 // Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
 // (temp_color += L_k / spp in sample order, Render.cuh:348); the range that ends at spp also tone-maps and writes the frame.
 int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats,
@@ -434,6 +442,14 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
     const bool want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
     if (prm->world > 1 && !tiled) return fail(CRT_ERR_INVALID_ARG, "crt_render: world > 1 needs CRT_FLAG_TILED_OUTPUT");
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
+    // a range that does not start a frame adds to the accumulator: it must hold exactly the samples before the range, of this frame
+    if (s_begin > 0 && !continues_frame(sc->acc, prm, s_begin, tiled)) {
+        const std::string have = sc->acc.samples == 0 ? std::string("no frame is in flight on the handle")
+            : "the frame in flight holds samples [0, " + std::to_string(sc->acc.samples) + ") of spp " + std::to_string(sc->acc.spp) + " at " + std::to_string(sc->acc.width) +
+              " x " + std::to_string(sc->acc.height) + ", rank " + std::to_string(sc->acc.rank) + " of " + std::to_string(sc->acc.world) + (sc->acc.tiled ? ", tiled" : ", row-major");
+        return fail(CRT_ERR_INVALID_ARG, "crt_render_range: a range with sample_begin " + std::to_string(s_begin) + " must continue the frame in flight: expected sample_begin == samples accumulated "
+                                         "and the same spp, width, height, rank, world and CRT_FLAG_TILED_OUTPUT as its earlier ranges, or sample_begin 0 to start over (" + have + ")");
+    }
     try {
         HIP_CHECK(hipSetDevice(sc->device));
         Shard sh = make_shard(prm->width, prm->height, prm->world);
@@ -477,8 +493,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         sc->last_ring_samples = ring.samples;
         sc->accum.ensure_uncached((size_t)sh.nslots * 3); // (always uncached: a progressive render may switch between launches with and without the ring)
         // the variance sums: valid from a range that starts at sample 0 with the flag, through ranges that continue that frame with it
-        const bool var_frame = want_var && (s_begin == 0 || (sc->var.valid && sc->var.samples == s_begin && sc->var.spp == prm->spp && sc->var.width == prm->width &&
-                                                             sc->var.height == prm->height && sc->var.rank == prm->rank && sc->var.world == prm->world));
+        const bool var_frame = want_var && (s_begin == 0 || (sc->var.valid && continues_frame(sc->var, prm, s_begin, tiled)));
         sc->var.valid = false;
         if (want_var) sc->accum_q.ensure_uncached((size_t)sh.nslots * 3);
         auto accumulate = [&](const AParams& A, uint32_t samples_done) {
@@ -1656,7 +1671,6 @@ int crt_preview(crt_scene* sc, uint8_t* out_rgb, float* out_mean, uint32_t* samp
         DevBuf<float> d_mean;
         d_rgb.alloc(npix * 3);
         if (out_mean) d_mean.alloc(npix * 3);
-        if (sc->acc.tiled) HIP_CHECK(hipMemset(d_rgb.p, 0, npix * 3));
         int rc = crt_preview_device(sc, d_rgb.p, out_mean ? d_mean.p : nullptr, nullptr, samples_done);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());

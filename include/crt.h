@@ -243,7 +243,16 @@ int crt_radiance_storage(crt_scene* scene, uint64_t* bytes, uint32_t* ring_sampl
  * owns (temp_color += L_k / spp, in sample order as Render.cuh:348).  Ranges must be submitted in ascending order
  * starting at 0, with the same camera / params, and no other render call on the handle in between; the range that
  * ends at spp tone-maps and writes out_rgb / out_mean -- bit-identical to one crt_render call.  For the other ranges
- * out_rgb / out_mean are not written and may be NULL. */
+ * out_rgb / out_mean are not written and may be NULL.
+ * A range with sample_begin == 0 always starts a frame over.  A range with sample_begin > 0 must continue the frame in flight on
+ * the handle: sample_begin equals the number of samples accumulated so far, and spp, width, height, rank, world and
+ * CRT_FLAG_TILED_OUTPUT are those of the frame's earlier ranges.  Anything else -- a first call with sample_begin > 0, a range after
+ * a finished frame (crt_render* or the range that ended at spp), a gap, an overlap, another size, spp or shard -- would add to
+ * sums that are uninitialised or belong to another frame, and is refused with CRT_ERR_INVALID_ARG before any device call
+ * (crt_last_error names crt_render_range and what was expected).  A refused call leaves the handle as it was: the frame in flight
+ * can still be previewed and continued.  Calls that do not touch the accumulator stay legal between ranges: crt_render_aov*,
+ * crt_preview*, crt_variance*, crt_intersect, crt_denoise*.  Camera, seed, p_rr, light_sample_n and traversal are not recorded on
+ * the handle and not checked: they must not change between the ranges of a frame. */
 int crt_render_range(crt_scene* scene, const crt_camera* cam, const crt_params* params, uint32_t sample_begin,
                      uint32_t sample_count, uint8_t* out_rgb, float* out_mean, crt_stats* stats);
 int crt_render_range_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, uint32_t sample_begin,
@@ -252,9 +261,19 @@ int crt_render_range_device(crt_scene* scene, const crt_camera* cam, const crt_p
 /* The displayable frame of a progressive render in flight -- the viewer half of SURVEY 8(f) row 4 (the reference shows nothing
  * until all spp are done and re-renders from scratch on every click, src/main.cu:368-377).  After a range that ends at
  * `done` < spp the accumulator holds sum_{k < done} L_k / spp; the preview is tone-map(accumulator * spp / done), written in the
- * layout of the range calls (row-major, or compact tiles with CRT_FLAG_TILED_OUTPUT).  It only READS the accumulator: the bits
+ * layout of the range calls (row-major, or compact tiles with CRT_FLAG_TILED_OUTPUT).  Operation by operation, with S = spp of the
+ * frame in flight and n = `done`, the samples accumulated:
+ *   a     = the accumulator's value: c of the crt_variance contract below after samples 0 .. n-1 (c = c + L_k / (float)S from +0.0f)
+ *   scale = (float)S / (float)n        one IEEE fp32 division
+ *   p     = a * scale                  per channel: one IEEE fp32 multiply, no FMA -- neither (a * S) / n nor a * S * (1 / n)
+ *   out_mean = p;  out_rgb = the frame's tone map of p
+ * Padding slots of a tiled shard (slots of tiles beyond the frame, or of pixels beyond its right / bottom edge) are RGB 0 and mean
+ * +0.0f; both forms write them (the device form writes every slot of d_rgb / d_mean itself).  It only READS the accumulator: the bits
  * of the final frame do not depend on whether, or how often, previews were taken.  *samples_done (optional) receives `done`.
- * CRT_ERR_INVALID_ARG when no progressive render is in flight (before the first range, after the one that ends at spp). */
+ * crt_preview_device is enqueued on hip_stream (NULL = default stream) without synchronizing; the caller orders it after the
+ * range calls (the same stream, or an event).  d_mean may be NULL and is then not touched.
+ * CRT_ERR_INVALID_ARG, before any device call: a null scene or RGB buffer; no progressive render in flight (before the first range,
+ * after the one that ends at spp). */
 int crt_preview(crt_scene* scene, uint8_t* out_rgb, float* out_mean, uint32_t* samples_done);
 int crt_preview_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_stream, uint32_t* samples_done);
 

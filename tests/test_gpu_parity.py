@@ -466,11 +466,9 @@ def test_triangle_soup_with_ties_and_degenerate_triangles(tmp_path, thresh):
         r.free()
 
 
-@pytest.mark.parametrize("scale", [1e-12, 1e12, 1e17])
-def test_extreme_coordinate_scales(tmp_path, scale):
-    """The soup scene with every coordinate scaled: products underflow to denormals / overflow to inf, NaNs appear in the
-    radiance (1e12) -- kernel and oracle must still agree bit for bit (the NaNs included), in both traversal modes."""
-    obj, mtl = _write_soup_scene(str(tmp_path), n=200, dup=20, degenerate=10)
+def _write_scaled_soup_scene(d, scale):
+    """The smaller soup scene with every vertex coordinate multiplied by `scale` (rounded to float32)"""
+    obj, mtl = _write_soup_scene(d, n=200, dup=20, degenerate=10)
     lines = open(obj).read().split("\n")
     with open(obj, "w") as f:
         for line in lines:
@@ -478,6 +476,14 @@ def test_extreme_coordinate_scales(tmp_path, scale):
                 x, y, z = (np.float32(float(v) * scale) for v in line.split()[1:4])
                 line = "v %.9g %.9g %.9g" % (x, y, z)
             f.write(line + "\n")
+    return obj, mtl
+
+
+@pytest.mark.parametrize("scale", [1e-12, 1e12, 1e17])
+def test_extreme_coordinate_scales(tmp_path, scale):
+    """The soup scene with every coordinate scaled: products underflow to denormals / overflow to inf, NaNs appear in the
+    radiance (1e12) -- kernel and oracle must still agree bit for bit (the NaNs included), in both traversal modes."""
+    obj, mtl = _write_scaled_soup_scene(str(tmp_path), scale)
     w, h, spp = 48, 36, 2
     scene = crt.Scene(w, h)
     scene.add_obj(obj, mtl)

@@ -15,23 +15,10 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 import util
+from util import assert_bits, restated_sums
 
 F = np.float32
 VARIANCE_EXPORTS = ("crt_variance", "crt_variance_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device")
-
-
-def restated_sums(L, S, n):
-    """c and q of the contract after samples 0 .. n-1 of S: every ufunc is one IEEE fp32 operation per element."""
-    fs = F(S)
-    c = np.zeros(L.shape[:2] + (3,), dtype=F)
-    q = np.zeros_like(c)
-    with np.errstate(all="ignore"):
-        for k in range(n):
-            x = L[:, :, k, :] / fs
-            c = c + x
-            q = q + x * x
-    assert c.dtype == F and q.dtype == F
-    return c, q
 
 
 def restated_variance(L, S, n=None):
@@ -45,14 +32,6 @@ def restated_variance(L, S, n=None):
         var = ((r * r) * d) / (fn - F(1.0))
     assert var.dtype == F
     return var
-
-
-def assert_bits(got, want, where=""):
-    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
-    assert got.shape == want.shape, (where, got.shape, want.shape)
-    nan = np.isnan(want)
-    same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
-    assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU --

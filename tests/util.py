@@ -37,6 +37,32 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
+def restated_sums(L, S, n):
+    """c and q of the crt_variance contract (include/crt.h) after samples 0 .. n-1 of S, from the oracle's per-path radiance
+    L (h, w, S, 3): every ufunc is one IEEE fp32 operation per element."""
+    F = np.float32
+    fs = F(S)
+    c = np.zeros(L.shape[:2] + (3,), dtype=F)
+    q = np.zeros_like(c)
+    with np.errstate(all="ignore"):
+        for k in range(n):
+            x = L[:, :, k, :] / fs
+            c = c + x
+            q = q + x * x
+    assert c.dtype == F and q.dtype == F
+    return c, q
+
+
+def assert_bits(got, want, where=""):
+    """float32 arrays equal on their uint32 views; NaN matches NaN"""
+    F = np.float32
+    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
+    assert got.shape == want.shape, (where, got.shape, want.shape)
+    nan = np.isnan(want)
+    same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
+    assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+
+
 def random_rays(name, n, seed):
     """Rays from inside the scene bounds towards random directions plus camera-like rays."""
     rng = np.random.default_rng(seed)
