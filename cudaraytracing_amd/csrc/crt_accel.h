@@ -602,7 +602,7 @@ inline int optimize_sah(std::vector<Node>& nodes, int passes, int n_threads = 0)
 // split "by index" (coinciding centroids).  Returns the depth, or -1 if the device build could not run (use build_sah then).
 int build_sah_device(const std::vector<Prim>& prims, std::vector<Node>& nodes, int32_t& root_ref, float* device_ms, uint32_t* index_splits = nullptr);
 
-// The nearest float <= f (up = false) or >= f (up = true) whose low 12 mantissa bits are `chunk` (< 4096): how crt_render.hip's
+// The nearest float <= f (up = false) or >= f (up = true) whose low 12 mantissa bits are `chunk` (< 4096): how crt_scene_layout.h's
 // nodes4i hides child indices in the planes of an inner child, moving them outwards only.  A magnitude below the smallest one with these
 // bits crosses zero to the smallest magnitude of the other sign (a denormal).  ok = false (f returned) when f is not finite or no finite
 // value has those bits on that side; ok is left alone otherwise.  (tests/test_with_bits.py checks it on the CPU.)

@@ -195,13 +195,6 @@ using namespace crtk;
 
 namespace {
 
-int fail(int status, const std::string& msg)
-{
-    crt_set_last_error_(msg.c_str());
-    return status;
-}
-int fail_hip(const HipFail& f) { return fail(CRT_ERR_HIP, std::string(f.what) + ": " + hipGetErrorString(f.e)); }
-
 const uint32_t kMaxSide = 1u << 24;
 bool sigma_ok(float s) { return s > 0.0f; } // (false for NaN)
 

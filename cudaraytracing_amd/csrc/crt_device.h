@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "crt_detmath.h"
+#include "crt_fastdiv.h"
 
 namespace crtdev {
 
@@ -68,7 +69,7 @@ struct DevScene {
     float coord_max;         // largest |coordinate| of a box of the 4-wide tree, +inf if one is not finite (start_ray: which rays may walk it)
     const float4* tri_nm;    // (normal.xyz, bits(material | emitter << 30 | SPECULAR << 31): TNM_*) per triangle: what entering a vertex needs, 16 B instead of 48 + 4
     uint32_t empty4_off;     // byte offset in nodes4 of a node of four empty slots, behind the tree (the decoupled-leaves step parks idle lanes there)
-    // the 4-wide tree without its rows of refs (round 6, crt_render.hip "nodes4i"): 6 x float4 (96 B) per node, the same plane-major rows [0..5];
+    // the 4-wide tree without its rows of refs (round 6, crt_scene_layout.h "nodes4i"): 6 x float4 (96 B) per node, the same plane-major rows [0..5];
     // nodes [0, n_mixed4i) have an inner child, the others only leaves; child refs and leaf records are implied (crt_mega3.hip: inner4_step_dec)
     const float4* nodes4i;
     const float4* leaf_geo_i; // leaf child k of node n: record 4 n + k (a sparse copy of leaf_geo's records, 5 x float4 each)
@@ -78,21 +79,7 @@ struct DevScene {
     uint32_t empty4i_off;    // byte offset in nodes4i of the node of four empty slots (numbered n: a fringe node)
 };
 
-// Exact unsigned 32-bit division by a run-time constant without the ~40-instruction hardware-less
-// divide sequence (Granlund & Montgomery / Hacker's Delight 10-9): q = (t + ((n - t) >> sh1)) >> sh2,
-// t = mulhi(m, n).  Valid for every n and every d >= 1 (tests/test_host_layer.py checks the host maths).
-struct FastDiv {
-    uint32_t m, sh; // sh = sh1 | sh2 << 8
-};
-inline FastDiv make_fastdiv(uint32_t d)
-{
-    uint32_t l = 0;
-    while (l < 32 && (1ull << l) < d) l++;
-    FastDiv f;
-    f.m = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-    f.sh = (l < 1 ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 8);
-    return f;
-}
+// FastDiv / make_fastdiv (the host half: crt_fastdiv.h); q = (t + ((n - t) >> sh1)) >> sh2, t = mulhi(m, n)
 __host__ __device__ __forceinline__ uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
 {
 #if defined(__HIP_DEVICE_COMPILE__)

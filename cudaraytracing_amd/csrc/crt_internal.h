@@ -1,11 +1,12 @@
 // cudaraytracing_amd/csrc/crt_internal.h -- between the translation units of libcrt.so's device layer: error plumbing, device
-// buffers, and the launch entry points each kernel file exports to the host code in crt_render.hip.
+// buffers, and the launch entry points each kernel file exports to the host code in crt_render.hip (crt_scene.h: the scene handle).
 #ifndef CRT_INTERNAL_H
 #define CRT_INTERNAL_H
 #include <cstdlib>
 #include "crt_mega3.h"
 
 #include <cstddef>
+#include <string>
 #include <vector>
 
 extern "C" void crt_set_last_error_(const char* msg);
@@ -21,6 +22,14 @@ struct HipFail {
         hipError_t e_ = (call);                                  \
         if (e_ != hipSuccess) throw HipFail{e_, #call};          \
     } while (0)
+
+// an entry point's error return: the message goes to crt_last_error
+inline int fail(int status, const std::string& msg)
+{
+    crt_set_last_error_(msg.c_str());
+    return status;
+}
+inline int fail_hip(const HipFail& f) { return fail(CRT_ERR_HIP, std::string(f.what) + ": " + hipGetErrorString(f.e)); }
 
 template <typename T> struct DevBuf {
     T* p = nullptr;
@@ -62,10 +71,12 @@ template <typename T> struct DevBuf {
         debug_fill();
     }
     bool uncached = false;
-    void upload(const std::vector<T>& v)
+    template <typename Row> T* upload(const std::vector<Row>& v) // (Row: T, or the plain-C++ row type of crt_scene_layout.h with T's layout)
     {
+        static_assert(sizeof(Row) == sizeof(T) && alignof(T) % alignof(Row) == 0, "upload is a byte copy");
         alloc(v.size());
         if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return p;
     }
     void release()
     {

@@ -87,7 +87,7 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 #define CRT_WAVES 4   /* waves per SIMD the kernel is compiled for; the LDS footprint of a pool must allow it (160 KiB per CU) */
 // R16: the traversal stack holds 16-bit node refs, twice as many levels in the same bytes (scenes whose 4-wide tree and leaf records
-// number at most 32 768 each: crt_scene::ref16_ok).  The levels beyond LDS cost a wave-uniform branch with 64-bit address arithmetic,
+// number at most 32 768 each: CAP_REF16, crt_scene_layout.h).  The levels beyond LDS cost a wave-uniform branch with 64-bit address arithmetic,
 // global stores and -- in the pop -- an exposed global load whenever ANY ray of a batch is that deep, which with three levels is
 // most batches (stamps: 830 of 5 800 cycles of an inner step, 560 of 4 100 of a leaf step); with six it is rare.  A ray on the
 // reference-arithmetic path (RF_EXACT: refs of the 2-wide trees, which do not fit) keeps its whole stack in the global area then.

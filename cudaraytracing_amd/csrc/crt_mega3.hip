@@ -898,7 +898,7 @@ struct Visit4 {
 template <bool IMPL>
 __device__ __forceinline__ void node_load(const DevScene& sc, const int ref, const wmask EN, const F3 dir, Visit4& V)
 {
-    // IMPL: the copy of the tree without its rows of refs (crt_render.hip "nodes4i": 96 B per node, SIX loads per visit instead of seven);
+    // IMPL: the copy of the tree without its rows of refs (crt_scene_layout.h "nodes4i": 96 B per node, SIX loads per visit instead of seven);
     // the children's refs and the leaves' records are implied.  A lane outside EN loads the EMPTY node.
     const char* nb = (const char*)(IMPL ? sc.nodes4i : sc.nodes4);
     const uint32_t noff = lanes(EN) ? (uint32_t)ref * (IMPL ? (uint32_t)(NODE4I_F4 * 16) : 128u) : (IMPL ? sc.empty4i_off : sc.empty4_off);

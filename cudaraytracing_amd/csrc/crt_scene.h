@@ -1,0 +1,103 @@
+// cudaraytracing_amd/csrc/crt_scene.h -- the scene handle of the device layer (struct crt_scene: the uploaded arrays, the buffers and
+// events a frame uses, what a progressive render has accumulated) and the small helpers crt_scene.hip (create / export / destroy) and
+// crt_render.hip (the launch logic) share.
+#ifndef CRT_SCENE_H
+#define CRT_SCENE_H
+#include "crt_internal.h"
+#include "crt_scene_layout.h"
+
+#include <cstdlib>
+#include <vector>
+
+// What the sums of a frame in flight on a handle hold: samples [0, samples) of spp, for this size, shard and output layout.
+struct FrameMark {
+    uint32_t samples = 0, spp = 0, width = 0, height = 0, rank = 0, world = 1, tiled = 0;
+    bool valid = false; // (crt_scene::var only) the last render call had CRT_FLAG_VARIANCE
+    void set(const crt_params* prm, uint32_t samples_, bool tiled_)
+    {
+        samples = samples_; spp = prm->spp; width = prm->width; height = prm->height;
+        rank = prm->rank; world = prm->world; tiled = tiled_ ? 1u : 0u;
+    }
+};
+
+struct crt_scene {
+    int device = 0;
+    crtk::DevBuf<float4> nodes, tri_geo, mats, ltri, nodes3, leaf_geo, tri_nm, nodes4, nodes4i, leaf_geo_i;
+    crtk::DevBuf<int32_t> rec_map;
+    uint32_t max_leaf = 0; // triangles in the largest leaf
+    crtk::DevBuf<int32_t> tri_mat, leaf_count;
+    crtk::DevBuf<uint4> lights;
+    // path pool + per-item radiance + cross-chunk accumulator
+    crtk::DevBuf<float4> p_ro, p_rd, p_vx, p_la, p_cc, p_vn, p_rec_a, p_rec_b, L;
+    crtk::DevBuf<uint4> p_id;
+    uint32_t n_mats = 0;
+    crtk::DevBuf<float2> p_res;
+    crtk::DevBuf<float> accum;
+    crtk::DevBuf<float4> aov_acc;                   // AOV pass: running sums of the pixel slots between its chunks (crt_render_aov)
+    crtk::DevBuf<unsigned long long> counters;      // [CNT_SHARDS][CNT_STRIDE]
+    crtk::DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
+    crtk::DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)
+    crtk::DevBuf<unsigned int> ring_done, ring_state; // commit ring: finished items per (shard, sample), shard words
+    crtk::DevBuf<float4> ring_L;                      // commit ring: radiance of [ring samples][shards * slots per shard] (uncached memory)
+    std::vector<unsigned int> ring_state_host;
+    uint64_t last_radiance_bytes = 0;           // per-work-item (or ring) radiance storage the last render used
+    uint32_t last_ring_samples = 0;             // its ring size in samples (0: one radiance per work item)
+    crtk::DevBuf<unsigned int> order_cnt;           // [ITEM_SHARDS][2] counters, one 128 B line each
+    crtk::DevBuf<unsigned int> slot_next[2];        // [SLOT_SHARDS][SLOT_STRIDE], one per pool half
+    crtk::DevBuf<int2> spill[2];                    // traversal stack overflow, one per pool half
+    hipStream_t aux_stream = nullptr;         // second pool half runs here so that k_logic overlaps k_trace
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr; // around the k_mega3 launches of the last frame, recorded without synchronizing (crt_last_launch_ms)
+    uint32_t last_launches = 0;
+    int n_cus = 0;
+    unsigned long long* h_counters = nullptr; // pinned copy of counters
+    crtdev::DevScene dev{};
+    crt_tree_scalars scalars{}; // (crt_scene_export)
+    int stack_cap = 0;
+    uint32_t n_tris = 0;
+    crt_accel_info accel{};
+    bool can(uint32_t cap) const { return (accel.layout_caps & cap) != 0; } // crtlayout::CAP_*
+    FrameMark acc; // progressive render in flight: what the accumulator holds (crt_preview)
+    // CRT_FLAG_VARIANCE: the sum of squares beside accum (3 planes of nslots, allocated when the flag is first used) and what the two
+    // sums hold (crt_variance): samples so far of the frame the flag has been on for since sample 0; valid = the last render call had it
+    crtk::DevBuf<float> accum_q;
+    FrameMark var;
+    std::vector<hipEvent_t> ev;
+    ~crt_scene()
+    {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        if (ev_k0) (void)hipEventDestroy(ev_k0);
+        if (ev_k1) (void)hipEventDestroy(ev_k1);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+        if (aux_stream) (void)hipStreamDestroy(aux_stream);
+        if (h_counters) (void)hipHostFree(h_counters);
+    }
+};
+
+namespace crtk {
+
+struct Shard {
+    uint32_t tiles_x, tiles_y, n_tiles, local_tiles, nslots;
+};
+inline Shard make_shard(uint32_t w, uint32_t h, uint32_t world)
+{
+    Shard s;
+    s.tiles_x = (w + CRT_TILE - 1) / CRT_TILE;
+    s.tiles_y = (h + CRT_TILE - 1) / CRT_TILE;
+    s.n_tiles = s.tiles_x * s.tiles_y;
+    s.local_tiles = (s.n_tiles + world - 1) / world; // padded so every rank writes the same number of slots
+    s.nslots = s.local_tiles * 64u;
+    return s;
+}
+
+inline uint32_t env_u32(const char* name, uint32_t dflt)
+{
+    const char* v = std::getenv(name);
+    if (!v || !*v) return dflt;
+    long x = std::strtol(v, nullptr, 10);
+    return x > 0 ? (uint32_t)x : dflt;
+}
+
+} // namespace crtk
+#endif

@@ -476,7 +476,7 @@ int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32
  * number of inputs outside the range that differ (those take the division itself).  A few milliseconds. */
 int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside);
 /* Test-only export of the traversal trees a scene handle holds, copied from DEVICE memory (what the kernels read; layouts:
- * csrc/crt_device.h, csrc/crt_render.hip).  `name` is one of the arrays "nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo",
+ * csrc/crt_device.h, csrc/crt_scene_layout.h).  `name` is one of the arrays "nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo",
  * "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", or "scalars" (one crt_tree_scalars).  *bytes receives the array's
  * size (0 for an array the scene does not have: "nodes" / "nodes3" when the tree is one leaf, the nodes4i set when layout_caps
  * bit 3 is clear); dst == NULL asks for the size only.  An unknown name, a null `bytes`, a null scene or a capacity below the size

@@ -154,7 +154,7 @@ def test_device_tree_is_the_host_tree_with_planes_at_signed_zeros(tmp_path, monk
 
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
 def test_collapse_by_dynamic_programming_against_the_greedy_one(name, monkeypatch):
-    """The 4-wide collapse minimises the summed area of the wide nodes (dynamic programming, csrc/crt_render.hip); the round-1 rule
+    """The 4-wide collapse minimises the summed area of the wide nodes (dynamic programming, csrc/crt_scene_layout.h); the round-1 rule
     (CRT_COLLAPSE=greedy: open the largest child until there are four) stays selectable.  Same frame either way (any tree over the
     reference's leaves gives the same hits); the optimal collapse has no more nodes and no more inner steps on the frame."""
     t = util.task(name)
@@ -186,7 +186,7 @@ def test_collapse_by_dynamic_programming_against_the_greedy_one(name, monkeypatc
         dp.free(); gr.free()
 
 
-TREE_HOOKS = {  # environment of crt_scene_create's tree set-up (csrc/crt_render.hip, csrc/crt_accel.h)
+TREE_HOOKS = {  # environment of crt_scene_create's tree set-up (csrc/crt_scene_layout.h, csrc/crt_accel.h)
     "default": {},
     "children of a node as the collapse leaves them": {"CRT_CHILD_ORDER": "none"},
     "children of a node by box area": {"CRT_CHILD_ORDER": "area"},

@@ -423,7 +423,7 @@ def test_with_bits_gives_up_next_to_flt_max(tmp_path):
     try:
         ex, info, v = _check(scene, r)
         assert v == [], v
-        # every other condition of the nodes4i copy holds (crt_render.hip: one-record leaves, <= 32 768 nodes, finite planes) ...
+        # every other condition of the nodes4i copy holds (crt_scene_layout.h: one-record leaves, <= 32 768 nodes, finite planes) ...
         n4c = info["n_nodes4"]
         assert n4c < 4095 and _leaf_sizes(scene).max() <= 2 and ex["root4"] >= 0 and np.isfinite(ex["coord_max"])
         # ... and some node with an inner child has hi.x = FLT_MAX (low bits 0xfff) on EVERY inner child: whichever of them nodes4i puts in

@@ -1,5 +1,5 @@
 """CPU property test of crtaccel::with_bits (csrc/crt_accel.h): the nudge that hides nodes4i's child indices in the low 12 mantissa bits of
-an inner child's planes (csrc/crt_render.hip).  A nudge in the wrong direction makes a box too small, which the exactness proof does not
+an inner child's planes (csrc/crt_scene_layout.h).  A nudge in the wrong direction makes a box too small, which the exactness proof does not
 allow (crt_accel.h).  tools/with_bits_check.cpp runs every input with all 4 096 chunks, moving down and up: a result that is finite, carries
 the chunk, lies on the asked side of the input and is the nearest such value; a give-up exactly when no finite such value exists."""
 import json

@@ -2,8 +2,8 @@
 
 The exactness proof of EXACT / FAST (csrc/crt_accel.h) rests on facts about the arrays the kernel walks, not on frames:
 every reference leaf is reached exactly once, a leaf's own box is the reference's bit for bit, an inner box contains every box below
-it, no plane is NaN.  This module restates every layout from the comments that define it (csrc/crt_device.h, csrc/crt_render.hip:
-crt_scene_create) and the kernel's nodes4i decode (csrc/crt_mega3.hip: inner4_step_dec) without calling product code; the single
+it, no plane is NaN.  This module restates every layout from the comments that define it (csrc/crt_device.h, csrc/crt_scene_layout.h:
+build_scene_layout) and the kernel's nodes4i decode (csrc/crt_mega3.hip: inner4_step_dec) without calling product code; the single
 source of truth is the reference BVH of the host layer (Scene.nodes(), Scene.triangles()).
 
 check_trees() returns a list of violations, each a string that starts with the invariant it breaks ("I1: ...").  I1 every leaf
@@ -462,7 +462,7 @@ def check_trees(ex, info, ref_nodes, ref_root, tris, stats=None):
         check_nodes4i_against_nodes4(w4, wi, mixed, v, order4, orderi, stats)
         planes += [wi.lo[wi.kind != 0], wi.hi[wi.kind != 0]]
 
-    # I7: depths as crt_render.hip counts them (root 1, the leaf level counts) and the stack they size
+    # I7: depths as crt_scene_layout.h counts them (root 1, the leaf level counts) and the stack they size
     if depth2 != int(info["depth2"]) or depth4 != int(info["depth4"]):
         v.append("I7: measured depths (%d, %d), accel_info (%d, %d)" % (depth2, depth4, info["depth2"], info["depth4"]))
     if int(ex["stack_cap"]) < max(depth2 + 2, 3 * depth4 + 2):

@@ -1,7 +1,7 @@
 // tools/wide_probe.cpp -- what an 8-wide node would change in the walk of k_mega3's decoupled inner step, counted on the host.
 //
 // The production tree is the binned-SAH tree over the reference's leaves (crt_accel.h: build_sah + one pass of optimize_sah) collapsed to W = 4
-// children per node by the dynamic programme of crt_render.hip (minimum summed area of the wide nodes).  This program builds the SAME binary tree
+// children per node by the dynamic programme of crt_scene_layout.h (minimum summed area of the wide nodes).  This program builds the SAME binary tree
 // from a scene file (host layer of libcrt.so, no GPU), collapses it with the same dynamic programme for W = 4 and W = 8, and walks both with the
 // same rays -- camera rays, one uniform-hemisphere bounce ray per primary hit and one ray towards a light sample per hit (the kernel's three
 // kinds) -- counting, per ray: wide nodes visited, child boxes tested (W per visit), leaf boxes hit.  CRT_TRAVERSAL_EXACT visits a node iff its
@@ -40,7 +40,7 @@ static bool hit_box(const Box& b, V3 o, V3 inv, V3 d)
 struct Wide { std::vector<Box> box; std::vector<int32_t> ref; }; // up to W children: ref >= 0 wide node, < 0 leaf
 struct WideTree { int W; std::vector<Wide> nodes; double summed_area = 0; };
 
-// the dynamic programme of crt_render.hip, for any W: which binary nodes become wide nodes so that the summed area of the wide nodes is least
+// the dynamic programme of crt_scene_layout.h, for any W: which binary nodes become wide nodes so that the summed area of the wide nodes is least
 static WideTree collapse(const std::vector<crtaccel::Node>& bin, int W)
 {
     const int A = (int)bin.size();

@@ -1,5 +1,5 @@
 // tools/with_bits_check.cpp -- CPU property check of crtaccel::with_bits (csrc/crt_accel.h), the helper that moves a plane of the
-// four-wide tree outwards to the nearest value whose low 12 mantissa bits carry a chunk of child indices (nodes4i, crt_render.hip).
+// four-wide tree outwards to the nearest value whose low 12 mantissa bits carry a chunk of child indices (nodes4i, crt_scene_layout.h).
 // For every input and all 4 096 chunks, in both directions:
 //   * ok: the result is finite, has the chunk in its low 12 bits, lies on the asked side of f (<= f down, >= f up) and is the NEAREST
 //     such value: the next value with the same low bits one chunk period further (across zero where the magnitude runs out) lies beyond f;
