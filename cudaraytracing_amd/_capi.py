@@ -8,7 +8,7 @@ import numpy as np
 from . import build as _build
 
 CRT_OK = 0
-ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP = -1, -2, -3   # include/crt.h: crt_status
+ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED = -1, -2, -3, -4   # include/crt.h: crt_status
 TRAVERSAL_EXACT = 0      # the default: provably the reference's frame
 TRAVERSAL_REFERENCE = 1
 TRAVERSAL_FAST = 2       # + distance pruning (measured rate of lost rays, include/crt.h)
@@ -148,6 +148,23 @@ class DenoiseInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AdaptiveParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("step_samples", C.c_uint32), ("threshold", C.c_float), ("mean_floor", C.c_float)]
+
+
+ADAPTIVE_PASSES_REPORTED = 64
+
+
+class AdaptiveInfo(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("pass_pixels", C.c_uint32 * ADAPTIVE_PASSES_REPORTED), ("paths", C.c_uint64),
+                ("paths_uniform", C.c_uint64), ("kernel_ms", C.c_float), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "pass_pixels"}
+        d["pass_pixels"] = [int(x) for x in self.pass_pixels[:max(0, min(self.passes - 1, ADAPTIVE_PASSES_REPORTED))]]
+        return d
+
+
 # the buffers of crt_aov_buffers: name -> (values per pixel, numpy type)
 AOV_BUFFERS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "coverage": (1, np.float32),
                "tri": (1, np.int32), "material": (1, np.int32)}
@@ -170,7 +187,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
-           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_multi_create", "crt_multi_destroy",
+           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
@@ -214,6 +231,11 @@ def lib():
     L.crt_preview_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.crt_variance.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     L.crt_variance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.crt_adaptive_defaults.argtypes = [C.POINTER(AdaptiveParams)]
+    L.crt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
+    L.crt_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdaptiveInfo)]
     L.crt_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovInfo)]
     L.crt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.c_void_p,
                                         C.POINTER(AovInfo)]

@@ -178,6 +178,8 @@ class Render:
         self.aov_buffers = None
         self.denoise_info = None
         self.variance_buffer = None
+        self.samples_buffer = None
+        self.adaptive_info = None
 
     def _handle(self, what):
         """The crt_scene* of this renderer; raises when there is none (freed, or a MultiRender, whose handle is a crt_multi*)."""
@@ -263,6 +265,29 @@ class Render:
         done = C.c_uint32(0)
         capi.check(capi.lib().crt_variance(h_, capi.ptr(var), C.byref(done)), "crt_variance")
         return var, int(done.value)
+
+    def run_view_adaptive(self, eye_pos, inv_view_mat, fovY, min_samples=None, step_samples=None, threshold=None, mean_floor=None,
+                          want_variance=False, width=None, height=None):
+        """Variance-driven adaptive sampling (crt_render_adaptive, contract: include/crt.h): every pixel gets min_samples samples, then
+        step_samples more per pass until the standard error of its mean is at most threshold x (mean + mean_floor) or it has all
+        self.spp.  None settings take crt_adaptive_defaults.  Returns the RGB8 frame (H, W, 3); self.mean_buffer is its mean,
+        self.samples_buffer the samples per pixel (H, W) uint32, self.variance_buffer (want_variance) the variance of that mean
+        (H, W, 3), self.adaptive_info the crt_adaptive_info dict.  Ends a progressive render in flight on the handle."""
+        h_ = self._handle("run_view_adaptive")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        ap = _adaptive_params(min_samples, step_samples, threshold, mean_floor)
+        w, h = prm.width, prm.height
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        mean = np.zeros((h, w, 3), dtype=np.float32)
+        samples = np.zeros((h, w), dtype=np.uint32)
+        var = np.zeros((h, w, 3), dtype=np.float32) if want_variance else None
+        info = capi.AdaptiveInfo()
+        capi.check(capi.lib().crt_render_adaptive(h_, C.byref(cam), C.byref(prm), C.byref(ap), capi.ptr(rgb), capi.ptr(mean), capi.ptr(samples),
+                                                  capi.ptr(var), C.byref(info)), "crt_render_adaptive")
+        self.frame_buffer, self.mean_buffer, self.samples_buffer, self.variance_buffer = rgb, mean, samples, var
+        self.adaptive_info = info.as_dict()
+        return rgb
 
     def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
                        want_variance=False, stats=False):
@@ -487,6 +512,9 @@ class MultiRender(Render):
     def run_view_range(self, *a, **k):
         raise NotImplementedError("progressive ranges are a single-device interface (crt_render_range)")
 
+    def run_view_adaptive(self, *a, **k):
+        raise NotImplementedError("adaptive sampling is a single-device interface (crt_render_adaptive)")
+
     def preview(self, *a, **k):
         raise NotImplementedError("previews are a single-device interface (crt_preview)")
 
@@ -541,6 +569,22 @@ def write_pfm(path, data):
         raise ValueError("write_pfm needs an (H, W) or (H, W, 3) array, got %r" % (a.shape,))
     ch = 1 if a.ndim == 2 else a.shape[2]
     capi.check(capi.lib().crt_write_pfm(os.fsencode(path), a.shape[1], a.shape[0], ch, capi.ptr(a)), "crt_write_pfm")
+
+
+def adaptive_defaults():
+    """crt_adaptive_defaults as a dict: min_samples, step_samples, threshold, mean_floor."""
+    p = capi.AdaptiveParams()
+    capi.check(capi.lib().crt_adaptive_defaults(C.byref(p)), "crt_adaptive_defaults")
+    return {n: getattr(p, n) for n, _ in p._fields_}
+
+
+def _adaptive_params(min_samples=None, step_samples=None, threshold=None, mean_floor=None):
+    p = capi.AdaptiveParams()
+    capi.check(capi.lib().crt_adaptive_defaults(C.byref(p)), "crt_adaptive_defaults")
+    for name, v in (("min_samples", min_samples), ("step_samples", step_samples), ("threshold", threshold), ("mean_floor", mean_floor)):
+        if v is not None:
+            setattr(p, name, int(v) if name.endswith("samples") else float(v))
+    return p
 
 
 def denoise_defaults():

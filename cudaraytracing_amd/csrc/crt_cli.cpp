@@ -8,6 +8,11 @@
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
 //           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
+//           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]
+// --adaptive THRESHOLD renders the frame with variance-driven adaptive sampling (crt_render_adaptive, one device): --spp is the cap, a
+// pixel stops once the standard error of its mean is at most THRESHOLD x (mean + floor); --adaptive-min / --adaptive-step override the
+// warm-up and the samples per pass of crt_adaptive_defaults, --adaptive-samples PATH writes the samples per pixel as a 1-channel PFM.
+// --variance, --denoise and --aov work on the adaptive frame as on the uniform one.
 // --variance PATH renders with CRT_FLAG_VARIANCE (the frame is the same bits) and writes the per-pixel variance of the mean
 // (crt_variance, one device) as a 3-channel PFM.  --denoise-variance makes --denoise use the variance-guided filter (crt_denoise_var,
 // its own defaults; --denoise-iterations / --denoise-sigma override them as well).
@@ -34,13 +39,17 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
-                             "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n", argv[0]);
+                             "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
+                             "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n", argv[0]);
         return 2;
     }
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, denoise, variance;
+        std::string out = "out.png", base_dir = ".", aov, denoise, variance, adaptive_samples;
+        crt_adaptive_params ad;
+        crt_adaptive_defaults(&ad);
+        bool adaptive = false, ad_option = false;
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false;
@@ -87,6 +96,10 @@ int main(int argc, char** argv)
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
             else if (a == "--denoise-variance") denoise_var = true;
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
+            else if (a == "--adaptive") { need(i, 1); ad.threshold = std::strtof(argv[++i], nullptr); adaptive = true; }
+            else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
+            else if (a == "--adaptive-step") { need(i, 1); ad.step_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
+            else if (a == "--adaptive-samples") { need(i, 1); adaptive_samples = argv[++i]; ad_option = true; }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
@@ -120,6 +133,8 @@ int main(int argc, char** argv)
         if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
         if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
         if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
+        if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
+        if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step and --adaptive-samples need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
         const bool want_var = !variance.empty() || denoise_var;
         {
@@ -139,11 +154,18 @@ int main(int argc, char** argv)
         crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
         float fov_y = task.fov_y * (float)M_PI / 180; // src/main.cu:278
         auto t0 = std::chrono::high_resolution_clock::now();
-        render.run_view(task.eye_pos, inv_view, fov_y);
+        if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
+        else render.run_view(task.eye_pos, inv_view, fov_y);
         std::chrono::duration<double> dt = std::chrono::high_resolution_clock::now() - t0;
-        const crt_stats& st = render.last_stats();
-        std::printf("render cost: %.6f seconds (device %.3f ms, %llu rays, %.1f Mrays/s)\n", dt.count(), st.total_ms,
-                    (unsigned long long)st.rays, st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0);
+        if (adaptive) {
+            const crt_adaptive_info& ai = render.last_adaptive_info();
+            std::printf("render cost: %.6f seconds (device %.3f ms, adaptive: %u passes, %llu of %llu paths)\n", dt.count(), ai.total_ms, ai.passes,
+                        (unsigned long long)ai.paths, (unsigned long long)ai.paths_uniform);
+        } else {
+            const crt_stats& st = render.last_stats();
+            std::printf("render cost: %.6f seconds (device %.3f ms, %llu rays, %.1f Mrays/s)\n", dt.count(), st.total_ms,
+                        (unsigned long long)st.rays, st.total_ms > 0 ? st.rays / st.total_ms / 1e3 : 0.0);
+        }
         if (multi) {
             const crt_multi_info& mi = render.last_multi_info();
             std::printf("ranks: %u, gather: %s, rccl ranks: %u (rccl %d), %llu B per rank, render %.3f ms + gather %.3f ms\n", mi.n_ranks,
@@ -157,6 +179,13 @@ int main(int argc, char** argv)
             const int rc = crt_write_pfm(variance.c_str(), task.width, task.height, 3, render.variance());
             if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the variance file failed: ") + crt_last_error());
             std::printf("%s\n", variance.c_str());
+        }
+        if (!adaptive_samples.empty()) {
+            std::vector<float> ns((size_t)task.width * task.height);
+            for (size_t k = 0; k < ns.size(); k++) ns[k] = (float)render.get_samples_buffer()[k];
+            const int rc = crt_write_pfm(adaptive_samples.c_str(), task.width, task.height, 1, ns.data());
+            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the samples file failed: ") + crt_last_error());
+            std::printf("%s\n", adaptive_samples.c_str());
         }
         if (!aov.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
         if (!aov.empty()) {

@@ -4,19 +4,6 @@
 
 namespace crtk {
 
-__device__ __forceinline__ FastDiv make_fastdiv_dev(uint32_t d)
-{
-    // k_accumulate runs once per pixel: derive the magic on the fly (same formula as make_fastdiv)
-    uint32_t l = d > 1 ? 32u - (uint32_t)__clz((int)(d - 1)) : 0u;
-    FastDiv f;
-    f.m = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-    f.sh = (l < 1 ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 8);
-    return f;
-}
-
-__device__ __forceinline__ float acc_load(const float* p) { return __uint_as_float(__hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
-__device__ __forceinline__ void acc_store(float* p, const float v) { __hip_atomic_store((unsigned int*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 // VAR (CRT_FLAG_VARIANCE): beside c, the sum of squares q = q + x * x of the same quotients x = L_k / spp, carried across chunks in the
 // planes of `qacc` as c is in A.accum; the last chunk then leaves c and q on the handle for crt_variance.  Without VAR the code is
 // what it was before the flag existed.
@@ -68,12 +55,6 @@ __global__ __launch_bounds__(256) void k_accumulate_var(const AParams A, float* 
 
 // crt_variance (contract: include/crt.h): the variance of the mean from the handle's sums c (A.accum) and q, n = samples so far, written
 // to A.out_mean in the frame's layout (slot -> pixel as k_preview; padding slots of a tiled shard +0).  Reads the sums only.
-__device__ __forceinline__ float variance_of(const float c, const float q, const float fn, const float rr)
-{
-    float d = fn * q - c * c;
-    d = d < 0.0f ? 0.0f : d;
-    return (rr * d) / (fn - 1.0f);
-}
 __global__ __launch_bounds__(256) void k_variance(const AParams A, const float* const qacc, const float fn, const float fs)
 {
     uint32_t slot = blockIdx.x * 256u + threadIdx.x;

@@ -678,6 +678,29 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view failed: ") + crt_last_error());
 }
 
+void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_view_adaptive: adaptive sampling is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view_adaptive after free()");
+    crt_camera cam;
+    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
+    cam.fov_y = fovY;
+    crt_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags_ & CRT_FLAG_TRACE_ALL;
+    const size_t n = scene_->get_pixels();
+    samples_buffer_.assign(n, 0u);
+    variance_buffer_.clear();
+    std::vector<float> v(want_variance ? 3 * n : 0, 0.0f);
+    const int rc = crt_render_adaptive(device_scene_, &cam, &p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(),
+                                       want_variance ? v.data() : nullptr, &adaptive_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view_adaptive failed: ") + crt_last_error());
+    variance_buffer_.swap(v);
+}
+
 void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)
 {
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov: the AOV pass is a single-device interface");

@@ -214,6 +214,12 @@ public:
     Render& operator=(const Render&) = delete;
     // run_view(eye_pos, inv_view_mat, fovY): inv_view column-major, fovY in radians
     void run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY);
+    // the adaptive frame of crt_render_adaptive (ap: crt_adaptive_defaults with overrides) in place of run_view's: frame and mean buffers as
+    // run_view leaves them, the samples per pixel in get_samples_buffer, and with want_variance the variance of the mean in variance();
+    // CRT_FLAG_STATS / _BOUNDED_RADIANCE do not apply; one device only
+    void run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance = false);
+    const uint32_t* get_samples_buffer() const { return samples_buffer_.data(); } // W x H, after run_view_adaptive
+    const crt_adaptive_info& last_adaptive_info() const { return adaptive_info_; }
     // first-hit albedo, normal and depth of the frame run_view draws with the same camera and settings (crt_render_aov); one device only
     void run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY);
     const float* get_albedo_buffer() const { return albedo_buffer_.data(); } // W x H x 3, row 0 = image top
@@ -266,7 +272,9 @@ private:
     std::vector<float> albedo_buffer_, normal_buffer_, depth_buffer_;
     std::vector<unsigned char> denoised_buffer_;
     std::vector<float> denoised_mean_buffer_;
-    std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame
+    std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame (run_view_adaptive fills it itself)
+    std::vector<uint32_t> samples_buffer_;
+    crt_adaptive_info adaptive_info_{};
     int device_ = 0;
     crt_denoise_info denoise_info_{};
     crt_stats stats_{};

@@ -102,6 +102,28 @@ __device__ __forceinline__ uint8_t tonemap(float c)
     return to_u8(255 * det_powf(cl, 0.6f));
 }
 
+// shared by the per-pixel-slot kernels of crt_frame.hip and crt_adaptive.hip
+__device__ __forceinline__ FastDiv make_fastdiv_dev(uint32_t d)
+{
+    // k_accumulate runs once per pixel: derive the magic on the fly (same formula as make_fastdiv)
+    uint32_t l = d > 1 ? 32u - (uint32_t)__clz((int)(d - 1)) : 0u;
+    FastDiv f;
+    f.m = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
+    f.sh = (l < 1 ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 8);
+    return f;
+}
+
+__device__ __forceinline__ float acc_load(const float* p) { return __uint_as_float(__hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
+__device__ __forceinline__ void acc_store(float* p, const float v) { __hip_atomic_store((unsigned int*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the variance of the mean from the sums c and q (contract: crt_variance, include/crt.h); rr = (fs / fn)^2
+__device__ __forceinline__ float variance_of(const float c, const float q, const float fn, const float rr)
+{
+    float d = fn * q - c * c;
+    d = d < 0.0f ? 0.0f : d;
+    return (rr * d) / (fn - 1.0f);
+}
+
 
 // wavefront pipeline (crt_wavefront.hip)
 #define REFILL_MIN 32
@@ -151,6 +173,28 @@ struct AovParams {
 };
 void launch_aov_rays(const AovParams& A, hipStream_t st);
 void launch_aov_resolve(const AovParams& A, hipStream_t st);
+
+// adaptive sampling (crt_adaptive.hip; host side: crt_render_adaptive in crt_render.hip; contract: include/crt.h).  Beside the frame's
+// sums c (A.accum) and q (qacc) the handle keeps, per pixel slot, whether the pixel still takes samples and how many it has; a pass
+// renders the slots of `list`.  All of these live in uncached memory and are accessed with agent-scope atomics only, as the sums are.
+struct AdaptiveParams {
+    AParams A;               // the frame's layout and sums; L, chunk_samples: the chunk k_adaptive_accumulate folds in
+    float* qacc;
+    uint32_t* active;        // [nslots] 1 = the pixel takes the next pass's samples (padding slots: 0)
+    uint32_t* nsamp;         // [nslots] n_p so far
+    uint32_t* list;          // [count] the active slots, in any order (k_adaptive_select)
+    unsigned int* count;
+    uint32_t n;              // samples every active pixel has (k_adaptive_accumulate: after its chunk)
+    float threshold, mean_floor;
+    uint32_t* out_samples;   // k_adaptive_resolve: beside A.out_rgb / A.out_mean (any may be null)
+    float* out_variance;
+};
+void launch_adaptive_init(const AdaptiveParams& D, hipStream_t st);       // after the warm-up: every pixel active, n_p = D.n
+void launch_adaptive_select(const AdaptiveParams& D, hipStream_t st);     // the stop criterion at n = D.n; compacts the active slots into list / count
+// item_list[pos] = the frame's work item (sample s of the chunk, slot list[a]) of cursor position pos = s * n_active + a
+void launch_adaptive_items(uint32_t* item_list, const uint32_t* list, uint32_t n_active, uint32_t n_items, uint32_t nslots, hipStream_t st);
+void launch_adaptive_accumulate(const AdaptiveParams& D, hipStream_t st); // the chunk's samples into c and q of the active slots
+void launch_adaptive_resolve(const AdaptiveParams& D, hipStream_t st);    // mean, RGB, samples, variance in the output layout
 
 } // namespace crtk
 #endif

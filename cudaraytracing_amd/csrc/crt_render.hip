@@ -1,7 +1,7 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
-// pipeline, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*,
-// crt_render_aov*, crt_intersect, crt_device_*).  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live in
-// crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_aov.hip.
+// pipeline, the passes of an adaptive frame, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*,
+// crt_render_adaptive*, crt_preview*, crt_variance*, crt_render_aov*, crt_intersect, crt_device_*).  The scene handle is made in
+// crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_aov.hip.
 #include "crt_scene.h"
 
 #include <algorithm>
@@ -212,6 +212,15 @@ AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh)
     return A;
 }
 
+// A pass of crt_render_adaptive, as render_impl sees it: a sample range of a frame with CRT_FLAG_VARIANCE whose sums are resolved by
+// the adaptive loop, not by the range that ends at spp.  list == nullptr: the warm-up, every pixel slot takes the range; otherwise only
+// the n_active slots of `list` (device memory) do, and D names the planes k_adaptive_accumulate updates.
+struct AdaptivePass {
+    const uint32_t* list;
+    uint32_t n_active;
+    AdaptiveParams D;
+};
+
 // One call of render_impl, as its two pipelines see it
 struct Frame {
     crt_scene* sc;
@@ -226,6 +235,8 @@ struct Frame {
     RingPlan ring;
     bool want_stats, tiled, want_var, var_frame;
     AParams A;
+    const AdaptivePass* ad; // crt_render_adaptive only
+    bool sparse() const { return ad && ad->list; }
 };
 
 // What both pipelines put into LParams: camera, size, shard, divisions, the handle's buffers
@@ -248,11 +259,11 @@ LParams frame_lparams(const Frame& f)
     return P;
 }
 
-// The work items of samples [s0, s0 + ns): one per pixel slot and sample, in ITEM_SHARDS cursor shards
-void set_chunk(LParams& P, uint32_t s0, uint32_t ns)
+// The work items of samples [s0, s0 + ns): one per pixel slot (an adaptive pass: per active slot) and sample, in ITEM_SHARDS cursor shards
+void set_chunk(LParams& P, uint32_t s0, uint32_t ns, uint32_t per_sample)
 {
     P.sample_begin = s0;
-    P.n_items = (uint32_t)((uint64_t)ns * P.nslots);
+    P.n_items = (uint32_t)((uint64_t)ns * per_sample);
     P.items_per_shard = ((P.n_items + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
 }
 
@@ -263,10 +274,14 @@ void accumulate_chunk(Frame& f, uint32_t s0, uint32_t ns)
     crt_scene* sc = f.sc;
     AParams& A = f.A;
     A.chunk_samples = ns;
-    A.first_chunk = s0 == 0; A.last_chunk = s0 + ns >= f.prm->spp;
+    A.first_chunk = s0 == 0; A.last_chunk = !f.ad && s0 + ns >= f.prm->spp; // (an adaptive frame is resolved by k_adaptive_resolve)
     if (f.ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
     if (!f.ring.samples || A.last_chunk) {
-        if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
+        if (f.sparse()) { // only the slots that took the pass
+            AdaptiveParams D = f.ad->D;
+            D.A = A; D.n = s0 + ns;
+            launch_adaptive_accumulate(D, f.st);
+        } else if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
         else launch_accumulate(A, f.st);
         HIP_CHECK(hipGetLastError());
         if (f.var_frame) { sc->var.valid = true; sc->var.set(f.prm, s0 + ns, f.tiled); }
@@ -337,7 +352,7 @@ void render_mega(Frame& f)
     const RingPlan& ring = f.ring;
     hipStream_t st = f.st;
     const bool timing = f.stats != nullptr;
-    const uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots : f.cap;
+    const uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots : f.sparse() ? (uint64_t)f.chunk * f.ad->n_active : f.cap;
     const MegaPlan mp = plan_mega3(sc, prm->traversal, f.want_stats, (prm->flags & CRT_FLAG_TRACE_ALL) != 0, false, ring.samples != 0, most_items, env_u32("CRT_MEGA_BLOCKS_PER_CU", 64));
     const uint32_t lanes = mp.lanes;
     sc->p_vx.ensure(lanes); sc->p_la.ensure(lanes); sc->p_cc.ensure(lanes); sc->p_id.ensure(lanes);
@@ -356,7 +371,7 @@ void render_mega(Frame& f)
     uint32_t launches = 0;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
-        set_chunk(P, s0, ns);
+        set_chunk(P, s0, ns, f.sparse() ? f.ad->n_active : P.nslots);
         if (ring.samples) { // cursor shard = ring.spsh pixel slots x ns samples
             P.items_per_shard = ring.spsh * ns;
             P.n_items = P.items_per_shard * ring.shards;
@@ -379,7 +394,15 @@ void render_mega(Frame& f)
         // the paths that stop at their first vertex are handed out last (k_order_items): 1 % of a whole C2 frame on one GPU,
         // 8 % of a rank's share on eight.  CRT_ITEM_ORDER=0 switches it off.
         P.item_list = nullptr;
-        {
+        if (f.sparse()) {
+            // an adaptive pass: the WHOLE cursor range goes through the list (order_window = the shard, so list index = cursor position),
+            // which names the frame's own work item (sample, slot) of every position: k_mega3 decodes it and writes L[item] as ever
+            P.order_window = P.items_per_shard;
+            sc->item_list.ensure(P.n_items);
+            launch_adaptive_items(sc->item_list.p, f.ad->list, f.ad->n_active, P.n_items, P.nslots, st);
+            HIP_CHECK(hipGetLastError());
+            P.item_list = sc->item_list.p;
+        } else {
             const char* eo = std::getenv("CRT_ITEM_ORDER");
             const bool order = !(eo && eo[0] == '0');
             if (order && P.n_items > 0) {
@@ -488,7 +511,7 @@ void render_wavefront(Frame& f)
     const int evs_per_half = 2 * kMaxBatch + 1;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
-        set_chunk(P, s0, ns);
+        set_chunk(P, s0, ns, P.nslots);
         HIP_CHECK(hipMemsetAsync(sc->item_next.p, 0, (size_t)ITEM_SHARDS * ITEM_STRIDE * sizeof(unsigned int), st));
         for (int h = 0; h < n_halves; h++) {
             PH[h] = P;
@@ -556,28 +579,37 @@ void render_wavefront(Frame& f)
     }
 }
 
-// Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
-// (temp_color += L_k / spp in sample order, Render.cuh:348); the range that ends at spp also tone-maps and writes the frame.
-int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats,
-                uint32_t s_begin = 0, uint32_t s_count = 0xffffffffu)
+// What crt_render refuses in a crt_params by itself (no scene, no sample range), before any device call
+int params_check(const crt_params* prm)
 {
-    if (!sc || !cam || !prm) return fail(CRT_ERR_INVALID_ARG, "crt_render: null argument");
-    if (s_count == 0xffffffffu) s_count = prm->spp > s_begin ? prm->spp - s_begin : 0;
-    if (s_count == 0 || (uint64_t)s_begin + s_count > prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render: sample range outside [0, spp)");
-    const uint32_t s_end = s_begin + s_count;
-    if (!d_rgb && s_end == prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render: null frame buffer");
     if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render: width, height and spp must be positive");
     if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, "crt_render: need rank < world");
     if (prm->light_sample_n < 0 || prm->light_sample_n > 4096) return fail(CRT_ERR_INVALID_ARG, "crt_render: light_sample_n must be in [0, 4096]");
     if ((uint64_t)prm->width * prm->height > 0xffffffffull) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 2^32 pixels");
     if (prm->traversal != CRT_TRAVERSAL_FAST && prm->traversal != CRT_TRAVERSAL_REFERENCE && prm->traversal != CRT_TRAVERSAL_EXACT)
         return fail(CRT_ERR_INVALID_ARG, "crt_render: unknown traversal mode");
+    if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, "crt_render: world > 1 needs CRT_FLAG_TILED_OUTPUT");
+    return CRT_OK;
+}
+
+// Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
+// (temp_color += L_k / spp in sample order, Render.cuh:348); the range that ends at spp also tone-maps and writes the frame.
+// ad: the range is a pass of crt_render_adaptive (AdaptivePass): nothing is tone-mapped, d_rgb / d_mean are not used.
+int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats,
+                uint32_t s_begin = 0, uint32_t s_count = 0xffffffffu, const AdaptivePass* ad = nullptr)
+{
+    if (!sc || !cam || !prm) return fail(CRT_ERR_INVALID_ARG, "crt_render: null argument");
+    if (s_count == 0xffffffffu) s_count = prm->spp > s_begin ? prm->spp - s_begin : 0;
+    if (s_count == 0 || (uint64_t)s_begin + s_count > prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render: sample range outside [0, spp)");
+    const uint32_t s_end = s_begin + s_count;
+    if (!d_rgb && s_end == prm->spp && !ad) return fail(CRT_ERR_INVALID_ARG, "crt_render: null frame buffer");
+    const int rc_prm = params_check(prm);
+    if (rc_prm != CRT_OK) return rc_prm;
     Frame f;
-    f.sc = sc; f.cam = cam; f.prm = prm; f.st = st; f.stats = stats; f.s_begin = s_begin; f.s_end = s_end;
+    f.sc = sc; f.cam = cam; f.prm = prm; f.st = st; f.stats = stats; f.s_begin = s_begin; f.s_end = s_end; f.ad = ad;
     f.want_stats = (prm->flags & CRT_FLAG_STATS) != 0;
     f.tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
     f.want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
-    if (prm->world > 1 && !f.tiled) return fail(CRT_ERR_INVALID_ARG, "crt_render: world > 1 needs CRT_FLAG_TILED_OUTPUT");
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
     // a range that does not start a frame adds to the accumulator: it must hold exactly the samples before the range, of this frame
     if (s_begin > 0 && !continues_frame(sc->acc, prm, s_begin, f.tiled)) {
@@ -616,6 +648,127 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         HIP_CHECK(hipMemsetAsync(sc->counters.p, 0, kCountersBytes, st));
         if (mega) render_mega(f);
         else render_wavefront(f);
+        return CRT_OK;
+    } catch (const HipFail& e) {
+        return fail_hip(e);
+    }
+}
+
+// ---------- crt_render_adaptive (contract: include/crt.h): passes of render_impl over the pixels a selection kernel leaves active ----------
+// Argument checks of both forms, before any device call.  The scene comes last so that the message names what is wrong with the other
+// arguments even where there is no scene.
+int adaptive_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, const void* out_rgb, const void* out_mean)
+{
+    if (!cam) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null camera");
+    if (!prm) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null params");
+    if (!ap) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null adaptive params");
+    if (!out_rgb && !out_mean) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: out_rgb and out_mean are both null");
+    if (ap->min_samples < 2 || ap->min_samples > prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: min_samples must be in [2, spp] (the variance needs two samples)");
+    if (ap->step_samples == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: step_samples must be positive");
+    if (!(ap->threshold >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: threshold must be >= 0 and not NaN");
+    if (!(ap->mean_floor >= 0.0f) || ap->mean_floor > FLT_MAX) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: mean_floor must be >= 0 and finite");
+    const int rc = params_check(prm);
+    if (rc != CRT_OK) return rc;
+    if (!sc) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null scene");
+    return CRT_OK;
+}
+
+// Pixels of the shard (its pixel slots without the padding of ragged tiles and of tiles beyond the frame)
+uint64_t shard_pixels(const crt_params* prm, const Shard& sh)
+{
+    uint64_t n = 0;
+    for (uint32_t lt = 0; lt < sh.local_tiles; lt++) {
+        const uint32_t tile = lt * prm->world + prm->rank;
+        if (tile >= sh.n_tiles) break;
+        const uint32_t ty = tile / sh.tiles_x, tx = tile - ty * sh.tiles_x;
+        n += (uint64_t)std::min<uint32_t>(CRT_TILE, prm->width - tx * CRT_TILE) * std::min<uint32_t>(CRT_TILE, prm->height - ty * CRT_TILE);
+    }
+    return n;
+}
+
+int adaptive_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean, void* d_samples,
+                  void* d_var, hipStream_t st, crt_adaptive_info* info)
+{
+    const int rc0 = adaptive_check(sc, cam, prm, ap, d_rgb, d_mean);
+    if (rc0 != CRT_OK) return rc0;
+    if (choose_pipeline(sc) != 4) return fail(CRT_ERR_UNSUPPORTED, "crt_render_adaptive: the fallback pipeline hands out its work items without the item list");
+    crt_params p = *prm; // the passes: ranges of a frame with the variance sums, without counters and without the commit ring
+    p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE);
+    const bool tiled = (p.flags & CRT_FLAG_TILED_OUTPUT) != 0;
+    const Shard sh = make_shard(p.width, p.height, p.world);
+    const uint32_t S = p.spp;
+    // whatever happens, no frame is in flight on the handle afterwards (the sums are an adaptive frame's: no range may continue them)
+    struct EndFrame {
+        crt_scene* sc;
+        ~EndFrame() { sc->acc.samples = 0; sc->var.valid = false; }
+    } end_frame{sc};
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (info) {
+            ensure_events(sc);
+            e0 = sc->ev[0]; e1 = sc->ev[1];
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        AdaptivePass pass;
+        std::memset(&pass, 0, sizeof(pass));
+        int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, 0, ap->min_samples, &pass); // the warm-up
+        if (rc != CRT_OK) return rc;
+        sc->ad_active.ensure_uncached(sh.nslots); sc->ad_nsamp.ensure_uncached(sh.nslots); sc->ad_list.ensure_uncached(sh.nslots);
+        sc->ad_count.ensure_uncached(1);
+        if (!sc->h_ad_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_ad_count, sizeof(unsigned int), hipHostMallocDefault));
+        FrameMark mark;
+        mark.set(&p, 0, tiled);
+        AdaptiveParams& D = pass.D;
+        D.A = frame_aparams(sc, mark, sh);
+        D.qacc = sc->accum_q.p;
+        D.active = sc->ad_active.p; D.nsamp = sc->ad_nsamp.p; D.list = sc->ad_list.p; D.count = sc->ad_count.p;
+        D.threshold = ap->threshold; D.mean_floor = ap->mean_floor;
+        D.n = ap->min_samples;
+        launch_adaptive_init(D, st);
+        HIP_CHECK(hipGetLastError());
+        crt_adaptive_info I;
+        std::memset(&I, 0, sizeof(I));
+        const uint64_t pixels = shard_pixels(&p, sh);
+        I.passes = 1; I.paths = pixels * ap->min_samples; I.paths_uniform = pixels * S;
+        double kernel_ms = 0.0;
+        bool kernel_unread = true; // a pass's launches have been enqueued whose time (ev_k0 .. ev_k1) has not been added yet
+        auto read_kernel_ms = [&]() { // after a synchronization
+            float ms = 0.0f;
+            if (info && kernel_unread) { HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1)); kernel_ms += ms; }
+            kernel_unread = false;
+        };
+        for (uint32_t n = ap->min_samples; n < S;) {
+            HIP_CHECK(hipMemsetAsync(sc->ad_count.p, 0, sizeof(unsigned int), st));
+            D.n = n;
+            launch_adaptive_select(D, st);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(sc->h_ad_count, sc->ad_count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of a pass: how many pixels go on
+            read_kernel_ms();
+            const uint32_t active = std::min<uint32_t>(*sc->h_ad_count, sh.nslots);
+            if (active == 0) break;
+            const uint32_t ns = std::min(ap->step_samples, S - n);
+            if (I.passes - 1u < CRT_ADAPTIVE_PASSES_REPORTED) I.pass_pixels[I.passes - 1u] = active;
+            pass.list = sc->ad_list.p; pass.n_active = active;
+            rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, n, ns, &pass);
+            if (rc != CRT_OK) return rc;
+            kernel_unread = true;
+            I.passes++; I.paths += (uint64_t)active * ns;
+            n += ns;
+        }
+        D.A.out_rgb = (uint8_t*)d_rgb; D.A.out_mean = (float*)d_mean;
+        D.out_samples = (uint32_t*)d_samples; D.out_variance = (float*)d_var;
+        launch_adaptive_resolve(D, st);
+        HIP_CHECK(hipGetLastError());
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            read_kernel_ms();
+            I.kernel_ms = (float)kernel_ms;
+            HIP_CHECK(hipEventElapsedTime(&I.total_ms, e0, e1));
+            *info = I;
+        }
         return CRT_OK;
     } catch (const HipFail& e) {
         return fail_hip(e);
@@ -790,6 +943,41 @@ int crt_render_range(crt_scene* sc, const crt_camera* cam, const crt_params* prm
         int rc = render_impl(sc, cam, prm, s.rgb.p, s.f32.p, nullptr, stats, sample_begin, sample_count);
         if (rc != CRT_OK) return rc;
         s.download(last ? out_rgb : nullptr, last ? out_mean : nullptr);
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_adaptive_defaults(crt_adaptive_params* ap)
+{
+    if (!ap) return fail(CRT_ERR_INVALID_ARG, "crt_adaptive_defaults: null argument");
+    ap->min_samples = 16; ap->step_samples = 64; ap->threshold = 0.05f; ap->mean_floor = 0.01f;
+    return CRT_OK;
+}
+
+int crt_render_adaptive_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean,
+                               void* d_samples, void* d_variance, void* stream, crt_adaptive_info* info)
+{
+    return adaptive_impl(sc, cam, prm, ap, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
+}
+
+int crt_render_adaptive(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, uint8_t* out_rgb, float* out_mean,
+                        uint32_t* out_samples, float* out_variance, crt_adaptive_info* info)
+{
+    const int rc0 = adaptive_check(sc, cam, prm, ap, out_rgb, out_mean);
+    if (rc0 != CRT_OK) return rc0;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
+        Staging s(npix, out_rgb != nullptr, out_mean != nullptr), v(npix, false, out_variance != nullptr);
+        DevBuf<uint32_t> n;
+        if (out_samples) n.alloc(npix);
+        const int rc = adaptive_impl(sc, cam, prm, ap, s.rgb.p, s.f32.p, n.p, v.f32.p, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        s.download(out_rgb, out_mean);
+        v.download(nullptr, out_variance);
+        if (out_samples) HIP_CHECK(hipMemcpy(out_samples, n.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);

@@ -62,6 +62,11 @@ struct crt_scene {
     // sums hold (crt_variance): samples so far of the frame the flag has been on for since sample 0; valid = the last render call had it
     crtk::DevBuf<float> accum_q;
     FrameMark var;
+    // crt_render_adaptive: per pixel slot whether it takes the next pass and its sample count, the compacted list of the active slots and
+    // its counter (uncached, agent-scope atomics only: crt_adaptive.hip), and the pinned word the counter is copied to once per pass
+    crtk::DevBuf<uint32_t> ad_active, ad_nsamp, ad_list;
+    crtk::DevBuf<unsigned int> ad_count;
+    unsigned int* h_ad_count = nullptr;
     std::vector<hipEvent_t> ev;
     ~crt_scene()
     {
@@ -72,6 +77,7 @@ struct crt_scene {
         if (ev_join) (void)hipEventDestroy(ev_join);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
         if (h_counters) (void)hipHostFree(h_counters);
+        if (h_ad_count) (void)hipHostFree(h_ad_count);
     }
 };
 

@@ -306,6 +306,70 @@ int crt_variance(crt_scene* scene, float* out_var, uint32_t* samples_done);
 /* d_var: a device buffer on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
 int crt_variance_device(crt_scene* scene, void* d_var, void* hip_stream, uint32_t* samples_done);
 
+/* Variance-driven adaptive sampling: one frame in which pixel p receives samples 0 .. n_p - 1 of its S = params->spp samples, n_p chosen
+ * per pixel by a stop criterion on the running sums of the crt_variance contract.  Sample k of pixel p is the path it is in crt_render's
+ * frame (same seed, same draws), S is the cap AND the divisor of every sample (x_k = L_k / (float)S, as the frame adds it), so a pixel
+ * that runs to the cap has the uniform frame's bits.  Operation by operation, every * + - / one IEEE fp32 operation, no FMA:
+ *   warm-up    every pixel gets samples 0 .. min_samples-1: c = c + x_k, q = q + x_k * x_k from +0.0f in sample order (the sums of
+ *              crt_variance; the warm-up IS a crt_render_range(0, min_samples) with CRT_FLAG_VARIANCE).  n = min_samples, every pixel active.
+ *   selection  while n < S, for each still-active pixel, with fn = (float)n, fs = (float)S:
+ *                r = fs / fn;  rr = r * r
+ *                per channel  d = fn * q - c * c;  d = d < 0.0f ? 0.0f : d;  var = (rr * d) / (fn - 1.0f)      (crt_variance's formula)
+ *                per channel  p = c * r                                                                          (crt_preview's mean)
+ *                v = (var.x + var.y) + var.z;   m = (p.x + p.y) + p.z
+ *                t = threshold * (m + mean_floor);   stop = v <= t * t
+ *              i.e. the pixel stops once the standard error of its mean is at most threshold x (mean + mean_floor), channels summed.
+ *              A pixel stays active iff it was active and !stop; NaN never satisfies <=, so a NaN pixel runs to the cap; a stopped pixel
+ *              never becomes active again.  No active pixel left: the loop ends.
+ *   step       ns = min(step_samples, S - n): the active pixels get samples n .. n+ns-1 added to c and q in sample order; n += ns (all
+ *              active pixels share n).
+ *   outputs    in the layout of crt_render's buffers (row-major, or the shard's compact tiles with CRT_FLAG_TILED_OUTPUT and rank / world;
+ *              padding slots 0 / +0.0f):  out_samples = n_p;  out_mean = c * ((float)S / (float)n_p) per channel -- one division, one
+ *              multiply, exactly c when n_p = S;  out_rgb = the frame's tone map of out_mean;  out_variance (3 floats per pixel) = the
+ *              variance formula above with fn = (float)n_p, what crt_denoise_var takes.  out_samples and out_variance may be NULL;
+ *              out_rgb and out_mean not both.
+ * The criterion looks at one pixel only, so rank / world shards and the chunking of a pass cannot change a result.
+ * Flags: CRT_FLAG_VARIANCE is implied; CRT_FLAG_STATS and CRT_FLAG_BOUNDED_RADIANCE are ignored (there is no commit ring).
+ * Handle state: afterwards NO frame is in flight on the handle -- crt_preview, crt_variance and a range with sample_begin > 0 are refused
+ * as after a finished frame, and a later crt_render is unaffected.  An adaptive call in the middle of a progressive frame ends that frame.
+ * Each pass traces only the active pixels' paths: a selection kernel compacts them, a list maps the render kernel's work cursor onto
+ * (sample, active pixel), and the per-path radiance buffer (sized for step_samples x pixel slots, as a uniform chunk) is written
+ * sparsely; the list costs 4 B per path of a pass beside it.
+ * CRT_ERR_INVALID_ARG, before any device call: a null scene, camera, params or adaptive params; both image outputs NULL; min_samples < 2
+ * or > spp; step_samples 0; a threshold that is negative or NaN (+inf is allowed: every pixel stops after the warm-up); a mean_floor
+ * that is negative or not finite; anything crt_render refuses.  CRT_ERR_UNSUPPORTED: the fallback pipeline (CRT_PIPELINE=2, or a scene
+ * beyond the render kernel's limits), which hands out its work items without the list.  crt_multi has no adaptive form.
+ * Cost: every pass is a launch of the persistent render kernel and ends with that kernel's tail, about 2 ms on the 800x600 frames
+ * measured whatever the number of active pixels, so the step size sets the price of the call (docs/experiments.md, "Adaptive sampling").
+ * crt_adaptive_defaults fills min_samples 16, step_samples 64, threshold 0.05, mean_floor 0.01.  The step is the one setting that has been
+ * measured -- 4, 16, 64 and 248 on 800x600 frames of the two shipped scenes with a cap of 512, where 16 took 1.4 times as long as 64 for
+ * the same error; the other three are a starting point that has NOT been tuned on any scene. */
+typedef struct {
+    uint32_t min_samples;   /* warm-up: every pixel gets samples [0, min_samples); 2 <= min_samples <= spp */
+    uint32_t step_samples;  /* samples a still-active pixel gets per pass; >= 1 */
+    float    threshold;     /* relative standard error of the pixel's mean at which it stops; >= 0, not NaN, +inf allowed */
+    float    mean_floor;    /* added to the mean in the criterion so dark pixels can stop; >= 0, finite */
+} crt_adaptive_params;
+#define CRT_ADAPTIVE_PASSES_REPORTED 64
+typedef struct {
+    uint32_t passes;        /* render passes that ran, the warm-up included */
+    uint32_t pass_pixels[CRT_ADAPTIVE_PASSES_REPORTED]; /* pixels still active in adaptive pass 0, 1, ... (the warm-up is not listed; passes beyond 64 are not recorded) */
+    uint64_t paths;         /* sum of n_p over the shard's pixels = paths traced */
+    uint64_t paths_uniform; /* pixels x spp: what crt_render would have traced */
+    float kernel_ms, total_ms; /* sum of the render kernel's launches (first launch's start to last launch's end of every pass) / the whole
+                                  device pipeline of the call, HIP events on its stream */
+} crt_adaptive_info;
+int crt_adaptive_defaults(crt_adaptive_params* params);
+/* host buffers: out_rgb 3 bytes, out_mean 3 floats, out_samples 1 uint32, out_variance 3 floats per pixel (or pixel slot); info optional */
+int crt_render_adaptive(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
+                        uint8_t* out_rgb, float* out_mean, uint32_t* out_samples, float* out_variance, crt_adaptive_info* info);
+/* Device buffers on the scene's device, work enqueued on hip_stream (NULL = default stream).  Unlike crt_render_device this form
+ * SYNCHRONIZES hip_stream once per pass: the host reads the number of active pixels (one 4-byte copy into pinned memory) to size the next
+ * pass and to end the loop.  The outputs are enqueued after the last pass without a further synchronization, unless info != NULL (the
+ * call then synchronizes once more to read the timers). */
+int crt_render_adaptive_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
+                               void* d_rgb, void* d_mean, void* d_samples, void* d_variance, void* hip_stream, crt_adaptive_info* info);
+
 /* First-hit auxiliary buffers (AOVs: the guides of a denoiser, depth and coverage for compositing, IDs for masks), aligned sample for
  * sample with the frame crt_render draws with the same camera / params.  Per pixel, the S = params->spp camera rays of samples
  * k = 0 .. S-1 -- the primary rays of the frame's paths: same seed, jitter draws and arithmetic -- are traced for their closest hit

@@ -1,0 +1,499 @@
+"""Variance-driven adaptive sampling: crt_render_adaptive / crt_render_adaptive_device / crt_adaptive_defaults (include/crt.h),
+Render.run_view_adaptive and adaptive_defaults in Python, crt_cli --adaptive.
+
+The expected values come from the oracle's per-path radiance (OracleScene.render(want_L=True) -> (h, w, S, 3)): the contract of
+include/crt.h is restated below in numpy float32, one ufunc per IEEE operation -- the warm-up sums of util.restated_sums, the stop
+criterion, the masked steps, the outputs -- and the device result must match it on uint32 views (NaN matches NaN), the RGB frame the
+oracle's tone map of the restated mean.
+
+The shape of the GPU tests is fixed: both shipped scenes at 37x27 (ragged tiles), cap 29, warm-up 4, step 6 (last step 28 -> 29),
+threshold 0.2, floor 0.01, seed 0.  What the restatement gives there, computed on the CPU with the oracle:
+    cornell-box   pixels per n_p (4 / 10 / 16 / 22 / 28 / 29) 427 / 107 / 96 / 52 / 35 / 282    pass_pixels [572, 465, 369, 317, 282]
+    veach-mis                                                  440 / 281 / 128 / 61 / 27 / 62     pass_pixels [559, 278, 150, 89, 62]
+"""
+import ctypes as C
+import functools
+import inspect
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import util
+from util import assert_bits, restated_sums
+
+F = np.float32
+SCENES = ["cornell-box", "veach-mis"]
+ADAPTIVE_EXPORTS = ("crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device")
+W, H, S = 37, 27, 29
+AD = dict(min_samples=4, step_samples=6, threshold=0.2, mean_floor=0.01)
+STOPS = (4, 10, 16, 22, 28, 29)
+EXPECTED = {"cornell-box": ((427, 107, 96, 52, 35, 282), [572, 465, 369, 317, 282]),
+            "veach-mis": ((440, 281, 128, 61, 27, 62), [559, 278, 150, 89, 62])}
+
+
+def variance_of_sums(c, q, fn, r):
+    """crt_variance's formula; fn, r: float32 scalars or (h, w, 1) arrays"""
+    d = fn * q - c * c
+    d = np.where(d < F(0.0), F(0.0), d)
+    return ((r * r) * d) / (fn - F(1.0))
+
+
+def restated_adaptive(L, S, min_samples, step_samples, threshold, mean_floor):
+    """The contract of crt_render_adaptive on per-path radiance L (h, w, S, 3): dict of samples (h, w) uint32, mean, variance
+    (h, w, 3) float32, rgb, pass_pixels, passes, paths."""
+    thr, floor, fs = F(threshold), F(mean_floor), F(S)
+    with np.errstate(all="ignore"):
+        c, q = restated_sums(L, S, min_samples)
+        n = min_samples
+        nsamp = np.full(L.shape[:2], n, dtype=np.uint32)
+        active = np.ones(L.shape[:2], dtype=bool)
+        pass_pixels = []
+        while n < S:
+            fn = F(n)
+            r = fs / fn
+            var = variance_of_sums(c, q, fn, r)
+            p = c * r
+            v = (var[..., 0] + var[..., 1]) + var[..., 2]
+            m = (p[..., 0] + p[..., 1]) + p[..., 2]
+            t = thr * (m + floor)
+            stop = v <= t * t
+            active = active & ~stop
+            if not active.any():
+                break
+            pass_pixels.append(int(active.sum()))
+            ns = min(step_samples, S - n)
+            a3 = active[..., None]
+            for k in range(n, n + ns):
+                x = L[:, :, k, :] / fs
+                c = np.where(a3, c + x, c)
+                q = np.where(a3, q + x * x, q)
+            n += ns
+            nsamp[active] = n
+        fn = nsamp.astype(F)[..., None]
+        r = fs / fn
+        mean = c * r
+        var = variance_of_sums(c, q, fn, r)
+    for a in (c, q, mean, var, v):
+        assert a.dtype == F
+    return dict(samples=nsamp, mean=mean, variance=var, rgb=O.tonemap(mean), pass_pixels=pass_pixels, passes=1 + len(pass_pixels),
+                paths=int(nsamp.astype(np.uint64).sum()), c=c)
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_adaptive_entry_points_are_exported():
+    lib = capi.lib()
+    for name in ADAPTIVE_EXPORTS:
+        assert name in capi.EXPORTS
+        getattr(lib, name)
+    lib.crt_abi_version.restype = C.c_int
+    assert lib.crt_abi_version() == 5 == capi.ABI_VERSION
+    assert hasattr(crt, "adaptive_defaults")
+    sig = inspect.signature(crt.Render.run_view_adaptive).parameters
+    for name in ("min_samples", "step_samples", "threshold", "mean_floor", "want_variance", "width", "height"):
+        assert name in sig
+    with pytest.raises(NotImplementedError):       # (like its siblings: no handle is looked at)
+        crt.MultiRender.run_view_adaptive(None, None, None, 0.0)
+    assert C.sizeof(capi.AdaptiveParams) == 16
+    assert C.sizeof(capi.AdaptiveInfo) == 4 + 4 * 64 + 4 + 8 + 8 + 4 + 4   # (4 bytes of padding before the first uint64_t)
+    assert capi.AdaptiveInfo.paths.offset == 264
+
+
+def test_adaptive_defaults_pass_their_own_rules():
+    d = crt.adaptive_defaults()
+    assert set(d) == {"min_samples", "step_samples", "threshold", "mean_floor"}
+    assert d["min_samples"] >= 2 and d["step_samples"] >= 1
+    assert d["threshold"] >= 0 and np.isfinite(d["mean_floor"]) and d["mean_floor"] >= 0
+    assert (d["min_samples"], d["step_samples"]) == (16, 64) and F(d["threshold"]) == F(0.05) and F(d["mean_floor"]) == F(0.01)
+    assert capi.lib().crt_adaptive_defaults(None) == capi.ERR_INVALID_ARG
+
+
+def test_adaptive_refusals_come_before_any_device_call():
+    """Every refusal of the contract with a null scene (there is no device call to make): CRT_ERR_INVALID_ARG, the outputs untouched, and
+    crt_last_error names the argument."""
+    lib = capi.lib()
+    n = 8 * 8
+    rgb, mean = np.full(n * 3, 9, dtype=np.uint8), np.full(n * 3, 9, dtype=F)
+    samples, var = np.full(n, 9, dtype=np.uint32), np.full(n * 3, 9, dtype=F)
+    info = capi.AdaptiveInfo()
+    info.passes = 77
+    cam = capi.Camera()
+
+    def call(form, scene=None, cam_=cam, prm=None, ap=None, out_rgb=rgb, out_mean=mean, no_prm=False, no_ap=False, **kw):
+        p = capi.Params(8, 8, 16, 0.8, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+        for k, v_ in (prm or {}).items():
+            setattr(p, k, v_)
+        a = capi.AdaptiveParams(4, 2, 0.1, 0.01)
+        for k, v_ in (ap or {}).items():
+            setattr(a, k, v_)
+        tail = (C.byref(info),) if form == "crt_render_adaptive" else (None, C.byref(info))
+        rc = getattr(lib, form)(scene, C.byref(cam_) if cam_ is not None else None, None if no_prm else C.byref(p), None if no_ap else C.byref(a),
+                                capi.ptr(out_rgb), capi.ptr(out_mean), capi.ptr(samples), capi.ptr(var), *tail)
+        return rc, lib.crt_last_error().decode()
+
+    cases = [(dict(), "scene"),
+             (dict(cam_=None), "camera"),
+             (dict(no_prm=True), "params"),
+             (dict(no_ap=True), "adaptive params"),
+             (dict(out_rgb=None, out_mean=None), "out_rgb and out_mean"),
+             (dict(ap=dict(min_samples=1)), "min_samples"),
+             (dict(ap=dict(min_samples=0)), "min_samples"),
+             (dict(ap=dict(min_samples=17)), "min_samples"),
+             (dict(ap=dict(step_samples=0)), "step_samples"),
+             (dict(ap=dict(threshold=-0.5)), "threshold"),
+             (dict(ap=dict(threshold=float("nan"))), "threshold"),
+             (dict(ap=dict(mean_floor=-1.0)), "mean_floor"),
+             (dict(ap=dict(mean_floor=float("inf"))), "mean_floor"),
+             (dict(ap=dict(mean_floor=float("nan"))), "mean_floor"),
+             # what crt_render refuses
+             (dict(prm=dict(width=0)), "width"),
+             (dict(prm=dict(spp=0)), "min_samples"),            # (no min_samples fits a cap of 0)
+             (dict(prm=dict(world=0)), "rank < world"),
+             (dict(prm=dict(rank=1)), "rank < world"),
+             (dict(prm=dict(world=2)), "CRT_FLAG_TILED_OUTPUT"),
+             (dict(prm=dict(light_sample_n=-1)), "light_sample_n"),
+             (dict(prm=dict(traversal=7)), "traversal")]
+    for form in ("crt_render_adaptive", "crt_render_adaptive_device"):
+        for kw, word in cases:
+            rc, err = call(form, **kw)
+            assert rc == capi.ERR_INVALID_ARG, (form, kw, rc, err)
+            assert word in err, (form, kw, err)
+        # accepted values are not what is refused: +inf threshold, threshold 0, floor 0, min_samples == spp, one of the two image outputs
+        for kw in (dict(ap=dict(threshold=float("inf"))), dict(ap=dict(threshold=0.0, mean_floor=0.0)), dict(ap=dict(min_samples=16)),
+                   dict(out_rgb=None), dict(out_mean=None)):
+            rc, err = call(form, **kw)
+            assert rc == capi.ERR_INVALID_ARG and "null scene" in err, (form, kw, err)
+    assert (rgb == 9).all() and (mean == 9).all() and (samples == 9).all() and (var == 9).all() and info.passes == 77
+
+
+def test_restatement_stops_at_the_relative_standard_error():
+    """The restated criterion against float64 on made-up samples (no oracle, no device): a pixel with n_p < S stopped because the
+    standard error of its mean (channels summed: sqrt of the summed variances of the mean) was at most threshold x (summed mean +
+    floor) at n_p, and was above it at every earlier decision; a pixel at the cap was above it at every decision.  Pixels whose float64
+    ratio lies within 1e-3 of the threshold at a decision are left out of that decision's check: the fp32 sums may fall on either side
+    (their relative error is a few 2^-24 x n, see tests/test_variance.py)."""
+    rng = np.random.default_rng(23)
+    S_, mn, st, thr, floor = 23, 3, 5, 0.25, 0.02
+    L = (rng.random((12, 14, S_, 3)) * rng.random((12, 14, 1, 1)) * 4).astype(F)
+    L[0, 0] = 0                       # all samples +0: variance 0 <= (thr x floor)^2, stops after the warm-up
+    L[0, 1] = 1.5                     # constant: variance 0 up to rounding
+    L[0, 2, ::2] = 0                  # a noisy one
+    L[0, 3, :, :] = np.nan            # NaN never satisfies <=: runs to the cap
+    got = restated_adaptive(L, S_, mn, st, thr, floor)
+    ns = got["samples"]
+    assert ns[0, 0] == mn and ns[0, 1] == mn and ns[0, 3] == S_
+    decisions = list(range(mn, S_, st))
+    assert set(np.unique(ns)) <= set(decisions) | {S_}
+    assert len(set(np.unique(ns))) >= 4, "the made-up samples do not exercise several stop values"
+    L64 = L.astype(np.float64)
+    finite = ~np.isnan(L64).any(axis=(2, 3))
+    for n in decisions:
+        mean = L64[:, :, :n].mean(axis=2).sum(axis=2)
+        se = np.sqrt((L64[:, :, :n].var(axis=2, ddof=1) / n).sum(axis=2))
+        ratio = se / (mean + floor)
+        clear = finite & (np.abs(ratio - thr) > 1e-3)
+        assert (ratio[clear & (ns == n)] <= thr).all(), n                 # stopped here: at or below the target
+        assert (ratio[clear & (ns > n)] > thr).all(), n                   # went on: above it
+    # the outputs: mean of the samples taken, variance of that mean
+    for (j, i) in ((0, 2), (5, 5), (11, 13)):
+        n = int(ns[j, i])
+        want = L64[j, i, :n].mean(axis=0)
+        assert np.allclose(got["mean"][j, i], want, rtol=1e-5), (j, i)
+        wv = L64[j, i, :n].var(axis=0, ddof=1) / n
+        assert (np.abs(got["variance"][j, i] - wv) <= 1e-4 * wv + 1e-5 * want ** 2).all(), (j, i)
+    assert got["paths"] == int(ns.sum()) and got["passes"] == 1 + len(got["pass_pixels"])
+    # threshold +inf: everything stops after the warm-up; threshold 0: only exact zeros do
+    assert (restated_adaptive(L[1:], S_, mn, st, np.inf, floor)["samples"] == mn).all()
+    z = restated_adaptive(L, S_, mn, st, 0.0, floor)["samples"]
+    assert z[0, 0] == mn and (z[1:] == S_).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in SCENES:
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_frame(name):
+    """(rgb, mean, L (H, W, S, 3)) of the oracle at the tests' shape with the scene's own P_RR and light_sample_n, seed 0"""
+    t = util.task(name)
+    eye, iv, fov = util.camera(name)
+    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, W, H, S, t.P_RR, t.light_sample_n, want_L=True)
+    c, _ = restated_sums(L, S, S)
+    assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
+    for a in (rgb, mean, L):
+        a.flags.writeable = False
+    return rgb, mean, L
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, **kw):
+    """The restated adaptive frame of a scene at the tests' shape (kw overrides AD), computed once; with the default settings it must
+    be the frame recorded at the top of this file -- if not, the inputs are wrong, not the kernel."""
+    _, _, L = oracle_frame(name)
+    got = restated_adaptive(L, S, **dict(AD, **kw))
+    if not kw:
+        counts = tuple(int((got["samples"] == n).sum()) for n in STOPS)
+        assert min(counts) >= 20 and sum(counts) == W * H, counts
+        assert (counts, got["pass_pixels"]) == EXPECTED[name], (counts, got["pass_pixels"])
+        assert got["passes"] == 6 and all(a % 64 for a in got["pass_pixels"])
+    for a in got.values():
+        if isinstance(a, np.ndarray):
+            a.flags.writeable = False
+    return got
+
+
+def gpu_adaptive(r, name, traversal=crt.TRAVERSAL_EXACT, want_variance=True, **kw):
+    eye, iv, fov = util.camera(name)
+    r.set_spp(S)
+    r.seed, r.traversal = 0, traversal
+    try:
+        rgb = r.run_view_adaptive(eye, iv, fov, want_variance=want_variance, width=W, height=H, **dict(AD, **kw))
+    finally:
+        r.traversal = crt.TRAVERSAL_EXACT
+    return dict(rgb=rgb, mean=r.mean_buffer, samples=r.samples_buffer, variance=r.variance_buffer, info=r.adaptive_info)
+
+
+def check_frame(got, want, where):
+    assert np.array_equal(got["samples"], want["samples"]), where + ": samples per pixel"
+    assert_bits(got["mean"], want["mean"], where + ": mean")
+    assert np.array_equal(got["rgb"], want["rgb"]), where + ": RGB"
+    if got["variance"] is not None:
+        assert_bits(got["variance"], want["variance"], where + ": variance")
+    info = got["info"]
+    assert info["pass_pixels"] == want["pass_pixels"], (where, info["pass_pixels"])
+    assert info["passes"] == want["passes"] and info["paths"] == want["paths"], (where, info)
+    assert info["paths_uniform"] == W * H * S
+    assert info["total_ms"] > 0 and 0 < info["kernel_ms"] <= info["total_ms"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("traversal", [crt.TRAVERSAL_EXACT, crt.TRAVERSAL_REFERENCE])
+def test_adaptive_frame_matches_restatement_on_the_oracles_radiance(renders, name, traversal):
+    want = restated(name)
+    got = gpu_adaptive(renders[name], name, traversal=traversal)
+    check_frame(got, want, "%s traversal %d" % (name, traversal))
+    assert got["info"]["passes"] == 6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_adaptive_pass_split_into_chunks_gives_the_same_bits(renders, name, monkeypatch):
+    # 1 280 pixel slots: chunks of 2^12 paths hold three samples, so every full pass is two launches and the warm-up two
+    monkeypatch.setenv("CRT_CHUNK_LOG2", "12")
+    got = gpu_adaptive(renders[name], name)
+    check_frame(got, restated(name), name + ", small chunks")
+    launches = renders[name].last_launch_ms()[1]
+    assert launches == 1, "the last pass (one sample) is one launch"
+    monkeypatch.delenv("CRT_CHUNK_LOG2")
+    got = gpu_adaptive(renders[name], name, step_samples=25)          # one adaptive pass of 25 samples
+    monkeypatch.setenv("CRT_CHUNK_LOG2", "12")
+    again = gpu_adaptive(renders[name], name, step_samples=25)
+    assert renders[name].last_launch_ms()[1] == 9, "25 samples in chunks of three"
+    want = restated(name, step_samples=25)
+    check_frame(got, want, name + ", one long pass")
+    check_frame(again, want, name + ", one long pass in nine launches")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_adaptive_shards_are_the_full_frame_at_their_pixels(renders, name):
+    r = renders[name]
+    want = restated(name)
+    eye, iv, fov = util.camera(name)
+    cam = r._cam(eye, iv, fov)
+    r.set_spp(S)
+    world, tx, ty = 2, (W + 7) // 8, (H + 7) // 8
+    ap = crt.api._adaptive_params(**AD)
+    paths, padding = 0, 0
+    for rank in range(world):
+        slots = crt.shard_slots(W, H, rank, world)
+        rgb, mean = np.full((slots, 3), 7, dtype=np.uint8), np.full((slots, 3), 7, dtype=F)
+        samples, var = np.full(slots, 7, dtype=np.uint32), np.full((slots, 3), 7, dtype=F)
+        info = capi.AdaptiveInfo()
+        prm = r._params(rank=rank, world=world, flags=capi.FLAG_TILED_OUTPUT, width=W, height=H)
+        capi.check(capi.lib().crt_render_adaptive(r._h, C.byref(cam), C.byref(prm), C.byref(ap), capi.ptr(rgb), capi.ptr(mean), capi.ptr(samples),
+                                                  capi.ptr(var), C.byref(info)), "crt_render_adaptive")
+        paths += info.paths
+        pixels = 0
+        for s in range(slots):
+            tile = (s // 64) * world + rank
+            i, j = (tile % tx) * 8 + (s % 64) % 8, (tile // tx) * 8 + (s % 64) // 8
+            if tile >= tx * ty or i >= W or j >= H:
+                padding += 1
+                assert samples[s] == 0 and not rgb[s].any() and not mean[s].view(np.uint32).any() and not var[s].view(np.uint32).any(), (rank, s)
+                continue
+            pixels += 1
+            where = "rank %d slot %d" % (rank, s)
+            assert samples[s] == want["samples"][j, i], where
+            assert_bits(mean[s], want["mean"][j, i], where)
+            assert_bits(var[s], want["variance"][j, i], where)
+            assert np.array_equal(rgb[s], want["rgb"][j, i]), where
+        assert info.paths_uniform == pixels * S
+    assert padding > 0 and paths == want["paths"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_adaptive_limits(renders, name):
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    orgb, omean, L = oracle_frame(name)
+    r.set_spp(S)
+    rgb_u = r.run_view(eye, iv, fov, width=W, height=H, want_variance=True).copy()
+    mean_u, var_u = r.mean_buffer.copy(), r.variance_buffer.copy()
+    assert np.array_equal(rgb_u, orgb) and np.array_equal(mean_u.view(np.uint32), omean.view(np.uint32))
+    # min_samples == spp: the uniform frame
+    got = gpu_adaptive(r, name, min_samples=S)
+    assert (got["samples"] == S).all() and got["info"]["passes"] == 1 and got["info"]["pass_pixels"] == []
+    assert got["info"]["paths"] == W * H * S
+    assert np.array_equal(got["rgb"], rgb_u)
+    assert_bits(got["mean"], mean_u, "min_samples == spp: mean")
+    assert_bits(got["variance"], var_u, "min_samples == spp: variance")
+    # threshold 0: the pixels that run to the cap carry the uniform frame's mean
+    got = gpu_adaptive(r, name, threshold=0.0)
+    want = restated(name, threshold=0.0)
+    check_frame(got, want, "threshold 0")
+    full = got["samples"] == S
+    assert full.sum() > W * H // 2
+    assert_bits(got["mean"][full], mean_u[full], "threshold 0: pixels at the cap")
+    # threshold +inf: the warm-up alone; the mean is crt_preview's after a range of four samples
+    got = gpu_adaptive(r, name, threshold=np.inf)
+    assert (got["samples"] == 4).all() and got["info"]["passes"] == 1 and got["info"]["paths"] == W * H * 4
+    assert r.run_view_range(eye, iv, fov, 0, 4, width=W, height=H) is None
+    prgb, pmean, done = r.preview(want_mean=True, width=W, height=H)
+    assert done == 4
+    assert_bits(got["mean"], pmean, "threshold +inf: mean")
+    assert np.array_equal(got["rgb"], prgb)
+    assert_bits(got["variance"], restated(name, threshold=np.inf)["variance"], "threshold +inf: variance")
+
+
+@pytest.mark.gpu
+def test_adaptive_device_form_on_a_stream_matches_host_form(renders):
+    from test_variance import hip_runtime
+    name = "veach-mis"
+    r = renders[name]
+    host = gpu_adaptive(r, name)
+    check_frame(host, restated(name), "host form")
+    H_ = hip_runtime()
+    eye, iv, fov = util.camera(name)
+    ptrs, stream = {}, C.c_void_p()
+    sizes = {"rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "var": W * H * 12}
+    try:
+        for n, size in sizes.items():
+            p = C.c_void_p()
+            assert H_.hipMalloc(C.byref(p), size) == 0
+            ptrs[n] = p.value
+            assert H_.hipMemset(p, 0x55, size) == 0          # (every output value must be written)
+        assert H_.hipStreamCreate(C.byref(stream)) == 0
+        cam, prm, ap = r._cam(eye, iv, fov), r._params(width=W, height=H), crt.api._adaptive_params(**AD)
+        info = capi.AdaptiveInfo()
+        capi.check(capi.lib().crt_render_adaptive_device(r._h, C.byref(cam), C.byref(prm), C.byref(ap), C.c_void_p(ptrs["rgb"]), C.c_void_p(ptrs["mean"]),
+                                                         C.c_void_p(ptrs["samples"]), C.c_void_p(ptrs["var"]), stream, C.byref(info)),
+                   "crt_render_adaptive_device")
+        assert H_.hipStreamSynchronize(stream) == 0
+        out = dict(rgb=np.zeros((H, W, 3), dtype=np.uint8), mean=np.zeros((H, W, 3), dtype=F), samples=np.zeros((H, W), dtype=np.uint32),
+                   var=np.zeros((H, W, 3), dtype=F))
+        for n, a in out.items():
+            assert H_.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+        check_frame(dict(rgb=out["rgb"], mean=out["mean"], samples=out["samples"], variance=out["var"], info=info.as_dict()), restated(name), "device form")
+        # without info, without the optional outputs, mean only
+        assert H_.hipMemset(C.c_void_p(ptrs["mean"]), 0x55, sizes["mean"]) == 0
+        capi.check(capi.lib().crt_render_adaptive_device(r._h, C.byref(cam), C.byref(prm), C.byref(ap), None, C.c_void_p(ptrs["mean"]), None, None, stream,
+                                                         None), "crt_render_adaptive_device")
+        assert H_.hipStreamSynchronize(stream) == 0
+        assert H_.hipMemcpy(out["mean"].ctypes.data, C.c_void_p(ptrs["mean"]), out["mean"].nbytes, 2) == 0
+        assert_bits(out["mean"], host["mean"], "device form, mean only")
+    finally:
+        if stream.value:
+            H_.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H_.hipFree(C.c_void_p(p))
+
+
+@pytest.mark.gpu
+def test_adaptive_leaves_no_frame_in_flight(monkeypatch):
+    name = "cornell-box"
+    t = util.task(name)
+    r = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)   # a fresh handle
+    try:
+        eye, iv, fov = util.camera(name)
+        orgb, omean, L = oracle_frame(name)
+        kw = dict(width=W, height=H)
+        want = restated(name)
+
+        def refused():
+            for call in (lambda: r.preview(**kw), lambda: r.variance(**kw), lambda: r.run_view_range(eye, iv, fov, 4, 2, **kw),
+                         lambda: r.run_view_range(eye, iv, fov, S - 1, 1, want_variance=True, **kw)):
+                with pytest.raises(crt.CrtError) as e:
+                    call()
+                assert e.value.status == capi.ERR_INVALID_ARG
+        check_frame(gpu_adaptive(r, name), want, "first call on the handle")
+        refused()
+        # a one-shot frame and a progressive frame afterwards are the oracle's
+        assert np.array_equal(r.run_view(eye, iv, fov, **kw), orgb)
+        assert_bits(r.mean_buffer, omean, "run_view after an adaptive frame")
+        check_frame(gpu_adaptive(r, name), want, "again")
+        assert r.run_view_range(eye, iv, fov, 0, 11, want_variance=True, **kw) is None
+        assert r.preview(**kw)[2] == 11
+        rgb = r.run_view_range(eye, iv, fov, 11, S - 11, want_variance=True, **kw)
+        assert np.array_equal(rgb, orgb)
+        assert_bits(r.mean_buffer, omean, "progressive frame after an adaptive frame")
+        # an adaptive call in the middle of a progressive frame ends that frame
+        assert r.run_view_range(eye, iv, fov, 0, 5, want_variance=True, **kw) is None
+        assert r.variance(**kw)[1] == 5
+        check_frame(gpu_adaptive(r, name), want, "in the middle of a progressive frame")
+        refused()
+        # a refused adaptive call leaves a frame in flight as it was
+        assert r.run_view_range(eye, iv, fov, 0, 5, **kw) is None
+        with pytest.raises(crt.CrtError):
+            r.run_view_adaptive(eye, iv, fov, min_samples=1, **kw)
+        assert r.preview(**kw)[2] == 5
+        assert np.array_equal(r.run_view_range(eye, iv, fov, 5, S - 5, **kw), orgb)
+        # the fallback pipeline hands out its work items without the list
+        with monkeypatch.context() as m:
+            m.setenv("CRT_PIPELINE", "2")
+            with pytest.raises(crt.CrtError) as e:
+                r.run_view_adaptive(eye, iv, fov, **dict(AD, **kw))
+            assert e.value.status == capi.ERR_UNSUPPORTED
+        check_frame(gpu_adaptive(r, name), want, "after the refusals")
+    finally:
+        r.free()
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_adaptive_frame_and_its_samples(renders, tmp_path):
+    from cudaraytracing_amd import build as b
+    from test_variance import read_pfm
+    cli = b.build_cli()
+    name = "veach-mis"
+    cfg = util.SCENES[name]
+    png, pfm, vpfm = (str(tmp_path / n) for n in ("adaptive.png", "samples.pfm", "var.pfm"))
+    base = [cli, cfg, "--spp", str(S), "--width", str(W), "--height", str(H), "--seed", "0", "--base-dir", util.ROOT]
+    res = subprocess.run(base + ["-o", png, "--adaptive", "0.2", "--adaptive-min", "4", "--adaptive-step", "6", "--adaptive-samples", pfm,
+                                 "--variance", vpfm], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    assert "adaptive: 6 passes" in res.stdout
+    got = gpu_adaptive(renders[name], name)
+    ref = str(tmp_path / "python.png")
+    renders[name].save_frame_buffer(ref)
+    assert open(png, "rb").read() == open(ref, "rb").read()
+    assert_bits(read_pfm(pfm), got["samples"].astype(F), "--adaptive-samples")
+    assert_bits(read_pfm(vpfm), got["variance"], "--variance of the adaptive frame")
+    bad = subprocess.run([cli, cfg, "--adaptive-samples", pfm], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--adaptive" in bad.stderr
+    bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--adaptive", "0.1"], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--adaptive" in bad.stderr
