@@ -4,6 +4,7 @@
 // (k_adaptive_accumulate), and at the end the sums become the frame (k_adaptive_resolve).
 // Memory: the sums, the active / sample-count planes, the list of active slots and its counter are uncached allocations accessed with
 // agent-scope atomics only; the item list is written with agent-scope stores, as k_order_items writes it (docs/experiments.md 6).
+// The slot map, the loads and stores of the sums, the sample fold and the output write are the frame kernels' (crt_internal.h).
 #include "crt_internal.h"
 
 namespace crtk {
@@ -17,8 +18,7 @@ __global__ __launch_bounds__(256) void k_adaptive_init(const AdaptiveParams D)
     const AParams& A = D.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, make_fastdiv_dev(A.tiles_x), A.width, A.height, i, j);
+    const bool valid = slot_pixel(A, slot).valid;
     word_store(D.active + slot, valid ? 1u : 0u);
     word_store(D.nsamp + slot, valid ? D.n : 0u);
 }
@@ -34,9 +34,8 @@ __global__ __launch_bounds__(256) void k_adaptive_select(const AdaptiveParams D)
     if (act) {
         const float fn = (float)D.n, fs = (float)A.spp;
         const float r = fs / fn, rr = r * r;
-        const F3 c = f3(acc_load(A.accum + slot), acc_load(A.accum + A.nslots + slot), acc_load(A.accum + 2ull * A.nslots + slot));
-        const F3 q = f3(acc_load(D.qacc + slot), acc_load(D.qacc + A.nslots + slot), acc_load(D.qacc + 2ull * A.nslots + slot));
-        const F3 var = f3(variance_of(c.x, q.x, fn, rr), variance_of(c.y, q.y, fn, rr), variance_of(c.z, q.z, fn, rr));
+        const F3 c = acc_load3(A.accum, A.nslots, slot);
+        const F3 var = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, rr);
         const F3 p = f3(c.x * r, c.y * r, c.z * r);
         const float v = (var.x + var.y) + var.z, m = (p.x + p.y) + p.z;
         const float t = D.threshold * (m + D.mean_floor);
@@ -66,57 +65,42 @@ __global__ __launch_bounds__(256) void k_adaptive_items(uint32_t* const item_lis
     __hip_atomic_store(&item_list[pos], s * nslots + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// k_accumulate_var for the slots that took the pass: c = c + x, q = q + x * x over the chunk's samples in sample order, x = L / (float)spp.
-// Slots that did not take it are not touched (their entries of L hold whatever an earlier launch left).
+// k_accumulate_var's fold (fold_samples) for the slots that took the pass.  Slots that did not take it are not touched (their entries of
+// L hold whatever an earlier launch left).
 __global__ __launch_bounds__(256) void k_adaptive_accumulate(const AdaptiveParams D)
 {
     const AParams& A = D.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots || word_load(D.active + slot) == 0u) return;
-    F3 c = f3(acc_load(A.accum + slot), acc_load(A.accum + A.nslots + slot), acc_load(A.accum + 2ull * A.nslots + slot));
-    F3 q = f3(acc_load(D.qacc + slot), acc_load(D.qacc + A.nslots + slot), acc_load(D.qacc + 2ull * A.nslots + slot));
-    const float fspp = (float)A.spp;
-    for (uint32_t s = 0; s < A.chunk_samples; s++) {
-        const float* lp = (const float*)&A.L[(uint64_t)s * A.nslots + slot]; // (agent-scope loads: see k_accumulate)
-        const float xx = acc_load(lp) / fspp, xy = acc_load(lp + 1) / fspp, xz = acc_load(lp + 2) / fspp;
-        c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
-        q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz;
-    }
-    acc_store(A.accum + slot, c.x); acc_store(A.accum + A.nslots + slot, c.y); acc_store(A.accum + 2ull * A.nslots + slot, c.z);
-    acc_store(D.qacc + slot, q.x); acc_store(D.qacc + A.nslots + slot, q.y); acc_store(D.qacc + 2ull * A.nslots + slot, q.z);
+    F3 c = acc_load3(A.accum, A.nslots, slot);
+    F3 q = acc_load3(D.qacc, A.nslots, slot);
+    fold_samples<true>(A, slot, c, q);
+    acc_store3(A.accum, A.nslots, slot, c);
+    acc_store3(D.qacc, A.nslots, slot, q);
     word_store(D.nsamp + slot, D.n);
 }
 
 // The frame: per pixel n_p, mean = c * (S / n_p), its tone map, and the variance of that mean, in the layout of crt_render's buffers
-// (slot -> pixel as k_preview; padding slots of a tiled shard 0 / +0).
+// (padding slots of a tiled shard 0 / +0).
 __global__ __launch_bounds__(256) void k_adaptive_resolve(const AdaptiveParams D)
 {
     const AParams& A = D.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, make_fastdiv_dev(A.tiles_x), A.width, A.height, i, j);
-    if (!valid && !A.tiled_output) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    if (!px.out) return;
     F3 p = f3(0.0f, 0.0f, 0.0f), v = f3(0.0f, 0.0f, 0.0f);
     uint32_t n = 0;
-    if (valid) {
+    if (px.valid) {
         n = word_load(D.nsamp + slot);
         const float fn = (float)n, fs = (float)A.spp;
-        const float r = fs / fn, rr = r * r;
-        const F3 c = f3(acc_load(A.accum + slot), acc_load(A.accum + A.nslots + slot), acc_load(A.accum + 2ull * A.nslots + slot));
+        const float r = fs / fn;
+        const F3 c = acc_load3(A.accum, A.nslots, slot);
         p = f3(c.x * r, c.y * r, c.z * r);
-        if (D.out_variance) {
-            const F3 q = f3(acc_load(D.qacc + slot), acc_load(D.qacc + A.nslots + slot), acc_load(D.qacc + 2ull * A.nslots + slot));
-            v = f3(variance_of(c.x, q.x, fn, rr), variance_of(c.y, q.y, fn, rr), variance_of(c.z, q.z, fn, rr));
-        }
+        if (D.out_variance) v = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, r * r);
     }
-    const uint64_t o = A.tiled_output ? (uint64_t)slot : (uint64_t)j * A.width + i;
-    if (A.out_rgb) {
-        A.out_rgb[o * 3 + 0] = valid ? tonemap(p.x) : 0;
-        A.out_rgb[o * 3 + 1] = valid ? tonemap(p.y) : 0;
-        A.out_rgb[o * 3 + 2] = valid ? tonemap(p.z) : 0;
-    }
-    if (A.out_mean) { A.out_mean[o * 3 + 0] = p.x; A.out_mean[o * 3 + 1] = p.y; A.out_mean[o * 3 + 2] = p.z; }
+    const uint64_t o = px.o;
+    write_color(A, o, px.valid, p);
     if (D.out_samples) D.out_samples[o] = n;
     if (D.out_variance) { D.out_variance[o * 3 + 0] = v.x; D.out_variance[o * 3 + 1] = v.y; D.out_variance[o * 3 + 2] = v.z; }
 }

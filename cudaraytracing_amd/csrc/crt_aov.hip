@@ -1,7 +1,7 @@
 // cudaraytracing_amd/csrc/crt_aov.hip -- the first-hit AOV pass (crt_render_aov, include/crt.h): per pixel, the camera rays of samples
 // 0 .. spp-1 -- the primary rays of the frame's paths, camera_dir -- traced by the render kernel's own closest-hit query, and the albedo,
 // normal, depth, coverage, triangle and material buffers made of their hits in sample order.  The host side (chunks over samples, the
-// trace) is in crt_render.hip.
+// trace) is in crt_render.hip; slot -> pixel -> output index is the frame kernels' (slot_pixel, crt_internal.h).
 #include "crt_internal.h"
 
 namespace crtk {
@@ -14,9 +14,8 @@ __global__ __launch_bounds__(256) void k_aov_rays(const AovParams A)
     const uint64_t item = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (item >= (uint64_t)A.n_samples * A.nslots) return;
     const uint32_t s = (uint32_t)(item / A.nslots), slot = (uint32_t)(item - (uint64_t)s * A.nslots);
-    uint32_t pi = 0, pj = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, A.tiles_x_div, A.width, A.height, pi, pj);
-    const F3 d = unit3(valid ? camera_dir(A, pj * A.width + pi, A.sample_begin + s, pi, pj) : f3(A.inv_view[6], A.inv_view[7], A.inv_view[8])); // Ray.cuh:13
+    const SlotPixel px = slot_pixel(A, slot);
+    const F3 d = unit3(px.valid ? camera_dir(A, px.j * A.width + px.i, A.sample_begin + s, px.i, px.j) : f3(A.inv_view[6], A.inv_view[7], A.inv_view[8])); // Ray.cuh:13
     A.pool.ro[item] = make_float4(A.eye[0], A.eye[1], A.eye[2], 0.0f);
     A.pool.rd[item] = make_float4(d.x, d.y, d.z, __uint_as_float((uint32_t)RAY_CLOSEST));
     A.pool.res[item] = make_float2(FLT_MAX, __int_as_float(-1));
@@ -29,14 +28,13 @@ __global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A)
 {
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, A.tiles_x_div, A.width, A.height, i, j);
-    if (!valid && (!A.tiled_output || !A.last_chunk)) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    if (!px.valid && (!px.out || !A.last_chunk)) return;
     F3 alb = f3(0.0f, 0.0f, 0.0f), nrm = f3(0.0f, 0.0f, 0.0f);
     float dsum = 0.0f;
     uint32_t hits = 0;
     int32_t tri0 = -1, mat0 = -1;
-    if (valid) {
+    if (px.valid) {
         float4* acc = A.acc + (size_t)slot * 3;
         if (!A.first_chunk) {
             const float4 a0 = acc[0], a1 = acc[1], a2 = acc[2];
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A)
             return;
         }
     }
-    const size_t o = A.tiled_output ? (size_t)slot : (size_t)j * A.width + i;
+    const size_t o = px.o;
     if (A.albedo) { A.albedo[o * 3 + 0] = alb.x; A.albedo[o * 3 + 1] = alb.y; A.albedo[o * 3 + 2] = alb.z; }
     if (A.normal) { A.normal[o * 3 + 0] = nrm.x; A.normal[o * 3 + 1] = nrm.y; A.normal[o * 3 + 2] = nrm.z; }
     if (A.depth) A.depth[o] = hits ? dsum / (float)hits : 0.0f;

@@ -1,5 +1,6 @@
 // cudaraytracing_amd/csrc/crt_denoise.hip -- the AOV-guided edge-avoiding a-trous filter (crt_denoise / crt_denoise_device, contract:
 // include/crt.h) and its variance-guided form (crt_denoise_var / crt_denoise_var_device): kernels and host code.  An image operation without a scene handle.
+// The two forms are one pack kernel, one templated pass body (its two instantiations keep their kernel names) and one host path.
 //
 // One call = k_denoise_pack (colour and guides into four float4 planes of the caller's scratch: a colour ping-pong pair, (normal.xyz,
 // depth) and (albedo.xyz, 0) -- three 16-byte loads per tap, coalesced along a row whatever the spacing) and one filter launch per pass.
@@ -29,6 +30,7 @@ struct DnParams {
 struct DnPack {
     uint64_t npix;
     const float* color; const float* albedo; const float* normal; const float* depth;
+    const float* variance;                    // crt_denoise_var; null: the plain form, .w of the colour plane 0
     float4* c0; float4* g0; float4* g1;
 };
 
@@ -36,7 +38,8 @@ __global__ __launch_bounds__(256) void k_denoise_pack(const DnPack K)
 {
     const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (p >= K.npix) return;
-    K.c0[p] = make_float4(K.color[p * 3], K.color[p * 3 + 1], K.color[p * 3 + 2], 0.0f);
+    const float v0 = K.variance ? (K.variance[p * 3] + K.variance[p * 3 + 1]) + K.variance[p * 3 + 2] : 0.0f;
+    K.c0[p] = make_float4(K.color[p * 3], K.color[p * 3 + 1], K.color[p * 3 + 2], v0);
     float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (K.normal) { g.x = K.normal[p * 3]; g.y = K.normal[p * 3 + 1]; g.z = K.normal[p * 3 + 2]; }
     if (K.depth) g.w = K.depth[p];
@@ -45,14 +48,16 @@ __global__ __launch_bounds__(256) void k_denoise_pack(const DnPack K)
     K.g1[p] = a;
 }
 
-struct DnSum { float x, y, z, den; };
+struct DnSum { float x, y, z, den, vnum; };
 
-// one tap of the contract (include/crt.h), operation by operation; hw = h[dy+2] * h[dx+2]
-__device__ __forceinline__ void dn_tap(const DnParams& P, const float4 cp, const float4 gp, const float4 ap, const float4 cq, const float4 gq,
-                                       const float4 aq, const float hw, DnSum& s)
+// one tap of the contract (include/crt.h), operation by operation; hw = h[dy+2] * h[dx+2]; n_c: the divisor of the colour term (the
+// pass's sigma^2, or the variance-guided form's sigma^2 g(p) + 1e-10); VAR: also the variance's numerator
+template <bool VAR>
+__device__ __forceinline__ void dn_tap(const DnParams& P, const float n_c, const float4 cp, const float4 gp, const float4 ap, const float4 cq,
+                                       const float4 gq, const float4 aq, const float hw, DnSum& s)
 {
     const float dcx = cp.x - cq.x, dcy = cp.y - cq.y, dcz = cp.z - cq.z;
-    const float e_c = (dcx * dcx + dcy * dcy + dcz * dcz) / P.sig2_c;
+    const float e_c = (dcx * dcx + dcy * dcy + dcz * dcz) / n_c;
     const float dnx = gp.x - gq.x, dny = gp.y - gq.y, dnz = gp.z - gq.z;
     const float e_n = (dnx * dnx + dny * dny + dnz * dnz) / P.sig2_n;
     const float dax = ap.x - aq.x, day = ap.y - aq.y, daz = ap.z - aq.z;
@@ -65,96 +70,44 @@ __device__ __forceinline__ void dn_tap(const DnParams& P, const float4 cp, const
     s.y = s.y + cq.y * w;
     s.z = s.z + cq.z * w;
     s.den = s.den + w;
+    if (VAR) s.vnum = s.vnum + cq.w * (w * w);
 }
 
 __device__ __forceinline__ float dn_h(const int d) { return d == 0 ? 0.375f : (d == 1 || d == -1) ? 0.25f : 0.0625f; }
-
-__device__ __forceinline__ void dn_write(const DnParams& P, const size_t p, const DnSum& s)
-{
-    const float cx = s.x / s.den, cy = s.y / s.den, cz = s.z / s.den;
-    if (!P.last) { P.c_out[p] = make_float4(cx, cy, cz, 0.0f); return; }
-    if (P.out_mean) { P.out_mean[p * 3] = cx; P.out_mean[p * 3 + 1] = cy; P.out_mean[p * 3 + 2] = cz; }
-    if (P.out_rgb) { P.out_rgb[p * 3] = tonemap(cx); P.out_rgb[p * 3 + 1] = tonemap(cy); P.out_rgb[p * 3 + 2] = tonemap(cz); }
-}
-
-// Block = 64 x 4 pixels, a wave = 64 consecutive pixels of one row.
-__global__ __launch_bounds__(256) void k_denoise_pass(const DnParams P, const int step)
-{
-    const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
-    const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
-    const int W = (int)P.width, H = (int)P.height;
-    if (x >= W || y >= H) return;
-    const size_t p = (size_t)y * P.width + (size_t)x;
-    const float4 cp = P.c_in[p], gp = P.g0[p], ap = P.g1[p];
-    DnSum s = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-        const int qy = y + dy * step;
-        if (qy < 0 || qy >= H) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + dx * step;
-            if (qx < 0 || qx >= W) continue;
-            const size_t q = (size_t)qy * P.width + (size_t)qx;
-            dn_tap(P, cp, gp, ap, P.c_in[q], P.g0[q], P.g1[q], dn_h(dy) * dn_h(dx), s);
-        }
-    }
-    dn_write(P, p, s);
-}
-
-// ---- variance-guided form (crt_denoise_var, contract: include/crt.h) ----
-// The same planes; the scalar variance v_i rides in the .w of the colour ping-pong pair.  A pass adds, per pixel, nine 4-byte loads for
-// g(p) (the .w of the pixels around p: lines the spacing-1 taps touch anyway) and a multiply-add pair per tap.  No LDS staging, as the
-// plain pass: it sits at the vector-ALU issue rate (docs/experiments.md, "The variance-guided filter").
-struct DnVarPack {
-    DnPack K;
-    const float* variance;
-};
-
-__global__ __launch_bounds__(256) void k_denoise_var_pack(const DnVarPack V)
-{
-    const DnPack& K = V.K;
-    const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (p >= K.npix) return;
-    const float v0 = (V.variance[p * 3] + V.variance[p * 3 + 1]) + V.variance[p * 3 + 2];
-    K.c0[p] = make_float4(K.color[p * 3], K.color[p * 3 + 1], K.color[p * 3 + 2], v0);
-    float4 g = make_float4(0.0f, 0.0f, 0.0f, 0.0f), a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (K.normal) { g.x = K.normal[p * 3]; g.y = K.normal[p * 3 + 1]; g.z = K.normal[p * 3 + 2]; }
-    if (K.depth) g.w = K.depth[p];
-    if (K.albedo) { a.x = K.albedo[p * 3]; a.y = K.albedo[p * 3 + 1]; a.z = K.albedo[p * 3 + 2]; }
-    K.g0[p] = g;
-    K.g1[p] = a;
-}
-
 __device__ __forceinline__ float dn_k(const int d) { return d == 0 ? 0.5f : 0.25f; }
 
-// P.sig2_c = sigma_color * sigma_color (the same in every pass); out_var: v_iterations of the last pass (may be null)
-__global__ __launch_bounds__(256) void k_denoise_var_pass(const DnParams P, const int step, float* const out_var)
+// A pass of either form.  Block = 64 x 4 pixels, a wave = 64 consecutive pixels of one row.
+// VAR (crt_denoise_var, contract: include/crt.h): the same planes; the scalar variance v_i rides in the .w of the colour ping-pong pair.
+// A pass adds, per pixel, nine 4-byte loads for g(p) (the .w of the pixels around p: lines the spacing-1 taps touch anyway) and a
+// multiply-add pair per tap; P.sig2_c = sigma_color * sigma_color (the same in every pass); out_var: v_iterations of the last pass (may be
+// null).  No LDS staging in either form: the pass sits at the vector-ALU issue rate (docs/experiments.md, "The variance-guided filter").
+template <bool VAR> __device__ __forceinline__ void denoise_pass(const DnParams& P, const int step, float* const out_var)
 {
     const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
     const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
     const int W = (int)P.width, H = (int)P.height;
     if (x >= W || y >= H) return;
     const size_t p = (size_t)y * P.width + (size_t)x;
-    // g(p): the 3x3 Gaussian of v_i at spacing 1, whatever the spacing of the pass
-    float gn = 0.0f, gd = 0.0f;
+    float n_c = P.sig2_c;
+    if (VAR) { // g(p): the 3x3 Gaussian of v_i at spacing 1, whatever the spacing of the pass
+        float gn = 0.0f, gd = 0.0f;
 #pragma unroll
-    for (int dy = -1; dy <= 1; dy++) {
-        const int ty = y + dy;
-        if (ty < 0 || ty >= H) continue;
+        for (int dy = -1; dy <= 1; dy++) {
+            const int ty = y + dy;
+            if (ty < 0 || ty >= H) continue;
 #pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int tx = x + dx;
-            if (tx < 0 || tx >= W) continue;
-            const float k = dn_k(dy) * dn_k(dx);
-            gn = gn + k * P.c_in[(size_t)ty * P.width + (size_t)tx].w;
-            gd = gd + k;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int tx = x + dx;
+                if (tx < 0 || tx >= W) continue;
+                const float k = dn_k(dy) * dn_k(dx);
+                gn = gn + k * P.c_in[(size_t)ty * P.width + (size_t)tx].w;
+                gd = gd + k;
+            }
         }
+        n_c = P.sig2_c * (gn / gd) + 1e-10f;
     }
-    const float n_c = P.sig2_c * (gn / gd) + 1e-10f;
     const float4 cp = P.c_in[p], gp = P.g0[p], ap = P.g1[p];
-    DnSum s = {0.0f, 0.0f, 0.0f, 0.0f};
-    float vnum = 0.0f;
+    DnSum s = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
         const int qy = y + dy * step;
@@ -164,30 +117,19 @@ __global__ __launch_bounds__(256) void k_denoise_var_pass(const DnParams P, cons
             const int qx = x + dx * step;
             if (qx < 0 || qx >= W) continue;
             const size_t q = (size_t)qy * P.width + (size_t)qx;
-            const float4 cq = P.c_in[q], gq = P.g0[q], aq = P.g1[q];
-            const float dcx = cp.x - cq.x, dcy = cp.y - cq.y, dcz = cp.z - cq.z;
-            const float e_c = (dcx * dcx + dcy * dcy + dcz * dcz) / n_c;
-            const float dnx = gp.x - gq.x, dny = gp.y - gq.y, dnz = gp.z - gq.z;
-            const float e_n = (dnx * dnx + dny * dny + dnz * dnz) / P.sig2_n;
-            const float dax = ap.x - aq.x, day = ap.y - aq.y, daz = ap.z - aq.z;
-            const float e_a = (dax * dax + day * day + daz * daz) / P.sig2_a;
-            const float m = gp.w > gq.w ? gp.w : gq.w;
-            const float r = (gp.w - gq.w) / (P.sigma_d * m);
-            const float e_d = m > 0.0f ? r * r : 0.0f;
-            const float w = (dn_h(dy) * dn_h(dx)) * det_expf(-(((e_c + e_n) + e_a) + e_d));
-            s.x = s.x + cq.x * w;
-            s.y = s.y + cq.y * w;
-            s.z = s.z + cq.z * w;
-            s.den = s.den + w;
-            vnum = vnum + cq.w * (w * w);
+            dn_tap<VAR>(P, n_c, cp, gp, ap, P.c_in[q], P.g0[q], P.g1[q], dn_h(dy) * dn_h(dx), s);
         }
     }
-    const float cx = s.x / s.den, cy = s.y / s.den, cz = s.z / s.den, v = vnum / (s.den * s.den);
-    if (!P.last) { P.c_out[p] = make_float4(cx, cy, cz, v); return; }
-    if (P.out_mean) { P.out_mean[p * 3] = cx; P.out_mean[p * 3 + 1] = cy; P.out_mean[p * 3 + 2] = cz; }
-    if (P.out_rgb) { P.out_rgb[p * 3] = tonemap(cx); P.out_rgb[p * 3 + 1] = tonemap(cy); P.out_rgb[p * 3 + 2] = tonemap(cz); }
-    if (out_var) out_var[p] = v;
+    const F3 c = f3(s.x / s.den, s.y / s.den, s.z / s.den);
+    const float v = VAR ? s.vnum / (s.den * s.den) : 0.0f;
+    if (!P.last) { P.c_out[p] = make_float4(c.x, c.y, c.z, v); return; }
+    write_color(P, p, true, c);
+    if (VAR && out_var) out_var[p] = v;
 }
+
+// (the two kernel names are what the docs and profiler traces cite)
+__global__ __launch_bounds__(256) void k_denoise_pass(const DnParams P, const int step) { denoise_pass<false>(P, step, nullptr); }
+__global__ __launch_bounds__(256) void k_denoise_var_pass(const DnParams P, const int step, float* const out_var) { denoise_pass<true>(P, step, out_var); }
 
 } // namespace crtk
 
@@ -258,14 +200,9 @@ int denoise_impl(const char* who, int device, const crt_denoise_params* prm, con
         DnPack K;
         K.npix = npix;
         K.color = in->color; K.albedo = in->albedo; K.normal = in->normal; K.depth = in->depth;
+        K.variance = d_variance;
         K.c0 = c[0]; K.g0 = plane + 2 * npix; K.g1 = plane + 3 * npix;
-        if (d_variance) {
-            DnVarPack V;
-            V.K = K; V.variance = d_variance;
-            hipLaunchKernelGGL(k_denoise_var_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, V);
-        } else {
-            hipLaunchKernelGGL(k_denoise_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, K);
-        }
+        hipLaunchKernelGGL(k_denoise_pack, dim3((uint32_t)((npix + 255) / 256)), dim3(256), 0, st, K);
         HIP_CHECK(hipGetLastError());
         DnParams P;
         std::memset(&P, 0, sizeof(P));
@@ -305,6 +242,40 @@ int denoise_impl(const char* who, int device, const crt_denoise_params* prm, con
     return status;
 }
 
+// The host-buffer form of either filter (the caller has checked the arguments): device copies of the inputs, denoise_impl under the
+// name `who_device`, then the copies back.  variance / out_variance: crt_denoise_var's, null for crt_denoise.
+int denoise_host(const char* who, const char* who_device, int device, const crt_denoise_params* prm, const crt_denoise_inputs* host_in, const float* variance,
+                 float* out_mean, uint8_t* out_rgb, float* out_variance, crt_denoise_info* info)
+{
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t npix = (uint64_t)prm->width * prm->height;
+        DevBuf<float> d_color, d_var, d_albedo, d_normal, d_depth, d_mean, d_ovar;
+        DevBuf<uint8_t> d_rgb;
+        DevBuf<float4> d_scratch;
+        crt_denoise_inputs d{};
+        d.color = d_color.upload(host_in->color, npix * 3);
+        d_var.upload(variance, npix * 3);
+        d.albedo = d_albedo.upload(host_in->albedo, npix * 3);
+        d.normal = d_normal.upload(host_in->normal, npix * 3);
+        d.depth = d_depth.upload(host_in->depth, npix);
+        if (out_mean) d_mean.alloc(npix * 3);
+        if (out_rgb) d_rgb.alloc(npix * 3);
+        if (out_variance) d_ovar.alloc(npix);
+        d_scratch.alloc(npix * 4);
+        const int rc = denoise_impl(who_device, device, prm, &d, d_var.p, d_mean.p, d_rgb.p, d_ovar.p, d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        d_mean.download(out_mean, npix * 3);
+        d_rgb.download(out_rgb, npix * 3);
+        d_ovar.download(out_variance, npix);
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -336,37 +307,7 @@ int crt_denoise(int device, const crt_denoise_params* prm, const crt_denoise_inp
 {
     const int rc0 = denoise_check("crt_denoise", prm, host_in, out_mean, out_rgb);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> d_color, d_albedo, d_normal, d_depth, d_mean;
-        DevBuf<uint8_t> d_rgb;
-        DevBuf<float4> d_scratch;
-        crt_denoise_inputs d{};
-        auto up = [&](DevBuf<float>& b, const float* h, uint64_t n) -> const float* {
-            if (!h) return nullptr;
-            b.alloc(n);
-            HIP_CHECK(hipMemcpy(b.p, h, n * sizeof(float), hipMemcpyHostToDevice));
-            return b.p;
-        };
-        d.color = up(d_color, host_in->color, npix * 3);
-        d.albedo = up(d_albedo, host_in->albedo, npix * 3);
-        d.normal = up(d_normal, host_in->normal, npix * 3);
-        d.depth = up(d_depth, host_in->depth, npix);
-        if (out_mean) d_mean.alloc(npix * 3);
-        if (out_rgb) d_rgb.alloc(npix * 3);
-        d_scratch.alloc(npix * 4);
-        const int rc = denoise_impl("crt_denoise_device", device, prm, &d, nullptr, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr, nullptr,
-                                    d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        if (out_mean) HIP_CHECK(hipMemcpy(out_mean, d_mean.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, d_rgb.p, npix * 3, hipMemcpyDeviceToHost));
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    return denoise_host("crt_denoise", "crt_denoise_device", device, prm, host_in, nullptr, out_mean, out_rgb, nullptr, info);
 }
 
 int crt_denoise_var_defaults(crt_denoise_params* prm)
@@ -393,40 +334,8 @@ int crt_denoise_var(int device, const crt_denoise_params* prm, const crt_denoise
 {
     const int rc0 = denoise_var_check("crt_denoise_var", prm, host_in, out_mean, out_rgb);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_var: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> d_color, d_var, d_albedo, d_normal, d_depth, d_mean, d_ovar;
-        DevBuf<uint8_t> d_rgb;
-        DevBuf<float4> d_scratch;
-        crt_denoise_var_inputs d{};
-        auto up = [&](DevBuf<float>& b, const float* h, uint64_t n) -> const float* {
-            if (!h) return nullptr;
-            b.alloc(n);
-            HIP_CHECK(hipMemcpy(b.p, h, n * sizeof(float), hipMemcpyHostToDevice));
-            return b.p;
-        };
-        d.color = up(d_color, host_in->color, npix * 3);
-        d.variance = up(d_var, host_in->variance, npix * 3);
-        d.albedo = up(d_albedo, host_in->albedo, npix * 3);
-        d.normal = up(d_normal, host_in->normal, npix * 3);
-        d.depth = up(d_depth, host_in->depth, npix);
-        if (out_mean) d_mean.alloc(npix * 3);
-        if (out_rgb) d_rgb.alloc(npix * 3);
-        if (out_variance) d_ovar.alloc(npix);
-        d_scratch.alloc(npix * 4);
-        const int rc = crt_denoise_var_device(device, prm, &d, out_mean ? d_mean.p : nullptr, out_rgb ? d_rgb.p : nullptr,
-                                              out_variance ? d_ovar.p : nullptr, d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        if (out_mean) HIP_CHECK(hipMemcpy(out_mean, d_mean.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, d_rgb.p, npix * 3, hipMemcpyDeviceToHost));
-        if (out_variance) HIP_CHECK(hipMemcpy(out_variance, d_ovar.p, npix * sizeof(float), hipMemcpyDeviceToHost));
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    const crt_denoise_inputs plain = {host_in->color, host_in->albedo, host_in->normal, host_in->depth};
+    return denoise_host("crt_denoise_var", "crt_denoise_var_device", device, prm, &plain, host_in->variance, out_mean, out_rgb, out_variance, info);
 }
 
 } // extern "C"

@@ -1,94 +1,65 @@
 // cudaraytracing_amd/csrc/crt_frame.hip -- the kernels around the render kernels: k_accumulate (per pixel c += L_k / spp in sample order, tone map:
 // include/Render.cuh:348-350; k_accumulate_var: also the sum of squares behind crt_variance, read out by k_variance), k_preview, and the kernels behind crt_intersect's ray upload and the crt_device_* self-tests.
+// The stages these share with crt_adaptive.hip -- slot to pixel to output index, the three-plane sums, the sample fold, the output write -- are in crt_internal.h.
 #include "crt_internal.h"
 
 namespace crtk {
 
-// VAR (CRT_FLAG_VARIANCE): beside c, the sum of squares q = q + x * x of the same quotients x = L_k / spp, carried across chunks in the
-// planes of `qacc` as c is in A.accum; the last chunk then leaves c and q on the handle for crt_variance.  Without VAR the code is
-// what it was before the flag existed.
+// VAR (CRT_FLAG_VARIANCE): beside c, the sum of squares q of the same quotients (fold_samples), carried across chunks in the planes of
+// `qacc` as c is in A.accum; the last chunk then leaves c and q on the handle for crt_variance.  Without VAR the code is what it was
+// before the flag existed.
 template <bool VAR> __device__ __forceinline__ void accumulate(const AParams& A, float* qacc)
 {
     uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, make_fastdiv_dev(A.tiles_x), A.width, A.height, i, j);
+    const SlotPixel px = slot_pixel(A, slot);
     F3 c = f3(0.0f, 0.0f, 0.0f);
     F3 q = f3(0.0f, 0.0f, 0.0f);
-    if (valid) {
-        // (the accumulator is uncached memory that commit-ring launches read and write with agent-scope atomics: the same accesses here)
-        if (!A.first_chunk) c = f3(acc_load(A.accum + slot), acc_load(A.accum + A.nslots + slot), acc_load(A.accum + 2ull * A.nslots + slot));
-        if (VAR && !A.first_chunk) q = f3(acc_load(qacc + slot), acc_load(qacc + A.nslots + slot), acc_load(qacc + 2ull * A.nslots + slot));
-        const float fspp = (float)A.spp;
-        for (uint32_t s = 0; s < A.chunk_samples; s++) { // temp_color += L / spp, in sample order (Render.cuh:348)
-            // (agent-scope loads: the radiance was written by the launch before this one, from other XCDs -- the same kind of hand-off as
-            // k_order_items -> k_mega3, whose plain loads were seen to return what an earlier kernel had left at the address, docs/experiments.md 6)
-            const float* lp = (const float*)&A.L[(uint64_t)s * A.nslots + slot];
-            const float lx = acc_load(lp), ly = acc_load(lp + 1), lz = acc_load(lp + 2);
-            if (VAR) {
-                const float xx = lx / fspp, xy = ly / fspp, xz = lz / fspp;
-                c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
-                q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz;
-            } else {
-                c.x = c.x + lx / fspp;
-                c.y = c.y + ly / fspp;
-                c.z = c.z + lz / fspp;
-            }
-        }
-        if (VAR) { acc_store(qacc + slot, q.x); acc_store(qacc + A.nslots + slot, q.y); acc_store(qacc + 2ull * A.nslots + slot, q.z); }
+    if (px.valid) {
+        if (!A.first_chunk) c = acc_load3(A.accum, A.nslots, slot);
+        if (VAR && !A.first_chunk) q = acc_load3(qacc, A.nslots, slot);
+        fold_samples<VAR>(A, slot, c, q);
+        if (VAR) acc_store3(qacc, A.nslots, slot, q);
         if (VAR || !A.last_chunk) {
-            acc_store(A.accum + slot, c.x); acc_store(A.accum + A.nslots + slot, c.y); acc_store(A.accum + 2ull * A.nslots + slot, c.z);
+            acc_store3(A.accum, A.nslots, slot, c);
             if (!A.last_chunk) return;
         }
-    } else if (!A.tiled_output || !A.last_chunk) {
+    } else if (!px.out || !A.last_chunk) {
         return;
     }
-    uint64_t o = A.tiled_output ? (uint64_t)slot : (uint64_t)j * A.width + i;
-    A.out_rgb[o * 3 + 0] = valid ? tonemap(c.x) : 0;
-    A.out_rgb[o * 3 + 1] = valid ? tonemap(c.y) : 0;
-    A.out_rgb[o * 3 + 2] = valid ? tonemap(c.z) : 0;
-    if (A.out_mean) { A.out_mean[o * 3 + 0] = c.x; A.out_mean[o * 3 + 1] = c.y; A.out_mean[o * 3 + 2] = c.z; }
+    write_color(A, px.o, px.valid, c);
 }
 
 __global__ __launch_bounds__(256) void k_accumulate(const AParams A) { accumulate<false>(A, nullptr); }
 __global__ __launch_bounds__(256) void k_accumulate_var(const AParams A, float* const qacc) { accumulate<true>(A, qacc); }
 
 // crt_variance (contract: include/crt.h): the variance of the mean from the handle's sums c (A.accum) and q, n = samples so far, written
-// to A.out_mean in the frame's layout (slot -> pixel as k_preview; padding slots of a tiled shard +0).  Reads the sums only.
+// to A.out_mean in the frame's layout (padding slots of a tiled shard +0).  Reads the sums only.
 __global__ __launch_bounds__(256) void k_variance(const AParams A, const float* const qacc, const float fn, const float fs)
 {
     uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, make_fastdiv_dev(A.tiles_x), A.width, A.height, i, j);
-    if (!valid && !A.tiled_output) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    if (!px.out) return;
     F3 v = f3(0.0f, 0.0f, 0.0f);
-    if (valid) {
-        const float r = fs / fn, rr = r * r;
-        v.x = variance_of(acc_load(A.accum + slot), acc_load(qacc + slot), fn, rr);
-        v.y = variance_of(acc_load(A.accum + A.nslots + slot), acc_load(qacc + A.nslots + slot), fn, rr);
-        v.z = variance_of(acc_load(A.accum + 2ull * A.nslots + slot), acc_load(qacc + 2ull * A.nslots + slot), fn, rr);
+    if (px.valid) {
+        const float r = fs / fn;
+        v = variance_of3(acc_load3(A.accum, A.nslots, slot), acc_load3(qacc, A.nslots, slot), fn, r * r);
     }
-    const uint64_t o = A.tiled_output ? (uint64_t)slot : (uint64_t)j * A.width + i;
-    A.out_mean[o * 3 + 0] = v.x; A.out_mean[o * 3 + 1] = v.y; A.out_mean[o * 3 + 2] = v.z;
+    A.out_mean[px.o * 3 + 0] = v.x; A.out_mean[px.o * 3 + 1] = v.y; A.out_mean[px.o * 3 + 2] = v.z;
 }
 
 // crt_preview: the frame a progressive render would show now.  The accumulator holds sum_{k < done} L_k / spp (Render.cuh:348
-// with the samples so far); its estimate of the mean is that sum * spp / done.  Reads the accumulator only.
+// with the samples so far); its estimate of the mean is that sum * spp / done.  Reads the accumulator only, with plain loads.
 __global__ __launch_bounds__(256) void k_preview(const AParams A, const float scale)
 {
     uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    uint32_t i = 0, j = 0;
-    const bool valid = slot_to_pixel(slot, A.rank, A.world, A.n_tiles, A.tiles_x, make_fastdiv_dev(A.tiles_x), A.width, A.height, i, j);
-    if (!valid && !A.tiled_output) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    if (!px.out) return;
     F3 c = f3(0.0f, 0.0f, 0.0f);
-    if (valid) c = f3(A.accum[slot] * scale, A.accum[A.nslots + slot] * scale, A.accum[2ull * A.nslots + slot] * scale);
-    const uint64_t o = A.tiled_output ? (uint64_t)slot : (uint64_t)j * A.width + i;
-    A.out_rgb[o * 3 + 0] = valid ? tonemap(c.x) : 0;
-    A.out_rgb[o * 3 + 1] = valid ? tonemap(c.y) : 0;
-    A.out_rgb[o * 3 + 2] = valid ? tonemap(c.z) : 0;
-    if (A.out_mean) { A.out_mean[o * 3 + 0] = c.x; A.out_mean[o * 3 + 1] = c.y; A.out_mean[o * 3 + 2] = c.z; }
+    if (px.valid) c = f3(A.accum[slot] * scale, A.accum[A.nslots + slot] * scale, A.accum[2ull * A.nslots + slot] * scale);
+    write_color(A, px.o, px.valid, c);
 }
 
 // ------------------------------------------------------------ test kernels --

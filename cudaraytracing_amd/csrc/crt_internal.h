@@ -1,5 +1,6 @@
 // cudaraytracing_amd/csrc/crt_internal.h -- between the translation units of libcrt.so's device layer: error plumbing, device
-// buffers, and the launch entry points each kernel file exports to the host code in crt_render.hip (crt_scene.h: the scene handle).
+// buffers (with the copies of the host-buffer forms), the stages the image-space kernels share (slot map, three-plane sums, sample fold,
+// output write), and the launch entry points each kernel file exports to the host code in crt_render.hip (crt_scene.h: the scene handle).
 #ifndef CRT_INTERNAL_H
 #define CRT_INTERNAL_H
 #include <cstdlib>
@@ -78,6 +79,18 @@ template <typename T> struct DevBuf {
         if (!v.empty()) HIP_CHECK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return p;
     }
+    // the host-buffer forms of the entry points: a buffer the size of the host array (null: none, and nothing to copy back)
+    T* upload(const T* h, size_t count)
+    {
+        if (!h) return nullptr;
+        alloc(count);
+        HIP_CHECK(hipMemcpy(p, h, count * sizeof(T), hipMemcpyHostToDevice));
+        return p;
+    }
+    void download(T* h, size_t count) const
+    {
+        if (h) HIP_CHECK(hipMemcpy(h, p, count * sizeof(T), hipMemcpyDeviceToHost));
+    }
     void release()
     {
         if (p) { (void)hipFree(p); p = nullptr; n = 0; uncached = false; }
@@ -87,7 +100,7 @@ template <typename T> struct DevBuf {
 
 const int kMaxBatch = 64;
 
-// the frame's tone map, shared by k_accumulate / k_preview (crt_frame.hip) and the denoiser's last pass (crt_denoise.hip)
+// the frame's tone map (write_color)
 __device__ __forceinline__ uint8_t to_u8(float v)
 {
     if (!(v == v)) return 0;
@@ -102,19 +115,75 @@ __device__ __forceinline__ uint8_t tonemap(float c)
     return to_u8(255 * det_powf(cl, 0.6f));
 }
 
-// shared by the per-pixel-slot kernels of crt_frame.hip and crt_adaptive.hip
-__device__ __forceinline__ FastDiv make_fastdiv_dev(uint32_t d)
+// ---- the image-space kernels' shared stages (crt_frame.hip, crt_adaptive.hip, crt_aov.hip; the denoiser takes write_color) ----
+// Which pixel slots a shard has and where each one's pixel lies in the output: the arguments of slot_to_pixel (crt_path.h) and the
+// output layout.  Filled on the host by fill_slot_map (crt_scene.h).
+struct SlotMap {
+    uint32_t width, height, rank, world, tiles_x, n_tiles, nslots, tiled_output;
+    FastDiv tiles_x_div;
+};
+// A slot of the map: `valid` = it is a pixel, (i, j); `out` = it has an entry in the output (every slot of a tiled output, padding
+// included; the pixels of a row-major one), at index o
+struct SlotPixel {
+    bool valid, out;
+    uint32_t i, j;
+    uint64_t o;
+};
+__device__ __forceinline__ SlotPixel slot_pixel(const SlotMap& m, const uint32_t slot)
 {
-    // k_accumulate runs once per pixel: derive the magic on the fly (same formula as make_fastdiv)
-    uint32_t l = d > 1 ? 32u - (uint32_t)__clz((int)(d - 1)) : 0u;
-    FastDiv f;
-    f.m = (uint32_t)((((1ull << l) - d) << 32) / d + 1);
-    f.sh = (l < 1 ? l : 1u) | ((l > 0 ? l - 1 : 0u) << 8);
-    return f;
+    SlotPixel p;
+    p.i = 0; p.j = 0;
+    p.valid = slot_to_pixel(slot, m.rank, m.world, m.n_tiles, m.tiles_x, m.tiles_x_div, m.width, m.height, p.i, p.j);
+    p.out = p.valid || m.tiled_output;
+    p.o = m.tiled_output ? (uint64_t)slot : (uint64_t)p.j * m.width + p.i;
+    return p;
 }
 
+// the frame kernels (k_accumulate, k_preview, k_variance) and, inside AdaptiveParams, the adaptive ones
+struct AParams : SlotMap {
+    uint32_t spp;
+    uint32_t chunk_samples;
+    uint32_t first_chunk, last_chunk;
+    const float4* L;
+    float* accum;      // 3 planes of nslots (running sum across chunks)
+    uint8_t* out_rgb;
+    float* out_mean;   // may be null
+};
+
+// The sums c and q: three planes of nslots floats in uncached memory that commit-ring launches read and write with agent-scope atomics --
+// the same accesses here
 __device__ __forceinline__ float acc_load(const float* p) { return __uint_as_float(__hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
 __device__ __forceinline__ void acc_store(float* p, const float v) { __hip_atomic_store((unsigned int*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ F3 acc_load3(const float* planes, const uint32_t nslots, const uint32_t slot)
+{
+    return f3(acc_load(planes + slot), acc_load(planes + nslots + slot), acc_load(planes + 2ull * nslots + slot));
+}
+__device__ __forceinline__ void acc_store3(float* planes, const uint32_t nslots, const uint32_t slot, const F3 v)
+{
+    acc_store(planes + slot, v.x); acc_store(planes + nslots + slot, v.y); acc_store(planes + 2ull * nslots + slot, v.z);
+}
+
+// The chunk's samples of a slot into its sums, in sample order: c = c + L / spp (Render.cuh:348); VAR (CRT_FLAG_VARIANCE, adaptive
+// passes): also the sum of squares q = q + x * x of the same quotients x.  Without VAR q is not touched.
+// (agent-scope loads: the radiance was written by the launch before this one, from other XCDs -- the same kind of hand-off as
+// k_order_items -> k_mega3, whose plain loads were seen to return what an earlier kernel had left at the address, docs/experiments.md 6)
+template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& A, const uint32_t slot, F3& c, F3& q)
+{
+    const float fspp = (float)A.spp;
+    for (uint32_t s = 0; s < A.chunk_samples; s++) {
+        const float* lp = (const float*)&A.L[(uint64_t)s * A.nslots + slot];
+        const float lx = acc_load(lp), ly = acc_load(lp + 1), lz = acc_load(lp + 2);
+        if (VAR) {
+            const float xx = lx / fspp, xy = ly / fspp, xz = lz / fspp;
+            c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
+            q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz;
+        } else {
+            c.x = c.x + lx / fspp;
+            c.y = c.y + ly / fspp;
+            c.z = c.z + lz / fspp;
+        }
+    }
+}
 
 // the variance of the mean from the sums c and q (contract: crt_variance, include/crt.h); rr = (fs / fn)^2
 __device__ __forceinline__ float variance_of(const float c, const float q, const float fn, const float rr)
@@ -122,6 +191,22 @@ __device__ __forceinline__ float variance_of(const float c, const float q, const
     float d = fn * q - c * c;
     d = d < 0.0f ? 0.0f : d;
     return (rr * d) / (fn - 1.0f);
+}
+__device__ __forceinline__ F3 variance_of3(const F3 c, const F3 q, const float fn, const float rr)
+{
+    return f3(variance_of(c.x, q.x, fn, rr), variance_of(c.y, q.y, fn, rr), variance_of(c.z, q.z, fn, rr));
+}
+
+// Colour c of a pixel into entry o of the outputs of parameter block P (P.out_mean and P.out_rgb, either may be null): the mean as it
+// is and its tone map; a padding slot of a tiled output (!valid) gets 0 and c, which its kernel left +0
+template <class PB> __device__ __forceinline__ void write_color(const PB& P, const uint64_t o, const bool valid, const F3 c)
+{
+    if (P.out_mean) { P.out_mean[o * 3 + 0] = c.x; P.out_mean[o * 3 + 1] = c.y; P.out_mean[o * 3 + 2] = c.z; }
+    if (P.out_rgb) {
+        P.out_rgb[o * 3 + 0] = valid ? tonemap(c.x) : 0;
+        P.out_rgb[o * 3 + 1] = valid ? tonemap(c.y) : 0;
+        P.out_rgb[o * 3 + 2] = valid ? tonemap(c.z) : 0;
+    }
 }
 
 
@@ -146,18 +231,14 @@ void launch_rcp_check(unsigned long long* counts);
 
 // first-hit AOV pass (crt_aov.hip; host side: crt_render_aov in crt_render.hip).  One chunk = samples [sample_begin, sample_begin + n_samples)
 // of every pixel slot of the shard; query ray / result item = sample offset in the chunk x nslots + slot.
-struct AovParams {
-    // the camera, as LParams holds it (camera_dir)
+struct AovParams : SlotMap {
+    // the camera, as LParams holds it (camera_dir; width and height: the slot map's)
     float eye[3];
     float inv_view[9];
     float scale, ar;
-    uint32_t width, height;
     uint64_t seed;
-    // the shard's pixel slots (slot_to_pixel)
-    uint32_t rank, world, tiles_x, n_tiles, nslots;
-    FastDiv tiles_x_div;
     uint32_t spp, sample_begin, n_samples;
-    uint32_t first_chunk, last_chunk, tiled_output;
+    uint32_t first_chunk, last_chunk;
     Pool pool;               // k_aov_rays: the query pool (ro, rd, res)
     const float* res;        // k_aov_resolve: (t, bits(triangle or -1)) of item i at res[i * res_stride]
     uint32_t res_stride;     // floats per item: 4 (k_mega3 query form, L) or 2 (k_trace, the pool's res plane)

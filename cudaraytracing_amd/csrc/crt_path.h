@@ -506,18 +506,6 @@ __device__ __forceinline__ F3 finish_path(const LParams& P, const Tables<LDS_TAB
     return L;
 }
 
-struct AParams {
-    uint32_t width, height, spp;
-    uint32_t rank, world, tiles_x, n_tiles;
-    uint32_t nslots;
-    uint32_t chunk_samples;
-    uint32_t first_chunk, last_chunk, tiled_output;
-    const float4* L;
-    float* accum;      // 3 planes of nslots (running sum across chunks)
-    uint8_t* out_rgb;
-    float* out_mean;   // may be null
-};
-
 // 1.0f / x, bit for bit, in 3 instructions + a guard instead of the 12 of the IEEE division expansion: v_rcp_f32 and one
 // Newton step in FMA.  Verified EXHAUSTIVELY on gfx950 (tools/exhaustive/rcp_check.hip, all 2^32 inputs; crt_selftest()
 // repeats the check through the C ABI): the bits differ from the division's only for zero / denormal x, |x| >= 2^126

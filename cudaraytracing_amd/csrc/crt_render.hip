@@ -2,6 +2,7 @@
 // pipeline, the passes of an adaptive frame, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*,
 // crt_render_adaptive*, crt_preview*, crt_variance*, crt_render_aov*, crt_intersect, crt_device_*).  The scene handle is made in
 // crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_aov.hip.
+// The slot map of a shard and the host's form of the slot rule: crt_scene.h; host-buffer copies: DevBuf::upload / download.
 #include "crt_scene.h"
 
 #include <algorithm>
@@ -205,9 +206,8 @@ AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh)
 {
     AParams A;
     std::memset(&A, 0, sizeof(A));
-    A.width = f.width; A.height = f.height; A.spp = f.spp;
-    A.rank = f.rank; A.world = f.world; A.tiles_x = sh.tiles_x; A.n_tiles = sh.n_tiles;
-    A.nslots = sh.nslots; A.tiled_output = f.tiled;
+    fill_slot_map(A, f, f.tiled != 0, sh);
+    A.spp = f.spp;
     A.accum = sc->accum.p;
     return A;
 }
@@ -382,12 +382,8 @@ void render_mega(Frame& f)
             P.ring_done = sc->ring_done.p; P.ring_state = sc->ring_state.p; P.accum = sc->accum.p; P.L = sc->ring_L.p;
             std::vector<unsigned int>& state = sc->ring_state_host; // (a member: the copy below may still read it after this scope)
             state.assign((size_t)ring.shards * ITEM_STRIDE, 0u);
-            for (uint32_t slot = 0; slot < sh.nslots; slot++) { // word 1: the pixel slots of the shard that are pixels
-                const uint32_t tile = (slot >> 6) * prm->world + prm->rank, pix = slot & 63u;
-                if (tile >= sh.n_tiles) continue;
-                const uint32_t ty = tile / sh.tiles_x, tx = tile - ty * sh.tiles_x;
-                if (tx * CRT_TILE + (pix & 7u) < prm->width && ty * CRT_TILE + (pix >> 3) < prm->height) state[(size_t)(slot / ring.spsh) * ITEM_STRIDE + 1]++;
-            }
+            // word 1: the pixel slots of the shard that are pixels (ring.spsh is a multiple of 64: a tile's slots lie in one shard)
+            for (uint32_t lt = 0; lt < sh.local_tiles; lt++) state[(size_t)(lt * 64u / ring.spsh) * ITEM_STRIDE + 1] += tile_pixels(f.A, lt);
             HIP_CHECK(hipMemcpyAsync(sc->ring_state.p, state.data(), state.size() * sizeof(unsigned int), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemsetAsync(sc->ring_done.p, 0, (size_t)ring.shards * ring.samples * sizeof(unsigned int), st));
         }
@@ -674,15 +670,10 @@ int adaptive_check(const crt_scene* sc, const crt_camera* cam, const crt_params*
 }
 
 // Pixels of the shard (its pixel slots without the padding of ragged tiles and of tiles beyond the frame)
-uint64_t shard_pixels(const crt_params* prm, const Shard& sh)
+uint64_t shard_pixels(const SlotMap& m)
 {
     uint64_t n = 0;
-    for (uint32_t lt = 0; lt < sh.local_tiles; lt++) {
-        const uint32_t tile = lt * prm->world + prm->rank;
-        if (tile >= sh.n_tiles) break;
-        const uint32_t ty = tile / sh.tiles_x, tx = tile - ty * sh.tiles_x;
-        n += (uint64_t)std::min<uint32_t>(CRT_TILE, prm->width - tx * CRT_TILE) * std::min<uint32_t>(CRT_TILE, prm->height - ty * CRT_TILE);
-    }
+    for (uint32_t lt = 0; lt < m.nslots / 64u; lt++) n += tile_pixels(m, lt);
     return n;
 }
 
@@ -729,7 +720,7 @@ int adaptive_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, c
         HIP_CHECK(hipGetLastError());
         crt_adaptive_info I;
         std::memset(&I, 0, sizeof(I));
-        const uint64_t pixels = shard_pixels(&p, sh);
+        const uint64_t pixels = shard_pixels(D.A);
         I.passes = 1; I.paths = pixels * ap->min_samples; I.paths_uniform = pixels * S;
         double kernel_ms = 0.0;
         bool kernel_unread = true; // a pass's launches have been enqueued whose time (ev_k0 .. ev_k1) has not been added yet
@@ -821,10 +812,8 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
         std::memcpy(A.eye, cam->eye, sizeof(A.eye));
         std::memcpy(A.inv_view, cam->inv_view, sizeof(A.inv_view));
         camera_scale_ar(cam, prm, A.scale, A.ar);
-        A.width = prm->width; A.height = prm->height; A.seed = prm->seed;
-        A.rank = prm->rank; A.world = prm->world; A.tiles_x = sh.tiles_x; A.n_tiles = sh.n_tiles; A.nslots = sh.nslots;
-        A.tiles_x_div = make_fastdiv(sh.tiles_x);
-        A.spp = prm->spp; A.tiled_output = tiled ? 1u : 0u;
+        fill_slot_map(A, *prm, tiled, sh);
+        A.seed = prm->seed; A.spp = prm->spp;
         A.pool.ro = sc->p_ro.p; A.pool.rd = sc->p_rd.p; A.pool.res = sc->p_res.p;
         A.tri_nm = sc->dev.tri_nm; A.mats = sc->dev.mats; A.acc = sc->aov_acc.p;
         A.albedo = out->albedo; A.normal = out->normal; A.depth = out->depth; A.coverage = out->coverage; A.tri = out->tri; A.material = out->material;
@@ -891,8 +880,8 @@ struct Staging {
     void download(uint8_t* out_rgb, float* out_f32)
     {
         HIP_CHECK(hipDeviceSynchronize()); // Render.cuh:440
-        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, rgb.p, npix * 3, hipMemcpyDeviceToHost)); // Render.cuh:464
-        if (out_f32) HIP_CHECK(hipMemcpy(out_f32, f32.p, npix * 3 * sizeof(float), hipMemcpyDeviceToHost));
+        rgb.download(out_rgb, npix * 3); // Render.cuh:464
+        f32.download(out_f32, npix * 3);
     }
 };
 
@@ -977,7 +966,7 @@ int crt_render_adaptive(crt_scene* sc, const crt_camera* cam, const crt_params* 
         if (rc != CRT_OK) return rc;
         s.download(out_rgb, out_mean);
         v.download(nullptr, out_variance);
-        if (out_samples) HIP_CHECK(hipMemcpy(out_samples, n.p, npix * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        n.download(out_samples, npix);
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);
@@ -1091,10 +1080,8 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
     try {
         HIP_CHECK(hipSetDevice(sc->device));
         DevBuf<float> o, d, lim;
-        o.alloc(n * 3ull); d.alloc(n * 3ull);
-        HIP_CHECK(hipMemcpy(o.p, origins, n * 12ull, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(d.p, dirs, n * 12ull, hipMemcpyHostToDevice));
-        if (any_hit) { lim.alloc(n); HIP_CHECK(hipMemcpy(lim.p, out_t, n * 4ull, hipMemcpyHostToDevice)); }
+        o.upload(origins, n * 3ull); d.upload(dirs, n * 3ull);
+        if (any_hit) lim.upload(out_t, n);
         // blocked() of Render.cuh:19-27 from a finished visibility ray (limit = out_t[i] on entry): REFERENCE compares the closest
         // hit, FAST recorded a hit only if it passes the comparison (shadow_blocked)
         const bool reference_mode = traversal == CRT_TRAVERSAL_REFERENCE;
@@ -1109,7 +1096,7 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
         Pool pool;
         std::memset(&pool, 0, sizeof(pool));
         pool.ro = sc->p_ro.p; pool.rd = sc->p_rd.p; pool.res = sc->p_res.p; pool.n = n;
-        launch_fill_rays(pool, n, o.p, d.p, raw_dir, any_hit ? lim.p : (const float*)nullptr);
+        launch_fill_rays(pool, n, o.p, d.p, raw_dir, lim.p);
         HIP_CHECK(hipGetLastError());
         uint32_t stride = 0;
         const float* d_res = trace_queries(sc, n, traversal, force_exact, nullptr, stride);
@@ -1148,8 +1135,7 @@ int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, 
         const int rc = aov_impl(sc, cam, prm, &d, nullptr, info);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
-        for (int i = 0; i < 6; i++)
-            if (host[i]) HIP_CHECK(hipMemcpy(host[i], buf[i].p, npix * (i < 2 ? 3 : 1) * sizeof(float), hipMemcpyDeviceToHost));
+        for (int i = 0; i < 6; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);
@@ -1168,13 +1154,11 @@ int crt_device_math(int device, const char* fn, uint32_t n, const float* a, cons
     try {
         HIP_CHECK(hipSetDevice(device));
         DevBuf<float> da, db, dout;
-        da.alloc(n); dout.alloc(n);
-        HIP_CHECK(hipMemcpy(da.p, a, n * 4ull, hipMemcpyHostToDevice));
-        if (b) { db.alloc(n); HIP_CHECK(hipMemcpy(db.p, b, n * 4ull, hipMemcpyHostToDevice)); }
-        launch_math(id, n, da.p, b ? db.p : nullptr, dout.p);
+        da.upload(a, n); db.upload(b, n); dout.alloc(n);
+        launch_math(id, n, da.p, db.p, dout.p);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out, dout.p, n * 4ull, hipMemcpyDeviceToHost));
+        dout.download(out, n);
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);
@@ -1188,13 +1172,11 @@ int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32
     try {
         HIP_CHECK(hipSetDevice(device));
         DevBuf<uint32_t> c, k, o;
-        c.alloc(n * 4ull); k.alloc(n * 2ull); o.alloc(n * 4ull);
-        HIP_CHECK(hipMemcpy(c.p, ctr4, n * 16ull, hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(k.p, key2, n * 8ull, hipMemcpyHostToDevice));
+        c.upload(ctr4, n * 4ull); k.upload(key2, n * 2ull); o.alloc(n * 4ull);
         launch_philox(n, c.p, k.p, o.p);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out4, o.p, n * 16ull, hipMemcpyDeviceToHost));
+        o.download(out4, n * 4ull);
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);
@@ -1213,7 +1195,7 @@ int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside)
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         unsigned long long h[2];
-        HIP_CHECK(hipMemcpy(h, c.p, sizeof(h), hipMemcpyDeviceToHost));
+        c.download(h, 2);
         *mismatches = h[0]; *outside = h[1];
         return CRT_OK;
     } catch (const HipFail& f) {

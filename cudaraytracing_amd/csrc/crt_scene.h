@@ -1,6 +1,6 @@
 // cudaraytracing_amd/csrc/crt_scene.h -- the scene handle of the device layer (struct crt_scene: the uploaded arrays, the buffers and
 // events a frame uses, what a progressive render has accumulated) and the small helpers crt_scene.hip (create / export / destroy) and
-// crt_render.hip (the launch logic) share.
+// crt_render.hip (the launch logic) share: the shard of a frame, its slot map for the image-space kernels, the host's form of the slot rule.
 #ifndef CRT_SCENE_H
 #define CRT_SCENE_H
 #include "crt_internal.h"
@@ -95,6 +95,26 @@ inline Shard make_shard(uint32_t w, uint32_t h, uint32_t world)
     s.local_tiles = (s.n_tiles + world - 1) / world; // padded so every rank writes the same number of slots
     s.nslots = s.local_tiles * 64u;
     return s;
+}
+
+// The slot map (crt_internal.h) of shard `sh` of a frame; F: crt_params or FrameMark (width, height, rank, world)
+template <class F> inline void fill_slot_map(SlotMap& m, const F& f, bool tiled, const Shard& sh)
+{
+    m.width = f.width; m.height = f.height; m.rank = f.rank; m.world = f.world;
+    m.tiles_x = sh.tiles_x; m.n_tiles = sh.n_tiles; m.nslots = sh.nslots;
+    m.tiled_output = tiled ? 1u : 0u;
+    m.tiles_x_div = make_fastdiv(sh.tiles_x);
+}
+
+// The host's form of the slot rule (slot_to_pixel, crt_path.h), a tile at a time: how many of the slots 64 * lt .. 64 * lt + 63 are
+// pixels.  Slot 64 * lt + pix is one iff the tile lies in the frame and (pix & 7, pix >> 3) lies in the part of the tile the frame covers.
+inline uint32_t tile_pixels(const SlotMap& m, uint32_t lt)
+{
+    const uint32_t tile = lt * m.world + m.rank;
+    if (tile >= m.n_tiles) return 0;
+    const uint32_t ty = tile / m.tiles_x, tx = tile - ty * m.tiles_x;
+    const uint32_t w = m.width - tx * CRT_TILE, h = m.height - ty * CRT_TILE;
+    return (w < CRT_TILE ? w : (uint32_t)CRT_TILE) * (h < CRT_TILE ? h : (uint32_t)CRT_TILE);
 }
 
 inline uint32_t env_u32(const char* name, uint32_t dflt)
