@@ -180,6 +180,10 @@ class Render:
         self.variance_buffer = None
         self.samples_buffer = None
         self.adaptive_info = None
+        self.temporal_info = None
+        self.temporal_history_buffer = None
+        self._temporal = None        # run_view_temporal: the history (temporal()'s `prev` dict), its camera and size
+        self._temporal_frames = 0    # frames since the last reset_temporal()
 
     def _handle(self, what):
         """The crt_scene* of this renderer; raises when there is none (freed, or a MultiRender, whose handle is a crt_multi*)."""
@@ -228,11 +232,7 @@ class Render:
         self.light_sample_n = int(n)
 
     def _cam(self, eye_pos, inv_view_mat, fovY):
-        cam = capi.Camera()
-        cam.eye[:] = [float(v) for v in np.asarray(eye_pos, dtype=np.float32)]
-        cam.inv_view[:] = [float(v) for v in np.asarray(inv_view_mat, dtype=np.float32).reshape(9)]
-        cam.fov_y = float(np.float32(fovY))
-        return cam
+        return _camera(eye_pos, inv_view_mat, fovY)
 
     def _params(self, rank=0, world=1, flags=0, width=None, height=None):
         return capi.Params(width or self.scene.width, height or self.scene.height, self.spp, float(self.P_RR),
@@ -412,6 +412,43 @@ class Render:
                                                **self.aov_buffers)
         return rgb, mean
 
+    def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, **overrides):
+        """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
+        AOV pass (albedo, normal, depth, material) and blends the frame into the history this object keeps -- colour, variance, history
+        length, depth, normal, material ID and camera of the previous call; the unfiltered result is the next call's history.
+        Returns (rgb, mean) of the accumulated frame, or with denoise=True of its variance-guided filter (denoise_var of the accumulated
+        mean and variance, the frame's guides).  seed=None renders with self.seed + the number of frames since the last reset (the
+        frames must not share a seed); overrides: depth_tolerance, normal_tolerance, alpha_min.  The first call, the first after
+        reset_temporal() and the first at another size start a history.  self.frame_buffer / self.mean_buffer hold the frame as
+        rendered, self.variance_buffer the accumulated variance, self.temporal_history_buffer the frames accumulated per pixel (H, W),
+        self.temporal_info the crt_temporal_info dict, self.aov_buffers the guides."""
+        self._handle("run_view_temporal")
+        keep_seed = self.seed
+        self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
+        try:
+            self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=True)
+            aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth", "material"), width=width, height=height)
+        finally:
+            self.seed = keep_seed
+        h, w = self.mean_buffer.shape[:2]
+        cam = (np.array(eye_pos, dtype=np.float32), np.array(inv_view_mat, dtype=np.float32).reshape(9), np.float32(fovY))
+        cur = {"color": self.mean_buffer, "variance": self.variance_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
+        t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h)) else None
+        rgb, mean, var, hist, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
+                                              return_info=True, **overrides)
+        self._temporal = {"prev": dict(cur, color=mean, variance=var, history=hist), "camera": cam, "size": (w, h)}
+        self._temporal_frames += 1
+        self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
+        self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
+        if denoise:
+            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, return_info=True, **self.aov_buffers)
+        return rgb, mean
+
+    def reset_temporal(self):
+        """Drops the history of run_view_temporal: the next call is a first frame (and renders with self.seed again)."""
+        self._temporal = None
+        self._temporal_frames = 0
+
     def intersect(self, origins, dirs, traversal=None):
         self._handle("intersect")
         o = np.ascontiguousarray(origins, dtype=np.float32)
@@ -535,6 +572,9 @@ class MultiRender(Render):
 
     def run_view_denoised(self, *a, **k):
         raise NotImplementedError("the denoiser is a single-device interface (crt_denoise): gather the frame first")
+
+    def run_view_temporal(self, *a, **k):
+        raise NotImplementedError("temporal accumulation is a single-device interface (crt_temporal): gather the frame first")
 
     def intersect(self, *a, **k):
         raise NotImplementedError("crt_intersect is a single-device interface")
@@ -709,6 +749,106 @@ def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                                                  C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
                                                  C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
                "crt_denoise_var_device")
+    return info.as_dict() if want_info else None
+
+
+def _camera(eye_pos, inv_view_mat, fovY):
+    cam = capi.Camera()
+    cam.eye[:] = [float(v) for v in np.asarray(eye_pos, dtype=np.float32)]
+    cam.inv_view[:] = [float(v) for v in np.asarray(inv_view_mat, dtype=np.float32).reshape(9)]
+    cam.fov_y = float(np.float32(fovY))
+    return cam
+
+
+def temporal_defaults():
+    """crt_temporal_defaults as a dict: depth_tolerance, normal_tolerance, alpha_min."""
+    p = capi.TemporalParams()
+    capi.check(capi.lib().crt_temporal_defaults(C.byref(p)), "crt_temporal_defaults")
+    return {n: getattr(p, n) for n in ("depth_tolerance", "normal_tolerance", "alpha_min")}
+
+
+def _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min):
+    p = capi.TemporalParams()
+    capi.check(capi.lib().crt_temporal_defaults(C.byref(p)), "crt_temporal_defaults")
+    p.width, p.height = int(width), int(height)
+    p.cur = _camera(*camera)
+    p.prev = _camera(*(prev_camera if prev_camera is not None else camera))
+    for name, v in (("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("alpha_min", alpha_min)):
+        if v is not None:
+            setattr(p, name, float(v))
+    return p
+
+
+# the buffers of crt_temporal_frame / crt_temporal_history: name -> (values per pixel, numpy type)
+_TEMPORAL_BUFFERS = {"color": (3, np.float32), "variance": (3, np.float32), "history": (1, np.float32), "depth": (1, np.float32),
+                     "normal": (3, np.float32), "id": (1, np.int32)}
+
+
+def _temporal_struct(struct, buffers, h, w, keep):
+    for name, _ in struct._fields_:
+        a = buffers.get(name)
+        if a is None:
+            continue
+        ch, dt = _TEMPORAL_BUFFERS[name]
+        a = np.ascontiguousarray(a, dtype=dt)
+        if a.shape != ((h, w, 3) if ch == 3 else (h, w)):
+            raise ValueError("temporal: %s has shape %r for a %d x %d frame" % (name, a.shape, w, h))
+        keep.append(a)
+        setattr(struct, name, a.ctypes.data)
+    unknown = set(buffers) - {n for n, _ in struct._fields_}
+    if unknown:
+        raise ValueError("temporal: unknown buffers %r" % sorted(unknown))
+    return struct
+
+
+def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, want_rgb=True,
+             return_info=False):
+    """Temporal accumulation with reprojection (crt_temporal, contract: include/crt.h).  cur: dict of the current frame -- color
+    (H, W, 3), depth (H, W), optionally variance, normal (H, W, 3) and id (H, W) int32; prev: dict of the history -- color, history,
+    depth, and variance / normal / id as cur has them -- or None for a first frame; camera, prev_camera: (eye, inv_view, fov_y) of the
+    two frames.  None settings take crt_temporal_defaults.  Returns (rgb, color, variance, history): the tone map (None without
+    want_rgb), the accumulated colour, its variance (None if cur has none) and the frames accumulated per pixel; with return_info
+    also the crt_temporal_info dict."""
+    c = np.ascontiguousarray(cur["color"], dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("temporal needs an (H, W, 3) colour image, got %r" % (c.shape,))
+    if prev is not None and prev_camera is None:
+        raise ValueError("temporal: a history needs the camera it was made with")
+    h, w = c.shape[:2]
+    keep = []
+    fc = _temporal_struct(capi.TemporalFrame(), cur, h, w, keep)
+    fp = _temporal_struct(capi.TemporalHistory(), prev, h, w, keep) if prev is not None else None
+    prm = _temporal_params(w, h, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min)
+    color = np.zeros((h, w, 3), dtype=np.float32)
+    var = np.zeros((h, w, 3), dtype=np.float32) if cur.get("variance") is not None else None
+    hist = np.zeros((h, w), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.TemporalInfo()
+    capi.check(capi.lib().crt_temporal(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, capi.ptr(color), capi.ptr(var),
+                                       capi.ptr(hist), capi.ptr(rgb), C.byref(info)), "crt_temporal")
+    out = (rgb, color, var, hist)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_ptr, out_variance_ptr=None, out_rgb_ptr=None, prev_ptrs=None,
+                    prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True):
+    """Enqueues crt_temporal_device with everything in device memory: cur_ptrs / prev_ptrs = {name: raw device pointer} with the names of
+    temporal()'s dicts (prev_ptrs None: no history).  With want_info the call synchronizes the stream and returns the crt_temporal_info
+    dict, else None."""
+    def fill(struct, ptrs):
+        for name, p in ptrs.items():
+            if name not in {n for n, _ in struct._fields_}:
+                raise ValueError("temporal_device: unknown buffer %r" % name)
+            setattr(struct, name, int(p) if p else None)
+        return struct
+    fc = fill(capi.TemporalFrame(), cur_ptrs)
+    fp = fill(capi.TemporalHistory(), prev_ptrs) if prev_ptrs is not None else None
+    prm = _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min)
+    info = capi.TemporalInfo()
+    vp = lambda p: C.c_void_p(p) if p else None
+    capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, vp(out_color_ptr),
+                                              vp(out_variance_ptr), vp(out_history_ptr), vp(out_rgb_ptr), vp(stream),
+                                              C.byref(info) if want_info else None), "crt_temporal_device")
     return info.as_dict() if want_info else None
 
 

@@ -9,6 +9,12 @@
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
 //           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]
+//           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise]
+// --temporal N renders N frames on one device and accumulates them over time (crt_temporal, its defaults): frame f = 0 .. N-1 has eye and
+// lookat moved by f x the --temporal-step vector and the seed --seed + f.  -o gets the last frame as rendered, --temporal-out PATH the
+// accumulated last frame; --temporal-denoise writes the variance-guided filter (crt_denoise_var, its defaults with the --denoise-iterations
+// / --denoise-sigma overrides) of the accumulated frame and its accumulated variance to --temporal-out instead.  --variance, --denoise and
+// --aov work on the last frame as rendered.
 // --adaptive THRESHOLD renders the frame with variance-driven adaptive sampling (crt_render_adaptive, one device): --spp is the cap, a
 // pixel stops once the standard error of its mean is at most THRESHOLD x (mean + floor); --adaptive-min / --adaptive-step override the
 // warm-up and the samples per pass of crt_adaptive_defaults, --adaptive-samples PATH writes the samples per pixel as a 1-channel PFM.
@@ -40,7 +46,8 @@ int main(int argc, char** argv)
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
-                             "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n", argv[0]);
+                             "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n"
+                             "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise]\n", argv[0]);
         return 2;
     }
     try {
@@ -53,6 +60,10 @@ int main(int argc, char** argv)
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false;
+        int temporal = 0;
+        bool temporal_option = false, temporal_denoise = false;
+        float temporal_step[3] = {0.0f, 0.0f, 0.0f};
+        std::string temporal_out;
         uint64_t seed = 0;
         int device = 0;
         bool reference = false, exact = false, fast = false, bounded = false;
@@ -100,6 +111,24 @@ int main(int argc, char** argv)
             else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-step") { need(i, 1); ad.step_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-samples") { need(i, 1); adaptive_samples = argv[++i]; ad_option = true; }
+            else if (a == "--temporal") {
+                need(i, 1);
+                temporal = std::atoi(argv[++i]);
+                if (temporal < 1) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal needs a positive number of frames");
+            }
+            else if (a == "--temporal-step") {
+                need(i, 1);
+                temporal_option = true;
+                const char* q = argv[++i];
+                for (int k = 0; k < 3; k++) {
+                    char* end = nullptr;
+                    temporal_step[k] = std::strtof(q, &end);
+                    if (end == q || (k < 2 ? *end != ',' : *end != 0)) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step needs three comma-separated values: x,y,z");
+                    q = end + 1;
+                }
+            }
+            else if (a == "--temporal-out") { need(i, 1); temporal_out = argv[++i]; temporal_option = true; }
+            else if (a == "--temporal-denoise") { temporal_denoise = true; temporal_option = true; }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
@@ -134,9 +163,17 @@ int main(int argc, char** argv)
         if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
         if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
         if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
+        if (multi && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates on one device (not with --gpus / --devices)");
+        if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
+        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out and --temporal-denoise need --temporal N");
+        if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step and --adaptive-samples need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
-        const bool want_var = !variance.empty() || denoise_var;
+        const bool want_var = !variance.empty() || denoise_var || temporal > 0;
+        crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
+        crt_denoise_var_defaults(&tdn);
+        if (dn_iterations) tdn.iterations = dn.iterations;
+        if (dn_sigma) { tdn.sigma_color = dn.sigma_color; tdn.sigma_normal = dn.sigma_normal; tdn.sigma_albedo = dn.sigma_albedo; tdn.sigma_depth = dn.sigma_depth; }
         {
             crt_denoise_params d;
             if (denoise_var) crt_denoise_var_defaults(&d); else crt_denoise_defaults(&d);
@@ -154,7 +191,23 @@ int main(int argc, char** argv)
         crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
         float fov_y = task.fov_y * (float)M_PI / 180; // src/main.cu:278
         auto t0 = std::chrono::high_resolution_clock::now();
-        if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
+        if (temporal) {
+            crt_temporal_params tp;
+            crt_temporal_defaults(&tp);
+            const float eye0[3] = {task.eye_pos[0], task.eye_pos[1], task.eye_pos[2]}, lookat0[3] = {task.lookat[0], task.lookat[1], task.lookat[2]};
+            for (int f = 0; f < temporal; f++) { // (the last frame's camera stays in task / inv_view for the outputs below)
+                for (int k = 0; k < 3; k++) {
+                    task.eye_pos[k] = eye0[k] + (float)f * temporal_step[k];
+                    task.lookat[k] = lookat0[k] + (float)f * temporal_step[k];
+                }
+                crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
+                render.set_seed(seed + (uint64_t)f);
+                render.run_temporal(task.eye_pos, inv_view, fov_y, tp);
+                std::printf("temporal frame %d: %llu of %llu pixels reprojected, device %.3f ms\n", f, (unsigned long long)render.last_temporal_info().reprojected,
+                            (unsigned long long)task.width * task.height, render.last_temporal_info().total_ms);
+            }
+        }
+        else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
         else render.run_view(task.eye_pos, inv_view, fov_y);
         std::chrono::duration<double> dt = std::chrono::high_resolution_clock::now() - t0;
         if (adaptive) {
@@ -213,6 +266,14 @@ int main(int argc, char** argv)
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);
             render.save_denoised_buffer(denoise.c_str());
             std::printf("%s\n", denoise.c_str());
+        }
+        if (!temporal_out.empty()) {
+            if (temporal_denoise) {
+                render.run_denoise_temporal(tdn);
+                std::printf("temporal denoise: %u passes, device %.3f ms\n", render.last_denoise_info().passes, render.last_denoise_info().total_ms);
+                render.save_denoised_buffer(temporal_out.c_str());
+            } else render.save_temporal_buffer(temporal_out.c_str());
+            std::printf("%s\n", temporal_out.c_str());
         }
         render.free();
         return 0;

@@ -715,9 +715,9 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
     p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_;
     const size_t n = scene_->get_pixels();
-    albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f);
+    albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f); material_buffer_.assign(n, 0);
     crt_aov_buffers out{};
-    out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data();
+    out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data(); out.material = material_buffer_.data();
     const int rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
 }
@@ -751,6 +751,20 @@ const float* Render::variance()
     return variance_buffer_.data();
 }
 
+// crt_denoise_var of a colour and its variance with the guides of the last run_aov
+void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm)
+{
+    const size_t n = scene_->get_pixels();
+    crt_denoise_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    crt_denoise_var_inputs in{};
+    in.color = color; in.variance = variance;
+    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), nullptr, &denoise_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
+}
+
 void Render::run_denoise_var(const crt_denoise_params& prm)
 {
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise_var: the denoiser is a single-device interface");
@@ -758,14 +772,52 @@ void Render::run_denoise_var(const crt_denoise_params& prm)
     const size_t n = scene_->get_pixels();
     if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
         throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var needs run_view and run_aov of this frame size first");
-    crt_denoise_params p = prm;
+    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
+}
+
+void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_temporal: temporal accumulation is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal after free()");
+    if (!(flags_ & CRT_FLAG_VARIANCE)) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal needs set_flags(CRT_FLAG_VARIANCE)");
+    run_view(eye_pos, inv_view_mat, fovY);
+    const float* var = variance();
+    run_aov(eye_pos, inv_view_mat, fovY);
+    crt_temporal_params p = prm;
     p.width = scene_->get_width(); p.height = scene_->get_height();
-    crt_denoise_var_inputs in{};
-    in.color = mean_buffer_.data(); in.variance = variance();
-    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), nullptr, &denoise_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise_var failed: ") + crt_last_error());
+    std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
+    std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
+    p.cur.fov_y = fovY;
+    const bool have = temporal_valid_ && temporal_width_ == p.width && temporal_height_ == p.height;
+    p.prev = have ? temporal_cam_ : p.cur;
+    const size_t n = scene_->get_pixels();
+    crt_temporal_frame cur{};
+    cur.color = mean_buffer_.data(); cur.variance = var; cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
+    crt_temporal_history prev{};
+    prev.color = temporal_color_.data(); prev.variance = temporal_variance_.data(); prev.history = temporal_history_.data();
+    prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
+    std::vector<float> color(3 * n, 0.0f), variance_out(3 * n, 0.0f), history(n, 0.0f);
+    temporal_rgb_.assign(3 * n, 0);
+    const int rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &temporal_info_);
+    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal failed: ") + crt_last_error()); }
+    temporal_color_.swap(color); temporal_variance_.swap(variance_out); temporal_history_.swap(history);
+    temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
+    temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
+    temporal_valid_ = true;
+}
+
+void Render::run_denoise_temporal(const crt_denoise_params& prm)
+{
+    if (!temporal_valid_ || temporal_color_.size() != (size_t)3 * scene_->get_pixels())
+        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first");
+    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm);
+}
+
+void Render::save_temporal_buffer(const char* save_path) const
+{
+    if (temporal_rgb_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_temporal_buffer before run_temporal");
+    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), temporal_rgb_.data());
+    if (rc != CRT_OK) throw Error(rc, std::string("save_temporal_buffer failed: ") + crt_last_error());
 }
 
 void Render::save_denoised_buffer(const char* save_path) const

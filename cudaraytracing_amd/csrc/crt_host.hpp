@@ -235,6 +235,21 @@ public:
     // per-pixel variance of the mean of the last run_view (crt_variance; needs set_flags(CRT_FLAG_VARIANCE) before it): W x H x 3,
     // fetched from the device on the first call after a frame; one device only
     const float* variance();
+    // One frame of a temporally accumulated sequence (crt_temporal; prm: crt_temporal_defaults with overrides, its sizes and cameras are set
+    // here): run_view (needs set_flags(CRT_FLAG_VARIANCE)), variance, run_aov, then the frame is blended into the history this object keeps
+    // -- colour, variance, history length, depth, normal, material ID and camera of the previous call -- and the unfiltered result becomes
+    // the new history.  The first call, the first after reset_temporal() or after a change of size starts a history.  Render every frame
+    // with another seed (set_seed).  frame and mean buffers hold the frame as rendered; one device only
+    void run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm);
+    void reset_temporal() { temporal_valid_ = false; }
+    const unsigned char* get_temporal_buffer() const { return temporal_rgb_.data(); }        // W x H x 3 RGB8: the accumulated frame
+    const float* get_temporal_mean_buffer() const { return temporal_color_.data(); }          // W x H x 3
+    const float* get_temporal_variance_buffer() const { return temporal_variance_.data(); }   // W x H x 3
+    const float* get_temporal_history_buffer() const { return temporal_history_.data(); }     // W x H: frames accumulated per pixel
+    const crt_temporal_info& last_temporal_info() const { return temporal_info_; }
+    // the accumulated frame filtered by crt_denoise_var with its accumulated variance and the guides of the last frame
+    void run_denoise_temporal(const crt_denoise_params& prm);
+    void save_temporal_buffer(const char* save_path) const;
     const unsigned char* get_denoised_buffer() const { return denoised_buffer_.data(); } // W x H x 3 RGB8
     const float* get_denoised_mean_buffer() const { return denoised_mean_buffer_.data(); } // W x H x 3
     const crt_denoise_info& last_denoise_info() const { return denoise_info_; }
@@ -274,6 +289,16 @@ private:
     std::vector<float> denoised_mean_buffer_;
     std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame (run_view_adaptive fills it itself)
     std::vector<uint32_t> samples_buffer_;
+    std::vector<int32_t> material_buffer_; // run_aov
+    // run_temporal: the accumulated frame = the next call's history, with the guides and the camera it was made with
+    std::vector<float> temporal_color_, temporal_variance_, temporal_history_, temporal_depth_, temporal_normal_;
+    std::vector<int32_t> temporal_id_;
+    std::vector<unsigned char> temporal_rgb_;
+    crt_camera temporal_cam_{};
+    unsigned temporal_width_ = 0, temporal_height_ = 0;
+    bool temporal_valid_ = false;
+    crt_temporal_info temporal_info_{};
+    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm);
     crt_adaptive_info adaptive_info_{};
     int device_ = 0;
     crt_denoise_info denoise_info_{};

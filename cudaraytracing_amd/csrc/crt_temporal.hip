@@ -1,0 +1,295 @@
+// cudaraytracing_amd/csrc/crt_temporal.hip -- temporal accumulation with reprojection (crt_temporal / crt_temporal_device, contract:
+// include/crt.h): kernel and host code.  An image operation without a scene handle, the temporal half of SVGF beside crt_denoise_var.
+//
+// One call = one launch of k_temporal: one thread per pixel, block = 64 x 4 pixels, a wave = 64 consecutive pixels of one row (the
+// denoiser's pass).  A thread rebuilds the world point of its pixel from the current camera and the depth, projects it into the
+// previous camera, gathers the four bilinear taps straight from the caller's buffers (neighbouring pixels of a row land on neighbouring
+// taps unless the surface is seen at a grazing angle) and blends or resets.  The count of pixels that took the history is one ballot,
+// one popcount and one atomic per wave, as k_adaptive_select counts its slots; it is kept only when the caller asks for the info.
+#include "crt_internal.h"
+
+#include <cstring>
+#include <string>
+
+namespace crtk {
+
+struct TpParams {
+    uint32_t width, height, tiles_x;
+    float eye[3], iv[9], scale, ar;           // current camera; scale / ar as camera_scale_ar (crt_render.hip)
+    float peye[3], piv[9], pscale;            // the camera the history was made with
+    float depth_tol, normal_tol2, alpha_min;  // normal_tol2 = normal_tolerance * normal_tolerance
+    const float* color; const float* variance; const float* depth; const float* normal; const int32_t* id;          // current frame
+    const float* pcolor; const float* pvariance; const float* phistory; const float* pdepth; const float* pnormal; const int32_t* pid;
+    float* out_mean;                          // out_color (write_color's names)
+    uint8_t* out_rgb;
+    float* out_variance;
+    float* out_history;
+    unsigned long long* count;                // pixels that took the history (null: not counted)
+};
+
+__global__ __launch_bounds__(256) void k_temporal(const TpParams P)
+{
+    const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
+    const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
+    const int W = (int)P.width, H = (int)P.height;
+    const bool inside = x < W && y < H;
+    bool took = false;
+    if (inside) {
+        const size_t p = (size_t)y * P.width + (size_t)x;
+        const F3 c = f3(P.color[p * 3], P.color[p * 3 + 1], P.color[p * 3 + 2]);
+        F3 v = f3(0.0f, 0.0f, 0.0f);
+        if (P.variance) v = f3(P.variance[p * 3], P.variance[p * 3 + 1], P.variance[p * 3 + 2]);
+        F3 oc = c, ov = v;
+        float oh = 1.0f;
+        if (P.pcolor) {
+            const float fw = (float)W, fh = (float)H, dp = P.depth[p];
+            // the pixel-centre ray of the current camera (camera_dir without the jitter) and the point it reaches at the stored depth
+            const float sx = (((2 * ((float)x + 0.5f)) / fw - 1) * P.scale) * P.ar;
+            const float sy = (1 - (2 * ((float)y + 0.5f)) / fh) * P.scale;
+            const F3 cd = unit3(f3(-sx, sy, 1));
+            const F3 d = unit3(f3(P.iv[0] * cd.x + (P.iv[3] * cd.y + P.iv[6] * cd.z),
+                                  P.iv[1] * cd.x + (P.iv[4] * cd.y + P.iv[7] * cd.z),
+                                  P.iv[2] * cd.x + (P.iv[5] * cd.y + P.iv[8] * cd.z)));
+            const F3 wp = f3(P.eye[0] + d.x * dp, P.eye[1] + d.y * dp, P.eye[2] + d.z * dp);
+            // into the previous camera: inverse of its rotation (the transpose), then the inverse of the image-plane map
+            const F3 pv = f3(wp.x - P.peye[0], wp.y - P.peye[1], wp.z - P.peye[2]);
+            const float cx = P.piv[0] * pv.x + (P.piv[1] * pv.y + P.piv[2] * pv.z);
+            const float cy = P.piv[3] * pv.x + (P.piv[4] * pv.y + P.piv[5] * pv.z);
+            const float cz = P.piv[6] * pv.x + (P.piv[7] * pv.y + P.piv[8] * pv.z);
+            const float tp = sqrt_f(dot3(pv, pv));
+            const float fx = (((((-cx) / cz) / (P.pscale * P.ar)) + 1) * fw) / 2 - 0.5f;
+            const float fy = (((1 - (cy / cz) / P.pscale) * fh) / 2) - 0.5f;
+            const bool ok = dp > 0.0f && cz > 0.0f && fx > -1.0f && fx < fw && fy > -1.0f && fy < fh; // (false for NaN)
+            if (ok) {
+                const float flx = floorf(fx), fly = floorf(fy);
+                const float wx = fx - flx, wy = fy - fly;
+                const int x0 = (int)flx, y0 = (int)fly; // -1 .. W - 1, -1 .. H - 1
+                const float tol = P.depth_tol * tp;
+                F3 n = f3(0.0f, 0.0f, 0.0f);
+                if (P.normal) n = f3(P.normal[p * 3], P.normal[p * 3 + 1], P.normal[p * 3 + 2]);
+                const int32_t idp = P.id ? P.id[p] : 0;
+                F3 hc = f3(0.0f, 0.0f, 0.0f), hv = f3(0.0f, 0.0f, 0.0f);
+                float hn = 0.0f, ws = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int qy = y0 + j;
+                    if (qy < 0 || qy >= H) continue;
+#pragma unroll
+                    for (int i = 0; i < 2; i++) {
+                        const int qx = x0 + i;
+                        if (qx < 0 || qx >= W) continue;
+                        const size_t q = (size_t)qy * P.width + (size_t)qx;
+                        const float pd = P.pdepth[q];
+                        if (!(pd > 0.0f)) continue;
+                        if (!(fabsf(pd - tp) <= tol)) continue;
+                        if (P.normal) {
+                            const float dnx = n.x - P.pnormal[q * 3], dny = n.y - P.pnormal[q * 3 + 1], dnz = n.z - P.pnormal[q * 3 + 2];
+                            if (!(dnx * dnx + dny * dny + dnz * dnz <= P.normal_tol2)) continue;
+                        }
+                        if (P.id && idp != P.pid[q]) continue;
+                        const float b = (i ? wx : 1 - wx) * (j ? wy : 1 - wy);
+                        hc.x = hc.x + P.pcolor[q * 3] * b;
+                        hc.y = hc.y + P.pcolor[q * 3 + 1] * b;
+                        hc.z = hc.z + P.pcolor[q * 3 + 2] * b;
+                        if (P.variance) {
+                            hv.x = hv.x + P.pvariance[q * 3] * b;
+                            hv.y = hv.y + P.pvariance[q * 3 + 1] * b;
+                            hv.z = hv.z + P.pvariance[q * 3 + 2] * b;
+                        }
+                        hn = hn + P.phistory[q] * b;
+                        ws = ws + b;
+                    }
+                }
+                if (ws > 0.015625f) {
+                    took = true;
+                    hn = hn / ws;
+                    oh = hn + 1;
+                    float a = 1 / oh;
+                    a = a < P.alpha_min ? P.alpha_min : a;
+                    const float k = 1 - a;
+                    oc = f3((hc.x / ws) * k + c.x * a, (hc.y / ws) * k + c.y * a, (hc.z / ws) * k + c.z * a);
+                    if (P.variance) {
+                        const float kk = k * k, aa = a * a;
+                        ov = f3((hv.x / ws) * kk + v.x * aa, (hv.y / ws) * kk + v.y * aa, (hv.z / ws) * kk + v.z * aa);
+                    }
+                }
+            }
+        }
+        write_color(P, p, true, oc);
+        if (P.out_variance) { P.out_variance[p * 3] = ov.x; P.out_variance[p * 3 + 1] = ov.y; P.out_variance[p * 3 + 2] = ov.z; }
+        P.out_history[p] = oh;
+    }
+    if (!P.count) return;
+    const unsigned long long mask = __ballot(took);
+    if (mask == 0ull) return;
+    if ((int)(threadIdx.x & 63u) == __ffsll((long long)mask) - 1)
+        __hip_atomic_fetch_add(P.count, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+} // namespace crtk
+
+using namespace crtk;
+
+namespace {
+
+const uint32_t kMaxSide = 1u << 24;
+bool tolerance_ok(float t) { return t > 0.0f; } // (false for NaN)
+
+// Argument checks of both forms, before any device call
+int temporal_check(const char* who, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, const void* out_color,
+                   const void* out_variance, const void* out_history)
+{
+    const std::string w(who);
+    if (!prm || !cur) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
+    if (!cur->color || !cur->depth) return fail(CRT_ERR_INVALID_ARG, w + ": the current frame needs colour and depth");
+    if (!out_color || !out_history) return fail(CRT_ERR_INVALID_ARG, w + ": out_color and out_history are required");
+    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (!tolerance_ok(prm->depth_tolerance) || !tolerance_ok(prm->normal_tolerance))
+        return fail(CRT_ERR_INVALID_ARG, w + ": every tolerance must be > 0 (+inf switches a test off)");
+    if (!(prm->alpha_min > 0.0f && prm->alpha_min <= 1.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": alpha_min must be in (0, 1]");
+    if ((cur->variance != nullptr) != (out_variance != nullptr))
+        return fail(CRT_ERR_INVALID_ARG, w + ": the current variance and out_variance go together");
+    if (prev) {
+        if (!prev->color || !prev->history || !prev->depth) return fail(CRT_ERR_INVALID_ARG, w + ": a history needs colour, history length and depth");
+        if (cur->variance && !prev->variance) return fail(CRT_ERR_INVALID_ARG, w + ": the history has no variance");
+        if ((cur->normal != nullptr) != (prev->normal != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": normals must be given in both frames or in neither");
+        if ((cur->id != nullptr) != (prev->id != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": IDs must be given in both frames or in neither");
+    }
+    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
+    if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
+    return CRT_OK;
+}
+
+void set_camera(const crt_camera& cam, float* eye, float* iv, float& scale)
+{
+    std::memcpy(eye, cam.eye, sizeof(cam.eye));
+    std::memcpy(iv, cam.inv_view, sizeof(cam.inv_view));
+    scale = det_tanf(cam.fov_y / 2);
+}
+
+int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, void* d_out_color,
+                  void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st, crt_temporal_info* info)
+{
+    const int rc = temporal_check(who, prm, cur, prev, d_out_color, d_out_variance, d_out_history);
+    if (rc != CRT_OK) return rc;
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int status = CRT_OK;
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        DevBuf<unsigned long long> d_count;
+        TpParams P;
+        std::memset(&P, 0, sizeof(P));
+        P.width = prm->width; P.height = prm->height;
+        P.tiles_x = (prm->width + 63) / 64;
+        set_camera(prm->cur, P.eye, P.iv, P.scale);
+        set_camera(prm->prev, P.peye, P.piv, P.pscale);
+        P.ar = (float)prm->width / (float)prm->height;
+        P.depth_tol = prm->depth_tolerance;
+        P.normal_tol2 = prm->normal_tolerance * prm->normal_tolerance;
+        P.alpha_min = prm->alpha_min;
+        P.color = cur->color; P.variance = cur->variance; P.depth = cur->depth;
+        if (prev) {
+            P.normal = cur->normal; P.id = cur->id; // (without a history nothing reads the guides)
+            P.pcolor = prev->color; P.pvariance = prev->variance; P.phistory = prev->history; P.pdepth = prev->depth;
+            P.pnormal = prev->normal; P.pid = prev->id;
+        }
+        P.out_mean = (float*)d_out_color; P.out_rgb = (uint8_t*)d_out_rgb;
+        P.out_variance = (float*)d_out_variance; P.out_history = (float*)d_out_history;
+        if (info) {
+            d_count.alloc(1);
+            HIP_CHECK(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
+            P.count = d_count.p;
+            HIP_CHECK(hipEventCreate(&e0));
+            HIP_CHECK(hipEventCreate(&e1));
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        hipLaunchKernelGGL(k_temporal, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P);
+        HIP_CHECK(hipGetLastError());
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            unsigned long long n = 0;
+            HIP_CHECK(hipMemcpyAsync(&n, d_count.p, sizeof(n), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            std::memset(info, 0, sizeof(*info));
+            info->reprojected = n;
+            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
+        }
+    } catch (const HipFail& f) {
+        status = fail_hip(f);
+    }
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return status;
+}
+
+// The host-buffer form (the caller has checked the arguments): device copies of the inputs, the device form, then the copies back.
+int temporal_host(int device, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, float* out_color,
+                  float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_info* info)
+{
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_temporal: device index out of range");
+    try {
+        HIP_CHECK(hipSetDevice(device));
+        const uint64_t npix = (uint64_t)prm->width * prm->height;
+        DevBuf<float> c_color, c_var, c_depth, c_normal, p_color, p_var, p_hist, p_depth, p_normal, o_color, o_var, o_hist;
+        DevBuf<int32_t> c_id, p_id;
+        DevBuf<uint8_t> o_rgb;
+        crt_temporal_frame dc{};
+        crt_temporal_history dp{};
+        dc.color = c_color.upload(cur->color, npix * 3);
+        dc.variance = c_var.upload(cur->variance, npix * 3);
+        dc.depth = c_depth.upload(cur->depth, npix);
+        dc.normal = c_normal.upload(cur->normal, npix * 3);
+        dc.id = c_id.upload(cur->id, npix);
+        if (prev) {
+            dp.color = p_color.upload(prev->color, npix * 3);
+            dp.variance = p_var.upload(prev->variance, npix * 3);
+            dp.history = p_hist.upload(prev->history, npix);
+            dp.depth = p_depth.upload(prev->depth, npix);
+            dp.normal = p_normal.upload(prev->normal, npix * 3);
+            dp.id = p_id.upload(prev->id, npix);
+        }
+        o_color.alloc(npix * 3);
+        o_hist.alloc(npix);
+        if (out_variance) o_var.alloc(npix * 3);
+        if (out_rgb) o_rgb.alloc(npix * 3);
+        const int rc = temporal_impl("crt_temporal_device", device, prm, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        o_color.download(out_color, npix * 3);
+        o_var.download(out_variance, npix * 3);
+        o_hist.download(out_history, npix);
+        o_rgb.download(out_rgb, npix * 3);
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+int crt_temporal_defaults(crt_temporal_params* prm)
+{
+    if (!prm) return fail(CRT_ERR_INVALID_ARG, "crt_temporal_defaults: null argument");
+    std::memset(prm, 0, sizeof(*prm));
+    prm->depth_tolerance = 0.05f; prm->normal_tolerance = 0.5f; prm->alpha_min = 0.05f;
+    return CRT_OK;
+}
+
+int crt_temporal_device(int device, const crt_temporal_params* prm, const crt_temporal_frame* dev_cur, const crt_temporal_history* dev_prev,
+                        void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* stream, crt_temporal_info* info)
+{
+    return temporal_impl("crt_temporal_device", device, prm, dev_cur, dev_prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, (hipStream_t)stream, info);
+}
+
+int crt_temporal(int device, const crt_temporal_params* prm, const crt_temporal_frame* host_cur, const crt_temporal_history* host_prev, float* out_color,
+                 float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_info* info)
+{
+    const int rc0 = temporal_check("crt_temporal", prm, host_cur, host_prev, out_color, out_variance, out_history);
+    if (rc0 != CRT_OK) return rc0;
+    return temporal_host(device, prm, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info);
+}
+
+} // extern "C"

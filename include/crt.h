@@ -478,6 +478,76 @@ int crt_denoise_var_device(int device, const crt_denoise_params* params, const c
                            void* d_out_rgb, void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream,
                            crt_denoise_info* info);
 
+/* Temporal accumulation with reprojection (the temporal half of SVGF, Schied et al. 2017): the frame of the current camera is blended
+ * with the accumulated frame of the previous camera, fetched where the surface point of each pixel was seen then, so that a moving
+ * camera keeps most of the samples it has already paid for.  An image operation: no scene handle, no scratch buffer.  Row-major images
+ * of width x height; color, variance, normal 3 floats per pixel; depth, history 1 float per pixel; id 1 int32 per pixel: what crt_render
+ * (out_mean), crt_variance and crt_render_aov (depth, normal, material or tri) return, as they are.  `history` is the number of frames
+ * accumulated in a pixel.  The caller keeps out_color, out_variance, out_history and the current frame's depth, normal and id as the next
+ * call's crt_temporal_history (with prev = this call's cur) and ping-pongs the buffers: outputs must not overlap any input.
+ * With scale = det_tanf(cur.fov_y / 2), scale' = det_tanf(prev.fov_y / 2), ar = (float)W / (float)H (host, as the camera rays take
+ * them), iv = cur.inv_view, iv' = prev.inv_view, eye = cur.eye, eye' = prev.eye, per pixel p = (x, y):
+ *   sx = (((2 * ((float)x + 0.5f)) / W - 1) * scale) * ar          sy = (1 - (2 * ((float)y + 0.5f)) / H) * scale
+ *   cd = unit3(-sx, sy, 1)                       unit3(a): z = a.x*a.x + (a.y*a.y + a.z*a.z); z > 0 ? a / sqrt(z) : a
+ *   wd = (iv[0]*cd.x + (iv[3]*cd.y + iv[6]*cd.z), iv[1]*cd.x + (iv[4]*cd.y + iv[7]*cd.z), iv[2]*cd.x + (iv[5]*cd.y + iv[8]*cd.z))
+ *   d  = unit3(wd)                               the pixel-centre camera ray
+ *   P  = eye + d * depth(p)                      per component: one multiply, one add
+ *   v  = P - eye'
+ *   cx = iv'[0]*v.x + (iv'[1]*v.y + iv'[2]*v.z)   cy = iv'[3]*v.x + (iv'[4]*v.y + iv'[5]*v.z)   cz = iv'[6]*v.x + (iv'[7]*v.y + iv'[8]*v.z)
+ *   tp = sqrt(v.x*v.x + (v.y*v.y + v.z*v.z))     the depth the previous frame would have stored for P
+ *   fx = (((((-cx) / cz) / (scale' * ar)) + 1) * W) / 2 - 0.5f     fy = (((1 - (cy / cz) / scale') * H) / 2) - 0.5f
+ *   ok = depth(p) > 0 && cz > 0 && fx > -1 && fx < W && fy > -1 && fy < H                  (a NaN anywhere: false)
+ *   x0 = floor(fx); wx = fx - x0; y0 = floor(fy); wy = fy - y0
+ *   taps q = (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner; a tap counts iff it is inside the image
+ *        && prev.depth(q) > 0 && |prev.depth(q) - tp| <= depth_tolerance * tp
+ *        && (normals given: dn = normal(p) - prev.normal(q); dn.x*dn.x + dn.y*dn.y + dn.z*dn.z <= normal_tolerance * normal_tolerance)
+ *        && (ids given: id(p) == prev.id(q));  for a tap that counts
+ *      b  = (i ? wx : 1 - wx) * (j ? wy : 1 - wy)
+ *      hc = hc + prev.color(q) * b;  hv = hv + prev.variance(q) * b;  hn = hn + prev.history(q) * b;  ws = ws + b
+ *   if ok && ws > 0.015625f:
+ *      hc = hc / ws; hv = hv / ws; hn = hn / ws;   n = hn + 1;   a = 1 / n;   a = a < alpha_min ? alpha_min : a;   k = 1 - a
+ *      out_color = hc * k + color(p) * a;   out_variance = hv * (k * k) + variance(p) * (a * a);   out_history = n
+ *   else (reset):  out_color = color(p);  out_variance = variance(p);  out_history = 1
+ * hc, hv (per channel), hn and ws start at +0.0f; sums run left to right as written; every * + - / and sqrt is one IEEE fp32 operation
+ * (no FMA, no reciprocal multiply).  Non-finite colours or variances in a tap that counts are not special-cased.  With alpha_min = 0 this
+ * would be the running mean of the frames; alpha_min bounds how long a stale sample lives.
+ * The pixel-centre ray and the MEAN hit distance of the pixel's jittered samples only approximate the surface point the pixel shows (at
+ * a silhouette the mean depth lies between two surfaces): the tolerances absorb that error, and a pixel they reject is reset.
+ * The variance line treats the two frames as independent estimates: render consecutive frames with DIFFERENT seeds, or the accumulated
+ * variance understates the noise (the same seed and camera would add the same frame to itself).
+ * Required: cur.color, cur.depth, out_color, out_history; with a history also prev.color, prev.history, prev.depth.  normal and id: in
+ * both frames or in neither.  cur.variance and out_variance: both or neither; prev.variance is then required too.  out_rgb (optional) is
+ * the frame's tone map of out_color, the bits crt_render writes for that mean.  host_prev / dev_prev == NULL: no history, every pixel
+ * resets.  crt_temporal_defaults fills depth_tolerance 0.05, normal_tolerance 0.5, alpha_min 0.05 (sizes and cameras zero); the two
+ * tolerances are the denoiser's sigma_depth and sigma_normal and were tuned on nothing; alpha_min was compared with 0.1 and 0.2 on two
+ * scenes and nothing more (docs/experiments.md, "Temporal accumulation").
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null required pointer, a size of 0, a tolerance that is not > 0 (NaN included;
+ * +inf is allowed and switches its test off), alpha_min outside (0, 1], a half-given pair.  A side longer than 2^24 pixels or more than
+ * 2^31 thread blocks of 64 x 4 pixels: CRT_ERR_UNSUPPORTED.
+ * Not done here: clamping the history to the colours around p (view-dependent highlights lag behind the camera), a wider search when
+ * the four taps fail, moving geometry, tiled shards. */
+typedef struct {
+    uint32_t width, height;
+    crt_camera cur, prev;          /* camera of the current frame / of the frame the history was made with */
+    float depth_tolerance;         /* relative; > 0, not NaN, +inf allowed */
+    float normal_tolerance;        /* > 0, not NaN, +inf allowed */
+    float alpha_min;               /* 0 < alpha_min <= 1 */
+} crt_temporal_params;
+typedef struct { const float* color; const float* variance; const float* depth; const float* normal; const int32_t* id; } crt_temporal_frame;   /* current frame */
+typedef struct { const float* color; const float* variance; const float* history; const float* depth; const float* normal; const int32_t* id; } crt_temporal_history;
+typedef struct {
+    float total_ms;        /* HIP-event time of the call's kernel on its stream */
+    uint64_t reprojected;  /* pixels that took the history */
+} crt_temporal_info;
+int crt_temporal_defaults(crt_temporal_params* params);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_temporal(int device, const crt_temporal_params* params, const crt_temporal_frame* host_cur, const crt_temporal_history* host_prev /* may be NULL */,
+                 float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then counts the reprojected pixels and synchronizes the stream to read them and the timer). */
+int crt_temporal_device(int device, const crt_temporal_params* params, const crt_temporal_frame* dev_cur, const crt_temporal_history* dev_prev,
+                        void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* hip_stream, crt_temporal_info* info);
+
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
  * (config_CUDA, src/main.cu:92-105); a crt_multi holds one device replica of the scene per entry of

@@ -1,0 +1,687 @@
+"""Temporal accumulation with reprojection (crt_temporal / crt_temporal_device, include/crt.h; temporal, temporal_device and
+Render.run_view_temporal in Python; crt_cli --temporal).
+
+The contract of include/crt.h is restated below in numpy float32, operation by operation, with the oracle's det_tanf
+(oracle_lib.math_fn("tan")) for the two camera scales and its tone map (oracle_lib.tonemap); the device result must match it bit for
+bit: colour, variance and history length on uint32 views (where the expected value is NaN the result must be NaN).  The restatement
+itself is checked against plain geometry on the CPU, and four GPU checks do not use it at all.
+"""
+import ctypes as C
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import util
+from util import assert_bits
+
+F = np.float32
+DEFAULTS = {"depth_tolerance": 0.05, "normal_tolerance": 0.5, "alpha_min": 0.05}
+
+
+def unit3(x, y, z):
+    """unit3 of csrc/crt_device.h: z = x*x + (y*y + z*z); a / sqrt(z) (a itself where z is not > 0)"""
+    n = x * x + (y * y + z * z)
+    s = np.sqrt(n)
+    pos = n > 0
+    return np.where(pos, x / s, x), np.where(pos, y / s, y), np.where(pos, z / s, z)
+
+
+def camera_scale(fov):
+    return O.math_fn("tan", np.array([F(fov) / F(2)], dtype=F))[0]
+
+
+def restated(cur, cam, prev=None, pcam=None, depth_tolerance=0.05, normal_tolerance=0.5, alpha_min=0.05):
+    """The contract, in numpy float32: every ufunc below is one IEEE fp32 operation per element.  cur / prev: the dicts crt.temporal
+    takes; cam / pcam: (eye, inv_view, fov_y).  Returns (color, variance or None, history, took): took = the pixels that took the history."""
+    color = np.ascontiguousarray(cur["color"], dtype=F)
+    H, W = color.shape[:2]
+    var = np.ascontiguousarray(cur["variance"], dtype=F) if cur.get("variance") is not None else None
+    ones = np.ones((H, W), dtype=F)
+    if prev is None:
+        return color.copy(), (var.copy() if var is not None else None), ones, np.zeros((H, W), dtype=bool)
+    depth = np.ascontiguousarray(cur["depth"], dtype=F)
+    eye, iv, fov = np.asarray(cam[0], dtype=F), np.asarray(cam[1], dtype=F).reshape(9), cam[2]
+    peye, piv, pfov = np.asarray(pcam[0], dtype=F), np.asarray(pcam[1], dtype=F).reshape(9), pcam[2]
+    scale, pscale = camera_scale(fov), camera_scale(pfov)
+    ar = F(W) / F(H)
+    dt, nt, amin = F(depth_tolerance), F(normal_tolerance), F(alpha_min)
+    fw, fh = F(W), F(H)
+    with np.errstate(all="ignore"):
+        x = np.broadcast_to(np.arange(W, dtype=F)[None, :], (H, W))
+        y = np.broadcast_to(np.arange(H, dtype=F)[:, None], (H, W))
+        sx = (((F(2) * (x + F(0.5))) / fw - F(1)) * scale) * ar
+        sy = (F(1) - (F(2) * (y + F(0.5))) / fh) * scale
+        cdx, cdy, cdz = unit3(-sx, sy, ones)
+        dx, dy, dz = unit3(iv[0] * cdx + (iv[3] * cdy + iv[6] * cdz), iv[1] * cdx + (iv[4] * cdy + iv[7] * cdz),
+                           iv[2] * cdx + (iv[5] * cdy + iv[8] * cdz))
+        px, py, pz = eye[0] + dx * depth, eye[1] + dy * depth, eye[2] + dz * depth
+        vx, vy, vz = px - peye[0], py - peye[1], pz - peye[2]
+        cx = piv[0] * vx + (piv[1] * vy + piv[2] * vz)
+        cy = piv[3] * vx + (piv[4] * vy + piv[5] * vz)
+        cz = piv[6] * vx + (piv[7] * vy + piv[8] * vz)
+        tp = np.sqrt(vx * vx + (vy * vy + vz * vz))
+        fx = (((((-cx) / cz) / (pscale * ar)) + F(1)) * fw) / F(2) - F(0.5)
+        fy = (((F(1) - (cy / cz) / pscale) * fh) / F(2)) - F(0.5)
+        ok = (depth > 0) & (cz > 0) & (fx > F(-1)) & (fx < fw) & (fy > F(-1)) & (fy < fh)
+        x0, y0 = np.floor(fx), np.floor(fy)
+        wx, wy = fx - x0, fy - y0
+        for a in (sx, tp, fx, wx):
+            assert a.dtype == F
+        x0i, y0i = np.where(ok, x0, 0).astype(np.int64), np.where(ok, y0, 0).astype(np.int64)
+        pc, ph, pd = (np.ascontiguousarray(prev[k], dtype=F) for k in ("color", "history", "depth"))
+        pv = np.ascontiguousarray(prev["variance"], dtype=F) if var is not None else None
+        normal = cur.get("normal")
+        ids = cur.get("id")
+        hc, hv = np.zeros((H, W, 3), dtype=F), np.zeros((H, W, 3), dtype=F)
+        hn, ws = np.zeros((H, W), dtype=F), np.zeros((H, W), dtype=F)
+        tol = dt * tp
+        for j in (0, 1):
+            qy = y0i + j
+            for i in (0, 1):
+                qx = x0i + i
+                counts = ok & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
+                qyc, qxc = np.clip(qy, 0, H - 1), np.clip(qx, 0, W - 1)
+                d = pd[qyc, qxc]
+                counts &= (d > 0) & (np.abs(d - tp) <= tol)
+                if normal is not None:
+                    dn = np.ascontiguousarray(normal, dtype=F) - np.ascontiguousarray(prev["normal"], dtype=F)[qyc, qxc]
+                    counts &= (dn[..., 0] * dn[..., 0] + dn[..., 1] * dn[..., 1]) + dn[..., 2] * dn[..., 2] <= nt * nt
+                if ids is not None:
+                    counts &= np.asarray(ids) == np.asarray(prev["id"])[qyc, qxc]
+                b = (wx if i else F(1) - wx) * (wy if j else F(1) - wy)
+                assert b.dtype == F
+                hc = np.where(counts[..., None], hc + pc[qyc, qxc] * b[..., None], hc)
+                if pv is not None:
+                    hv = np.where(counts[..., None], hv + pv[qyc, qxc] * b[..., None], hv)
+                hn = np.where(counts, hn + ph[qyc, qxc] * b, hn)
+                ws = np.where(counts, ws + b, ws)
+        took = ok & (ws > F(0.015625))
+        n = hn / ws + F(1)
+        a = F(1) / n
+        a = np.where(a < amin, amin, a)
+        k = F(1) - a
+        out_c = np.where(took[..., None], (hc / ws[..., None]) * k[..., None] + color * a[..., None], color)
+        out_v = None
+        if var is not None:
+            out_v = np.where(took[..., None], (hv / ws[..., None]) * (k * k)[..., None] + var * (a * a)[..., None], var)
+            assert out_v.dtype == F
+        out_h = np.where(took, n, F(1))
+    assert out_c.dtype == F and out_h.dtype == F
+    return out_c, out_v, out_h, took
+
+
+def check_against_restatement(cur, cam, prev, pcam, where, **kw):
+    """crt.temporal against the restatement, bit for bit; returns (rgb, color, variance, history, info, took)"""
+    rgb, color, var, hist, info = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, return_info=True, **kw)
+    want_c, want_v, want_h, took = restated(cur, cam, prev, pcam, **kw)
+    assert_bits(color, want_c, where + ": colour")
+    assert_bits(hist, want_h, where + ": history")
+    if want_v is None:
+        assert var is None
+    else:
+        assert_bits(var, want_v, where + ": variance")
+    assert np.array_equal(rgb, O.tonemap(color)), where + ": rgb is not the tone map of the colour"
+    assert info["reprojected"] == int(took.sum()), (where, info, int(took.sum()))
+    return rgb, color, var, hist, info, took
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_temporal_entry_points_and_defaults():
+    lib = capi.lib()
+    for name in ("crt_temporal_defaults", "crt_temporal", "crt_temporal_device"):
+        assert name in capi.EXPORTS and getattr(lib, name)
+    p = capi.TemporalParams()
+    C.memset(C.byref(p), 0x7f, C.sizeof(p))
+    assert lib.crt_temporal_defaults(C.byref(p)) == capi.CRT_OK
+    assert (p.width, p.height) == (0, 0)
+    for cam in (p.cur, p.prev):
+        assert list(cam.eye) == [0.0] * 3 and list(cam.inv_view) == [0.0] * 9 and cam.fov_y == 0.0
+    for name, v in DEFAULTS.items():
+        assert F(getattr(p, name)) == F(v), name
+    assert crt.temporal_defaults() == {k: float(F(v)) for k, v in DEFAULTS.items()}
+    assert lib.crt_temporal_defaults(None) == capi.ERR_INVALID_ARG and lib.crt_last_error()
+    assert lib.crt_abi_version() == 5
+    with pytest.raises(NotImplementedError):
+        crt.MultiRender.run_view_temporal(None)
+
+
+def test_temporal_arguments_are_checked_before_any_device_call():
+    """Every invalid call of both forms is CRT_ERR_INVALID_ARG, also on a machine without a GPU: the arguments are checked first.  The
+    non-null buffers here are dummies that must never be dereferenced."""
+    lib = capi.lib()
+    dummy = C.create_string_buffer(256)
+    d = C.cast(dummy, C.c_void_p)
+    w, h = 64, 48
+
+    def params(**over):
+        p = capi.TemporalParams()
+        assert lib.crt_temporal_defaults(C.byref(p)) == capi.CRT_OK
+        p.width, p.height = w, h
+        for k, v in over.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    def frame(**over):
+        f = dict(color=d, variance=d, depth=d, normal=d, id=d)
+        f.update(over)
+        return C.byref(capi.TemporalFrame(**f))
+
+    def history(**over):
+        f = dict(color=d, variance=d, history=d, depth=d, normal=d, id=d)
+        f.update(over)
+        return C.byref(capi.TemporalHistory(**f))
+
+    def both(prm, cur, prev, color=d, var=d, hist=d, rgb=d, status=capi.ERR_INVALID_ARG):
+        r1 = lib.crt_temporal(0, prm, cur, prev, color, var, hist, rgb, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_temporal_device(0, prm, cur, prev, color, var, hist, rgb, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == status, (r1, r2, e1, e2)
+        assert e1 and e2
+        return e1
+
+    assert b"null" in both(None, frame(), history())
+    assert b"null" in both(params(), None, history())
+    for prev in (history(), None):
+        both(params(), frame(color=None), prev)
+        both(params(), frame(depth=None), prev)
+        both(params(), frame(), prev, color=None)
+        both(params(), frame(), prev, hist=None)
+        both(params(width=0), frame(), prev)
+        both(params(height=0), frame(), prev)
+        for name in ("depth_tolerance", "normal_tolerance"):
+            for bad in (0.0, -0.0, -1.0, float("nan"), float("-inf")):
+                assert b"tolerance" in both(params(**{name: bad}), frame(), prev), (name, bad)
+        for bad in (0.0, -0.5, 1.5, float("nan"), float("inf")):
+            assert b"alpha_min" in both(params(alpha_min=bad), frame(), prev), bad
+        assert b"variance" in both(params(), frame(variance=None), prev)            # out_variance without the current variance
+        assert b"variance" in both(params(), frame(), prev, var=None)               # ... and the other way round
+    for missing in ("color", "history", "depth"):
+        assert b"history" in both(params(), frame(), history(**{missing: None})), missing
+    assert b"variance" in both(params(), frame(), history(variance=None))
+    assert b"normals" in both(params(), frame(normal=None), history())
+    assert b"normals" in both(params(), frame(), history(normal=None))
+    assert b"IDs" in both(params(), frame(id=None), history())
+    assert b"IDs" in both(params(), frame(), history(id=None))
+    # sizes the launch cannot cover: the denoiser's answer
+    both(params(width=(1 << 24) + 1), frame(), history(), status=capi.ERR_UNSUPPORTED)
+    both(params(width=1 << 24, height=1 << 24), frame(), history(), status=capi.ERR_UNSUPPORTED)
+    assert lib.crt_temporal(-1, params(), frame(), history(), d, d, d, d, None) == capi.ERR_INVALID_ARG
+    assert lib.crt_temporal_device(-1, params(), frame(), history(), d, d, d, d, None, None) == capi.ERR_INVALID_ARG
+    with pytest.raises(ValueError):
+        crt.temporal({"color": np.zeros((4, 4, 3), F), "depth": np.zeros((4, 5), F)}, (np.zeros(3), np.zeros(9), 1.0))
+
+
+def plane_setup(W, H, eye):
+    """A camera at `eye` looking along +z at the plane z = 100, fov 40 degrees: (camera, float64 depth along the pixel-centre rays,
+    float64 world points of the pixels).  The ray is the contract's, in float64."""
+    eye = np.asarray(eye, dtype=np.float64)
+    iv = crt.get_inverse_view_matrix(eye.astype(F), (eye + [0, 0, 1]).astype(F), [0, 1, 0])
+    fov = crt.fov_to_radians(40.0)
+    scale, ar = np.tan(np.float64(fov) / 2), W / H
+    x, y = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    sx = ((2 * (x + 0.5)) / W - 1) * scale * ar
+    sy = (1 - (2 * (y + 0.5)) / H) * scale
+    cd = np.stack([-sx, sy, np.ones_like(sx)], axis=-1)
+    cd /= np.linalg.norm(cd, axis=-1, keepdims=True)
+    m = iv.astype(np.float64).reshape(3, 3).T          # column-major storage: m[r, c] = iv[c * 3 + r]
+    d = cd @ m.T
+    d /= np.linalg.norm(d, axis=-1, keepdims=True)
+    depth = (100.0 - eye[2]) / d[..., 2]
+    return (eye.astype(F), iv, fov), depth, eye + d * depth[..., None]
+
+
+def plane_colour(P):
+    """linear in world x and y, far from 0"""
+    X, Y = P[..., 0], P[..., 1]
+    return np.stack([300 + X + 0.5 * Y, 400 - 2 * X + Y, 1000 + 3 * X - 2 * Y], axis=-1)
+
+
+@pytest.mark.parametrize("size", [(64, 48), (61, 47)])
+@pytest.mark.parametrize("move", [(10, 0, 0), (7.3, -4.1, 0), (3, 2, 15), (0, 0, -20)])
+def test_restatement_reprojects_a_plane(size, move):
+    """The restated contract against geometry (no device).  A colour that is linear in world x and y on a plane parallel to the image
+    plane is linear in the previous frame's pixel coordinates, so its bilinear interpolation at the reprojected point is the colour of
+    the pixel's own world point.  History length 10^6 with alpha_min 2^-20 and a current colour of 0: output = history x k with k within
+    2^-24 of 1 - 2^-20.  Bound 1e-5 relative; measured at most 2.9e-7 with the prototype of the contract."""
+    W, H = size
+    pcam, pdepth, pP = plane_setup(W, H, (0, 0, 0))
+    cam, depth, P = plane_setup(W, H, move)
+    prev = {"color": plane_colour(pP).astype(F), "history": np.full((H, W), 1e6, dtype=F), "depth": pdepth.astype(F)}
+    cur = {"color": np.zeros((H, W, 3), dtype=F), "depth": depth.astype(F)}
+    out, var, hist, took = restated(cur, cam, prev, pcam, alpha_min=2.0 ** -20)
+    assert var is None
+    # where the point lands in the previous frame, in float64 and from the world point alone
+    scale = np.tan(np.float64(pcam[2]) / 2)
+    c = (P - pcam[0].astype(np.float64)) @ pcam[1].astype(np.float64).reshape(3, 3).T      # (cx: inv_view'[0..2] . v, ...)
+    fx = ((-c[..., 0] / c[..., 2]) / (scale * W / H) + 1) * W / 2 - 0.5
+    fy = (1 - (c[..., 1] / c[..., 2]) / scale) * H / 2 - 0.5
+    eps = 1e-4                                          # (off the frame by more than the fp32 rounding of fx and fy)
+    inside = (fx >= 0) & (fx <= W - 1) & (fy >= 0) & (fy <= H - 1)
+    off = (fx < -1 - eps) | (fx > W + eps) | (fy < -1 - eps) | (fy > H + eps)
+    assert inside.sum() > W * H // 4
+    assert took[inside].all() and (np.abs(hist[inside] - 1e6) < 2).all()       # (the weighted mean of 10^6s, to rounding, + 1)
+    want = plane_colour(P)
+    rel = np.abs(out.astype(np.float64) / (1 - 2.0 ** -20) - want) / np.abs(want)
+    print("%dx%d move %r: %d pixels inside, largest relative error %.3g; %d off the frame" % (W, H, move, inside.sum(), rel[inside].max(), off.sum()))
+    assert rel[inside].max() < 1e-5
+    if move != (3, 2, 15):                              # (moving forward, every pixel stays in the previous frame)
+        assert off.sum() >= H
+    assert not took[off].any()
+    assert np.array_equal(out[off].view(np.uint32), cur["color"][off].view(np.uint32)) and (hist[off] == F(1)).all()
+
+
+def test_cli_refuses_temporal_options_it_cannot_combine():
+    """Exit status 1 and a message that names the option, before any device is touched."""
+    from cudaraytracing_amd import build as b
+    cli, cfg = b.build_cli(), util.SCENES["veach-mis"]
+    for extra in (["--gpus", "2"], ["--devices", "0,0", "--gather", "copy"], ["--adaptive", "0.05"]):
+        bad = subprocess.run([cli, cfg, "--base-dir", util.ROOT, "--temporal", "2"] + extra, capture_output=True, text=True, timeout=60)
+        assert bad.returncode == 1 and "--temporal" in bad.stderr and extra[0][:6] in bad.stderr, (extra, bad.stderr)
+    for args in (["--temporal-out", "x.png"], ["--temporal-step", "1,0,0"], ["--temporal-denoise"], ["--temporal", "2", "--temporal-denoise"],
+                 ["--temporal", "0"], ["--temporal", "2", "--temporal-step", "1,2"]):
+        bad = subprocess.run([cli, cfg, "--base-dir", util.ROOT] + args, capture_output=True, text=True, timeout=60)
+        assert bad.returncode == 1 and "--temporal" in bad.stderr, (args, bad.stderr)
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+# per-frame camera moves: (step, the lookat point moves along)
+MOVES = {"cornell-box": ((20.0, 0.0, 10.0), True), "veach-mis": ((0.0, 0.1, 0.3), False)}
+
+
+def camera_at(name, f, static=False):
+    t = util.task(name)
+    step, with_lookat = MOVES[name]
+    s = F(0 if static else f) * np.asarray(step, dtype=F)
+    eye = t.eye_pos + s
+    lookat = t.lookat + s if with_lookat else t.lookat
+    return eye, crt.get_inverse_view_matrix(eye, lookat, t.up), crt.fov_to_radians(t.fov_y)
+
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in ("cornell-box", "veach-mis"):
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+def render_frame(r, cam, width, height, spp, seed):
+    """A GPU render with the flag and its AOV pass: (the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth})"""
+    r.set_spp(spp)
+    r.seed = seed
+    try:
+        rgb = r.run_view(*cam, width=width, height=height, want_variance=True).copy()
+        mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+        g = r.run_view_aov(*cam, want=("albedo", "normal", "depth", "material"), width=width, height=height)
+    finally:
+        r.seed = 0
+    cur = {"color": mean, "variance": var, "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
+    return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
+
+
+_frames = {}
+
+
+def frames(renders, name, width, height, n, seed0, static=False):
+    """n moving (or static) frames with seeds seed0 .. seed0 + n - 1, rendered once per module: [(cur, rgb, guides, camera)]"""
+    key = (name, width, height, n, seed0, static)
+    if key not in _frames:
+        _frames[key] = []
+        for f in range(n):
+            cam = camera_at(name, f, static)
+            _frames[key].append(render_frame(renders[name], cam, width, height, 4, seed0 + f) + (cam,))
+    return _frames[key]
+
+
+def subset(cur, variant):
+    drop = {"full": (), "no guides": ("normal", "id"), "no variance": ("variance",)}[variant]
+    return {k: v for k, v in cur.items() if k not in drop}
+
+
+def as_history(cur, color, var, hist):
+    prev = dict(cur, color=color, history=hist)
+    if var is not None:
+        prev["variance"] = var
+    return prev
+
+
+def check_branches(cur, took, where):
+    reset = (~took) & (cur["depth"] > 0)
+    print("%s: %d pixels reprojected, %d pixels with a hit reset" % (where, took.sum(), reset.sum()))
+    assert took.sum() >= 100, where
+    assert reset.sum() >= 16, where
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["full", "no guides", "no variance"])
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_temporal_rendered_frames_match_restatement(renders, name, variant):
+    """Three chained frames of a moving camera: the third frame's history is itself an output."""
+    fr = frames(renders, name, 64, 48, 3, 40)
+    prev = pcam = None
+    for f, (cur, _, _, cam) in enumerate(fr):
+        cur = subset(cur, variant)
+        where = "%s 64x48 %s frame %d" % (name, variant, f)
+        _, color, var, hist, _, took = check_against_restatement(cur, cam, prev, pcam, where)
+        if f:
+            check_branches(cur, took, where)
+            assert abs(hist.max() - (f + 1)) < 1e-4
+        else:
+            assert not took.any() and (hist == 1).all()
+        prev, pcam = as_history(cur, color, var, hist), cam
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(61, 47), (100, 70)])
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_temporal_ragged_sizes_match_restatement(renders, name, size):
+    (c0, _, _, cam0), (c1, _, _, cam1) = frames(renders, name, size[0], size[1], 2, 50)
+    prev = as_history(c0, c0["color"], c0["variance"], np.ones(c0["depth"].shape, dtype=F))
+    took = check_against_restatement(c1, cam1, prev, cam0, "%s %dx%d" % (name, size[0], size[1]))[5]
+    assert took.sum() >= 100
+
+
+def synthetic(w, h, seed):
+    """Two frames of random colours, variances and normals on the inside of a sphere around the eye (depth 40, the previous frame's
+    within +-8 %, so that the default tolerance passes some taps and fails others), cameras that differ by a rotation of a few degrees
+    and in fov_y.  Returns (cur, cam, prev, pcam)."""
+    rng = np.random.default_rng(seed)
+
+    def frame():
+        n = np.array([0.0, 0.0, 1.0]) + rng.normal(size=(h, w, 3)) * 0.25
+        return {"color": (rng.random((h, w, 3)) * 100).astype(F), "variance": (rng.random((h, w, 3)) * 300).astype(F),
+                "depth": (F(40.0) * (F(0.92) + rng.random((h, w)).astype(F) * F(0.16))).astype(F),
+                "normal": (n / np.linalg.norm(n, axis=2, keepdims=True)).astype(F), "id": np.full((h, w), 3, dtype=np.int32)}
+
+    cur, prev = frame(), frame()
+    cur["depth"][:] = 40.0
+    prev["history"] = (1 + rng.integers(0, 40, (h, w))).astype(F)
+    cur["depth"][h // 3:h // 3 + 9, w // 4:w // 4 + 13] = 0.0               # a block of "miss" pixels in each frame
+    prev["depth"][h // 2:h // 2 + 7, w // 2:w // 2 + 15] = 0.0
+    prev["id"][4:15, 30:48] = 7                                             # a block of differing IDs
+    cur["id"][28:40, 5:20] = 9
+    eye = np.array([1.0, 2.0, 3.0], dtype=F)
+    up = [0.0, 1.0, 0.0]
+    cam = (eye, crt.get_inverse_view_matrix(eye, eye + np.array([0.0, 0.0, 1.0], dtype=F), up), F(0.7))
+    t = np.radians(8.0)
+    pcam = (eye, crt.get_inverse_view_matrix(eye, eye + np.array([np.sin(t), 0.03, np.cos(t)], dtype=F), up), F(0.8))
+    return cur, cam, prev, pcam
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["full", "no guides", "no variance"])
+def test_temporal_synthetic_inputs(variant):
+    cur, cam, prev, pcam = synthetic(70, 45, 21)
+    cur, prev = subset(cur, variant), subset(prev, variant)
+    _, color, var, hist, _, took = check_against_restatement(cur, cam, prev, pcam, "synthetic " + variant)
+    check_branches(cur, took, "synthetic " + variant)
+    assert not took[cur["depth"] == 0].any()
+    assert not took[:, :2].any() or not took[:, -2:].any()                 # a band of pixels leaves the frame on one side
+    assert np.isfinite(color).all() and (hist[took] > 1).all()
+    # the tolerances switched off: every pixel that lands in the frame on a hit takes the history
+    inf = float("inf")
+    took2 = check_against_restatement(cur, cam, prev, pcam, "synthetic, no tests, " + variant, depth_tolerance=inf, normal_tolerance=inf,
+                                      alpha_min=1.0)[5]
+    assert took2.sum() > took.sum()
+
+
+@pytest.mark.gpu
+def test_temporal_non_finite_pixels():
+    cur, cam, prev, pcam = synthetic(70, 45, 22)
+    cur["color"][7, 9, 1] = np.inf
+    cur["color"][30, 50, 0] = np.nan
+    prev["color"][12, 33, 2] = np.inf
+    prev["color"][25, 20, 0] = np.nan
+    cur["depth"][20, 40] = np.inf
+    cur["depth"][21, 44] = np.nan
+    prev["depth"][10, 20] = np.inf
+    prev["depth"][35, 50] = np.nan
+    prev["variance"][18, 28, 1] = np.inf
+    prev["variance"][31, 41, 0] = np.nan
+    prev["variance"][5, 60, 2] = -5.0
+    inf = float("inf")
+    for kw in ({}, {"depth_tolerance": inf, "normal_tolerance": inf}):      # (with the tests off, every planted tap counts)
+        _, color, var, hist, _, took = check_against_restatement(cur, cam, prev, pcam, "non-finite %r" % (kw,), **kw)
+        assert not took[20, 40] and not took[21, 44]
+        assert np.isnan(color).any() and np.isfinite(color).any() and np.isfinite(hist).all()
+    assert np.isnan(var).any() and np.isinf(color).any()
+
+
+def assert_is_current_frame(out, cur, where):
+    rgb, color, var, hist, info = out
+    assert np.array_equal(color.view(np.uint32), cur["color"].view(np.uint32)), where
+    assert np.array_equal(var.view(np.uint32), cur["variance"].view(np.uint32)), where
+    assert (hist == F(1)).all() and info["reprojected"] == 0, where
+    assert np.array_equal(rgb, O.tonemap(cur["color"])), where
+
+
+@pytest.mark.gpu
+def test_temporal_without_a_usable_history_returns_the_current_frame():
+    """Independent of the restatement: a previous camera that looks the opposite way (every point of the frame is behind it) and no
+    history at all both give the current frame's bits, history 1, nothing reprojected."""
+    cur, cam, prev, _ = synthetic(70, 45, 23)
+    eye = cam[0]
+    back = (eye, crt.get_inverse_view_matrix(eye, eye + np.array([0.0, 0.0, -1.0], dtype=F), [0.0, 1.0, 0.0]), cam[2])
+    inf = float("inf")
+    out = crt.temporal(cur, cam, prev=prev, prev_camera=back, depth_tolerance=inf, normal_tolerance=inf, return_info=True)
+    assert_is_current_frame(out, cur, "camera turned round")
+    assert_is_current_frame(crt.temporal(cur, cam, return_info=True), cur, "no history")
+
+
+@pytest.mark.gpu
+def test_temporal_rejects_the_history_where_the_depth_disagrees():
+    """Independent of the restatement: identical cameras and guides, so a pixel reprojects onto itself (to rounding: the other taps lie
+    in its 3x3 neighbourhood and weigh next to nothing).  With the previous depth x 1.5 inside a rectangle, a pixel whose 3x3
+    neighbourhood lies in the rectangle has no tap within 5 % and is reset; a pixel two or more away from it keeps its history."""
+    w, h = 70, 45
+    rng = np.random.default_rng(5)
+    yy, xx = np.mgrid[0:h, 0:w]
+    depth = (30 + 3 * np.sin(xx / 9.0) + 2 * np.cos(yy / 7.0)).astype(F)      # smooth: neighbours within 2 %
+    normal = np.zeros((h, w, 3), dtype=F)
+    normal[..., 2] = 1.0
+    cur = {"color": (rng.random((h, w, 3)) * 100).astype(F), "variance": (rng.random((h, w, 3)) * 300).astype(F), "depth": depth,
+           "normal": normal, "id": np.zeros((h, w), dtype=np.int32)}
+    prev = dict(cur, color=(rng.random((h, w, 3)) * 100).astype(F), history=np.full((h, w), 5, dtype=F), depth=depth.copy())
+    x0, x1, y0, y1 = 20, 41, 10, 29
+    prev["depth"][y0:y1, x0:x1] *= F(1.5)
+    eye = np.array([1.0, 2.0, 3.0], dtype=F)
+    cam = (eye, crt.get_inverse_view_matrix(eye, eye + np.array([0.3, 0.1, 1.0], dtype=F), [0.0, 1.0, 0.0]), F(0.7))
+    _, color, var, hist, info = crt.temporal(cur, cam, prev=prev, prev_camera=cam, return_info=True)
+    core = np.zeros((h, w), dtype=bool)
+    core[y0 + 1:y1 - 1, x0 + 1:x1 - 1] = True
+    far = np.ones((h, w), dtype=bool)
+    far[y0 - 2:y1 + 2, x0 - 2:x1 + 2] = False
+    far[0, :] = far[-1, :] = far[:, 0] = far[:, -1] = False
+    assert (hist[core] == F(1)).all()
+    assert np.array_equal(color[core].view(np.uint32), cur["color"][core].view(np.uint32))
+    assert (np.abs(hist[far] - F(6)) < 1e-5).all()        # (the weighted mean of fives, to rounding)
+    assert not np.array_equal(color[far], cur["color"][far])
+    assert core.sum() <= w * h - info["reprojected"] <= (~far).sum()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("static", [True, False], ids=["static", "moving"])
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_temporal_accumulation_reduces_the_error_against_a_converged_frame(renders, name, static):
+    """64 x 48, spp 4, 8 frames with seeds 100 .. 107, defaults; R = spp 256, seed 7 at the last camera; mse on the RGB8 tone maps.
+    The numpy prototype of the contract (threshold 1/100 instead of 1/64) measured, last frame alone / accumulated: cornell-box static
+    1479.5 / 531.5, moving (20, 0, 10) per frame 1648.6 / 694.7; veach-mis static 670.3 / 235.1, moving (0, 0.1, 0.3) 719.8 / 361.0.
+    The restatement above on the CPU oracle's frames (the device's frames, bit for bit): 1479.5 / 561.9, 1648.6 / 536.3, 670.3 / 264.6,
+    722.6 / 367.9."""
+    fr = frames(renders, name, 64, 48, 8, 100, static)
+    prev = pcam = None
+    for cur, noisy_rgb, _, cam in fr:
+        rgb, color, var, hist = crt.temporal(cur, cam, prev=prev, prev_camera=pcam)
+        prev, pcam = as_history(cur, color, var, hist), cam
+    r = renders[name]
+    r.set_spp(256)
+    r.seed = 7
+    try:
+        ref_rgb = r.run_view(*pcam, width=64, height=48).copy()
+    finally:
+        r.seed = 0
+
+    def mse(x):
+        d = x.astype(np.float64) - ref_rgb.astype(np.float64)
+        return float(np.mean(d * d))
+
+    print("%s %s: mse of the last frame alone %.1f, accumulated %.1f (longest history %d)" % (name, "static" if static else "moving", mse(noisy_rgb),
+                                                                                            mse(rgb), hist.max()))
+    assert mse(rgb) < mse(noisy_rgb)
+
+
+def hip_runtime():
+    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
+    capi.lib()
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    H = C.CDLL(path)
+    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    H.hipFree.argtypes = [C.c_void_p]
+    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    H.hipStreamSynchronize.argtypes = [C.c_void_p]
+    H.hipStreamDestroy.argtypes = [C.c_void_p]
+    return H
+
+
+@pytest.mark.gpu
+def test_temporal_device_form_on_a_stream_matches_host_form(renders):
+    name, w, h = "veach-mis", 100, 70
+    (c0, _, _, cam0), (c1, _, _, cam1) = frames(renders, name, w, h, 2, 50)
+    prev = as_history(c0, c0["color"], c0["variance"], np.full((h, w), 3, dtype=F))
+    want_rgb, want_c, want_v, want_h, want_info = crt.temporal(c1, cam1, prev=prev, prev_camera=cam0, return_info=True)
+    assert 100 <= want_info["reprojected"] < w * h
+    H = hip_runtime()
+    ptrs = {}
+    stream = C.c_void_p()
+    host = {"cur_" + k: v for k, v in c1.items()}
+    host.update({"prev_" + k: v for k, v in prev.items()})
+    sizes = {n: a.nbytes for n, a in host.items()}
+    sizes.update({"out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4, "out_rgb": w * h * 3})
+    try:
+        for n, size in sizes.items():
+            p = C.c_void_p()
+            assert H.hipMalloc(C.byref(p), size) == 0
+            ptrs[n] = p.value
+            assert H.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the kernel)
+        for n, a in host.items():
+            assert H.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
+        assert H.hipStreamCreate(C.byref(stream)) == 0
+
+        def run(want_info, variance=True, out_rgb=True):
+            cur_p = {k: ptrs["cur_" + k] for k in c1 if variance or k != "variance"}
+            prev_p = {k: ptrs["prev_" + k] for k in prev if variance or k != "variance"}
+            return crt.temporal_device(w, h, cam1, cur_p, ptrs["out_color"], ptrs["out_hist"], out_variance_ptr=ptrs["out_var"] if variance else None,
+                                       out_rgb_ptr=ptrs["out_rgb"] if out_rgb else None, prev_ptrs=prev_p, prev_camera=cam0, stream=stream.value,
+                                       want_info=want_info)
+
+        def fetch():
+            c, v = np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=F)
+            hh, r = np.zeros((h, w), dtype=F), np.zeros((h, w, 3), dtype=np.uint8)
+            for a, n in ((c, "out_color"), (v, "out_var"), (hh, "out_hist"), (r, "out_rgb")):
+                assert H.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+            return c, v, hh, r
+
+        assert run(False) is None
+        assert H.hipStreamSynchronize(stream) == 0
+        c, v, hh, r = fetch()
+        assert_bits(c, want_c, "device form")
+        assert_bits(v, want_v, "device form, variance")
+        assert_bits(hh, want_h, "device form, history")
+        assert np.array_equal(r, want_rgb)
+        # colour and history only, with the timer and the count (the call synchronizes the stream)
+        for n in ("out_color", "out_var", "out_hist", "out_rgb"):
+            assert H.hipMemset(C.c_void_p(ptrs[n]), 0x55, sizes[n]) == 0
+        info = run(True, variance=False, out_rgb=False)
+        assert info["reprojected"] == want_info["reprojected"] and info["total_ms"] > 0, info
+        c, v, hh, r = fetch()
+        assert_bits(c, want_c, "device form, colour only")
+        assert_bits(hh, want_h, "device form, colour only: history")
+        assert (r == 0x55).all() and (v.view(np.uint32) == 0x55555555).all()
+    finally:
+        if stream.value:
+            H.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+@pytest.mark.gpu
+def test_run_view_temporal_equals_the_calls_by_hand(renders):
+    name, w, h = "cornell-box", 64, 48
+    r = renders[name]
+    fr = frames(renders, name, w, h, 3, 40)                  # seeds 40, 41, 42: self.seed + the frames since the reset
+    r.set_spp(4)
+    r.seed = 40
+    try:
+        r.reset_temporal()
+        prev = pcam = None
+        for f, (cur, noisy_rgb, g, cam) in enumerate(fr):
+            want_rgb, want_c, want_v, want_h, want_info = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, return_info=True)
+            prev, pcam = as_history(cur, want_c, want_v, want_h), cam
+            rgb, mean = r.run_view_temporal(*cam, width=w, height=h, denoise=(f == 2))
+            if f == 2:
+                want_rgb, want_mean = crt.denoise_var(want_c, want_v, **g)
+                assert r.denoise_info["passes"] == 3
+            else:
+                want_mean = want_c
+            assert_bits(mean, want_mean, "run_view_temporal frame %d" % f)
+            assert np.array_equal(rgb, want_rgb)
+            assert_bits(r.variance_buffer, want_v, "variance_buffer")
+            assert_bits(r.temporal_history_buffer, want_h, "temporal_history_buffer")
+            assert r.temporal_info["reprojected"] == want_info["reprojected"] and r.seed == 40
+            assert np.array_equal(r.frame_buffer, noisy_rgb) and np.array_equal(r.mean_buffer.view(np.uint32), cur["color"].view(np.uint32))
+        assert r.temporal_info["reprojected"] >= 100
+        # the filtered frame did not become the history: a fourth call with an explicit seed continues the unfiltered one
+        cur3, _, _, cam3 = fr[1]
+        want = crt.temporal(cur3, cam3, prev=prev, prev_camera=pcam)
+        rgb, mean = r.run_view_temporal(*cam3, seed=41, width=w, height=h)
+        assert_bits(mean, want[1], "fourth frame")
+        # a change of size drops the history, and so does reset_temporal(): first frames, rendered with self.seed again
+        r.run_view_temporal(*fr[0][3], width=w - 3, height=h)
+        assert (r.temporal_history_buffer == 1).all() and r.temporal_info["reprojected"] == 0
+        r.reset_temporal()
+        rgb, mean = r.run_view_temporal(*fr[0][3], width=w, height=h)
+        assert (r.temporal_history_buffer == 1).all() and r.temporal_info["reprojected"] == 0
+        assert_bits(mean, fr[0][0]["color"], "first frame after the reset")
+        assert np.array_equal(rgb, fr[0][1])
+        # a following run_view gives the frame it gave before
+        assert np.array_equal(r.run_view(*fr[0][3], width=w, height=h), fr[0][1])
+        assert np.array_equal(r.mean_buffer.view(np.uint32), fr[0][0]["color"].view(np.uint32)) and r.variance_buffer is None
+    finally:
+        r.seed = 0
+        r.reset_temporal()
+
+
+@pytest.mark.gpu
+def test_cli_accumulates_a_moving_sequence(renders, tmp_path):
+    from PIL import Image
+    from cudaraytracing_amd import build as b
+    cli = b.build_cli()
+    name, w, h = "cornell-box", 64, 48
+    cfg = util.SCENES[name]
+    base = [cli, cfg, "--spp", "4", "--width", str(w), "--height", str(h), "--seed", "40", "--base-dir", util.ROOT]
+    step = ["--temporal", "3", "--temporal-step", ",".join(repr(float(v)) for v in MOVES[name][0])]
+    last, acc, den = (str(tmp_path / n) for n in ("last.png", "acc.png", "den.png"))
+    res = subprocess.run(base + step + ["-o", last, "--temporal-out", acc], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    res2 = subprocess.run(base + step + ["-o", last, "--temporal-out", den, "--temporal-denoise"], capture_output=True, text=True, timeout=120)
+    assert res2.returncode == 0, res2.stderr
+    prev = pcam = None
+    for cur, noisy_rgb, g, cam in frames(renders, name, w, h, 3, 40):
+        rgb, color, var, hist = crt.temporal(cur, cam, prev=prev, prev_camera=pcam)
+        prev, pcam = as_history(cur, color, var, hist), cam
+    assert np.array_equal(np.asarray(Image.open(last)), noisy_rgb)
+    assert np.array_equal(np.asarray(Image.open(acc)), rgb)
+    assert np.array_equal(np.asarray(Image.open(den)), crt.denoise_var(color, var, **g)[0])

@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""Cost and effect of temporal accumulation (crt_temporal, include/crt.h).
+
+Cost: for each size, the HIP-event time of crt_temporal_device (crt_temporal_info.total_ms: its one kernel on the stream) over --calls
+calls after --warmup warm-up calls, on two cornell-box frames of --spp samples one camera step apart, rendered here with their variance
+and AOVs; all buffers given (variance, normals, IDs, RGB8 out).  In the same process, the calls taking turns, the a-trous denoiser's
+time per pass (crt_denoise_device, 3 iterations, as tools/denoise_probe.py measures it).  Prints the median and best ms per call, the
+fraction of pixels that took the history and the rate of the compulsory bytes -- 44 B read per current pixel, 48 B per history pixel,
+31 B written -- over the median time.
+
+Effect: at --error-size, spp 8, 8 frames with seeds 100 .. 107, per scene with a static and a moving camera and for each alpha_min of
+--alpha-min: the mean squared error of the RGB8 tone map against an spp 256, seed 7 frame of the last camera for the last frame alone,
+its variance-guided denoise (crt_denoise_var), the accumulated frame, and the variance-guided denoise of the accumulated frame with
+its accumulated variance.
+
+One JSON line per figure on stderr, one JSON document on stdout.
+
+  python tools/temporal_probe.py [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--spp 4] [--error-size 160x120] [--alpha-min 0.05,0.1,0.2]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import cudaraytracing_amd as crt  # noqa: E402
+from cudaraytracing_amd import _capi as capi  # noqa: E402
+
+F = np.float32
+COMPULSORY_BYTES = 44 + 48 + 31
+# per-frame camera moves: (step, the lookat point moves along)
+MOVES = {"cornell-box": ((20.0, 0.0, 10.0), True), "veach-mis": ((0.0, 0.1, 0.3), False)}
+
+
+def hip_runtime():
+    capi.lib()
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    H = C.CDLL(path)
+    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    H.hipFree.argtypes = [C.c_void_p]
+    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return H
+
+
+def camera_at(t, scene, f):
+    step, with_lookat = MOVES[scene]
+    s = F(f) * np.asarray(step, dtype=F)
+    eye = t.eye_pos + s
+    return eye, crt.get_inverse_view_matrix(eye, t.lookat + s if with_lookat else t.lookat, t.up), crt.fov_to_radians(t.fov_y)
+
+
+def render_frame(r, cam, spp, seed):
+    """(the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth})"""
+    r.set_spp(spp)
+    r.seed = seed
+    rgb = r.run_view(*cam, want_variance=True).copy()
+    g = r.run_view_aov(*cam, want=("albedo", "normal", "depth", "material"))
+    cur = {"color": r.mean_buffer.copy(), "variance": r.variance_buffer.copy(), "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
+    return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
+
+
+def cost(a, H, out):
+    scene = "cornell-box"
+    t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+        cams = [camera_at(t, scene, f) for f in (0, 1)]
+        (c0, _, _), (c1, _, g1) = (render_frame(r, cams[f], a.spp, f) for f in (0, 1))
+        r.free()
+        prev = dict(c0, history=np.ones((h, w), dtype=F))
+        host = {"cur_" + k: v for k, v in c1.items()}
+        host.update({"prev_" + k: v for k, v in prev.items()})
+        host["albedo"] = g1["albedo"]
+        scratch_bytes = crt.denoise_scratch_bytes(w, h)
+        ptrs = {}
+        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_color", w * h * 12), ("out_var", w * h * 12), ("out_hist", w * h * 4),
+                                                                                    ("out_rgb", w * h * 3), ("scratch", scratch_bytes)]:
+            p = C.c_void_p()
+            if H.hipMalloc(C.byref(p), nbytes) != 0:
+                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
+            ptrs[name] = p.value
+        for name, v in host.items():
+            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise RuntimeError("hipMemcpy failed")
+
+        def call_temporal():
+            return crt.temporal_device(w, h, cams[1], {k: ptrs["cur_" + k] for k in c1}, ptrs["out_color"], ptrs["out_hist"],
+                                       out_variance_ptr=ptrs["out_var"], out_rgb_ptr=ptrs["out_rgb"], prev_ptrs={k: ptrs["prev_" + k] for k in prev},
+                                       prev_camera=cams[0])
+
+        def call_denoise():
+            return crt.denoise_device(w, h, ptrs["cur_color"], ptrs["out_color"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes,
+                                      albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["cur_normal"], depth_ptr=ptrs["cur_depth"], iterations=3)["total_ms"]
+
+        ms, ms_dn, info = [], [], None
+        for _ in range(a.warmup + a.calls):
+            info = call_temporal()
+            ms.append(info["total_ms"])
+            ms_dn.append(call_denoise())
+        ms, ms_dn = ms[a.warmup:], ms_dn[a.warmup:]
+        med = statistics.median(ms)
+        run = {"width": w, "height": h, "temporal_ms_median": round(med, 4), "temporal_ms_best": round(min(ms), 4),
+               "temporal_ms_worst": round(max(ms), 4), "reprojected_fraction": round(info["reprojected"] / (w * h), 4),
+               "compulsory_TB_per_s": round(COMPULSORY_BYTES * w * h / (med * 1e-3) / 1e12, 4),
+               "denoise_ms_per_pass_median": round(statistics.median(ms_dn) / 3, 4),
+               "temporal_over_denoise_pass": round(med / (statistics.median(ms_dn) / 3), 4)}
+        out["cost"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+def mse(x, ref):
+    d = x.astype(np.float64) - ref.astype(np.float64)
+    return float(np.mean(d * d))
+
+
+def effect(a, out):
+    w, h = (int(v) for v in a.error_size.split("x"))
+    for scene in ("cornell-box", "veach-mis"):
+        t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 8, t.P_RR, t.light_sample_n)
+        for moving in (False, True):
+            frames = []
+            for f in range(8):
+                cam = camera_at(t, scene, f if moving else 0)
+                frames.append(render_frame(r, cam, 8, 100 + f) + (cam,))
+            r.set_spp(256)
+            r.seed = 7
+            ref = r.run_view(*frames[-1][3]).copy()
+            cur, noisy_rgb, g, _ = frames[-1]
+            base = {"scene": scene, "camera": "moving" if moving else "static", "width": w, "height": h,
+                    "mse_last_frame": round(mse(noisy_rgb, ref), 1),
+                    "mse_last_frame_denoise_var": round(mse(crt.denoise_var(cur["color"], cur["variance"], **g)[0], ref), 1)}
+            for alpha_min in [float(v) for v in a.alpha_min.split(",")]:
+                prev = pcam = None
+                for cur, _, g, cam in frames:
+                    rgb, color, var, hist, info = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, alpha_min=alpha_min, return_info=True)
+                    prev, pcam = dict(cur, color=color, variance=var, history=hist), cam
+                run = dict(base, alpha_min=alpha_min, mse_accumulated=round(mse(rgb, ref), 1),
+                           mse_accumulated_denoise_var=round(mse(crt.denoise_var(color, var, **g)[0], ref), 1),
+                           reprojected_fraction_last=round(info["reprojected"] / (w * h), 4), mean_history=round(float(hist.mean()), 2))
+                out["effect"].append(run)
+                print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="800x600,3840x2160")
+    ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--spp", type=int, default=4)
+    ap.add_argument("--error-size", default="160x120")
+    ap.add_argument("--alpha-min", default="0.05,0.1,0.2")
+    ap.add_argument("--skip-cost", action="store_true")
+    ap.add_argument("--skip-effect", action="store_true")
+    a = ap.parse_args()
+    if crt.device_count() < 1:
+        raise SystemExit("temporal_probe: no HIP device")
+    out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": []}
+    if not a.skip_cost:
+        cost(a, hip_runtime(), out)
+    if not a.skip_effect:
+        effect(a, out)
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
