@@ -7,8 +7,8 @@
 namespace crtk {
 
 // ----------------------------------------------------------- megakernels ----
-// Fused forms of the two kernels above: one persistent launch per chunk, path logic and traversal in the same
-// waves, rays and results never leave the chip (no rounds, no relaunches, no per-round drain); the path state planes
+// Fused forms of the wavefront pipeline's logic and trace kernels (crt_wavefront.hip): one persistent launch per chunk, path logic and
+// traversal in the same waves, rays and results never leave the chip (no rounds, no relaunches, no per-round drain); the path state planes
 // (80 B per path + 32 B vertex records) stay L2 / MALL resident because there are only as many paths as resident
 // rays.  (The first such kernel kept one ray per lane in registers: 42 % lane utilisation, removed.)
 struct MParams {
@@ -122,9 +122,25 @@ static_assert(sizeof(Pool3Lds) * 4 * CRT_WAVES <= 160 * 1024, "the pool does not
 // leaves the inner ring once instead of once per leaf, and the stack holds inner nodes only -- six 16-bit levels cover scenes of
 // 32 768 four-wide nodes whatever the number of leaves (24-bit leaf refs travel in the queue entries).
 #ifndef LEAFQ_CAP
-#define LEAFQ_CAP 256 /* entries of the leaf queue, a power of two; the inner step counts a visit's entries before it writes any (crt_mega3.hip: inner4_step_dec) */
+#define LEAFQ_CAP 256 /* entries of the leaf queue, a power of two; the inner step counts a visit's entries before it writes any (crt_mega3_decoupled.h: visit_front) */
 #endif
 static_assert((LEAFQ_CAP & (LEAFQ_CAP - 1)) == 0 && LEAFQ_CAP >= 128, "leaf queue: a power of two, room for half a batch of inner steps");
+// ---- when the decoupled steps run (tuning constants; the kernel's scheduler and alternating loop, crt_mega3.hip) ----
+// LEAFQ_FIRST: with this many entries the leaf queue goes before everything else: the queue is emptied early and stays far from full
+// (when inner batches were still cut to a quarter of its free entries: C2 93.9 -> 92.1 ms, veach-mis spp 256 90.6 -> 89.4;
+// 40 / 56 / 32: 91.9 / 92.9 / 92.0 and 89.6 / 89.5 / 90.8; with full batches 32 / 40 / 56 against 48: within 0.5 %)
+constexpr int LEAFQ_FIRST = 48;
+// (an inner step starts with fewer than LEAFQ_FIRST entries in the queue -- from that many on the leaf step goes first, in the scheduler
+// and in the alternating loop -- and must find room for a reference-arithmetic batch, 64 entries appended outside the counted
+// ones, plus four entries, the least a 4-wide visit needs to keep one lane: otherwise it would take every lane back, for ever)
+static_assert(LEAFQ_FIRST >= 1 && LEAFQ_FIRST + 64 + 4 <= LEAFQ_CAP, "leaf queue: LEAFQ_FIRST - 1 entries + a reference-arithmetic batch + one lane's four entries must fit LEAFQ_CAP");
+// VISIT2_MIN: the decoupled inner step visits a SECOND node while at least this many lanes of its batch go on.  C2 82.7 -> 81.7 ms,
+// veach-mis spp 256 81.8 -> 80.3 (40 .. 52: the same; 16 / 32: 82.6 / 82.1 and 80.8 / 80.6; as a loop, or three / four visits: worse).
+constexpr int VISIT2_MIN = 44;
+// CHAIN_MIN: the two traversal steps alternate without going back to the scheduler while the other side holds at least this many rays.
+// Coupled form: C2 92.6 -> 91.1 ms, veach-mis spp 256 88.0 -> 84.8 with CHAIN_MIN 44 (56 / 48 / 40 / 32 / 20: 93.0 / 91.3 / 91.2 / 91.7 /
+// 93.2 and 85.9 / 84.9 / 84.9 / 86.2 / 90.2); decoupled form: 92.2 -> 87.7 and 89.5 -> 84.8 (32 / 52: the same).
+constexpr int CHAIN_MIN = 44;
 #define RD_PEND_SHIFT 8
 #define RD_PEND_MASK 0x3ff00u  /* word D, bits 8-17: leaf-queue entries of the ray that have not been tested yet */
 #define RD_FIN 0x8000000u      /* word D: the traversal of the inner nodes is over */
@@ -164,11 +180,18 @@ static_assert(offsetof(MParams3, dbg_loads) == 748 && offsetof(MParams3, dbg_val
 
 // ---- exported by crt_mega3.hip ----
 typedef void (*Mega3Kernel)(const MParams3);
-// The instantiation of k_mega3 for a traversal mode (0 FAST, 1 REFERENCE, 2 EXACT), with or without counters, every sample traced
-// or not, render or query form, 32- or 16-bit stack entries (never for REFERENCE), commit ring, decoupled leaves (EXACT only)
-Mega3Kernel mega3_kernel(int mode, bool stats, bool all, bool query, bool r16, bool ring = false, bool dec = false, bool impl = false); // impl: the tree without its rows of refs (dec && r16 only)
-uint32_t mega3_pool_p(bool dec, bool ring);   // rays per wave of that kernel's pool
-int mega3_lds_levels(bool dec, bool r16);     // traversal-stack levels it keeps in LDS
+// An instantiation of k_mega3 as the host needs it: the kernel, the rays per wave of its pool, the traversal-stack levels the pool keeps
+// in LDS (crt_mega3.hip makes one per instantiation from the template arguments themselves)
+struct Mega3Variant {
+    uint32_t key;
+    Mega3Kernel kern;
+    uint32_t pool_p;
+    int lds_levels;
+};
+// The instantiation for a traversal mode (0 FAST, 1 REFERENCE, 2 EXACT), with or without counters, every sample traced or not, render
+// or query form, 32- or 16-bit stack entries (never for REFERENCE), commit ring, decoupled leaves (EXACT only), the tree without its rows
+// of refs (impl: dec && r16 only).  nullptr: there is none.
+const Mega3Variant* mega3_variant(int mode, bool stats, bool all, bool query, bool r16, bool ring = false, bool dec = false, bool impl = false);
 bool bbprof_launch(Mega3Kernel kern, MParams3 M3, uint32_t blocks, hipStream_t st); // tools/bbprof hook (false: launch as usual)
 void launch_order_items(bool ring, uint32_t blocks, hipStream_t st, const LParams& P, uint32_t* list, unsigned int* cnt);
 

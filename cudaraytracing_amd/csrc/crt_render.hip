@@ -130,14 +130,16 @@ MegaPlan plan_mega3(const crt_scene* sc, uint32_t traversal, bool want_stats, bo
     const int mode3 = traversal == CRT_TRAVERSAL_REFERENCE ? 1 : traversal == CRT_TRAVERSAL_EXACT ? 2 : 0;
     const bool dec = use_dec(sc, mode3);
     m.r16 = use_ref16(sc, mode3, dec);
-    m.kern = mega3_kernel(mode3, want_stats, mode3 != 1 && trace_all, query, m.r16, ring, dec, use_impl(sc, dec, m.r16));
+    const Mega3Variant* v = mega3_variant(mode3, want_stats, mode3 != 1 && trace_all, query, m.r16, ring, dec, use_impl(sc, dec, m.r16));
+    if (!v) throw HipFail{hipErrorInvalidValue, "plan_mega3: no instantiation of k_mega3 for this request"};
+    m.kern = v->kern;
     int per_cu = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, m.kern, 64, 0) != hipSuccess || per_cu < 1) per_cu = 1;
     per_cu = (int)std::min<uint32_t>((uint32_t)per_cu, per_cu_cap);
-    const uint32_t pool_p = mega3_pool_p(dec, ring);
+    const uint32_t pool_p = v->pool_p; // (the pool and the LDS levels of the kernel that is launched, from its own descriptor)
     m.blocks = std::min<uint32_t>((uint32_t)std::min<uint64_t>((items + pool_p - 1) / pool_p, 0x7fffffffull), (uint32_t)(sc->n_cus * per_cu));
     m.lanes = m.blocks * pool_p;
-    m.lds_levels = mega3_lds_levels(dec, m.r16);
+    m.lds_levels = v->lds_levels;
     // (16-bit layout: a ray on the reference-arithmetic path keeps its whole stack in the global area)
     m.spill_entries = (size_t)(m.r16 ? std::max(1, sc->stack_cap) : std::max(1, sc->stack_cap - m.lds_levels)) * m.lanes;
     return m;

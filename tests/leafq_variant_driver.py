@@ -1,6 +1,6 @@
 """Run in a child process by test_leafq_overflow.py with CRT_LIB_PATH = a libcrt.so built with -DLEAFQ_CAP=128: renders crops of both
 shipped scenes through the default (decoupled-leaves) kernel and its counting form and compares them with the oracle bit for bit; prints
-one JSON line with what differed and how often the queue-overflow paths of the inner step ran (crt_mega3.hip: inner4_step_dec CHECK 1 /
+one JSON line with what differed and how often the queue-overflow paths of the inner step ran (crt_mega3_decoupled.h: visit_front CHECK 1 /
 2: lanes taken back out of a first visit, second visits dropped)."""
 import json
 import os

@@ -469,7 +469,10 @@ def test_all_stack_layouts(name, monkeypatch):
     where node AND leaf refs fit 16 bits (both benchmark scenes), four 32-bit levels otherwise.  Decoupled leaves (CRT_TRAVERSAL_EXACT):
     the stack holds inner nodes only -- six 16-bit levels while the four-wide nodes number at most 32 768, else three of 32 bits --
     and the leaf tests are entries of a queue.  In a 16-bit layout a ray on the reference-arithmetic path keeps its whole stack in the
-    global spill area (CRT_FLAG_FORCE_EXACT puts every ray there).  Same frames, same ray counts, same closest hits in every form."""
+    global spill area (CRT_FLAG_FORCE_EXACT puts every ray there).  Same frames, same ray counts, same closest hits in every form --
+    and in every instantiation of each: with counters (CRT_FLAG_STATS), with every sample traced (CRT_FLAG_TRACE_ALL), with both, with
+    the commit ring (forced to two samples) and with the ring and every sample traced; with the query loop below that is every row
+    of the kernel's table of instantiations (crt_mega3.hip: mega3_legal)."""
     t = util.task(name)
     eye, iv, fov = util.camera(name)
     osc = util.oracle_scene(name)
@@ -489,6 +492,21 @@ def test_all_stack_layouts(name, monkeypatch):
                 rgb = r.run_view(eye, iv, fov, width=96, height=72)
                 assert np.array_equal(rgb, orgb) and np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), (layout, mode, flags)
                 assert r.stats["rays"] == st["rays"]
+            # the other instantiations of each layout: counters, every sample traced (the frame is the oracle's all the same: a sample that
+            # is answered without its ray adds +0), the commit ring -- forced to two samples -- and their combinations
+            ST, ALL = crt.FLAG_STATS, crt.FLAG_TRACE_ALL
+            for mode, flags, ring in ([(m, f, g) for m in (crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT) for f, g in ((ST, False), (ALL, False), (ST | ALL, False), (0, True), (ALL, True))]
+                                      + [(crt.TRAVERSAL_REFERENCE, ST, False), (crt.TRAVERSAL_REFERENCE, 0, True)]):
+                if ring:
+                    monkeypatch.setenv("CRT_COMMIT_RING_LOG2", "1")
+                else:
+                    monkeypatch.delenv("CRT_COMMIT_RING_LOG2", raising=False)
+                r.traversal, r.extra_flags = mode, flags
+                rgb = r.run_view(eye, iv, fov, width=96, height=72)
+                assert np.array_equal(rgb, orgb) and np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), (layout, mode, flags, ring)
+                assert r.stats["rays"] == st["rays"], (layout, mode, flags, ring)
+                assert r.radiance_storage()[1] == (2 if ring else 0), (layout, mode, flags, ring)
+            monkeypatch.delenv("CRT_COMMIT_RING_LOG2", raising=False)
             r.extra_flags = 0
             for mode in (crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT, crt.TRAVERSAL_FAST | crt.INTERSECT_FORCE_EXACT,
                          crt.TRAVERSAL_EXACT | crt.INTERSECT_FORCE_EXACT, crt.TRAVERSAL_REFERENCE):

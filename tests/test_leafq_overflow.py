@@ -1,6 +1,6 @@
 """The leaf queue of the decoupled-leaves kernel when it runs full: an inner step counts a visit's queue entries before it
 writes any; if they do not fit, the lanes beyond a quarter of the free entries are taken out of a first visit again (queued as they came)
-and a second visit is dropped whole (crt_mega3.hip: inner4_step_dec, CHECK 1 / 2).  With the production queue of 256 entries that is
+and a second visit is dropped whole (crt_mega3_decoupled.h: visit_front, CHECK 1 / 2).  With the production queue of 256 entries that is
 rare; a library built with -DLEAFQ_CAP=128 (tools/ab_build.sh) makes both paths run in most batches.  The frames of both scenes, with and
 without CRT_FLAG_FORCE_EXACT (every ray on the reference-arithmetic arm, whose appends lie outside the counted ones) and with every
 sample traced, must stay the oracle's bit for bit, and the counting kernel must report that the paths ran."""

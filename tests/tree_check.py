@@ -3,7 +3,7 @@
 The exactness proof of EXACT / FAST (csrc/crt_accel.h) rests on facts about the arrays the kernel walks, not on frames:
 every reference leaf is reached exactly once, a leaf's own box is the reference's bit for bit, an inner box contains every box below
 it, no plane is NaN.  This module restates every layout from the comments that define it (csrc/crt_device.h, csrc/crt_scene_layout.h:
-build_scene_layout) and the kernel's nodes4i decode (csrc/crt_mega3.hip: inner4_step_dec) without calling product code; the single
+build_scene_layout) and the kernel's nodes4i decode (csrc/crt_mega3_decoupled.h: visit_front) without calling product code; the single
 source of truth is the reference BVH of the host layer (Scene.nodes(), Scene.triangles()).
 
 check_trees() returns a list of violations, each a string that starts with the invariant it breaks ("I1: ...").  I1 every leaf

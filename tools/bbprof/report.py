@@ -27,7 +27,7 @@ def phase_ranges():
     k0 = next(i for i, l in enumerate(lines) if "void k_mega3(const MParams3 M3)" in l) + 1
     marks = [("sched", r"^\s*for \(;;\) \{\s*$"), ("inner", r"auto inner_arm = "), ("leaf", r"auto leaf_arm = "), ("inner", r"auto inner_arm_dec = "), ("leaf", r"auto leaf_arm_dec = "),
              ("sched2", r"^\s*const bool plain = MODE == 1 \|\| n_exact == 0;"),
-             ("LA", r"if \(act == PH3_LA\) \{"), ("LB", r"else if \(act == PH3_LB\) \{"), ("LC", r"if \(act != PH3_LA && act != PH3_LB\) \{"), ("end", r"^#undef PUSH3")]
+             ("LA", r"if \(act == PH3_LA\) \{"), ("LB", r"else if \(act == PH3_LB\) \{"), ("LC", r"if \(act != PH3_LA && act != PH3_LB\) \{"), ("end", r"^\s*// ---- counters ----")]
     at, cur = [], k0
     for name, pat in marks:
         while not re.search(pat, lines[cur]):
@@ -53,7 +53,7 @@ def phase_ranges():
 def function_map():
     """file -> sorted list of (first line, name) of the function definitions in the kernel sources."""
     out = {}
-    for fn in ("crt_mega3.hip", "crt_mega3.h", "crt_path.h", "crt_device.h", "crt_detmath.h", "crt_trace.h"):
+    for fn in ("crt_mega3.hip", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_path.h", "crt_device.h", "crt_detmath.h", "crt_trace.h"):
         defs = []
         for i, l in enumerate(open(os.path.join(SRC, fn)).read().split("\n")):
             if not re.match(r"^(__device__|__global__|static|inline|__host__|CRT_HD)\b", l) or l.rstrip().endswith(";"):
