@@ -412,13 +412,14 @@ class Render:
                                                **self.aov_buffers)
         return rgb, mean
 
-    def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, **overrides):
+    def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, **overrides):
         """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
         AOV pass (albedo, normal, depth, material) and blends the frame into the history this object keeps -- colour, variance, history
         length, depth, normal, material ID and camera of the previous call; the unfiltered result is the next call's history.
         Returns (rgb, mean) of the accumulated frame, or with denoise=True of its variance-guided filter (denoise_var of the accumulated
         mean and variance, the frame's guides).  seed=None renders with self.seed + the number of frames since the last reset (the
-        frames must not share a seed); overrides: depth_tolerance, normal_tolerance, alpha_min.  The first call, the first after
+        frames must not share a seed); overrides: depth_tolerance, normal_tolerance, alpha_min; clamp: temporal()'s (None: the history is
+        not clamped; self.temporal_info then has no `clamped`).  The first call, the first after
         reset_temporal() and the first at another size start a history.  self.frame_buffer / self.mean_buffer hold the frame as
         rendered, self.variance_buffer the accumulated variance, self.temporal_history_buffer the frames accumulated per pixel (H, W),
         self.temporal_info the crt_temporal_info dict, self.aov_buffers the guides."""
@@ -435,7 +436,7 @@ class Render:
         cur = {"color": self.mean_buffer, "variance": self.variance_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
         t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h)) else None
         rgb, mean, var, hist, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
-                                              return_info=True, **overrides)
+                                              return_info=True, clamp=clamp, **overrides)
         self._temporal = {"prev": dict(cur, color=mean, variance=var, history=hist), "camera": cam, "size": (w, h)}
         self._temporal_frames += 1
         self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
@@ -767,6 +768,31 @@ def temporal_defaults():
     return {n: getattr(p, n) for n in ("depth_tolerance", "normal_tolerance", "alpha_min")}
 
 
+def temporal_clamp_defaults():
+    """crt_temporal_clamp_defaults as a dict: radius, gamma."""
+    c = capi.TemporalClamp()
+    capi.check(capi.lib().crt_temporal_clamp_defaults(C.byref(c)), "crt_temporal_clamp_defaults")
+    return {"radius": int(c.radius), "gamma": float(c.gamma)}
+
+
+def _temporal_clamp(clamp):
+    """clamp=True (the defaults) or a dict of radius / gamma -> crt_temporal_clamp"""
+    c = capi.TemporalClamp()
+    capi.check(capi.lib().crt_temporal_clamp_defaults(C.byref(c)), "crt_temporal_clamp_defaults")
+    if clamp is True:
+        return c
+    if not isinstance(clamp, dict) or set(clamp) - {"radius", "gamma"}:
+        raise ValueError("temporal: clamp must be None, True or a dict of radius / gamma, got %r" % (clamp,))
+    if clamp.get("radius") is not None:
+        r = int(clamp["radius"])
+        if r != clamp["radius"] or not 0 <= r < 2 ** 32:
+            raise ValueError("temporal: the clamp's radius must be an integer 1 .. 3, got %r" % (clamp["radius"],))
+        c.radius = r
+    if clamp.get("gamma") is not None:
+        c.gamma = float(clamp["gamma"])
+    return c
+
+
 def _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min):
     p = capi.TemporalParams()
     capi.check(capi.lib().crt_temporal_defaults(C.byref(p)), "crt_temporal_defaults")
@@ -802,13 +828,14 @@ def _temporal_struct(struct, buffers, h, w, keep):
 
 
 def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, want_rgb=True,
-             return_info=False):
+             return_info=False, clamp=None):
     """Temporal accumulation with reprojection (crt_temporal, contract: include/crt.h).  cur: dict of the current frame -- color
     (H, W, 3), depth (H, W), optionally variance, normal (H, W, 3) and id (H, W) int32; prev: dict of the history -- color, history,
     depth, and variance / normal / id as cur has them -- or None for a first frame; camera, prev_camera: (eye, inv_view, fov_y) of the
     two frames.  None settings take crt_temporal_defaults.  Returns (rgb, color, variance, history): the tone map (None without
     want_rgb), the accumulated colour, its variance (None if cur has none) and the frames accumulated per pixel; with return_info
-    also the crt_temporal_info dict."""
+    also the crt_temporal_info dict.  clamp: None (crt_temporal), True or a dict of radius / gamma (crt_temporal_clamped with its defaults /
+    with these values: the history is clamped to its neighbourhood in the current frame, and the info dict gains `clamped`)."""
     c = np.ascontiguousarray(cur["color"], dtype=np.float32)
     if c.ndim != 3 or c.shape[2] != 3:
         raise ValueError("temporal needs an (H, W, 3) colour image, got %r" % (c.shape,))
@@ -823,18 +850,23 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
     var = np.zeros((h, w, 3), dtype=np.float32) if cur.get("variance") is not None else None
     hist = np.zeros((h, w), dtype=np.float32)
     rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
-    info = capi.TemporalInfo()
-    capi.check(capi.lib().crt_temporal(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, capi.ptr(color), capi.ptr(var),
-                                       capi.ptr(hist), capi.ptr(rgb), C.byref(info)), "crt_temporal")
+    if clamp is None:
+        info = capi.TemporalInfo()
+        capi.check(capi.lib().crt_temporal(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, capi.ptr(color), capi.ptr(var),
+                                           capi.ptr(hist), capi.ptr(rgb), C.byref(info)), "crt_temporal")
+    else:
+        info = capi.TemporalClampInfo()
+        capi.check(capi.lib().crt_temporal_clamped(device, C.byref(prm), C.byref(_temporal_clamp(clamp)), C.byref(fc), C.byref(fp) if fp is not None else None,
+                                                   capi.ptr(color), capi.ptr(var), capi.ptr(hist), capi.ptr(rgb), C.byref(info)), "crt_temporal_clamped")
     out = (rgb, color, var, hist)
     return out + (info.as_dict(),) if return_info else out
 
 
 def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_ptr, out_variance_ptr=None, out_rgb_ptr=None, prev_ptrs=None,
-                    prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True):
+                    prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True, clamp=None):
     """Enqueues crt_temporal_device with everything in device memory: cur_ptrs / prev_ptrs = {name: raw device pointer} with the names of
     temporal()'s dicts (prev_ptrs None: no history).  With want_info the call synchronizes the stream and returns the crt_temporal_info
-    dict, else None."""
+    dict, else None.  clamp: as temporal() (crt_temporal_clamped_device; the dict gains `clamped`)."""
     def fill(struct, ptrs):
         for name, p in ptrs.items():
             if name not in {n for n, _ in struct._fields_}:
@@ -844,11 +876,18 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
     fc = fill(capi.TemporalFrame(), cur_ptrs)
     fp = fill(capi.TemporalHistory(), prev_ptrs) if prev_ptrs is not None else None
     prm = _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min)
-    info = capi.TemporalInfo()
     vp = lambda p: C.c_void_p(p) if p else None
-    capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, vp(out_color_ptr),
-                                              vp(out_variance_ptr), vp(out_history_ptr), vp(out_rgb_ptr), vp(stream),
-                                              C.byref(info) if want_info else None), "crt_temporal_device")
+    if clamp is None:
+        info = capi.TemporalInfo()
+        capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, vp(out_color_ptr),
+                                                  vp(out_variance_ptr), vp(out_history_ptr), vp(out_rgb_ptr), vp(stream),
+                                                  C.byref(info) if want_info else None), "crt_temporal_device")
+    else:
+        info = capi.TemporalClampInfo()
+        capi.check(capi.lib().crt_temporal_clamped_device(device, C.byref(prm), C.byref(_temporal_clamp(clamp)), C.byref(fc),
+                                                          C.byref(fp) if fp is not None else None, vp(out_color_ptr), vp(out_variance_ptr),
+                                                          vp(out_history_ptr), vp(out_rgb_ptr), vp(stream), C.byref(info) if want_info else None),
+                   "crt_temporal_clamped_device")
     return info.as_dict() if want_info else None
 
 

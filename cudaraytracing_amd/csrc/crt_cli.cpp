@@ -9,12 +9,13 @@
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
 //           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]
-//           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise]
+//           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 // --temporal N renders N frames on one device and accumulates them over time (crt_temporal, its defaults): frame f = 0 .. N-1 has eye and
 // lookat moved by f x the --temporal-step vector and the seed --seed + f.  -o gets the last frame as rendered, --temporal-out PATH the
 // accumulated last frame; --temporal-denoise writes the variance-guided filter (crt_denoise_var, its defaults with the --denoise-iterations
 // / --denoise-sigma overrides) of the accumulated frame and its accumulated variance to --temporal-out instead.  --variance, --denoise and
-// --aov work on the last frame as rendered.
+// --aov work on the last frame as rendered.  --temporal-clamp GAMMA[,RADIUS] clamps the history to mean +- GAMMA deviations of the
+// (2 RADIUS + 1)^2 current pixels around each pixel (crt_temporal_clamped; RADIUS 1 .. 3, default: crt_temporal_clamp_defaults').
 // --adaptive THRESHOLD renders the frame with variance-driven adaptive sampling (crt_render_adaptive, one device): --spp is the cap, a
 // pixel stops once the standard error of its mean is at most THRESHOLD x (mean + floor); --adaptive-min / --adaptive-step override the
 // warm-up and the samples per pass of crt_adaptive_defaults, --adaptive-samples PATH writes the samples per pixel as a 1-channel PFM.
@@ -47,7 +48,7 @@ int main(int argc, char** argv)
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n"
-                             "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise]\n", argv[0]);
+                             "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n", argv[0]);
         return 2;
     }
     try {
@@ -61,7 +62,9 @@ int main(int argc, char** argv)
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false;
         int temporal = 0;
-        bool temporal_option = false, temporal_denoise = false;
+        bool temporal_option = false, temporal_denoise = false, temporal_clamp = false;
+        crt_temporal_clamp tclamp;
+        crt_temporal_clamp_defaults(&tclamp);
         float temporal_step[3] = {0.0f, 0.0f, 0.0f};
         std::string temporal_out;
         uint64_t seed = 0;
@@ -129,6 +132,21 @@ int main(int argc, char** argv)
             }
             else if (a == "--temporal-out") { need(i, 1); temporal_out = argv[++i]; temporal_option = true; }
             else if (a == "--temporal-denoise") { temporal_denoise = true; temporal_option = true; }
+            else if (a == "--temporal-clamp") {
+                need(i, 1);
+                temporal_clamp = temporal_option = true;
+                const char* q = argv[++i];
+                char* end = nullptr;
+                tclamp.gamma = std::strtof(q, &end);
+                bool good = end != q && (*end == 0 || *end == ',') && tclamp.gamma >= 0.0f; // (false for NaN)
+                if (good && *end == ',') {
+                    q = end + 1;
+                    const long r = std::strtol(q, &end, 10);
+                    good = end != q && *end == 0 && r >= 1 && r <= 3;
+                    tclamp.radius = (uint32_t)r;
+                }
+                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-clamp needs GAMMA[,RADIUS]: GAMMA >= 0, RADIUS 1 .. 3");
+            }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
@@ -165,7 +183,7 @@ int main(int argc, char** argv)
         if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
         if (multi && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates on one device (not with --gpus / --devices)");
         if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
-        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out and --temporal-denoise need --temporal N");
+        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise and --temporal-clamp need --temporal N");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step and --adaptive-samples need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
@@ -202,9 +220,11 @@ int main(int argc, char** argv)
                 }
                 crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
                 render.set_seed(seed + (uint64_t)f);
-                render.run_temporal(task.eye_pos, inv_view, fov_y, tp);
+                render.run_temporal(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr);
                 std::printf("temporal frame %d: %llu of %llu pixels reprojected, device %.3f ms\n", f, (unsigned long long)render.last_temporal_info().reprojected,
                             (unsigned long long)task.width * task.height, render.last_temporal_info().total_ms);
+                if (temporal_clamp) std::printf("temporal frame %d: %llu histories clamped (gamma %g, radius %u)\n", f, (unsigned long long)render.last_temporal_clamped(),
+                                                (double)tclamp.gamma, tclamp.radius);
             }
         }
         else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);

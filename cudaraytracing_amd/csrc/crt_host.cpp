@@ -775,7 +775,7 @@ void Render::run_denoise_var(const crt_denoise_params& prm)
     denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
 }
 
-void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm)
+void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp)
 {
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_temporal: temporal accumulation is a single-device interface");
     if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal after free()");
@@ -798,7 +798,14 @@ void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], f
     prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
     std::vector<float> color(3 * n, 0.0f), variance_out(3 * n, 0.0f), history(n, 0.0f);
     temporal_rgb_.assign(3 * n, 0);
-    const int rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &temporal_info_);
+    int rc;
+    temporal_clamped_ = 0;
+    if (clamp) {
+        crt_temporal_clamp_info ci{};
+        rc = crt_temporal_clamped(device_, &p, clamp, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &ci);
+        temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
+        temporal_clamped_ = ci.clamped;
+    } else rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &temporal_info_);
     if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal failed: ") + crt_last_error()); }
     temporal_color_.swap(color); temporal_variance_.swap(variance_out); temporal_history_.swap(history);
     temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;

@@ -239,14 +239,16 @@ public:
     // here): run_view (needs set_flags(CRT_FLAG_VARIANCE)), variance, run_aov, then the frame is blended into the history this object keeps
     // -- colour, variance, history length, depth, normal, material ID and camera of the previous call -- and the unfiltered result becomes
     // the new history.  The first call, the first after reset_temporal() or after a change of size starts a history.  Render every frame
-    // with another seed (set_seed).  frame and mean buffers hold the frame as rendered; one device only
-    void run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm);
+    // with another seed (set_seed).  frame and mean buffers hold the frame as rendered; one device only.  clamp != nullptr: the history is
+    // clamped to its neighbourhood (crt_temporal_clamped); last_temporal_clamped() is then the count of pixels it moved
+    void run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp = nullptr);
     void reset_temporal() { temporal_valid_ = false; }
     const unsigned char* get_temporal_buffer() const { return temporal_rgb_.data(); }        // W x H x 3 RGB8: the accumulated frame
     const float* get_temporal_mean_buffer() const { return temporal_color_.data(); }          // W x H x 3
     const float* get_temporal_variance_buffer() const { return temporal_variance_.data(); }   // W x H x 3
     const float* get_temporal_history_buffer() const { return temporal_history_.data(); }     // W x H: frames accumulated per pixel
     const crt_temporal_info& last_temporal_info() const { return temporal_info_; }
+    uint64_t last_temporal_clamped() const { return temporal_clamped_; }
     // the accumulated frame filtered by crt_denoise_var with its accumulated variance and the guides of the last frame
     void run_denoise_temporal(const crt_denoise_params& prm);
     void save_temporal_buffer(const char* save_path) const;
@@ -298,6 +300,7 @@ private:
     unsigned temporal_width_ = 0, temporal_height_ = 0;
     bool temporal_valid_ = false;
     crt_temporal_info temporal_info_{};
+    uint64_t temporal_clamped_ = 0;
     void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm);
     crt_adaptive_info adaptive_info_{};
     int device_ = 0;

@@ -6,6 +6,11 @@
 // previous camera, gathers the four bilinear taps straight from the caller's buffers (neighbouring pixels of a row land on neighbouring
 // taps unless the surface is seen at a grazing angle) and blends or resets.  The count of pixels that took the history is one ballot,
 // one popcount and one atomic per wave, as k_adaptive_select counts its slots; it is kept only when the caller asks for the info.
+//
+// k_temporal<true> (crt_temporal_clamped) adds the neighbourhood clamp between the interpolation and the blend: mean and standard
+// deviation of the current colour over the (2 radius + 1)^2 pixels around p, straight from the caller's buffer (a wave's 64 pixels share
+// all but 2 radius columns of their taps), the history colour clamped to mean +- gamma deviations, and a second count on the same ballot
+// path.  The statistics run INSIDE the branch of the pixels that take the history, not before it: see docs/experiments.md.
 #include "crt_internal.h"
 
 #include <cstring>
@@ -24,16 +29,40 @@ struct TpParams {
     uint8_t* out_rgb;
     float* out_variance;
     float* out_history;
-    unsigned long long* count;                // pixels that took the history (null: not counted)
+    unsigned long long* count;                // [0] pixels that took the history, [1] of those: moved by the clamp (null: not counted)
+    int radius;                               // k_temporal<true> only: crt_temporal_clamp
+    float gamma;
 };
 
+// One channel of the interpolated history, hc / ws; with CLAMP clamped into [mu - gamma sd, mu + gamma sd] of the neighbourhood sums
+// (`moved` is set if that changed it).  A NaN in the history or in the box fails both comparisons and the history passes through.
+template <bool CLAMP>
+__device__ __forceinline__ float history_channel(float hc, float ws, float s1, float s2, float cnt, float gamma, bool& moved)
+{
+    float h = hc / ws;
+    if (CLAMP) {
+        const float mu = s1 / cnt;
+        float e = s2 / cnt - mu * mu;
+        e = e < 0.0f ? 0.0f : e;
+        const float w = gamma * sqrt_f(e);
+        const float lo = mu - w, hi = mu + w;
+        const bool below = h < lo;
+        h = below ? lo : h;
+        const bool above = h > hi;
+        h = above ? hi : h;
+        moved |= below | above;
+    }
+    return h;
+}
+
+template <bool CLAMP>
 __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
 {
     const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
     const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
     const int W = (int)P.width, H = (int)P.height;
     const bool inside = x < W && y < H;
-    bool took = false;
+    bool took = false, clamped = false;
     if (inside) {
         const size_t p = (size_t)y * P.width + (size_t)x;
         const F3 c = f3(P.color[p * 3], P.color[p * 3 + 1], P.color[p * 3 + 2]);
@@ -107,7 +136,27 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
                     float a = 1 / oh;
                     a = a < P.alpha_min ? P.alpha_min : a;
                     const float k = 1 - a;
-                    oc = f3((hc.x / ws) * k + c.x * a, (hc.y / ws) * k + c.y * a, (hc.z / ws) * k + c.z * a);
+                    // sums of the current colour and its squares around p; every tap is tested against the image, so every read is inside it
+                    F3 s1 = f3(0.0f, 0.0f, 0.0f), s2 = f3(0.0f, 0.0f, 0.0f);
+                    float cnt = 0.0f;
+                    if (CLAMP) {
+                        for (int dy = -P.radius; dy <= P.radius; dy++) {
+                            const int ty = y + dy;
+                            if (ty < 0 || ty >= H) continue;
+                            for (int dx = -P.radius; dx <= P.radius; dx++) {
+                                const int tx = x + dx;
+                                if (tx < 0 || tx >= W) continue;
+                                const size_t t = ((size_t)ty * P.width + (size_t)tx) * 3;
+                                const float tr = P.color[t], tg = P.color[t + 1], tb = P.color[t + 2];
+                                s1.x = s1.x + tr; s1.y = s1.y + tg; s1.z = s1.z + tb;
+                                s2.x = s2.x + tr * tr; s2.y = s2.y + tg * tg; s2.z = s2.z + tb * tb;
+                                cnt = cnt + 1;
+                            }
+                        }
+                    }
+                    oc = f3(history_channel<CLAMP>(hc.x, ws, s1.x, s2.x, cnt, P.gamma, clamped) * k + c.x * a,
+                            history_channel<CLAMP>(hc.y, ws, s1.y, s2.y, cnt, P.gamma, clamped) * k + c.y * a,
+                            history_channel<CLAMP>(hc.z, ws, s1.z, s2.z, cnt, P.gamma, clamped) * k + c.z * a);
                     if (P.variance) {
                         const float kk = k * k, aa = a * a;
                         ov = f3((hv.x / ws) * kk + v.x * aa, (hv.y / ws) * kk + v.y * aa, (hv.z / ws) * kk + v.z * aa);
@@ -122,8 +171,13 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
     if (!P.count) return;
     const unsigned long long mask = __ballot(took);
     if (mask == 0ull) return;
-    if ((int)(threadIdx.x & 63u) == __ffsll((long long)mask) - 1)
-        __hip_atomic_fetch_add(P.count, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const bool first = (int)(threadIdx.x & 63u) == __ffsll((long long)mask) - 1;
+    if (first) __hip_atomic_fetch_add(P.count, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CLAMP) { // (a clamped pixel took the history: the wave is still here, and `first` is one of its lanes)
+        const unsigned long long cmask = __ballot(clamped);
+        if (cmask != 0ull && first)
+            __hip_atomic_fetch_add(P.count + 1, (unsigned long long)__popcll(cmask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 } // namespace crtk
@@ -133,11 +187,13 @@ using namespace crtk;
 namespace {
 
 const uint32_t kMaxSide = 1u << 24;
+const uint32_t CLAMP_DEFAULT_RADIUS = 1;   // crt_temporal_clamp_defaults: chosen by the sweep of docs/experiments.md
+const float CLAMP_DEFAULT_GAMMA = 1.0f;
 bool tolerance_ok(float t) { return t > 0.0f; } // (false for NaN)
 
-// Argument checks of both forms, before any device call
-int temporal_check(const char* who, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, const void* out_color,
-                   const void* out_variance, const void* out_history)
+// Argument checks of all four calls, before any device call (clamp: null for crt_temporal / crt_temporal_device)
+int temporal_check(const char* who, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                   const crt_temporal_history* prev, const void* out_color, const void* out_variance, const void* out_history)
 {
     const std::string w(who);
     if (!prm || !cur) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
@@ -155,6 +211,10 @@ int temporal_check(const char* who, const crt_temporal_params* prm, const crt_te
         if ((cur->normal != nullptr) != (prev->normal != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": normals must be given in both frames or in neither");
         if ((cur->id != nullptr) != (prev->id != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": IDs must be given in both frames or in neither");
     }
+    if (clamp) {
+        if (clamp->radius < 1 || clamp->radius > 3) return fail(CRT_ERR_INVALID_ARG, w + ": the clamp's radius must be 1 .. 3");
+        if (!(clamp->gamma >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": the clamp's gamma must be >= 0 (+inf never clamps)"); // (false for NaN)
+    }
     if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
     if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
     return CRT_OK;
@@ -167,10 +227,14 @@ void set_camera(const crt_camera& cam, float* eye, float* iv, float& scale)
     scale = det_tanf(cam.fov_y / 2);
 }
 
-int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, void* d_out_color,
-                  void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st, crt_temporal_info* info)
+// what crt_temporal_info and crt_temporal_clamp_info are filled from
+struct TemporalCounts { float total_ms; unsigned long long reprojected, clamped; };
+
+int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                  const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st,
+                  TemporalCounts* info)
 {
-    const int rc = temporal_check(who, prm, cur, prev, d_out_color, d_out_variance, d_out_history);
+    const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history);
     if (rc != CRT_OK) return rc;
     if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -197,22 +261,25 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
         P.out_mean = (float*)d_out_color; P.out_rgb = (uint8_t*)d_out_rgb;
         P.out_variance = (float*)d_out_variance; P.out_history = (float*)d_out_history;
         if (info) {
-            d_count.alloc(1);
-            HIP_CHECK(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
+            d_count.alloc(2);
+            HIP_CHECK(hipMemsetAsync(d_count.p, 0, 2 * sizeof(unsigned long long), st));
             P.count = d_count.p;
             HIP_CHECK(hipEventCreate(&e0));
             HIP_CHECK(hipEventCreate(&e1));
             HIP_CHECK(hipEventRecord(e0, st));
         }
-        hipLaunchKernelGGL(k_temporal, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P);
+        const dim3 grid(P.tiles_x * ((prm->height + 3) / 4));
+        if (clamp) {
+            P.radius = (int)clamp->radius; P.gamma = clamp->gamma;
+            hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, st, P);
+        } else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(256), 0, st, P);
         HIP_CHECK(hipGetLastError());
         if (info) {
             HIP_CHECK(hipEventRecord(e1, st));
-            unsigned long long n = 0;
-            HIP_CHECK(hipMemcpyAsync(&n, d_count.p, sizeof(n), hipMemcpyDeviceToHost, st));
+            unsigned long long n[2] = {0, 0};
+            HIP_CHECK(hipMemcpyAsync(n, d_count.p, sizeof(n), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->reprojected = n;
+            info->reprojected = n[0]; info->clamped = n[1];
             HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
         }
     } catch (const HipFail& f) {
@@ -223,11 +290,13 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
     return status;
 }
 
-// The host-buffer form (the caller has checked the arguments): device copies of the inputs, the device form, then the copies back.
-int temporal_host(int device, const crt_temporal_params* prm, const crt_temporal_frame* cur, const crt_temporal_history* prev, float* out_color,
-                  float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_info* info)
+// The host-buffer form: the argument checks, device copies of the inputs, the device form, then the copies back.
+int temporal_host(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                  const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, TemporalCounts* info)
 {
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_temporal: device index out of range");
+    const int rc0 = temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history);
+    if (rc0 != CRT_OK) return rc0;
+    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
     try {
         HIP_CHECK(hipSetDevice(device));
         const uint64_t npix = (uint64_t)prm->width * prm->height;
@@ -253,7 +322,7 @@ int temporal_host(int device, const crt_temporal_params* prm, const crt_temporal
         o_hist.alloc(npix);
         if (out_variance) o_var.alloc(npix * 3);
         if (out_rgb) o_rgb.alloc(npix * 3);
-        const int rc = temporal_impl("crt_temporal_device", device, prm, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info);
+        const int rc = temporal_impl(who, device, prm, clamp, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
         o_color.download(out_color, npix * 3);
@@ -264,6 +333,38 @@ int temporal_host(int device, const crt_temporal_params* prm, const crt_temporal
     } catch (const HipFail& f) {
         return fail_hip(f);
     }
+}
+
+// the two info structs, filled from the counts of a call that succeeded
+void fill_info(crt_temporal_info* info, const TemporalCounts& n)
+{
+    std::memset(info, 0, sizeof(*info));
+    info->total_ms = n.total_ms; info->reprojected = n.reprojected;
+}
+void fill_info(crt_temporal_clamp_info* info, const TemporalCounts& n)
+{
+    std::memset(info, 0, sizeof(*info));
+    info->total_ms = n.total_ms; info->reprojected = n.reprojected; info->clamped = n.clamped;
+}
+
+template <class Info>
+int temporal_device_form(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                         const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* stream, Info* info)
+{
+    TemporalCounts n{};
+    const int rc = temporal_impl(who, device, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, (hipStream_t)stream, info ? &n : nullptr);
+    if (rc == CRT_OK && info) fill_info(info, n);
+    return rc;
+}
+
+template <class Info>
+int temporal_host_form(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                       const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, Info* info)
+{
+    TemporalCounts n{};
+    const int rc = temporal_host(who, device, prm, clamp, cur, prev, out_color, out_variance, out_history, out_rgb, info ? &n : nullptr);
+    if (rc == CRT_OK && info) fill_info(info, n);
+    return rc;
 }
 
 } // namespace
@@ -278,18 +379,39 @@ int crt_temporal_defaults(crt_temporal_params* prm)
     return CRT_OK;
 }
 
+int crt_temporal_clamp_defaults(crt_temporal_clamp* clamp)
+{
+    if (!clamp) return fail(CRT_ERR_INVALID_ARG, "crt_temporal_clamp_defaults: null argument");
+    std::memset(clamp, 0, sizeof(*clamp));
+    clamp->radius = CLAMP_DEFAULT_RADIUS; clamp->gamma = CLAMP_DEFAULT_GAMMA;
+    return CRT_OK;
+}
+
 int crt_temporal_device(int device, const crt_temporal_params* prm, const crt_temporal_frame* dev_cur, const crt_temporal_history* dev_prev,
                         void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* stream, crt_temporal_info* info)
 {
-    return temporal_impl("crt_temporal_device", device, prm, dev_cur, dev_prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, (hipStream_t)stream, info);
+    return temporal_device_form("crt_temporal_device", device, prm, nullptr, dev_cur, dev_prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, stream, info);
 }
 
 int crt_temporal(int device, const crt_temporal_params* prm, const crt_temporal_frame* host_cur, const crt_temporal_history* host_prev, float* out_color,
                  float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_info* info)
 {
-    const int rc0 = temporal_check("crt_temporal", prm, host_cur, host_prev, out_color, out_variance, out_history);
-    if (rc0 != CRT_OK) return rc0;
-    return temporal_host(device, prm, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info);
+    return temporal_host_form("crt_temporal", device, prm, nullptr, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info);
+}
+
+int crt_temporal_clamped_device(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* dev_cur,
+                                const crt_temporal_history* dev_prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb,
+                                void* stream, crt_temporal_clamp_info* info)
+{
+    return temporal_device_form("crt_temporal_clamped_device", device, prm, clamp, dev_cur, dev_prev, d_out_color, d_out_variance, d_out_history, d_out_rgb,
+                                stream, info);
+}
+
+int crt_temporal_clamped(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* host_cur,
+                         const crt_temporal_history* host_prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb,
+                         crt_temporal_clamp_info* info)
+{
+    return temporal_host_form("crt_temporal_clamped", device, prm, clamp, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info);
 }
 
 } // extern "C"

@@ -524,8 +524,8 @@ int crt_denoise_var_device(int device, const crt_denoise_params* params, const c
  * CRT_ERR_INVALID_ARG, checked before any device call: a null required pointer, a size of 0, a tolerance that is not > 0 (NaN included;
  * +inf is allowed and switches its test off), alpha_min outside (0, 1], a half-given pair.  A side longer than 2^24 pixels or more than
  * 2^31 thread blocks of 64 x 4 pixels: CRT_ERR_UNSUPPORTED.
- * Not done here: clamping the history to the colours around p (view-dependent highlights lag behind the camera), a wider search when
- * the four taps fail, moving geometry, tiled shards. */
+ * Not done here: a wider search when the four taps fail, moving geometry, tiled shards.  Clamping the history to the colours around p
+ * (view-dependent highlights lag behind the camera) is crt_temporal_clamped, below. */
 typedef struct {
     uint32_t width, height;
     crt_camera cur, prev;          /* camera of the current frame / of the frame the history was made with */
@@ -547,6 +547,52 @@ int crt_temporal(int device, const crt_temporal_params* params, const crt_tempor
  * (the call then counts the reprojected pixels and synchronizes the stream to read them and the timer). */
 int crt_temporal_device(int device, const crt_temporal_params* params, const crt_temporal_frame* dev_cur, const crt_temporal_history* dev_prev,
                         void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* hip_stream, crt_temporal_info* info);
+
+/* crt_temporal with the history clamped to its neighbourhood (the variance clamp of temporal anti-aliasing, Salvi 2016): before the
+ * blend, the interpolated history colour of a pixel is clamped, per channel, to mean +- gamma standard deviations of the CURRENT frame's
+ * colour over the (2 * radius + 1)^2 pixels around it, so that a history that no longer resembles what the pixel shows now (a
+ * view-dependent highlight that has moved on, a surface the tolerances let through) is pulled to the present instead of blended in.
+ * Everything of crt_temporal's definition up to and including `hc = hc / ws; ... k = 1 - a` is unchanged.  For a pixel p = (x, y) that
+ * takes the history (ok && ws > 0.015625f), with H = hc / ws per channel and r = radius:
+ *   s1 = s2 = +0.0f per channel; cnt = +0.0f
+ *   taps t = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r inner; a tap outside the image is skipped (p itself always counts)
+ *        s1 = s1 + color(t);   s2 = s2 + color(t) * color(t);   cnt = cnt + 1
+ *   mu = s1 / cnt;   e = s2 / cnt - mu * mu;   e = e < 0 ? 0 : e;   sd = sqrt(e);   w = gamma * sd
+ *   lo = mu - w;     hi = mu + w
+ *   Hc = H < lo ? lo : H;    Hc = Hc > hi ? hi : Hc
+ *   out_color = Hc * k + color(p) * a
+ *   clamped(p) = one of the six comparisons (two per channel) was true
+ * Every * + - / and sqrt is one IEEE fp32 operation (no FMA, no reciprocal multiply); sums run left to right as written.  A NaN in H, lo
+ * or hi makes both comparisons false and H passes through; with gamma = +inf, w is +inf or (sd = 0) NaN and nothing is ever clamped:
+ * the call then writes crt_temporal's bits.  The neighbourhood takes every tap inside the image whatever its depth or ID: a box that
+ * spans two surfaces is wider and clamps less, the safe side.
+ * out_variance and out_history are crt_temporal's, from the UNclamped hv and hn: the carried variance therefore understates the noise of
+ * a clamped pixel (its history was replaced by a statistic of one frame), and its history length overstates what it has accumulated.
+ * Reset pixels and calls without a history are crt_temporal's.  clamp == NULL: the call is crt_temporal / crt_temporal_device (the same
+ * kernel, the same bits; clamped = 0).  crt_temporal_clamp_defaults fills radius 1, gamma 1 (docs/experiments.md, "The neighbourhood
+ * clamp": the setting with the smallest summed error ratio over four sequences; what it does and does not repair is stated there).
+ * CRT_ERR_INVALID_ARG, checked before any device call: everything crt_temporal refuses, a radius outside 1 .. 3, a gamma that is
+ * negative or NaN.
+ * Not done here: cutting the history length or inflating the variance of clamped pixels, clamping in another colour space (YCoCg), a
+ * neighbourhood restricted to the pixel's surface, the 3x3 fallback search, tiled shards and crt_multi. */
+typedef struct {
+    uint32_t radius;   /* neighbourhood is (2*radius+1)^2 pixels of the CURRENT frame's colour; 1 .. 3 */
+    float    gamma;    /* half-width of the box in standard deviations; >= 0, not NaN, +inf allowed (never clamps) */
+} crt_temporal_clamp;
+typedef struct {
+    float total_ms;        /* as crt_temporal_info */
+    uint64_t reprojected;  /* as crt_temporal_info */
+    uint64_t clamped;      /* of those: pixels where at least one channel of the history was moved by the clamp */
+} crt_temporal_clamp_info;
+int crt_temporal_clamp_defaults(crt_temporal_clamp* clamp);
+/* host buffers, as crt_temporal; clamp may be NULL; info optional */
+int crt_temporal_clamped(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_frame* host_cur,
+                         const crt_temporal_history* host_prev /* may be NULL */, float* out_color, float* out_variance, float* out_history,
+                         uint8_t* out_rgb, crt_temporal_clamp_info* info);
+/* device buffers on hip_stream, as crt_temporal_device (info != NULL: counts both, synchronizes the stream) */
+int crt_temporal_clamped_device(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_frame* dev_cur,
+                                const crt_temporal_history* dev_prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb,
+                                void* hip_stream, crt_temporal_clamp_info* info);
 
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there

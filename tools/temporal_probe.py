@@ -13,9 +13,17 @@ Effect: at --error-size, spp 8, 8 frames with seeds 100 .. 107, per scene with a
 its variance-guided denoise (crt_denoise_var), the accumulated frame, and the variance-guided denoise of the accumulated frame with
 its accumulated variance.
 
+--clamp: the neighbourhood clamp (crt_temporal_clamped).  Cost: at each size the clamped call at radius 1, 2 and 3 (gamma: the
+default) takes turns with the unclamped call in the same loop; median ms of each, its ratio to the unclamped median of this run, the
+share of pixels clamped and the (2 radius + 1)^2 x 12 cached bytes a pixel's neighbourhood reads.  Effect: the sequences above with the
+default alpha_min, for every radius of 1, 2, 3 and gamma of --clamp-gammas: the accumulated error, that of its variance-guided denoise,
+and the share of pixels clamped in the last frame; then the setting with the smallest sum over the sequences of clamped / unclamped
+accumulated error.
+
 One JSON line per figure on stderr, one JSON document on stdout.
 
   python tools/temporal_probe.py [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--spp 4] [--error-size 160x120] [--alpha-min 0.05,0.1,0.2]
+                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf]
 """
 import argparse
 import ctypes as C
@@ -90,19 +98,24 @@ def cost(a, H, out):
             if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
                 raise RuntimeError("hipMemcpy failed")
 
-        def call_temporal():
+        def call_temporal(clamp=None):
             return crt.temporal_device(w, h, cams[1], {k: ptrs["cur_" + k] for k in c1}, ptrs["out_color"], ptrs["out_hist"],
                                        out_variance_ptr=ptrs["out_var"], out_rgb_ptr=ptrs["out_rgb"], prev_ptrs={k: ptrs["prev_" + k] for k in prev},
-                                       prev_camera=cams[0])
+                                       prev_camera=cams[0], clamp=clamp)
 
         def call_denoise():
             return crt.denoise_device(w, h, ptrs["cur_color"], ptrs["out_color"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes,
                                       albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["cur_normal"], depth_ptr=ptrs["cur_depth"], iterations=3)["total_ms"]
 
         ms, ms_dn, info = [], [], None
+        radii = (1, 2, 3) if a.clamp else ()
+        ms_cl, info_cl = {r: [] for r in radii}, {}
         for _ in range(a.warmup + a.calls):
             info = call_temporal()
             ms.append(info["total_ms"])
+            for r in radii:
+                info_cl[r] = call_temporal({"radius": r})
+                ms_cl[r].append(info_cl[r]["total_ms"])
             ms_dn.append(call_denoise())
         ms, ms_dn = ms[a.warmup:], ms_dn[a.warmup:]
         med = statistics.median(ms)
@@ -113,6 +126,15 @@ def cost(a, H, out):
                "temporal_over_denoise_pass": round(med / (statistics.median(ms_dn) / 3), 4)}
         out["cost"].append(run)
         print(json.dumps(run), file=sys.stderr, flush=True)
+        for r in radii:
+            m = statistics.median(ms_cl[r][a.warmup:])
+            run = {"width": w, "height": h, "clamp_radius": r, "clamp_gamma": crt.temporal_clamp_defaults()["gamma"], "clamped_ms_median": round(m, 4),
+                   "clamped_ms_best": round(min(ms_cl[r][a.warmup:]), 4), "clamped_ms_worst": round(max(ms_cl[r][a.warmup:]), 4),
+                   "unclamped_ms_median": round(med, 4), "clamped_over_unclamped": round(m / med, 4),
+                   "clamped_fraction": round(info_cl[r]["clamped"] / (w * h), 4), "reprojected_fraction": round(info_cl[r]["reprojected"] / (w * h), 4),
+                   "neighbourhood_bytes_per_pixel": (2 * r + 1) ** 2 * 12}
+            out["clamp_cost"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
         for p in ptrs.values():
             H.hipFree(C.c_void_p(p))
 
@@ -149,7 +171,33 @@ def effect(a, out):
                            reprojected_fraction_last=round(info["reprojected"] / (w * h), 4), mean_history=round(float(hist.mean()), 2))
                 out["effect"].append(run)
                 print(json.dumps(run), file=sys.stderr, flush=True)
+            if not a.clamp:
+                continue
+            for radius in (1, 2, 3):
+                for gamma in [float(v) for v in a.clamp_gammas.split(",")]:
+                    prev = pcam = None
+                    for cur, _, g, cam in frames:
+                        rgb, color, var, hist, info = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, return_info=True,
+                                                                   clamp={"radius": radius, "gamma": gamma})
+                        prev, pcam = dict(cur, color=color, variance=var, history=hist), cam
+                    run = dict(base, clamp_radius=radius, clamp_gamma=repr(gamma), mse_accumulated=round(mse(rgb, ref), 1),
+                               mse_accumulated_denoise_var=round(mse(crt.denoise_var(color, var, **g)[0], ref), 1),
+                               clamped_fraction_last=round(info["clamped"] / (w * h), 4))
+                    out["clamp_effect"].append(run)
+                    print(json.dumps(run), file=sys.stderr, flush=True)
         r.free()
+    if a.clamp:
+        # the sum over the sequences of clamped / unclamped accumulated error (the unclamped one: gamma = inf), per setting
+        rows = out["clamp_effect"]
+        plain = {(x["scene"], x["camera"]): x["mse_accumulated"] for x in rows if x["clamp_gamma"] == "inf" and x["clamp_radius"] == 1}
+        sums = {}
+        for x in rows:
+            key = (x["clamp_radius"], x["clamp_gamma"])
+            sums[key] = sums.get(key, 0.0) + x["mse_accumulated"] / plain[(x["scene"], x["camera"])]
+        best = min(sums, key=sums.get)
+        out["clamp_ratio_sums"] = [{"clamp_radius": k[0], "clamp_gamma": k[1], "ratio_sum": round(v, 3)} for k, v in sorted(sums.items())]
+        out["clamp_best"] = {"clamp_radius": best[0], "clamp_gamma": best[1], "ratio_sum": round(sums[best], 3), "defaults": crt.temporal_clamp_defaults()}
+        print(json.dumps(out["clamp_best"]), file=sys.stderr, flush=True)
 
 
 def main():
@@ -160,12 +208,14 @@ def main():
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--error-size", default="160x120")
     ap.add_argument("--alpha-min", default="0.05,0.1,0.2")
+    ap.add_argument("--clamp", action="store_true")
+    ap.add_argument("--clamp-gammas", default="0.5,1,1.5,2,3,inf")
     ap.add_argument("--skip-cost", action="store_true")
     ap.add_argument("--skip-effect", action="store_true")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("temporal_probe: no HIP device")
-    out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": []}
+    out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "clamp_cost": [], "clamp_effect": []}
     if not a.skip_cost:
         cost(a, hip_runtime(), out)
     if not a.skip_effect:
