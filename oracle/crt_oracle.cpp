@@ -349,6 +349,20 @@ static float g_ray_log_limit = std::numeric_limits<float>::quiet_NaN(); /* the v
  * blocked visibility ray.  Bin 0 also takes everything below, bin 23 everything above; [24] = answers with a hit, [25] = all rays. */
 static uint64_t* g_margin_hist = nullptr;
 
+/* diagnostic draw log (orc_draw_log_*): every raw 32-bit word in the order the oracle CONSUMES it, which is the order the reference's one
+ * sequential stream per pixel hands words out (Render.cuh:344-345, :216, Global.h:59-60, DeviceLights.cuh:35, DeviceTriangle.cuh:69-70,
+ * Global.h:70-71); a word that is drawn but not used (out[1..2] of a bounce that dies, out[3] of every draw) is not logged.  Per path:
+ * the offset of its first word (the two jitters), the camera ray as handed to Ray's constructor, and whether the path took the
+ * emitter-probe branch (Render.cuh:304-313) at least once. */
+struct DrawLog {
+    std::vector<uint32_t> words;
+    std::vector<uint64_t> off;
+    std::vector<uint8_t> flag;
+    std::vector<float> ray;
+};
+static DrawLog* g_draw_log = nullptr;
+inline void log_draw(uint32_t w) { if (g_draw_log) g_draw_log->words.push_back(w); }
+
 struct Ray {
     V3 origin, dir, inv_dir;
     Ray(V3 o, V3 d) : origin(o)
@@ -543,6 +557,7 @@ LightSample sample_light(const PathCtx& c, int light, uint32_t depth, uint32_t i
     const Object& obj = c.sc.objects[c.sc.light_objs[light]];
     uint32_t r[4];
     orc_draw(c.seed, c.pixel, c.k, depth, ORC_RNG_NEE, idx, r);
+    log_draw(r[0]); log_draw(r[1]); log_draw(r[2]);
     uint32_t ti = (uint32_t)((uint64_t)r[0] % (uint64_t)obj.triangles.size());
     const Triangle& T = obj.triangles[ti];
     float alpha = orc_uniform(r[1]);
@@ -576,9 +591,11 @@ V3 cast_ray_v2(PathCtx& c, Ray ray)
             uint32_t r[4];
             orc_draw(c.seed, c.pixel, c.k, depth, ORC_RNG_BOUNCE, 0, r);
             float RR = orc_uniform(r[0]);
+            log_draw(r[0]);
             if (RR > c.P_RR) {
                 done = true;
             } else {
+                log_draw(r[1]); log_draw(r[2]);
                 V3 reflect_dir = normalized(sample_hemisphere(hit.normal, orc_uniform(r[1]), orc_uniform(r[2])));
                 tmp = Ray(hit.pos, reflect_dir);
             }
@@ -643,11 +660,13 @@ V3 cast_ray_v2(PathCtx& c, Ray ray)
                     float d_phi = (float)(delta_coeff * 120 * M_PI / 180);
                     uint32_t r[4];
                     orc_draw(c.seed, c.pixel, c.k, depth, ORC_RNG_PROBE, 0, r);
+                    log_draw(r[0]); log_draw(r[1]);
                     V3 ref = normalized(sample_lobe(out, d_theta, d_phi, orc_uniform(r[0]), orc_uniform(r[1])));
                     Ray probe(to_hit.pos, ref);
                     tr.st.probe_rays++;
                     HitPayload hit = tr.intersect(probe.origin, probe.dir, probe.inv_dir);
                     if (hit.m.has_emit) {         /* :304 */
+                        if (g_draw_log) g_draw_log->flag.back() = 1;
                         float log_shininess = om_log10f(to_hit.m.ns);
                         float shininess_coeff = (float)(log_shininess * 0.5 + 1); /* :307 double */
                         float ip = (float)(2.0f * M_PI) / 8.f;                     /* :308 */
@@ -785,6 +804,27 @@ extern "C" uint64_t orc_ray_log_end(float* out, uint64_t cap_rays)
     return n;
 }
 
+/* diagnostic: see DrawLog.  orc_draw_log_end(NULL, ...) returns the number of words so far (and the number of paths in *n_paths) and keeps
+ * the log open; with buffers it copies words[<= cap_words], offsets[paths + 1] (the last one = the number of words), flags[paths],
+ * rays[paths][6] for at most cap_paths paths and closes the log. */
+extern "C" void orc_draw_log_begin(void) { delete g_draw_log; g_draw_log = new DrawLog(); }
+extern "C" uint64_t orc_draw_log_end(uint32_t* words, uint64_t cap_words, uint64_t* offsets, uint8_t* flags, float* rays, uint64_t cap_paths,
+                                     uint64_t* n_paths)
+{
+    if (!g_draw_log) { if (n_paths) *n_paths = 0; return 0; }
+    const uint64_t nw = g_draw_log->words.size(), np = g_draw_log->off.size();
+    if (n_paths) *n_paths = np;
+    if (!words) return nw;
+    std::memcpy(words, g_draw_log->words.data(), (size_t)std::min(nw, cap_words) * sizeof(uint32_t));
+    const uint64_t k = std::min(np, cap_paths);
+    if (offsets) { std::memcpy(offsets, g_draw_log->off.data(), (size_t)k * sizeof(uint64_t)); offsets[k] = k < np ? g_draw_log->off[k] : nw; }
+    if (flags) std::memcpy(flags, g_draw_log->flag.data(), (size_t)k);
+    if (rays) std::memcpy(rays, g_draw_log->ray.data(), (size_t)k * 6 * sizeof(float));
+    delete g_draw_log;
+    g_draw_log = nullptr;
+    return nw;
+}
+
 /* diagnostic: see g_margin_hist.  orc_margin_hist(NULL) starts (and zeroes) the histogram, orc_margin_hist(out26) copies and stops it */
 extern "C" void orc_margin_hist(uint64_t* out)
 {
@@ -813,6 +853,13 @@ int orc_render(const orc_scene* sc, const orc_camera* cam, const orc_params* p, 
                 float x = (2 * (i + orc_uniform(r[0])) / p->width - 1) * scale * ar; /* :344 */
                 float y = (1 - 2 * (j + orc_uniform(r[1])) / p->height) * scale;     /* :345 */
                 V3 dir = mat3_mul(cam->inv_view, normalized(v3(-x, y, 1)));          /* :346 */
+                if (g_draw_log) {
+                    g_draw_log->off.push_back(g_draw_log->words.size());
+                    g_draw_log->flag.push_back(0);
+                    const float rec[6] = {eye.x, eye.y, eye.z, dir.x, dir.y, dir.z};
+                    g_draw_log->ray.insert(g_draw_log->ray.end(), rec, rec + 6);
+                    log_draw(r[0]); log_draw(r[1]);
+                }
                 Ray ray(eye, dir);
                 PathCtx c{tr, *sc, p->seed, pixel_index, k, p->light_sample_n, p->p_rr};
                 tr.st.paths++;

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/oracle_kat.json: known answers produced by the CPU oracle itself
 (loader/BVH hashes, intersect / per-path / image KATs, traversal counters).  They pin the
-oracle against accidental change; they are NOT reference outputs (the reference cannot be
-built here, see oracle/crt_oracle.h)."""
+oracle against accidental change; they are NOT reference outputs (those are in
+tests/golden/reference_pin/, written by make_reference_golden.py)."""
 import hashlib
 import json
 import os

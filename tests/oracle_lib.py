@@ -98,6 +98,12 @@ def lib():
     L.orc_sample_hemisphere.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.orc_sample_lobe.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
     L.orc_tonemap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
+    L.orc_ray_log_begin.restype = None
+    L.orc_ray_log_end.restype = C.c_uint64
+    L.orc_ray_log_end.argtypes = [C.c_void_p, C.c_uint64]
+    L.orc_draw_log_begin.restype = None
+    L.orc_draw_log_end.restype = C.c_uint64
+    L.orc_draw_log_end.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     _lib = L
     return L
 
@@ -253,6 +259,38 @@ class OracleScene:
         st = OrcStats()
         lib().orc_intersect(self.h, n, _p(o), _p(d), _p(tri), _p(t), C.byref(st))
         return tri, t, st.as_dict()
+
+
+def ray_log_begin():
+    lib().orc_ray_log_begin()
+
+
+def ray_log_end():
+    """Every ray orc_render traced since ray_log_begin(): (n, 10) float32 -- origin, direction, hit t, hit triangle or -1,
+    visibility limit (NaN for a closest-hit ray), box-entry distance of the hit leaf."""
+    n = int(lib().orc_ray_log_end(None, 0))
+    log = np.zeros((n, 10), dtype=np.float32)
+    lib().orc_ray_log_end(_p(log), n)
+    return log
+
+
+def draw_log_begin():
+    lib().orc_draw_log_begin()
+
+
+def draw_log_end():
+    """What orc_render consumed since draw_log_begin(): the tape of raw 32-bit words in consumption order (the order of the
+    reference's sequential per-pixel stream), offsets (paths + 1) of each path's first word (its two jitters), one flag per
+    path ("took the emitter-probe branch", Render.cuh:304-313) and each path's camera ray as handed to Ray's constructor."""
+    npaths = C.c_uint64(0)
+    nw = int(lib().orc_draw_log_end(None, 0, None, None, None, 0, C.byref(npaths)))
+    n = int(npaths.value)
+    words = np.zeros(nw, dtype=np.uint32)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    flags = np.zeros(n, dtype=np.uint8)
+    rays = np.zeros((n, 6), dtype=np.float32)
+    lib().orc_draw_log_end(_p(words), nw, _p(off), _p(flags), _p(rays), n, None)
+    return {"words": words, "off": off, "flags": flags, "rays": rays}
 
 
 def inverse_view(eye, lookat, up):
