@@ -674,7 +674,7 @@ __global__ __launch_bounds__(64) void k_order_items(const LParams P, uint32_t* l
             bool valid; uint32_t pi, pj, pixel_index, k;
             decode_item<RING>(P, i, pixel_index, k, valid, pi, pj);
             exists |= 1u << j;
-            // the roulette of the first vertex, as logic_B draws it (Render.cuh:223-227)
+            // the roulette of the first vertex: must agree with roulette (crt_path.h) at depth 0, which logic_B calls (Render.cuh:223-227)
             if (valid && !(rng_uniform(rng_draw(P.seed, pixel_index, k, 0, RNG_BOUNCE, 0).x) > P.p_rr)) goes_on |= 1u << j;
         }
     }

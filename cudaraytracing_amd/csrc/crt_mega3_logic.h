@@ -106,37 +106,25 @@ __device__ __forceinline__ uint32_t route_complete(const uint32_t rec_flags, con
 }
 
 
-// Visibility of a next-event sample (Render.cuh:19-27, :272): tl - hit.t > EPSILON with hit.t = FLT_MAX when nothing was
-// hit.  An any-hit ray only ever records hits that satisfy the comparison, so its answer is "recorded a hit", plus the
-// reference's own quirk that an infinite limit minus FLT_MAX is still "blocked".
-template <int MODE>
-__device__ __forceinline__ bool shadow_blocked(float tl, float T, int tri)
-{
-    if (MODE != 1) return tri >= 0 || tl - FLT_MAX > CRT_EPSILON;
-    return tl - T > CRT_EPSILON;
-}
+#define ST_TL_INF (1u << 12) /* state word of the la plane, bits 12 .. 15 are free: the in-flight next-event ray's limit is +inf (shadow_blocked_bit) */
 
-
-// Backward recursion over k_mega3's vertex records, deepest first (Render.cuh:238-326; crt_path.h: finish_path is the wavefront pipeline's).
-// Round 6 layout: vertex j of a path that went ON from it has  rec_a[j] = (L_dir.xyz, bits(triangle-row word: material | flags)), written
-// by LB when the roulette lets the path continue, and  rec_b[j].w = cos to vertex j + 1, written when that vertex is found (rec_b[j].xyz,
-// the direction that arrived at j, is written for SPECULAR vertices only: nothing else reads it).  The deepest vertex has no record: its
-// L_dir arrives in the la plane (`have_ld`) when the path stopped there, is rec_a's when the ray that left it found nothing, and is not
-// needed when it is an emitter.  Against one 16-byte record store more per vertex and one per path that stops (round 5).
+// Backward recursion over k_mega3's vertex records, deepest first (Render.cuh:238-326; crt_path.h: finish_path is the wavefront pipeline's,
+// seed_emitter, seed_direct and indirect_step are both's).  Vertex j of a path that went ON from it has  rec_a[j] = (L_dir.xyz, bits(triangle-row word:
+// material | flags)), written by LB when the roulette lets the path continue, and  rec_b[j].w = cos to vertex j + 1, written when that
+// vertex is found (rec_b[j].xyz, the direction that arrived at j, is written for SPECULAR vertices only: nothing else reads it).  The
+// deepest vertex has no record: its L_dir arrives in the la plane (`have_ld`) when the path stopped there, is rec_a's when the ray that left
+// it found nothing, and is not needed when it is an emitter.  Against one 16-byte record store more per vertex and one per path that stops.
 __device__ __forceinline__ F3 finish_path_m3(const LParams& P, const Tables<false>& tb, const uint32_t slot, const int deepest, const bool emissive, const F3 ke,
                                             const bool have_ld, const F3 ld)
 {
     const Pool& pl = P.pool;
-    F3 L = f3(0.0f, 0.0f, 0.0f);
-    if (deepest < 0) return L;
-    const float inv_pdf_sphere = (float)(2.0f * 3.14159265358979323846); // Global.h:96-99
-    if (emissive) {
-        L = deepest == 0 ? add3(f3(0.0f, 0.0f, 0.0f), ke) : f3(0.0f, 0.0f, 0.0f); // :249-255, :323
-    } else if (have_ld) {
-        L = add3(f3(0.0f, 0.0f, 0.0f), ld); // final hit: direct light only (:316-319)
-    } else {
+    if (deepest < 0) return f3(0.0f, 0.0f, 0.0f);
+    F3 L;
+    if (emissive) L = seed_emitter(deepest, ke);
+    else if (have_ld) L = seed_direct(ld);
+    else {
         const float4 a = gld_rec(&pl.rec_a[(size_t)deepest * pl.n + slot]);
-        L = add3(f3(0.0f, 0.0f, 0.0f), f3(a.x, a.y, a.z));
+        L = seed_direct(f3(a.x, a.y, a.z));
     }
     // (the loads of CRT_FINISH_PF vertices are fetched together, as in finish_path)
     for (int v = deepest - 1; v >= 0; v -= CRT_FINISH_PF) {
@@ -152,22 +140,11 @@ __device__ __forceinline__ F3 finish_path_m3(const LParams& P, const Tables<fals
         for (int j = 0; j < CRT_FINISH_PF; j++) fm[j] = mat_row(tb, TNM_MAT(__float_as_uint(a[j].w)), 0);
 #pragma unroll
         for (int j = 0; j < CRT_FINISH_PF; j++) {
-            if (v - j >= 0) {
-                F3 ind = mul3(L, f3(fm[j].x, fm[j].y, fm[j].z)); // L (.) f_r * cos * inv_pdf / P_RR  (:293)
-                ind = scale3(ind, cs[j]);
-                ind = scale3(ind, inv_pdf_sphere);
-                ind = div3(ind, P.p_rr);
-                L = add3(ind, f3(a[j].x, a[j].y, a[j].z)); // :323
-            }
+            if (v - j >= 0) L = indirect_step(L, f3(fm[j].x, fm[j].y, fm[j].z), cs[j], P.p_rr, f3(a[j].x, a[j].y, a[j].z));
         }
     }
     return L;
 }
-
-
-// The same with the limit known only as "is +inf" (TRI_CC below): tl - FLT_MAX > EPSILON holds for tl = +inf alone (a finite tl gives <= 0, NaN fails)
-__device__ __forceinline__ bool shadow_blocked_bit(const bool tl_inf, const int tri) { return tri >= 0 || tl_inf; }
-#define ST_TL_INF (1u << 12) /* state word of the la plane, bits 12 .. 15 are free: the in-flight next-event ray's limit is +inf */
 
 
 // LA: consumes the result of a next-event sample that is not the last one of its vertex, of a closest-hit ray
@@ -245,19 +222,12 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
             // the previous vertex (vn: its triangle's row) is not the deepest one: cosine of its indirect term (Render.cuh:291)
             const size_t pr = (size_t)(s.depth - 1) * pl.n + g;
             const F3 pn = s.nrm;
-            float cos_prev = dot3(unit3(sub3(pos, s.ro)), pn); // prev.pos == origin of this ray
-            cos_prev = cos_prev > 0.0f ? cos_prev : 0.0f;
-            gst_rec(&pl.rec_b[pr].w, cos_prev); // (finish_path_m3: the cosine lives in rec_b.w, rec_a.w is the vertex's material)
+            const float cos_prev = cos_to_next(s.ro, pos, pn); // prev.pos == origin of this ray
+            gst_rec(&pl.rec_b[pr].w, cos_prev);
             if (TNM_SPECULAR(__float_as_uint(vn.w))) { // SPECULAR: emitter probe, Render.cuh:294-303
                 const float ns = mat_row(tb, s.mat, 0).w;
                 const float4 pb = gld_rec(&pl.rec_b[pr]); // direction that arrived at the previous vertex
-                const float delta_coeff = (float)((double)(det_expf(25 / ns) - 1) / (2.71828182845904523536 - 1));
-                const F3 in = unit3(f3(pb.x, pb.y, pb.z));
-                const F3 out = sub3(in, scale3(pn, 2.f * dot3(in, pn)));
-                const float d_theta = (float)((double)(delta_coeff * 30) * 3.14159265358979323846 / 180);
-                const float d_phi = (float)((double)(delta_coeff * 120) * 3.14159265358979323846 / 180);
-                const U4 rp = rng_draw(P.seed, s.pixel_index, s.k, s.depth - 1, RNG_PROBE, 0);
-                const F3 refd = unit3(sample_lobe(out, d_theta, d_phi, rng_uniform(rp.x), rng_uniform(rp.y)));
+                const F3 refd = probe_dir(P.seed, s.pixel_index, s.k, s.depth - 1, ns, f3(pb.x, pb.y, pb.z), pn);
                 // the probe leaves from prev.pos (= this ray's origin); the bounce direction waits in rec_b[depth]
                 gst_rec(&pl.rec_b[(size_t)s.depth * pl.n + g], make_float4(s.rd.x, s.rd.y, s.rd.z, 0.0f));
                 gst(&pl.vx[g], make_float4(pos.x, pos.y, pos.z, __int_as_float(res_tri)));
@@ -278,15 +248,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
                 const size_t pr = (size_t)(s.depth - 1) * pl.n + g;
                 const F3 pn = s.nrm;
                 const float4 pm0 = mat_row(tb, s.mat, 0), pm1 = mat_row(tb, s.mat, 1);
-                const float log_shininess = det_log10f(pm0.w);
-                const float shininess_coeff = (float)((double)log_shininess * 0.5 + 1);
-                const float ip = (float)(2.0f * 3.14159265358979323846) / 8.f;
-                const F3 hp = add3(s.ro, scalel3(res_t, s.rd));
-                float ct = dot3(unit3(sub3(hp, s.ro)), pn); // probe origin == prev.pos
-                ct = ct > 0.0f ? ct : 0.0f;
-                // shininess * (ke (.) kd) * cos * inv_pdf  (:311, eager)
-                const F3 kekd = mul3(f3(h2.x, h2.y, h2.z), f3(pm1.x, pm1.y, pm1.z));
-                const F3 temp = scale3(scale3(scalel3(shininess_coeff, kekd), ct), ip);
+                const F3 temp = probe_term(pn, f3(pm1.x, pm1.y, pm1.z), f3(h2.x, h2.y, h2.z), s.ro, s.rd, res_t, pm0.w); // the probe's origin is prev.pos
                 float4 a = gld_rec(&pl.rec_a[pr]);
                 a.x = a.x + temp.x; a.y = a.y + temp.y; a.z = a.z + temp.z;
                 gst_rec(&pl.rec_a[pr], a);
@@ -374,14 +336,8 @@ __device__ __forceinline__ uint32_t logic_B(const LParams& P, const uint32_t g, 
         const bool blocked = TRI_CC ? shadow_blocked_bit((st & ST_TL_INF) != 0u, __float_as_int(qb.w)) : shadow_blocked<MODE>(cc.w, qa.w, __float_as_int(qb.w));
         if (!blocked) Ld = add3(Ld, f3(cc.x, cc.y, cc.z));
     }
-    bool stop = depth == CRT_BOUNCE_STACK_SIZE - 1; // bounce stack full
     U4 rb;
-    rb.x = rb.y = rb.z = rb.w = 0;
-    if (!stop) {
-        rb = rng_draw(P.seed, idv.x, idv.y, depth, RNG_BOUNCE, 0);
-        stop = rng_uniform(rb.x) > P.p_rr;
-    }
-    if (stop) { // the deepest vertex: its L_dir goes to LC in the la plane, it has no record (finish_path_m3)
+    if (roulette(P.seed, idv.x, idv.y, depth, P.p_rr, rb)) { // the deepest vertex: its L_dir goes to LC in the la plane, it has no record (finish_path_m3)
         gst(&pl.la[g], make_float4(Ld.x, Ld.y, Ld.z, __uint_as_float(depth | ((uint32_t)ST_FIN << 8))));
         return PH3_LC;
     }
@@ -389,7 +345,7 @@ __device__ __forceinline__ uint32_t logic_B(const LParams& P, const uint32_t g, 
     const float4 vn = gld(&P.sc.tri_nm[TRI_CC ? __float_as_uint(cc.w) : idv.w]);
     const float4 vx = qa;
     gst_rec(&pl.rec_a[(size_t)depth * pl.n + g], make_float4(Ld.x, Ld.y, Ld.z, vn.w)); // the vertex's record: L_dir and its material (with the row's flag bits)
-    const F3 ndir = unit3(sample_hemisphere(f3(vn.x, vn.y, vn.z), rng_uniform(rb.y), rng_uniform(rb.z)));
+    const F3 ndir = bounce_dir(f3(vn.x, vn.y, vn.z), rb);
     // (leaving this store out -- the plane then still holds a state only LB consumes, which LA and LC can read as "the ray for vertex depth + 1
     // is in flight" -- was measured in round 6: C2 +0.4 %, veach-mis +0.3 %: LA's load of the line then misses the L2 the store had left it in)
     depth++;
@@ -465,7 +421,7 @@ __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb
                 first_ = false;
             }
             if (item == ITEM_NONE) item = RING ? grab_item_ring(P.item_next, P.items_per_shard, P.ring_shards, home_)
-                                               : grab_item(nullptr, P.item_next, P.items_per_shard, P.n_items, blockIdx.x & (ITEM_SHARDS - 1));
+                                               : grab_item(P.item_next, P.items_per_shard, P.n_items, blockIdx.x & (ITEM_SHARDS - 1));
             if (item == ITEM_NONE) return LC_DEAD;
             if (P.item_list) { // the tail of every cursor shard is handed out "paths that stop at their first vertex last" (k_order_items)
                 const uint32_t sh_ = fast_div(item, P.items_per_shard_div.m, P.items_per_shard_div.sh);
@@ -505,7 +461,7 @@ __device__ __forceinline__ bool query_C(const LParams& P, const uint32_t g, cons
     const float4 la = gld(&pl.la[g]);
     const uint4 idv = load_path_id(P, g);
     if (((__float_as_uint(la.w) >> 8) & 15u) != ST_NEW) gst(&P.L[idv.z], make_float4(qa.w, qb.w, 0.0f, 0.0f));
-    const uint32_t item = grab_item(nullptr, P.item_next, P.items_per_shard, P.n_items, blockIdx.x & (ITEM_SHARDS - 1));
+    const uint32_t item = grab_item(P.item_next, P.items_per_shard, P.n_items, blockIdx.x & (ITEM_SHARDS - 1));
     if (item == ITEM_NONE) return false;
     store_path_id(P, g, item);
     gst(&pl.la[g], make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)ST_HIT << 8)));

@@ -40,18 +40,20 @@ static_assert(ST_COUNT_ <= 16, "a stage is kept in 4 bits");
 enum { RAY_NONE = 0, RAY_CLOSEST = 1, RAY_SHADOW = 2 };
 #define ITEM_NONE 0xffffffffu
 
-// Path pool, structure of arrays; every plane has `n` entries.
+// Path pool, structure of arrays; every plane has `n` entries.  Where the two pipelines keep different things in a plane, "W:" is the wavefront
+// pipeline (read by k_logic, crt_wavefront.hip) and "M:" is k_mega3 (logic_A / logic_B / logic_C, crt_mega3_logic.h).
 struct Pool {
-    float4* ro;   // ray origin.xyz, t_limit (shadow rays: Render.cuh:272)
-    float4* rd;   // ray direction.xyz (normalised as Ray does), bits(ray kind)
-    float4* vx;   // current vertex position.xyz, bits(triangle) (k_mega3, round 6: only the vertex that waits for a SPECULAR probe's result)
-    float4* la;   // next-event accumulator L_dir.xyz of the current vertex, bits(depth | stage << 8 | sample << 16)
-    float4* cc;   // contribution of the in-flight shadow ray .xyz, distance to the light sample (k_mega3 but for REFERENCE: bits(the vertex's triangle))
-    float4* vn;   // normal.xyz and bits(material) of the current vertex (of the PREVIOUS vertex while a bounce ray is in flight)
-    uint4* id;    // pixel index, sample index, work item, unused -- written once per path (k_mega3: the work item alone, 4 B; REFERENCE: + triangle, 8 B)
-    float2* res;  // result of the slot's last ray: t, bits(triangle or -1)
-    float4* rec_a; // [depth][n]: L_dir.xyz of that vertex, cos to the next vertex                (k_mega3: L_dir.xyz, bits(material word) -- finish_path_m3)
-    float4* rec_b; // [depth][n]: incoming direction.xyz, bits(material)                           (k_mega3: direction of SPECULAR vertices only, cos to the next vertex)
+    float4* ro;   // W: ray origin.xyz, t_limit (shadow rays: Render.cuh:272); so are the query rays of crt_intersect and the AOV pass.  M: unused (a path's ray lives in the LDS record; query rays arrive as LParams::q_o / q_d)
+    float4* rd;   // W: ray direction.xyz (normalised as Ray does), bits(ray kind).  M: as ro
+    float4* vx;   // W: current vertex position.xyz, bits(triangle).  M: the same, only for the vertex that waits for a SPECULAR probe's result
+    float4* la;   // next-event accumulator L_dir.xyz of the current vertex, bits(depth | stage << 8 | sample << 16 [M: | ST_TL_INF])
+    float4* cc;   // contribution of the in-flight shadow ray .xyz; .w  W: unused,  M: bits(the vertex's triangle) (REFERENCE: the ray's t_limit)
+    float4* vn;   // W: normal.xyz, bits(material) of the current vertex (of the PREVIOUS one while a bounce ray is in flight).  M: unused (both come from the triangle's row of tri_nm)
+    uint4* id;    // W: pixel index, sample index, work item, unused.  M: the work item alone, 4 B (REFERENCE: + triangle, 8 B): load_path_id
+    float2* res;  // W: result of the slot's last ray: t, bits(triangle or -1).  M: unused
+    float4* rec_a; // [depth][n]  W: L_dir.xyz of that vertex, cos to the next vertex.  M: L_dir.xyz, bits(triangle-row word: material | flags)
+    float4* rec_b; // [depth][n]  W: incoming direction.xyz, bits(material).  M: direction of SPECULAR vertices only, cos to the next vertex
+                   // (the records are written when a vertex is entered / left and read back once: W by finish_path, M by finish_path_m3)
     uint32_t n;
 };
 
@@ -148,8 +150,7 @@ __device__ __forceinline__ void gst_rec(float* p, const float v) { gst(p, v); }
 
 // Takes the next work item for every lane that is active here with ONE atomic per wave and
 // shard (ballot of the active lanes, the first one adds their count, prefix rank per lane).
-__device__ __forceinline__ uint32_t grab_item(const unsigned int* /*unused*/, unsigned int* item_next, uint32_t per, uint32_t n_items,
-                                              uint32_t home)
+__device__ __forceinline__ uint32_t grab_item(unsigned int* item_next, uint32_t per, uint32_t n_items, uint32_t home)
 {
     const int lane = threadIdx.x & 63;
     uint32_t item = ITEM_NONE;
@@ -204,6 +205,8 @@ __device__ __forceinline__ uint32_t grab_item_ring(unsigned int* item_next, cons
 }
 
 // ---------------------------------------------------------------- logic ----
+#define CRT_FINISH_PF 4 /* vertex records that finish_path fetches together */
+
 struct PathCounters {
     uint32_t rays, shadow, probe, paths;
     uint32_t untraced; // next-event samples answered without traversal (contribution exactly zero); counted in rays / shadow too
@@ -463,24 +466,104 @@ __device__ __forceinline__ void store_path_tri(const LParams& P, const uint32_t 
     *(CRT_GAS uint32_t*)((uint32_t*)((uint2*)P.pool.id + g) + 1) = tri;
 }
 
-// Backward recursion over the vertex records, deepest first: Render.cuh:238-326.
+// ---- the reference's per-vertex formulas (Render.cuh:199-326), once for both pipelines: functions of values, in the reference's float
+// order; where the operands are kept and when they are loaded is the business of k_logic (crt_wavefront.hip) and of logic_A / logic_B
+// (crt_mega3_logic.h) ----
+
+// blocked() (Render.cuh:19-27, :272): tl - hit.t > EPSILON with hit.t = FLT_MAX when nothing was hit.  REFERENCE (MODE 1) answers the ray
+// with the closest-hit query and compares its distance T.  An any-hit ray only ever records hits that satisfy the comparison, so its answer
+// is "recorded a hit", plus the reference's own quirk that an infinite limit minus FLT_MAX is still "blocked".
+template <int MODE>
+__host__ __device__ __forceinline__ bool shadow_blocked(float tl, float T, int tri)
+{
+    if (MODE != 1) return tri >= 0 || tl - FLT_MAX > CRT_EPSILON;
+    return tl - T > CRT_EPSILON;
+}
+// The any-hit form with the limit known only as "is +inf": tl - FLT_MAX > EPSILON holds for tl = +inf alone (a finite tl gives <= 0, NaN fails)
+__device__ __forceinline__ bool shadow_blocked_bit(const bool tl_inf, const int tri) { return tri >= 0 || tl_inf; }
+
+// Cosine of a vertex's indirect term, clamped (Render.cuh:291): the vertex at `from` with normal n, the next one at `to`.
+__device__ __forceinline__ float cos_to_next(const F3 from, const F3 to, const F3 n)
+{
+    const float c = dot3(unit3(sub3(to, from)), n);
+    return c > 0.0f ? c : 0.0f;
+}
+
+// Direction of a SPECULAR vertex's emitter probe (Render.cuh:294-303): the vertex `depth` with normal n and shininess ns, reached along
+// `arrived`.  The caller makes the ray's unit direction of it with unit3 (Ray.cuh:13).
+__device__ __forceinline__ F3 probe_dir(const uint64_t seed, const uint32_t pixel_index, const uint32_t k, const uint32_t depth, const float ns, const F3 arrived,
+                                        const F3 n)
+{
+    const float delta_coeff = (float)((double)(det_expf(25 / ns) - 1) / (2.71828182845904523536 - 1));
+    const F3 in = unit3(arrived);
+    const F3 out = sub3(in, scale3(n, 2.f * dot3(in, n)));
+    const float d_theta = (float)((double)(delta_coeff * 30) * 3.14159265358979323846 / 180);
+    const float d_phi = (float)((double)(delta_coeff * 120) * 3.14159265358979323846 / 180);
+    const U4 rp = rng_draw(seed, pixel_index, k, depth, RNG_PROBE, 0);
+    return unit3(sample_lobe(out, d_theta, d_phi, rng_uniform(rp.x), rng_uniform(rp.y)));
+}
+
+// What a probe that found an emitter (ke) adds to the L_dir of the vertex it left (at o, normal n, shininess ns, diffuse kd) along d, at
+// distance t: shininess * (ke (.) kd) * cos * inv_pdf, evaluated eagerly (Render.cuh:304-313).
+// (The order of the parameters is one that leaves k_mega3's instruction streams what they were with the formula written out in logic_A;
+// most orders move one v_mov_b32 of the default kernel: docs/experiments.md.)
+__device__ __forceinline__ F3 probe_term(const F3 n, const F3 kd, const F3 ke, const F3 o, const F3 d, const float t, const float ns)
+{
+    const float log_shininess = det_log10f(ns);
+    const float shininess_coeff = (float)((double)log_shininess * 0.5 + 1);
+    const float ip = (float)(2.0f * 3.14159265358979323846) / 8.f;
+    const F3 hit = add3(o, scalel3(t, d)); // DeviceTriangle.cuh:50
+    const float ct = cos_to_next(o, hit, n);
+    const F3 kekd = mul3(ke, kd);
+    return scale3(scale3(scalel3(shininess_coeff, kekd), ct), ip);
+}
+
+// Russian roulette at vertex `depth` (Render.cuh:210-213): true = the path stops here (bounce stack full, or the draw says so).  rb is the
+// vertex's RNG_BOUNCE draw, whose y and z choose the bounce direction; all zero when the stack is full and nothing is drawn.
+__device__ __forceinline__ bool roulette(const uint64_t seed, const uint32_t pixel_index, const uint32_t k, const uint32_t depth, const float p_rr, U4& rb)
+{
+    bool stop = depth == CRT_BOUNCE_STACK_SIZE - 1; // bounce stack full
+    rb.x = rb.y = rb.z = rb.w = 0;
+    if (!stop) {
+        rb = rng_draw(seed, pixel_index, k, depth, RNG_BOUNCE, 0);
+        stop = rng_uniform(rb.x) > p_rr;
+    }
+    return stop;
+}
+// The bounce off a vertex with normal n (Render.cuh:214-228); the caller makes the ray's unit direction of it with unit3 (Ray.cuh:13).
+__device__ __forceinline__ F3 bounce_dir(const F3 n, const U4 rb) { return unit3(sample_hemisphere(n, rng_uniform(rb.y), rng_uniform(rb.z))); }
+
+// One step of the backward recursion: L of a vertex from the L of the next one (Render.cuh:293, :323).
+__device__ __forceinline__ F3 indirect_step(const F3 L, const F3 f_r, const float cos_next, const float p_rr, const F3 L_dir)
+{
+    const float inv_pdf_sphere = (float)(2.0f * 3.14159265358979323846); // Global.h:96-99
+    F3 ind = mul3(L, f_r); // L (.) f_r * cos * inv_pdf / P_RR  (:293)
+    ind = scale3(ind, cos_next);
+    ind = scale3(ind, inv_pdf_sphere);
+    ind = div3(ind, p_rr);
+    return add3(ind, L_dir); // :323
+}
+
+// L of a path's deepest vertex, where the backward recursion starts.  An emitter: its ke if the camera sees it, nothing if a bounce found it
+// (Render.cuh:249-255, :323).  Any other vertex: its direct light alone (:316-319).
+__device__ __forceinline__ F3 seed_emitter(const int deepest, const F3 ke) { return deepest == 0 ? add3(f3(0.0f, 0.0f, 0.0f), ke) : f3(0.0f, 0.0f, 0.0f); }
+__device__ __forceinline__ F3 seed_direct(const F3 l_dir) { return add3(f3(0.0f, 0.0f, 0.0f), l_dir); }
+
+// Backward recursion over the wavefront pipeline's vertex records, deepest first (Render.cuh:238-326): rec_a = (L_dir.xyz, cos to the next
+// vertex), rec_b.w = bits(material).  (k_mega3 keeps other records: finish_path_m3, crt_mega3_logic.h.)
+// The recursion is a serial chain, but its loads are not: the records (and material rows) of CRT_FINISH_PF vertices are fetched together,
+// so a chunk costs two memory round trips instead of two per vertex (lanes with fewer vertices re-read vertex 0 and skip the arithmetic).
 template <bool LDS_TABLES>
 __device__ __forceinline__ F3 finish_path(const LParams& P, const Tables<LDS_TABLES>& tb, uint32_t slot, int deepest, bool emissive, F3 ke)
 {
     const Pool& pl = P.pool;
-    F3 L = f3(0.0f, 0.0f, 0.0f);
-    if (deepest < 0) return L;
-    const float inv_pdf_sphere = (float)(2.0f * 3.14159265358979323846); // Global.h:96-99
-    if (emissive) {
-        L = deepest == 0 ? add3(f3(0.0f, 0.0f, 0.0f), ke) : f3(0.0f, 0.0f, 0.0f); // :249-255, :323
-    } else {
-        float4 a = gld_rec(&pl.rec_a[(size_t)deepest * pl.n + slot]);
-        L = add3(f3(0.0f, 0.0f, 0.0f), f3(a.x, a.y, a.z)); // final hit: direct light only (:316-319)
+    if (deepest < 0) return f3(0.0f, 0.0f, 0.0f);
+    F3 L;
+    if (emissive) L = seed_emitter(deepest, ke);
+    else {
+        const float4 a = gld_rec(&pl.rec_a[(size_t)deepest * pl.n + slot]);
+        L = seed_direct(f3(a.x, a.y, a.z));
     }
-    // The recursion is a serial chain, but its loads are not: the records (and material rows) of CRT_FINISH_PF vertices are
-    // fetched together, so a chunk costs two memory round trips instead of two per vertex (lanes with fewer vertices re-read
-    // vertex 0 and skip the arithmetic).
-#define CRT_FINISH_PF 4
     for (int v = deepest - 1; v >= 0; v -= CRT_FINISH_PF) {
         float4 a[CRT_FINISH_PF], fm[CRT_FINISH_PF];
         uint32_t mat[CRT_FINISH_PF];
@@ -494,13 +577,7 @@ __device__ __forceinline__ F3 finish_path(const LParams& P, const Tables<LDS_TAB
         for (int j = 0; j < CRT_FINISH_PF; j++) fm[j] = mat_row(tb, mat[j], 0);
 #pragma unroll
         for (int j = 0; j < CRT_FINISH_PF; j++) {
-            if (v - j >= 0) {
-                F3 ind = mul3(L, f3(fm[j].x, fm[j].y, fm[j].z)); // L (.) f_r * cos * inv_pdf / P_RR  (:293)
-                ind = scale3(ind, a[j].w);
-                ind = scale3(ind, inv_pdf_sphere);
-                ind = div3(ind, P.p_rr);
-                L = add3(ind, f3(a[j].x, a[j].y, a[j].z)); // :323
-            }
+            if (v - j >= 0) L = indirect_step(L, f3(fm[j].x, fm[j].y, fm[j].z), a[j].w, P.p_rr, f3(a[j].x, a[j].y, a[j].z));
         }
     }
     return L;

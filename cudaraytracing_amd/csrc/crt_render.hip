@@ -1084,13 +1084,12 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
         DevBuf<float> o, d, lim;
         o.upload(origins, n * 3ull); d.upload(dirs, n * 3ull);
         if (any_hit) lim.upload(out_t, n);
-        // blocked() of Render.cuh:19-27 from a finished visibility ray (limit = out_t[i] on entry): REFERENCE compares the closest
-        // hit, FAST recorded a hit only if it passes the comparison (shadow_blocked)
+        // blocked() of Render.cuh:19-27 from a finished visibility ray (limit = out_t[i] on entry): shadow_blocked (crt_path.h)
         const bool reference_mode = traversal == CRT_TRAVERSAL_REFERENCE;
         auto answer = [&](uint32_t i, float T, int32_t tri) {
             if (!any_hit) { out_t[i] = T; out_tri[i] = tri; return; }
             const float tl = out_t[i];
-            const bool blocked = reference_mode ? (tl - T > CRT_EPSILON) : (tri >= 0 || tl - FLT_MAX > CRT_EPSILON);
+            const bool blocked = reference_mode ? shadow_blocked<1>(tl, T, tri) : shadow_blocked<0>(tl, T, tri);
             out_t[i] = blocked ? 1.0f : 0.0f;
             out_tri[i] = blocked ? tri : -1;
         };

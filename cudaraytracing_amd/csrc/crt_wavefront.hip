@@ -21,8 +21,9 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
 
     // ---- phase 1: consume the result of the slot's last ray ----
     if (stage == ST_SHADOW) {
-        // visibility of next-event sample q (Render.cuh:19-27, :272-284)
-        bool blocked = s.tl - res_t > CRT_EPSILON;
+        // visibility of next-event sample q (Render.cuh:19-27, :272-284).  The limit against the distance k_trace answered with: the closest
+        // hit's, or -- any-hit rays -- that of a hit that passes the comparison, else FLT_MAX
+        bool blocked = shadow_blocked<1>(s.tl, res_t, res_tri);
         if (!blocked) s.Ld = add3(s.Ld, s.c);
         s.q++;
         if (s.q < (uint32_t)(sc.n_lights * P.lsn)) do_shadow_setup = true; else do_nee_done = true;
@@ -39,20 +40,12 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
                 // cosine of its indirect term (Render.cuh:291)
                 const size_t pr = (size_t)(s.depth - 1) * pl.n + slot;
                 F3 pn = s.nrm;
-                float cos_prev = dot3(unit3(sub3(pos, s.ro)), pn); // prev.pos == origin of this ray
-                cos_prev = cos_prev > 0.0f ? cos_prev : 0.0f;
-                pl.rec_a[pr].w = cos_prev;
+                pl.rec_a[pr].w = cos_to_next(s.ro, pos, pn); // prev.pos == origin of this ray
                 float4 pm1 = mat_row(tb, s.mat, 1);
                 if (__float_as_uint(pm1.w) & 2u) { // SPECULAR: emitter probe, Render.cuh:294-303
                     float ns = mat_row(tb, s.mat, 0).w;
                     float4 pb = pl.rec_b[pr]; // direction that arrived at the previous vertex
-                    float delta_coeff = (float)((double)(det_expf(25 / ns) - 1) / (2.71828182845904523536 - 1));
-                    F3 in = unit3(f3(pb.x, pb.y, pb.z));
-                    F3 out = sub3(in, scale3(pn, 2.f * dot3(in, pn)));
-                    float d_theta = (float)((double)(delta_coeff * 30) * 3.14159265358979323846 / 180);
-                    float d_phi = (float)((double)(delta_coeff * 120) * 3.14159265358979323846 / 180);
-                    U4 rp = rng_draw(P.seed, s.pixel_index, s.k, s.depth - 1, RNG_PROBE, 0);
-                    F3 refd = unit3(sample_lobe(out, d_theta, d_phi, rng_uniform(rp.x), rng_uniform(rp.y)));
+                    F3 refd = probe_dir(P.seed, s.pixel_index, s.k, s.depth - 1, ns, f3(pb.x, pb.y, pb.z), pn);
                     // the probe leaves from prev.pos (= this ray's origin); keep the bounce direction for rec_b
                     pl.rec_b[(size_t)s.depth * pl.n + slot] = make_float4(s.rd.x, s.rd.y, s.rd.z, 0.0f);
                     s.rd = unit3(refd); // Ray.cuh:13
@@ -75,15 +68,7 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
                 const size_t pr = (size_t)(s.depth - 1) * pl.n + slot;
                 F3 pn = s.nrm;
                 float4 pm0 = mat_row(tb, s.mat, 0), pm1 = mat_row(tb, s.mat, 1);
-                float log_shininess = det_log10f(pm0.w);
-                float shininess_coeff = (float)((double)log_shininess * 0.5 + 1);
-                float ip = (float)(2.0f * 3.14159265358979323846) / 8.f;
-                F3 hp = add3(s.ro, scalel3(res_t, s.rd));
-                float ct = dot3(unit3(sub3(hp, s.ro)), pn); // probe origin == prev.pos
-                ct = ct > 0.0f ? ct : 0.0f;
-                // shininess * (ke (.) kd) * cos * inv_pdf  (:311, eager)
-                F3 kekd = mul3(f3(q2.x, q2.y, q2.z), f3(pm1.x, pm1.y, pm1.z));
-                F3 temp = scale3(scale3(scalel3(shininess_coeff, kekd), ct), ip);
+                F3 temp = probe_term(pn, f3(pm1.x, pm1.y, pm1.z), f3(q2.x, q2.y, q2.z), s.ro, s.rd, res_t, pm0.w); // the probe's origin is prev.pos
                 float4 a = pl.rec_a[pr];
                 a.x = a.x + temp.x; a.y = a.y + temp.y; a.z = a.z + temp.z;
                 pl.rec_a[pr] = a;
@@ -121,18 +106,12 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
     // ---- phase 3: direct light of vertex `depth` is complete: Russian roulette and bounce (Render.cuh:210-228) ----
     if (do_nee_done) {
         pl.rec_a[(size_t)s.depth * pl.n + slot] = make_float4(s.Ld.x, s.Ld.y, s.Ld.z, 0.0f);
-        bool stop = s.depth == CRT_BOUNCE_STACK_SIZE - 1; // bounce stack full
         U4 rb;
-        rb.x = rb.y = rb.z = rb.w = 0;
-        if (!stop) {
-            rb = rng_draw(P.seed, s.pixel_index, s.k, s.depth, RNG_BOUNCE, 0);
-            stop = rng_uniform(rb.x) > P.p_rr;
-        }
-        if (stop) {
+        if (roulette(P.seed, s.pixel_index, s.k, s.depth, P.p_rr, rb)) {
             fin_deepest = (int)s.depth; fin_emissive = false;
             do_finish = true;
         } else {
-            F3 ndir = unit3(sample_hemisphere(s.nrm, rng_uniform(rb.y), rng_uniform(rb.z)));
+            F3 ndir = bounce_dir(s.nrm, rb);
             s.ro = s.pos;
             s.rd = unit3(ndir); // Ray.cuh:13
             s.tl = 0.0f; s.kind = RAY_CLOSEST;
@@ -154,7 +133,7 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
     if (do_new) {
         s.stage = ST_DEAD;
         for (;;) {
-            s.item = grab_item(nullptr, P.item_next, P.items_per_shard, P.n_items, (blockIdx.x * 4u + (threadIdx.x >> 6)) & (ITEM_SHARDS - 1));
+            s.item = grab_item(P.item_next, P.items_per_shard, P.n_items, (blockIdx.x * 4u + (threadIdx.x >> 6)) & (ITEM_SHARDS - 1));
             if (s.item == ITEM_NONE) break;
             bool valid; uint32_t pi, pj;
             decode_item(P, s.item, s.pixel_index, s.k, valid, pi, pj);
@@ -441,7 +420,8 @@ __device__ __forceinline__ int trav_begin(const DevScene& sc, TravLane& L, uint3
     L.sp = 0;
     // rays with a zero / denormal direction component (inv_dir not finite) can put NaNs into the
     // slab test; they walk the reference topology, whose box tests are the reference's own (crt_accel.h)
-    // (the same predicate as k_mega3's start_ray: a non-finite ORIGIN puts NaNs into the min / max form of the slab test too)
+    // (a non-finite ORIGIN puts NaNs into the min / max form of the slab test too.  This test asks that every component of 1/d, o and d is
+    // finite; k_mega3's start_ray asks more, a bound on the plane distances: (coord_max + max |o|) * max |1/d| <= 2^126, and a finite d.)
     const bool finite_inv = absf(L.r.inv.x) <= FLT_MAX && absf(L.r.inv.y) <= FLT_MAX && absf(L.r.inv.z) <= FLT_MAX;
     const bool finite_o = absf(L.r.o.x) <= FLT_MAX && absf(L.r.o.y) <= FLT_MAX && absf(L.r.o.z) <= FLT_MAX;
     const bool finite_d = absf(L.r.d.x) <= FLT_MAX && absf(L.r.d.y) <= FLT_MAX && absf(L.r.d.z) <= FLT_MAX; // (1/d != 0)
@@ -579,26 +559,18 @@ void launch_logic(bool lds_tables, uint32_t blocks, hipStream_t st, const LParam
     if (lds_tables) hipLaunchKernelGGL(k_logic<true>, dim3(blocks), dim3(256), 0, st, P);
     else hipLaunchKernelGGL(k_logic<false>, dim3(blocks), dim3(256), 0, st, P);
 }
-template <int MODE, bool STATS> static int blocks_per_cu_(size_t lds)
-{
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace<MODE, STATS>, 256, lds) != hipSuccess || nb < 1) nb = 1;
-    return nb;
-}
-// mode_id = (REFERENCE ? 2 : EXACT ? 4 : 0) + (counters ? 1 : 0)
+// the six k_trace instantiations, by mode_id = (REFERENCE ? 2 : EXACT ? 4 : 0) + (counters ? 1 : 0)
+typedef void (*TraceKernel)(const TParams);
+static TraceKernel const TRACE_KERNELS[6] = {k_trace<0, false>, k_trace<0, true>, k_trace<1, false>, k_trace<1, true>, k_trace<2, false>, k_trace<2, true>};
 int trace_blocks_per_cu(int mode_id, size_t lds)
 {
-    return mode_id == 5 ? blocks_per_cu_<2, true>(lds) : mode_id == 4 ? blocks_per_cu_<2, false>(lds) : mode_id == 3 ? blocks_per_cu_<1, true>(lds)
-         : mode_id == 2 ? blocks_per_cu_<1, false>(lds) : mode_id == 1 ? blocks_per_cu_<0, true>(lds) : blocks_per_cu_<0, false>(lds);
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, TRACE_KERNELS[mode_id], 256, lds) != hipSuccess || nb < 1) nb = 1;
+    return nb;
 }
 void launch_trace(int mode_id, const TParams& T, uint32_t blocks, size_t lds, hipStream_t st)
 {
-    if (mode_id == 5) hipLaunchKernelGGL((k_trace<2, true>), dim3(blocks), dim3(256), lds, st, T);
-    else if (mode_id == 4) hipLaunchKernelGGL((k_trace<2, false>), dim3(blocks), dim3(256), lds, st, T);
-    else if (mode_id == 3) hipLaunchKernelGGL((k_trace<1, true>), dim3(blocks), dim3(256), lds, st, T);
-    else if (mode_id == 2) hipLaunchKernelGGL((k_trace<1, false>), dim3(blocks), dim3(256), lds, st, T);
-    else if (mode_id == 1) hipLaunchKernelGGL((k_trace<0, true>), dim3(blocks), dim3(256), lds, st, T);
-    else hipLaunchKernelGGL((k_trace<0, false>), dim3(blocks), dim3(256), lds, st, T);
+    hipLaunchKernelGGL(TRACE_KERNELS[mode_id], dim3(blocks), dim3(256), lds, st, T);
 }
 
 } // namespace crtk
