@@ -144,7 +144,7 @@ struct AParams : SlotMap {
     uint32_t spp;
     uint32_t chunk_samples;
     uint32_t first_chunk, last_chunk;
-    const float4* L;
+    const Rad3* L;     // the chunk's radiance, 12 bytes per work item: L[sample of the chunk * nslots + slot]
     float* accum;      // 3 planes of nslots (running sum across chunks)
     uint8_t* out_rgb;
     float* out_mean;   // may be null
@@ -165,22 +165,24 @@ __device__ __forceinline__ void acc_store3(float* planes, const uint32_t nslots,
 
 // The chunk's samples of a slot into its sums, in sample order: c = c + L / spp (Render.cuh:348); VAR (CRT_FLAG_VARIANCE, adaptive
 // passes): also the sum of squares q = q + x * x of the same quotients x.  Without VAR q is not touched.
-// (agent-scope loads: the radiance was written by the launch before this one, from other XCDs -- the same kind of hand-off as
-// k_order_items -> k_mega3, whose plain loads were seen to return what an earlier kernel had left at the address, docs/experiments.md 6)
+// The radiance is read with ONE plain 12-byte load per sample: the launch that wrote it has ended, and a kernel boundary makes its stores
+// visible (docs/experiments.md 6.14; the three 4-byte agent-scope loads per sample that stood here since round 5 cost more than a quarter
+// of k_accumulate).  The sums keep their agent scope: launches with the commit ring write them from inside the launch.
 template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& A, const uint32_t slot, F3& c, F3& q)
 {
     const float fspp = (float)A.spp;
-    for (uint32_t s = 0; s < A.chunk_samples; s++) {
-        const float* lp = (const float*)&A.L[(uint64_t)s * A.nslots + slot];
-        const float lx = acc_load(lp), ly = acc_load(lp + 1), lz = acc_load(lp + 2);
+    const Rad3* lp = A.L + slot;
+#pragma unroll 4
+    for (uint32_t s = 0; s < A.chunk_samples; s++, lp += A.nslots) {
+        const Rad3 l = load_radiance(lp);
         if (VAR) {
-            const float xx = lx / fspp, xy = ly / fspp, xz = lz / fspp;
+            const float xx = l.x / fspp, xy = l.y / fspp, xz = l.z / fspp;
             c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
             q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz;
         } else {
-            c.x = c.x + lx / fspp;
-            c.y = c.y + ly / fspp;
-            c.z = c.z + lz / fspp;
+            c.x = c.x + l.x / fspp;
+            c.y = c.y + l.y / fspp;
+            c.z = c.z + l.z / fspp;
         }
     }
 }
@@ -241,7 +243,7 @@ struct AovParams : SlotMap {
     uint32_t first_chunk, last_chunk;
     Pool pool;               // k_aov_rays: the query pool (ro, rd, res)
     const float* res;        // k_aov_resolve: (t, bits(triangle or -1)) of item i at res[i * res_stride]
-    uint32_t res_stride;     // floats per item: 4 (k_mega3 query form, L) or 2 (k_trace, the pool's res plane)
+    uint32_t res_stride;     // floats per item: 4 (k_mega3 query form, its float4 answers) or 2 (k_trace, the pool's res plane)
     const float4* tri_nm;    // scene: normal.xyz, bits(material word) per triangle
     const float4* mats;      // scene: 3 rows per material, row 1 = kd.xyz
     float4* acc;             // [nslots][3] running sums across chunks: (albedo.xyz, depth), (normal.xyz, bits(hits)), (bits(tri_0), bits(m_0), -, -)

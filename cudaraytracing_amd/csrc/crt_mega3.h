@@ -175,7 +175,7 @@ struct MParams3 {
     int32_t dbg_loads, dbg_valu; // unused by the kernel; tools/bbprof passes the address of its counter buffer in these two dwords
 };
 
-static_assert(offsetof(MParams3, dbg_loads) == 748 && offsetof(MParams3, dbg_valu) == 752, "tools/bbprof/instrument.py reads the counter buffer's address from these two kernel-argument dwords");
+static_assert(offsetof(MParams3, dbg_loads) == 756 && offsetof(MParams3, dbg_valu) == 760, "tools/bbprof/instrument.py reads the counter buffer's address from these two kernel-argument dwords");
 
 
 // ---- exported by crt_mega3.hip ----

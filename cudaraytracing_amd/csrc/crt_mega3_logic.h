@@ -110,7 +110,7 @@ __device__ __forceinline__ uint32_t route_complete(const uint32_t rec_flags, con
 
 // Backward recursion over k_mega3's vertex records, deepest first (Render.cuh:238-326; crt_path.h: finish_path is the wavefront pipeline's,
 // seed_emitter, seed_direct and indirect_step are both's).  Vertex j of a path that went ON from it has  rec_a[j] = (L_dir.xyz, bits(triangle-row word:
-// material | flags)), written by LB when the roulette lets the path continue, and  rec_b[j].w = cos to vertex j + 1, written when that
+// material | flags)), written by LB when the roulette lets the path continue, and  rec_c[j] = cos to vertex j + 1, written when that
 // vertex is found (rec_b[j].xyz, the direction that arrived at j, is written for SPECULAR vertices only: nothing else reads it).  The
 // deepest vertex has no record: its L_dir arrives in the la plane (`have_ld`) when the path stopped there, is rec_a's when the ray that left
 // it found nothing, and is not needed when it is an emitter.  Against one 16-byte record store more per vertex and one per path that stops.
@@ -134,7 +134,7 @@ __device__ __forceinline__ F3 finish_path_m3(const LParams& P, const Tables<fals
         for (int j = 0; j < CRT_FINISH_PF; j++) {
             const int vj = v - j > 0 ? v - j : 0;
             a[j] = gld_rec(&pl.rec_a[(size_t)vj * pl.n + slot]);
-            cs[j] = __uint_as_float(gld((const uint32_t*)&pl.rec_b[(size_t)vj * pl.n + slot].w));
+            cs[j] = gld(&pl.rec_c[(size_t)vj * pl.n + slot]);
         }
 #pragma unroll
         for (int j = 0; j < CRT_FINISH_PF; j++) fm[j] = mat_row(tb, TNM_MAT(__float_as_uint(a[j].w)), 0);
@@ -223,7 +223,7 @@ __device__ __forceinline__ uint32_t logic_A(const LParams& P, const Tables<false
             const size_t pr = (size_t)(s.depth - 1) * pl.n + g;
             const F3 pn = s.nrm;
             const float cos_prev = cos_to_next(s.ro, pos, pn); // prev.pos == origin of this ray
-            gst_rec(&pl.rec_b[pr].w, cos_prev);
+            gst_rec(&pl.rec_c[pr], cos_prev);
             if (TNM_SPECULAR(__float_as_uint(vn.w))) { // SPECULAR: emitter probe, Render.cuh:294-303
                 const float ns = mat_row(tb, s.mat, 0).w;
                 const float4 pb = gld_rec(&pl.rec_b[pr]); // direction that arrived at the previous vertex
@@ -398,16 +398,12 @@ __device__ __forceinline__ int logic_C(const LParams& P, const Tables<false>& tb
         if (ring) {
             const uint32_t sh = fast_div(idv.z, P.items_per_shard_div.m, P.items_per_shard_div.sh), c = idv.z - sh * P.items_per_shard;
             const uint32_t s = fast_div(c, P.spsh_div.m, P.spsh_div.sh), rs = s & P.ring_mask;
-            float4* Lr = P.L + (size_t)rs * P.ring_stride + (size_t)sh * P.spsh + (c - s * P.spsh);
-            ring_store16(Lr, L.x, L.y, L.z);
+            Rad3* Lr = P.L + (size_t)rs * P.ring_stride + (size_t)sh * P.spsh + (c - s * P.spsh);
+            ring_store12(Lr, L.x, L.y, L.z);
             fin_key = (sh << 16) | rs;
         } else {
-            // written once, read once by k_accumulate after the launch: a streaming store keeps it from displacing the path state
-            // and the scene in L2
-            // (ONE 16-byte store -- three 4-byte ones until round 5: the instruction count is what costs)
-            typedef float f4v_ __attribute__((ext_vector_type(4)));
-            f4v_ Lv_; Lv_.x = L.x; Lv_.y = L.y; Lv_.z = L.z; Lv_.w = 0.0f;
-            __builtin_nontemporal_store(Lv_, (CRT_GAS f4v_*)&P.L[idv.z]);
+            // (ONE store -- three 4-byte ones until round 5, then a 16-byte one with a zero word: docs/experiments.md 6.14)
+            store_radiance(&P.L[idv.z], L.x, L.y, L.z);
         }
     }
     bool first_ = pre_ok_ && !waiting;
@@ -460,7 +456,7 @@ __device__ __forceinline__ bool query_C(const LParams& P, const uint32_t g, cons
     const Pool& pl = P.pool;
     const float4 la = gld(&pl.la[g]);
     const uint4 idv = load_path_id(P, g);
-    if (((__float_as_uint(la.w) >> 8) & 15u) != ST_NEW) gst(&P.L[idv.z], make_float4(qa.w, qb.w, 0.0f, 0.0f));
+    if (((__float_as_uint(la.w) >> 8) & 15u) != ST_NEW) gst(&P.L4[idv.z], make_float4(qa.w, qb.w, 0.0f, 0.0f));
     const uint32_t item = grab_item(P.item_next, P.items_per_shard, P.n_items, blockIdx.x & (ITEM_SHARDS - 1));
     if (item == ITEM_NONE) return false;
     store_path_id(P, g, item);

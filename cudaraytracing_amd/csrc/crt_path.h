@@ -52,10 +52,19 @@ struct Pool {
     uint4* id;    // W: pixel index, sample index, work item, unused.  M: the work item alone, 4 B (REFERENCE: + triangle, 8 B): load_path_id
     float2* res;  // W: result of the slot's last ray: t, bits(triangle or -1).  M: unused
     float4* rec_a; // [depth][n]  W: L_dir.xyz of that vertex, cos to the next vertex.  M: L_dir.xyz, bits(triangle-row word: material | flags)
-    float4* rec_b; // [depth][n]  W: incoming direction.xyz, bits(material).  M: direction of SPECULAR vertices only, cos to the next vertex
+    float4* rec_b; // [depth][n]  W: incoming direction.xyz, bits(material).  M: direction of SPECULAR vertices only
+    float* rec_c;  // [depth][n]  W: unused.  M: cos to the next vertex, a dense 4-byte plane (a wave's 152 slots: 5 lines, not the 19 of a word in every 16 bytes)
                    // (the records are written when a vertex is entered / left and read back once: W by finish_path, M by finish_path_m3)
     uint32_t n;
 };
+
+// A finished path's radiance, 12 bytes: the entry of L[item] between the render kernel and the fold (fold_samples, crt_internal.h), and
+// of the commit ring.  (crt_intersect's answers are float4 entries: their index stride is the other member of LParams' union, so that
+// no entry of one form is addressed with the other's stride.)
+struct Rad3 {
+    float x, y, z;
+};
+static_assert(sizeof(Rad3) == 12 && alignof(Rad3) == 4, "a radiance entry is three floats");
 
 struct LParams {
     DevScene sc;
@@ -77,7 +86,10 @@ struct LParams {
     uint32_t n_mats;
     FastDiv lsn_div, nslots_div, tiles_x_div;
     unsigned int* item_next; // [ITEM_SHARDS * ITEM_STRIDE] cursors, relative to the shard start
-    float4* L;              // per work item radiance (crt_intersect: per query ray (t, bits(triangle), -, -))
+    union {
+        Rad3* L;            // render: a finished path's radiance, one entry per work item -- or, the commit ring, per (sample mod ring, slot)
+        float4* L4;         // crt_intersect: per query ray (t, bits(triangle), -, -)
+    };
     unsigned long long* counters;
     const float4* q_o;      // crt_intersect: origins / normalised directions of the query rays (work item = ray index)
     const float4* q_d;
@@ -137,9 +149,25 @@ __device__ __forceinline__ float4 gld(const float4* p) { const crt_f4v_ v = *(co
 __device__ __forceinline__ uint4 gld(const uint4* p) { const crt_u4v_ v = *(const CRT_GAS crt_u4v_*)p; return make_uint4(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ int32_t gld(const int32_t* p) { return *(const CRT_GAS int32_t*)p; }
 __device__ __forceinline__ uint32_t gld(const uint32_t* p) { return *(const CRT_GAS uint32_t*)p; }
+__device__ __forceinline__ float gld(const float* p) { return *(const CRT_GAS float*)p; }
 __device__ __forceinline__ void gst(float4* p, const float4 v) { crt_f4v_ t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; *(CRT_GAS crt_f4v_*)p = t; }
 __device__ __forceinline__ void gst(uint4* p, const uint4 v) { crt_u4v_ t; t.x = v.x; t.y = v.y; t.z = v.z; t.w = v.w; *(CRT_GAS crt_u4v_*)p = t; }
 __device__ __forceinline__ void gst(float* p, const float v) { *(CRT_GAS float*)p = v; }
+// A finished path's radiance into its entry: ONE 12-byte store (global_store_dwordx3; the instruction count is what costs in LC), streaming:
+// written once, read once by the fold after the launch, it should not displace the path state and the scene in L2
+typedef float crt_f3v_ __attribute__((ext_vector_type(3)));
+typedef crt_f3v_ crt_f3v_a4_ __attribute__((aligned(4))); // (an entry is 4-byte aligned: item * 12)
+__device__ __forceinline__ void store_radiance(Rad3* p, const float x, const float y, const float z)
+{
+    crt_f3v_ v; v.x = x; v.y = y; v.z = z;
+    __builtin_nontemporal_store(v, (CRT_GAS crt_f3v_a4_*)p);
+}
+__device__ __forceinline__ Rad3 load_radiance(const Rad3* p) // plain: the launch that wrote it has ended
+{
+    const crt_f3v_ v = *(const CRT_GAS crt_f3v_a4_*)p;
+    Rad3 r; r.x = v.x; r.y = v.y; r.z = v.z;
+    return r;
+}
 // The vertex records (rec_a / rec_b): written when a vertex is entered, read once when the path ends.  (Streaming them past the L2 -- nt
 // loads and stores -- was measured in round 5: fabric traffic 348.6 -> 330.8 GB, L2 miss rate 0.475 -> 0.418, and the frame +14 %: the reads
 // at a path's end then always go to the memory side, and LC waits for them.  Round 6, the STORES alone streamed, the loads plain: C2 +7.4 %,
@@ -271,14 +299,14 @@ __device__ __forceinline__ unsigned int ring_load(const unsigned int* p) { retur
 __device__ __forceinline__ float ring_loadf(const float* p) { return __uint_as_float(__hip_atomic_load((ring_word_ptr)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
 __device__ __forceinline__ void ring_storef(float* p, const float v) { __hip_atomic_store((ring_word_ptr)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ring_wait_mem() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// A path's radiance as ONE 16-byte store with the scope bits of an agent-scope atomic store (what ring_storef's instruction carries,
-// four times as wide: three 4-byte write-through stores per path were a fifth of the ring's cost).  The compiler does not count it;
+// A path's radiance as ONE 12-byte store with the scope bits of an agent-scope atomic store (what ring_storef's instruction carries,
+// three times as wide: three 4-byte write-through stores per path were a fifth of the ring's cost).  The compiler does not count it;
 // ring_publish waits for everything outstanding before the path is counted.
-__device__ __forceinline__ void ring_store16(float4* p, const float x, const float y, const float z)
+__device__ __forceinline__ void ring_store12(Rad3* p, const float x, const float y, const float z)
 {
-    typedef float v4f_ __attribute__((ext_vector_type(4)));
-    v4f_ v; v.x = x; v.y = y; v.z = z; v.w = 0.0f;
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
+    typedef float v3f_ __attribute__((ext_vector_type(3)));
+    v3f_ v; v.x = x; v.y = y; v.z = z;
+    asm volatile("global_store_dwordx3 %0, %1, off sc0 sc1" : : "v"(p), "v"(v) : "memory");
 }
 #define RING_BUSY 0x80000000u
 
@@ -311,7 +339,7 @@ __device__ __forceinline__ void ring_commit(const LParams& P, const uint32_t sh)
         }
         if (!__builtin_amdgcn_readfirstlane((int)got)) continue;
         // ---- sample w of the shard: c += L / spp for every pixel slot (Render.cuh:348); four slots per lane and round trip ----
-        const float4* Lr = P.L + (size_t)(w & P.ring_mask) * P.ring_stride + (size_t)sh * P.spsh;
+        const Rad3* Lr = P.L + (size_t)(w & P.ring_mask) * P.ring_stride + (size_t)sh * P.spsh;
         const bool from_zero = P.sample_begin + w == 0u;
         for (uint32_t i0 = (uint32_t)lane; i0 < P.spsh; i0 += 256u) {
             float l[4][3], c[4][3];

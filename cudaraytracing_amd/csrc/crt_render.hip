@@ -74,7 +74,7 @@ void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale,
     ar = (float)prm->width / (float)prm->height;
 }
 
-const uint64_t kMaxChunkItems = 1ull << 30; // paths per chunk (17 GB of per-path radiance: sized for 288 GB of HBM, every launch ends with a 2 ms tail)
+const uint64_t kMaxChunkItems = 1ull << 30; // paths per chunk (12.9 GB of per-path radiance: sized for 288 GB of HBM, every launch ends with a 2 ms tail)
 
 struct TraceSetup {
     TParams T;
@@ -147,14 +147,15 @@ MegaPlan plan_mega3(const crt_scene* sc, uint32_t traversal, bool want_stats, bo
 
 // Traces the n query rays in the handle's query pool (p_ro / p_rd, p_res primed: the form k_fill_rays writes) on stream st with the
 // traversal phases of the render kernel itself -- k_mega3 in query form (work item = ray), or k_trace on the fallback pipeline -- and
-// leaves the answers on the device: (t or FLT_MAX, bits(triangle or -1)) of ray i at the returned pointer + i * stride floats (L, stride
-// 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV pass.
+// leaves the answers on the device: (t or FLT_MAX, bits(triangle or -1)) of ray i at the returned pointer + i * stride floats (the float4
+// answers of the query form, stride 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV pass.
 const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride)
 {
     if (choose_pipeline(sc) == 4) {
         const MegaPlan mp = plan_mega3(sc, traversal, false, false, true, false, n, 0xffffffffu);
         const uint32_t lanes = mp.lanes;
-        sc->p_la.ensure(lanes); sc->p_id.ensure(lanes); sc->L.ensure(n);
+        sc->p_la.ensure(lanes); sc->p_id.ensure(lanes);
+        float4* const answers = sc->L.answers(n);
         sc->spill[0].ensure(mp.spill_entries);
         MParams3 M3;
         std::memset(&M3, 0, sizeof(M3));
@@ -163,7 +164,7 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
         P.pool.la = sc->p_la.p; P.pool.id = sc->p_id.p; P.pool.n = lanes;
         P.n_items = n;
         P.items_per_shard = ((n + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
-        P.item_next = sc->item_next.p; P.L = sc->L.p; P.counters = sc->counters.p;
+        P.item_next = sc->item_next.p; P.L4 = answers; P.counters = sc->counters.p;
         P.q_o = sc->p_ro.p; P.q_d = sc->p_rd.p;
         P.nslots = 1; P.nslots_div = make_fastdiv(1); P.tiles_x = 1; P.tiles_x_div = make_fastdiv(1); P.lsn_div = make_fastdiv(1);
         M3.M.sc = sc->dev; M3.M.counters = sc->counters.p; M3.M.spill_stride = lanes; M3.M.stack_cap = mp.lds_levels;
@@ -173,7 +174,7 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
         hipLaunchKernelGGL(mp.kern, dim3(mp.blocks), dim3(64), 0, st, M3);
         HIP_CHECK(hipGetLastError());
         stride = 4;
-        return (const float*)sc->L.p;
+        return (const float*)answers;
     }
     Pool pool;
     std::memset(&pool, 0, sizeof(pool));
@@ -200,6 +201,16 @@ void ensure_events(crt_scene* sc)
         hipEvent_t e;
         HIP_CHECK(hipEventCreate(&e));
         sc->ev.push_back(e);
+    }
+}
+
+// The event pairs around the launches of a timed megakernel frame, one per chunk
+void ensure_chunk_events(crt_scene* sc, uint32_t chunks)
+{
+    while (sc->ev_chunk.size() < 2 * (size_t)chunks) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        sc->ev_chunk.push_back(e);
     }
 }
 
@@ -234,6 +245,7 @@ struct Frame {
     Shard sh;
     uint32_t chunk; // samples per launch (megakernel) or per pool fill (wavefront)
     uint64_t cap;   // radiance entries: work items of a chunk, or the ring
+    Rad3* L;        // the chunk's radiance, cap entries (null with the ring, whose entries are crt_scene::ring_L)
     RingPlan ring;
     bool want_stats, tiled, want_var, var_frame;
     AParams A;
@@ -257,7 +269,7 @@ LParams frame_lparams(const Frame& f)
     P.rank = prm->rank; P.world = prm->world; P.tiles_x = f.sh.tiles_x; P.n_tiles = f.sh.n_tiles;
     P.nslots = f.sh.nslots;
     P.inv_lsn_pow2 = inv_if_pow2(prm->light_sample_n); P.lsn_div = make_fastdiv((uint32_t)std::max(1, prm->light_sample_n)); P.nslots_div = make_fastdiv(f.sh.nslots); P.tiles_x_div = make_fastdiv(f.sh.tiles_x);
-    P.L = sc->L.p; P.counters = sc->counters.p; P.item_next = sc->item_next.p; P.n_mats = sc->n_mats;
+    P.L = f.L; P.counters = sc->counters.p; P.item_next = sc->item_next.p; P.n_mats = sc->n_mats;
     return P;
 }
 
@@ -360,16 +372,22 @@ void render_mega(Frame& f)
     sc->p_vx.ensure(lanes); sc->p_la.ensure(lanes); sc->p_cc.ensure(lanes); sc->p_id.ensure(lanes);
     sc->p_rec_a.ensure((size_t)lanes * CRT_BOUNCE_STACK_SIZE);
     sc->p_rec_b.ensure((size_t)lanes * CRT_BOUNCE_STACK_SIZE);
+    sc->p_rec_c.ensure((size_t)lanes * CRT_BOUNCE_STACK_SIZE);
     sc->spill[0].ensure(mp.spill_entries);
     LParams P = frame_lparams(f);
     P.pool.vx = sc->p_vx.p; P.pool.la = sc->p_la.p; P.pool.cc = sc->p_cc.p; P.pool.vn = sc->p_vn.p; P.pool.id = sc->p_id.p;
-    P.pool.rec_a = sc->p_rec_a.p; P.pool.rec_b = sc->p_rec_b.p; P.pool.n = lanes;
+    P.pool.rec_a = sc->p_rec_a.p; P.pool.rec_b = sc->p_rec_b.p; P.pool.rec_c = sc->p_rec_c.p; P.pool.n = lanes;
     MParams M;
     std::memset(&M, 0, sizeof(M));
     M.sc = sc->dev; M.counters = sc->counters.p; M.spill = sc->spill[0].p; M.spill_stride = lanes; M.stack_cap = mp.lds_levels;
-    hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-    if (timing) { e0 = sc->ev[0]; e1 = sc->ev[1]; e2 = sc->ev[2]; e3 = sc->ev[3]; HIP_CHECK(hipEventRecord(e0, st)); }
-    double kernel_ms = 0.0;
+    // A timed frame: one event pair around every chunk's launch (crt_scene::ev_chunk), read after the frame's one synchronisation below --
+    // the stream is never waited for between a launch and its fold
+    hipEvent_t e0 = nullptr, e3 = nullptr;
+    if (timing) {
+        ensure_chunk_events(sc, (f.s_end - f.s_begin + f.chunk - 1) / f.chunk);
+        e0 = sc->ev[0]; e3 = sc->ev[3];
+        HIP_CHECK(hipEventRecord(e0, st));
+    }
     uint32_t launches = 0;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
@@ -426,7 +444,7 @@ void render_mega(Frame& f)
         P.items_per_shard_div = make_fastdiv(std::max(1u, P.items_per_shard));
         M.P = P;
         HIP_CHECK(hipMemsetAsync(sc->item_next.p, 0, (size_t)(ring.samples ? ring.shards : (uint32_t)ITEM_SHARDS) * ITEM_STRIDE * sizeof(unsigned int), st));
-        if (timing) HIP_CHECK(hipEventRecord(e1, st));
+        if (timing) HIP_CHECK(hipEventRecord(sc->ev_chunk[2 * launches], st));
         if (s0 == f.s_begin) HIP_CHECK(hipEventRecord(sc->ev_k0, st));
         {
             MParams3 M3;
@@ -438,13 +456,7 @@ void render_mega(Frame& f)
         }
         HIP_CHECK(hipGetLastError());
         if (s0 + ns >= f.s_end) HIP_CHECK(hipEventRecord(sc->ev_k1, st));
-        if (timing) {
-            HIP_CHECK(hipEventRecord(e2, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            float ms = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&ms, e1, e2));
-            kernel_ms += ms;
-        }
+        if (timing) HIP_CHECK(hipEventRecord(sc->ev_chunk[2 * launches + 1], st));
         launches++;
         sc->last_launches = launches;
         accumulate_chunk(f, s0, ns);
@@ -453,6 +465,12 @@ void render_mega(Frame& f)
         HIP_CHECK(hipEventRecord(e3, st));
         HIP_CHECK(hipMemcpyAsync(sc->h_counters, sc->counters.p, kCountersBytes, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
+        double kernel_ms = 0.0;
+        for (uint32_t c = 0; c < launches; c++) {
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_chunk[2 * c], sc->ev_chunk[2 * c + 1]));
+            kernel_ms += ms;
+        }
         float total = 0.0f;
         HIP_CHECK(hipEventElapsedTime(&total, e0, e3));
         read_stats(sc, f.stats, true, kernel_ms, 0.0, total, launches);
@@ -629,8 +647,9 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
             f.chunk = s_count;
             f.cap = (uint64_t)f.ring.samples * f.ring.spsh * f.ring.shards;
             sc->ring_L.ensure_uncached(f.cap);
-        } else sc->L.ensure(f.cap);
-        sc->last_radiance_bytes = f.cap * sizeof(float4);
+            f.L = nullptr;
+        } else f.L = sc->L.radiance(f.cap);
+        sc->last_radiance_bytes = f.cap * sizeof(Rad3);
         sc->last_ring_samples = f.ring.samples;
         sc->accum.ensure_uncached((size_t)f.sh.nslots * 3); // (always uncached: a progressive render may switch between launches with and without the ring)
         // the variance sums: valid from a range that starts at sample 0 with the flag, through ranges that continue that frame with it
@@ -640,7 +659,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         FrameMark frame;
         frame.set(prm, 0, f.tiled);
         f.A = frame_aparams(sc, frame, f.sh);
-        f.A.L = sc->L.p;
+        f.A.L = f.L;
         f.A.out_rgb = (uint8_t*)d_rgb; f.A.out_mean = (float*)d_mean;
         if (stats) ensure_events(sc);
         HIP_CHECK(hipMemsetAsync(sc->counters.p, 0, kCountersBytes, st));

@@ -20,6 +20,15 @@ struct FrameMark {
     }
 };
 
+// What a launch without the commit ring leaves per work item, in one allocation that grows to the larger use: a render's radiance (12
+// bytes, crtk::Rad3) or the answers of k_mega3's query form (16 bytes: crt_intersect, the AOV pass).  Each form has its own accessor and
+// its own element type, so an entry of one is never addressed with the stride of the other.
+struct ItemResults {
+    crtk::DevBuf<float> words;
+    crtk::Rad3* radiance(size_t n) { words.ensure(n * 3); return reinterpret_cast<crtk::Rad3*>(words.p); }
+    float4* answers(size_t n) { words.ensure(n * 4); return reinterpret_cast<float4*>(words.p); } // (hipMalloc's alignment)
+};
+
 struct crt_scene {
     int device = 0;
     crtk::DevBuf<float4> nodes, tri_geo, mats, ltri, nodes3, leaf_geo, tri_nm, nodes4, nodes4i, leaf_geo_i;
@@ -28,7 +37,9 @@ struct crt_scene {
     crtk::DevBuf<int32_t> tri_mat, leaf_count;
     crtk::DevBuf<uint4> lights;
     // path pool + per-item radiance + cross-chunk accumulator
-    crtk::DevBuf<float4> p_ro, p_rd, p_vx, p_la, p_cc, p_vn, p_rec_a, p_rec_b, L;
+    crtk::DevBuf<float4> p_ro, p_rd, p_vx, p_la, p_cc, p_vn, p_rec_a, p_rec_b;
+    crtk::DevBuf<float> p_rec_c; // k_mega3: the vertex records' cosine plane
+    ItemResults L;
     crtk::DevBuf<uint4> p_id;
     uint32_t n_mats = 0;
     crtk::DevBuf<float2> p_res;
@@ -38,7 +49,7 @@ struct crt_scene {
     crtk::DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
     crtk::DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)
     crtk::DevBuf<unsigned int> ring_done, ring_state; // commit ring: finished items per (shard, sample), shard words
-    crtk::DevBuf<float4> ring_L;                      // commit ring: radiance of [ring samples][shards * slots per shard] (uncached memory)
+    crtk::DevBuf<crtk::Rad3> ring_L;                     // commit ring: radiance of [ring samples][shards * slots per shard] (uncached memory)
     std::vector<unsigned int> ring_state_host;
     uint64_t last_radiance_bytes = 0;           // per-work-item (or ring) radiance storage the last render used
     uint32_t last_ring_samples = 0;             // its ring size in samples (0: one radiance per work item)
@@ -68,9 +79,11 @@ struct crt_scene {
     crtk::DevBuf<unsigned int> ad_count;
     unsigned int* h_ad_count = nullptr;
     std::vector<hipEvent_t> ev;
+    std::vector<hipEvent_t> ev_chunk; // a timed megakernel frame: (before, after) the launch of chunk i at [2 i], [2 i + 1]
     ~crt_scene()
     {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+        for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
         if (ev_k0) (void)hipEventDestroy(ev_k0);
         if (ev_k1) (void)hipEventDestroy(ev_k1);
         if (ev_fork) (void)hipEventDestroy(ev_fork);

@@ -125,7 +125,7 @@ __device__ __forceinline__ bool logic_advance(const LParams& P, const Tables<LDS
     // ---- phase 4: path complete ----
     if (do_finish) {
         F3 L = finish_path(P, tb, slot, fin_deepest, fin_emissive, fin_ke);
-        P.L[s.item] = make_float4(L.x, L.y, L.z, 0.0f);
+        store_radiance(&P.L[s.item], L.x, L.y, L.z);
         do_new = true; // regenerate in place
     }
 

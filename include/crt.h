@@ -130,8 +130,8 @@ enum {
                                     box arithmetic on the reference topology, still pruned / any-hit); results are unchanged */
     CRT_FLAG_BOUNDED_RADIANCE = 16u, /* keep the radiance of a WINDOW of samples instead of one value per path: the frame's sum c += L_k / spp
                                     (Render.cuh:348) is made in sample order inside the launch ("commit ring", docs/experiments.md section 9), the
-                                    whole sample range is one launch whatever its size, and the handle needs 16 B x pixels x 32 ... 64
-                                    samples (245 MB for 800x600) instead of 16 B per path (3.9 GB for 800x600 spp 512; 17 GB per 2^30 paths).
+                                    whole sample range is one launch whatever its size, and the handle needs 12 B x pixels x 32 ... 64
+                                    samples (184 MB for 800x600) instead of 12 B per path (2.95 GB for 800x600 spp 512; 12.9 GB per 2^30 paths).
                                     Same bits.  Costs time (800x600 spp 512: 167 ms instead of 93): off by default -- memory is what this
                                     device has plenty of.  Ignored with CRT_FLAG_STATS, by the fallback pipeline, and when the sample range
                                     is no longer than the window, and switched off for the call by CRT_FLAG_VARIANCE (the ring keeps
@@ -235,7 +235,7 @@ int crt_render_device(crt_scene* scene, const crt_camera* cam, const crt_params*
 int crt_last_launch_ms(crt_scene* scene, float* ms, uint32_t* launches);
 
 /* Bytes of per-path radiance storage the handle's last render used, and the size of its commit ring in samples (0 = one radiance per
- * path of a chunk; see CRT_FLAG_BOUNDED_RADIANCE). */
+ * path of a chunk; otherwise one per pixel slot of a ring sample; 12 bytes each; see CRT_FLAG_BOUNDED_RADIANCE). */
 int crt_radiance_storage(crt_scene* scene, uint64_t* bytes, uint32_t* ring_samples);
 
 /* Progressive rendering (the reference re-renders all spp on every click, src/main.cu:368-377):
@@ -297,7 +297,7 @@ int crt_preview_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_st
  * render (or any range of the frame in flight, from sample 0 on) was submitted without the flag; n < 2 (a finished spp 1 frame
  * included: one sample has no variance).
  * Precision: a sum of squares, not Welford's update -- both carry two values per channel across chunks, this one adds one multiply and
- * one add per sample to a pass that is bound by reading 16 B per path, and keeps c the frame's own bits.  The sum of squares loses
+ * one add per sample to a pass that is bound by reading 12 B per path, and keeps c the frame's own bits.  The sum of squares loses
  * accuracy where variance / mean^2 approaches n x 2^-24; a Welford form would not.  Measured against the float64 sample variance of the
  * same samples on 64x48 spp 8 and 32x24 spp 512 frames of the two shipped scenes: largest relative error 3.44e-6 / 2.75e-6 at spp 8 and
  * 2.68e-6 / 3.46e-6 at spp 512 (cornell-box / veach-mis), 99th percentile below 2.3e-6, smallest variance / mean^2 met 4.4e-4; every
