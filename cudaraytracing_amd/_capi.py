@@ -180,6 +180,26 @@ class TemporalClampInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class TemporalMomentPlanes(C.Structure):
+    _fields_ = [("m1", C.c_void_p), ("m2", C.c_void_p)]
+
+
+class VarianceEstimateParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("min_history", C.c_uint32), ("radius", C.c_uint32),
+                ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("of_mean", C.c_uint32), ("history_cap", C.c_float)]
+
+
+class VarianceEstimateInputs(C.Structure):
+    _fields_ = [("m1", C.c_void_p), ("m2", C.c_void_p), ("history", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class VarianceEstimateInfo(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("spatial", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("step_samples", C.c_uint32), ("threshold", C.c_float), ("mean_floor", C.c_float)]
 
@@ -219,7 +239,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
-           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_multi_create", "crt_multi_destroy",
+           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
@@ -292,6 +312,17 @@ def lib():
     L.crt_temporal_clamped_device.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame),
                                               C.POINTER(TemporalHistory), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(TemporalClampInfo)]
+    L.crt_temporal_moments.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory),
+                                       C.POINTER(TemporalMomentPlanes), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(TemporalClampInfo)]
+    L.crt_temporal_moments_device.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame),
+                                              C.POINTER(TemporalHistory), C.POINTER(TemporalMomentPlanes), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalClampInfo)]
+    L.crt_variance_estimate_defaults.argtypes = [C.POINTER(VarianceEstimateParams)]
+    L.crt_variance_estimate.argtypes = [C.c_int, C.POINTER(VarianceEstimateParams), C.POINTER(VarianceEstimateInputs), C.c_void_p,
+                                        C.POINTER(VarianceEstimateInfo)]
+    L.crt_variance_estimate_device.argtypes = [C.c_int, C.POINTER(VarianceEstimateParams), C.POINTER(VarianceEstimateInputs), C.c_void_p, C.c_void_p,
+                                               C.POINTER(VarianceEstimateInfo)]
     L.crt_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.crt_multi_destroy.argtypes = [C.c_void_p]
     L.crt_multi_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats),

@@ -181,6 +181,7 @@ class Render:
         self.samples_buffer = None
         self.adaptive_info = None
         self.temporal_info = None
+        self.variance_estimate_info = None
         self.temporal_history_buffer = None
         self._temporal = None        # run_view_temporal: the history (temporal()'s `prev` dict), its camera and size
         self._temporal_frames = 0    # frames since the last reset_temporal()
@@ -412,7 +413,8 @@ class Render:
                                                **self.aov_buffers)
         return rgb, mean
 
-    def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, **overrides):
+    def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, variance="samples",
+                          **overrides):
         """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
         AOV pass (albedo, normal, depth, material) and blends the frame into the history this object keeps -- colour, variance, history
         length, depth, normal, material ID and camera of the previous call; the unfiltered result is the next call's history.
@@ -422,8 +424,18 @@ class Render:
         not clamped; self.temporal_info then has no `clamped`).  The first call, the first after
         reset_temporal() and the first at another size start a history.  self.frame_buffer / self.mean_buffer hold the frame as
         rendered, self.variance_buffer the accumulated variance, self.temporal_history_buffer the frames accumulated per pixel (H, W),
-        self.temporal_info the crt_temporal_info dict, self.aov_buffers the guides."""
+        self.temporal_info the crt_temporal_info dict, self.aov_buffers the guides.
+        variance="moments": the frame is rendered WITHOUT want_variance (so one sample per pixel works), the history also keeps the
+        moment planes of crt_temporal_moments, and self.variance_buffer -- what denoise=True feeds to denoise_var -- is
+        variance_estimate of them with the frame's normal and depth; overrides may then also name variance_estimate's settings, and
+        self.variance_estimate_info holds its info dict.  A change of `variance` starts a history."""
+        if variance not in ("samples", "moments"):
+            raise ValueError("run_view_temporal: variance must be 'samples' or 'moments', got %r" % (variance,))
         self._handle("run_view_temporal")
+        if variance == "moments":
+            return self._run_view_temporal_moments(eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides)
+        if self._temporal is not None and "m1" in self._temporal:
+            self._temporal = None
         keep_seed = self.seed
         self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
         try:
@@ -440,6 +452,31 @@ class Render:
         self._temporal = {"prev": dict(cur, color=mean, variance=var, history=hist), "camera": cam, "size": (w, h)}
         self._temporal_frames += 1
         self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
+        self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
+        if denoise:
+            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, return_info=True, **self.aov_buffers)
+        return rgb, mean
+
+    def _run_view_temporal_moments(self, eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides):
+        estimate = {k: overrides.pop(k) for k in list(overrides) if k in _ESTIMATE_SETTINGS}
+        keep_seed = self.seed
+        self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
+        try:
+            self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height)
+            aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth", "material"), width=width, height=height)
+        finally:
+            self.seed = keep_seed
+        h, w = self.mean_buffer.shape[:2]
+        cam = (np.array(eye_pos, dtype=np.float32), np.array(inv_view_mat, dtype=np.float32).reshape(9), np.float32(fovY))
+        cur = {"color": self.mean_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
+        t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h) and "m1" in self._temporal) else None
+        rgb, mean, _, hist, m1, m2, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
+                                                    return_info=True, clamp=clamp, moments={"m1": t["m1"], "m2": t["m2"]} if t else True, **overrides)
+        self._temporal = {"prev": dict(cur, color=mean, history=hist), "camera": cam, "size": (w, h), "m1": m1, "m2": m2}
+        self._temporal_frames += 1
+        self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
+        var, self.variance_estimate_info = variance_estimate(m1, m2, hist, normal=aov["normal"], depth=aov["depth"], device=self.device,
+                                                             return_info=True, **estimate)
         self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
         if denoise:
             rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, return_info=True, **self.aov_buffers)
@@ -827,15 +864,32 @@ def _temporal_struct(struct, buffers, h, w, keep):
     return struct
 
 
+def _moment_planes(moments, h, w, keep):
+    """moments=dict(m1=, m2=) of the history -> crt_temporal_moment_planes"""
+    if not isinstance(moments, dict) or set(moments) != {"m1", "m2"}:
+        raise ValueError("temporal: moments must be None, True or a dict of m1 and m2, got %r" % (moments,))
+    planes = capi.TemporalMomentPlanes()
+    for name in ("m1", "m2"):
+        a = np.ascontiguousarray(moments[name], dtype=np.float32)
+        if a.shape != (h, w, 3):
+            raise ValueError("temporal: %s has shape %r for a %d x %d frame" % (name, a.shape, w, h))
+        keep.append(a)
+        setattr(planes, name, a.ctypes.data)
+    return planes
+
+
 def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, want_rgb=True,
-             return_info=False, clamp=None):
+             return_info=False, clamp=None, moments=None):
     """Temporal accumulation with reprojection (crt_temporal, contract: include/crt.h).  cur: dict of the current frame -- color
     (H, W, 3), depth (H, W), optionally variance, normal (H, W, 3) and id (H, W) int32; prev: dict of the history -- color, history,
     depth, and variance / normal / id as cur has them -- or None for a first frame; camera, prev_camera: (eye, inv_view, fov_y) of the
     two frames.  None settings take crt_temporal_defaults.  Returns (rgb, color, variance, history): the tone map (None without
     want_rgb), the accumulated colour, its variance (None if cur has none) and the frames accumulated per pixel; with return_info
     also the crt_temporal_info dict.  clamp: None (crt_temporal), True or a dict of radius / gamma (crt_temporal_clamped with its defaults /
-    with these values: the history is clamped to its neighbourhood in the current frame, and the info dict gains `clamped`)."""
+    with these values: the history is clamped to its neighbourhood in the current frame, and the info dict gains `clamped`).
+    moments: None, or -- crt_temporal_moments -- the dict(m1=, m2=) of the history's moment planes (True for a first frame, where there is
+    no history): the call then returns (rgb, color, variance, history, m1, m2), the info dict has `clamped` (0 without a clamp), and
+    m1 / m2 / history are what variance_estimate takes."""
     c = np.ascontiguousarray(cur["color"], dtype=np.float32)
     if c.ndim != 3 or c.shape[2] != 3:
         raise ValueError("temporal needs an (H, W, 3) colour image, got %r" % (c.shape,))
@@ -850,6 +904,18 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
     var = np.zeros((h, w, 3), dtype=np.float32) if cur.get("variance") is not None else None
     hist = np.zeros((h, w), dtype=np.float32)
     rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    if moments is not None:
+        if (moments is True) != (prev is None):
+            raise ValueError("temporal: moments=True goes with a first frame, a dict of m1 and m2 with a history")
+        planes = _moment_planes(moments, h, w, keep) if prev is not None else None
+        m1, m2 = np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w, 3), dtype=np.float32)
+        info = capi.TemporalClampInfo()
+        capi.check(capi.lib().crt_temporal_moments(device, C.byref(prm), C.byref(_temporal_clamp(clamp)) if clamp is not None else None, C.byref(fc),
+                                                   C.byref(fp) if fp is not None else None, C.byref(planes) if planes is not None else None,
+                                                   capi.ptr(color), capi.ptr(var), capi.ptr(hist), capi.ptr(m1), capi.ptr(m2), capi.ptr(rgb),
+                                                   C.byref(info)), "crt_temporal_moments")
+        out = (rgb, color, var, hist, m1, m2)
+        return out + (info.as_dict(),) if return_info else out
     if clamp is None:
         info = capi.TemporalInfo()
         capi.check(capi.lib().crt_temporal(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, capi.ptr(color), capi.ptr(var),
@@ -863,10 +929,12 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
 
 
 def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_ptr, out_variance_ptr=None, out_rgb_ptr=None, prev_ptrs=None,
-                    prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True, clamp=None):
+                    prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True, clamp=None,
+                    moments=None):
     """Enqueues crt_temporal_device with everything in device memory: cur_ptrs / prev_ptrs = {name: raw device pointer} with the names of
     temporal()'s dicts (prev_ptrs None: no history).  With want_info the call synchronizes the stream and returns the crt_temporal_info
-    dict, else None.  clamp: as temporal() (crt_temporal_clamped_device; the dict gains `clamped`)."""
+    dict, else None.  clamp: as temporal() (crt_temporal_clamped_device; the dict gains `clamped`).  moments: None, or
+    dict(out_m1=, out_m2=) of raw device pointers and, with a history, m1= and m2= of its planes (crt_temporal_moments_device)."""
     def fill(struct, ptrs):
         for name, p in ptrs.items():
             if name not in {n for n, _ in struct._fields_}:
@@ -877,6 +945,19 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
     fp = fill(capi.TemporalHistory(), prev_ptrs) if prev_ptrs is not None else None
     prm = _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min)
     vp = lambda p: C.c_void_p(p) if p else None
+    if moments is not None:
+        if not isinstance(moments, dict) or set(moments) - {"m1", "m2", "out_m1", "out_m2"}:
+            raise ValueError("temporal_device: moments must be None or a dict of out_m1, out_m2 and the history's m1, m2, got %r" % (moments,))
+        planes = None
+        if moments.get("m1") or moments.get("m2"):
+            planes = capi.TemporalMomentPlanes(moments.get("m1") or None, moments.get("m2") or None)
+        info = capi.TemporalClampInfo()
+        capi.check(capi.lib().crt_temporal_moments_device(device, C.byref(prm), C.byref(_temporal_clamp(clamp)) if clamp is not None else None, C.byref(fc),
+                                                          C.byref(fp) if fp is not None else None, C.byref(planes) if planes is not None else None,
+                                                          vp(out_color_ptr), vp(out_variance_ptr), vp(out_history_ptr), vp(moments.get("out_m1")),
+                                                          vp(moments.get("out_m2")), vp(out_rgb_ptr), vp(stream), C.byref(info) if want_info else None),
+                   "crt_temporal_moments_device")
+        return info.as_dict() if want_info else None
     if clamp is None:
         info = capi.TemporalInfo()
         capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, vp(out_color_ptr),
@@ -888,6 +969,78 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
                                                           C.byref(fp) if fp is not None else None, vp(out_color_ptr), vp(out_variance_ptr),
                                                           vp(out_history_ptr), vp(out_rgb_ptr), vp(stream), C.byref(info) if want_info else None),
                    "crt_temporal_clamped_device")
+    return info.as_dict() if want_info else None
+
+
+_ESTIMATE_SETTINGS = ("min_history", "radius", "sigma_normal", "sigma_depth", "of_mean", "history_cap")
+# What this module and crt_cli choose where the library's default (of_mean 0, SVGF's) is not asked for by name: the variance of the
+# accumulated mean, which is what the filter is handed (docs/experiments.md, "Variance from temporal moments")
+ESTIMATE_OF_MEAN = 1
+
+
+def variance_estimate_defaults():
+    """crt_variance_estimate_defaults as a dict: min_history, radius, sigma_normal, sigma_depth, of_mean, history_cap -- the library's."""
+    p = capi.VarianceEstimateParams()
+    capi.check(capi.lib().crt_variance_estimate_defaults(C.byref(p)), "crt_variance_estimate_defaults")
+    return {n: getattr(p, n) for n in _ESTIMATE_SETTINGS}
+
+
+def _estimate_params(width, height, settings):
+    unknown = set(settings) - set(_ESTIMATE_SETTINGS)
+    if unknown:
+        raise ValueError("variance_estimate: unknown settings %r" % sorted(unknown))
+    p = capi.VarianceEstimateParams()
+    capi.check(capi.lib().crt_variance_estimate_defaults(C.byref(p)), "crt_variance_estimate_defaults")
+    p.width, p.height = int(width), int(height)
+    p.of_mean = ESTIMATE_OF_MEAN
+    for name, v in settings.items():
+        if v is None:
+            continue
+        if name in ("min_history", "radius", "of_mean"):
+            if int(v) != v or not 0 <= int(v) < 2 ** 32:
+                raise ValueError("variance_estimate: %s must be a non-negative integer, got %r" % (name, v))
+            v = int(v)
+        setattr(p, name, v)
+    return p
+
+
+def variance_estimate(m1, m2, history, normal=None, depth=None, device=0, return_info=False, **settings):
+    """Per-pixel variance from temporal moments (crt_variance_estimate, contract: include/crt.h): m1, m2 (H, W, 3) and history (H, W) as
+    temporal(moments=...) returns them, normal / depth the current frame's AOVs (optional).  settings: min_history, radius, sigma_normal,
+    sigma_depth, of_mean, history_cap; None or absent takes crt_variance_estimate_defaults, except of_mean, which is 1 here (the variance
+    of the accumulated mean: docs/experiments.md).  Returns the (H, W, 3) variance, what denoise_var takes; with return_info also the
+    crt_variance_estimate_info dict (total_ms, spatial)."""
+    a1 = np.ascontiguousarray(m1, dtype=np.float32)
+    if a1.ndim != 3 or a1.shape[2] != 3:
+        raise ValueError("variance_estimate needs (H, W, 3) moments, got %r" % (a1.shape,))
+    h, w = a1.shape[:2]
+    inputs, keep = capi.VarianceEstimateInputs(), []
+    for name, a, shape in (("m1", a1, (h, w, 3)), ("m2", m2, (h, w, 3)), ("history", history, (h, w)), ("normal", normal, (h, w, 3)),
+                           ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("variance_estimate: %s has shape %r, expected %r" % (name, a.shape, shape))
+        keep.append(a)
+        setattr(inputs, name, a.ctypes.data)
+    prm = _estimate_params(w, h, settings)
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    info = capi.VarianceEstimateInfo()
+    capi.check(capi.lib().crt_variance_estimate(device, C.byref(prm), C.byref(inputs), capi.ptr(out), C.byref(info)), "crt_variance_estimate")
+    return (out, info.as_dict()) if return_info else out
+
+
+def variance_estimate_device(width, height, m1_ptr, m2_ptr, history_ptr, out_variance_ptr, normal_ptr=None, depth_ptr=None, device=0, stream=None,
+                             want_info=True, **settings):
+    """Enqueues crt_variance_estimate_device with everything in device memory (raw device pointers); settings as variance_estimate.  With
+    want_info the call synchronizes the stream and returns the info dict, else None."""
+    inputs = capi.VarianceEstimateInputs(m1_ptr or None, m2_ptr or None, history_ptr or None, normal_ptr or None, depth_ptr or None)
+    prm = _estimate_params(width, height, settings)
+    info = capi.VarianceEstimateInfo()
+    capi.check(capi.lib().crt_variance_estimate_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
+                                                       C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
+               "crt_variance_estimate_device")
     return info.as_dict() if want_info else None
 
 

@@ -10,12 +10,16 @@
 //           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
+//           [--temporal-variance samples|moments[,MIN_HISTORY]]
 // --temporal N renders N frames on one device and accumulates them over time (crt_temporal, its defaults): frame f = 0 .. N-1 has eye and
 // lookat moved by f x the --temporal-step vector and the seed --seed + f.  -o gets the last frame as rendered, --temporal-out PATH the
 // accumulated last frame; --temporal-denoise writes the variance-guided filter (crt_denoise_var, its defaults with the --denoise-iterations
 // / --denoise-sigma overrides) of the accumulated frame and its accumulated variance to --temporal-out instead.  --variance, --denoise and
 // --aov work on the last frame as rendered.  --temporal-clamp GAMMA[,RADIUS] clamps the history to mean +- GAMMA deviations of the
 // (2 RADIUS + 1)^2 current pixels around each pixel (crt_temporal_clamped; RADIUS 1 .. 3, default: crt_temporal_clamp_defaults').
+// --temporal-variance moments[,MIN_HISTORY] measures the variance --temporal-denoise filters with from the temporal moments of each pixel
+// (crt_temporal_moments, crt_variance_estimate with its defaults, of_mean 1 and MIN_HISTORY) instead of carrying the per-sample variance
+// along: the frames are then rendered without CRT_FLAG_VARIANCE and --spp 1 works.  samples (the default) is the carried variance.
 // --adaptive THRESHOLD renders the frame with variance-driven adaptive sampling (crt_render_adaptive, one device): --spp is the cap, a
 // pixel stops once the standard error of its mean is at most THRESHOLD x (mean + floor); --adaptive-min / --adaptive-step override the
 // warm-up and the samples per pass of crt_adaptive_defaults, --adaptive-samples PATH writes the samples per pixel as a 1-channel PFM.
@@ -48,7 +52,8 @@ int main(int argc, char** argv)
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n"
-                             "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n", argv[0]);
+                             "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
+                             "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n", argv[0]);
         return 2;
     }
     try {
@@ -62,7 +67,10 @@ int main(int argc, char** argv)
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false;
         int temporal = 0;
-        bool temporal_option = false, temporal_denoise = false, temporal_clamp = false;
+        bool temporal_option = false, temporal_denoise = false, temporal_clamp = false, temporal_moments = false;
+        crt_variance_estimate_params tvar; // --temporal-variance moments: the estimate's defaults with of_mean 1 and MIN_HISTORY
+        crt_variance_estimate_defaults(&tvar);
+        tvar.of_mean = 1; // (the variance of the accumulated mean, which is what the filter is handed: docs/experiments.md)
         crt_temporal_clamp tclamp;
         crt_temporal_clamp_defaults(&tclamp);
         float temporal_step[3] = {0.0f, 0.0f, 0.0f};
@@ -147,6 +155,23 @@ int main(int argc, char** argv)
                 }
                 if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-clamp needs GAMMA[,RADIUS]: GAMMA >= 0, RADIUS 1 .. 3");
             }
+            else if (a == "--temporal-variance") {
+                need(i, 1);
+                temporal_option = true;
+                const std::string v = argv[++i];
+                bool good = true;
+                if (v == "samples") temporal_moments = false;
+                else if (v == "moments") temporal_moments = true;
+                else if (v.rfind("moments,", 0) == 0) {
+                    const char* q = v.c_str() + 8;
+                    char* end = nullptr;
+                    const long m = std::strtol(q, &end, 10);
+                    good = *q >= '0' && *q <= '9' && *end == 0 && m >= 1 && m <= 1000000;
+                    tvar.min_history = (uint32_t)m;
+                    temporal_moments = true;
+                } else good = false;
+                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-variance needs samples or moments[,MIN_HISTORY]: MIN_HISTORY >= 1");
+            }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
@@ -183,11 +208,11 @@ int main(int argc, char** argv)
         if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
         if (multi && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates on one device (not with --gpus / --devices)");
         if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
-        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise and --temporal-clamp need --temporal N");
+        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp and --temporal-variance need --temporal N");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step and --adaptive-samples need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
-        const bool want_var = !variance.empty() || denoise_var || temporal > 0;
+        const bool want_var = !variance.empty() || denoise_var || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
         crt_denoise_var_defaults(&tdn);
         if (dn_iterations) tdn.iterations = dn.iterations;
@@ -220,11 +245,15 @@ int main(int argc, char** argv)
                 }
                 crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
                 render.set_seed(seed + (uint64_t)f);
-                render.run_temporal(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr);
+                if (temporal_moments) render.run_temporal_moments(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr, tvar);
+                else render.run_temporal(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr);
                 std::printf("temporal frame %d: %llu of %llu pixels reprojected, device %.3f ms\n", f, (unsigned long long)render.last_temporal_info().reprojected,
                             (unsigned long long)task.width * task.height, render.last_temporal_info().total_ms);
                 if (temporal_clamp) std::printf("temporal frame %d: %llu histories clamped (gamma %g, radius %u)\n", f, (unsigned long long)render.last_temporal_clamped(),
                                                 (double)tclamp.gamma, tclamp.radius);
+                if (temporal_moments) std::printf("temporal frame %d: variance of %llu pixels from their neighbourhood (history below %u), device %.3f ms\n", f,
+                                                  (unsigned long long)render.last_variance_estimate_info().spatial, tvar.min_history,
+                                                  render.last_variance_estimate_info().total_ms);
             }
         }
         else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);

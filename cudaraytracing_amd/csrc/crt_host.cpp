@@ -788,7 +788,7 @@ void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], f
     std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
     std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
     p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && temporal_width_ == p.width && temporal_height_ == p.height;
+    const bool have = temporal_valid_ && !temporal_moments_ && temporal_width_ == p.width && temporal_height_ == p.height;
     p.prev = have ? temporal_cam_ : p.cur;
     const size_t n = scene_->get_pixels();
     crt_temporal_frame cur{};
@@ -811,6 +811,50 @@ void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], f
     temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
     temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
     temporal_valid_ = true;
+    temporal_moments_ = false;
+}
+
+void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
+                                  const crt_variance_estimate_params& est)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_temporal_moments: temporal accumulation is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal_moments after free()");
+    run_view(eye_pos, inv_view_mat, fovY);
+    run_aov(eye_pos, inv_view_mat, fovY);
+    crt_temporal_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
+    std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
+    p.cur.fov_y = fovY;
+    const bool have = temporal_valid_ && temporal_moments_ && temporal_width_ == p.width && temporal_height_ == p.height;
+    p.prev = have ? temporal_cam_ : p.cur;
+    const size_t n = scene_->get_pixels();
+    crt_temporal_frame cur{};
+    cur.color = mean_buffer_.data(); cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
+    crt_temporal_history prev{};
+    prev.color = temporal_color_.data(); prev.history = temporal_history_.data();
+    prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
+    const crt_temporal_moment_planes planes = {temporal_m1_.data(), temporal_m2_.data()};
+    std::vector<float> color(3 * n, 0.0f), history(n, 0.0f), m1(3 * n, 0.0f), m2(3 * n, 0.0f), estimate(3 * n, 0.0f);
+    temporal_rgb_.assign(3 * n, 0);
+    crt_temporal_clamp_info ci{};
+    int rc = crt_temporal_moments(device_, &p, clamp, &cur, have ? &prev : nullptr, have ? &planes : nullptr, color.data(), nullptr, history.data(), m1.data(),
+                                  m2.data(), temporal_rgb_.data(), &ci);
+    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
+    temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
+    temporal_clamped_ = ci.clamped;
+    crt_variance_estimate_params e = est;
+    e.width = p.width; e.height = p.height;
+    crt_variance_estimate_inputs in{};
+    in.m1 = m1.data(); in.m2 = m2.data(); in.history = history.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    rc = crt_variance_estimate(device_, &e, &in, estimate.data(), &estimate_info_);
+    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
+    temporal_color_.swap(color); temporal_variance_.swap(estimate); temporal_history_.swap(history);
+    temporal_m1_.swap(m1); temporal_m2_.swap(m2);
+    temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
+    temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
+    temporal_valid_ = true;
+    temporal_moments_ = true;
 }
 
 void Render::run_denoise_temporal(const crt_denoise_params& prm)

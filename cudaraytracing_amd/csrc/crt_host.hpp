@@ -242,6 +242,13 @@ public:
     // with another seed (set_seed).  frame and mean buffers hold the frame as rendered; one device only.  clamp != nullptr: the history is
     // clamped to its neighbourhood (crt_temporal_clamped); last_temporal_clamped() is then the count of pixels it moved
     void run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp = nullptr);
+    // run_temporal with the variance measured instead of carried: the frame needs no CRT_FLAG_VARIANCE (one sample per pixel works), the
+    // history also keeps the moment planes of crt_temporal_moments, and get_temporal_variance_buffer() -- what run_denoise_temporal
+    // filters with -- is crt_variance_estimate of them with the frame's normal and depth (est: crt_variance_estimate_defaults with
+    // overrides, its sizes are set here).  A history made by run_temporal is not continued, nor the other way round.
+    void run_temporal_moments(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
+                              const crt_variance_estimate_params& est);
+    const crt_variance_estimate_info& last_variance_estimate_info() const { return estimate_info_; }
     void reset_temporal() { temporal_valid_ = false; }
     const unsigned char* get_temporal_buffer() const { return temporal_rgb_.data(); }        // W x H x 3 RGB8: the accumulated frame
     const float* get_temporal_mean_buffer() const { return temporal_color_.data(); }          // W x H x 3
@@ -301,6 +308,9 @@ private:
     bool temporal_valid_ = false;
     crt_temporal_info temporal_info_{};
     uint64_t temporal_clamped_ = 0;
+    std::vector<float> temporal_m1_, temporal_m2_;   // run_temporal_moments: the history's moment planes
+    bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
+    crt_variance_estimate_info estimate_info_{};
     void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm);
     crt_adaptive_info adaptive_info_{};
     int device_ = 0;

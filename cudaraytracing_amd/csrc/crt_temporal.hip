@@ -11,6 +11,11 @@
 // deviation of the current colour over the (2 radius + 1)^2 pixels around p, straight from the caller's buffer (a wave's 64 pixels share
 // all but 2 radius columns of their taps), the history colour clamped to mean +- gamma deviations, and a second count on the same ballot
 // path.  The statistics run INSIDE the branch of the pixels that take the history, not before it: see docs/experiments.md.
+//
+// k_temporal<CLAMP, true> (crt_temporal_moments) carries two more history planes, the running first and second moments of the UNclamped
+// colour: their taps ride on the predicates and the weight b of the colour's taps (24 B more per tap that counts), their blend on n, a
+// and k, and 24 B more are stored per pixel.  <false, false> and <true, false> are the kernels of the older entry points, instruction
+// for instruction what they were before the third parameter (the new fields of TpParams stand at its end).
 #include "crt_internal.h"
 
 #include <cstring>
@@ -30,8 +35,10 @@ struct TpParams {
     float* out_variance;
     float* out_history;
     unsigned long long* count;                // [0] pixels that took the history, [1] of those: moved by the clamp (null: not counted)
-    int radius;                               // k_temporal<true> only: crt_temporal_clamp
+    int radius;                               // k_temporal<true, *> only: crt_temporal_clamp
     float gamma;
+    const float* pm1; const float* pm2;       // k_temporal<*, true> only: the history's moment planes (null without a history)
+    float* out_m1; float* out_m2;
 };
 
 // One channel of the interpolated history, hc / ws; with CLAMP clamped into [mu - gamma sd, mu + gamma sd] of the neighbourhood sums
@@ -55,7 +62,7 @@ __device__ __forceinline__ float history_channel(float hc, float ws, float s1, f
     return h;
 }
 
-template <bool CLAMP>
+template <bool CLAMP, bool MOMENTS>
 __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
 {
     const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
@@ -70,6 +77,8 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
         if (P.variance) v = f3(P.variance[p * 3], P.variance[p * 3 + 1], P.variance[p * 3 + 2]);
         F3 oc = c, ov = v;
         float oh = 1.0f;
+        F3 o1 = c, o2 = f3(0.0f, 0.0f, 0.0f);
+        if (MOMENTS) o2 = f3(c.x * c.x, c.y * c.y, c.z * c.z);
         if (P.pcolor) {
             const float fw = (float)W, fh = (float)H, dp = P.depth[p];
             // the pixel-centre ray of the current camera (camera_dir without the jitter) and the point it reaches at the stored depth
@@ -97,7 +106,7 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
                 F3 n = f3(0.0f, 0.0f, 0.0f);
                 if (P.normal) n = f3(P.normal[p * 3], P.normal[p * 3 + 1], P.normal[p * 3 + 2]);
                 const int32_t idp = P.id ? P.id[p] : 0;
-                F3 hc = f3(0.0f, 0.0f, 0.0f), hv = f3(0.0f, 0.0f, 0.0f);
+                F3 hc = f3(0.0f, 0.0f, 0.0f), hv = f3(0.0f, 0.0f, 0.0f), h1 = f3(0.0f, 0.0f, 0.0f), h2 = f3(0.0f, 0.0f, 0.0f);
                 float hn = 0.0f, ws = 0.0f;
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
@@ -124,6 +133,14 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
                             hv.x = hv.x + P.pvariance[q * 3] * b;
                             hv.y = hv.y + P.pvariance[q * 3 + 1] * b;
                             hv.z = hv.z + P.pvariance[q * 3 + 2] * b;
+                        }
+                        if (MOMENTS) {
+                            h1.x = h1.x + P.pm1[q * 3] * b;
+                            h1.y = h1.y + P.pm1[q * 3 + 1] * b;
+                            h1.z = h1.z + P.pm1[q * 3 + 2] * b;
+                            h2.x = h2.x + P.pm2[q * 3] * b;
+                            h2.y = h2.y + P.pm2[q * 3 + 1] * b;
+                            h2.z = h2.z + P.pm2[q * 3 + 2] * b;
                         }
                         hn = hn + P.phistory[q] * b;
                         ws = ws + b;
@@ -161,12 +178,20 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
                         const float kk = k * k, aa = a * a;
                         ov = f3((hv.x / ws) * kk + v.x * aa, (hv.y / ws) * kk + v.y * aa, (hv.z / ws) * kk + v.z * aa);
                     }
+                    if (MOMENTS) { // never clamped: m1 is the running mean of what the pixel was seen to show
+                        o1 = f3((h1.x / ws) * k + c.x * a, (h1.y / ws) * k + c.y * a, (h1.z / ws) * k + c.z * a);
+                        o2 = f3((h2.x / ws) * k + o2.x * a, (h2.y / ws) * k + o2.y * a, (h2.z / ws) * k + o2.z * a);
+                    }
                 }
             }
         }
         write_color(P, p, true, oc);
         if (P.out_variance) { P.out_variance[p * 3] = ov.x; P.out_variance[p * 3 + 1] = ov.y; P.out_variance[p * 3 + 2] = ov.z; }
         P.out_history[p] = oh;
+        if (MOMENTS) {
+            P.out_m1[p * 3] = o1.x; P.out_m1[p * 3 + 1] = o1.y; P.out_m1[p * 3 + 2] = o1.z;
+            P.out_m2[p * 3] = o2.x; P.out_m2[p * 3 + 1] = o2.y; P.out_m2[p * 3 + 2] = o2.z;
+        }
     }
     if (!P.count) return;
     const unsigned long long mask = __ballot(took);
@@ -191,9 +216,14 @@ const uint32_t CLAMP_DEFAULT_RADIUS = 1;   // crt_temporal_clamp_defaults: chose
 const float CLAMP_DEFAULT_GAMMA = 1.0f;
 bool tolerance_ok(float t) { return t > 0.0f; } // (false for NaN)
 
-// Argument checks of all four calls, before any device call (clamp: null for crt_temporal / crt_temporal_device)
+// crt_temporal_moments / _device: the history's moment planes (null iff there is no history) and the two outputs
+struct MomentArgs { const crt_temporal_moment_planes* prev; void* out_m1; void* out_m2; };
+
+// Argument checks of all six calls, before any device call (clamp: null for crt_temporal / crt_temporal_device; mom: null for all but
+// crt_temporal_moments / _device)
 int temporal_check(const char* who, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                   const crt_temporal_history* prev, const void* out_color, const void* out_variance, const void* out_history)
+                   const crt_temporal_history* prev, const void* out_color, const void* out_variance, const void* out_history,
+                   const MomentArgs* mom)
 {
     const std::string w(who);
     if (!prm || !cur) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
@@ -210,6 +240,12 @@ int temporal_check(const char* who, const crt_temporal_params* prm, const crt_te
         if (cur->variance && !prev->variance) return fail(CRT_ERR_INVALID_ARG, w + ": the history has no variance");
         if ((cur->normal != nullptr) != (prev->normal != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": normals must be given in both frames or in neither");
         if ((cur->id != nullptr) != (prev->id != nullptr)) return fail(CRT_ERR_INVALID_ARG, w + ": IDs must be given in both frames or in neither");
+    }
+    if (mom) {
+        if (!mom->out_m1 || !mom->out_m2) return fail(CRT_ERR_INVALID_ARG, w + ": out_m1 and out_m2 are required");
+        if ((prev != nullptr) != (mom->prev != nullptr))
+            return fail(CRT_ERR_INVALID_ARG, w + ": a history and its moment planes go together");
+        if (mom->prev && (!mom->prev->m1 || !mom->prev->m2)) return fail(CRT_ERR_INVALID_ARG, w + ": the moment planes need m1 and m2");
     }
     if (clamp) {
         if (clamp->radius < 1 || clamp->radius > 3) return fail(CRT_ERR_INVALID_ARG, w + ": the clamp's radius must be 1 .. 3");
@@ -232,9 +268,9 @@ struct TemporalCounts { float total_ms; unsigned long long reprojected, clamped;
 
 int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
                   const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st,
-                  TemporalCounts* info)
+                  TemporalCounts* info, const MomentArgs* mom = nullptr)
 {
-    const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history);
+    const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, mom);
     if (rc != CRT_OK) return rc;
     if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -269,10 +305,14 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
             HIP_CHECK(hipEventRecord(e0, st));
         }
         const dim3 grid(P.tiles_x * ((prm->height + 3) / 4));
-        if (clamp) {
-            P.radius = (int)clamp->radius; P.gamma = clamp->gamma;
-            hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, st, P);
-        } else hipLaunchKernelGGL(k_temporal<false>, grid, dim3(256), 0, st, P);
+        if (clamp) { P.radius = (int)clamp->radius; P.gamma = clamp->gamma; }
+        if (mom) {
+            if (mom->prev) { P.pm1 = mom->prev->m1; P.pm2 = mom->prev->m2; }
+            P.out_m1 = (float*)mom->out_m1; P.out_m2 = (float*)mom->out_m2;
+            if (clamp) hipLaunchKernelGGL((k_temporal<true, true>), grid, dim3(256), 0, st, P);
+            else hipLaunchKernelGGL((k_temporal<false, true>), grid, dim3(256), 0, st, P);
+        } else if (clamp) hipLaunchKernelGGL((k_temporal<true, false>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((k_temporal<false, false>), grid, dim3(256), 0, st, P);
         HIP_CHECK(hipGetLastError());
         if (info) {
             HIP_CHECK(hipEventRecord(e1, st));
@@ -292,15 +332,19 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
 
 // The host-buffer form: the argument checks, device copies of the inputs, the device form, then the copies back.
 int temporal_host(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                  const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, TemporalCounts* info)
+                  const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, TemporalCounts* info,
+                  const MomentArgs* mom = nullptr)
 {
-    const int rc0 = temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history);
+    const int rc0 = temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history, mom);
     if (rc0 != CRT_OK) return rc0;
     if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
     try {
         HIP_CHECK(hipSetDevice(device));
         const uint64_t npix = (uint64_t)prm->width * prm->height;
         DevBuf<float> c_color, c_var, c_depth, c_normal, p_color, p_var, p_hist, p_depth, p_normal, o_color, o_var, o_hist;
+        DevBuf<float> p_m1, p_m2, o_m1, o_m2;
+        crt_temporal_moment_planes dm{};
+        MomentArgs dmom{};
         DevBuf<int32_t> c_id, p_id;
         DevBuf<uint8_t> o_rgb;
         crt_temporal_frame dc{};
@@ -322,9 +366,24 @@ int temporal_host(const char* who, int device, const crt_temporal_params* prm, c
         o_hist.alloc(npix);
         if (out_variance) o_var.alloc(npix * 3);
         if (out_rgb) o_rgb.alloc(npix * 3);
-        const int rc = temporal_impl(who, device, prm, clamp, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info);
+        if (mom) {
+            if (mom->prev) {
+                dm.m1 = p_m1.upload(mom->prev->m1, npix * 3);
+                dm.m2 = p_m2.upload(mom->prev->m2, npix * 3);
+                dmom.prev = &dm;
+            }
+            o_m1.alloc(npix * 3);
+            o_m2.alloc(npix * 3);
+            dmom.out_m1 = o_m1.p; dmom.out_m2 = o_m2.p;
+        }
+        const int rc = temporal_impl(who, device, prm, clamp, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info,
+                                     mom ? &dmom : nullptr);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
+        if (mom) {
+            o_m1.download((float*)mom->out_m1, npix * 3);
+            o_m2.download((float*)mom->out_m2, npix * 3);
+        }
         o_color.download(out_color, npix * 3);
         o_var.download(out_variance, npix * 3);
         o_hist.download(out_history, npix);
@@ -349,20 +408,23 @@ void fill_info(crt_temporal_clamp_info* info, const TemporalCounts& n)
 
 template <class Info>
 int temporal_device_form(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                         const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* stream, Info* info)
+                         const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, void* stream, Info* info,
+                         const MomentArgs* mom = nullptr)
 {
     TemporalCounts n{};
-    const int rc = temporal_impl(who, device, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, (hipStream_t)stream, info ? &n : nullptr);
+    const int rc = temporal_impl(who, device, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, d_out_rgb, (hipStream_t)stream,
+                                 info ? &n : nullptr, mom);
     if (rc == CRT_OK && info) fill_info(info, n);
     return rc;
 }
 
 template <class Info>
 int temporal_host_form(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                       const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, Info* info)
+                       const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, Info* info,
+                       const MomentArgs* mom = nullptr)
 {
     TemporalCounts n{};
-    const int rc = temporal_host(who, device, prm, clamp, cur, prev, out_color, out_variance, out_history, out_rgb, info ? &n : nullptr);
+    const int rc = temporal_host(who, device, prm, clamp, cur, prev, out_color, out_variance, out_history, out_rgb, info ? &n : nullptr, mom);
     if (rc == CRT_OK && info) fill_info(info, n);
     return rc;
 }
@@ -412,6 +474,24 @@ int crt_temporal_clamped(int device, const crt_temporal_params* prm, const crt_t
                          crt_temporal_clamp_info* info)
 {
     return temporal_host_form("crt_temporal_clamped", device, prm, clamp, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info);
+}
+
+int crt_temporal_moments_device(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* dev_cur,
+                                const crt_temporal_history* dev_prev, const crt_temporal_moment_planes* dev_prev_moments, void* d_out_color,
+                                void* d_out_variance, void* d_out_history, void* d_out_m1, void* d_out_m2, void* d_out_rgb, void* stream,
+                                crt_temporal_clamp_info* info)
+{
+    const MomentArgs mom = {dev_prev_moments, d_out_m1, d_out_m2};
+    return temporal_device_form("crt_temporal_moments_device", device, prm, clamp, dev_cur, dev_prev, d_out_color, d_out_variance, d_out_history, d_out_rgb,
+                                stream, info, &mom);
+}
+
+int crt_temporal_moments(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* host_cur,
+                         const crt_temporal_history* host_prev, const crt_temporal_moment_planes* host_prev_moments, float* out_color,
+                         float* out_variance, float* out_history, float* out_m1, float* out_m2, uint8_t* out_rgb, crt_temporal_clamp_info* info)
+{
+    const MomentArgs mom = {host_prev_moments, out_m1, out_m2};
+    return temporal_host_form("crt_temporal_moments", device, prm, clamp, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info, &mom);
 }
 
 } // extern "C"

@@ -594,6 +594,79 @@ int crt_temporal_clamped_device(int device, const crt_temporal_params* params, c
                                 const crt_temporal_history* dev_prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb,
                                 void* hip_stream, crt_temporal_clamp_info* info);
 
+/* crt_temporal_clamped that also carries the first two moments of what each pixel was seen to show over its history, so that the
+ * variance handed to crt_denoise_var can be measured (crt_variance_estimate, below) instead of carried: two more history planes in
+ * (prev_moments: m1, m2, 3 floats per pixel each, row-major) and two more out (out_m1, out_m2), kept by the caller with the rest of the
+ * history.  Everything of crt_temporal_clamped's definition stands unchanged -- taps, tolerances, ws > 0.015625f, n, a, k, the clamp,
+ * out_color, out_variance, out_history, both counts -- and clamp may be NULL (then crt_temporal's).  In addition, per channel, with
+ * c = color(p):
+ *   for a tap that counts, with the same b:    h1 = h1 + prev.m1(q) * b;   h2 = h2 + prev.m2(q) * b          (both from +0.0f)
+ *   a pixel that takes the history:            h1 = h1 / ws;   h2 = h2 / ws
+ *                                              out_m1 = h1 * k + c * a;    out_m2 = h2 * k + (c * c) * a
+ *   a reset pixel, or no history:              out_m1 = c;                 out_m2 = c * c
+ * Every * + / is one IEEE fp32 operation (no FMA), left to right as written.  The moments are never clamped: m1 is the UNclamped running
+ * mean, so with clamp == NULL the bits of out_m1 are the bits of out_color, and with a clamp they differ on the pixels it moved -- which
+ * is why m1 is carried at all (m2 - out_color^2 would measure the distance to the clamped mean, not the pixel's own noise).
+ * cur.variance / out_variance stay optional, both or neither: at one sample per pixel, where crt_variance has nothing to return, the
+ * caller gives neither.  Non-finite values are not special-cased.
+ * CRT_ERR_INVALID_ARG, checked before any device call: everything crt_temporal_clamped refuses, a NULL out_m1 or out_m2, moment planes
+ * without a history or a history without moment planes, a NULL plane inside a given struct.
+ * Not done here: moments of the luminance alone, of the demodulated colour, a shorter history for clamped pixels. */
+typedef struct { const float* m1; const float* m2; } crt_temporal_moment_planes;  /* 3 floats per pixel each, row-major */
+/* host buffers, as crt_temporal_clamped; clamp may be NULL; host_prev_moments is NULL iff host_prev is NULL; info optional */
+int crt_temporal_moments(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_frame* host_cur,
+                         const crt_temporal_history* host_prev /* may be NULL */, const crt_temporal_moment_planes* host_prev_moments,
+                         float* out_color, float* out_variance, float* out_history, float* out_m1, float* out_m2, uint8_t* out_rgb,
+                         crt_temporal_clamp_info* info);
+/* device buffers on hip_stream, as crt_temporal_clamped_device (info != NULL: counts both, synchronizes the stream) */
+int crt_temporal_moments_device(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_frame* dev_cur,
+                                const crt_temporal_history* dev_prev, const crt_temporal_moment_planes* dev_prev_moments, void* d_out_color,
+                                void* d_out_variance, void* d_out_history, void* d_out_m1, void* d_out_m2, void* d_out_rgb, void* hip_stream,
+                                crt_temporal_clamp_info* info);
+
+/* Variance from temporal moments (SVGF, Schied et al. 2017, section 4.2): what crt_denoise_var takes as `variance`, estimated from what
+ * each pixel was actually seen to do over its history instead of carried along with it.  An image operation: no scene handle, no scratch.
+ * m1, m2, history: what crt_temporal_moments wrote (required); normal, depth: the current frame's AOVs (either may be NULL: its term is
+ * +0.0f).  Output: 3 floats per pixel.  Per pixel p = (x, y) and per channel, with n = history(p), fm = (float)min_history, r = radius:
+ *   temporal branch, n >= fm:
+ *      e = m2(p) - m1(p) * m1(p);   e = e < 0 ? 0 : e   (NaN stays NaN);   var = e
+ *   spatial branch, otherwise (a NaN n lands here): the pixel has not seen enough frames, so its neighbours stand in for them
+ *      taps q = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r inner; a tap outside the image is skipped
+ *        e_n, e_d: exactly crt_denoise's lines (e_d on the relative depth, m > 0 ? r * r : 0)
+ *        w  = exp(-(e_n + e_d))                                                                  (det_expf)
+ *        s1 = s1 + m1(q) * w;   s2 = s2 + m2(q) * w;   sw = sw + w                               (all from +0.0f)
+ *      mu = s1 / sw;   e = s2 / sw - mu * mu;   e = e < 0 ? 0 : e;   var = e * (fm / n)          (the boost SVGF gives a short history)
+ *   of_mean != 0:   ne = n > history_cap ? history_cap : n;   var = var / ne
+ * Every * + - / is one IEEE fp32 operation (no FMA, no reciprocal multiply), left to right as written.  Non-finite inputs are not
+ * special-cased: the arithmetic defines the result.  of_mean = 0 is SVGF's choice, the variance of ONE frame's sample of the pixel;
+ * of_mean = 1 divides by the number of frames the blend can hold (history_cap = 2 / alpha_min - 1 for crt_temporal's defaults), an
+ * estimate of the variance of the accumulated mean itself.  docs/experiments.md, "Variance from temporal moments", has both measured.
+ * crt_variance_estimate_defaults fills min_history 4, radius 3, sigma_normal 0.5, sigma_depth 0.05, of_mean 0, history_cap 39.
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null required pointer, a size of 0, min_history 0, a radius outside 1 .. 3, a
+ * sigma that is not > 0, a history_cap that is < 1 or NaN.  A side longer than 2^24 pixels or more than 2^31 thread blocks of 64 x 4
+ * pixels: CRT_ERR_UNSUPPORTED. */
+typedef struct {
+    uint32_t width, height;
+    uint32_t min_history;     /* below this history length the spatial estimate is used; >= 1 */
+    uint32_t radius;          /* spatial window (2 radius + 1)^2; 1 .. 3 */
+    float sigma_normal, sigma_depth;   /* as crt_denoise's; > 0, not NaN, +inf switches the term off */
+    uint32_t of_mean;         /* 0: variance of one frame's sample (SVGF); 1: divided by the capped history length */
+    float history_cap;        /* of_mean only: n_e = history > cap ? cap : history; >= 1, +inf allowed */
+} crt_variance_estimate_params;
+typedef struct { const float* m1; const float* m2; const float* history; const float* normal; const float* depth; } crt_variance_estimate_inputs;
+typedef struct {
+    float total_ms;        /* HIP-event time of the call's kernel on its stream */
+    uint64_t spatial;      /* pixels that took the spatial branch */
+} crt_variance_estimate_info;
+int crt_variance_estimate_defaults(crt_variance_estimate_params* params);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_variance_estimate(int device, const crt_variance_estimate_params* params, const crt_variance_estimate_inputs* host_in,
+                          float* out_variance, crt_variance_estimate_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then counts the pixels of the spatial branch and synchronizes the stream to read them and the timer). */
+int crt_variance_estimate_device(int device, const crt_variance_estimate_params* params, const crt_variance_estimate_inputs* dev_in,
+                                 void* d_out_variance, void* hip_stream, crt_variance_estimate_info* info);
+
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
  * (config_CUDA, src/main.cu:92-105); a crt_multi holds one device replica of the scene per entry of

@@ -20,10 +20,18 @@ default alpha_min, for every radius of 1, 2, 3 and gamma of --clamp-gammas: the 
 and the share of pixels clamped in the last frame; then the setting with the smallest sum over the sequences of clamped / unclamped
 accumulated error.
 
+--moments: variance from temporal moments (crt_temporal_moments, crt_variance_estimate).  Cost: at each size, taking turns in one loop,
+crt_temporal_clamped_device and crt_temporal_moments_device with the default clamp, the two without a clamp, crt_variance_estimate_device
+on what the moments call wrote -- with min_history 1 (every pixel in the temporal branch), the default 4 on a two-frame history (every
+pixel in the spatial branch, radius 3) and 2 (the reset pixels only) -- and the denoiser.  Effect: the four sequences, unclamped and
+with the default clamp, each accumulated frame under crt_denoise_var fed with (a) the carried variance, (b) the moment estimate with
+of_mean 0, (c) with of_mean 1; then the same at one sample per pixel, where only (b) and (c) exist and the comparison is the last frame
+under crt_denoise.
+
 One JSON line per figure on stderr, one JSON document on stdout.
 
   python tools/temporal_probe.py [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--spp 4] [--error-size 160x120] [--alpha-min 0.05,0.1,0.2]
-                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf]
+                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments]
 """
 import argparse
 import ctypes as C
@@ -63,13 +71,15 @@ def camera_at(t, scene, f):
     return eye, crt.get_inverse_view_matrix(eye, t.lookat + s if with_lookat else t.lookat, t.up), crt.fov_to_radians(t.fov_y)
 
 
-def render_frame(r, cam, spp, seed):
-    """(the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth})"""
+def render_frame(r, cam, spp, seed, variance=True):
+    """(the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth}); variance=False: rendered without the flag (spp 1)"""
     r.set_spp(spp)
     r.seed = seed
-    rgb = r.run_view(*cam, want_variance=True).copy()
+    rgb = r.run_view(*cam, want_variance=variance).copy()
     g = r.run_view_aov(*cam, want=("albedo", "normal", "depth", "material"))
-    cur = {"color": r.mean_buffer.copy(), "variance": r.variance_buffer.copy(), "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
+    cur = {"color": r.mean_buffer.copy(), "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
+    if variance:
+        cur["variance"] = r.variance_buffer.copy()
     return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
 
 
@@ -200,6 +210,112 @@ def effect(a, out):
         print(json.dumps(out["clamp_best"]), file=sys.stderr, flush=True)
 
 
+def moments_cost(a, H, out):
+    scene = "cornell-box"
+    t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+        cams = [camera_at(t, scene, f) for f in (0, 1)]
+        (c0, _, _), (c1, _, g1) = (render_frame(r, cams[f], a.spp, f) for f in (0, 1))
+        r.free()
+        prev = dict(c0, history=np.ones((h, w), dtype=F))
+        host = {"cur_" + k: v for k, v in c1.items()}
+        host.update({"prev_" + k: v for k, v in prev.items()})
+        host.update({"prev_m1": c0["color"], "prev_m2": (c0["color"] * c0["color"]).astype(F), "albedo": g1["albedo"]})
+        scratch_bytes = crt.denoise_scratch_bytes(w, h)
+        ptrs = {}
+        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_color", w * h * 12), ("out_var", w * h * 12), ("out_hist", w * h * 4),
+                                                                                    ("out_rgb", w * h * 3), ("out_m1", w * h * 12), ("out_m2", w * h * 12),
+                                                                                    ("out_est", w * h * 12), ("scratch", scratch_bytes)]:
+            p = C.c_void_p()
+            if H.hipMalloc(C.byref(p), nbytes) != 0:
+                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
+            ptrs[name] = p.value
+        for name, v in host.items():
+            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise RuntimeError("hipMemcpy failed")
+        planes = {"m1": ptrs["prev_m1"], "m2": ptrs["prev_m2"], "out_m1": ptrs["out_m1"], "out_m2": ptrs["out_m2"]}
+
+        def call_temporal(clamp, moments):
+            return crt.temporal_device(w, h, cams[1], {k: ptrs["cur_" + k] for k in c1}, ptrs["out_color"], ptrs["out_hist"],
+                                       out_variance_ptr=ptrs["out_var"], out_rgb_ptr=ptrs["out_rgb"], prev_ptrs={k: ptrs["prev_" + k] for k in prev},
+                                       prev_camera=cams[0], clamp=clamp, moments=planes if moments else None)
+
+        def call_estimate(min_history):
+            return crt.variance_estimate_device(w, h, ptrs["out_m1"], ptrs["out_m2"], ptrs["out_hist"], ptrs["out_est"], normal_ptr=ptrs["cur_normal"],
+                                                depth_ptr=ptrs["cur_depth"], min_history=min_history)
+
+        def call_denoise():
+            return crt.denoise_device(w, h, ptrs["cur_color"], ptrs["out_color"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes,
+                                      albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["cur_normal"], depth_ptr=ptrs["cur_depth"], iterations=3)["total_ms"]
+
+        ms = {k: [] for k in ("clamped", "clamped_moments", "plain", "plain_moments", "estimate_temporal", "estimate_spatial", "estimate_mixed", "denoise3")}
+        info = {}
+        for _ in range(a.warmup + a.calls):
+            for key, clamp, moments in (("clamped", True, False), ("clamped_moments", True, True), ("plain", None, False), ("plain_moments", None, True)):
+                info[key] = call_temporal(clamp, moments)
+                ms[key].append(info[key]["total_ms"])
+            for key, m in (("estimate_temporal", 1), ("estimate_spatial", 4), ("estimate_mixed", 2)):     # (after a moments call: its outputs)
+                info[key] = call_estimate(m)
+                ms[key].append(info[key]["total_ms"])
+            ms["denoise3"].append(call_denoise())
+        med = {k: statistics.median(v[a.warmup:]) for k, v in ms.items()}
+        run = {"width": w, "height": h}
+        run.update({k + "_ms_median": round(v, 4) for k, v in med.items()})
+        run.update({k + "_ms_best_worst": [round(min(ms[k][a.warmup:]), 4), round(max(ms[k][a.warmup:]), 4)] for k in ("clamped_moments", "plain_moments",
+                                                                                                                   "estimate_spatial")})
+        pass_ms = med["denoise3"] / 3
+        run.update({"clamped_moments_over_clamped": round(med["clamped_moments"] / med["clamped"], 4),
+                    "plain_moments_over_plain": round(med["plain_moments"] / med["plain"], 4), "denoise_ms_per_pass_median": round(pass_ms, 4),
+                    "estimate_temporal_over_denoise_pass": round(med["estimate_temporal"] / pass_ms, 4),
+                    "estimate_spatial_over_denoise_pass": round(med["estimate_spatial"] / pass_ms, 4),
+                    "estimate_mixed_over_denoise_pass": round(med["estimate_mixed"] / pass_ms, 4),
+                    "reprojected_fraction": round(info["plain_moments"]["reprojected"] / (w * h), 4),
+                    "spatial_fraction_temporal_spatial_mixed": [round(info[k]["spatial"] / (w * h), 4) for k in ("estimate_temporal", "estimate_spatial",
+                                                                                                                 "estimate_mixed")]})
+        out["moments_cost"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+def moments_effect(a, out):
+    w, h = (int(v) for v in a.error_size.split("x"))
+    for scene in ("cornell-box", "veach-mis"):
+        t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 8, t.P_RR, t.light_sample_n)
+        for moving in (False, True):
+            cams = [camera_at(t, scene, f if moving else 0) for f in range(8)]
+            r.set_spp(256)
+            r.seed = 7
+            ref = r.run_view(*cams[-1]).copy()
+            for spp in (8, 1):
+                frames = [render_frame(r, cams[f], spp, 100 + f, variance=spp > 1) + (cams[f],) for f in range(8)]
+                cur, noisy_rgb, g, _ = frames[-1]
+                run = {"scene": scene, "camera": "moving" if moving else "static", "width": w, "height": h, "spp": spp,
+                       "mse_last_frame": round(mse(noisy_rgb, ref), 1), "mse_last_frame_denoise": round(mse(crt.denoise(cur["color"], **g)[0], ref), 1)}
+                if spp > 1:
+                    run["mse_last_frame_denoise_var"] = round(mse(crt.denoise_var(cur["color"], cur["variance"], **g)[0], ref), 1)
+                for tag, clamp in (("plain", None), ("clamp", True)):
+                    prev = pcam = pm = None
+                    for cur, _, g, cam in frames:
+                        rgb, color, var, hist, m1, m2 = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, clamp=clamp, moments=pm if prev is not None else True)
+                        prev, pcam, pm = dict(cur, color=color, history=hist), cam, {"m1": m1, "m2": m2}
+                        if var is not None:
+                            prev["variance"] = var
+                    run[tag + "_mse_accumulated"] = round(mse(rgb, ref), 1)
+                    if var is not None:
+                        run[tag + "_mse_denoise_var_carried"] = round(mse(crt.denoise_var(color, var, **g)[0], ref), 1)
+                    for of_mean in (0, 1):
+                        e, einfo = crt.variance_estimate(m1, m2, hist, normal=g["normal"], depth=g["depth"], of_mean=of_mean, return_info=True)
+                        run[tag + "_mse_denoise_var_moments_of_mean%d" % of_mean] = round(mse(crt.denoise_var(color, e, **g)[0], ref), 1)
+                    run[tag + "_spatial_last"] = einfo["spatial"]
+                out["moments_effect"].append(run)
+                print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="800x600,3840x2160")
@@ -210,12 +326,21 @@ def main():
     ap.add_argument("--alpha-min", default="0.05,0.1,0.2")
     ap.add_argument("--clamp", action="store_true")
     ap.add_argument("--clamp-gammas", default="0.5,1,1.5,2,3,inf")
+    ap.add_argument("--moments", action="store_true")
     ap.add_argument("--skip-cost", action="store_true")
     ap.add_argument("--skip-effect", action="store_true")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("temporal_probe: no HIP device")
-    out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "clamp_cost": [], "clamp_effect": []}
+    out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "clamp_cost": [], "clamp_effect": [], "moments_cost": [],
+           "moments_effect": []}
+    if a.moments:                                            # (its own tables only: the others are the earlier sections')
+        if not a.skip_cost:
+            moments_cost(a, hip_runtime(), out)
+        if not a.skip_effect:
+            moments_effect(a, out)
+        print(json.dumps(out), flush=True)
+        return
     if not a.skip_cost:
         cost(a, hip_runtime(), out)
     if not a.skip_effect:
