@@ -217,6 +217,21 @@ class AdaptiveInfo(C.Structure):
         return d
 
 
+class MapInfo(C.Structure):
+    _fields_ = [("paths", C.c_uint64), ("paths_uniform", C.c_uint64), ("launches", C.c_uint32), ("max_samples", C.c_uint32),
+                ("kernel_ms", C.c_float), ("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PlanInfo(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("spp", C.c_uint32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # the buffers of crt_aov_buffers: name -> (values per pixel, numpy type)
 AOV_BUFFERS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "coverage": (1, np.float32),
                "tri": (1, np.int32), "material": (1, np.int32)}
@@ -243,7 +258,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
-           "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm"]
+           "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
+           "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device"]
 
 _lib = None
 
@@ -348,6 +364,16 @@ def lib():
     L.crt_image_load.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_uint64]
     L.crt_write_png.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
     L.crt_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    L.crt_render_map.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.POINTER(MapInfo)]
+    L.crt_render_map_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
+    L.crt_sample_plan.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.POINTER(PlanInfo)]
+    L.crt_sample_plan_device.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(PlanInfo)]
+    L.crt_render_planned.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
+    L.crt_render_planned_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
     _lib = L
     return L
 

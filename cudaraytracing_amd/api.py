@@ -180,6 +180,7 @@ class Render:
         self.variance_buffer = None
         self.samples_buffer = None
         self.adaptive_info = None
+        self.map_info = None
         self.temporal_info = None
         self.variance_estimate_info = None
         self.temporal_history_buffer = None
@@ -289,6 +290,89 @@ class Render:
         self.frame_buffer, self.mean_buffer, self.samples_buffer, self.variance_buffer = rgb, mean, samples, var
         self.adaptive_info = info.as_dict()
         return rgb
+
+    def _map_frame(self, what, call, prm, want_variance):
+        """The host form of a call that writes crt_render_map's outputs: call(rgb, mean, samples, var, info) -> status"""
+        w, h = prm.width, prm.height
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        mean = np.zeros((h, w, 3), dtype=np.float32)
+        samples = np.zeros((h, w), dtype=np.uint32)
+        var = np.zeros((h, w, 3), dtype=np.float32) if want_variance else None
+        info = capi.MapInfo()
+        capi.check(call(capi.ptr(rgb), capi.ptr(mean), capi.ptr(samples), capi.ptr(var), C.byref(info)), what)
+        self.frame_buffer, self.mean_buffer, self.samples_buffer, self.variance_buffer = rgb, mean, samples, var
+        self.map_info = info.as_dict()
+        return rgb
+
+    def run_view_map(self, eye_pos, inv_view_mat, fovY, sample_map, sample_begin=0, want_variance=False, width=None, height=None):
+        """A frame with a caller-given number of samples per pixel (crt_render_map, contract: include/crt.h): pixel p gets samples
+        sample_begin .. n_p - 1 of self.spp, n_p = min(max(sample_map[p], max(sample_begin, 1)), spp); sample_map is (H, W), any integer
+        type.  sample_begin > 0 continues the frame in flight (run_view_range(0, sample_begin, want_variance=True)).  Returns the RGB8
+        frame (H, W, 3); self.mean_buffer is its mean, self.samples_buffer the samples per pixel (H, W) uint32, self.variance_buffer
+        (want_variance) the variance of that mean, self.map_info the crt_map_info dict.  No frame is in flight afterwards."""
+        h_ = self._handle("run_view_map")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        m = np.ascontiguousarray(sample_map, dtype=np.uint32)
+        if m.shape != (prm.height, prm.width):
+            raise ValueError("run_view_map needs an (H, W) = (%d, %d) sample map, got %r" % (prm.height, prm.width, m.shape))
+        return self._map_frame("crt_render_map", lambda rgb, mean, samples, var, info: capi.lib().crt_render_map(
+            h_, C.byref(cam), C.byref(prm), capi.ptr(m), int(sample_begin), rgb, mean, samples, var, info), prm, want_variance)
+
+    def run_view_planned(self, eye_pos, inv_view_mat, fovY, min_samples=None, threshold=None, mean_floor=None, want_variance=False,
+                         width=None, height=None):
+        """The adaptive frame in two launches (crt_render_planned): min_samples samples of every pixel, the sample plan made from their
+        variance (sample_plan), the rest of every pixel's samples in one launch per chunk.  None settings take crt_adaptive_defaults.
+        Results as run_view_map; self.map_info counts the warm-up's paths and launches too."""
+        h_ = self._handle("run_view_planned")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        ap = _adaptive_params(min_samples, None, threshold, mean_floor)
+        return self._map_frame("crt_render_planned", lambda rgb, mean, samples, var, info: capi.lib().crt_render_planned(
+            h_, C.byref(cam), C.byref(prm), C.byref(ap), rgb, mean, samples, var, info), prm, want_variance)
+
+    def sample_plan(self, threshold=None, mean_floor=None, width=None, height=None):
+        """(map (H, W) uint32, samples done) of crt_sample_plan: the samples each pixel needs for the standard error of its mean to
+        reach threshold x (mean + mean_floor), from the sums of the frame in flight (ranges with want_variance).  Reads only; the map
+        is what run_view_map takes with sample_begin = samples done.  None settings take crt_adaptive_defaults."""
+        h_ = self._handle("sample_plan")
+        ap = _adaptive_params(None, None, threshold, mean_floor)
+        w, h = width or self.scene.width, height or self.scene.height
+        m = np.zeros((h, w), dtype=np.uint32)
+        info = capi.PlanInfo()
+        capi.check(capi.lib().crt_sample_plan(h_, ap.threshold, ap.mean_floor, capi.ptr(m), C.byref(info)), "crt_sample_plan")
+        return m, int(info.samples)
+
+    def _map_device(self, what, call, ptrs, stream, want_info):
+        info = capi.MapInfo()
+        out = [C.c_void_p(ptrs[n]) if ptrs.get(n) else None for n in ("rgb", "mean", "samples", "variance")]
+        capi.check(call(*out, C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None), what)
+        if want_info:
+            self.map_info = info.as_dict()
+        return self.map_info if want_info else None
+
+    def run_view_map_device(self, eye_pos, inv_view_mat, fovY, d_map_ptr, ptrs, sample_begin=0, stream=None, rank=0, world=1, tiled=False,
+                            want_info=True, width=None, height=None):
+        """crt_render_map_device: d_map_ptr a raw device pointer to the (H, W) uint32 map, ptrs = {"rgb", "mean", "samples", "variance":
+        raw device pointer or None} (row-major, or the shard's compact tiles with tiled / world > 1), work enqueued on `stream`.  The
+        call synchronizes the stream once (twice with want_info, which sets self.map_info)."""
+        h_ = self._handle("run_view_map_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
+        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        return self._map_device("crt_render_map_device", lambda rgb, mean, samples, var, st, info: capi.lib().crt_render_map_device(
+            h_, C.byref(cam), C.byref(prm), C.c_void_p(d_map_ptr), int(sample_begin), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
+
+    def run_view_planned_device(self, eye_pos, inv_view_mat, fovY, ptrs, min_samples=None, threshold=None, mean_floor=None, stream=None,
+                                rank=0, world=1, tiled=False, want_info=True, width=None, height=None):
+        """crt_render_planned_device: outputs and synchronization as run_view_map_device."""
+        h_ = self._handle("run_view_planned_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
+        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        ap = _adaptive_params(min_samples, None, threshold, mean_floor)
+        return self._map_device("crt_render_planned_device", lambda rgb, mean, samples, var, st, info: capi.lib().crt_render_planned_device(
+            h_, C.byref(cam), C.byref(prm), C.byref(ap), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
 
     def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
                        want_variance=False, stats=False):
@@ -589,6 +673,21 @@ class MultiRender(Render):
 
     def run_view_adaptive(self, *a, **k):
         raise NotImplementedError("adaptive sampling is a single-device interface (crt_render_adaptive)")
+
+    def run_view_map(self, *a, **k):
+        raise NotImplementedError("sample maps are a single-device interface (crt_render_map)")
+
+    def run_view_map_device(self, *a, **k):
+        raise NotImplementedError("sample maps are a single-device interface (crt_render_map_device)")
+
+    def run_view_planned(self, *a, **k):
+        raise NotImplementedError("planned adaptive frames are a single-device interface (crt_render_planned)")
+
+    def run_view_planned_device(self, *a, **k):
+        raise NotImplementedError("planned adaptive frames are a single-device interface (crt_render_planned_device)")
+
+    def sample_plan(self, *a, **k):
+        raise NotImplementedError("the sample plan is a single-device interface (crt_sample_plan)")
 
     def preview(self, *a, **k):
         raise NotImplementedError("previews are a single-device interface (crt_preview)")

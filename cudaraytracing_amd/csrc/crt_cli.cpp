@@ -8,7 +8,7 @@
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
 //           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
-//           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]
+//           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]]
 // --temporal N renders N frames on one device and accumulates them over time (crt_temporal, its defaults): frame f = 0 .. N-1 has eye and
@@ -23,7 +23,9 @@
 // --adaptive THRESHOLD renders the frame with variance-driven adaptive sampling (crt_render_adaptive, one device): --spp is the cap, a
 // pixel stops once the standard error of its mean is at most THRESHOLD x (mean + floor); --adaptive-min / --adaptive-step override the
 // warm-up and the samples per pass of crt_adaptive_defaults, --adaptive-samples PATH writes the samples per pixel as a 1-channel PFM.
-// --variance, --denoise and --aov work on the adaptive frame as on the uniform one.
+// --variance, --denoise and --aov work on the adaptive frame as on the uniform one.  --adaptive-planned renders it in two launches
+// instead (crt_render_planned): the warm-up, then every pixel's remaining samples as planned from the warm-up's variance; --adaptive-step
+// does not apply.
 // --variance PATH renders with CRT_FLAG_VARIANCE (the frame is the same bits) and writes the per-pixel variance of the mean
 // (crt_variance, one device) as a 3-channel PFM.  --denoise-variance makes --denoise use the variance-guided filter (crt_denoise_var,
 // its own defaults; --denoise-iterations / --denoise-sigma override them as well).
@@ -51,7 +53,7 @@ int main(int argc, char** argv)
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
-                             "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH]\n"
+                             "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n", argv[0]);
         return 2;
@@ -62,7 +64,7 @@ int main(int argc, char** argv)
         std::string out = "out.png", base_dir = ".", aov, denoise, variance, adaptive_samples;
         crt_adaptive_params ad;
         crt_adaptive_defaults(&ad);
-        bool adaptive = false, ad_option = false;
+        bool adaptive = false, ad_option = false, planned = false;
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false;
@@ -122,6 +124,7 @@ int main(int argc, char** argv)
             else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-step") { need(i, 1); ad.step_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-samples") { need(i, 1); adaptive_samples = argv[++i]; ad_option = true; }
+            else if (a == "--adaptive-planned") { planned = true; ad_option = true; }
             else if (a == "--temporal") {
                 need(i, 1);
                 temporal = std::atoi(argv[++i]);
@@ -210,7 +213,7 @@ int main(int argc, char** argv)
         if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
         if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp and --temporal-variance need --temporal N");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
-        if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step and --adaptive-samples need --adaptive THRESHOLD");
+        if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
         const bool want_var = !variance.empty() || denoise_var || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
@@ -256,10 +259,15 @@ int main(int argc, char** argv)
                                                   render.last_variance_estimate_info().total_ms);
             }
         }
+        else if (adaptive && planned) render.run_view_planned(task.eye_pos, inv_view, fov_y, ad, want_var);
         else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
         else render.run_view(task.eye_pos, inv_view, fov_y);
         std::chrono::duration<double> dt = std::chrono::high_resolution_clock::now() - t0;
-        if (adaptive) {
+        if (adaptive && planned) {
+            const crt_map_info& mi = render.last_map_info();
+            std::printf("render cost: %.6f seconds (device %.3f ms, planned: %u launches, %llu of %llu paths)\n", dt.count(), mi.total_ms, mi.launches,
+                        (unsigned long long)mi.paths, (unsigned long long)mi.paths_uniform);
+        } else if (adaptive) {
             const crt_adaptive_info& ai = render.last_adaptive_info();
             std::printf("render cost: %.6f seconds (device %.3f ms, adaptive: %u passes, %llu of %llu paths)\n", dt.count(), ai.total_ms, ai.passes,
                         (unsigned long long)ai.paths, (unsigned long long)ai.paths_uniform);

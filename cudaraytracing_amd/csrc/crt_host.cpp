@@ -678,10 +678,11 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view failed: ") + crt_last_error());
 }
 
-void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+// the arguments and buffers run_view_adaptive, run_view_map and run_view_planned share: `render` makes the library call on them
+template <class Call> void Render::sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render)
 {
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_view_adaptive: adaptive sampling is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view_adaptive after free()");
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
     crt_camera cam;
     std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
     std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
@@ -695,10 +696,30 @@ void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[
     samples_buffer_.assign(n, 0u);
     variance_buffer_.clear();
     std::vector<float> v(want_variance ? 3 * n : 0, 0.0f);
-    const int rc = crt_render_adaptive(device_scene_, &cam, &p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(),
-                                       want_variance ? v.data() : nullptr, &adaptive_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view_adaptive failed: ") + crt_last_error());
+    const int rc = render(&cam, &p, want_variance ? v.data() : nullptr);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
     variance_buffer_.swap(v);
+}
+
+void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+{
+    sampled_frame("Render::run_view_adaptive", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_adaptive(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &adaptive_info_);
+    });
+}
+
+void Render::run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin, bool want_variance)
+{
+    sampled_frame("Render::run_view_map", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_map(device_scene_, cam, p, sample_map, sample_begin, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
+    });
+}
+
+void Render::run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+{
+    sampled_frame("Render::run_view_planned", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_planned(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
+    });
 }
 
 void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)

@@ -218,7 +218,12 @@ public:
     // run_view leaves them, the samples per pixel in get_samples_buffer, and with want_variance the variance of the mean in variance();
     // CRT_FLAG_STATS / _BOUNDED_RADIANCE do not apply; one device only
     void run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance = false);
-    const uint32_t* get_samples_buffer() const { return samples_buffer_.data(); } // W x H, after run_view_adaptive
+    // the frame of crt_render_map (sample_map: W x H counts, row 0 = image top; sample_begin > 0 continues the frame in flight) and of
+    // crt_render_planned (ap.step_samples is ignored): buffers as run_view_adaptive leaves them, the call's figures in last_map_info
+    void run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin = 0, bool want_variance = false);
+    void run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance = false);
+    const crt_map_info& last_map_info() const { return map_info_; }
+    const uint32_t* get_samples_buffer() const { return samples_buffer_.data(); } // W x H, after run_view_adaptive / _map / _planned
     const crt_adaptive_info& last_adaptive_info() const { return adaptive_info_; }
     // first-hit albedo, normal and depth of the frame run_view draws with the same camera and settings (crt_render_aov); one device only
     void run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY);
@@ -313,6 +318,8 @@ private:
     crt_variance_estimate_info estimate_info_{};
     void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm);
     crt_adaptive_info adaptive_info_{};
+    crt_map_info map_info_{};
+    template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);
     int device_ = 0;
     crt_denoise_info denoise_info_{};
     crt_stats stats_{};

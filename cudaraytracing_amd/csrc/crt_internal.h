@@ -168,12 +168,13 @@ __device__ __forceinline__ void acc_store3(float* planes, const uint32_t nslots,
 // The radiance is read with ONE plain 12-byte load per sample: the launch that wrote it has ended, and a kernel boundary makes its stores
 // visible (docs/experiments.md 6.14; the three 4-byte agent-scope loads per sample that stood here since round 5 cost more than a quarter
 // of k_accumulate).  The sums keep their agent scope: launches with the commit ring write them from inside the launch.
-template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& A, const uint32_t slot, F3& c, F3& q)
+// fold_samples_n: the first `count` samples of the chunk.
+template <bool VAR> __device__ __forceinline__ void fold_samples_n(const AParams& A, const uint32_t slot, const uint32_t count, F3& c, F3& q)
 {
     const float fspp = (float)A.spp;
     const Rad3* lp = A.L + slot;
 #pragma unroll 4
-    for (uint32_t s = 0; s < A.chunk_samples; s++, lp += A.nslots) {
+    for (uint32_t s = 0; s < count; s++, lp += A.nslots) {
         const Rad3 l = load_radiance(lp);
         if (VAR) {
             const float xx = l.x / fspp, xy = l.y / fspp, xz = l.z / fspp;
@@ -186,6 +187,8 @@ template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& 
         }
     }
 }
+// every slot takes the whole chunk (the frame kernels, an adaptive pass); fold_samples_n with a count of its own per slot: a sample map
+template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& A, const uint32_t slot, F3& c, F3& q) { fold_samples_n<VAR>(A, slot, A.chunk_samples, c, q); }
 
 // the variance of the mean from the sums c and q (contract: crt_variance, include/crt.h); rr = (fs / fn)^2
 __device__ __forceinline__ float variance_of(const float c, const float q, const float fn, const float rr)
@@ -278,6 +281,30 @@ void launch_adaptive_select(const AdaptiveParams& D, hipStream_t st);     // the
 void launch_adaptive_items(uint32_t* item_list, const uint32_t* list, uint32_t n_active, uint32_t n_items, uint32_t nslots, hipStream_t st);
 void launch_adaptive_accumulate(const AdaptiveParams& D, hipStream_t st); // the chunk's samples into c and q of the active slots
 void launch_adaptive_resolve(const AdaptiveParams& D, hipStream_t st);    // mean, RGB, samples, variance in the output layout
+
+// sample maps (crt_sample_map.hip; host side: crt_render_map, crt_sample_plan and crt_render_planned in crt_render.hip; contract:
+// include/crt.h).  The count plane n_p is the adaptive frame's (AdaptiveParams::nsamp: k_adaptive_resolve makes the frame from it); the
+// histogram and the cursors live in uncached memory and are accessed with agent-scope atomics only, as the planes are.
+struct MapParams {
+    AParams A;               // the frame's layout and sums; L, first_chunk: the chunk k_map_fold folds in
+    float* qacc;
+    uint32_t* nsamp;         // [nslots] n_p (padding slots: 0)
+    const uint32_t* map;     // k_map_prepare: the caller's counts, one per pixel of the W x H image (row-major) or, map_per_slot, per pixel slot
+    uint32_t map_per_slot;
+    uint32_t sample_begin;   // k_map_prepare: the samples every pixel has already
+    unsigned int* hist;      // k_map_prepare: [spp + 1] slots per value of n_p, zeroed before the launch
+    unsigned int* cursor;    // k_map_items: [spp] where the next entry of sample s goes in its chunk's list
+    uint32_t* item_list;     // k_map_items: n_items entries
+    uint32_t n_items;
+    uint32_t s0, ns;         // k_map_items, k_map_fold: the chunk's samples [s0, s0 + ns)
+    uint32_t n;              // k_sample_plan: samples in the sums
+    float threshold, mean_floor;
+    uint32_t* out_map;       // k_sample_plan: in the frame's output layout
+};
+void launch_map_prepare(const MapParams& D, hipStream_t st);
+void launch_map_items(const MapParams& D, hipStream_t st);
+void launch_map_fold(const MapParams& D, hipStream_t st);
+void launch_sample_plan(const MapParams& D, hipStream_t st);
 
 } // namespace crtk
 #endif

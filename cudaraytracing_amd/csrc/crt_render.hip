@@ -1,7 +1,8 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
 // pipeline, the passes of an adaptive frame, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*,
-// crt_render_adaptive*, crt_preview*, crt_variance*, crt_render_aov*, crt_intersect, crt_device_*).  The scene handle is made in
-// crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_aov.hip.
+// crt_render_adaptive*, crt_render_map*, crt_sample_plan*, crt_render_planned*, crt_preview*, crt_variance*, crt_render_aov*, crt_intersect,
+// crt_device_*).  The scene handle is made in
+// crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_sample_map.hip, crt_aov.hip.
 // The slot map of a shard and the host's form of the slot rule: crt_scene.h; host-buffer copies: DevBuf::upload / download.
 #include "crt_scene.h"
 
@@ -228,10 +229,17 @@ AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh)
 // A pass of crt_render_adaptive, as render_impl sees it: a sample range of a frame with CRT_FLAG_VARIANCE whose sums are resolved by
 // the adaptive loop, not by the range that ends at spp.  list == nullptr: the warm-up, every pixel slot takes the range; otherwise only
 // the n_active slots of `list` (device memory) do, and D names the planes k_adaptive_accumulate updates.
+// map != nullptr: the range is the launches of crt_render_map instead -- every pixel slot takes its own number of the range's samples
+// (MapPass), list / n_active / D are not used.
+struct MapPass {
+    MapParams D;                       // the count plane, the cursors and the sums: what k_map_items and k_map_fold take
+    std::vector<uint32_t> chunk_items; // work items of chunk 0, 1, ... of the range: the slots with n_p > s, summed over the chunk's samples
+};
 struct AdaptivePass {
     const uint32_t* list;
     uint32_t n_active;
     AdaptiveParams D;
+    const MapPass* map;
 };
 
 // One call of render_impl, as its two pipelines see it
@@ -250,7 +258,8 @@ struct Frame {
     bool want_stats, tiled, want_var, var_frame;
     AParams A;
     const AdaptivePass* ad; // crt_render_adaptive only
-    bool sparse() const { return ad && ad->list; }
+    bool sparse() const { return ad && (ad->list || ad->map); } // the launch's work items come from a list
+    const MapPass* map() const { return ad ? ad->map : nullptr; }
 };
 
 // What both pipelines put into LParams: camera, size, shard, divisions, the handle's buffers
@@ -273,11 +282,12 @@ LParams frame_lparams(const Frame& f)
     return P;
 }
 
-// The work items of samples [s0, s0 + ns): one per pixel slot (an adaptive pass: per active slot) and sample, in ITEM_SHARDS cursor shards
-void set_chunk(LParams& P, uint32_t s0, uint32_t ns, uint32_t per_sample)
+// The n_items work items of the chunk of samples that starts at s0 -- one per pixel slot and sample; an adaptive pass: per active slot
+// and sample; a sample map: per sample the slots that take it -- in ITEM_SHARDS cursor shards
+void set_chunk(LParams& P, uint32_t s0, uint32_t n_items)
 {
     P.sample_begin = s0;
-    P.n_items = (uint32_t)((uint64_t)ns * per_sample);
+    P.n_items = n_items;
     P.items_per_shard = ((P.n_items + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
 }
 
@@ -291,7 +301,11 @@ void accumulate_chunk(Frame& f, uint32_t s0, uint32_t ns)
     A.first_chunk = s0 == 0; A.last_chunk = !f.ad && s0 + ns >= f.prm->spp; // (an adaptive frame is resolved by k_adaptive_resolve)
     if (f.ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
     if (!f.ring.samples || A.last_chunk) {
-        if (f.sparse()) { // only the slots that took the pass
+        if (f.map()) { // every slot its own number of the chunk's samples
+            MapParams D = f.map()->D;
+            D.A = A; D.s0 = s0; D.ns = ns;
+            launch_map_fold(D, f.st);
+        } else if (f.sparse()) { // only the slots that took the pass
             AdaptiveParams D = f.ad->D;
             D.A = A; D.n = s0 + ns;
             launch_adaptive_accumulate(D, f.st);
@@ -366,7 +380,10 @@ void render_mega(Frame& f)
     const RingPlan& ring = f.ring;
     hipStream_t st = f.st;
     const bool timing = f.stats != nullptr;
-    const uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots : f.sparse() ? (uint64_t)f.chunk * f.ad->n_active : f.cap;
+    const uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots
+        : f.map()                            ? *std::max_element(f.map()->chunk_items.begin(), f.map()->chunk_items.end())
+        : f.sparse()                         ? (uint64_t)f.chunk * f.ad->n_active
+                                             : f.cap;
     const MegaPlan mp = plan_mega3(sc, prm->traversal, f.want_stats, (prm->flags & CRT_FLAG_TRACE_ALL) != 0, false, ring.samples != 0, most_items, env_u32("CRT_MEGA_BLOCKS_PER_CU", 64));
     const uint32_t lanes = mp.lanes;
     sc->p_vx.ensure(lanes); sc->p_la.ensure(lanes); sc->p_cc.ensure(lanes); sc->p_id.ensure(lanes);
@@ -391,7 +408,7 @@ void render_mega(Frame& f)
     uint32_t launches = 0;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
-        set_chunk(P, s0, ns, f.sparse() ? f.ad->n_active : P.nslots);
+        set_chunk(P, s0, f.map() ? f.map()->chunk_items[launches] : (uint32_t)((uint64_t)ns * (f.sparse() ? f.ad->n_active : P.nslots)));
         if (ring.samples) { // cursor shard = ring.spsh pixel slots x ns samples
             P.items_per_shard = ring.spsh * ns;
             P.n_items = P.items_per_shard * ring.shards;
@@ -415,7 +432,14 @@ void render_mega(Frame& f)
             // which names the frame's own work item (sample, slot) of every position: k_mega3 decodes it and writes L[item] as ever
             P.order_window = P.items_per_shard;
             sc->item_list.ensure(P.n_items);
-            launch_adaptive_items(sc->item_list.p, f.ad->list, f.ad->n_active, P.n_items, P.nslots, st);
+            if (f.map()) { // (a sample map: the slots with n_p > s, sample by sample)
+                MapParams D = f.map()->D;
+                D.item_list = sc->item_list.p; D.n_items = P.n_items; D.s0 = s0; D.ns = ns;
+                // (the kernel fills every position when the histogram is the count plane's; cleared first, so that a position it did not
+                // fill names work item 0 of the chunk, inside L, not what an earlier launch left there)
+                HIP_CHECK(hipMemsetAsync(sc->item_list.p, 0, (size_t)P.n_items * sizeof(uint32_t), st));
+                launch_map_items(D, st);
+            } else launch_adaptive_items(sc->item_list.p, f.ad->list, f.ad->n_active, P.n_items, P.nslots, st);
             HIP_CHECK(hipGetLastError());
             P.item_list = sc->item_list.p;
         } else {
@@ -527,7 +551,7 @@ void render_wavefront(Frame& f)
     const int evs_per_half = 2 * kMaxBatch + 1;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
-        set_chunk(P, s0, ns, P.nslots);
+        set_chunk(P, s0, (uint32_t)((uint64_t)ns * P.nslots));
         HIP_CHECK(hipMemsetAsync(sc->item_next.p, 0, (size_t)ITEM_SHARDS * ITEM_STRIDE * sizeof(unsigned int), st));
         for (int h = 0; h < n_halves; h++) {
             PH[h] = P;
@@ -595,6 +619,14 @@ void render_wavefront(Frame& f)
     }
 }
 
+// Samples per launch of a range of s_count samples without the commit ring: as many whole samples of every pixel slot as kMaxChunkItems
+// paths hold, at least one
+uint32_t chunk_samples(uint32_t nslots, uint32_t s_count)
+{
+    const uint64_t max_items = std::min<uint64_t>(kMaxChunkItems, 1ull << std::min(30u, env_u32("CRT_CHUNK_LOG2", 30))); // (test hook: small chunks)
+    return (uint32_t)std::min<uint64_t>(s_count, std::max<uint64_t>(1, max_items / nslots));
+}
+
 // What crt_render refuses in a crt_params by itself (no scene, no sample range), before any device call
 int params_check(const crt_params* prm)
 {
@@ -638,8 +670,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
     try {
         HIP_CHECK(hipSetDevice(sc->device));
         f.sh = make_shard(prm->width, prm->height, prm->world);
-        const uint64_t max_items = std::min<uint64_t>(kMaxChunkItems, 1ull << std::min(30u, env_u32("CRT_CHUNK_LOG2", 30))); // (test hook: small chunks)
-        f.chunk = (uint32_t)std::min<uint64_t>(s_count, std::max<uint64_t>(1, max_items / f.sh.nslots));
+        f.chunk = chunk_samples(f.sh.nslots, s_count);
         f.cap = (uint64_t)f.chunk * f.sh.nslots;
         const bool mega = choose_pipeline(sc) == 4;
         f.ring = plan_ring(sc, prm, f.sh, s_count, mega, f.want_stats, f.want_var);
@@ -787,6 +818,194 @@ int adaptive_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, c
     }
 }
 
+// ---------- crt_render_map, crt_sample_plan, crt_render_planned (contract: include/crt.h): per-pixel sample counts in one launch per chunk ----------
+const uint32_t kMaxMapSpp = 1u << 24; // (the histogram and the cursors: 8 B per sample of the cap on the device, as much pinned)
+
+int threshold_check(const char* who, float threshold, float mean_floor)
+{
+    if (!(threshold >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": threshold must be >= 0 and not NaN");
+    if (!(mean_floor >= 0.0f) || mean_floor > FLT_MAX) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": mean_floor must be >= 0 and finite");
+    return CRT_OK;
+}
+
+// Argument checks of crt_render_map* (planned == nullptr) and crt_render_planned*, before any device call; the scene comes last, as in
+// adaptive_check
+int map_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const void* map, uint32_t s_begin, const crt_adaptive_params* planned,
+              bool is_planned, const void* out_rgb, const void* out_mean)
+{
+    const char* who = is_planned ? "crt_render_planned" : "crt_render_map";
+    const std::string w(who);
+    if (!cam) return fail(CRT_ERR_INVALID_ARG, w + ": null camera");
+    if (!prm) return fail(CRT_ERR_INVALID_ARG, w + ": null params");
+    if (is_planned && !planned) return fail(CRT_ERR_INVALID_ARG, w + ": null adaptive params");
+    if (!is_planned && !map) return fail(CRT_ERR_INVALID_ARG, w + ": null sample map");
+    if (!out_rgb && !out_mean) return fail(CRT_ERR_INVALID_ARG, w + ": out_rgb and out_mean are both null");
+    if (is_planned) {
+        if (planned->min_samples < 2 || planned->min_samples > prm->spp) return fail(CRT_ERR_INVALID_ARG, w + ": min_samples must be in [2, spp] (the variance needs two samples)");
+        const int rc = threshold_check(who, planned->threshold, planned->mean_floor);
+        if (rc != CRT_OK) return rc;
+    }
+    const int rc = params_check(prm);
+    if (rc != CRT_OK) return rc;
+    if (!is_planned && s_begin >= prm->spp) return fail(CRT_ERR_INVALID_ARG, w + ": sample_begin must be below spp");
+    if (prm->spp > kMaxMapSpp) return fail(CRT_ERR_UNSUPPORTED, w + ": spp above 2^24");
+    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > kMaxChunkItems) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^30 pixel slots in a shard");
+    if (!sc) return fail(CRT_ERR_INVALID_ARG, w + ": null scene");
+    if (choose_pipeline(sc) != 4) return fail(CRT_ERR_UNSUPPORTED, w + ": the fallback pipeline hands out its work items without the item list");
+    if (!is_planned && s_begin > 0) {
+        const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
+        if (!continues_frame(sc->acc, prm, s_begin, tiled) || !sc->var.valid || !continues_frame(sc->var, prm, s_begin, tiled))
+            return fail(CRT_ERR_INVALID_ARG, w + ": sample_begin " + std::to_string(s_begin) + " must continue the frame in flight: exactly samples [0, sample_begin) of every pixel "
+                                             "with CRT_FLAG_VARIANCE from sample 0 on, and the same spp, width, height, rank, world and CRT_FLAG_TILED_OUTPUT (" +
+                                             (sc->acc.samples == 0 ? std::string("no frame is in flight on the handle")
+                                                                   : "the frame in flight holds samples [0, " + std::to_string(sc->acc.samples) + ") of spp " + std::to_string(sc->acc.spp) +
+                                                                         (sc->var.valid ? ", with" : ", without") + " valid variance sums") + ")");
+    }
+    return CRT_OK;
+}
+
+// Both calls.  planned == nullptr: d_map is the caller's W x H map and s_begin its sample_begin.  Otherwise the warm-up range and the
+// plan come first, and the map is the plan's, per pixel slot, on the device all the way.
+int map_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* d_map, uint32_t s_begin, const crt_adaptive_params* planned,
+             bool is_planned, void* d_rgb, void* d_mean, void* d_samples, void* d_var, hipStream_t st, crt_map_info* info)
+{
+    const int rc0 = map_check(sc, cam, prm, d_map, s_begin, planned, is_planned, d_rgb, d_mean);
+    if (rc0 != CRT_OK) return rc0;
+    crt_params p = *prm; // ranges of a frame with the variance sums, without counters and without the commit ring
+    p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE);
+    const bool tiled = (p.flags & CRT_FLAG_TILED_OUTPUT) != 0;
+    const Shard sh = make_shard(p.width, p.height, p.world);
+    const uint32_t S = p.spp;
+    struct EndFrame { // whatever happens from here on, no frame is in flight on the handle afterwards
+        crt_scene* sc;
+        ~EndFrame() { sc->acc.samples = 0; sc->var.valid = false; }
+    } end_frame{sc};
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (info) {
+            ensure_events(sc);
+            e0 = sc->ev[0]; e1 = sc->ev[1];
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        // (before anything takes their addresses: render_impl's own calls then find them in place)
+        sc->accum.ensure_uncached((size_t)sh.nslots * 3); sc->accum_q.ensure_uncached((size_t)sh.nslots * 3);
+        sc->ad_nsamp.ensure_uncached(sh.nslots); sc->ad_list.ensure_uncached(sh.nslots);
+        sc->map_hist.ensure_uncached((size_t)S + 1); sc->map_cursor.ensure_uncached(S);
+        const size_t words = 2 * ((size_t)S + 1);
+        if (sc->h_map_words < words) {
+            if (sc->h_map) { (void)hipHostFree(sc->h_map); sc->h_map = nullptr; sc->h_map_words = 0; }
+            HIP_CHECK(hipHostMalloc((void**)&sc->h_map, words * sizeof(unsigned int), hipHostMallocDefault));
+            sc->h_map_words = words;
+        }
+        unsigned int* const h_hist = sc->h_map;
+        unsigned int* const h_cursor = sc->h_map + S + 1;
+        AdaptivePass pass;
+        std::memset(&pass, 0, sizeof(pass));
+        uint32_t warm_launches = 0;
+        if (is_planned) { // the warm-up: crt_render_range(0, min_samples) with the variance sums
+            s_begin = planned->min_samples;
+            const int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, 0, s_begin, &pass);
+            if (rc != CRT_OK) return rc;
+            warm_launches = sc->last_launches;
+        }
+        FrameMark mark;
+        mark.set(&p, 0, tiled);
+        MapPass mp;
+        std::memset(&mp.D, 0, sizeof(mp.D));
+        MapParams& D = mp.D;
+        D.A = frame_aparams(sc, mark, sh);
+        D.qacc = sc->accum_q.p; D.nsamp = sc->ad_nsamp.p; D.hist = sc->map_hist.p; D.cursor = sc->map_cursor.p;
+        D.sample_begin = s_begin;
+        D.map = d_map;
+        if (is_planned) { // the plan at n = min_samples, one count per pixel slot
+            MapParams Q = D;
+            Q.A.tiled_output = 1u;
+            Q.n = s_begin; Q.threshold = planned->threshold; Q.mean_floor = planned->mean_floor; Q.out_map = sc->ad_list.p;
+            launch_sample_plan(Q, st);
+            HIP_CHECK(hipGetLastError());
+            D.map = sc->ad_list.p; D.map_per_slot = 1u;
+        }
+        HIP_CHECK(hipMemsetAsync(sc->map_hist.p, 0, ((size_t)S + 1) * sizeof(unsigned int), st));
+        launch_map_prepare(D, st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(h_hist, sc->map_hist.p, ((size_t)S + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of the call: how many slots take each sample
+        double kernel_ms = 0.0;
+        if (info && warm_launches) {
+            float ms = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1));
+            kernel_ms += ms;
+        }
+        // count_s = slots with n_p > s, from the top of the histogram down (h_hist[0]: the padding slots)
+        crt_map_info I;
+        std::memset(&I, 0, sizeof(I));
+        uint32_t max_np = 0;
+        uint64_t pixels = 0, all_samples = 0;
+        for (uint32_t v = 1; v <= S; v++) {
+            const uint64_t c = std::min<uint32_t>(h_hist[v], sh.nslots);
+            pixels += c; all_samples += c * v;
+            if (c) max_np = v;
+        }
+        pixels = std::min<uint64_t>(pixels, sh.nslots); // (a histogram that is not one cannot size a list beyond the chunk)
+        I.max_samples = max_np; I.launches = warm_launches;
+        I.paths = all_samples - (is_planned ? 0u : pixels * s_begin); // (n_p >= sample_begin at every pixel)
+        I.paths_uniform = pixels * S;
+        if (max_np > s_begin) {
+            const uint32_t s_count = max_np - s_begin, chunk = chunk_samples(sh.nslots, s_count);
+            uint64_t above = 0; // slots with n_p > s
+            std::vector<uint32_t> count(s_count);
+            for (uint32_t s = max_np; s-- > s_begin;) {
+                above = std::min<uint64_t>(above + h_hist[s + 1], sh.nslots);
+                count[s - s_begin] = (uint32_t)above;
+            }
+            for (uint32_t s0 = s_begin; s0 < max_np; s0 += chunk) {
+                uint64_t at = 0; // (at most chunk x nslots <= 2^30)
+                for (uint32_t s = s0; s < std::min(s0 + chunk, max_np); s++) { h_cursor[s] = (unsigned int)at; at += count[s - s_begin]; }
+                mp.chunk_items.push_back((uint32_t)at);
+            }
+            HIP_CHECK(hipMemcpyAsync(sc->map_cursor.p + s_begin, h_cursor + s_begin, (size_t)s_count * sizeof(unsigned int), hipMemcpyHostToDevice, st));
+            pass.map = &mp;
+            const int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, s_begin, s_count, &pass);
+            if (rc != CRT_OK) return rc;
+            I.launches += (uint32_t)mp.chunk_items.size();
+        }
+        AdaptiveParams R; // the frame: k_adaptive_resolve on the count plane and the sums
+        std::memset(&R, 0, sizeof(R));
+        R.A = D.A; R.qacc = D.qacc; R.nsamp = D.nsamp;
+        R.A.out_rgb = (uint8_t*)d_rgb; R.A.out_mean = (float*)d_mean;
+        R.out_samples = (uint32_t*)d_samples; R.out_variance = (float*)d_var;
+        launch_adaptive_resolve(R, st);
+        HIP_CHECK(hipGetLastError());
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            if (I.launches > warm_launches) {
+                float ms = 0.0f;
+                HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1));
+                kernel_ms += ms;
+            }
+            I.kernel_ms = (float)kernel_ms;
+            HIP_CHECK(hipEventElapsedTime(&I.total_ms, e0, e1));
+            *info = I;
+        }
+        return CRT_OK;
+    } catch (const HipFail& e) {
+        return fail_hip(e);
+    }
+}
+
+// Argument checks of both forms of crt_sample_plan, before any device call
+int plan_check(const crt_scene* sc, float threshold, float mean_floor, const void* out)
+{
+    if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: null argument");
+    const int rc = threshold_check("crt_sample_plan", threshold, mean_floor);
+    if (rc != CRT_OK) return rc;
+    if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
+    if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: fewer than 2 samples accumulated (one sample has no variance)");
+    return CRT_OK;
+}
+
 // The first-hit AOV pass (crt_render_aov): the camera rays of samples 0 .. spp-1 of every pixel slot of the shard, in chunks of whole
 // samples of at most kAovChunkRays rays (32 B of query pool + 16 B of results per ray: 1.6 GB), each traced by trace_queries and folded
 // into the per-slot running sums in sample order (k_aov_resolve).  Uses the handle's query pool and trace buffers, as crt_intersect does;
@@ -906,6 +1125,30 @@ struct Staging {
     }
 };
 
+// The host-buffer forms of crt_render_map and crt_render_planned: device buffers for map_impl, then the copies back
+int map_host(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* sample_map, uint32_t s_begin, const crt_adaptive_params* planned, bool is_planned,
+             uint8_t* out_rgb, float* out_mean, uint32_t* out_samples, float* out_variance, crt_map_info* info)
+{
+    const int rc0 = map_check(sc, cam, prm, sample_map, s_begin, planned, is_planned, out_rgb, out_mean);
+    if (rc0 != CRT_OK) return rc0;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
+        Staging s(npix, out_rgb != nullptr, out_mean != nullptr), v(npix, false, out_variance != nullptr);
+        DevBuf<uint32_t> n, m;
+        if (out_samples) n.alloc(npix);
+        if (!is_planned) m.upload(sample_map, (size_t)prm->width * prm->height);
+        const int rc = map_impl(sc, cam, prm, m.p, s_begin, planned, is_planned, s.rgb.p, s.f32.p, n.p, v.f32.p, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        s.download(out_rgb, out_mean);
+        v.download(nullptr, out_variance);
+        n.download(out_samples, npix);
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
 } // namespace
 
 extern "C" {
@@ -988,6 +1231,69 @@ int crt_render_adaptive(crt_scene* sc, const crt_camera* cam, const crt_params* 
         s.download(out_rgb, out_mean);
         v.download(nullptr, out_variance);
         n.download(out_samples, npix);
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_render_map_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const void* d_sample_map, uint32_t sample_begin, void* d_rgb, void* d_mean,
+                          void* d_samples, void* d_variance, void* stream, crt_map_info* info)
+{
+    return map_impl(sc, cam, prm, (const uint32_t*)d_sample_map, sample_begin, nullptr, false, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
+}
+
+int crt_render_map(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* sample_map, uint32_t sample_begin, uint8_t* out_rgb, float* out_mean,
+                   uint32_t* out_samples, float* out_variance, crt_map_info* info)
+{
+    return map_host(sc, cam, prm, sample_map, sample_begin, nullptr, false, out_rgb, out_mean, out_samples, out_variance, info);
+}
+
+int crt_render_planned_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean, void* d_samples,
+                              void* d_variance, void* stream, crt_map_info* info)
+{
+    return map_impl(sc, cam, prm, nullptr, 0, ap, true, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
+}
+
+int crt_render_planned(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, uint8_t* out_rgb, float* out_mean,
+                       uint32_t* out_samples, float* out_variance, crt_map_info* info)
+{
+    return map_host(sc, cam, prm, nullptr, 0, ap, true, out_rgb, out_mean, out_samples, out_variance, info);
+}
+
+int crt_sample_plan_device(crt_scene* sc, float threshold, float mean_floor, void* d_map, void* stream, crt_plan_info* info)
+{
+    const int rc = plan_check(sc, threshold, mean_floor, d_map);
+    if (rc != CRT_OK) return rc;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        MapParams D;
+        std::memset(&D, 0, sizeof(D));
+        D.A = frame_aparams(sc, sc->var, make_shard(sc->var.width, sc->var.height, sc->var.world));
+        D.qacc = sc->accum_q.p;
+        D.n = sc->var.samples; D.threshold = threshold; D.mean_floor = mean_floor; D.out_map = (uint32_t*)d_map;
+        launch_sample_plan(D, (hipStream_t)stream);
+        HIP_CHECK(hipGetLastError());
+        if (info) { info->samples = sc->var.samples; info->spp = sc->var.spp; }
+        return CRT_OK;
+    } catch (const HipFail& f) {
+        return fail_hip(f);
+    }
+}
+
+int crt_sample_plan(crt_scene* sc, float threshold, float mean_floor, uint32_t* out_map, crt_plan_info* info)
+{
+    const int rc0 = plan_check(sc, threshold, mean_floor, out_map);
+    if (rc0 != CRT_OK) return rc0;
+    try {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(sc->var.width, sc->var.height, sc->var.world, sc->var.tiled != 0);
+        DevBuf<uint32_t> m;
+        m.alloc(npix);
+        const int rc = crt_sample_plan_device(sc, threshold, mean_floor, m.p, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        m.download(out_map, npix);
         return CRT_OK;
     } catch (const HipFail& f) {
         return fail_hip(f);

@@ -78,6 +78,12 @@ struct crt_scene {
     crtk::DevBuf<uint32_t> ad_active, ad_nsamp, ad_list;
     crtk::DevBuf<unsigned int> ad_count;
     unsigned int* h_ad_count = nullptr;
+    // crt_render_map: the histogram of the per-slot counts (spp + 1 words) and the cursors of the item-list kernel (spp words), uncached
+    // (crt_sample_map.hip; the counts themselves are ad_nsamp, a planned frame's map ad_list), and their pinned mirror: the histogram
+    // the host sizes the chunks from in words [0, spp], the cursors' start values it uploads in words [spp + 1, 2 spp]
+    crtk::DevBuf<unsigned int> map_hist, map_cursor;
+    unsigned int* h_map = nullptr;
+    size_t h_map_words = 0;
     std::vector<hipEvent_t> ev;
     std::vector<hipEvent_t> ev_chunk; // a timed megakernel frame: (before, after) the launch of chunk i at [2 i], [2 i + 1]
     ~crt_scene()
@@ -91,6 +97,7 @@ struct crt_scene {
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_ad_count) (void)hipHostFree(h_ad_count);
+        if (h_map) (void)hipHostFree(h_map);
     }
 };
 

@@ -819,6 +819,91 @@ int crt_write_png(const char* path, uint32_t width, uint32_t height, const uint8
  * buffers' depth / coverage (1 channel) or albedo / normal (3 channels). */
 int crt_write_pfm(const char* path, uint32_t width, uint32_t height, uint32_t channels, const float* data);
 
+/* Sample maps: one frame in which pixel p receives samples sample_begin .. n_p - 1 of its S = params->spp samples, n_p GIVEN per pixel
+ * by the caller (an importance or foveation map, a mask of a region to refine, a plan made from an earlier frame's variance) -- where
+ * crt_render_adaptive finds n_p itself, one launch of the render kernel per step.  Here all the samples a pixel still needs go into ONE
+ * launch per chunk (below).  Sample k of pixel p is the path it is in crt_render's frame (same seed, same draws), S is the cap AND the
+ * divisor of every sample, exactly as in crt_render_adaptive.  Operation by operation:
+ *   count      sample_map holds one uint32 per pixel of the WHOLE width x height image, row-major, also for a rank / world shard (which
+ *              reads the entries of its own pixels).  n_p = min(max(map[p], max(sample_begin, 1)), S): a pixel cannot take fewer samples than
+ *              it has, nor none at all, nor more than the cap; a map value of 0 or above S is legal and is clamped.
+ *   sums       c = c + x_k, q = q + x_k * x_k with x_k = L_k / (float)S for k = sample_begin .. n_p - 1 in sample order (the sums of
+ *              crt_variance; from +0.0f if sample_begin = 0), every * + / one IEEE fp32 operation, no FMA.
+ *   outputs    exactly crt_render_adaptive's, made by the same kernel, in the layout of crt_render's buffers (row-major, or the shard's
+ *              compact tiles with CRT_FLAG_TILED_OUTPUT; padding slots 0 / +0.0f): out_samples = n_p; out_mean = c * ((float)S / (float)n_p)
+ *              per channel; out_rgb = the frame's tone map of out_mean; out_variance = crt_variance's formula with fn = (float)n_p.  For
+ *              n_p = 1 the variance is what IEEE arithmetic gives that formula: (rr * d) / (1.0f - 1.0f), i.e. NaN for d = 0 and +inf
+ *              otherwise -- one sample has no variance, and the call does not hide it.  out_samples and out_variance may be NULL; out_rgb
+ *              and out_mean not both.
+ * sample_begin = 0 starts a frame.  sample_begin > 0 continues the frame in flight on the handle, which must hold exactly samples
+ * [0, sample_begin) of every pixel with valid variance sums -- the state after crt_render_range(0, sample_begin) with CRT_FLAG_VARIANCE
+ * (in one range or several) -- and have the same spp, width, height, rank, world and CRT_FLAG_TILED_OUTPUT.  Anything else is
+ * CRT_ERR_INVALID_ARG before any device call, and the handle stays as it was: the frame in flight can still be previewed and continued.
+ * Flags: CRT_FLAG_VARIANCE is implied; CRT_FLAG_STATS and CRT_FLAG_BOUNDED_RADIANCE are ignored.  Afterwards NO frame is in flight on
+ * the handle, as after crt_render_adaptive: crt_preview, crt_variance, crt_sample_plan and a range or map with sample_begin > 0 are
+ * refused, and a later crt_render is unaffected.
+ * How it runs: a prepare kernel computes n_p per pixel slot and a histogram of n_p over 0 .. S; the host reads the S + 1 words of the
+ * histogram once, through pinned memory -- ONE synchronization of the stream per call, in both forms, however many chunks follow -- and
+ * from count_s = pixels with n_p > s sizes every chunk of samples [s0, s0 + ns): its number of work items and where each sample's
+ * entries start in its item list.  Per chunk a list kernel writes the list (sample-major, the pixel slots of a wave side by side), the
+ * render kernel runs once over it, and a fold kernel adds min(n_p, s0 + ns) - s0 samples to each pixel's sums.  Chunks beyond the largest
+ * n_p are not launched (max n_p = sample_begin: no launch at all).
+ * Limits: the per-path radiance buffer stays dense per chunk, (samples of the chunk) x (pixel slots) x 12 B, whatever the map holds,
+ * and a chunk holds as many whole samples as 2^30 paths allow, as crt_render's; the list costs 4 B per work item of a chunk beside it;
+ * a chunk's number of work items and every item number stay below 2^32 (the chunk is capped at 2^30 paths).  spp above 2^24 (the
+ * histogram and the cursors cost 8 B per sample of the cap) or more than 2^30 pixel slots in a shard: CRT_ERR_UNSUPPORTED.
+ * CRT_ERR_INVALID_ARG, before any device call: a null scene, camera, params or map; both image outputs NULL; sample_begin >= spp;
+ * anything crt_render refuses; a sample_begin > 0 that does not continue the frame in flight.  CRT_ERR_UNSUPPORTED: the fallback
+ * pipeline (CRT_PIPELINE=2, or a scene beyond the render kernel's limits).  crt_multi has no map form. */
+typedef struct {
+    uint64_t paths;         /* paths this call traced: sum over the shard's pixels of n_p - sample_begin (crt_render_planned: of n_p, the warm-up included) */
+    uint64_t paths_uniform; /* pixels x spp: what crt_render would have traced */
+    uint32_t launches;      /* launches of the render kernel (crt_render_planned: the warm-up's included) */
+    uint32_t max_samples;   /* the largest n_p of the shard */
+    float kernel_ms, total_ms; /* the render kernel's launches (first launch's start to last launch's end; crt_render_planned: plus the
+                                  warm-up's) / the whole device pipeline of the call, HIP events on its stream */
+} crt_map_info;
+/* host buffers: sample_map width x height uint32; the outputs as crt_render_adaptive's; info optional */
+int crt_render_map(crt_scene* scene, const crt_camera* cam, const crt_params* params, const uint32_t* sample_map, uint32_t sample_begin,
+                   uint8_t* out_rgb, float* out_mean, uint32_t* out_samples, float* out_variance, crt_map_info* info);
+/* Device buffers on the scene's device (d_sample_map: width x height uint32, written before the call in stream order), work enqueued on
+ * hip_stream (NULL = default stream).  SYNCHRONIZES hip_stream once, after the prepare kernel, to read the histogram; the launches and
+ * the outputs are enqueued after it without a further synchronization, unless info != NULL (once more, to read the timers). */
+int crt_render_map_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const void* d_sample_map, uint32_t sample_begin,
+                          void* d_rgb, void* d_mean, void* d_samples, void* d_variance, void* hip_stream, crt_map_info* info);
+
+/* The sample count each pixel needs, from the sums of the frame in flight: crt_render_adaptive's stop criterion solved for n (the
+ * variance of the mean falls as 1 / n).  Reads the handle's sums only; writes one uint32 per pixel in the layout of the frame's out_mean
+ * (row-major, or the shard's compact tiles, padding slots 0).  With n = samples accumulated, S = the frame's spp, fn = (float)n,
+ * fs = (float)S, every operation one IEEE fp32 operation, no FMA:
+ *   r = fs / fn;  rr = r * r;  per channel var = crt_variance's formula, p = c * r
+ *   v = (var.x + var.y) + var.z;   m = (p.x + p.y) + p.z
+ *   t = threshold * (m + mean_floor);   tt = t * t;   w = (fn * v) / tt
+ *   n_p = (w < fs) ? max(n, (uint32_t)ceilf(w)) : S
+ * so NaN, +inf and w >= S all give the cap; threshold 0 sends every pixel to the cap, threshold +inf every pixel to n.  A row-major map
+ * of a whole frame is what crt_render_map takes with sample_begin = n.
+ * CRT_ERR_INVALID_ARG, before any device call: a null scene or map; a threshold that is negative or NaN; a mean_floor that is negative
+ * or not finite; what crt_variance refuses (no valid variance sums on the handle; n < 2). */
+typedef struct {
+    uint32_t samples;       /* n: the samples in the sums the plan was made from */
+    uint32_t spp;           /* S: the cap */
+} crt_plan_info;
+int crt_sample_plan(crt_scene* scene, float threshold, float mean_floor, uint32_t* out_map, crt_plan_info* info);
+/* d_map: a device buffer on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
+int crt_sample_plan_device(crt_scene* scene, float threshold, float mean_floor, void* d_map, void* hip_stream, crt_plan_info* info);
+
+/* The adaptive frame in two launches: the warm-up crt_render_range(0, min_samples) with the variance sums, crt_sample_plan at
+ * n = min_samples with adaptive->threshold and mean_floor, and crt_render_map of that plan with sample_begin = min_samples -- composed on
+ * the device, the plan never visits the host.  adaptive->step_samples is ignored; the other fields are checked as crt_render_adaptive
+ * checks them.  Outputs, handle state, limits and the one synchronization are crt_render_map's.  Unlike crt_render_adaptive, which looks
+ * again after every step, the plan trusts the variance estimate of the first min_samples samples: a pixel whose early samples happen to
+ * agree stops at min_samples whatever comes later, and one with an early outlier is sent further than the iterative call would send it
+ * (docs/experiments.md, "Sample maps and planned adaptive frames"). */
+int crt_render_planned(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
+                       uint8_t* out_rgb, float* out_mean, uint32_t* out_samples, float* out_variance, crt_map_info* info);
+int crt_render_planned_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
+                              void* d_rgb, void* d_mean, void* d_samples, void* d_variance, void* hip_stream, crt_map_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,591 @@
+"""Sample maps and planned adaptive frames: crt_render_map, crt_sample_plan, crt_render_planned and their _device forms (include/crt.h),
+Render.run_view_map / sample_plan / run_view_planned in Python, crt_cli --adaptive-planned.
+
+The expected values come from the oracle's per-path radiance (OracleScene.render(want_L=True) -> (h, w, S, 3)): the contracts of
+include/crt.h are restated below in numpy float32, one ufunc per IEEE operation, and the device result must match them on uint32 views
+(NaN matches NaN), the RGB frame the oracle's tone map of the restated mean.
+
+The shape is tests/test_adaptive.py's: both shipped scenes at 37x27 (ragged tiles, 1 280 pixel slots), cap 29, seed 0, each scene's own
+P_RR and light_sample_n.  What the restated plan gives there at min_samples 4, threshold 0.2, floor 0.01, computed on the CPU with the
+oracle (EXPECTED below):
+    cornell-box   427 pixels at n_p = 4, 198 at 29, every value 4 .. 29 at >= 6 pixels, 12 781 paths of 28 971
+    veach-mis     440 pixels at n_p = 4,  30 at 29, every value 4 .. 29 at >= 5 pixels,  8 683 paths
+"""
+import ctypes as C
+import functools
+import inspect
+import math
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import util
+from util import assert_bits, restated_sums
+
+F = np.float32
+SCENES = ["cornell-box", "veach-mis"]
+MAP_EXPORTS = ("crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned",
+               "crt_render_planned_device")
+W, H, S = 37, 27, 29
+PLAN = dict(min_samples=4, threshold=0.2, mean_floor=0.01)
+# pixels at n_p = min_samples, pixels at the cap, fewest pixels at any value between, paths
+EXPECTED = {"cornell-box": (427, 198, 6, 12781), "veach-mis": (440, 30, 5, 8683)}
+
+
+def ragged_map():
+    """(7 x + 3 y^2) mod (S + 3): holds 0, values above S, and neighbours that differ"""
+    y, x = np.mgrid[0:H, 0:W]
+    m = ((7 * x + 3 * y * y) % (S + 3)).astype(np.uint32)
+    assert (m == 0).any() and (m > S).any() and (m[:, 1:] != m[:, :-1]).all()
+    return m
+
+
+def counts_of(m, sample_begin=0):
+    """n_p = min(max(map[p], max(sample_begin, 1)), S)"""
+    return np.minimum(np.maximum(np.asarray(m, dtype=np.uint32), np.uint32(max(sample_begin, 1))), np.uint32(S))
+
+
+def variance_of_sums(c, q, fn, r):
+    """crt_variance's formula; fn, r: float32 scalars or (h, w, 1) arrays"""
+    d = fn * q - c * c
+    d = np.where(d < F(0.0), F(0.0), d)
+    return ((r * r) * d) / (fn - F(1.0))
+
+
+def restated_map(L, n_p, sample_begin=0):
+    """The contract of crt_render_map on per-path radiance L (h, w, S, 3) for the counts n_p (h, w): samples sample_begin .. n_p - 1 on
+    top of the sums of samples [0, sample_begin).  Dict of samples, mean, variance, rgb, paths (of the whole frame), c."""
+    fs = F(S)
+    n_p = np.asarray(n_p, dtype=np.uint32)
+    assert n_p.min() >= max(sample_begin, 1) and n_p.max() <= S
+    with np.errstate(all="ignore"):
+        c, q = restated_sums(L, S, sample_begin)
+        for k in range(sample_begin, int(n_p.max())):
+            a3 = (n_p > k)[..., None]
+            x = L[:, :, k, :] / fs
+            c = np.where(a3, c + x, c)
+            q = np.where(a3, q + x * x, q)
+        fn = n_p.astype(F)[..., None]
+        r = fs / fn
+        mean = c * r
+        var = variance_of_sums(c, q, fn, r)
+    for a in (c, q, mean, var):
+        assert a.dtype == F
+    return dict(samples=n_p, mean=mean, variance=var, rgb=O.tonemap(mean), paths=int(n_p.astype(np.uint64).sum()), c=c)
+
+
+def restated_plan(L, n, threshold, mean_floor):
+    """The contract of crt_sample_plan on the sums of samples [0, n): (n_p (h, w) uint32, w (h, w) float32)"""
+    thr, floor, fs, fn = F(threshold), F(mean_floor), F(S), F(n)
+    with np.errstate(all="ignore"):
+        c, q = restated_sums(L, S, n)
+        r = fs / fn
+        var = variance_of_sums(c, q, fn, r)
+        p = c * r
+        v = (var[..., 0] + var[..., 1]) + var[..., 2]
+        m = (p[..., 0] + p[..., 1]) + p[..., 2]
+        t = thr * (m + floor)
+        tt = t * t
+        w = (fn * v) / tt
+        below = w < fs                                   # (false for NaN)
+        up = np.ceil(np.where(below, w, F(0.0))).astype(np.uint32)
+    assert w.dtype == F
+    return np.where(below, np.maximum(np.uint32(n), up), np.uint32(S)).astype(np.uint32), w
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_map_entry_points_are_exported():
+    lib = capi.lib()
+    for name in MAP_EXPORTS:
+        assert name in capi.EXPORTS
+        getattr(lib, name)
+    lib.crt_abi_version.restype = C.c_int
+    assert lib.crt_abi_version() == 5 == capi.ABI_VERSION
+    for meth, names in (("run_view_map", ("sample_map", "sample_begin", "want_variance", "width", "height")),
+                        ("sample_plan", ("threshold", "mean_floor")),
+                        ("run_view_planned", ("min_samples", "threshold", "mean_floor", "want_variance", "width", "height")),
+                        ("run_view_map_device", ("stream", "rank", "world")), ("run_view_planned_device", ("stream", "rank", "world"))):
+        sig = inspect.signature(getattr(crt.Render, meth)).parameters
+        for name in names:
+            assert name in sig, (meth, name)
+        with pytest.raises(NotImplementedError):       # (like its siblings: no handle is looked at)
+            getattr(crt.MultiRender, meth)(None)
+    assert C.sizeof(capi.MapInfo) == 8 + 8 + 4 + 4 + 4 + 4 and C.sizeof(capi.PlanInfo) == 8
+
+
+def test_map_refusals_come_before_any_device_call():
+    """Every refusal that needs no scene, with a null scene (there is no device call to make): CRT_ERR_INVALID_ARG, the outputs untouched,
+    and crt_last_error names the argument."""
+    lib = capi.lib()
+    n = 8 * 8
+    rgb, mean = np.full(n * 3, 9, dtype=np.uint8), np.full(n * 3, 9, dtype=F)
+    samples, var, smap = np.full(n, 9, dtype=np.uint32), np.full(n * 3, 9, dtype=F), np.full(n, 3, dtype=np.uint32)
+    info = capi.MapInfo()
+    info.launches = 77
+    cam = capi.Camera()
+
+    def call(form, cam_=cam, prm=None, ap=None, out_rgb=rgb, out_mean=mean, no_prm=False, no_second=False, sample_begin=0):
+        p = capi.Params(8, 8, 16, 0.8, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+        for k, v_ in (prm or {}).items():
+            setattr(p, k, v_)
+        a = capi.AdaptiveParams(4, 0, 0.1, 0.01)          # (step_samples 0: ignored by the planned call)
+        for k, v_ in (ap or {}).items():
+            setattr(a, k, v_)
+        planned = "planned" in form
+        second = (None if no_second else C.byref(a),) if planned else (None if no_second else capi.ptr(smap), sample_begin)
+        tail = (None, C.byref(info)) if form.endswith("_device") else (C.byref(info),)
+        rc = getattr(lib, form)(None, C.byref(cam_) if cam_ is not None else None, None if no_prm else C.byref(p), *second,
+                                capi.ptr(out_rgb), capi.ptr(out_mean), capi.ptr(samples), capi.ptr(var), *tail)
+        return rc, lib.crt_last_error().decode()
+
+    common = [(dict(), "null scene"), (dict(cam_=None), "camera"), (dict(no_prm=True), "params"),
+              (dict(out_rgb=None, out_mean=None), "out_rgb and out_mean"),
+              (dict(prm=dict(width=0)), "width"), (dict(prm=dict(world=0)), "rank < world"), (dict(prm=dict(rank=1)), "rank < world"),
+              (dict(prm=dict(world=2)), "CRT_FLAG_TILED_OUTPUT"), (dict(prm=dict(light_sample_n=-1)), "light_sample_n"),
+              (dict(prm=dict(traversal=7)), "traversal")]
+    only = {"map": [(dict(no_second=True), "sample map"), (dict(sample_begin=16), "sample_begin"), (dict(sample_begin=17), "sample_begin"),
+                    (dict(prm=dict(spp=0)), "spp")],
+            "planned": [(dict(no_second=True), "adaptive params"), (dict(ap=dict(min_samples=1)), "min_samples"),
+                        (dict(ap=dict(min_samples=17)), "min_samples"), (dict(ap=dict(threshold=-0.5)), "threshold"),
+                        (dict(ap=dict(threshold=float("nan"))), "threshold"), (dict(ap=dict(mean_floor=-1.0)), "mean_floor"),
+                        (dict(ap=dict(mean_floor=float("inf"))), "mean_floor"), (dict(prm=dict(spp=0)), "min_samples")]}
+    for kind in ("map", "planned"):
+        for form in ("crt_render_" + kind, "crt_render_%s_device" % kind):
+            for kw, word in common + only[kind]:
+                rc, err = call(form, **kw)
+                assert rc == capi.ERR_INVALID_ARG, (form, kw, rc, err)
+                assert word in err, (form, kw, err)
+            for kw in (dict(out_rgb=None), dict(out_mean=None), dict(ap=dict(threshold=float("inf"))), dict(ap=dict(threshold=0.0, mean_floor=0.0))):
+                rc, err = call(form, **kw)
+                assert rc == capi.ERR_INVALID_ARG and "null scene" in err, (form, kw, err)
+    assert (rgb == 9).all() and (mean == 9).all() and (samples == 9).all() and (var == 9).all() and info.launches == 77
+    pinfo = capi.PlanInfo()
+    assert lib.crt_sample_plan(None, 0.1, 0.01, capi.ptr(smap), C.byref(pinfo)) == capi.ERR_INVALID_ARG
+    assert lib.crt_sample_plan_device(None, 0.1, 0.01, capi.ptr(smap), None, C.byref(pinfo)) == capi.ERR_INVALID_ARG
+    assert (smap == 3).all()
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_frame(name):
+    """(rgb, mean, L (H, W, S, 3)) of the oracle at the tests' shape with the scene's own P_RR and light_sample_n, seed 0"""
+    t = util.task(name)
+    eye, iv, fov = util.camera(name)
+    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, W, H, S, t.P_RR, t.light_sample_n, want_L=True)
+    for a in (rgb, mean, L):
+        a.flags.writeable = False
+    return rgb, mean, L
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, kind, **kw):
+    """Restated frames, computed once: kind "ragged" (the ragged map from sample 0), "floor4" (max(ragged map, 4)), "planned" (kw
+    overrides PLAN: range + plan + map)"""
+    _, _, L = oracle_frame(name)
+    if kind == "ragged":
+        got = restated_map(L, counts_of(ragged_map()))
+    elif kind == "floor4":
+        got = restated_map(L, counts_of(ragged_map(), 4))
+    else:
+        s = dict(PLAN, **kw)
+        n_p, _ = restated_plan(L, s["min_samples"], s["threshold"], s["mean_floor"])
+        got = restated_map(L, n_p, s["min_samples"])
+        got["plan"] = n_p
+    for a in got.values():
+        if isinstance(a, np.ndarray):
+            a.flags.writeable = False
+    return got
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_restated_map_at_the_cap_is_the_oracles_mean(name):
+    orgb, omean, L = oracle_frame(name)
+    got = restated_map(L, np.full((H, W), S, dtype=np.uint32))
+    assert_bits(got["mean"], omean, "map == S")
+    assert np.array_equal(got["rgb"], orgb) and got["paths"] == W * H * S
+    # continuing from 4 samples is starting from none
+    assert_bits(restated_map(L, counts_of(ragged_map(), 4), 4)["c"], restated(name, "floor4")["c"], "continuation")
+
+
+@pytest.mark.parametrize("name", SCENES)
+def test_restated_plan_is_the_recorded_distribution(name):
+    """If this fails the inputs are wrong, not the kernel."""
+    _, _, L = oracle_frame(name)
+    n_p, w = restated_plan(L, PLAN["min_samples"], PLAN["threshold"], PLAN["mean_floor"])
+    assert np.isfinite(w).all(), "the NaN / inf arm is covered by the two threshold limits, not by these frames"
+    at_min, at_cap, fewest, paths = EXPECTED[name]
+    hist = np.bincount(n_p.ravel(), minlength=S + 1)
+    assert hist[:4].sum() == 0 and hist.sum() == W * H
+    assert (int(hist[4]), int(hist[S]), int(n_p.astype(np.uint64).sum())) == (at_min, at_cap, paths), (hist, n_p.sum())
+    assert hist[4:].min() >= fewest, hist
+    assert W * H * S == 28971
+    # the two limits: threshold 0 -> the cap (w = x / 0: +inf or NaN), threshold +inf -> n
+    assert (restated_plan(L, 4, 0.0, 0.01)[0] == S).all()
+    assert (restated_plan(L, 4, np.inf, 0.01)[0] == 4).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in SCENES:
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+def result(r, rgb):
+    return dict(rgb=rgb, mean=r.mean_buffer, samples=r.samples_buffer, variance=r.variance_buffer, info=r.map_info)
+
+
+def gpu_map(r, name, m, sample_begin=0, traversal=crt.TRAVERSAL_EXACT):
+    eye, iv, fov = util.camera(name)
+    r.set_spp(S)
+    r.seed, r.traversal = 0, traversal
+    try:
+        rgb = r.run_view_map(eye, iv, fov, m, sample_begin=sample_begin, want_variance=True, width=W, height=H)
+    finally:
+        r.traversal = crt.TRAVERSAL_EXACT
+    return result(r, rgb)
+
+
+def gpu_planned(r, name, **kw):
+    eye, iv, fov = util.camera(name)
+    r.set_spp(S)
+    r.seed = 0
+    return result(r, r.run_view_planned(eye, iv, fov, want_variance=True, width=W, height=H, **dict(PLAN, **kw)))
+
+
+def check_frame(got, want, where, paths=None, launches=None):
+    assert np.array_equal(got["samples"], want["samples"]), where + ": samples per pixel"
+    assert_bits(got["mean"], want["mean"], where + ": mean")
+    assert np.array_equal(got["rgb"], want["rgb"]), where + ": RGB"
+    assert_bits(got["variance"], want["variance"], where + ": variance")
+    info = got["info"]
+    assert info["paths"] == (want["paths"] if paths is None else paths), (where, info)
+    assert info["paths_uniform"] == W * H * S and info["max_samples"] == int(want["samples"].max())
+    if launches is not None:
+        assert info["launches"] == launches, (where, info)
+    assert info["total_ms"] > 0 and 0 <= info["kernel_ms"] <= info["total_ms"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("traversal", [crt.TRAVERSAL_EXACT, crt.TRAVERSAL_REFERENCE])
+def test_map_frame_matches_restatement_on_the_oracles_radiance(renders, name, traversal):
+    want = restated(name, "ragged")
+    assert want["samples"].min() == 1 and want["samples"].max() == S
+    got = gpu_map(renders[name], name, ragged_map(), traversal=traversal)
+    check_frame(got, want, "%s traversal %d" % (name, traversal), launches=1)
+    one = want["samples"] == 1                            # one sample: the variance is what IEEE gives 0 / 0 or x / 0
+    assert one.any() and not np.isfinite(got["variance"][one]).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_map_frame_in_chunks_gives_the_same_bits(renders, name, monkeypatch):
+    # 1 280 pixel slots: chunks of 2^12 paths hold three samples
+    monkeypatch.setenv("CRT_CHUNK_LOG2", "12")
+    r = renders[name]
+    got = gpu_map(r, name, ragged_map())
+    want = restated(name, "ragged")
+    check_frame(got, want, name + ", small chunks", launches=10)
+    assert r.last_launch_ms()[1] == math.ceil(int(want["samples"].max()) / 3) == 10
+    # a map whose largest count is no multiple of three and below the cap: the chunks beyond it are not launched
+    m = np.minimum(ragged_map(), 14)
+    _, _, L = oracle_frame(name)
+    check_frame(gpu_map(r, name, m), restated_map(L, counts_of(m)), name + ", small chunks, largest count 14", launches=5)
+    assert r.last_launch_ms()[1] == 5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_uniform_maps_are_the_uniform_frame_and_the_first_sample(renders, name):
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    orgb, omean, L = oracle_frame(name)
+    r.set_spp(S)
+    rgb_u = r.run_view(eye, iv, fov, width=W, height=H, want_variance=True).copy()
+    mean_u, var_u = r.mean_buffer.copy(), r.variance_buffer.copy()
+    assert np.array_equal(rgb_u, orgb)
+    assert_bits(mean_u, omean, "run_view")
+    got = gpu_map(r, name, np.full((H, W), S))
+    assert (got["samples"] == S).all() and got["info"]["paths"] == W * H * S
+    assert np.array_equal(got["rgb"], rgb_u)
+    assert_bits(got["mean"], mean_u, "map == S: mean")
+    assert_bits(got["variance"], var_u, "map == S: variance")
+    got = gpu_map(r, name, np.ones((H, W)))
+    assert (got["samples"] == 1).all() and got["info"]["paths"] == W * H
+    with np.errstate(all="ignore"):
+        c1 = restated_sums(L, S, 1)[0]
+        assert_bits(got["mean"], c1 * (F(S) / F(1)), "map == 1: c x S after one sample")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_map_continues_a_range_with_the_variance_sums(renders, name):
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    orgb, omean, _ = oracle_frame(name)
+    kw = dict(width=W, height=H)
+    m = ragged_map()
+    want = restated(name, "floor4")
+    r.set_spp(S)
+    assert r.run_view_range(eye, iv, fov, 0, 4, want_variance=True, **kw) is None
+    got = gpu_map(r, name, m, sample_begin=4)
+    check_frame(got, want, "range(0, 4) + map from 4", paths=want["paths"] - 4 * W * H)
+    check_frame(gpu_map(r, name, np.maximum(m, 4)), want, "max(map, 4) from 0")
+    # no frame in flight after a map frame
+    with pytest.raises(crt.CrtError) as e:
+        gpu_map(r, name, m, sample_begin=4)
+    assert e.value.status == capi.ERR_INVALID_ARG
+    # a range without the variance sums, and one with 5 samples done, are not what sample_begin 4 continues
+    assert r.run_view_range(eye, iv, fov, 0, 4, **kw) is None
+    with pytest.raises(crt.CrtError) as e:
+        gpu_map(r, name, m, sample_begin=4)
+    assert e.value.status == capi.ERR_INVALID_ARG and "sample_begin" in str(e.value)
+    assert r.run_view_range(eye, iv, fov, 0, 5, want_variance=True, **kw) is None
+    with pytest.raises(crt.CrtError) as e:
+        gpu_map(r, name, m, sample_begin=4)
+    assert e.value.status == capi.ERR_INVALID_ARG
+    # after a refusal the frame in flight still continues
+    assert r.preview(**kw)[2] == 5 and r.variance(**kw)[1] == 5
+    assert np.array_equal(r.run_view_range(eye, iv, fov, 5, S - 5, want_variance=True, **kw), orgb)
+    assert_bits(r.mean_buffer, omean, "the frame in flight after refused map calls")
+
+
+class DeviceBuffers:
+    """Raw device buffers through the HIP runtime the library is linked against: {name: bytes}, each filled with 0x55"""
+
+    def __init__(self, sizes, stream=False):
+        from test_variance import hip_runtime
+        self.H = hip_runtime()
+        self.ptrs, self.sizes, self.stream = {}, dict(sizes), C.c_void_p()
+        try:
+            for n, size in sizes.items():
+                p = C.c_void_p()
+                assert self.H.hipMalloc(C.byref(p), size) == 0
+                self.ptrs[n] = p.value
+                assert self.H.hipMemset(p, 0x55, size) == 0          # (every output value must be written)
+            if stream:
+                assert self.H.hipStreamCreate(C.byref(self.stream)) == 0
+        except BaseException:
+            self.free()
+            raise
+
+    def upload(self, name, a):
+        assert a.nbytes == self.sizes[name]
+        assert self.H.hipMemcpy(C.c_void_p(self.ptrs[name]), a.ctypes.data, a.nbytes, 1) == 0   # hipMemcpyHostToDevice
+
+    def download(self, name, a):
+        assert a.nbytes == self.sizes[name]
+        assert self.H.hipMemcpy(a.ctypes.data, C.c_void_p(self.ptrs[name]), a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+        return a
+
+    def sync(self):
+        assert self.H.hipStreamSynchronize(self.stream) == 0
+
+    def free(self):
+        if self.stream.value:
+            self.H.hipStreamDestroy(self.stream)
+            self.stream = C.c_void_p()
+        for p in self.ptrs.values():
+            self.H.hipFree(C.c_void_p(p))
+        self.ptrs = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_map_shards_are_the_full_frame_at_their_pixels(renders, name):
+    r = renders[name]
+    want = restated(name, "ragged")
+    eye, iv, fov = util.camera(name)
+    r.set_spp(S)
+    world, tx, ty = 2, (W + 7) // 8, (H + 7) // 8
+    paths, padding = 0, 0
+    for rank in range(world):
+        slots = crt.shard_slots(W, H, rank, world)
+        d = DeviceBuffers({"map": W * H * 4, "rgb": slots * 3, "mean": slots * 12, "samples": slots * 4, "variance": slots * 12})
+        try:
+            d.upload("map", ragged_map())                 # the whole image's map, also for a shard
+            info = r.run_view_map_device(eye, iv, fov, d.ptrs["map"], d.ptrs, rank=rank, world=world, width=W, height=H)
+            assert d.H.hipStreamSynchronize(None) == 0
+            rgb, mean = d.download("rgb", np.zeros((slots, 3), dtype=np.uint8)), d.download("mean", np.zeros((slots, 3), dtype=F))
+            samples, var = d.download("samples", np.zeros(slots, dtype=np.uint32)), d.download("variance", np.zeros((slots, 3), dtype=F))
+        finally:
+            d.free()
+        paths += info["paths"]
+        pixels = 0
+        for s in range(slots):
+            tile = (s // 64) * world + rank
+            i, j = (tile % tx) * 8 + (s % 64) % 8, (tile // tx) * 8 + (s % 64) // 8
+            if tile >= tx * ty or i >= W or j >= H:
+                padding += 1
+                assert samples[s] == 0 and not rgb[s].any() and not mean[s].view(np.uint32).any() and not var[s].view(np.uint32).any(), (rank, s)
+                continue
+            pixels += 1
+            where = "rank %d slot %d" % (rank, s)
+            assert samples[s] == want["samples"][j, i], where
+            assert_bits(mean[s], want["mean"][j, i], where)
+            assert_bits(var[s], want["variance"][j, i], where)
+            assert np.array_equal(rgb[s], want["rgb"][j, i]), where
+        assert info["paths_uniform"] == pixels * S
+    assert padding > 0 and paths == want["paths"]
+
+
+@pytest.mark.gpu
+def test_map_device_form_on_a_stream_matches_host_form(renders):
+    name = "veach-mis"
+    r = renders[name]
+    want = restated(name, "ragged")
+    host = gpu_map(r, name, ragged_map())
+    check_frame(host, want, "host form")
+    eye, iv, fov = util.camera(name)
+    d = DeviceBuffers({"map": W * H * 4, "rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "variance": W * H * 12}, stream=True)
+    try:
+        d.upload("map", ragged_map())
+        info = r.run_view_map_device(eye, iv, fov, d.ptrs["map"], d.ptrs, stream=d.stream.value, width=W, height=H)
+        d.sync()
+        got = dict(rgb=d.download("rgb", np.zeros((H, W, 3), dtype=np.uint8)), mean=d.download("mean", np.zeros((H, W, 3), dtype=F)),
+                   samples=d.download("samples", np.zeros((H, W), dtype=np.uint32)), variance=d.download("variance", np.zeros((H, W, 3), dtype=F)),
+                   info=info)
+        check_frame(got, want, "device form", launches=1)
+        # without info, without the optional outputs, mean only
+        assert d.H.hipMemset(C.c_void_p(d.ptrs["mean"]), 0x55, W * H * 12) == 0
+        assert r.run_view_map_device(eye, iv, fov, d.ptrs["map"], {"mean": d.ptrs["mean"]}, stream=d.stream.value, want_info=False, width=W,
+                                     height=H) is None
+        d.sync()
+        assert_bits(d.download("mean", np.zeros((H, W, 3), dtype=F)), host["mean"], "device form, mean only")
+        # the planned frame's device form
+        assert d.H.hipMemset(C.c_void_p(d.ptrs["mean"]), 0x55, W * H * 12) == 0
+        info = r.run_view_planned_device(eye, iv, fov, d.ptrs, stream=d.stream.value, width=W, height=H, **PLAN)
+        d.sync()
+        planned = restated(name, "planned")
+        got = dict(rgb=d.download("rgb", np.zeros((H, W, 3), dtype=np.uint8)), mean=d.download("mean", np.zeros((H, W, 3), dtype=F)),
+                   samples=d.download("samples", np.zeros((H, W), dtype=np.uint32)), variance=d.download("variance", np.zeros((H, W, 3), dtype=F)),
+                   info=info)
+        check_frame(got, planned, "planned, device form", launches=2)
+    finally:
+        d.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_sample_plan_matches_restatement(renders, name):
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    _, _, L = oracle_frame(name)
+    kw = dict(width=W, height=H)
+    r.set_spp(S)
+    assert r.run_view_range(eye, iv, fov, 0, 4, want_variance=True, **kw) is None
+    got, done = r.sample_plan(threshold=0.2, mean_floor=0.01, **kw)
+    assert done == 4
+    want, _ = restated_plan(L, 4, 0.2, 0.01)
+    assert np.array_equal(got, want)
+    at_min, at_cap, fewest, paths = EXPECTED[name]
+    assert (int((got == 4).sum()), int((got == S).sum()), int(got.sum())) == (at_min, at_cap, paths)
+    assert np.bincount(got.ravel())[4:].min() >= fewest
+    assert (r.sample_plan(threshold=0.0, mean_floor=0.01, **kw)[0] == S).all()
+    assert (r.sample_plan(threshold=np.inf, mean_floor=0.01, **kw)[0] == 4).all()
+    # it reads only: the frame in flight goes on, and its plan is what the map call takes
+    assert r.preview(**kw)[2] == 4
+    check_frame(gpu_map(r, name, got, sample_begin=4), restated(name, "planned"), "range + plan + map", paths=int(want.sum()) - 4 * W * H)
+    # no variance frame in flight: after the map frame, and after a range without the flag
+    for prepare in (lambda: None, lambda: r.run_view_range(eye, iv, fov, 0, 4, **kw)):
+        prepare()
+        with pytest.raises(crt.CrtError) as e:
+            r.sample_plan(**kw)
+        assert e.value.status == capi.ERR_INVALID_ARG
+    for bad in (dict(threshold=-1.0), dict(threshold=np.nan), dict(mean_floor=np.inf)):
+        with pytest.raises(crt.CrtError) as e:
+            r.sample_plan(**dict(kw, **bad))
+        assert e.value.status == capi.ERR_INVALID_ARG
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+def test_planned_frame_matches_range_plan_map_restated(name, monkeypatch):
+    t = util.task(name)
+    r = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)   # a fresh handle
+    try:
+        eye, iv, fov = util.camera(name)
+        orgb, omean, L = oracle_frame(name)
+        kw = dict(width=W, height=H)
+        want = restated(name, "planned")
+        assert np.array_equal(want["plan"], want["samples"])
+        check_frame(gpu_planned(r, name), want, "first call on the handle", launches=2)
+        assert want["paths"] == EXPECTED[name][3]
+        # afterwards no frame is in flight, and a later frame is unaffected
+        for call in (lambda: r.preview(**kw), lambda: r.variance(**kw), lambda: r.sample_plan(**kw),
+                     lambda: r.run_view_range(eye, iv, fov, 4, 2, want_variance=True, **kw)):
+            with pytest.raises(crt.CrtError) as e:
+                call()
+            assert e.value.status == capi.ERR_INVALID_ARG
+        rgb_u = r.run_view(eye, iv, fov, want_variance=True, **kw).copy()
+        mean_u, var_u = r.mean_buffer.copy(), r.variance_buffer.copy()
+        assert np.array_equal(rgb_u, orgb)
+        assert_bits(mean_u, omean, "run_view after a planned frame")
+        # threshold 0: the uniform frame's bits
+        got = gpu_planned(r, name, threshold=0.0)
+        assert (got["samples"] == S).all() and got["info"]["paths"] == W * H * S
+        assert np.array_equal(got["rgb"], rgb_u)
+        assert_bits(got["mean"], mean_u, "threshold 0: mean")
+        assert_bits(got["variance"], var_u, "threshold 0: variance")
+        # threshold +inf: the warm-up alone; the mean is crt_preview's after a range of four samples
+        got = gpu_planned(r, name, threshold=np.inf)
+        assert (got["samples"] == 4).all() and got["info"]["paths"] == W * H * 4 and got["info"]["launches"] == 1
+        assert r.run_view_range(eye, iv, fov, 0, 4, **kw) is None
+        prgb, pmean, done = r.preview(want_mean=True, **kw)
+        assert done == 4
+        assert_bits(got["mean"], pmean, "threshold +inf: mean")
+        assert np.array_equal(got["rgb"], prgb)
+        assert_bits(got["variance"], restated(name, "planned", threshold=np.inf)["variance"], "threshold +inf: variance")
+        # a refused planned call leaves the frame in flight as it was
+        with pytest.raises(crt.CrtError):
+            r.run_view_planned(eye, iv, fov, min_samples=1, **kw)
+        assert r.preview(**kw)[2] == 4
+        assert np.array_equal(r.run_view_range(eye, iv, fov, 4, S - 4, **kw), orgb)
+        # the warm-up in chunks of three samples, the rest in chunks of three
+        with monkeypatch.context() as m:
+            m.setenv("CRT_CHUNK_LOG2", "12")
+            check_frame(gpu_planned(r, name), want, "small chunks", launches=2 + math.ceil((S - 4) / 3))
+        # the fallback pipeline hands out its work items without the list
+        with monkeypatch.context() as m:
+            m.setenv("CRT_PIPELINE", "2")
+            for call in (lambda: r.run_view_planned(eye, iv, fov, **dict(PLAN, **kw)), lambda: r.run_view_map(eye, iv, fov, ragged_map(), **kw)):
+                with pytest.raises(crt.CrtError) as e:
+                    call()
+                assert e.value.status == capi.ERR_UNSUPPORTED
+        check_frame(gpu_planned(r, name), want, "after the refusals", launches=2)
+    finally:
+        r.free()
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_planned_frame_and_its_samples(renders, tmp_path):
+    from cudaraytracing_amd import build as b
+    from test_variance import read_pfm
+    cli = b.build_cli()
+    name = "veach-mis"
+    cfg = util.SCENES[name]
+    png, pfm, vpfm = (str(tmp_path / n) for n in ("planned.png", "samples.pfm", "var.pfm"))
+    base = [cli, cfg, "--spp", str(S), "--width", str(W), "--height", str(H), "--seed", "0", "--base-dir", util.ROOT]
+    res = subprocess.run(base + ["-o", png, "--adaptive", "0.2", "--adaptive-min", "4", "--adaptive-planned", "--adaptive-samples", pfm,
+                                 "--variance", vpfm], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    assert "planned: 2 launches, %d of %d paths" % (EXPECTED[name][3], W * H * S) in res.stdout
+    got = gpu_planned(renders[name], name)
+    ref = str(tmp_path / "python.png")
+    renders[name].save_frame_buffer(ref)
+    assert open(png, "rb").read() == open(ref, "rb").read()
+    assert_bits(read_pfm(pfm), got["samples"].astype(F), "--adaptive-samples")
+    assert_bits(read_pfm(vpfm), got["variance"], "--variance of the planned frame")
+    bad = subprocess.run([cli, cfg, "--adaptive-planned"], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--adaptive" in bad.stderr
