@@ -1,48 +1,37 @@
-// cudaraytracing_amd/csrc/crt_adaptive.hip -- the kernels of crt_render_adaptive (contract: include/crt.h; host loop: crt_render.hip):
-// between the passes of k_mega3, one thread per pixel slot decides which pixels go on (k_adaptive_select), a list turns the render kernel's
-// work cursor into (sample, active pixel) (k_adaptive_items), the pass's radiance goes into the sums of the pixels that took it
-// (k_adaptive_accumulate), and at the end the sums become the frame (k_adaptive_resolve).
-// Memory: the sums, the active / sample-count planes, the list of active slots and its counter are uncached allocations accessed with
+// cudaraytracing_amd/csrc/crt_adaptive.hip -- the kernels of crt_render_adaptive (contract: include/crt.h; host loop: crt_sparse.hip):
+// between the passes of k_mega3, one thread per pixel slot decides which pixels go on and counts the coming pass into their n_p
+// (k_adaptive_select), a list turns the render kernel's work cursor into (sample, active pixel) (k_adaptive_items), and at the end the
+// sums become the frame (k_adaptive_resolve, for every sparse frame).  A pass's radiance goes into the sums by k_map_fold
+// (crt_sample_map.hip): a slot that goes on has n_p = the pass's end, one that has stopped has n_p <= the pass's begin.
+// Memory: the sums, the sample-count plane, the list of active slots and its counter are uncached allocations accessed with
 // agent-scope atomics only; the item list is written with agent-scope stores, as k_order_items writes it (docs/experiments.md 6).
-// The slot map, the loads and stores of the sums, the sample fold and the output write are the frame kernels' (crt_internal.h).
+// The slot map, the accessors, the stop criterion and the output write are the image-space kernels' (crt_stages.h).
 #include "crt_internal.h"
 
 namespace crtk {
 
-__device__ __forceinline__ uint32_t word_load(const uint32_t* p) { return __hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void word_store(uint32_t* p, const uint32_t v) { __hip_atomic_store((unsigned int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// After the warm-up: every pixel of the shard is active and has D.n samples; padding slots never are and have none.
+// After the warm-up: every pixel of the shard has D.n samples; padding slots have none (and, D.n >= 2, never count as active).
 __global__ __launch_bounds__(256) void k_adaptive_init(const AdaptiveParams D)
 {
-    const AParams& A = D.A;
+    const AParams& A = D.sums.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    const bool valid = slot_pixel(A, slot).valid;
-    word_store(D.active + slot, valid ? 1u : 0u);
-    word_store(D.nsamp + slot, valid ? D.n : 0u);
+    word_store(D.sums.nsamp + slot, slot_pixel(A, slot).valid ? D.n : 0u);
 }
 
-// The stop criterion of include/crt.h for every still-active slot at n = D.n samples, and the list of the slots that go on: per wave a
-// ballot, a popcount and ONE atomic on the counter.  The order of the list is whatever the atomics make it: it decides which wave traces
-// a path, never what the path is.
+// The stop criterion of include/crt.h for every still-active slot -- n_p == D.n: a slot that stopped earlier has fewer -- and the list of
+// the slots that go on, whose n_p becomes that of the end of the coming pass, D.n + D.ns_pass (a slot that stops keeps its count): per
+// wave a ballot, a popcount and ONE atomic on the counter.  The order of the list is whatever the atomics make it: it decides which wave
+// traces a path, never what the path is.
 __global__ __launch_bounds__(256) void k_adaptive_select(const AdaptiveParams D)
 {
-    const AParams& A = D.A;
+    const AParams& A = D.sums.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    bool act = slot < A.nslots && word_load(D.active + slot) != 0u;
+    bool act = slot < A.nslots && word_load(D.sums.nsamp + slot) == D.n;
     if (act) {
-        const float fn = (float)D.n, fs = (float)A.spp;
-        const float r = fs / fn, rr = r * r;
-        const F3 c = acc_load3(A.accum, A.nslots, slot);
-        const F3 var = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, rr);
-        const F3 p = f3(c.x * r, c.y * r, c.z * r);
-        const float v = (var.x + var.y) + var.z, m = (p.x + p.y) + p.z;
-        const float t = D.threshold * (m + D.mean_floor);
-        if (v <= t * t) { // (false for NaN: such a pixel runs to the cap)
-            act = false;
-            word_store(D.active + slot, 0u);
-        }
+        const StopCriterion k = stop_criterion(A, D.sums.qacc, slot, D.n, D.threshold, D.mean_floor);
+        if (k.v <= k.tt) act = false; // (false for NaN: such a pixel runs to the cap)
+        else word_store(D.sums.nsamp + slot, D.n + D.ns_pass);
     }
     const unsigned long long mask = __ballot(act);
     if (mask == 0ull) return;
@@ -65,24 +54,9 @@ __global__ __launch_bounds__(256) void k_adaptive_items(uint32_t* const item_lis
     __hip_atomic_store(&item_list[pos], s * nslots + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// k_accumulate_var's fold (fold_samples) for the slots that took the pass.  Slots that did not take it are not touched (their entries of
-// L hold whatever an earlier launch left).
-__global__ __launch_bounds__(256) void k_adaptive_accumulate(const AdaptiveParams D)
-{
-    const AParams& A = D.A;
-    const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    if (slot >= A.nslots || word_load(D.active + slot) == 0u) return;
-    F3 c = acc_load3(A.accum, A.nslots, slot);
-    F3 q = acc_load3(D.qacc, A.nslots, slot);
-    fold_samples<true>(A, slot, c, q);
-    acc_store3(A.accum, A.nslots, slot, c);
-    acc_store3(D.qacc, A.nslots, slot, q);
-    word_store(D.nsamp + slot, D.n);
-}
-
 // The frame: per pixel n_p, mean = c * (S / n_p), its tone map, and the variance of that mean, in the layout of crt_render's buffers
 // (padding slots of a tiled shard 0 / +0).
-__global__ __launch_bounds__(256) void k_adaptive_resolve(const AdaptiveParams D)
+__global__ __launch_bounds__(256) void k_adaptive_resolve(const SumsParams D, uint32_t* const out_samples, float* const out_variance)
 {
     const AParams& A = D.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
@@ -97,23 +71,24 @@ __global__ __launch_bounds__(256) void k_adaptive_resolve(const AdaptiveParams D
         const float r = fs / fn;
         const F3 c = acc_load3(A.accum, A.nslots, slot);
         p = f3(c.x * r, c.y * r, c.z * r);
-        if (D.out_variance) v = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, r * r);
+        if (out_variance) v = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, r * r);
     }
     const uint64_t o = px.o;
     write_color(A, o, px.valid, p);
-    if (D.out_samples) D.out_samples[o] = n;
-    if (D.out_variance) { D.out_variance[o * 3 + 0] = v.x; D.out_variance[o * 3 + 1] = v.y; D.out_variance[o * 3 + 2] = v.z; }
+    if (out_samples) out_samples[o] = n;
+    if (out_variance) { out_variance[o * 3 + 0] = v.x; out_variance[o * 3 + 1] = v.y; out_variance[o * 3 + 2] = v.z; }
 }
 
-// ---- exported to crt_render.hip ----
-static dim3 slot_grid(const AdaptiveParams& D) { return dim3((D.A.nslots + 255) / 256); }
-void launch_adaptive_init(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_init, slot_grid(D), dim3(256), 0, st, D); }
-void launch_adaptive_select(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_select, slot_grid(D), dim3(256), 0, st, D); }
+// ---- exported to crt_sparse.hip ----
+void launch_adaptive_init(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_init, slot_grid(D.sums.A), dim3(256), 0, st, D); }
+void launch_adaptive_select(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_select, slot_grid(D.sums.A), dim3(256), 0, st, D); }
 void launch_adaptive_items(uint32_t* item_list, const uint32_t* list, uint32_t n_active, uint32_t n_items, uint32_t nslots, hipStream_t st)
 {
     hipLaunchKernelGGL(k_adaptive_items, dim3((n_items + 255) / 256), dim3(256), 0, st, item_list, list, n_active, make_fastdiv(n_active), n_items, nslots);
 }
-void launch_adaptive_accumulate(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_accumulate, slot_grid(D), dim3(256), 0, st, D); }
-void launch_adaptive_resolve(const AdaptiveParams& D, hipStream_t st) { hipLaunchKernelGGL(k_adaptive_resolve, slot_grid(D), dim3(256), 0, st, D); }
+void launch_adaptive_resolve(const SumsParams& D, uint32_t* out_samples, float* out_variance, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_adaptive_resolve, slot_grid(D.A), dim3(256), 0, st, D, out_samples, out_variance);
+}
 
 } // namespace crtk

@@ -1,6 +1,6 @@
 // cudaraytracing_amd/csrc/crt_frame.hip -- the kernels around the render kernels: k_accumulate (per pixel c += L_k / spp in sample order, tone map:
 // include/Render.cuh:348-350; k_accumulate_var: also the sum of squares behind crt_variance, read out by k_variance), k_preview, and the kernels behind crt_intersect's ray upload and the crt_device_* self-tests.
-// The stages these share with crt_adaptive.hip -- slot to pixel to output index, the three-plane sums, the sample fold, the output write -- are in crt_internal.h.
+// The stages these share with crt_adaptive.hip -- slot to pixel to output index, the three-plane sums, the sample fold, the output write -- are in crt_stages.h.
 #include "crt_internal.h"
 
 namespace crtk {

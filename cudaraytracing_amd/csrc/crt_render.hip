@@ -1,10 +1,11 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
-// pipeline, the passes of an adaptive frame, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*,
-// crt_render_adaptive*, crt_render_map*, crt_sample_plan*, crt_render_planned*, crt_preview*, crt_variance*, crt_render_aov*, crt_intersect,
-// crt_device_*).  The scene handle is made in
-// crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_sample_map.hip, crt_aov.hip.
+// pipeline, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*,
+// crt_render_aov*, crt_intersect, crt_device_*).  The frames in which not every pixel takes every sample (crt_render_adaptive*,
+// crt_render_map*, crt_sample_plan*, crt_render_planned*) are ranges of render_impl with an item source: crt_sparse.hip, which sees this
+// file through crt_render.h.  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip,
+// crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_sample_map.hip, crt_aov.hip.
 // The slot map of a shard and the host's form of the slot rule: crt_scene.h; host-buffer copies: DevBuf::upload / download.
-#include "crt_scene.h"
+#include "crt_render.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -61,11 +62,6 @@ static bool use_impl(const crt_scene* sc, bool dec, bool r16)
     const char* e = std::getenv("CRT_IMPL");
     return !(e && e[0] == '0');
 }
-// Which pipeline renders: 4 = k_mega3 (the product), 2 = the wavefront pipeline (k_logic + k_trace).  k_mega3 keeps the best
-// triangle's offset inside its leaf in 16 bits, addresses nodes and leaf records with 32-bit byte offsets and the traversal stack
-// depth in 8 bits; scenes beyond any of these fall back to the wavefront pipeline, which has no such limits.  The CRT_TEST_*
-// variables lower the limits so that the tests can force each fallback on a small scene.
-uint32_t choose_pipeline(const crt_scene* sc);
 
 // The camera's half-height at distance 1 and aspect ratio (Render.cuh:338-339), as the camera rays of a frame (camera_dir) and of the AOV
 // pass take them
@@ -74,8 +70,6 @@ void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale,
     scale = det_tanf(cam->fov_y / 2);
     ar = (float)prm->width / (float)prm->height;
 }
-
-const uint64_t kMaxChunkItems = 1ull << 30; // paths per chunk (12.9 GB of per-path radiance: sized for 288 GB of HBM, every launch ends with a 2 ms tail)
 
 struct TraceSetup {
     TParams T;
@@ -187,6 +181,10 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
     return (const float*)sc->p_res.p;
 }
 
+} // namespace
+
+namespace crtk { // (declared in crt_render.h)
+
 // Whether a range that begins at sample s_begin > 0 continues the frame `f` records (crt_scene::acc for the sum c, crt_scene::var for
 // the sum of squares q): the samples before it are in the sums, and spp, size, shard and layout are the frame's.
 bool continues_frame(const FrameMark& f, const crt_params* prm, uint32_t s_begin, bool tiled)
@@ -205,16 +203,6 @@ void ensure_events(crt_scene* sc)
     }
 }
 
-// The event pairs around the launches of a timed megakernel frame, one per chunk
-void ensure_chunk_events(crt_scene* sc, uint32_t chunks)
-{
-    while (sc->ev_chunk.size() < 2 * (size_t)chunks) {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreate(&e));
-        sc->ev_chunk.push_back(e);
-    }
-}
-
 // Frame-kernel parameters (k_accumulate, k_preview, k_variance) of the frame `f` describes, on the handle's accumulator
 AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh)
 {
@@ -226,21 +214,19 @@ AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh)
     return A;
 }
 
-// A pass of crt_render_adaptive, as render_impl sees it: a sample range of a frame with CRT_FLAG_VARIANCE whose sums are resolved by
-// the adaptive loop, not by the range that ends at spp.  list == nullptr: the warm-up, every pixel slot takes the range; otherwise only
-// the n_active slots of `list` (device memory) do, and D names the planes k_adaptive_accumulate updates.
-// map != nullptr: the range is the launches of crt_render_map instead -- every pixel slot takes its own number of the range's samples
-// (MapPass), list / n_active / D are not used.
-struct MapPass {
-    MapParams D;                       // the count plane, the cursors and the sums: what k_map_items and k_map_fold take
-    std::vector<uint32_t> chunk_items; // work items of chunk 0, 1, ... of the range: the slots with n_p > s, summed over the chunk's samples
-};
-struct AdaptivePass {
-    const uint32_t* list;
-    uint32_t n_active;
-    AdaptiveParams D;
-    const MapPass* map;
-};
+} // namespace crtk
+
+namespace {
+
+// The event pairs around the launches of a timed megakernel frame, one per chunk
+void ensure_chunk_events(crt_scene* sc, uint32_t chunks)
+{
+    while (sc->ev_chunk.size() < 2 * (size_t)chunks) {
+        hipEvent_t e;
+        HIP_CHECK(hipEventCreate(&e));
+        sc->ev_chunk.push_back(e);
+    }
+}
 
 // One call of render_impl, as its two pipelines see it
 struct Frame {
@@ -257,9 +243,8 @@ struct Frame {
     RingPlan ring;
     bool want_stats, tiled, want_var, var_frame;
     AParams A;
-    const AdaptivePass* ad; // crt_render_adaptive only
-    bool sparse() const { return ad && (ad->list || ad->map); } // the launch's work items come from a list
-    const MapPass* map() const { return ad ? ad->map : nullptr; }
+    const ItemSource* src; // null: every pixel slot takes every sample of the range
+    bool open;             // the frame is resolved by the caller, not by the range that ends at spp
 };
 
 // What both pipelines put into LParams: camera, size, shard, divisions, the handle's buffers
@@ -282,8 +267,8 @@ LParams frame_lparams(const Frame& f)
     return P;
 }
 
-// The n_items work items of the chunk of samples that starts at s0 -- one per pixel slot and sample; an adaptive pass: per active slot
-// and sample; a sample map: per sample the slots that take it -- in ITEM_SHARDS cursor shards
+// The n_items work items of the chunk of samples that starts at s0 -- one per pixel slot and sample, or what the range's item source
+// lists -- in ITEM_SHARDS cursor shards
 void set_chunk(LParams& P, uint32_t s0, uint32_t n_items)
 {
     P.sample_begin = s0;
@@ -298,18 +283,11 @@ void accumulate_chunk(Frame& f, uint32_t s0, uint32_t ns)
     crt_scene* sc = f.sc;
     AParams& A = f.A;
     A.chunk_samples = ns;
-    A.first_chunk = s0 == 0; A.last_chunk = !f.ad && s0 + ns >= f.prm->spp; // (an adaptive frame is resolved by k_adaptive_resolve)
+    A.first_chunk = s0 == 0; A.last_chunk = !f.open && s0 + ns >= f.prm->spp;
     if (f.ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
     if (!f.ring.samples || A.last_chunk) {
-        if (f.map()) { // every slot its own number of the chunk's samples
-            MapParams D = f.map()->D;
-            D.A = A; D.s0 = s0; D.ns = ns;
-            launch_map_fold(D, f.st);
-        } else if (f.sparse()) { // only the slots that took the pass
-            AdaptiveParams D = f.ad->D;
-            D.A = A; D.n = s0 + ns;
-            launch_adaptive_accumulate(D, f.st);
-        } else if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
+        if (f.src) f.src->fold(A, s0, ns, f.st);
+        else if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
         else launch_accumulate(A, f.st);
         HIP_CHECK(hipGetLastError());
         if (f.var_frame) { sc->var.valid = true; sc->var.set(f.prm, s0 + ns, f.tiled); }
@@ -380,10 +358,12 @@ void render_mega(Frame& f)
     const RingPlan& ring = f.ring;
     hipStream_t st = f.st;
     const bool timing = f.stats != nullptr;
-    const uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots
-        : f.map()                            ? *std::max_element(f.map()->chunk_items.begin(), f.map()->chunk_items.end())
-        : f.sparse()                         ? (uint64_t)f.chunk * f.ad->n_active
-                                             : f.cap;
+    auto chunk_items = [&](uint32_t k, uint32_t ns) { return f.src ? f.src->items(k, ns) : (uint32_t)((uint64_t)ns * sh.nslots); };
+    uint64_t most_items = ring.samples ? (uint64_t)(f.s_end - f.s_begin) * sh.nslots : f.cap;
+    if (f.src) { // the largest chunk the source lists
+        most_items = 0;
+        for (uint32_t s0 = f.s_begin, k = 0; s0 < f.s_end; s0 += f.chunk, k++) most_items = std::max<uint64_t>(most_items, chunk_items(k, std::min(f.chunk, f.s_end - s0)));
+    }
     const MegaPlan mp = plan_mega3(sc, prm->traversal, f.want_stats, (prm->flags & CRT_FLAG_TRACE_ALL) != 0, false, ring.samples != 0, most_items, env_u32("CRT_MEGA_BLOCKS_PER_CU", 64));
     const uint32_t lanes = mp.lanes;
     sc->p_vx.ensure(lanes); sc->p_la.ensure(lanes); sc->p_cc.ensure(lanes); sc->p_id.ensure(lanes);
@@ -408,7 +388,7 @@ void render_mega(Frame& f)
     uint32_t launches = 0;
     for (uint32_t s0 = f.s_begin; s0 < f.s_end; s0 += f.chunk) {
         uint32_t ns = std::min(f.chunk, f.s_end - s0);
-        set_chunk(P, s0, f.map() ? f.map()->chunk_items[launches] : (uint32_t)((uint64_t)ns * (f.sparse() ? f.ad->n_active : P.nslots)));
+        set_chunk(P, s0, chunk_items(launches, ns));
         if (ring.samples) { // cursor shard = ring.spsh pixel slots x ns samples
             P.items_per_shard = ring.spsh * ns;
             P.n_items = P.items_per_shard * ring.shards;
@@ -427,19 +407,11 @@ void render_mega(Frame& f)
         // the paths that stop at their first vertex are handed out last (k_order_items): 1 % of a whole C2 frame on one GPU,
         // 8 % of a rank's share on eight.  CRT_ITEM_ORDER=0 switches it off.
         P.item_list = nullptr;
-        if (f.sparse()) {
-            // an adaptive pass: the WHOLE cursor range goes through the list (order_window = the shard, so list index = cursor position),
-            // which names the frame's own work item (sample, slot) of every position: k_mega3 decodes it and writes L[item] as ever
+        if (f.src) {
+            // the WHOLE cursor range goes through the source's list (order_window = the shard, so list index = cursor position)
             P.order_window = P.items_per_shard;
             sc->item_list.ensure(P.n_items);
-            if (f.map()) { // (a sample map: the slots with n_p > s, sample by sample)
-                MapParams D = f.map()->D;
-                D.item_list = sc->item_list.p; D.n_items = P.n_items; D.s0 = s0; D.ns = ns;
-                // (the kernel fills every position when the histogram is the count plane's; cleared first, so that a position it did not
-                // fill names work item 0 of the chunk, inside L, not what an earlier launch left there)
-                HIP_CHECK(hipMemsetAsync(sc->item_list.p, 0, (size_t)P.n_items * sizeof(uint32_t), st));
-                launch_map_items(D, st);
-            } else launch_adaptive_items(sc->item_list.p, f.ad->list, f.ad->n_active, P.n_items, P.nslots, st);
+            f.src->fill(sc->item_list.p, s0, ns, P.n_items, st);
             HIP_CHECK(hipGetLastError());
             P.item_list = sc->item_list.p;
         } else {
@@ -619,6 +591,28 @@ void render_wavefront(Frame& f)
     }
 }
 
+} // namespace
+
+namespace crtk { // (declared in crt_render.h)
+
+// Which pipeline renders: 4 = k_mega3 (the product), 2 = the wavefront pipeline (k_logic + k_trace).  k_mega3 keeps the best
+// triangle's offset inside its leaf in 16 bits, addresses nodes and leaf records with 32-bit byte offsets and the traversal stack
+// depth in 8 bits; scenes beyond any of these fall back to the wavefront pipeline, which has no such limits.  The CRT_TEST_*
+// variables lower the limits so that the tests can force each fallback on a small scene.
+uint32_t choose_pipeline(const crt_scene* sc)
+{
+    uint32_t pipeline = env_u32("CRT_PIPELINE", 4);
+    if (pipeline != 2) pipeline = 4;
+    const uint64_t max_leaf = env_u32("CRT_TEST_MAX_LEAF", CRT_MEGA3_MAX_LEAF);
+    const uint64_t max_bytes = std::getenv("CRT_TEST_MAX_BYTES") ? (uint64_t)env_u32("CRT_TEST_MAX_BYTES", 0xffffffffu) : (1ull << 32);
+    const uint32_t max_stack = env_u32("CRT_TEST_MAX_STACK", CRT_MEGA3_MAX_STACK);
+    if (pipeline == 4 && sc->max_leaf > max_leaf) pipeline = 2;
+    if (pipeline == 4 && (sc->nodes4.n * sizeof(float4) >= max_bytes || sc->nodes3.n * sizeof(float4) >= max_bytes || sc->leaf_geo.n * sizeof(float4) >= max_bytes))
+        pipeline = 2; // (33 M nodes / 53 M records)
+    if (pipeline == 4 && (uint32_t)sc->stack_cap > max_stack) pipeline = 2; // a deeper stack would spill into the flag bits of word D
+    return pipeline;
+}
+
 // Samples per launch of a range of s_count samples without the commit ring: as many whole samples of every pixel slot as kMaxChunkItems
 // paths hold, at least one
 uint32_t chunk_samples(uint32_t nslots, uint32_t s_count)
@@ -627,47 +621,50 @@ uint32_t chunk_samples(uint32_t nslots, uint32_t s_count)
     return (uint32_t)std::min<uint64_t>(s_count, std::max<uint64_t>(1, max_items / nslots));
 }
 
-// What crt_render refuses in a crt_params by itself (no scene, no sample range), before any device call
-int params_check(const crt_params* prm)
+// What `who` (crt_render and, through it, every call that renders a frame; crt_render_aov) refuses in a crt_params by itself (no scene,
+// no sample range), before any device call.  `aov`: the AOV pass takes no next-event samples, and its pixel count is tested last.
+int params_check(const char* who, const crt_params* prm, bool aov)
 {
-    if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render: width, height and spp must be positive");
-    if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, "crt_render: need rank < world");
-    if (prm->light_sample_n < 0 || prm->light_sample_n > 4096) return fail(CRT_ERR_INVALID_ARG, "crt_render: light_sample_n must be in [0, 4096]");
-    if ((uint64_t)prm->width * prm->height > 0xffffffffull) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 2^32 pixels");
+    const std::string w(who);
+    const bool too_many_pixels = (uint64_t)prm->width * prm->height > 0xffffffffull;
+    if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width, height and spp must be positive");
+    if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, w + ": need rank < world");
+    if (!aov && (prm->light_sample_n < 0 || prm->light_sample_n > 4096)) return fail(CRT_ERR_INVALID_ARG, w + ": light_sample_n must be in [0, 4096]");
+    if (!aov && too_many_pixels) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels"); // (a render reports it here ...)
     if (prm->traversal != CRT_TRAVERSAL_FAST && prm->traversal != CRT_TRAVERSAL_REFERENCE && prm->traversal != CRT_TRAVERSAL_EXACT)
-        return fail(CRT_ERR_INVALID_ARG, "crt_render: unknown traversal mode");
-    if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, "crt_render: world > 1 needs CRT_FLAG_TILED_OUTPUT");
+        return fail(CRT_ERR_INVALID_ARG, w + ": unknown traversal mode");
+    if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, w + ": world > 1 needs CRT_FLAG_TILED_OUTPUT");
+    if (too_many_pixels) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels"); // (... the AOV pass here: a render has returned above)
     return CRT_OK;
 }
 
 // Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
 // (temp_color += L_k / spp in sample order, Render.cuh:348); the range that ends at spp also tone-maps and writes the frame.
-// ad: the range is a pass of crt_render_adaptive (AdaptivePass): nothing is tone-mapped, d_rgb / d_mean are not used.
-int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats,
-                uint32_t s_begin = 0, uint32_t s_count = 0xffffffffu, const AdaptivePass* ad = nullptr)
+// src, open: crt_render.h.
+int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats, uint32_t s_begin,
+                uint32_t s_count, const ItemSource* src, bool open)
 {
     if (!sc || !cam || !prm) return fail(CRT_ERR_INVALID_ARG, "crt_render: null argument");
     if (s_count == 0xffffffffu) s_count = prm->spp > s_begin ? prm->spp - s_begin : 0;
     if (s_count == 0 || (uint64_t)s_begin + s_count > prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render: sample range outside [0, spp)");
     const uint32_t s_end = s_begin + s_count;
-    if (!d_rgb && s_end == prm->spp && !ad) return fail(CRT_ERR_INVALID_ARG, "crt_render: null frame buffer");
-    const int rc_prm = params_check(prm);
+    if (!d_rgb && s_end == prm->spp && !open) return fail(CRT_ERR_INVALID_ARG, "crt_render: null frame buffer");
+    const int rc_prm = params_check("crt_render", prm);
     if (rc_prm != CRT_OK) return rc_prm;
     Frame f;
-    f.sc = sc; f.cam = cam; f.prm = prm; f.st = st; f.stats = stats; f.s_begin = s_begin; f.s_end = s_end; f.ad = ad;
+    f.sc = sc; f.cam = cam; f.prm = prm; f.st = st; f.stats = stats; f.s_begin = s_begin; f.s_end = s_end; f.src = src; f.open = open;
     f.want_stats = (prm->flags & CRT_FLAG_STATS) != 0;
     f.tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
     f.want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
     // a range that does not start a frame adds to the accumulator: it must hold exactly the samples before the range, of this frame
     if (s_begin > 0 && !continues_frame(sc->acc, prm, s_begin, f.tiled)) {
-        const std::string have = sc->acc.samples == 0 ? std::string("no frame is in flight on the handle")
-            : "the frame in flight holds samples [0, " + std::to_string(sc->acc.samples) + ") of spp " + std::to_string(sc->acc.spp) + " at " + std::to_string(sc->acc.width) +
-              " x " + std::to_string(sc->acc.height) + ", rank " + std::to_string(sc->acc.rank) + " of " + std::to_string(sc->acc.world) + (sc->acc.tiled ? ", tiled" : ", row-major");
+        const std::string have = sc->acc.in_flight(" at " + std::to_string(sc->acc.width) + " x " + std::to_string(sc->acc.height) + ", rank " + std::to_string(sc->acc.rank) +
+                                                   " of " + std::to_string(sc->acc.world) + (sc->acc.tiled ? ", tiled" : ", row-major"));
         return fail(CRT_ERR_INVALID_ARG, "crt_render_range: a range with sample_begin " + std::to_string(s_begin) + " must continue the frame in flight: expected sample_begin == samples accumulated "
                                          "and the same spp, width, height, rank, world and CRT_FLAG_TILED_OUTPUT as its earlier ranges, or sample_begin 0 to start over (" + have + ")");
     }
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         f.sh = make_shard(prm->width, prm->height, prm->world);
         f.chunk = chunk_samples(f.sh.nslots, s_count);
@@ -697,314 +694,12 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         if (mega) render_mega(f);
         else render_wavefront(f);
         return CRT_OK;
-    } catch (const HipFail& e) {
-        return fail_hip(e);
-    }
+    });
 }
 
-// ---------- crt_render_adaptive (contract: include/crt.h): passes of render_impl over the pixels a selection kernel leaves active ----------
-// Argument checks of both forms, before any device call.  The scene comes last so that the message names what is wrong with the other
-// arguments even where there is no scene.
-int adaptive_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, const void* out_rgb, const void* out_mean)
-{
-    if (!cam) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null camera");
-    if (!prm) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null params");
-    if (!ap) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null adaptive params");
-    if (!out_rgb && !out_mean) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: out_rgb and out_mean are both null");
-    if (ap->min_samples < 2 || ap->min_samples > prm->spp) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: min_samples must be in [2, spp] (the variance needs two samples)");
-    if (ap->step_samples == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: step_samples must be positive");
-    if (!(ap->threshold >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: threshold must be >= 0 and not NaN");
-    if (!(ap->mean_floor >= 0.0f) || ap->mean_floor > FLT_MAX) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: mean_floor must be >= 0 and finite");
-    const int rc = params_check(prm);
-    if (rc != CRT_OK) return rc;
-    if (!sc) return fail(CRT_ERR_INVALID_ARG, "crt_render_adaptive: null scene");
-    return CRT_OK;
-}
+} // namespace crtk
 
-// Pixels of the shard (its pixel slots without the padding of ragged tiles and of tiles beyond the frame)
-uint64_t shard_pixels(const SlotMap& m)
-{
-    uint64_t n = 0;
-    for (uint32_t lt = 0; lt < m.nslots / 64u; lt++) n += tile_pixels(m, lt);
-    return n;
-}
-
-int adaptive_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean, void* d_samples,
-                  void* d_var, hipStream_t st, crt_adaptive_info* info)
-{
-    const int rc0 = adaptive_check(sc, cam, prm, ap, d_rgb, d_mean);
-    if (rc0 != CRT_OK) return rc0;
-    if (choose_pipeline(sc) != 4) return fail(CRT_ERR_UNSUPPORTED, "crt_render_adaptive: the fallback pipeline hands out its work items without the item list");
-    crt_params p = *prm; // the passes: ranges of a frame with the variance sums, without counters and without the commit ring
-    p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE);
-    const bool tiled = (p.flags & CRT_FLAG_TILED_OUTPUT) != 0;
-    const Shard sh = make_shard(p.width, p.height, p.world);
-    const uint32_t S = p.spp;
-    // whatever happens, no frame is in flight on the handle afterwards (the sums are an adaptive frame's: no range may continue them)
-    struct EndFrame {
-        crt_scene* sc;
-        ~EndFrame() { sc->acc.samples = 0; sc->var.valid = false; }
-    } end_frame{sc};
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (info) {
-            ensure_events(sc);
-            e0 = sc->ev[0]; e1 = sc->ev[1];
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
-        AdaptivePass pass;
-        std::memset(&pass, 0, sizeof(pass));
-        int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, 0, ap->min_samples, &pass); // the warm-up
-        if (rc != CRT_OK) return rc;
-        sc->ad_active.ensure_uncached(sh.nslots); sc->ad_nsamp.ensure_uncached(sh.nslots); sc->ad_list.ensure_uncached(sh.nslots);
-        sc->ad_count.ensure_uncached(1);
-        if (!sc->h_ad_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_ad_count, sizeof(unsigned int), hipHostMallocDefault));
-        FrameMark mark;
-        mark.set(&p, 0, tiled);
-        AdaptiveParams& D = pass.D;
-        D.A = frame_aparams(sc, mark, sh);
-        D.qacc = sc->accum_q.p;
-        D.active = sc->ad_active.p; D.nsamp = sc->ad_nsamp.p; D.list = sc->ad_list.p; D.count = sc->ad_count.p;
-        D.threshold = ap->threshold; D.mean_floor = ap->mean_floor;
-        D.n = ap->min_samples;
-        launch_adaptive_init(D, st);
-        HIP_CHECK(hipGetLastError());
-        crt_adaptive_info I;
-        std::memset(&I, 0, sizeof(I));
-        const uint64_t pixels = shard_pixels(D.A);
-        I.passes = 1; I.paths = pixels * ap->min_samples; I.paths_uniform = pixels * S;
-        double kernel_ms = 0.0;
-        bool kernel_unread = true; // a pass's launches have been enqueued whose time (ev_k0 .. ev_k1) has not been added yet
-        auto read_kernel_ms = [&]() { // after a synchronization
-            float ms = 0.0f;
-            if (info && kernel_unread) { HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1)); kernel_ms += ms; }
-            kernel_unread = false;
-        };
-        for (uint32_t n = ap->min_samples; n < S;) {
-            HIP_CHECK(hipMemsetAsync(sc->ad_count.p, 0, sizeof(unsigned int), st));
-            D.n = n;
-            launch_adaptive_select(D, st);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(sc->h_ad_count, sc->ad_count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of a pass: how many pixels go on
-            read_kernel_ms();
-            const uint32_t active = std::min<uint32_t>(*sc->h_ad_count, sh.nslots);
-            if (active == 0) break;
-            const uint32_t ns = std::min(ap->step_samples, S - n);
-            if (I.passes - 1u < CRT_ADAPTIVE_PASSES_REPORTED) I.pass_pixels[I.passes - 1u] = active;
-            pass.list = sc->ad_list.p; pass.n_active = active;
-            rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, n, ns, &pass);
-            if (rc != CRT_OK) return rc;
-            kernel_unread = true;
-            I.passes++; I.paths += (uint64_t)active * ns;
-            n += ns;
-        }
-        D.A.out_rgb = (uint8_t*)d_rgb; D.A.out_mean = (float*)d_mean;
-        D.out_samples = (uint32_t*)d_samples; D.out_variance = (float*)d_var;
-        launch_adaptive_resolve(D, st);
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            read_kernel_ms();
-            I.kernel_ms = (float)kernel_ms;
-            HIP_CHECK(hipEventElapsedTime(&I.total_ms, e0, e1));
-            *info = I;
-        }
-        return CRT_OK;
-    } catch (const HipFail& e) {
-        return fail_hip(e);
-    }
-}
-
-// ---------- crt_render_map, crt_sample_plan, crt_render_planned (contract: include/crt.h): per-pixel sample counts in one launch per chunk ----------
-const uint32_t kMaxMapSpp = 1u << 24; // (the histogram and the cursors: 8 B per sample of the cap on the device, as much pinned)
-
-int threshold_check(const char* who, float threshold, float mean_floor)
-{
-    if (!(threshold >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": threshold must be >= 0 and not NaN");
-    if (!(mean_floor >= 0.0f) || mean_floor > FLT_MAX) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": mean_floor must be >= 0 and finite");
-    return CRT_OK;
-}
-
-// Argument checks of crt_render_map* (planned == nullptr) and crt_render_planned*, before any device call; the scene comes last, as in
-// adaptive_check
-int map_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const void* map, uint32_t s_begin, const crt_adaptive_params* planned,
-              bool is_planned, const void* out_rgb, const void* out_mean)
-{
-    const char* who = is_planned ? "crt_render_planned" : "crt_render_map";
-    const std::string w(who);
-    if (!cam) return fail(CRT_ERR_INVALID_ARG, w + ": null camera");
-    if (!prm) return fail(CRT_ERR_INVALID_ARG, w + ": null params");
-    if (is_planned && !planned) return fail(CRT_ERR_INVALID_ARG, w + ": null adaptive params");
-    if (!is_planned && !map) return fail(CRT_ERR_INVALID_ARG, w + ": null sample map");
-    if (!out_rgb && !out_mean) return fail(CRT_ERR_INVALID_ARG, w + ": out_rgb and out_mean are both null");
-    if (is_planned) {
-        if (planned->min_samples < 2 || planned->min_samples > prm->spp) return fail(CRT_ERR_INVALID_ARG, w + ": min_samples must be in [2, spp] (the variance needs two samples)");
-        const int rc = threshold_check(who, planned->threshold, planned->mean_floor);
-        if (rc != CRT_OK) return rc;
-    }
-    const int rc = params_check(prm);
-    if (rc != CRT_OK) return rc;
-    if (!is_planned && s_begin >= prm->spp) return fail(CRT_ERR_INVALID_ARG, w + ": sample_begin must be below spp");
-    if (prm->spp > kMaxMapSpp) return fail(CRT_ERR_UNSUPPORTED, w + ": spp above 2^24");
-    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > kMaxChunkItems) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^30 pixel slots in a shard");
-    if (!sc) return fail(CRT_ERR_INVALID_ARG, w + ": null scene");
-    if (choose_pipeline(sc) != 4) return fail(CRT_ERR_UNSUPPORTED, w + ": the fallback pipeline hands out its work items without the item list");
-    if (!is_planned && s_begin > 0) {
-        const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
-        if (!continues_frame(sc->acc, prm, s_begin, tiled) || !sc->var.valid || !continues_frame(sc->var, prm, s_begin, tiled))
-            return fail(CRT_ERR_INVALID_ARG, w + ": sample_begin " + std::to_string(s_begin) + " must continue the frame in flight: exactly samples [0, sample_begin) of every pixel "
-                                             "with CRT_FLAG_VARIANCE from sample 0 on, and the same spp, width, height, rank, world and CRT_FLAG_TILED_OUTPUT (" +
-                                             (sc->acc.samples == 0 ? std::string("no frame is in flight on the handle")
-                                                                   : "the frame in flight holds samples [0, " + std::to_string(sc->acc.samples) + ") of spp " + std::to_string(sc->acc.spp) +
-                                                                         (sc->var.valid ? ", with" : ", without") + " valid variance sums") + ")");
-    }
-    return CRT_OK;
-}
-
-// Both calls.  planned == nullptr: d_map is the caller's W x H map and s_begin its sample_begin.  Otherwise the warm-up range and the
-// plan come first, and the map is the plan's, per pixel slot, on the device all the way.
-int map_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* d_map, uint32_t s_begin, const crt_adaptive_params* planned,
-             bool is_planned, void* d_rgb, void* d_mean, void* d_samples, void* d_var, hipStream_t st, crt_map_info* info)
-{
-    const int rc0 = map_check(sc, cam, prm, d_map, s_begin, planned, is_planned, d_rgb, d_mean);
-    if (rc0 != CRT_OK) return rc0;
-    crt_params p = *prm; // ranges of a frame with the variance sums, without counters and without the commit ring
-    p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE);
-    const bool tiled = (p.flags & CRT_FLAG_TILED_OUTPUT) != 0;
-    const Shard sh = make_shard(p.width, p.height, p.world);
-    const uint32_t S = p.spp;
-    struct EndFrame { // whatever happens from here on, no frame is in flight on the handle afterwards
-        crt_scene* sc;
-        ~EndFrame() { sc->acc.samples = 0; sc->var.valid = false; }
-    } end_frame{sc};
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (info) {
-            ensure_events(sc);
-            e0 = sc->ev[0]; e1 = sc->ev[1];
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
-        // (before anything takes their addresses: render_impl's own calls then find them in place)
-        sc->accum.ensure_uncached((size_t)sh.nslots * 3); sc->accum_q.ensure_uncached((size_t)sh.nslots * 3);
-        sc->ad_nsamp.ensure_uncached(sh.nslots); sc->ad_list.ensure_uncached(sh.nslots);
-        sc->map_hist.ensure_uncached((size_t)S + 1); sc->map_cursor.ensure_uncached(S);
-        const size_t words = 2 * ((size_t)S + 1);
-        if (sc->h_map_words < words) {
-            if (sc->h_map) { (void)hipHostFree(sc->h_map); sc->h_map = nullptr; sc->h_map_words = 0; }
-            HIP_CHECK(hipHostMalloc((void**)&sc->h_map, words * sizeof(unsigned int), hipHostMallocDefault));
-            sc->h_map_words = words;
-        }
-        unsigned int* const h_hist = sc->h_map;
-        unsigned int* const h_cursor = sc->h_map + S + 1;
-        AdaptivePass pass;
-        std::memset(&pass, 0, sizeof(pass));
-        uint32_t warm_launches = 0;
-        if (is_planned) { // the warm-up: crt_render_range(0, min_samples) with the variance sums
-            s_begin = planned->min_samples;
-            const int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, 0, s_begin, &pass);
-            if (rc != CRT_OK) return rc;
-            warm_launches = sc->last_launches;
-        }
-        FrameMark mark;
-        mark.set(&p, 0, tiled);
-        MapPass mp;
-        std::memset(&mp.D, 0, sizeof(mp.D));
-        MapParams& D = mp.D;
-        D.A = frame_aparams(sc, mark, sh);
-        D.qacc = sc->accum_q.p; D.nsamp = sc->ad_nsamp.p; D.hist = sc->map_hist.p; D.cursor = sc->map_cursor.p;
-        D.sample_begin = s_begin;
-        D.map = d_map;
-        if (is_planned) { // the plan at n = min_samples, one count per pixel slot
-            MapParams Q = D;
-            Q.A.tiled_output = 1u;
-            Q.n = s_begin; Q.threshold = planned->threshold; Q.mean_floor = planned->mean_floor; Q.out_map = sc->ad_list.p;
-            launch_sample_plan(Q, st);
-            HIP_CHECK(hipGetLastError());
-            D.map = sc->ad_list.p; D.map_per_slot = 1u;
-        }
-        HIP_CHECK(hipMemsetAsync(sc->map_hist.p, 0, ((size_t)S + 1) * sizeof(unsigned int), st));
-        launch_map_prepare(D, st);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpyAsync(h_hist, sc->map_hist.p, ((size_t)S + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of the call: how many slots take each sample
-        double kernel_ms = 0.0;
-        if (info && warm_launches) {
-            float ms = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1));
-            kernel_ms += ms;
-        }
-        // count_s = slots with n_p > s, from the top of the histogram down (h_hist[0]: the padding slots)
-        crt_map_info I;
-        std::memset(&I, 0, sizeof(I));
-        uint32_t max_np = 0;
-        uint64_t pixels = 0, all_samples = 0;
-        for (uint32_t v = 1; v <= S; v++) {
-            const uint64_t c = std::min<uint32_t>(h_hist[v], sh.nslots);
-            pixels += c; all_samples += c * v;
-            if (c) max_np = v;
-        }
-        pixels = std::min<uint64_t>(pixels, sh.nslots); // (a histogram that is not one cannot size a list beyond the chunk)
-        I.max_samples = max_np; I.launches = warm_launches;
-        I.paths = all_samples - (is_planned ? 0u : pixels * s_begin); // (n_p >= sample_begin at every pixel)
-        I.paths_uniform = pixels * S;
-        if (max_np > s_begin) {
-            const uint32_t s_count = max_np - s_begin, chunk = chunk_samples(sh.nslots, s_count);
-            uint64_t above = 0; // slots with n_p > s
-            std::vector<uint32_t> count(s_count);
-            for (uint32_t s = max_np; s-- > s_begin;) {
-                above = std::min<uint64_t>(above + h_hist[s + 1], sh.nslots);
-                count[s - s_begin] = (uint32_t)above;
-            }
-            for (uint32_t s0 = s_begin; s0 < max_np; s0 += chunk) {
-                uint64_t at = 0; // (at most chunk x nslots <= 2^30)
-                for (uint32_t s = s0; s < std::min(s0 + chunk, max_np); s++) { h_cursor[s] = (unsigned int)at; at += count[s - s_begin]; }
-                mp.chunk_items.push_back((uint32_t)at);
-            }
-            HIP_CHECK(hipMemcpyAsync(sc->map_cursor.p + s_begin, h_cursor + s_begin, (size_t)s_count * sizeof(unsigned int), hipMemcpyHostToDevice, st));
-            pass.map = &mp;
-            const int rc = render_impl(sc, cam, &p, nullptr, nullptr, st, nullptr, s_begin, s_count, &pass);
-            if (rc != CRT_OK) return rc;
-            I.launches += (uint32_t)mp.chunk_items.size();
-        }
-        AdaptiveParams R; // the frame: k_adaptive_resolve on the count plane and the sums
-        std::memset(&R, 0, sizeof(R));
-        R.A = D.A; R.qacc = D.qacc; R.nsamp = D.nsamp;
-        R.A.out_rgb = (uint8_t*)d_rgb; R.A.out_mean = (float*)d_mean;
-        R.out_samples = (uint32_t*)d_samples; R.out_variance = (float*)d_var;
-        launch_adaptive_resolve(R, st);
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            if (I.launches > warm_launches) {
-                float ms = 0.0f;
-                HIP_CHECK(hipEventElapsedTime(&ms, sc->ev_k0, sc->ev_k1));
-                kernel_ms += ms;
-            }
-            I.kernel_ms = (float)kernel_ms;
-            HIP_CHECK(hipEventElapsedTime(&I.total_ms, e0, e1));
-            *info = I;
-        }
-        return CRT_OK;
-    } catch (const HipFail& e) {
-        return fail_hip(e);
-    }
-}
-
-// Argument checks of both forms of crt_sample_plan, before any device call
-int plan_check(const crt_scene* sc, float threshold, float mean_floor, const void* out)
-{
-    if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: null argument");
-    const int rc = threshold_check("crt_sample_plan", threshold, mean_floor);
-    if (rc != CRT_OK) return rc;
-    if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
-    if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, "crt_sample_plan: fewer than 2 samples accumulated (one sample has no variance)");
-    return CRT_OK;
-}
+namespace {
 
 // The first-hit AOV pass (crt_render_aov): the camera rays of samples 0 .. spp-1 of every pixel slot of the shard, in chunks of whole
 // samples of at most kAovChunkRays rays (32 B of query pool + 16 B of results per ray: 1.6 GB), each traced by trace_queries and folded
@@ -1018,12 +713,8 @@ int aov_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm,
     if (!sc || !cam || !prm || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: null argument");
     if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->tri && !out->material)
         return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: no output buffer");
-    if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: width, height and spp must be positive");
-    if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: need rank < world");
-    if (prm->traversal != CRT_TRAVERSAL_FAST && prm->traversal != CRT_TRAVERSAL_REFERENCE && prm->traversal != CRT_TRAVERSAL_EXACT)
-        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: unknown traversal mode");
-    if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: world > 1 needs CRT_FLAG_TILED_OUTPUT");
-    if ((uint64_t)prm->width * prm->height > 0xffffffffull) return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov: more than 2^32 pixels");
+    const int rc = params_check("crt_render_aov", prm, true);
+    if (rc != CRT_OK) return rc;
     if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
         return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov: more than 2^31 pixel slots in a shard");
     return CRT_OK;
@@ -1035,7 +726,7 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
     if (rc != CRT_OK) return rc;
     const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
     const Shard sh = make_shard(prm->width, prm->height, prm->world);
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
         const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
@@ -1081,72 +772,7 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
             HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
         }
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
-}
-
-uint32_t choose_pipeline(const crt_scene* sc)
-{
-    uint32_t pipeline = env_u32("CRT_PIPELINE", 4);
-    if (pipeline != 2) pipeline = 4;
-    const uint64_t max_leaf = env_u32("CRT_TEST_MAX_LEAF", CRT_MEGA3_MAX_LEAF);
-    const uint64_t max_bytes = std::getenv("CRT_TEST_MAX_BYTES") ? (uint64_t)env_u32("CRT_TEST_MAX_BYTES", 0xffffffffu) : (1ull << 32);
-    const uint32_t max_stack = env_u32("CRT_TEST_MAX_STACK", CRT_MEGA3_MAX_STACK);
-    if (pipeline == 4 && sc->max_leaf > max_leaf) pipeline = 2;
-    if (pipeline == 4 && (sc->nodes4.n * sizeof(float4) >= max_bytes || sc->nodes3.n * sizeof(float4) >= max_bytes || sc->leaf_geo.n * sizeof(float4) >= max_bytes))
-        pipeline = 2; // (33 M nodes / 53 M records)
-    if (pipeline == 4 && (uint32_t)sc->stack_cap > max_stack) pipeline = 2; // a deeper stack would spill into the flag bits of word D
-    return pipeline;
-}
-
-// Pixels (or, tiled, pixel slots) of the frame buffers a shard writes
-uint64_t out_pixels(uint32_t w, uint32_t h, uint32_t world, bool tiled)
-{
-    return tiled ? make_shard(w, h, world).nslots : (uint64_t)w * h;
-}
-
-// The host-buffer form of an entry that writes an rgb8 frame and / or three float planes: device buffers for the device form (null
-// where not asked for), then the copies back
-struct Staging {
-    uint64_t npix;
-    DevBuf<uint8_t> rgb;
-    DevBuf<float> f32;
-    Staging(uint64_t npix_, bool want_rgb, bool want_f32) : npix(npix_)
-    {
-        if (want_rgb) rgb.alloc(npix * 3);
-        if (want_f32) f32.alloc(npix * 3);
-    }
-    void download(uint8_t* out_rgb, float* out_f32)
-    {
-        HIP_CHECK(hipDeviceSynchronize()); // Render.cuh:440
-        rgb.download(out_rgb, npix * 3); // Render.cuh:464
-        f32.download(out_f32, npix * 3);
-    }
-};
-
-// The host-buffer forms of crt_render_map and crt_render_planned: device buffers for map_impl, then the copies back
-int map_host(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* sample_map, uint32_t s_begin, const crt_adaptive_params* planned, bool is_planned,
-             uint8_t* out_rgb, float* out_mean, uint32_t* out_samples, float* out_variance, crt_map_info* info)
-{
-    const int rc0 = map_check(sc, cam, prm, sample_map, s_begin, planned, is_planned, out_rgb, out_mean);
-    if (rc0 != CRT_OK) return rc0;
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
-        Staging s(npix, out_rgb != nullptr, out_mean != nullptr), v(npix, false, out_variance != nullptr);
-        DevBuf<uint32_t> n, m;
-        if (out_samples) n.alloc(npix);
-        if (!is_planned) m.upload(sample_map, (size_t)prm->width * prm->height);
-        const int rc = map_impl(sc, cam, prm, m.p, s_begin, planned, is_planned, s.rgb.p, s.f32.p, n.p, v.f32.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        s.download(out_rgb, out_mean);
-        v.download(nullptr, out_variance);
-        n.download(out_samples, npix);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 } // namespace
@@ -1162,16 +788,14 @@ int crt_render(crt_scene* sc, const crt_camera* cam, const crt_params* prm, uint
 {
     if (!sc || !prm || !out_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_render: null argument");
     if (prm->world == 0 || prm->rank >= prm->world || prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render: bad shard or size");
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0), true, out_mean != nullptr);
         int rc = render_impl(sc, cam, prm, s.rgb.p, s.f32.p, nullptr, stats);
         if (rc != CRT_OK) return rc;
         s.download(out_rgb, out_mean);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_render_range_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, uint32_t sample_begin, uint32_t sample_count,
@@ -1190,114 +814,14 @@ int crt_render_range(crt_scene* sc, const crt_camera* cam, const crt_params* prm
         return fail(CRT_ERR_INVALID_ARG, "crt_render_range: sample range outside [0, spp)");
     const bool last = sample_begin + sample_count == prm->spp;
     if (last && !out_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_render_range: the range that ends at spp needs a frame buffer");
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0), last, last && out_mean);
         int rc = render_impl(sc, cam, prm, s.rgb.p, s.f32.p, nullptr, stats, sample_begin, sample_count);
         if (rc != CRT_OK) return rc;
         s.download(last ? out_rgb : nullptr, last ? out_mean : nullptr);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
-}
-
-int crt_adaptive_defaults(crt_adaptive_params* ap)
-{
-    if (!ap) return fail(CRT_ERR_INVALID_ARG, "crt_adaptive_defaults: null argument");
-    ap->min_samples = 16; ap->step_samples = 64; ap->threshold = 0.05f; ap->mean_floor = 0.01f;
-    return CRT_OK;
-}
-
-int crt_render_adaptive_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean,
-                               void* d_samples, void* d_variance, void* stream, crt_adaptive_info* info)
-{
-    return adaptive_impl(sc, cam, prm, ap, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
-}
-
-int crt_render_adaptive(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, uint8_t* out_rgb, float* out_mean,
-                        uint32_t* out_samples, float* out_variance, crt_adaptive_info* info)
-{
-    const int rc0 = adaptive_check(sc, cam, prm, ap, out_rgb, out_mean);
-    if (rc0 != CRT_OK) return rc0;
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
-        Staging s(npix, out_rgb != nullptr, out_mean != nullptr), v(npix, false, out_variance != nullptr);
-        DevBuf<uint32_t> n;
-        if (out_samples) n.alloc(npix);
-        const int rc = adaptive_impl(sc, cam, prm, ap, s.rgb.p, s.f32.p, n.p, v.f32.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        s.download(out_rgb, out_mean);
-        v.download(nullptr, out_variance);
-        n.download(out_samples, npix);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
-}
-
-int crt_render_map_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const void* d_sample_map, uint32_t sample_begin, void* d_rgb, void* d_mean,
-                          void* d_samples, void* d_variance, void* stream, crt_map_info* info)
-{
-    return map_impl(sc, cam, prm, (const uint32_t*)d_sample_map, sample_begin, nullptr, false, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
-}
-
-int crt_render_map(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const uint32_t* sample_map, uint32_t sample_begin, uint8_t* out_rgb, float* out_mean,
-                   uint32_t* out_samples, float* out_variance, crt_map_info* info)
-{
-    return map_host(sc, cam, prm, sample_map, sample_begin, nullptr, false, out_rgb, out_mean, out_samples, out_variance, info);
-}
-
-int crt_render_planned_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, void* d_rgb, void* d_mean, void* d_samples,
-                              void* d_variance, void* stream, crt_map_info* info)
-{
-    return map_impl(sc, cam, prm, nullptr, 0, ap, true, d_rgb, d_mean, d_samples, d_variance, (hipStream_t)stream, info);
-}
-
-int crt_render_planned(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_adaptive_params* ap, uint8_t* out_rgb, float* out_mean,
-                       uint32_t* out_samples, float* out_variance, crt_map_info* info)
-{
-    return map_host(sc, cam, prm, nullptr, 0, ap, true, out_rgb, out_mean, out_samples, out_variance, info);
-}
-
-int crt_sample_plan_device(crt_scene* sc, float threshold, float mean_floor, void* d_map, void* stream, crt_plan_info* info)
-{
-    const int rc = plan_check(sc, threshold, mean_floor, d_map);
-    if (rc != CRT_OK) return rc;
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        MapParams D;
-        std::memset(&D, 0, sizeof(D));
-        D.A = frame_aparams(sc, sc->var, make_shard(sc->var.width, sc->var.height, sc->var.world));
-        D.qacc = sc->accum_q.p;
-        D.n = sc->var.samples; D.threshold = threshold; D.mean_floor = mean_floor; D.out_map = (uint32_t*)d_map;
-        launch_sample_plan(D, (hipStream_t)stream);
-        HIP_CHECK(hipGetLastError());
-        if (info) { info->samples = sc->var.samples; info->spp = sc->var.spp; }
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
-}
-
-int crt_sample_plan(crt_scene* sc, float threshold, float mean_floor, uint32_t* out_map, crt_plan_info* info)
-{
-    const int rc0 = plan_check(sc, threshold, mean_floor, out_map);
-    if (rc0 != CRT_OK) return rc0;
-    try {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(sc->var.width, sc->var.height, sc->var.world, sc->var.tiled != 0);
-        DevBuf<uint32_t> m;
-        m.alloc(npix);
-        const int rc = crt_sample_plan_device(sc, threshold, mean_floor, m.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        m.download(out_map, npix);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_last_launch_ms(crt_scene* sc, float* ms, uint32_t* launches)
@@ -1318,20 +842,11 @@ int crt_radiance_storage(crt_scene* sc, uint64_t* bytes, uint32_t* ring_samples)
     return CRT_OK;
 }
 
-// Argument checks of both forms of crt_variance, before any device call
-static int variance_check(const crt_scene* sc, const void* out)
-{
-    if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, "crt_variance: null argument");
-    if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, "crt_variance: no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
-    if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, "crt_variance: fewer than 2 samples accumulated (one sample has no variance)");
-    return CRT_OK;
-}
-
 int crt_variance_device(crt_scene* sc, void* d_var, void* stream, uint32_t* samples_done)
 {
-    const int rc = variance_check(sc, d_var);
+    const int rc = sums_check("crt_variance", sc, d_var);
     if (rc != CRT_OK) return rc;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         AParams A = frame_aparams(sc, sc->var, make_shard(sc->var.width, sc->var.height, sc->var.world));
         A.out_mean = (float*)d_var;
@@ -1339,32 +854,28 @@ int crt_variance_device(crt_scene* sc, void* d_var, void* stream, uint32_t* samp
         HIP_CHECK(hipGetLastError());
         if (samples_done) *samples_done = sc->var.samples;
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_variance(crt_scene* sc, float* out_var, uint32_t* samples_done)
 {
-    const int rc0 = variance_check(sc, out_var);
+    const int rc0 = sums_check("crt_variance", sc, out_var);
     if (rc0 != CRT_OK) return rc0;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(sc->var.width, sc->var.height, sc->var.world, sc->var.tiled != 0), false, true);
         const int rc = crt_variance_device(sc, s.f32.p, nullptr, samples_done);
         if (rc != CRT_OK) return rc;
         s.download(nullptr, out_var);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_preview_device(crt_scene* sc, void* d_rgb, void* d_mean, void* stream, uint32_t* samples_done)
 {
     if (!sc || !d_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_preview: null argument");
     if (sc->acc.samples == 0) return fail(CRT_ERR_INVALID_ARG, "crt_preview: no progressive render in flight (submit a range that ends before spp first)");
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         AParams A = frame_aparams(sc, sc->acc, make_shard(sc->acc.width, sc->acc.height, sc->acc.world));
         A.out_rgb = (uint8_t*)d_rgb; A.out_mean = (float*)d_mean;
@@ -1373,25 +884,21 @@ int crt_preview_device(crt_scene* sc, void* d_rgb, void* d_mean, void* stream, u
         HIP_CHECK(hipGetLastError());
         if (samples_done) *samples_done = sc->acc.samples;
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_preview(crt_scene* sc, uint8_t* out_rgb, float* out_mean, uint32_t* samples_done)
 {
     if (!sc || !out_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_preview: null argument");
     if (sc->acc.samples == 0) return fail(CRT_ERR_INVALID_ARG, "crt_preview: no progressive render in flight (submit a range that ends before spp first)");
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(sc->acc.width, sc->acc.height, sc->acc.world, sc->acc.tiled != 0), true, out_mean != nullptr);
         int rc = crt_preview_device(sc, s.rgb.p, s.f32.p, nullptr, samples_done);
         if (rc != CRT_OK) return rc;
         s.download(out_rgb, out_mean);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* dirs, uint32_t traversal, int32_t* out_tri, float* out_t)
@@ -1404,7 +911,7 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
     if (traversal != CRT_TRAVERSAL_FAST && traversal != CRT_TRAVERSAL_REFERENCE && traversal != CRT_TRAVERSAL_EXACT)
         return fail(CRT_ERR_INVALID_ARG, "crt_intersect: unknown traversal mode");
     if (n == 0) return CRT_OK;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         DevBuf<float> o, d, lim;
         o.upload(origins, n * 3ull); d.upload(dirs, n * 3ull);
@@ -1435,9 +942,7 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
             answer(i, res[(size_t)i * stride], tri);
         }
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_render_aov_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_out, void* stream, crt_aov_info* info)
@@ -1450,7 +955,7 @@ int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, 
     const int rc0 = aov_check(sc, cam, prm, host_out);
     if (rc0 != CRT_OK) return rc0;
     const crt_aov_buffers& h = *host_out;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
         void* const host[6] = {h.albedo, h.normal, h.depth, h.coverage, h.tri, h.material}; // 4-byte values: three per pixel, three, then one each
@@ -1463,9 +968,7 @@ int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, 
         HIP_CHECK(hipDeviceSynchronize());
         for (int i = 0; i < 6; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_device_math(int device, const char* fn, uint32_t n, const float* a, const float* b, float* out)
@@ -1477,7 +980,7 @@ int crt_device_math(int device, const char* fn, uint32_t n, const float* a, cons
         if (std::strcmp(fn, names[i]) == 0) id = i;
     if (id < 0) return fail(CRT_ERR_INVALID_ARG, std::string("crt_device_math: unknown function ") + fn);
     if (n == 0) return CRT_OK;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(device));
         DevBuf<float> da, db, dout;
         da.upload(a, n); db.upload(b, n); dout.alloc(n);
@@ -1486,16 +989,14 @@ int crt_device_math(int device, const char* fn, uint32_t n, const float* a, cons
         HIP_CHECK(hipDeviceSynchronize());
         dout.download(out, n);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4)
 {
     if (!ctr4 || !key2 || !out4) return fail(CRT_ERR_INVALID_ARG, "crt_device_philox: null argument");
     if (n == 0) return CRT_OK;
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(device));
         DevBuf<uint32_t> c, k, o;
         c.upload(ctr4, n * 4ull); k.upload(key2, n * 2ull); o.alloc(n * 4ull);
@@ -1504,15 +1005,13 @@ int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32
         HIP_CHECK(hipDeviceSynchronize());
         o.download(out4, n * 4ull);
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside)
 {
     if (!mismatches || !outside) return fail(CRT_ERR_INVALID_ARG, "crt_device_rcp_check: null argument");
-    try {
+    return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(device));
         DevBuf<unsigned long long> c;
         c.alloc(2);
@@ -1524,9 +1023,7 @@ int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside)
         c.download(h, 2);
         *mismatches = h[0]; *outside = h[1];
         return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    });
 }
 
 } // extern "C"

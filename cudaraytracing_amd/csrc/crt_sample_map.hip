@@ -1,17 +1,14 @@
 // cudaraytracing_amd/csrc/crt_sample_map.hip -- the kernels of crt_render_map, crt_sample_plan and crt_render_planned (contract:
-// include/crt.h; host side: crt_render.hip): a frame in which pixel p gets samples sample_begin .. n_p - 1, n_p given per pixel, in ONE
+// include/crt.h; host side: crt_sparse.hip): a frame in which pixel p gets samples sample_begin .. n_p - 1, n_p given per pixel, in ONE
 // launch of k_mega3 per chunk of samples.  k_map_prepare turns the caller's map into the per-slot counts and their histogram, from which
 // the host sizes every chunk; k_map_items writes a chunk's item list (sample-major, a wave's slots side by side); k_map_fold adds each
-// slot's own number of the chunk's samples to its sums; k_sample_plan solves the adaptive stop criterion for n.  The frame itself is
-// k_adaptive_resolve's (crt_adaptive.hip).
+// slot's own number of the chunk's samples to its sums, for the passes of crt_render_adaptive too; k_sample_plan solves the adaptive stop
+// criterion for n.  The frame itself is k_adaptive_resolve's (crt_adaptive.hip).
 // Memory: the sums, the count plane, the histogram and the cursors are uncached allocations accessed with agent-scope atomics only; the
 // item list is written with agent-scope stores, as k_order_items and k_adaptive_items write it (docs/experiments.md 6).
 #include "crt_internal.h"
 
 namespace crtk {
-
-__device__ __forceinline__ uint32_t map_word_load(const uint32_t* p) { return __hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void map_word_store(uint32_t* p, const uint32_t v) { __hip_atomic_store((unsigned int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // n_p = min(max(map[p], max(sample_begin, 1)), S) per pixel slot (padding slots 0) into the count plane, and the histogram of n_p over
 // 0 .. S.  The histogram is aggregated per wave before any atomic: the wave walks the distinct values among its lanes -- the first
@@ -19,7 +16,7 @@ __device__ __forceinline__ void map_word_store(uint32_t* p, const uint32_t v) { 
 // not one per slot on one address.  Every lane of a wave stays in the loop (its condition is a ballot): no lane returns early.
 __global__ __launch_bounds__(256) void k_map_prepare(const MapParams D)
 {
-    const AParams& A = D.A;
+    const AParams& A = D.sums.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     const bool in = slot < A.nslots;
     uint32_t np = 0;
@@ -29,7 +26,7 @@ __global__ __launch_bounds__(256) void k_map_prepare(const MapParams D)
             const uint32_t m = D.map[D.map_per_slot ? (uint64_t)slot : (uint64_t)px.j * A.width + px.i];
             np = min(max(m, max(D.sample_begin, 1u)), A.spp);
         }
-        map_word_store(D.nsamp + slot, np);
+        word_store(D.sums.nsamp + slot, np);
     }
     const int lane = threadIdx.x & 63;
     bool todo = in;
@@ -54,9 +51,9 @@ __global__ __launch_bounds__(256) void k_map_prepare(const MapParams D)
 // 512 samples everywhere; docs/experiments.md, "Sample maps and planned adaptive frames", has the remedy that was not run on a device.)
 __global__ __launch_bounds__(256) void k_map_items(const MapParams D)
 {
-    const AParams& A = D.A;
+    const AParams& A = D.sums.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
-    const uint32_t np = slot < A.nslots ? map_word_load(D.nsamp + slot) : 0u;
+    const uint32_t np = slot < A.nslots ? word_load(D.sums.nsamp + slot) : 0u;
     const uint32_t hi = min(np, D.s0 + D.ns);
     const uint32_t last_item = D.ns * A.nslots - 1u; // (ns x nslots < 2^32: the chunk's cap)
     const int lane = threadIdx.x & 63;
@@ -77,13 +74,13 @@ __global__ __launch_bounds__(256) void k_map_items(const MapParams D)
 
 // The chunk's samples into c and q: slot p takes min(n_p, s0 + ns) - s0 of them (none if n_p <= s0: its entries of L hold whatever an
 // earlier launch left).  The chunk that starts at sample 0 starts the sums of every slot at +0, padding included.
-__global__ __launch_bounds__(256) void k_map_fold(const MapParams D)
+__global__ __launch_bounds__(256) void k_map_fold(const SumsParams D, const uint32_t s0, const uint32_t ns)
 {
     const AParams& A = D.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
-    const uint32_t np = map_word_load(D.nsamp + slot);
-    const uint32_t count = np > D.s0 ? min(np, D.s0 + D.ns) - D.s0 : 0u;
+    const uint32_t np = word_load(D.nsamp + slot);
+    const uint32_t count = np > s0 ? min(np, s0 + ns) - s0 : 0u;
     if (count == 0u && !A.first_chunk) return;
     F3 c = f3(0.0f, 0.0f, 0.0f), q = f3(0.0f, 0.0f, 0.0f);
     if (!A.first_chunk) { c = acc_load3(A.accum, A.nslots, slot); q = acc_load3(D.qacc, A.nslots, slot); }
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(256) void k_map_fold(const MapParams D)
 // layout (padding slots of a tiled shard 0).  Reads the sums only.
 __global__ __launch_bounds__(256) void k_sample_plan(const MapParams D)
 {
-    const AParams& A = D.A;
+    const AParams& A = D.sums.A;
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
     const SlotPixel px = slot_pixel(A, slot);
@@ -104,24 +101,17 @@ __global__ __launch_bounds__(256) void k_sample_plan(const MapParams D)
     uint32_t np = 0;
     if (px.valid) {
         const float fn = (float)D.n, fs = (float)A.spp;
-        const float r = fs / fn, rr = r * r;
-        const F3 c = acc_load3(A.accum, A.nslots, slot);
-        const F3 var = variance_of3(c, acc_load3(D.qacc, A.nslots, slot), fn, rr);
-        const F3 p = f3(c.x * r, c.y * r, c.z * r);
-        const float v = (var.x + var.y) + var.z, m = (p.x + p.y) + p.z;
-        const float t = D.threshold * (m + D.mean_floor);
-        const float tt = t * t;
-        const float w = (fn * v) / tt;
+        const StopCriterion k = stop_criterion(A, D.sums.qacc, slot, D.n, D.threshold, D.mean_floor);
+        const float w = (fn * k.v) / k.tt;
         np = (w < fs) ? max(D.n, (uint32_t)ceilf(w)) : A.spp; // (NaN, +inf and w >= S: the cap; w < S is below 2^32, and a negative w cannot occur: v >= 0)
     }
     D.out_map[px.o] = np;
 }
 
-// ---- exported to crt_render.hip ----
-static dim3 slot_grid(const MapParams& D) { return dim3((D.A.nslots + 255) / 256); }
-void launch_map_prepare(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_map_prepare, slot_grid(D), dim3(256), 0, st, D); }
-void launch_map_items(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_map_items, slot_grid(D), dim3(256), 0, st, D); }
-void launch_map_fold(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_map_fold, slot_grid(D), dim3(256), 0, st, D); }
-void launch_sample_plan(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_sample_plan, slot_grid(D), dim3(256), 0, st, D); }
+// ---- exported to crt_sparse.hip ----
+void launch_map_prepare(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_map_prepare, slot_grid(D.sums.A), dim3(256), 0, st, D); }
+void launch_map_items(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_map_items, slot_grid(D.sums.A), dim3(256), 0, st, D); }
+void launch_map_fold(const SumsParams& D, uint32_t s0, uint32_t ns, hipStream_t st) { hipLaunchKernelGGL(k_map_fold, slot_grid(D.A), dim3(256), 0, st, D, s0, ns); }
+void launch_sample_plan(const MapParams& D, hipStream_t st) { hipLaunchKernelGGL(k_sample_plan, slot_grid(D.sums.A), dim3(256), 0, st, D); }
 
 } // namespace crtk

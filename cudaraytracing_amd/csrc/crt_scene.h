@@ -1,6 +1,6 @@
 // cudaraytracing_amd/csrc/crt_scene.h -- the scene handle of the device layer (struct crt_scene: the uploaded arrays, the buffers and
 // events a frame uses, what a progressive render has accumulated) and the small helpers crt_scene.hip (create / export / destroy) and
-// crt_render.hip (the launch logic) share: the shard of a frame, its slot map for the image-space kernels, the host's form of the slot rule.
+// crt_render.hip / crt_sparse.hip (the launch logic) share: the shard of a frame, its slot map for the image-space kernels, the host's form of the slot rule.
 #ifndef CRT_SCENE_H
 #define CRT_SCENE_H
 #include "crt_internal.h"
@@ -17,6 +17,12 @@ struct FrameMark {
     {
         samples = samples_; spp = prm->spp; width = prm->width; height = prm->height;
         rank = prm->rank; world = prm->world; tiled = tiled_ ? 1u : 0u;
+    }
+    // for the message of a range that does not continue the frame: what the sums hold, `tail` after the samples and spp
+    std::string in_flight(const std::string& tail) const
+    {
+        return samples == 0 ? std::string("no frame is in flight on the handle")
+                            : "the frame in flight holds samples [0, " + std::to_string(samples) + ") of spp " + std::to_string(spp) + tail;
     }
 };
 
@@ -73,9 +79,9 @@ struct crt_scene {
     // sums hold (crt_variance): samples so far of the frame the flag has been on for since sample 0; valid = the last render call had it
     crtk::DevBuf<float> accum_q;
     FrameMark var;
-    // crt_render_adaptive: per pixel slot whether it takes the next pass and its sample count, the compacted list of the active slots and
-    // its counter (uncached, agent-scope atomics only: crt_adaptive.hip), and the pinned word the counter is copied to once per pass
-    crtk::DevBuf<uint32_t> ad_active, ad_nsamp, ad_list;
+    // crt_render_adaptive: per pixel slot its sample count, the compacted list of the slots that take the next pass and its counter
+    // (uncached, agent-scope atomics only: crt_adaptive.hip), and the pinned word the counter is copied to once per pass
+    crtk::DevBuf<uint32_t> ad_nsamp, ad_list;
     crtk::DevBuf<unsigned int> ad_count;
     unsigned int* h_ad_count = nullptr;
     // crt_render_map: the histogram of the per-slot counts (spp + 1 words) and the cursors of the item-list kernel (spp words), uncached
@@ -135,6 +141,16 @@ inline uint32_t tile_pixels(const SlotMap& m, uint32_t lt)
     const uint32_t ty = tile / m.tiles_x, tx = tile - ty * m.tiles_x;
     const uint32_t w = m.width - tx * CRT_TILE, h = m.height - ty * CRT_TILE;
     return (w < CRT_TILE ? w : (uint32_t)CRT_TILE) * (h < CRT_TILE ? h : (uint32_t)CRT_TILE);
+}
+
+// What crt_variance and crt_sample_plan (`who`) need of the handle: sums of at least two samples of a frame with CRT_FLAG_VARIANCE
+inline int sums_check(const char* who, const crt_scene* sc, const void* out)
+{
+    const std::string w(who);
+    if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
+    if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, w + ": no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
+    if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, w + ": fewer than 2 samples accumulated (one sample has no variance)");
+    return CRT_OK;
 }
 
 inline uint32_t env_u32(const char* name, uint32_t dflt)

@@ -228,6 +228,20 @@ def test_restated_plan_is_the_recorded_distribution(name):
     assert (restated_plan(L, 4, np.inf, 0.01)[0] == 4).all()
 
 
+@pytest.mark.parametrize("name", SCENES)
+def test_restated_map_of_the_adaptive_counts_is_the_adaptive_frame(name):
+    """An adaptive frame is the map frame of its own sample counts: both fold samples 0 .. n_p - 1 of a pixel in order.  If this fails
+    the inputs are wrong, not the kernels."""
+    import test_adaptive as TA
+    assert (TA.W, TA.H, TA.S) == (W, H, S)
+    _, _, L = oracle_frame(name)
+    ad = TA.restated_adaptive(L, S, **TA.AD)
+    got = restated_map(L, ad["samples"])
+    assert np.array_equal(got["samples"], ad["samples"]) and got["paths"] == ad["paths"]
+    assert_bits(got["mean"], ad["mean"], "map of the adaptive counts: mean")
+    assert_bits(got["variance"], ad["variance"], "map of the adaptive counts: variance")
+
+
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
 @pytest.fixture(scope="module")
@@ -359,6 +373,25 @@ def test_map_continues_a_range_with_the_variance_sums(renders, name):
     assert r.preview(**kw)[2] == 5 and r.variance(**kw)[1] == 5
     assert np.array_equal(r.run_view_range(eye, iv, fov, 5, S - 5, want_variance=True, **kw), orgb)
     assert_bits(r.mean_buffer, omean, "the frame in flight after refused map calls")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("chunk_log2", [None, "12"])
+def test_map_of_the_adaptive_frames_samples_is_the_adaptive_frame(renders, name, chunk_log2, monkeypatch):
+    """crt_render_adaptive's out_samples fed to crt_render_map from sample 0: the same frame, bit for bit -- the passes and the map's
+    chunks fold through one kernel.  Once more with both calls in chunks of three samples."""
+    import test_adaptive as TA
+    if chunk_log2:
+        monkeypatch.setenv("CRT_CHUNK_LOG2", chunk_log2)
+    r = renders[name]
+    ad = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in TA.gpu_adaptive(r, name).items()}
+    assert ad["info"]["passes"] == 6 and ad["samples"].min() == 4 and ad["samples"].max() == S
+    got = gpu_map(r, name, ad["samples"])
+    assert np.array_equal(got["samples"], ad["samples"]) and got["info"]["paths"] == ad["info"]["paths"]
+    assert_bits(got["mean"], ad["mean"], "map of the adaptive samples: mean")
+    assert np.array_equal(got["rgb"], ad["rgb"])
+    assert_bits(got["variance"], ad["variance"], "map of the adaptive samples: variance")
 
 
 class DeviceBuffers:

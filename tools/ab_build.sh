@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds a variant of libcrt.so next to the default one: tools/ab_build.sh <name> [extra compiler flags...] -> cudaraytracing_amd/lib/ab/<name>.so
-# Every translation unit that sees the render kernel's headers (crt_mega3.h / crt_path.h: crt_mega3, crt_wavefront, crt_frame, crt_adaptive, crt_sample_map, crt_render, crt_scene)
+# Every translation unit that sees the render kernel's headers (crt_mega3.h / crt_path.h: build.KERNEL_HEADER_UNITS)
 # is recompiled with the extra flags into a private object directory, so that a -D which changes a shared layout (MParams3, LParams,
 # pool sizes, LEAF_REC_MAX ...) cannot produce a library whose units disagree; the host-only units (loader, tree builders,
 # multi-device entry) are the default build's.  AB_UNITS="crt_mega3.hip" restricts the recompilation for flags known to be local.
@@ -13,7 +13,7 @@ dev=$(python3 -c "import sys; sys.path.insert(0, '$root'); from cudaraytracing_a
 obj=$root/cudaraytracing_amd/lib/obj
 priv=$root/cudaraytracing_amd/lib/obj_ab/$name
 rm -rf $priv; mkdir -p $priv
-units=${AB_UNITS:-"crt_mega3.hip crt_wavefront.hip crt_frame.hip crt_adaptive.hip crt_sample_map.hip crt_render.hip crt_scene.hip"}
+units=${AB_UNITS:-$(python3 -c "import sys; sys.path.insert(0, '$root'); from cudaraytracing_amd import build as b; print(' '.join(b.KERNEL_HEADER_UNITS))")}
 pids=()
 for u in $units; do
   /opt/rocm/bin/hipcc $flags "$@" -c $root/cudaraytracing_amd/csrc/$u -o $priv/${u%.*}.o &

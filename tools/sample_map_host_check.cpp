@@ -1,8 +1,8 @@
-// tools/sample_map_host_check.cpp -- the kernels of cudaraytracing_amd/csrc/crt_sample_map.hip compiled for the HOST and run against plain
-// restatements, for AddressSanitizer / UBSan runs without a device.  The kernel file is included as it is; this file stands in for what
-// it takes from crt_internal.h (the slot map, the sums' accessors, the sample fold, the variance formula: the same text) and for the
-// device's launch indices, wave intrinsics and atomics.  A wave is 64 host threads that meet at a barrier in every cross-lane operation,
-// so a ballot sees all its lanes' predicates as the hardware's does; a block is run wave after wave.
+// tools/sample_map_host_check.cpp -- the kernels of cudaraytracing_amd/csrc/crt_sample_map.hip and crt_adaptive.hip compiled for the HOST
+// and run against plain restatements, for AddressSanitizer / UBSan runs without a device.  The kernel files and the stages they share
+// (crt_stages.h) are included as they are; this file stands in for what they take from crt_path.h and crt_device.h (the same text) and
+// for the device's launch indices, wave intrinsics and atomics.  A wave is 64 host threads that meet at a barrier in every cross-lane
+// operation, so a ballot sees all its lanes' predicates as the hardware's does; a block is run wave after wave.
 // Every buffer is sized exactly (std::vector of the element count the host code allocates), so an access one element out is a report.
 //
 //   g++ -std=c++17 -O1 -g -pthread -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
@@ -16,13 +16,15 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <set>
 #include <thread>
 #include <vector>
 
+#include "crt_detmath.h"
 #include "crt_fastdiv.h"
 
 // ---- stand-ins for the device ----
-#define CRT_INTERNAL_H // (crt_sample_map.hip's only include: replaced by what follows)
+#define CRT_INTERNAL_H // (the kernel files' only include: replaced by what follows)
 #define __global__
 #define __device__
 #define __forceinline__ inline
@@ -80,21 +82,20 @@ static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); 
 static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
 
 // a launch: block after block, wave after wave, 64 threads each
-template <class K, class P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, const P& params)
+template <class K, class... P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, P... params)
 {
     for (uint32_t b = 0; b < grid.x; b++)
         for (uint32_t w0 = 0; w0 < block.x; w0 += 64) {
             std::vector<std::thread> lanes;
             for (uint32_t l = 0; l < 64; l++)
-                lanes.emplace_back([=] { blockIdx.x = b; threadIdx.x = w0 + l; kernel(params); });
+                lanes.emplace_back([=] { blockIdx.x = b; threadIdx.x = w0 + l; kernel(params...); });
             for (std::thread& t : lanes) t.join();
         }
 }
 
-// ---- what crt_sample_map.hip takes from crt_internal.h / crt_path.h / crt_device.h: the same text ----
+// ---- what the kernels and crt_stages.h take from crt_path.h / crt_device.h: the same text ----
 namespace crtk {
-using crtdev::FastDiv;
-using crtdev::make_fastdiv;
+using namespace crtdev; // FastDiv, make_fastdiv, det_powf
 static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
 {
     const uint32_t t = (uint32_t)(((uint64_t)m * n) >> 32);
@@ -102,6 +103,8 @@ static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
 }
 struct F3 { float x, y, z; };
 static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
+static float maxf_ref(float x, float y) { return x > y ? x : y; }
+static float minf_ref(float x, float y) { return x < y ? x : y; }
 struct Rad3 { float x, y, z; };
 static Rad3 load_radiance(const Rad3* p) { return *p; }
 static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t n_tiles, uint32_t tiles_x, FastDiv tiles_x_div, uint32_t width, uint32_t height,
@@ -115,82 +118,10 @@ static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t
     j = ty * CRT_TILE + (pix >> 3);
     return i < width && j < height;
 }
-struct SlotMap {
-    uint32_t width, height, rank, world, tiles_x, n_tiles, nslots, tiled_output;
-    FastDiv tiles_x_div;
-};
-struct SlotPixel {
-    bool valid, out;
-    uint32_t i, j;
-    uint64_t o;
-};
-static SlotPixel slot_pixel(const SlotMap& m, const uint32_t slot)
-{
-    SlotPixel p;
-    p.i = 0; p.j = 0;
-    p.valid = slot_to_pixel(slot, m.rank, m.world, m.n_tiles, m.tiles_x, m.tiles_x_div, m.width, m.height, p.i, p.j);
-    p.out = p.valid || m.tiled_output;
-    p.o = m.tiled_output ? (uint64_t)slot : (uint64_t)p.j * m.width + p.i;
-    return p;
-}
-struct AParams : SlotMap {
-    uint32_t spp;
-    uint32_t chunk_samples;
-    uint32_t first_chunk, last_chunk;
-    const Rad3* L;
-    float* accum;
-    uint8_t* out_rgb;
-    float* out_mean;
-};
-static float acc_load(const float* p) { return __uint_as_float(__hip_atomic_load((const unsigned int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
-static void acc_store(float* p, const float v) { __hip_atomic_store((unsigned int*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-static F3 acc_load3(const float* planes, const uint32_t nslots, const uint32_t slot)
-{
-    return f3(acc_load(planes + slot), acc_load(planes + nslots + slot), acc_load(planes + 2ull * nslots + slot));
-}
-static void acc_store3(float* planes, const uint32_t nslots, const uint32_t slot, const F3 v)
-{
-    acc_store(planes + slot, v.x); acc_store(planes + nslots + slot, v.y); acc_store(planes + 2ull * nslots + slot, v.z);
-}
-template <bool VAR> static void fold_samples_n(const AParams& A, const uint32_t slot, const uint32_t count, F3& c, F3& q)
-{
-    const float fspp = (float)A.spp;
-    const Rad3* lp = A.L + slot;
-    for (uint32_t s = 0; s < count; s++, lp += A.nslots) {
-        const Rad3 l = load_radiance(lp);
-        const float xx = l.x / fspp, xy = l.y / fspp, xz = l.z / fspp;
-        c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
-        if (VAR) { q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz; }
-    }
-}
-static float variance_of(const float c, const float q, const float fn, const float rr)
-{
-    float d = fn * q - c * c;
-    d = d < 0.0f ? 0.0f : d;
-    return (rr * d) / (fn - 1.0f);
-}
-static F3 variance_of3(const F3 c, const F3 q, const float fn, const float rr)
-{
-    return f3(variance_of(c.x, q.x, fn, rr), variance_of(c.y, q.y, fn, rr), variance_of(c.z, q.z, fn, rr));
-}
-struct MapParams {
-    AParams A;
-    float* qacc;
-    uint32_t* nsamp;
-    const uint32_t* map;
-    uint32_t map_per_slot;
-    uint32_t sample_begin;
-    unsigned int* hist;
-    unsigned int* cursor;
-    uint32_t* item_list;
-    uint32_t n_items;
-    uint32_t s0, ns;
-    uint32_t n;
-    float threshold, mean_floor;
-    uint32_t* out_map;
-};
 } // namespace crtk
 
+#include "crt_stages.h"
+#include "crt_adaptive.hip"
 #include "crt_sample_map.hip"
 
 using namespace crtk;
@@ -203,15 +134,51 @@ static int g_fail = 0;
 
 static bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b); }
 
+// The slot map of shard rank / world of a w x h frame of cap S
+static AParams frame_of(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t world)
+{
+    AParams A{};
+    A.width = w; A.height = h; A.rank = rank; A.world = world; A.tiles_x = (w + 7) / 8; A.n_tiles = A.tiles_x * ((h + 7) / 8);
+    A.nslots = (A.n_tiles + world - 1) / world * 64; A.tiled_output = world > 1; A.tiles_x_div = make_fastdiv(A.tiles_x); A.spp = S;
+    return A;
+}
+
+// ---- plain restatements, on planes c3 / q3 of nslots floats per channel ----
+// the stop criterion at a slot whose sums hold n of S samples: (v, t * t)
+static void restated_criterion(const std::vector<float>& c3, const std::vector<float>& q3, uint32_t nslots, uint32_t slot, uint32_t n, uint32_t S, float thr, float floor_,
+                               float& v, float& tt)
+{
+    const float fn = (float)n, r = (float)S / fn;
+    float v3[3], p3[3];
+    for (int ch = 0; ch < 3; ch++) {
+        const float c = c3[(size_t)ch * nslots + slot], q = q3[(size_t)ch * nslots + slot];
+        const float d = fn * q - c * c;
+        v3[ch] = ((r * r) * (d < 0.0f ? 0.0f : d)) / (fn - 1.0f);
+        p3[ch] = c * r;
+    }
+    v = (v3[0] + v3[1]) + v3[2];
+    const float t = thr * (((p3[0] + p3[1]) + p3[2]) + floor_);
+    tt = t * t;
+}
+// the first `count` samples of the chunk L into the sums of a slot
+static void restated_fold(std::vector<float>& c3, std::vector<float>& q3, const std::vector<Rad3>& L, uint32_t nslots, uint32_t slot, uint32_t count, uint32_t S)
+{
+    for (int ch = 0; ch < 3; ch++)
+        for (uint32_t s = 0; s < count; s++) {
+            const Rad3& l = L[(size_t)s * nslots + slot];
+            const float x = (ch == 0 ? l.x : ch == 1 ? l.y : l.z) / (float)S;
+            c3[(size_t)ch * nslots + slot] = c3[(size_t)ch * nslots + slot] + x;
+            q3[(size_t)ch * nslots + slot] = q3[(size_t)ch * nslots + slot] + x * x;
+        }
+}
+
 // One frame of w x h, cap S, as shard rank / world, from sample_begin, in chunks of `chunk` samples: every kernel against its restatement
 static void run_case(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t world, uint32_t sample_begin, uint32_t chunk)
 {
-    const uint32_t tiles_x = (w + 7) / 8, tiles_y = (h + 7) / 8, n_tiles = tiles_x * tiles_y, nslots = (n_tiles + world - 1) / world * 64;
-    MapParams D;
-    std::memset(&D, 0, sizeof(D));
-    AParams& A = D.A;
-    A.width = w; A.height = h; A.rank = rank; A.world = world; A.tiles_x = tiles_x; A.n_tiles = n_tiles; A.nslots = nslots;
-    A.tiled_output = world > 1; A.tiles_x_div = make_fastdiv(tiles_x); A.spp = S;
+    MapParams D{};
+    AParams& A = D.sums.A;
+    A = frame_of(w, h, S, rank, world);
+    const uint32_t tiles_x = A.tiles_x, n_tiles = A.n_tiles, nslots = A.nslots;
     std::vector<uint32_t> map((size_t)w * h), nsamp(nslots, 0xdeadbeefu);
     for (uint32_t y = 0; y < h; y++)
         for (uint32_t x = 0; x < w; x++) map[(size_t)y * w + x] = (7 * x + 3 * y * y) % (S + 3);
@@ -223,7 +190,7 @@ static void run_case(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t
     for (float& v : accum) v = sample_begin ? rnd() : -7.0f; // (from sample 0 the first chunk must overwrite them)
     for (float& v : qacc) v = sample_begin ? rnd() : -7.0f;
     std::vector<float> c_ref = accum, q_ref = qacc;
-    D.qacc = qacc.data(); D.nsamp = nsamp.data(); D.map = map.data(); D.hist = hist.data(); D.cursor = cursor.data(); A.accum = accum.data();
+    D.sums.qacc = qacc.data(); D.sums.nsamp = nsamp.data(); D.map = map.data(); D.hist = hist.data(); D.cursor = cursor.data(); A.accum = accum.data();
     D.sample_begin = sample_begin;
     launch_map_prepare(D, nullptr);
     // restated counts and histogram
@@ -269,18 +236,9 @@ static void run_case(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t
         uint32_t end = 0; // every sample's cursor has moved from its first position to its last + 1
         for (uint32_t s = s0; s < s0 + ns; s++) { end += count[s]; CHECK(cursor[s] == end, "cursor of sample %u is %u, expected %u", s, cursor[s], end); }
         A.L = L.data(); A.first_chunk = s0 == 0;
-        launch_map_fold(D, nullptr);
-        for (uint32_t slot = 0; slot < nslots; slot++)
-            for (int ch = 0; ch < 3; ch++) {
-                float& c = c_ref[(size_t)ch * nslots + slot];
-                float& q = q_ref[(size_t)ch * nslots + slot];
-                if (s0 == 0) { c = 0.0f; q = 0.0f; }
-                for (uint32_t s = s0; s < s0 + ns && s < np[slot]; s++) {
-                    const Rad3& l = L[(size_t)(s - s0) * nslots + slot];
-                    const float x = (ch == 0 ? l.x : ch == 1 ? l.y : l.z) / (float)S;
-                    c = c + x; q = q + x * x;
-                }
-            }
+        launch_map_fold(D.sums, s0, ns, nullptr);
+        if (s0 == 0) { std::fill(c_ref.begin(), c_ref.end(), 0.0f); std::fill(q_ref.begin(), q_ref.end(), 0.0f); }
+        for (uint32_t slot = 0; slot < nslots; slot++) restated_fold(c_ref, q_ref, L, nslots, slot, np[slot] > s0 ? std::min(np[slot] - s0, ns) : 0u, S);
     }
     if (max_np > sample_begin)
         for (size_t k = 0; k < accum.size(); k++)
@@ -297,22 +255,86 @@ static void run_case(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t
                 if (!px.out) continue;
                 uint32_t want = 0;
                 if (px.valid) {
-                    const float fn = (float)n, fs = (float)S, r = fs / fn, rr = r * r;
-                    float v3[3], p3[3];
-                    for (int ch = 0; ch < 3; ch++) {
-                        const float c = accum[(size_t)ch * nslots + slot], q = qacc[(size_t)ch * nslots + slot];
-                        float d = fn * q - c * c;
-                        d = d < 0.0f ? 0.0f : d;
-                        v3[ch] = (rr * d) / (fn - 1.0f);
-                        p3[ch] = c * r;
-                    }
-                    const float v = (v3[0] + v3[1]) + v3[2], m = (p3[0] + p3[1]) + p3[2];
-                    const float t = thr * (m + 0.01f), tt = t * t, wv = (fn * v) / tt;
+                    float v, tt;
+                    restated_criterion(accum, qacc, nslots, slot, n, S, thr, 0.01f, v, tt);
+                    const float fs = (float)S, wv = ((float)n * v) / tt;
                     want = wv < fs ? std::max(n, (uint32_t)std::ceil(wv)) : S;
                 }
                 CHECK(out[px.o] == want, "%ux%u S %u threshold %g: plan of slot %u is %u, expected %u", w, h, S, thr, slot, out[px.o], want);
             }
         }
+    }
+}
+
+// crt_render_adaptive's device side over two passes of `step` samples after a warm-up of n0, each pass in chunks of `chunk` samples:
+// counts after the warm-up (k_adaptive_init), k_adaptive_select, k_adaptive_items, k_map_fold -- against a restatement that keeps an explicit `active` array and writes a slot's count after every chunk it took
+static void run_adaptive_case(uint32_t w, uint32_t h, uint32_t S, uint32_t rank, uint32_t world, float thr, uint32_t n0, uint32_t step, uint32_t chunk)
+{
+    const float floor_ = 0.01f;
+    AdaptiveParams D{};
+    AParams& A = D.sums.A;
+    A = frame_of(w, h, S, rank, world);
+    const uint32_t nslots = A.nslots;
+    std::vector<uint32_t> nsamp(nslots, 0xdeadbeefu), list(nslots, 0xffffffffu);
+    std::vector<unsigned int> counter(1, 0u);
+    std::vector<float> accum((size_t)nslots * 3, 0.0f), qacc((size_t)nslots * 3, 0.0f);
+    std::srand(w * 131 + h * 17 + S + rank);
+    auto rnd = [] { return (float)(1 + std::rand() % 1000) / 250.0f; };
+    // the warm-up's sums, of every slot as the uniform fold leaves them: n0 samples that differ, so every variance is positive
+    for (uint32_t s = 0; s < n0; s++)
+        for (size_t k = 0; k < accum.size(); k++) { const float x = rnd() / (float)S; accum[k] = accum[k] + x; qacc[k] = qacc[k] + x * x; }
+    std::vector<float> c_ref = accum, q_ref = qacc;
+    A.accum = accum.data(); D.sums.qacc = qacc.data(); D.sums.nsamp = nsamp.data(); D.list = list.data(); D.count = counter.data();
+    D.threshold = thr; D.mean_floor = floor_; D.n = n0;
+    launch_adaptive_init(D, nullptr);
+    std::vector<uint8_t> active(nslots, 0);
+    std::vector<uint32_t> n_ref(nslots, 0u);
+    for (uint32_t slot = 0; slot < nslots; slot++) {
+        active[slot] = slot_pixel(A, slot).valid; n_ref[slot] = active[slot] ? n0 : 0u;
+        CHECK(nsamp[slot] == n_ref[slot], "init: n_p of slot %u is %u, expected %u", slot, nsamp[slot], n_ref[slot]);
+    }
+    const size_t pixels = (size_t)std::count(active.begin(), active.end(), 1);
+    uint32_t n = n0;
+    for (int pass = 0; pass < 2 && n < S; pass++) {
+        const uint32_t ns_pass = std::min(step, S - n);
+        counter[0] = 0u; D.n = n; D.ns_pass = ns_pass;
+        launch_adaptive_select(D, nullptr);
+        std::set<uint32_t> on;
+        for (uint32_t slot = 0; slot < nslots; slot++) {
+            if (!active[slot]) continue;
+            float v, tt;
+            restated_criterion(c_ref, q_ref, nslots, slot, n, S, thr, floor_, v, tt);
+            if (v <= tt) active[slot] = 0;
+            else on.insert(slot);
+        }
+        // what the two extreme thresholds are there for, of the restatement itself: +inf stops every pixel at the first select, 0 none ever
+        if (thr == INFINITY) CHECK(on.empty(), "pass %d: %zu slots go on at threshold +inf", pass, on.size());
+        if (thr == 0.0f) CHECK(on.size() == pixels, "pass %d: %zu of the shard's %zu pixels go on at threshold 0", pass, on.size(), pixels);
+        const uint32_t n_active = counter[0];
+        CHECK(n_active == on.size(), "pass %d: %u slots go on, expected %zu", pass, n_active, on.size());
+        if (n_active != on.size()) return;
+        std::set<uint32_t> listed(list.begin(), list.begin() + n_active);
+        CHECK(listed == on, "pass %d: the list does not name the active slots once each", pass);
+        if (n_active == 0) break;
+        for (uint32_t s0 = n; s0 < n + ns_pass; s0 += chunk) {
+            const uint32_t ns = std::min(chunk, n + ns_pass - s0), n_items = ns * n_active;
+            std::vector<uint32_t> items(n_items, 0xffffffffu); // exactly the chunk's work items
+            launch_adaptive_items(items.data(), list.data(), n_active, n_items, nslots, nullptr);
+            for (uint32_t pos = 0; pos < n_items; pos++)
+                CHECK(items[pos] == (pos / n_active) * nslots + list[pos % n_active], "pass %d: item %u of the list is %u", pass, pos, items[pos]);
+            std::vector<Rad3> L((size_t)ns * nslots); // dense per chunk
+            for (Rad3& l : L) l = Rad3{rnd(), rnd(), rnd()};
+            A.L = L.data(); A.first_chunk = 0; A.chunk_samples = ns;
+            launch_map_fold(D.sums, s0, ns, nullptr);
+            for (uint32_t slot = 0; slot < nslots; slot++) {
+                if (!active[slot]) continue;
+                restated_fold(c_ref, q_ref, L, nslots, slot, ns, S);
+                n_ref[slot] = s0 + ns;
+            }
+        }
+        n += ns_pass;
+        for (uint32_t slot = 0; slot < nslots; slot++) CHECK(nsamp[slot] == n_ref[slot], "pass %d: n_p of slot %u is %u, expected %u", pass, slot, nsamp[slot], n_ref[slot]);
+        for (size_t k = 0; k < accum.size(); k++) CHECK(same_bits(accum[k], c_ref[k]) && same_bits(qacc[k], q_ref[k]), "pass %d: sums of plane entry %zu differ", pass, k);
     }
 }
 
@@ -328,6 +350,13 @@ int main()
             if (S > 4) { run_case(sh[0], sh[1], S, 0, 1, 4, 3); cases++; } // continuing a frame of four samples
             for (uint32_t rank = 0; rank < 2; rank++, cases++) run_case(sh[0], sh[1], S, rank, 2, 0, 3); // two tiled shards
         }
+    // crt_render_adaptive's kernels, 13 x 9 (ragged tiles in both directions) of cap 12: a warm-up of 4, passes of 5 (the second cut to 3) in
+    // chunks of 2; every pixel stops at the first select (+inf), none does (0), some do
+    for (float thr : {INFINITY, 0.0f, 0.15f}) {
+        run_adaptive_case(13, 9, 12, 0, 1, thr, 4, 5, 2);
+        for (uint32_t rank = 0; rank < 2; rank++) run_adaptive_case(13, 9, 12, rank, 2, thr, 4, 5, 2);
+        cases += 3;
+    }
     std::printf("%d cases, %d failures\n", cases, g_fail);
     return g_fail ? 1 : 0;
 }
