@@ -244,6 +244,10 @@ class Task(C.Structure):
                 ("light_sample_n", C.c_uint32), ("spp", C.c_uint32), ("p_rr", C.c_float)]
 
 
+class ItemOrderInfo(C.Structure):
+    _fields_ = [("lists_built", C.c_uint64), ("lists_reused", C.c_uint64), ("classes", C.c_uint32), ("window", C.c_uint32)]
+
+
 NODE_DTYPE = np.dtype([("lc", "<i4"), ("rc", "<i4"), ("n", "<u4"), ("it", "<i4"), ("aa", "<f4", 3), ("bb", "<f4", 3)])
 TRI_DTYPE = np.dtype([("v1", "<f4", 3), ("v2", "<f4", 3), ("v3", "<f4", 3), ("normal", "<f4", 3), ("area", "<f4"),
                       ("area_of_obj", "<f4"), ("material", "<i4")])
@@ -259,7 +263,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
-           "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device"]
+           "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
+           "crt_item_order"]
 
 _lib = None
 
@@ -374,6 +379,8 @@ def lib():
                                      C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
     L.crt_render_planned_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
+    if hasattr(L, "crt_item_order"):  # (a CRT_LIB_PATH library of this ABI version from before the entry point was appended has none)
+        L.crt_item_order.argtypes = [C.c_void_p, C.POINTER(ItemOrderInfo)]
     _lib = L
     return L
 

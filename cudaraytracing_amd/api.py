@@ -404,6 +404,13 @@ class Render:
         capi.check(capi.lib().crt_last_launch_ms(self._handle("last_launch_ms"), C.byref(ms), C.byref(n)), "crt_last_launch_ms")
         return float(ms.value), int(n.value)
 
+    def item_order(self):
+        """{"lists_built", "lists_reused", "classes", "window"} of the handle (crt_item_order): how often a launch of the render kernel
+        built the order of its last work items and how often it found it built; classes and window of the last launch."""
+        info = capi.ItemOrderInfo()
+        capi.check(capi.lib().crt_item_order(self._handle("item_order"), C.byref(info)), "crt_item_order")
+        return {"lists_built": int(info.lists_built), "lists_reused": int(info.lists_reused), "classes": int(info.classes), "window": int(info.window)}
+
     def radiance_storage(self):
         """(bytes, ring samples) of the per-path radiance storage of the last render on this handle (crt_radiance_storage): one value per
         path of a chunk, or -- FLAG_BOUNDED_RADIANCE -- a ring of that many samples."""

@@ -3,6 +3,7 @@
 #ifndef CRT_MEGA3_H
 #define CRT_MEGA3_H
 #include "crt_path.h"
+#include "crt_item_order.h"
 
 namespace crtk {
 
@@ -193,7 +194,7 @@ struct Mega3Variant {
 // of refs (impl: dec && r16 only).  nullptr: there is none.
 const Mega3Variant* mega3_variant(int mode, bool stats, bool all, bool query, bool r16, bool ring = false, bool dec = false, bool impl = false);
 bool bbprof_launch(Mega3Kernel kern, MParams3 M3, uint32_t blocks, hipStream_t st); // tools/bbprof hook (false: launch as usual)
-void launch_order_items(bool ring, uint32_t blocks, hipStream_t st, const LParams& P, uint32_t* list, unsigned int* cnt);
+void launch_order_items(bool ring, uint32_t blocks, hipStream_t st, const LParams& P, const OrderClasses& C, uint32_t* list, unsigned int* cnt);
 
 } // namespace crtk
 #endif

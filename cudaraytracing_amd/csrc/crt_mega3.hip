@@ -1,7 +1,7 @@
 // cudaraytracing_amd/csrc/crt_mega3.hip -- k_mega3, the render kernel: one persistent launch per chunk of samples, path logic and traversal in the
 // same waves, every wave the owner of a pool of rays in LDS (layouts, limits and tuning constants: crt_mega3.h; shared path logic: crt_path.h).
 // This file holds the kernel itself -- the scheduler, the loop of alternating traversal steps, the dispatch to the named steps, the
-// counters -- k_order_items, the table of the kernel's instantiations and the tools/bbprof hook.  The steps live in headers that only this
+// counters -- the launch of k_order_items (crt_item_order.h), the table of the kernel's instantiations and the tools/bbprof hook.  The steps live in headers that only this
 // file includes: crt_mega3_math.h (box and triangle arithmetic), crt_mega3_wave.h (scalar helpers, the ring append, the -DCRT_STAMPS clock),
 // crt_mega3_logic.h (start_ray, LA / LB / LC), crt_mega3_coupled.h and crt_mega3_decoupled.h (what the two forms of the traversal steps are made of).
 // Replaces view_render_kernel / cast_ray_v2 / DeviceBVH::intersect (include/Render.cuh:199-354, include/DeviceBVH.cuh:87-170).
@@ -11,6 +11,7 @@
 #include "crt_mega3_logic.h"
 #include "crt_mega3_coupled.h"
 #include "crt_mega3_decoupled.h"
+#include "crt_item_order.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -646,71 +647,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CRT_WAVES, C
 }
 
 
-// Orders the LAST order_window work items of every cursor shard (what the waves are handed when a launch ends): first the paths whose
-// roulette draw lets them continue past their first vertex, then the ones it stops there (and the padding slots of ragged tiles).  The draws are addressed (crt_detmath.h), so this is known before
-// anything is traced; the order of the work items cannot change a result (every path writes its own L[item]).  Why: every launch ends
-// with each wave running its pool dry, and the time that takes is the longest path started last -- with one-vertex paths at the
-// end of every shard the fixed cost of a launch drops from 2.5 ms to about 1 ms (tools/share_probe.py: a rank's share of C2 at 1 / 2 / 4 /
-// 8 ranks 107.3 / 54.9 / 28.4 / 15.9 ms without, 106.8 / 54.1 / 27.5 / 14.6 ms with, this pass included).  One wave orders a span of
-// 1 024 items of one shard with two atomics (a cache line per counter).
-template <bool RING>
-__global__ __launch_bounds__(64) void k_order_items(const LParams P, uint32_t* list, unsigned int* cnt)
-{
-    const uint32_t spans = (P.order_window + 1023u) / 1024u;
-    const uint32_t sh = blockIdx.x / spans, sp = blockIdx.x - sh * spans;
-    const uint32_t slo = sh * P.items_per_shard;
-    if (slo >= P.n_items) return;
-    const uint32_t hi = min(slo + P.items_per_shard, P.n_items);
-    const uint32_t lo = hi - min(P.order_window, hi - slo); // the window: the last order_window items of the shard
-    const uint32_t b = lo + sp * 1024u;
-    if (b >= hi) return;
-    uint32_t* out = list + (size_t)sh * P.order_window; // out[k] = the item handed out in place of item lo + k
-    const uint32_t lane = threadIdx.x;
-    uint32_t goes_on = 0, exists = 0; // bit j: item b + 64 j + lane
-#pragma unroll 1
-    for (uint32_t j = 0; j < 16; j++) {
-        const uint32_t i = b + j * 64u + lane;
-        if (i < hi) {
-            bool valid; uint32_t pi, pj, pixel_index, k;
-            decode_item<RING>(P, i, pixel_index, k, valid, pi, pj);
-            exists |= 1u << j;
-            // the roulette of the first vertex: must agree with roulette (crt_path.h) at depth 0, which logic_B calls (Render.cuh:223-227)
-            if (valid && !(rng_uniform(rng_draw(P.seed, pixel_index, k, 0, RNG_BOUNCE, 0).x) > P.p_rr)) goes_on |= 1u << j;
-        }
-    }
-    uint32_t n_on = 0, n_all = 0;
-#pragma unroll 1
-    for (uint32_t j = 0; j < 16; j++) {
-        n_on += (uint32_t)__popcll(__ballot((goes_on >> j) & 1u));
-        n_all += (uint32_t)__popcll(__ballot((exists >> j) & 1u));
-    }
-    unsigned int base_on = 0, base_off = 0;
-    if (lane == 0) { // (one 128 B line per counter: the atomics of a shard serialise on their line, those of different shards must not)
-        base_on = atomicAdd(cnt + (sh * 2u) * 32u, n_on);
-        base_off = atomicAdd(cnt + (sh * 2u + 1u) * 32u, n_all - n_on);
-    }
-    base_on = (unsigned int)__builtin_amdgcn_readfirstlane((int)base_on);
-    base_off = (unsigned int)__builtin_amdgcn_readfirstlane((int)base_off);
-    const uint32_t wn = hi - lo;
-#pragma unroll 1
-    for (uint32_t j = 0; j < 16; j++) {
-        const bool on_j = (goes_on >> j) & 1u, ex_j = (exists >> j) & 1u;
-        const unsigned long long m_on = __ballot(on_j), m_off = __ballot(ex_j && !on_j);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        const uint32_t i = b + j * 64u + lane;
-        if (on_j) __hip_atomic_store(&out[base_on + (uint32_t)__popcll(m_on & below)], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else if (ex_j) __hip_atomic_store(&out[wn - 1u - (base_off + (uint32_t)__popcll(m_off & below))], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        base_on += (unsigned int)__popcll(m_on);
-        base_off += (unsigned int)__popcll(m_off);
-    }
-}
-
-
 // ---- exported to crt_render.hip ----
-void launch_order_items(bool ring, uint32_t blocks, hipStream_t st, const LParams& P, uint32_t* list, unsigned int* cnt)
+// k_order_items (crt_item_order.h): the count pass and the place pass over `blocks` spans (cnt: zero on entry)
+void launch_order_items(bool ring, uint32_t blocks, hipStream_t st, const LParams& P, const OrderClasses& C, uint32_t* list, unsigned int* cnt)
 {
-    if (ring) hipLaunchKernelGGL(k_order_items<true>, dim3(blocks), dim3(64), 0, st, P, list, cnt);
-    else hipLaunchKernelGGL(k_order_items<false>, dim3(blocks), dim3(64), 0, st, P, list, cnt);
+    if (ring) {
+        hipLaunchKernelGGL((k_order_items<true, false>), dim3(blocks), dim3(64), 0, st, P, C, list, cnt);
+        hipLaunchKernelGGL((k_order_items<true, true>), dim3(blocks), dim3(64), 0, st, P, C, list, cnt);
+    } else {
+        hipLaunchKernelGGL((k_order_items<false, false>), dim3(blocks), dim3(64), 0, st, P, C, list, cnt);
+        hipLaunchKernelGGL((k_order_items<false, true>), dim3(blocks), dim3(64), 0, st, P, C, list, cnt);
+    }
 }
 
 // ---- the instantiations ----

@@ -349,6 +349,35 @@ RingPlan plan_ring(const crt_scene* sc, const crt_params* prm, const Shard& sh, 
     return ring;
 }
 
+// ---- the order of a launch's last work items (k_order_items): the window and the classes, chosen by measurement on C2
+// (docs/experiments.md, "The order of a launch's last paths") ----
+constexpr uint32_t kOrderWindow = 1u << 19; // work items at the end of every cursor shard
+// CRT_ORDER_CLASSES: the lower bounds of the classes above the first, ascending roulette lengths from 2 on, at most seven ("2": the paths
+// that stop at their first vertex last and nothing more).  Anything else: the default.
+OrderClasses order_classes_from_env()
+{
+    OrderClasses C;
+    std::memset(&C, 0, sizeof(C));
+    const uint32_t dflt[] = {1, 2, 3, 5, 9};
+    C.n = (uint32_t)(sizeof(dflt) / sizeof(dflt[0]));
+    for (uint32_t c = 0; c < C.n; c++) C.lo[c] = dflt[c];
+    const char* e = std::getenv("CRT_ORDER_CLASSES");
+    if (!e || !*e) return C;
+    OrderClasses E;
+    std::memset(&E, 0, sizeof(E));
+    E.n = 1; E.lo[0] = 1;
+    for (const char* p = e; *p;) {
+        char* end = nullptr;
+        const long v = std::strtol(p, &end, 10);
+        if (end == p || E.n == ORDER_CLASSES_MAX || v <= (long)E.lo[E.n - 1] || v > CRT_BOUNCE_STACK_SIZE) return C;
+        E.lo[E.n++] = (uint32_t)v;
+        p = end;
+        if (*p == ',') p++;
+        else if (*p) return C;
+    }
+    return E.n >= 2 ? E : C;
+}
+
 // ---------- fused persistent megakernel: one launch per chunk ----------
 void render_mega(Frame& f)
 {
@@ -404,12 +433,14 @@ void render_mega(Frame& f)
             HIP_CHECK(hipMemcpyAsync(sc->ring_state.p, state.data(), state.size() * sizeof(unsigned int), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemsetAsync(sc->ring_done.p, 0, (size_t)ring.shards * ring.samples * sizeof(unsigned int), st));
         }
-        // the paths that stop at their first vertex are handed out last (k_order_items): 1 % of a whole C2 frame on one GPU,
-        // 8 % of a rank's share on eight.  CRT_ITEM_ORDER=0 switches it off.
+        // the end of every cursor shard is handed out longest roulette length first (k_order_items, crt_item_order.h; the measurements:
+        // docs/experiments.md, "The order of a launch's last paths").  CRT_ITEM_ORDER=0 switches it off.
         P.item_list = nullptr;
+        sc->order_classes = 0; sc->order_window = 0;
         if (f.src) {
             // the WHOLE cursor range goes through the source's list (order_window = the shard, so list index = cursor position)
             P.order_window = P.items_per_shard;
+            sc->order_key.valid = 0; // (the source's list takes the buffer)
             sc->item_list.ensure(P.n_items);
             f.src->fill(sc->item_list.p, s0, ns, P.n_items, st);
             HIP_CHECK(hipGetLastError());
@@ -418,23 +449,43 @@ void render_mega(Frame& f)
             const char* eo = std::getenv("CRT_ITEM_ORDER");
             const bool order = !(eo && eo[0] == '0');
             if (order && P.n_items > 0) {
-                // the window: the last 2^19 work items of every shard (measured on C2, wall time of a rank's share at 1 / 2 / 4 / 8 ranks: no
-                // order 107.3 / 54.9 / 28.4 / 15.9 ms; 2^17: 107.4 / 54.5 / 28.3 / 15.2; 2^19: 106.8 / 54.2 / 27.7 / 14.6; whole shards:
-                // 107.2 / 54.1 / 27.5 / 14.6 -- the pass itself costs 0.9 ms for the 245.8 M items of a whole frame)
-                P.order_window = std::min<uint32_t>(P.items_per_shard, env_u32("CRT_ORDER_WINDOW", 1u << 19));
-                if (ring.samples) { // the window may span half the ring: its items stand for the launch's last sample at the gate
+                // the window: the last CRT_ORDER_WINDOW work items of every shard
+                P.order_window = std::min<uint32_t>(P.items_per_shard, env_u32("CRT_ORDER_WINDOW", kOrderWindow));
+                if (ring.samples) { // the window may span half the ring: its items stand for the launch's last sample at the gate, in whatever order
                     P.order_window = std::min<uint32_t>(P.order_window, (ring.samples / 2u) * ring.spsh);
                     P.tail_first = P.items_per_shard - P.order_window;
                 }
                 P.items_per_shard_div = make_fastdiv(std::max(1u, P.items_per_shard));
                 const uint32_t n_sh = ring.samples ? ring.shards : (uint32_t)ITEM_SHARDS;
-                sc->item_list.ensure((size_t)n_sh * P.order_window);
-                sc->order_cnt.ensure((size_t)n_sh * 2 * 32);
-                HIP_CHECK(hipMemsetAsync(sc->order_cnt.p, 0, (size_t)n_sh * 2 * 32 * sizeof(unsigned int), st));
-                const uint32_t spans = (P.order_window + 1023u) / 1024u;
-                launch_order_items(ring.samples != 0, n_sh * spans, st, P, sc->item_list.p, sc->order_cnt.p);
-                HIP_CHECK(hipGetLastError());
+                const OrderClasses C = order_classes_from_env();
+                // The list is a function of the key alone (crt_scene.h: ItemOrderKey), not of the camera or the scene: a launch whose key is the one the
+                // handle's list was built for takes it as it is -- no memset, no order pass.  One list per handle: a frame of several chunks
+                // builds one per chunk.
+                ItemOrderKey key;
+                std::memset(&key, 0, sizeof(key));
+                key.valid = 1; key.seed = P.seed; key.stream = (uint64_t)(uintptr_t)st; key.sample_begin = P.sample_begin; key.n_items = P.n_items;
+                key.items_per_shard = P.items_per_shard; key.order_window = P.order_window; key.shards = n_sh; key.ring = ring.samples ? 1u : 0u;
+                key.spsh = ring.samples ? ring.spsh : 0u; key.nslots = P.nslots; key.rank = P.rank; key.world = P.world; key.tiles_x = P.tiles_x;
+                key.n_tiles = P.n_tiles; key.width = P.width; key.height = P.height;
+                std::memcpy(&key.p_rr_bits, &P.p_rr, sizeof(float));
+                key.n_classes = C.n;
+                for (uint32_t c = 0; c < C.n; c++) key.class_lo[c] = C.lo[c];
+                const size_t list_n = (size_t)n_sh * P.order_window, cnt_n = (size_t)n_sh * C.n * 32;
+                if (sc->item_list.n < list_n || sc->order_cnt.n < cnt_n) sc->order_key.valid = 0; // (a new allocation holds no list)
+                sc->item_list.ensure(list_n);
+                sc->order_cnt.ensure(cnt_n);
+                if (std::memcmp(&key, &sc->order_key, sizeof(key)) == 0) sc->order_reused++;
+                else {
+                    sc->order_key.valid = 0;
+                    HIP_CHECK(hipMemsetAsync(sc->order_cnt.p, 0, cnt_n * sizeof(unsigned int), st));
+                    const uint32_t spans = (P.order_window + 1023u) / 1024u;
+                    launch_order_items(ring.samples != 0, n_sh * spans, st, P, C, sc->item_list.p, sc->order_cnt.p);
+                    HIP_CHECK(hipGetLastError());
+                    sc->order_key = key;
+                    sc->order_built++;
+                }
                 P.item_list = sc->item_list.p;
+                sc->order_classes = C.n; sc->order_window = P.order_window;
             }
         }
         P.items_per_shard_div = make_fastdiv(std::max(1u, P.items_per_shard));
@@ -839,6 +890,14 @@ int crt_radiance_storage(crt_scene* sc, uint64_t* bytes, uint32_t* ring_samples)
     if (!sc || !bytes) return fail(CRT_ERR_INVALID_ARG, "crt_radiance_storage: null argument");
     *bytes = sc->last_radiance_bytes;
     if (ring_samples) *ring_samples = sc->last_ring_samples;
+    return CRT_OK;
+}
+
+int crt_item_order(crt_scene* sc, crt_item_order_info* info)
+{
+    if (!sc || !info) return fail(CRT_ERR_INVALID_ARG, "crt_item_order: null argument");
+    info->lists_built = sc->order_built; info->lists_reused = sc->order_reused;
+    info->classes = sc->order_classes; info->window = sc->order_window;
     return CRT_OK;
 }
 

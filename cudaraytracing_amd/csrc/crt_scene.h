@@ -26,6 +26,17 @@ struct FrameMark {
     }
 };
 
+// Everything the list k_order_items writes depends on: the draws (seed, first sample, p_rr), the geometry of the work items and the cursor
+// shards (what decode_item reads), the window, the classes -- and the stream the list was built on, which orders the build before its use.
+// Camera, scene and traversal are not in it: a caller that renders a view again with a fixed seed finds the list built.
+// Plain words, zeroed before they are filled, so that two keys compare with memcmp.
+struct ItemOrderKey {
+    uint64_t seed, stream;
+    uint32_t valid, sample_begin, n_items, items_per_shard, order_window, shards, ring, spsh, nslots, rank, world, tiles_x, n_tiles, width, height, p_rr_bits;
+    uint32_t n_classes, class_lo[8];
+    uint32_t pad_;
+};
+
 // What a launch without the commit ring leaves per work item, in one allocation that grows to the larger use: a render's radiance (12
 // bytes, crtk::Rad3) or the answers of k_mega3's query form (16 bytes: crt_intersect, the AOV pass).  Each form has its own accessor and
 // its own element type, so an entry of one is never addressed with the stride of the other.
@@ -59,7 +70,10 @@ struct crt_scene {
     std::vector<unsigned int> ring_state_host;
     uint64_t last_radiance_bytes = 0;           // per-work-item (or ring) radiance storage the last render used
     uint32_t last_ring_samples = 0;             // its ring size in samples (0: one radiance per work item)
-    crtk::DevBuf<unsigned int> order_cnt;           // [ITEM_SHARDS][2] counters, one 128 B line each
+    crtk::DevBuf<unsigned int> order_cnt;           // k_order_items: [cursor shards][classes] counters, one 128 B line each
+    ItemOrderKey order_key{};                        // what item_list holds (valid = false: nothing a launch may reuse)
+    uint64_t order_built = 0, order_reused = 0;     // launches that built item_list with k_order_items / found it built (crt_item_order)
+    uint32_t order_classes = 0, order_window = 0;   // of the handle's last launch of the render kernel (0: handed out in cursor order, or by a sparse frame's list)
     crtk::DevBuf<unsigned int> slot_next[2];        // [SLOT_SHARDS][SLOT_STRIDE], one per pool half
     crtk::DevBuf<int2> spill[2];                    // traversal stack overflow, one per pool half
     hipStream_t aux_stream = nullptr;         // second pool half runs here so that k_logic overlaps k_trace

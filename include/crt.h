@@ -904,6 +904,18 @@ int crt_render_planned(crt_scene* scene, const crt_camera* cam, const crt_params
 int crt_render_planned_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
                               void* d_rgb, void* d_mean, void* d_samples, void* d_variance, void* hip_stream, crt_map_info* info);
 
+/* The order in which the render kernel hands out the last work items of a launch (the paths the roulette draws will let run longest
+ * first: it shortens the end of a launch, where every wave runs its pool dry, and cannot change a result).  The order is a list on the
+ * handle that depends on the seed, the sample range, the size and shard of the frame, p_rr and the stream -- not on the camera or the
+ * scene -- and is built again only when one of these changes between two launches.  For the handle: the launches of the render kernel
+ * that built the list and that found it built, and of the last launch the number of length classes and the work items per cursor shard
+ * that were ordered (both 0: cursor order -- CRT_ITEM_ORDER=0, the fallback pipeline -- or the list of a sparse frame). */
+typedef struct {
+    uint64_t lists_built, lists_reused;
+    uint32_t classes, window;
+} crt_item_order_info;
+int crt_item_order(crt_scene* scene, crt_item_order_info* info);
+
 #ifdef __cplusplus
 }
 #endif
