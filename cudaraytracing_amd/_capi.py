@@ -128,6 +128,15 @@ class AovInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AovSpecularParams(C.Structure):
+    _fields_ = [("max_bounces", C.c_uint32)]
+
+
+class AovSpecularBuffers(C.Structure):
+    _fields_ = [("guide_albedo", C.c_void_p), ("last_normal", C.c_void_p), ("path_depth", C.c_void_p), ("bounces", C.c_void_p),
+                ("last_tri", C.c_void_p)]
+
+
 class DenoiseParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float),
                 ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
@@ -235,6 +244,9 @@ class PlanInfo(C.Structure):
 # the buffers of crt_aov_buffers: name -> (values per pixel, numpy type)
 AOV_BUFFERS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "coverage": (1, np.float32),
                "tri": (1, np.int32), "material": (1, np.int32)}
+# the buffers of crt_aov_specular_buffers
+AOV_SPECULAR_BUFFERS = {"guide_albedo": (3, np.float32), "last_normal": (3, np.float32), "path_depth": (1, np.float32),
+                        "bounces": (1, np.float32), "last_tri": (1, np.int32)}
 
 
 class Task(C.Structure):
@@ -264,7 +276,7 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
            "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
-           "crt_item_order"]
+           "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device"]
 
 _lib = None
 
@@ -312,6 +324,11 @@ def lib():
     L.crt_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovInfo)]
     L.crt_render_aov_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.c_void_p,
                                         C.POINTER(AovInfo)]
+    L.crt_aov_specular_defaults.argtypes = [C.POINTER(AovSpecularParams)]
+    L.crt_render_aov_specular.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovSpecularParams),
+                                          C.POINTER(AovSpecularBuffers), C.POINTER(AovInfo)]
+    L.crt_render_aov_specular_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovSpecularParams),
+                                                 C.POINTER(AovSpecularBuffers), C.c_void_p, C.POINTER(AovInfo)]
     L.crt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
     L.crt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.crt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.POINTER(DenoiseInfo)]

@@ -175,6 +175,7 @@ class Render:
         self.mean_buffer = None
         self.stats = None
         self.aov_info = None
+        self.aov_specular_info = None
         self.aov_buffers = None
         self.denoise_info = None
         self.variance_buffer = None
@@ -485,15 +486,60 @@ class Render:
             self.aov_info = info.as_dict()
         return self.aov_info if want_info else None
 
+    def run_view_aov_specular(self, eye_pos, inv_view_mat, fovY, max_bounces=None, want=tuple(capi.AOV_SPECULAR_BUFFERS), width=None, height=None):
+        """AOVs that follow perfect-mirror bounces from the first hit (crt_render_aov_specular, contract: include/crt.h): returns
+        {name: array} for the names in `want` (guide_albedo, last_normal: (H, W, 3) float32; path_depth, bounces: (H, W) float32;
+        last_tri: (H, W) int32).  max_bounces None: crt_aov_specular_defaults'.  self.aov_specular_info gets rays (camera and
+        reflected), chunks, total_ms."""
+        h_ = self._handle("run_view_aov_specular")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        w, h = prm.width, prm.height
+        out, bufs = {}, capi.AovSpecularBuffers()
+        for name in want:
+            ch, dt = capi.AOV_SPECULAR_BUFFERS[name]
+            out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
+            setattr(bufs, name, out[name].ctypes.data)
+        sp, info = _aov_specular_params(max_bounces), capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov_specular(h_, C.byref(cam), C.byref(prm), C.byref(sp), C.byref(bufs), C.byref(info)), "crt_render_aov_specular")
+        self.aov_specular_info = info.as_dict()
+        return out
+
+    def run_view_aov_specular_device(self, eye_pos, inv_view_mat, fovY, ptrs, max_bounces=None, stream=None, rank=0, world=1, tiled=False,
+                                     want_info=True, width=None, height=None):
+        """The same with outputs in device memory: ptrs = {name: raw device pointer}, layout as run_view_aov_device.  The call
+        synchronizes the stream once per bounce and chunk (and once more with want_info, which sets self.aov_specular_info)."""
+        h_ = self._handle("run_view_aov_specular_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
+        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        bufs = capi.AovSpecularBuffers()
+        for name, p in ptrs.items():
+            if name not in capi.AOV_SPECULAR_BUFFERS:
+                raise ValueError("unknown specular AOV buffer %r" % name)
+            setattr(bufs, name, int(p) if p else None)
+        sp, info = _aov_specular_params(max_bounces), capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov_specular_device(h_, C.byref(cam), C.byref(prm), C.byref(sp), C.byref(bufs),
+                                                             C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
+                   "crt_render_aov_specular_device")
+        if want_info:
+            self.aov_specular_info = info.as_dict()
+        return self.aov_specular_info if want_info else None
+
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
-                          sigma_depth=None, width=None, height=None, variance_guided=False):
+                          sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
-        variance_guided: render with want_variance and filter with crt_denoise_var (its own defaults) and self.variance_buffer."""
+        variance_guided: render with want_variance and filter with crt_denoise_var (its own defaults) and self.variance_buffer.
+        specular_guides: the albedo guide is guide_albedo of run_view_aov_specular (max_bounces) -- what a mirror reflects instead of the
+        mirror; normal and depth stay first-hit."""
         self._handle("run_view_denoised")
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=variance_guided)
         self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        if specular_guides:
+            self.aov_buffers["albedo"] = self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=max_bounces, want=("guide_albedo",),
+                                                                    width=width, height=height)["guide_albedo"]
         if variance_guided:
             rgb, mean, self.denoise_info = denoise_var(self.mean_buffer, self.variance_buffer, iterations=iterations, sigma_color=sigma_color,
                                                        sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
@@ -714,6 +760,12 @@ class MultiRender(Render):
     def run_view_aov_device(self, *a, **k):
         raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_device)")
 
+    def run_view_aov_specular(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_specular)")
+
+    def run_view_aov_specular_device(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_specular_device)")
+
     def run_view_denoised(self, *a, **k):
         raise NotImplementedError("the denoiser is a single-device interface (crt_denoise): gather the frame first")
 
@@ -768,6 +820,21 @@ def _adaptive_params(min_samples=None, step_samples=None, threshold=None, mean_f
     for name, v in (("min_samples", min_samples), ("step_samples", step_samples), ("threshold", threshold), ("mean_floor", mean_floor)):
         if v is not None:
             setattr(p, name, int(v) if name.endswith("samples") else float(v))
+    return p
+
+
+def aov_specular_defaults():
+    """crt_aov_specular_defaults as a dict: max_bounces."""
+    p = capi.AovSpecularParams()
+    capi.check(capi.lib().crt_aov_specular_defaults(C.byref(p)), "crt_aov_specular_defaults")
+    return {"max_bounces": int(p.max_bounces)}
+
+
+def _aov_specular_params(max_bounces=None):
+    p = capi.AovSpecularParams()
+    capi.check(capi.lib().crt_aov_specular_defaults(C.byref(p)), "crt_aov_specular_defaults")
+    if max_bounces is not None:
+        p.max_bounces = int(max_bounces)
     return p
 
 

@@ -6,8 +6,8 @@
 //
 //   crt_cli <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
-//           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]
-//           [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
+//           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]
+//           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]]
@@ -34,6 +34,10 @@
 // albedo, depth) override crt_denoise_defaults.
 // --aov PREFIX also writes the first-hit AOVs of the frame (crt_render_aov, one device): PREFIX_albedo.png (8-bit, 255 x clamp(a, 0, 1)
 // truncated, no gamma), PREFIX_normal.png (255 x clamp((n + 1) / 2, 0, 1)) and PREFIX_depth.pfm (floats).
+// --aov-specular PREFIX[,MAX_BOUNCES] writes the AOVs that follow mirror bounces (crt_render_aov_specular, one device; MAX_BOUNCES 1 .. 8,
+// default: crt_aov_specular_defaults') as PFM files: PREFIX_guide_albedo.pfm and PREFIX_last_normal.pfm (3 channels), PREFIX_path_depth.pfm
+// and PREFIX_bounces.pfm (1 channel).  --denoise-specular makes --denoise take guide_albedo of that pass (MAX_BOUNCES of --aov-specular if
+// given) as its albedo guide instead of the first-hit albedo; normal and depth stay first-hit.
 // --gpus N renders on devices 0..N-1 of this node in one process (crt_multi: interleaved pixel tiles, one RCCL all-gather);
 // --devices names the device of every rank explicitly (a repeated index puts two ranks on one GPU: --gather copy only).
 #include "crt_host.hpp"
@@ -51,7 +55,8 @@ int main(int argc, char** argv)
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
-                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX]\n"
+                             "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
+                             "       [--denoise-specular]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
@@ -61,13 +66,14 @@ int main(int argc, char** argv)
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, denoise, variance, adaptive_samples;
+        std::string out = "out.png", base_dir = ".", aov, aov_specular, denoise, variance, adaptive_samples;
         crt_adaptive_params ad;
         crt_adaptive_defaults(&ad);
         bool adaptive = false, ad_option = false, planned = false;
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
-        bool dn_iterations = false, dn_sigma = false, denoise_var = false;
+        bool dn_iterations = false, dn_sigma = false, denoise_var = false, denoise_specular = false;
+        uint32_t specular_bounces = 0; // 0: crt_aov_specular_defaults'
         int temporal = 0;
         bool temporal_option = false, temporal_denoise = false, temporal_clamp = false, temporal_moments = false;
         crt_variance_estimate_params tvar; // --temporal-variance moments: the estimate's defaults with of_mean 1 and MIN_HISTORY
@@ -117,6 +123,19 @@ int main(int argc, char** argv)
             }
             else if (a == "--base-dir") { need(i, 1); base_dir = argv[++i]; }
             else if (a == "--aov") { need(i, 1); aov = argv[++i]; }
+            else if (a == "--aov-specular") {
+                need(i, 1);
+                aov_specular = argv[++i];
+                const size_t comma = aov_specular.rfind(',');
+                if (comma != std::string::npos) {
+                    const int b = std::atoi(aov_specular.c_str() + comma + 1);
+                    if (b < 1 || b > 8) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular PREFIX[,MAX_BOUNCES] needs MAX_BOUNCES in 1 .. 8");
+                    specular_bounces = (uint32_t)b;
+                    aov_specular.resize(comma);
+                }
+                if (aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular needs a PREFIX");
+            }
+            else if (a == "--denoise-specular") denoise_specular = true;
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
             else if (a == "--denoise-variance") denoise_var = true;
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
@@ -205,6 +224,8 @@ int main(int argc, char** argv)
                     scene.get_light_objs().size());
         const bool multi = !devices.empty();
         if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
+        if (multi && !aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular renders on one device (not with --gpus / --devices)");
+        if (denoise_specular && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-specular needs --denoise PATH");
         if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
         if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
         if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
@@ -316,6 +337,21 @@ int main(int argc, char** argv)
             if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_depth_buffer());
             if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the AOV files failed: ") + crt_last_error());
             std::printf("%s\n%s\n%s\n", pa.c_str(), pn.c_str(), pd.c_str());
+        }
+        if (!aov_specular.empty() || denoise_specular) { // (after --aov's files: as the guide it replaces the first-hit albedo)
+            render.run_aov_specular(task.eye_pos, inv_view, fov_y, specular_bounces, denoise_specular);
+            const crt_aov_info& ai = render.last_aov_specular_info();
+            std::printf("aov-specular: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
+        }
+        if (!aov_specular.empty()) {
+            const std::string pg = aov_specular + "_guide_albedo.pfm", pn = aov_specular + "_last_normal.pfm", pd = aov_specular + "_path_depth.pfm",
+                              pb = aov_specular + "_bounces.pfm";
+            int rc = crt_write_pfm(pg.c_str(), task.width, task.height, 3, render.get_guide_albedo_buffer());
+            if (rc == CRT_OK) rc = crt_write_pfm(pn.c_str(), task.width, task.height, 3, render.get_last_normal_buffer());
+            if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_path_depth_buffer());
+            if (rc == CRT_OK) rc = crt_write_pfm(pb.c_str(), task.width, task.height, 1, render.get_bounces_buffer());
+            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the specular AOV files failed: ") + crt_last_error());
+            std::printf("%s\n%s\n%s\n%s\n", pg.c_str(), pn.c_str(), pd.c_str(), pb.c_str());
         }
         if (!denoise.empty()) {
             if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);

@@ -743,6 +743,32 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
 }
 
+void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces, bool as_albedo_guide)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov_specular: the AOV pass is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov_specular after free()");
+    crt_camera cam;
+    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
+    cam.fov_y = fovY;
+    crt_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_;
+    crt_aov_specular_params sp;
+    crt_aov_specular_defaults(&sp);
+    if (max_bounces) sp.max_bounces = max_bounces;
+    const size_t n = scene_->get_pixels();
+    guide_albedo_buffer_.assign(3 * n, 0.0f); last_normal_buffer_.assign(3 * n, 0.0f); path_depth_buffer_.assign(n, 0.0f); bounces_buffer_.assign(n, 0.0f);
+    crt_aov_specular_buffers out{};
+    out.guide_albedo = guide_albedo_buffer_.data(); out.last_normal = last_normal_buffer_.data(); out.path_depth = path_depth_buffer_.data();
+    out.bounces = bounces_buffer_.data();
+    const int rc = crt_render_aov_specular(device_scene_, &cam, &p, &sp, &out, &aov_specular_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov_specular failed: ") + crt_last_error());
+    if (as_albedo_guide) albedo_buffer_ = guide_albedo_buffer_;
+}
+
 void Render::run_denoise(const crt_denoise_params& prm)
 {
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise: the denoiser is a single-device interface");

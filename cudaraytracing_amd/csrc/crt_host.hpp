@@ -231,6 +231,14 @@ public:
     const float* get_normal_buffer() const { return normal_buffer_.data(); } // W x H x 3
     const float* get_depth_buffer() const { return depth_buffer_.data(); }   // W x H
     const crt_aov_info& last_aov_info() const { return aov_info_; }
+    // the AOVs that follow mirror bounces (crt_render_aov_specular; max_bounces 0: crt_aov_specular_defaults'); one device only.
+    // as_albedo_guide: guide_albedo also replaces the albedo of the last run_aov as the guide of run_denoise / run_denoise_var
+    void run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces = 0, bool as_albedo_guide = false);
+    const float* get_guide_albedo_buffer() const { return guide_albedo_buffer_.data(); } // W x H x 3
+    const float* get_last_normal_buffer() const { return last_normal_buffer_.data(); }   // W x H x 3
+    const float* get_path_depth_buffer() const { return path_depth_buffer_.data(); }     // W x H
+    const float* get_bounces_buffer() const { return bounces_buffer_.data(); }           // W x H
+    const crt_aov_info& last_aov_specular_info() const { return aov_specular_info_; }
     // the frame of the last run_view filtered by crt_denoise with the albedo, normal and depth of the last run_aov as guides (call both
     // first, with the same camera); prm: crt_denoise_defaults with overrides, its width and height are set here; one device only
     void run_denoise(const crt_denoise_params& prm);
@@ -324,6 +332,8 @@ private:
     crt_denoise_info denoise_info_{};
     crt_stats stats_{};
     crt_aov_info aov_info_{};
+    std::vector<float> guide_albedo_buffer_, last_normal_buffer_, path_depth_buffer_, bounces_buffer_; // run_aov_specular
+    crt_aov_info aov_specular_info_{};
 };
 
 } // namespace crt

@@ -157,6 +157,40 @@ struct AovParams : SlotMap {
 void launch_aov_rays(const AovParams& A, hipStream_t st);
 void launch_aov_resolve(const AovParams& A, hipStream_t st);
 
+// AOV pass that follows mirror bounces (crt_aov.hip; host side: crt_render_aov_specular in crt_render.hip).  Items as above.  A stage
+// reads the answers of the n_in rays traced last (stage 0: the camera rays, ray i = item i; later: the reflected rays, ray i of item
+// in_item[i]), advances the chain state of their items and compacts the rays that go on into the other half of the query pool.
+struct AovSpecParams : SlotMap {
+    uint32_t spp, n_samples;
+    uint32_t first_chunk, last_chunk;
+    uint32_t max_bounces;
+    // k_aov_bounce
+    uint32_t n_in, stage0;
+    const float4* in_ro;     // the rays traced (xyz)
+    const float4* in_rd;
+    const uint32_t* in_item;
+    const float* res;        // their answers, as AovParams::res
+    uint32_t res_stride;
+    float4* out_ro;          // the rays that go on, primed as k_aov_rays primes them: at most n_in
+    float4* out_rd;
+    float2* out_res;
+    uint32_t* out_item;
+    unsigned int* count;     // how many (zeroed by the host)
+    float4* state;           // per item: thr.xyz, len
+    int2* aux;               // per item: (last triangle hit, or -1 after a miss), B; a sample whose camera ray missed: (-1, 0)
+    const float4* tri_nm;
+    const float4* mats;      // 3 rows per material, row 1 = kd.xyz, row 2 = ke.xyz
+    // k_aov_spec_resolve
+    float4* acc;             // [nslots][3] running sums across chunks: (guide.xyz, sum D), (normal.xyz, bits(hits)), (sum B, bits(tri_L of sample 0), -, -)
+    float* guide_albedo;     // outputs (any may be null), layout as AovParams
+    float* last_normal;
+    float* path_depth;
+    float* bounces;
+    int32_t* last_tri;
+};
+void launch_aov_bounce(const AovSpecParams& S, hipStream_t st);
+void launch_aov_spec_resolve(const AovSpecParams& S, hipStream_t st);
+
 // sparse frames (parameter blocks: crt_stages.h; host side: crt_sparse.hip)
 // crt_adaptive.hip
 void launch_adaptive_init(const AdaptiveParams& D, hipStream_t st);       // after the warm-up: n_p = D.n at every pixel, 0 at padding slots

@@ -1,5 +1,5 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
-// pipeline, the AOV pass, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*,
+// pipeline, the AOV passes, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*,
 // crt_render_aov*, crt_intersect, crt_device_*).  The frames in which not every pixel takes every sample (crt_render_adaptive*,
 // crt_render_map*, crt_sample_plan*, crt_render_planned*) are ranges of render_impl with an item source: crt_sparse.hip, which sees this
 // file through crt_render.h.  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip,
@@ -143,8 +143,9 @@ MegaPlan plan_mega3(const crt_scene* sc, uint32_t traversal, bool want_stats, bo
 // Traces the n query rays in the handle's query pool (p_ro / p_rd, p_res primed: the form k_fill_rays writes) on stream st with the
 // traversal phases of the render kernel itself -- k_mega3 in query form (work item = ray), or k_trace on the fallback pipeline -- and
 // leaves the answers on the device: (t or FLT_MAX, bits(triangle or -1)) of ray i at the returned pointer + i * stride floats (the float4
-// answers of the query form, stride 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV pass.
-const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride)
+// answers of the query form, stride 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV passes.  first: the rays
+// are those from `first` on in the pool (the pass that follows mirror bounces keeps its rays in two halves of the pool).
+const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride, size_t first = 0)
 {
     if (choose_pipeline(sc) == 4) {
         const MegaPlan mp = plan_mega3(sc, traversal, false, false, true, false, n, 0xffffffffu);
@@ -160,7 +161,7 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
         P.n_items = n;
         P.items_per_shard = ((n + ITEM_SHARDS - 1) / ITEM_SHARDS + 63u) & ~63u;
         P.item_next = sc->item_next.p; P.L4 = answers; P.counters = sc->counters.p;
-        P.q_o = sc->p_ro.p; P.q_d = sc->p_rd.p;
+        P.q_o = sc->p_ro.p + first; P.q_d = sc->p_rd.p + first;
         P.nslots = 1; P.nslots_div = make_fastdiv(1); P.tiles_x = 1; P.tiles_x_div = make_fastdiv(1); P.lsn_div = make_fastdiv(1);
         M3.M.sc = sc->dev; M3.M.counters = sc->counters.p; M3.M.spill_stride = lanes; M3.M.stack_cap = mp.lds_levels;
         M3.spill = (int*)sc->spill[0].p;
@@ -173,12 +174,12 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
     }
     Pool pool;
     std::memset(&pool, 0, sizeof(pool));
-    pool.ro = sc->p_ro.p; pool.rd = sc->p_rd.p; pool.res = sc->p_res.p; pool.n = n;
+    pool.ro = sc->p_ro.p + first; pool.rd = sc->p_rd.p + first; pool.res = sc->p_res.p + first; pool.n = n;
     TraceSetup TS = make_trace_setup(sc, pool, traversal, false);
     launch_trace_pass(sc, TS, st);
     HIP_CHECK(hipGetLastError());
     stride = 2;
-    return (const float*)sc->p_res.p;
+    return (const float*)(sc->p_res.p + first);
 }
 
 } // namespace
@@ -826,6 +827,109 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
     });
 }
 
+// The AOV pass that follows mirror bounces (crt_render_aov_specular): chunks as aov_impl's.  After a chunk's camera rays are traced,
+// k_aov_bounce advances every item's chain and compacts the reflected rays into the other half of the query pool (the halves alternate
+// from bounce to bounce: a stage never writes the rays or answers another of its threads still reads); the host reads their count --
+// one 4-byte copy into pinned memory and one synchronization per bounce and chunk -- traces that many and runs the next stage on their
+// answers.  A count of 0 ends the chunk's bounces; the stage after the last bounce allowed has nothing to compact and needs no count.
+int aov_specular_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp, const crt_aov_specular_buffers* out)
+{
+    if (!sc || !cam || !prm || !sp || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: null argument");
+    if (!out->guide_albedo && !out->last_normal && !out->path_depth && !out->bounces && !out->last_tri)
+        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: no output buffer");
+    if (sp->max_bounces < 1 || sp->max_bounces > 8) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: max_bounces must be in [1, 8]");
+    const int rc = params_check("crt_render_aov_specular", prm, true);
+    if (rc != CRT_OK) return rc;
+    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
+        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov_specular: more than 2^31 pixel slots in a shard");
+    return CRT_OK;
+}
+
+int aov_specular_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp, const crt_aov_specular_buffers* out,
+                      hipStream_t st, crt_aov_info* info)
+{
+    const int rc = aov_specular_check(sc, cam, prm, sp, out);
+    if (rc != CRT_OK) return rc;
+    const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
+    const Shard sh = make_shard(prm->width, prm->height, prm->world);
+    return hip_guard([&]() -> int {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
+        const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
+        // every buffer at its final size before the first launch: growing one later would drop what a stage has left in it
+        sc->p_ro.ensure(2 * max_rays); sc->p_rd.ensure(2 * max_rays); sc->p_res.ensure(2 * max_rays); sc->aovs_item.ensure(2 * max_rays);
+        sc->aovs_state.ensure(max_rays); sc->aovs_aux.ensure(max_rays);
+        if (choose_pipeline(sc) == 4) (void)sc->L.answers(max_rays);
+        sc->aov_acc.ensure((size_t)sh.nslots * 3);
+        sc->aovs_count.ensure_uncached(1);
+        if (!sc->h_aovs_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_aovs_count, sizeof(unsigned int), hipHostMallocDefault));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (info) {
+            ensure_events(sc);
+            e0 = sc->ev[0]; e1 = sc->ev[1];
+            HIP_CHECK(hipEventRecord(e0, st));
+        }
+        AovParams A;
+        std::memset(&A, 0, sizeof(A));
+        std::memcpy(A.eye, cam->eye, sizeof(A.eye));
+        std::memcpy(A.inv_view, cam->inv_view, sizeof(A.inv_view));
+        camera_scale_ar(cam, prm, A.scale, A.ar);
+        fill_slot_map(A, *prm, tiled, sh);
+        A.seed = prm->seed; A.spp = prm->spp;
+        A.pool.ro = sc->p_ro.p; A.pool.rd = sc->p_rd.p; A.pool.res = sc->p_res.p;
+        AovSpecParams S;
+        std::memset(&S, 0, sizeof(S));
+        fill_slot_map(S, *prm, tiled, sh);
+        S.spp = prm->spp; S.max_bounces = sp->max_bounces;
+        S.count = sc->aovs_count.p; S.state = sc->aovs_state.p; S.aux = sc->aovs_aux.p;
+        S.tri_nm = sc->dev.tri_nm; S.mats = sc->dev.mats; S.acc = sc->aov_acc.p;
+        S.guide_albedo = out->guide_albedo; S.last_normal = out->last_normal; S.path_depth = out->path_depth; S.bounces = out->bounces; S.last_tri = out->last_tri;
+        const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
+        uint64_t rays = 0;
+        uint32_t chunks = 0;
+        for (uint32_t s0 = 0; s0 < prm->spp; s0 += chunk) {
+            const uint32_t ns = std::min(chunk, prm->spp - s0);
+            const uint32_t n = ns * sh.nslots;
+            A.sample_begin = s0; A.n_samples = ns; A.pool.n = n;
+            launch_aov_rays(A, st);
+            HIP_CHECK(hipGetLastError());
+            S.res = trace_queries(sc, n, prm->traversal, force_exact, st, S.res_stride);
+            rays += n;
+            size_t in = 0, outh = max_rays; // where in the pool the rays traced last are, and where those that go on are put
+            uint32_t n_in = n;
+            for (uint32_t stage = 0; n_in > 0; stage++) {
+                S.stage0 = stage == 0; S.n_in = n_in;
+                S.in_ro = sc->p_ro.p + in; S.in_rd = sc->p_rd.p + in; S.in_item = sc->aovs_item.p + in;
+                S.out_ro = sc->p_ro.p + outh; S.out_rd = sc->p_rd.p + outh; S.out_res = sc->p_res.p + outh; S.out_item = sc->aovs_item.p + outh;
+                HIP_CHECK(hipMemsetAsync(sc->aovs_count.p, 0, sizeof(unsigned int), st));
+                launch_aov_bounce(S, st);
+                HIP_CHECK(hipGetLastError());
+                if (stage == sp->max_bounces) break; // (every chain that came this far is at the cap)
+                HIP_CHECK(hipMemcpyAsync(sc->h_aovs_count, sc->aovs_count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of a bounce: how many rays go on
+                n_in = std::min<uint32_t>(*sc->h_aovs_count, n_in);
+                if (n_in == 0) break;
+                S.res = trace_queries(sc, n_in, prm->traversal, force_exact, st, S.res_stride, outh);
+                rays += n_in;
+                std::swap(in, outh);
+            }
+            S.n_samples = ns;
+            S.first_chunk = s0 == 0; S.last_chunk = s0 + ns == prm->spp;
+            launch_aov_spec_resolve(S, st);
+            HIP_CHECK(hipGetLastError());
+            chunks++;
+        }
+        if (info) {
+            HIP_CHECK(hipEventRecord(e1, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            std::memset(info, 0, sizeof(*info));
+            info->rays = rays; info->chunks = chunks;
+            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
+        }
+        return CRT_OK;
+    });
+}
+
 } // namespace
 
 extern "C" {
@@ -1026,6 +1130,41 @@ int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, 
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
         for (int i = 0; i < 6; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
+        return CRT_OK;
+    });
+}
+
+int crt_aov_specular_defaults(crt_aov_specular_params* p)
+{
+    if (!p) return fail(CRT_ERR_INVALID_ARG, "crt_aov_specular_defaults: null argument");
+    p->max_bounces = 2;
+    return CRT_OK;
+}
+
+int crt_render_aov_specular_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp,
+                                   const crt_aov_specular_buffers* dev_out, void* stream, crt_aov_info* info)
+{
+    return aov_specular_impl(sc, cam, prm, sp, dev_out, (hipStream_t)stream, info);
+}
+
+int crt_render_aov_specular(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp,
+                            const crt_aov_specular_buffers* host_out, crt_aov_info* info)
+{
+    const int rc0 = aov_specular_check(sc, cam, prm, sp, host_out);
+    if (rc0 != CRT_OK) return rc0;
+    const crt_aov_specular_buffers& h = *host_out;
+    return hip_guard([&]() -> int {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
+        void* const host[5] = {h.guide_albedo, h.last_normal, h.path_depth, h.bounces, h.last_tri}; // 4-byte values: three per pixel, three, then one each
+        DevBuf<float> buf[5];
+        for (int i = 0; i < 5; i++)
+            if (host[i]) buf[i].alloc(npix * (i < 2 ? 3 : 1));
+        const crt_aov_specular_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p};
+        const int rc = aov_specular_impl(sc, cam, prm, sp, &d, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int i = 0; i < 5; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
         return CRT_OK;
     });
 }

@@ -62,6 +62,13 @@ struct crt_scene {
     crtk::DevBuf<float2> p_res;
     crtk::DevBuf<float> accum;
     crtk::DevBuf<float4> aov_acc;                   // AOV pass: running sums of the pixel slots between its chunks (crt_render_aov)
+    // crt_render_aov_specular: per camera ray of a chunk the chain state (thr.xyz, len) and (last triangle, bounces); the items of the
+    // rays in the two halves of the query pool; the counter of the rays that go on (uncached) and the pinned word it is copied to
+    crtk::DevBuf<float4> aovs_state;
+    crtk::DevBuf<int2> aovs_aux;
+    crtk::DevBuf<uint32_t> aovs_item;
+    crtk::DevBuf<unsigned int> aovs_count;
+    unsigned int* h_aovs_count = nullptr;
     crtk::DevBuf<unsigned long long> counters;      // [CNT_SHARDS][CNT_STRIDE]
     crtk::DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
     crtk::DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)
@@ -117,6 +124,7 @@ struct crt_scene {
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
         if (h_counters) (void)hipHostFree(h_counters);
         if (h_ad_count) (void)hipHostFree(h_ad_count);
+        if (h_aovs_count) (void)hipHostFree(h_aovs_count);
         if (h_map) (void)hipHostFree(h_map);
     }
 };

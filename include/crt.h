@@ -401,6 +401,52 @@ int crt_render_aov(crt_scene* scene, const crt_camera* cam, const crt_params* pa
 int crt_render_aov_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* dev_out,
                           void* hip_stream, crt_aov_info* info);
 
+/* AOVs that follow perfect-mirror bounces: what a SPECULAR surface reflects instead of the surface itself, as guides of the denoiser.
+ * Per sample k of a pixel the first ray is crt_render_aov's (origin eye, the unit camera direction, closest hit with params->traversal).
+ * If it misses, the sample is no hit and adds nothing anywhere.  Otherwise a chain starts with len = +0.0f, B = 0, thr unset, and at
+ * every hit (triangle tri, distance t, material m; o, d the ray's origin and unit direction):
+ *   len = len + t
+ *   the chain goes on iff m is SPECULAR (the flag the render kernel reads: crt_material.mode == 1; the shipped loader: Ns > 1) and
+ *   B < max_bounces.  Then, per channel / component,
+ *     thr = (B == 0) ? kd(m) : thr * kd(m)
+ *     n   = crt_triangle.normal of tri, as stored
+ *     P   = o + d * t                                 one multiply, then one add
+ *     c   = d.x * n.x + (d.y * n.y + d.z * n.z);  c2 = c + c
+ *     r   = d - n * c2                                one multiply, then one subtract
+ *   the next ray has origin P (no offset: a hit at t <= epsilon is rejected by the intersector, as for every ray) and the direction r
+ *   normalised as crt_intersect normalises a raw direction;  B = B + 1;  it is traced for its closest hit.
+ * The chain ends at a hit it does not go on from (tri_L, m_L), or at a miss.  Of a sample that is a hit:  D = len;  B = the reflected
+ * rays traced;  if the chain ended at a hit, G = kd(m_L) if B == 0, else G = thr * (kd(m_L) + e) with e = ke(m_L) < 1 ? ke(m_L) : 1
+ * per channel (one add, then one multiply), and N = the stored normal of tri_L;  if it ended at a miss, G and N are absent.
+ * Per pixel, in sample order, from +0.0f, S = params->spp, n_hit = the samples that are hits:
+ *   guide_albedo 3 floats  a = a + G / S over the samples that have a G
+ *   last_normal  3 floats  the same with N
+ *   path_depth   float     (sum of D) / (float)n_hit; 0.0f if n_hit = 0
+ *   bounces      float     (sum of (float)B) / (float)n_hit; 0.0f if n_hit = 0
+ *   last_tri     int32     tri_L of sample 0; -1 if sample 0 missed or its chain ended at a miss
+ * IEEE fp32, no FMA, no reciprocal multiply.  A pixel none of whose samples hits a SPECULAR triangle has crt_render_aov's albedo, normal
+ * and depth in guide_albedo, last_normal and path_depth bit for bit, bounces 0 and last_tri = tri.  No refraction; a rough (glossy)
+ * SPECULAR surface is followed as a perfect mirror.
+ * Layout (row-major, or tiled shards with CRT_FLAG_TILED_OUTPUT; padding slots 0 and -1), chunks of whole samples of at most 2^25
+ * camera rays, the ignored params and the progressive frame in flight (left alone) are crt_render_aov's.  A chunk needs 104 B of the
+ * handle's query buffers (two halves, which the bounces alternate between) and 24 B of chain state per camera ray.  Any buffer may be NULL, not all five.  A null pointer, five NULL
+ * buffers, max_bounces outside 1 .. 8, spp 0 or a size of 0 is CRT_ERR_INVALID_ARG, checked before any device call.
+ * info->rays counts the camera rays (as crt_render_aov's) and the reflected rays (of pixels; a padding slot's ray is not followed),
+ * info->chunks the chunks of whole samples. */
+typedef struct { uint32_t max_bounces; } crt_aov_specular_params;   /* 1 .. 8 */
+typedef struct { float* guide_albedo; float* last_normal; float* path_depth; float* bounces; int32_t* last_tri; } crt_aov_specular_buffers;
+int crt_aov_specular_defaults(crt_aov_specular_params* params);     /* max_bounces 2 */
+/* host_out: host buffers (W*H or slots elements of 3 or 1 values each); info optional */
+int crt_render_aov_specular(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_specular_params* specular,
+                            const crt_aov_specular_buffers* host_out, crt_aov_info* info);
+/* dev_out: device buffers on the scene's device, work enqueued on hip_stream (NULL = default stream).  Unlike crt_render_aov_device the
+ * call is not asynchronous: after each bounce of each chunk the host reads how many rays go on -- one 4-byte copy into pinned memory and
+ * one synchronization of the stream per bounce and chunk, as crt_render_adaptive_device per pass -- to trace only those and to stop at
+ * 0 (a scene without SPECULAR triangles: one synchronization per chunk).  The last bounce allowed needs none.  The outputs are enqueued
+ * after it without a further synchronization, unless info != NULL (the call then synchronizes once more to read the timer). */
+int crt_render_aov_specular_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_specular_params* specular,
+                                   const crt_aov_specular_buffers* dev_out, void* hip_stream, crt_aov_info* info);
+
 /* AOV-guided edge-avoiding denoiser: an a-trous ("with holes") wavelet filter with edge-stopping weights on colour, normal, albedo and
  * depth (Dammertz et al. 2010), run as `iterations` passes over a frame's pre-tone-map mean radiance (out_mean of crt_render), guided by
  * the buffers crt_render_aov returns.  An image operation: no scene handle.  Row-major images of width x height; color, albedo, normal

@@ -4,11 +4,20 @@ buffers) and of crt_render_device at the same camera and params, each around the
 call; best of --reps.  Prints one JSON line.  Device buffers come from the HIP runtime libcrt.so is linked against (ctypes).
 
   python tools/aov_probe.py [--spp 16,64,512] [--scenes cornell-box,veach-mis] [--reps 3]
+
+--specular instead times the pass that follows mirror bounces (crt_render_aov_specular_device, all five buffers, --bounces) beside
+crt_render_aov_device in one process, the two taking turns: the HIP-event time of each call (its info) and the host-clock time around
+it, median and best of --reps, at --spp (default 64).  The specular call synchronizes its stream once per bounce and chunk to read how
+many rays go on; `syncs` is that count and `sync_us` the host-clock time of one 4-byte device-to-host copy on the idle device, which is
+what one such round trip costs at least.
+
+  python tools/aov_probe.py --specular [--spp 64] [--bounces 1,2] [--reps 20]
 """
 import argparse
 import ctypes as C
 import json
 import os
+import statistics
 import sys
 import time
 
@@ -25,7 +34,60 @@ def hip_runtime():
     H = C.CDLL(path)
     H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
     H.hipFree.argtypes = [C.c_void_p]
+    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     return H
+
+
+def specular(a, H, dev_alloc):
+    """The two AOV passes side by side (see the module's text)."""
+    w, h = a.width, a.height
+    ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
+    sptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_SPECULAR_BUFFERS.items()}
+    word = C.c_uint32()
+    us = []
+    for _ in range(200):
+        H.hipDeviceSynchronize()
+        t0 = time.perf_counter()
+        H.hipMemcpy(C.addressof(word), C.c_void_p(ptrs["depth"]), 4, 2)  # hipMemcpyDeviceToHost
+        us.append((time.perf_counter() - t0) * 1e6)
+    out = {"width": w, "height": h, "reps": a.reps, "sync_us": round(statistics.median(us[20:]), 2), "runs": []}
+    spps = [int(s) for s in a.spp.split(",")] if a.spp != "16,64,512" else [64]
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        sc = crt.Scene.from_task(t, w, h)
+        r = crt.Render(sc, 1, t.P_RR, t.light_sample_n)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        for spp in spps:
+            r.set_spp(spp)
+            for mb in [int(v) for v in a.bounces.split(",")]:
+                ev = {"aov": [], "spec": []}
+                host = {"aov": [], "spec": []}
+                for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
+                    for key, fn in (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, ptrs)),
+                                    ("spec", lambda: r.run_view_aov_specular_device(t.eye_pos, iv, fov, sptrs, max_bounces=mb))):
+                        H.hipDeviceSynchronize()
+                        t0 = time.perf_counter()
+                        info = fn()
+                        dt = (time.perf_counter() - t0) * 1e3
+                        if i >= 2:
+                            ev[key].append(info["total_ms"])
+                            host[key].append(dt)
+                info = r.aov_specular_info
+                camera_rays = r.aov_info["rays"]
+                # one synchronization after every bounce kernel but the one at the cap; a chunk whose count comes back 0 stops there
+                run = {"scene": name, "spp": spp, "max_bounces": mb, "chunks": info["chunks"], "camera_rays": camera_rays,
+                       "reflected_rays": info["rays"] - camera_rays,
+                       "aov_event_ms": round(statistics.median(ev["aov"]), 4), "aov_event_ms_best": round(min(ev["aov"]), 4),
+                       "specular_event_ms": round(statistics.median(ev["spec"]), 4), "specular_event_ms_best": round(min(ev["spec"]), 4),
+                       "aov_host_ms": round(statistics.median(host["aov"]), 4), "specular_host_ms": round(statistics.median(host["spec"]), 4),
+                       "specular_over_aov": round(statistics.median(ev["spec"]) / statistics.median(ev["aov"]), 3)}
+                out["runs"].append(run)
+                print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+    for p in list(ptrs.values()) + list(sptrs.values()):
+        H.hipFree(C.c_void_p(p))
+    print(json.dumps(out), flush=True)
 
 
 def main():
@@ -35,6 +97,8 @@ def main():
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--specular", action="store_true", help="time crt_render_aov_specular_device beside crt_render_aov_device")
+    ap.add_argument("--bounces", default="1,2", help="--specular: the max_bounces values")
     a = ap.parse_args()
     w, h = a.width, a.height
     H = hip_runtime()
@@ -45,6 +109,8 @@ def main():
             raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
         return p.value
 
+    if a.specular:
+        return specular(a, H, dev_alloc)
     rgb = dev_alloc(w * h * 3)
     ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
     out = {"width": w, "height": h, "reps": a.reps, "runs": []}

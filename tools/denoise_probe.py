@@ -8,6 +8,14 @@ pass over the time -- next to the rate of the compulsory 52 B per pixel and pass
 written) in the same run, the two forms' calls taking turns, and prints its figures and the ratio to the plain form.
 
   python tools/denoise_probe.py [--sizes 800x600,3840x2160] [--iterations 3,5] [--calls 50] [--warmup 5] [--spp 4] [--variance]
+
+--error measures what the filters leave instead of what they cost: per scene (--scenes), a frame of --error-spp samples (seed 0) at
+--error-size, filtered by crt_denoise and by crt_denoise_var (their defaults) with the first-hit albedo and with guide_albedo of
+crt_render_aov_specular (--bounces) as the albedo guide -- normal and depth first-hit throughout -- and the mean squared error of each
+RGB8 result against a frame of --ref-spp samples (seed 999).  --sigma-albedo also lists the error for other values of that one sigma.
+
+  python tools/denoise_probe.py --error [--scenes cornell-box,veach-mis] [--error-size 160x120] [--error-spp 8] [--ref-spp 256]
+                                [--bounces 1,2] [--sigma-albedo 0.05,0.1,0.2,0.4]
 """
 import argparse
 import ctypes as C
@@ -36,6 +44,43 @@ def hip_runtime():
     return H
 
 
+def error_table(a):
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "spp": a.error_spp, "ref_spp": a.ref_spp, "runs": []}
+    sigmas = [None] + [float(v) for v in a.sigma_albedo.split(",") if v]
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = 999
+        ref = r.run_view(t.eye_pos, iv, fov).astype(np.float64)
+        r.seed = 0
+        r.set_spp(a.error_spp)
+        noisy_rgb = r.run_view(t.eye_pos, iv, fov, want_variance=True).copy()
+        mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+        g = r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth"))
+        guides = {"first-hit": g["albedo"]}
+        for mb in [int(v) for v in a.bounces.split(",")]:
+            guides["guide_albedo, max_bounces %d" % mb] = r.run_view_aov_specular(t.eye_pos, iv, fov, max_bounces=mb, want=("guide_albedo",))["guide_albedo"]
+        r.free()
+
+        def mse(x):
+            return round(float(np.mean((x.astype(np.float64) - ref) ** 2)), 1)
+
+        run = {"scene": name, "unfiltered": mse(noisy_rgb), "rows": []}
+        for label, alb in guides.items():
+            for sa in sigmas:
+                row = {"albedo_guide": label, "sigma_albedo": sa,
+                       "denoise": mse(crt.denoise(mean, albedo=alb, normal=g["normal"], depth=g["depth"], sigma_albedo=sa)[0]),
+                       "denoise_var": mse(crt.denoise_var(mean, var, albedo=alb, normal=g["normal"], depth=g["depth"], sigma_albedo=sa)[0])}
+                run["rows"].append(row)
+                print(json.dumps(dict(row, scene=name)), file=sys.stderr, flush=True)
+        out["runs"].append(run)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="800x600,3840x2160")
@@ -45,9 +90,18 @@ def main():
     ap.add_argument("--spp", type=int, default=4)
     ap.add_argument("--scene", default="cornell-box")
     ap.add_argument("--variance", action="store_true", help="time crt_denoise_var_device beside crt_denoise_device")
+    ap.add_argument("--error", action="store_true", help="the error the filters leave, with the first-hit and the specular albedo guide")
+    ap.add_argument("--scenes", default="cornell-box,veach-mis")
+    ap.add_argument("--error-size", default="160x120")
+    ap.add_argument("--error-spp", type=int, default=8)
+    ap.add_argument("--ref-spp", type=int, default=256)
+    ap.add_argument("--bounces", default="1,2")
+    ap.add_argument("--sigma-albedo", default="")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
+    if a.error:
+        return error_table(a)
     H = hip_runtime()
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
     iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
