@@ -128,6 +128,21 @@ class AovInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class AovShadingBuffers(C.Structure):
+    _fields_ = [("emission", C.c_void_p), ("diffuse_albedo", C.c_void_p)]
+
+
+class ModulateParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("albedo_floor", C.c_float)]
+
+
+class ModulateInfo(C.Structure):
+    _fields_ = [("total_ms", C.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class AovSpecularParams(C.Structure):
     _fields_ = [("max_bounces", C.c_uint32)]
 
@@ -247,6 +262,8 @@ AOV_BUFFERS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1
 # the buffers of crt_aov_specular_buffers
 AOV_SPECULAR_BUFFERS = {"guide_albedo": (3, np.float32), "last_normal": (3, np.float32), "path_depth": (1, np.float32),
                         "bounces": (1, np.float32), "last_tri": (1, np.int32)}
+# the buffers of crt_aov_shading_buffers
+AOV_SHADING_BUFFERS = {"emission": (3, np.float32), "diffuse_albedo": (3, np.float32)}
 
 
 class Task(C.Structure):
@@ -276,7 +293,9 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
            "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
-           "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device"]
+           "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device",
+           "crt_render_aov_shading", "crt_render_aov_shading_device", "crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate",
+           "crt_modulate_device"]
 
 _lib = None
 
@@ -329,6 +348,18 @@ def lib():
                                           C.POINTER(AovSpecularBuffers), C.POINTER(AovInfo)]
     L.crt_render_aov_specular_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovSpecularParams),
                                                  C.POINTER(AovSpecularBuffers), C.c_void_p, C.POINTER(AovInfo)]
+    L.crt_render_aov_shading.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovShadingBuffers),
+                                         C.POINTER(AovInfo)]
+    L.crt_render_aov_shading_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovShadingBuffers),
+                                                C.c_void_p, C.POINTER(AovInfo)]
+    L.crt_modulate_defaults.argtypes = [C.POINTER(ModulateParams)]
+    L.crt_demodulate.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.POINTER(ModulateInfo)]
+    L.crt_demodulate_device.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(ModulateInfo)]
+    L.crt_modulate.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ModulateInfo)]
+    L.crt_modulate_device.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(ModulateInfo)]
     L.crt_denoise_defaults.argtypes = [C.POINTER(DenoiseParams)]
     L.crt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
     L.crt_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.POINTER(DenoiseInfo)]

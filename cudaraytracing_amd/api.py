@@ -177,6 +177,7 @@ class Render:
         self.aov_info = None
         self.aov_specular_info = None
         self.aov_buffers = None
+        self.shading_buffers = None  # run_view_denoised / run_view_temporal with demodulate: emission and diffuse_albedo of the frame
         self.denoise_info = None
         self.variance_buffer = None
         self.samples_buffer = None
@@ -486,6 +487,49 @@ class Render:
             self.aov_info = info.as_dict()
         return self.aov_info if want_info else None
 
+    def run_view_aov_shading(self, eye_pos, inv_view_mat, fovY, want=tuple(capi.AOV_SHADING_BUFFERS), first=(), width=None, height=None):
+        """Shading AOVs (crt_render_aov_shading, contract: include/crt.h): emission -- ke / spp over the samples whose camera ray hits
+        an emitter -- and diffuse_albedo -- kd / spp over the other hits --, what demodulate() takes.  `first` names buffers of
+        run_view_aov to fill from the same trace (crt_render_aov's bits).  Returns {name: array} for the names in `want` and `first`;
+        self.aov_info gets rays, chunks, total_ms."""
+        h_ = self._handle("run_view_aov_shading")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        w, h = prm.width, prm.height
+        out, bufs, fbufs = {}, capi.AovShadingBuffers(), capi.AovBuffers()
+        for names, table, struct in ((want, capi.AOV_SHADING_BUFFERS, bufs), (first, capi.AOV_BUFFERS, fbufs)):
+            for name in names:
+                ch, dt = table[name]
+                out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
+                setattr(struct, name, out[name].ctypes.data)
+        info = capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov_shading(h_, C.byref(cam), C.byref(prm), C.byref(fbufs) if first else None, C.byref(bufs), C.byref(info)),
+                   "crt_render_aov_shading")
+        self.aov_info = info.as_dict()
+        return out
+
+    def run_view_aov_shading_device(self, eye_pos, inv_view_mat, fovY, ptrs, first_ptrs=None, stream=None, rank=0, world=1, tiled=False,
+                                    want_info=True, width=None, height=None):
+        """The same with outputs in device memory: ptrs = {"emission" / "diffuse_albedo": raw device pointer}, first_ptrs the same for
+        buffers of run_view_aov_device (None: none); layout, stream and want_info as run_view_aov_device."""
+        h_ = self._handle("run_view_aov_shading_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
+        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        bufs, fbufs = capi.AovShadingBuffers(), capi.AovBuffers()
+        for given, table, struct in ((ptrs, capi.AOV_SHADING_BUFFERS, bufs), (first_ptrs or {}, capi.AOV_BUFFERS, fbufs)):
+            for name, p in given.items():
+                if name not in table:
+                    raise ValueError("unknown AOV buffer %r" % name)
+                setattr(struct, name, int(p) if p else None)
+        info = capi.AovInfo()
+        capi.check(capi.lib().crt_render_aov_shading_device(h_, C.byref(cam), C.byref(prm), C.byref(fbufs) if first_ptrs else None, C.byref(bufs),
+                                                            C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
+                   "crt_render_aov_shading_device")
+        if want_info:
+            self.aov_info = info.as_dict()
+        return self.aov_info if want_info else None
+
     def run_view_aov_specular(self, eye_pos, inv_view_mat, fovY, max_bounces=None, want=tuple(capi.AOV_SPECULAR_BUFFERS), width=None, height=None):
         """AOVs that follow perfect-mirror bounces from the first hit (crt_render_aov_specular, contract: include/crt.h): returns
         {name: array} for the names in `want` (guide_albedo, last_normal: (H, W, 3) float32; path_depth, bounces: (H, W) float32;
@@ -527,31 +571,46 @@ class Render:
         return self.aov_specular_info if want_info else None
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
-                          sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None):
+                          sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
+                          demodulate=False, albedo_floor=None):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
         variance_guided: render with want_variance and filter with crt_denoise_var (its own defaults) and self.variance_buffer.
         specular_guides: the albedo guide is guide_albedo of run_view_aov_specular (max_bounces) -- what a mirror reflects instead of the
-        mirror; normal and depth stay first-hit."""
+        mirror; normal and depth stay first-hit.
+        demodulate: the filter runs on irradiance.  The shading AOVs (self.shading_buffers: emission, diffuse_albedo) come from the same
+        pass as the guides, the frame (and, variance_guided, its variance) goes through demodulate(albedo_floor), is filtered with the
+        caller's sigmas -- the albedo guide is still passed; sigma_albedo=float("inf") drops it -- and comes back through modulate()."""
         self._handle("run_view_denoised")
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=variance_guided)
-        self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        guides = ("albedo", "normal", "depth")
+        if demodulate:
+            aov = self.run_view_aov_shading(eye_pos, inv_view_mat, fovY, first=guides, width=width, height=height)
+            self.aov_buffers = {k: aov[k] for k in guides}
+            self.shading_buffers = {k: aov[k] for k in capi.AOV_SHADING_BUFFERS}
+        else:
+            self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=guides, width=width, height=height)
         if specular_guides:
             self.aov_buffers["albedo"] = self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=max_bounces, want=("guide_albedo",),
                                                                     width=width, height=height)["guide_albedo"]
+        color, var = self.mean_buffer, self.variance_buffer if variance_guided else None
+        if demodulate:
+            sh = self.shading_buffers
+            got = _demodulate(color, sh["diffuse_albedo"], sh["emission"], variance=var, albedo_floor=albedo_floor, device=self.device)
+            color, var = got if variance_guided else (got, None)
+        settings = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
+                        device=self.device, want_rgb=not demodulate, return_info=True)
         if variance_guided:
-            rgb, mean, self.denoise_info = denoise_var(self.mean_buffer, self.variance_buffer, iterations=iterations, sigma_color=sigma_color,
-                                                       sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
-                                                       device=self.device, return_info=True, **self.aov_buffers)
-            return rgb, mean
-        rgb, mean, self.denoise_info = denoise(self.mean_buffer, iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal,
-                                               sigma_albedo=sigma_albedo, sigma_depth=sigma_depth, device=self.device, return_info=True,
-                                               **self.aov_buffers)
+            rgb, mean, self.denoise_info = denoise_var(color, var, **settings, **self.aov_buffers)
+        else:
+            rgb, mean, self.denoise_info = denoise(color, **settings, **self.aov_buffers)
+        if demodulate:
+            rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
         return rgb, mean
 
     def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, variance="samples",
-                          **overrides):
+                          demodulate=False, albedo_floor=None, **overrides):
         """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
         AOV pass (albedo, normal, depth, material) and blends the frame into the history this object keeps -- colour, variance, history
         length, depth, normal, material ID and camera of the previous call; the unfiltered result is the next call's history.
@@ -565,59 +624,85 @@ class Render:
         variance="moments": the frame is rendered WITHOUT want_variance (so one sample per pixel works), the history also keeps the
         moment planes of crt_temporal_moments, and self.variance_buffer -- what denoise=True feeds to denoise_var -- is
         variance_estimate of them with the frame's normal and depth; overrides may then also name variance_estimate's settings, and
-        self.variance_estimate_info holds its info dict.  A change of `variance` starts a history."""
+        self.variance_estimate_info holds its info dict.  A change of `variance` starts a history.
+        demodulate: the sequence is accumulated as irradiance.  Each frame's shading AOVs (self.shading_buffers) come from the pass of
+        its guides; the frame and its variance go through demodulate(albedo_floor) before the blend, so the history -- and with it the
+        clamp's neighbourhood, the moments and self.variance_buffer -- holds irradiance and its variance.  What is returned (and, with
+        denoise=True, filtered first, on irradiance) goes through modulate() with the CURRENT frame's buffers.  A change of `demodulate`
+        starts a history."""
         if variance not in ("samples", "moments"):
             raise ValueError("run_view_temporal: variance must be 'samples' or 'moments', got %r" % (variance,))
         self._handle("run_view_temporal")
+        demodulate = bool(demodulate)
+        if self._temporal is not None and self._temporal.get("demodulate", False) != demodulate:
+            self._temporal = None
         if variance == "moments":
-            return self._run_view_temporal_moments(eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides)
+            return self._run_view_temporal_moments(eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides, demodulate, albedo_floor)
         if self._temporal is not None and "m1" in self._temporal:
             self._temporal = None
-        keep_seed = self.seed
-        self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
-        try:
-            self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=True)
-            aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth", "material"), width=width, height=height)
-        finally:
-            self.seed = keep_seed
+        aov = self._temporal_frame(eye_pos, inv_view_mat, fovY, seed, width, height, True, demodulate)
         h, w = self.mean_buffer.shape[:2]
         cam = (np.array(eye_pos, dtype=np.float32), np.array(inv_view_mat, dtype=np.float32).reshape(9), np.float32(fovY))
         cur = {"color": self.mean_buffer, "variance": self.variance_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
+        if demodulate:
+            sh = self.shading_buffers
+            cur["color"], cur["variance"] = _demodulate(self.mean_buffer, sh["diffuse_albedo"], sh["emission"], variance=self.variance_buffer,
+                                                        albedo_floor=albedo_floor, device=self.device)
         t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h)) else None
         rgb, mean, var, hist, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
-                                              return_info=True, clamp=clamp, **overrides)
-        self._temporal = {"prev": dict(cur, color=mean, variance=var, history=hist), "camera": cam, "size": (w, h)}
+                                              return_info=True, clamp=clamp, want_rgb=not demodulate, **overrides)
+        self._temporal = {"prev": dict(cur, color=mean, variance=var, history=hist), "camera": cam, "size": (w, h), "demodulate": demodulate}
         self._temporal_frames += 1
-        self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
         self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
-        if denoise:
-            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, return_info=True, **self.aov_buffers)
-        return rgb, mean
+        return self._temporal_result(rgb, mean, var, denoise, demodulate, albedo_floor)
 
-    def _run_view_temporal_moments(self, eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides):
-        estimate = {k: overrides.pop(k) for k in list(overrides) if k in _ESTIMATE_SETTINGS}
+    def _temporal_frame(self, eye_pos, inv_view_mat, fovY, seed, width, height, want_variance, demodulate):
+        """Renders a frame of run_view_temporal with its seed and runs the pass of its guides (self.aov_buffers) and, demodulate, of its
+        shading AOVs (self.shading_buffers); returns the first-hit buffers the blend takes."""
+        names = ("albedo", "normal", "depth", "material")
         keep_seed = self.seed
         self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
         try:
-            self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height)
-            aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth", "material"), width=width, height=height)
+            self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=want_variance)
+            if demodulate:
+                aov = self.run_view_aov_shading(eye_pos, inv_view_mat, fovY, first=names, width=width, height=height)
+                self.shading_buffers = {k: aov[k] for k in capi.AOV_SHADING_BUFFERS}
+            else:
+                aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=names, width=width, height=height)
         finally:
             self.seed = keep_seed
+        self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
+        return aov
+
+    def _temporal_result(self, rgb, mean, var, denoise, demodulate, albedo_floor):
+        """What run_view_temporal returns of the accumulated frame (mean, var): filtered with denoise, and back from irradiance with
+        demodulate."""
+        if denoise:
+            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, want_rgb=not demodulate, return_info=True, **self.aov_buffers)
+        if demodulate:
+            sh = self.shading_buffers
+            rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
+        return rgb, mean
+
+    def _run_view_temporal_moments(self, eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides, demodulate=False, albedo_floor=None):
+        estimate = {k: overrides.pop(k) for k in list(overrides) if k in _ESTIMATE_SETTINGS}
+        aov = self._temporal_frame(eye_pos, inv_view_mat, fovY, seed, width, height, False, demodulate)
         h, w = self.mean_buffer.shape[:2]
         cam = (np.array(eye_pos, dtype=np.float32), np.array(inv_view_mat, dtype=np.float32).reshape(9), np.float32(fovY))
         cur = {"color": self.mean_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
+        if demodulate:
+            sh = self.shading_buffers
+            cur["color"] = _demodulate(self.mean_buffer, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
         t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h) and "m1" in self._temporal) else None
         rgb, mean, _, hist, m1, m2, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
-                                                    return_info=True, clamp=clamp, moments={"m1": t["m1"], "m2": t["m2"]} if t else True, **overrides)
-        self._temporal = {"prev": dict(cur, color=mean, history=hist), "camera": cam, "size": (w, h), "m1": m1, "m2": m2}
+                                                    return_info=True, clamp=clamp, moments={"m1": t["m1"], "m2": t["m2"]} if t else True,
+                                                    want_rgb=not demodulate, **overrides)
+        self._temporal = {"prev": dict(cur, color=mean, history=hist), "camera": cam, "size": (w, h), "m1": m1, "m2": m2, "demodulate": demodulate}
         self._temporal_frames += 1
-        self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
         var, self.variance_estimate_info = variance_estimate(m1, m2, hist, normal=aov["normal"], depth=aov["depth"], device=self.device,
                                                              return_info=True, **estimate)
         self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
-        if denoise:
-            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, return_info=True, **self.aov_buffers)
-        return rgb, mean
+        return self._temporal_result(rgb, mean, var, denoise, demodulate, albedo_floor)
 
     def reset_temporal(self):
         """Drops the history of run_view_temporal: the next call is a first frame (and renders with self.seed again)."""
@@ -759,6 +844,12 @@ class MultiRender(Render):
 
     def run_view_aov_device(self, *a, **k):
         raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_device)")
+
+    def run_view_aov_shading(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_shading)")
+
+    def run_view_aov_shading_device(self, *a, **k):
+        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_shading_device)")
 
     def run_view_aov_specular(self, *a, **k):
         raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_specular)")
@@ -961,6 +1052,101 @@ def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                                                  C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
                "crt_denoise_var_device")
     return info.as_dict() if want_info else None
+
+
+def modulate_defaults():
+    """crt_modulate_defaults as a dict: albedo_floor."""
+    p = capi.ModulateParams()
+    capi.check(capi.lib().crt_modulate_defaults(C.byref(p)), "crt_modulate_defaults")
+    return {"albedo_floor": float(p.albedo_floor)}
+
+
+def _modulate_params(width, height, albedo_floor):
+    p = capi.ModulateParams()
+    capi.check(capi.lib().crt_modulate_defaults(C.byref(p)), "crt_modulate_defaults")
+    p.width, p.height = int(width), int(height)
+    if albedo_floor is not None:
+        p.albedo_floor = float(albedo_floor)
+    return p
+
+
+def _modulate_images(who, image, others):
+    """The (H, W, 3) float32 image of demodulate / modulate and the buffers that must have its shape (None: not given)."""
+    c = np.ascontiguousarray(image, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("%s needs an (H, W, 3) image, got %r" % (who, c.shape))
+    out = [c]
+    for name, a in others:
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != c.shape:
+                raise ValueError("%s: %s has shape %r, expected %r" % (who, name, a.shape, c.shape))
+        out.append(a)
+    return out
+
+
+def demodulate(color, albedo, emission=None, variance=None, albedo_floor=None, device=0, return_info=False):
+    """Radiance to irradiance (crt_demodulate, contract: include/crt.h): (color - emission) / albedo per channel wherever albedo >
+    albedo_floor, color - emission elsewhere; all (H, W, 3) float32 -- albedo and emission are diffuse_albedo and emission of
+    Render.run_view_aov_shading.  Returns the irradiance, with `variance` (of Render.variance()) the pair (irradiance, variance /
+    albedo^2); with return_info also the crt_modulate_info dict."""
+    if albedo is None:
+        raise ValueError("demodulate needs the albedo buffer (Render.run_view_aov_shading: diffuse_albedo)")
+    c, a, e, v = _modulate_images("demodulate", color, (("albedo", albedo), ("emission", emission), ("variance", variance)))
+    h, w = c.shape[:2]
+    prm = _modulate_params(w, h, albedo_floor)
+    out = np.zeros((h, w, 3), dtype=np.float32)
+    ovar = np.zeros((h, w, 3), dtype=np.float32) if v is not None else None
+    info = capi.ModulateInfo()
+    capi.check(capi.lib().crt_demodulate(device, C.byref(prm), capi.ptr(c), capi.ptr(a), capi.ptr(e), capi.ptr(v), capi.ptr(out), capi.ptr(ovar),
+                                         C.byref(info)), "crt_demodulate")
+    res = ((out,) if v is None else (out, ovar)) + ((info.as_dict(),) if return_info else ())
+    return res[0] if len(res) == 1 else res
+
+
+def modulate(irradiance, albedo, emission=None, albedo_floor=None, device=0, want_rgb=True, return_info=False):
+    """Irradiance back to radiance (crt_modulate): irradiance * albedo wherever albedo > albedo_floor, plus emission.  Returns (rgb,
+    mean): the frame's RGB8 tone map (None without want_rgb) and the radiance; with return_info also the crt_modulate_info dict."""
+    if albedo is None:
+        raise ValueError("modulate needs the albedo buffer (Render.run_view_aov_shading: diffuse_albedo)")
+    i, a, e = _modulate_images("modulate", irradiance, (("albedo", albedo), ("emission", emission)))
+    h, w = i.shape[:2]
+    prm = _modulate_params(w, h, albedo_floor)
+    mean = np.zeros((h, w, 3), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.ModulateInfo()
+    capi.check(capi.lib().crt_modulate(device, C.byref(prm), capi.ptr(i), capi.ptr(a), capi.ptr(e), capi.ptr(mean), capi.ptr(rgb), C.byref(info)),
+               "crt_modulate")
+    return (rgb, mean, info.as_dict()) if return_info else (rgb, mean)
+
+
+def _vp(p):
+    return C.c_void_p(p) if p else None
+
+
+def demodulate_device(width, height, color_ptr, albedo_ptr, out_ptr, emission_ptr=None, variance_ptr=None, out_variance_ptr=None, albedo_floor=None,
+                      device=0, stream=None, want_info=True):
+    """Enqueues crt_demodulate_device on raw device pointers.  With want_info the call synchronizes the stream and returns the
+    crt_modulate_info dict, else None."""
+    prm = _modulate_params(width, height, albedo_floor)
+    info = capi.ModulateInfo()
+    capi.check(capi.lib().crt_demodulate_device(device, C.byref(prm), _vp(color_ptr), _vp(albedo_ptr), _vp(emission_ptr), _vp(variance_ptr), _vp(out_ptr),
+                                                _vp(out_variance_ptr), _vp(stream), C.byref(info) if want_info else None), "crt_demodulate_device")
+    return info.as_dict() if want_info else None
+
+
+def modulate_device(width, height, irradiance_ptr, albedo_ptr, out_mean_ptr, out_rgb_ptr=None, emission_ptr=None, albedo_floor=None, device=0,
+                    stream=None, want_info=True):
+    """Enqueues crt_modulate_device on raw device pointers; out_mean_ptr or out_rgb_ptr may be None, not both.  want_info as
+    demodulate_device."""
+    prm = _modulate_params(width, height, albedo_floor)
+    info = capi.ModulateInfo()
+    capi.check(capi.lib().crt_modulate_device(device, C.byref(prm), _vp(irradiance_ptr), _vp(albedo_ptr), _vp(emission_ptr), _vp(out_mean_ptr),
+                                              _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None), "crt_modulate_device")
+    return info.as_dict() if want_info else None
+
+
+_demodulate, _modulate = demodulate, modulate  # (the Render methods have a `demodulate` argument of their own)
 
 
 def _camera(eye_pos, inv_view_mat, fovY):

@@ -1,7 +1,8 @@
 // cudaraytracing_amd/csrc/crt_aov.hip -- the first-hit AOV pass (crt_render_aov, include/crt.h): per pixel, the camera rays of samples
 // 0 .. spp-1 -- the primary rays of the frame's paths, camera_dir -- traced by the render kernel's own closest-hit query, and the albedo,
 // normal, depth, coverage, triangle and material buffers made of their hits in sample order.  The host side (chunks over samples, the
-// trace) is in crt_render.hip; slot -> pixel -> output index is the frame kernels' (slot_pixel, crt_internal.h).
+// trace) is in crt_render.hip; slot -> pixel -> output index is the frame kernels' (slot_pixel, crt_internal.h).  The same pass with the
+// emission and non-emitter albedo buffers beside them (crt_render_aov_shading) is the resolve's second instantiation.
 // Below it, the pass that follows perfect-mirror bounces from those hits (crt_render_aov_specular): a bounce kernel and its own resolve.
 #include "crt_internal.h"
 
@@ -25,23 +26,33 @@ __global__ __launch_bounds__(256) void k_aov_rays(const AovParams A)
 // One thread per pixel slot: the chunk's samples in order, each hit adding kd / spp, normal / spp and t to the running sums (IEEE
 // division and addition, no contraction: k_accumulate's c + L / spp), carried to the next chunk in A.acc.  The last chunk writes the
 // outputs.
-__global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A)
+// SHADING (crt_render_aov_shading): the same trace also feeds two more sums -- ke / spp over the hits on emitters (TNM_EMITTER: the
+// flag the render kernel ends a path on) and kd / spp over the others; ke is row 2 of the material whose row 1 the hit has fetched.
+// They cross chunks in the two spare floats of accumulator row 2 and a fourth row, so a slot then has four rows, not three.
+// The plain instantiation takes H and never reads it; its listing must stay the untemplated kernel's, instruction for instruction
+// (crt_render_aov's bits and time do not depend on the shading form: docs/experiments.md, "Albedo demodulation").
+template <bool SHADING> __global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A, const AovShadingOut H)
 {
     const uint32_t slot = blockIdx.x * 256u + threadIdx.x;
     if (slot >= A.nslots) return;
     const SlotPixel px = slot_pixel(A, slot);
     if (!px.valid && (!px.out || !A.last_chunk)) return;
     F3 alb = f3(0.0f, 0.0f, 0.0f), nrm = f3(0.0f, 0.0f, 0.0f);
+    F3 emi = f3(0.0f, 0.0f, 0.0f), dal = f3(0.0f, 0.0f, 0.0f);
     float dsum = 0.0f;
     uint32_t hits = 0;
     int32_t tri0 = -1, mat0 = -1;
     if (px.valid) {
-        float4* acc = A.acc + (size_t)slot * 3;
+        float4* acc = A.acc + (size_t)slot * (SHADING ? 4 : 3);
         if (!A.first_chunk) {
             const float4 a0 = acc[0], a1 = acc[1], a2 = acc[2];
             alb = f3(a0.x, a0.y, a0.z); dsum = a0.w;
             nrm = f3(a1.x, a1.y, a1.z); hits = __float_as_uint(a1.w);
             tri0 = __float_as_int(a2.x); mat0 = __float_as_int(a2.y);
+            if (SHADING) {
+                const float4 a3 = acc[3];
+                emi = f3(a2.z, a2.w, a3.x); dal = f3(a3.y, a3.z, a3.w);
+            }
         }
         const float fspp = (float)A.spp;
         for (uint32_t s = 0; s < A.n_samples; s++) {
@@ -57,13 +68,26 @@ __global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A)
                 nrm.x = nrm.x + tn.x / fspp; nrm.y = nrm.y + tn.y / fspp; nrm.z = nrm.z + tn.z / fspp;
                 dsum = dsum + t;
                 hits++;
+                if (SHADING) {
+                    if (TNM_EMITTER(__float_as_uint(tn.w))) {
+                        const float4 ke = A.mats[(size_t)m * 3 + 2];
+                        emi.x = emi.x + ke.x / fspp; emi.y = emi.y + ke.y / fspp; emi.z = emi.z + ke.z / fspp;
+                    } else {
+                        dal.x = dal.x + kd.x / fspp; dal.y = dal.y + kd.y / fspp; dal.z = dal.z + kd.z / fspp;
+                    }
+                }
             }
             if (A.first_chunk && s == 0) { tri0 = tri >= 0 ? tri : -1; mat0 = m; }
         }
         if (!A.last_chunk) {
             acc[0] = make_float4(alb.x, alb.y, alb.z, dsum);
             acc[1] = make_float4(nrm.x, nrm.y, nrm.z, __uint_as_float(hits));
-            acc[2] = make_float4(__int_as_float(tri0), __int_as_float(mat0), 0.0f, 0.0f);
+            if (SHADING) {
+                acc[2] = make_float4(__int_as_float(tri0), __int_as_float(mat0), emi.x, emi.y);
+                acc[3] = make_float4(emi.z, dal.x, dal.y, dal.z);
+            } else {
+                acc[2] = make_float4(__int_as_float(tri0), __int_as_float(mat0), 0.0f, 0.0f);
+            }
             return;
         }
     }
@@ -74,6 +98,10 @@ __global__ __launch_bounds__(256) void k_aov_resolve(const AovParams A)
     if (A.coverage) A.coverage[o] = (float)hits / (float)A.spp;
     if (A.tri) A.tri[o] = tri0;
     if (A.material) A.material[o] = mat0;
+    if (SHADING) {
+        if (H.emission) { H.emission[o * 3 + 0] = emi.x; H.emission[o * 3 + 1] = emi.y; H.emission[o * 3 + 2] = emi.z; }
+        if (H.diffuse_albedo) { H.diffuse_albedo[o * 3 + 0] = dal.x; H.diffuse_albedo[o * 3 + 1] = dal.y; H.diffuse_albedo[o * 3 + 2] = dal.z; }
+    }
 }
 
 // ---- the pass that follows mirror bounces (crt_render_aov_specular, include/crt.h) ----
@@ -201,6 +229,10 @@ void launch_aov_rays(const AovParams& A, hipStream_t st)
     const uint64_t n = (uint64_t)A.n_samples * A.nslots;
     hipLaunchKernelGGL(k_aov_rays, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, A);
 }
-void launch_aov_resolve(const AovParams& A, hipStream_t st) { hipLaunchKernelGGL(k_aov_resolve, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A); }
+void launch_aov_resolve(const AovParams& A, hipStream_t st) { hipLaunchKernelGGL(k_aov_resolve<false>, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, AovShadingOut{nullptr, nullptr}); }
+void launch_aov_resolve_shading(const AovParams& A, const AovShadingOut& H, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_aov_resolve<true>, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, H);
+}
 
 } // namespace crtk

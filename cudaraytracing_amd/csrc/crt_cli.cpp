@@ -10,7 +10,11 @@
 //           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
-//           [--temporal-variance samples|moments[,MIN_HISTORY]]
+//           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
+// --aov-shading PREFIX writes the shading AOVs of the frame (crt_render_aov_shading, one device, the trace of --aov): PREFIX.emission.pfm
+// and PREFIX.diffuse_albedo.pfm (3 channels).  --demodulate makes --denoise and --temporal work on irradiance: the frame (and its
+// variance) goes through crt_demodulate with those two buffers before the filter or the blend and the result through crt_modulate, so
+// --temporal's history holds irradiance and --temporal-out is modulated with the last frame's buffers.
 // --temporal N renders N frames on one device and accumulates them over time (crt_temporal, its defaults): frame f = 0 .. N-1 has eye and
 // lookat moved by f x the --temporal-step vector and the seed --seed + f.  -o gets the last frame as rendered, --temporal-out PATH the
 // accumulated last frame; --temporal-denoise writes the variance-guided filter (crt_denoise_var, its defaults with the --denoise-iterations
@@ -56,7 +60,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
-                             "       [--denoise-specular]\n"
+                             "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
@@ -66,7 +70,8 @@ int main(int argc, char** argv)
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, aov_specular, denoise, variance, adaptive_samples;
+        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, denoise, variance, adaptive_samples;
+        bool demodulate = false;
         crt_adaptive_params ad;
         crt_adaptive_defaults(&ad);
         bool adaptive = false, ad_option = false, planned = false;
@@ -135,6 +140,8 @@ int main(int argc, char** argv)
                 }
                 if (aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular needs a PREFIX");
             }
+            else if (a == "--aov-shading") { need(i, 1); aov_shading = argv[++i]; if (aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading needs a PREFIX"); }
+            else if (a == "--demodulate") demodulate = true;
             else if (a == "--denoise-specular") denoise_specular = true;
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
             else if (a == "--denoise-variance") denoise_var = true;
@@ -225,6 +232,8 @@ int main(int argc, char** argv)
         const bool multi = !devices.empty();
         if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
         if (multi && !aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular renders on one device (not with --gpus / --devices)");
+        if (multi && !aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading renders on one device (not with --gpus / --devices)");
+        if (demodulate && denoise.empty() && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--demodulate needs --denoise PATH or --temporal N");
         if (denoise_specular && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-specular needs --denoise PATH");
         if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
         if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
@@ -254,6 +263,8 @@ int main(int argc, char** argv)
         render.set_seed(seed);
         render.set_traversal(reference ? CRT_TRAVERSAL_REFERENCE : (fast && !exact) ? CRT_TRAVERSAL_FAST : CRT_TRAVERSAL_EXACT);
         render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u));
+        render.set_aov_shading(!aov_shading.empty());
+        if (demodulate) render.set_demodulate(true);
         float inv_view[9];
         crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
         float fov_y = task.fov_y * (float)M_PI / 180; // src/main.cu:278
@@ -318,7 +329,16 @@ int main(int argc, char** argv)
             if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the samples file failed: ") + crt_last_error());
             std::printf("%s\n", adaptive_samples.c_str());
         }
-        if (!aov.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
+        if (!aov.empty() || !aov_shading.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
+        if (!aov_shading.empty()) {
+            const crt_aov_info& ai = render.last_aov_info();
+            std::printf("aov-shading: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
+            const std::string pe = aov_shading + ".emission.pfm", pa = aov_shading + ".diffuse_albedo.pfm";
+            int rc = crt_write_pfm(pe.c_str(), task.width, task.height, 3, render.get_emission_buffer());
+            if (rc == CRT_OK) rc = crt_write_pfm(pa.c_str(), task.width, task.height, 3, render.get_diffuse_albedo_buffer());
+            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the shading AOV files failed: ") + crt_last_error());
+            std::printf("%s\n%s\n", pe.c_str(), pa.c_str());
+        }
         if (!aov.empty()) {
             const crt_aov_info& ai = render.last_aov_info();
             std::printf("aov: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);

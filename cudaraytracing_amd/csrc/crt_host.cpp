@@ -739,8 +739,43 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f); material_buffer_.assign(n, 0);
     crt_aov_buffers out{};
     out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data(); out.material = material_buffer_.data();
-    const int rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
+    int rc;
+    if (aov_shading_) {
+        emission_buffer_.assign(3 * n, 0.0f); diffuse_albedo_buffer_.assign(3 * n, 0.0f);
+        const crt_aov_shading_buffers shading{emission_buffer_.data(), diffuse_albedo_buffer_.data()};
+        rc = crt_render_aov_shading(device_scene_, &cam, &p, &out, &shading, &aov_info_);
+    } else rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
+}
+
+crt_modulate_params Render::modulate_params(const char* who) const
+{
+    if (emission_buffer_.size() != (size_t)3 * scene_->get_pixels() || diffuse_albedo_buffer_.size() != emission_buffer_.size())
+        throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " with set_demodulate needs run_aov of this frame size first");
+    crt_modulate_params m;
+    crt_modulate_defaults(&m);
+    m.width = scene_->get_width(); m.height = scene_->get_height(); m.albedo_floor = albedo_floor_;
+    return m;
+}
+
+// crt_demodulate of a colour (and its variance, if any) with the shading AOVs of the last run_aov
+void Render::demodulate_of(const char* who, const float* color, const float* variance, std::vector<float>& irradiance, std::vector<float>& irradiance_variance) const
+{
+    const crt_modulate_params m = modulate_params(who);
+    const size_t n = scene_->get_pixels();
+    irradiance.assign(3 * n, 0.0f);
+    if (variance) irradiance_variance.assign(3 * n, 0.0f);
+    const int rc = crt_demodulate(device_, &m, color, diffuse_albedo_buffer_.data(), emission_buffer_.data(), variance, irradiance.data(),
+                                  variance ? irradiance_variance.data() : nullptr, nullptr);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
+}
+
+// crt_modulate of an irradiance with the same buffers
+void Render::modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const
+{
+    const crt_modulate_params m = modulate_params(who);
+    const int rc = crt_modulate(device_, &m, irradiance, diffuse_albedo_buffer_.data(), emission_buffer_.data(), out_mean, out_rgb, nullptr);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
 }
 
 void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces, bool as_albedo_guide)
@@ -781,8 +816,14 @@ void Render::run_denoise(const crt_denoise_params& prm)
     crt_denoise_inputs in{};
     in.color = mean_buffer_.data(); in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    const int rc = crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), &denoise_info_);
+    std::vector<float> irradiance, none;
+    if (demodulate_) {
+        demodulate_of("Render::run_denoise", mean_buffer_.data(), nullptr, irradiance, none);
+        in.color = irradiance.data();
+    }
+    const int rc = crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &denoise_info_);
     if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise failed: ") + crt_last_error());
+    if (demodulate_) modulate_of("Render::run_denoise", denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
 }
 
 const float* Render::variance()
@@ -799,17 +840,24 @@ const float* Render::variance()
 }
 
 // crt_denoise_var of a colour and its variance with the guides of the last run_aov
-void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm)
+// (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
+void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance)
 {
     const size_t n = scene_->get_pixels();
     crt_denoise_params p = prm;
     p.width = scene_->get_width(); p.height = scene_->get_height();
+    std::vector<float> irradiance, irradiance_variance;
+    if (demodulate_ && !is_irradiance) {
+        demodulate_of(who, color, variance, irradiance, irradiance_variance);
+        color = irradiance.data(); variance = irradiance_variance.data();
+    }
     crt_denoise_var_inputs in{};
     in.color = color; in.variance = variance;
     in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), nullptr, &denoise_info_);
+    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), nullptr, &denoise_info_);
     if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
+    if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
 }
 
 void Render::run_denoise_var(const crt_denoise_params& prm)
@@ -835,25 +883,33 @@ void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], f
     std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
     std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
     p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && !temporal_moments_ && temporal_width_ == p.width && temporal_height_ == p.height;
+    const bool have = temporal_valid_ && !temporal_moments_ && temporal_demodulated_ == demodulate_ && temporal_width_ == p.width && temporal_height_ == p.height;
     p.prev = have ? temporal_cam_ : p.cur;
     const size_t n = scene_->get_pixels();
     crt_temporal_frame cur{};
     cur.color = mean_buffer_.data(); cur.variance = var; cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
+    std::vector<float> irradiance, irradiance_variance;
+    if (demodulate_) {
+        demodulate_of("Render::run_temporal", mean_buffer_.data(), var, irradiance, irradiance_variance);
+        cur.color = irradiance.data(); cur.variance = irradiance_variance.data();
+    }
     crt_temporal_history prev{};
     prev.color = temporal_color_.data(); prev.variance = temporal_variance_.data(); prev.history = temporal_history_.data();
     prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
     std::vector<float> color(3 * n, 0.0f), variance_out(3 * n, 0.0f), history(n, 0.0f);
     temporal_rgb_.assign(3 * n, 0);
+    unsigned char* const call_rgb = demodulate_ ? nullptr : temporal_rgb_.data(); // (irradiance has no tone map worth having: modulate_of writes the RGB8)
     int rc;
     temporal_clamped_ = 0;
     if (clamp) {
         crt_temporal_clamp_info ci{};
-        rc = crt_temporal_clamped(device_, &p, clamp, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &ci);
+        rc = crt_temporal_clamped(device_, &p, clamp, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), call_rgb, &ci);
         temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
         temporal_clamped_ = ci.clamped;
-    } else rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), temporal_rgb_.data(), &temporal_info_);
+    } else rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), call_rgb, &temporal_info_);
     if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal failed: ") + crt_last_error()); }
+    if (demodulate_) modulate_of("Render::run_temporal", color.data(), nullptr, temporal_rgb_.data());
+    temporal_demodulated_ = demodulate_;
     temporal_color_.swap(color); temporal_variance_.swap(variance_out); temporal_history_.swap(history);
     temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
     temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
@@ -873,11 +929,16 @@ void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_m
     std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
     std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
     p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && temporal_moments_ && temporal_width_ == p.width && temporal_height_ == p.height;
+    const bool have = temporal_valid_ && temporal_moments_ && temporal_demodulated_ == demodulate_ && temporal_width_ == p.width && temporal_height_ == p.height;
     p.prev = have ? temporal_cam_ : p.cur;
     const size_t n = scene_->get_pixels();
     crt_temporal_frame cur{};
     cur.color = mean_buffer_.data(); cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
+    std::vector<float> irradiance, none;
+    if (demodulate_) {
+        demodulate_of("Render::run_temporal_moments", mean_buffer_.data(), nullptr, irradiance, none);
+        cur.color = irradiance.data();
+    }
     crt_temporal_history prev{};
     prev.color = temporal_color_.data(); prev.history = temporal_history_.data();
     prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
@@ -886,7 +947,7 @@ void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_m
     temporal_rgb_.assign(3 * n, 0);
     crt_temporal_clamp_info ci{};
     int rc = crt_temporal_moments(device_, &p, clamp, &cur, have ? &prev : nullptr, have ? &planes : nullptr, color.data(), nullptr, history.data(), m1.data(),
-                                  m2.data(), temporal_rgb_.data(), &ci);
+                                  m2.data(), demodulate_ ? nullptr : temporal_rgb_.data(), &ci); // (demodulate_: modulate_of writes the RGB8 below)
     if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
     temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
     temporal_clamped_ = ci.clamped;
@@ -896,6 +957,8 @@ void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_m
     in.m1 = m1.data(); in.m2 = m2.data(); in.history = history.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
     rc = crt_variance_estimate(device_, &e, &in, estimate.data(), &estimate_info_);
     if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
+    if (demodulate_) modulate_of("Render::run_temporal_moments", color.data(), nullptr, temporal_rgb_.data());
+    temporal_demodulated_ = demodulate_;
     temporal_color_.swap(color); temporal_variance_.swap(estimate); temporal_history_.swap(history);
     temporal_m1_.swap(m1); temporal_m2_.swap(m2);
     temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
@@ -908,7 +971,8 @@ void Render::run_denoise_temporal(const crt_denoise_params& prm)
 {
     if (!temporal_valid_ || temporal_color_.size() != (size_t)3 * scene_->get_pixels())
         throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first");
-    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm);
+    if (temporal_demodulated_ != demodulate_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal: set_demodulate changed since run_temporal");
+    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm, temporal_demodulated_);
 }
 
 void Render::save_temporal_buffer(const char* save_path) const

@@ -231,6 +231,17 @@ public:
     const float* get_normal_buffer() const { return normal_buffer_.data(); } // W x H x 3
     const float* get_depth_buffer() const { return depth_buffer_.data(); }   // W x H
     const crt_aov_info& last_aov_info() const { return aov_info_; }
+    // on: run_aov also fills the shading AOVs from its one trace (crt_render_aov_shading): emission and diffuse_albedo, W x H x 3 each
+    void set_aov_shading(bool on) { aov_shading_ = on; }
+    const float* get_emission_buffer() const { return emission_buffer_.data(); }
+    const float* get_diffuse_albedo_buffer() const { return diffuse_albedo_buffer_.data(); }
+    // on: the filters and the temporal pass work on irradiance (crt_demodulate / crt_modulate with albedo_floor and the shading AOVs of
+    // the last run_aov, which set_demodulate therefore switches on).  run_denoise / run_denoise_var demodulate the frame (and its
+    // variance), filter, and modulate the result.  run_temporal / run_temporal_moments demodulate each frame before the blend, so the
+    // history, get_temporal_mean_buffer() and get_temporal_variance_buffer() hold irradiance, while get_temporal_buffer() (RGB8) is the
+    // accumulated frame modulated with the current frame's buffers; run_denoise_temporal filters the irradiance and modulates.  A
+    // change of the switch starts a history.
+    void set_demodulate(bool on, float albedo_floor = 0.0f) { demodulate_ = on; albedo_floor_ = albedo_floor; if (on) aov_shading_ = true; }
     // the AOVs that follow mirror bounces (crt_render_aov_specular; max_bounces 0: crt_aov_specular_defaults'); one device only.
     // as_albedo_guide: guide_albedo also replaces the albedo of the last run_aov as the guide of run_denoise / run_denoise_var
     void run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces = 0, bool as_albedo_guide = false);
@@ -324,7 +335,15 @@ private:
     std::vector<float> temporal_m1_, temporal_m2_;   // run_temporal_moments: the history's moment planes
     bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
     crt_variance_estimate_info estimate_info_{};
-    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm);
+    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance = false);
+    // set_aov_shading / set_demodulate
+    bool aov_shading_ = false, demodulate_ = false;
+    float albedo_floor_ = 0.0f;
+    bool temporal_demodulated_ = false;              // the history holds irradiance
+    std::vector<float> emission_buffer_, diffuse_albedo_buffer_;
+    crt_modulate_params modulate_params(const char* who) const;
+    void demodulate_of(const char* who, const float* color, const float* variance, std::vector<float>& irradiance, std::vector<float>& irradiance_variance) const;
+    void modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const;
     crt_adaptive_info adaptive_info_{};
     crt_map_info map_info_{};
     template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);

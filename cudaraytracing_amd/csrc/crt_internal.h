@@ -147,6 +147,7 @@ struct AovParams : SlotMap {
     const float4* tri_nm;    // scene: normal.xyz, bits(material word) per triangle
     const float4* mats;      // scene: 3 rows per material, row 1 = kd.xyz
     float4* acc;             // [nslots][3] running sums across chunks: (albedo.xyz, depth), (normal.xyz, bits(hits)), (bits(tri_0), bits(m_0), -, -)
+                             // the shading form: [nslots][4], row 2 = (bits(tri_0), bits(m_0), emission.xy), row 3 = (emission.z, diffuse_albedo.xyz)
     float* albedo;           // outputs (any may be null): row-major W x H, or nslots with tiled_output
     float* normal;
     float* depth;
@@ -156,6 +157,12 @@ struct AovParams : SlotMap {
 };
 void launch_aov_rays(const AovParams& A, hipStream_t st);
 void launch_aov_resolve(const AovParams& A, hipStream_t st);
+// crt_render_aov_shading: the outputs the shading form of the resolve writes beside AovParams' (either may be null), same layout
+struct AovShadingOut {
+    float* emission;
+    float* diffuse_albedo;
+};
+void launch_aov_resolve_shading(const AovParams& A, const AovShadingOut& H, hipStream_t st);
 
 // AOV pass that follows mirror bounces (crt_aov.hip; host side: crt_render_aov_specular in crt_render.hip).  Items as above.  A stage
 // reads the answers of the n_in rays traced last (stage 0: the camera rays, ray i = item i; later: the reflected rays, ray i of item

@@ -760,11 +760,12 @@ namespace {
 const uint32_t kAovChunkRays = 1u << 25;
 
 // Argument checks of both forms, before any device call
+bool aov_no_buffer(const crt_aov_buffers* out) { return !out->albedo && !out->normal && !out->depth && !out->coverage && !out->tri && !out->material; }
+
 int aov_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out)
 {
     if (!sc || !cam || !prm || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: null argument");
-    if (!out->albedo && !out->normal && !out->depth && !out->coverage && !out->tri && !out->material)
-        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: no output buffer");
+    if (aov_no_buffer(out)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: no output buffer");
     const int rc = params_check("crt_render_aov", prm, true);
     if (rc != CRT_OK) return rc;
     if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
@@ -772,10 +773,30 @@ int aov_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm,
     return CRT_OK;
 }
 
-int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out, hipStream_t st, crt_aov_info* info)
+// The same for crt_render_aov_shading: `first` may be null (a struct that is given must name a buffer, as crt_render_aov's), `shading` not
+int aov_shading_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* first, const crt_aov_shading_buffers* shading)
 {
-    const int rc = aov_check(sc, cam, prm, out);
+    if (!sc || !cam || !prm || !shading) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: null argument");
+    if (!shading->emission && !shading->diffuse_albedo) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: no output buffer in shading");
+    if (first && aov_no_buffer(first)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: no output buffer in first (pass NULL for none)");
+    const int rc = params_check("crt_render_aov_shading", prm, true);
     if (rc != CRT_OK) return rc;
+    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
+        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov_shading: more than 2^31 pixel slots in a shard");
+    return CRT_OK;
+}
+
+// Which call aov_impl serves.  first_hit: crt_render_aov (out required, shading unused).  shading: crt_render_aov_shading -- out may be
+// null, the resolve's shading form writes both structs from the one trace and a slot has four accumulator rows.
+enum class AovForm { first_hit, shading };
+
+// The pass on device buffers.  The entry point has checked the arguments of its form (aov_check / aov_shading_check), once.
+int aov_impl(AovForm form, crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out, const crt_aov_shading_buffers* shading,
+             hipStream_t st, crt_aov_info* info)
+{
+    if (form == AovForm::first_hit) shading = nullptr;
+    const crt_aov_buffers none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (!out) out = &none;
     const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
     const Shard sh = make_shard(prm->width, prm->height, prm->world);
     return hip_guard([&]() -> int {
@@ -783,7 +804,7 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
         const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
         const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
         sc->p_ro.ensure(max_rays); sc->p_rd.ensure(max_rays); sc->p_res.ensure(max_rays);
-        sc->aov_acc.ensure((size_t)sh.nslots * 3);
+        sc->aov_acc.ensure((size_t)sh.nslots * (shading ? kAovAccRowsShading : kAovAccRows));
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (info) {
             ensure_events(sc);
@@ -811,7 +832,8 @@ int aov_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const 
             launch_aov_rays(A, st);
             HIP_CHECK(hipGetLastError());
             A.res = trace_queries(sc, n, prm->traversal, force_exact, st, A.res_stride);
-            launch_aov_resolve(A, st);
+            if (shading) launch_aov_resolve_shading(A, AovShadingOut{shading->emission, shading->diffuse_albedo}, st);
+            else launch_aov_resolve(A, st);
             HIP_CHECK(hipGetLastError());
             rays += n;
             chunks++;
@@ -860,7 +882,7 @@ int aov_specular_impl(crt_scene* sc, const crt_camera* cam, const crt_params* pr
         sc->p_ro.ensure(2 * max_rays); sc->p_rd.ensure(2 * max_rays); sc->p_res.ensure(2 * max_rays); sc->aovs_item.ensure(2 * max_rays);
         sc->aovs_state.ensure(max_rays); sc->aovs_aux.ensure(max_rays);
         if (choose_pipeline(sc) == 4) (void)sc->L.answers(max_rays);
-        sc->aov_acc.ensure((size_t)sh.nslots * 3);
+        sc->aov_acc.ensure((size_t)sh.nslots * kAovAccRows);
         sc->aovs_count.ensure_uncached(1);
         if (!sc->h_aovs_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_aovs_count, sizeof(unsigned int), hipHostMallocDefault));
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1110,7 +1132,9 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
 
 int crt_render_aov_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_out, void* stream, crt_aov_info* info)
 {
-    return aov_impl(sc, cam, prm, dev_out, (hipStream_t)stream, info);
+    const int rc = aov_check(sc, cam, prm, dev_out);
+    if (rc != CRT_OK) return rc;
+    return aov_impl(AovForm::first_hit, sc, cam, prm, dev_out, nullptr, (hipStream_t)stream, info);
 }
 
 int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* host_out, crt_aov_info* info)
@@ -1126,10 +1150,44 @@ int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, 
         for (int i = 0; i < 6; i++)
             if (host[i]) buf[i].alloc(npix * (i < 2 ? 3 : 1));
         const crt_aov_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p, (int32_t*)buf[5].p};
-        const int rc = aov_impl(sc, cam, prm, &d, nullptr, info);
+        const int rc = aov_impl(AovForm::first_hit, sc, cam, prm, &d, nullptr, nullptr, info);
         if (rc != CRT_OK) return rc;
         HIP_CHECK(hipDeviceSynchronize());
         for (int i = 0; i < 6; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
+        return CRT_OK;
+    });
+}
+
+int crt_render_aov_shading_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_first,
+                                  const crt_aov_shading_buffers* dev_shading, void* stream, crt_aov_info* info)
+{
+    const int rc = aov_shading_check(sc, cam, prm, dev_first, dev_shading);
+    if (rc != CRT_OK) return rc;
+    return aov_impl(AovForm::shading, sc, cam, prm, dev_first, dev_shading, (hipStream_t)stream, info);
+}
+
+int crt_render_aov_shading(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* host_first,
+                           const crt_aov_shading_buffers* host_shading, crt_aov_info* info)
+{
+    const int rc0 = aov_shading_check(sc, cam, prm, host_first, host_shading);
+    if (rc0 != CRT_OK) return rc0;
+    return hip_guard([&]() -> int {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
+        const crt_aov_buffers none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const crt_aov_buffers& h = host_first ? *host_first : none;
+        // 4-byte values: crt_aov_buffers' six (three per pixel, three, then one each), then the two shading buffers (three per pixel)
+        void* const host[8] = {h.albedo, h.normal, h.depth, h.coverage, h.tri, h.material, host_shading->emission, host_shading->diffuse_albedo};
+        const auto values = [](int i) { return (i < 2 || i >= 6) ? 3 : 1; };
+        DevBuf<float> buf[8];
+        for (int i = 0; i < 8; i++)
+            if (host[i]) buf[i].alloc(npix * values(i));
+        const crt_aov_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p, (int32_t*)buf[5].p};
+        const crt_aov_shading_buffers ds{buf[6].p, buf[7].p};
+        const int rc = aov_impl(AovForm::shading, sc, cam, prm, host_first ? &d : nullptr, &ds, nullptr, info);
+        if (rc != CRT_OK) return rc;
+        HIP_CHECK(hipDeviceSynchronize());
+        for (int i = 0; i < 8; i++) buf[i].download((float*)host[i], npix * values(i));
         return CRT_OK;
     });
 }

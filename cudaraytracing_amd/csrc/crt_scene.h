@@ -46,6 +46,10 @@ struct ItemResults {
     float4* answers(size_t n) { words.ensure(n * 4); return reinterpret_cast<float4*>(words.p); } // (hipMalloc's alignment)
 };
 
+// float4 rows of crt_scene::aov_acc per pixel slot (the layout: AovParams::acc, crt_internal.h): the AOV passes' three, and the four of
+// the shading form, whose six extra sums fill the two spare floats of row 2 and a fourth row
+const size_t kAovAccRows = 3, kAovAccRowsShading = 4;
+
 struct crt_scene {
     int device = 0;
     crtk::DevBuf<float4> nodes, tri_geo, mats, ltri, nodes3, leaf_geo, tri_nm, nodes4, nodes4i, leaf_geo_i;
@@ -61,7 +65,7 @@ struct crt_scene {
     uint32_t n_mats = 0;
     crtk::DevBuf<float2> p_res;
     crtk::DevBuf<float> accum;
-    crtk::DevBuf<float4> aov_acc;                   // AOV pass: running sums of the pixel slots between its chunks (crt_render_aov)
+    crtk::DevBuf<float4> aov_acc;                   // AOV pass: running sums of the pixel slots between its chunks (crt_render_aov): kAovAccRows per slot, kAovAccRowsShading for crt_render_aov_shading
     // crt_render_aov_specular: per camera ray of a chunk the chain state (thr.xyz, len) and (last triangle, bounces); the items of the
     // rays in the two halves of the query pool; the counter of the rays that go on (uncached) and the pinned word it is copied to
     crtk::DevBuf<float4> aovs_state;

@@ -401,6 +401,32 @@ int crt_render_aov(crt_scene* scene, const crt_camera* cam, const crt_params* pa
 int crt_render_aov_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* dev_out,
                           void* hip_stream, crt_aov_info* info);
 
+/* Shading AOVs: what the frame's radiance factors into, so that an image filter can work on irradiance instead (crt_demodulate below).
+ * In the reference's path loop the radiance of sample k is ke(m_k) and nothing else if its camera ray hits an emitter, and carries the
+ * factor kd(m_k) in every term otherwise; so  frame = emission + sum_k kd(m_k) * I_k / S.  crt_render_aov's albedo sums kd over ALL
+ * hits, emitters included; these two buffers split the hits.
+ * Rays, chunks, layout (row-major, or the tiled shard with CRT_FLAG_TILED_OUTPUT), the ignored params and the frame in flight on the
+ * handle (left alone) are exactly crt_render_aov's; a sample is a hit when its camera ray hits a triangle tri_k with material m_k.  An
+ * emitter is a material with the flag the render kernel ends a path on: crt_material.has_emit != 0.  S = params->spp; both sums start
+ * at +0.0f and run in sample order:
+ *   emission        3 floats  e = e + ke(m_k) / S over the hits on emitters          ke = crt_material.ke
+ *   diffuse_albedo  3 floats  b = b + kd(m_k) / S over the hits on non-emitters      kd = crt_material.kd
+ * IEEE fp32 divisions, no FMA, no reciprocal multiply; padding slots get 0.  At a pixel none of whose samples hits an emitter,
+ * diffuse_albedo has albedo's bits and emission is +0.  ONE trace serves both structs: `first` may be NULL; when it is not, its
+ * buffers (any may be NULL, not all six) get crt_render_aov's bits.  `shading` must not be NULL and must name at least one buffer.
+ * A null scene, camera, params or shading, no buffer in shading, six NULL buffers in a `first` that is given, spp 0 or a size of 0 is
+ * CRT_ERR_INVALID_ARG, checked before any device call, as is everything crt_render_aov refuses.  Works on both pipelines and with
+ * EXACT, REFERENCE and FAST traversal.  info as crt_render_aov's.  Not followed: emission seen through a mirror (the SPECULAR probe
+ * term keeps its kd factor and stays in the irradiance). */
+typedef struct { float* emission; float* diffuse_albedo; } crt_aov_shading_buffers;   /* 3 floats per pixel each */
+/* host buffers (W*H or slots elements of 3 or 1 values each); info optional */
+int crt_render_aov_shading(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* host_first /* may be NULL */,
+                           const crt_aov_shading_buffers* host_shading, crt_aov_info* info);
+/* device buffers on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then synchronizes the stream to read the timer) */
+int crt_render_aov_shading_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_buffers* dev_first /* may be NULL */,
+                                  const crt_aov_shading_buffers* dev_shading, void* hip_stream, crt_aov_info* info);
+
 /* AOVs that follow perfect-mirror bounces: what a SPECULAR surface reflects instead of the surface itself, as guides of the denoiser.
  * Per sample k of a pixel the first ray is crt_render_aov's (origin eye, the unit camera direction, closest hit with params->traversal).
  * If it misses, the sample is no hit and adds nothing anywhere.  Otherwise a chain starts with len = +0.0f, B = 0, thr unset, and at
@@ -523,6 +549,47 @@ int crt_denoise_var(int device, const crt_denoise_params* params, const crt_deno
 int crt_denoise_var_device(int device, const crt_denoise_params* params, const crt_denoise_var_inputs* dev_in, void* d_out_mean,
                            void* d_out_rgb, void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream,
                            crt_denoise_info* info);
+
+/* Albedo demodulation: filter irradiance, not radiance.  crt_demodulate takes the emission off a frame and divides it by the albedo,
+ * crt_modulate puts both back, so that crt_denoise* and crt_temporal* in between see neither the surfaces' colour nor the lights
+ * (SVGF, Schied et al. 2017, section 4).  With emission and diffuse_albedo of crt_render_aov_shading the factorisation is exact for this
+ * renderer: frame = emission + sum_k kd(m_k) * I_k / S.  Image operations: no scene handle, no scratch.  Row-major images of width x
+ * height, 3 floats per pixel every one (out_rgb: 3 bytes).  Per pixel and channel, in fp32, one IEEE operation per symbol (no FMA, no
+ * reciprocal multiply):
+ *   use = albedo > albedo_floor                                   (false for a NaN albedo)
+ *   crt_demodulate:  d = color - emission                         (emission NULL: d = color)
+ *                    irradiance   = use ? d / albedo : d
+ *                    out_variance = use ? variance / (albedo * albedo) : variance      (variance, out_variance: both or neither)
+ *   crt_modulate:    m = use ? irradiance * albedo : irradiance
+ *                    c = m + emission                             (emission NULL: c = m)
+ *                    out_mean = c;  out_rgb = the frame's tone map of c (the bits crt_render writes for that mean); either may be
+ *                    NULL, not both
+ * Where the albedo is not above the floor the value passes through both ways, so the pair is the identity there (a pixel without a hit,
+ * a channel the surface absorbs: its radiance is +0 anyway).  Non-finite inputs are not special-cased: the arithmetic defines the
+ * result.  albedo_floor must be >= 0 and not NaN; crt_modulate_defaults fills 0 (width and height 0).
+ * A null params, image, albedo or output pointer, a size of 0, a bad floor, variance without out_variance or the reverse, or two NULL
+ * outputs of crt_modulate is CRT_ERR_INVALID_ARG, checked before any device call.  (A side longer than 2^24 pixels:
+ * CRT_ERR_UNSUPPORTED.)  An output may be the input image itself; otherwise buffers must not overlap. */
+typedef struct {
+    uint32_t width, height;
+    float albedo_floor;
+} crt_modulate_params;
+typedef struct {
+    float total_ms;    /* HIP-event time of the call's kernel on its stream */
+} crt_modulate_info;
+int crt_modulate_defaults(crt_modulate_params* params);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_demodulate(int device, const crt_modulate_params* params, const float* color, const float* albedo, const float* emission /* may be NULL */,
+                   const float* variance /* may be NULL */, float* out_irradiance, float* out_variance /* with variance */, crt_modulate_info* info);
+int crt_modulate(int device, const crt_modulate_params* params, const float* irradiance, const float* albedo, const float* emission /* may be NULL */,
+                 float* out_mean, uint8_t* out_rgb, crt_modulate_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then synchronizes the stream to read the timer).  Buffers that are all 16-byte aligned (out_rgb: 4-byte) take 16-byte
+ * accesses; any other alignment of whole floats works, component by component. */
+int crt_demodulate_device(int device, const crt_modulate_params* params, const void* d_color, const void* d_albedo, const void* d_emission,
+                          const void* d_variance, void* d_out_irradiance, void* d_out_variance, void* hip_stream, crt_modulate_info* info);
+int crt_modulate_device(int device, const crt_modulate_params* params, const void* d_irradiance, const void* d_albedo, const void* d_emission,
+                        void* d_out_mean, void* d_out_rgb, void* hip_stream, crt_modulate_info* info);
 
 /* Temporal accumulation with reprojection (the temporal half of SVGF, Schied et al. 2017): the frame of the current camera is blended
  * with the accumulated frame of the previous camera, fetched where the surface point of each pixel was seen then, so that a moving

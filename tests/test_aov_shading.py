@@ -1,0 +1,367 @@
+"""Shading AOVs (crt_render_aov_shading / crt_render_aov_shading_device, include/crt.h; Render.run_view_aov_shading in Python; crt_cli
+--aov-shading): the emission and the non-emitter albedo that the frame's radiance factors into.
+
+The expected buffers come from the oracle's primary rays (test_aov.primary_rays), folded in numpy float32 exactly as the contract says:
+e = e + ke / S over the hits on emitters, b = b + kd / S over the other hits, in sample order.  Every buffer must match bit for bit.
+The CPU tests check the factorisation itself on the oracle's frames: frame = E + sum_k kd(m_k) * I_k / S.
+"""
+import ctypes as C
+import functools
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import test_aov as aov
+import util
+
+F = np.float32
+NAMES = ("emission", "diffuse_albedo")
+SCENE_NAMES = ("cornell-box", "veach-mis")
+SHADING_EXPORTS = ("crt_render_aov_shading", "crt_render_aov_shading_device")
+
+
+@functools.lru_cache(maxsize=None)
+def hits_of(name, width, height, spp, crop=None, seed=0):
+    """(tri (pixels, spp), emit (pixels, spp) bool, kd, ke (pixels, spp, 3), (rows, columns)) of the oracle's primary rays; kd / ke of a
+    miss are those of triangle 0 and must not be used"""
+    _, _, _, tri, shape = aov.primary_rays(name, width, height, spp, crop, seed)
+    tris = util.oracle_scene(name).tris()
+    ti = np.maximum(tri, 0)
+    emit = (tri >= 0) & (tris["has_emit"][ti] != 0)
+    return tri, emit, tris["kd"][ti].astype(F), tris["ke"][ti].astype(F), shape
+
+
+@functools.lru_cache(maxsize=None)
+def expected_shading(name, width, height, spp, crop=None, seed=0):
+    """The contract of include/crt.h, restated in numpy float32 on the oracle's primary rays: {emission, diffuse_albedo} (rows, columns, 3)"""
+    tri, emit, kd, ke, (ch, cw) = hits_of(name, width, height, spp, crop, seed)
+    p = tri.shape[0]
+    e = np.zeros((p, 3), dtype=F)
+    b = np.zeros((p, 3), dtype=F)
+    fs = F(spp)
+    for k in range(spp):
+        hit = tri[:, k] >= 0
+        e = np.where(emit[:, k, None], e + ke[:, k] / fs, e)
+        b = np.where((hit & ~emit[:, k])[:, None], b + kd[:, k] / fs, b)
+    assert e.dtype == F and b.dtype == F
+    return {"emission": e.reshape(ch, cw, 3), "diffuse_albedo": b.reshape(ch, cw, 3)}
+
+
+def classes_of(name, width, height, spp, crop=None):
+    """How many pixels of the frame are of each kind the resolve treats differently"""
+    tri, emit, kd, _, _ = hits_of(name, width, height, spp, crop)
+    hit = tri >= 0
+    n_hit, n_emit = hit.sum(axis=1), emit.sum(axis=1)
+    zero_kd = hit & ~emit & (kd == 0).any(axis=2)
+    return {"all_emitter": int(((n_emit == spp)).sum()), "mixed": int(((n_emit > 0) & (n_emit < n_hit)).sum()),
+            "no_hit": int((n_hit == 0).sum()), "partly_covered": int(((n_hit > 0) & (n_hit < spp)).sum()),
+            "zero_kd_channel": int(zero_kd.any(axis=1).sum())}
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_shading_entry_points_are_exported():
+    lib = capi.lib()
+    for name in SHADING_EXPORTS:
+        assert name in capi.EXPORTS
+        getattr(lib, name)
+    assert tuple(capi.AOV_SHADING_BUFFERS) == NAMES
+    assert tuple(capi.AOV_BUFFERS) == aov.NAMES  # (unchanged)
+    assert hasattr(crt.Render, "run_view_aov_shading") and hasattr(crt.Render, "run_view_aov_shading_device")
+    assert lib.crt_abi_version() == 5
+
+
+def test_shading_arguments_are_checked_before_any_device_call():
+    """Every invalid call is CRT_ERR_INVALID_ARG, also on a machine without a GPU.  A non-null scene here is a dummy that must never be
+    dereferenced."""
+    lib = capi.lib()
+    dummy = C.create_string_buffer(256)
+    sc = C.cast(dummy, C.c_void_p)
+    cam = capi.Camera()
+    good = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+    buf = np.zeros(64 * 48 * 3, dtype=np.float32)
+    sh = capi.AovShadingBuffers()
+    sh.emission = buf.ctypes.data
+    first = capi.AovBuffers()
+    first.albedo = buf.ctypes.data
+    no_sh, no_first = capi.AovShadingBuffers(), capi.AovBuffers()
+
+    def both(scene, camera, prm, f, s):
+        r1 = lib.crt_render_aov_shading(scene, camera, prm, f, s, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_render_aov_shading_device(scene, camera, prm, f, s, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == capi.ERR_INVALID_ARG, (r1, r2, e1, e2)
+        return e1
+
+    for f in (None, C.byref(first)):
+        assert b"null" in both(None, C.byref(cam), C.byref(good), f, C.byref(sh))
+        assert b"null" in both(sc, None, C.byref(good), f, C.byref(sh))
+        assert b"null" in both(sc, C.byref(cam), None, f, C.byref(sh))
+        assert b"null" in both(sc, C.byref(cam), C.byref(good), f, None)
+        assert b"no output" in both(sc, C.byref(cam), C.byref(good), f, C.byref(no_sh))
+        for field, value in (("spp", 0), ("width", 0), ("height", 0)):
+            p = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+            setattr(p, field, value)
+            both(sc, C.byref(cam), C.byref(p), f, C.byref(sh))
+        bad_shard = capi.Params(64, 48, 4, 0.6, 1, 0, 3, 3, capi.TRAVERSAL_EXACT, capi.FLAG_TILED_OUTPUT)
+        both(sc, C.byref(cam), C.byref(bad_shard), f, C.byref(sh))
+        untiled = capi.Params(64, 48, 4, 0.6, 1, 0, 1, 3, capi.TRAVERSAL_EXACT, 0)
+        both(sc, C.byref(cam), C.byref(untiled), f, C.byref(sh))
+        bad_mode = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, 7, 0)
+        both(sc, C.byref(cam), C.byref(bad_mode), f, C.byref(sh))
+    assert b"no output" in both(sc, C.byref(cam), C.byref(good), C.byref(no_first), C.byref(sh))
+
+
+def test_multi_render_refuses_the_shading_pass():
+    for method in ("run_view_aov_shading", "run_view_aov_shading_device"):
+        with pytest.raises(NotImplementedError):
+            getattr(crt.MultiRender, method)(None)
+
+
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_radiance_factors_into_emission_and_albedo_on_the_oracle(name):
+    """64 x 48 spp 4, the oracle's frame and per-sample radiance: a sample whose camera ray hits an emitter has ke's bits; frame - E is
+    exactly +0 wherever A is 0; and (frame - E) / A, the irradiance demodulate() returns, is finite and not negative."""
+    w, h, spp = 64, 48, 4
+    t = util.task(name)
+    eye, iv, fov = util.camera(name)
+    _, frame, L, _ = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n, want_L=True)
+    tri, emit, _, ke, _ = hits_of(name, w, h, spp)
+    assert emit.any() and (~emit & (tri >= 0)).any()
+    L = L.reshape(w * h, spp, 3)
+    util.assert_bits(L[emit], ke[emit], "%s: radiance of the samples that hit an emitter" % name)
+    want = expected_shading(name, w, h, spp)
+    E, A = want["emission"], want["diffuse_albedo"]
+    all_emit = emit.all(axis=1).reshape(h, w)
+    assert all_emit.any()
+    util.assert_bits(frame[all_emit], E[all_emit], "%s: frame at the pixels all of whose samples hit emitters" % name)
+    d = frame - E
+    assert d.dtype == F and (A == 0).any()
+    assert (util.bits(d[A == 0]) == 0).all(), "%s: frame - E is not +0 where A is 0" % name
+    with np.errstate(all="ignore"):
+        irr = np.where(A > 0, d / A, d)
+    assert np.isfinite(irr).all() and (irr >= 0).all(), (name, float(irr.min()), float(irr.max()))
+    print("%s: irradiance in [%g, %g]" % (name, float(irr.min()), float(irr.max())))
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in SCENE_NAMES:
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+def assert_same(got, want, where=""):
+    for n in NAMES + aov.NAMES:
+        if n not in want:
+            continue
+        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
+        assert g.shape == w.shape and g.dtype == w.dtype, (n, g.shape, w.shape)
+        same = g.view(np.uint32) == w.view(np.uint32)
+        assert same.all(), "%s %s: %d of %d values differ (first at %r)" % (where, n, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+
+
+def run_shading(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0, **kw):
+    eye, iv, fov = util.camera(name)
+    r.set_spp(spp)
+    r.seed = seed
+    r.traversal = traversal
+    try:
+        return r.run_view_aov_shading(eye, iv, fov, width=width, height=height, **kw)
+    finally:
+        r.traversal = crt.TRAVERSAL_EXACT
+        r.seed = 0
+
+
+def check_small_frame(renders, name, traversal):
+    got = run_shading(renders[name], name, 4, 64, 48, traversal=traversal, first=aov.NAMES)
+    assert renders[name].aov_info["chunks"] == 1 and renders[name].aov_info["rays"] == 64 * 48 * 4
+    assert_same(got, expected_shading(name, 64, 48, 4), name)
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("traversal", [crt.TRAVERSAL_EXACT, crt.TRAVERSAL_REFERENCE], ids=["exact", "reference"])
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_shading_small_frames_match_oracle(renders, name, traversal):
+    """64 x 48 spp 4.  The frame has every kind of pixel: all samples on emitters, emitter and non-emitter samples, no hit, partly
+    covered -- and, on cornell-box, hits on a surface with a zero kd channel."""
+    k = classes_of(name, 64, 48, 4)
+    print(name, k)
+    if name == "cornell-box":
+        assert (k["all_emitter"], k["mixed"], k["no_hit"], k["partly_covered"]) == (11, 6, 851, 115) and k["zero_kd_channel"] > 0
+    else:
+        assert (k["all_emitter"], k["mixed"]) == (33, 17)
+    got = check_small_frame(renders, name, traversal)
+    # the same trace also serves crt_render_aov's struct: its six buffers have that call's bits
+    assert_same(got, aov.run_aov(renders[name], name, 4, 64, 48, traversal=traversal), "%s first" % name)
+    aov.assert_same(got, aov.expected_aov(name, 64, 48, 4), "%s first against the oracle" % name)
+    # where no sample hits an emitter the split changes nothing
+    _, emit, _, _, _ = hits_of(name, 64, 48, 4)
+    quiet = ~emit.any(axis=1).reshape(48, 64)
+    assert quiet.any() and not quiet.all()
+    assert (util.bits(got["diffuse_albedo"][quiet]) == util.bits(got["albedo"][quiet])).all()
+    assert (util.bits(got["emission"][quiet]) == 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_shading_on_the_fallback_pipeline(renders, name, monkeypatch):
+    monkeypatch.setenv("CRT_PIPELINE", "2")
+    check_small_frame(renders, name, crt.TRAVERSAL_EXACT)
+
+
+@pytest.mark.gpu
+def test_shading_fast_traversal_and_a_subset_of_the_buffers(renders):
+    name = "veach-mis"
+    want = expected_shading(name, 64, 48, 4)
+    got = run_shading(renders[name], name, 4, 64, 48, traversal=crt.TRAVERSAL_FAST)
+    assert_same(got, want, "fast")
+    for n in NAMES:  # one buffer alone, without `first`
+        got = run_shading(renders[name], name, 4, 64, 48, want=(n,))
+        assert tuple(got) == (n,)
+        assert_same(got, {n: want[n]}, "only " + n)
+
+
+@pytest.mark.gpu
+def test_shading_tiled_shard_with_padding_slots(renders):
+    """61 x 47 as rank 1 of 3: 8 x 6 tiles, ragged in both directions; the shard's 16 tiles of 64 slots, padding slots 0."""
+    name, w, h, rank, world, spp = "cornell-box", 61, 47, 1, 3, 4
+    r = renders[name]
+    want = expected_shading(name, w, h, spp)
+    assert (want["emission"] != 0).any()
+    eye, iv, fov = util.camera(name)
+    r.set_spp(spp)
+    cam = r._cam(eye, iv, fov)
+    slots = crt.shard_slots(w, h, rank, world)
+    bufs, fbufs, arrs = capi.AovShadingBuffers(), capi.AovBuffers(), {}
+    for n in NAMES + ("albedo", "tri"):
+        ch, dt = (capi.AOV_SHADING_BUFFERS if n in NAMES else capi.AOV_BUFFERS)[n]
+        arrs[n] = np.full((slots, ch), 7, dtype=dt)  # (padding slots must come back as 0 / -1)
+        setattr(bufs if n in NAMES else fbufs, n, arrs[n].ctypes.data)
+    prm = r._params(rank=rank, world=world, flags=capi.FLAG_TILED_OUTPUT, width=w, height=h)
+    info = capi.AovInfo()
+    capi.check(capi.lib().crt_render_aov_shading(r._h, C.byref(cam), C.byref(prm), C.byref(fbufs), C.byref(bufs), C.byref(info)), "crt_render_aov_shading")
+    assert info.rays == slots * spp and info.chunks == 1
+    tx, ty = (w + 7) // 8, (h + 7) // 8
+    expect = {n: np.zeros((slots, 3), dtype=F) for n in NAMES}
+    pixels = padding = 0
+    for s in range(slots):
+        tile = (s // 64) * world + rank
+        i, j = (tile % tx) * 8 + (s % 64) % 8, (tile // tx) * 8 + (s % 64) // 8
+        if tile < tx * ty and i < w and j < h:
+            pixels += 1
+            for n in NAMES:
+                expect[n][s] = want[n][j, i]
+        else:
+            padding += 1
+            assert (arrs["albedo"][s] == 0).all() and arrs["tri"][s] == -1
+    assert pixels > 0 and padding > 0
+    for n in NAMES:
+        assert (util.bits(arrs[n]) == util.bits(expect[n])).all(), n
+
+
+@functools.lru_cache(maxsize=None)
+def emitter_crop(name):
+    """A 24 x 16 crop of the 800 x 600 frame around the first pixel of the 64 x 48 one (a pixel there is 12.5 here) that has samples on
+    an emitter and samples beside it: the edge of a light"""
+    tri, emit, _, _, _ = hits_of(name, 64, 48, 4)
+    n_emit = emit.sum(axis=1)
+    ys, xs = np.nonzero(((n_emit > 0) & (n_emit < (tri >= 0).sum(axis=1))).reshape(48, 64))
+    cx, cy = int(xs[0] * 12.5 + 6), int(ys[0] * 12.5 + 6)
+    return (min(max(cx - 12, 0), 800 - 24), min(max(cy - 8, 0), 600 - 16), 24, 16)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", SCENE_NAMES)
+def test_shading_crop_of_full_camera_in_chunks(renders, name):
+    """800 x 600 at spp 160: more camera rays than a chunk's 2^25, so the six extra running sums cross a chunk border in the fourth
+    accumulator row.  The crop lies on a light."""
+    spp = 160
+    x0, y0, cw, ch = emitter_crop(name)
+    want = expected_shading(name, 800, 600, spp, crop=(x0, y0, cw, ch))
+    lit = (want["emission"] != 0).any(axis=2)
+    assert lit.any() and not lit.all(), "the crop at (%d, %d) shows %d emitter pixels" % (x0, y0, int(lit.sum()))
+    got = run_shading(renders[name], name, spp, first=("albedo", "depth", "tri"))
+    info = renders[name].aov_info
+    assert info["chunks"] >= 2 and info["rays"] == 800 * 600 * spp, info
+    crop = {n: got[n][y0:y0 + ch, x0:x0 + cw] for n in got}
+    assert_same(crop, want, name)
+    aov.assert_same(crop, {n: v for n, v in aov.expected_aov(name, 800, 600, spp, crop=(x0, y0, cw, ch)).items() if n in crop}, name + " first")
+
+
+@pytest.mark.gpu
+def test_shading_device_form_on_a_stream_matches_host_form(renders):
+    name, w, h = "veach-mis", 80, 56
+    r = renders[name]
+    want = run_shading(r, name, 3, w, h, first=("normal", "material"))
+    assert (want["emission"] != 0).any()
+    eye, iv, fov = util.camera(name)
+    H = aov.hip_runtime()
+    tables = dict(capi.AOV_BUFFERS, **capi.AOV_SHADING_BUFFERS)
+    ptrs, sizes = {}, {}
+    stream = C.c_void_p()
+    try:
+        for n in want:
+            sizes[n] = w * h * tables[n][0] * 4
+            p = C.c_void_p()
+            assert H.hipMalloc(C.byref(p), sizes[n]) == 0
+            ptrs[n] = p.value
+            assert H.hipMemset(p, 0x55, sizes[n]) == 0  # (every value must be written by the pass)
+        assert H.hipStreamCreate(C.byref(stream)) == 0
+        r.set_spp(3)
+        assert r.run_view_aov_shading_device(eye, iv, fov, {n: ptrs[n] for n in NAMES}, first_ptrs={n: ptrs[n] for n in ("normal", "material")},
+                                             stream=stream.value, want_info=False, width=w, height=h) is None
+        assert H.hipStreamSynchronize(stream) == 0
+
+        def fetch(names):
+            out = {}
+            for n in names:
+                ch, dt = tables[n]
+                a = np.zeros((h, w, ch) if ch == 3 else (h, w), dtype=dt)
+                assert H.hipMemcpy(a.ctypes.data, ptrs[n], sizes[n], 2) == 0  # hipMemcpyDeviceToHost
+                out[n] = a
+            return out
+
+        assert_same(fetch(want), want, "device form")
+        # one buffer, no `first`, with the pass's timer (the call synchronizes the stream)
+        assert H.hipMemset(C.c_void_p(ptrs["emission"]), 0, sizes["emission"]) == 0
+        info = r.run_view_aov_shading_device(eye, iv, fov, {"emission": ptrs["emission"]}, stream=stream.value, width=w, height=h)
+        assert info["chunks"] == 1 and info["rays"] == w * h * 3 and info["total_ms"] > 0
+        assert_same(fetch(["emission"]), {"emission": want["emission"]}, "subset")
+        with pytest.raises(ValueError):
+            r.run_view_aov_shading_device(eye, iv, fov, {"albedo": ptrs["emission"]}, width=w, height=h)
+    finally:
+        if stream.value:
+            H.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_shading_files(renders, tmp_path):
+    from cudaraytracing_amd import build as b
+    cli = b.build_cli()
+    prefix = str(tmp_path / "veach")
+    cfg = util.SCENES["veach-mis"]
+    res = subprocess.run([cli, cfg, "-o", prefix + ".png", "--spp", "2", "--width", "96", "--height", "72", "--seed", "42", "--base-dir", util.ROOT,
+                          "--aov-shading", prefix], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    got = run_shading(renders["veach-mis"], "veach-mis", 2, 96, 72, seed=42)
+    assert (got["emission"] != 0).any()
+    for n in NAMES:
+        hdr, a = aov.read_pfm("%s.%s.pfm" % (prefix, n))
+        assert hdr[0] == b"PF" and hdr[2] == b"-1.0"
+        assert (util.bits(a) == util.bits(got[n])).all(), n
+    bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--aov-shading", prefix], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--aov-shading" in bad.stderr

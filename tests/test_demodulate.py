@@ -1,0 +1,502 @@
+"""Albedo demodulation (crt_demodulate / crt_modulate and their _device forms, include/crt.h; demodulate, modulate,
+Render.run_view_denoised(demodulate=True) and Render.run_view_temporal(demodulate=True) in Python; crt_cli --demodulate).
+
+The contract of include/crt.h is restated below in numpy float32, one ufunc per operation, with the oracle's tone map; the device
+result must match it bit for bit (uint32 views; where the expected value is NaN the result must be NaN).
+"""
+import ctypes as C
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import test_aov as aov
+import test_temporal as T
+import util
+
+F = np.float32
+MODULATE_EXPORTS = ("crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate", "crt_modulate_device")
+assert_bits = util.assert_bits
+
+
+def restated_demodulate(color, albedo, emission=None, variance=None, albedo_floor=0.0):
+    """irradiance, or (irradiance, variance) with a variance: every ufunc is one IEEE fp32 operation per element"""
+    color, albedo = np.asarray(color, dtype=F), np.asarray(albedo, dtype=F)
+    with np.errstate(all="ignore"):
+        use = albedo > F(albedo_floor)
+        d = color - np.asarray(emission, dtype=F) if emission is not None else color
+        irr = np.where(use, d / albedo, d)
+        assert irr.dtype == F
+        if variance is None:
+            return irr
+        variance = np.asarray(variance, dtype=F)
+        return irr, np.where(use, variance / (albedo * albedo), variance)
+
+
+def restated_modulate(irradiance, albedo, emission=None, albedo_floor=0.0, before_emission=False):
+    """(rgb, mean); before_emission: m, the value before the final add"""
+    irradiance, albedo = np.asarray(irradiance, dtype=F), np.asarray(albedo, dtype=F)
+    with np.errstate(all="ignore"):
+        m = np.where(albedo > F(albedo_floor), irradiance * albedo, irradiance)
+        if before_emission:
+            return m
+        c = m + np.asarray(emission, dtype=F) if emission is not None else m
+    assert c.dtype == F
+    return O.tonemap(c), c
+
+
+def synthetic(w, h, seed, albedo_floor=0.0):
+    """colour, albedo, emission, variance (h, w, 3) with every special value the contract speaks of sprinkled in"""
+    rng = np.random.default_rng(seed)
+    n = h * w * 3
+    color = (rng.random(n) * 40).astype(F)
+    albedo = (rng.random(n) * 0.9 + 0.05).astype(F)
+    emission = np.where(rng.random(n) < 0.2, rng.random(n) * 300, 0).astype(F)
+    variance = (rng.random(n) * 3).astype(F)
+    special = np.array([0.0, -0.0, -0.5, np.nan, np.inf, -np.inf, albedo_floor, 1e-30, 1e30], dtype=F)
+    for k, a in enumerate((albedo, color, emission, variance)):
+        idx = rng.permutation(n)[:max(9, n // 6)]
+        a[idx] = special[(np.arange(idx.size) + k) % special.size]
+    return tuple(a.reshape(h, w, 3) for a in (color, albedo, emission, variance))
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_modulate_entry_points_are_exported():
+    lib = capi.lib()
+    for name in MODULATE_EXPORTS:
+        assert name in capi.EXPORTS
+        getattr(lib, name)
+    for name in ("demodulate", "modulate", "demodulate_device", "modulate_device", "modulate_defaults"):
+        assert hasattr(crt, name) and name in crt.__all__
+    assert crt.modulate_defaults() == {"albedo_floor": 0.0}
+    p = capi.ModulateParams(3, 4, 7.0)
+    assert lib.crt_modulate_defaults(C.byref(p)) == 0 and (p.width, p.height, p.albedo_floor) == (0, 0, 0.0)
+    assert lib.crt_modulate_defaults(None) == capi.ERR_INVALID_ARG
+
+
+def test_modulate_arguments_are_checked_before_any_device_call():
+    """Every invalid call is CRT_ERR_INVALID_ARG, also on a machine without a GPU: the arguments are checked first (the pointers here
+    are host memory that a device call would fault on)."""
+    lib = capi.lib()
+    buf = np.zeros(8 * 6 * 3, dtype=np.float32)
+    d = buf.ctypes.data
+
+    def params(**over):
+        p = capi.ModulateParams(8, 6, 0.0)
+        for k, v in over.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    def demod(prm, color=d, albedo=d, emission=d, variance=d, out=d, out_variance=d):
+        r1 = lib.crt_demodulate(0, prm, color, albedo, emission, variance, out, out_variance, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_demodulate_device(0, prm, color, albedo, emission, variance, out, out_variance, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == capi.ERR_INVALID_ARG, (r1, r2, e1, e2)
+        return e1
+
+    def mod(prm, irradiance=d, albedo=d, emission=d, mean=d, rgb=d):
+        r1 = lib.crt_modulate(0, prm, irradiance, albedo, emission, mean, rgb, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_modulate_device(0, prm, irradiance, albedo, emission, mean, rgb, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == capi.ERR_INVALID_ARG, (r1, r2, e1, e2)
+        return e1
+
+    for call in (demod, mod):
+        assert b"null" in call(None)
+        assert b"null" in call(params(), None)
+        assert b"null" in call(params(), d, None)
+        assert b"positive" in call(params(width=0))
+        assert b"positive" in call(params(height=0))
+        for floor in (-0.25, float("nan"), float("-inf")):
+            assert b"albedo_floor" in call(params(albedo_floor=floor))
+    assert b"null output" in demod(params(), out=None)
+    assert b"together" in demod(params(), variance=None)
+    assert b"together" in demod(params(), out_variance=None)
+    assert b"no output" in mod(params(), mean=None, rgb=None)
+
+
+def test_python_validates_shapes():
+    good = np.zeros((5, 7, 3), dtype=F)
+    with pytest.raises(ValueError):
+        crt.demodulate(np.zeros((5, 7), dtype=F), good)
+    with pytest.raises(ValueError):
+        crt.demodulate(good, None)
+    for bad in (np.zeros((5, 7), dtype=F), np.zeros((7, 5, 3), dtype=F), np.zeros((5, 7, 1), dtype=F)):
+        with pytest.raises(ValueError):
+            crt.demodulate(good, bad)
+        with pytest.raises(ValueError):
+            crt.demodulate(good, good, emission=bad)
+        with pytest.raises(ValueError):
+            crt.demodulate(good, good, variance=bad)
+        with pytest.raises(ValueError):
+            crt.modulate(good, bad)
+        with pytest.raises(ValueError):
+            crt.modulate(good, good, emission=bad)
+    with pytest.raises(ValueError):
+        crt.modulate(np.zeros((5, 7, 4), dtype=F), good)
+    with pytest.raises(ValueError):
+        crt.modulate(good, None)
+
+
+def test_multi_render_refuses_demodulation():
+    for method in ("run_view_denoised", "run_view_temporal"):
+        with pytest.raises(NotImplementedError):
+            getattr(crt.MultiRender, method)(None, demodulate=True)
+
+
+def ulp_distance(a, b):
+    """of finite float32 values of one sign, on their ordered-integer views"""
+    return np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))
+
+
+@pytest.mark.parametrize("albedo_floor", [0.0, 0.01])
+def test_restatement_round_trip(albedo_floor):
+    """modulate(demodulate(x)): where the albedo is used, m = (d / a) * a is within 2 ulp of d = x - E.  The quotient q is correctly
+    rounded, |q - d / a| <= ulp(q) / 2 <= 2^-24 q, which the product carries to at most 2^-24 d: one ulp of d at the top of its binade.
+    The product's own rounding adds half an ulp of m.  Where the albedo is not used the pair is the identity, bit for bit."""
+    rng = np.random.default_rng(11)
+    shape = (37, 53, 3)
+    x = (rng.random(shape) * 50 + 0.5).astype(F)
+    a = np.where(rng.random(shape) < 0.3, rng.random(shape) * albedo_floor, rng.random(shape) * 0.9 + 0.05).astype(F)
+    a[rng.random(shape) < 0.05] = albedo_floor
+    e = np.where(rng.random(shape) < 0.2, x * F(0.5), 0).astype(F)
+    use = a > F(albedo_floor)
+    assert use.any() and (~use).any()
+    irr = restated_demodulate(x, a, e, albedo_floor=albedo_floor)
+    m = restated_modulate(irr, a, e, albedo_floor=albedo_floor, before_emission=True)
+    d = x - e
+    assert (d > 0).all() and (m > 0).all()
+    dist = ulp_distance(m, d)
+    print("floor %g: largest distance %d ulp" % (albedo_floor, int(dist[use].max())))
+    assert dist[use].max() <= 2
+    # without `use`: the value passes through both ways; without emission the pair is then the identity
+    assert (util.bits(m[~use]) == util.bits(d[~use])).all()
+    a0 = np.full(shape, albedo_floor, dtype=F)
+    _, back = restated_modulate(restated_demodulate(x, a0, albedo_floor=albedo_floor), a0, albedo_floor=albedo_floor)
+    assert (util.bits(back) == util.bits(x)).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in ("cornell-box", "veach-mis"):
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+GUIDES = ("albedo", "normal", "depth")
+_frames = {}
+
+
+def frame_of(renders, name, width, height, spp, seed=0, cam=None, variance=True):
+    """A GPU render (with its variance) and the shading pass with the guides from the same trace, rendered once per module:
+    {rgb, color, variance, emission, diffuse_albedo, albedo, normal, depth, material}"""
+    key = (name, width, height, spp, seed, None if cam is None else tuple(np.asarray(cam[0], dtype=F)), variance)
+    if key not in _frames:
+        r = renders[name]
+        cam_ = cam if cam is not None else util.camera(name)
+        r.set_spp(spp)
+        r.seed = seed
+        try:
+            rgb = r.run_view(*cam_, width=width, height=height, want_variance=variance).copy()
+            out = {"rgb": rgb, "color": r.mean_buffer.copy(), "variance": r.variance_buffer.copy() if variance else None}
+            out.update(r.run_view_aov_shading(*cam_, first=GUIDES + ("material",), width=width, height=height))
+        finally:
+            r.seed = 0
+        _frames[key] = out
+    return _frames[key]
+
+
+def check_pair(color, albedo, emission, variance, albedo_floor, where):
+    """demodulate and modulate of the host forms against the restatement; returns the irradiance"""
+    want = restated_demodulate(color, albedo, emission, variance, albedo_floor)
+    got = crt.demodulate(color, albedo, emission, variance, albedo_floor=albedo_floor)
+    if variance is None:
+        want, got = (want,), (got,)
+    assert_bits(got[0], want[0], where + " irradiance")
+    if variance is not None:
+        assert_bits(got[1], want[1], where + " variance")
+    want_rgb, want_mean = restated_modulate(want[0], albedo, emission, albedo_floor)
+    rgb, mean = crt.modulate(want[0], albedo, emission, albedo_floor=albedo_floor)
+    assert_bits(mean, want_mean, where + " mean")
+    assert np.array_equal(rgb, want_rgb), where + " rgb"
+    rgb2, mean2 = crt.modulate(want[0], albedo, emission, albedo_floor=albedo_floor, want_rgb=False)
+    assert rgb2 is None
+    assert_bits(mean2, want_mean, where + " mean alone")
+    return want[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_rendered_frames_match_restatement(renders, name):
+    f = frame_of(renders, name, 64, 48, 4)
+    assert (f["emission"] != 0).any() and (f["diffuse_albedo"] == 0).any()
+    irr = check_pair(f["color"], f["diffuse_albedo"], f["emission"], f["variance"], 0.0, name)
+    # what the factorisation promises of a device frame as well
+    assert np.isfinite(irr).all() and (irr >= 0).all()
+    # and the round trip gives the frame back to within 2 ulp of (frame - E) before the final add
+    m = restated_modulate(irr, f["diffuse_albedo"], albedo_floor=0.0, before_emission=True)
+    d = f["color"] - f["emission"]
+    use = (f["diffuse_albedo"] > 0) & (d > 0)
+    assert ulp_distance(m[use], d[use]).max() <= 2
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(7, 5), (61, 47), (130, 9)])
+@pytest.mark.parametrize("albedo_floor", [0.0, 0.125])
+def test_synthetic_inputs_match_restatement(size, albedo_floor):
+    """105, 8601 and 3510 components: a tail of 1, 1 and 2 after the last whole quad; albedo 0, negative, NaN, +-inf and exactly the
+    floor; NaN and +-inf in colour, emission and variance"""
+    w, h = size
+    assert (w * h * 3) % 4 != 0
+    color, albedo, emission, variance = synthetic(w, h, w * h, albedo_floor)
+    assert (albedo == F(albedo_floor)).any() and np.isnan(albedo).any() and np.isinf(albedo).any() and (albedo < 0).any()
+    assert np.isnan(color).any() and np.isinf(emission).any()
+    where = "%dx%d floor %g" % (w, h, albedo_floor)
+    check_pair(color, albedo, emission, variance, albedo_floor, where)
+    check_pair(color, albedo, None, variance, albedo_floor, where + " no emission")
+    check_pair(color, albedo, emission, None, albedo_floor, where + " no variance")
+    check_pair(color, albedo, None, None, albedo_floor, where + " neither")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "one float in"])
+def test_device_forms_on_a_stream(offset):
+    """The device forms on a non-default stream without info; then every base pointer one float (out_rgb: one byte) in, which takes
+    the same data through the component-by-component path."""
+    w, h, floor = 61, 47, 0.125
+    n = w * h * 3
+    color, albedo, emission, variance = synthetic(w, h, 5, floor)
+    want_irr, want_var = restated_demodulate(color, albedo, emission, variance, floor)
+    want_rgb, want_mean = restated_modulate(want_irr, albedo, emission, floor)
+    H = aov.hip_runtime()
+    names = ("color", "albedo", "emission", "variance", "irr", "ivar", "mean", "rgb")
+    ptrs = {}
+    stream = C.c_void_p()
+    try:
+        for k in names:
+            p = C.c_void_p()
+            assert H.hipMalloc(C.byref(p), (n + 4) * 4) == 0
+            assert H.hipMemset(p, 0x55, (n + 4) * 4) == 0
+            ptrs[k] = p.value
+        at = {k: ptrs[k] + (offset if k == "rgb" else 4 * offset) for k in names}
+        for k, a in (("color", color), ("albedo", albedo), ("emission", emission), ("variance", variance)):
+            assert H.hipMemcpy(C.c_void_p(at[k]), a.ctypes.data, n * 4, 1) == 0  # hipMemcpyHostToDevice
+        assert H.hipStreamCreate(C.byref(stream)) == 0
+        assert crt.demodulate_device(w, h, at["color"], at["albedo"], at["irr"], emission_ptr=at["emission"], variance_ptr=at["variance"],
+                                     out_variance_ptr=at["ivar"], albedo_floor=floor, stream=stream.value, want_info=False) is None
+        assert crt.modulate_device(w, h, at["irr"], at["albedo"], at["mean"], out_rgb_ptr=at["rgb"], emission_ptr=at["emission"], albedo_floor=floor,
+                                   stream=stream.value, want_info=False) is None
+        assert H.hipStreamSynchronize(stream) == 0
+
+        def fetch(k, dtype=F):
+            a = np.zeros((h, w, 3), dtype=dtype)
+            assert H.hipMemcpy(a.ctypes.data, C.c_void_p(at[k]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+            return a
+
+        assert_bits(fetch("irr"), want_irr, "device irradiance")
+        assert_bits(fetch("ivar"), want_var, "device variance")
+        assert_bits(fetch("mean"), want_mean, "device mean")
+        assert np.array_equal(fetch("rgb", np.uint8), want_rgb)
+        # nothing written past either end of an output
+        edge = np.zeros(n + 4, dtype=np.uint32)
+        for k in ("irr", "ivar", "mean"):
+            assert H.hipMemcpy(edge.ctypes.data, C.c_void_p(ptrs[k]), edge.nbytes, 2) == 0
+            assert (edge[:offset] == 0x55555555).all() and (edge[offset + n:] == 0x55555555).all(), k
+        # NULL emission and variance, one output of modulate, with the timer (the calls synchronize the stream)
+        info = crt.demodulate_device(w, h, at["color"], at["albedo"], at["irr"], albedo_floor=floor, stream=stream.value)
+        assert info["total_ms"] > 0
+        irr2 = restated_demodulate(color, albedo, albedo_floor=floor)
+        assert_bits(fetch("irr"), irr2, "device irradiance, no emission")
+        info = crt.modulate_device(w, h, at["irr"], at["albedo"], None, out_rgb_ptr=at["rgb"], albedo_floor=floor, stream=stream.value)
+        assert info["total_ms"] > 0
+        assert np.array_equal(fetch("rgb", np.uint8), restated_modulate(irr2, albedo, albedo_floor=floor)[0])
+        assert_bits(fetch("mean"), want_mean, "device mean untouched")
+    finally:
+        if stream.value:
+            H.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+# ---- the chain ----
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variance_guided", [False, True], ids=["plain", "variance-guided"])
+def test_run_view_denoised_demodulated_equals_the_pieces_by_hand(renders, variance_guided):
+    name, w, h = "veach-mis", 96, 72
+    r = renders[name]
+    f = frame_of(renders, name, w, h, 4)
+    g = {k: f[k] for k in GUIDES}
+    E, A = f["emission"], f["diffuse_albedo"]
+    settings = dict(sigma_color=8.0, sigma_albedo=float("inf"))
+    if variance_guided:
+        irr, ivar = crt.demodulate(f["color"], A, E, f["variance"])
+        _, den = crt.denoise_var(irr, ivar, want_rgb=False, **settings, **g)
+    else:
+        _, den = crt.denoise(crt.demodulate(f["color"], A, E), want_rgb=False, **settings, **g)
+    want_rgb, want_mean = crt.modulate(den, A, E)
+    r.set_spp(4)
+    eye, iv, fov = util.camera(name)
+    rgb, mean = r.run_view_denoised(eye, iv, fov, width=w, height=h, variance_guided=variance_guided, demodulate=True, **settings)
+    assert_bits(mean, want_mean, "run_view_denoised(demodulate=True)")
+    assert np.array_equal(rgb, want_rgb)
+    assert np.array_equal(r.frame_buffer, f["rgb"]) and r.denoise_info["passes"] == 3
+    for k in ("emission", "diffuse_albedo"):
+        assert_bits(r.shading_buffers[k], f[k], k)
+    for k in GUIDES:
+        assert_bits(r.aov_buffers[k], f[k], k)
+    # the switch is off by default, and off is what it was
+    rgb0, mean0 = r.run_view_denoised(eye, iv, fov, width=w, height=h, variance_guided=variance_guided, **settings)
+    want0 = (crt.denoise_var(f["color"], f["variance"], **settings, **g) if variance_guided else crt.denoise(f["color"], **settings, **g))
+    assert_bits(mean0, want0[1], "run_view_denoised")
+    assert np.array_equal(rgb0, want0[0]) and not np.array_equal(rgb0, rgb)
+
+
+@pytest.mark.gpu
+def test_run_view_temporal_demodulated_equals_the_pieces_by_hand(renders):
+    """Three frames of a moving camera with the clamp: the history holds irradiance, what comes back is modulated with the current
+    frame's buffers; then the flag's change starts a history."""
+    name, w, h = "cornell-box", 64, 48
+    r = renders[name]
+    cams = [T.camera_at(name, f) for f in range(3)]
+    frames = [frame_of(renders, name, w, h, 4, seed=40 + f, cam=cams[f]) for f in range(3)]  # seeds 40, 41, 42: self.seed + the frames since the reset
+    r.set_spp(4)
+    r.seed = 40
+    try:
+        r.reset_temporal()
+        prev = pcam = None
+        for f in range(3):
+            cam, fr = cams[f], frames[f]
+            E, A = fr["emission"], fr["diffuse_albedo"]
+            irr, ivar = crt.demodulate(fr["color"], A, E, fr["variance"])
+            cur = {"color": irr, "variance": ivar, "depth": fr["depth"], "normal": fr["normal"], "id": fr["material"]}
+            _, want_c, want_v, want_h, want_info = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, clamp=True, want_rgb=False, return_info=True)
+            prev, pcam = dict(cur, color=want_c, variance=want_v, history=want_h), cam
+            rgb, mean = r.run_view_temporal(*cam, width=w, height=h, clamp=True, demodulate=True, denoise=(f == 2))
+            if f == 2:
+                _, den = crt.denoise_var(want_c, want_v, want_rgb=False, **{k: fr[k] for k in GUIDES})
+                want_rgb, want_mean = crt.modulate(den, A, E)
+            else:
+                want_rgb, want_mean = crt.modulate(want_c, A, E)
+            assert_bits(mean, want_mean, "run_view_temporal(demodulate=True) frame %d" % f)
+            assert np.array_equal(rgb, want_rgb)
+            assert_bits(r.variance_buffer, want_v, "variance_buffer")
+            assert_bits(r.temporal_history_buffer, want_h, "temporal_history_buffer")
+            assert r.temporal_info["reprojected"] == want_info["reprojected"] and r.temporal_info["clamped"] == want_info["clamped"]
+            assert np.array_equal(r.frame_buffer, fr["rgb"]) and r.seed == 40
+        assert r.temporal_info["reprojected"] >= 100
+        # a change of the flag starts a history: a first frame (rendered with the seed after the three so far), each way
+        cam = T.camera_at(name, 1)
+        r.run_view_temporal(*cam, width=w, height=h, clamp=True)
+        assert (r.temporal_history_buffer == 1).all() and r.temporal_info["reprojected"] == 0
+        r.run_view_temporal(*cam, width=w, height=h, clamp=True)
+        assert r.temporal_info["reprojected"] >= 100
+        r.run_view_temporal(*cam, width=w, height=h, clamp=True, demodulate=True)
+        assert (r.temporal_history_buffer == 1).all() and r.temporal_info["reprojected"] == 0
+    finally:
+        r.seed = 0
+        r.reset_temporal()
+
+
+@pytest.mark.gpu
+def test_run_view_temporal_demodulated_with_moments(renders):
+    """variance="moments": the moments are those of the irradiance"""
+    name, w, h = "cornell-box", 64, 48
+    r = renders[name]
+    cams = [T.camera_at(name, f) for f in range(2)]
+    frames = [frame_of(renders, name, w, h, 4, seed=40 + f, cam=cams[f]) for f in range(2)]
+    r.set_spp(4)
+    r.seed = 40
+    try:
+        r.reset_temporal()
+        prev = pcam = moments = None
+        for f in range(2):
+            cam, fr = cams[f], frames[f]
+            E, A = fr["emission"], fr["diffuse_albedo"]
+            cur = {"color": crt.demodulate(fr["color"], A, E), "depth": fr["depth"], "normal": fr["normal"], "id": fr["material"]}
+            _, want_c, _, want_h, m1, m2 = crt.temporal(cur, cam, prev=prev, prev_camera=pcam, moments=moments or True, want_rgb=False)
+            prev, pcam, moments = dict(cur, color=want_c, history=want_h), cam, {"m1": m1, "m2": m2}
+            rgb, mean = r.run_view_temporal(*cam, width=w, height=h, variance="moments", demodulate=True)
+            want_rgb, want_mean = crt.modulate(want_c, A, E)
+            assert_bits(mean, want_mean, "moments frame %d" % f)
+            assert np.array_equal(rgb, want_rgb)
+            assert_bits(r.variance_buffer, crt.variance_estimate(m1, m2, want_h, normal=fr["normal"], depth=fr["depth"]), "estimate")
+    finally:
+        r.seed = 0
+        r.reset_temporal()
+
+
+@pytest.mark.gpu
+def test_cli_demodulates_the_denoiser_and_the_sequence(renders, tmp_path):
+    from PIL import Image
+    from cudaraytracing_amd import build as b
+    cli = b.build_cli()
+    name = "veach-mis"
+    cfg = util.SCENES[name]
+    base = [cli, cfg, "--spp", "2", "--width", "96", "--height", "72", "--seed", "42", "--base-dir", util.ROOT]
+    noisy, den, acc = (str(tmp_path / n) for n in ("noisy.png", "den.png", "acc.png"))
+    res = subprocess.run(base + ["-o", noisy, "--denoise", den, "--demodulate", "--denoise-sigma", "8,0.5,inf,0.05"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    f = frame_of(renders, name, 96, 72, 2, seed=42)
+    irr = crt.demodulate(f["color"], f["diffuse_albedo"], f["emission"])
+    _, filtered = crt.denoise(irr, sigma_color=8, sigma_albedo=float("inf"), want_rgb=False, **{k: f[k] for k in GUIDES})
+    assert np.array_equal(np.asarray(Image.open(den)), crt.modulate(filtered, f["diffuse_albedo"], f["emission"])[0])
+    assert np.array_equal(np.asarray(Image.open(noisy)), f["rgb"])
+    # two frames of a static camera, accumulated as irradiance
+    res = subprocess.run(base + ["-o", noisy, "--temporal", "2", "--temporal-out", acc, "--demodulate"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    cam = util.camera(name)
+    prev = None
+    for k in range(2):
+        fr = frame_of(renders, name, 96, 72, 2, seed=42 + k)
+        i, v = crt.demodulate(fr["color"], fr["diffuse_albedo"], fr["emission"], fr["variance"])
+        cur = {"color": i, "variance": v, "depth": fr["depth"], "normal": fr["normal"], "id": fr["material"]}
+        _, c, cv, hist = crt.temporal(cur, cam, prev=prev, prev_camera=cam if prev else None, want_rgb=False)
+        prev = dict(cur, color=c, variance=cv, history=hist)
+    assert np.array_equal(np.asarray(Image.open(acc)), crt.modulate(c, fr["diffuse_albedo"], fr["emission"])[0])
+    bad = subprocess.run(base + ["--demodulate"], capture_output=True, text=True, timeout=60)
+    assert bad.returncode == 1 and "--demodulate" in bad.stderr
+
+
+# ---- the effect ----
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_demodulated_filter_against_a_converged_frame(renders, name):
+    """The frames of test_denoise_reduces_the_error_against_a_converged_frame: 160 x 120, N = spp 8 seed 0, R = spp 256 seed 7; mse on
+    the RGB8 tone maps.  P = N filtered with crt_denoise's defaults, D = N demodulated, filtered with sigma_color 8 and no albedo guide
+    term (sigma_albedo +inf), modulated.  The device is bit-exact to the restatement, so the numpy prototype's figures are the
+    expectation: veach-mis 149.6 (P) against 126.6 (D), cornell-box 169.3 against 162.0.  veach-mis' margin of 15 % is asserted;
+    cornell-box' 4 % is too thin to gate on and is only printed."""
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    r.set_spp(256)
+    r.seed = 7
+    try:
+        ref_rgb = r.run_view(eye, iv, fov, width=160, height=120).copy()
+    finally:
+        r.seed = 0
+    r.set_spp(8)
+    plain_rgb, _ = r.run_view_denoised(eye, iv, fov, width=160, height=120)
+    noisy_rgb = r.frame_buffer.copy()
+    demod_rgb, _ = r.run_view_denoised(eye, iv, fov, width=160, height=120, demodulate=True, sigma_color=8.0, sigma_albedo=float("inf"))
+
+    def mse(x):
+        d = x.astype(np.float64) - ref_rgb.astype(np.float64)
+        return float(np.mean(d * d))
+
+    print("%s: mse noisy %.1f, crt_denoise defaults %.1f, demodulated sigma_color 8 %.1f" % (name, mse(noisy_rgb), mse(plain_rgb), mse(demod_rgb)))
+    if name == "veach-mis":
+        assert mse(demod_rgb) < mse(plain_rgb)

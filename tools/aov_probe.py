@@ -12,6 +12,12 @@ many rays go on; `syncs` is that count and `sync_us` the host-clock time of one 
 what one such round trip costs at least.
 
   python tools/aov_probe.py --specular [--spp 64] [--bounces 1,2] [--reps 20]
+
+--shading times the pass with the shading AOVs (crt_render_aov_shading_device, the six first-hit buffers and its two) beside
+crt_render_aov_device in one process, the two taking turns: the HIP-event time of each call, median and best of --reps, at --spp
+(default 64).
+
+  python tools/aov_probe.py --shading [--spp 64] [--reps 20]
 """
 import argparse
 import ctypes as C
@@ -51,7 +57,7 @@ def specular(a, H, dev_alloc):
         H.hipMemcpy(C.addressof(word), C.c_void_p(ptrs["depth"]), 4, 2)  # hipMemcpyDeviceToHost
         us.append((time.perf_counter() - t0) * 1e6)
     out = {"width": w, "height": h, "reps": a.reps, "sync_us": round(statistics.median(us[20:]), 2), "runs": []}
-    spps = [int(s) for s in a.spp.split(",")] if a.spp != "16,64,512" else [64]
+    spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
     for name in a.scenes.split(","):
         t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
         sc = crt.Scene.from_task(t, w, h)
@@ -90,15 +96,52 @@ def specular(a, H, dev_alloc):
     print(json.dumps(out), flush=True)
 
 
+def shading(a, H, dev_alloc):
+    """--shading: crt_render_aov_shading_device (all eight buffers) beside crt_render_aov_device (its six), the two taking turns: the
+    HIP-event time of each call, median and best of --reps.  One trace serves both structs, so the difference is the resolve's."""
+    w, h = a.width, a.height
+    ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
+    sptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_SHADING_BUFFERS.items()}
+    out = {"width": w, "height": h, "reps": a.reps, "runs": []}
+    spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 1, t.P_RR, t.light_sample_n)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        for spp in spps:
+            r.set_spp(spp)
+            ev = {"aov": [], "shading": []}
+            for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
+                for key, fn in (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, ptrs)),
+                                ("shading", lambda: r.run_view_aov_shading_device(t.eye_pos, iv, fov, sptrs, first_ptrs=ptrs))):
+                    H.hipDeviceSynchronize()
+                    info = fn()
+                    if i >= 2:
+                        ev[key].append(info["total_ms"])
+            med = {k: statistics.median(v) for k, v in ev.items()}
+            run = {"scene": name, "spp": spp, "chunks": r.aov_info["chunks"], "rays": r.aov_info["rays"],
+                   "aov_event_ms": round(med["aov"], 4), "aov_event_ms_best": round(min(ev["aov"]), 4),
+                   "shading_event_ms": round(med["shading"], 4), "shading_event_ms_best": round(min(ev["shading"]), 4),
+                   "shading_over_aov": round(med["shading"] / med["aov"], 4)}
+            out["runs"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+    for p in list(ptrs.values()) + list(sptrs.values()):
+        H.hipFree(C.c_void_p(p))
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--spp", default="16,64,512")
+    ap.add_argument("--spp", default=None, help="comma-separated; default 16,64,512, with --specular / --shading 64")
     ap.add_argument("--scenes", default="cornell-box,veach-mis")
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--specular", action="store_true", help="time crt_render_aov_specular_device beside crt_render_aov_device")
     ap.add_argument("--bounces", default="1,2", help="--specular: the max_bounces values")
+    ap.add_argument("--shading", action="store_true", help="time crt_render_aov_shading_device beside crt_render_aov_device")
     a = ap.parse_args()
     w, h = a.width, a.height
     H = hip_runtime()
@@ -111,6 +154,8 @@ def main():
 
     if a.specular:
         return specular(a, H, dev_alloc)
+    if a.shading:
+        return shading(a, H, dev_alloc)
     rgb = dev_alloc(w * h * 3)
     ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
     out = {"width": w, "height": h, "reps": a.reps, "runs": []}
@@ -133,7 +178,7 @@ def main():
                     best = dt if best is None else min(best, dt)
             return best
 
-        for spp in [int(s) for s in a.spp.split(",")]:
+        for spp in [int(s) for s in (a.spp or "16,64,512").split(",")]:
             r.set_spp(spp)
             aov_ms = timed(lambda: r.run_view_aov_device(t.eye_pos, iv, fov, ptrs, want_info=False))
             frame_ms = timed(lambda: r.run_view_device(t.eye_pos, iv, fov, rgb, want_stats=False))

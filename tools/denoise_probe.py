@@ -16,6 +16,15 @@ RGB8 result against a frame of --ref-spp samples (seed 999).  --sigma-albedo als
 
   python tools/denoise_probe.py --error [--scenes cornell-box,veach-mis] [--error-size 160x120] [--error-spp 8] [--ref-spp 256]
                                 [--bounces 1,2] [--sigma-albedo 0.05,0.1,0.2,0.4]
+
+--demodulate times crt_demodulate_device (with variance) and crt_modulate_device (both outputs) at --sizes beside one filter pass in
+the same process; with --error it lists, per scene, albedo guide, --sigma-color and sigma_albedo (default, +inf), the error of both
+filters on radiance and on irradiance (demodulate, filter, modulate) against the converged frame of --ref-seed; --sigma-albedo adds
+values between the two.  The scene name cornell-box-textured stands for cornell-box with a map_Kd texture on its walls (--cells per
+side, scenes/gen_cornell_box.py), generated into a temporary directory.
+
+  python tools/denoise_probe.py --demodulate [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5]
+  python tools/denoise_probe.py --error --demodulate [--sigma-color 4,6,8,16] [--ref-seed 7] [--bounces 2]
 """
 import argparse
 import ctypes as C
@@ -42,6 +51,113 @@ def hip_runtime():
     H.hipFree.argtypes = [C.c_void_p]
     H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
     return H
+
+
+def demodulated_error_table(a):
+    """--error --demodulate: per scene, albedo guide, sigma_color and sigma_albedo (the filter's default, +inf), the error of crt_denoise
+    and crt_denoise_var on radiance and on irradiance (demodulate, filter, modulate)"""
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "spp": a.error_spp, "ref_spp": a.ref_spp, "ref_seed": a.ref_seed, "runs": []}
+    sigma_albedos = [None] + [float(v) for v in a.sigma_albedo.split(",") if v] + [float("inf")]
+    for name in a.scenes.split(","):
+        textured = name == "cornell-box-textured"  # cornell-box with a map_Kd texture on its walls, generated here
+        t = crt.Task(os.path.join(ROOT, "scenes", "cornell-box" if textured else name, "config.json"), base_dir=ROOT)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        if textured:
+            import tempfile
+            sys.path.insert(0, os.path.join(ROOT, "scenes"))
+            import gen_cornell_box
+            with tempfile.TemporaryDirectory(prefix="crt_textured_") as d:  # (the loader reads the files in add_obj and keeps nothing of them open)
+                obj, mtl_dir, _ = gen_cornell_box.write_textured_variant(d, a.cells)
+                scene = crt.Scene(w, h)
+                scene.add_obj(obj, mtl_dir)
+                scene.set_BVH(t.bvh_thresh_n)
+        else:
+            scene = crt.Scene.from_task(t, w, h)
+        r = crt.Render(scene, a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = a.ref_seed
+        ref = r.run_view(t.eye_pos, iv, fov).astype(np.float64)
+        r.seed = 0
+        r.set_spp(a.error_spp)
+        noisy_rgb = r.run_view(t.eye_pos, iv, fov, want_variance=True).copy()
+        mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+        g = r.run_view_aov_shading(t.eye_pos, iv, fov, first=("albedo", "normal", "depth"))
+        E, A = g["emission"], g["diffuse_albedo"]
+        guides = {"first-hit": g["albedo"]}
+        for mb in [int(v) for v in a.bounces.split(",") if v]:
+            guides["guide_albedo, max_bounces %d" % mb] = r.run_view_aov_specular(t.eye_pos, iv, fov, max_bounces=mb, want=("guide_albedo",))["guide_albedo"]
+        r.free()
+        irr, ivar = crt.demodulate(mean, A, E, var)
+
+        def mse(x):
+            return round(float(np.mean((x.astype(np.float64) - ref) ** 2)), 1)
+
+        run = {"scene": name, "unfiltered": mse(noisy_rgb), "rows": []}
+        for label, alb in guides.items():
+            for sc in [float(v) for v in a.sigma_color.split(",")]:
+                for sa in sigma_albedos:
+                    k = dict(albedo=alb, normal=g["normal"], depth=g["depth"], sigma_color=sc, sigma_albedo=sa)
+                    row = {"albedo_guide": label, "sigma_color": sc, "sigma_albedo": "default" if sa is None else repr(sa),
+                           "denoise": mse(crt.denoise(mean, **k)[0]), "denoise_var": mse(crt.denoise_var(mean, var, **k)[0]),
+                           "demodulated_denoise": mse(crt.modulate(crt.denoise(irr, want_rgb=False, **k)[1], A, E)[0]),
+                           "demodulated_denoise_var": mse(crt.modulate(crt.denoise_var(irr, ivar, want_rgb=False, **k)[1], A, E)[0])}
+                    run["rows"].append(row)
+                    print(json.dumps(dict(row, scene=name)), file=sys.stderr, flush=True)
+        out["runs"].append(run)
+    print(json.dumps(out), flush=True)
+
+
+def modulate_times(a, H):
+    """--demodulate: crt_demodulate_device (with variance) and crt_modulate_device (both outputs) beside ONE filter pass -- the
+    difference of crt_denoise_device with two iterations and with one -- the four calls taking turns, on synthetic images.  The byte
+    rate is that of the compulsory traffic: 72 B per pixel for demodulate with variance (four planes read, two written), 39 B for
+    modulate with both outputs (three read, 12 + 3 B written)."""
+    import numpy as np
+    out = {"calls": a.calls, "warmup": a.warmup, "runs": []}
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        n = w * h
+        rng = np.random.default_rng(1)
+        host = {"color": (rng.random((h, w, 3)) * 20).astype(np.float32), "albedo": (rng.random((h, w, 3)) * 0.9 + 0.05).astype(np.float32),
+                "emission": np.where(rng.random((h, w, 3)) < 0.05, 100.0, 0.0).astype(np.float32), "variance": rng.random((h, w, 3)).astype(np.float32),
+                "normal": rng.random((h, w, 3)).astype(np.float32), "depth": (rng.random((h, w)) + 1).astype(np.float32)}
+        scratch_bytes = crt.denoise_scratch_bytes(w, h)
+        ptrs = {}
+        for name, nbytes in [(k, v.nbytes) for k, v in host.items()] + [("irr", n * 12), ("ivar", n * 12), ("out_mean", n * 12), ("out_rgb", n * 3),
+                                                                              ("scratch", scratch_bytes)]:
+            p = C.c_void_p()
+            if H.hipMalloc(C.byref(p), nbytes) != 0:
+                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
+            ptrs[name] = p.value
+        for name, v in host.items():
+            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise RuntimeError("hipMemcpy failed")
+        calls = {
+            "demodulate": lambda: crt.demodulate_device(w, h, ptrs["color"], ptrs["albedo"], ptrs["irr"], emission_ptr=ptrs["emission"],
+                                                        variance_ptr=ptrs["variance"], out_variance_ptr=ptrs["ivar"])["total_ms"],
+            "modulate": lambda: crt.modulate_device(w, h, ptrs["irr"], ptrs["albedo"], ptrs["out_mean"], out_rgb_ptr=ptrs["out_rgb"],
+                                                    emission_ptr=ptrs["emission"])["total_ms"],
+            "denoise_1": lambda: crt.denoise_device(w, h, ptrs["irr"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes, albedo_ptr=ptrs["albedo"],
+                                                    normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"], iterations=1)["total_ms"],
+            "denoise_2": lambda: crt.denoise_device(w, h, ptrs["irr"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes, albedo_ptr=ptrs["albedo"],
+                                                    normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"], iterations=2)["total_ms"]}
+        ms = {k: [] for k in calls}
+        for _ in range(a.warmup + a.calls):
+            for k, f in calls.items():
+                ms[k].append(f())
+        med = {k: statistics.median(v[a.warmup:]) for k, v in ms.items()}
+        run = {"width": w, "height": h, "demodulate_ms": round(med["demodulate"], 4), "modulate_ms": round(med["modulate"], 4),
+               "denoise_pass_ms": round(med["denoise_2"] - med["denoise_1"], 4), "denoise_1_iteration_ms": round(med["denoise_1"], 4),
+               "demodulate_best_ms": round(min(ms["demodulate"][a.warmup:]), 4), "modulate_best_ms": round(min(ms["modulate"][a.warmup:]), 4),
+               "demodulate_TB_per_s": round(72 * n / (med["demodulate"] * 1e-3) / 1e12, 3),
+               "modulate_TB_per_s": round(39 * n / (med["modulate"] * 1e-3) / 1e12, 3)}
+        out["runs"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+    print(json.dumps(out), flush=True)
 
 
 def error_table(a):
@@ -97,12 +213,18 @@ def main():
     ap.add_argument("--ref-spp", type=int, default=256)
     ap.add_argument("--bounces", default="1,2")
     ap.add_argument("--sigma-albedo", default="")
+    ap.add_argument("--demodulate", action="store_true", help="time crt_demodulate_device / crt_modulate_device beside one filter pass; with --error: the filters on irradiance")
+    ap.add_argument("--sigma-color", default="4,6,8,16", help="--error --demodulate: the colour sigmas of the table")
+    ap.add_argument("--cells", type=int, default=12, help="--error --demodulate with the scene cornell-box-textured: cells per wall side")
+    ap.add_argument("--ref-seed", type=int, default=999, help="--error --demodulate: the seed of the converged frame")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
     if a.error:
-        return error_table(a)
+        return demodulated_error_table(a) if a.demodulate else error_table(a)
     H = hip_runtime()
+    if a.demodulate:
+        return modulate_times(a, H)
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
     iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
     fov = crt.fov_to_radians(t.fov_y)

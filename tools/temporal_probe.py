@@ -28,10 +28,14 @@ with the default clamp, each accumulated frame under crt_denoise_var fed with (a
 of_mean 0, (c) with of_mean 1; then the same at one sample per pixel, where only (b) and (c) exist and the comparison is the last frame
 under crt_denoise.
 
+--demodulate: albedo demodulation (crt_demodulate / crt_modulate).  Effect only: the four sequences, unclamped and with the default
+clamp, accumulated as radiance and as irradiance; per combination the accumulated error and that of its variance-guided filter (with
+the filter's sigma_albedo and with +inf), which on irradiance runs before the accumulated frame is modulated.
+
 One JSON line per figure on stderr, one JSON document on stdout.
 
   python tools/temporal_probe.py [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--spp 4] [--error-size 160x120] [--alpha-min 0.05,0.1,0.2]
-                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments]
+                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments] [--demodulate]
 """
 import argparse
 import ctypes as C
@@ -316,6 +320,49 @@ def moments_effect(a, out):
         r.free()
 
 
+def demodulate_effect(a, out):
+    """--demodulate: the four sequences, unclamped and with the default clamp, accumulated as radiance and as irradiance (each frame
+    through demodulate with its own shading AOVs, the accumulated frame through modulate with the last frame's): the accumulated
+    error and that of its variance-guided filter -- on irradiance, the filter runs before modulate."""
+    w, h = (int(v) for v in a.error_size.split("x"))
+    for scene in ("cornell-box", "veach-mis"):
+        t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 8, t.P_RR, t.light_sample_n)
+        for moving in (False, True):
+            cams = [camera_at(t, scene, f if moving else 0) for f in range(8)]
+            r.set_spp(256)
+            r.seed = 7
+            ref = r.run_view(*cams[-1]).copy()
+            frames = []
+            for f in range(8):
+                cur, rgb, g = render_frame(r, cams[f], 8, 100 + f)
+                sh = r.run_view_aov_shading(*cams[f])
+                irr, ivar = crt.demodulate(cur["color"], sh["diffuse_albedo"], sh["emission"], cur["variance"])
+                frames.append((cur, dict(cur, color=irr, variance=ivar), sh, g, cams[f]))
+            run = {"scene": scene, "camera": "moving" if moving else "static", "width": w, "height": h}
+            for tag, clamp in (("plain", None), ("clamp", True)):
+                for kind in ("radiance", "irradiance"):
+                    prev = pcam = None
+                    for cur, dcur, sh, g, cam in frames:
+                        c = dcur if kind == "irradiance" else cur
+                        rgb, color, var, hist = crt.temporal(c, cam, prev=prev, prev_camera=pcam, clamp=clamp)
+                        prev, pcam = dict(c, color=color, variance=var, history=hist), cam
+                    if kind == "irradiance":
+                        E, A = sh["emission"], sh["diffuse_albedo"]
+                        rgb = crt.modulate(color, A, E)[0]
+                        den = crt.modulate(crt.denoise_var(color, var, want_rgb=False, **g)[1], A, E)[0]
+                        den_inf = crt.modulate(crt.denoise_var(color, var, want_rgb=False, sigma_albedo=float("inf"), **g)[1], A, E)[0]
+                    else:
+                        den = crt.denoise_var(color, var, **g)[0]
+                        den_inf = crt.denoise_var(color, var, sigma_albedo=float("inf"), **g)[0]
+                    run["%s_%s_mse_accumulated" % (tag, kind)] = round(mse(rgb, ref), 1)
+                    run["%s_%s_mse_accumulated_denoise_var" % (tag, kind)] = round(mse(den, ref), 1)
+                    run["%s_%s_mse_accumulated_denoise_var_sigma_albedo_inf" % (tag, kind)] = round(mse(den_inf, ref), 1)
+            out["demodulate_effect"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="800x600,3840x2160")
@@ -327,6 +374,7 @@ def main():
     ap.add_argument("--clamp", action="store_true")
     ap.add_argument("--clamp-gammas", default="0.5,1,1.5,2,3,inf")
     ap.add_argument("--moments", action="store_true")
+    ap.add_argument("--demodulate", action="store_true", help="the sequences accumulated as irradiance beside radiance")
     ap.add_argument("--skip-cost", action="store_true")
     ap.add_argument("--skip-effect", action="store_true")
     a = ap.parse_args()
@@ -334,6 +382,11 @@ def main():
         raise SystemExit("temporal_probe: no HIP device")
     out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "clamp_cost": [], "clamp_effect": [], "moments_cost": [],
            "moments_effect": []}
+    if a.demodulate:                                         # (its own table only)
+        out["demodulate_effect"] = []
+        demodulate_effect(a, out)
+        print(json.dumps(out), flush=True)
+        return
     if a.moments:                                            # (its own tables only: the others are the earlier sections')
         if not a.skip_cost:
             moments_cost(a, hip_runtime(), out)
