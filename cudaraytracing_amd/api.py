@@ -242,6 +242,11 @@ class Render:
         return capi.Params(width or self.scene.width, height or self.scene.height, self.spp, float(self.P_RR),
                            self.light_sample_n, self.seed, rank, world, self.traversal, flags)
 
+    def _device_params(self, rank, world, tiled, width, height):
+        """The crt_params of a device form: its shard, and the tiled output layout a shard of several always has"""
+        return self._params(rank=rank, world=world, flags=(capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags,
+                            width=width, height=height)
+
     def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False):
         """Renders the whole frame; returns the RGB8 frame buffer (H, W, 3).  want_variance: render with FLAG_VARIANCE (the frame is
         the same bits) and leave the per-pixel variance of the mean, (H, W, 3) float32 (crt_variance), in self.variance_buffer."""
@@ -360,8 +365,7 @@ class Render:
         call synchronizes the stream once (twice with want_info, which sets self.map_info)."""
         h_ = self._handle("run_view_map_device")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        prm = self._device_params(rank, world, tiled, width, height)
         return self._map_device("crt_render_map_device", lambda rgb, mean, samples, var, st, info: capi.lib().crt_render_map_device(
             h_, C.byref(cam), C.byref(prm), C.c_void_p(d_map_ptr), int(sample_begin), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
 
@@ -370,8 +374,7 @@ class Render:
         """crt_render_planned_device: outputs and synchronization as run_view_map_device."""
         h_ = self._handle("run_view_planned_device")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        prm = self._device_params(rank, world, tiled, width, height)
         ap = _adaptive_params(min_samples, None, threshold, mean_floor)
         return self._map_device("crt_render_planned_device", lambda rgb, mean, samples, var, st, info: capi.lib().crt_render_planned_device(
             h_, C.byref(cam), C.byref(prm), C.byref(ap), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
@@ -437,8 +440,7 @@ class Render:
         """Enqueues a render whose outputs stay in device memory (raw device pointers)."""
         self._handle("run_view_device")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
+        prm = self._device_params(rank, world, tiled, width, height)
         st = capi.Stats()
         capi.check(capi.lib().crt_render_device(self._h, C.byref(cam), C.byref(prm), C.c_void_p(d_rgb_ptr),
                                                 C.c_void_p(d_mean_ptr) if d_mean_ptr else None,
@@ -448,127 +450,95 @@ class Render:
             self.stats = st.as_dict()
         return self.stats
 
+    def _aov_host(self, fn, view, width, height, groups, info_attr, sp=None):
+        """The host form `fn` of an AOV pass for view = (eye_pos, inv_view_mat, fovY).  groups: per buffer struct of the C call, in its
+        order, (names wanted, buffer table, ctypes struct, pass NULL when no name is given); sp: the AovSpecularParams of the specular
+        form.  Returns {name: zeroed array the pass has filled}; self.<info_attr> gets the crt_aov_info dict."""
+        h_ = self._handle("run_view" + fn[len("crt_render"):])
+        cam = self._cam(*view)
+        prm = self._params(flags=self.extra_flags, width=width, height=height)
+        w, h = prm.width, prm.height
+        out, structs = {}, []
+        for names, table, struct, null_if_empty in groups:
+            bufs = struct()
+            for name in names:
+                ch, dt = table[name]
+                out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
+                setattr(bufs, name, out[name].ctypes.data)
+            structs.append(None if (null_if_empty and not names) else C.byref(bufs))
+        info = capi.AovInfo()
+        capi.check(getattr(capi.lib(), fn)(h_, C.byref(cam), C.byref(prm), *([C.byref(sp)] if sp else []), *structs, C.byref(info)), fn)
+        setattr(self, info_attr, info.as_dict())
+        return out
+
+    def _aov_device(self, fn, view, shard, groups, info_attr, stream, want_info, sp=None, kind="AOV"):
+        """The device form `fn` of an AOV pass for view = (eye_pos, inv_view_mat, fovY) and shard = (rank, world, tiled, width, height).
+        groups as _aov_host's, with {name: raw device pointer} (or None) for the names; kind: what an unknown name is called.  With
+        want_info sets and returns self.<info_attr>."""
+        h_ = self._handle("run_view" + fn[len("crt_render"):])
+        cam = self._cam(*view)
+        prm = self._device_params(*shard)
+        structs = []
+        for ptrs, table, struct, null_if_empty in groups:
+            bufs = struct()
+            for name, p in (ptrs or {}).items():
+                if name not in table:
+                    raise ValueError("unknown %s buffer %r" % (kind, name))
+                setattr(bufs, name, int(p) if p else None)
+            structs.append(None if (null_if_empty and not ptrs) else C.byref(bufs))
+        info = capi.AovInfo()
+        capi.check(getattr(capi.lib(), fn)(h_, C.byref(cam), C.byref(prm), *([C.byref(sp)] if sp else []), *structs,
+                                           C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None), fn)
+        if want_info:
+            setattr(self, info_attr, info.as_dict())
+        return getattr(self, info_attr) if want_info else None
+
     def run_view_aov(self, eye_pos, inv_view_mat, fovY, want=tuple(capi.AOV_BUFFERS), width=None, height=None):
         """First-hit AOVs of the frame run_view draws with the same camera and settings (crt_render_aov): per pixel, the spp camera
         rays of the frame's paths traced for their closest hit.  Returns {name: array} for the names in `want` (albedo, normal:
         (H, W, 3) float32; depth, coverage: (H, W) float32; tri, material: (H, W) int32); self.aov_info gets rays, chunks, total_ms."""
-        h_ = self._handle("run_view_aov")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=self.extra_flags, width=width, height=height)
-        w, h = prm.width, prm.height
-        out, bufs = {}, capi.AovBuffers()
-        for name in want:
-            ch, dt = capi.AOV_BUFFERS[name]
-            out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
-            setattr(bufs, name, out[name].ctypes.data)
-        info = capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov(h_, C.byref(cam), C.byref(prm), C.byref(bufs), C.byref(info)), "crt_render_aov")
-        self.aov_info = info.as_dict()
-        return out
+        return self._aov_host("crt_render_aov", (eye_pos, inv_view_mat, fovY), width, height, [(want, capi.AOV_BUFFERS, capi.AovBuffers, False)], "aov_info")
 
     def run_view_aov_device(self, eye_pos, inv_view_mat, fovY, ptrs, stream=None, rank=0, world=1, tiled=False, want_info=True,
                             width=None, height=None):
         """Enqueues the AOV pass with outputs in device memory: ptrs = {name: raw device pointer} (row-major W x H, or the shard's
         compact tiles with tiled / world > 1, as run_view_device).  With want_info the call synchronizes the stream and sets
         self.aov_info."""
-        h_ = self._handle("run_view_aov_device")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
-        bufs = capi.AovBuffers()
-        for name, p in ptrs.items():
-            if name not in capi.AOV_BUFFERS:
-                raise ValueError("unknown AOV buffer %r" % name)
-            setattr(bufs, name, int(p) if p else None)
-        info = capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov_device(h_, C.byref(cam), C.byref(prm), C.byref(bufs), C.c_void_p(stream) if stream else None,
-                                                    C.byref(info) if want_info else None), "crt_render_aov_device")
-        if want_info:
-            self.aov_info = info.as_dict()
-        return self.aov_info if want_info else None
+        return self._aov_device("crt_render_aov_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
+                                [(ptrs, capi.AOV_BUFFERS, capi.AovBuffers, False)], "aov_info", stream, want_info)
 
     def run_view_aov_shading(self, eye_pos, inv_view_mat, fovY, want=tuple(capi.AOV_SHADING_BUFFERS), first=(), width=None, height=None):
         """Shading AOVs (crt_render_aov_shading, contract: include/crt.h): emission -- ke / spp over the samples whose camera ray hits
         an emitter -- and diffuse_albedo -- kd / spp over the other hits --, what demodulate() takes.  `first` names buffers of
         run_view_aov to fill from the same trace (crt_render_aov's bits).  Returns {name: array} for the names in `want` and `first`;
         self.aov_info gets rays, chunks, total_ms."""
-        h_ = self._handle("run_view_aov_shading")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=self.extra_flags, width=width, height=height)
-        w, h = prm.width, prm.height
-        out, bufs, fbufs = {}, capi.AovShadingBuffers(), capi.AovBuffers()
-        for names, table, struct in ((want, capi.AOV_SHADING_BUFFERS, bufs), (first, capi.AOV_BUFFERS, fbufs)):
-            for name in names:
-                ch, dt = table[name]
-                out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
-                setattr(struct, name, out[name].ctypes.data)
-        info = capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov_shading(h_, C.byref(cam), C.byref(prm), C.byref(fbufs) if first else None, C.byref(bufs), C.byref(info)),
-                   "crt_render_aov_shading")
-        self.aov_info = info.as_dict()
-        return out
+        out = self._aov_host("crt_render_aov_shading", (eye_pos, inv_view_mat, fovY), width, height,
+                             [(first, capi.AOV_BUFFERS, capi.AovBuffers, True), (want, capi.AOV_SHADING_BUFFERS, capi.AovShadingBuffers, False)], "aov_info")
+        return {name: out[name] for name in (*want, *first)}
 
     def run_view_aov_shading_device(self, eye_pos, inv_view_mat, fovY, ptrs, first_ptrs=None, stream=None, rank=0, world=1, tiled=False,
                                     want_info=True, width=None, height=None):
         """The same with outputs in device memory: ptrs = {"emission" / "diffuse_albedo": raw device pointer}, first_ptrs the same for
         buffers of run_view_aov_device (None: none); layout, stream and want_info as run_view_aov_device."""
-        h_ = self._handle("run_view_aov_shading_device")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
-        bufs, fbufs = capi.AovShadingBuffers(), capi.AovBuffers()
-        for given, table, struct in ((ptrs, capi.AOV_SHADING_BUFFERS, bufs), (first_ptrs or {}, capi.AOV_BUFFERS, fbufs)):
-            for name, p in given.items():
-                if name not in table:
-                    raise ValueError("unknown AOV buffer %r" % name)
-                setattr(struct, name, int(p) if p else None)
-        info = capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov_shading_device(h_, C.byref(cam), C.byref(prm), C.byref(fbufs) if first_ptrs else None, C.byref(bufs),
-                                                            C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
-                   "crt_render_aov_shading_device")
-        if want_info:
-            self.aov_info = info.as_dict()
-        return self.aov_info if want_info else None
+        return self._aov_device("crt_render_aov_shading_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
+                                [(first_ptrs, capi.AOV_BUFFERS, capi.AovBuffers, True), (ptrs, capi.AOV_SHADING_BUFFERS, capi.AovShadingBuffers, False)],
+                                "aov_info", stream, want_info)
 
     def run_view_aov_specular(self, eye_pos, inv_view_mat, fovY, max_bounces=None, want=tuple(capi.AOV_SPECULAR_BUFFERS), width=None, height=None):
         """AOVs that follow perfect-mirror bounces from the first hit (crt_render_aov_specular, contract: include/crt.h): returns
         {name: array} for the names in `want` (guide_albedo, last_normal: (H, W, 3) float32; path_depth, bounces: (H, W) float32;
         last_tri: (H, W) int32).  max_bounces None: crt_aov_specular_defaults'.  self.aov_specular_info gets rays (camera and
         reflected), chunks, total_ms."""
-        h_ = self._handle("run_view_aov_specular")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=self.extra_flags, width=width, height=height)
-        w, h = prm.width, prm.height
-        out, bufs = {}, capi.AovSpecularBuffers()
-        for name in want:
-            ch, dt = capi.AOV_SPECULAR_BUFFERS[name]
-            out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
-            setattr(bufs, name, out[name].ctypes.data)
-        sp, info = _aov_specular_params(max_bounces), capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov_specular(h_, C.byref(cam), C.byref(prm), C.byref(sp), C.byref(bufs), C.byref(info)), "crt_render_aov_specular")
-        self.aov_specular_info = info.as_dict()
-        return out
+        return self._aov_host("crt_render_aov_specular", (eye_pos, inv_view_mat, fovY), width, height,
+                              [(want, capi.AOV_SPECULAR_BUFFERS, capi.AovSpecularBuffers, False)], "aov_specular_info", sp=_aov_specular_params(max_bounces))
 
     def run_view_aov_specular_device(self, eye_pos, inv_view_mat, fovY, ptrs, max_bounces=None, stream=None, rank=0, world=1, tiled=False,
                                      want_info=True, width=None, height=None):
         """The same with outputs in device memory: ptrs = {name: raw device pointer}, layout as run_view_aov_device.  The call
         synchronizes the stream once per bounce and chunk (and once more with want_info, which sets self.aov_specular_info)."""
-        h_ = self._handle("run_view_aov_specular_device")
-        cam = self._cam(eye_pos, inv_view_mat, fovY)
-        flags = (capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags
-        prm = self._params(rank=rank, world=world, flags=flags, width=width, height=height)
-        bufs = capi.AovSpecularBuffers()
-        for name, p in ptrs.items():
-            if name not in capi.AOV_SPECULAR_BUFFERS:
-                raise ValueError("unknown specular AOV buffer %r" % name)
-            setattr(bufs, name, int(p) if p else None)
-        sp, info = _aov_specular_params(max_bounces), capi.AovInfo()
-        capi.check(capi.lib().crt_render_aov_specular_device(h_, C.byref(cam), C.byref(prm), C.byref(sp), C.byref(bufs),
-                                                             C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
-                   "crt_render_aov_specular_device")
-        if want_info:
-            self.aov_specular_info = info.as_dict()
-        return self.aov_specular_info if want_info else None
+        return self._aov_device("crt_render_aov_specular_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
+                                [(ptrs, capi.AOV_SPECULAR_BUFFERS, capi.AovSpecularBuffers, False)], "aov_specular_info", stream, want_info,
+                                sp=_aov_specular_params(max_bounces), kind="specular AOV")
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
                           sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
@@ -806,76 +776,49 @@ class MultiRender(Render):
             self.frame_buffer, self.mean_buffer = rgb, mean
         return rgb
 
-    def run_view_range(self, *a, **k):
-        raise NotImplementedError("progressive ranges are a single-device interface (crt_render_range)")
-
-    def run_view_adaptive(self, *a, **k):
-        raise NotImplementedError("adaptive sampling is a single-device interface (crt_render_adaptive)")
-
-    def run_view_map(self, *a, **k):
-        raise NotImplementedError("sample maps are a single-device interface (crt_render_map)")
-
-    def run_view_map_device(self, *a, **k):
-        raise NotImplementedError("sample maps are a single-device interface (crt_render_map_device)")
-
-    def run_view_planned(self, *a, **k):
-        raise NotImplementedError("planned adaptive frames are a single-device interface (crt_render_planned)")
-
-    def run_view_planned_device(self, *a, **k):
-        raise NotImplementedError("planned adaptive frames are a single-device interface (crt_render_planned_device)")
-
-    def sample_plan(self, *a, **k):
-        raise NotImplementedError("the sample plan is a single-device interface (crt_sample_plan)")
-
-    def preview(self, *a, **k):
-        raise NotImplementedError("previews are a single-device interface (crt_preview)")
-
-    def variance(self, *a, **k):
-        raise NotImplementedError("the variance buffer is a single-device interface (crt_variance)")
-
-    def accel_info(self):
-        raise NotImplementedError("crt_scene_accel_info is a single-device interface")
-
-    def run_view_device(self, *a, **k):
-        raise NotImplementedError("MultiRender owns its device buffers (crt_multi_frame_device)")
-
-    def run_view_aov(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov)")
-
-    def run_view_aov_device(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_device)")
-
-    def run_view_aov_shading(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_shading)")
-
-    def run_view_aov_shading_device(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_shading_device)")
-
-    def run_view_aov_specular(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_specular)")
-
-    def run_view_aov_specular_device(self, *a, **k):
-        raise NotImplementedError("the AOV pass is a single-device interface (crt_render_aov_specular_device)")
-
-    def run_view_denoised(self, *a, **k):
-        raise NotImplementedError("the denoiser is a single-device interface (crt_denoise): gather the frame first")
-
-    def run_view_temporal(self, *a, **k):
-        raise NotImplementedError("temporal accumulation is a single-device interface (crt_temporal): gather the frame first")
-
-    def intersect(self, *a, **k):
-        raise NotImplementedError("crt_intersect is a single-device interface")
-
-    def blocked(self, *a, **k):
-        raise NotImplementedError("crt_intersect is a single-device interface")
-
-    def last_launch_ms(self):
-        raise NotImplementedError("crt_last_launch_ms is a single-device interface (per-rank kernel times: rank_stats)")
-
     def free(self):
         if self._mh:
             capi.lib().crt_multi_destroy(self._mh)
             self._mh = C.c_void_p()
+
+
+# The single-device interfaces of Render that a MultiRender refuses, each with what it says
+_MULTI_REFUSALS = {
+    "run_view_range": "progressive ranges are a single-device interface (crt_render_range)",
+    "run_view_adaptive": "adaptive sampling is a single-device interface (crt_render_adaptive)",
+    "run_view_map": "sample maps are a single-device interface (crt_render_map)",
+    "run_view_map_device": "sample maps are a single-device interface (crt_render_map_device)",
+    "run_view_planned": "planned adaptive frames are a single-device interface (crt_render_planned)",
+    "run_view_planned_device": "planned adaptive frames are a single-device interface (crt_render_planned_device)",
+    "sample_plan": "the sample plan is a single-device interface (crt_sample_plan)",
+    "preview": "previews are a single-device interface (crt_preview)",
+    "variance": "the variance buffer is a single-device interface (crt_variance)",
+    "accel_info": "crt_scene_accel_info is a single-device interface",
+    "run_view_device": "MultiRender owns its device buffers (crt_multi_frame_device)",
+    "run_view_aov": "the AOV pass is a single-device interface (crt_render_aov)",
+    "run_view_aov_device": "the AOV pass is a single-device interface (crt_render_aov_device)",
+    "run_view_aov_shading": "the AOV pass is a single-device interface (crt_render_aov_shading)",
+    "run_view_aov_shading_device": "the AOV pass is a single-device interface (crt_render_aov_shading_device)",
+    "run_view_aov_specular": "the AOV pass is a single-device interface (crt_render_aov_specular)",
+    "run_view_aov_specular_device": "the AOV pass is a single-device interface (crt_render_aov_specular_device)",
+    "run_view_denoised": "the denoiser is a single-device interface (crt_denoise): gather the frame first",
+    "run_view_temporal": "temporal accumulation is a single-device interface (crt_temporal): gather the frame first",
+    "intersect": "crt_intersect is a single-device interface",
+    "blocked": "crt_intersect is a single-device interface",
+    "last_launch_ms": "crt_last_launch_ms is a single-device interface (per-rank kernel times: rank_stats)",
+}
+
+
+def _refusal(name, message):
+    def method(self, *a, **k):
+        raise NotImplementedError(message)
+    method.__name__, method.__qualname__ = name, "MultiRender." + name
+    method.__doc__ = "Not on a MultiRender: %s." % message
+    return method
+
+
+for _name, _message in _MULTI_REFUSALS.items():
+    setattr(MultiRender, _name, _refusal(_name, _message))
 
 
 def image_load(path):

@@ -1,7 +1,7 @@
 // cudaraytracing_amd/csrc/crt_aov.hip -- the first-hit AOV pass (crt_render_aov, include/crt.h): per pixel, the camera rays of samples
 // 0 .. spp-1 -- the primary rays of the frame's paths, camera_dir -- traced by the render kernel's own closest-hit query, and the albedo,
 // normal, depth, coverage, triangle and material buffers made of their hits in sample order.  The host side (chunks over samples, the
-// trace) is in crt_render.hip; slot -> pixel -> output index is the frame kernels' (slot_pixel, crt_internal.h).  The same pass with the
+// trace) is in crt_aov_pass.hip; slot -> pixel -> output index is the frame kernels' (slot_pixel, crt_internal.h).  The same pass with the
 // emission and non-emitter albedo buffers beside them (crt_render_aov_shading) is the resolve's second instantiation.
 // Below it, the pass that follows perfect-mirror bounces from those hits (crt_render_aov_specular): a bounce kernel and its own resolve.
 #include "crt_internal.h"
@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256) void k_aov_spec_resolve(const AovSpecParams S)
     if (S.last_tri) S.last_tri[o] = tri0;
 }
 
-// ---- exported to crt_render.hip ----
+// ---- exported to crt_aov_pass.hip ----
 void launch_aov_bounce(const AovSpecParams& S, hipStream_t st) { hipLaunchKernelGGL(k_aov_bounce, dim3((S.n_in + 255) / 256), dim3(256), 0, st, S); }
 void launch_aov_spec_resolve(const AovSpecParams& S, hipStream_t st) { hipLaunchKernelGGL(k_aov_spec_resolve, dim3((S.nslots + 255) / 256), dim3(256), 0, st, S); }
 void launch_aov_rays(const AovParams& A, hipStream_t st)

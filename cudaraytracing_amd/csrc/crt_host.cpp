@@ -647,18 +647,24 @@ void Render::set_height(const unsigned& h)
     mean_buffer_.assign((size_t)3 * scene_->get_pixels(), 0.0f);
 }
 
+// the camera and the settings of this object as the C ABI takes them: the whole frame on one rank, with the caller's flags
+void Render::view_args(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t flags, crt_camera& cam, crt_params& p) const
+{
+    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
+    cam.fov_y = fovY;
+    std::memset(&p, 0, sizeof(p));
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags;
+}
+
 void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY)
 {
     if (!device_scene_ && !multi_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view after free()");
     crt_camera cam;
-    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
-    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
-    cam.fov_y = fovY;
     crt_params p;
-    std::memset(&p, 0, sizeof(p));
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE);
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE), cam, p);
     variance_buffer_.clear();
     int rc;
     if (multi_) {
@@ -684,14 +690,8 @@ template <class Call> void Render::sampled_frame(const char* who, const float ey
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": a single-device interface");
     if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
     crt_camera cam;
-    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
-    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
-    cam.fov_y = fovY;
     crt_params p;
-    std::memset(&p, 0, sizeof(p));
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags_ & CRT_FLAG_TRACE_ALL;
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & CRT_FLAG_TRACE_ALL, cam, p);
     const size_t n = scene_->get_pixels();
     samples_buffer_.assign(n, 0u);
     variance_buffer_.clear();
@@ -727,14 +727,8 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov: the AOV pass is a single-device interface");
     if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov after free()");
     crt_camera cam;
-    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
-    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
-    cam.fov_y = fovY;
     crt_params p;
-    std::memset(&p, 0, sizeof(p));
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
     const size_t n = scene_->get_pixels();
     albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f); material_buffer_.assign(n, 0);
     crt_aov_buffers out{};
@@ -783,14 +777,8 @@ void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9
     if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov_specular: the AOV pass is a single-device interface");
     if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov_specular after free()");
     crt_camera cam;
-    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
-    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
-    cam.fov_y = fovY;
     crt_params p;
-    std::memset(&p, 0, sizeof(p));
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
     crt_aov_specular_params sp;
     crt_aov_specular_defaults(&sp);
     if (max_bounces) sp.max_bounces = max_bounces;

@@ -346,6 +346,7 @@ private:
     void modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const;
     crt_adaptive_info adaptive_info_{};
     crt_map_info map_info_{};
+    void view_args(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t flags, crt_camera& cam, crt_params& p) const;
     template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);
     int device_ = 0;
     crt_denoise_info denoise_info_{};

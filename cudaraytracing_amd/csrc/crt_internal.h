@@ -131,7 +131,7 @@ void launch_math(int fn, uint32_t n, const float* a, const float* b, float* out)
 void launch_philox(uint32_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out);
 void launch_rcp_check(unsigned long long* counts);
 
-// first-hit AOV pass (crt_aov.hip; host side: crt_render_aov in crt_render.hip).  One chunk = samples [sample_begin, sample_begin + n_samples)
+// first-hit AOV pass (crt_aov.hip; host side: crt_render_aov in crt_aov_pass.hip).  One chunk = samples [sample_begin, sample_begin + n_samples)
 // of every pixel slot of the shard; query ray / result item = sample offset in the chunk x nslots + slot.
 struct AovParams : SlotMap {
     // the camera, as LParams holds it (camera_dir; width and height: the slot map's)
@@ -164,7 +164,7 @@ struct AovShadingOut {
 };
 void launch_aov_resolve_shading(const AovParams& A, const AovShadingOut& H, hipStream_t st);
 
-// AOV pass that follows mirror bounces (crt_aov.hip; host side: crt_render_aov_specular in crt_render.hip).  Items as above.  A stage
+// AOV pass that follows mirror bounces (crt_aov.hip; host side: crt_render_aov_specular in crt_aov_pass.hip).  Items as above.  A stage
 // reads the answers of the n_in rays traced last (stage 0: the camera rays, ray i = item i; later: the reflected rays, ray i of item
 // in_item[i]), advances the chain state of their items and compacts the rays that go on into the other half of the query pool.
 struct AovSpecParams : SlotMap {

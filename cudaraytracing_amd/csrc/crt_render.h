@@ -1,5 +1,5 @@
 // cudaraytracing_amd/csrc/crt_render.h -- what crt_sparse.hip (the sparse frames: crt_render_adaptive, crt_render_map, crt_sample_plan,
-// crt_render_planned) takes from crt_render.hip, and nothing else of it.
+// crt_render_planned) and crt_aov_pass.hip (the AOV passes: crt_render_aov*) take from crt_render.hip, and nothing else of it.
 #ifndef CRT_RENDER_H
 #define CRT_RENDER_H
 #include "crt_scene.h"
@@ -22,10 +22,13 @@ struct ItemSource {
 const uint64_t kMaxChunkItems = 1ull << 30; // paths per chunk (12.9 GB of per-path radiance: sized for 288 GB of HBM, every launch ends with a 2 ms tail)
 uint32_t chunk_samples(uint32_t nslots, uint32_t s_count);
 uint32_t choose_pipeline(const crt_scene* sc);
-int params_check(const char* who, const crt_params* prm, bool aov = false);
+int params_check(const char* who, const crt_params* prm, bool camera_rays_only = false);
 bool continues_frame(const FrameMark& f, const crt_params* prm, uint32_t s_begin, bool tiled);
 AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh);
 void ensure_events(crt_scene* sc);
+void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale, float& ar);
+// The n query rays in the handle's query pool, from `first` on, traced on st: the answers stay on the device, `stride` floats apart
+const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride, size_t first = 0);
 // src: the range's item source.  open: the range belongs to a frame its caller resolves (every range of a sparse frame, its uniform
 // warm-up and the ranges with a source alike): the range that ends at spp tone-maps nothing, d_rgb / d_mean are not used.
 int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, void* d_rgb, void* d_mean, hipStream_t st, crt_stats* stats, uint32_t s_begin = 0,

@@ -1,9 +1,9 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
-// pipeline, the AOV passes, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*,
-// crt_render_aov*, crt_intersect, crt_device_*).  The frames in which not every pixel takes every sample (crt_render_adaptive*,
-// crt_render_map*, crt_sample_plan*, crt_render_planned*) are ranges of render_impl with an item source: crt_sparse.hip, which sees this
-// file through crt_render.h.  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live in crt_mega3.hip,
-// crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_sample_map.hip, crt_aov.hip.
+// pipeline, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*, crt_intersect,
+// crt_device_*).  The frames in which not every pixel takes every sample (crt_render_adaptive*, crt_render_map*, crt_sample_plan*,
+// crt_render_planned*) are ranges of render_impl with an item source: crt_sparse.hip; the AOV passes trace their rays with trace_queries:
+// crt_aov_pass.hip.  Both see this file through crt_render.h.  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live
+// in crt_mega3.hip, crt_wavefront.hip, crt_frame.hip, crt_adaptive.hip, crt_sample_map.hip.
 // The slot map of a shard and the host's form of the slot rule: crt_scene.h; host-buffer copies: DevBuf::upload / download.
 #include "crt_render.h"
 
@@ -61,14 +61,6 @@ static bool use_impl(const crt_scene* sc, bool dec, bool r16)
     if (!dec || !r16 || !sc->can(CAP_IMPL)) return false;
     const char* e = std::getenv("CRT_IMPL");
     return !(e && e[0] == '0');
-}
-
-// The camera's half-height at distance 1 and aspect ratio (Render.cuh:338-339), as the camera rays of a frame (camera_dir) and of the AOV
-// pass take them
-void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale, float& ar)
-{
-    scale = det_tanf(cam->fov_y / 2);
-    ar = (float)prm->width / (float)prm->height;
 }
 
 struct TraceSetup {
@@ -140,12 +132,24 @@ MegaPlan plan_mega3(const crt_scene* sc, uint32_t traversal, bool want_stats, bo
     return m;
 }
 
+} // namespace
+
+namespace crtk { // (declared in crt_render.h)
+
+// The camera's half-height at distance 1 and aspect ratio (Render.cuh:338-339), as the camera rays of a frame (camera_dir) and of the AOV
+// pass take them
+void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale, float& ar)
+{
+    scale = det_tanf(cam->fov_y / 2);
+    ar = (float)prm->width / (float)prm->height;
+}
+
 // Traces the n query rays in the handle's query pool (p_ro / p_rd, p_res primed: the form k_fill_rays writes) on stream st with the
 // traversal phases of the render kernel itself -- k_mega3 in query form (work item = ray), or k_trace on the fallback pipeline -- and
 // leaves the answers on the device: (t or FLT_MAX, bits(triangle or -1)) of ray i at the returned pointer + i * stride floats (the float4
 // answers of the query form, stride 4, or p_res, stride 2).  Does not synchronize.  crt_intersect and the AOV passes.  first: the rays
 // are those from `first` on in the pool (the pass that follows mirror bounces keeps its rays in two halves of the pool).
-const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride, size_t first = 0)
+const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride, size_t first)
 {
     if (choose_pipeline(sc) == 4) {
         const MegaPlan mp = plan_mega3(sc, traversal, false, false, true, false, n, 0xffffffffu);
@@ -182,9 +186,6 @@ const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool f
     return (const float*)(sc->p_res.p + first);
 }
 
-} // namespace
-
-namespace crtk { // (declared in crt_render.h)
 
 // Whether a range that begins at sample s_begin > 0 continues the frame `f` records (crt_scene::acc for the sum c, crt_scene::var for
 // the sum of squares q): the samples before it are in the sums, and spp, size, shard and layout are the frame's.
@@ -673,16 +674,16 @@ uint32_t chunk_samples(uint32_t nslots, uint32_t s_count)
     return (uint32_t)std::min<uint64_t>(s_count, std::max<uint64_t>(1, max_items / nslots));
 }
 
-// What `who` (crt_render and, through it, every call that renders a frame; crt_render_aov) refuses in a crt_params by itself (no scene,
-// no sample range), before any device call.  `aov`: the AOV pass takes no next-event samples, and its pixel count is tested last.
-int params_check(const char* who, const crt_params* prm, bool aov)
+// What `who` (crt_render and, through it, every call that renders a frame; the AOV passes) refuses in a crt_params by itself (no scene,
+// no sample range), before any device call.  `camera_rays_only`: an AOV pass takes no next-event samples, and its pixel count is tested last.
+int params_check(const char* who, const crt_params* prm, bool camera_rays_only)
 {
     const std::string w(who);
     const bool too_many_pixels = (uint64_t)prm->width * prm->height > 0xffffffffull;
     if (prm->width == 0 || prm->height == 0 || prm->spp == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width, height and spp must be positive");
     if (prm->world == 0 || prm->rank >= prm->world) return fail(CRT_ERR_INVALID_ARG, w + ": need rank < world");
-    if (!aov && (prm->light_sample_n < 0 || prm->light_sample_n > 4096)) return fail(CRT_ERR_INVALID_ARG, w + ": light_sample_n must be in [0, 4096]");
-    if (!aov && too_many_pixels) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels"); // (a render reports it here ...)
+    if (!camera_rays_only && (prm->light_sample_n < 0 || prm->light_sample_n > 4096)) return fail(CRT_ERR_INVALID_ARG, w + ": light_sample_n must be in [0, 4096]");
+    if (!camera_rays_only && too_many_pixels) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^32 pixels"); // (a render reports it here ...)
     if (prm->traversal != CRT_TRAVERSAL_FAST && prm->traversal != CRT_TRAVERSAL_REFERENCE && prm->traversal != CRT_TRAVERSAL_EXACT)
         return fail(CRT_ERR_INVALID_ARG, w + ": unknown traversal mode");
     if (prm->world > 1 && !(prm->flags & CRT_FLAG_TILED_OUTPUT)) return fail(CRT_ERR_INVALID_ARG, w + ": world > 1 needs CRT_FLAG_TILED_OUTPUT");
@@ -750,209 +751,6 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
 }
 
 } // namespace crtk
-
-namespace {
-
-// The first-hit AOV pass (crt_render_aov): the camera rays of samples 0 .. spp-1 of every pixel slot of the shard, in chunks of whole
-// samples of at most kAovChunkRays rays (32 B of query pool + 16 B of results per ray: 1.6 GB), each traced by trace_queries and folded
-// into the per-slot running sums in sample order (k_aov_resolve).  Uses the handle's query pool and trace buffers, as crt_intersect does;
-// the accumulator of a progressive render (accum, acc) is not touched.
-const uint32_t kAovChunkRays = 1u << 25;
-
-// Argument checks of both forms, before any device call
-bool aov_no_buffer(const crt_aov_buffers* out) { return !out->albedo && !out->normal && !out->depth && !out->coverage && !out->tri && !out->material; }
-
-int aov_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out)
-{
-    if (!sc || !cam || !prm || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: null argument");
-    if (aov_no_buffer(out)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov: no output buffer");
-    const int rc = params_check("crt_render_aov", prm, true);
-    if (rc != CRT_OK) return rc;
-    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
-        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov: more than 2^31 pixel slots in a shard");
-    return CRT_OK;
-}
-
-// The same for crt_render_aov_shading: `first` may be null (a struct that is given must name a buffer, as crt_render_aov's), `shading` not
-int aov_shading_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* first, const crt_aov_shading_buffers* shading)
-{
-    if (!sc || !cam || !prm || !shading) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: null argument");
-    if (!shading->emission && !shading->diffuse_albedo) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: no output buffer in shading");
-    if (first && aov_no_buffer(first)) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_shading: no output buffer in first (pass NULL for none)");
-    const int rc = params_check("crt_render_aov_shading", prm, true);
-    if (rc != CRT_OK) return rc;
-    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
-        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov_shading: more than 2^31 pixel slots in a shard");
-    return CRT_OK;
-}
-
-// Which call aov_impl serves.  first_hit: crt_render_aov (out required, shading unused).  shading: crt_render_aov_shading -- out may be
-// null, the resolve's shading form writes both structs from the one trace and a slot has four accumulator rows.
-enum class AovForm { first_hit, shading };
-
-// The pass on device buffers.  The entry point has checked the arguments of its form (aov_check / aov_shading_check), once.
-int aov_impl(AovForm form, crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* out, const crt_aov_shading_buffers* shading,
-             hipStream_t st, crt_aov_info* info)
-{
-    if (form == AovForm::first_hit) shading = nullptr;
-    const crt_aov_buffers none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!out) out = &none;
-    const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
-    const Shard sh = make_shard(prm->width, prm->height, prm->world);
-    return hip_guard([&]() -> int {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
-        const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
-        sc->p_ro.ensure(max_rays); sc->p_rd.ensure(max_rays); sc->p_res.ensure(max_rays);
-        sc->aov_acc.ensure((size_t)sh.nslots * (shading ? kAovAccRowsShading : kAovAccRows));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (info) {
-            ensure_events(sc);
-            e0 = sc->ev[0]; e1 = sc->ev[1];
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
-        AovParams A;
-        std::memset(&A, 0, sizeof(A));
-        std::memcpy(A.eye, cam->eye, sizeof(A.eye));
-        std::memcpy(A.inv_view, cam->inv_view, sizeof(A.inv_view));
-        camera_scale_ar(cam, prm, A.scale, A.ar);
-        fill_slot_map(A, *prm, tiled, sh);
-        A.seed = prm->seed; A.spp = prm->spp;
-        A.pool.ro = sc->p_ro.p; A.pool.rd = sc->p_rd.p; A.pool.res = sc->p_res.p;
-        A.tri_nm = sc->dev.tri_nm; A.mats = sc->dev.mats; A.acc = sc->aov_acc.p;
-        A.albedo = out->albedo; A.normal = out->normal; A.depth = out->depth; A.coverage = out->coverage; A.tri = out->tri; A.material = out->material;
-        const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
-        uint64_t rays = 0;
-        uint32_t chunks = 0;
-        for (uint32_t s0 = 0; s0 < prm->spp; s0 += chunk) {
-            const uint32_t ns = std::min(chunk, prm->spp - s0);
-            const uint32_t n = ns * sh.nslots;
-            A.sample_begin = s0; A.n_samples = ns; A.pool.n = n;
-            A.first_chunk = s0 == 0; A.last_chunk = s0 + ns == prm->spp;
-            launch_aov_rays(A, st);
-            HIP_CHECK(hipGetLastError());
-            A.res = trace_queries(sc, n, prm->traversal, force_exact, st, A.res_stride);
-            if (shading) launch_aov_resolve_shading(A, AovShadingOut{shading->emission, shading->diffuse_albedo}, st);
-            else launch_aov_resolve(A, st);
-            HIP_CHECK(hipGetLastError());
-            rays += n;
-            chunks++;
-        }
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->rays = rays; info->chunks = chunks;
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-        return CRT_OK;
-    });
-}
-
-// The AOV pass that follows mirror bounces (crt_render_aov_specular): chunks as aov_impl's.  After a chunk's camera rays are traced,
-// k_aov_bounce advances every item's chain and compacts the reflected rays into the other half of the query pool (the halves alternate
-// from bounce to bounce: a stage never writes the rays or answers another of its threads still reads); the host reads their count --
-// one 4-byte copy into pinned memory and one synchronization per bounce and chunk -- traces that many and runs the next stage on their
-// answers.  A count of 0 ends the chunk's bounces; the stage after the last bounce allowed has nothing to compact and needs no count.
-int aov_specular_check(const crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp, const crt_aov_specular_buffers* out)
-{
-    if (!sc || !cam || !prm || !sp || !out) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: null argument");
-    if (!out->guide_albedo && !out->last_normal && !out->path_depth && !out->bounces && !out->last_tri)
-        return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: no output buffer");
-    if (sp->max_bounces < 1 || sp->max_bounces > 8) return fail(CRT_ERR_INVALID_ARG, "crt_render_aov_specular: max_bounces must be in [1, 8]");
-    const int rc = params_check("crt_render_aov_specular", prm, true);
-    if (rc != CRT_OK) return rc;
-    if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
-        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov_specular: more than 2^31 pixel slots in a shard");
-    return CRT_OK;
-}
-
-int aov_specular_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp, const crt_aov_specular_buffers* out,
-                      hipStream_t st, crt_aov_info* info)
-{
-    const int rc = aov_specular_check(sc, cam, prm, sp, out);
-    if (rc != CRT_OK) return rc;
-    const bool tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
-    const Shard sh = make_shard(prm->width, prm->height, prm->world);
-    return hip_guard([&]() -> int {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint32_t chunk = std::min<uint32_t>(prm->spp, std::max<uint32_t>(1u, kAovChunkRays / sh.nslots));
-        const uint64_t max_rays = (uint64_t)chunk * sh.nslots;
-        // every buffer at its final size before the first launch: growing one later would drop what a stage has left in it
-        sc->p_ro.ensure(2 * max_rays); sc->p_rd.ensure(2 * max_rays); sc->p_res.ensure(2 * max_rays); sc->aovs_item.ensure(2 * max_rays);
-        sc->aovs_state.ensure(max_rays); sc->aovs_aux.ensure(max_rays);
-        if (choose_pipeline(sc) == 4) (void)sc->L.answers(max_rays);
-        sc->aov_acc.ensure((size_t)sh.nslots * kAovAccRows);
-        sc->aovs_count.ensure_uncached(1);
-        if (!sc->h_aovs_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_aovs_count, sizeof(unsigned int), hipHostMallocDefault));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (info) {
-            ensure_events(sc);
-            e0 = sc->ev[0]; e1 = sc->ev[1];
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
-        AovParams A;
-        std::memset(&A, 0, sizeof(A));
-        std::memcpy(A.eye, cam->eye, sizeof(A.eye));
-        std::memcpy(A.inv_view, cam->inv_view, sizeof(A.inv_view));
-        camera_scale_ar(cam, prm, A.scale, A.ar);
-        fill_slot_map(A, *prm, tiled, sh);
-        A.seed = prm->seed; A.spp = prm->spp;
-        A.pool.ro = sc->p_ro.p; A.pool.rd = sc->p_rd.p; A.pool.res = sc->p_res.p;
-        AovSpecParams S;
-        std::memset(&S, 0, sizeof(S));
-        fill_slot_map(S, *prm, tiled, sh);
-        S.spp = prm->spp; S.max_bounces = sp->max_bounces;
-        S.count = sc->aovs_count.p; S.state = sc->aovs_state.p; S.aux = sc->aovs_aux.p;
-        S.tri_nm = sc->dev.tri_nm; S.mats = sc->dev.mats; S.acc = sc->aov_acc.p;
-        S.guide_albedo = out->guide_albedo; S.last_normal = out->last_normal; S.path_depth = out->path_depth; S.bounces = out->bounces; S.last_tri = out->last_tri;
-        const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
-        uint64_t rays = 0;
-        uint32_t chunks = 0;
-        for (uint32_t s0 = 0; s0 < prm->spp; s0 += chunk) {
-            const uint32_t ns = std::min(chunk, prm->spp - s0);
-            const uint32_t n = ns * sh.nslots;
-            A.sample_begin = s0; A.n_samples = ns; A.pool.n = n;
-            launch_aov_rays(A, st);
-            HIP_CHECK(hipGetLastError());
-            S.res = trace_queries(sc, n, prm->traversal, force_exact, st, S.res_stride);
-            rays += n;
-            size_t in = 0, outh = max_rays; // where in the pool the rays traced last are, and where those that go on are put
-            uint32_t n_in = n;
-            for (uint32_t stage = 0; n_in > 0; stage++) {
-                S.stage0 = stage == 0; S.n_in = n_in;
-                S.in_ro = sc->p_ro.p + in; S.in_rd = sc->p_rd.p + in; S.in_item = sc->aovs_item.p + in;
-                S.out_ro = sc->p_ro.p + outh; S.out_rd = sc->p_rd.p + outh; S.out_res = sc->p_res.p + outh; S.out_item = sc->aovs_item.p + outh;
-                HIP_CHECK(hipMemsetAsync(sc->aovs_count.p, 0, sizeof(unsigned int), st));
-                launch_aov_bounce(S, st);
-                HIP_CHECK(hipGetLastError());
-                if (stage == sp->max_bounces) break; // (every chain that came this far is at the cap)
-                HIP_CHECK(hipMemcpyAsync(sc->h_aovs_count, sc->aovs_count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of a bounce: how many rays go on
-                n_in = std::min<uint32_t>(*sc->h_aovs_count, n_in);
-                if (n_in == 0) break;
-                S.res = trace_queries(sc, n_in, prm->traversal, force_exact, st, S.res_stride, outh);
-                rays += n_in;
-                std::swap(in, outh);
-            }
-            S.n_samples = ns;
-            S.first_chunk = s0 == 0; S.last_chunk = s0 + ns == prm->spp;
-            launch_aov_spec_resolve(S, st);
-            HIP_CHECK(hipGetLastError());
-            chunks++;
-        }
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->rays = rays; info->chunks = chunks;
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-        return CRT_OK;
-    });
-}
-
-} // namespace
 
 extern "C" {
 
@@ -1126,103 +924,6 @@ int crt_intersect(crt_scene* sc, uint32_t n, const float* origins, const float* 
             std::memcpy(&tri, &res[(size_t)i * stride + 1], 4);
             answer(i, res[(size_t)i * stride], tri);
         }
-        return CRT_OK;
-    });
-}
-
-int crt_render_aov_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_out, void* stream, crt_aov_info* info)
-{
-    const int rc = aov_check(sc, cam, prm, dev_out);
-    if (rc != CRT_OK) return rc;
-    return aov_impl(AovForm::first_hit, sc, cam, prm, dev_out, nullptr, (hipStream_t)stream, info);
-}
-
-int crt_render_aov(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* host_out, crt_aov_info* info)
-{
-    const int rc0 = aov_check(sc, cam, prm, host_out);
-    if (rc0 != CRT_OK) return rc0;
-    const crt_aov_buffers& h = *host_out;
-    return hip_guard([&]() -> int {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
-        void* const host[6] = {h.albedo, h.normal, h.depth, h.coverage, h.tri, h.material}; // 4-byte values: three per pixel, three, then one each
-        DevBuf<float> buf[6];
-        for (int i = 0; i < 6; i++)
-            if (host[i]) buf[i].alloc(npix * (i < 2 ? 3 : 1));
-        const crt_aov_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p, (int32_t*)buf[5].p};
-        const int rc = aov_impl(AovForm::first_hit, sc, cam, prm, &d, nullptr, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        for (int i = 0; i < 6; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
-        return CRT_OK;
-    });
-}
-
-int crt_render_aov_shading_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* dev_first,
-                                  const crt_aov_shading_buffers* dev_shading, void* stream, crt_aov_info* info)
-{
-    const int rc = aov_shading_check(sc, cam, prm, dev_first, dev_shading);
-    if (rc != CRT_OK) return rc;
-    return aov_impl(AovForm::shading, sc, cam, prm, dev_first, dev_shading, (hipStream_t)stream, info);
-}
-
-int crt_render_aov_shading(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_buffers* host_first,
-                           const crt_aov_shading_buffers* host_shading, crt_aov_info* info)
-{
-    const int rc0 = aov_shading_check(sc, cam, prm, host_first, host_shading);
-    if (rc0 != CRT_OK) return rc0;
-    return hip_guard([&]() -> int {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
-        const crt_aov_buffers none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        const crt_aov_buffers& h = host_first ? *host_first : none;
-        // 4-byte values: crt_aov_buffers' six (three per pixel, three, then one each), then the two shading buffers (three per pixel)
-        void* const host[8] = {h.albedo, h.normal, h.depth, h.coverage, h.tri, h.material, host_shading->emission, host_shading->diffuse_albedo};
-        const auto values = [](int i) { return (i < 2 || i >= 6) ? 3 : 1; };
-        DevBuf<float> buf[8];
-        for (int i = 0; i < 8; i++)
-            if (host[i]) buf[i].alloc(npix * values(i));
-        const crt_aov_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p, (int32_t*)buf[5].p};
-        const crt_aov_shading_buffers ds{buf[6].p, buf[7].p};
-        const int rc = aov_impl(AovForm::shading, sc, cam, prm, host_first ? &d : nullptr, &ds, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        for (int i = 0; i < 8; i++) buf[i].download((float*)host[i], npix * values(i));
-        return CRT_OK;
-    });
-}
-
-int crt_aov_specular_defaults(crt_aov_specular_params* p)
-{
-    if (!p) return fail(CRT_ERR_INVALID_ARG, "crt_aov_specular_defaults: null argument");
-    p->max_bounces = 2;
-    return CRT_OK;
-}
-
-int crt_render_aov_specular_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp,
-                                   const crt_aov_specular_buffers* dev_out, void* stream, crt_aov_info* info)
-{
-    return aov_specular_impl(sc, cam, prm, sp, dev_out, (hipStream_t)stream, info);
-}
-
-int crt_render_aov_specular(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_specular_params* sp,
-                            const crt_aov_specular_buffers* host_out, crt_aov_info* info)
-{
-    const int rc0 = aov_specular_check(sc, cam, prm, sp, host_out);
-    if (rc0 != CRT_OK) return rc0;
-    const crt_aov_specular_buffers& h = *host_out;
-    return hip_guard([&]() -> int {
-        HIP_CHECK(hipSetDevice(sc->device));
-        const uint64_t npix = out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
-        void* const host[5] = {h.guide_albedo, h.last_normal, h.path_depth, h.bounces, h.last_tri}; // 4-byte values: three per pixel, three, then one each
-        DevBuf<float> buf[5];
-        for (int i = 0; i < 5; i++)
-            if (host[i]) buf[i].alloc(npix * (i < 2 ? 3 : 1));
-        const crt_aov_specular_buffers d{buf[0].p, buf[1].p, buf[2].p, buf[3].p, (int32_t*)buf[4].p};
-        const int rc = aov_specular_impl(sc, cam, prm, sp, &d, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        for (int i = 0; i < 5; i++) buf[i].download((float*)host[i], npix * (i < 2 ? 3 : 1));
         return CRT_OK;
     });
 }

@@ -1,6 +1,6 @@
 // cudaraytracing_amd/csrc/crt_scene.h -- the scene handle of the device layer (struct crt_scene: the uploaded arrays, the buffers and
 // events a frame uses, what a progressive render has accumulated) and the small helpers crt_scene.hip (create / export / destroy) and
-// crt_render.hip / crt_sparse.hip (the launch logic) share: the shard of a frame, its slot map for the image-space kernels, the host's form of the slot rule.
+// crt_render.hip / crt_sparse.hip / crt_aov_pass.hip (the launch logic) share: the shard of a frame, its slot map for the image-space kernels, the host's form of the slot rule.
 #ifndef CRT_SCENE_H
 #define CRT_SCENE_H
 #include "crt_internal.h"

@@ -383,12 +383,11 @@ def test_adaptive_limits(renders, name):
 
 @pytest.mark.gpu
 def test_adaptive_device_form_on_a_stream_matches_host_form(renders):
-    from test_variance import hip_runtime
     name = "veach-mis"
     r = renders[name]
     host = gpu_adaptive(r, name)
     check_frame(host, restated(name), "host form")
-    H_ = hip_runtime()
+    H_ = util.hip_runtime()
     eye, iv, fov = util.camera(name)
     ptrs, stream = {}, C.c_void_p()
     sizes = {"rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "var": W * H * 12}
@@ -477,7 +476,6 @@ def test_adaptive_leaves_no_frame_in_flight(monkeypatch):
 @pytest.mark.gpu
 def test_cli_writes_the_adaptive_frame_and_its_samples(renders, tmp_path):
     from cudaraytracing_amd import build as b
-    from test_variance import read_pfm
     cli = b.build_cli()
     name = "veach-mis"
     cfg = util.SCENES[name]
@@ -491,8 +489,8 @@ def test_cli_writes_the_adaptive_frame_and_its_samples(renders, tmp_path):
     ref = str(tmp_path / "python.png")
     renders[name].save_frame_buffer(ref)
     assert open(png, "rb").read() == open(ref, "rb").read()
-    assert_bits(read_pfm(pfm), got["samples"].astype(F), "--adaptive-samples")
-    assert_bits(read_pfm(vpfm), got["variance"], "--variance of the adaptive frame")
+    assert_bits(util.read_pfm(pfm)[1], got["samples"].astype(F), "--adaptive-samples")
+    assert_bits(util.read_pfm(vpfm)[1], got["variance"], "--variance of the adaptive frame")
     bad = subprocess.run([cli, cfg, "--adaptive-samples", pfm], capture_output=True, text=True, timeout=60)
     assert bad.returncode == 1 and "--adaptive" in bad.stderr
     bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--adaptive", "0.1"], capture_output=True, text=True, timeout=60)

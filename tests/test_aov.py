@@ -13,24 +13,10 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
-import oracle_lib as O
 import util
 
 NAMES = ("albedo", "normal", "depth", "coverage", "tri", "material")
 AOV_EXPORTS = ("crt_render_aov", "crt_render_aov_device", "crt_write_pfm")
-
-
-def read_pfm(path):
-    """(header lines, array with row 0 = image top) of a little-endian PFM, read with numpy alone."""
-    raw = open(path, "rb").read()
-    parts = raw.split(b"\n", 3)
-    kind, dims, scale, body = parts
-    w, h = (int(v) for v in dims.split())
-    ch = {b"PF": 3, b"Pf": 1}[kind]
-    a = np.frombuffer(body, dtype="<f4")
-    assert a.size == w * h * ch
-    a = a.reshape((h, w, ch) if ch == 3 else (h, w))
-    return (kind, dims, scale), np.ascontiguousarray(a[::-1])
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU --
@@ -81,6 +67,37 @@ def test_aov_arguments_are_checked_before_any_device_call():
     both(sc, C.byref(cam), C.byref(bad_mode), C.byref(bufs))
 
 
+def test_every_aov_entry_point_refuses_the_shared_bad_inputs():
+    """The six entry points share one argument check: each bad input is CRT_ERR_INVALID_ARG from every one of them, before any device
+    call, and the message begins with the entry's base name.  The scene is a dummy that must never be dereferenced."""
+    lib = capi.lib()
+    dummy = C.create_string_buffer(256)
+    sc, cam, sp = C.cast(dummy, C.c_void_p), capi.Camera(), capi.AovSpecularParams(2)
+    buf = np.zeros(64 * 48 * 3, dtype=np.float32)
+    first, shading, specular = capi.AovBuffers(), capi.AovShadingBuffers(), capi.AovSpecularBuffers()
+    first.albedo = shading.emission = specular.guide_albedo = buf.ctypes.data
+
+    def params(**fields):
+        p = capi.Params(64, 48, 4, 0.6, 1, 0, 0, 1, capi.TRAVERSAL_EXACT, 0)
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    bad = {"null scene": (None, C.byref(cam), params()), "null camera": (sc, None, params()), "null params": (sc, C.byref(cam), None),
+           "spp 0": (sc, C.byref(cam), params(spp=0)), "width 0": (sc, C.byref(cam), params(width=0)), "height 0": (sc, C.byref(cam), params(height=0)),
+           "rank >= world": (sc, C.byref(cam), params(rank=3, world=3, flags=capi.FLAG_TILED_OUTPUT)),
+           "world > 1, not tiled": (sc, C.byref(cam), params(rank=1, world=3)), "unknown traversal": (sc, C.byref(cam), params(traversal=7))}
+    # what each form takes between the params and (the device form's stream and) the info
+    own = {"crt_render_aov": (C.byref(first),), "crt_render_aov_shading": (None, C.byref(shading)),
+           "crt_render_aov_specular": (C.byref(sp), C.byref(specular))}
+    for base, args in own.items():
+        for fn, tail in ((base, (None,)), (base + "_device", (None, None))):
+            for what, head in bad.items():
+                rc = getattr(lib, fn)(*head, *args, *tail)
+                err = lib.crt_last_error()
+                assert rc == capi.ERR_INVALID_ARG and err.startswith(base.encode() + b": "), (fn, what, rc, err)
+
+
 def test_write_pfm_round_trips(tmp_path):
     rng = np.random.default_rng(5)
     one = (rng.normal(size=(5, 7)) * 1e3).astype(np.float32)
@@ -93,7 +110,7 @@ def test_write_pfm_round_trips(tmp_path):
         capi.check(lib.crt_write_pfm(path.encode(), a.shape[1], a.shape[0], ch, capi.ptr(a)), "crt_write_pfm")
         raw = open(path, "rb").read()
         assert raw.startswith(kind + b"\n%d %d\n-1.0\n" % (a.shape[1], a.shape[0]))
-        hdr, back = read_pfm(path)
+        hdr, back = util.read_pfm(path)
         assert hdr == (kind, b"%d %d" % (a.shape[1], a.shape[0]), b"-1.0")
         assert np.array_equal(back.view(np.uint32), a.view(np.uint32))
         # bottom-up rows: the file's first row is the image's last
@@ -124,28 +141,10 @@ def renders():
 def primary_rays(name, width, height, spp, crop=None, seed=0):
     """The oracle's primary rays of a render (crop of a width x height frame): (origins, directions, t, tri) as (pixels, spp, ...)
     arrays in pixel order, then sample order."""
-    sc = util.oracle_scene(name)
-    t = util.task(name)
     eye, iv, fov = util.camera(name)
-    L = O.lib()
-    L.orc_ray_log_begin.restype = None
-    L.orc_ray_log_end.restype = C.c_uint64
-    L.orc_ray_log_end.argtypes = [C.c_void_p, C.c_uint64]
-    L.orc_ray_log_begin()
-    sc.render(eye, iv, fov, width, height, spp, 0.0, t.light_sample_n, seed=seed, crop=crop)
-    n = int(L.orc_ray_log_end(None, 0))
-    log = np.zeros((n, 10), dtype=np.float32)
-    L.orc_ray_log_end(log.ctypes.data_as(C.c_void_p), n)
-    eye32 = np.asarray(eye, dtype=np.float32)
-    keep = np.isnan(log[:, 8]) & np.all(log[:, 0:3].view(np.uint32) == eye32.view(np.uint32), axis=1)
-    prim = log[keep]
-    cw, ch = (crop[2], crop[3]) if crop else (width, height)
-    assert prim.shape[0] == cw * ch * spp
-    # (pixel, sample) order: with p_rr = 0 each path is its camera ray and that vertex's next-event samples, so the camera rays are
-    # the log's closest-hit rays from the eye, one path after the other
+    o, d, t, tri, (ch, cw) = util.primary_rays_of(util.oracle_scene(name), eye, iv, fov, util.task(name).light_sample_n, width, height, spp, crop, seed)
     p = cw * ch
-    return (prim[:, 0:3].reshape(p, spp, 3), prim[:, 3:6].reshape(p, spp, 3), prim[:, 6].reshape(p, spp),
-            prim[:, 7].astype(np.int32).reshape(p, spp), (ch, cw))
+    return o.reshape(p, spp, 3), d.reshape(p, spp, 3), t.reshape(p, spp), tri.reshape(p, spp), (ch, cw)
 
 
 def expected_aov(name, width, height, spp, crop=None, seed=0):
@@ -175,19 +174,6 @@ def expected_aov(name, width, height, spp, crop=None, seed=0):
             "coverage": cov.reshape(ch, cw), "tri": tri0.reshape(ch, cw), "material": mat0.reshape(ch, cw)}
 
 
-def assert_same(got, want, where=""):
-    for n in NAMES:
-        if n not in want:
-            continue
-        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
-        assert g.shape == w.shape, (n, g.shape, w.shape)
-        if g.dtype == np.float32:
-            same = g.view(np.uint32) == w.view(np.uint32)
-        else:
-            same = g == w
-        assert same.all(), "%s %s: %d of %d values differ" % (where, n, int((~same).sum()), same.size)
-
-
 def run_aov(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0):
     eye, iv, fov = util.camera(name)
     r.set_spp(spp)
@@ -206,7 +192,7 @@ def test_aov_small_frames_match_oracle(renders, name):
     got = run_aov(renders[name], name, 4, 64, 48)
     assert renders[name].aov_info["chunks"] == 1 and renders[name].aov_info["rays"] == 64 * 48 * 4
     want = expected_aov(name, 64, 48, 4)
-    assert_same(got, want, name)
+    util.assert_same(got, want, NAMES, name)
     assert (got["tri"] >= 0).any() and (got["coverage"] > 0).any()
 
 
@@ -220,7 +206,7 @@ def test_aov_crop_of_full_camera_in_chunks(renders, name, x0, y0):
     assert info["chunks"] >= 2 and info["rays"] == 800 * 600 * spp, info
     want = expected_aov(name, 800, 600, spp, crop=(x0, y0, 24, 16))
     crop = {n: got[n][y0:y0 + 16, x0:x0 + 24] for n in NAMES}
-    assert_same(crop, want, name)
+    util.assert_same(crop, want, NAMES, name)
 
 
 @pytest.mark.gpu
@@ -240,7 +226,7 @@ def test_aov_spp1_equals_intersect_on_the_logged_primary_rays(renders, name):
 def test_aov_traversal_modes_agree(renders, name):
     base = run_aov(renders[name], name, 4, 64, 48, seed=3)
     for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST):
-        assert_same(run_aov(renders[name], name, 4, 64, 48, traversal=mode, seed=3), base, "%s mode %d" % (name, mode))
+        util.assert_same(run_aov(renders[name], name, 4, 64, 48, traversal=mode, seed=3), base, NAMES, "%s mode %d" % (name, mode))
 
 
 @pytest.mark.gpu
@@ -249,7 +235,7 @@ def test_aov_kernel_variants_agree(renders, var, value, monkeypatch):
     base = {n: run_aov(renders[n], n, 4, 64, 48) for n in renders}
     monkeypatch.setenv(var, value)
     for n in renders:
-        assert_same(run_aov(renders[n], n, 4, 64, 48), base[n], "%s %s=%s" % (n, var, value))
+        util.assert_same(run_aov(renders[n], n, 4, 64, 48), base[n], NAMES, "%s %s=%s" % (n, var, value))
 
 
 @pytest.mark.gpu
@@ -277,7 +263,7 @@ def test_aov_tiled_shards_deinterleave_to_row_major(renders):
     for n in NAMES:
         img = untile_numpy(np.stack(shards[n]), w, h)
         img = img if capi.AOV_BUFFERS[n][0] == 3 else img[:, :, 0]
-        assert_same({n: img}, {n: full[n]}, "tiled")
+        util.assert_same({n: img}, full, (n,), "tiled")
         # padding slots: every slot of the gathered tiles that is no pixel
         tx, ty = (w + 7) // 8, (h + 7) // 8
         g = np.stack(shards[n])
@@ -303,7 +289,7 @@ def test_aov_calls_between_progressive_ranges(renders, pipeline, monkeypatch):
     one_mean = r.mean_buffer.copy()
     aov = r.run_view_aov(eye, iv, fov, width=64, height=48)
     assert r.run_view_range(eye, iv, fov, 0, 1, width=64, height=48) is None
-    assert_same(r.run_view_aov(eye, iv, fov, width=64, height=48), aov, "after range 0")
+    util.assert_same(r.run_view_aov(eye, iv, fov, width=64, height=48), aov, NAMES, "after range 0")
     _, _, done = r.preview(width=64, height=48)
     assert done == 1
     assert r.run_view_range(eye, iv, fov, 1, 2, width=64, height=48) is None
@@ -313,62 +299,21 @@ def test_aov_calls_between_progressive_ranges(renders, pipeline, monkeypatch):
     assert np.array_equal(r.mean_buffer.view(np.uint32), one_mean.view(np.uint32))
 
 
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
 @pytest.mark.gpu
 def test_aov_device_form_on_a_stream_matches_host_form(renders):
     name, w, h = "veach-mis", 80, 56
     r = renders[name]
     want = run_aov(r, name, 3, w, h)
     eye, iv, fov = util.camera(name)
-    H = hip_runtime()
-    ptrs, sizes = {}, {}
-    stream = C.c_void_p()
-    try:
-        for n in NAMES:
-            sizes[n] = w * h * capi.AOV_BUFFERS[n][0] * 4
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), sizes[n]) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, sizes[n]) == 0  # (every value must be written by the pass)
-        assert H.hipStreamCreate(C.byref(stream)) == 0
-        assert r.run_view_aov_device(eye, iv, fov, ptrs, stream=stream.value, want_info=False, width=w, height=h) is None
-        assert H.hipStreamSynchronize(stream) == 0
-
-        def fetch(names):
-            out = {}
-            for n in names:
-                ch, dt = capi.AOV_BUFFERS[n]
-                a = np.zeros((h, w, ch) if ch == 3 else (h, w), dtype=dt)
-                assert H.hipMemcpy(a.ctypes.data, ptrs[n], sizes[n], 2) == 0  # hipMemcpyDeviceToHost
-                out[n] = a
-            return out
-
-        assert_same(fetch(NAMES), want, "device form")
+    with util.DeviceBuffers({n: capi.AOV_BUFFERS[n] for n in NAMES}, w, h) as d:
+        assert r.run_view_aov_device(eye, iv, fov, d.ptrs, stream=d.stream, want_info=False, width=w, height=h) is None
+        d.synchronize()
+        util.assert_same(d.fetch(NAMES), want, NAMES, "device form")
         # a subset of the buffers, with the pass's timer (the call synchronizes the stream)
-        assert H.hipMemset(C.c_void_p(ptrs["depth"]), 0, sizes["depth"]) == 0
-        info = r.run_view_aov_device(eye, iv, fov, {"depth": ptrs["depth"]}, stream=stream.value, width=w, height=h)
+        d.fill("depth", 0)
+        info = r.run_view_aov_device(eye, iv, fov, {"depth": d.ptrs["depth"]}, stream=d.stream, width=w, height=h)
         assert info["chunks"] == 1 and info["rays"] == w * h * 3 and info["total_ms"] > 0
-        assert_same(fetch(["depth"]), {"depth": want["depth"]}, "subset")
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        util.assert_same(d.fetch(["depth"]), want, ("depth",), "subset")
 
 
 def to_u8(v):
@@ -393,7 +338,7 @@ def test_cli_writes_aov_files(renders, tmp_path):
     nrm = to_u8(np.float32(255.0) * np.clip((got["normal"] + one) / two, np.float32(0), np.float32(1)))
     assert np.array_equal(np.asarray(Image.open(prefix + "_albedo.png")), alb)
     assert np.array_equal(np.asarray(Image.open(prefix + "_normal.png")), nrm)
-    hdr, depth = read_pfm(prefix + "_depth.pfm")
+    hdr, depth = util.read_pfm(prefix + "_depth.pfm")
     assert hdr[0] == b"Pf" and hdr[2] == b"-1.0"
     assert np.array_equal(depth.view(np.uint32), got["depth"].view(np.uint32))
     bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--aov", prefix], capture_output=True, text=True, timeout=60)

@@ -161,16 +161,6 @@ def renders():
         r.free()
 
 
-def assert_same(got, want, where=""):
-    for n in NAMES + aov.NAMES:
-        if n not in want:
-            continue
-        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
-        assert g.shape == w.shape and g.dtype == w.dtype, (n, g.shape, w.shape)
-        same = g.view(np.uint32) == w.view(np.uint32)
-        assert same.all(), "%s %s: %d of %d values differ (first at %r)" % (where, n, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
-
-
 def run_shading(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0, **kw):
     eye, iv, fov = util.camera(name)
     r.set_spp(spp)
@@ -186,7 +176,7 @@ def run_shading(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_E
 def check_small_frame(renders, name, traversal):
     got = run_shading(renders[name], name, 4, 64, 48, traversal=traversal, first=aov.NAMES)
     assert renders[name].aov_info["chunks"] == 1 and renders[name].aov_info["rays"] == 64 * 48 * 4
-    assert_same(got, expected_shading(name, 64, 48, 4), name)
+    util.assert_same(got, expected_shading(name, 64, 48, 4), NAMES, name)
     return got
 
 
@@ -204,8 +194,8 @@ def test_shading_small_frames_match_oracle(renders, name, traversal):
         assert (k["all_emitter"], k["mixed"]) == (33, 17)
     got = check_small_frame(renders, name, traversal)
     # the same trace also serves crt_render_aov's struct: its six buffers have that call's bits
-    assert_same(got, aov.run_aov(renders[name], name, 4, 64, 48, traversal=traversal), "%s first" % name)
-    aov.assert_same(got, aov.expected_aov(name, 64, 48, 4), "%s first against the oracle" % name)
+    util.assert_same(got, aov.run_aov(renders[name], name, 4, 64, 48, traversal=traversal), aov.NAMES, "%s first" % name)
+    util.assert_same(got, aov.expected_aov(name, 64, 48, 4), aov.NAMES, "%s first against the oracle" % name)
     # where no sample hits an emitter the split changes nothing
     _, emit, _, _, _ = hits_of(name, 64, 48, 4)
     quiet = ~emit.any(axis=1).reshape(48, 64)
@@ -226,11 +216,11 @@ def test_shading_fast_traversal_and_a_subset_of_the_buffers(renders):
     name = "veach-mis"
     want = expected_shading(name, 64, 48, 4)
     got = run_shading(renders[name], name, 4, 64, 48, traversal=crt.TRAVERSAL_FAST)
-    assert_same(got, want, "fast")
+    util.assert_same(got, want, NAMES, "fast")
     for n in NAMES:  # one buffer alone, without `first`
         got = run_shading(renders[name], name, 4, 64, 48, want=(n,))
         assert tuple(got) == (n,)
-        assert_same(got, {n: want[n]}, "only " + n)
+        util.assert_same(got, want, (n,), "only " + n)
 
 
 @pytest.mark.gpu
@@ -296,8 +286,8 @@ def test_shading_crop_of_full_camera_in_chunks(renders, name):
     info = renders[name].aov_info
     assert info["chunks"] >= 2 and info["rays"] == 800 * 600 * spp, info
     crop = {n: got[n][y0:y0 + ch, x0:x0 + cw] for n in got}
-    assert_same(crop, want, name)
-    aov.assert_same(crop, {n: v for n, v in aov.expected_aov(name, 800, 600, spp, crop=(x0, y0, cw, ch)).items() if n in crop}, name + " first")
+    util.assert_same(crop, want, NAMES, name)
+    util.assert_same(crop, aov.expected_aov(name, 800, 600, spp, crop=(x0, y0, cw, ch)), ("albedo", "depth", "tri"), name + " first")
 
 
 @pytest.mark.gpu
@@ -307,45 +297,20 @@ def test_shading_device_form_on_a_stream_matches_host_form(renders):
     want = run_shading(r, name, 3, w, h, first=("normal", "material"))
     assert (want["emission"] != 0).any()
     eye, iv, fov = util.camera(name)
-    H = aov.hip_runtime()
     tables = dict(capi.AOV_BUFFERS, **capi.AOV_SHADING_BUFFERS)
-    ptrs, sizes = {}, {}
-    stream = C.c_void_p()
-    try:
-        for n in want:
-            sizes[n] = w * h * tables[n][0] * 4
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), sizes[n]) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, sizes[n]) == 0  # (every value must be written by the pass)
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+    with util.DeviceBuffers({n: tables[n] for n in want}, w, h) as d:
         r.set_spp(3)
-        assert r.run_view_aov_shading_device(eye, iv, fov, {n: ptrs[n] for n in NAMES}, first_ptrs={n: ptrs[n] for n in ("normal", "material")},
-                                             stream=stream.value, want_info=False, width=w, height=h) is None
-        assert H.hipStreamSynchronize(stream) == 0
-
-        def fetch(names):
-            out = {}
-            for n in names:
-                ch, dt = tables[n]
-                a = np.zeros((h, w, ch) if ch == 3 else (h, w), dtype=dt)
-                assert H.hipMemcpy(a.ctypes.data, ptrs[n], sizes[n], 2) == 0  # hipMemcpyDeviceToHost
-                out[n] = a
-            return out
-
-        assert_same(fetch(want), want, "device form")
+        assert r.run_view_aov_shading_device(eye, iv, fov, {n: d.ptrs[n] for n in NAMES}, first_ptrs={n: d.ptrs[n] for n in ("normal", "material")},
+                                             stream=d.stream, want_info=False, width=w, height=h) is None
+        d.synchronize()
+        util.assert_same(d.fetch(want), want, tuple(want), "device form")
         # one buffer, no `first`, with the pass's timer (the call synchronizes the stream)
-        assert H.hipMemset(C.c_void_p(ptrs["emission"]), 0, sizes["emission"]) == 0
-        info = r.run_view_aov_shading_device(eye, iv, fov, {"emission": ptrs["emission"]}, stream=stream.value, width=w, height=h)
+        d.fill("emission", 0)
+        info = r.run_view_aov_shading_device(eye, iv, fov, {"emission": d.ptrs["emission"]}, stream=d.stream, width=w, height=h)
         assert info["chunks"] == 1 and info["rays"] == w * h * 3 and info["total_ms"] > 0
-        assert_same(fetch(["emission"]), {"emission": want["emission"]}, "subset")
+        util.assert_same(d.fetch(["emission"]), want, ("emission",), "subset")
         with pytest.raises(ValueError):
-            r.run_view_aov_shading_device(eye, iv, fov, {"albedo": ptrs["emission"]}, width=w, height=h)
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+            r.run_view_aov_shading_device(eye, iv, fov, {"albedo": d.ptrs["emission"]}, width=w, height=h)
 
 
 @pytest.mark.gpu
@@ -360,7 +325,7 @@ def test_cli_writes_the_shading_files(renders, tmp_path):
     got = run_shading(renders["veach-mis"], "veach-mis", 2, 96, 72, seed=42)
     assert (got["emission"] != 0).any()
     for n in NAMES:
-        hdr, a = aov.read_pfm("%s.%s.pfm" % (prefix, n))
+        hdr, a = util.read_pfm("%s.%s.pfm" % (prefix, n))
         assert hdr[0] == b"PF" and hdr[2] == b"-1.0"
         assert (util.bits(a) == util.bits(got[n])).all(), n
     bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--aov-shading", prefix], capture_output=True, text=True, timeout=60)

@@ -2,8 +2,8 @@
 run_view_denoised(specular_guides=True) in Python; crt_cli --aov-specular / --denoise-specular).
 
 The expected buffers are the contract of include/crt.h restated in numpy float32: the oracle's primary rays (its ray log, as
-tests/test_aov.py takes them), the bounces through OracleScene.intersect -- which normalises a raw direction as Ray's constructor does
--- and kd, ke, normal and mode from OracleScene.tris().  Every buffer must match bit for bit.
+tests/test_aov.py takes them: util.primary_rays_of), the bounces through OracleScene.intersect -- which normalises a raw direction as
+Ray's constructor does -- and kd, ke, normal and mode from OracleScene.tris().  Every buffer must match bit for bit.
 """
 import ctypes as C
 import functools
@@ -25,26 +25,6 @@ SPECULAR = 1  # crt_material.mode / the oracle's mode of a SPECULAR material (th
 
 
 # -------------------------------------------------------------------------------------------------------- restatement --
-
-def primary_rays_of(osc, eye, iv, fov, lsn, width, height, spp, crop=None, seed=0):
-    """The oracle's primary rays of a render of scene `osc` (crop of a width x height frame), as tests/test_aov.py::primary_rays takes
-    them from the ray log: (origins, directions, t, tri) as (pixels x spp, ...) arrays in pixel order, then sample order, and (h, w)."""
-    L = O.lib()
-    L.orc_ray_log_begin.restype = None
-    L.orc_ray_log_end.restype = C.c_uint64
-    L.orc_ray_log_end.argtypes = [C.c_void_p, C.c_uint64]
-    L.orc_ray_log_begin()
-    osc.render(eye, iv, fov, width, height, spp, 0.0, lsn, seed=seed, crop=crop)
-    n = int(L.orc_ray_log_end(None, 0))
-    log = np.zeros((n, 10), dtype=F)
-    L.orc_ray_log_end(log.ctypes.data_as(C.c_void_p), n)
-    eye32 = np.asarray(eye, dtype=F)
-    keep = np.isnan(log[:, 8]) & np.all(log[:, 0:3].view(np.uint32) == eye32.view(np.uint32), axis=1)
-    prim = log[keep]
-    cw, ch = (crop[2], crop[3]) if crop else (width, height)
-    assert prim.shape[0] == cw * ch * spp
-    return prim[:, 0:3].copy(), prim[:, 3:6].copy(), prim[:, 6].copy(), prim[:, 7].astype(np.int32), (ch, cw)
-
 
 def unit3(v):
     """Ray's constructor: v / sqrt(x x + (y y + z z)) per component, v itself if the sum is not positive"""
@@ -89,7 +69,7 @@ def chains(osc, o, d, t, tri, max_bounces):
 
 
 def restated(osc, rays, spp, max_bounces):
-    """The five buffers of the contract from the primary rays `rays` of primary_rays_of, and the per-sample chains."""
+    """The five buffers of the contract from the primary rays `rays` of util.primary_rays_of, and the per-sample chains."""
     o, d, t, tri, (ch, cw) = rays
     tris = osc.tris()
     hit, length, B, thr, last = chains(osc, o, d, t, tri, max_bounces)
@@ -128,15 +108,7 @@ def restated(osc, rays, spp, max_bounces):
 def expected(name, width, height, spp, max_bounces, crop=None, seed=0):
     osc, t = util.oracle_scene(name), util.task(name)
     eye, iv, fov = util.camera(name)
-    return restated(osc, primary_rays_of(osc, eye, iv, fov, t.light_sample_n, width, height, spp, crop, seed), spp, max_bounces)
-
-
-def assert_same(got, want, where="", names=NAMES):
-    for n in names:
-        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
-        assert g.shape == w.shape, (n, g.shape, w.shape)
-        same = g.view(np.uint32) == w.view(np.uint32) if g.dtype == np.float32 else g == w
-        assert same.all(), "%s %s: %d of %d values differ (first at %r)" % (where, n, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+    return restated(osc, util.primary_rays_of(osc, eye, iv, fov, t.light_sample_n, width, height, spp, crop, seed), spp, max_bounces)
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU --
@@ -229,7 +201,7 @@ def mirror_expected(d):
     obj, mtl = write_mirror_scene(d)
     osc = O.OracleScene([(obj, mtl)], MIRROR_THRESH)
     eye, iv, fov = mirror_camera()
-    rays = primary_rays_of(osc, eye, iv, fov, 1, MIRROR_W, MIRROR_H, MIRROR_SPP)
+    rays = util.primary_rays_of(osc, eye, iv, fov, 1, MIRROR_W, MIRROR_H, MIRROR_SPP)
     return {mb: restated(osc, rays, MIRROR_SPP, mb) for mb in (1, 2, 8)}
 
 
@@ -282,7 +254,7 @@ def test_aov_specular_veach_matches_restatement(renders, max_bounces):
     r = renders["veach-mis"]
     got = run_spec(r, "veach-mis", 4, 64, 48, max_bounces)
     want, ch = expected("veach-mis", 64, 48, 4, max_bounces)
-    assert_same(got, want, "veach-mis max_bounces %d" % max_bounces)
+    util.assert_same(got, want, NAMES, "veach-mis max_bounces %d" % max_bounces)
     assert (got["bounces"] > 0).any() and (got["bounces"] == 0).any()
     tris = util.oracle_scene("veach-mis").tris()
     assert ((ch["B"] >= 1) & (ch["last"] >= 0) & (tris["has_emit"][np.maximum(ch["last"], 0)] != 0)).any()  # a chain ends at an emitter
@@ -299,11 +271,10 @@ def test_aov_specular_changes_nothing_on_cornell_box(renders):
     assert r.aov_specular_info["rays"] == 64 * 48 * 4 and r.aov_specular_info["chunks"] == 1
     eye, iv, fov = util.camera("cornell-box")
     aov = r.run_view_aov(eye, iv, fov, width=64, height=48)
-    assert_same({"guide_albedo": got["guide_albedo"], "last_normal": got["last_normal"], "path_depth": got["path_depth"], "last_tri": got["last_tri"]},
-                {"guide_albedo": aov["albedo"], "last_normal": aov["normal"], "path_depth": aov["depth"], "last_tri": aov["tri"]},
-                "cornell-box", ("guide_albedo", "last_normal", "path_depth", "last_tri"))
+    util.assert_same(got, {"guide_albedo": aov["albedo"], "last_normal": aov["normal"], "path_depth": aov["depth"], "last_tri": aov["tri"]},
+                     ("guide_albedo", "last_normal", "path_depth", "last_tri"), "cornell-box")
     assert not got["bounces"].any() and (got["last_tri"] >= 0).any()
-    assert_same(got, expected("cornell-box", 64, 48, 4, 2)[0], "cornell-box")
+    util.assert_same(got, expected("cornell-box", 64, 48, 4, 2)[0], NAMES, "cornell-box")
 
 
 @pytest.mark.gpu
@@ -313,7 +284,7 @@ def test_aov_specular_invariant_on_veach_pixels_without_a_specular_hit(renders):
     eye, iv, fov = util.camera("veach-mis")
     r.set_spp(4)
     aov = r.run_view_aov(eye, iv, fov, width=64, height=48)
-    _, _, _, tri, _ = primary_rays_of(util.oracle_scene("veach-mis"), eye, iv, fov, util.task("veach-mis").light_sample_n, 64, 48, 4)
+    _, _, _, tri, _ = util.primary_rays_of(util.oracle_scene("veach-mis"), eye, iv, fov, util.task("veach-mis").light_sample_n, 64, 48, 4)
     mode = util.oracle_scene("veach-mis").tris()["mode"]
     plain = ~((tri >= 0) & (mode[np.maximum(tri, 0)] == SPECULAR)).reshape(48, 64, 4).any(axis=2)
     assert plain.any() and (~plain).any()
@@ -334,7 +305,7 @@ def test_aov_specular_mirror_to_mirror_chains(tmp_path):
         eye, iv, fov = mirror_camera()
         for mb in (1, 2, 8):
             got = r.run_view_aov_specular(eye, iv, fov, max_bounces=mb)
-            assert_same(got, want[mb][0], "mirrors max_bounces %d" % mb)
+            util.assert_same(got, want[mb][0], NAMES, "mirrors max_bounces %d" % mb)
             # the camera rays of every slot, padding included (33 x 17 is ragged), and the reflected rays of the pixels alone
             assert r.aov_specular_info["rays"] == crt.shard_slots(MIRROR_W, MIRROR_H, 0, 1) * MIRROR_SPP + int(want[mb][1]["B"].sum())
     finally:
@@ -355,7 +326,7 @@ def test_aov_specular_crop_of_full_camera_in_chunks(renders):
     x0, y0, cw, ch = PLATE_CROP
     want, chain = expected("veach-mis", 800, 600, spp, 2, crop=PLATE_CROP)
     assert (chain["B"] > 0).mean() > 0.5
-    assert_same({n: got[n][y0:y0 + ch, x0:x0 + cw] for n in NAMES}, want, "chunks")
+    util.assert_same({n: got[n][y0:y0 + ch, x0:x0 + cw] for n in NAMES}, want, NAMES, "chunks")
 
 
 @pytest.mark.gpu
@@ -363,7 +334,7 @@ def test_aov_specular_traversal_modes_agree(renders):
     base = run_spec(renders["veach-mis"], "veach-mis", 4, 64, 48, 2, seed=3)
     assert (base["bounces"] > 0).any()
     for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST):
-        assert_same(run_spec(renders["veach-mis"], "veach-mis", 4, 64, 48, 2, traversal=mode, seed=3), base, "mode %d" % mode)
+        util.assert_same(run_spec(renders["veach-mis"], "veach-mis", 4, 64, 48, 2, traversal=mode, seed=3), base, NAMES, "mode %d" % mode)
 
 
 @pytest.mark.gpu
@@ -372,7 +343,7 @@ def test_aov_specular_kernel_variants_agree(renders, var, value, monkeypatch):
     base = {n: run_spec(renders[n], n, 4, 64, 48, 2) for n in renders}
     monkeypatch.setenv(var, value)
     for n in renders:
-        assert_same(run_spec(renders[n], n, 4, 64, 48, 2), base[n], "%s %s=%s" % (n, var, value))
+        util.assert_same(run_spec(renders[n], n, 4, 64, 48, 2), base[n], NAMES, "%s %s=%s" % (n, var, value))
 
 
 @pytest.mark.gpu
@@ -404,29 +375,13 @@ def test_aov_specular_tiled_shards_deinterleave_to_row_major(renders):
         g = np.stack(shards[n])
         img = untile_numpy(g, w, h)
         img = img if capi.AOV_SPECULAR_BUFFERS[n][0] == 3 else img[:, :, 0]
-        assert_same({n: img}, {n: full[n]}, "tiled", (n,))
+        util.assert_same({n: img}, full, (n,), "tiled")
         for rank in range(world):
             for s in range(g.shape[1]):
                 tile = (s // 64) * world + rank
                 i, j = (tile % tx) * 8 + (s % 64) % 8, (tile // tx) * 8 + (s % 64) // 8
                 if tile >= tx * ty or i >= w or j >= h:
                     assert np.all(g[rank, s] == (-1 if n == "last_tri" else 0)), (n, rank, s)
-
-
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
 
 
 @pytest.mark.gpu
@@ -440,46 +395,21 @@ def test_aov_specular_device_form_on_a_stream_between_progressive_ranges(renders
     r.set_spp(3)
     one = r.run_view(eye, iv, fov, width=w, height=h).copy()
     one_mean = r.mean_buffer.copy()
-    H = hip_runtime()
-    ptrs, sizes = {}, {}
-    stream = C.c_void_p()
-    try:
-        for n in NAMES:
-            sizes[n] = w * h * capi.AOV_SPECULAR_BUFFERS[n][0] * 4
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), sizes[n]) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, sizes[n]) == 0  # (every value must be written by the pass)
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+    with util.DeviceBuffers({n: capi.AOV_SPECULAR_BUFFERS[n] for n in NAMES}, w, h) as d:
         assert r.run_view_range(eye, iv, fov, 0, 2, width=w, height=h) is None
-        assert r.run_view_aov_specular_device(eye, iv, fov, ptrs, max_bounces=2, stream=stream.value, want_info=False, width=w, height=h) is None
-        assert H.hipStreamSynchronize(stream) == 0
-
-        def fetch(names):
-            out = {}
-            for n in names:
-                ch, dt = capi.AOV_SPECULAR_BUFFERS[n]
-                a = np.zeros((h, w, ch) if ch == 3 else (h, w), dtype=dt)
-                assert H.hipMemcpy(a.ctypes.data, ptrs[n], sizes[n], 2) == 0  # hipMemcpyDeviceToHost
-                out[n] = a
-            return out
-
-        assert_same(fetch(NAMES), want, "device form")
+        assert r.run_view_aov_specular_device(eye, iv, fov, d.ptrs, max_bounces=2, stream=d.stream, want_info=False, width=w, height=h) is None
+        d.synchronize()
+        util.assert_same(d.fetch(NAMES), want, NAMES, "device form")
         _, _, done = r.preview(width=w, height=h)
         assert done == 2
         rgb = r.run_view_range(eye, iv, fov, 2, 1, width=w, height=h)
         assert np.array_equal(rgb, one)
         assert np.array_equal(r.mean_buffer.view(np.uint32), one_mean.view(np.uint32))
         # a subset of the buffers, with the pass's timer
-        assert H.hipMemset(C.c_void_p(ptrs["bounces"]), 0, sizes["bounces"]) == 0
-        info = r.run_view_aov_specular_device(eye, iv, fov, {"bounces": ptrs["bounces"]}, max_bounces=2, stream=stream.value, width=w, height=h)
+        d.fill("bounces", 0)
+        info = r.run_view_aov_specular_device(eye, iv, fov, {"bounces": d.ptrs["bounces"]}, max_bounces=2, stream=d.stream, width=w, height=h)
         assert info["chunks"] == 1 and info["rays"] > w * h * 3 and info["total_ms"] > 0
-        assert_same(fetch(["bounces"]), want, "subset", ("bounces",))
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        util.assert_same(d.fetch(["bounces"]), want, ("bounces",), "subset")
 
 
 @pytest.mark.gpu
@@ -512,16 +442,6 @@ def test_run_view_denoised_with_specular_guides_equals_the_calls_by_hand(renders
     assert np.array_equal(r.aov_buffers["albedo"].view(np.uint32), one.view(np.uint32))
 
 
-def read_pfm(path):
-    raw = open(path, "rb").read()
-    kind, dims, scale, body = raw.split(b"\n", 3)
-    w, h = (int(v) for v in dims.split())
-    ch = {b"PF": 3, b"Pf": 1}[kind]
-    a = np.frombuffer(body, dtype="<f4")
-    assert a.size == w * h * ch and scale == b"-1.0"
-    return np.ascontiguousarray(a.reshape((h, w, ch) if ch == 3 else (h, w))[::-1])
-
-
 @pytest.mark.gpu
 def test_cli_writes_specular_aov_files_and_the_denoised_frame(renders, tmp_path):
     from PIL import Image
@@ -535,7 +455,8 @@ def test_cli_writes_specular_aov_files_and_the_denoised_frame(renders, tmp_path)
     r = renders["veach-mis"]
     got = run_spec(r, "veach-mis", 2, 96, 72, 1, seed=42)
     for n in ("guide_albedo", "last_normal", "path_depth", "bounces"):
-        assert np.array_equal(read_pfm("%s_%s.pfm" % (prefix, n)).view(np.uint32), got[n].view(np.uint32)), n
+        hdr, a = util.read_pfm("%s_%s.pfm" % (prefix, n))
+        assert hdr[2] == b"-1.0" and np.array_equal(a.view(np.uint32), got[n].view(np.uint32)), n
     eye, iv, fov = util.camera("veach-mis")
     r.set_spp(2)
     r.seed = 42

@@ -13,7 +13,6 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 import oracle_lib as O
-import test_aov as aov
 import test_temporal as T
 import util
 
@@ -280,7 +279,7 @@ def test_device_forms_on_a_stream(offset):
     color, albedo, emission, variance = synthetic(w, h, 5, floor)
     want_irr, want_var = restated_demodulate(color, albedo, emission, variance, floor)
     want_rgb, want_mean = restated_modulate(want_irr, albedo, emission, floor)
-    H = aov.hip_runtime()
+    H = util.hip_runtime()
     names = ("color", "albedo", "emission", "variance", "irr", "ivar", "mean", "rgb")
     ptrs = {}
     stream = C.c_void_p()

@@ -274,28 +274,12 @@ def test_denoise_does_not_filter_across_a_normal_edge(sigma_color):
     assert not np.array_equal(a[:, :w // 2], color[:, :w // 2])   # ... and the halves are filtered within themselves
 
 
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
 @pytest.mark.gpu
 def test_denoise_device_form_on_a_stream_matches_host_form(renders):
     name, w, h, it = "veach-mis", 100, 70, 4
     _, mean, g = frame_and_guides(renders[name], name, w, h, 4)
     want_rgb, want_mean = crt.denoise(mean, iterations=it, **g)
-    H = hip_runtime()
+    H = util.hip_runtime()
     ptrs = {}
     stream = C.c_void_p()
     scratch_bytes = crt.denoise_scratch_bytes(w, h)

@@ -282,22 +282,6 @@ def test_preview_of_tiled_shards(renders, name, world):
     assert np.array_equal(untile_numpy(np.stack(rgbs), w, h), prgb)
 
 
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SCENES)
 def test_device_forms_on_a_stream(renders, name):
@@ -308,7 +292,7 @@ def test_device_forms_on_a_stream(renders, name):
     _, p, prgb = restated_preview(L, S, 3)
     r = renders[name]
     r.set_spp(S)
-    lib, H = capi.lib(), hip_runtime()
+    lib, H = capi.lib(), util.hip_runtime()
     eye, iv, fov = util.camera(name)
     cam = r._cam(eye, iv, fov)
     prm = r._params(rank=rank, world=world, flags=capi.FLAG_TILED_OUTPUT, width=w, height=h)

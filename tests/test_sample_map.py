@@ -398,8 +398,7 @@ class DeviceBuffers:
     """Raw device buffers through the HIP runtime the library is linked against: {name: bytes}, each filled with 0x55"""
 
     def __init__(self, sizes, stream=False):
-        from test_variance import hip_runtime
-        self.H = hip_runtime()
+        self.H = util.hip_runtime()
         self.ptrs, self.sizes, self.stream = {}, dict(sizes), C.c_void_p()
         try:
             for n, size in sizes.items():
@@ -604,7 +603,6 @@ def test_planned_frame_matches_range_plan_map_restated(name, monkeypatch):
 @pytest.mark.gpu
 def test_cli_writes_the_planned_frame_and_its_samples(renders, tmp_path):
     from cudaraytracing_amd import build as b
-    from test_variance import read_pfm
     cli = b.build_cli()
     name = "veach-mis"
     cfg = util.SCENES[name]
@@ -618,7 +616,7 @@ def test_cli_writes_the_planned_frame_and_its_samples(renders, tmp_path):
     ref = str(tmp_path / "python.png")
     renders[name].save_frame_buffer(ref)
     assert open(png, "rb").read() == open(ref, "rb").read()
-    assert_bits(read_pfm(pfm), got["samples"].astype(F), "--adaptive-samples")
-    assert_bits(read_pfm(vpfm), got["variance"], "--variance of the planned frame")
+    assert_bits(util.read_pfm(pfm)[1], got["samples"].astype(F), "--adaptive-samples")
+    assert_bits(util.read_pfm(vpfm)[1], got["variance"], "--variance of the planned frame")
     bad = subprocess.run([cli, cfg, "--adaptive-planned"], capture_output=True, text=True, timeout=60)
     assert bad.returncode == 1 and "--adaptive" in bad.stderr

@@ -540,22 +540,6 @@ def test_temporal_accumulation_reduces_the_error_against_a_converged_frame(rende
     assert mse(rgb) < mse(noisy_rgb)
 
 
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
 @pytest.mark.gpu
 def test_temporal_device_form_on_a_stream_matches_host_form(renders):
     name, w, h = "veach-mis", 100, 70
@@ -563,7 +547,7 @@ def test_temporal_device_form_on_a_stream_matches_host_form(renders):
     prev = as_history(c0, c0["color"], c0["variance"], np.full((h, w), 3, dtype=F))
     want_rgb, want_c, want_v, want_h, want_info = crt.temporal(c1, cam1, prev=prev, prev_camera=cam0, return_info=True)
     assert 100 <= want_info["reprojected"] < w * h
-    H = hip_runtime()
+    H = util.hip_runtime()
     ptrs = {}
     stream = C.c_void_p()
     host = {"cur_" + k: v for k, v in c1.items()}

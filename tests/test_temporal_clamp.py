@@ -428,7 +428,7 @@ def test_clamped_device_form_on_a_stream_matches_host_form(renders):
     clamp = {"radius": 2, "gamma": 0.75}
     want_rgb, want_c, want_v, want_h, want_info = crt.temporal(c1, cam1, prev=prev, prev_camera=cam0, return_info=True, clamp=clamp)
     assert 100 <= want_info["clamped"] < want_info["reprojected"] - 100
-    Hr = T.hip_runtime()
+    Hr = util.hip_runtime()
     ptrs = {}
     stream = C.c_void_p()
     host = {"cur_" + k: v for k, v in c1.items()}

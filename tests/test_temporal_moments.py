@@ -711,7 +711,7 @@ def test_moments_device_forms_on_a_stream_match_host_forms(renders):
     est = dict(min_history=3, radius=2, of_mean=1, history_cap=3.5)
     want_e, want_einfo = crt.variance_estimate(want_m1, want_m2, want_h, normal=g1["normal"], depth=g1["depth"], return_info=True, **est)
     assert 100 <= want_einfo["spatial"] < w * h - 100
-    Hr = T.hip_runtime()
+    Hr = util.hip_runtime()
     ptrs = {}
     stream = C.c_void_p()
     host = {"cur_" + k: v for k, v in c1.items()}

@@ -285,28 +285,12 @@ def test_variance_tiled_shards_deinterleave_to_row_major(renders, world):
     assert padding > 0
 
 
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
 @pytest.mark.gpu
 def test_variance_device_form_on_a_stream_matches_host_form(renders):
     name, w, h, spp = "cornell-box", 100, 70, 4
     r = renders[name]
     rgb0, mean0, var0 = gpu_frame(r, name, w, h, spp)
-    H = hip_runtime()
+    H = util.hip_runtime()
     eye, iv, fov = util.camera(name)
     ptrs, stream = {}, C.c_void_p()
     sizes = {"rgb": w * h * 3, "mean": w * h * 12, "var": w * h * 12}
@@ -364,17 +348,6 @@ def test_variance_precision_against_float64(renders, name, w, h, spp):
     assert (var[dark].view(np.uint32) == 0).all()           # a pixel whose samples are all +0
 
 
-def read_pfm(path):
-    """Array (row 0 = image top) of a little-endian PFM, read with numpy alone."""
-    kind, dims, scale, body = open(path, "rb").read().split(b"\n", 3)
-    w, h = (int(v) for v in dims.split())
-    ch = {b"PF": 3, b"Pf": 1}[kind]
-    assert float(scale) < 0
-    a = np.frombuffer(body, dtype="<f4")
-    assert a.size == w * h * ch
-    return np.ascontiguousarray(a.reshape((h, w, ch) if ch == 3 else (h, w))[::-1])
-
-
 @pytest.mark.gpu
 def test_cli_writes_the_variance_buffer(renders, tmp_path):
     from cudaraytracing_amd import build as b
@@ -388,7 +361,7 @@ def test_cli_writes_the_variance_buffer(renders, tmp_path):
     assert res.returncode == 0, res.stderr
     assert open(plain, "rb").read() == open(flagged, "rb").read()
     _, _, var = gpu_frame(renders["veach-mis"], "veach-mis", 96, 72, 4, seed=42)
-    assert_bits(read_pfm(pfm), var, "--variance")
+    assert_bits(util.read_pfm(pfm)[1], var, "--variance")
     bad = subprocess.run([cli, cfg, "--devices", "0,0", "--gather", "copy", "--variance", pfm], capture_output=True, text=True, timeout=60)
     assert bad.returncode == 1 and "--variance" in bad.stderr
     bad = subprocess.run([cli, cfg, "--gpus", "2", "--variance", pfm], capture_output=True, text=True, timeout=60)

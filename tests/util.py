@@ -1,10 +1,13 @@
-"""Shared helpers for the test-suite (scene setup for both the product and the oracle)."""
+"""Shared helpers for the test-suite (scene setup for both the product and the oracle, bit comparisons, the oracle's ray log, PFM files,
+device buffers through the HIP runtime)."""
+import ctypes as C
 import functools
 import os
 
 import numpy as np
 
 import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
 import oracle_lib as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -61,6 +64,112 @@ def assert_bits(got, want, where=""):
     nan = np.isnan(want)
     same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
     assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+
+
+def assert_same(got, want, names, where=""):
+    """The buffers `names` of the dicts got and want have one shape and type and the same bits (float32 on its uint32 view)"""
+    for n in names:
+        g, w = np.ascontiguousarray(got[n]), np.ascontiguousarray(want[n])
+        assert g.shape == w.shape and g.dtype == w.dtype, (where, n, g.shape, w.shape, g.dtype, w.dtype)
+        same = g.view(np.uint32) == w.view(np.uint32) if g.dtype == np.float32 else g == w
+        assert same.all(), "%s %s: %d of %d values differ (first at %r)" % (where, n, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+
+
+def read_pfm(path):
+    """((kind, dimensions, scale) header lines, array with row 0 = image top) of a little-endian PFM, read with numpy alone."""
+    kind, dims, scale, body = open(path, "rb").read().split(b"\n", 3)
+    w, h = (int(v) for v in dims.split())
+    ch = {b"PF": 3, b"Pf": 1}[kind]
+    assert float(scale) < 0
+    a = np.frombuffer(body, dtype="<f4")
+    assert a.size == w * h * ch
+    return (kind, dims, scale), np.ascontiguousarray(a.reshape((h, w, ch) if ch == 3 else (h, w))[::-1])
+
+
+def primary_rays_of(osc, eye, iv, fov, lsn, width, height, spp, crop=None, seed=0):
+    """The oracle's primary rays of a render of scene `osc` (crop of a width x height frame), from its ray log: (origins, directions, t,
+    tri) as (pixels x spp, ...) arrays in pixel order, then sample order, and (h, w)."""
+    L = O.lib()
+    L.orc_ray_log_begin.restype = None
+    L.orc_ray_log_end.restype = C.c_uint64
+    L.orc_ray_log_end.argtypes = [C.c_void_p, C.c_uint64]
+    L.orc_ray_log_begin()
+    osc.render(eye, iv, fov, width, height, spp, 0.0, lsn, seed=seed, crop=crop)
+    n = int(L.orc_ray_log_end(None, 0))
+    log = np.zeros((n, 10), dtype=np.float32)
+    L.orc_ray_log_end(log.ctypes.data_as(C.c_void_p), n)
+    eye32 = np.asarray(eye, dtype=np.float32)
+    keep = np.isnan(log[:, 8]) & np.all(log[:, 0:3].view(np.uint32) == eye32.view(np.uint32), axis=1)
+    prim = log[keep]
+    cw, ch = (crop[2], crop[3]) if crop else (width, height)
+    assert prim.shape[0] == cw * ch * spp
+    # (pixel, sample) order: with p_rr = 0 each path is its camera ray and that vertex's next-event samples, so the camera rays are
+    # the log's closest-hit rays from the eye, one path after the other
+    return prim[:, 0:3].copy(), prim[:, 3:6].copy(), prim[:, 6].copy(), prim[:, 7].astype(np.int32), (ch, cw)
+
+
+def hip_runtime():
+    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
+    capi.lib()
+    with open("/proc/self/maps") as f:
+        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
+    H = C.CDLL(path)
+    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    H.hipFree.argtypes = [C.c_void_p]
+    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
+    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
+    H.hipStreamSynchronize.argtypes = [C.c_void_p]
+    H.hipStreamDestroy.argtypes = [C.c_void_p]
+    return H
+
+
+class DeviceBuffers:
+    """with DeviceBuffers({name: (channels, dtype)}, w, h) as d: one device buffer per name for a w x h image of 4-byte values, filled with
+    0x55 (every value must be written by what is tested), and a stream.  d.ptrs: {name: raw device pointer}, d.stream: the stream's
+    handle; everything is released on exit."""
+
+    def __init__(self, table, w, h):
+        self.H, self.table, self.w, self.h = hip_runtime(), table, w, h
+        self.ptrs, self._stream = {}, C.c_void_p()
+
+    def nbytes(self, name):
+        return self.w * self.h * self.table[name][0] * 4
+
+    def __enter__(self):
+        try:
+            for n in self.table:
+                p = C.c_void_p()
+                assert self.H.hipMalloc(C.byref(p), self.nbytes(n)) == 0
+                self.ptrs[n] = p.value
+                self.fill(n, 0x55)
+            assert self.H.hipStreamCreate(C.byref(self._stream)) == 0
+        except BaseException:
+            self.__exit__()
+            raise
+        self.stream = self._stream.value
+        return self
+
+    def __exit__(self, *exc):
+        if self._stream.value:
+            self.H.hipStreamDestroy(self._stream)
+        for p in self.ptrs.values():
+            self.H.hipFree(C.c_void_p(p))
+
+    def fill(self, name, byte):
+        assert self.H.hipMemset(C.c_void_p(self.ptrs[name]), byte, self.nbytes(name)) == 0
+
+    def synchronize(self):
+        assert self.H.hipStreamSynchronize(self._stream) == 0
+
+    def fetch(self, names):
+        """{name: (h, w, 3) or (h, w) array} of the buffers' contents"""
+        out = {}
+        for n in names:
+            ch, dt = self.table[n]
+            out[n] = np.zeros((self.h, self.w, ch) if ch == 3 else (self.h, self.w), dtype=dt)
+            assert self.H.hipMemcpy(out[n].ctypes.data, self.ptrs[n], self.nbytes(n), 2) == 0  # hipMemcpyDeviceToHost
+        return out
 
 
 def random_rays(name, n, seed):
