@@ -165,6 +165,11 @@ class DenoiseVarInputs(C.Structure):
     _fields_ = [("color", C.c_void_p), ("variance", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
 
 
+class NlmParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("radius", C.c_uint32), ("patch", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
 class DenoiseInfo(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("passes", C.c_uint32)]
 
@@ -287,7 +292,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
-           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
+           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
            "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
@@ -369,6 +374,12 @@ def lib():
     L.crt_denoise_var.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.POINTER(DenoiseInfo)]
     L.crt_denoise_var_device.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(DenoiseInfo)]
+    L.crt_denoise_nlm_defaults.argtypes = [C.POINTER(NlmParams)]
+    L.crt_denoise_nlm_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.crt_denoise_nlm.argtypes = [C.c_int, C.POINTER(NlmParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(DenoiseInfo)]
+    L.crt_denoise_nlm_device.argtypes = [C.c_int, C.POINTER(NlmParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(DenoiseInfo)]
     L.crt_temporal_defaults.argtypes = [C.POINTER(TemporalParams)]
     L.crt_temporal.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory), C.c_void_p, C.c_void_p,

@@ -542,18 +542,33 @@ class Render:
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
                           sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
-                          demodulate=False, albedo_floor=None):
+                          demodulate=False, albedo_floor=None, nlm=None):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
         variance_guided: render with want_variance and filter with crt_denoise_var (its own defaults) and self.variance_buffer.
+        nlm: True, or a dict of denoise_nlm's settings (radius, patch, k, alpha): render with want_variance and filter with crt_denoise_nlm
+        instead of the a-trous filter; the sigma_normal, sigma_albedo and sigma_depth arguments go to it.  It composes with specular_guides
+        and demodulate as variance_guided does, and excludes variance_guided, iterations and sigma_color (ValueError).
         specular_guides: the albedo guide is guide_albedo of run_view_aov_specular (max_bounces) -- what a mirror reflects instead of the
         mirror; normal and depth stay first-hit.
         demodulate: the filter runs on irradiance.  The shading AOVs (self.shading_buffers: emission, diffuse_albedo) come from the same
         pass as the guides, the frame (and, variance_guided, its variance) goes through demodulate(albedo_floor), is filtered with the
         caller's sigmas -- the albedo guide is still passed; sigma_albedo=float("inf") drops it -- and comes back through modulate()."""
         self._handle("run_view_denoised")
-        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=variance_guided)
+        nlm_settings = None
+        if nlm is not None and nlm is not False:
+            if variance_guided or iterations is not None or sigma_color is not None:
+                raise ValueError("run_view_denoised: nlm excludes variance_guided, iterations and sigma_color (the a-trous filter's)")
+            nlm_settings = {} if nlm is True else dict(nlm)
+            unknown = sorted(set(nlm_settings) - set(_NLM_SETTINGS))
+            if unknown:
+                raise ValueError("run_view_denoised: unknown nlm settings %r" % (unknown,))
+            for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
+                if v is not None:
+                    nlm_settings[name] = v
+        with_variance = variance_guided or nlm_settings is not None
+        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=with_variance)
         guides = ("albedo", "normal", "depth")
         if demodulate:
             aov = self.run_view_aov_shading(eye_pos, inv_view_mat, fovY, first=guides, width=width, height=height)
@@ -564,14 +579,17 @@ class Render:
         if specular_guides:
             self.aov_buffers["albedo"] = self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=max_bounces, want=("guide_albedo",),
                                                                     width=width, height=height)["guide_albedo"]
-        color, var = self.mean_buffer, self.variance_buffer if variance_guided else None
+        color, var = self.mean_buffer, self.variance_buffer if with_variance else None
         if demodulate:
             sh = self.shading_buffers
             got = _demodulate(color, sh["diffuse_albedo"], sh["emission"], variance=var, albedo_floor=albedo_floor, device=self.device)
-            color, var = got if variance_guided else (got, None)
+            color, var = got if with_variance else (got, None)
         settings = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
                         device=self.device, want_rgb=not demodulate, return_info=True)
-        if variance_guided:
+        if nlm_settings is not None:
+            rgb, mean, self.denoise_info = denoise_nlm(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **nlm_settings,
+                                                       **self.aov_buffers)
+        elif variance_guided:
             rgb, mean, self.denoise_info = denoise_var(color, var, **settings, **self.aov_buffers)
         else:
             rgb, mean, self.denoise_info = denoise(color, **settings, **self.aov_buffers)
@@ -994,6 +1012,83 @@ def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                                                  C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
                                                  C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
                "crt_denoise_var_device")
+    return info.as_dict() if want_info else None
+
+
+_NLM_SETTINGS = ("radius", "patch", "k", "alpha", "sigma_normal", "sigma_albedo", "sigma_depth")
+
+
+def denoise_nlm_defaults():
+    """crt_denoise_nlm_defaults as a dict: radius, patch, k, alpha and the three guide sigmas."""
+    p = capi.NlmParams()
+    capi.check(capi.lib().crt_denoise_nlm_defaults(C.byref(p)), "crt_denoise_nlm_defaults")
+    return {n: getattr(p, n) for n in _NLM_SETTINGS}
+
+
+def _nlm_params(width, height, **settings):
+    p = capi.NlmParams()
+    capi.check(capi.lib().crt_denoise_nlm_defaults(C.byref(p)), "crt_denoise_nlm_defaults")
+    p.width, p.height = int(width), int(height)
+    for name in _NLM_SETTINGS:
+        v = settings.get(name)
+        if v is not None:
+            setattr(p, name, int(v) if name in ("radius", "patch") else float(v))
+    return p
+
+
+def denoise_nlm_scratch_bytes(width, height):
+    n = C.c_uint64()
+    capi.check(capi.lib().crt_denoise_nlm_scratch_bytes(width, height, C.byref(n)), "crt_denoise_nlm_scratch_bytes")
+    return int(n.value)
+
+
+def denoise_nlm(color, variance, albedo=None, normal=None, depth=None, radius=None, patch=None, k=None, alpha=None, sigma_normal=None,
+                sigma_albedo=None, sigma_depth=None, device=0, want_rgb=True, want_variance=False, return_info=False):
+    """Non-local means with variance-normalised patch distances, joint with the guides (crt_denoise_nlm, contract: include/crt.h):
+    `variance` is the (H, W, 3) buffer of Render.variance(); None settings take crt_denoise_nlm_defaults.  Returns (rgb, mean), with
+    want_variance (rgb, mean, var) -- var (H, W) float32 -- and with return_info also the crt_denoise_info dict."""
+    c = np.ascontiguousarray(color, dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("denoise_nlm needs an (H, W, 3) colour image, got %r" % (c.shape,))
+    if variance is None:
+        raise ValueError("denoise_nlm needs the variance buffer (Render.variance)")
+    h, w = c.shape[:2]
+    inputs, keep = capi.DenoiseVarInputs(), [c]
+    inputs.color = c.ctypes.data
+    for name, a, shape in (("variance", variance, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError("denoise_nlm: %s has shape %r, expected %r" % (name, a.shape, shape))
+        keep.append(a)
+        setattr(inputs, name, a.ctypes.data)
+    prm = _nlm_params(w, h, radius=radius, patch=patch, k=k, alpha=alpha, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth)
+    mean = np.zeros((h, w, 3), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    var = np.zeros((h, w), dtype=np.float32) if want_variance else None
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise_nlm(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(var), C.byref(info)),
+               "crt_denoise_nlm")
+    out = (rgb, mean, var) if want_variance else (rgb, mean)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def denoise_nlm_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out_rgb_ptr, out_variance_ptr, scratch_ptr, scratch_bytes,
+                       albedo_ptr=None, normal_ptr=None, depth_ptr=None, radius=None, patch=None, k=None, alpha=None, sigma_normal=None,
+                       sigma_albedo=None, sigma_depth=None, device=0, stream=None, want_info=True):
+    """Enqueues the non-local-means filter with everything in device memory (raw device pointers, crt_denoise_nlm_device); the caller
+    owns the scratch (denoise_nlm_scratch_bytes).  With want_info the call synchronizes the stream and returns the info dict."""
+    inputs = capi.DenoiseVarInputs(color_ptr or None, variance_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
+    prm = _nlm_params(width, height, radius=radius, patch=patch, k=k, alpha=alpha, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo,
+                      sigma_depth=sigma_depth)
+    info = capi.DenoiseInfo()
+    capi.check(capi.lib().crt_denoise_nlm_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
+                                                 C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None,
+                                                 C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
+                                                 C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
+                                                 C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
+               "crt_denoise_nlm_device")
     return info.as_dict() if want_info else None
 
 

@@ -8,6 +8,7 @@
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]
 //           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
+//           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
@@ -32,7 +33,9 @@
 // does not apply.
 // --variance PATH renders with CRT_FLAG_VARIANCE (the frame is the same bits) and writes the per-pixel variance of the mean
 // (crt_variance, one device) as a 3-channel PFM.  --denoise-variance makes --denoise use the variance-guided filter (crt_denoise_var,
-// its own defaults; --denoise-iterations / --denoise-sigma override them as well).
+// its own defaults; --denoise-iterations / --denoise-sigma override them as well).  --denoise-nlm makes --denoise use the non-local-means
+// filter (crt_denoise_nlm, its own defaults); --denoise-nlm-params sets its radius, patch and k, --denoise-sigma its three guide sigmas (the
+// colour value is ignored: the filter has no colour sigma).  Not with --denoise-variance or --denoise-iterations.
 // --denoise PATH renders as usual, then filters the frame with the AOV-guided a-trous denoiser (crt_denoise, one device) and writes the
 // result as a PNG to PATH; -o and --aov outputs are unchanged by it.  --denoise-iterations (1 .. 5) and --denoise-sigma (colour, normal,
 // albedo, depth) override crt_denoise_defaults.
@@ -62,6 +65,7 @@ int main(int argc, char** argv)
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
                              "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
+                             "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n", argv[0]);
@@ -78,6 +82,9 @@ int main(int argc, char** argv)
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false, denoise_specular = false;
+        bool denoise_nlm = false, nlm_params = false;
+        crt_nlm_params nlm; // --denoise-nlm: the filter's defaults with the overrides
+        crt_denoise_nlm_defaults(&nlm);
         uint32_t specular_bounces = 0; // 0: crt_aov_specular_defaults'
         int temporal = 0;
         bool temporal_option = false, temporal_denoise = false, temporal_clamp = false, temporal_moments = false;
@@ -145,6 +152,20 @@ int main(int argc, char** argv)
             else if (a == "--denoise-specular") denoise_specular = true;
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
             else if (a == "--denoise-variance") denoise_var = true;
+            else if (a == "--denoise-nlm") denoise_nlm = true;
+            else if (a == "--denoise-nlm-params") {
+                need(i, 1);
+                nlm_params = true;
+                const char* q = argv[++i];
+                char* end = nullptr;
+                const long radius = std::strtol(q, &end, 10);
+                bool good = end != q && *end == ',';
+                long patch = 0;
+                if (good) { q = end + 1; patch = std::strtol(q, &end, 10); good = end != q && *end == ','; }
+                if (good) { q = end + 1; nlm.k = std::strtof(q, &end); good = end != q && *end == 0; }
+                if (!good || radius < 0 || patch < 0) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm-params needs three comma-separated values: RADIUS,PATCH,K");
+                nlm.radius = (uint32_t)radius; nlm.patch = (uint32_t)patch;
+            }
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
             else if (a == "--adaptive") { need(i, 1); ad.threshold = std::strtof(argv[++i], nullptr); adaptive = true; }
             else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
@@ -245,7 +266,13 @@ int main(int argc, char** argv)
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
-        const bool want_var = !variance.empty() || denoise_var || (temporal > 0 && !temporal_moments);
+        if (multi && denoise_nlm) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm filters on one device (not with --gpus / --devices)");
+        if (denoise_nlm && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm needs --denoise PATH");
+        if (nlm_params && !denoise_nlm) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm-params needs --denoise-nlm");
+        if (denoise_nlm && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is a filter of its own (not with --denoise-variance)");
+        if (denoise_nlm && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is one pass (not with --denoise-iterations)");
+        if (denoise_nlm && dn_sigma) { nlm.sigma_normal = dn.sigma_normal; nlm.sigma_albedo = dn.sigma_albedo; nlm.sigma_depth = dn.sigma_depth; }
+        const bool want_var = !variance.empty() || denoise_var || denoise_nlm || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
         crt_denoise_var_defaults(&tdn);
         if (dn_iterations) tdn.iterations = dn.iterations;
@@ -374,7 +401,7 @@ int main(int argc, char** argv)
             std::printf("%s\n%s\n%s\n%s\n", pg.c_str(), pn.c_str(), pd.c_str(), pb.c_str());
         }
         if (!denoise.empty()) {
-            if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
+            if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
             const crt_denoise_info& di = render.last_denoise_info();
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);
             render.save_denoised_buffer(denoise.c_str());

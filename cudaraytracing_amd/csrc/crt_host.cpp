@@ -829,7 +829,8 @@ const float* Render::variance()
 
 // crt_denoise_var of a colour and its variance with the guides of the last run_aov
 // (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
-void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance)
+void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance,
+                            const crt_nlm_params* nlm)
 {
     const size_t n = scene_->get_pixels();
     crt_denoise_params p = prm;
@@ -843,7 +844,15 @@ void Render::denoise_var_of(const char* who, const float* color, const float* va
     in.color = color; in.variance = variance;
     in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    const int rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), nullptr, &denoise_info_);
+    unsigned char* const call_rgb = demodulate_ ? nullptr : denoised_buffer_.data();
+    int rc;
+    if (nlm) {
+        crt_nlm_params q = *nlm;
+        q.width = p.width; q.height = p.height;
+        rc = crt_denoise_nlm(device_, &q, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
+    } else {
+        rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
+    }
     if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
     if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
 }
@@ -856,6 +865,16 @@ void Render::run_denoise_var(const crt_denoise_params& prm)
     if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
         throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var needs run_view and run_aov of this frame size first");
     denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
+}
+
+void Render::run_denoise_nlm(const crt_nlm_params& prm)
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise_nlm: the denoiser is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm after free()");
+    const size_t n = scene_->get_pixels();
+    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
+        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm needs run_view and run_aov of this frame size first");
+    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
 }
 
 void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp)

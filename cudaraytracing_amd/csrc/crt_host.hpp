@@ -256,6 +256,8 @@ public:
     // the same with the variance-guided filter (crt_denoise_var; prm: crt_denoise_var_defaults with overrides): the last run_view must
     // have had CRT_FLAG_VARIANCE (set_flags)
     void run_denoise_var(const crt_denoise_params& prm);
+    // the same with the non-local-means filter (crt_denoise_nlm; prm: crt_denoise_nlm_defaults with overrides), CRT_FLAG_VARIANCE likewise
+    void run_denoise_nlm(const crt_nlm_params& prm);
     // per-pixel variance of the mean of the last run_view (crt_variance; needs set_flags(CRT_FLAG_VARIANCE) before it): W x H x 3,
     // fetched from the device on the first call after a frame; one device only
     const float* variance();
@@ -335,7 +337,8 @@ private:
     std::vector<float> temporal_m1_, temporal_m2_;   // run_temporal_moments: the history's moment planes
     bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
     crt_variance_estimate_info estimate_info_{};
-    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance = false);
+    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance = false,
+                        const crt_nlm_params* nlm = nullptr); // nlm: crt_denoise_nlm with these settings instead (prm unused)
     // set_aov_shading / set_demodulate
     bool aov_shading_ = false, demodulate_ = false;
     float albedo_floor_ = 0.0f;

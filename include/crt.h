@@ -550,6 +550,63 @@ int crt_denoise_var_device(int device, const crt_denoise_params* params, const c
                            void* d_out_rgb, void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream,
                            crt_denoise_info* info);
 
+/* Non-local means with variance-normalised patch distances (Rousselle et al. 2012), joint with the guides (Rousselle et al. 2013): one
+ * pass whose weight between two pixels comes from how much the patches around them differ beyond what their variances explain, so the
+ * filter follows the sample count by itself and keeps structure that the guides do not see.  Inputs and outputs are crt_denoise_var's:
+ * color and variance required, albedo / normal / depth optional (a NULL guide makes its term +0.0f); out_mean and / or out_rgb (the
+ * frame's tone map of the mean), not both NULL, and optionally out_variance (1 float per pixel).  An image operation: row-major, no
+ * scene handle.  info->passes is 1.
+ *   v(p)  = (variance(p).x + variance(p).y) + variance(p).z
+ *   g(p)  = the 3x3 Gaussian of v around p: exactly crt_denoise_var's g of pass 0 (k = {1/4, 1/2, 1/4}, dy outer, dx inner, taps outside
+ *           the image skipped, gn / gd)
+ *   k2    = k * k
+ * For pixel p and window offset o = (ox, oy), oy = -radius..radius outer, ox = -radius..radius inner, q = p + o; a q outside the image
+ * is skipped:
+ *   D = +0, n = 0
+ *   for py = -patch..patch (outer):  row = +0
+ *     for px = -patch..patch (inner):  t = p + (px, py), u = t + o;  t or u outside the image: skipped (nothing added, n unchanged)
+ *       dc  = c(t) - c(u)                          s = dc.x*dc.x + dc.y*dc.y + dc.z*dc.z
+ *       mn  = g(u) < g(t) ? g(u) : g(t)
+ *       d   = (s - alpha * (g(t) + mn)) / (1e-10f + k2 * (g(t) + g(u)))
+ *       row = row + d;  n = n + 1
+ *     D = D + row                                  (after every py, also when the row had no tap)
+ *   Dm  = D / (float)n                             (n >= 1: the patch centre is always inside)
+ *   e_p = Dm < 0 ? 0 : Dm                          (a NaN passes through)
+ *   e_n, e_a, e_d between p and q: exactly crt_denoise's, with sigma_normal, sigma_albedo, sigma_depth
+ *   w   = exp(-(((e_p + e_n) + e_a) + e_d))        (det_expf)
+ *   num = num + c(q) * w (per channel)    den = den + w    vnum = vnum + v(q) * (w * w)
+ *   out_mean(p) = num / den (per channel)          out_variance(p) = vnum / (den * den)
+ * All arithmetic is fp32 with one IEEE operation per symbol (no FMA, no reciprocal multiply); sums start at +0.0f and run left to right
+ * as written.  Non-finite inputs are not special-cased.
+ * The pair term d depends on (t, o) only, not on p, and so does whether a tap is skipped.  A row sum row(x, y + py, o) is therefore the
+ * same number for every pixel of column x that reaches that row: an implementation may compute each d once per (t, o) and each row sum
+ * once per (x, row, o), and still match a per-pixel evaluation bit for bit.  The library has both forms (csrc/crt_nlm.hip: k_nlm_shared
+ * shares them through LDS, k_nlm_direct does not); the environment variable CRT_NLM_FORM=direct|shared, read per call, selects one
+ * (for tests; any other value is CRT_ERR_INVALID_ARG), and both give the same bits.
+ * radius is 1 .. 8 (a search window of (2 radius + 1)^2), patch 0 .. 3 (patches of (2 patch + 1)^2), k > 0 and finite (the damping of
+ * the patch distance), alpha >= 0 and finite (how much of the variance is taken off a squared difference); each sigma > 0 and not NaN,
+ * +inf switches its term off.  A null params, inputs, color or variance, a size of 0, a setting outside these ranges, two NULL outputs,
+ * a negative device or a scratch buffer that is missing, too small or not 16-byte aligned is CRT_ERR_INVALID_ARG, checked before any
+ * device call.  (A side longer than 2^24 pixels: CRT_ERR_UNSUPPORTED.)  Scratch: 48 B per pixel (crt_denoise_nlm_scratch_bytes: three
+ * float4 planes -- (colour, g), (normal, depth), (albedo, v)).
+ * crt_denoise_nlm_defaults fills radius 5, patch 1, k 0.7, alpha 1, sigma_normal 0.5, sigma_albedo 0.1, sigma_depth 0.05: the set with the
+ * smallest summed error relative to crt_denoise_var's defaults on the 160x120 spp 8 and spp 32 frames of the two shipped scenes
+ * (docs/experiments.md, "The non-local-means filter"). */
+typedef struct {
+    uint32_t width, height;
+    uint32_t radius;      /* search window (2 radius + 1)^2: 1 .. 8 */
+    uint32_t patch;       /* patches of (2 patch + 1)^2: 0 .. 3 */
+    float k;              /* damping of the patch distance: > 0, finite */
+    float alpha;          /* how much of the variance is taken off a squared difference: >= 0, finite */
+    float sigma_normal, sigma_albedo, sigma_depth;   /* as crt_denoise: > 0, not NaN, +inf switches the term off */
+} crt_nlm_params;
+int crt_denoise_nlm_defaults(crt_nlm_params* params);
+int crt_denoise_nlm_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+int crt_denoise_nlm(int device, const crt_nlm_params* params, const crt_denoise_var_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                    float* out_variance, crt_denoise_info* info);
+int crt_denoise_nlm_device(int device, const crt_nlm_params* params, const crt_denoise_var_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
+                           void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream, crt_denoise_info* info);
+
 /* Albedo demodulation: filter irradiance, not radiance.  crt_demodulate takes the emission off a frame and divides it by the albedo,
  * crt_modulate puts both back, so that crt_denoise* and crt_temporal* in between see neither the surfaces' colour nor the lights
  * (SVGF, Schied et al. 2017, section 4).  With emission and diffuse_albedo of crt_render_aov_shading the factorisation is exact for this

@@ -1,0 +1,562 @@
+"""Non-local means with variance-normalised patch distances, joint with the guides (crt_denoise_nlm / crt_denoise_nlm_device,
+include/crt.h; denoise_nlm and Render.run_view_denoised(nlm=...) in Python; crt_cli --denoise-nlm).
+
+The contract of include/crt.h is restated below in numpy float32, operation by operation, with the oracle's det_expf
+(oracle_lib.math_fn("exp")) and tone map (oracle_lib.tonemap); the device result must match it bit for bit, the filtered variance
+included, from both forms of the kernel (CRT_NLM_FORM=direct|shared).  Comparisons are on uint32 views; where the expected value is NaN the
+result must be NaN (payload not compared).  Two checks need no restatement: weights that are all 1, and an edge no weight crosses.
+"""
+import ctypes as C
+import subprocess
+
+import numpy as np
+import pytest
+
+import cudaraytracing_amd as crt
+from cudaraytracing_amd import _capi as capi
+import oracle_lib as O
+import util
+
+DEFAULTS = {"radius": 5, "patch": 1, "k": 0.7, "alpha": 1.0, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
+K3 = np.array([1.0 / 4, 1.0 / 2, 1.0 / 4], dtype=np.float32)
+F = np.float32
+NLM_EXPORTS = ("crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device")
+FORMS = ("direct", "shared")
+
+
+def shifted(a, dy, dx):
+    """(a at (y + dy, x + dx), whether that pixel is inside the image); outside: some value that the caller masks"""
+    h, w = a.shape[:2]
+    ys, xs = np.arange(h) + dy, np.arange(w) + dx
+    inside = ((ys >= 0) & (ys < h))[:, None] & ((xs >= 0) & (xs < w))[None, :]
+    return a[np.clip(ys, 0, h - 1)][:, np.clip(xs, 0, w - 1)], inside
+
+
+def restated(color, variance, albedo=None, normal=None, depth=None, radius=5, patch=2, k=0.7, alpha=1.0, sigma_normal=0.5, sigma_albedo=0.1,
+             sigma_depth=0.05):
+    """The contract, in numpy float32: every ufunc below is one IEEE fp32 operation per element.  Returns (out_mean, out_variance).
+    Per window offset o the pair terms d_o(t) are an image, a row sum is that image added along x in the contract's order, and D is the
+    row sums added along y: the numbers a per-pixel evaluation adds, in its order."""
+    c = np.ascontiguousarray(color, dtype=F)
+    var3 = np.ascontiguousarray(variance, dtype=F)
+    h, w = c.shape[:2]
+    sn, sa, sd, al = F(sigma_normal), F(sigma_albedo), F(sigma_depth), F(alpha)
+    k2 = F(k) * F(k)
+    zero = np.zeros((h, w), dtype=F)
+
+    def sq3(a, b):
+        d = a - b
+        return d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+
+    with np.errstate(all="ignore"):
+        v = (var3[..., 0] + var3[..., 1]) + var3[..., 2]
+        gn, gd = np.zeros((h, w), dtype=F), np.zeros((h, w), dtype=F)
+        for dy in range(-1, 2):
+            for dx in range(-1, 2):
+                vt, inside = shifted(v, dy, dx)
+                kk = K3[dy + 1] * K3[dx + 1]
+                gn = np.where(inside, gn + kk * vt, gn)
+                gd = np.where(inside, gd + kk, gd)
+        g = gn / gd
+        num = np.zeros((h, w, 3), dtype=F)
+        den = np.zeros((h, w), dtype=F)
+        vnum = np.zeros((h, w), dtype=F)
+        for oy in range(-radius, radius + 1):
+            for ox in range(-radius, radius + 1):
+                cu, u_inside = shifted(c, oy, ox)          # at every t: u = t + o; at every p: q = p + o
+                gu, _ = shifted(g, oy, ox)
+                mn = np.where(gu < g, gu, g)
+                d = (sq3(c, cu) - al * (g + mn)) / (F(1e-10) + k2 * (g + gu))
+                row = np.zeros((h, w), dtype=F)            # row(x, ty, o) at (ty, x)
+                row_n = np.zeros((h, w), dtype=np.int64)
+                for px in range(-patch, patch + 1):
+                    dt, t_inside = shifted(d, 0, px)
+                    ut, _ = shifted(u_inside, 0, px)
+                    ok = t_inside & ut
+                    row = np.where(ok, row + dt, row)
+                    row_n += ok
+                D = np.zeros((h, w), dtype=F)
+                n = np.zeros((h, w), dtype=np.int64)
+                for py in range(-patch, patch + 1):
+                    rt, r_inside = shifted(row, py, 0)     # (a row whose u's are outside has no tap: its sum is +0)
+                    nt, _ = shifted(row_n, py, 0)
+                    D = D + np.where(r_inside, rt, F(0.0))
+                    n += np.where(r_inside, nt, 0)
+                Dm = D / n.astype(F)
+                e_p = np.where(Dm < F(0.0), F(0.0), Dm)
+                e_n = sq3(normal, shifted(normal, oy, ox)[0]) / (sn * sn) if normal is not None else zero
+                e_a = sq3(albedo, shifted(albedo, oy, ox)[0]) / (sa * sa) if albedo is not None else zero
+                if depth is not None:
+                    dq = shifted(depth, oy, ox)[0]
+                    m = np.where(depth > dq, depth, dq)
+                    r = (depth - dq) / (sd * m)
+                    e_d = np.where(m > 0, r * r, F(0.0))
+                else:
+                    e_d = zero
+                wgt = O.math_fn("exp", -(((e_p + e_n) + e_a) + e_d))
+                assert wgt.dtype == F and d.dtype == F and D.dtype == F
+                assert (n[u_inside] >= 1).all()
+                num = np.where(u_inside[..., None], num + cu * wgt[..., None], num)
+                den = np.where(u_inside, den + wgt, den)
+                vnum = np.where(u_inside, vnum + shifted(v, oy, ox)[0] * (wgt * wgt), vnum)
+        mean = num / den[..., None]
+        var = vnum / (den * den)
+    assert mean.dtype == F and var.dtype == F
+    return mean, var
+
+
+def assert_bits(got, want, where=""):
+    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
+    assert got.shape == want.shape, (where, got.shape, want.shape)
+    nan = np.isnan(want)
+    same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
+    assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
+
+
+def check_against_restatement(color, variance, where, want_rgb=True, **kw):
+    rgb, mean, var = crt.denoise_nlm(color, variance, want_rgb=want_rgb, want_variance=True, **kw)
+    want_mean, want_var = restated(color, variance, **kw)
+    assert_bits(mean, want_mean, where + ": mean")
+    assert_bits(var, want_var, where + ": variance")
+    if want_rgb:
+        assert np.array_equal(rgb, O.tonemap(mean)), where + ": rgb is not the tone map of the mean"
+    return rgb, mean, var
+
+
+def unit_weight_input(w=20, h=14):
+    return np.full((h, w, 3), 2.0, dtype=F), np.full((h, w, 3), 1.0, dtype=F)
+
+
+def check_unit_weights(mean, var, color, radius):
+    """every weight 1: the mean is the colour exactly, the variance v / N(p), N(p) the window taps inside the image"""
+    h, w = color.shape[:2]
+    assert np.array_equal(mean, color)
+    ys, xs = np.arange(h), np.arange(w)
+    ny = np.minimum(ys + radius, h - 1) - np.maximum(ys - radius, 0) + 1
+    nx = np.minimum(xs + radius, w - 1) - np.maximum(xs - radius, 0) + 1
+    N = ny[:, None] * nx[None, :]
+    assert N[0, 0] == (radius + 1) ** 2 and N[h // 2, 0] == (radius + 1) * (2 * radius + 1) and N[h // 2, w // 2] == (2 * radius + 1) ** 2  # corner, edge, interior
+    assert np.allclose(var, 3.0 / N, rtol=1e-6, atol=0)
+
+
+def stepped_image(w=40, h=30):
+    """levels 0 and 1024: a vertical step, a box and a single pixel"""
+    color = np.zeros((h, w, 3), dtype=F)
+    color[:, w // 2:] = 1024.0
+    color[5:12, 4:11] = 1024.0
+    color[20, 30] = 0.0
+    return color, np.full((h, w, 3), 1.0, dtype=F)
+
+
+NO_CROSSING = [(1, 0, 1.0), (3, 1, 0.7), (5, 2, 0.45), (8, 3, 1.0)]
+
+
+# ------------------------------------------------------------------------------------------------------------------ CPU --
+
+def test_nlm_entry_points_are_exported():
+    lib = capi.lib()
+    for name in NLM_EXPORTS:
+        assert name in capi.EXPORTS
+        assert getattr(lib, name) is not None
+    for name in ("denoise_nlm", "denoise_nlm_device", "denoise_nlm_defaults", "denoise_nlm_scratch_bytes"):
+        assert name in crt.__all__ and callable(getattr(crt, name))
+    assert lib.crt_abi_version() == 5 == capi.ABI_VERSION
+
+
+def test_nlm_defaults_and_scratch_size():
+    lib = capi.lib()
+    p = capi.NlmParams(7, 7, 99, 99, -1.0, -1.0, -1.0, -1.0, -1.0)
+    assert lib.crt_denoise_nlm_defaults(C.byref(p)) == capi.CRT_OK
+    assert (p.width, p.height) == (0, 0) and (p.radius, p.patch) == (DEFAULTS["radius"], DEFAULTS["patch"])
+    for name in ("k", "alpha", "sigma_normal", "sigma_albedo", "sigma_depth"):
+        assert F(getattr(p, name)) == F(DEFAULTS[name]), name
+    assert crt.denoise_nlm_defaults() == {k: (v if k in ("radius", "patch") else float(F(v))) for k, v in DEFAULTS.items()}
+    assert lib.crt_denoise_nlm_defaults(None) == capi.ERR_INVALID_ARG and lib.crt_last_error()
+    # the guide sigmas are crt_denoise's
+    assert all(crt.denoise_nlm_defaults()[s] == crt.denoise_defaults()[s] for s in ("sigma_normal", "sigma_albedo", "sigma_depth"))
+    assert crt.denoise_nlm_scratch_bytes(100, 70) == 100 * 70 * 48
+    n = C.c_uint64()
+    for bad in ((0, 70, C.byref(n)), (100, 0, C.byref(n)), (100, 70, None)):
+        assert lib.crt_denoise_nlm_scratch_bytes(*bad) == capi.ERR_INVALID_ARG
+
+
+def test_nlm_arguments_are_checked_before_any_device_call():
+    """Every invalid call is CRT_ERR_INVALID_ARG with a message, from both entry points, also on a machine without a GPU.  The non-null
+    buffers here are dummies that must never be dereferenced."""
+    lib = capi.lib()
+    dummy = C.create_string_buffer(256)
+    d = C.cast(dummy, C.c_void_p)
+    w, h = 64, 48
+    need = crt.denoise_nlm_scratch_bytes(w, h)
+    inf, nan = float("inf"), float("nan")
+
+    def params(**over):
+        p = capi.NlmParams()
+        assert lib.crt_denoise_nlm_defaults(C.byref(p)) == capi.CRT_OK
+        p.width, p.height = w, h
+        for k, v in over.items():
+            setattr(p, k, v)
+        return C.byref(p)
+
+    def inputs(color=d, variance=d):
+        return C.byref(capi.DenoiseVarInputs(color, variance, d, d, d))
+
+    def both(prm, inp, mean=d, rgb=d, want=capi.ERR_INVALID_ARG):
+        r1 = lib.crt_denoise_nlm(0, prm, inp, mean, rgb, d, None)
+        e1 = lib.crt_last_error()
+        r2 = lib.crt_denoise_nlm_device(0, prm, inp, mean, rgb, d, d, need, None, None)
+        e2 = lib.crt_last_error()
+        assert r1 == r2 == want, (r1, r2, e1, e2)
+        assert e1 and e2
+        return e1
+
+    assert b"null" in both(None, inputs())
+    assert b"null" in both(params(), None)
+    assert b"null" in both(params(), inputs(color=None))
+    assert b"variance" in both(params(), inputs(variance=None))
+    both(params(width=0), inputs())
+    both(params(height=0), inputs())
+    for bad in (0, 9, 1000):
+        assert b"radius" in both(params(radius=bad), inputs())
+    for bad in (4, 1000):
+        assert b"patch" in both(params(patch=bad), inputs())
+    for bad in (0.0, -0.0, -1.0, nan, inf, -inf):
+        assert b"k must" in both(params(k=bad), inputs()), bad
+    for bad in (-1e-3, -1.0, nan, inf, -inf):
+        assert b"alpha" in both(params(alpha=bad), inputs()), bad
+    for name in ("sigma_normal", "sigma_albedo", "sigma_depth"):
+        for bad in (0.0, -0.0, -1.0, nan, -inf):
+            assert b"sigma" in both(params(**{name: bad}), inputs()), (name, bad)
+    assert b"no output" in both(params(), inputs(), mean=None, rgb=None)
+    for scratch, size in ((None, need), (d, need - 1), (d, 0), (C.c_void_p(d.value + 4), need)):
+        assert lib.crt_denoise_nlm_device(0, params(), inputs(), d, d, d, scratch, size, None, None) == capi.ERR_INVALID_ARG
+        assert b"scratch" in lib.crt_last_error()
+    assert lib.crt_denoise_nlm(-1, params(), inputs(), d, d, d, None) == capi.ERR_INVALID_ARG and b"device" in lib.crt_last_error()
+    assert lib.crt_denoise_nlm_device(-1, params(), inputs(), d, d, d, d, need, None, None) == capi.ERR_INVALID_ARG and b"device" in lib.crt_last_error()
+    assert b"2^24" in both(params(width=(1 << 24) + 1), inputs(), want=capi.ERR_UNSUPPORTED)
+
+
+def test_restatement_with_unit_weights():
+    """A constant colour, a constant variance, alpha 0 and no guides: every d is 0 / x = 0, every weight exp(-0) = 1."""
+    color, variance = unit_weight_input()
+    mean, var = restated(color, variance, radius=5, patch=2, alpha=0.0)
+    check_unit_weights(mean, var, color, 5)
+
+
+@pytest.mark.parametrize("radius,patch,k", NO_CROSSING)
+def test_restatement_gives_no_weight_across_a_step(radius, patch, k):
+    """Levels 0 and 1024 with variance (1, 1, 1): a patch pair with one tap across the step has d >= (3 x 1024^2 - 6) / 6 k2 there and
+    -1 / k2 at its other taps, so D / n > 1e4 and the weight is exactly 0; a pair with none has D < 0 and the weight 1.  1024 x w is
+    exact, so the output is the input bit for bit."""
+    color, variance = stepped_image()
+    mean, var = restated(color, variance, radius=radius, patch=patch, k=k)
+    assert_bits(mean, color, "restated, step")
+    assert (var <= F(3.0)).all() and (var > 0).all() and var[20, 30] == F(3.0)   # the single pixel keeps its own variance
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU --
+
+@pytest.fixture(scope="module")
+def renders():
+    out = {}
+    for name in ("cornell-box", "veach-mis"):
+        t = util.task(name)
+        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
+    yield out
+    for r in out.values():
+        r.free()
+
+
+def frame_and_guides(r, name, width, height, spp, seed=0):
+    """(rgb, mean, variance, {albedo, normal, depth}) of a GPU render with the flag and its AOV pass"""
+    eye, iv, fov = util.camera(name)
+    r.set_spp(spp)
+    r.seed = seed
+    try:
+        rgb = r.run_view(eye, iv, fov, width=width, height=height, want_variance=True).copy()
+        mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+        g = r.run_view_aov(eye, iv, fov, want=("albedo", "normal", "depth"), width=width, height=height)
+    finally:
+        r.seed = 0
+    return rgb, mean, var, g
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_nlm_rendered_frames_match_restatement(renders, name):
+    """64 x 48: the window of radius 8 leaves the image from a third of the pixels, and the tile rows of the shared form are ragged."""
+    _, mean, var, g = frame_and_guides(renders[name], name, 64, 48, 4)
+    assert (g["depth"] > 0).any() and (var > 0).any()
+    for radius, patch in ((1, 0), (3, 1), (5, 2), (8, 3)):
+        _, got, _ = check_against_restatement(mean, var, "%s 64x48 r%d f%d" % (name, radius, patch), radius=radius, patch=patch, k=0.7, **g)
+        assert not np.array_equal(got, mean)
+    check_against_restatement(mean, var, "%s 64x48 k 0.45 alpha 0.5" % name, radius=5, patch=2, k=0.45, alpha=0.5, **g)
+
+
+def synthetic(w, h, seed):
+    """As test_denoise_variance.py's, at any size: noise with a smooth patch, blocks of zero depth and of zero variance.  The noise is
+    small against the variance, so that weights between different pixels survive."""
+    rng = np.random.default_rng(seed)
+    color = (F(10.0) + rng.random((h, w, 3)) * 4).astype(F)
+    n = rng.normal(size=(h, w, 3))
+    normal = (n / np.linalg.norm(n, axis=2, keepdims=True)).astype(F)
+    albedo = rng.random((h, w, 3)).astype(F)
+    depth = (F(50.0) - rng.random((h, w)).astype(F) * F(50.0)).astype(F)  # (0, 50]
+    assert (depth > 0).all() and (depth <= 50).all()
+    depth[h // 3:h // 3 + 9, w // 4:w // 4 + 13] = 0.0                     # a block of "miss" pixels
+    color[2:20, 3:30] = color[0, 0] + (rng.random(color[2:20, 3:30].shape) * 0.5).astype(F)
+    normal[0:24, 0:40] = normal[0, 0]
+    albedo[0:24, 0:40] = albedo[0, 0]
+    depth[0:10, 0:40] = depth[0, 0]
+    variance = (rng.random((h, w, 3)) * 3).astype(F)
+    variance[5:16, 8:22] = 0.0                                             # a block of zero variance inside the smooth patch
+    variance[max(h - 8, 0):, max(w - 11, 0):] = 0.0                        # ... and one in the noise, at the corner
+    return color, variance, {"albedo": albedo, "normal": normal, "depth": depth}
+
+
+SIZES = [(100, 70, 5, 2), (61, 47, 5, 2), (130, 9, 8, 3), (9, 7, 5, 2), (1, 1, 1, 1), (3, 2, 1, 1)]
+
+
+@pytest.fixture(scope="module")
+def synthetic_cases():
+    """(inputs, the restatement's result) per size: computed once, shared by the tests below, never written to"""
+    out = {}
+    for w, h, radius, patch in SIZES:
+        color, variance, g = synthetic(w, h, 20 + w)
+        out[(w, h)] = (color, variance, g, restated(color, variance, radius=radius, patch=patch, **g))
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("w,h,radius,patch", SIZES)
+def test_nlm_ragged_and_tiny_sizes_match_restatement(synthetic_cases, w, h, radius, patch):
+    """100 x 70 and 61 x 47: tiles cut by both far edges; 130 x 9 at (8, 3) and 9 x 7 at (5, 2): every window and most patches leave the
+    image; 1 x 1 and 3 x 2: smaller than a patch."""
+    color, variance, g, (want_mean, want_var) = synthetic_cases[(w, h)]
+    if w >= 61:
+        assert (g["depth"] == 0).any() and (variance.sum(axis=2) == 0).any()
+    rgb, mean, var = crt.denoise_nlm(color, variance, radius=radius, patch=patch, want_variance=True, **g)
+    where = "%dx%d r%d f%d" % (w, h, radius, patch)
+    assert_bits(mean, want_mean, where + ": mean")
+    assert_bits(var, want_var, where + ": variance")
+    assert np.array_equal(rgb, O.tonemap(mean))
+    assert np.isfinite(mean).all() and np.isfinite(var).all()
+    if w * h == 1:
+        assert_bits(mean, color, "1x1")
+    if w >= 61:
+        assert not np.array_equal(mean, color)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("w,h", [(100, 70), (130, 9), (9, 7)])
+def test_nlm_forms_give_the_same_bits(synthetic_cases, monkeypatch, form, w, h):
+    """CRT_NLM_FORM is read per call: each form against the restatement, so the two against each other."""
+    color, variance, g, (want_mean, want_var) = synthetic_cases[(w, h)]
+    radius, patch = [(r, f) for ww, hh, r, f in SIZES if (ww, hh) == (w, h)][0]
+    monkeypatch.setenv("CRT_NLM_FORM", form)
+    rgb, mean, var = crt.denoise_nlm(color, variance, radius=radius, patch=patch, want_variance=True, **g)
+    assert_bits(mean, want_mean, "%s %dx%d: mean" % (form, w, h))
+    assert_bits(var, want_var, "%s %dx%d: variance" % (form, w, h))
+    assert np.array_equal(rgb, O.tonemap(mean))
+    monkeypatch.setenv("CRT_NLM_FORM", "neither")
+    with pytest.raises(Exception, match="CRT_NLM_FORM"):
+        crt.denoise_nlm(color, variance, **g)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("drop", [("albedo",), ("normal",), ("depth",), ("albedo", "normal", "depth")])
+def test_nlm_null_guides(drop):
+    color, variance, g = synthetic(70, 45, 11)
+    kw = {k: v for k, v in g.items() if k not in drop}
+    _, mean, var = check_against_restatement(color, variance, "synthetic without %r" % (drop,), radius=3, patch=1, **kw)
+    assert np.isfinite(mean).all() and not np.array_equal(mean, color)
+    assert np.isfinite(var).all() and (var >= 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", FORMS)
+def test_nlm_non_finite_pixels(monkeypatch, form):
+    monkeypatch.setenv("CRT_NLM_FORM", form)
+    color, variance, g = synthetic(70, 45, 12)
+    bad_c, bad_v = color.copy(), variance.copy()
+    bad_c[7, 9, 1] = np.inf
+    bad_c[25, 60, 2] = -np.inf
+    bad_c[30, 50, 0] = np.nan
+    _, m1, v1 = check_against_restatement(bad_c, variance, "inf and NaN colours", radius=3, patch=1, **g)
+    assert np.isnan(m1).any() and np.isfinite(m1).any()
+    bad_v[12, 40, 2] = np.inf
+    bad_v[25, 20, 0] = np.nan
+    bad_v[33, 60, 1] = -5.0
+    _, m2, v2 = check_against_restatement(color, bad_v, "inf, NaN and negative variances", radius=3, patch=1, want_rgb=False, **g)
+    assert np.isnan(v2).any() and np.isfinite(v2).any() and np.isfinite(m2).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", FORMS)
+def test_nlm_unit_weights_on_the_device(monkeypatch, form):
+    monkeypatch.setenv("CRT_NLM_FORM", form)
+    color, variance = unit_weight_input()
+    _, mean, var = crt.denoise_nlm(color, variance, radius=5, patch=2, alpha=0.0, want_variance=True)
+    check_unit_weights(mean, var, color, 5)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", FORMS)
+def test_nlm_gives_no_weight_across_a_step_on_the_device(monkeypatch, form):
+    monkeypatch.setenv("CRT_NLM_FORM", form)
+    color, variance = stepped_image()
+    for radius, patch, k in NO_CROSSING:
+        _, mean, var = crt.denoise_nlm(color, variance, radius=radius, patch=patch, k=k, want_variance=True)
+        assert_bits(mean, color, "%s r%d f%d k%g" % (form, radius, patch, k))
+        assert (var <= F(3.0)).all() and (var > 0).all() and var[20, 30] == F(3.0)
+
+
+@pytest.mark.gpu
+def test_nlm_device_form_on_a_stream_matches_host_form(renders):
+    name, w, h = "veach-mis", 100, 70
+    kw = dict(radius=4, patch=2, k=0.6)
+    _, mean, variance, g = frame_and_guides(renders[name], name, w, h, 4)
+    want_rgb, want_mean, want_var = crt.denoise_nlm(mean, variance, want_variance=True, **kw, **g)
+    H = util.hip_runtime()
+    ptrs = {}
+    stream = C.c_void_p()
+    scratch_bytes = crt.denoise_nlm_scratch_bytes(w, h)
+    host = {"color": mean, "variance": variance, "albedo": g["albedo"], "normal": g["normal"], "depth": g["depth"]}
+    sizes = {n: a.nbytes for n, a in host.items()}
+    sizes.update({"out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4, "scratch": scratch_bytes})
+    try:
+        for n, size in sizes.items():
+            p = C.c_void_p()
+            assert H.hipMalloc(C.byref(p), size) == 0
+            ptrs[n] = p.value
+            assert H.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the filter)
+        for n, a in host.items():
+            assert H.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
+        assert H.hipStreamCreate(C.byref(stream)) == 0
+
+        def run(want_info, out_mean=True, out_rgb=True, out_var=True):
+            return crt.denoise_nlm_device(w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"] if out_mean else None,
+                                          ptrs["out_rgb"] if out_rgb else None, ptrs["out_var"] if out_var else None, ptrs["scratch"],
+                                          scratch_bytes, albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"],
+                                          stream=stream.value, want_info=want_info, **kw)
+
+        def fetch():
+            m, r, v = np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=np.uint8), np.zeros((h, w), dtype=F)
+            assert H.hipMemcpy(m.ctypes.data, C.c_void_p(ptrs["out_mean"]), m.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+            assert H.hipMemcpy(r.ctypes.data, C.c_void_p(ptrs["out_rgb"]), r.nbytes, 2) == 0
+            assert H.hipMemcpy(v.ctypes.data, C.c_void_p(ptrs["out_var"]), v.nbytes, 2) == 0
+            return m, r, v
+
+        assert run(False) is None
+        assert H.hipStreamSynchronize(stream) == 0
+        m, r, v = fetch()
+        assert_bits(m, want_mean, "device form")
+        assert_bits(v, want_var, "device form, variance")
+        assert np.array_equal(r, want_rgb)
+        # the mean only, with the timer (the call synchronizes the stream)
+        for n in ("out_mean", "out_rgb", "out_var"):
+            assert H.hipMemset(C.c_void_p(ptrs[n]), 0x55, sizes[n]) == 0
+        info = run(True, out_rgb=False, out_var=False)
+        assert info["passes"] == 1 and info["total_ms"] > 0, info
+        m, r, v = fetch()
+        assert_bits(m, want_mean, "device form, mean only")
+        assert (r == 0x55).all() and (v.view(np.uint32) == 0x55555555).all()
+    finally:
+        if stream.value:
+            H.hipStreamDestroy(stream)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+
+
+@pytest.mark.gpu
+def test_run_view_denoised_nlm_equals_the_calls_by_hand(renders):
+    name, w, h = "cornell-box", 96, 72
+    r = renders[name]
+    eye, iv, fov = util.camera(name)
+    rgb0, mean0, var0, g = frame_and_guides(r, name, w, h, 4)
+    want_rgb, want_mean = crt.denoise_nlm(mean0, var0, **g)
+    r.set_spp(4)
+    rgb, mean = r.run_view_denoised(eye, iv, fov, width=w, height=h, nlm=True)
+    assert_bits(mean, want_mean, "run_view_denoised(nlm=True)")
+    assert np.array_equal(rgb, want_rgb)
+    assert np.array_equal(r.frame_buffer, rgb0) and r.denoise_info["passes"] == 1
+    assert_bits(r.variance_buffer, var0, "variance_buffer")
+    _, mean2 = r.run_view_denoised(eye, iv, fov, width=w, height=h, nlm={"radius": 3, "patch": 1, "k": 0.5}, sigma_normal=0.25)
+    assert_bits(mean2, crt.denoise_nlm(mean0, var0, radius=3, patch=1, k=0.5, sigma_normal=0.25, **g)[1], "run_view_denoised with nlm settings")
+    # on irradiance: demodulate -> nlm -> modulate by hand
+    rgb3, mean3 = r.run_view_denoised(eye, iv, fov, width=w, height=h, nlm=True, demodulate=True)
+    sh = r.shading_buffers
+    irr, ivar = crt.demodulate(mean0, sh["diffuse_albedo"], sh["emission"], variance=var0)
+    filtered = crt.denoise_nlm(irr, ivar, want_rgb=False, **r.aov_buffers)[1]
+    want_rgb3, want_mean3 = crt.modulate(filtered, sh["diffuse_albedo"], sh["emission"])
+    assert_bits(mean3, want_mean3, "run_view_denoised(nlm=True, demodulate=True)")
+    assert np.array_equal(rgb3, want_rgb3)
+    # what excludes it
+    for bad in (dict(variance_guided=True), dict(iterations=2), dict(sigma_color=3.0)):
+        with pytest.raises(ValueError, match="nlm"):
+            r.run_view_denoised(eye, iv, fov, width=w, height=h, nlm=True, **bad)
+    with pytest.raises(ValueError, match="nlm"):
+        r.run_view_denoised(eye, iv, fov, width=w, height=h, nlm={"sigma_color": 3.0})
+    # the plain and the variance-guided forms are what they were, and so is a following render
+    _, mean4 = r.run_view_denoised(eye, iv, fov, width=w, height=h)
+    assert_bits(mean4, crt.denoise(mean0, **g)[1], "plain run_view_denoised")
+    assert r.variance_buffer is None
+    _, mean5 = r.run_view_denoised(eye, iv, fov, width=w, height=h, variance_guided=True)
+    assert_bits(mean5, crt.denoise_var(mean0, var0, **g)[1], "variance-guided run_view_denoised")
+    assert np.array_equal(r.run_view(eye, iv, fov, width=w, height=h), rgb0)
+    assert np.array_equal(r.mean_buffer.view(np.uint32), mean0.view(np.uint32))
+
+
+@pytest.mark.gpu
+def test_cli_writes_the_nlm_frame(renders, tmp_path):
+    from PIL import Image
+    from cudaraytracing_amd import build as b
+    cli = b.build_cli()
+    cfg = util.SCENES["veach-mis"]
+    base = [cli, cfg, "--spp", "4", "--width", "96", "--height", "72", "--seed", "42", "--base-dir", util.ROOT]
+    noisy, den, den2 = (str(tmp_path / n) for n in ("noisy.png", "den.png", "den2.png"))
+    res = subprocess.run(base + ["-o", noisy, "--denoise", den, "--denoise-nlm"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    rgb, mean, var, g = frame_and_guides(renders["veach-mis"], "veach-mis", 96, 72, 4, seed=42)
+    assert np.array_equal(np.asarray(Image.open(noisy)), rgb)
+    assert np.array_equal(np.asarray(Image.open(den)), crt.denoise_nlm(mean, var, **g)[0])
+    res = subprocess.run(base + ["-o", noisy, "--denoise", den2, "--denoise-nlm", "--denoise-nlm-params", "3,1,0.5", "--denoise-sigma", "77,0.25,0.2,0.1"],
+                         capture_output=True, text=True, timeout=120)
+    assert res.returncode == 0, res.stderr
+    want = crt.denoise_nlm(mean, var, radius=3, patch=1, k=0.5, sigma_normal=0.25, sigma_albedo=0.2, sigma_depth=0.1, **g)[0]
+    assert np.array_equal(np.asarray(Image.open(den2)), want)
+    for extra in (["--denoise", den, "--denoise-nlm", "--denoise-variance"], ["--denoise", den, "--denoise-nlm", "--denoise-iterations", "2"],
+                  ["--denoise-nlm"], ["--gpus", "2", "--denoise-nlm"], ["--devices", "0,0", "--gather", "copy", "--denoise-nlm"]):
+        bad = subprocess.run([cli, cfg] + extra, capture_output=True, text=True, timeout=60)
+        assert bad.returncode == 1 and "--denoise-nlm" in bad.stderr, extra
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
+def test_nlm_defaults_against_a_converged_frame(renders, name):
+    """160 x 120: noisy = spp 32 seed 0, converged = spp 256 seed 7, mean squared error of the RGB8 tone maps; spp 8 is printed only.
+    The restatement of the contract with the defaults (radius 5, patch 1, k 0.7) on the oracle's frames, on the CPU -- noisy / crt_denoise
+    / crt_denoise_var / crt_denoise_nlm: cornell-box spp 32: 433.7 / 124.0 / 110.9 / 111.3, veach-mis spp 32: 116.0 / 135.1 / 74.8 / 53.5;
+    spp 8: cornell-box 964.5 / 169.3 / 159.9 / 169.0, veach-mis 351.5 / 149.6 / 112.1 / 113.4.  Asserted at spp 32, as those figures
+    carry it: on veach-mis the defaults are strictly below crt_denoise_var's and crt_denoise's, on cornell-box strictly below the noisy
+    frame and crt_denoise's (there crt_denoise_var's defaults are level with them: not asserted)."""
+    r = renders[name]
+    ref_rgb = frame_and_guides(r, name, 160, 120, 256, seed=7)[0]
+
+    def mse(x):
+        d = x.astype(np.float64) - ref_rgb.astype(np.float64)
+        return float(np.mean(d * d))
+
+    err = {}
+    for spp in (8, 32):
+        noisy_rgb, noisy_mean, noisy_var, g = frame_and_guides(r, name, 160, 120, spp, seed=0)
+        err[spp] = {"noisy": mse(noisy_rgb), "plain": mse(crt.denoise(noisy_mean, **g)[0]), "var": mse(crt.denoise_var(noisy_mean, noisy_var, **g)[0]),
+                    "nlm": mse(crt.denoise_nlm(noisy_mean, noisy_var, **g)[0])}
+        print("%s spp %d: mse noisy %.1f, crt_denoise defaults %.1f, crt_denoise_var defaults %.1f, crt_denoise_nlm defaults %.1f"
+              % (name, spp, err[spp]["noisy"], err[spp]["plain"], err[spp]["var"], err[spp]["nlm"]))
+    e = err[32]
+    if name == "veach-mis":
+        assert e["nlm"] < e["var"] and e["nlm"] < e["plain"]
+    else:
+        assert e["nlm"] < e["noisy"] and e["nlm"] < e["plain"]

@@ -25,6 +25,15 @@ side, scenes/gen_cornell_box.py), generated into a temporary directory.
 
   python tools/denoise_probe.py --demodulate [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5]
   python tools/denoise_probe.py --error --demodulate [--sigma-color 4,6,8,16] [--ref-seed 7] [--bounces 2]
+
+--nlm times crt_denoise_nlm_device (--nlm-params RADIUS,PATCH,K, default: the filter's) at --sizes beside crt_denoise_var_device's 3
+iterations in one process: the variance-guided call and the two forms of the non-local-means kernel (CRT_NLM_FORM=direct|shared, read
+per call) taking turns, HIP events, the median of --calls calls.  With --error it lists, per scene, the error of the unfiltered frame,
+of crt_denoise, crt_denoise_var and crt_denoise_nlm (their defaults, first-hit guides) at spp 8 and spp 32 against --ref-spp samples of
+--ref-seed (give --ref-seed 7 for the frames of docs/experiments.md).
+
+  python tools/denoise_probe.py --nlm [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--nlm-params 5,1,0.7]
+  python tools/denoise_probe.py --nlm --error --ref-seed 7
 """
 import argparse
 import ctypes as C
@@ -160,6 +169,97 @@ def modulate_times(a, H):
     print(json.dumps(out), flush=True)
 
 
+def nlm_settings(a):
+    if not a.nlm_params:
+        return {}
+    radius, patch, k = a.nlm_params.split(",")
+    return {"radius": int(radius), "patch": int(patch), "k": float(k)}
+
+
+def nlm_error_table(a):
+    """--nlm --error: the four rows of docs/experiments.md, "The non-local-means filter", on the device"""
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "ref_spp": a.ref_spp, "ref_seed": a.ref_seed, "nlm": nlm_settings(a) or crt.denoise_nlm_defaults(), "rows": []}
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = a.ref_seed
+        ref = r.run_view(t.eye_pos, iv, fov).astype(np.float64)
+        r.seed = 0
+
+        def mse(x):
+            return round(float(np.mean((x.astype(np.float64) - ref) ** 2)), 1)
+
+        for spp in (8, 32):
+            r.set_spp(spp)
+            noisy_rgb = r.run_view(t.eye_pos, iv, fov, want_variance=True).copy()
+            mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+            g = r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth"))
+            row = {"scene": name, "spp": spp, "unfiltered": mse(noisy_rgb), "denoise": mse(crt.denoise(mean, **g)[0]),
+                   "denoise_var": mse(crt.denoise_var(mean, var, **g)[0]), "denoise_nlm": mse(crt.denoise_nlm(mean, var, **nlm_settings(a), **g)[0]),
+                   "denoise_nlm_no_guides": mse(crt.denoise_nlm(mean, var, **nlm_settings(a))[0])}
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        r.free()
+    print(json.dumps(out), flush=True)
+
+
+def nlm_times(a, H):
+    """--nlm: crt_denoise_var_device (3 iterations) and the two forms of crt_denoise_nlm_device, the three calls taking turns"""
+    t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
+    iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+    fov = crt.fov_to_radians(t.fov_y)
+    out = {"scene": a.scene, "spp": a.spp, "calls": a.calls, "warmup": a.warmup, "nlm": nlm_settings(a) or crt.denoise_nlm_defaults(), "runs": []}
+    before = os.environ.get("CRT_NLM_FORM")
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+        r.run_view(t.eye_pos, iv, fov, want_variance=True)
+        host = dict(r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth")), color=r.mean_buffer, variance=r.variance_buffer)
+        r.free()
+        scratch_bytes = max(crt.denoise_scratch_bytes(w, h), crt.denoise_nlm_scratch_bytes(w, h))
+        ptrs = {}
+        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_mean", w * h * 12), ("out_rgb", w * h * 3), ("out_var", w * h * 4),
+                                                                                    ("scratch", scratch_bytes)]:
+            p = C.c_void_p()
+            if H.hipMalloc(C.byref(p), nbytes) != 0:
+                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
+            ptrs[name] = p.value
+        for name, v in host.items():
+            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
+                raise RuntimeError("hipMemcpy failed")
+        common = dict(albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"])
+        args = (w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["out_var"], ptrs["scratch"], scratch_bytes)
+
+        def call_nlm(form):
+            os.environ["CRT_NLM_FORM"] = form
+            return crt.denoise_nlm_device(*args, **common, **nlm_settings(a))["total_ms"]
+
+        calls = {"denoise_var_3": lambda: crt.denoise_var_device(*args, iterations=3, **common)["total_ms"],
+                 "nlm_direct": lambda: call_nlm("direct"), "nlm_shared": lambda: call_nlm("shared")}
+        ms = {k: [] for k in calls}
+        for _ in range(a.warmup + a.calls):
+            for k, f in calls.items():
+                ms[k].append(f())
+        run = {"width": w, "height": h}
+        for k, v in ms.items():
+            run[k + "_ms_median"] = round(statistics.median(v[a.warmup:]), 4)
+            run[k + "_ms_best"] = round(min(v[a.warmup:]), 4)
+        run["shared_over_direct"] = round(run["nlm_shared_ms_median"] / run["nlm_direct_ms_median"], 4)
+        out["runs"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        for p in ptrs.values():
+            H.hipFree(C.c_void_p(p))
+    if before is None:
+        os.environ.pop("CRT_NLM_FORM", None)
+    else:
+        os.environ["CRT_NLM_FORM"] = before
+    print(json.dumps(out), flush=True)
+
+
 def error_table(a):
     import numpy as np
     w, h = (int(v) for v in a.error_size.split("x"))
@@ -217,12 +317,16 @@ def main():
     ap.add_argument("--sigma-color", default="4,6,8,16", help="--error --demodulate: the colour sigmas of the table")
     ap.add_argument("--cells", type=int, default=12, help="--error --demodulate with the scene cornell-box-textured: cells per wall side")
     ap.add_argument("--ref-seed", type=int, default=999, help="--error --demodulate: the seed of the converged frame")
+    ap.add_argument("--nlm", action="store_true", help="time crt_denoise_nlm_device (both forms) beside crt_denoise_var_device; with --error: the error rows at spp 8 and 32")
+    ap.add_argument("--nlm-params", default="", help="--nlm: RADIUS,PATCH,K instead of the filter's defaults")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
     if a.error:
-        return demodulated_error_table(a) if a.demodulate else error_table(a)
+        return nlm_error_table(a) if a.nlm else demodulated_error_table(a) if a.demodulate else error_table(a)
     H = hip_runtime()
+    if a.nlm:
+        return nlm_times(a, H)
     if a.demodulate:
         return modulate_times(a, H)
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
