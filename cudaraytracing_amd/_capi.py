@@ -294,7 +294,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
            "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
-           "crt_device_math", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
+           "crt_device_math", "crt_device_fn", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
            "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
@@ -410,6 +410,7 @@ def lib():
     L.crt_multi_frame_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.crt_intersect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.crt_device_math.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.crt_device_fn.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     L.crt_device_philox.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crt_device_rcp_check.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.crt_scene_export.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]

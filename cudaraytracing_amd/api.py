@@ -1462,6 +1462,24 @@ def device_math(fn, a, b=None, device=0):
     return out
 
 
+def device_fn(name, records, out_words, device=0):
+    """One named device function per row of `records` (crt_device_fn, include/crt.h): an (n, input words) array of uint32 or float32,
+    taken as bits; returns the (n, out_words) results as uint32.  Row i is computed by lane i % 64 of wave i / 64."""
+    r = np.asarray(records)
+    if r.dtype not in (np.dtype(np.uint32), np.dtype(np.float32), np.dtype(np.int32)):
+        raise TypeError("device_fn: records must be uint32, int32 or float32 (they are passed as bits)")
+    r = np.ascontiguousarray(r).view(np.uint32)
+    if r.ndim == 1:
+        r = r.reshape(-1, 1)
+    if r.ndim != 2:
+        raise ValueError("device_fn: records must be (n, input words)")
+    n, in_words = r.shape
+    out = np.zeros((max(n, 1), max(int(out_words), 1)), dtype=np.uint32)
+    src = r if n else np.zeros((1, max(in_words, 1)), dtype=np.uint32)
+    capi.check(capi.lib().crt_device_fn(device, name.encode(), n, capi.ptr(src), in_words, capi.ptr(out), int(out_words)), "crt_device_fn")
+    return out[:n, :int(out_words)]
+
+
 def device_rcp_check(device=0):
     """(mismatches inside the guarded range, mismatches outside it) of the kernels' short reciprocal against
     the division 1.0f / x over all 2^32 inputs (crt_device_rcp_check)."""

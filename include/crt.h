@@ -893,6 +893,22 @@ int crt_intersect(crt_scene* scene, uint32_t n, const float* origins, const floa
  * tests against the oracle.  fn in {"sin","cos","tan","acos","atan2","exp","log10","pow","uniform"}. */
 int crt_device_math(int device, const char* fn, uint32_t n, const float* a, const float* b, float* out);
 int crt_device_philox(int device, uint32_t n, const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);
+/* One named device function per element, as the render kernels call it, for value-level parity tests.  A record is a fixed number of
+ * 32-bit words, floats and integers alike, passed as bits: element i reads in[i * in_words ..] and writes out[i * out_words ..].
+ * Element i is computed by thread i of a launch with 256-thread blocks, so it is lane i % 64 of wave i / 64: the elements
+ * [64 w, 64 w + 64) meet the wave-uniform branches (the guard of unit3 / div3) together.  Draws go in as raw words and become uniforms
+ * through the kernels' own mapping.  name (input words -> output words):
+ *   sin cos tan asin acos atan exp log log10 uniform (1 -> 1), sincos (1 -> 2: sin, cos), atan2 (y, x) pow (x, y) (2 -> 1);
+ *   dot3 (a, b: 6 -> 1), cross3 (a, b: 6 -> 3), norm3 (3 -> 1), unit3 (3 -> 3), div3 (a, s: 4 -> 3), make_ray (d: 3 -> 6 = unit3(d), 1 / each);
+ *   to_world (a, N: 6 -> 3), sample_hemisphere (N, word1, word2: 5 -> 3), sample_lobe (out, delta_theta, delta_phi, word1, word2: 7 -> 3),
+ *   bounce_dir (N, rb.y, rb.z: 5 -> 3);
+ *   cos_to_next (from, to, n: 9 -> 1), roulette (seed lo, seed hi, pixel, k, depth, p_rr: 6 -> 5 = stop, rb.xyzw),
+ *   probe_dir (seed lo, seed hi, pixel, k, depth, ns, arrived, n: 12 -> 3), probe_term (n, kd, ke, o, d, t, ns: 17 -> 3),
+ *   indirect_step (L, f_r, cos, p_rr, L_dir: 11 -> 3), seed_direct (L_dir: 3 -> 3), seed_emitter (deepest, ke: 4 -> 3);
+ *   tonemap (1 -> 1: the byte of one channel).
+ * An unknown name, a null pointer, word counts other than the function's or a negative device are CRT_ERR_INVALID_ARG, reported before
+ * any device call; n == 0 is CRT_OK. */
+int crt_device_fn(int device, const char* name, uint32_t n, const uint32_t* in, uint32_t in_words, uint32_t* out, uint32_t out_words);
 /* Exhaustive self-check of the short reciprocal the kernels use in place of the division 1.0f / x (Ray.cuh:14,
  * DeviceTriangle.cuh:47): evaluates both for all 2^32 bit patterns of x on the device and returns, in *mismatches, the
  * number of inputs INSIDE the guarded range (2^-126 <= |x| < 2^126) whose bits differ (must be 0), and in *outside the

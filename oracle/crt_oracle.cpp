@@ -901,6 +901,8 @@ void orc_math(const char* fn, uint32_t n, const float* a, const float* b, float*
         else if (f == "cos") out[i] = om_cosf(x);
         else if (f == "tan") out[i] = om_tanf(x);
         else if (f == "acos") out[i] = om_acosf(x);
+        else if (f == "asin") out[i] = om_asinf(x);
+        else if (f == "atan") out[i] = om_atanf(x);
         else if (f == "atan2") out[i] = om_atan2f(x, y);
         else if (f == "exp") out[i] = om_expf(x);
         else if (f == "log") out[i] = om_logf(x);
@@ -925,6 +927,37 @@ void orc_sample_lobe(const float o[3], float dt, float dp, float u1, float u2, f
 {
     V3 r = sample_lobe(v3(o[0], o[1], o[2]), dt, dp, u1, u2);
     res[0] = r.x; res[1] = r.y; res[2] = r.z;
+}
+/* The samplers and vector units above over n records of 32-bit words (floats as bits, draws as raw words mapped by orc_uniform), for
+ * value-level comparisons with the device at sizes where one call per element from Python is too slow.  Returns the output words per
+ * record, or -1 for an unknown name / a wrong input record length. */
+int orc_fn(const char* fn, uint32_t n, const uint32_t* in, uint32_t in_words, uint32_t* out)
+{
+    const std::string f(fn);
+    struct Row { const char* name; uint32_t iw, ow; };
+    static const Row rows[] = {{"to_world", 6, 3}, {"sample_hemisphere", 5, 3}, {"sample_lobe", 7, 3}, {"bounce_dir", 5, 3},
+                               {"normalized", 3, 3}, {"norm", 3, 1}, {"dot", 6, 1}, {"cross", 6, 3}};
+    const Row* row = nullptr;
+    for (const Row& r : rows)
+        if (f == r.name) row = &r;
+    if (!row || row->iw != in_words) return -1;
+    auto fl = [](uint32_t u) { float v; std::memcpy(&v, &u, 4); return v; };
+    auto bits = [](float v) { uint32_t u; std::memcpy(&u, &v, 4); return u; };
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t* w = in + (size_t)i * in_words;
+        uint32_t* o = out + (size_t)i * row->ow;
+        auto vec = [&](int k) { return v3(fl(w[k]), fl(w[k + 1]), fl(w[k + 2])); };
+        auto put = [&](V3 r) { o[0] = bits(r.x); o[1] = bits(r.y); o[2] = bits(r.z); };
+        if (f == "to_world") put(to_world(vec(0), vec(3)));
+        else if (f == "sample_hemisphere") put(sample_hemisphere(vec(0), orc_uniform(w[3]), orc_uniform(w[4])));
+        else if (f == "sample_lobe") put(sample_lobe(vec(0), fl(w[3]), fl(w[4]), orc_uniform(w[5]), orc_uniform(w[6])));
+        else if (f == "bounce_dir") put(normalized(sample_hemisphere(vec(0), orc_uniform(w[3]), orc_uniform(w[4])))); /* Render.cuh:214 + Ray.cuh:13 */
+        else if (f == "normalized") put(normalized(vec(0)));
+        else if (f == "norm") o[0] = bits(norm(vec(0)));
+        else if (f == "dot") o[0] = bits(dot(vec(0), vec(3)));
+        else put(cross(vec(0), vec(3)));
+    }
+    return (int)row->ow;
 }
 void orc_tonemap(uint32_t n, const float* c, uint8_t* out)
 {

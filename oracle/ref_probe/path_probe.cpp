@@ -8,8 +8,12 @@
  * cuRAND headers of standin/ and the deterministic libm of det_libm.cpp.
  * Nothing of the reference is copied here; this file only calls it.
  *
- *   path_probe MODE job.bin out.bin          MODE = scene | intersect | paths | frame
+ *   path_probe MODE job.bin out.bin          MODE = scene | intersect | paths | frame | samplers
  *
+ * samplers (no scene): job.bin = u32 n_w, f32 a[n_w][3], f32 N[n_w][3], u32 n_h, f32 N[n_h][3], u32 tape[n_h][2], u32 n_l,
+ *   f32 (out[3], delta_theta, delta_phi)[n_l], u32 tape[n_l][2];  out.bin = f32 to_world[n_w][3], f32 get_cuda_random_sphere_vector[n_h][3],
+ *   f32 get_cuda_random_specular_sphere_vector[n_l][3]   (Global.h:35-94)
+ * every other mode:
  * job.bin (little-endian):  u32 n_obj, n_obj x { u32 len, OBJ path, u32 len, MTL dir }, u32 bvh_thresh_n, then
  *   scene      --
  *   intersect  u32 n, f32 origin[n][3], f32 dir[n][3], f32 limit[n]
@@ -119,6 +123,35 @@ int main(int argc, char** argv)
         std::ifstream in(argv[2], std::ios::binary);
         if (!in) { std::fprintf(stderr, "path_probe: cannot read %s\n", argv[2]); return 2; }
         job.buf.assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+    }
+    if (mode == "samplers") {
+        /* Global.h:35-94 at chosen inputs; no scene.  The two tape words of a record are what its two curand_uniform calls read. */
+        Out out{std::fopen(argv[3], "wb")};
+        if (!out.f) { std::fprintf(stderr, "path_probe: cannot write %s\n", argv[3]); return 2; }
+        const uint32_t n_w = job.get<uint32_t>();
+        const std::vector<float> wa = job.array<float>(3 * (size_t)n_w), wn = job.array<float>(3 * (size_t)n_w);
+        const uint32_t n_h = job.get<uint32_t>();
+        const std::vector<float> hn = job.array<float>(3 * (size_t)n_h);
+        const std::vector<uint32_t> hw = job.array<uint32_t>(2 * (size_t)n_h);
+        const uint32_t n_l = job.get<uint32_t>();
+        const std::vector<float> lr = job.array<float>(5 * (size_t)n_l);
+        const std::vector<uint32_t> lw = job.array<uint32_t>(2 * (size_t)n_l);
+        curandState st;
+        for (uint32_t i = 0; i < n_w; i++)
+            out.vec(to_world(Eigen::Vector3f(wa[3 * i], wa[3 * i + 1], wa[3 * i + 2]), Eigen::Vector3f(wn[3 * i], wn[3 * i + 1], wn[3 * i + 2])));
+        for (uint32_t i = 0; i < n_h; i++) {
+            ref_tape_select(hw.data() + 2 * (size_t)i, 2);
+            curand_init(0, 0, 0, &st);
+            out.vec(get_cuda_random_sphere_vector(Eigen::Vector3f(hn[3 * i], hn[3 * i + 1], hn[3 * i + 2]), &st));
+        }
+        for (uint32_t i = 0; i < n_l; i++) {
+            ref_tape_select(lw.data() + 2 * (size_t)i, 2);
+            curand_init(0, 0, 0, &st);
+            const float* r = &lr[5 * (size_t)i];
+            out.vec(get_cuda_random_specular_sphere_vector(Eigen::Vector3f(r[0], r[1], r[2]), r[3], r[4], &st));
+        }
+        if (std::fclose(out.f) != 0) return 2;
+        return 0;
     }
     /* the scene, through the reference's Loader, Object and Scene, in the order its render_view() adds objects */
     Scene scene(1, 1);

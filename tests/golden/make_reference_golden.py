@@ -7,6 +7,8 @@ that take the emitter-probe branch (Render.cuh:304-313), and the probe's outputs
 of words it consumed, view_render_kernel's bytes per pixel with the number of words it consumed.  Per intersect case: the rays, the
 visibility limits, and DeviceBVH::intersect's hit / blocked()'s verdict per ray.  Per scene case: a digest of every field of the
 reference's BVH nodes, triangles and light triangles (the dump itself where it is small), and the SHA-1 of every scene file read.
+samplers.npz: the records of tests/device_fn_sets.py's sampler_records() and what the reference's to_world,
+get_cuda_random_sphere_vector and get_cuda_random_specular_sphere_vector (Global.h:35-94) return for them.
 Data only; a second run reproduces every file byte for byte."""
 import json
 import os
@@ -99,6 +101,15 @@ for case in RP.FRAME_CASES:
              emitter_probe_paths_agree=agree, emitter_probe_paths_agree_unoptimised=agree_unopt, max_depth=int(of["stats"]["max_depth"]), files_sha1=spec.file_hashes())
     meta["frames"][case["id"]] = m
 meta["emitter_probe_paths_agree"] = agree_everywhere
+
+# the reference's own to_world / get_cuda_random_sphere_vector / get_cuda_random_specular_sphere_vector (Global.h:35-94) at chosen inputs
+import device_fn_sets as DS  # noqa: E402
+recs = DS.sampler_records()
+res = RP.probe_samplers(recs, tmp)
+arrays = {"in_" + k: recs[k] for k in RP.SAMPLER_FNS}
+arrays.update({"out_" + k: res[k] for k in RP.SAMPLER_FNS})
+sizes["samplers"] = RP.save("samplers", arrays)
+meta["samplers"] = {k: int(len(recs[k])) for k in RP.SAMPLER_FNS}
 
 with open(os.path.join(RP.GOLD, "meta.json"), "w") as f:
     json.dump(meta, f, indent=1, sort_keys=True)

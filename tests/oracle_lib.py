@@ -97,6 +97,7 @@ def lib():
     L.orc_vec_op.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
     L.orc_sample_hemisphere.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p]
     L.orc_sample_lobe.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
+    L.orc_fn.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     L.orc_tonemap.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p]
     L.orc_ray_log_begin.restype = None
     L.orc_ray_log_end.restype = C.c_uint64
@@ -348,6 +349,19 @@ def sample_lobe(o, dt, dp, u1, u2):
     out = np.zeros(3, dtype=np.float32)
     lib().orc_sample_lobe(_p(oo), float(dt), float(dp), float(u1), float(u2), _p(out))
     return out
+
+
+def fn(name, records):
+    """orc_fn: the oracle's to_world / sample_hemisphere / sample_lobe / bounce_dir / normalized / norm / dot / cross over the rows of an
+    (n, input words) array of bits (uint32 or float32); returns (n, output words) uint32."""
+    r = np.ascontiguousarray(records)
+    assert r.dtype in (np.dtype(np.uint32), np.dtype(np.float32)) and r.ndim == 2
+    r = r.view(np.uint32)
+    out = np.zeros((r.shape[0], 3), dtype=np.uint32)
+    ow = lib().orc_fn(name.encode(), r.shape[0], _p(r), r.shape[1], _p(out))
+    if ow < 0:
+        raise KeyError((name, r.shape[1]))
+    return out.reshape(-1)[:r.shape[0] * ow].reshape(r.shape[0], ow).copy()
 
 
 def tonemap(c):

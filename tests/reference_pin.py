@@ -252,6 +252,31 @@ def probe_frame(spec, case, lens, words, tmpdir, pixels=None, binary=None):
     return rgb, used, per_pixel
 
 
+SAMPLER_FNS = ("to_world", "sample_hemisphere", "sample_lobe")   # Global.h:35-94: to_world, get_cuda_random_sphere_vector, get_cuda_random_specular_sphere_vector
+
+
+def samplers_job(recs):
+    """The records of tests/device_fn_sets.py's sampler_records() (uint32 bits: (a, N), (N, two tape words), (out, delta_theta,
+    delta_phi, two tape words)) as a job of the probe's `samplers` mode, which needs no scene"""
+    tw, sh, sl = (np.ascontiguousarray(recs[k], dtype=np.uint32) for k in SAMPLER_FNS)
+    assert tw.shape[1] == 6 and sh.shape[1] == 5 and sl.shape[1] == 7
+    return struct.pack("<I", len(tw)) + np.ascontiguousarray(tw[:, 0:3]).tobytes() + np.ascontiguousarray(tw[:, 3:6]).tobytes() + \
+        struct.pack("<I", len(sh)) + np.ascontiguousarray(sh[:, 0:3]).tobytes() + np.ascontiguousarray(sh[:, 3:5]).tobytes() + \
+        struct.pack("<I", len(sl)) + np.ascontiguousarray(sl[:, 0:5]).tobytes() + np.ascontiguousarray(sl[:, 5:7]).tobytes()
+
+
+def probe_samplers(recs, tmpdir):
+    """the reference's own three sampler functions at the records: {name: (n, 3) uint32 bits of the result vector}"""
+    _, out, _ = run_probe("samplers", samplers_job(recs), tmpdir)
+    res, pos = {}, 0
+    for k in SAMPLER_FNS:
+        n = len(recs[k])
+        res[k] = np.frombuffer(out, dtype="<u4", count=3 * n, offset=pos).reshape(n, 3).copy()
+        pos += 12 * n
+    assert pos == len(out)
+    return res
+
+
 # ------------------------------------------------------------------------------------------------ the oracle's side
 def oracle_frame(spec, case, osc=None):
     """The oracle's frame of a case with its draw log: rgb, per-path L (h, w, spp, 3), tape words, words per path, flags, camera rays."""
