@@ -91,29 +91,27 @@ class MultiInfo(C.Structure):
         return d
 
 
-class BvhBuildInfo(C.Structure):
+class InfoStruct(C.Structure):
+    """An info struct of plain numbers: as_dict() is its fields by name."""
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class BvhBuildInfo(InfoStruct):
     _fields_ = [("n_triangles", C.c_uint32), ("n_nodes", C.c_uint32), ("levels", C.c_uint32), ("host_ranges", C.c_uint32),
                 ("host_triangles", C.c_uint32), ("host_sorts", C.c_uint32), ("host_sort_elements", C.c_uint64), ("device_ms", C.c_float), ("total_ms", C.c_float), ("host_build_ms", C.c_float)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class AccelInfo(C.Structure):
+class AccelInfo(InfoStruct):
     _fields_ = [("n_leaves", C.c_uint32), ("n_nodes2", C.c_uint32), ("n_nodes4", C.c_uint32), ("depth2", C.c_uint32), ("depth4", C.c_uint32),
                 ("sah_on_device", C.c_uint32), ("index_splits", C.c_uint32), ("sah_ms", C.c_float), ("sah_device_ms", C.c_float), ("runtime_init_ms", C.c_float), ("layout_caps", C.c_uint32)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class TreeScalars(C.Structure):
+class TreeScalars(InfoStruct):
     _fields_ = [("root_fast", C.c_int32), ("root_exact", C.c_int32), ("root3_fast", C.c_int32), ("root3_exact", C.c_int32), ("root4", C.c_int32),
                 ("root4i", C.c_int32), ("n_mixed4i", C.c_uint32), ("empty4_off", C.c_uint32), ("empty4i_off", C.c_uint32), ("coord_max", C.c_float),
                 ("stack_cap", C.c_uint32), ("node4i_f4", C.c_uint32)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class AovBuffers(C.Structure):
@@ -121,11 +119,8 @@ class AovBuffers(C.Structure):
                 ("material", C.c_void_p)]
 
 
-class AovInfo(C.Structure):
+class AovInfo(InfoStruct):
     _fields_ = [("rays", C.c_uint64), ("chunks", C.c_uint32), ("total_ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class AovShadingBuffers(C.Structure):
@@ -136,11 +131,8 @@ class ModulateParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("albedo_floor", C.c_float)]
 
 
-class ModulateInfo(C.Structure):
+class ModulateInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class AovSpecularParams(C.Structure):
@@ -170,11 +162,8 @@ class NlmParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
 
-class DenoiseInfo(C.Structure):
+class DenoiseInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("passes", C.c_uint32)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class TemporalParams(C.Structure):
@@ -191,22 +180,16 @@ class TemporalHistory(C.Structure):
                 ("id", C.c_void_p)]
 
 
-class TemporalInfo(C.Structure):
+class TemporalInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("reprojected", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class TemporalClamp(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
 
 
-class TemporalClampInfo(C.Structure):
+class TemporalClampInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("reprojected", C.c_uint64), ("clamped", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class TemporalMomentPlanes(C.Structure):
@@ -222,11 +205,8 @@ class VarianceEstimateInputs(C.Structure):
     _fields_ = [("m1", C.c_void_p), ("m2", C.c_void_p), ("history", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
 
 
-class VarianceEstimateInfo(C.Structure):
+class VarianceEstimateInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("spatial", C.c_uint64)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class AdaptiveParams(C.Structure):
@@ -246,19 +226,13 @@ class AdaptiveInfo(C.Structure):
         return d
 
 
-class MapInfo(C.Structure):
+class MapInfo(InfoStruct):
     _fields_ = [("paths", C.c_uint64), ("paths_uniform", C.c_uint64), ("launches", C.c_uint32), ("max_samples", C.c_uint32),
                 ("kernel_ms", C.c_float), ("total_ms", C.c_float)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class PlanInfo(C.Structure):
+class PlanInfo(InfoStruct):
     _fields_ = [("samples", C.c_uint32), ("spp", C.c_uint32)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 # the buffers of crt_aov_buffers: name -> (values per pixel, numpy type)

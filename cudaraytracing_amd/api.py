@@ -890,32 +890,67 @@ def _aov_specular_params(max_bounces=None):
     return p
 
 
+def _vp(p):
+    return C.c_void_p(p) if p else None
+
+
+def _defaults(struct, call, width=None, height=None, **settings):
+    """A params struct as its defaults call (crt_*_defaults, by name) fills it, then the frame's size if given, then the settings that
+    are not None, each as the type of its field."""
+    p = struct()
+    capi.check(getattr(capi.lib(), call)(C.byref(p)), call)
+    if width is not None:
+        p.width, p.height = int(width), int(height)
+    for name, v in settings.items():
+        if v is not None:
+            setattr(p, name, type(getattr(p, name))(v))
+    return p
+
+
+def _settings(p, names=None):
+    """The settings of a params struct as a dict (names None: every field but the frame's size)."""
+    return {n: getattr(p, n) for n in names or [f for f, _ in p._fields_ if f not in ("width", "height")]}
+
+
+def _image_inputs(who, what, fields, struct=None, needs=None):
+    """The host arrays of an image operation.  fields = ((name, array or None, values per pixel), ...): the first is the (H, W, 3) image
+    (`what` in the error), the others must be (H, W, 3) or (H, W) with its H and W; needs = (name, what it is) of a buffer that may
+    not be None.  Returns them as contiguous float32 arrays (None stays None), and sets the fields of the ctypes `struct` to their
+    addresses: the caller keeps the list for as long as the struct is in use."""
+    c = np.ascontiguousarray(fields[0][1], dtype=np.float32)
+    if c.ndim != 3 or c.shape[2] != 3:
+        raise ValueError("%s needs %s, got %r" % (who, what, c.shape))
+    if needs is not None and dict((n, a) for n, a, _ in fields)[needs[0]] is None:
+        raise ValueError("%s needs %s" % (who, needs[1]))
+    h, w = c.shape[:2]
+    arrays = [c]
+    for name, a, channels in fields[1:]:
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            shape = (h, w, 3) if channels == 3 else (h, w)
+            if a.shape != shape:
+                raise ValueError("%s: %s has shape %r, expected %r" % (who, name, a.shape, shape))
+        arrays.append(a)
+    if struct is not None:
+        for (name, _, _), a in zip(fields, arrays):
+            if a is not None:
+                setattr(struct, name, a.ctypes.data)
+    return arrays
+
+
 def denoise_defaults():
     """crt_denoise_defaults as a dict: iterations and the four sigmas."""
-    p = capi.DenoiseParams()
-    capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
-    return {n: getattr(p, n) for n, _ in p._fields_ if n not in ("width", "height")}
+    return _settings(_defaults(capi.DenoiseParams, "crt_denoise_defaults"))
 
 
 def denoise_var_defaults():
     """crt_denoise_var_defaults as a dict: iterations and the four sigmas of the variance-guided filter."""
-    p = capi.DenoiseParams()
-    capi.check(capi.lib().crt_denoise_var_defaults(C.byref(p)), "crt_denoise_var_defaults")
-    return {n: getattr(p, n) for n, _ in p._fields_ if n not in ("width", "height")}
+    return _settings(_defaults(capi.DenoiseParams, "crt_denoise_var_defaults"))
 
 
 def _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=False):
-    p = capi.DenoiseParams()
-    if var:
-        capi.check(capi.lib().crt_denoise_var_defaults(C.byref(p)), "crt_denoise_var_defaults")
-    else:
-        capi.check(capi.lib().crt_denoise_defaults(C.byref(p)), "crt_denoise_defaults")
-    p.width, p.height = int(width), int(height)
-    for name, v in (("iterations", iterations), ("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo),
-                    ("sigma_depth", sigma_depth)):
-        if v is not None:
-            setattr(p, name, int(v) if name == "iterations" else float(v))
-    return p
+    return _defaults(capi.DenoiseParams, "crt_denoise_var_defaults" if var else "crt_denoise_defaults", width, height, iterations=iterations,
+                     sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth)
 
 
 def denoise_scratch_bytes(width, height):
@@ -929,20 +964,10 @@ def denoise(color, albedo=None, normal=None, depth=None, iterations=None, sigma_
     """AOV-guided edge-avoiding a-trous filter (crt_denoise, contract: include/crt.h) of an (H, W, 3) float32 image of pre-tone-map
     radiance; albedo, normal (H, W, 3) and depth (H, W) are optional guides, None settings take crt_denoise_defaults.  Returns
     (rgb, mean): the RGB8 tone map (None without want_rgb) and the filtered radiance; with return_info also the crt_denoise_info dict."""
-    c = np.ascontiguousarray(color, dtype=np.float32)
-    if c.ndim != 3 or c.shape[2] != 3:
-        raise ValueError("denoise needs an (H, W, 3) colour image, got %r" % (c.shape,))
-    h, w = c.shape[:2]
-    inputs, keep = capi.DenoiseInputs(), [c]
-    inputs.color = c.ctypes.data
-    for name, a, shape in (("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise ValueError("denoise: %s has shape %r, expected %r" % (name, a.shape, shape))
-        keep.append(a)
-        setattr(inputs, name, a.ctypes.data)
+    inputs = capi.DenoiseInputs()
+    keep = _image_inputs("denoise", "an (H, W, 3) colour image", (("color", color, 3), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1)),
+                         inputs)
+    h, w = keep[0].shape[:2]
     prm = _denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
     mean = np.zeros((h, w, 3), dtype=np.float32)
     rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
@@ -959,10 +984,36 @@ def denoise_device(width, height, color_ptr, out_mean_ptr, out_rgb_ptr, scratch_
     inputs = capi.DenoiseInputs(color_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
     prm = _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth)
     info = capi.DenoiseInfo()
-    capi.check(capi.lib().crt_denoise_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
-                                             C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None, C.c_void_p(scratch_ptr) if scratch_ptr else None,
-                                             int(scratch_bytes), C.c_void_p(stream) if stream else None,
-                                             C.byref(info) if want_info else None), "crt_denoise_device")
+    capi.check(capi.lib().crt_denoise_device(device, C.byref(prm), C.byref(inputs), _vp(out_mean_ptr), _vp(out_rgb_ptr), _vp(scratch_ptr),
+                                             int(scratch_bytes), _vp(stream), C.byref(info) if want_info else None), "crt_denoise_device")
+    return info.as_dict() if want_info else None
+
+
+def _denoise_var_host(who, prm_of, color, variance, albedo, normal, depth, device, want_rgb, want_variance, return_info):
+    """denoise_var / denoise_nlm on host arrays: the two calls share their inputs, outputs and info; prm_of(w, h): the params struct"""
+    inputs = capi.DenoiseVarInputs()
+    keep = _image_inputs(who, "an (H, W, 3) colour image", (("color", color, 3), ("variance", variance, 3), ("albedo", albedo, 3),
+                                                            ("normal", normal, 3), ("depth", depth, 1)), inputs,
+                         needs=("variance", "the variance buffer (Render.variance)"))
+    h, w = keep[0].shape[:2]
+    prm = prm_of(w, h)
+    mean = np.zeros((h, w, 3), dtype=np.float32)
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    var = np.zeros((h, w), dtype=np.float32) if want_variance else None
+    info = capi.DenoiseInfo()
+    capi.check(getattr(capi.lib(), "crt_" + who)(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(var), C.byref(info)),
+               "crt_" + who)
+    out = (rgb, mean, var) if want_variance else (rgb, mean)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def _denoise_var_device(who, prm, color_ptr, variance_ptr, albedo_ptr, normal_ptr, depth_ptr, out_mean_ptr, out_rgb_ptr, out_variance_ptr, scratch_ptr,
+                        scratch_bytes, device, stream, want_info):
+    """denoise_var_device / denoise_nlm_device: as _denoise_var_host"""
+    inputs = capi.DenoiseVarInputs(color_ptr or None, variance_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
+    info = capi.DenoiseInfo()
+    capi.check(getattr(capi.lib(), who)(device, C.byref(prm), C.byref(inputs), _vp(out_mean_ptr), _vp(out_rgb_ptr), _vp(out_variance_ptr),
+                                        _vp(scratch_ptr), int(scratch_bytes), _vp(stream), C.byref(info) if want_info else None), who)
     return info.as_dict() if want_info else None
 
 
@@ -971,31 +1022,8 @@ def denoise_var(color, variance, albedo=None, normal=None, depth=None, iteration
     """Variance-guided form of the filter (crt_denoise_var, contract: include/crt.h): `variance` is the (H, W, 3) buffer of
     Render.variance(); None settings take crt_denoise_var_defaults.  Returns (rgb, mean), with want_variance (rgb, mean, var) -- var
     (H, W) float32, the filter's estimate of the noise left -- and with return_info also the crt_denoise_info dict."""
-    c = np.ascontiguousarray(color, dtype=np.float32)
-    if c.ndim != 3 or c.shape[2] != 3:
-        raise ValueError("denoise_var needs an (H, W, 3) colour image, got %r" % (c.shape,))
-    if variance is None:
-        raise ValueError("denoise_var needs the variance buffer (Render.variance)")
-    h, w = c.shape[:2]
-    inputs, keep = capi.DenoiseVarInputs(), [c]
-    inputs.color = c.ctypes.data
-    for name, a, shape in (("variance", variance, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise ValueError("denoise_var: %s has shape %r, expected %r" % (name, a.shape, shape))
-        keep.append(a)
-        setattr(inputs, name, a.ctypes.data)
-    prm = _denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=True)
-    mean = np.zeros((h, w, 3), dtype=np.float32)
-    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
-    var = np.zeros((h, w), dtype=np.float32) if want_variance else None
-    info = capi.DenoiseInfo()
-    capi.check(capi.lib().crt_denoise_var(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(var), C.byref(info)),
-               "crt_denoise_var")
-    out = (rgb, mean, var) if want_variance else (rgb, mean)
-    return out + (info.as_dict(),) if return_info else out
+    return _denoise_var_host("denoise_var", lambda w, h: _denoise_params(w, h, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=True),
+                             color, variance, albedo, normal, depth, device, want_rgb, want_variance, return_info)
 
 
 def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out_rgb_ptr, out_variance_ptr, scratch_ptr, scratch_bytes,
@@ -1003,16 +1031,9 @@ def denoise_var_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                        sigma_albedo=None, sigma_depth=None, device=0, stream=None, want_info=True):
     """Enqueues the variance-guided filter with everything in device memory (raw device pointers, crt_denoise_var_device); the scratch
     is that of denoise_device (denoise_scratch_bytes).  With want_info the call synchronizes the stream and returns the info dict."""
-    inputs = capi.DenoiseVarInputs(color_ptr or None, variance_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
     prm = _denoise_params(width, height, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, var=True)
-    info = capi.DenoiseInfo()
-    capi.check(capi.lib().crt_denoise_var_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
-                                                 C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None,
-                                                 C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
-                                                 C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
-                                                 C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
-               "crt_denoise_var_device")
-    return info.as_dict() if want_info else None
+    return _denoise_var_device("crt_denoise_var_device", prm, color_ptr, variance_ptr, albedo_ptr, normal_ptr, depth_ptr, out_mean_ptr, out_rgb_ptr,
+                               out_variance_ptr, scratch_ptr, scratch_bytes, device, stream, want_info)
 
 
 _NLM_SETTINGS = ("radius", "patch", "k", "alpha", "sigma_normal", "sigma_albedo", "sigma_depth")
@@ -1020,20 +1041,11 @@ _NLM_SETTINGS = ("radius", "patch", "k", "alpha", "sigma_normal", "sigma_albedo"
 
 def denoise_nlm_defaults():
     """crt_denoise_nlm_defaults as a dict: radius, patch, k, alpha and the three guide sigmas."""
-    p = capi.NlmParams()
-    capi.check(capi.lib().crt_denoise_nlm_defaults(C.byref(p)), "crt_denoise_nlm_defaults")
-    return {n: getattr(p, n) for n in _NLM_SETTINGS}
+    return _settings(_defaults(capi.NlmParams, "crt_denoise_nlm_defaults"), _NLM_SETTINGS)
 
 
 def _nlm_params(width, height, **settings):
-    p = capi.NlmParams()
-    capi.check(capi.lib().crt_denoise_nlm_defaults(C.byref(p)), "crt_denoise_nlm_defaults")
-    p.width, p.height = int(width), int(height)
-    for name in _NLM_SETTINGS:
-        v = settings.get(name)
-        if v is not None:
-            setattr(p, name, int(v) if name in ("radius", "patch") else float(v))
-    return p
+    return _defaults(capi.NlmParams, "crt_denoise_nlm_defaults", width, height, **{n: settings.get(n) for n in _NLM_SETTINGS})
 
 
 def denoise_nlm_scratch_bytes(width, height):
@@ -1047,31 +1059,9 @@ def denoise_nlm(color, variance, albedo=None, normal=None, depth=None, radius=No
     """Non-local means with variance-normalised patch distances, joint with the guides (crt_denoise_nlm, contract: include/crt.h):
     `variance` is the (H, W, 3) buffer of Render.variance(); None settings take crt_denoise_nlm_defaults.  Returns (rgb, mean), with
     want_variance (rgb, mean, var) -- var (H, W) float32 -- and with return_info also the crt_denoise_info dict."""
-    c = np.ascontiguousarray(color, dtype=np.float32)
-    if c.ndim != 3 or c.shape[2] != 3:
-        raise ValueError("denoise_nlm needs an (H, W, 3) colour image, got %r" % (c.shape,))
-    if variance is None:
-        raise ValueError("denoise_nlm needs the variance buffer (Render.variance)")
-    h, w = c.shape[:2]
-    inputs, keep = capi.DenoiseVarInputs(), [c]
-    inputs.color = c.ctypes.data
-    for name, a, shape in (("variance", variance, (h, w, 3)), ("albedo", albedo, (h, w, 3)), ("normal", normal, (h, w, 3)), ("depth", depth, (h, w))):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise ValueError("denoise_nlm: %s has shape %r, expected %r" % (name, a.shape, shape))
-        keep.append(a)
-        setattr(inputs, name, a.ctypes.data)
-    prm = _nlm_params(w, h, radius=radius, patch=patch, k=k, alpha=alpha, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth)
-    mean = np.zeros((h, w, 3), dtype=np.float32)
-    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
-    var = np.zeros((h, w), dtype=np.float32) if want_variance else None
-    info = capi.DenoiseInfo()
-    capi.check(capi.lib().crt_denoise_nlm(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(var), C.byref(info)),
-               "crt_denoise_nlm")
-    out = (rgb, mean, var) if want_variance else (rgb, mean)
-    return out + (info.as_dict(),) if return_info else out
+    settings = dict(radius=radius, patch=patch, k=k, alpha=alpha, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth)
+    return _denoise_var_host("denoise_nlm", lambda w, h: _nlm_params(w, h, **settings), color, variance, albedo, normal, depth, device, want_rgb,
+                             want_variance, return_info)
 
 
 def denoise_nlm_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out_rgb_ptr, out_variance_ptr, scratch_ptr, scratch_bytes,
@@ -1079,48 +1069,19 @@ def denoise_nlm_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                        sigma_albedo=None, sigma_depth=None, device=0, stream=None, want_info=True):
     """Enqueues the non-local-means filter with everything in device memory (raw device pointers, crt_denoise_nlm_device); the caller
     owns the scratch (denoise_nlm_scratch_bytes).  With want_info the call synchronizes the stream and returns the info dict."""
-    inputs = capi.DenoiseVarInputs(color_ptr or None, variance_ptr or None, albedo_ptr or None, normal_ptr or None, depth_ptr or None)
     prm = _nlm_params(width, height, radius=radius, patch=patch, k=k, alpha=alpha, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo,
                       sigma_depth=sigma_depth)
-    info = capi.DenoiseInfo()
-    capi.check(capi.lib().crt_denoise_nlm_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_mean_ptr) if out_mean_ptr else None,
-                                                 C.c_void_p(out_rgb_ptr) if out_rgb_ptr else None,
-                                                 C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
-                                                 C.c_void_p(scratch_ptr) if scratch_ptr else None, int(scratch_bytes),
-                                                 C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
-               "crt_denoise_nlm_device")
-    return info.as_dict() if want_info else None
+    return _denoise_var_device("crt_denoise_nlm_device", prm, color_ptr, variance_ptr, albedo_ptr, normal_ptr, depth_ptr, out_mean_ptr, out_rgb_ptr,
+                               out_variance_ptr, scratch_ptr, scratch_bytes, device, stream, want_info)
 
 
 def modulate_defaults():
     """crt_modulate_defaults as a dict: albedo_floor."""
-    p = capi.ModulateParams()
-    capi.check(capi.lib().crt_modulate_defaults(C.byref(p)), "crt_modulate_defaults")
-    return {"albedo_floor": float(p.albedo_floor)}
+    return _settings(_defaults(capi.ModulateParams, "crt_modulate_defaults"))
 
 
 def _modulate_params(width, height, albedo_floor):
-    p = capi.ModulateParams()
-    capi.check(capi.lib().crt_modulate_defaults(C.byref(p)), "crt_modulate_defaults")
-    p.width, p.height = int(width), int(height)
-    if albedo_floor is not None:
-        p.albedo_floor = float(albedo_floor)
-    return p
-
-
-def _modulate_images(who, image, others):
-    """The (H, W, 3) float32 image of demodulate / modulate and the buffers that must have its shape (None: not given)."""
-    c = np.ascontiguousarray(image, dtype=np.float32)
-    if c.ndim != 3 or c.shape[2] != 3:
-        raise ValueError("%s needs an (H, W, 3) image, got %r" % (who, c.shape))
-    out = [c]
-    for name, a in others:
-        if a is not None:
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            if a.shape != c.shape:
-                raise ValueError("%s: %s has shape %r, expected %r" % (who, name, a.shape, c.shape))
-        out.append(a)
-    return out
+    return _defaults(capi.ModulateParams, "crt_modulate_defaults", width, height, albedo_floor=albedo_floor)
 
 
 def demodulate(color, albedo, emission=None, variance=None, albedo_floor=None, device=0, return_info=False):
@@ -1130,7 +1091,8 @@ def demodulate(color, albedo, emission=None, variance=None, albedo_floor=None, d
     albedo^2); with return_info also the crt_modulate_info dict."""
     if albedo is None:
         raise ValueError("demodulate needs the albedo buffer (Render.run_view_aov_shading: diffuse_albedo)")
-    c, a, e, v = _modulate_images("demodulate", color, (("albedo", albedo), ("emission", emission), ("variance", variance)))
+    c, a, e, v = _image_inputs("demodulate", "an (H, W, 3) image", (("color", color, 3), ("albedo", albedo, 3), ("emission", emission, 3),
+                                                                    ("variance", variance, 3)))
     h, w = c.shape[:2]
     prm = _modulate_params(w, h, albedo_floor)
     out = np.zeros((h, w, 3), dtype=np.float32)
@@ -1147,7 +1109,7 @@ def modulate(irradiance, albedo, emission=None, albedo_floor=None, device=0, wan
     mean): the frame's RGB8 tone map (None without want_rgb) and the radiance; with return_info also the crt_modulate_info dict."""
     if albedo is None:
         raise ValueError("modulate needs the albedo buffer (Render.run_view_aov_shading: diffuse_albedo)")
-    i, a, e = _modulate_images("modulate", irradiance, (("albedo", albedo), ("emission", emission)))
+    i, a, e = _image_inputs("modulate", "an (H, W, 3) image", (("irradiance", irradiance, 3), ("albedo", albedo, 3), ("emission", emission, 3)))
     h, w = i.shape[:2]
     prm = _modulate_params(w, h, albedo_floor)
     mean = np.zeros((h, w, 3), dtype=np.float32)
@@ -1156,10 +1118,6 @@ def modulate(irradiance, albedo, emission=None, albedo_floor=None, device=0, wan
     capi.check(capi.lib().crt_modulate(device, C.byref(prm), capi.ptr(i), capi.ptr(a), capi.ptr(e), capi.ptr(mean), capi.ptr(rgb), C.byref(info)),
                "crt_modulate")
     return (rgb, mean, info.as_dict()) if return_info else (rgb, mean)
-
-
-def _vp(p):
-    return C.c_void_p(p) if p else None
 
 
 def demodulate_device(width, height, color_ptr, albedo_ptr, out_ptr, emission_ptr=None, variance_ptr=None, out_variance_ptr=None, albedo_floor=None,
@@ -1197,22 +1155,17 @@ def _camera(eye_pos, inv_view_mat, fovY):
 
 def temporal_defaults():
     """crt_temporal_defaults as a dict: depth_tolerance, normal_tolerance, alpha_min."""
-    p = capi.TemporalParams()
-    capi.check(capi.lib().crt_temporal_defaults(C.byref(p)), "crt_temporal_defaults")
-    return {n: getattr(p, n) for n in ("depth_tolerance", "normal_tolerance", "alpha_min")}
+    return _settings(_defaults(capi.TemporalParams, "crt_temporal_defaults"), ("depth_tolerance", "normal_tolerance", "alpha_min"))
 
 
 def temporal_clamp_defaults():
     """crt_temporal_clamp_defaults as a dict: radius, gamma."""
-    c = capi.TemporalClamp()
-    capi.check(capi.lib().crt_temporal_clamp_defaults(C.byref(c)), "crt_temporal_clamp_defaults")
-    return {"radius": int(c.radius), "gamma": float(c.gamma)}
+    return _settings(_defaults(capi.TemporalClamp, "crt_temporal_clamp_defaults"))
 
 
 def _temporal_clamp(clamp):
     """clamp=True (the defaults) or a dict of radius / gamma -> crt_temporal_clamp"""
-    c = capi.TemporalClamp()
-    capi.check(capi.lib().crt_temporal_clamp_defaults(C.byref(c)), "crt_temporal_clamp_defaults")
+    c = _defaults(capi.TemporalClamp, "crt_temporal_clamp_defaults")
     if clamp is True:
         return c
     if not isinstance(clamp, dict) or set(clamp) - {"radius", "gamma"}:
@@ -1228,14 +1181,10 @@ def _temporal_clamp(clamp):
 
 
 def _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min):
-    p = capi.TemporalParams()
-    capi.check(capi.lib().crt_temporal_defaults(C.byref(p)), "crt_temporal_defaults")
-    p.width, p.height = int(width), int(height)
+    p = _defaults(capi.TemporalParams, "crt_temporal_defaults", width, height, depth_tolerance=depth_tolerance, normal_tolerance=normal_tolerance,
+                  alpha_min=alpha_min)
     p.cur = _camera(*camera)
     p.prev = _camera(*(prev_camera if prev_camera is not None else camera))
-    for name, v in (("depth_tolerance", depth_tolerance), ("normal_tolerance", normal_tolerance), ("alpha_min", alpha_min)):
-        if v is not None:
-            setattr(p, name, float(v))
     return p
 
 
@@ -1341,7 +1290,6 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
     fc = fill(capi.TemporalFrame(), cur_ptrs)
     fp = fill(capi.TemporalHistory(), prev_ptrs) if prev_ptrs is not None else None
     prm = _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min)
-    vp = lambda p: C.c_void_p(p) if p else None
     if moments is not None:
         if not isinstance(moments, dict) or set(moments) - {"m1", "m2", "out_m1", "out_m2"}:
             raise ValueError("temporal_device: moments must be None or a dict of out_m1, out_m2 and the history's m1, m2, got %r" % (moments,))
@@ -1351,20 +1299,20 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
         info = capi.TemporalClampInfo()
         capi.check(capi.lib().crt_temporal_moments_device(device, C.byref(prm), C.byref(_temporal_clamp(clamp)) if clamp is not None else None, C.byref(fc),
                                                           C.byref(fp) if fp is not None else None, C.byref(planes) if planes is not None else None,
-                                                          vp(out_color_ptr), vp(out_variance_ptr), vp(out_history_ptr), vp(moments.get("out_m1")),
-                                                          vp(moments.get("out_m2")), vp(out_rgb_ptr), vp(stream), C.byref(info) if want_info else None),
+                                                          _vp(out_color_ptr), _vp(out_variance_ptr), _vp(out_history_ptr), _vp(moments.get("out_m1")),
+                                                          _vp(moments.get("out_m2")), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
                    "crt_temporal_moments_device")
         return info.as_dict() if want_info else None
     if clamp is None:
         info = capi.TemporalInfo()
-        capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, vp(out_color_ptr),
-                                                  vp(out_variance_ptr), vp(out_history_ptr), vp(out_rgb_ptr), vp(stream),
+        capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, _vp(out_color_ptr),
+                                                  _vp(out_variance_ptr), _vp(out_history_ptr), _vp(out_rgb_ptr), _vp(stream),
                                                   C.byref(info) if want_info else None), "crt_temporal_device")
     else:
         info = capi.TemporalClampInfo()
         capi.check(capi.lib().crt_temporal_clamped_device(device, C.byref(prm), C.byref(_temporal_clamp(clamp)), C.byref(fc),
-                                                          C.byref(fp) if fp is not None else None, vp(out_color_ptr), vp(out_variance_ptr),
-                                                          vp(out_history_ptr), vp(out_rgb_ptr), vp(stream), C.byref(info) if want_info else None),
+                                                          C.byref(fp) if fp is not None else None, _vp(out_color_ptr), _vp(out_variance_ptr),
+                                                          _vp(out_history_ptr), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
                    "crt_temporal_clamped_device")
     return info.as_dict() if want_info else None
 
@@ -1377,19 +1325,14 @@ ESTIMATE_OF_MEAN = 1
 
 def variance_estimate_defaults():
     """crt_variance_estimate_defaults as a dict: min_history, radius, sigma_normal, sigma_depth, of_mean, history_cap -- the library's."""
-    p = capi.VarianceEstimateParams()
-    capi.check(capi.lib().crt_variance_estimate_defaults(C.byref(p)), "crt_variance_estimate_defaults")
-    return {n: getattr(p, n) for n in _ESTIMATE_SETTINGS}
+    return _settings(_defaults(capi.VarianceEstimateParams, "crt_variance_estimate_defaults"), _ESTIMATE_SETTINGS)
 
 
 def _estimate_params(width, height, settings):
     unknown = set(settings) - set(_ESTIMATE_SETTINGS)
     if unknown:
         raise ValueError("variance_estimate: unknown settings %r" % sorted(unknown))
-    p = capi.VarianceEstimateParams()
-    capi.check(capi.lib().crt_variance_estimate_defaults(C.byref(p)), "crt_variance_estimate_defaults")
-    p.width, p.height = int(width), int(height)
-    p.of_mean = ESTIMATE_OF_MEAN
+    p = _defaults(capi.VarianceEstimateParams, "crt_variance_estimate_defaults", width, height, of_mean=ESTIMATE_OF_MEAN)
     for name, v in settings.items():
         if v is None:
             continue
@@ -1407,20 +1350,10 @@ def variance_estimate(m1, m2, history, normal=None, depth=None, device=0, return
     sigma_depth, of_mean, history_cap; None or absent takes crt_variance_estimate_defaults, except of_mean, which is 1 here (the variance
     of the accumulated mean: docs/experiments.md).  Returns the (H, W, 3) variance, what denoise_var takes; with return_info also the
     crt_variance_estimate_info dict (total_ms, spatial)."""
-    a1 = np.ascontiguousarray(m1, dtype=np.float32)
-    if a1.ndim != 3 or a1.shape[2] != 3:
-        raise ValueError("variance_estimate needs (H, W, 3) moments, got %r" % (a1.shape,))
-    h, w = a1.shape[:2]
-    inputs, keep = capi.VarianceEstimateInputs(), []
-    for name, a, shape in (("m1", a1, (h, w, 3)), ("m2", m2, (h, w, 3)), ("history", history, (h, w)), ("normal", normal, (h, w, 3)),
-                           ("depth", depth, (h, w))):
-        if a is None:
-            continue
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.shape != shape:
-            raise ValueError("variance_estimate: %s has shape %r, expected %r" % (name, a.shape, shape))
-        keep.append(a)
-        setattr(inputs, name, a.ctypes.data)
+    inputs = capi.VarianceEstimateInputs()
+    keep = _image_inputs("variance_estimate", "(H, W, 3) moments", (("m1", m1, 3), ("m2", m2, 3), ("history", history, 1), ("normal", normal, 3),
+                                                                    ("depth", depth, 1)), inputs)
+    h, w = keep[0].shape[:2]
     prm = _estimate_params(w, h, settings)
     out = np.zeros((h, w, 3), dtype=np.float32)
     info = capi.VarianceEstimateInfo()
@@ -1435,9 +1368,8 @@ def variance_estimate_device(width, height, m1_ptr, m2_ptr, history_ptr, out_var
     inputs = capi.VarianceEstimateInputs(m1_ptr or None, m2_ptr or None, history_ptr or None, normal_ptr or None, depth_ptr or None)
     prm = _estimate_params(width, height, settings)
     info = capi.VarianceEstimateInfo()
-    capi.check(capi.lib().crt_variance_estimate_device(device, C.byref(prm), C.byref(inputs), C.c_void_p(out_variance_ptr) if out_variance_ptr else None,
-                                                       C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None),
-               "crt_variance_estimate_device")
+    capi.check(capi.lib().crt_variance_estimate_device(device, C.byref(prm), C.byref(inputs), _vp(out_variance_ptr), _vp(stream),
+                                                       C.byref(info) if want_info else None), "crt_variance_estimate_device")
     return info.as_dict() if want_info else None
 
 

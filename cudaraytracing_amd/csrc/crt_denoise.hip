@@ -7,7 +7,7 @@
 // A pass is one thread per pixel, 25 taps in the contract's order, every tap read from global memory through the caches; the last pass
 // writes out_mean and the tone-mapped RGB8 itself.  (A form that staged the tile and its halo in LDS for spacing 1 and 2 was measured and
 // dropped: the pass is bound by vector-ALU issue, not by its loads -- docs/experiments.md, "The a-trous denoiser".)
-#include "crt_internal.h"
+#include "crt_filter_host.h"
 
 #include <cstring>
 #include <limits>
@@ -137,23 +137,18 @@ using namespace crtk;
 
 namespace {
 
-const uint32_t kMaxSide = 1u << 24;
-bool sigma_ok(float s) { return s > 0.0f; } // (false for NaN)
-
 // Argument checks of both forms, before any device call
 int denoise_check(const char* who, const crt_denoise_params* prm, const crt_denoise_inputs* in, const void* out_mean, const void* out_rgb)
 {
     const std::string w(who);
     if (!prm || !in) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!in->color) return fail(CRT_ERR_INVALID_ARG, w + ": null colour buffer");
-    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (const int rc = size_positive(w, prm->width, prm->height)) return rc;
     if (prm->iterations < 1 || prm->iterations > 5) return fail(CRT_ERR_INVALID_ARG, w + ": iterations must be 1 .. 5");
     if (!sigma_ok(prm->sigma_color) || !sigma_ok(prm->sigma_normal) || !sigma_ok(prm->sigma_albedo) || !sigma_ok(prm->sigma_depth))
         return fail(CRT_ERR_INVALID_ARG, w + ": every sigma must be > 0 (+inf switches a term off)");
     if (!out_mean && !out_rgb) return fail(CRT_ERR_INVALID_ARG, w + ": no output buffer");
-    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
-    if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
-    return CRT_OK;
+    return size_supported(w, prm->width, prm->height, 64, 4);
 }
 
 uint64_t scratch_bytes_of(uint32_t width, uint32_t height) { return (uint64_t)width * height * 4u * sizeof(float4); }
@@ -178,22 +173,10 @@ int denoise_impl(const char* who, int device, const crt_denoise_params* prm, con
                  void* d_out_rgb, float* d_out_var, void* d_scratch, uint64_t scratch_bytes, hipStream_t st, crt_denoise_info* info)
 {
     const std::string w(who);
-    const int rc = denoise_check(who, prm, in, d_out_mean, d_out_rgb);
+    int rc = denoise_check(who, prm, in, d_out_mean, d_out_rgb);
+    if (rc == CRT_OK) rc = scratch_ok(w, d_scratch, scratch_bytes, scratch_bytes_of(prm->width, prm->height), "crt_denoise_scratch_bytes");
     if (rc != CRT_OK) return rc;
-    if (!d_scratch) return fail(CRT_ERR_INVALID_ARG, w + ": null scratch buffer");
-    if (scratch_bytes < scratch_bytes_of(prm->width, prm->height))
-        return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer too small (crt_denoise_scratch_bytes)");
-    if ((uintptr_t)d_scratch % sizeof(float4) != 0) return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer not 16-byte aligned");
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, w + ": device index out of range");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int status = CRT_OK;
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        if (info) {
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
+    rc = timed_launch(w, device, st, info, [&] {
         const uint64_t npix = (uint64_t)prm->width * prm->height;
         float4* plane = (float4*)d_scratch;
         float4* c[2] = {plane, plane + npix};
@@ -227,19 +210,9 @@ int denoise_impl(const char* who, int device, const crt_denoise_params* prm, con
             }
             HIP_CHECK(hipGetLastError());
         }
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->passes = prm->iterations;
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-    } catch (const HipFail& f) {
-        status = fail_hip(f);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return status;
+    });
+    if (rc == CRT_OK && info) info->passes = prm->iterations;
+    return rc;
 }
 
 // The host-buffer form of either filter (the caller has checked the arguments): device copies of the inputs, denoise_impl under the
@@ -247,33 +220,19 @@ int denoise_impl(const char* who, int device, const crt_denoise_params* prm, con
 int denoise_host(const char* who, const char* who_device, int device, const crt_denoise_params* prm, const crt_denoise_inputs* host_in, const float* variance,
                  float* out_mean, uint8_t* out_rgb, float* out_variance, crt_denoise_info* info)
 {
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> d_color, d_var, d_albedo, d_normal, d_depth, d_mean, d_ovar;
-        DevBuf<uint8_t> d_rgb;
-        DevBuf<float4> d_scratch;
+    const uint64_t npix = (uint64_t)prm->width * prm->height;
+    return host_form(who, device, [&](HostCopies& c) {
         crt_denoise_inputs d{};
-        d.color = d_color.upload(host_in->color, npix * 3);
-        d_var.upload(variance, npix * 3);
-        d.albedo = d_albedo.upload(host_in->albedo, npix * 3);
-        d.normal = d_normal.upload(host_in->normal, npix * 3);
-        d.depth = d_depth.upload(host_in->depth, npix);
-        if (out_mean) d_mean.alloc(npix * 3);
-        if (out_rgb) d_rgb.alloc(npix * 3);
-        if (out_variance) d_ovar.alloc(npix);
-        d_scratch.alloc(npix * 4);
-        const int rc = denoise_impl(who_device, device, prm, &d, d_var.p, d_mean.p, d_rgb.p, d_ovar.p, d_scratch.p, npix * 4 * sizeof(float4), nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        d_mean.download(out_mean, npix * 3);
-        d_rgb.download(out_rgb, npix * 3);
-        d_ovar.download(out_variance, npix);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+        d.color = c.in(host_in->color, npix * 3);
+        const float* d_var = c.in(variance, npix * 3);
+        d.albedo = c.in(host_in->albedo, npix * 3);
+        d.normal = c.in(host_in->normal, npix * 3);
+        d.depth = c.in(host_in->depth, npix);
+        float* d_mean = c.out(out_mean, npix * 3);
+        uint8_t* d_rgb = c.out(out_rgb, npix * 3);
+        float* d_ovar = c.out(out_variance, npix);
+        return denoise_impl(who_device, device, prm, &d, d_var, d_mean, d_rgb, d_ovar, c.scratch<float4>(npix * 4), npix * 4 * sizeof(float4), nullptr, info);
+    });
 }
 
 } // namespace

@@ -2,7 +2,7 @@
 // operations that take a frame from radiance to irradiance and back, so that the denoiser and the temporal pass can filter what does
 // not carry the surfaces' albedo or the lights.  Image operations without a scene handle and without scratch, like the denoiser.
 // The kernels are in crt_modulate.h, in a form the host can compile as well (tools/modulate_host_check.cpp).
-#include "crt_internal.h"
+#include "crt_filter_host.h"
 #include "crt_modulate.h"
 
 #include <cstring>
@@ -12,17 +12,14 @@ using namespace crtk;
 
 namespace {
 
-const uint32_t kMaxSide = 1u << 24; // (the denoiser's limit)
-
 // What both operations and both forms check, before any device call
 int modulate_check(const std::string& w, const crt_modulate_params* prm, const void* image, const void* albedo)
 {
     if (!prm) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!image || !albedo) return fail(CRT_ERR_INVALID_ARG, w + ": null image or albedo buffer");
-    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (const int rc = size_positive(w, prm->width, prm->height)) return rc;
     if (!(prm->albedo_floor >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": albedo_floor must be >= 0 and not NaN");
-    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
-    return CRT_OK;
+    return sides_supported(w, prm->width, prm->height); // (a flat launch over the floats: no tile count to bound)
 }
 int demodulate_check(const char* who, const crt_modulate_params* prm, const void* color, const void* albedo, const void* variance, const void* out,
                      const void* out_variance)
@@ -45,35 +42,6 @@ int remodulate_check(const char* who, const crt_modulate_params* prm, const void
 
 bool aligned16(const void* p) { return (uintptr_t)p % 16u == 0; } // (a null pointer is)
 
-// One kernel on the stream between the two events of `info` (if any); `launch` enqueues it
-template <class Launch> int timed(const char* who, int device, hipStream_t st, crt_modulate_info* info, Launch launch)
-{
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int status = CRT_OK;
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        if (info) {
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
-        launch();
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-    } catch (const HipFail& f) {
-        status = fail_hip(f);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return status;
-}
-
 int demodulate_impl(int device, const crt_modulate_params* prm, const float* color, const float* albedo, const float* emission, const float* variance,
                     float* out, float* out_variance, hipStream_t st, crt_modulate_info* info)
 {
@@ -83,7 +51,7 @@ int demodulate_impl(int device, const crt_modulate_params* prm, const float* col
     P.floor = prm->albedo_floor;
     P.color = color; P.albedo = albedo; P.emission = emission; P.variance = variance; P.out = out; P.out_variance = out_variance;
     P.vec = aligned16(color) && aligned16(albedo) && aligned16(emission) && aligned16(variance) && aligned16(out) && aligned16(out_variance);
-    return timed("crt_demodulate_device", device, st, info, [&] { launch_demodulate(P, st); });
+    return timed_launch("crt_demodulate_device", device, st, info, [&] { launch_demodulate(P, st); });
 }
 
 int modulate_impl(int device, const crt_modulate_params* prm, const float* irradiance, const float* albedo, const float* emission, float* out_mean,
@@ -95,7 +63,7 @@ int modulate_impl(int device, const crt_modulate_params* prm, const float* irrad
     P.floor = prm->albedo_floor;
     P.irradiance = irradiance; P.albedo = albedo; P.emission = emission; P.out_mean = out_mean; P.out_rgb = out_rgb;
     P.vec = aligned16(irradiance) && aligned16(albedo) && aligned16(emission) && aligned16(out_mean) && (uintptr_t)out_rgb % 4u == 0;
-    return timed("crt_modulate_device", device, st, info, [&] { launch_modulate(P, st); });
+    return timed_launch("crt_modulate_device", device, st, info, [&] { launch_modulate(P, st); });
 }
 
 } // namespace
@@ -124,23 +92,11 @@ int crt_demodulate(int device, const crt_modulate_params* prm, const float* colo
 {
     const int rc0 = demodulate_check("crt_demodulate", prm, color, albedo, variance, out_irradiance, out_variance);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_demodulate: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t n = (uint64_t)prm->width * prm->height * 3u;
-        DevBuf<float> d_color, d_albedo, d_emission, d_variance, d_out, d_ovar;
-        d_color.upload(color, n); d_albedo.upload(albedo, n); d_emission.upload(emission, n); d_variance.upload(variance, n);
-        d_out.alloc(n);
-        if (out_variance) d_ovar.alloc(n);
-        const int rc = demodulate_impl(device, prm, d_color.p, d_albedo.p, d_emission.p, d_variance.p, d_out.p, d_ovar.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        d_out.download(out_irradiance, n);
-        d_ovar.download(out_variance, n);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    const uint64_t n = (uint64_t)prm->width * prm->height * 3u;
+    return host_form("crt_demodulate", device, [&](HostCopies& c) {
+        const float *d_color = c.in(color, n), *d_albedo = c.in(albedo, n), *d_emission = c.in(emission, n), *d_variance = c.in(variance, n);
+        return demodulate_impl(device, prm, d_color, d_albedo, d_emission, d_variance, c.out(out_irradiance, n), c.out(out_variance, n), nullptr, info);
+    });
 }
 
 int crt_modulate_device(int device, const crt_modulate_params* prm, const void* d_irradiance, const void* d_albedo, const void* d_emission,
@@ -157,24 +113,11 @@ int crt_modulate(int device, const crt_modulate_params* prm, const float* irradi
 {
     const int rc0 = remodulate_check("crt_modulate", prm, irradiance, albedo, out_mean, out_rgb);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_modulate: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t n = (uint64_t)prm->width * prm->height * 3u;
-        DevBuf<float> d_irr, d_albedo, d_emission, d_mean;
-        DevBuf<uint8_t> d_rgb;
-        d_irr.upload(irradiance, n); d_albedo.upload(albedo, n); d_emission.upload(emission, n);
-        if (out_mean) d_mean.alloc(n);
-        if (out_rgb) d_rgb.alloc(n);
-        const int rc = modulate_impl(device, prm, d_irr.p, d_albedo.p, d_emission.p, d_mean.p, d_rgb.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        d_mean.download(out_mean, n);
-        d_rgb.download(out_rgb, n);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+    const uint64_t n = (uint64_t)prm->width * prm->height * 3u;
+    return host_form("crt_modulate", device, [&](HostCopies& c) {
+        const float *d_irradiance = c.in(irradiance, n), *d_albedo = c.in(albedo, n), *d_emission = c.in(emission, n);
+        return modulate_impl(device, prm, d_irradiance, d_albedo, d_emission, c.out(out_mean, n), c.out(out_rgb, n), nullptr, info);
+    });
 }
 
 } // extern "C"

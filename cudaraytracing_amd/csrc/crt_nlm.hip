@@ -9,7 +9,7 @@
 //                 row sum once, then per pixel the column of row sums, the guide terms and the weight; sums in registers across offsets.
 // CRT_NLM_FORM=direct|shared (read per call; tests and tools/denoise_probe.py) selects the form; unset: the faster one at 800x600
 // (docs/experiments.md, "The non-local-means filter").
-#include "crt_internal.h"
+#include "crt_filter_host.h"
 #include "crt_nlm.h"
 
 #include <cmath>
@@ -70,9 +70,6 @@ using namespace crtk;
 
 namespace {
 
-const uint32_t kMaxSide = 1u << 24;
-bool sigma_ok(float s) { return s > 0.0f; } // (false for NaN)
-
 uint64_t scratch_bytes_of(uint32_t width, uint32_t height) { return (uint64_t)width * height * 3u * sizeof(float4); }
 
 // 0: the default form, 1: direct, 2: shared, -1: a value that is neither
@@ -92,7 +89,7 @@ int nlm_check(const char* who, const crt_nlm_params* prm, const crt_denoise_var_
     if (!prm || !in) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!in->color) return fail(CRT_ERR_INVALID_ARG, w + ": null colour buffer");
     if (!in->variance) return fail(CRT_ERR_INVALID_ARG, w + ": null variance buffer");
-    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (const int rc = size_positive(w, prm->width, prm->height)) return rc;
     if (prm->radius < 1 || prm->radius > (uint32_t)kNlmMaxRadius) return fail(CRT_ERR_INVALID_ARG, w + ": radius must be 1 .. 8");
     if (prm->patch > (uint32_t)kNlmMaxPatch) return fail(CRT_ERR_INVALID_ARG, w + ": patch must be 0 .. 3");
     if (!(prm->k > 0.0f) || !std::isfinite(prm->k)) return fail(CRT_ERR_INVALID_ARG, w + ": k must be > 0 and finite");
@@ -100,34 +97,20 @@ int nlm_check(const char* who, const crt_nlm_params* prm, const crt_denoise_var_
     if (!sigma_ok(prm->sigma_normal) || !sigma_ok(prm->sigma_albedo) || !sigma_ok(prm->sigma_depth))
         return fail(CRT_ERR_INVALID_ARG, w + ": every sigma must be > 0 (+inf switches a term off)");
     if (!out_mean && !out_rgb) return fail(CRT_ERR_INVALID_ARG, w + ": no output buffer");
-    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
-    if ((uint64_t)((prm->width + kNlmTileW - 1) / kNlmTileW) * ((prm->height + 3) / 4) > 0x7fffffffull)
-        return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
-    return CRT_OK;
+    return size_supported(w, prm->width, prm->height, kNlmTileW, 4); // (the narrower tile with the lower one: no fewer blocks than either form launches)
 }
 
 int nlm_impl(const char* who, int device, const crt_nlm_params* prm, const crt_denoise_var_inputs* in, void* d_out_mean, void* d_out_rgb, float* d_out_var,
              void* d_scratch, uint64_t scratch_bytes, hipStream_t st, crt_denoise_info* info)
 {
     const std::string w(who);
-    const int rc = nlm_check(who, prm, in, d_out_mean, d_out_rgb);
+    int rc = nlm_check(who, prm, in, d_out_mean, d_out_rgb);
+    if (rc == CRT_OK) rc = scratch_ok(w, d_scratch, scratch_bytes, scratch_bytes_of(prm->width, prm->height), "crt_denoise_nlm_scratch_bytes");
     if (rc != CRT_OK) return rc;
-    if (!d_scratch) return fail(CRT_ERR_INVALID_ARG, w + ": null scratch buffer");
-    if (scratch_bytes < scratch_bytes_of(prm->width, prm->height))
-        return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer too small (crt_denoise_nlm_scratch_bytes)");
-    if ((uintptr_t)d_scratch % sizeof(float4) != 0) return fail(CRT_ERR_INVALID_ARG, w + ": scratch buffer not 16-byte aligned");
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, w + ": device index out of range");
     const int form = form_of_environment();
-    if (form < 0) return fail(CRT_ERR_INVALID_ARG, w + ": CRT_NLM_FORM must be direct or shared");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int status = CRT_OK;
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        if (info) {
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
+    if (form < 0 && device >= 0) // (a bad device index is reported first: timed_launch's test)
+        return fail(CRT_ERR_INVALID_ARG, w + ": CRT_NLM_FORM must be direct or shared");
+    rc = timed_launch(w, device, st, info, [&] {
         const uint64_t npix = (uint64_t)prm->width * prm->height;
         float4* plane = (float4*)d_scratch;
         NlmPack K;
@@ -154,20 +137,9 @@ int nlm_impl(const char* who, int device, const crt_nlm_params* prm, const crt_d
             hipLaunchKernelGGL(k_nlm_shared, dim3(P.tiles_x * ((prm->height + kNlmTileH - 1) / kNlmTileH)), dim3(kNlmThreads),
                                nlm_lds_bytes(P.radius, P.patch), st, P);
         }
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->passes = 1;
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-    } catch (const HipFail& f) {
-        status = fail_hip(f);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return status;
+    });
+    if (rc == CRT_OK && info) info->passes = 1;
+    return rc;
 }
 
 } // namespace
@@ -203,33 +175,19 @@ int crt_denoise_nlm(int device, const crt_nlm_params* prm, const crt_denoise_var
 {
     const int rc0 = nlm_check("crt_denoise_nlm", prm, host_in, out_mean, out_rgb);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_denoise_nlm: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> d_color, d_var, d_albedo, d_normal, d_depth, d_mean, d_ovar;
-        DevBuf<uint8_t> d_rgb;
-        DevBuf<float4> d_scratch;
+    const uint64_t npix = (uint64_t)prm->width * prm->height;
+    return host_form("crt_denoise_nlm", device, [&](HostCopies& c) {
         crt_denoise_var_inputs d{};
-        d.color = d_color.upload(host_in->color, npix * 3);
-        d.variance = d_var.upload(host_in->variance, npix * 3);
-        d.albedo = d_albedo.upload(host_in->albedo, npix * 3);
-        d.normal = d_normal.upload(host_in->normal, npix * 3);
-        d.depth = d_depth.upload(host_in->depth, npix);
-        if (out_mean) d_mean.alloc(npix * 3);
-        if (out_rgb) d_rgb.alloc(npix * 3);
-        if (out_variance) d_ovar.alloc(npix);
-        d_scratch.alloc(npix * 3);
-        const int rc = nlm_impl("crt_denoise_nlm_device", device, prm, &d, d_mean.p, d_rgb.p, d_ovar.p, d_scratch.p, npix * 3 * sizeof(float4), nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        d_mean.download(out_mean, npix * 3);
-        d_rgb.download(out_rgb, npix * 3);
-        d_ovar.download(out_variance, npix);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+        d.color = c.in(host_in->color, npix * 3);
+        d.variance = c.in(host_in->variance, npix * 3);
+        d.albedo = c.in(host_in->albedo, npix * 3);
+        d.normal = c.in(host_in->normal, npix * 3);
+        d.depth = c.in(host_in->depth, npix);
+        float* d_mean = c.out(out_mean, npix * 3);
+        uint8_t* d_rgb = c.out(out_rgb, npix * 3);
+        float* d_ovar = c.out(out_variance, npix);
+        return nlm_impl("crt_denoise_nlm_device", device, prm, &d, d_mean, d_rgb, d_ovar, c.scratch<float4>(npix * 3), npix * 3 * sizeof(float4), nullptr, info);
+    });
 }
 
 } // extern "C"

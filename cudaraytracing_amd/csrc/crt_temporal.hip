@@ -16,7 +16,7 @@
 // colour: their taps ride on the predicates and the weight b of the colour's taps (24 B more per tap that counts), their blend on n, a
 // and k, and 24 B more are stored per pixel.  <false, false> and <true, false> are the kernels of the older entry points, instruction
 // for instruction what they were before the third parameter (the new fields of TpParams stand at its end).
-#include "crt_internal.h"
+#include "crt_filter_host.h"
 
 #include <cstring>
 #include <string>
@@ -211,7 +211,6 @@ using namespace crtk;
 
 namespace {
 
-const uint32_t kMaxSide = 1u << 24;
 const uint32_t CLAMP_DEFAULT_RADIUS = 1;   // crt_temporal_clamp_defaults: chosen by the sweep of docs/experiments.md
 const float CLAMP_DEFAULT_GAMMA = 1.0f;
 bool tolerance_ok(float t) { return t > 0.0f; } // (false for NaN)
@@ -229,7 +228,7 @@ int temporal_check(const char* who, const crt_temporal_params* prm, const crt_te
     if (!prm || !cur) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!cur->color || !cur->depth) return fail(CRT_ERR_INVALID_ARG, w + ": the current frame needs colour and depth");
     if (!out_color || !out_history) return fail(CRT_ERR_INVALID_ARG, w + ": out_color and out_history are required");
-    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (const int rc = size_positive(w, prm->width, prm->height)) return rc;
     if (!tolerance_ok(prm->depth_tolerance) || !tolerance_ok(prm->normal_tolerance))
         return fail(CRT_ERR_INVALID_ARG, w + ": every tolerance must be > 0 (+inf switches a test off)");
     if (!(prm->alpha_min > 0.0f && prm->alpha_min <= 1.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": alpha_min must be in (0, 1]");
@@ -251,9 +250,7 @@ int temporal_check(const char* who, const crt_temporal_params* prm, const crt_te
         if (clamp->radius < 1 || clamp->radius > 3) return fail(CRT_ERR_INVALID_ARG, w + ": the clamp's radius must be 1 .. 3");
         if (!(clamp->gamma >= 0.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": the clamp's gamma must be >= 0 (+inf never clamps)"); // (false for NaN)
     }
-    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
-    if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
-    return CRT_OK;
+    return size_supported(w, prm->width, prm->height, 64, 4);
 }
 
 void set_camera(const crt_camera& cam, float* eye, float* iv, float& scale)
@@ -272,126 +269,41 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
 {
     const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, mom);
     if (rc != CRT_OK) return rc;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int status = CRT_OK;
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        DevBuf<unsigned long long> d_count;
-        TpParams P;
-        std::memset(&P, 0, sizeof(P));
-        P.width = prm->width; P.height = prm->height;
-        P.tiles_x = (prm->width + 63) / 64;
-        set_camera(prm->cur, P.eye, P.iv, P.scale);
-        set_camera(prm->prev, P.peye, P.piv, P.pscale);
-        P.ar = (float)prm->width / (float)prm->height;
-        P.depth_tol = prm->depth_tolerance;
-        P.normal_tol2 = prm->normal_tolerance * prm->normal_tolerance;
-        P.alpha_min = prm->alpha_min;
-        P.color = cur->color; P.variance = cur->variance; P.depth = cur->depth;
-        if (prev) {
-            P.normal = cur->normal; P.id = cur->id; // (without a history nothing reads the guides)
-            P.pcolor = prev->color; P.pvariance = prev->variance; P.phistory = prev->history; P.pdepth = prev->depth;
-            P.pnormal = prev->normal; P.pid = prev->id;
-        }
-        P.out_mean = (float*)d_out_color; P.out_rgb = (uint8_t*)d_out_rgb;
-        P.out_variance = (float*)d_out_variance; P.out_history = (float*)d_out_history;
-        if (info) {
-            d_count.alloc(2);
-            HIP_CHECK(hipMemsetAsync(d_count.p, 0, 2 * sizeof(unsigned long long), st));
-            P.count = d_count.p;
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
+    TpParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = prm->width; P.height = prm->height;
+    P.tiles_x = (prm->width + 63) / 64;
+    set_camera(prm->cur, P.eye, P.iv, P.scale);
+    set_camera(prm->prev, P.peye, P.piv, P.pscale);
+    P.ar = (float)prm->width / (float)prm->height;
+    P.depth_tol = prm->depth_tolerance;
+    P.normal_tol2 = prm->normal_tolerance * prm->normal_tolerance;
+    P.alpha_min = prm->alpha_min;
+    P.color = cur->color; P.variance = cur->variance; P.depth = cur->depth;
+    if (prev) {
+        P.normal = cur->normal; P.id = cur->id; // (without a history nothing reads the guides)
+        P.pcolor = prev->color; P.pvariance = prev->variance; P.phistory = prev->history; P.pdepth = prev->depth;
+        P.pnormal = prev->normal; P.pid = prev->id;
+    }
+    P.out_mean = (float*)d_out_color; P.out_rgb = (uint8_t*)d_out_rgb;
+    P.out_variance = (float*)d_out_variance; P.out_history = (float*)d_out_history;
+    if (clamp) { P.radius = (int)clamp->radius; P.gamma = clamp->gamma; }
+    if (mom) {
+        if (mom->prev) { P.pm1 = mom->prev->m1; P.pm2 = mom->prev->m2; }
+        P.out_m1 = (float*)mom->out_m1; P.out_m2 = (float*)mom->out_m2;
+    }
+    unsigned long long n[2] = {0, 0};
+    const int status = timed_launch(who, device, st, info, n, 2, [&](unsigned long long* d_count) {
+        P.count = d_count;
         const dim3 grid(P.tiles_x * ((prm->height + 3) / 4));
-        if (clamp) { P.radius = (int)clamp->radius; P.gamma = clamp->gamma; }
         if (mom) {
-            if (mom->prev) { P.pm1 = mom->prev->m1; P.pm2 = mom->prev->m2; }
-            P.out_m1 = (float*)mom->out_m1; P.out_m2 = (float*)mom->out_m2;
             if (clamp) hipLaunchKernelGGL((k_temporal<true, true>), grid, dim3(256), 0, st, P);
             else hipLaunchKernelGGL((k_temporal<false, true>), grid, dim3(256), 0, st, P);
         } else if (clamp) hipLaunchKernelGGL((k_temporal<true, false>), grid, dim3(256), 0, st, P);
         else hipLaunchKernelGGL((k_temporal<false, false>), grid, dim3(256), 0, st, P);
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            unsigned long long n[2] = {0, 0};
-            HIP_CHECK(hipMemcpyAsync(n, d_count.p, sizeof(n), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            info->reprojected = n[0]; info->clamped = n[1];
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-    } catch (const HipFail& f) {
-        status = fail_hip(f);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    });
+    if (status == CRT_OK && info) { info->reprojected = n[0]; info->clamped = n[1]; }
     return status;
-}
-
-// The host-buffer form: the argument checks, device copies of the inputs, the device form, then the copies back.
-int temporal_host(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                  const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, TemporalCounts* info,
-                  const MomentArgs* mom = nullptr)
-{
-    const int rc0 = temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history, mom);
-    if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> c_color, c_var, c_depth, c_normal, p_color, p_var, p_hist, p_depth, p_normal, o_color, o_var, o_hist;
-        DevBuf<float> p_m1, p_m2, o_m1, o_m2;
-        crt_temporal_moment_planes dm{};
-        MomentArgs dmom{};
-        DevBuf<int32_t> c_id, p_id;
-        DevBuf<uint8_t> o_rgb;
-        crt_temporal_frame dc{};
-        crt_temporal_history dp{};
-        dc.color = c_color.upload(cur->color, npix * 3);
-        dc.variance = c_var.upload(cur->variance, npix * 3);
-        dc.depth = c_depth.upload(cur->depth, npix);
-        dc.normal = c_normal.upload(cur->normal, npix * 3);
-        dc.id = c_id.upload(cur->id, npix);
-        if (prev) {
-            dp.color = p_color.upload(prev->color, npix * 3);
-            dp.variance = p_var.upload(prev->variance, npix * 3);
-            dp.history = p_hist.upload(prev->history, npix);
-            dp.depth = p_depth.upload(prev->depth, npix);
-            dp.normal = p_normal.upload(prev->normal, npix * 3);
-            dp.id = p_id.upload(prev->id, npix);
-        }
-        o_color.alloc(npix * 3);
-        o_hist.alloc(npix);
-        if (out_variance) o_var.alloc(npix * 3);
-        if (out_rgb) o_rgb.alloc(npix * 3);
-        if (mom) {
-            if (mom->prev) {
-                dm.m1 = p_m1.upload(mom->prev->m1, npix * 3);
-                dm.m2 = p_m2.upload(mom->prev->m2, npix * 3);
-                dmom.prev = &dm;
-            }
-            o_m1.alloc(npix * 3);
-            o_m2.alloc(npix * 3);
-            dmom.out_m1 = o_m1.p; dmom.out_m2 = o_m2.p;
-        }
-        const int rc = temporal_impl(who, device, prm, clamp, &dc, prev ? &dp : nullptr, o_color.p, o_var.p, o_hist.p, o_rgb.p, nullptr, info,
-                                     mom ? &dmom : nullptr);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        if (mom) {
-            o_m1.download((float*)mom->out_m1, npix * 3);
-            o_m2.download((float*)mom->out_m2, npix * 3);
-        }
-        o_color.download(out_color, npix * 3);
-        o_var.download(out_variance, npix * 3);
-        o_hist.download(out_history, npix);
-        o_rgb.download(out_rgb, npix * 3);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
 }
 
 // the two info structs, filled from the counts of a call that succeeded
@@ -418,13 +330,48 @@ int temporal_device_form(const char* who, int device, const crt_temporal_params*
     return rc;
 }
 
+// The host-buffer form: the argument checks, device copies of the inputs, the device form, then the copies back.
 template <class Info>
 int temporal_host_form(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
                        const crt_temporal_history* prev, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, Info* info,
                        const MomentArgs* mom = nullptr)
 {
+    const int rc0 = temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history, mom);
+    if (rc0 != CRT_OK) return rc0;
+    const uint64_t npix = (uint64_t)prm->width * prm->height;
     TemporalCounts n{};
-    const int rc = temporal_host(who, device, prm, clamp, cur, prev, out_color, out_variance, out_history, out_rgb, info ? &n : nullptr, mom);
+    const int rc = host_form(who, device, [&](HostCopies& c) {
+        crt_temporal_frame dc{};
+        crt_temporal_history dp{};
+        crt_temporal_moment_planes dm{};
+        MomentArgs dmom{};
+        dc.color = c.in(cur->color, npix * 3);
+        dc.variance = c.in(cur->variance, npix * 3);
+        dc.depth = c.in(cur->depth, npix);
+        dc.normal = c.in(cur->normal, npix * 3);
+        dc.id = c.in(cur->id, npix);
+        if (prev) {
+            dp.color = c.in(prev->color, npix * 3);
+            dp.variance = c.in(prev->variance, npix * 3);
+            dp.history = c.in(prev->history, npix);
+            dp.depth = c.in(prev->depth, npix);
+            dp.normal = c.in(prev->normal, npix * 3);
+            dp.id = c.in(prev->id, npix);
+        }
+        float *o_color = c.out(out_color, npix * 3), *o_hist = c.out(out_history, npix), *o_var = c.out(out_variance, npix * 3);
+        uint8_t* o_rgb = c.out(out_rgb, npix * 3);
+        if (mom) {
+            if (mom->prev) {
+                dm.m1 = c.in(mom->prev->m1, npix * 3);
+                dm.m2 = c.in(mom->prev->m2, npix * 3);
+                dmom.prev = &dm;
+            }
+            dmom.out_m1 = c.out((float*)mom->out_m1, npix * 3);
+            dmom.out_m2 = c.out((float*)mom->out_m2, npix * 3);
+        }
+        return temporal_impl(who, device, prm, clamp, &dc, prev ? &dp : nullptr, o_color, o_var, o_hist, o_rgb, nullptr, info ? &n : nullptr,
+                             mom ? &dmom : nullptr);
+    });
     if (rc == CRT_OK && info) fill_info(info, n);
     return rc;
 }

@@ -8,7 +8,7 @@
 // normal and depth terms, and boosts it by min_history / history; its taps (40 B each) are read straight from the caller's buffers.  One
 // ballot per wave decides whether the wave enters the tap loop at all -- after a few frames the short histories lie along disocclusion
 // edges and most waves have none -- and the same mask is the wave's share of the count of such pixels (one popcount, one atomic).
-#include "crt_internal.h"
+#include "crt_filter_host.h"
 
 #include <cstring>
 #include <string>
@@ -101,9 +101,6 @@ using namespace crtk;
 
 namespace {
 
-const uint32_t kMaxSide = 1u << 24;
-bool sigma_ok(float s) { return s > 0.0f; } // (false for NaN)
-
 // Argument checks of both forms, before any device call
 int estimate_check(const char* who, const crt_variance_estimate_params* prm, const crt_variance_estimate_inputs* in, const void* out_variance)
 {
@@ -111,15 +108,13 @@ int estimate_check(const char* who, const crt_variance_estimate_params* prm, con
     if (!prm || !in) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!in->m1 || !in->m2 || !in->history) return fail(CRT_ERR_INVALID_ARG, w + ": m1, m2 and history are required");
     if (!out_variance) return fail(CRT_ERR_INVALID_ARG, w + ": null output buffer");
-    if (prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, w + ": width and height must be positive");
+    if (const int rc = size_positive(w, prm->width, prm->height)) return rc;
     if (prm->min_history < 1) return fail(CRT_ERR_INVALID_ARG, w + ": min_history must be >= 1");
     if (prm->radius < 1 || prm->radius > 3) return fail(CRT_ERR_INVALID_ARG, w + ": radius must be 1 .. 3");
     if (!sigma_ok(prm->sigma_normal) || !sigma_ok(prm->sigma_depth))
         return fail(CRT_ERR_INVALID_ARG, w + ": every sigma must be > 0 (+inf switches a term off)");
     if (!(prm->history_cap >= 1.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": history_cap must be >= 1 (+inf: no cap)"); // (false for NaN)
-    if (prm->width > kMaxSide || prm->height > kMaxSide) return fail(CRT_ERR_UNSUPPORTED, w + ": a side longer than 2^24 pixels");
-    if ((uint64_t)((prm->width + 63) / 64) * ((prm->height + 3) / 4) > 0x7fffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 thread blocks");
-    return CRT_OK;
+    return size_supported(w, prm->width, prm->height, 64, 4);
 }
 
 int estimate_impl(const char* who, int device, const crt_variance_estimate_params* prm, const crt_variance_estimate_inputs* in, void* d_out,
@@ -127,48 +122,24 @@ int estimate_impl(const char* who, int device, const crt_variance_estimate_param
 {
     const int rc = estimate_check(who, prm, in, d_out);
     if (rc != CRT_OK) return rc;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, std::string(who) + ": device index out of range");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int status = CRT_OK;
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        DevBuf<unsigned long long> d_count;
-        VeParams P;
-        std::memset(&P, 0, sizeof(P));
-        P.width = prm->width; P.height = prm->height;
-        P.tiles_x = (prm->width + 63) / 64;
-        P.radius = (int)prm->radius;
-        P.min_history = (float)prm->min_history;
-        P.sig2_n = prm->sigma_normal * prm->sigma_normal;
-        P.sigma_d = prm->sigma_depth;
-        P.of_mean = prm->of_mean;
-        P.history_cap = prm->history_cap;
-        P.m1 = in->m1; P.m2 = in->m2; P.history = in->history; P.normal = in->normal; P.depth = in->depth;
-        P.out = (float*)d_out;
-        if (info) {
-            d_count.alloc(1);
-            HIP_CHECK(hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), st));
-            P.count = d_count.p;
-            HIP_CHECK(hipEventCreate(&e0));
-            HIP_CHECK(hipEventCreate(&e1));
-            HIP_CHECK(hipEventRecord(e0, st));
-        }
+    VeParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.width = prm->width; P.height = prm->height;
+    P.tiles_x = (prm->width + 63) / 64;
+    P.radius = (int)prm->radius;
+    P.min_history = (float)prm->min_history;
+    P.sig2_n = prm->sigma_normal * prm->sigma_normal;
+    P.sigma_d = prm->sigma_depth;
+    P.of_mean = prm->of_mean;
+    P.history_cap = prm->history_cap;
+    P.m1 = in->m1; P.m2 = in->m2; P.history = in->history; P.normal = in->normal; P.depth = in->depth;
+    P.out = (float*)d_out;
+    unsigned long long spatial = 0;
+    const int status = timed_launch(who, device, st, info, &spatial, 1, [&](unsigned long long* d_count) {
+        P.count = d_count;
         hipLaunchKernelGGL(k_variance_estimate, dim3(P.tiles_x * ((prm->height + 3) / 4)), dim3(256), 0, st, P);
-        HIP_CHECK(hipGetLastError());
-        if (info) {
-            HIP_CHECK(hipEventRecord(e1, st));
-            unsigned long long n = 0;
-            HIP_CHECK(hipMemcpyAsync(&n, d_count.p, sizeof(n), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            std::memset(info, 0, sizeof(*info));
-            info->spatial = n;
-            HIP_CHECK(hipEventElapsedTime(&info->total_ms, e0, e1));
-        }
-    } catch (const HipFail& f) {
-        status = fail_hip(f);
-    }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
+    });
+    if (status == CRT_OK && info) info->spatial = spatial;
     return status;
 }
 
@@ -198,26 +169,16 @@ int crt_variance_estimate(int device, const crt_variance_estimate_params* prm, c
 {
     const int rc0 = estimate_check("crt_variance_estimate", prm, host_in, out_variance);
     if (rc0 != CRT_OK) return rc0;
-    if (device < 0) return fail(CRT_ERR_INVALID_ARG, "crt_variance_estimate: device index out of range");
-    try {
-        HIP_CHECK(hipSetDevice(device));
-        const uint64_t npix = (uint64_t)prm->width * prm->height;
-        DevBuf<float> d_m1, d_m2, d_hist, d_normal, d_depth, d_out;
+    const uint64_t npix = (uint64_t)prm->width * prm->height;
+    return host_form("crt_variance_estimate", device, [&](HostCopies& c) {
         crt_variance_estimate_inputs d{};
-        d.m1 = d_m1.upload(host_in->m1, npix * 3);
-        d.m2 = d_m2.upload(host_in->m2, npix * 3);
-        d.history = d_hist.upload(host_in->history, npix);
-        d.normal = d_normal.upload(host_in->normal, npix * 3);
-        d.depth = d_depth.upload(host_in->depth, npix);
-        d_out.alloc(npix * 3);
-        const int rc = estimate_impl("crt_variance_estimate", device, prm, &d, d_out.p, nullptr, info);
-        if (rc != CRT_OK) return rc;
-        HIP_CHECK(hipDeviceSynchronize());
-        d_out.download(out_variance, npix * 3);
-        return CRT_OK;
-    } catch (const HipFail& f) {
-        return fail_hip(f);
-    }
+        d.m1 = c.in(host_in->m1, npix * 3);
+        d.m2 = c.in(host_in->m2, npix * 3);
+        d.history = c.in(host_in->history, npix);
+        d.normal = c.in(host_in->normal, npix * 3);
+        d.depth = c.in(host_in->depth, npix);
+        return estimate_impl("crt_variance_estimate", device, prm, &d, c.out(out_variance, npix * 3), nullptr, info);
+    });
 }
 
 } // extern "C"
