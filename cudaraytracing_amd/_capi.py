@@ -209,6 +209,23 @@ class VarianceEstimateInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("spatial", C.c_uint64)]
 
 
+class UpsampleParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("low_width", C.c_uint32), ("low_height", C.c_uint32), ("radius", C.c_uint32),
+                ("min_weight", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
+
+
+class UpsampleLow(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("variance", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class UpsampleGuides(C.Structure):
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class UpsampleInfo(InfoStruct):
+    _fields_ = [("total_ms", C.c_float), ("fallback_pixels", C.c_uint64)]
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("step_samples", C.c_uint32), ("threshold", C.c_float), ("mean_floor", C.c_float)]
 
@@ -274,7 +291,7 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
            "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device",
            "crt_render_aov_shading", "crt_render_aov_shading_device", "crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate",
-           "crt_modulate_device"]
+           "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device"]
 
 _lib = None
 
@@ -377,6 +394,11 @@ def lib():
                                         C.POINTER(VarianceEstimateInfo)]
     L.crt_variance_estimate_device.argtypes = [C.c_int, C.POINTER(VarianceEstimateParams), C.POINTER(VarianceEstimateInputs), C.c_void_p, C.c_void_p,
                                                C.POINTER(VarianceEstimateInfo)]
+    L.crt_upsample_defaults.argtypes = [C.POINTER(UpsampleParams)]
+    L.crt_upsample.argtypes = [C.c_int, C.POINTER(UpsampleParams), C.POINTER(UpsampleLow), C.POINTER(UpsampleGuides), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.POINTER(UpsampleInfo)]
+    L.crt_upsample_device.argtypes = [C.c_int, C.POINTER(UpsampleParams), C.POINTER(UpsampleLow), C.POINTER(UpsampleGuides), C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.POINTER(UpsampleInfo)]
     L.crt_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.crt_multi_destroy.argtypes = [C.c_void_p]
     L.crt_multi_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats),

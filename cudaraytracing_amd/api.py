@@ -185,6 +185,9 @@ class Render:
         self.map_info = None
         self.temporal_info = None
         self.variance_estimate_info = None
+        self.low_frame = None            # run_view_upsampled: rgb, mean, variance, albedo, normal, depth (and the shading AOVs) of the low-resolution frame
+        self.upsampled_variance = None
+        self.upsample_info = None
         self.temporal_history_buffer = None
         self._temporal = None        # run_view_temporal: the history (temporal()'s `prev` dict), its camera and size
         self._temporal_frames = 0    # frames since the last reset_temporal()
@@ -597,6 +600,53 @@ class Render:
             rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
         return rgb, mean
 
+    def run_view_upsampled(self, eye_pos, inv_view_mat, fovY, factor=2, width=None, height=None, guide_spp=None, demodulate=True, filter_low=False,
+                           albedo_floor=None, **upsample_settings):
+        """Resolution scaling: the frame's paths at (W / factor, H / factor), its first hits at (W, H), and crt_upsample in between
+        (contract: include/crt.h).  Renders the low-resolution frame with want_variance, runs the shading AOV pass with albedo, normal and
+        depth at the low size and again at the full size -- there with guide_spp samples per pixel (None: self.spp; self.spp is what it was
+        afterwards) --, upsamples the low frame along the two sets of guides and returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32).
+        demodulate (the default): what is upsampled is irradiance -- the low frame and its variance through demodulate(albedo_floor) with
+        the LOW shading AOVs, the result through modulate() with the FULL-resolution ones, so texture and the edges of emitters come from
+        the full-resolution pass; False: the radiance itself is upsampled.  filter_low: denoise_var (its defaults) on the low image first;
+        the variance that is upsampled is then still the unfiltered frame's and overstates what is left.  upsample_settings: radius,
+        min_weight, sigma_normal, sigma_albedo, sigma_depth of upsample().  factor is 2 .. 8 and must divide both sides (ValueError).
+        Kept: self.low_frame (rgb, mean, variance and the AOVs of the low frame), self.aov_buffers and self.shading_buffers (full
+        resolution), self.upsampled_variance (of what was upsampled: irradiance with demodulate), self.upsample_info."""
+        w, h = width or self.scene.width, height or self.scene.height
+        if factor != int(factor) or not 2 <= int(factor) <= 8:
+            raise ValueError("run_view_upsampled: factor must be an integer 2 .. 8, got %r" % (factor,))
+        factor = int(factor)
+        if w % factor or h % factor:
+            raise ValueError("run_view_upsampled: %d x %d is not divisible by the factor %d" % (w, h, factor))
+        self._handle("run_view_upsampled")
+        lw, lh = w // factor, h // factor
+        view, guides = (eye_pos, inv_view_mat, fovY), ("albedo", "normal", "depth")
+        low_rgb = self.run_view(*view, width=lw, height=lh, want_variance=True)
+        low = dict(self.run_view_aov_shading(*view, first=guides, width=lw, height=lh), rgb=low_rgb, mean=self.mean_buffer, variance=self.variance_buffer)
+        spp = self.spp
+        try:
+            if guide_spp is not None:
+                self.set_spp(guide_spp)
+            full = self.run_view_aov_shading(*view, first=guides, width=w, height=h)
+        finally:
+            self.spp = spp
+        self.low_frame = low
+        self.aov_buffers = {k: full[k] for k in guides}
+        self.shading_buffers = {k: full[k] for k in capi.AOV_SHADING_BUFFERS}
+        color, var = low["mean"], low["variance"]
+        if demodulate:
+            color, var = _demodulate(color, low["diffuse_albedo"], low["emission"], variance=var, albedo_floor=albedo_floor, device=self.device)
+        low_guides = {k: low[k] for k in guides}
+        if filter_low:
+            color = denoise_var(color, var, device=self.device, want_rgb=False, **low_guides)[1]
+        rgb, mean, self.upsampled_variance, self.upsample_info = upsample(dict(low_guides, color=color, variance=var), w, h, guides=self.aov_buffers,
+                                                                          device=self.device, want_rgb=not demodulate, return_info=True,
+                                                                          **upsample_settings)
+        if demodulate:
+            rgb, mean = _modulate(mean, full["diffuse_albedo"], full["emission"], albedo_floor=albedo_floor, device=self.device)
+        return rgb, mean
+
     def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, variance="samples",
                           demodulate=False, albedo_floor=None, **overrides):
         """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
@@ -821,6 +871,7 @@ _MULTI_REFUSALS = {
     "run_view_aov_specular_device": "the AOV pass is a single-device interface (crt_render_aov_specular_device)",
     "run_view_denoised": "the denoiser is a single-device interface (crt_denoise): gather the frame first",
     "run_view_temporal": "temporal accumulation is a single-device interface (crt_temporal): gather the frame first",
+    "run_view_upsampled": "upsampling is a single-device interface (crt_upsample): gather the frames first",
     "intersect": "crt_intersect is a single-device interface",
     "blocked": "crt_intersect is a single-device interface",
     "last_launch_ms": "crt_last_launch_ms is a single-device interface (per-rank kernel times: rank_stats)",
@@ -1143,6 +1194,87 @@ def modulate_device(width, height, irradiance_ptr, albedo_ptr, out_mean_ptr, out
 
 
 _demodulate, _modulate = demodulate, modulate  # (the Render methods have a `demodulate` argument of their own)
+
+
+_UPSAMPLE_SETTINGS = ("radius", "min_weight", "sigma_normal", "sigma_albedo", "sigma_depth")
+
+
+def upsample_defaults():
+    """crt_upsample_defaults as a dict: radius, min_weight and the three guide sigmas."""
+    return _settings(_defaults(capi.UpsampleParams, "crt_upsample_defaults"), _UPSAMPLE_SETTINGS)
+
+
+def _upsample_params(who, width, height, low_width, low_height, settings):
+    unknown = set(settings) - set(_UPSAMPLE_SETTINGS)
+    if unknown:
+        raise ValueError("%s: unknown settings %r" % (who, sorted(unknown)))
+    r = settings.get("radius")
+    if r is not None and (int(r) != r or not 0 <= int(r) < 2 ** 32):
+        raise ValueError("%s: radius must be an integer 1 .. 4, got %r" % (who, r))
+    p = _defaults(capi.UpsampleParams, "crt_upsample_defaults", width, height, **settings)
+    p.low_width, p.low_height = int(low_width), int(low_height)
+    return p
+
+
+def upsample(low, width, height, guides=None, device=0, want_rgb=True, return_info=False, **settings):
+    """Guide-driven upsampling (crt_upsample, contract: include/crt.h) of a low-resolution image to width x height.  low: dict of the
+    (h, w, 3) float32 image `color` and optionally its `variance` (h, w, 3) and the low-resolution guides albedo, normal (h, w, 3) and
+    depth (h, w); guides: dict of the same guides at (height, width), or None for the plain tent interpolation.  A guide counts when it
+    is given at both sizes.  settings: radius, min_weight, sigma_normal, sigma_albedo, sigma_depth; None or absent takes
+    crt_upsample_defaults.  Returns (rgb, color), with a variance (rgb, color, variance): the RGB8 tone map (None without want_rgb), the
+    upsampled image and its variance; with return_info also the crt_upsample_info dict (total_ms, fallback_pixels)."""
+    for name, d, known in (("low", low, capi.UpsampleLow), ("guides", guides or {}, capi.UpsampleGuides)):
+        unknown = set(d) - {n for n, _ in known._fields_}
+        if unknown:
+            raise ValueError("upsample: unknown %s buffers %r" % (name, sorted(unknown)))
+    if low.get("color") is None:
+        raise ValueError("upsample needs the low-resolution image (low['color'])")
+    lo, hi = capi.UpsampleLow(), capi.UpsampleGuides()
+    keep = _image_inputs("upsample", "an (h, w, 3) low-resolution image", (("color", low["color"], 3), ("variance", low.get("variance"), 3),
+                                                                           ("albedo", low.get("albedo"), 3), ("normal", low.get("normal"), 3),
+                                                                           ("depth", low.get("depth"), 1)), lo)
+    lh, lw = keep[0].shape[:2]
+    width, height = int(width), int(height)
+    if guides is not None:
+        for name, channels in (("albedo", 3), ("normal", 3), ("depth", 1)):
+            a = guides.get(name)
+            if a is None:
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != ((height, width, 3) if channels == 3 else (height, width)):
+                raise ValueError("upsample: the %s guide has shape %r for a %d x %d output" % (name, a.shape, width, height))
+            keep.append(a)
+            setattr(hi, name, a.ctypes.data)
+    prm = _upsample_params("upsample", width, height, lw, lh, settings)
+    color = np.zeros((height, width, 3), dtype=np.float32)
+    var = np.zeros((height, width, 3), dtype=np.float32) if keep[1] is not None else None
+    rgb = np.zeros((height, width, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.UpsampleInfo()
+    capi.check(capi.lib().crt_upsample(device, C.byref(prm), C.byref(lo), C.byref(hi) if guides is not None else None, capi.ptr(color), capi.ptr(var),
+                                       capi.ptr(rgb), C.byref(info)), "crt_upsample")
+    out = (rgb, color) if var is None else (rgb, color, var)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def upsample_device(width, height, low_width, low_height, low_ptrs, out_color_ptr, out_variance_ptr=None, out_rgb_ptr=None, guide_ptrs=None, device=0,
+                    stream=None, want_info=True, **settings):
+    """Enqueues crt_upsample_device with everything in device memory: low_ptrs / guide_ptrs = {name: raw device pointer} with the names of
+    upsample()'s dicts (guide_ptrs None: no guides).  out_color_ptr or out_rgb_ptr may be None, not both.  With want_info the call
+    synchronizes the stream and returns the crt_upsample_info dict, else None."""
+    def fill(struct, ptrs):
+        for name, p in ptrs.items():
+            if name not in {n for n, _ in struct._fields_}:
+                raise ValueError("upsample_device: unknown buffer %r" % name)
+            setattr(struct, name, int(p) if p else None)
+        return struct
+    lo = fill(capi.UpsampleLow(), low_ptrs)
+    hi = fill(capi.UpsampleGuides(), guide_ptrs) if guide_ptrs is not None else None
+    prm = _upsample_params("upsample_device", width, height, low_width, low_height, settings)
+    info = capi.UpsampleInfo()
+    capi.check(capi.lib().crt_upsample_device(device, C.byref(prm), C.byref(lo), C.byref(hi) if hi is not None else None, _vp(out_color_ptr),
+                                              _vp(out_variance_ptr), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
+               "crt_upsample_device")
+    return info.as_dict() if want_info else None
 
 
 def _camera(eye_pos, inv_view_mat, fovY):

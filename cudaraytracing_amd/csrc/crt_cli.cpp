@@ -12,6 +12,12 @@
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
+//           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]
+// --upsample FACTOR[,RADIUS] --upsample-out PATH also renders the frame with resolution scaling (one device) and writes it as a PNG to PATH:
+// the paths at (W / FACTOR, H / FACTOR), the shading AOVs with albedo, normal and depth at that size and at (W, H) -- there with
+// --upsample-guide-spp samples per pixel (default: --spp) --, the low frame demodulated, upsampled along the two sets of guides
+// (crt_upsample, its defaults; RADIUS 1 .. 4) and modulated with the full-resolution buffers.  FACTOR is 2 .. 8 and must divide --width and
+// --height.  -o stays the plain frame at full size.  It runs last: --aov and --aov-shading write the buffers of the plain frame.
 // --aov-shading PREFIX writes the shading AOVs of the frame (crt_render_aov_shading, one device, the trace of --aov): PREFIX.emission.pfm
 // and PREFIX.diffuse_albedo.pfm (3 channels).  --demodulate makes --denoise and --temporal work on irradiance: the frame (and its
 // variance) goes through crt_demodulate with those two buffers before the filter or the blend and the result through crt_modulate, so
@@ -68,7 +74,8 @@ int main(int argc, char** argv)
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
-                             "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n", argv[0]);
+                             "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n"
+                             "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n", argv[0]);
         return 2;
     }
     try {
@@ -95,6 +102,11 @@ int main(int argc, char** argv)
         crt_temporal_clamp_defaults(&tclamp);
         float temporal_step[3] = {0.0f, 0.0f, 0.0f};
         std::string temporal_out;
+        unsigned upsample = 0, upsample_guide_spp = 0; // --upsample: the factor; 0 samples = the frame's
+        bool upsample_option = false;
+        crt_upsample_params up; // the operation's defaults with RADIUS
+        crt_upsample_defaults(&up);
+        std::string upsample_out;
         uint64_t seed = 0;
         int device = 0;
         bool reference = false, exact = false, fast = false, bounded = false;
@@ -149,6 +161,28 @@ int main(int argc, char** argv)
             }
             else if (a == "--aov-shading") { need(i, 1); aov_shading = argv[++i]; if (aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading needs a PREFIX"); }
             else if (a == "--demodulate") demodulate = true;
+            else if (a == "--upsample") {
+                need(i, 1);
+                const char* q = argv[++i];
+                char* end = nullptr;
+                const long f = std::strtol(q, &end, 10);
+                long r = 1;
+                bool good = end != q && (*end == 0 || *end == ',');
+                if (good && *end == ',') {
+                    q = end + 1;
+                    r = std::strtol(q, &end, 10);
+                    good = end != q && *end == 0;
+                }
+                if (!good || f < 2 || f > 8 || r < 1 || r > 4) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample needs FACTOR[,RADIUS] with FACTOR 2 .. 8 and RADIUS 1 .. 4");
+                upsample = (unsigned)f; up.radius = (uint32_t)r;
+            }
+            else if (a == "--upsample-out") { need(i, 1); upsample_out = argv[++i]; upsample_option = true; }
+            else if (a == "--upsample-guide-spp") {
+                need(i, 1);
+                const int n = std::atoi(argv[++i]);
+                if (n < 1) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample-guide-spp needs a positive count");
+                upsample_guide_spp = (unsigned)n; upsample_option = true;
+            }
             else if (a == "--denoise-specular") denoise_specular = true;
             else if (a == "--denoise") { need(i, 1); denoise = argv[++i]; }
             else if (a == "--denoise-variance") denoise_var = true;
@@ -261,6 +295,11 @@ int main(int argc, char** argv)
         if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
         if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
         if (multi && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates on one device (not with --gpus / --devices)");
+        if (multi && upsample) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample runs on one device (not with --gpus / --devices)");
+        if (upsample_option && !upsample) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample-out and --upsample-guide-spp need --upsample FACTOR");
+        if (upsample && upsample_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample needs --upsample-out PATH");
+        if (upsample && (task.width % upsample || task.height % upsample))
+            throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample: FACTOR must divide --width and --height");
         if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
         if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp and --temporal-variance need --temporal N");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
@@ -414,6 +453,13 @@ int main(int argc, char** argv)
                 render.save_denoised_buffer(temporal_out.c_str());
             } else render.save_temporal_buffer(temporal_out.c_str());
             std::printf("%s\n", temporal_out.c_str());
+        }
+        if (upsample) { // (last: it leaves the low frame's sums on the handle and its own AOV buffers)
+            render.run_view_upsampled(task.eye_pos, inv_view, fov_y, upsample, up, upsample_guide_spp);
+            const crt_upsample_info& ui = render.last_upsample_info();
+            std::printf("upsample: factor %u, radius %u, %llu fallback pixels, device %.3f ms\n", upsample, up.radius, (unsigned long long)ui.fallback_pixels, ui.total_ms);
+            render.save_upsampled_buffer(upsample_out.c_str());
+            std::printf("%s\n", upsample_out.c_str());
         }
         render.free();
         return 0;

@@ -982,6 +982,71 @@ void Render::run_denoise_temporal(const crt_denoise_params& prm)
     denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm, temporal_demodulated_);
 }
 
+void Render::run_view_upsampled(const float eye_pos[3], const float inv_view_mat[9], float fovY, unsigned factor, const crt_upsample_params& prm, unsigned guide_spp)
+{
+    const char* who = "Render::run_view_upsampled";
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": upsampling is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
+    const unsigned W = scene_->get_width(), H = scene_->get_height();
+    if (factor < 2 || factor > 8) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must be 2 .. 8");
+    if (W % factor || H % factor) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must divide width and height");
+    const unsigned lw = W / factor, lh = H / factor;
+    const size_t nl = (size_t)lw * lh, n = scene_->get_pixels();
+    auto check = [&](int rc, const char* step) { if (rc != CRT_OK) throw Error(rc, std::string(who) + ": " + step + " failed: " + crt_last_error()); };
+    // the low-resolution frame, its variance and its AOVs
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, (flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE)) | CRT_FLAG_VARIANCE, cam, p);
+    p.width = lw; p.height = lh;
+    std::vector<unsigned char> low_rgb(3 * nl, 0);
+    std::vector<float> low_mean(3 * nl, 0.0f), low_var(3 * nl, 0.0f), l_albedo(3 * nl, 0.0f), l_normal(3 * nl, 0.0f), l_depth(nl, 0.0f), l_emission(3 * nl, 0.0f),
+        l_diffuse(3 * nl, 0.0f);
+    crt_stats low_stats;
+    variance_buffer_.clear(); // (the handle's sums are the low frame's from here on)
+    check(crt_render(device_scene_, &cam, &p, low_rgb.data(), low_mean.data(), &low_stats), "the low-resolution frame");
+    check(crt_variance(device_scene_, low_var.data(), nullptr), "its variance");
+    p.flags = 0;
+    crt_aov_buffers la{};
+    la.albedo = l_albedo.data(); la.normal = l_normal.data(); la.depth = l_depth.data();
+    const crt_aov_shading_buffers ls{l_emission.data(), l_diffuse.data()};
+    crt_aov_info low_aov;
+    check(crt_render_aov_shading(device_scene_, &cam, &p, &la, &ls, &low_aov), "the low-resolution AOV pass");
+    // the full-resolution AOVs: run_aov with the shading buffers and guide_spp samples
+    const bool shading = aov_shading_;
+    const unsigned spp = spp_;
+    aov_shading_ = true;
+    if (guide_spp) spp_ = guide_spp;
+    try {
+        run_aov(eye_pos, inv_view_mat, fovY);
+    } catch (...) {
+        aov_shading_ = shading; spp_ = spp;
+        throw;
+    }
+    aov_shading_ = shading; spp_ = spp;
+    // irradiance at the low size, upsampled, radiance at the full size
+    crt_modulate_params m;
+    crt_modulate_defaults(&m);
+    m.width = lw; m.height = lh; m.albedo_floor = albedo_floor_;
+    std::vector<float> irr(3 * nl, 0.0f), ivar(3 * nl, 0.0f), up(3 * n, 0.0f), up_var(3 * n, 0.0f);
+    check(crt_demodulate(device_, &m, low_mean.data(), l_diffuse.data(), l_emission.data(), low_var.data(), irr.data(), ivar.data(), nullptr), "crt_demodulate");
+    crt_upsample_params u = prm;
+    u.width = W; u.height = H; u.low_width = lw; u.low_height = lh;
+    const crt_upsample_low low{irr.data(), ivar.data(), l_albedo.data(), l_normal.data(), l_depth.data()};
+    const crt_upsample_guides guides{albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
+    check(crt_upsample(device_, &u, &low, &guides, up.data(), up_var.data(), nullptr, &upsample_info_), "crt_upsample");
+    upsampled_buffer_.assign(3 * n, 0); upsampled_mean_buffer_.assign(3 * n, 0.0f);
+    m.width = W; m.height = H;
+    check(crt_modulate(device_, &m, up.data(), diffuse_albedo_buffer_.data(), emission_buffer_.data(), upsampled_mean_buffer_.data(), upsampled_buffer_.data(), nullptr),
+          "crt_modulate");
+}
+
+void Render::save_upsampled_buffer(const char* save_path) const
+{
+    if (upsampled_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_upsampled_buffer before run_view_upsampled");
+    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), upsampled_buffer_.data());
+    if (rc != CRT_OK) throw Error(rc, std::string("save_upsampled_buffer failed: ") + crt_last_error());
+}
+
 void Render::save_temporal_buffer(const char* save_path) const
 {
     if (temporal_rgb_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_temporal_buffer before run_temporal");

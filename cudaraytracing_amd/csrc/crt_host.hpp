@@ -285,6 +285,17 @@ public:
     // the accumulated frame filtered by crt_denoise_var with its accumulated variance and the guides of the last frame
     void run_denoise_temporal(const crt_denoise_params& prm);
     void save_temporal_buffer(const char* save_path) const;
+    // Resolution scaling (crt_upsample; prm: crt_upsample_defaults with overrides, its sizes are set here): the frame's paths at
+    // (W / factor, H / factor) with its variance, the shading AOVs with albedo, normal and depth at that size and at (W, H) -- there with
+    // guide_spp samples per pixel, 0: the frame's --, the low frame demodulated with the low buffers, upsampled along the two sets of
+    // guides and modulated with the full-resolution buffers.  factor is 2 .. 8 and divides both sides.  The AOV buffers are then those
+    // of a run_aov with set_aov_shading at (W, H); frame and mean buffers are untouched; the handle's sums are the low frame's.  One
+    // device only.
+    void run_view_upsampled(const float eye_pos[3], const float inv_view_mat[9], float fovY, unsigned factor, const crt_upsample_params& prm, unsigned guide_spp = 0);
+    const unsigned char* get_upsampled_buffer() const { return upsampled_buffer_.data(); }   // W x H x 3 RGB8
+    const float* get_upsampled_mean_buffer() const { return upsampled_mean_buffer_.data(); } // W x H x 3
+    const crt_upsample_info& last_upsample_info() const { return upsample_info_; }
+    void save_upsampled_buffer(const char* save_path) const;
     const unsigned char* get_denoised_buffer() const { return denoised_buffer_.data(); } // W x H x 3 RGB8
     const float* get_denoised_mean_buffer() const { return denoised_mean_buffer_.data(); } // W x H x 3
     const crt_denoise_info& last_denoise_info() const { return denoise_info_; }
@@ -357,6 +368,9 @@ private:
     crt_aov_info aov_info_{};
     std::vector<float> guide_albedo_buffer_, last_normal_buffer_, path_depth_buffer_, bounces_buffer_; // run_aov_specular
     crt_aov_info aov_specular_info_{};
+    std::vector<unsigned char> upsampled_buffer_;    // run_view_upsampled
+    std::vector<float> upsampled_mean_buffer_;
+    crt_upsample_info upsample_info_{};
 };
 
 } // namespace crt

@@ -837,6 +837,63 @@ int crt_variance_estimate(int device, const crt_variance_estimate_params* params
 int crt_variance_estimate_device(int device, const crt_variance_estimate_params* params, const crt_variance_estimate_inputs* dev_in,
                                  void* d_out_variance, void* hip_stream, crt_variance_estimate_info* info);
 
+/* Guide-driven upsampling: an image rendered at low_width x low_height brought to width x height along guides that exist at BOTH sizes
+ * (joint bilateral upsampling, Kopf et al. 2007).  Meant for irradiance (crt_demodulate of a low-resolution frame): the first-hit passes
+ * that produce albedo, normal and depth are cheap at full size, paths are not, and irradiance is smooth between geometric edges.  An
+ * image operation: no scene handle, no scratch; the taps come straight from the caller's buffers.  Row-major images; color, variance,
+ * albedo and normal 3 floats per pixel, depth 1.  `low` holds the low-resolution image and its guides, `guides` the output-resolution
+ * guides.  Per output pixel p = (x, y), all in fp32:
+ *   sx = (float)low_width / (float)width                      sy = (float)low_height / (float)height
+ *   u  = ((float)x + 0.5f) * sx - 0.5f                        v  = ((float)y + 0.5f) * sy - 0.5f
+ *   x0 = (int)floorf(u)                                       y0 = (int)floorf(v)
+ *        (low pixel X covers the part [X / sx, (X + 1) / sx) of the output's columns: the camera ray divides pixel + jitter by the width)
+ *   taps q = (tx, ty): ty = y0 - radius + 1 .. y0 + radius outer, tx = x0 - radius + 1 .. x0 + radius inner; a tap outside the low image
+ *   is skipped (nothing is added for it)
+ *     wx = 1.0f - fabsf(u - (float)tx) / (float)radius        wy = 1.0f - fabsf(v - (float)ty) / (float)radius        hw = wy * wx
+ *     e_n, e_a, e_d: exactly crt_denoise's lines, between guides(p) (output resolution) and low(q) (low resolution), p's value first
+ *     w    = hw * exp(-((e_n + e_a) + e_d))                                                     (exp: det_expf)
+ *     num  = num + color(q) * w        den  = den + w        vnum  = vnum + variance(q) * (w * w)           (per channel)
+ *     snum = snum + color(q) * hw      sden = sden + hw      svnum = svnum + variance(q) * (hw * hw)
+ *   guided       = den > min_weight * sden                                                      (false for NaN)
+ *   out_color    = guided ? num / den : snum / sden                                             (per channel)
+ *   out_variance = guided ? vnum / (den * den) : svnum / (sden * sden)
+ *   out_rgb      = the frame's tone map of out_color (the bits crt_render writes for that mean)
+ * Every sum starts at +0.0f and runs left to right as written; every * + - / is one IEEE fp32 operation (no FMA, no reciprocal
+ * multiply).  A pixel none of whose taps agrees with its guides (a feature thinner than a low-resolution pixel) falls back to the plain
+ * tent interpolation instead of amplifying rounding noise; info->fallback_pixels counts the pixels with `guided` false.
+ * A guide term is used only when both of its buffers are given (low->normal and guides->normal, ...); one of a pair without the other
+ * is CRT_ERR_INVALID_ARG; a term without buffers is +0.0f.  guides == NULL: all three terms are off, whatever `low` holds, and the result
+ * is the tent interpolation.  Non-finite inputs are not special-cased: the arithmetic defines the result.  With equal sizes, radius 1
+ * and no guides the output has the input's bits.  For 1 <= low_width <= width every pixel has a tap inside the low image.
+ * crt_upsample_defaults fills radius 1, min_weight 1/64 (the share at which crt_temporal gives up its taps), sigma_normal 0.5,
+ * sigma_albedo 0.1, sigma_depth 0.05 (the denoiser's; sizes 0).  Nobody has tuned them for this operation on anything but the frames of
+ * docs/experiments.md, "Guide-driven upsampling".
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null params, low or low->color; a size of 0; a low side longer than the
+ * output's; a radius outside 1 .. 4; a min_weight that is negative, infinite or NaN; a sigma that is not > 0; low->variance and
+ * out_variance not given together; neither out_color nor out_rgb.  A side longer than 2^24 pixels or more than 2^31 thread blocks of
+ * 64 x 4 pixels: CRT_ERR_UNSUPPORTED. */
+typedef struct {
+    uint32_t width, height;          /* the output */
+    uint32_t low_width, low_height;  /* the input: 1 <= low_width <= width, 1 <= low_height <= height */
+    uint32_t radius;                 /* 1 .. 4: (2 radius)^2 low-resolution taps per output pixel; 1 = the bilinear footprint */
+    float min_weight;                /* >= 0, finite: below this share of the spatial weight the guides are dropped for the pixel */
+    float sigma_normal, sigma_albedo, sigma_depth;  /* as crt_denoise: > 0, not NaN, +inf switches the term off */
+} crt_upsample_params;
+typedef struct { const float* color; const float* variance; const float* albedo; const float* normal; const float* depth; } crt_upsample_low;  /* low_width x low_height */
+typedef struct { const float* albedo; const float* normal; const float* depth; } crt_upsample_guides;                                         /* width x height */
+typedef struct {
+    float total_ms;            /* HIP-event time of the call's kernel on its stream */
+    uint64_t fallback_pixels;  /* pixels with `guided` false */
+} crt_upsample_info;
+int crt_upsample_defaults(crt_upsample_params* params);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_upsample(int device, const crt_upsample_params* params, const crt_upsample_low* host_low, const crt_upsample_guides* host_guides /* may be NULL */,
+                 float* out_color, float* out_variance /* with low->variance */, uint8_t* out_rgb, crt_upsample_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then counts the fallback pixels and synchronizes the stream to read them and the timer).  Outputs must not overlap inputs. */
+int crt_upsample_device(int device, const crt_upsample_params* params, const crt_upsample_low* dev_low, const crt_upsample_guides* dev_guides,
+                        void* d_out_color, void* d_out_variance, void* d_out_rgb, void* hip_stream, crt_upsample_info* info);
+
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
  * (config_CUDA, src/main.cu:92-105); a crt_multi holds one device replica of the scene per entry of
