@@ -18,6 +18,7 @@ FLAG_FORCE_EXACT = 4
 FLAG_TRACE_ALL = 8
 FLAG_BOUNDED_RADIANCE = 16
 FLAG_VARIANCE = 32
+FLAG_HALF_BUFFERS = 64   # implies FLAG_VARIANCE
 GATHER_AUTO, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 INTERSECT_RAW_DIRECTIONS, INTERSECT_FORCE_EXACT, INTERSECT_VISIBILITY = 0x100, 0x200, 0x400
 TILE = 8
@@ -226,6 +227,25 @@ class UpsampleInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("fallback_pixels", C.c_uint64)]
 
 
+SELECT_MAX_CANDIDATES = 4
+
+
+class FilterSelectParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("n_candidates", C.c_uint32), ("error_radius", C.c_uint32), ("blend_radius", C.c_uint32)]
+
+
+class FilterSelectInputs(C.Structure):
+    _fields_ = [("half_a", C.c_void_p), ("half_b", C.c_void_p), ("half_variance", C.c_void_p), ("filtered_a", C.c_void_p * SELECT_MAX_CANDIDATES),
+                ("filtered_b", C.c_void_p * SELECT_MAX_CANDIDATES)]
+
+
+class FilterSelectInfo(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("chosen", C.c_uint64 * SELECT_MAX_CANDIDATES)]
+
+    def as_dict(self):
+        return {"total_ms": float(self.total_ms), "chosen": [int(x) for x in self.chosen]}
+
+
 class AdaptiveParams(C.Structure):
     _fields_ = [("min_samples", C.c_uint32), ("step_samples", C.c_uint32), ("threshold", C.c_float), ("mean_floor", C.c_float)]
 
@@ -291,7 +311,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned", "crt_render_planned_device",
            "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device",
            "crt_render_aov_shading", "crt_render_aov_shading_device", "crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate",
-           "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device"]
+           "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device", "crt_half_buffers", "crt_half_buffers_device",
+           "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device"]
 
 _lib = None
 
@@ -399,6 +420,14 @@ def lib():
                                C.POINTER(UpsampleInfo)]
     L.crt_upsample_device.argtypes = [C.c_int, C.POINTER(UpsampleParams), C.POINTER(UpsampleLow), C.POINTER(UpsampleGuides), C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.POINTER(UpsampleInfo)]
+    L.crt_half_buffers.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.crt_half_buffers_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+    L.crt_filter_select_defaults.argtypes = [C.POINTER(FilterSelectParams)]
+    L.crt_filter_select_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.crt_filter_select.argtypes = [C.c_int, C.POINTER(FilterSelectParams), C.POINTER(FilterSelectInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.POINTER(FilterSelectInfo)]
+    L.crt_filter_select_device.argtypes = [C.c_int, C.POINTER(FilterSelectParams), C.POINTER(FilterSelectInputs), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(FilterSelectInfo)]
     L.crt_multi_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     L.crt_multi_destroy.argtypes = [C.c_void_p]
     L.crt_multi_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats),

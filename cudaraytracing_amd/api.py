@@ -188,6 +188,10 @@ class Render:
         self.low_frame = None            # run_view_upsampled: rgb, mean, variance, albedo, normal, depth (and the shading AOVs) of the low-resolution frame
         self.upsampled_variance = None
         self.upsample_info = None
+        self.half_a_buffer = None        # run_view(want_halves=True): the means of the even and of the odd samples
+        self.half_b_buffer = None
+        self.select_buffers = None       # run_view_selected: choice, error, the halves, their variance and the filtered candidates
+        self.select_info = None
         self.temporal_history_buffer = None
         self._temporal = None        # run_view_temporal: the history (temporal()'s `prev` dict), its camera and size
         self._temporal_frames = 0    # frames since the last reset_temporal()
@@ -250,14 +254,16 @@ class Render:
         return self._params(rank=rank, world=world, flags=(capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags,
                             width=width, height=height)
 
-    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False):
+    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False, want_halves=False):
         """Renders the whole frame; returns the RGB8 frame buffer (H, W, 3).  want_variance: render with FLAG_VARIANCE (the frame is
-        the same bits) and leave the per-pixel variance of the mean, (H, W, 3) float32 (crt_variance), in self.variance_buffer."""
+        the same bits) and leave the per-pixel variance of the mean, (H, W, 3) float32 (crt_variance), in self.variance_buffer.
+        want_halves: render with FLAG_HALF_BUFFERS (which implies FLAG_VARIANCE; the same bits again) and leave the means of the even
+        and of the odd samples (crt_half_buffers) in self.half_a_buffer / self.half_b_buffer beside the variance."""
         if not self._h:
             raise RuntimeError("Render.run_view after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags,
-                           width=width, height=height)
+        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) |
+                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | self.extra_flags, width=width, height=height)
         w, h = prm.width, prm.height
         rgb = np.zeros((h, w, 3), dtype=np.uint8)
         mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
@@ -265,8 +271,19 @@ class Render:
         capi.check(capi.lib().crt_render(self._h, C.byref(cam), C.byref(prm), capi.ptr(rgb), capi.ptr(mean),
                                          C.byref(st)), "crt_render")
         self.frame_buffer, self.mean_buffer, self.stats = rgb, mean, st.as_dict()
-        self.variance_buffer = self.variance(width=w, height=h)[0] if want_variance else None
+        self.variance_buffer = self.variance(width=w, height=h)[0] if (want_variance or want_halves) else None
+        self.half_a_buffer, self.half_b_buffer = self.half_buffers(width=w, height=h)[:2] if want_halves else (None, None)
         return rgb
+
+    def half_buffers(self, width=None, height=None):
+        """(a, b, samples done) of crt_half_buffers: the means of the even and of the odd samples of every pixel, (H, W, 3) float32 each,
+        from the sums a render with want_halves keeps on the handle -- two independent estimates of the frame.  Reads only."""
+        h_ = self._handle("half_buffers")
+        w, h = width or self.scene.width, height or self.scene.height
+        a, b = np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w, 3), dtype=np.float32)
+        done = C.c_uint32(0)
+        capi.check(capi.lib().crt_half_buffers(h_, capi.ptr(a), capi.ptr(b), C.byref(done)), "crt_half_buffers")
+        return a, b, int(done.value)
 
     def variance(self, width=None, height=None):
         """(var (H, W, 3) float32, samples done) of crt_variance: the estimated variance of the mean the frame -- or, between the ranges
@@ -383,16 +400,17 @@ class Render:
             h_, C.byref(cam), C.byref(prm), C.byref(ap), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
 
     def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
-                       want_variance=False, stats=False):
+                       want_variance=False, stats=False, want_halves=False):
         """Progressive rendering: adds samples [sample_begin, sample_begin + sample_count) of the spp samples per pixel to the
         accumulator of the device scene; ranges go in ascending order from 0.  Returns the RGB8 frame once the range that ends
         at spp has been rendered (bit-identical to run_view), None before.  A range with sample_begin > 0 that does not continue
-        the frame in flight on the handle (samples so far, spp, size) raises CrtError."""
+        the frame in flight on the handle (samples so far, spp, size) raises CrtError.  want_halves: the range goes with
+        FLAG_HALF_BUFFERS (half_buffers() reads the halves between the ranges and after the last)."""
         if not self._h:
             raise RuntimeError("Render.run_view_range after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
-        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) | self.extra_flags,
-                           width=width, height=height)
+        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) |
+                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | self.extra_flags, width=width, height=height)
         w, h = prm.width, prm.height
         last = sample_begin + sample_count == self.spp
         rgb = np.zeros((h, w, 3), dtype=np.uint8) if last else None
@@ -598,6 +616,30 @@ class Render:
             rgb, mean, self.denoise_info = denoise(color, **settings, **self.aov_buffers)
         if demodulate:
             rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
+        return rgb, mean
+
+    def run_view_selected(self, eye_pos, inv_view_mat, fovY, candidates=("var", "nlm"), error_radius=None, blend_radius=None, width=None, height=None):
+        """The frame of run_view with, per pixel, the one of the candidate filters whose error estimated against the independent other
+        half frame is smallest (crt_filter_select, contract: include/crt.h).  Renders with want_halves, takes the guides of run_view_aov,
+        runs every candidate on each half -- "none" (the half as it is), "atrous" (denoise), "var" (denoise_var) or "nlm" (denoise_nlm),
+        each with its own defaults; the variance-taking ones get 2 x the frame's variance, the variance of one half's mean -- and calls
+        filter_select.  Returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32).  Kept: the noisy frame in self.frame_buffer /
+        self.mean_buffer, the guides in self.aov_buffers, self.select_buffers (choice (H, W) uint8, error (H, W) float32, half_a, half_b,
+        half_variance, filtered_a, filtered_b) and self.select_info (total_ms, chosen)."""
+        names = tuple(candidates)
+        unknown = [n for n in names if n not in _SELECT_CANDIDATES]
+        if unknown or not 1 <= len(names) <= capi.SELECT_MAX_CANDIDATES:
+            raise ValueError("run_view_selected: candidates must be 1 .. %d of %r, got %r" % (capi.SELECT_MAX_CANDIDATES, _SELECT_CANDIDATES, names))
+        self._handle("run_view_selected")
+        self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_halves=True)
+        guides = self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        a, b = self.half_a_buffer, self.half_b_buffer
+        half_var = np.float32(2.0) * self.variance_buffer
+        fa = [_select_candidate(n, a, half_var, guides, self.device) for n in names]
+        fb = [_select_candidate(n, b, half_var, guides, self.device) for n in names]
+        rgb, mean, choice, error, self.select_info = filter_select(a, b, half_var, fa, fb, error_radius=error_radius, blend_radius=blend_radius,
+                                                                   device=self.device, return_info=True)
+        self.select_buffers = {"choice": choice, "error": error, "half_a": a, "half_b": b, "half_variance": half_var, "filtered_a": fa, "filtered_b": fb}
         return rgb, mean
 
     def run_view_upsampled(self, eye_pos, inv_view_mat, fovY, factor=2, width=None, height=None, guide_spp=None, demodulate=True, filter_low=False,
@@ -817,9 +859,12 @@ class MultiRender(Render):
         self.rank_stats = None
         self.info = None
 
-    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, to_host=True, want_variance=False):
+    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, to_host=True, want_variance=False,
+                 want_halves=False):
         if want_variance:
             raise NotImplementedError("the variance buffer is a single-device interface (crt_variance): there is no gather for it")
+        if want_halves:
+            raise NotImplementedError("the half buffers are a single-device interface (crt_half_buffers): there is no gather for them")
         if not self._mh:
             raise RuntimeError("MultiRender.run_view after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
@@ -861,6 +906,8 @@ _MULTI_REFUSALS = {
     "sample_plan": "the sample plan is a single-device interface (crt_sample_plan)",
     "preview": "previews are a single-device interface (crt_preview)",
     "variance": "the variance buffer is a single-device interface (crt_variance)",
+    "half_buffers": "the half buffers are a single-device interface (crt_half_buffers)",
+    "run_view_selected": "filter selection is a single-device interface (crt_half_buffers, crt_filter_select): gather the frame first",
     "accel_info": "crt_scene_accel_info is a single-device interface",
     "run_view_device": "MultiRender owns its device buffers (crt_multi_frame_device)",
     "run_view_aov": "the AOV pass is a single-device interface (crt_render_aov)",
@@ -1274,6 +1321,95 @@ def upsample_device(width, height, low_width, low_height, low_ptrs, out_color_pt
     capi.check(capi.lib().crt_upsample_device(device, C.byref(prm), C.byref(lo), C.byref(hi) if hi is not None else None, _vp(out_color_ptr),
                                               _vp(out_variance_ptr), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
                "crt_upsample_device")
+    return info.as_dict() if want_info else None
+
+
+_SELECT_SETTINGS = ("error_radius", "blend_radius")
+_SELECT_CANDIDATES = ("none", "atrous", "var", "nlm")
+
+
+def _select_candidate(name, half, half_variance, guides, device):
+    """Candidate filter `name` of run_view_selected applied to one half frame, with its own defaults"""
+    if name == "none":
+        return half
+    if name == "atrous":
+        return denoise(half, device=device, want_rgb=False, **guides)[1]
+    if name == "var":
+        return denoise_var(half, half_variance, device=device, want_rgb=False, **guides)[1]
+    return denoise_nlm(half, half_variance, device=device, want_rgb=False, **guides)[1]
+
+
+def filter_select_defaults():
+    """crt_filter_select_defaults as a dict: error_radius and blend_radius."""
+    return _settings(_defaults(capi.FilterSelectParams, "crt_filter_select_defaults"), _SELECT_SETTINGS)
+
+
+def filter_select_scratch_bytes(width, height):
+    n = C.c_uint64()
+    capi.check(capi.lib().crt_filter_select_scratch_bytes(width, height, C.byref(n)), "crt_filter_select_scratch_bytes")
+    return int(n.value)
+
+
+def _select_params(who, width, height, n_candidates, error_radius, blend_radius):
+    for name, v in (("error_radius", error_radius), ("blend_radius", blend_radius)):
+        if v is not None and (int(v) != v or not 0 <= int(v) < 2 ** 32):
+            raise ValueError("%s: %s must be a non-negative integer, got %r" % (who, name, v))
+    if not 1 <= n_candidates <= capi.SELECT_MAX_CANDIDATES:
+        raise ValueError("%s needs 1 .. %d candidates, got %d" % (who, capi.SELECT_MAX_CANDIDATES, n_candidates))
+    return _defaults(capi.FilterSelectParams, "crt_filter_select_defaults", width, height, n_candidates=n_candidates, error_radius=error_radius,
+                     blend_radius=blend_radius)
+
+
+def filter_select(half_a, half_b, half_variance, filtered_a, filtered_b, error_radius=None, blend_radius=None, device=0, want_rgb=True, want_mean=True,
+                  want_choice=True, want_error=True, return_info=False):
+    """Error-estimated filter selection (crt_filter_select, contract: include/crt.h).  half_a, half_b: the two half frames
+    (Render.half_buffers), half_variance: the variance of ONE half's mean (2 x Render.variance), filtered_a / filtered_b: sequences of
+    1 .. 4 images, filter k applied to half_a and to half_b; all (H, W, 3) float32.  None radii take crt_filter_select_defaults.
+    Returns (rgb, mean, choice, error): the RGB8 tone map, the blended frame, the chosen candidate per pixel (H, W) uint8 and its
+    estimated squared error (H, W) float32 -- None for an output that is not wanted; with return_info also the crt_filter_select_info
+    dict (total_ms, chosen: pixels per candidate)."""
+    fa, fb = list(filtered_a), list(filtered_b)
+    if len(fa) != len(fb):
+        raise ValueError("filter_select: %d images filtered from half_a, %d from half_b" % (len(fa), len(fb)))
+    fields = (("half_a", half_a, 3), ("half_b", half_b, 3), ("half_variance", half_variance, 3)) + \
+        tuple(("filtered_a[%d]" % k, x, 3) for k, x in enumerate(fa)) + tuple(("filtered_b[%d]" % k, x, 3) for k, x in enumerate(fb))
+    if any(x is None for _, x, _ in fields):
+        raise ValueError("filter_select: every input image is required")
+    keep = _image_inputs("filter_select", "an (H, W, 3) half frame", fields)
+    h, w = keep[0].shape[:2]
+    prm = _select_params("filter_select", w, h, len(fa), error_radius, blend_radius)
+    inputs = capi.FilterSelectInputs()
+    inputs.half_a, inputs.half_b, inputs.half_variance = (x.ctypes.data for x in keep[:3])
+    for k in range(len(fa)):
+        inputs.filtered_a[k], inputs.filtered_b[k] = keep[3 + k].ctypes.data, keep[3 + len(fa) + k].ctypes.data
+    mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    choice = np.zeros((h, w), dtype=np.uint8) if want_choice else None
+    error = np.zeros((h, w), dtype=np.float32) if want_error else None
+    info = capi.FilterSelectInfo()
+    capi.check(capi.lib().crt_filter_select(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), capi.ptr(choice), capi.ptr(error),
+                                            C.byref(info)), "crt_filter_select")
+    out = (rgb, mean, choice, error)
+    return out + (info.as_dict(),) if return_info else out
+
+
+def filter_select_device(width, height, half_a_ptr, half_b_ptr, half_variance_ptr, filtered_a_ptrs, filtered_b_ptrs, out_mean_ptr, out_rgb_ptr,
+                         scratch_ptr, scratch_bytes, out_choice_ptr=None, out_error_ptr=None, error_radius=None, blend_radius=None, device=0,
+                         stream=None, want_info=True):
+    """Enqueues crt_filter_select_device with everything in device memory (raw device pointers; filtered_a_ptrs / filtered_b_ptrs:
+    sequences of 1 .. 4); the caller owns the scratch (filter_select_scratch_bytes).  out_mean_ptr or out_rgb_ptr may be None, not
+    both.  With want_info the call synchronizes the stream and returns the crt_filter_select_info dict, else None."""
+    fa, fb = list(filtered_a_ptrs), list(filtered_b_ptrs)
+    if len(fa) != len(fb):
+        raise ValueError("filter_select_device: %d images filtered from half_a, %d from half_b" % (len(fa), len(fb)))
+    prm = _select_params("filter_select_device", width, height, len(fa), error_radius, blend_radius)
+    inputs = capi.FilterSelectInputs(half_a_ptr or None, half_b_ptr or None, half_variance_ptr or None)
+    for k in range(len(fa)):
+        inputs.filtered_a[k], inputs.filtered_b[k] = fa[k] or None, fb[k] or None
+    info = capi.FilterSelectInfo()
+    capi.check(capi.lib().crt_filter_select_device(device, C.byref(prm), C.byref(inputs), _vp(out_mean_ptr), _vp(out_rgb_ptr), _vp(out_choice_ptr),
+                                                   _vp(out_error_ptr), _vp(scratch_ptr), int(scratch_bytes), _vp(stream),
+                                                   C.byref(info) if want_info else None), "crt_filter_select_device")
     return info.as_dict() if want_info else None
 
 

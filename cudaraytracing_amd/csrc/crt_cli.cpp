@@ -42,6 +42,10 @@
 // its own defaults; --denoise-iterations / --denoise-sigma override them as well).  --denoise-nlm makes --denoise use the non-local-means
 // filter (crt_denoise_nlm, its own defaults); --denoise-nlm-params sets its radius, patch and k, --denoise-sigma its three guide sigmas (the
 // colour value is ignored: the filter has no colour sigma).  Not with --denoise-variance or --denoise-iterations.
+// --denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]] makes --denoise pick, per pixel, the one of the filters in LIST -- none, atrous, var,
+// nlm, joined by + (1 .. 4 of them), each with its own defaults -- whose error estimated against the other half frame is smallest
+// (CRT_FLAG_HALF_BUFFERS, crt_half_buffers, crt_filter_select; the radii default to crt_filter_select_defaults').  --denoise-choice PATH
+// writes the choice map as a PNG (candidate k of K as the grey 255 k / max(K - 1, 1)).  Not with the other --denoise-* options or --demodulate.
 // --denoise PATH renders as usual, then filters the frame with the AOV-guided a-trous denoiser (crt_denoise, one device) and writes the
 // result as a PNG to PATH; -o and --aov outputs are unchanged by it.  --denoise-iterations (1 .. 5) and --denoise-sigma (colour, normal,
 // albedo, depth) override crt_denoise_defaults.
@@ -55,6 +59,7 @@
 // --devices names the device of every rank explicitly (a repeated index puts two ranks on one GPU: --gather copy only).
 #include "crt_host.hpp"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -72,6 +77,7 @@ int main(int argc, char** argv)
                              "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
+                             "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm joined by +)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n"
@@ -92,6 +98,10 @@ int main(int argc, char** argv)
         bool denoise_nlm = false, nlm_params = false;
         crt_nlm_params nlm; // --denoise-nlm: the filter's defaults with the overrides
         crt_denoise_nlm_defaults(&nlm);
+        std::vector<int> select_candidates; // --denoise-select: crt::Render::SELECT_* of LIST
+        crt_filter_select_params sel;       // ... and the selection's defaults with the radii given
+        crt_filter_select_defaults(&sel);
+        std::string denoise_choice;
         uint32_t specular_bounces = 0; // 0: crt_aov_specular_defaults'
         int temporal = 0;
         bool temporal_option = false, temporal_denoise = false, temporal_clamp = false, temporal_moments = false;
@@ -256,6 +266,34 @@ int main(int argc, char** argv)
                 } else good = false;
                 if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-variance needs samples or moments[,MIN_HISTORY]: MIN_HISTORY >= 1");
             }
+            else if (a == "--denoise-choice") { need(i, 1); denoise_choice = argv[++i]; }
+            else if (a == "--denoise-select") {
+                need(i, 1);
+                const std::string v = argv[++i];
+                const size_t comma = v.find(',');
+                const std::string list = v.substr(0, comma);
+                bool good = !list.empty();
+                for (size_t at = 0; good && at <= list.size();) {
+                    const size_t plus = std::min(list.find('+', at), list.size());
+                    const std::string name = list.substr(at, plus - at);
+                    const int id = name == "none" ? crt::Render::SELECT_NONE : name == "atrous" ? crt::Render::SELECT_ATROUS : name == "var" ? crt::Render::SELECT_VAR
+                                 : name == "nlm" ? crt::Render::SELECT_NLM : -1;
+                    good = id >= 0 && select_candidates.size() < CRT_SELECT_MAX_CANDIDATES;
+                    select_candidates.push_back(id);
+                    at = plus + 1;
+                }
+                uint32_t* dst[2] = {&sel.error_radius, &sel.blend_radius};
+                const char* q = comma == std::string::npos ? "" : v.c_str() + comma + 1;
+                for (int k = 0; good && comma != std::string::npos && k < 2; k++) {
+                    char* end = nullptr;
+                    const long r = std::strtol(q, &end, 10);
+                    good = *q >= '0' && *q <= '9' && (*end == 0 || (k == 0 && *end == ',')) && r <= (k == 0 ? 8 : 4);
+                    *dst[k] = (uint32_t)r;
+                    if (*end == 0) break;
+                    q = end + 1;
+                }
+                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs LIST[,ERROR_RADIUS[,BLEND_RADIUS]]: LIST 1 .. 4 of none, atrous, var, nlm joined by +, ERROR_RADIUS 0 .. 8, BLEND_RADIUS 0 .. 4");
+            }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
                 need(i, 1);
@@ -311,6 +349,12 @@ int main(int argc, char** argv)
         if (denoise_nlm && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is a filter of its own (not with --denoise-variance)");
         if (denoise_nlm && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is one pass (not with --denoise-iterations)");
         if (denoise_nlm && dn_sigma) { nlm.sigma_normal = dn.sigma_normal; nlm.sigma_albedo = dn.sigma_albedo; nlm.sigma_depth = dn.sigma_depth; }
+        const bool denoise_select = !select_candidates.empty();
+        if (denoise_select && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs --denoise PATH");
+        if (!denoise_choice.empty() && !denoise_select) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-choice needs --denoise-select LIST");
+        if (denoise_select && (denoise_var || denoise_nlm || dn_iterations || dn_sigma || denoise_specular || demodulate))
+            throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select runs every filter with its own defaults on radiance (not with the other --denoise-* options or --demodulate)");
+        if (denoise_select && (adaptive || temporal)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs the half buffers of a uniformly sampled frame (not with --adaptive or --temporal)");
         const bool want_var = !variance.empty() || denoise_var || denoise_nlm || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
         crt_denoise_var_defaults(&tdn);
@@ -328,7 +372,7 @@ int main(int argc, char** argv)
         crt::Render& render = render_one_or_many;
         render.set_seed(seed);
         render.set_traversal(reference ? CRT_TRAVERSAL_REFERENCE : (fast && !exact) ? CRT_TRAVERSAL_FAST : CRT_TRAVERSAL_EXACT);
-        render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u));
+        render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u) | (denoise_select ? CRT_FLAG_HALF_BUFFERS : 0u));
         render.set_aov_shading(!aov_shading.empty());
         if (demodulate) render.set_demodulate(true);
         float inv_view[9];
@@ -439,7 +483,22 @@ int main(int argc, char** argv)
             if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the specular AOV files failed: ") + crt_last_error());
             std::printf("%s\n%s\n%s\n%s\n", pg.c_str(), pn.c_str(), pd.c_str(), pb.c_str());
         }
-        if (!denoise.empty()) {
+        if (denoise_select) {
+            render.run_denoise_select(select_candidates, sel);
+            const crt_filter_select_info& si = render.last_select_info();
+            std::printf("denoise-select: error radius %u, blend radius %u, pixels per candidate %llu %llu %llu %llu, device %.3f ms\n", sel.error_radius, sel.blend_radius,
+                        (unsigned long long)si.chosen[0], (unsigned long long)si.chosen[1], (unsigned long long)si.chosen[2], (unsigned long long)si.chosen[3], si.total_ms);
+            render.save_denoised_buffer(denoise.c_str());
+            std::printf("%s\n", denoise.c_str());
+            if (!denoise_choice.empty()) {
+                const size_t n = (size_t)task.width * task.height, top = select_candidates.size() > 1 ? select_candidates.size() - 1 : 1;
+                std::vector<uint8_t> grey(3 * n);
+                for (size_t k = 0; k < n; k++) grey[3 * k] = grey[3 * k + 1] = grey[3 * k + 2] = (uint8_t)(255u * render.get_choice_buffer()[k] / top);
+                const int rc = crt_write_png(denoise_choice.c_str(), task.width, task.height, grey.data());
+                if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the choice map failed: ") + crt_last_error());
+                std::printf("%s\n", denoise_choice.c_str());
+            }
+        } else if (!denoise.empty()) {
             if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
             const crt_denoise_info& di = render.last_denoise_info();
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);

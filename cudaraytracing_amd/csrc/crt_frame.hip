@@ -1,5 +1,5 @@
 // cudaraytracing_amd/csrc/crt_frame.hip -- the kernels around the render kernels: k_accumulate (per pixel c += L_k / spp in sample order, tone map:
-// include/Render.cuh:348-350; k_accumulate_var: also the sum of squares behind crt_variance, read out by k_variance), k_preview, and the kernels behind crt_intersect's ray upload and the crt_device_* self-tests.
+// include/Render.cuh:348-350; k_accumulate_var: also the sum of squares behind crt_variance, read out by k_variance; k_accumulate_half: also the half sums behind crt_half_buffers, read out by k_half_buffers), k_preview, and the kernels behind crt_intersect's ray upload and the crt_device_* self-tests.
 // The stages these share with crt_adaptive.hip -- slot to pixel to output index, the three-plane sums, the sample fold, the output write -- are in crt_stages.h.
 #include "crt_internal.h"
 
@@ -32,6 +32,51 @@ template <bool VAR> __device__ __forceinline__ void accumulate(const AParams& A,
 
 __global__ __launch_bounds__(256) void k_accumulate(const AParams A) { accumulate<false>(A, nullptr); }
 __global__ __launch_bounds__(256) void k_accumulate_var(const AParams A, float* const qacc) { accumulate<true>(A, qacc); }
+
+// CRT_FLAG_HALF_BUFFERS: k_accumulate_var, and the sums of the even and of the odd samples (fold_samples_half) carried in the six planes
+// of `hacc` -- h0 in planes 0 .. 2, h1 in 3 .. 5 -- as q is in qacc.  parity: of the chunk's first sample in the frame.
+__global__ __launch_bounds__(256) void k_accumulate_half(const AParams A, float* const qacc, float* const hacc, const uint32_t parity)
+{
+    uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= A.nslots) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    F3 c = f3(0.0f, 0.0f, 0.0f);
+    if (px.valid) {
+        F3 q = f3(0.0f, 0.0f, 0.0f), h0 = f3(0.0f, 0.0f, 0.0f), h1 = f3(0.0f, 0.0f, 0.0f);
+        float* const hacc1 = hacc + 3ull * A.nslots;
+        if (!A.first_chunk) {
+            c = acc_load3(A.accum, A.nslots, slot); q = acc_load3(qacc, A.nslots, slot);
+            h0 = acc_load3(hacc, A.nslots, slot); h1 = acc_load3(hacc1, A.nslots, slot);
+        }
+        fold_samples_half(A, slot, A.chunk_samples, parity, c, q, h0, h1);
+        acc_store3(qacc, A.nslots, slot, q);
+        acc_store3(hacc, A.nslots, slot, h0); acc_store3(hacc1, A.nslots, slot, h1);
+        acc_store3(A.accum, A.nslots, slot, c);
+        if (!A.last_chunk) return;
+    } else if (!px.out || !A.last_chunk) {
+        return;
+    }
+    write_color(A, px.o, px.valid, c);
+}
+
+// crt_half_buffers (contract: include/crt.h): the two half means from the handle's sums h0 and h1, scale_a = S / n_a, scale_b = S / n_b,
+// in the frame's layout (padding slots of a tiled shard +0).  Reads the sums only; either output may be null.
+__global__ __launch_bounds__(256) void k_half_buffers(const AParams A, const float* const hacc, float* const out_a, float* const out_b, const float scale_a,
+                                                      const float scale_b)
+{
+    uint32_t slot = blockIdx.x * 256u + threadIdx.x;
+    if (slot >= A.nslots) return;
+    const SlotPixel px = slot_pixel(A, slot);
+    if (!px.out) return;
+    F3 a = f3(0.0f, 0.0f, 0.0f), b = f3(0.0f, 0.0f, 0.0f);
+    if (px.valid) {
+        const F3 h0 = acc_load3(hacc, A.nslots, slot), h1 = acc_load3(hacc + 3ull * A.nslots, A.nslots, slot);
+        a = f3(h0.x * scale_a, h0.y * scale_a, h0.z * scale_a);
+        b = f3(h1.x * scale_b, h1.y * scale_b, h1.z * scale_b);
+    }
+    if (out_a) { out_a[px.o * 3 + 0] = a.x; out_a[px.o * 3 + 1] = a.y; out_a[px.o * 3 + 2] = a.z; }
+    if (out_b) { out_b[px.o * 3 + 0] = b.x; out_b[px.o * 3 + 1] = b.y; out_b[px.o * 3 + 2] = b.z; }
+}
 
 // crt_variance (contract: include/crt.h): the variance of the mean from the handle's sums c (A.accum) and q, n = samples so far, written
 // to A.out_mean in the frame's layout (padding slots of a tiled shard +0).  Reads the sums only.
@@ -130,6 +175,14 @@ __global__ void k_philox(uint32_t n, const uint32_t* ctr, const uint32_t* key, u
 // ---- exported to crt_render.hip ----
 void launch_accumulate(const AParams& A, hipStream_t st) { hipLaunchKernelGGL(k_accumulate, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A); }
 void launch_accumulate_var(const AParams& A, float* qacc, hipStream_t st) { hipLaunchKernelGGL(k_accumulate_var, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, qacc); }
+void launch_accumulate_half(const AParams& A, float* qacc, float* hacc, uint32_t parity, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_accumulate_half, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, qacc, hacc, parity);
+}
+void launch_half_buffers(const AParams& A, const float* hacc, float* out_a, float* out_b, float scale_a, float scale_b, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_half_buffers, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, hacc, out_a, out_b, scale_a, scale_b);
+}
 void launch_variance(const AParams& A, const float* qacc, float fn, float fs, hipStream_t st)
 {
     hipLaunchKernelGGL(k_variance, dim3((A.nslots + 255) / 256), dim3(256), 0, st, A, qacc, fn, fs);

@@ -664,7 +664,7 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     if (!device_scene_ && !multi_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view after free()");
     crt_camera cam;
     crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE), cam, p);
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS), cam, p);
     variance_buffer_.clear();
     int rc;
     if (multi_) {
@@ -875,6 +875,66 @@ void Render::run_denoise_nlm(const crt_nlm_params& prm)
     if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
         throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm needs run_view and run_aov of this frame size first");
     denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
+}
+
+void Render::run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm)
+{
+    const char* who = "Render::run_denoise_select";
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": filter selection is a single-device interface");
+    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
+    if (demodulate_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": the half frames are filtered as radiance (not with set_demodulate)");
+    if (candidates.empty() || candidates.size() > CRT_SELECT_MAX_CANDIDATES) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs 1 .. 4 candidates");
+    const size_t n = scene_->get_pixels();
+    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
+        throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs run_view and run_aov of this frame size first");
+    std::vector<float> half[2] = {std::vector<float>(3 * n), std::vector<float>(3 * n)}, half_variance(3 * n);
+    int rc = crt_half_buffers(device_scene_, half[0].data(), half[1].data(), nullptr);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
+    const float* var = variance();
+    for (size_t i = 0; i < 3 * n; i++) half_variance[i] = 2.0f * var[i];
+    // every candidate on either half, with its own defaults and the guides of the last run_aov
+    std::vector<std::vector<float>> filtered[2];
+    crt_filter_select_inputs in{};
+    in.half_a = half[0].data(); in.half_b = half[1].data(); in.half_variance = half_variance.data();
+    const uint32_t w = scene_->get_width(), h = scene_->get_height();
+    for (int side = 0; side < 2; side++) {
+        filtered[side].resize(candidates.size());
+        for (size_t k = 0; k < candidates.size(); k++) {
+            const float* image = half[side].data();
+            if (candidates[k] != SELECT_NONE) {
+                filtered[side][k].assign(3 * n, 0.0f);
+                crt_denoise_var_inputs vin{};
+                vin.color = half[side].data(); vin.variance = half_variance.data();
+                vin.albedo = albedo_buffer_.data(); vin.normal = normal_buffer_.data(); vin.depth = depth_buffer_.data();
+                if (candidates[k] == SELECT_ATROUS) {
+                    crt_denoise_params p;
+                    crt_denoise_defaults(&p);
+                    p.width = w; p.height = h;
+                    crt_denoise_inputs din{};
+                    din.color = vin.color; din.albedo = vin.albedo; din.normal = vin.normal; din.depth = vin.depth;
+                    rc = crt_denoise(device_, &p, &din, filtered[side][k].data(), nullptr, nullptr);
+                } else if (candidates[k] == SELECT_VAR) {
+                    crt_denoise_params p;
+                    crt_denoise_var_defaults(&p);
+                    p.width = w; p.height = h;
+                    rc = crt_denoise_var(device_, &p, &vin, filtered[side][k].data(), nullptr, nullptr, nullptr);
+                } else if (candidates[k] == SELECT_NLM) {
+                    crt_nlm_params p;
+                    crt_denoise_nlm_defaults(&p);
+                    p.width = w; p.height = h;
+                    rc = crt_denoise_nlm(device_, &p, &vin, filtered[side][k].data(), nullptr, nullptr, nullptr);
+                } else throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": unknown candidate");
+                if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
+                image = filtered[side][k].data();
+            }
+            (side == 0 ? in.filtered_a : in.filtered_b)[k] = image;
+        }
+    }
+    crt_filter_select_params p = prm;
+    p.width = w; p.height = h; p.n_candidates = (uint32_t)candidates.size();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f); choice_buffer_.assign(n, 0);
+    rc = crt_filter_select(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), choice_buffer_.data(), nullptr, &select_info_);
+    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
 }
 
 void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp)

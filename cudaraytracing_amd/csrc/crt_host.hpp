@@ -258,6 +258,14 @@ public:
     void run_denoise_var(const crt_denoise_params& prm);
     // the same with the non-local-means filter (crt_denoise_nlm; prm: crt_denoise_nlm_defaults with overrides), CRT_FLAG_VARIANCE likewise
     void run_denoise_nlm(const crt_nlm_params& prm);
+    // Error-estimated filter selection (crt_half_buffers, crt_filter_select): the last run_view must have had CRT_FLAG_HALF_BUFFERS
+    // (set_flags).  candidates: 1 .. 4 of SELECT_NONE / _ATROUS / _VAR / _NLM, each run with its own defaults on either half frame, the
+    // variance-taking ones with 2 x variance(); prm: crt_filter_select_defaults with overrides, its sizes and n_candidates are set here.
+    // The result is the denoised buffer; the choice map is get_choice_buffer().  Not with set_demodulate.
+    enum { SELECT_NONE = 0, SELECT_ATROUS = 1, SELECT_VAR = 2, SELECT_NLM = 3 };
+    void run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm);
+    const crt_filter_select_info& last_select_info() const { return select_info_; }
+    const std::vector<unsigned char>& get_choice_buffer() const { return choice_buffer_; }
     // per-pixel variance of the mean of the last run_view (crt_variance; needs set_flags(CRT_FLAG_VARIANCE) before it): W x H x 3,
     // fetched from the device on the first call after a frame; one device only
     const float* variance();
@@ -309,7 +317,7 @@ public:
     void set_light_sample_n(const int& n) { light_sample_n_ = (unsigned)n; }
     void set_seed(uint64_t s) { seed_ = s; }
     void set_traversal(uint32_t t) { traversal_ = t; }
-    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE, CRT_FLAG_VARIANCE
+    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE, CRT_FLAG_VARIANCE, CRT_FLAG_HALF_BUFFERS
     void set_width(const unsigned& w);
     void set_height(const unsigned& h);
     const crt_stats& last_stats() const { return stats_; }
@@ -364,6 +372,8 @@ private:
     template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);
     int device_ = 0;
     crt_denoise_info denoise_info_{};
+    crt_filter_select_info select_info_{};
+    std::vector<unsigned char> choice_buffer_;
     crt_stats stats_{};
     crt_aov_info aov_info_{};
     std::vector<float> guide_albedo_buffer_, last_normal_buffer_, path_depth_buffer_, bounces_buffer_; // run_aov_specular

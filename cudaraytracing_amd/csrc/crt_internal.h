@@ -124,6 +124,8 @@ void launch_trace(int mode_id, const TParams& T, uint32_t blocks, size_t lds, hi
 // frame and test kernels (crt_frame.hip)
 void launch_accumulate(const AParams& A, hipStream_t st);
 void launch_accumulate_var(const AParams& A, float* qacc, hipStream_t st); // CRT_FLAG_VARIANCE: c and the sum of squares q (3 planes of nslots)
+void launch_accumulate_half(const AParams& A, float* qacc, float* hacc, uint32_t parity, hipStream_t st); // CRT_FLAG_HALF_BUFFERS: c, q and the half sums (6 planes); parity of the chunk's first sample
+void launch_half_buffers(const AParams& A, const float* hacc, float* out_a, float* out_b, float scale_a, float scale_b, hipStream_t st); // crt_half_buffers
 void launch_variance(const AParams& A, const float* qacc, float fn, float fs, hipStream_t st); // crt_variance: A.accum, qacc -> A.out_mean
 void launch_preview(const AParams& A, float scale, hipStream_t st);
 void launch_fill_rays(const Pool& pool, uint32_t n, const float* o, const float* d, bool raw_dir, const float* limits);

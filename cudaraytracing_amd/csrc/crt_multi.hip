@@ -373,7 +373,7 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
             crt_params p = *prm;
             p.rank = r; p.world = world;
             p.flags |= CRT_FLAG_TILED_OUTPUT;
-            p.flags &= ~(uint32_t)CRT_FLAG_VARIANCE; // (there is no gather for the variance buffer: crt_variance is a single-device interface)
+            p.flags &= ~(uint32_t)(CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS); // (there is no gather for the variance buffer or the halves: crt_variance and crt_half_buffers are single-device interfaces)
             if (hipSetDevice(rk.device) != hipSuccess) { rcs[r] = CRT_ERR_HIP; errs[r] = "hipSetDevice failed"; return; }
             rcs[r] = crt_render_device(rk.scene, cam, &p, rk.local, want_mean ? rk.local + mean_off : nullptr, rk.stream, &st[r]);
             if (rcs[r] != CRT_OK) errs[r] = crt_last_error();

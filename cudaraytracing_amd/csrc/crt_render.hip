@@ -1,5 +1,5 @@
 // cudaraytracing_amd/csrc/crt_render.hip -- the launch logic of the device layer of libcrt.so: a frame (or a sample range of one) on either
-// pipeline, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*, crt_intersect,
+// pipeline, ray queries, and their entry points in the C ABI of include/crt.h (crt_render*, crt_preview*, crt_variance*, crt_half_buffers*, crt_intersect,
 // crt_device_*).  The frames in which not every pixel takes every sample (crt_render_adaptive*, crt_render_map*, crt_sample_plan*,
 // crt_render_planned*) are ranges of render_impl with an item source: crt_sparse.hip; the AOV passes trace their rays with trace_queries:
 // crt_aov_pass.hip.  Both see this file through crt_render.h.  The scene handle is made in crt_scene.hip (crt_scene.h); the kernels live
@@ -243,7 +243,7 @@ struct Frame {
     uint64_t cap;   // radiance entries: work items of a chunk, or the ring
     Rad3* L;        // the chunk's radiance, cap entries (null with the ring, whose entries are crt_scene::ring_L)
     RingPlan ring;
-    bool want_stats, tiled, want_var, var_frame;
+    bool want_stats, tiled, want_var, var_frame, want_half, half_frame;
     AParams A;
     const ItemSource* src; // null: every pixel slot takes every sample of the range
     bool open;             // the frame is resolved by the caller, not by the range that ends at spp
@@ -289,10 +289,12 @@ void accumulate_chunk(Frame& f, uint32_t s0, uint32_t ns)
     if (f.ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
     if (!f.ring.samples || A.last_chunk) {
         if (f.src) f.src->fold(A, s0, ns, f.st);
+        else if (f.want_half) launch_accumulate_half(A, sc->accum_q.p, sc->accum_h.p, s0 & 1u, f.st);
         else if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
         else launch_accumulate(A, f.st);
         HIP_CHECK(hipGetLastError());
         if (f.var_frame) { sc->var.valid = true; sc->var.set(f.prm, s0 + ns, f.tiled); }
+        if (f.half_frame) { sc->half.valid = true; sc->half.set(f.prm, s0 + ns, f.tiled); }
     }
     sc->acc.set(f.prm, A.last_chunk ? 0u : s0 + ns, f.tiled);
 }
@@ -704,11 +706,19 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
     if (!d_rgb && s_end == prm->spp && !open) return fail(CRT_ERR_INVALID_ARG, "crt_render: null frame buffer");
     const int rc_prm = params_check("crt_render", prm);
     if (rc_prm != CRT_OK) return rc_prm;
+    // CRT_FLAG_HALF_BUFFERS implies CRT_FLAG_VARIANCE: from here on the call is one with both
+    crt_params prm_both;
+    if (prm->flags & CRT_FLAG_HALF_BUFFERS) {
+        prm_both = *prm;
+        prm_both.flags |= CRT_FLAG_VARIANCE;
+        prm = &prm_both;
+    }
     Frame f;
     f.sc = sc; f.cam = cam; f.prm = prm; f.st = st; f.stats = stats; f.s_begin = s_begin; f.s_end = s_end; f.src = src; f.open = open;
     f.want_stats = (prm->flags & CRT_FLAG_STATS) != 0;
     f.tiled = (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0;
     f.want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
+    f.want_half = (prm->flags & CRT_FLAG_HALF_BUFFERS) != 0 && !src; // (a sparse frame keeps no halves)
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
     // a range that does not start a frame adds to the accumulator: it must hold exactly the samples before the range, of this frame
     if (s_begin > 0 && !continues_frame(sc->acc, prm, s_begin, f.tiled)) {
@@ -737,6 +747,10 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         f.var_frame = f.want_var && (s_begin == 0 || (sc->var.valid && continues_frame(sc->var, prm, s_begin, f.tiled)));
         sc->var.valid = false;
         if (f.want_var) sc->accum_q.ensure_uncached((size_t)f.sh.nslots * 3);
+        // the half sums: by the same rule
+        f.half_frame = f.want_half && (s_begin == 0 || (sc->half.valid && continues_frame(sc->half, prm, s_begin, f.tiled)));
+        sc->half.valid = false;
+        if (f.want_half) sc->accum_h.ensure_uncached((size_t)f.sh.nslots * 6);
         FrameMark frame;
         frame.set(prm, 0, f.tiled);
         f.A = frame_aparams(sc, frame, f.sh);
@@ -850,6 +864,38 @@ int crt_variance(crt_scene* sc, float* out_var, uint32_t* samples_done)
         const int rc = crt_variance_device(sc, s.f32.p, nullptr, samples_done);
         if (rc != CRT_OK) return rc;
         s.download(nullptr, out_var);
+        return CRT_OK;
+    });
+}
+
+int crt_half_buffers_device(crt_scene* sc, void* d_a, void* d_b, void* stream, uint32_t* samples_done)
+{
+    const int rc = halves_check("crt_half_buffers", sc, d_a, d_b);
+    if (rc != CRT_OK) return rc;
+    return hip_guard([&]() -> int {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const AParams A = frame_aparams(sc, sc->half, make_shard(sc->half.width, sc->half.height, sc->half.world));
+        const uint32_t n = sc->half.samples;
+        const float fs = (float)sc->half.spp;
+        launch_half_buffers(A, sc->accum_h.p, (float*)d_a, (float*)d_b, fs / (float)((n + 1) / 2), fs / (float)(n / 2), (hipStream_t)stream);
+        HIP_CHECK(hipGetLastError());
+        if (samples_done) *samples_done = n;
+        return CRT_OK;
+    });
+}
+
+int crt_half_buffers(crt_scene* sc, float* out_a, float* out_b, uint32_t* samples_done)
+{
+    const int rc0 = halves_check("crt_half_buffers", sc, out_a, out_b);
+    if (rc0 != CRT_OK) return rc0;
+    return hip_guard([&]() -> int {
+        HIP_CHECK(hipSetDevice(sc->device));
+        const uint64_t npix = out_pixels(sc->half.width, sc->half.height, sc->half.world, sc->half.tiled != 0);
+        Staging sa(npix, false, out_a != nullptr), sb(npix, false, out_b != nullptr);
+        const int rc = crt_half_buffers_device(sc, sa.f32.p, sb.f32.p, nullptr, samples_done);
+        if (rc != CRT_OK) return rc;
+        if (out_a) sa.download(nullptr, out_a);
+        if (out_b) sb.download(nullptr, out_b);
         return CRT_OK;
     });
 }

@@ -104,6 +104,10 @@ struct crt_scene {
     // sums hold (crt_variance): samples so far of the frame the flag has been on for since sample 0; valid = the last render call had it
     crtk::DevBuf<float> accum_q;
     FrameMark var;
+    // CRT_FLAG_HALF_BUFFERS: the sums of the even and of the odd samples (6 planes of nslots, allocated when the flag is first used) and
+    // what they hold (crt_half_buffers), by var's rules: valid = the last render call had the flag, and so had every range since sample 0
+    crtk::DevBuf<float> accum_h;
+    FrameMark half;
     // crt_render_adaptive: per pixel slot its sample count, the compacted list of the slots that take the next pass and its counter
     // (uncached, agent-scope atomics only: crt_adaptive.hip), and the pinned word the counter is copied to once per pass
     crtk::DevBuf<uint32_t> ad_nsamp, ad_list;
@@ -176,6 +180,16 @@ inline int sums_check(const char* who, const crt_scene* sc, const void* out)
     if (!sc || !out) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (!sc->var.valid) return fail(CRT_ERR_INVALID_ARG, w + ": no render with CRT_FLAG_VARIANCE on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
     if (sc->var.samples < 2) return fail(CRT_ERR_INVALID_ARG, w + ": fewer than 2 samples accumulated (one sample has no variance)");
+    return CRT_OK;
+}
+
+// What crt_half_buffers needs of the handle: half sums of at least two samples of a frame with CRT_FLAG_HALF_BUFFERS
+inline int halves_check(const char* who, const crt_scene* sc, const void* out_a, const void* out_b)
+{
+    const std::string w(who);
+    if (!sc || (!out_a && !out_b)) return fail(CRT_ERR_INVALID_ARG, w + ": null argument (a scene and at least one of the two buffers)");
+    if (!sc->half.valid) return fail(CRT_ERR_INVALID_ARG, w + ": no render with CRT_FLAG_HALF_BUFFERS on the handle yet, or the last render (or a range of the frame in flight) was submitted without it");
+    if (sc->half.samples < 2) return fail(CRT_ERR_INVALID_ARG, w + ": fewer than 2 samples accumulated (the half of the odd samples is empty)");
     return CRT_OK;
 }
 

@@ -104,6 +104,24 @@ template <bool VAR> __device__ __forceinline__ void fold_samples_n(const AParams
 }
 // every slot takes the whole chunk (the frame kernels); fold_samples_n with a count of its own per slot: a sparse frame
 template <bool VAR> __device__ __forceinline__ void fold_samples(const AParams& A, const uint32_t slot, F3& c, F3& q) { fold_samples_n<VAR>(A, slot, A.chunk_samples, c, q); }
+// fold_samples_n<true>'s sibling for CRT_FLAG_HALF_BUFFERS (contract: crt_half_buffers, include/crt.h): c and q exactly as there, and the
+// same quotients x into h0 (even k) or h1 (odd k), k = the sample's index in the FRAME: `parity` is that of the chunk's first sample
+// (AParams does not carry the chunk's start; the launch passes it).  A sibling and not a third template parameter of fold_samples_n, so
+// that the kernels built from that one keep their instructions.
+__device__ __forceinline__ void fold_samples_half(const AParams& A, const uint32_t slot, const uint32_t count, const uint32_t parity, F3& c, F3& q, F3& h0, F3& h1)
+{
+    const float fspp = (float)A.spp;
+    const Rad3* lp = A.L + slot;
+#pragma unroll 4
+    for (uint32_t s = 0; s < count; s++, lp += A.nslots) {
+        const Rad3 l = load_radiance(lp);
+        const float xx = l.x / fspp, xy = l.y / fspp, xz = l.z / fspp;
+        c.x = c.x + xx; c.y = c.y + xy; c.z = c.z + xz;
+        q.x = q.x + xx * xx; q.y = q.y + xy * xy; q.z = q.z + xz * xz;
+        if (((s + parity) & 1u) == 0u) { h0.x = h0.x + xx; h0.y = h0.y + xy; h0.z = h0.z + xz; }
+        else { h1.x = h1.x + xx; h1.y = h1.y + xy; h1.z = h1.z + xz; }
+    }
+}
 
 // the variance of the mean from the sums c and q (contract: crt_variance, include/crt.h); rr = (fs / fn)^2
 __device__ __forceinline__ float variance_of(const float c, const float q, const float fn, const float rr)

@@ -136,10 +136,14 @@ enum {
                                     device has plenty of.  Ignored with CRT_FLAG_STATS, by the fallback pipeline, and when the sample range
                                     is no longer than the window, and switched off for the call by CRT_FLAG_VARIANCE (the ring keeps
                                     no per-path radiance to square: crt_radiance_storage then reports ring_samples = 0) */
-    CRT_FLAG_VARIANCE = 32u      /* keep, beside the frame's sum, the per-pixel sum of squares of the samples on the scene handle:
+    CRT_FLAG_VARIANCE = 32u,     /* keep, beside the frame's sum, the per-pixel sum of squares of the samples on the scene handle:
                                     crt_variance reads the variance of the frame's mean from it.  The frame is bit for bit the frame without
                                     the flag.  Switches the commit ring of CRT_FLAG_BOUNDED_RADIANCE (and of the CRT_COMMIT_RING_LOG2 test
                                     hook) off for the call, as CRT_FLAG_STATS does.  Cleared by crt_multi_render (no gather for the buffer) */
+    CRT_FLAG_HALF_BUFFERS = 64u  /* keep, beside c and q, the sums of the even and of the odd samples of every pixel on the scene handle:
+                                    crt_half_buffers reads two independent half-sample frames from them.  Implies CRT_FLAG_VARIANCE: the call
+                                    behaves as if both were set (commit ring off included); frame, c and q are bit for bit those of
+                                    CRT_FLAG_VARIANCE alone.  Cleared by crt_multi_render, as CRT_FLAG_VARIANCE is */
 };
 
 typedef struct {
@@ -305,6 +309,28 @@ int crt_preview_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_st
 int crt_variance(crt_scene* scene, float* out_var, uint32_t* samples_done);
 /* d_var: a device buffer on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
 int crt_variance_device(crt_scene* scene, void* d_var, void* hip_stream, uint32_t* samples_done);
+
+/* Half-frame buffers (CRT_FLAG_HALF_BUFFERS): the frame as two independent estimates, one from the even and one from the odd samples of
+ * every pixel -- what an error estimate of a filtered frame needs (Rousselle et al. 2012; crt_filter_select below).  With the flag,
+ * crt_render, crt_render_device, crt_render_range and crt_render_range_device keep, beside c and q of the crt_variance contract, two more
+ * sums per pixel slot and channel on the scene handle (6 planes of the shard's slots, uncached, allocated when the flag is first used).
+ * With S = params->spp, x_k = L_k / (float)S (the very quotient the frame adds) and k the sample's index IN THE FRAME (not in the chunk
+ * or in the range):
+ *   h0 = h0 + x_k   for even k          h1 = h1 + x_k   for odd k          from +0.0f, in sample order, one IEEE fp32 add each
+ * carried across chunks and progressive ranges as q is.  With n = samples accumulated so far, n_a = (n + 1) / 2 and n_b = n / 2
+ * (integer divisions: the even and the odd samples among 0 .. n - 1), per channel:
+ *   out_a = h0 * ((float)S / (float)n_a)          out_b = h1 * ((float)S / (float)n_b)
+ * one fp32 division and one multiplication, as in crt_preview: the means of the two halves.  Layout: crt_variance's (row-major, or the
+ * shard's compact tiles with CRT_FLAG_TILED_OUTPUT; padding slots +0.0f), 3 floats per pixel.  Either output may be NULL, not both.
+ * Reads the sums only.  *samples_done (optional) receives n.  c is not h0 + h1 in fp32 (the sums differ in order by design); the mean
+ * of the halves weighted by n_a and n_b agrees with the frame's mean to rounding.
+ * CRT_ERR_INVALID_ARG, checked before any device call, the handle untouched: a null scene, or both buffers null; no render with the
+ * flag on the handle yet; the last render (or any range of the frame in flight, from sample 0 on) was submitted without the flag;
+ * n < 2 (the odd half is empty).  crt_render_adaptive, crt_render_map and crt_render_planned keep no halves: after them the call is
+ * refused. */
+int crt_half_buffers(crt_scene* scene, float* out_a, float* out_b, uint32_t* samples_done);
+/* d_a, d_b: device buffers on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
+int crt_half_buffers_device(crt_scene* scene, void* d_a, void* d_b, void* hip_stream, uint32_t* samples_done);
 
 /* Variance-driven adaptive sampling: one frame in which pixel p receives samples 0 .. n_p - 1 of its S = params->spp samples, n_p chosen
  * per pixel by a stop criterion on the running sums of the crt_variance contract.  Sample k of pixel p is the path it is in crt_render's
@@ -893,6 +919,61 @@ int crt_upsample(int device, const crt_upsample_params* params, const crt_upsamp
  * (the call then counts the fallback pixels and synchronizes the stream to read them and the timer).  Outputs must not overlap inputs. */
 int crt_upsample_device(int device, const crt_upsample_params* params, const crt_upsample_low* dev_low, const crt_upsample_guides* dev_guides,
                         void* d_out_color, void* d_out_variance, void* d_out_rgb, void* hip_stream, crt_upsample_info* info);
+
+/* Error-estimated filter selection: per pixel, the one of K filtered candidates whose error, estimated against an independent half
+ * frame, is smallest (Rousselle et al. 2012).  The caller renders with CRT_FLAG_HALF_BUFFERS, applies every candidate filter k to half
+ * A and to half B (crt_half_buffers), and passes the halves, the variance of ONE half's mean (2 x crt_variance) and the 2 K filtered
+ * images.  An image operation like the denoisers: no scene handle, row-major images, 3 floats per pixel.  With a = half_a, b = half_b,
+ * v = half_variance, fa_k = filtered_a[k], fb_k = filtered_b[k], all in fp32, every * + - / one IEEE operation, no FMA:
+ *  1 per pixel and candidate, per channel:
+ *      da = fa_k - b;  db = fb_k - a;  t = (da * da - v) + (db * db - v)
+ *    then  e_k = ((t_x + t_y) + t_z) / 6.0f;  an e_k that is not finite (NaN, +-inf) becomes +inf.
+ *    (fa_k - b is the half filter's error plus b's noise, which is independent of fa_k: the square overstates the squared error by v.)
+ *  2 smoothing, separable, in-image taps only, r = error_radius:
+ *      H_k(x, y) = sum over dx = -r .. r ascending of e_k(x + dx, y), from +0.0f
+ *      E_k(x, y) = (sum over dy = -r .. r ascending of H_k(x, y + dy), from +0.0f) / (float)(nx * ny)
+ *    nx, ny: the taps inside the image along each axis.
+ *  3 choice:  best = 0;  for k = 1 .. K - 1:  if (E_k < E_best) best = k.  Ties, NaN and all +inf stay with the lower index.
+ *    out_choice = best;  out_error = E_best.
+ *  4 blend, s = blend_radius: over the in-image pixels of the (2 s + 1)^2 window, m_k = the number that chose k, m = their total;
+ *      o = +0.0f;  for ascending k with m_k > 0:  o = o + ((float)m_k / (float)m) * ((fa_k + fb_k) * 0.5f)      (per channel)
+ *    a candidate nobody in the window chose contributes nothing (not 0 x its value).  out_mean = o; out_rgb = the frame's tone map of o.
+ * info->chosen[k]: the pixels with out_choice = k.  crt_filter_select_defaults fills error_radius 3, blend_radius 1, n_candidates 2
+ * (sizes 0); the radii are untuned beyond docs/experiments.md, "Half buffers and filter selection".
+ * Scratch (the _device form): crt_filter_select_scratch_bytes(width, height) bytes, 16-byte aligned: the choice map between the two
+ * kernels.
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null params or inputs; a size of 0; n_candidates outside 1 .. 4; error_radius
+ * above 8; blend_radius above 4; a null half_a, half_b, half_variance or filtered image below n_candidates; neither out_mean nor
+ * out_rgb; a null, small or misaligned scratch buffer.  A side longer than 2^24 pixels or more than 2^31 thread blocks of 32 x 8
+ * pixels: CRT_ERR_UNSUPPORTED. */
+#define CRT_SELECT_MAX_CANDIDATES 4
+typedef struct {
+    uint32_t width, height;
+    uint32_t n_candidates;   /* K: 1 .. 4 */
+    uint32_t error_radius;   /* r: 0 .. 8 */
+    uint32_t blend_radius;   /* s: 0 .. 4 */
+} crt_filter_select_params;
+typedef struct {
+    const float* half_a; const float* half_b;     /* crt_half_buffers */
+    const float* half_variance;                   /* the variance of one half's mean: 2 x crt_variance */
+    const float* filtered_a[CRT_SELECT_MAX_CANDIDATES]; /* filter k applied to half_a ... */
+    const float* filtered_b[CRT_SELECT_MAX_CANDIDATES]; /* ... and to half_b; entries k >= n_candidates are not read */
+} crt_filter_select_inputs;
+typedef struct {
+    float total_ms;                               /* HIP-event time of the call's two kernels on its stream */
+    uint64_t chosen[CRT_SELECT_MAX_CANDIDATES];   /* pixels per candidate */
+} crt_filter_select_info;
+int crt_filter_select_defaults(crt_filter_select_params* params);
+int crt_filter_select_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+/* host buffers; allocates and frees its own device memory on `device`; out_choice (W x H bytes), out_error (W x H floats) and info are
+ * optional, one of out_mean and out_rgb is required */
+int crt_filter_select(int device, const crt_filter_select_params* params, const crt_filter_select_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                      uint8_t* out_choice, float* out_error, crt_filter_select_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then counts the choices and synchronizes the stream to read them and the timer).  Outputs must not overlap inputs. */
+int crt_filter_select_device(int device, const crt_filter_select_params* params, const crt_filter_select_inputs* dev_in, void* d_out_mean,
+                             void* d_out_rgb, void* d_out_choice, void* d_out_error, void* d_scratch, uint64_t scratch_bytes, void* hip_stream,
+                             crt_filter_select_info* info);
 
 /* ------------------------------------------------------------------------
  * Multi-device rendering in ONE process.  The reference picks device 0 and stops there
