@@ -21,6 +21,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 from util import assert_bits, restated_sums
@@ -387,40 +388,25 @@ def test_adaptive_device_form_on_a_stream_matches_host_form(renders):
     r = renders[name]
     host = gpu_adaptive(r, name)
     check_frame(host, restated(name), "host form")
-    H_ = util.hip_runtime()
     eye, iv, fov = util.camera(name)
-    ptrs, stream = {}, C.c_void_p()
-    sizes = {"rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "var": W * H * 12}
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert H_.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert H_.hipMemset(p, 0x55, size) == 0          # (every output value must be written)
-        assert H_.hipStreamCreate(C.byref(stream)) == 0
+    # (every output value must be written: the buffers are filled with 0x55)
+    with DeviceBuffers({"rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "var": W * H * 12}, stream=True) as d:
+        ptrs, stream = d.ptrs, C.c_void_p(d.stream)
         cam, prm, ap = r._cam(eye, iv, fov), r._params(width=W, height=H), crt.api._adaptive_params(**AD)
         info = capi.AdaptiveInfo()
         capi.check(capi.lib().crt_render_adaptive_device(r._h, C.byref(cam), C.byref(prm), C.byref(ap), C.c_void_p(ptrs["rgb"]), C.c_void_p(ptrs["mean"]),
                                                          C.c_void_p(ptrs["samples"]), C.c_void_p(ptrs["var"]), stream, C.byref(info)),
                    "crt_render_adaptive_device")
-        assert H_.hipStreamSynchronize(stream) == 0
-        out = dict(rgb=np.zeros((H, W, 3), dtype=np.uint8), mean=np.zeros((H, W, 3), dtype=F), samples=np.zeros((H, W), dtype=np.uint32),
-                   var=np.zeros((H, W, 3), dtype=F))
-        for n, a in out.items():
-            assert H_.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+        d.synchronize()
+        out = dict(rgb=d.download("rgb", (H, W, 3), np.uint8), mean=d.download("mean", (H, W, 3), F), samples=d.download("samples", (H, W), np.uint32),
+                   var=d.download("var", (H, W, 3), F))
         check_frame(dict(rgb=out["rgb"], mean=out["mean"], samples=out["samples"], variance=out["var"], info=info.as_dict()), restated(name), "device form")
         # without info, without the optional outputs, mean only
-        assert H_.hipMemset(C.c_void_p(ptrs["mean"]), 0x55, sizes["mean"]) == 0
+        d.fill("mean")
         capi.check(capi.lib().crt_render_adaptive_device(r._h, C.byref(cam), C.byref(prm), C.byref(ap), None, C.c_void_p(ptrs["mean"]), None, None, stream,
                                                          None), "crt_render_adaptive_device")
-        assert H_.hipStreamSynchronize(stream) == 0
-        assert H_.hipMemcpy(out["mean"].ctypes.data, C.c_void_p(ptrs["mean"]), out["mean"].nbytes, 2) == 0
-        assert_bits(out["mean"], host["mean"], "device form, mean only")
-    finally:
-        if stream.value:
-            H_.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H_.hipFree(C.c_void_p(p))
+        d.synchronize()
+        assert_bits(d.download("mean", out=out["mean"]), host["mean"], "device form, mean only")
 
 
 @pytest.mark.gpu

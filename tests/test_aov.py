@@ -13,6 +13,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
 
 NAMES = ("albedo", "normal", "depth", "coverage", "tri", "material")
@@ -305,7 +306,7 @@ def test_aov_device_form_on_a_stream_matches_host_form(renders):
     r = renders[name]
     want = run_aov(r, name, 3, w, h)
     eye, iv, fov = util.camera(name)
-    with util.DeviceBuffers({n: capi.AOV_BUFFERS[n] for n in NAMES}, w, h) as d:
+    with DeviceBuffers.image({n: capi.AOV_BUFFERS[n] for n in NAMES}, w, h) as d:
         assert r.run_view_aov_device(eye, iv, fov, d.ptrs, stream=d.stream, want_info=False, width=w, height=h) is None
         d.synchronize()
         util.assert_same(d.fetch(NAMES), want, NAMES, "device form")

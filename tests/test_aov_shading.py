@@ -14,6 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import test_aov as aov
 import util
 
@@ -298,7 +299,7 @@ def test_shading_device_form_on_a_stream_matches_host_form(renders):
     assert (want["emission"] != 0).any()
     eye, iv, fov = util.camera(name)
     tables = dict(capi.AOV_BUFFERS, **capi.AOV_SHADING_BUFFERS)
-    with util.DeviceBuffers({n: tables[n] for n in want}, w, h) as d:
+    with DeviceBuffers.image({n: tables[n] for n in want}, w, h) as d:
         r.set_spp(3)
         assert r.run_view_aov_shading_device(eye, iv, fov, {n: d.ptrs[n] for n in NAMES}, first_ptrs={n: d.ptrs[n] for n in ("normal", "material")},
                                              stream=d.stream, want_info=False, width=w, height=h) is None

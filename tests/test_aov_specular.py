@@ -15,6 +15,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 
@@ -395,7 +396,7 @@ def test_aov_specular_device_form_on_a_stream_between_progressive_ranges(renders
     r.set_spp(3)
     one = r.run_view(eye, iv, fov, width=w, height=h).copy()
     one_mean = r.mean_buffer.copy()
-    with util.DeviceBuffers({n: capi.AOV_SPECULAR_BUFFERS[n] for n in NAMES}, w, h) as d:
+    with DeviceBuffers.image({n: capi.AOV_SPECULAR_BUFFERS[n] for n in NAMES}, w, h) as d:
         assert r.run_view_range(eye, iv, fov, 0, 2, width=w, height=h) is None
         assert r.run_view_aov_specular_device(eye, iv, fov, d.ptrs, max_bounces=2, stream=d.stream, want_info=False, width=w, height=h) is None
         d.synchronize()

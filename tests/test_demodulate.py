@@ -12,6 +12,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import test_temporal as T
 import util
@@ -279,54 +280,39 @@ def test_device_forms_on_a_stream(offset):
     color, albedo, emission, variance = synthetic(w, h, 5, floor)
     want_irr, want_var = restated_demodulate(color, albedo, emission, variance, floor)
     want_rgb, want_mean = restated_modulate(want_irr, albedo, emission, floor)
-    H = util.hip_runtime()
     names = ("color", "albedo", "emission", "variance", "irr", "ivar", "mean", "rgb")
-    ptrs = {}
-    stream = C.c_void_p()
-    try:
-        for k in names:
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), (n + 4) * 4) == 0
-            assert H.hipMemset(p, 0x55, (n + 4) * 4) == 0
-            ptrs[k] = p.value
-        at = {k: ptrs[k] + (offset if k == "rgb" else 4 * offset) for k in names}
+    with DeviceBuffers({k: (n + 4) * 4 for k in names}, stream=True) as d:
+        ptrs, stream = d.ptrs, d.stream
+        off = {k: offset if k == "rgb" else 4 * offset for k in names}
+        at = {k: ptrs[k] + off[k] for k in names}
         for k, a in (("color", color), ("albedo", albedo), ("emission", emission), ("variance", variance)):
-            assert H.hipMemcpy(C.c_void_p(at[k]), a.ctypes.data, n * 4, 1) == 0  # hipMemcpyHostToDevice
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+            d.upload(k, a, offset=off[k])
         assert crt.demodulate_device(w, h, at["color"], at["albedo"], at["irr"], emission_ptr=at["emission"], variance_ptr=at["variance"],
-                                     out_variance_ptr=at["ivar"], albedo_floor=floor, stream=stream.value, want_info=False) is None
+                                     out_variance_ptr=at["ivar"], albedo_floor=floor, stream=stream, want_info=False) is None
         assert crt.modulate_device(w, h, at["irr"], at["albedo"], at["mean"], out_rgb_ptr=at["rgb"], emission_ptr=at["emission"], albedo_floor=floor,
-                                   stream=stream.value, want_info=False) is None
-        assert H.hipStreamSynchronize(stream) == 0
+                                   stream=stream, want_info=False) is None
+        d.synchronize()
 
         def fetch(k, dtype=F):
-            a = np.zeros((h, w, 3), dtype=dtype)
-            assert H.hipMemcpy(a.ctypes.data, C.c_void_p(at[k]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            return a
+            return d.download(k, (h, w, 3), dtype, offset=off[k])
 
         assert_bits(fetch("irr"), want_irr, "device irradiance")
         assert_bits(fetch("ivar"), want_var, "device variance")
         assert_bits(fetch("mean"), want_mean, "device mean")
         assert np.array_equal(fetch("rgb", np.uint8), want_rgb)
         # nothing written past either end of an output
-        edge = np.zeros(n + 4, dtype=np.uint32)
         for k in ("irr", "ivar", "mean"):
-            assert H.hipMemcpy(edge.ctypes.data, C.c_void_p(ptrs[k]), edge.nbytes, 2) == 0
+            edge = d.download(k, n + 4, np.uint32)
             assert (edge[:offset] == 0x55555555).all() and (edge[offset + n:] == 0x55555555).all(), k
         # NULL emission and variance, one output of modulate, with the timer (the calls synchronize the stream)
-        info = crt.demodulate_device(w, h, at["color"], at["albedo"], at["irr"], albedo_floor=floor, stream=stream.value)
+        info = crt.demodulate_device(w, h, at["color"], at["albedo"], at["irr"], albedo_floor=floor, stream=stream)
         assert info["total_ms"] > 0
         irr2 = restated_demodulate(color, albedo, albedo_floor=floor)
         assert_bits(fetch("irr"), irr2, "device irradiance, no emission")
-        info = crt.modulate_device(w, h, at["irr"], at["albedo"], None, out_rgb_ptr=at["rgb"], albedo_floor=floor, stream=stream.value)
+        info = crt.modulate_device(w, h, at["irr"], at["albedo"], None, out_rgb_ptr=at["rgb"], albedo_floor=floor, stream=stream)
         assert info["total_ms"] > 0
         assert np.array_equal(fetch("rgb", np.uint8), restated_modulate(irr2, albedo, albedo_floor=floor)[0])
         assert_bits(fetch("mean"), want_mean, "device mean untouched")
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
 
 
 # ---- the chain ----

@@ -14,6 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 
@@ -279,51 +280,33 @@ def test_denoise_device_form_on_a_stream_matches_host_form(renders):
     name, w, h, it = "veach-mis", 100, 70, 4
     _, mean, g = frame_and_guides(renders[name], name, w, h, 4)
     want_rgb, want_mean = crt.denoise(mean, iterations=it, **g)
-    H = util.hip_runtime()
-    ptrs = {}
-    stream = C.c_void_p()
     scratch_bytes = crt.denoise_scratch_bytes(w, h)
-    sizes = {"color": mean.nbytes, "albedo": g["albedo"].nbytes, "normal": g["normal"].nbytes, "depth": g["depth"].nbytes,
-             "out_mean": w * h * 12, "out_rgb": w * h * 3, "scratch": scratch_bytes}
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the filter)
-        for n, a in (("color", mean), ("albedo", g["albedo"]), ("normal", g["normal"]), ("depth", g["depth"])):
-            assert H.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+    host = {"color": mean, "albedo": g["albedo"], "normal": g["normal"], "depth": g["depth"]}
+    # (every output value must be written by the filter: what is not uploaded is filled with 0x55)
+    with DeviceBuffers({**host, "out_mean": w * h * 12, "out_rgb": w * h * 3, "scratch": scratch_bytes}, stream=True) as d:
+        ptrs = d.ptrs
 
         def run(want_info, out_mean=True, out_rgb=True):
             return crt.denoise_device(w, h, ptrs["color"], ptrs["out_mean"] if out_mean else None, ptrs["out_rgb"] if out_rgb else None,
                                       ptrs["scratch"], scratch_bytes, albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"],
-                                      depth_ptr=ptrs["depth"], iterations=it, stream=stream.value, want_info=want_info)
+                                      depth_ptr=ptrs["depth"], iterations=it, stream=d.stream, want_info=want_info)
 
         def fetch():
-            m, r = np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=np.uint8)
-            assert H.hipMemcpy(m.ctypes.data, C.c_void_p(ptrs["out_mean"]), m.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            assert H.hipMemcpy(r.ctypes.data, C.c_void_p(ptrs["out_rgb"]), r.nbytes, 2) == 0
-            return m, r
+            return d.download("out_mean", (h, w, 3), F), d.download("out_rgb", (h, w, 3), np.uint8)
 
         assert run(False) is None
-        assert H.hipStreamSynchronize(stream) == 0
+        d.synchronize()
         m, r = fetch()
         assert_bits(m, want_mean, "device form")
         assert np.array_equal(r, want_rgb)
         # one output only, with the timer (the call synchronizes the stream)
-        assert H.hipMemset(C.c_void_p(ptrs["out_mean"]), 0x55, sizes["out_mean"]) == 0
-        assert H.hipMemset(C.c_void_p(ptrs["out_rgb"]), 0x55, sizes["out_rgb"]) == 0
+        d.fill("out_mean")
+        d.fill("out_rgb")
         info = run(True, out_rgb=False)
         assert info["passes"] == it and info["total_ms"] > 0, info
         m, r = fetch()
         assert_bits(m, want_mean, "device form, mean only")
         assert (r == 0x55).all()
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
 
 
 @pytest.mark.gpu

@@ -14,6 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 
@@ -418,55 +419,36 @@ def test_nlm_device_form_on_a_stream_matches_host_form(renders):
     kw = dict(radius=4, patch=2, k=0.6)
     _, mean, variance, g = frame_and_guides(renders[name], name, w, h, 4)
     want_rgb, want_mean, want_var = crt.denoise_nlm(mean, variance, want_variance=True, **kw, **g)
-    H = util.hip_runtime()
-    ptrs = {}
-    stream = C.c_void_p()
     scratch_bytes = crt.denoise_nlm_scratch_bytes(w, h)
     host = {"color": mean, "variance": variance, "albedo": g["albedo"], "normal": g["normal"], "depth": g["depth"]}
-    sizes = {n: a.nbytes for n, a in host.items()}
-    sizes.update({"out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4, "scratch": scratch_bytes})
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the filter)
-        for n, a in host.items():
-            assert H.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+    outs = {"out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4}
+    # (every output value must be written by the filter: what is not uploaded is filled with 0x55)
+    with DeviceBuffers({**host, **outs, "scratch": scratch_bytes}, stream=True) as d:
+        ptrs = d.ptrs
 
         def run(want_info, out_mean=True, out_rgb=True, out_var=True):
             return crt.denoise_nlm_device(w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"] if out_mean else None,
                                           ptrs["out_rgb"] if out_rgb else None, ptrs["out_var"] if out_var else None, ptrs["scratch"],
                                           scratch_bytes, albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"],
-                                          stream=stream.value, want_info=want_info, **kw)
+                                          stream=d.stream, want_info=want_info, **kw)
 
         def fetch():
-            m, r, v = np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=np.uint8), np.zeros((h, w), dtype=F)
-            assert H.hipMemcpy(m.ctypes.data, C.c_void_p(ptrs["out_mean"]), m.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            assert H.hipMemcpy(r.ctypes.data, C.c_void_p(ptrs["out_rgb"]), r.nbytes, 2) == 0
-            assert H.hipMemcpy(v.ctypes.data, C.c_void_p(ptrs["out_var"]), v.nbytes, 2) == 0
-            return m, r, v
+            return d.download("out_mean", (h, w, 3), F), d.download("out_rgb", (h, w, 3), np.uint8), d.download("out_var", (h, w), F)
 
         assert run(False) is None
-        assert H.hipStreamSynchronize(stream) == 0
+        d.synchronize()
         m, r, v = fetch()
         assert_bits(m, want_mean, "device form")
         assert_bits(v, want_var, "device form, variance")
         assert np.array_equal(r, want_rgb)
         # the mean only, with the timer (the call synchronizes the stream)
-        for n in ("out_mean", "out_rgb", "out_var"):
-            assert H.hipMemset(C.c_void_p(ptrs[n]), 0x55, sizes[n]) == 0
+        for n in outs:
+            d.fill(n)
         info = run(True, out_rgb=False, out_var=False)
         assert info["passes"] == 1 and info["total_ms"] > 0, info
         m, r, v = fetch()
         assert_bits(m, want_mean, "device form, mean only")
         assert (r == 0x55).all() and (v.view(np.uint32) == 0x55555555).all()
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
 
 
 @pytest.mark.gpu

@@ -14,8 +14,8 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
-import own_runtime
 import util
 
 F = np.float32
@@ -377,23 +377,20 @@ def test_device_form_on_a_stream():
     names = ["a", "b", "v"] + ["fa%d" % k for k in range(K)] + ["fb%d" % k for k in range(K)]
     table = {n: (3, F) for n in names}
     table.update({"mean": (3, F), "rgb": (3, np.uint8), "error": (1, F), "choice": (1, np.uint8), "scratch": (1, F)})
-    with own_runtime.DeviceBuffers(table, w, h) as d:
+    with DeviceBuffers.image(table, w, h) as d:
         for n, x in zip(names, [a, b, v] + fa + fb):
-            assert d.H.hipMemcpy(C.c_void_p(d.ptrs[n]), x.ctypes.data, x.nbytes, 1) == 0  # hipMemcpyHostToDevice
+            d.upload(n, x)
         assert crt.filter_select_scratch_bytes(w, h) <= d.nbytes("scratch")
         args = (w, h, d.ptrs["a"], d.ptrs["b"], d.ptrs["v"], [d.ptrs["fa%d" % k] for k in range(K)], [d.ptrs["fb%d" % k] for k in range(K)])
         none = crt.filter_select_device(*args, d.ptrs["mean"], d.ptrs["rgb"], d.ptrs["scratch"], d.nbytes("scratch"), out_choice_ptr=d.ptrs["choice"],
                                         out_error_ptr=d.ptrs["error"], error_radius=r, blend_radius=s, stream=d.stream, want_info=False)
         assert none is None
         d.synchronize()
-        got = d.fetch(("mean", "error"))
-        rgb, gchoice = np.zeros((h, w, 3), dtype=np.uint8), np.zeros((h, w), dtype=np.uint8)
-        assert d.H.hipMemcpy(rgb.ctypes.data, C.c_void_p(d.ptrs["rgb"]), rgb.nbytes, 2) == 0
-        assert d.H.hipMemcpy(gchoice.ctypes.data, C.c_void_p(d.ptrs["choice"]), gchoice.nbytes, 2) == 0
+        got = d.fetch(("mean", "error", "rgb", "choice"))
         info = crt.filter_select_device(*args, None, d.ptrs["rgb"], d.ptrs["scratch"], d.nbytes("scratch"), error_radius=r, blend_radius=s, stream=d.stream)
     assert_bits(got["mean"], mean, "device form mean")
     assert_bits(got["error"], error, "device form error")
-    assert np.array_equal(rgb, O.tonemap(mean)) and np.array_equal(gchoice, choice)
+    assert np.array_equal(got["rgb"], O.tonemap(mean)) and np.array_equal(got["choice"], choice)
     assert info["chosen"] == chosen and info["total_ms"] > 0
 
 

@@ -14,7 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
-import own_runtime
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
 from util import assert_bits, restated_sums
 
@@ -269,7 +269,7 @@ def test_halves_device_form_on_a_stream(renders):
     want_a, want_b = restated_halves(L, spp)
     eye, iv, fov = util.camera(name)
     table = {"rgb": (3, np.uint8), "mean": (3, F), "a": (3, F), "b": (3, F)}
-    with own_runtime.DeviceBuffers(table, W, H) as d:
+    with DeviceBuffers.image(table, W, H) as d:
         r.set_spp(spp)
         r.extra_flags = capi.FLAG_HALF_BUFFERS
         try:

@@ -13,13 +13,11 @@ Sizes.  A launch without the commit ring has 64 cursor shards of roundup64(ceil(
                         64 shards of 64 slots x 1 100 samples = 70 400 items = 68 spans and 768 items, 22 of them beyond the frame's slots;
                         the window is at most half the ring, 512 x 64 items
 CRT_ORDER_WINDOW=1000 is smaller than every one of these shards and no whole number of spans; 1 << 20 is larger than all of them."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import cudaraytracing_amd as crt
-from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
 
 pytestmark = pytest.mark.gpu
@@ -49,36 +47,13 @@ def _frame(r, name, w, h):
     return rgb, util.bits(r.mean_buffer).copy(), {k: r.stats[k] for k in COUNTERS}
 
 
-def _hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
-
-
 def _shard_frame(r, name, w, h, rank, world):
     """the same for the compact tiles of rank / world, outputs in device memory (run_view_device; with stats the call synchronizes)"""
-    H = _hip_runtime()
     eye, iv, fov = util.camera(name)
     slots = crt.shard_slots(w, h, rank, world)
-    rgb, mean = np.zeros((slots, 3), dtype=np.uint8), np.zeros((slots, 3), dtype=np.float32)
-    ptrs = []
-    try:
-        for a in (rgb, mean):
-            q = C.c_void_p()
-            assert H.hipMalloc(C.byref(q), a.nbytes) == 0
-            ptrs.append(q.value)
-        st = r.run_view_device(eye, iv, fov, ptrs[0], ptrs[1], None, rank=rank, world=world, tiled=True, want_stats=True, width=w, height=h)
-        for a, q in zip((rgb, mean), ptrs):
-            assert H.hipMemcpy(a.ctypes.data, C.c_void_p(q), a.nbytes, 2) == 0   # hipMemcpyDeviceToHost (after the null stream's work)
-    finally:
-        for q in ptrs:
-            H.hipFree(C.c_void_p(q))
+    with DeviceBuffers({"rgb": slots * 3, "mean": slots * 12}) as d:
+        st = r.run_view_device(eye, iv, fov, d.ptrs["rgb"], d.ptrs["mean"], None, rank=rank, world=world, tiled=True, want_stats=True, width=w, height=h)
+        rgb, mean = d.download("rgb", (slots, 3), np.uint8), d.download("mean", (slots, 3), np.float32)   # (after the null stream's work)
     return rgb, util.bits(mean), {k: st[k] for k in COUNTERS}
 
 

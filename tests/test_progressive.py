@@ -16,6 +16,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 from util import assert_bits, restated_sums
@@ -292,32 +293,22 @@ def test_device_forms_on_a_stream(renders, name):
     _, p, prgb = restated_preview(L, S, 3)
     r = renders[name]
     r.set_spp(S)
-    lib, H = capi.lib(), util.hip_runtime()
+    lib = capi.lib()
     eye, iv, fov = util.camera(name)
     cam = r._cam(eye, iv, fov)
     prm = r._params(rank=rank, world=world, flags=capi.FLAG_TILED_OUTPUT, width=w, height=h)
     slots = crt.shard_slots(w, h, rank, world)
-    sizes = {"rgb": slots * 3, "mean": slots * 12}
-    ptrs, stream = {}, C.c_void_p()
+    with DeviceBuffers({"rgb": slots * 3, "mean": slots * 12}, stream=True) as d:
+        ptrs, stream = d.ptrs, C.c_void_p(d.stream)
 
-    def fill():
-        for k, size in sizes.items():
-            assert H.hipMemset(C.c_void_p(ptrs[k]), 0x55, size) == 0
+        def fill():
+            d.fill("rgb")
+            d.fill("mean")
 
-    def fetch():
-        assert H.hipStreamSynchronize(stream) == 0
-        rgb, mean = np.zeros((slots, 3), dtype=np.uint8), np.zeros((slots, 3), dtype=F)
-        for a, k in ((rgb, "rgb"), (mean, "mean")):
-            assert H.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[k]), a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
-        return rgb, mean
+        def fetch():
+            d.synchronize()
+            return d.download("rgb", (slots, 3), np.uint8), d.download("mean", (slots, 3), F)
 
-    try:
-        for k, size in sizes.items():
-            q = C.c_void_p()
-            assert H.hipMalloc(C.byref(q), size) == 0
-            ptrs[k] = q.value
-        fill()
-        assert H.hipStreamCreate(C.byref(stream)) == 0
         capi.check(lib.crt_render_range_device(r._h, C.byref(cam), C.byref(prm), 0, 3, None, None, stream, None), "crt_render_range_device")
         done = C.c_uint32()
         capi.check(lib.crt_preview_device(r._h, C.c_void_p(ptrs["rgb"]), C.c_void_p(ptrs["mean"]), stream, C.byref(done)), "crt_preview_device")
@@ -353,11 +344,6 @@ def test_device_forms_on_a_stream(renders, name):
         assert np.array_equal(rgb3, one_rgb)
         assert_bits(mean3, shard_of(omean, w, h, rank, world)[0], "last range against the oracle")
         assert np.array_equal(rgb3, shard_of(orgb, w, h, rank, world)[0])
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for q in ptrs.values():
-            H.hipFree(C.c_void_p(q))
 
 
 SOUP = dict(scale=1e12, w=48, h=36, S=4, n=2, seed=5, p_rr=0.6, lsn=2)

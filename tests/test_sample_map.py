@@ -22,6 +22,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 from util import assert_bits, restated_sums
@@ -394,45 +395,6 @@ def test_map_of_the_adaptive_frames_samples_is_the_adaptive_frame(renders, name,
     assert_bits(got["variance"], ad["variance"], "map of the adaptive samples: variance")
 
 
-class DeviceBuffers:
-    """Raw device buffers through the HIP runtime the library is linked against: {name: bytes}, each filled with 0x55"""
-
-    def __init__(self, sizes, stream=False):
-        self.H = util.hip_runtime()
-        self.ptrs, self.sizes, self.stream = {}, dict(sizes), C.c_void_p()
-        try:
-            for n, size in sizes.items():
-                p = C.c_void_p()
-                assert self.H.hipMalloc(C.byref(p), size) == 0
-                self.ptrs[n] = p.value
-                assert self.H.hipMemset(p, 0x55, size) == 0          # (every output value must be written)
-            if stream:
-                assert self.H.hipStreamCreate(C.byref(self.stream)) == 0
-        except BaseException:
-            self.free()
-            raise
-
-    def upload(self, name, a):
-        assert a.nbytes == self.sizes[name]
-        assert self.H.hipMemcpy(C.c_void_p(self.ptrs[name]), a.ctypes.data, a.nbytes, 1) == 0   # hipMemcpyHostToDevice
-
-    def download(self, name, a):
-        assert a.nbytes == self.sizes[name]
-        assert self.H.hipMemcpy(a.ctypes.data, C.c_void_p(self.ptrs[name]), a.nbytes, 2) == 0   # hipMemcpyDeviceToHost
-        return a
-
-    def sync(self):
-        assert self.H.hipStreamSynchronize(self.stream) == 0
-
-    def free(self):
-        if self.stream.value:
-            self.H.hipStreamDestroy(self.stream)
-            self.stream = C.c_void_p()
-        for p in self.ptrs.values():
-            self.H.hipFree(C.c_void_p(p))
-        self.ptrs = {}
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SCENES)
 def test_map_shards_are_the_full_frame_at_their_pixels(renders, name):
@@ -444,15 +406,12 @@ def test_map_shards_are_the_full_frame_at_their_pixels(renders, name):
     paths, padding = 0, 0
     for rank in range(world):
         slots = crt.shard_slots(W, H, rank, world)
-        d = DeviceBuffers({"map": W * H * 4, "rgb": slots * 3, "mean": slots * 12, "samples": slots * 4, "variance": slots * 12})
-        try:
-            d.upload("map", ragged_map())                 # the whole image's map, also for a shard
+        # (the whole image's map, also for a shard)
+        with DeviceBuffers({"map": ragged_map(), "rgb": slots * 3, "mean": slots * 12, "samples": slots * 4, "variance": slots * 12}) as d:
             info = r.run_view_map_device(eye, iv, fov, d.ptrs["map"], d.ptrs, rank=rank, world=world, width=W, height=H)
-            assert d.H.hipStreamSynchronize(None) == 0
-            rgb, mean = d.download("rgb", np.zeros((slots, 3), dtype=np.uint8)), d.download("mean", np.zeros((slots, 3), dtype=F))
-            samples, var = d.download("samples", np.zeros(slots, dtype=np.uint32)), d.download("variance", np.zeros((slots, 3), dtype=F))
-        finally:
-            d.free()
+            d.synchronize()                               # (no stream of its own: the null stream)
+            rgb, mean = d.download("rgb", (slots, 3), np.uint8), d.download("mean", (slots, 3), F)
+            samples, var = d.download("samples", slots, np.uint32), d.download("variance", (slots, 3), F)
         paths += info["paths"]
         pixels = 0
         for s in range(slots):
@@ -480,32 +439,25 @@ def test_map_device_form_on_a_stream_matches_host_form(renders):
     host = gpu_map(r, name, ragged_map())
     check_frame(host, want, "host form")
     eye, iv, fov = util.camera(name)
-    d = DeviceBuffers({"map": W * H * 4, "rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "variance": W * H * 12}, stream=True)
-    try:
-        d.upload("map", ragged_map())
-        info = r.run_view_map_device(eye, iv, fov, d.ptrs["map"], d.ptrs, stream=d.stream.value, width=W, height=H)
-        d.sync()
-        got = dict(rgb=d.download("rgb", np.zeros((H, W, 3), dtype=np.uint8)), mean=d.download("mean", np.zeros((H, W, 3), dtype=F)),
-                   samples=d.download("samples", np.zeros((H, W), dtype=np.uint32)), variance=d.download("variance", np.zeros((H, W, 3), dtype=F)),
-                   info=info)
-        check_frame(got, want, "device form", launches=1)
+    def frame(d, info):
+        return dict(rgb=d.download("rgb", (H, W, 3), np.uint8), mean=d.download("mean", (H, W, 3), F), samples=d.download("samples", (H, W), np.uint32),
+                    variance=d.download("variance", (H, W, 3), F), info=info)
+
+    with DeviceBuffers({"map": ragged_map(), "rgb": W * H * 3, "mean": W * H * 12, "samples": W * H * 4, "variance": W * H * 12}, stream=True) as d:
+        info = r.run_view_map_device(eye, iv, fov, d.ptrs["map"], d.ptrs, stream=d.stream, width=W, height=H)
+        d.synchronize()
+        check_frame(frame(d, info), want, "device form", launches=1)
         # without info, without the optional outputs, mean only
-        assert d.H.hipMemset(C.c_void_p(d.ptrs["mean"]), 0x55, W * H * 12) == 0
-        assert r.run_view_map_device(eye, iv, fov, d.ptrs["map"], {"mean": d.ptrs["mean"]}, stream=d.stream.value, want_info=False, width=W,
+        d.fill("mean")
+        assert r.run_view_map_device(eye, iv, fov, d.ptrs["map"], {"mean": d.ptrs["mean"]}, stream=d.stream, want_info=False, width=W,
                                      height=H) is None
-        d.sync()
-        assert_bits(d.download("mean", np.zeros((H, W, 3), dtype=F)), host["mean"], "device form, mean only")
+        d.synchronize()
+        assert_bits(d.download("mean", (H, W, 3), F), host["mean"], "device form, mean only")
         # the planned frame's device form
-        assert d.H.hipMemset(C.c_void_p(d.ptrs["mean"]), 0x55, W * H * 12) == 0
-        info = r.run_view_planned_device(eye, iv, fov, d.ptrs, stream=d.stream.value, width=W, height=H, **PLAN)
-        d.sync()
-        planned = restated(name, "planned")
-        got = dict(rgb=d.download("rgb", np.zeros((H, W, 3), dtype=np.uint8)), mean=d.download("mean", np.zeros((H, W, 3), dtype=F)),
-                   samples=d.download("samples", np.zeros((H, W), dtype=np.uint32)), variance=d.download("variance", np.zeros((H, W, 3), dtype=F)),
-                   info=info)
-        check_frame(got, planned, "planned, device form", launches=2)
-    finally:
-        d.free()
+        d.fill("mean")
+        info = r.run_view_planned_device(eye, iv, fov, d.ptrs, stream=d.stream, width=W, height=H, **PLAN)
+        d.synchronize()
+        check_frame(frame(d, info), restated(name, "planned"), "planned, device form", launches=2)
 
 
 @pytest.mark.gpu

@@ -13,6 +13,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import test_temporal as T
 import util
@@ -428,58 +429,40 @@ def test_clamped_device_form_on_a_stream_matches_host_form(renders):
     clamp = {"radius": 2, "gamma": 0.75}
     want_rgb, want_c, want_v, want_h, want_info = crt.temporal(c1, cam1, prev=prev, prev_camera=cam0, return_info=True, clamp=clamp)
     assert 100 <= want_info["clamped"] < want_info["reprojected"] - 100
-    Hr = util.hip_runtime()
-    ptrs = {}
-    stream = C.c_void_p()
     host = {"cur_" + k: v for k, v in c1.items()}
     host.update({"prev_" + k: v for k, v in prev.items()})
-    sizes = {n: a.nbytes for n, a in host.items()}
-    sizes.update({"out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4, "out_rgb": w * h * 3})
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert Hr.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert Hr.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the kernel)
-        for n, a in host.items():
-            assert Hr.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        assert Hr.hipStreamCreate(C.byref(stream)) == 0
+    outs = {"out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4, "out_rgb": w * h * 3}
+    # (every output value must be written by the kernel: what is not uploaded is filled with 0x55)
+    with DeviceBuffers({**host, **outs}, stream=True) as d:
+        ptrs = d.ptrs
 
         def run(want_info, variance=True, out_rgb=True):
             cur_p = {k: ptrs["cur_" + k] for k in c1 if variance or k != "variance"}
             prev_p = {k: ptrs["prev_" + k] for k in prev if variance or k != "variance"}
             return crt.temporal_device(w, h, cam1, cur_p, ptrs["out_color"], ptrs["out_hist"], out_variance_ptr=ptrs["out_var"] if variance else None,
-                                       out_rgb_ptr=ptrs["out_rgb"] if out_rgb else None, prev_ptrs=prev_p, prev_camera=cam0, stream=stream.value,
+                                       out_rgb_ptr=ptrs["out_rgb"] if out_rgb else None, prev_ptrs=prev_p, prev_camera=cam0, stream=d.stream,
                                        want_info=want_info, clamp=clamp)
 
         def fetch():
-            c, v = np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=F)
-            hh, r = np.zeros((h, w), dtype=F), np.zeros((h, w, 3), dtype=np.uint8)
-            for a, n in ((c, "out_color"), (v, "out_var"), (hh, "out_hist"), (r, "out_rgb")):
-                assert Hr.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
-            return c, v, hh, r
+            return (d.download("out_color", (h, w, 3), F), d.download("out_var", (h, w, 3), F), d.download("out_hist", (h, w), F),
+                    d.download("out_rgb", (h, w, 3), np.uint8))
 
         assert run(False) is None
-        assert Hr.hipStreamSynchronize(stream) == 0
+        d.synchronize()
         c, v, hh, r = fetch()
         assert_bits(c, want_c, "device form")
         assert_bits(v, want_v, "device form, variance")
         assert_bits(hh, want_h, "device form, history")
         assert np.array_equal(r, want_rgb)
         # colour and history only, with the timer and the counts (the call synchronizes the stream)
-        for n in ("out_color", "out_var", "out_hist", "out_rgb"):
-            assert Hr.hipMemset(C.c_void_p(ptrs[n]), 0x55, sizes[n]) == 0
+        for n in outs:
+            d.fill(n)
         info = run(True, variance=False, out_rgb=False)
         assert info["reprojected"] == want_info["reprojected"] and info["clamped"] == want_info["clamped"] and info["total_ms"] > 0, info
         c, v, hh, r = fetch()
         assert_bits(c, want_c, "device form, colour only")
         assert_bits(hh, want_h, "device form, colour only: history")
         assert (r == 0x55).all() and (v.view(np.uint32) == 0x55555555).all()
-    finally:
-        if stream.value:
-            Hr.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            Hr.hipFree(C.c_void_p(p))
 
 
 @pytest.mark.gpu

@@ -16,6 +16,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import test_temporal as T
 import test_temporal_clamp as TC
@@ -711,55 +712,39 @@ def test_moments_device_forms_on_a_stream_match_host_forms(renders):
     est = dict(min_history=3, radius=2, of_mean=1, history_cap=3.5)
     want_e, want_einfo = crt.variance_estimate(want_m1, want_m2, want_h, normal=g1["normal"], depth=g1["depth"], return_info=True, **est)
     assert 100 <= want_einfo["spatial"] < w * h - 100
-    Hr = util.hip_runtime()
-    ptrs = {}
-    stream = C.c_void_p()
     host = {"cur_" + k: v for k, v in c1.items()}
     host.update({"prev_" + k: v for k, v in prev.items()})
     host.update({"prev_m1": pm["m1"], "prev_m2": pm["m2"]})
-    sizes = {n: a.nbytes for n, a in host.items()}
     outs = {"out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4, "out_rgb": w * h * 3, "out_m1": w * h * 12, "out_m2": w * h * 12,
             "out_est": w * h * 12}
-    sizes.update(outs)
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert Hr.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert Hr.hipMemset(p, 0x55, size) == 0          # (every output value must be written by the kernels)
-        for n, a in host.items():
-            assert Hr.hipMemcpy(C.c_void_p(ptrs[n]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
-        assert Hr.hipStreamCreate(C.byref(stream)) == 0
+    # (every output value must be written by the kernels: what is not uploaded is filled with 0x55)
+    with DeviceBuffers({**host, **outs}, stream=True) as d:
+        ptrs = d.ptrs
 
         def run(want_info, variance=True, out_rgb=True):
             cur_p = {k: ptrs["cur_" + k] for k in c1 if variance or k != "variance"}
             prev_p = {k: ptrs["prev_" + k] for k in prev if variance or k != "variance"}
             i1 = crt.temporal_device(w, h, cam1, cur_p, ptrs["out_color"], ptrs["out_hist"], out_variance_ptr=ptrs["out_var"] if variance else None,
-                                     out_rgb_ptr=ptrs["out_rgb"] if out_rgb else None, prev_ptrs=prev_p, prev_camera=cam0, stream=stream.value,
+                                     out_rgb_ptr=ptrs["out_rgb"] if out_rgb else None, prev_ptrs=prev_p, prev_camera=cam0, stream=d.stream,
                                      want_info=want_info, clamp=clamp,
                                      moments={"m1": ptrs["prev_m1"], "m2": ptrs["prev_m2"], "out_m1": ptrs["out_m1"], "out_m2": ptrs["out_m2"]})
             # the estimate reads what the call before it wrote, in stream order
             i2 = crt.variance_estimate_device(w, h, ptrs["out_m1"], ptrs["out_m2"], ptrs["out_hist"], ptrs["out_est"], normal_ptr=ptrs["cur_normal"],
-                                              depth_ptr=ptrs["cur_depth"], stream=stream.value, want_info=want_info, **est)
+                                              depth_ptr=ptrs["cur_depth"], stream=d.stream, want_info=want_info, **est)
             return i1, i2
 
         def fetch():
-            got = {}
-            for n, size in outs.items():
-                a = np.zeros(size, dtype=np.uint8)
-                assert Hr.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), size, 2) == 0  # hipMemcpyDeviceToHost
-                got[n] = a if n == "out_rgb" else a.view(F)
-            return got
+            return {n: d.download(n, size, np.uint8) if n == "out_rgb" else d.download(n, size // 4, F) for n, size in outs.items()}
 
         assert run(False) == (None, None)
-        assert Hr.hipStreamSynchronize(stream) == 0
+        d.synchronize()
         got = fetch()
         for n, want in (("out_color", want_c), ("out_var", want_v), ("out_hist", want_h), ("out_m1", want_m1), ("out_m2", want_m2), ("out_est", want_e)):
             assert_bits(got[n].reshape(want.shape), want, "device form: " + n)
         assert np.array_equal(got["out_rgb"].reshape(h, w, 3), want_rgb)
         # without the variance pair and the RGB8, with the timers and the counts (each call synchronizes the stream)
         for n in outs:
-            assert Hr.hipMemset(C.c_void_p(ptrs[n]), 0x55, sizes[n]) == 0
+            d.fill(n)
         i1, i2 = run(True, variance=False, out_rgb=False)
         assert i1["reprojected"] == want_info["reprojected"] and i1["clamped"] == want_info["clamped"] and i1["total_ms"] > 0, i1
         assert i2["spatial"] == want_einfo["spatial"] and i2["total_ms"] > 0, i2
@@ -767,11 +752,6 @@ def test_moments_device_forms_on_a_stream_match_host_forms(renders):
         for n, want in (("out_color", want_c), ("out_hist", want_h), ("out_m1", want_m1), ("out_m2", want_m2), ("out_est", want_e)):
             assert_bits(got[n].reshape(want.shape), want, "device form, colour only: " + n)
         assert (got["out_rgb"] == 0x55).all() and (got["out_var"].view(np.uint32) == 0x55555555).all()
-    finally:
-        if stream.value:
-            Hr.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            Hr.hipFree(C.c_void_p(p))
 
 
 def render_frame_without_variance(r, cam, width, height, spp, seed):

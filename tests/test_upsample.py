@@ -14,6 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
 
@@ -455,10 +456,10 @@ def test_device_form_on_a_stream():
     low_table = {"color": (3, F), "variance": (3, F), "albedo": (3, F), "normal": (3, F), "depth": (1, F)}
     # (rgb: 3 bytes per pixel in a buffer of 12: what lies behind them must stay as it was)
     full_table = {"albedo": (3, F), "normal": (3, F), "depth": (1, F), "out_color": (3, F), "out_variance": (3, F), "out_rgb": (3, np.uint32)}
-    with util.DeviceBuffers(low_table, lw, lh) as dl, util.DeviceBuffers(full_table, w, h) as dh:
+    with DeviceBuffers.image(low_table, lw, lh) as dl, DeviceBuffers.image(full_table, w, h) as dh:
         for d, src in ((dl, low), (dh, guides)):
             for k, a in src.items():
-                assert d.H.hipMemcpy(C.c_void_p(d.ptrs[k]), a.ctypes.data, a.nbytes, 1) == 0  # hipMemcpyHostToDevice
+                d.upload(k, a)
         guide_ptrs = {k: dh.ptrs[k] for k in GUIDES}
 
         def run(want_info, color=True, variance=True, rgb=True):

@@ -14,6 +14,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
 from util import assert_bits, restated_sums
 
@@ -290,37 +291,22 @@ def test_variance_device_form_on_a_stream_matches_host_form(renders):
     name, w, h, spp = "cornell-box", 100, 70, 4
     r = renders[name]
     rgb0, mean0, var0 = gpu_frame(r, name, w, h, spp)
-    H = util.hip_runtime()
     eye, iv, fov = util.camera(name)
-    ptrs, stream = {}, C.c_void_p()
-    sizes = {"rgb": w * h * 3, "mean": w * h * 12, "var": w * h * 12}
-    try:
-        for n, size in sizes.items():
-            p = C.c_void_p()
-            assert H.hipMalloc(C.byref(p), size) == 0
-            ptrs[n] = p.value
-            assert H.hipMemset(p, 0x55, size) == 0          # (every output value must be written)
-        assert H.hipStreamCreate(C.byref(stream)) == 0
+    # (every output value must be written: the buffers are filled with 0x55)
+    with DeviceBuffers({"rgb": w * h * 3, "mean": w * h * 12, "var": w * h * 12}, stream=True) as d:
         r.set_spp(spp)
         r.extra_flags = capi.FLAG_VARIANCE
         try:
-            r.run_view_device(eye, iv, fov, ptrs["rgb"], ptrs["mean"], stream=stream.value, want_stats=False, width=w, height=h)
+            r.run_view_device(eye, iv, fov, d.ptrs["rgb"], d.ptrs["mean"], stream=d.stream, want_stats=False, width=w, height=h)
         finally:
             r.extra_flags = 0
         done = C.c_uint32()
-        capi.check(capi.lib().crt_variance_device(r._h, C.c_void_p(ptrs["var"]), stream, C.byref(done)), "crt_variance_device")
+        capi.check(capi.lib().crt_variance_device(r._h, C.c_void_p(d.ptrs["var"]), C.c_void_p(d.stream), C.byref(done)), "crt_variance_device")
         assert done.value == spp
-        assert H.hipStreamSynchronize(stream) == 0
-        rgb, mean, var = np.zeros((h, w, 3), dtype=np.uint8), np.zeros((h, w, 3), dtype=F), np.zeros((h, w, 3), dtype=F)
-        for a, n in ((rgb, "rgb"), (mean, "mean"), (var, "var")):
-            assert H.hipMemcpy(a.ctypes.data, C.c_void_p(ptrs[n]), a.nbytes, 2) == 0  # hipMemcpyDeviceToHost
+        d.synchronize()
+        rgb, mean, var = d.download("rgb", (h, w, 3), np.uint8), d.download("mean", (h, w, 3), F), d.download("var", (h, w, 3), F)
         assert np.array_equal(rgb, rgb0) and np.array_equal(mean.view(np.uint32), mean0.view(np.uint32))
         assert_bits(var, var0, "device form")
-    finally:
-        if stream.value:
-            H.hipStreamDestroy(stream)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
 
 
 @pytest.mark.gpu

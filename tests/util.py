@@ -1,5 +1,4 @@
-"""Shared helpers for the test-suite (scene setup for both the product and the oracle, bit comparisons, the oracle's ray log, PFM files,
-device buffers through the HIP runtime)."""
+"""Shared helpers for the test-suite (scene setup for both the product and the oracle, bit comparisons, the oracle's ray log, PFM files)."""
 import ctypes as C
 import functools
 import os
@@ -7,7 +6,6 @@ import os
 import numpy as np
 
 import cudaraytracing_amd as crt
-from cudaraytracing_amd import _capi as capi
 import oracle_lib as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -106,70 +104,6 @@ def primary_rays_of(osc, eye, iv, fov, lsn, width, height, spp, crop=None, seed=
     # (pixel, sample) order: with p_rr = 0 each path is its camera ray and that vertex's next-event samples, so the camera rays are
     # the log's closest-hit rays from the eye, one path after the other
     return prim[:, 0:3].copy(), prim[:, 3:6].copy(), prim[:, 6].copy(), prim[:, 7].astype(np.int32), (ch, cw)
-
-
-def hip_runtime():
-    """The HIP runtime libcrt.so is linked against (already mapped into the process), through ctypes."""
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    H.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    H.hipStreamSynchronize.argtypes = [C.c_void_p]
-    H.hipStreamDestroy.argtypes = [C.c_void_p]
-    return H
-
-
-class DeviceBuffers:
-    """with DeviceBuffers({name: (channels, dtype)}, w, h) as d: one device buffer per name for a w x h image of 4-byte values, filled with
-    0x55 (every value must be written by what is tested), and a stream.  d.ptrs: {name: raw device pointer}, d.stream: the stream's
-    handle; everything is released on exit."""
-
-    def __init__(self, table, w, h):
-        self.H, self.table, self.w, self.h = hip_runtime(), table, w, h
-        self.ptrs, self._stream = {}, C.c_void_p()
-
-    def nbytes(self, name):
-        return self.w * self.h * self.table[name][0] * 4
-
-    def __enter__(self):
-        try:
-            for n in self.table:
-                p = C.c_void_p()
-                assert self.H.hipMalloc(C.byref(p), self.nbytes(n)) == 0
-                self.ptrs[n] = p.value
-                self.fill(n, 0x55)
-            assert self.H.hipStreamCreate(C.byref(self._stream)) == 0
-        except BaseException:
-            self.__exit__()
-            raise
-        self.stream = self._stream.value
-        return self
-
-    def __exit__(self, *exc):
-        if self._stream.value:
-            self.H.hipStreamDestroy(self._stream)
-        for p in self.ptrs.values():
-            self.H.hipFree(C.c_void_p(p))
-
-    def fill(self, name, byte):
-        assert self.H.hipMemset(C.c_void_p(self.ptrs[name]), byte, self.nbytes(name)) == 0
-
-    def synchronize(self):
-        assert self.H.hipStreamSynchronize(self._stream) == 0
-
-    def fetch(self, names):
-        """{name: (h, w, 3) or (h, w) array} of the buffers' contents"""
-        out = {}
-        for n in names:
-            ch, dt = self.table[n]
-            out[n] = np.zeros((self.h, self.w, ch) if ch == 3 else (self.h, self.w), dtype=dt)
-            assert self.H.hipMemcpy(out[n].ctypes.data, self.ptrs[n], self.nbytes(n), 2) == 0  # hipMemcpyDeviceToHost
-        return out
 
 
 def random_rays(name, n, seed):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of the first-hit AOV pass next to the frame: for each scene and spp, the host-clock time of crt_render_aov_device (all six
 buffers) and of crt_render_device at the same camera and params, each around the device call plus a synchronize, after a warm-up
-call; best of --reps.  Prints one JSON line.  Device buffers come from the HIP runtime libcrt.so is linked against (ctypes).
+call; best of --reps.  Prints one JSON line.  Device buffers come from cudaraytracing_amd/hipmem.py.
 
   python tools/aov_probe.py [--spp 16,64,512] [--scenes cornell-box,veach-mis] [--reps 3]
 
@@ -20,41 +20,36 @@ crt_render_aov_device in one process, the two taking turns: the HIP-event time o
   python tools/aov_probe.py --shading [--spp 64] [--reps 20]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
 from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 
-def hip_runtime():
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
+def image_buffers(a, table):
+    return hipmem.DeviceBuffers.image(table, a.width, a.height, stream=False)
 
 
-def specular(a, H, dev_alloc):
+def specular(a):
     """The two AOV passes side by side (see the module's text)."""
     w, h = a.width, a.height
-    ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
-    sptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_SPECULAR_BUFFERS.items()}
-    word = C.c_uint32()
+    first, second = image_buffers(a, capi.AOV_BUFFERS), image_buffers(a, capi.AOV_SPECULAR_BUFFERS)
+    ptrs, sptrs = first.ptrs, second.ptrs
+    word = np.zeros(1, dtype=np.uint32)
     us = []
     for _ in range(200):
-        H.hipDeviceSynchronize()
+        hipmem.device_synchronize()
         t0 = time.perf_counter()
-        H.hipMemcpy(C.addressof(word), C.c_void_p(ptrs["depth"]), 4, 2)  # hipMemcpyDeviceToHost
+        first.download("depth", out=word, offset=0)
         us.append((time.perf_counter() - t0) * 1e6)
     out = {"width": w, "height": h, "reps": a.reps, "sync_us": round(statistics.median(us[20:]), 2), "runs": []}
     spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
@@ -72,7 +67,7 @@ def specular(a, H, dev_alloc):
                 for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
                     for key, fn in (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, ptrs)),
                                     ("spec", lambda: r.run_view_aov_specular_device(t.eye_pos, iv, fov, sptrs, max_bounces=mb))):
-                        H.hipDeviceSynchronize()
+                        hipmem.device_synchronize()
                         t0 = time.perf_counter()
                         info = fn()
                         dt = (time.perf_counter() - t0) * 1e3
@@ -91,17 +86,17 @@ def specular(a, H, dev_alloc):
                 out["runs"].append(run)
                 print(json.dumps(run), file=sys.stderr, flush=True)
         r.free()
-    for p in list(ptrs.values()) + list(sptrs.values()):
-        H.hipFree(C.c_void_p(p))
+    first.free()
+    second.free()
     print(json.dumps(out), flush=True)
 
 
-def shading(a, H, dev_alloc):
+def shading(a):
     """--shading: crt_render_aov_shading_device (all eight buffers) beside crt_render_aov_device (its six), the two taking turns: the
     HIP-event time of each call, median and best of --reps.  One trace serves both structs, so the difference is the resolve's."""
     w, h = a.width, a.height
-    ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
-    sptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_SHADING_BUFFERS.items()}
+    first, second = image_buffers(a, capi.AOV_BUFFERS), image_buffers(a, capi.AOV_SHADING_BUFFERS)
+    ptrs, sptrs = first.ptrs, second.ptrs
     out = {"width": w, "height": h, "reps": a.reps, "runs": []}
     spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
     for name in a.scenes.split(","):
@@ -115,7 +110,7 @@ def shading(a, H, dev_alloc):
             for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
                 for key, fn in (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, ptrs)),
                                 ("shading", lambda: r.run_view_aov_shading_device(t.eye_pos, iv, fov, sptrs, first_ptrs=ptrs))):
-                    H.hipDeviceSynchronize()
+                    hipmem.device_synchronize()
                     info = fn()
                     if i >= 2:
                         ev[key].append(info["total_ms"])
@@ -127,8 +122,8 @@ def shading(a, H, dev_alloc):
             out["runs"].append(run)
             print(json.dumps(run), file=sys.stderr, flush=True)
         r.free()
-    for p in list(ptrs.values()) + list(sptrs.values()):
-        H.hipFree(C.c_void_p(p))
+    first.free()
+    second.free()
     print(json.dumps(out), flush=True)
 
 
@@ -144,20 +139,12 @@ def main():
     ap.add_argument("--shading", action="store_true", help="time crt_render_aov_shading_device beside crt_render_aov_device")
     a = ap.parse_args()
     w, h = a.width, a.height
-    H = hip_runtime()
-
-    def dev_alloc(nbytes):
-        p = C.c_void_p()
-        if H.hipMalloc(C.byref(p), nbytes) != 0:
-            raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-        return p.value
-
     if a.specular:
-        return specular(a, H, dev_alloc)
+        return specular(a)
     if a.shading:
-        return shading(a, H, dev_alloc)
-    rgb = dev_alloc(w * h * 3)
-    ptrs = {n: dev_alloc(w * h * ch * 4) for n, (ch, _) in capi.AOV_BUFFERS.items()}
+        return shading(a)
+    frame, aovs = hipmem.DeviceBuffers({"rgb": w * h * 3}), image_buffers(a, capi.AOV_BUFFERS)
+    rgb, ptrs = frame.ptrs["rgb"], aovs.ptrs
     out = {"width": w, "height": h, "reps": a.reps, "runs": []}
     for name in a.scenes.split(","):
         t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
@@ -169,10 +156,10 @@ def main():
         def timed(fn):
             best = None
             for i in range(a.reps + 1):  # (the first call warms up: allocations, code objects)
-                H.hipDeviceSynchronize()
+                hipmem.device_synchronize()
                 t0 = time.perf_counter()
                 fn()
-                H.hipDeviceSynchronize()
+                hipmem.device_synchronize()
                 dt = (time.perf_counter() - t0) * 1e3
                 if i > 0:
                     best = dt if best is None else min(best, dt)
@@ -189,8 +176,8 @@ def main():
                                 "rays": rays, "primary_Grays_per_s": round(rays / aov_ms / 1e6, 3)})
             print(json.dumps(out["runs"][-1]), file=sys.stderr, flush=True)
         r.free()
-    for p in [rgb] + list(ptrs.values()):
-        H.hipFree(C.c_void_p(p))
+    frame.free()
+    aovs.free()
     print(json.dumps(out), flush=True)
 
 

@@ -36,7 +36,6 @@ of crt_denoise, crt_denoise_var and crt_denoise_nlm (their defaults, first-hit g
   python tools/denoise_probe.py --nlm --error --ref-seed 7
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -45,21 +44,10 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
-from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 CACHE_SIDE_BYTES = 25 * 40 + 12   # per pixel and pass: 10 floats per tap, 3 floats written
 COMPULSORY_BYTES = 40 + 12
-
-
-def hip_runtime():
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
 
 
 def demodulated_error_table(a):
@@ -118,7 +106,7 @@ def demodulated_error_table(a):
     print(json.dumps(out), flush=True)
 
 
-def modulate_times(a, H):
+def modulate_times(a):
     """--demodulate: crt_demodulate_device (with variance) and crt_modulate_device (both outputs) beside ONE filter pass -- the
     difference of crt_denoise_device with two iterations and with one -- the four calls taking turns, on synthetic images.  The byte
     rate is that of the compulsory traffic: 72 B per pixel for demodulate with variance (four planes read, two written), 39 B for
@@ -133,16 +121,9 @@ def modulate_times(a, H):
                 "emission": np.where(rng.random((h, w, 3)) < 0.05, 100.0, 0.0).astype(np.float32), "variance": rng.random((h, w, 3)).astype(np.float32),
                 "normal": rng.random((h, w, 3)).astype(np.float32), "depth": (rng.random((h, w)) + 1).astype(np.float32)}
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(k, v.nbytes) for k, v in host.items()] + [("irr", n * 12), ("ivar", n * 12), ("out_mean", n * 12), ("out_rgb", n * 3),
-                                                                              ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "irr": n * 12, "ivar": n * 12, "out_mean": n * 12, "out_rgb": n * 3,
+                                    "scratch": scratch_bytes})
+        ptrs = dev.ptrs
         calls = {
             "demodulate": lambda: crt.demodulate_device(w, h, ptrs["color"], ptrs["albedo"], ptrs["irr"], emission_ptr=ptrs["emission"],
                                                         variance_ptr=ptrs["variance"], out_variance_ptr=ptrs["ivar"])["total_ms"],
@@ -164,8 +145,7 @@ def modulate_times(a, H):
                "modulate_TB_per_s": round(39 * n / (med["modulate"] * 1e-3) / 1e12, 3)}
         out["runs"].append(run)
         print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
     print(json.dumps(out), flush=True)
 
 
@@ -207,7 +187,7 @@ def nlm_error_table(a):
     print(json.dumps(out), flush=True)
 
 
-def nlm_times(a, H):
+def nlm_times(a):
     """--nlm: crt_denoise_var_device (3 iterations) and the two forms of crt_denoise_nlm_device, the three calls taking turns"""
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
     iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
@@ -221,16 +201,9 @@ def nlm_times(a, H):
         host = dict(r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth")), color=r.mean_buffer, variance=r.variance_buffer)
         r.free()
         scratch_bytes = max(crt.denoise_scratch_bytes(w, h), crt.denoise_nlm_scratch_bytes(w, h))
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_mean", w * h * 12), ("out_rgb", w * h * 3), ("out_var", w * h * 4),
-                                                                                    ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4,
+                                    "scratch": scratch_bytes})
+        ptrs = dev.ptrs
         common = dict(albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"])
         args = (w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["out_var"], ptrs["scratch"], scratch_bytes)
 
@@ -251,8 +224,7 @@ def nlm_times(a, H):
         run["shared_over_direct"] = round(run["nlm_shared_ms_median"] / run["nlm_direct_ms_median"], 4)
         out["runs"].append(run)
         print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
     if before is None:
         os.environ.pop("CRT_NLM_FORM", None)
     else:
@@ -324,11 +296,10 @@ def main():
         raise SystemExit("denoise_probe: no HIP device")
     if a.error:
         return nlm_error_table(a) if a.nlm else demodulated_error_table(a) if a.demodulate else error_table(a)
-    H = hip_runtime()
     if a.nlm:
-        return nlm_times(a, H)
+        return nlm_times(a)
     if a.demodulate:
-        return modulate_times(a, H)
+        return modulate_times(a)
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
     iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
     fov = crt.fov_to_radians(t.fov_y)
@@ -342,16 +313,9 @@ def main():
             host["variance"] = r.variance_buffer
         r.free()
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_mean", w * h * 12), ("out_rgb", w * h * 3), ("out_var", w * h * 4),
-                                                                                    ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4,
+                                    "scratch": scratch_bytes})
+        ptrs = dev.ptrs
 
         def call(iterations):
             return crt.denoise_device(w, h, ptrs["color"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes,
@@ -382,8 +346,7 @@ def main():
                             "var_ms_per_pass": round(med_var / it, 4), "var_over_plain": round(med_var / med, 4)})
             out["runs"].append(run)
             print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
     print(json.dumps(out), flush=True)
 
 

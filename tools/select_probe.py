@@ -39,20 +39,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
 from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 F = np.float32
 GUIDES = ("albedo", "normal", "depth")
-
-
-def hip_runtime():
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
 
 
 def emit(out, key, run):
@@ -76,7 +66,6 @@ def candidate(name, half, half_var, guides):
 
 
 def part_time(a, out):
-    H = hip_runtime()
     for size in a.sizes.split(","):
         w, h = (int(v) for v in size.split("x"))
         t, scene, cam = scene_view("cornell-box", w, h)
@@ -93,17 +82,9 @@ def part_time(a, out):
             for n in names[1:]:
                 host["f%s_%s" % (side, n)] = candidate(n, half[side], hv, guides)
         sel_scratch, dn_scratch = crt.filter_select_scratch_bytes(w, h), crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("mean", w * h * 12), ("rgb", w * h * 3), ("choice", w * h), ("error", w * h * 4),
-                                                                                    ("sel_scratch", sel_scratch), ("dn_scratch", dn_scratch)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            v = np.ascontiguousarray(v)
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "mean": w * h * 12, "rgb": w * h * 3, "choice": w * h, "error": w * h * 4,
+                                    "sel_scratch": sel_scratch, "dn_scratch": dn_scratch})
+        ptrs = dev.ptrs
 
         def fptr(side, n):
             return ptrs[side] if n == "none" else ptrs["f%s_%s" % (side, n)]
@@ -134,21 +115,15 @@ def part_time(a, out):
                                "chosen": info[k]["chosen"], "compulsory_bytes_per_pixel": compulsory,
                                "compulsory_TB_per_s": round(compulsory * w * h / (med * 1e-3) / 1e12, 4), "atrous_pass_ms_median": round(one_pass, 4),
                                "select_over_atrous_pass": round(med / one_pass, 3)})
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
 
 
 def part_flag(a, out):
-    H = hip_runtime()
     w, h = (int(v) for v in a.flag_size.split("x"))
     t, scene, cam = scene_view("cornell-box", w, h)
     r = crt.Render(scene, a.flag_spp, t.P_RR, t.light_sample_n)
-    bufs = {}
-    for name, nbytes in (("rgb", w * h * 3), ("mean", w * h * 12), ("a", w * h * 12), ("b", w * h * 12)):
-        p = C.c_void_p()
-        if H.hipMalloc(C.byref(p), nbytes) != 0:
-            raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-        bufs[name] = p.value
+    dev = hipmem.DeviceBuffers({"rgb": w * h * 3, "mean": w * h * 12, "a": w * h * 12, "b": w * h * 12})
+    bufs = dev.ptrs
     kinds = {"plain": 0, "variance": capi.FLAG_VARIANCE, "half_buffers": capi.FLAG_HALF_BUFFERS}
     runs, read_ms = {k: [] for k in kinds}, []
     import time
@@ -156,11 +131,11 @@ def part_flag(a, out):
         for kind, flags in kinds.items():
             r.extra_flags = flags
             st = r.run_view_device(*cam, bufs["rgb"], bufs["mean"])
-            H.hipDeviceSynchronize()
+            hipmem.device_synchronize()
             if kind == "half_buffers":
                 t0 = time.perf_counter()
                 capi.check(capi.lib().crt_half_buffers_device(r._h, C.c_void_p(bufs["a"]), C.c_void_p(bufs["b"]), None, None), "crt_half_buffers_device")
-                H.hipDeviceSynchronize()
+                hipmem.device_synchronize()
                 if i > 0:
                     read_ms.append((time.perf_counter() - t0) * 1e3)
             if i > 0:
@@ -173,8 +148,7 @@ def part_flag(a, out):
     run["crt_half_buffers_device_wall_ms"] = round(statistics.median(read_ms), 3)
     emit(out, "flag", run)
     r.free()
-    for p in bufs.values():
-        H.hipFree(C.c_void_p(p))
+    dev.free()
 
 
 def window_mean(e, r):

@@ -38,7 +38,6 @@ One JSON line per figure on stderr, one JSON document on stdout.
                                  [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments] [--demodulate]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -49,23 +48,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
-from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 F = np.float32
 COMPULSORY_BYTES = 44 + 48 + 31
 # per-frame camera moves: (step, the lookat point moves along)
 MOVES = {"cornell-box": ((20.0, 0.0, 10.0), True), "veach-mis": ((0.0, 0.1, 0.3), False)}
-
-
-def hip_runtime():
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
 
 
 def camera_at(t, scene, f):
@@ -87,7 +75,7 @@ def render_frame(r, cam, spp, seed, variance=True):
     return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
 
 
-def cost(a, H, out):
+def cost(a, out):
     scene = "cornell-box"
     t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
     for size in a.sizes.split(","):
@@ -101,16 +89,9 @@ def cost(a, H, out):
         host.update({"prev_" + k: v for k, v in prev.items()})
         host["albedo"] = g1["albedo"]
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_color", w * h * 12), ("out_var", w * h * 12), ("out_hist", w * h * 4),
-                                                                                    ("out_rgb", w * h * 3), ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4,
+                                    "out_rgb": w * h * 3, "scratch": scratch_bytes})
+        ptrs = dev.ptrs
 
         def call_temporal(clamp=None):
             return crt.temporal_device(w, h, cams[1], {k: ptrs["cur_" + k] for k in c1}, ptrs["out_color"], ptrs["out_hist"],
@@ -149,8 +130,7 @@ def cost(a, H, out):
                    "neighbourhood_bytes_per_pixel": (2 * r + 1) ** 2 * 12}
             out["clamp_cost"].append(run)
             print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
 
 
 def mse(x, ref):
@@ -214,7 +194,7 @@ def effect(a, out):
         print(json.dumps(out["clamp_best"]), file=sys.stderr, flush=True)
 
 
-def moments_cost(a, H, out):
+def moments_cost(a, out):
     scene = "cornell-box"
     t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
     for size in a.sizes.split(","):
@@ -228,17 +208,10 @@ def moments_cost(a, H, out):
         host.update({"prev_" + k: v for k, v in prev.items()})
         host.update({"prev_m1": c0["color"], "prev_m2": (c0["color"] * c0["color"]).astype(F), "albedo": g1["albedo"]})
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_color", w * h * 12), ("out_var", w * h * 12), ("out_hist", w * h * 4),
-                                                                                    ("out_rgb", w * h * 3), ("out_m1", w * h * 12), ("out_m2", w * h * 12),
-                                                                                    ("out_est", w * h * 12), ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4,
+                                    "out_rgb": w * h * 3, "out_m1": w * h * 12, "out_m2": w * h * 12,
+                                    "out_est": w * h * 12, "scratch": scratch_bytes})
+        ptrs = dev.ptrs
         planes = {"m1": ptrs["prev_m1"], "m2": ptrs["prev_m2"], "out_m1": ptrs["out_m1"], "out_m2": ptrs["out_m2"]}
 
         def call_temporal(clamp, moments):
@@ -280,8 +253,7 @@ def moments_cost(a, H, out):
                                                                                                                  "estimate_mixed")]})
         out["moments_cost"].append(run)
         print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
 
 
 def moments_effect(a, out):
@@ -389,13 +361,13 @@ def main():
         return
     if a.moments:                                            # (its own tables only: the others are the earlier sections')
         if not a.skip_cost:
-            moments_cost(a, hip_runtime(), out)
+            moments_cost(a, out)
         if not a.skip_effect:
             moments_effect(a, out)
         print(json.dumps(out), flush=True)
         return
     if not a.skip_cost:
-        cost(a, hip_runtime(), out)
+        cost(a, out)
     if not a.skip_effect:
         effect(a, out)
     print(json.dumps(out), flush=True)

@@ -27,7 +27,6 @@ One JSON line per figure on stderr, one JSON document on stdout.
                                  [--sigma-albedo 0.05,0.1,0.2,inf] [--skip-cost] [--skip-effect]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import statistics
@@ -39,25 +38,14 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
-from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 F = np.float32
 GUIDES = ("albedo", "normal", "depth")
 OUT_BYTES, GUIDE_BYTES, LOW_BYTES = 27, 28, 52
 
 
-def hip_runtime():
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    H = C.CDLL(path)
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
-    H.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return H
-
-
-def cost(a, H, out):
+def cost(a, out):
     scene = "cornell-box"
     t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
     cam = (t.eye_pos, crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up), crt.fov_to_radians(t.fov_y))
@@ -72,16 +60,9 @@ def cost(a, H, out):
         host.update({"full_" + k: v for k, v in full.items()})
         host["full_color"] = np.zeros((h, w, 3), dtype=F)  # what the denoiser pass filters: its time does not depend on the values
         scratch_bytes = crt.denoise_scratch_bytes(w, h)
-        ptrs = {}
-        for name, nbytes in [(n, v.nbytes) for n, v in host.items()] + [("out_color", w * h * 12), ("out_var", w * h * 12), ("out_rgb", w * h * 3),
-                                                                                    ("scratch", scratch_bytes)]:
-            p = C.c_void_p()
-            if H.hipMalloc(C.byref(p), nbytes) != 0:
-                raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-            ptrs[name] = p.value
-        for name, v in host.items():
-            if H.hipMemcpy(C.c_void_p(ptrs[name]), v.ctypes.data, v.nbytes, 1) != 0:  # hipMemcpyHostToDevice
-                raise RuntimeError("hipMemcpy failed")
+        dev = hipmem.DeviceBuffers({**host, "out_color": w * h * 12, "out_var": w * h * 12, "out_rgb": w * h * 3,
+                                    "scratch": scratch_bytes})
+        ptrs = dev.ptrs
 
         def call_upsample(radius):
             return crt.upsample_device(w, h, lw, lh, {k: ptrs["low_" + k] for k in low}, ptrs["out_color"], out_variance_ptr=ptrs["out_var"],
@@ -112,8 +93,7 @@ def cost(a, H, out):
                    "denoise_ms_per_pass_median": round(dn_pass, 4), "upsample_over_denoise_pass": round(med / dn_pass, 4)}
             out["cost"].append(run)
             print(json.dumps(run), file=sys.stderr, flush=True)
-        for p in ptrs.values():
-            H.hipFree(C.c_void_p(p))
+        dev.free()
 
 
 def mse(x, ref):
@@ -226,7 +206,7 @@ def main():
         raise SystemExit("upsample_probe: no HIP device")
     out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "sweep": []}
     if not a.skip_cost:
-        cost(a, hip_runtime(), out)
+        cost(a, out)
     if not a.skip_effect:
         effect(a, out)
     print(json.dumps(out), flush=True)

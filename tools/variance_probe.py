@@ -18,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
 from cudaraytracing_amd import _capi as capi  # noqa: E402
+from cudaraytracing_amd import hipmem  # noqa: E402
 
 
 def main():
@@ -30,18 +31,9 @@ def main():
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("variance_probe: no HIP device")
-    capi.lib()
-    with open("/proc/self/maps") as f:
-        H = C.CDLL(next(line.split()[-1] for line in f if "libamdhip64" in line))
-    H.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    H.hipFree.argtypes = [C.c_void_p]
     w, h = a.width, a.height
-    bufs = {}
-    for name, nbytes in (("rgb", w * h * 3), ("mean", w * h * 12), ("var", w * h * 12)):
-        p = C.c_void_p()
-        if H.hipMalloc(C.byref(p), nbytes) != 0:
-            raise RuntimeError("hipMalloc of %d bytes failed" % nbytes)
-        bufs[name] = p.value
+    dev = hipmem.DeviceBuffers({"rgb": w * h * 3, "mean": w * h * 12, "var": w * h * 12})
+    bufs = dev.ptrs
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
     r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
     iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
@@ -49,10 +41,10 @@ def main():
 
     def frame(flag):
         r.extra_flags = capi.FLAG_VARIANCE if flag else 0
-        H.hipDeviceSynchronize()
+        hipmem.device_synchronize()
         t0 = time.perf_counter()
         st = r.run_view_device(t.eye_pos, iv, fov, bufs["rgb"], bufs["mean"])
-        H.hipDeviceSynchronize()
+        hipmem.device_synchronize()
         return {"wall_ms": (time.perf_counter() - t0) * 1e3, "total_ms": st["total_ms"], "kernel_ms": st["kernel_ms"],
                 "rest_ms": st["total_ms"] - st["kernel_ms"]}
 
@@ -62,10 +54,10 @@ def main():
         for flag in (False, True):
             f = frame(flag)
             if flag:
-                H.hipDeviceSynchronize()
+                hipmem.device_synchronize()
                 t0 = time.perf_counter()
                 capi.check(capi.lib().crt_variance_device(r._h, C.c_void_p(bufs["var"]), None, None), "crt_variance_device")
-                H.hipDeviceSynchronize()
+                hipmem.device_synchronize()
                 f["read_ms"] = (time.perf_counter() - t0) * 1e3
             if i > 0:
                 runs[flag].append(f)
@@ -79,8 +71,7 @@ def main():
                     "plain_min_max": [round(min(f[key] for f in runs[False]), 3), round(max(f[key] for f in runs[False]), 3)]}
     out["crt_variance_device_wall_ms"] = round(statistics.median(read_ms), 3)
     r.free()
-    for p in bufs.values():
-        H.hipFree(C.c_void_p(p))
+    dev.free()
     print(json.dumps(out), flush=True)
 
 
