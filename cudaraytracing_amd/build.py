@@ -2,6 +2,7 @@
 
   lib/libcrt.so   HIP kernels (gfx950) + host layer + C ABI   (hipcc)
   lib/crt_cli     headless config.json -> PNG command line     (hipcc, links libcrt.so)
+  lib/render_host_check   tools/render_host_check.cpp, a GPU test's program   (likewise)
 
 The flags matter for bit parity with the CPU oracle: no FMA contraction, no
 fast-math, correctly rounded fp32 divide / sqrt on the device.
@@ -20,7 +21,7 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"] + os.environ.get("CRT_EXTRA_CXXFLAGS", "").split()
 DEVICE = ["--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 
-LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp"]
+LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp", "crt_host_render.cpp", "crt_host_capi.cpp"]
 LIB_DEPS = LIB_SOURCES + ["crt_path.h", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_item_order.h", "crt_internal.h", "crt_stages.h", "crt_filter_host.h", "crt_modulate.h", "crt_nlm.h", "crt_upsample.h", "crt_select.h", "crt_render.h", "crt_scene.h", "crt_scene_layout.h", "crt_fastdiv.h", "crt_device.h", "crt_trace.h", "crt_accel.h", "crt_detmath.h", "crt_host.hpp", "crt_png.h", "crt_jpeg.h", "crt_formats.h", "crt_image.h", "crt_bvh_build.h",
                           os.path.join("..", "..", "include", "crt.h")]
 # the units that see the render kernel's headers (crt_mega3.h / crt_path.h): a variant build with a -D that changes a shared layout compiles all of these (tools/ab_build.sh)
@@ -157,22 +158,32 @@ def build_lib(force=False, verbose=False):
     return LIB
 
 
-def build_cli(force=False, verbose=False):
-    src = os.path.join(CSRC, "crt_cli.cpp")
+def _build_program(src, exe, force, verbose):
+    """A host program on crt_host.hpp, linked against the libcrt.so beside it"""
     if not os.path.exists(src):
         return None
-    if not force and not _stale(CLI, ["crt_cli.cpp", "crt_host.hpp"]) and os.path.getmtime(CLI) >= os.path.getmtime(LIB):
-        return CLI
-    cmd = [HIPCC] + COMMON + [src, "-L" + LIBDIR, "-lcrt", "-Wl,-rpath,$ORIGIN", "-o", CLI]
+    if not force and os.path.exists(exe) and os.path.getmtime(exe) >= max(os.path.getmtime(f) for f in (src, os.path.join(CSRC, "crt_host.hpp"), LIB)):
+        return exe
+    cmd = [HIPCC] + COMMON + [src, "-L" + LIBDIR, "-lcrt", "-Wl,-rpath,$ORIGIN", "-o", exe]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)
-    return CLI
+    return exe
+
+
+def build_cli(force=False, verbose=False):
+    return _build_program(os.path.join(CSRC, "crt_cli.cpp"), CLI, force, verbose)
+
+
+def build_render_check(force=False, verbose=False):
+    """tools/render_host_check.cpp: crt::Render against the library calls it is made of (tests/test_host_layer.py runs it on a GPU)"""
+    return _build_program(os.path.join(HERE, "..", "tools", "render_host_check.cpp"), os.path.join(LIBDIR, "render_host_check"), force, verbose)
 
 
 def build_all(force=False, verbose=False):
     build_lib(force, verbose)
     build_cli(force, verbose)
+    build_render_check(force, verbose)
 
 
 if __name__ == "__main__":

@@ -65,6 +65,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -323,17 +324,23 @@ int main(int argc, char** argv)
         std::printf("triangles: %zu, BVH nodes: %zu, lights: %zu\n", scene.get_triangles().size(), scene.get_bvh().get_nodes_size(),
                     scene.get_light_objs().size());
         const bool multi = !devices.empty();
-        if (multi && !aov.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov renders on one device (not with --gpus / --devices)");
-        if (multi && !aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular renders on one device (not with --gpus / --devices)");
-        if (multi && !aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading renders on one device (not with --gpus / --devices)");
+        // The options that work on one device.  The first refusal that applies is the one reported, so the rows stand in the order of
+        // the refusals and refuse_on_many takes the next `count` of them where theirs stood among the other checks.
+        const struct { bool present; const char* what; } one_device[] = {
+            {!aov.empty(), "--aov renders on one device"}, {!aov_specular.empty(), "--aov-specular renders on one device"},
+            {!aov_shading.empty(), "--aov-shading renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
+            {!variance.empty(), "--variance reads one device's buffer"}, {denoise_var, "--denoise-variance filters on one device"},
+            {adaptive, "--adaptive renders on one device"}, {temporal != 0, "--temporal accumulates on one device"}, {upsample != 0, "--upsample runs on one device"},
+            {denoise_nlm, "--denoise-nlm filters on one device"}};
+        size_t row = 0;
+        auto refuse_on_many = [&](size_t count) {
+            for (; count-- > 0; row++)
+                if (multi && one_device[row].present) throw crt::Error(CRT_ERR_INVALID_ARG, std::string(one_device[row].what) + " (not with --gpus / --devices)");
+        };
+        refuse_on_many(3);
         if (demodulate && denoise.empty() && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--demodulate needs --denoise PATH or --temporal N");
         if (denoise_specular && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-specular needs --denoise PATH");
-        if (multi && !denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise filters on one device (not with --gpus / --devices)");
-        if (multi && !variance.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--variance reads one device's buffer (not with --gpus / --devices)");
-        if (multi && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance filters on one device (not with --gpus / --devices)");
-        if (multi && adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive renders on one device (not with --gpus / --devices)");
-        if (multi && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates on one device (not with --gpus / --devices)");
-        if (multi && upsample) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample runs on one device (not with --gpus / --devices)");
+        refuse_on_many(6);
         if (upsample_option && !upsample) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample-out and --upsample-guide-spp need --upsample FACTOR");
         if (upsample && upsample_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample needs --upsample-out PATH");
         if (upsample && (task.width % upsample || task.height % upsample))
@@ -343,7 +350,7 @@ int main(int argc, char** argv)
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
-        if (multi && denoise_nlm) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm filters on one device (not with --gpus / --devices)");
+        refuse_on_many(1);
         if (denoise_nlm && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm needs --denoise PATH");
         if (nlm_params && !denoise_nlm) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm-params needs --denoise-nlm");
         if (denoise_nlm && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is a filter of its own (not with --denoise-variance)");
@@ -375,6 +382,16 @@ int main(int argc, char** argv)
         render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u) | (denoise_select ? CRT_FLAG_HALF_BUFFERS : 0u));
         render.set_aov_shading(!aov_shading.empty());
         if (demodulate) render.set_demodulate(true);
+        // One output's files -- a PFM of 1 or 3 channels of floats, or with channels 0 a PNG of RGB8 -- are written, then their paths printed
+        struct OutFile { std::string path; uint32_t channels; const void* data; };
+        auto write_files = [&](const char* what, std::initializer_list<OutFile> files) {
+            for (const OutFile& f : files) {
+                const int rc = f.channels ? crt_write_pfm(f.path.c_str(), task.width, task.height, f.channels, (const float*)f.data)
+                                          : crt_write_png(f.path.c_str(), task.width, task.height, (const uint8_t*)f.data);
+                if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the ") + what + " failed: " + crt_last_error());
+            }
+            for (const OutFile& f : files) std::printf("%s\n", f.path.c_str());
+        };
         float inv_view[9];
         crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
         float fov_y = task.fov_y * (float)M_PI / 180; // src/main.cu:278
@@ -427,27 +444,17 @@ int main(int argc, char** argv)
         }
         render.save_frame_buffer(out.c_str());
         std::printf("%s\n", out.c_str());
-        if (!variance.empty()) {
-            const int rc = crt_write_pfm(variance.c_str(), task.width, task.height, 3, render.variance());
-            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the variance file failed: ") + crt_last_error());
-            std::printf("%s\n", variance.c_str());
-        }
+        if (!variance.empty()) write_files("variance file", {{variance, 3, render.variance()}});
         if (!adaptive_samples.empty()) {
             std::vector<float> ns((size_t)task.width * task.height);
             for (size_t k = 0; k < ns.size(); k++) ns[k] = (float)render.get_samples_buffer()[k];
-            const int rc = crt_write_pfm(adaptive_samples.c_str(), task.width, task.height, 1, ns.data());
-            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the samples file failed: ") + crt_last_error());
-            std::printf("%s\n", adaptive_samples.c_str());
+            write_files("samples file", {{adaptive_samples, 1, ns.data()}});
         }
         if (!aov.empty() || !aov_shading.empty() || !denoise.empty()) render.run_aov(task.eye_pos, inv_view, fov_y);
         if (!aov_shading.empty()) {
             const crt_aov_info& ai = render.last_aov_info();
             std::printf("aov-shading: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
-            const std::string pe = aov_shading + ".emission.pfm", pa = aov_shading + ".diffuse_albedo.pfm";
-            int rc = crt_write_pfm(pe.c_str(), task.width, task.height, 3, render.get_emission_buffer());
-            if (rc == CRT_OK) rc = crt_write_pfm(pa.c_str(), task.width, task.height, 3, render.get_diffuse_albedo_buffer());
-            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the shading AOV files failed: ") + crt_last_error());
-            std::printf("%s\n%s\n", pe.c_str(), pa.c_str());
+            write_files("shading AOV files", {{aov_shading + ".emission.pfm", 3, render.get_emission_buffer()}, {aov_shading + ".diffuse_albedo.pfm", 3, render.get_diffuse_albedo_buffer()}});
         }
         if (!aov.empty()) {
             const crt_aov_info& ai = render.last_aov_info();
@@ -461,28 +468,16 @@ int main(int argc, char** argv)
                 albedo[k] = to_u8(255.0f * unit_clamp(render.get_albedo_buffer()[k]));
                 normal[k] = to_u8(255.0f * unit_clamp((render.get_normal_buffer()[k] + 1.0f) / 2.0f));
             }
-            const std::string pa = aov + "_albedo.png", pn = aov + "_normal.png", pd = aov + "_depth.pfm";
-            int rc = crt_write_png(pa.c_str(), task.width, task.height, albedo.data());
-            if (rc == CRT_OK) rc = crt_write_png(pn.c_str(), task.width, task.height, normal.data());
-            if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_depth_buffer());
-            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the AOV files failed: ") + crt_last_error());
-            std::printf("%s\n%s\n%s\n", pa.c_str(), pn.c_str(), pd.c_str());
+            write_files("AOV files", {{aov + "_albedo.png", 0, albedo.data()}, {aov + "_normal.png", 0, normal.data()}, {aov + "_depth.pfm", 1, render.get_depth_buffer()}});
         }
         if (!aov_specular.empty() || denoise_specular) { // (after --aov's files: as the guide it replaces the first-hit albedo)
             render.run_aov_specular(task.eye_pos, inv_view, fov_y, specular_bounces, denoise_specular);
             const crt_aov_info& ai = render.last_aov_specular_info();
             std::printf("aov-specular: %llu rays in %u chunks, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
         }
-        if (!aov_specular.empty()) {
-            const std::string pg = aov_specular + "_guide_albedo.pfm", pn = aov_specular + "_last_normal.pfm", pd = aov_specular + "_path_depth.pfm",
-                              pb = aov_specular + "_bounces.pfm";
-            int rc = crt_write_pfm(pg.c_str(), task.width, task.height, 3, render.get_guide_albedo_buffer());
-            if (rc == CRT_OK) rc = crt_write_pfm(pn.c_str(), task.width, task.height, 3, render.get_last_normal_buffer());
-            if (rc == CRT_OK) rc = crt_write_pfm(pd.c_str(), task.width, task.height, 1, render.get_path_depth_buffer());
-            if (rc == CRT_OK) rc = crt_write_pfm(pb.c_str(), task.width, task.height, 1, render.get_bounces_buffer());
-            if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the specular AOV files failed: ") + crt_last_error());
-            std::printf("%s\n%s\n%s\n%s\n", pg.c_str(), pn.c_str(), pd.c_str(), pb.c_str());
-        }
+        if (!aov_specular.empty())
+            write_files("specular AOV files", {{aov_specular + "_guide_albedo.pfm", 3, render.get_guide_albedo_buffer()}, {aov_specular + "_last_normal.pfm", 3, render.get_last_normal_buffer()},
+                                               {aov_specular + "_path_depth.pfm", 1, render.get_path_depth_buffer()}, {aov_specular + "_bounces.pfm", 1, render.get_bounces_buffer()}});
         if (denoise_select) {
             render.run_denoise_select(select_candidates, sel);
             const crt_filter_select_info& si = render.last_select_info();
@@ -494,9 +489,7 @@ int main(int argc, char** argv)
                 const size_t n = (size_t)task.width * task.height, top = select_candidates.size() > 1 ? select_candidates.size() - 1 : 1;
                 std::vector<uint8_t> grey(3 * n);
                 for (size_t k = 0; k < n; k++) grey[3 * k] = grey[3 * k + 1] = grey[3 * k + 2] = (uint8_t)(255u * render.get_choice_buffer()[k] / top);
-                const int rc = crt_write_png(denoise_choice.c_str(), task.width, task.height, grey.data());
-                if (rc != CRT_OK) throw crt::Error(rc, std::string("writing the choice map failed: ") + crt_last_error());
-                std::printf("%s\n", denoise_choice.c_str());
+                write_files("choice map", {{denoise_choice, 0, grey.data()}});
             }
         } else if (!denoise.empty()) {
             if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);

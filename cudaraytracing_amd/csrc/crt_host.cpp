@@ -602,749 +602,4 @@ void load_task_scene(const crt_task& task, Scene& scene, const std::string& base
     }
 }
 
-// ------------------------------------------------------------------ Render --
-Render::Render(Scene* scene, unsigned spp, float P_RR, unsigned light_sample_n, int device)
-    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR), device_(device)
-{
-    if (!scene) throw Error(CRT_ERR_INVALID_ARG, "Render: null scene");
-    const crt_scene_desc& d = scene->flat();
-    int rc = crt_scene_create(&d, device, &device_scene_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render: crt_scene_create failed: ") + crt_last_error());
-    frame_buffer_.assign((size_t)3 * scene->get_pixels(), 0);
-    mean_buffer_.assign((size_t)3 * scene->get_pixels(), 0.0f);
-}
-// Several devices (the reference stops at device 0, src/main.cu:92-105): one replica of the scene per entry of `devices`, the
-// frame sharded by interleaved pixel tiles and gathered with one RCCL all-gather (include/crt.h, crt_multi).
-Render::Render(Scene* scene, unsigned spp, float P_RR, unsigned light_sample_n, const std::vector<int>& devices, uint32_t gather)
-    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR)
-{
-    if (!scene) throw Error(CRT_ERR_INVALID_ARG, "Render: null scene");
-    if (devices.empty()) throw Error(CRT_ERR_INVALID_ARG, "Render: empty device list");
-    const crt_scene_desc& d = scene->flat();
-    int rc = crt_multi_create(&d, devices.data(), (uint32_t)devices.size(), gather, &multi_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render: crt_multi_create failed: ") + crt_last_error());
-    rank_stats_.resize(devices.size());
-    frame_buffer_.assign((size_t)3 * scene->get_pixels(), 0);
-    mean_buffer_.assign((size_t)3 * scene->get_pixels(), 0.0f);
-}
-Render::~Render() { free(); }
-
-void Render::free()
-{
-    if (device_scene_) { crt_scene_destroy(device_scene_); device_scene_ = nullptr; }
-    if (multi_) { crt_multi_destroy(multi_); multi_ = nullptr; }
-}
-void Render::set_width(const unsigned& w)
-{
-    scene_->set_width(w);
-    frame_buffer_.assign((size_t)3 * scene_->get_pixels(), 0);
-    mean_buffer_.assign((size_t)3 * scene_->get_pixels(), 0.0f);
-}
-void Render::set_height(const unsigned& h)
-{
-    scene_->set_height(h);
-    frame_buffer_.assign((size_t)3 * scene_->get_pixels(), 0);
-    mean_buffer_.assign((size_t)3 * scene_->get_pixels(), 0.0f);
-}
-
-// the camera and the settings of this object as the C ABI takes them: the whole frame on one rank, with the caller's flags
-void Render::view_args(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t flags, crt_camera& cam, crt_params& p) const
-{
-    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
-    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
-    cam.fov_y = fovY;
-    std::memset(&p, 0, sizeof(p));
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
-    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags;
-}
-
-void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY)
-{
-    if (!device_scene_ && !multi_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view after free()");
-    crt_camera cam;
-    crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS), cam, p);
-    variance_buffer_.clear();
-    int rc;
-    if (multi_) {
-        rc = crt_multi_render(multi_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), rank_stats_.data(), &multi_info_);
-        if (rc == CRT_OK) { // totals over the ranks; times of the slowest one
-            stats_ = rank_stats_[0];
-            for (size_t r = 1; r < rank_stats_.size(); r++) {
-                const crt_stats& o = rank_stats_[r];
-                stats_.paths += o.paths; stats_.rays += o.rays; stats_.shadow_rays += o.shadow_rays; stats_.probe_rays += o.probe_rays;
-                stats_.rays_untraced += o.rays_untraced;
-                stats_.kernel_ms = std::max(stats_.kernel_ms, o.kernel_ms); stats_.total_ms = std::max(stats_.total_ms, o.total_ms);
-            }
-        }
-    } else {
-        rc = crt_render(device_scene_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), &stats_);
-    }
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_view failed: ") + crt_last_error());
-}
-
-// the arguments and buffers run_view_adaptive, run_view_map and run_view_planned share: `render` makes the library call on them
-template <class Call> void Render::sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
-    crt_camera cam;
-    crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, flags_ & CRT_FLAG_TRACE_ALL, cam, p);
-    const size_t n = scene_->get_pixels();
-    samples_buffer_.assign(n, 0u);
-    variance_buffer_.clear();
-    std::vector<float> v(want_variance ? 3 * n : 0, 0.0f);
-    const int rc = render(&cam, &p, want_variance ? v.data() : nullptr);
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-    variance_buffer_.swap(v);
-}
-
-void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
-{
-    sampled_frame("Render::run_view_adaptive", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
-        return crt_render_adaptive(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &adaptive_info_);
-    });
-}
-
-void Render::run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin, bool want_variance)
-{
-    sampled_frame("Render::run_view_map", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
-        return crt_render_map(device_scene_, cam, p, sample_map, sample_begin, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
-    });
-}
-
-void Render::run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
-{
-    sampled_frame("Render::run_view_planned", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
-        return crt_render_planned(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
-    });
-}
-
-void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov: the AOV pass is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov after free()");
-    crt_camera cam;
-    crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
-    const size_t n = scene_->get_pixels();
-    albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f); material_buffer_.assign(n, 0);
-    crt_aov_buffers out{};
-    out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data(); out.material = material_buffer_.data();
-    int rc;
-    if (aov_shading_) {
-        emission_buffer_.assign(3 * n, 0.0f); diffuse_albedo_buffer_.assign(3 * n, 0.0f);
-        const crt_aov_shading_buffers shading{emission_buffer_.data(), diffuse_albedo_buffer_.data()};
-        rc = crt_render_aov_shading(device_scene_, &cam, &p, &out, &shading, &aov_info_);
-    } else rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov failed: ") + crt_last_error());
-}
-
-crt_modulate_params Render::modulate_params(const char* who) const
-{
-    if (emission_buffer_.size() != (size_t)3 * scene_->get_pixels() || diffuse_albedo_buffer_.size() != emission_buffer_.size())
-        throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " with set_demodulate needs run_aov of this frame size first");
-    crt_modulate_params m;
-    crt_modulate_defaults(&m);
-    m.width = scene_->get_width(); m.height = scene_->get_height(); m.albedo_floor = albedo_floor_;
-    return m;
-}
-
-// crt_demodulate of a colour (and its variance, if any) with the shading AOVs of the last run_aov
-void Render::demodulate_of(const char* who, const float* color, const float* variance, std::vector<float>& irradiance, std::vector<float>& irradiance_variance) const
-{
-    const crt_modulate_params m = modulate_params(who);
-    const size_t n = scene_->get_pixels();
-    irradiance.assign(3 * n, 0.0f);
-    if (variance) irradiance_variance.assign(3 * n, 0.0f);
-    const int rc = crt_demodulate(device_, &m, color, diffuse_albedo_buffer_.data(), emission_buffer_.data(), variance, irradiance.data(),
-                                  variance ? irradiance_variance.data() : nullptr, nullptr);
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-}
-
-// crt_modulate of an irradiance with the same buffers
-void Render::modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const
-{
-    const crt_modulate_params m = modulate_params(who);
-    const int rc = crt_modulate(device_, &m, irradiance, diffuse_albedo_buffer_.data(), emission_buffer_.data(), out_mean, out_rgb, nullptr);
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-}
-
-void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces, bool as_albedo_guide)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_aov_specular: the AOV pass is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_aov_specular after free()");
-    crt_camera cam;
-    crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
-    crt_aov_specular_params sp;
-    crt_aov_specular_defaults(&sp);
-    if (max_bounces) sp.max_bounces = max_bounces;
-    const size_t n = scene_->get_pixels();
-    guide_albedo_buffer_.assign(3 * n, 0.0f); last_normal_buffer_.assign(3 * n, 0.0f); path_depth_buffer_.assign(n, 0.0f); bounces_buffer_.assign(n, 0.0f);
-    crt_aov_specular_buffers out{};
-    out.guide_albedo = guide_albedo_buffer_.data(); out.last_normal = last_normal_buffer_.data(); out.path_depth = path_depth_buffer_.data();
-    out.bounces = bounces_buffer_.data();
-    const int rc = crt_render_aov_specular(device_scene_, &cam, &p, &sp, &out, &aov_specular_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_aov_specular failed: ") + crt_last_error());
-    if (as_albedo_guide) albedo_buffer_ = guide_albedo_buffer_;
-}
-
-void Render::run_denoise(const crt_denoise_params& prm)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise: the denoiser is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise after free()");
-    const size_t n = scene_->get_pixels();
-    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
-        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise needs run_view and run_aov of this frame size first");
-    crt_denoise_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    crt_denoise_inputs in{};
-    in.color = mean_buffer_.data(); in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    std::vector<float> irradiance, none;
-    if (demodulate_) {
-        demodulate_of("Render::run_denoise", mean_buffer_.data(), nullptr, irradiance, none);
-        in.color = irradiance.data();
-    }
-    const int rc = crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &denoise_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string("Render::run_denoise failed: ") + crt_last_error());
-    if (demodulate_) modulate_of("Render::run_denoise", denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
-}
-
-const float* Render::variance()
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::variance: the variance buffer is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::variance after free()");
-    if (variance_buffer_.empty()) {
-        std::vector<float> v(3 * scene_->get_pixels(), 0.0f);
-        const int rc = crt_variance(device_scene_, v.data(), nullptr);
-        if (rc != CRT_OK) throw Error(rc, std::string("Render::variance failed: ") + crt_last_error());
-        variance_buffer_.swap(v);
-    }
-    return variance_buffer_.data();
-}
-
-// crt_denoise_var of a colour and its variance with the guides of the last run_aov
-// (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
-void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance,
-                            const crt_nlm_params* nlm)
-{
-    const size_t n = scene_->get_pixels();
-    crt_denoise_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    std::vector<float> irradiance, irradiance_variance;
-    if (demodulate_ && !is_irradiance) {
-        demodulate_of(who, color, variance, irradiance, irradiance_variance);
-        color = irradiance.data(); variance = irradiance_variance.data();
-    }
-    crt_denoise_var_inputs in{};
-    in.color = color; in.variance = variance;
-    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    unsigned char* const call_rgb = demodulate_ ? nullptr : denoised_buffer_.data();
-    int rc;
-    if (nlm) {
-        crt_nlm_params q = *nlm;
-        q.width = p.width; q.height = p.height;
-        rc = crt_denoise_nlm(device_, &q, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
-    } else {
-        rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
-    }
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-    if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
-}
-
-void Render::run_denoise_var(const crt_denoise_params& prm)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise_var: the denoiser is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var after free()");
-    const size_t n = scene_->get_pixels();
-    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
-        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_var needs run_view and run_aov of this frame size first");
-    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
-}
-
-void Render::run_denoise_nlm(const crt_nlm_params& prm)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_denoise_nlm: the denoiser is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm after free()");
-    const size_t n = scene_->get_pixels();
-    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
-        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm needs run_view and run_aov of this frame size first");
-    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
-}
-
-void Render::run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm)
-{
-    const char* who = "Render::run_denoise_select";
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": filter selection is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
-    if (demodulate_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": the half frames are filtered as radiance (not with set_demodulate)");
-    if (candidates.empty() || candidates.size() > CRT_SELECT_MAX_CANDIDATES) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs 1 .. 4 candidates");
-    const size_t n = scene_->get_pixels();
-    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
-        throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs run_view and run_aov of this frame size first");
-    std::vector<float> half[2] = {std::vector<float>(3 * n), std::vector<float>(3 * n)}, half_variance(3 * n);
-    int rc = crt_half_buffers(device_scene_, half[0].data(), half[1].data(), nullptr);
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-    const float* var = variance();
-    for (size_t i = 0; i < 3 * n; i++) half_variance[i] = 2.0f * var[i];
-    // every candidate on either half, with its own defaults and the guides of the last run_aov
-    std::vector<std::vector<float>> filtered[2];
-    crt_filter_select_inputs in{};
-    in.half_a = half[0].data(); in.half_b = half[1].data(); in.half_variance = half_variance.data();
-    const uint32_t w = scene_->get_width(), h = scene_->get_height();
-    for (int side = 0; side < 2; side++) {
-        filtered[side].resize(candidates.size());
-        for (size_t k = 0; k < candidates.size(); k++) {
-            const float* image = half[side].data();
-            if (candidates[k] != SELECT_NONE) {
-                filtered[side][k].assign(3 * n, 0.0f);
-                crt_denoise_var_inputs vin{};
-                vin.color = half[side].data(); vin.variance = half_variance.data();
-                vin.albedo = albedo_buffer_.data(); vin.normal = normal_buffer_.data(); vin.depth = depth_buffer_.data();
-                if (candidates[k] == SELECT_ATROUS) {
-                    crt_denoise_params p;
-                    crt_denoise_defaults(&p);
-                    p.width = w; p.height = h;
-                    crt_denoise_inputs din{};
-                    din.color = vin.color; din.albedo = vin.albedo; din.normal = vin.normal; din.depth = vin.depth;
-                    rc = crt_denoise(device_, &p, &din, filtered[side][k].data(), nullptr, nullptr);
-                } else if (candidates[k] == SELECT_VAR) {
-                    crt_denoise_params p;
-                    crt_denoise_var_defaults(&p);
-                    p.width = w; p.height = h;
-                    rc = crt_denoise_var(device_, &p, &vin, filtered[side][k].data(), nullptr, nullptr, nullptr);
-                } else if (candidates[k] == SELECT_NLM) {
-                    crt_nlm_params p;
-                    crt_denoise_nlm_defaults(&p);
-                    p.width = w; p.height = h;
-                    rc = crt_denoise_nlm(device_, &p, &vin, filtered[side][k].data(), nullptr, nullptr, nullptr);
-                } else throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": unknown candidate");
-                if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-                image = filtered[side][k].data();
-            }
-            (side == 0 ? in.filtered_a : in.filtered_b)[k] = image;
-        }
-    }
-    crt_filter_select_params p = prm;
-    p.width = w; p.height = h; p.n_candidates = (uint32_t)candidates.size();
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f); choice_buffer_.assign(n, 0);
-    rc = crt_filter_select(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), choice_buffer_.data(), nullptr, &select_info_);
-    if (rc != CRT_OK) throw Error(rc, std::string(who) + " failed: " + crt_last_error());
-}
-
-void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_temporal: temporal accumulation is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal after free()");
-    if (!(flags_ & CRT_FLAG_VARIANCE)) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal needs set_flags(CRT_FLAG_VARIANCE)");
-    run_view(eye_pos, inv_view_mat, fovY);
-    const float* var = variance();
-    run_aov(eye_pos, inv_view_mat, fovY);
-    crt_temporal_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
-    std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
-    p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && !temporal_moments_ && temporal_demodulated_ == demodulate_ && temporal_width_ == p.width && temporal_height_ == p.height;
-    p.prev = have ? temporal_cam_ : p.cur;
-    const size_t n = scene_->get_pixels();
-    crt_temporal_frame cur{};
-    cur.color = mean_buffer_.data(); cur.variance = var; cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
-    std::vector<float> irradiance, irradiance_variance;
-    if (demodulate_) {
-        demodulate_of("Render::run_temporal", mean_buffer_.data(), var, irradiance, irradiance_variance);
-        cur.color = irradiance.data(); cur.variance = irradiance_variance.data();
-    }
-    crt_temporal_history prev{};
-    prev.color = temporal_color_.data(); prev.variance = temporal_variance_.data(); prev.history = temporal_history_.data();
-    prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
-    std::vector<float> color(3 * n, 0.0f), variance_out(3 * n, 0.0f), history(n, 0.0f);
-    temporal_rgb_.assign(3 * n, 0);
-    unsigned char* const call_rgb = demodulate_ ? nullptr : temporal_rgb_.data(); // (irradiance has no tone map worth having: modulate_of writes the RGB8)
-    int rc;
-    temporal_clamped_ = 0;
-    if (clamp) {
-        crt_temporal_clamp_info ci{};
-        rc = crt_temporal_clamped(device_, &p, clamp, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), call_rgb, &ci);
-        temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
-        temporal_clamped_ = ci.clamped;
-    } else rc = crt_temporal(device_, &p, &cur, have ? &prev : nullptr, color.data(), variance_out.data(), history.data(), call_rgb, &temporal_info_);
-    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal failed: ") + crt_last_error()); }
-    if (demodulate_) modulate_of("Render::run_temporal", color.data(), nullptr, temporal_rgb_.data());
-    temporal_demodulated_ = demodulate_;
-    temporal_color_.swap(color); temporal_variance_.swap(variance_out); temporal_history_.swap(history);
-    temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
-    temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
-    temporal_valid_ = true;
-    temporal_moments_ = false;
-}
-
-void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
-                                  const crt_variance_estimate_params& est)
-{
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_temporal_moments: temporal accumulation is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_temporal_moments after free()");
-    run_view(eye_pos, inv_view_mat, fovY);
-    run_aov(eye_pos, inv_view_mat, fovY);
-    crt_temporal_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    std::memcpy(p.cur.eye, eye_pos, sizeof(p.cur.eye));
-    std::memcpy(p.cur.inv_view, inv_view_mat, sizeof(p.cur.inv_view));
-    p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && temporal_moments_ && temporal_demodulated_ == demodulate_ && temporal_width_ == p.width && temporal_height_ == p.height;
-    p.prev = have ? temporal_cam_ : p.cur;
-    const size_t n = scene_->get_pixels();
-    crt_temporal_frame cur{};
-    cur.color = mean_buffer_.data(); cur.depth = depth_buffer_.data(); cur.normal = normal_buffer_.data(); cur.id = material_buffer_.data();
-    std::vector<float> irradiance, none;
-    if (demodulate_) {
-        demodulate_of("Render::run_temporal_moments", mean_buffer_.data(), nullptr, irradiance, none);
-        cur.color = irradiance.data();
-    }
-    crt_temporal_history prev{};
-    prev.color = temporal_color_.data(); prev.history = temporal_history_.data();
-    prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
-    const crt_temporal_moment_planes planes = {temporal_m1_.data(), temporal_m2_.data()};
-    std::vector<float> color(3 * n, 0.0f), history(n, 0.0f), m1(3 * n, 0.0f), m2(3 * n, 0.0f), estimate(3 * n, 0.0f);
-    temporal_rgb_.assign(3 * n, 0);
-    crt_temporal_clamp_info ci{};
-    int rc = crt_temporal_moments(device_, &p, clamp, &cur, have ? &prev : nullptr, have ? &planes : nullptr, color.data(), nullptr, history.data(), m1.data(),
-                                  m2.data(), demodulate_ ? nullptr : temporal_rgb_.data(), &ci); // (demodulate_: modulate_of writes the RGB8 below)
-    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
-    temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
-    temporal_clamped_ = ci.clamped;
-    crt_variance_estimate_params e = est;
-    e.width = p.width; e.height = p.height;
-    crt_variance_estimate_inputs in{};
-    in.m1 = m1.data(); in.m2 = m2.data(); in.history = history.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
-    rc = crt_variance_estimate(device_, &e, &in, estimate.data(), &estimate_info_);
-    if (rc != CRT_OK) { temporal_valid_ = false; throw Error(rc, std::string("Render::run_temporal_moments failed: ") + crt_last_error()); }
-    if (demodulate_) modulate_of("Render::run_temporal_moments", color.data(), nullptr, temporal_rgb_.data());
-    temporal_demodulated_ = demodulate_;
-    temporal_color_.swap(color); temporal_variance_.swap(estimate); temporal_history_.swap(history);
-    temporal_m1_.swap(m1); temporal_m2_.swap(m2);
-    temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
-    temporal_cam_ = p.cur; temporal_width_ = p.width; temporal_height_ = p.height;
-    temporal_valid_ = true;
-    temporal_moments_ = true;
-}
-
-void Render::run_denoise_temporal(const crt_denoise_params& prm)
-{
-    if (!temporal_valid_ || temporal_color_.size() != (size_t)3 * scene_->get_pixels())
-        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first");
-    if (temporal_demodulated_ != demodulate_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal: set_demodulate changed since run_temporal");
-    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm, temporal_demodulated_);
-}
-
-void Render::run_view_upsampled(const float eye_pos[3], const float inv_view_mat[9], float fovY, unsigned factor, const crt_upsample_params& prm, unsigned guide_spp)
-{
-    const char* who = "Render::run_view_upsampled";
-    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": upsampling is a single-device interface");
-    if (!device_scene_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
-    const unsigned W = scene_->get_width(), H = scene_->get_height();
-    if (factor < 2 || factor > 8) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must be 2 .. 8");
-    if (W % factor || H % factor) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must divide width and height");
-    const unsigned lw = W / factor, lh = H / factor;
-    const size_t nl = (size_t)lw * lh, n = scene_->get_pixels();
-    auto check = [&](int rc, const char* step) { if (rc != CRT_OK) throw Error(rc, std::string(who) + ": " + step + " failed: " + crt_last_error()); };
-    // the low-resolution frame, its variance and its AOVs
-    crt_camera cam;
-    crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, (flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE)) | CRT_FLAG_VARIANCE, cam, p);
-    p.width = lw; p.height = lh;
-    std::vector<unsigned char> low_rgb(3 * nl, 0);
-    std::vector<float> low_mean(3 * nl, 0.0f), low_var(3 * nl, 0.0f), l_albedo(3 * nl, 0.0f), l_normal(3 * nl, 0.0f), l_depth(nl, 0.0f), l_emission(3 * nl, 0.0f),
-        l_diffuse(3 * nl, 0.0f);
-    crt_stats low_stats;
-    variance_buffer_.clear(); // (the handle's sums are the low frame's from here on)
-    check(crt_render(device_scene_, &cam, &p, low_rgb.data(), low_mean.data(), &low_stats), "the low-resolution frame");
-    check(crt_variance(device_scene_, low_var.data(), nullptr), "its variance");
-    p.flags = 0;
-    crt_aov_buffers la{};
-    la.albedo = l_albedo.data(); la.normal = l_normal.data(); la.depth = l_depth.data();
-    const crt_aov_shading_buffers ls{l_emission.data(), l_diffuse.data()};
-    crt_aov_info low_aov;
-    check(crt_render_aov_shading(device_scene_, &cam, &p, &la, &ls, &low_aov), "the low-resolution AOV pass");
-    // the full-resolution AOVs: run_aov with the shading buffers and guide_spp samples
-    const bool shading = aov_shading_;
-    const unsigned spp = spp_;
-    aov_shading_ = true;
-    if (guide_spp) spp_ = guide_spp;
-    try {
-        run_aov(eye_pos, inv_view_mat, fovY);
-    } catch (...) {
-        aov_shading_ = shading; spp_ = spp;
-        throw;
-    }
-    aov_shading_ = shading; spp_ = spp;
-    // irradiance at the low size, upsampled, radiance at the full size
-    crt_modulate_params m;
-    crt_modulate_defaults(&m);
-    m.width = lw; m.height = lh; m.albedo_floor = albedo_floor_;
-    std::vector<float> irr(3 * nl, 0.0f), ivar(3 * nl, 0.0f), up(3 * n, 0.0f), up_var(3 * n, 0.0f);
-    check(crt_demodulate(device_, &m, low_mean.data(), l_diffuse.data(), l_emission.data(), low_var.data(), irr.data(), ivar.data(), nullptr), "crt_demodulate");
-    crt_upsample_params u = prm;
-    u.width = W; u.height = H; u.low_width = lw; u.low_height = lh;
-    const crt_upsample_low low{irr.data(), ivar.data(), l_albedo.data(), l_normal.data(), l_depth.data()};
-    const crt_upsample_guides guides{albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
-    check(crt_upsample(device_, &u, &low, &guides, up.data(), up_var.data(), nullptr, &upsample_info_), "crt_upsample");
-    upsampled_buffer_.assign(3 * n, 0); upsampled_mean_buffer_.assign(3 * n, 0.0f);
-    m.width = W; m.height = H;
-    check(crt_modulate(device_, &m, up.data(), diffuse_albedo_buffer_.data(), emission_buffer_.data(), upsampled_mean_buffer_.data(), upsampled_buffer_.data(), nullptr),
-          "crt_modulate");
-}
-
-void Render::save_upsampled_buffer(const char* save_path) const
-{
-    if (upsampled_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_upsampled_buffer before run_view_upsampled");
-    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), upsampled_buffer_.data());
-    if (rc != CRT_OK) throw Error(rc, std::string("save_upsampled_buffer failed: ") + crt_last_error());
-}
-
-void Render::save_temporal_buffer(const char* save_path) const
-{
-    if (temporal_rgb_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_temporal_buffer before run_temporal");
-    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), temporal_rgb_.data());
-    if (rc != CRT_OK) throw Error(rc, std::string("save_temporal_buffer failed: ") + crt_last_error());
-}
-
-void Render::save_denoised_buffer(const char* save_path) const
-{
-    if (denoised_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_denoised_buffer before run_denoise");
-    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), denoised_buffer_.data());
-    if (rc != CRT_OK) throw Error(rc, std::string("save_denoised_buffer failed: ") + crt_last_error());
-}
-
-void Render::save_frame_buffer(const char* save_path) const
-{
-    int rc = crt_write_png(save_path, scene_->get_width(), scene_->get_height(), frame_buffer_.data());
-    if (rc != CRT_OK) throw Error(rc, std::string("save_frame_buffer failed: ") + crt_last_error());
-}
-
 } // namespace crt
-
-// =========================================================== C ABI (host) ==
-namespace {
-thread_local std::string g_last_error;
-}
-extern "C" void crt_set_last_error_(const char* msg) { g_last_error = msg ? msg : ""; }
-
-struct crt_host_scene {
-    crt::Scene scene;
-    crt_host_scene(uint32_t w, uint32_t h) : scene(w, h) {}
-};
-
-#define CRT_HOST_TRY(...)                                                                   \
-    try { __VA_ARGS__; return CRT_OK; }                                                            \
-    catch (const crt::Error& e) { g_last_error = e.what(); return e.status; }               \
-    catch (const std::bad_alloc&) { g_last_error = "out of host memory"; return CRT_ERR_OOM; } \
-    catch (const std::exception& e) { g_last_error = e.what(); return CRT_ERR_INVALID_ARG; }
-
-extern "C" {
-
-const char* crt_strerror(int status)
-{
-    switch (status) {
-    case CRT_OK: return "ok";
-    case CRT_ERR_INVALID_ARG: return "invalid argument";
-    case CRT_ERR_NO_DEVICE: return "no HIP device";
-    case CRT_ERR_HIP: return "HIP runtime error";
-    case CRT_ERR_UNSUPPORTED: return "unsupported";
-    case CRT_ERR_IO: return "I/O error";
-    case CRT_ERR_PARSE: return "parse error";
-    case CRT_ERR_OOM: return "out of memory";
-    default: return "unknown status";
-    }
-}
-const char* crt_last_error(void) { return g_last_error.c_str(); }
-int crt_abi_version(void) { return CRT_ABI_VERSION; }
-
-int crt_host_scene_create(uint32_t width, uint32_t height, crt_host_scene** out)
-{
-    if (!out || width == 0 || height == 0) { g_last_error = "crt_host_scene_create: bad arguments"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY(*out = new crt_host_scene(width, height));
-}
-int crt_host_scene_destroy(crt_host_scene* s)
-{
-    delete s;
-    return CRT_OK;
-}
-int crt_host_scene_add_obj(crt_host_scene* s, const char* obj_path, const char* mtl_dir)
-{
-    if (!s || !obj_path || !mtl_dir) { g_last_error = "crt_host_scene_add_obj: null argument"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY({
-        crt::Loader loader;
-        loader.read_OBJ(obj_path, mtl_dir);
-        std::vector<crt::Triangle> tris, light_tris;
-        for (uint64_t i = 0; i < loader.size(); i++) {
-            loader.load_object(i, tris, light_tris);
-            if (!tris.empty()) { crt::Object o(tris); s->scene.add_normal_obj(o); }
-            if (!light_tris.empty()) { crt::Object o(light_tris); s->scene.add_light_obj(o); }
-        }
-    });
-}
-int crt_host_scene_set_bvh(crt_host_scene* s, uint32_t thresh_n)
-{
-    if (!s) { g_last_error = "crt_host_scene_set_bvh: null scene"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY(s->scene.set_BVH(thresh_n));
-}
-int crt_host_scene_set_bvh_device(crt_host_scene* s, uint32_t thresh_n, int device, crt_bvh_build_info* info)
-{
-    if (!s) { g_last_error = "crt_host_scene_set_bvh_device: null scene"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY(s->scene.set_BVH_device(thresh_n, device, info));
-}
-int crt_host_scene_desc(const crt_host_scene* s, crt_scene_desc* out)
-{
-    if (!s || !out) { g_last_error = "crt_host_scene_desc: null argument"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY(*out = const_cast<crt_host_scene*>(s)->scene.flat());
-}
-int crt_host_scene_num_objects(const crt_host_scene* s, uint32_t* n)
-{
-    if (!s || !n) { g_last_error = "crt_host_scene_num_objects: null argument"; return CRT_ERR_INVALID_ARG; }
-    *n = (uint32_t)s->scene.get_objects().size();
-    return CRT_OK;
-}
-int crt_host_scene_object(const crt_host_scene* s, uint32_t index, float* area, int32_t* is_light, uint32_t* n_tris)
-{
-    if (!s || index >= s->scene.get_objects().size()) { g_last_error = "crt_host_scene_object: bad index"; return CRT_ERR_INVALID_ARG; }
-    const auto& o = s->scene.get_objects()[index];
-    if (area) *area = o.second.get_area();
-    if (is_light) *is_light = o.first ? 1 : 0;
-    if (n_tris) *n_tris = (uint32_t)o.second.get_triangles().size();
-    return CRT_OK;
-}
-int crt_inverse_view(const float eye[3], const float lookat[3], const float up[3], float out[9])
-{
-    if (!eye || !lookat || !up || !out) { g_last_error = "crt_inverse_view: null argument"; return CRT_ERR_INVALID_ARG; }
-    crt::get_inverse_view_matrix(eye, lookat, up, out);
-    return CRT_OK;
-}
-int crt_image_load(const char* path, int32_t* x, int32_t* y, int32_t* comp, uint8_t* out, uint64_t cap)
-{
-    if (!path || !x || !y || !comp) { g_last_error = "crt_image_load: null argument"; return CRT_ERR_INVALID_ARG; }
-    try {
-        crtimg::Image img;
-        const std::string err = crtimg::load(path, img);
-        if (!err.empty()) { g_last_error = "crt_image_load: " + err; return err.rfind("cannot open", 0) == 0 ? CRT_ERR_IO : CRT_ERR_UNSUPPORTED; }
-        *x = img.width; *y = img.height; *comp = img.comp;
-        if (out) {
-            if (cap < img.px.size()) { g_last_error = "crt_image_load: buffer too small"; return CRT_ERR_INVALID_ARG; }
-            std::memcpy(out, img.px.data(), img.px.size());
-        }
-        return CRT_OK;
-    } catch (const std::bad_alloc&) { // (a file may honestly announce more pixels than the host has memory for)
-        g_last_error = "crt_image_load: out of host memory";
-        return CRT_ERR_OOM;
-    }
-}
-int crt_task_load(const char* path, crt_task* out)
-{
-    if (!path || !out) { g_last_error = "crt_task_load: null argument"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY(*out = crt::load_task(path));
-}
-int crt_task_obj(const char* path, uint32_t index, char* obj_path, char* mtl_dir, uint32_t cap)
-{
-    if (!path || !obj_path || !mtl_dir) { g_last_error = "crt_task_obj: null argument"; return CRT_ERR_INVALID_ARG; }
-    CRT_HOST_TRY({
-        crt::TaskObjs all;
-        (void)crt::load_task(path, &all);
-        if (index >= all.size()) throw crt::Error(CRT_ERR_INVALID_ARG, "crt_task_obj: index beyond the file's OBJ_paths");
-        if (all[index].first.size() + 1 > cap || all[index].second.size() + 1 > cap) throw crt::Error(CRT_ERR_INVALID_ARG, "crt_task_obj: buffer too small");
-        std::memcpy(obj_path, all[index].first.c_str(), all[index].first.size() + 1);
-        std::memcpy(mtl_dir, all[index].second.c_str(), all[index].second.size() + 1);
-    });
-}
-
-// ---- PNG (stored deflate blocks; replaces stbi_write_png, Render.cuh:489-493) ----
-static uint32_t crc_table[256];
-static bool crc_ready = false;
-static uint32_t crc32_update(uint32_t c, const uint8_t* p, size_t n)
-{
-    if (!crc_ready) {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t k = i;
-            for (int j = 0; j < 8; j++) k = (k & 1) ? 0xEDB88320u ^ (k >> 1) : k >> 1;
-            crc_table[i] = k;
-        }
-        crc_ready = true;
-    }
-    for (size_t i = 0; i < n; i++) c = crc_table[(c ^ p[i]) & 0xff] ^ (c >> 8);
-    return c;
-}
-static void put32(std::vector<uint8_t>& v, uint32_t x)
-{
-    v.push_back((uint8_t)(x >> 24)); v.push_back((uint8_t)(x >> 16)); v.push_back((uint8_t)(x >> 8)); v.push_back((uint8_t)x);
-}
-static void chunk(std::vector<uint8_t>& png, const char* type, const std::vector<uint8_t>& data)
-{
-    put32(png, (uint32_t)data.size());
-    size_t start = png.size();
-    png.insert(png.end(), type, type + 4);
-    png.insert(png.end(), data.begin(), data.end());
-    uint32_t c = crc32_update(0xffffffffu, png.data() + start, png.size() - start) ^ 0xffffffffu;
-    put32(png, c);
-}
-int crt_write_png(const char* path, uint32_t width, uint32_t height, const uint8_t* rgb)
-{
-    if (!path || !rgb || width == 0 || height == 0) { g_last_error = "crt_write_png: bad arguments"; return CRT_ERR_INVALID_ARG; }
-    std::vector<uint8_t> raw;
-    raw.reserve((size_t)height * (3 * width + 1));
-    for (uint32_t y = 0; y < height; y++) {
-        raw.push_back(0); // filter: none
-        raw.insert(raw.end(), rgb + (size_t)y * width * 3, rgb + (size_t)(y + 1) * width * 3);
-    }
-    std::vector<uint8_t> z;
-    z.push_back(0x78); z.push_back(0x01);
-    uint32_t a = 1, b = 0;
-    size_t pos = 0;
-    while (pos < raw.size() || raw.empty()) {
-        size_t n = std::min<size_t>(65535, raw.size() - pos);
-        z.push_back(pos + n >= raw.size() ? 1 : 0);
-        z.push_back((uint8_t)(n & 0xff)); z.push_back((uint8_t)(n >> 8));
-        z.push_back((uint8_t)(~n & 0xff)); z.push_back((uint8_t)((~n >> 8) & 0xff));
-        z.insert(z.end(), raw.begin() + pos, raw.begin() + pos + n);
-        for (size_t i = 0; i < n; i++) { a = (a + raw[pos + i]) % 65521u; b = (b + a) % 65521u; }
-        pos += n;
-        if (raw.empty()) break;
-    }
-    put32(z, (b << 16) | a);
-    std::vector<uint8_t> png = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
-    std::vector<uint8_t> ihdr;
-    put32(ihdr, width); put32(ihdr, height);
-    ihdr.push_back(8); ihdr.push_back(2); ihdr.push_back(0); ihdr.push_back(0); ihdr.push_back(0);
-    chunk(png, "IHDR", ihdr);
-    chunk(png, "IDAT", z);
-    chunk(png, "IEND", std::vector<uint8_t>());
-    FILE* f = std::fopen(path, "wb");
-    if (!f) { g_last_error = std::string("cannot open for writing: ") + path; return CRT_ERR_IO; }
-    size_t w = std::fwrite(png.data(), 1, png.size(), f);
-    std::fclose(f);
-    if (w != png.size()) { g_last_error = std::string("short write: ") + path; return CRT_ERR_IO; }
-    return CRT_OK;
-}
-
-int crt_write_pfm(const char* path, uint32_t width, uint32_t height, uint32_t channels, const float* data)
-{
-    if (!path || !data || width == 0 || height == 0 || (channels != 1 && channels != 3)) { g_last_error = "crt_write_pfm: bad arguments"; return CRT_ERR_INVALID_ARG; }
-    static_assert(sizeof(float) == 4, "PFM samples are 32-bit floats");
-    const uint32_t probe = 1;
-    if (*(const uint8_t*)&probe != 1) { g_last_error = "crt_write_pfm: big-endian host"; return CRT_ERR_UNSUPPORTED; } // (scale -1.0 says little-endian)
-    const std::string header = std::string(channels == 3 ? "PF" : "Pf") + "\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n";
-    FILE* f = std::fopen(path, "wb");
-    if (!f) { g_last_error = std::string("cannot open for writing: ") + path; return CRT_ERR_IO; }
-    bool ok = std::fwrite(header.data(), 1, header.size(), f) == header.size();
-    const size_t row = (size_t)width * channels;
-    for (uint32_t y = height; ok && y-- > 0;) // bottom row first
-        ok = std::fwrite(data + (size_t)y * row, sizeof(float), row, f) == row;
-    ok = std::fclose(f) == 0 && ok;
-    if (!ok) { g_last_error = std::string("short write: ") + path; return CRT_ERR_IO; }
-    return CRT_OK;
-}
-
-} // extern "C"

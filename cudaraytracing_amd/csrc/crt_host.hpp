@@ -381,6 +381,12 @@ private:
     std::vector<unsigned char> upsampled_buffer_;    // run_view_upsampled
     std::vector<float> upsampled_mean_buffer_;
     crt_upsample_info upsample_info_{};
+    // the rules the methods share, each stated once (crt_host_render.cpp); hidden: no symbols of the library
+    __attribute__((visibility("hidden"))) void alive(const char* who) const;
+    __attribute__((visibility("hidden"))) void one_device(const char* who, const char* noun) const;
+    __attribute__((visibility("hidden"))) void need_guides(const std::string& who) const;
+    template <class Blend> void temporal_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, bool moments,
+                                               const float* var, Blend blend);
 };
 
 } // namespace crt

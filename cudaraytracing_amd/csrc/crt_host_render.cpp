@@ -1,0 +1,522 @@
+// cudaraytracing_amd/csrc/crt_host_render.cpp -- crt::Render (see crt_host.hpp): the reference's Render class (include/Render.cuh:357-557)
+// over the C ABI of include/crt.h.
+#include "crt_host.hpp"
+
+#include <algorithm>
+#include <cstring>
+
+namespace crt {
+
+namespace {
+// a library status as an Error: "`who` failed: ..." or, with the step of a longer method, "`who`: `step` failed: ..."
+void check(int rc, std::string who, const char* step = nullptr)
+{
+    if (rc == CRT_OK) return;
+    if (step) (who += ": ") += step;
+    throw Error(rc, who + " failed: " + crt_last_error());
+}
+// what the save_* methods do once their buffer exists; `who` is the method's name
+void save_rgb8(const char* who, const char* save_path, const Scene& scene, const std::vector<unsigned char>& rgb)
+{
+    check(crt_write_png(save_path, scene.get_width(), scene.get_height(), rgb.data()), who);
+}
+// one frame of a temporal sequence as the library takes it, and the buffers of the history it makes (Render::temporal_frame)
+struct TemporalStep {
+    crt_temporal_params p;
+    crt_temporal_frame cur;
+    const crt_temporal_history* prev;                    // nullptr: no history is continued
+    std::vector<float> color, variance, history, m1, m2; // (m1, m2: of a history with moment planes)
+    unsigned char* rgb;
+};
+} // namespace
+
+// ------------------------------------------------------------------ Render --
+// a Render that has given up its device objects runs nothing
+void Render::alive(const char* who) const
+{
+    if (!device_scene_ && !multi_) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " after free()");
+}
+// every method but run_view works on one device only; `noun` is what the method's refusal calls it (nullptr: nothing)
+void Render::one_device(const char* who, const char* noun) const
+{
+    if (multi_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": " + (noun ? std::string(noun) + " is " : std::string()) + "a single-device interface");
+    alive(who);
+}
+// the filters take the frame of run_view and the guides of run_aov
+void Render::need_guides(const std::string& who) const
+{
+    const size_t n = scene_->get_pixels();
+    if (albedo_buffer_.size() != 3 * n || normal_buffer_.size() != 3 * n || depth_buffer_.size() != n || mean_buffer_.size() != 3 * n)
+        throw Error(CRT_ERR_INVALID_ARG, who + " needs run_view and run_aov of this frame size first");
+}
+
+Render::Render(Scene* scene, unsigned spp, float P_RR, unsigned light_sample_n, int device)
+    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR), device_(device)
+{
+    if (!scene) throw Error(CRT_ERR_INVALID_ARG, "Render: null scene");
+    const crt_scene_desc& d = scene->flat();
+    check(crt_scene_create(&d, device, &device_scene_), "Render: crt_scene_create");
+    frame_buffer_.assign((size_t)3 * scene->get_pixels(), 0);
+    mean_buffer_.assign((size_t)3 * scene->get_pixels(), 0.0f);
+}
+// Several devices (the reference stops at device 0, src/main.cu:92-105): one replica of the scene per entry of `devices`, the
+// frame sharded by interleaved pixel tiles and gathered with one RCCL all-gather (include/crt.h, crt_multi).
+Render::Render(Scene* scene, unsigned spp, float P_RR, unsigned light_sample_n, const std::vector<int>& devices, uint32_t gather)
+    : scene_(scene), spp_(spp), light_sample_n_(light_sample_n), P_RR_(P_RR)
+{
+    if (!scene) throw Error(CRT_ERR_INVALID_ARG, "Render: null scene");
+    if (devices.empty()) throw Error(CRT_ERR_INVALID_ARG, "Render: empty device list");
+    const crt_scene_desc& d = scene->flat();
+    check(crt_multi_create(&d, devices.data(), (uint32_t)devices.size(), gather, &multi_), "Render: crt_multi_create");
+    rank_stats_.resize(devices.size());
+    frame_buffer_.assign((size_t)3 * scene->get_pixels(), 0);
+    mean_buffer_.assign((size_t)3 * scene->get_pixels(), 0.0f);
+}
+Render::~Render() { free(); }
+
+void Render::free()
+{
+    if (device_scene_) { crt_scene_destroy(device_scene_); device_scene_ = nullptr; }
+    if (multi_) { crt_multi_destroy(multi_); multi_ = nullptr; }
+}
+void Render::set_width(const unsigned& w)
+{
+    scene_->set_width(w);
+    frame_buffer_.assign((size_t)3 * scene_->get_pixels(), 0);
+    mean_buffer_.assign((size_t)3 * scene_->get_pixels(), 0.0f);
+}
+void Render::set_height(const unsigned& h)
+{
+    scene_->set_height(h);
+    frame_buffer_.assign((size_t)3 * scene_->get_pixels(), 0);
+    mean_buffer_.assign((size_t)3 * scene_->get_pixels(), 0.0f);
+}
+
+// the camera and the settings of this object as the C ABI takes them: the whole frame on one rank, with the caller's flags
+void Render::view_args(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t flags, crt_camera& cam, crt_params& p) const
+{
+    std::memcpy(cam.eye, eye_pos, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, inv_view_mat, sizeof(cam.inv_view));
+    cam.fov_y = fovY;
+    std::memset(&p, 0, sizeof(p));
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    p.spp = spp_; p.p_rr = P_RR_; p.light_sample_n = (int32_t)light_sample_n_;
+    p.seed = seed_; p.rank = 0; p.world = 1; p.traversal = traversal_; p.flags = flags;
+}
+
+void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY)
+{
+    alive("Render::run_view");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS), cam, p);
+    variance_buffer_.clear();
+    int rc;
+    if (multi_) {
+        rc = crt_multi_render(multi_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), rank_stats_.data(), &multi_info_);
+        if (rc == CRT_OK) { // totals over the ranks; times of the slowest one
+            stats_ = rank_stats_[0];
+            for (size_t r = 1; r < rank_stats_.size(); r++) {
+                const crt_stats& o = rank_stats_[r];
+                stats_.paths += o.paths; stats_.rays += o.rays; stats_.shadow_rays += o.shadow_rays; stats_.probe_rays += o.probe_rays;
+                stats_.rays_untraced += o.rays_untraced;
+                stats_.kernel_ms = std::max(stats_.kernel_ms, o.kernel_ms); stats_.total_ms = std::max(stats_.total_ms, o.total_ms);
+            }
+        }
+    } else rc = crt_render(device_scene_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), &stats_);
+    check(rc, "Render::run_view");
+}
+
+// the arguments and buffers run_view_adaptive, run_view_map and run_view_planned share: `render` makes the library call on them
+template <class Call> void Render::sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render)
+{
+    one_device(who, nullptr);
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & CRT_FLAG_TRACE_ALL, cam, p);
+    const size_t n = scene_->get_pixels();
+    samples_buffer_.assign(n, 0u);
+    variance_buffer_.clear();
+    std::vector<float> v(want_variance ? 3 * n : 0, 0.0f);
+    check(render(&cam, &p, want_variance ? v.data() : nullptr), who);
+    variance_buffer_.swap(v);
+}
+
+void Render::run_view_adaptive(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+{
+    sampled_frame("Render::run_view_adaptive", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_adaptive(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &adaptive_info_);
+    });
+}
+
+void Render::run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin, bool want_variance)
+{
+    sampled_frame("Render::run_view_map", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_map(device_scene_, cam, p, sample_map, sample_begin, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
+    });
+}
+
+void Render::run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance)
+{
+    sampled_frame("Render::run_view_planned", eye_pos, inv_view_mat, fovY, want_variance, [&](const crt_camera* cam, const crt_params* p, float* var) {
+        return crt_render_planned(device_scene_, cam, p, &ap, frame_buffer_.data(), mean_buffer_.data(), samples_buffer_.data(), var, &map_info_);
+    });
+}
+
+void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)
+{
+    one_device("Render::run_aov", "the AOV pass");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
+    const size_t n = scene_->get_pixels();
+    albedo_buffer_.assign(3 * n, 0.0f); normal_buffer_.assign(3 * n, 0.0f); depth_buffer_.assign(n, 0.0f); material_buffer_.assign(n, 0);
+    crt_aov_buffers out{};
+    out.albedo = albedo_buffer_.data(); out.normal = normal_buffer_.data(); out.depth = depth_buffer_.data(); out.material = material_buffer_.data();
+    int rc;
+    if (aov_shading_) {
+        emission_buffer_.assign(3 * n, 0.0f); diffuse_albedo_buffer_.assign(3 * n, 0.0f);
+        const crt_aov_shading_buffers shading{emission_buffer_.data(), diffuse_albedo_buffer_.data()};
+        rc = crt_render_aov_shading(device_scene_, &cam, &p, &out, &shading, &aov_info_);
+    } else rc = crt_render_aov(device_scene_, &cam, &p, &out, &aov_info_);
+    check(rc, "Render::run_aov");
+}
+
+crt_modulate_params Render::modulate_params(const char* who) const
+{
+    if (emission_buffer_.size() != (size_t)3 * scene_->get_pixels() || diffuse_albedo_buffer_.size() != emission_buffer_.size())
+        throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " with set_demodulate needs run_aov of this frame size first");
+    crt_modulate_params m;
+    crt_modulate_defaults(&m);
+    m.width = scene_->get_width(); m.height = scene_->get_height(); m.albedo_floor = albedo_floor_;
+    return m;
+}
+
+// crt_demodulate of a colour (and its variance, if any) with the shading AOVs of the last run_aov
+void Render::demodulate_of(const char* who, const float* color, const float* variance, std::vector<float>& irradiance, std::vector<float>& irradiance_variance) const
+{
+    const crt_modulate_params m = modulate_params(who);
+    const size_t n = scene_->get_pixels();
+    irradiance.assign(3 * n, 0.0f);
+    if (variance) irradiance_variance.assign(3 * n, 0.0f);
+    check(crt_demodulate(device_, &m, color, diffuse_albedo_buffer_.data(), emission_buffer_.data(), variance, irradiance.data(),
+                         variance ? irradiance_variance.data() : nullptr, nullptr), who);
+}
+
+// crt_modulate of an irradiance with the same buffers
+void Render::modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const
+{
+    const crt_modulate_params m = modulate_params(who);
+    check(crt_modulate(device_, &m, irradiance, diffuse_albedo_buffer_.data(), emission_buffer_.data(), out_mean, out_rgb, nullptr), who);
+}
+
+void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t max_bounces, bool as_albedo_guide)
+{
+    one_device("Render::run_aov_specular", "the AOV pass");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
+    crt_aov_specular_params sp;
+    crt_aov_specular_defaults(&sp);
+    if (max_bounces) sp.max_bounces = max_bounces;
+    const size_t n = scene_->get_pixels();
+    guide_albedo_buffer_.assign(3 * n, 0.0f); last_normal_buffer_.assign(3 * n, 0.0f); path_depth_buffer_.assign(n, 0.0f); bounces_buffer_.assign(n, 0.0f);
+    crt_aov_specular_buffers out{};
+    out.guide_albedo = guide_albedo_buffer_.data(); out.last_normal = last_normal_buffer_.data(); out.path_depth = path_depth_buffer_.data();
+    out.bounces = bounces_buffer_.data();
+    check(crt_render_aov_specular(device_scene_, &cam, &p, &sp, &out, &aov_specular_info_), "Render::run_aov_specular");
+    if (as_albedo_guide) albedo_buffer_ = guide_albedo_buffer_;
+}
+
+void Render::run_denoise(const crt_denoise_params& prm)
+{
+    one_device("Render::run_denoise", "the denoiser");
+    const size_t n = scene_->get_pixels();
+    need_guides("Render::run_denoise");
+    crt_denoise_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    crt_denoise_inputs in{};
+    in.color = mean_buffer_.data(); in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    std::vector<float> irradiance, none;
+    if (demodulate_) {
+        demodulate_of("Render::run_denoise", mean_buffer_.data(), nullptr, irradiance, none);
+        in.color = irradiance.data();
+    }
+    check(crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &denoise_info_), "Render::run_denoise");
+    if (demodulate_) modulate_of("Render::run_denoise", denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
+}
+
+const float* Render::variance()
+{
+    one_device("Render::variance", "the variance buffer");
+    if (variance_buffer_.empty()) {
+        std::vector<float> v(3 * scene_->get_pixels(), 0.0f);
+        check(crt_variance(device_scene_, v.data(), nullptr), "Render::variance");
+        variance_buffer_.swap(v);
+    }
+    return variance_buffer_.data();
+}
+
+// crt_denoise_var of a colour and its variance with the guides of the last run_aov
+// (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
+void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance,
+                            const crt_nlm_params* nlm)
+{
+    const size_t n = scene_->get_pixels();
+    crt_denoise_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    std::vector<float> irradiance, irradiance_variance;
+    if (demodulate_ && !is_irradiance) {
+        demodulate_of(who, color, variance, irradiance, irradiance_variance);
+        color = irradiance.data(); variance = irradiance_variance.data();
+    }
+    crt_denoise_var_inputs in{};
+    in.color = color; in.variance = variance;
+    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    unsigned char* const call_rgb = demodulate_ ? nullptr : denoised_buffer_.data();
+    int rc;
+    if (nlm) {
+        crt_nlm_params q = *nlm;
+        q.width = p.width; q.height = p.height;
+        rc = crt_denoise_nlm(device_, &q, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
+    } else rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
+    check(rc, who);
+    if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
+}
+
+void Render::run_denoise_var(const crt_denoise_params& prm)
+{
+    one_device("Render::run_denoise_var", "the denoiser");
+    need_guides("Render::run_denoise_var");
+    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
+}
+
+void Render::run_denoise_nlm(const crt_nlm_params& prm)
+{
+    one_device("Render::run_denoise_nlm", "the denoiser");
+    need_guides("Render::run_denoise_nlm");
+    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
+}
+
+void Render::run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm)
+{
+    const char* who = "Render::run_denoise_select";
+    one_device(who, "filter selection");
+    if (demodulate_) throw Error(CRT_ERR_UNSUPPORTED, std::string(who) + ": the half frames are filtered as radiance (not with set_demodulate)");
+    if (candidates.empty() || candidates.size() > CRT_SELECT_MAX_CANDIDATES) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs 1 .. 4 candidates");
+    const size_t n = scene_->get_pixels();
+    need_guides(who);
+    std::vector<float> half[2] = {std::vector<float>(3 * n), std::vector<float>(3 * n)}, half_variance(3 * n);
+    check(crt_half_buffers(device_scene_, half[0].data(), half[1].data(), nullptr), who);
+    const float* var = variance();
+    for (size_t i = 0; i < 3 * n; i++) half_variance[i] = 2.0f * var[i];
+    const uint32_t w = scene_->get_width(), h = scene_->get_height();
+    // one candidate on one half frame, with its own defaults and the guides of the last run_aov
+    auto filter = [&](int candidate, const float* image, float* out) {
+        crt_denoise_var_inputs vin{};
+        vin.color = image; vin.variance = half_variance.data();
+        vin.albedo = albedo_buffer_.data(); vin.normal = normal_buffer_.data(); vin.depth = depth_buffer_.data();
+        if (candidate == SELECT_NLM) {
+            crt_nlm_params p;
+            crt_denoise_nlm_defaults(&p);
+            p.width = w; p.height = h;
+            return crt_denoise_nlm(device_, &p, &vin, out, nullptr, nullptr, nullptr);
+        }
+        if (candidate != SELECT_ATROUS && candidate != SELECT_VAR) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": unknown candidate");
+        crt_denoise_params p;
+        if (candidate == SELECT_VAR) crt_denoise_var_defaults(&p); else crt_denoise_defaults(&p);
+        p.width = w; p.height = h;
+        if (candidate == SELECT_VAR) return crt_denoise_var(device_, &p, &vin, out, nullptr, nullptr, nullptr);
+        crt_denoise_inputs din{};
+        din.color = vin.color; din.albedo = vin.albedo; din.normal = vin.normal; din.depth = vin.depth;
+        return crt_denoise(device_, &p, &din, out, nullptr, nullptr);
+    };
+    std::vector<std::vector<float>> filtered[2];
+    crt_filter_select_inputs in{};
+    in.half_a = half[0].data(); in.half_b = half[1].data(); in.half_variance = half_variance.data();
+    for (int side = 0; side < 2; side++) {
+        filtered[side].resize(candidates.size());
+        for (size_t k = 0; k < candidates.size(); k++) {
+            const float* image = half[side].data();
+            if (candidates[k] != SELECT_NONE) {
+                filtered[side][k].assign(3 * n, 0.0f);
+                check(filter(candidates[k], image, filtered[side][k].data()), who);
+                image = filtered[side][k].data();
+            }
+            (side == 0 ? in.filtered_a : in.filtered_b)[k] = image;
+        }
+    }
+    crt_filter_select_params p = prm;
+    p.width = w; p.height = h; p.n_candidates = (uint32_t)candidates.size();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f); choice_buffer_.assign(n, 0);
+    check(crt_filter_select(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), choice_buffer_.data(), nullptr, &select_info_), who);
+}
+
+// What run_temporal and run_temporal_moments share, around the library calls `blend` makes on the step.  Before them: the size and the
+// cameras, whether the history is continued (one with moment planes is not continued without them, nor the other way round), the frame
+// with `var`, the variance of its mean (nullptr: none is carried), or its irradiance, and the history.  After them: a failure drops the
+// history; otherwise the step's buffers become it, with the frame's guides, camera and size.
+template <class Blend> void Render::temporal_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm,
+                                                   bool moments, const float* var, Blend blend)
+{
+    TemporalStep s{};
+    s.p = prm;
+    s.p.width = scene_->get_width(); s.p.height = scene_->get_height();
+    std::memcpy(s.p.cur.eye, eye_pos, sizeof(s.p.cur.eye));
+    std::memcpy(s.p.cur.inv_view, inv_view_mat, sizeof(s.p.cur.inv_view));
+    s.p.cur.fov_y = fovY;
+    const bool have = temporal_valid_ && temporal_moments_ == moments && temporal_demodulated_ == demodulate_ && temporal_width_ == s.p.width && temporal_height_ == s.p.height;
+    s.p.prev = have ? temporal_cam_ : s.p.cur;
+    const size_t n = scene_->get_pixels();
+    s.cur.color = mean_buffer_.data(); s.cur.variance = var; s.cur.depth = depth_buffer_.data(); s.cur.normal = normal_buffer_.data(); s.cur.id = material_buffer_.data();
+    std::vector<float> irradiance, irradiance_variance;
+    if (demodulate_) {
+        demodulate_of(who, mean_buffer_.data(), var, irradiance, irradiance_variance);
+        s.cur.color = irradiance.data();
+        if (var) s.cur.variance = irradiance_variance.data();
+    }
+    crt_temporal_history prev{};
+    prev.color = temporal_color_.data(); prev.variance = moments ? nullptr : temporal_variance_.data(); prev.history = temporal_history_.data();
+    prev.depth = temporal_depth_.data(); prev.normal = temporal_normal_.data(); prev.id = temporal_id_.data();
+    s.prev = have ? &prev : nullptr;
+    s.color.assign(3 * n, 0.0f); s.variance.assign(3 * n, 0.0f); s.history.assign(n, 0.0f);
+    if (moments) { s.m1.assign(3 * n, 0.0f); s.m2.assign(3 * n, 0.0f); }
+    temporal_rgb_.assign(3 * n, 0);
+    s.rgb = demodulate_ ? nullptr : temporal_rgb_.data(); // (irradiance has no tone map worth having: modulate_of writes the RGB8 below)
+    const int rc = blend(s);
+    if (rc != CRT_OK) temporal_valid_ = false;
+    check(rc, who);
+    if (demodulate_) modulate_of(who, s.color.data(), nullptr, temporal_rgb_.data());
+    temporal_demodulated_ = demodulate_;
+    temporal_color_.swap(s.color); temporal_variance_.swap(s.variance); temporal_history_.swap(s.history);
+    if (moments) { temporal_m1_.swap(s.m1); temporal_m2_.swap(s.m2); }
+    temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
+    temporal_cam_ = s.p.cur; temporal_width_ = s.p.width; temporal_height_ = s.p.height;
+    temporal_valid_ = true;
+    temporal_moments_ = moments;
+}
+
+void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp)
+{
+    const char* who = "Render::run_temporal";
+    one_device(who, "temporal accumulation");
+    if (!(flags_ & CRT_FLAG_VARIANCE)) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs set_flags(CRT_FLAG_VARIANCE)");
+    run_view(eye_pos, inv_view_mat, fovY);
+    const float* var = variance();
+    run_aov(eye_pos, inv_view_mat, fovY);
+    temporal_frame(who, eye_pos, inv_view_mat, fovY, prm, false, var, [&](TemporalStep& s) {
+        temporal_clamped_ = 0;
+        if (!clamp) return crt_temporal(device_, &s.p, &s.cur, s.prev, s.color.data(), s.variance.data(), s.history.data(), s.rgb, &temporal_info_);
+        crt_temporal_clamp_info ci{};
+        const int rc = crt_temporal_clamped(device_, &s.p, clamp, &s.cur, s.prev, s.color.data(), s.variance.data(), s.history.data(), s.rgb, &ci);
+        temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
+        temporal_clamped_ = ci.clamped;
+        return rc;
+    });
+}
+
+void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
+                                  const crt_variance_estimate_params& est)
+{
+    const char* who = "Render::run_temporal_moments";
+    one_device(who, "temporal accumulation");
+    run_view(eye_pos, inv_view_mat, fovY);
+    run_aov(eye_pos, inv_view_mat, fovY);
+    temporal_frame(who, eye_pos, inv_view_mat, fovY, prm, true, nullptr, [&](TemporalStep& s) {
+        const crt_temporal_moment_planes planes = {temporal_m1_.data(), temporal_m2_.data()};
+        crt_temporal_clamp_info ci{};
+        const int rc = crt_temporal_moments(device_, &s.p, clamp, &s.cur, s.prev, s.prev ? &planes : nullptr, s.color.data(), nullptr, s.history.data(), s.m1.data(),
+                                            s.m2.data(), s.rgb, &ci);
+        if (rc != CRT_OK) return rc;
+        temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
+        temporal_clamped_ = ci.clamped;
+        crt_variance_estimate_params e = est; // the variance the history keeps: the estimate from its moments
+        e.width = s.p.width; e.height = s.p.height;
+        crt_variance_estimate_inputs in{};
+        in.m1 = s.m1.data(); in.m2 = s.m2.data(); in.history = s.history.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+        return crt_variance_estimate(device_, &e, &in, s.variance.data(), &estimate_info_);
+    });
+}
+
+void Render::run_denoise_temporal(const crt_denoise_params& prm)
+{
+    if (!temporal_valid_ || temporal_color_.size() != (size_t)3 * scene_->get_pixels())
+        throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first");
+    if (temporal_demodulated_ != demodulate_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal: set_demodulate changed since run_temporal");
+    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm, temporal_demodulated_);
+}
+
+void Render::run_view_upsampled(const float eye_pos[3], const float inv_view_mat[9], float fovY, unsigned factor, const crt_upsample_params& prm, unsigned guide_spp)
+{
+    const char* who = "Render::run_view_upsampled";
+    one_device(who, "upsampling");
+    const unsigned W = scene_->get_width(), H = scene_->get_height();
+    if (factor < 2 || factor > 8) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must be 2 .. 8");
+    if (W % factor || H % factor) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must divide width and height");
+    const unsigned lw = W / factor, lh = H / factor;
+    const size_t nl = (size_t)lw * lh, n = scene_->get_pixels();
+    // the low-resolution frame, its variance and its AOVs
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, (flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE)) | CRT_FLAG_VARIANCE, cam, p);
+    p.width = lw; p.height = lh;
+    std::vector<unsigned char> low_rgb(3 * nl, 0);
+    std::vector<float> low_mean(3 * nl, 0.0f), low_var(3 * nl, 0.0f), l_albedo(3 * nl, 0.0f), l_normal(3 * nl, 0.0f), l_depth(nl, 0.0f), l_emission(3 * nl, 0.0f),
+        l_diffuse(3 * nl, 0.0f);
+    crt_stats low_stats;
+    variance_buffer_.clear(); // (the handle's sums are the low frame's from here on)
+    check(crt_render(device_scene_, &cam, &p, low_rgb.data(), low_mean.data(), &low_stats), who, "the low-resolution frame");
+    check(crt_variance(device_scene_, low_var.data(), nullptr), who, "its variance");
+    p.flags = 0;
+    crt_aov_buffers la{};
+    la.albedo = l_albedo.data(); la.normal = l_normal.data(); la.depth = l_depth.data();
+    const crt_aov_shading_buffers ls{l_emission.data(), l_diffuse.data()};
+    crt_aov_info low_aov;
+    check(crt_render_aov_shading(device_scene_, &cam, &p, &la, &ls, &low_aov), who, "the low-resolution AOV pass");
+    {   // the full-resolution AOVs: run_aov with the shading buffers and guide_spp samples; the settings come back however it ends
+        struct Restore { bool& shading; unsigned& spp; const bool shading_was; const unsigned spp_was; ~Restore() { shading = shading_was; spp = spp_was; } }
+            restore{aov_shading_, spp_, aov_shading_, spp_};
+        aov_shading_ = true;
+        if (guide_spp) spp_ = guide_spp;
+        run_aov(eye_pos, inv_view_mat, fovY);
+    }
+    // irradiance at the low size, upsampled, radiance at the full size
+    crt_modulate_params m;
+    crt_modulate_defaults(&m);
+    m.width = lw; m.height = lh; m.albedo_floor = albedo_floor_;
+    std::vector<float> irr(3 * nl, 0.0f), ivar(3 * nl, 0.0f), up(3 * n, 0.0f), up_var(3 * n, 0.0f);
+    check(crt_demodulate(device_, &m, low_mean.data(), l_diffuse.data(), l_emission.data(), low_var.data(), irr.data(), ivar.data(), nullptr), who, "crt_demodulate");
+    crt_upsample_params u = prm;
+    u.width = W; u.height = H; u.low_width = lw; u.low_height = lh;
+    const crt_upsample_low low{irr.data(), ivar.data(), l_albedo.data(), l_normal.data(), l_depth.data()};
+    const crt_upsample_guides guides{albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
+    check(crt_upsample(device_, &u, &low, &guides, up.data(), up_var.data(), nullptr, &upsample_info_), who, "crt_upsample");
+    upsampled_buffer_.assign(3 * n, 0); upsampled_mean_buffer_.assign(3 * n, 0.0f);
+    m.width = W; m.height = H;
+    check(crt_modulate(device_, &m, up.data(), diffuse_albedo_buffer_.data(), emission_buffer_.data(), upsampled_mean_buffer_.data(), upsampled_buffer_.data(), nullptr),
+          who, "crt_modulate");
+}
+
+void Render::save_upsampled_buffer(const char* save_path) const
+{
+    if (upsampled_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_upsampled_buffer before run_view_upsampled");
+    save_rgb8("save_upsampled_buffer", save_path, *scene_, upsampled_buffer_);
+}
+
+void Render::save_temporal_buffer(const char* save_path) const
+{
+    if (temporal_rgb_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_temporal_buffer before run_temporal");
+    save_rgb8("save_temporal_buffer", save_path, *scene_, temporal_rgb_);
+}
+
+void Render::save_denoised_buffer(const char* save_path) const
+{
+    if (denoised_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_denoised_buffer before run_denoise");
+    save_rgb8("save_denoised_buffer", save_path, *scene_, denoised_buffer_);
+}
+
+void Render::save_frame_buffer(const char* save_path) const { save_rgb8("save_frame_buffer", save_path, *scene_, frame_buffer_); }
+
+} // namespace crt

@@ -322,3 +322,15 @@ int use(Scene* scene, Eigen::Vector3f eye, Eigen::Matrix3f inv_view, float fov_y
            "-I", os.path.join(util.ROOT, "tests", "shim_decls"), str(tmp_path / "main.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
+
+
+@pytest.mark.gpu
+def test_render_class_map_frames_refusals_and_temporal_history(tmp_path):
+    """tools/render_host_check.cpp: what crt_cli never asks of crt::Render.  run_view_map against crt_render_map, the text and status
+    of every refusal the class makes itself (several devices, after free(), a missing earlier step, a bad factor, an unwritable path),
+    and two frames each of run_temporal, run_temporal with a clamp, run_temporal_moments and run_temporal again against the library
+    calls they are made of -- bit for bit, with no history carried from one kind to the other."""
+    from cudaraytracing_amd import build as b
+    exe = b.build_render_check()
+    r = subprocess.run([exe, util.SCENES["cornell-box"], util.ROOT, str(tmp_path / "no_such_directory")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]

@@ -1,0 +1,330 @@
+// tools/render_host_check.cpp -- crt::Render (cudaraytracing_amd/csrc/crt_host.hpp) where crt_cli does not reach it: run_view_map, the
+// refusals of the class itself, and the history run_temporal / run_temporal_moments keep between calls.  Needs a GPU.  cornell-box at
+// 32 x 24, spp 4, seed 0; every result is compared bit for bit with the same library calls made directly on a second scene handle, every
+// refusal with the text and status written out below.  Exits 1 at the first mismatch with one line that names the comparison.
+//
+//   cudaraytracing_amd/build.py builds it beside crt_cli, as lib/render_host_check
+//   render_host_check scenes/cornell-box/config.json <base dir of the OBJ paths> <a directory that does not exist>
+#include "../cudaraytracing_amd/csrc/crt_host.hpp"
+
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace {
+
+const uint32_t W = 32, H = 24, S = 4;
+const size_t N = (size_t)W * H;
+
+[[noreturn]] void fail(const std::string& what)
+{
+    std::fprintf(stderr, "render_host_check: %s\n", what.c_str());
+    std::exit(1);
+}
+void ok(int rc, const char* call) { if (rc != CRT_OK) fail(std::string(call) + " failed: " + crt_last_error()); }
+template <class T> void same(const std::string& what, const T* a, const T* b, size_t n)
+{
+    if (std::memcmp(a, b, n * sizeof(T)) != 0) fail(what + " differs");
+}
+// `call` must throw crt::Error with this status and this text
+void refused(const std::string& what, int status, const std::string& text, const std::function<void()>& call)
+{
+    try {
+        call();
+    } catch (const crt::Error& e) {
+        if (e.status != status || text != e.what())
+            fail(what + ": got (" + std::to_string(e.status) + ") \"" + e.what() + "\", expected (" + std::to_string(status) + ") \"" + text + "\"");
+        return;
+    }
+    fail(what + ": no error, expected \"" + text + "\"");
+}
+
+struct View {
+    float eye[3], inv_view[9], fov_y;
+};
+// what Render::run_view hands the library for this view: the whole frame on one rank
+void direct_args(const crt_task& task, const View& v, uint64_t seed, uint32_t flags, crt_camera& cam, crt_params& p)
+{
+    std::memcpy(cam.eye, v.eye, sizeof(cam.eye));
+    std::memcpy(cam.inv_view, v.inv_view, sizeof(cam.inv_view));
+    cam.fov_y = v.fov_y;
+    std::memset(&p, 0, sizeof(p));
+    p.width = W; p.height = H; p.spp = S; p.p_rr = task.p_rr; p.light_sample_n = (int32_t)task.light_sample_n;
+    p.seed = seed; p.rank = 0; p.world = 1; p.traversal = CRT_TRAVERSAL_EXACT; p.flags = flags;
+}
+
+// ---- 1. run_view_map against crt_render_map ----
+void check_map(crt::Render& r, crt_scene* direct, const crt_task& task, const View& v)
+{
+    std::vector<uint32_t> map(N); // tests/test_sample_map.py, ragged_map(): zeros, ones, values above spp, neighbours that differ
+    for (uint32_t y = 0; y < H; y++)
+        for (uint32_t x = 0; x < W; x++) map[(size_t)y * W + x] = (7 * x + 3 * y * y) % (S + 3);
+    crt_camera cam;
+    crt_params p;
+    direct_args(task, v, 0, 0, cam, p);
+    std::vector<uint8_t> rgb(3 * N);
+    std::vector<float> mean(3 * N), var(3 * N);
+    std::vector<uint32_t> samples(N);
+    crt_map_info info;
+    ok(crt_render_map(direct, &cam, &p, map.data(), 0, rgb.data(), mean.data(), samples.data(), var.data(), &info), "crt_render_map");
+    r.run_view_map(v.eye, v.inv_view, v.fov_y, map.data(), 0, true);
+    same("run_view_map: frame", (const uint8_t*)r.get_frame_buffer(), rgb.data(), 3 * N);
+    same("run_view_map: mean", r.get_mean_buffer(), mean.data(), 3 * N);
+    same("run_view_map: samples", r.get_samples_buffer(), samples.data(), N);
+    same("run_view_map: variance", r.variance(), var.data(), 3 * N);
+    if (r.last_map_info().paths != info.paths || r.last_map_info().max_samples != info.max_samples) fail("run_view_map: last_map_info differs");
+    // sample_begin > 0 continues a frame in flight, and no method of Render leaves one: the library refuses the call on either handle,
+    // before any device work, and the frame and mean buffers stay the first call's
+    const int rc = crt_render_map(direct, &cam, &p, map.data(), 2, rgb.data(), mean.data(), samples.data(), var.data(), &info);
+    const std::string why = crt_last_error();
+    if (rc != CRT_ERR_INVALID_ARG) fail("crt_render_map with sample_begin 2 after a finished frame: status " + std::to_string(rc));
+    refused("run_view_map with sample_begin 2", rc, "Render::run_view_map failed: " + why, [&] { r.run_view_map(v.eye, v.inv_view, v.fov_y, map.data(), 2, true); });
+    same("run_view_map with sample_begin 2: frame", (const uint8_t*)r.get_frame_buffer(), rgb.data(), 3 * N);
+    same("run_view_map with sample_begin 2: mean", r.get_mean_buffer(), mean.data(), 3 * N);
+}
+
+// ---- 2. the refusals ----
+struct Call {
+    const char* who;
+    const char* on_several; // the refusal of a Render on several devices, after `who`
+    std::function<void()> run;
+};
+// every method of `r` that works on one device
+std::vector<Call> single_device_calls(crt::Render& r, const View& v, const uint32_t* map)
+{
+    static crt_adaptive_params ad;
+    static crt_denoise_params dn, dv;
+    static crt_nlm_params nlm;
+    static crt_filter_select_params sel;
+    static crt_temporal_params tp;
+    static crt_variance_estimate_params est;
+    static crt_upsample_params up;
+    crt_adaptive_defaults(&ad); crt_denoise_defaults(&dn); crt_denoise_var_defaults(&dv); crt_denoise_nlm_defaults(&nlm);
+    crt_filter_select_defaults(&sel); crt_temporal_defaults(&tp); crt_variance_estimate_defaults(&est); crt_upsample_defaults(&up);
+    crt::Render* q = &r;
+    return {
+        {"Render::run_view_adaptive", ": a single-device interface", [=] { q->run_view_adaptive(v.eye, v.inv_view, v.fov_y, ad); }},
+        {"Render::run_view_map", ": a single-device interface", [=] { q->run_view_map(v.eye, v.inv_view, v.fov_y, map); }},
+        {"Render::run_view_planned", ": a single-device interface", [=] { q->run_view_planned(v.eye, v.inv_view, v.fov_y, ad); }},
+        {"Render::run_aov", ": the AOV pass is a single-device interface", [=] { q->run_aov(v.eye, v.inv_view, v.fov_y); }},
+        {"Render::run_aov_specular", ": the AOV pass is a single-device interface", [=] { q->run_aov_specular(v.eye, v.inv_view, v.fov_y); }},
+        {"Render::run_denoise", ": the denoiser is a single-device interface", [=] { q->run_denoise(dn); }},
+        {"Render::variance", ": the variance buffer is a single-device interface", [=] { q->variance(); }},
+        {"Render::run_denoise_var", ": the denoiser is a single-device interface", [=] { q->run_denoise_var(dv); }},
+        {"Render::run_denoise_nlm", ": the denoiser is a single-device interface", [=] { q->run_denoise_nlm(nlm); }},
+        {"Render::run_denoise_select", ": filter selection is a single-device interface", [=] { q->run_denoise_select({crt::Render::SELECT_VAR}, sel); }},
+        {"Render::run_temporal", ": temporal accumulation is a single-device interface", [=] { q->run_temporal(v.eye, v.inv_view, v.fov_y, tp); }},
+        {"Render::run_temporal_moments", ": temporal accumulation is a single-device interface", [=] { q->run_temporal_moments(v.eye, v.inv_view, v.fov_y, tp, nullptr, est); }},
+        {"Render::run_view_upsampled", ": upsampling is a single-device interface", [=] { q->run_view_upsampled(v.eye, v.inv_view, v.fov_y, 1, up); }},
+    };
+}
+
+void check_refusals(crt::Scene& scene, const crt_task& task, const View& v, const std::string& no_such_dir)
+{
+    const std::vector<uint32_t> map(N, 1u);
+    const std::string first = " needs run_view and run_aov of this frame size first", bad_png = no_such_dir + "/x.png", io = "cannot open for writing: " + bad_png;
+    crt_denoise_params dn, dv;
+    crt_nlm_params nlm;
+    crt_filter_select_params sel;
+    crt_temporal_params tp;
+    crt_upsample_params up;
+    crt_denoise_defaults(&dn); crt_denoise_var_defaults(&dv); crt_denoise_nlm_defaults(&nlm); crt_filter_select_defaults(&sel); crt_temporal_defaults(&tp);
+    crt_upsample_defaults(&up);
+    {   // two ranks on one device: none of these methods has a form for it.  (No flag is set, the factor is 1: the refusal that
+        // names several devices comes before the method's other ones.)
+        crt::Render many(&scene, S, task.p_rr, task.light_sample_n, std::vector<int>{0, 0}, CRT_GATHER_COPY);
+        for (const Call& c : single_device_calls(many, v, map.data()))
+            refused(std::string(c.who) + " on two ranks", CRT_ERR_UNSUPPORTED, std::string(c.who) + c.on_several, c.run);
+        many.free();
+        refused("Render::run_view on two ranks after free()", CRT_ERR_INVALID_ARG, "Render::run_view after free()", [&] { many.run_view(v.eye, v.inv_view, v.fov_y); });
+        for (const Call& c : single_device_calls(many, v, map.data())) // (free() leaves no sign that there were several devices)
+            refused(std::string(c.who) + " on two ranks after free()", CRT_ERR_INVALID_ARG, std::string(c.who) + " after free()", c.run);
+    }
+    crt::Render r(&scene, S, task.p_rr, task.light_sample_n, 0);
+    // before run_aov (the mean buffer exists from the constructor on, the guides do not)
+    refused("run_denoise before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise" + first, [&] { r.run_denoise(dn); });
+    refused("run_denoise_var before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_var" + first, [&] { r.run_denoise_var(dv); });
+    refused("run_denoise_nlm before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm" + first, [&] { r.run_denoise_nlm(nlm); });
+    refused("run_denoise_select before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_select" + first, [&] { r.run_denoise_select({crt::Render::SELECT_VAR}, sel); });
+    refused("run_denoise_select without candidates", CRT_ERR_INVALID_ARG, "Render::run_denoise_select needs 1 .. 4 candidates", [&] { r.run_denoise_select({}, sel); });
+    r.set_demodulate(true);
+    refused("run_denoise_select with set_demodulate", CRT_ERR_UNSUPPORTED, "Render::run_denoise_select: the half frames are filtered as radiance (not with set_demodulate)",
+            [&] { r.run_denoise_select({}, sel); });
+    r.set_demodulate(false);
+    r.set_aov_shading(false);
+    refused("run_denoise_temporal before run_temporal", CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first",
+            [&] { r.run_denoise_temporal(dv); });
+    // the save_* methods before their buffers exist; the frame buffer always exists, so that one fails in the writer
+    refused("save_upsampled_buffer", CRT_ERR_INVALID_ARG, "save_upsampled_buffer before run_view_upsampled", [&] { r.save_upsampled_buffer(bad_png.c_str()); });
+    refused("save_temporal_buffer", CRT_ERR_INVALID_ARG, "save_temporal_buffer before run_temporal", [&] { r.save_temporal_buffer(bad_png.c_str()); });
+    refused("save_denoised_buffer", CRT_ERR_INVALID_ARG, "save_denoised_buffer before run_denoise", [&] { r.save_denoised_buffer(bad_png.c_str()); });
+    refused("save_frame_buffer", CRT_ERR_IO, "save_frame_buffer failed: " + io, [&] { r.save_frame_buffer(bad_png.c_str()); });
+    refused("run_temporal without CRT_FLAG_VARIANCE", CRT_ERR_INVALID_ARG, "Render::run_temporal needs set_flags(CRT_FLAG_VARIANCE)",
+            [&] { r.run_temporal(v.eye, v.inv_view, v.fov_y, tp); });
+    const char* who = "Render::run_view_upsampled";
+    refused("run_view_upsampled by 1", CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must be 2 .. 8", [&] { r.run_view_upsampled(v.eye, v.inv_view, v.fov_y, 1, up); });
+    refused("run_view_upsampled by 9", CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must be 2 .. 8", [&] { r.run_view_upsampled(v.eye, v.inv_view, v.fov_y, 9, up); });
+    refused("run_view_upsampled by 5", CRT_ERR_INVALID_ARG, std::string(who) + ": the factor must divide width and height",
+            [&] { r.run_view_upsampled(v.eye, v.inv_view, v.fov_y, 5, up); });
+    // with their buffers, the other three fail in the writer as well, each under its own name
+    r.set_flags(CRT_FLAG_VARIANCE);
+    r.run_temporal(v.eye, v.inv_view, v.fov_y, tp);
+    r.run_denoise(dn);
+    r.run_view_upsampled(v.eye, v.inv_view, v.fov_y, 2, up);
+    refused("save_temporal_buffer to no directory", CRT_ERR_IO, "save_temporal_buffer failed: " + io, [&] { r.save_temporal_buffer(bad_png.c_str()); });
+    refused("save_denoised_buffer to no directory", CRT_ERR_IO, "save_denoised_buffer failed: " + io, [&] { r.save_denoised_buffer(bad_png.c_str()); });
+    refused("save_upsampled_buffer to no directory", CRT_ERR_IO, "save_upsampled_buffer failed: " + io, [&] { r.save_upsampled_buffer(bad_png.c_str()); });
+    // after free(): every method, whatever else is wrong with the call
+    r.set_flags(0);
+    r.free();
+    refused("Render::run_view after free()", CRT_ERR_INVALID_ARG, "Render::run_view after free()", [&] { r.run_view(v.eye, v.inv_view, v.fov_y); });
+    for (const Call& c : single_device_calls(r, v, map.data()))
+        refused(std::string(c.who) + " after free()", CRT_ERR_INVALID_ARG, std::string(c.who) + " after free()", c.run);
+}
+
+// ---- 3. the history of run_temporal and run_temporal_moments ----
+// the same sequence from the library's calls: what a Render keeps between two frames
+struct History {
+    bool valid = false, moments = false;
+    crt_camera cam{};
+    std::vector<float> color, variance, history, depth, normal, m1, m2;
+    std::vector<int32_t> id;
+    std::vector<uint8_t> rgb;
+    uint64_t reprojected = 0, clamped = 0;
+};
+enum Kind { PLAIN, CLAMPED, MOMENTS };
+
+void direct_frame(crt_scene* direct, const crt_task& task, const View& v, uint64_t seed, Kind kind, const crt_temporal_clamp& clamp, History& hs)
+{
+    crt_camera cam;
+    crt_params p;
+    direct_args(task, v, seed, CRT_FLAG_VARIANCE, cam, p);
+    std::vector<uint8_t> rgb(3 * N);
+    std::vector<float> mean(3 * N), var(3 * N), albedo(3 * N), normal(3 * N), depth(N);
+    std::vector<int32_t> id(N);
+    crt_stats stats;
+    ok(crt_render(direct, &cam, &p, rgb.data(), mean.data(), &stats), "crt_render");
+    if (kind != MOMENTS) ok(crt_variance(direct, var.data(), nullptr), "crt_variance");
+    p.flags = 0;
+    crt_aov_buffers aov{};
+    aov.albedo = albedo.data(); aov.normal = normal.data(); aov.depth = depth.data(); aov.material = id.data();
+    crt_aov_info aov_info;
+    ok(crt_render_aov(direct, &cam, &p, &aov, &aov_info), "crt_render_aov");
+    crt_temporal_params tp;
+    crt_temporal_defaults(&tp);
+    tp.width = W; tp.height = H; tp.cur = cam;
+    const bool have = hs.valid && hs.moments == (kind == MOMENTS);
+    tp.prev = have ? hs.cam : cam;
+    crt_temporal_frame cur{};
+    cur.color = mean.data(); cur.variance = kind == MOMENTS ? nullptr : var.data(); cur.depth = depth.data(); cur.normal = normal.data(); cur.id = id.data();
+    crt_temporal_history prev{};
+    prev.color = hs.color.data(); prev.variance = kind == MOMENTS ? nullptr : hs.variance.data(); prev.history = hs.history.data();
+    prev.depth = hs.depth.data(); prev.normal = hs.normal.data(); prev.id = hs.id.data();
+    std::vector<float> color(3 * N), variance(3 * N), history(N), m1(3 * N), m2(3 * N);
+    hs.rgb.assign(3 * N, 0);
+    hs.clamped = 0;
+    if (kind == PLAIN) {
+        crt_temporal_info ti{};
+        ok(crt_temporal(0, &tp, &cur, have ? &prev : nullptr, color.data(), variance.data(), history.data(), hs.rgb.data(), &ti), "crt_temporal");
+        hs.reprojected = ti.reprojected;
+    } else {
+        crt_temporal_clamp_info ci{};
+        if (kind == CLAMPED) {
+            ok(crt_temporal_clamped(0, &tp, &clamp, &cur, have ? &prev : nullptr, color.data(), variance.data(), history.data(), hs.rgb.data(), &ci), "crt_temporal_clamped");
+        } else {
+            const crt_temporal_moment_planes planes = {hs.m1.data(), hs.m2.data()};
+            ok(crt_temporal_moments(0, &tp, &clamp, &cur, have ? &prev : nullptr, have ? &planes : nullptr, color.data(), nullptr, history.data(), m1.data(), m2.data(),
+                                    hs.rgb.data(), &ci), "crt_temporal_moments");
+            crt_variance_estimate_params e;
+            crt_variance_estimate_defaults(&e);
+            e.width = W; e.height = H;
+            crt_variance_estimate_inputs in{};
+            in.m1 = m1.data(); in.m2 = m2.data(); in.history = history.data(); in.normal = normal.data(); in.depth = depth.data();
+            ok(crt_variance_estimate(0, &e, &in, variance.data(), nullptr), "crt_variance_estimate");
+        }
+        hs.reprojected = ci.reprojected; hs.clamped = ci.clamped;
+    }
+    hs.color.swap(color); hs.variance.swap(variance); hs.history.swap(history); hs.m1.swap(m1); hs.m2.swap(m2);
+    hs.depth.swap(depth); hs.normal.swap(normal); hs.id.swap(id);
+    hs.cam = cam; hs.valid = true; hs.moments = kind == MOMENTS;
+}
+
+void check_temporal(crt::Render& r, crt_scene* direct, const crt_task& task)
+{
+    crt_temporal_params tp;
+    crt_temporal_defaults(&tp);
+    crt_temporal_clamp clamp;
+    crt_temporal_clamp_defaults(&clamp);
+    crt_variance_estimate_params est;
+    crt_variance_estimate_defaults(&est);
+    r.set_flags(CRT_FLAG_VARIANCE);
+    History hs;
+    // two frames each; run_temporal with and without the clamp keep one kind of history, so reset_temporal() parts them
+    const struct { const char* name; Kind kind; bool reset; } runs[] = {
+        {"run_temporal", PLAIN, false}, {"run_temporal with a clamp", CLAMPED, true}, {"run_temporal_moments", MOMENTS, false}, {"run_temporal again", PLAIN, false}};
+    uint64_t seed = 0;
+    for (const auto& run : runs) {
+        if (run.reset) { r.reset_temporal(); hs.valid = false; }
+        for (int f = 0; f < 2; f++, seed++) {
+            float eye[3], lookat[3];
+            for (int k = 0; k < 3; k++) { eye[k] = task.eye_pos[k] + (k == 0 ? 4.0f * f : 0.0f); lookat[k] = task.lookat[k] + (k == 0 ? 4.0f * f : 0.0f); }
+            View v;
+            std::memcpy(v.eye, eye, sizeof(eye));
+            crt::get_inverse_view_matrix(eye, lookat, task.up, v.inv_view);
+            v.fov_y = task.fov_y * (float)M_PI / 180;
+            r.set_seed(seed);
+            if (run.kind == MOMENTS) r.run_temporal_moments(v.eye, v.inv_view, v.fov_y, tp, &clamp, est);
+            else r.run_temporal(v.eye, v.inv_view, v.fov_y, tp, run.kind == CLAMPED ? &clamp : nullptr);
+            direct_frame(direct, task, v, seed, run.kind, clamp, hs);
+            const std::string what = std::string(run.name) + ", frame " + std::to_string(f) + ": ";
+            same(what + "accumulated mean", r.get_temporal_mean_buffer(), hs.color.data(), 3 * N);
+            same(what + "variance", r.get_temporal_variance_buffer(), hs.variance.data(), 3 * N);
+            same(what + "history", r.get_temporal_history_buffer(), hs.history.data(), N);
+            same(what + "RGB8", r.get_temporal_buffer(), (const unsigned char*)hs.rgb.data(), 3 * N);
+            if (r.last_temporal_info().reprojected != hs.reprojected) fail(what + "reprojected differs");
+            if (r.last_temporal_clamped() != hs.clamped) fail(what + "clamped differs");
+            // a history of the other kind, or none, is not continued; one of this kind is
+            if (f == 0 ? r.last_temporal_info().reprojected != 0 : r.last_temporal_info().reprojected == 0)
+                fail(what + std::to_string(r.last_temporal_info().reprojected) + " pixels reprojected");
+        }
+    }
+}
+
+} // namespace
+
+int main(int argc, char** argv)
+{
+    if (argc != 4) {
+        std::fprintf(stderr, "usage: %s <config.json> <base dir> <a directory that does not exist>\n", argv[0]);
+        return 2;
+    }
+    try {
+        crt::TaskObjs all_objs;
+        crt_task task = crt::load_task(argv[1], &all_objs);
+        task.width = W; task.height = H; task.spp = S;
+        crt::Scene scene(W, H);
+        crt::load_task_scene(task, scene, argv[2], &all_objs);
+        scene.set_BVH(task.bvh_thresh_n);
+        View v;
+        std::memcpy(v.eye, task.eye_pos, sizeof(v.eye));
+        crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, v.inv_view);
+        v.fov_y = task.fov_y * (float)M_PI / 180;
+        crt_scene* direct = nullptr;
+        ok(crt_scene_create(&scene.flat(), 0, &direct), "crt_scene_create");
+        {
+            crt::Render r(&scene, S, task.p_rr, task.light_sample_n, 0);
+            check_map(r, direct, task, v);
+            check_temporal(r, direct, task);
+        }
+        check_refusals(scene, task, v, argv[3]);
+        crt_scene_destroy(direct);
+    } catch (const crt::Error& e) {
+        fail(std::string("unexpected error: ") + e.what() + " (" + crt_strerror(e.status) + ")");
+    }
+    std::printf("render_host_check: ok\n");
+    return 0;
+}
