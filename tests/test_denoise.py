@@ -22,6 +22,7 @@ DENOISE_EXPORTS = ("crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_den
 DEFAULTS = {"iterations": 3, "sigma_color": 4.0, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
 H5 = np.array([1.0 / 16, 1.0 / 4, 3.0 / 8, 1.0 / 4, 1.0 / 16], dtype=np.float32)
 F = np.float32
+assert_bits = util.assert_bits
 
 
 def restated(color, albedo=None, normal=None, depth=None, iterations=3, sigma_color=4.0, sigma_normal=0.5, sigma_albedo=0.1,
@@ -69,14 +70,6 @@ def restated(color, albedo=None, normal=None, depth=None, iterations=3, sigma_co
             c = num / den[..., None]
     assert c.dtype == F
     return c
-
-
-def assert_bits(got, want, where=""):
-    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
-    assert got.shape == want.shape, (where, got.shape, want.shape)
-    nan = np.isnan(want)
-    same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
-    assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
 
 
 def check_against_restatement(color, where, want_rgb=True, **kw):

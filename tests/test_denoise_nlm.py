@@ -21,6 +21,7 @@ import util
 DEFAULTS = {"radius": 5, "patch": 1, "k": 0.7, "alpha": 1.0, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
 K3 = np.array([1.0 / 4, 1.0 / 2, 1.0 / 4], dtype=np.float32)
 F = np.float32
+assert_bits = util.assert_bits
 NLM_EXPORTS = ("crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device")
 FORMS = ("direct", "shared")
 
@@ -104,14 +105,6 @@ def restated(color, variance, albedo=None, normal=None, depth=None, radius=5, pa
         var = vnum / (den * den)
     assert mean.dtype == F and var.dtype == F
     return mean, var
-
-
-def assert_bits(got, want, where=""):
-    got, want = np.ascontiguousarray(got, dtype=F), np.ascontiguousarray(want, dtype=F)
-    assert got.shape == want.shape, (where, got.shape, want.shape)
-    nan = np.isnan(want)
-    same = np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
-    assert same.all(), "%s: %d of %d values differ (first at %r)" % (where, int((~same).sum()), same.size, tuple(np.argwhere(~same)[0]))
 
 
 def check_against_restatement(color, variance, where, want_rgb=True, **kw):

@@ -16,18 +16,17 @@ CPU tests: the entry point's argument checks; csrc/crt_detmath.h compiled for th
 fixture where oracle/_ref/path_probe exists); and anchors of the oracle against numpy float64, so that "the device equals the oracle"
 means something."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import cudaraytracing_amd as crt
 import device_fn_sets as DS
+import host_program as HP
 import oracle_lib as O
 import reference_pin as RP
 from cudaraytracing_amd import _capi as capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F, U = np.float32, np.uint32
 gpu = pytest.mark.gpu
 live = pytest.mark.skipif(not RP.have_probe(), reason="oracle/_ref/path_probe is not built (needs the reference tree: make -C oracle)")
@@ -92,13 +91,6 @@ def test_device_fn_argument_checks_need_no_device():
 HOST_FNS = ("sin", "cos", "tan", "asin", "acos", "atan", "exp", "log", "log10", "sincos.s", "sincos.c", "uniform")
 
 
-def _build_host_check(tmp, name, extra):
-    exe = os.path.join(tmp, name)
-    subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "cudaraytracing_amd", "csrc")] + extra +
-                   [os.path.join(ROOT, "tools", "detmath_host_check.cpp"), "-o", exe], check=True, cwd=ROOT, timeout=600)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def host_check_run(tmp_path_factory):
     """both builds of tools/detmath_host_check.cpp run on X + borders and the pairs: (x, a, b, bytes plain, status and bytes sanitised)"""
@@ -108,13 +100,7 @@ def host_check_run(tmp_path_factory):
     job = os.path.join(tmp, "in.bin")
     with open(job, "wb") as f:
         f.write(np.array([x.size], dtype="<u4").tobytes() + x.tobytes() + np.array([a.size], dtype="<u4").tobytes() + a.tobytes() + b.tobytes())
-    res = []
-    for name, extra in (("plain", ["-O2"]), ("sanitised", ["-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all"])):
-        exe = _build_host_check(tmp, "detmath_host_check_" + name, extra)
-        outp = os.path.join(tmp, name + ".bin")
-        p = subprocess.run([exe, job, outp], cwd=ROOT, capture_output=True, text=True, timeout=600)
-        res.append((p.returncode, open(outp, "rb").read() if os.path.exists(outp) else b"", p.stderr[-2000:]))
-    return x, a, b, res
+    return x, a, b, HP.run_both_forms("detmath_host_check.cpp", tmp, job)
 
 
 def test_detmath_header_on_the_host_gives_the_oracle_bits(host_check_run):

@@ -15,6 +15,7 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
+import host_program as HP
 import oracle_lib as O
 import util
 
@@ -242,13 +243,6 @@ def test_restatement_picks_the_blur_on_the_flat_half_and_the_identity_on_the_che
         assert mse(mean) < min(candidates), (seed, mse(mean), candidates)
 
 
-def _build_host_check(tmp, name, extra):
-    exe = os.path.join(tmp, name)
-    subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-I" + os.path.join(ROOT, "cudaraytracing_amd", "csrc")] + extra +
-                   [os.path.join(ROOT, "tools", "select_host_check.cpp"), "-o", exe], check=True, cwd=ROOT, timeout=600)
-    return exe
-
-
 @pytest.fixture(scope="module")
 def host_check_run(tmp_path_factory):
     """both builds of tools/select_host_check.cpp run over CASES, each with every output and with one output at a time:
@@ -264,13 +258,7 @@ def host_check_run(tmp_path_factory):
     job = os.path.join(tmp, "in.bin")
     with open(job, "wb") as f:
         f.write(b"".join(blob))
-    res = []
-    for name, extra in (("plain", ["-O2"]), ("sanitised", ["-O1", "-g", "-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=all"])):
-        exe = _build_host_check(tmp, "select_host_check_" + name, extra)
-        outp = os.path.join(tmp, name + ".bin")
-        p = subprocess.run([exe, job, outp], cwd=ROOT, capture_output=True, text=True, timeout=600)
-        res.append((p.returncode, open(outp, "rb").read() if os.path.exists(outp) else b"", (p.stdout + p.stderr)[-2000:]))
-    return jobs, res
+    return jobs, HP.run_both_forms("select_host_check.cpp", tmp, job)
 
 
 def test_kernel_text_on_the_host_gives_the_restatement_bits(host_check_run):

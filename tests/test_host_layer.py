@@ -318,7 +318,8 @@ int use(Scene* scene, Eigen::Vector3f eye, Eigen::Matrix3f inv_view, float fov_y
     return fb ? 0 : 1;
 }
 ''')
-    cmd = ["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror=narrowing", "-I", os.path.join(util.ROOT, "include"),
+    from host_program import CXX
+    cmd = [CXX, "-std=c++17", "-fsyntax-only", "-Wall", "-Werror=narrowing", "-I", os.path.join(util.ROOT, "include"),
            "-I", os.path.join(util.ROOT, "tests", "shim_decls"), str(tmp_path / "main.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,26 +7,23 @@ scene's tree, and with it the frame TIME, does not depend on the machine's core 
 libcrt.so, no device."""
 import json
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program as HP
 
 
 @pytest.mark.parametrize("scene", ["cornell-box", "veach-mis"])
 def test_batched_pass_is_deterministic_valid_and_as_good_as_the_serial_pass(tmp_path, scene):
     from cudaraytracing_amd import build as b
     b.build_lib()
-    exe = str(tmp_path / "sah_opt_bench")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + os.path.join(ROOT, "include"), "-I" + b.CSRC, os.path.join(ROOT, "tools", "sah_opt_bench.cpp"),
-                    "-L" + b.LIBDIR, "-lcrt", "-Wl,-rpath," + b.LIBDIR, "-o", exe], check=True, cwd=ROOT, timeout=600)
+    exe = HP.build("sah_opt_bench.cpp", str(tmp_path / "sah_opt_bench"),
+                   extra=["-pthread", "-I" + os.path.join(HP.ROOT, "include"), "-L" + b.LIBDIR, "-lcrt", "-Wl,-rpath," + b.LIBDIR])
     areas = set()
     for threads in ("3", "8"):
-        p = subprocess.run([exe, os.path.join("scenes", scene, "config.json"), "1"], cwd=ROOT, capture_output=True, text=True, timeout=300,
-                           env=dict(os.environ, CRT_SAH_OPT_THREADS=threads))
-        assert p.returncode == 0, p.stderr[-2000:]
-        first = json.loads(p.stdout.splitlines()[0])
+        rc, out, err = HP.run(exe, [os.path.join("scenes", scene, "config.json"), "1"], timeout=300, env=dict(os.environ, CRT_SAH_OPT_THREADS=threads))
+        assert rc == 0, err
+        first = json.loads(out.splitlines()[0])
         assert first["one_thread_equals_many"] is True and first["valid_tree"] is True, first
         assert first["summed_area_batched"] < first["summed_area_built"], first
         assert first["summed_area_batched"] <= first["summed_area_serial"] * 1.001, first

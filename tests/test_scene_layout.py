@@ -10,6 +10,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
+import host_program as HP
 import tree_check as TC
 import util
 from test_gpu_parity import _write_box_scene, _write_soup_scene
@@ -20,10 +21,7 @@ COUNTS = ["n_leaves", "n_nodes2", "n_nodes4", "depth2", "depth4", "index_splits"
 
 @pytest.fixture(scope="module")
 def tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("layout_tool") / "scene_layout_dump")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-ffp-contract=off", "-fno-fast-math", "-I" + os.path.join(util.ROOT, "cudaraytracing_amd", "csrc"),
-                    os.path.join(util.ROOT, "tools", "scene_layout_dump.cpp"), "-o", exe], check=True, cwd=util.ROOT, timeout=600)
-    return exe
+    return HP.build("scene_layout_dump.cpp", str(tmp_path_factory.mktemp("layout_tool") / "scene_layout_dump"), extra=["-pthread", "-fno-fast-math"])
 
 
 def _make(name, d):

@@ -3,19 +3,15 @@ an inner child's planes (csrc/crt_scene_layout.h).  A nudge in the wrong directi
 allow (crt_accel.h).  tools/with_bits_check.cpp runs every input with all 4 096 chunks, moving down and up: a result that is finite, carries
 the chunk, lies on the asked side of the input and is the nearest such value; a give-up exactly when no finite such value exists."""
 import json
-import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_program as HP
 
 
 def test_with_bits_is_the_nearest_value_with_the_chunk_on_the_asked_side(tmp_path):
-    exe = str(tmp_path / "with_bits_check")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-pthread", "-I" + os.path.join(ROOT, "cudaraytracing_amd", "csrc"),
-                    os.path.join(ROOT, "tools", "with_bits_check.cpp"), "-o", exe], check=True, cwd=ROOT, timeout=600)
-    p = subprocess.run([exe, "1000000", "7"], cwd=ROOT, capture_output=True, text=True, timeout=900)
-    r = json.loads(p.stdout.splitlines()[0])
-    assert p.returncode == 0 and r["violations"] == 0, r
+    exe = HP.build("with_bits_check.cpp", str(tmp_path / "with_bits_check"), extra=["-pthread"])
+    rc, out, _ = HP.run(exe, ["1000000", "7"], timeout=900)
+    r = json.loads(out.splitlines()[0])
+    assert rc == 0 and r["violations"] == 0, r
     assert r["calls"] == r["inputs"] * 4096 * 2 and r["inputs"] >= 1000000 + r["special"]
     # every branch was taken: results on both sides of zero, crossings of zero, and give-ups (non-finite inputs, +-FLT_MAX's neighbours)
     assert r["ok"] > 0 and r["crossed_zero"] > 0 and r["gave_up"] > 0, r

@@ -1,0 +1,143 @@
+// tools/host_device.h -- what the tools/*_host_check.cpp programs put in the device's place, stated once.  Those programs compile kernel
+// text of cudaraytracing_amd/csrc (headers that include nothing, crt_sample_map.hip, crt_adaptive.hip) for the HOST and run it against
+// plain restatements under AddressSanitizer / UBSan; this header supplies what that text takes from outside: the HIP qualifiers and
+// types, the atomics and bit casts, the few definitions of crt_device.h / crt_path.h it uses, and the launch with its indices.
+// A program that defines CRT_HOST_WAVES before the include gets a wave of 64 host threads with the cross-lane operations (and needs
+// -pthread); without it a launch is a plain loop over blocks and threads, for kernels that have no cross-lane operation.
+//
+// Every program builds with one line (tests/host_program.py; the threaded ones add -pthread):
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow \
+//       -fno-sanitize-recover=all tools/NAME_host_check.cpp -o /tmp/NAME_host_check && /tmp/NAME_host_check
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#ifdef CRT_HOST_WAVES
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include <vector>
+#endif
+
+#include "crt_detmath.h"
+#include "crt_fastdiv.h"
+
+// ---- stand-ins for the device ----
+#define __global__
+#define __device__
+#define __host__
+#define __forceinline__ inline
+#define __launch_bounds__(n)
+#define CRT_TILE 8 // crt_device.h
+struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
+typedef void* hipStream_t;
+struct alignas(16) float4 { float x, y, z, w; };
+static float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+#define __HIP_MEMORY_SCOPE_AGENT 0
+#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
+#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
+#define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
+static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
+static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
+using std::max;
+using std::min;
+
+// ---- what the kernel text takes from crt_device.h / crt_path.h: the same text ----
+namespace crtk {
+using namespace crtdev; // FastDiv, make_fastdiv, det_powf, det_expf, U4, rng_draw, rng_uniform
+// crt_device.h: fast_div (its host branch)
+static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
+{
+    const uint32_t t = (uint32_t)(((uint64_t)m * n) >> 32);
+    return (t + ((n - t) >> (sh & 255u))) >> (sh >> 8);
+}
+// crt_device.h: F3, f3
+struct F3 { float x, y, z; };
+static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
+// crt_device.h: maxf_ref, minf_ref
+static float maxf_ref(float x, float y) { return x > y ? x : y; }
+static float minf_ref(float x, float y) { return x < y ? x : y; }
+// crt_path.h: Rad3
+struct Rad3 { float x, y, z; };
+// crt_path.h: load_radiance (there one 12-byte load of the three floats)
+static Rad3 load_radiance(const Rad3* p) { return *p; }
+// crt_path.h: slot_to_pixel
+static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t n_tiles, uint32_t tiles_x, FastDiv tiles_x_div, uint32_t width, uint32_t height,
+                          uint32_t& i, uint32_t& j)
+{
+    uint32_t tile = (slot >> 6) * world + rank;
+    uint32_t pix = slot & 63u;
+    if (tile >= n_tiles) return false;
+    uint32_t ty = fast_div(tile, tiles_x_div.m, tiles_x_div.sh), tx = tile - ty * tiles_x;
+    i = tx * CRT_TILE + (pix & 7u);
+    j = ty * CRT_TILE + (pix >> 3);
+    return i < width && j < height;
+}
+} // namespace crtk
+
+// ---- the launch: its indices, and with CRT_HOST_WAVES the wave ----
+struct Idx { uint32_t x; };
+static thread_local Idx blockIdx, threadIdx, gridDim;
+
+#ifndef CRT_HOST_WAVES
+// a launch of kernels without a cross-lane operation: a plain loop over blocks and threads
+template <class K, class... P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, P... params)
+{
+    gridDim.x = grid.x;
+    for (uint32_t b = 0; b < grid.x; b++)
+        for (uint32_t t = 0; t < block.x; t++) { blockIdx.x = b; threadIdx.x = t; kernel(params...); }
+}
+#else
+// A wave is 64 host threads that meet at a barrier in every cross-lane operation, so a ballot sees all its lanes' predicates as the
+// hardware's does.
+struct Wave { // the 64 lanes of the wave that is running
+    std::mutex m;
+    std::condition_variable cv;
+    int waiting = 0;
+    unsigned long gen = 0;
+    int in[64], vals[64];
+    // The barrier: every lane hands in a value and returns when all 64 have, with the 64 values in vals.  (vals is written again by
+    // the last lane to reach the NEXT barrier, so after every lane has read it.)
+    void barrier(int v = 0)
+    {
+        std::unique_lock<std::mutex> l(m);
+        in[threadIdx.x & 63] = v;
+        const unsigned long g = gen;
+        if (++waiting == 64) { waiting = 0; std::copy(in, in + 64, vals); gen++; cv.notify_all(); }
+        else cv.wait(l, [&] { return gen != g; });
+    }
+};
+static Wave g_wave;
+static unsigned long long __ballot(bool p)
+{
+    g_wave.barrier(p);
+    unsigned long long m = 0;
+    for (int lane = 0; lane < 64; lane++) m |= (unsigned long long)(g_wave.vals[lane] != 0) << lane;
+    return m;
+}
+static int __builtin_amdgcn_readlane(int v, int lane_from)
+{
+    g_wave.barrier(v);
+    return g_wave.vals[lane_from];
+}
+static int __ffsll(long long v) { return __builtin_ffsll(v); }
+static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
+
+// a launch: block after block, wave after wave (a block of 64 threads is one wave).  The 64 lane threads live for the whole launch
+// and meet at the end of every wave, so a wave starts when the one before it has ended.
+template <class K, class... P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, P... params)
+{
+    std::vector<std::thread> lanes;
+    for (uint32_t l = 0; l < 64; l++)
+        lanes.emplace_back([=] {
+            gridDim.x = grid.x;
+            for (uint32_t b = 0; b < grid.x; b++)
+                for (uint32_t w0 = 0; w0 < block.x; w0 += 64) {
+                    blockIdx.x = b; threadIdx.x = w0 + l;
+                    kernel(params...);
+                    g_wave.barrier();
+                }
+        });
+    for (std::thread& t : lanes) t.join();
+}
+#endif

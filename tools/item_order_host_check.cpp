@@ -1,99 +1,24 @@
 // tools/item_order_host_check.cpp -- k_order_items (cudaraytracing_amd/csrc/crt_item_order.h: the roulette length, the classes, the count
 // pass and the place pass) compiled for the HOST and run against plain restatements, for AddressSanitizer / UBSan runs without a device.
-// The header is included as it is; this file stands in for what it takes from crt_path.h and crt_device.h (the same text: decode_item,
-// slot_to_pixel, roulette, the fields of LParams they read) and for the device's launch indices, wave intrinsics and atomics.  A wave is 64
-// host threads that meet at a barrier in every cross-lane operation, as in tools/sample_map_host_check.cpp.
+// The header is included as it is; tools/host_device.h stands in for the device's launch indices, wave intrinsics and atomics and for
+// slot_to_pixel, and this file for the rest of what the header takes from crt_path.h (the same text: decode_item, roulette, the fields of
+// LParams they read).  A wave is 64 host threads that meet at a barrier in every cross-lane operation, as in
+// tools/sample_map_host_check.cpp; every block here is one wave.
 // Every buffer is sized exactly (std::vector of the element count the host code allocates), so an access one element out is a report.
 //
-//   g++ -std=c++17 -O1 -g -pthread -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/item_order_host_check.cpp -o /tmp/item_order_host_check && /tmp/item_order_host_check
-#include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <cstdint>
+// tests/test_host_checks.py builds and runs it:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       -pthread tools/item_order_host_check.cpp -o /tmp/item_order_host_check && /tmp/item_order_host_check
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
-#include <thread>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
+#define CRT_HOST_WAVES
+#include "host_device.h"
 
-// ---- stand-ins for the device ----
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
+// ---- what the header takes from crt_path.h beyond host_device.h: the same text ----
 #define CRT_BOUNCE_STACK_SIZE 64
-struct Idx { uint32_t x; };
-static thread_local Idx blockIdx, threadIdx;
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-
-struct Wave { // the 64 lanes of the wave that is running
-    std::mutex m;
-    std::condition_variable cv;
-    int waiting = 0;
-    unsigned long gen = 0;
-    std::atomic<unsigned long long> bits{0};
-    int vals[64];
-    void barrier()
-    {
-        std::unique_lock<std::mutex> l(m);
-        const unsigned long g = gen;
-        if (++waiting == 64) { waiting = 0; gen++; cv.notify_all(); }
-        else cv.wait(l, [&] { return gen != g; });
-    }
-};
-static Wave g_wave;
-static unsigned long long __ballot(bool p)
-{
-    const int lane = threadIdx.x & 63;
-    if (p) g_wave.bits.fetch_or(1ull << lane);
-    g_wave.barrier();
-    const unsigned long long m = g_wave.bits.load();
-    g_wave.barrier();
-    if (lane == 0) g_wave.bits.store(0);
-    g_wave.barrier();
-    return m;
-}
-static int __builtin_amdgcn_readlane(int v, int lane_from)
-{
-    g_wave.vals[threadIdx.x & 63] = v;
-    g_wave.barrier();
-    const int r = g_wave.vals[lane_from];
-    g_wave.barrier();
-    return r;
-}
-static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-#define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
-using std::max;
-using std::min;
-
-// a launch of one-wave blocks: block after block, 64 threads each
-template <class K, class... P> static void launch(K kernel, uint32_t blocks, P... params)
-{
-    for (uint32_t b = 0; b < blocks; b++) {
-        std::vector<std::thread> lanes;
-        for (uint32_t l = 0; l < 64; l++)
-            lanes.emplace_back([=] { blockIdx.x = b; threadIdx.x = l; kernel(params...); });
-        for (std::thread& t : lanes) t.join();
-    }
-}
-
-// ---- what the header takes from crt_path.h: the same text ----
 namespace crtk {
-using namespace crtdev; // FastDiv, make_fastdiv, U4, rng_draw, rng_uniform, RNG_BOUNCE
-static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
-{
-    const uint32_t t = (uint32_t)(((uint64_t)m * n) >> 32);
-    return (t + ((n - t) >> (sh & 255u))) >> (sh >> 8);
-}
 struct LParams { // (the fields k_order_items and decode_item read)
     uint32_t width, height;
     float p_rr;
@@ -106,17 +31,6 @@ struct LParams { // (the fields k_order_items and decode_item read)
     uint32_t spsh;
     FastDiv spsh_div;
 };
-static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t n_tiles, uint32_t tiles_x, FastDiv tiles_x_div, uint32_t width, uint32_t height,
-                          uint32_t& i, uint32_t& j)
-{
-    uint32_t tile = (slot >> 6) * world + rank;
-    uint32_t pix = slot & 63u;
-    if (tile >= n_tiles) return false;
-    uint32_t ty = fast_div(tile, tiles_x_div.m, tiles_x_div.sh), tx = tile - ty * tiles_x;
-    i = tx * CRT_TILE + (pix & 7u);
-    j = ty * CRT_TILE + (pix >> 3);
-    return i < width && j < height;
-}
 template <bool RING = false>
 static void decode_item(const LParams& P, uint32_t item, uint32_t& pixel_index, uint32_t& k, bool& valid, uint32_t& pi, uint32_t& pj)
 {
@@ -217,12 +131,13 @@ static void run_case(uint32_t w, uint32_t h, uint32_t rank, uint32_t world, uint
     const uint32_t sentinel = 0xfffffffeu;
     std::vector<uint32_t> list((size_t)n_sh * P.order_window, sentinel);
     std::vector<unsigned int> cnt((size_t)n_sh * C.n * 32, 0u);
+    const dim3 grid(n_sh * spans), block(64); // one wave per block
     if (ring) {
-        launch(k_order_items<true, false>, n_sh * spans, P, C, list.data(), cnt.data());
-        launch(k_order_items<true, true>, n_sh * spans, P, C, list.data(), cnt.data());
+        hipLaunchKernelGGL(k_order_items<true, false>, grid, block, 0, nullptr, P, C, list.data(), cnt.data());
+        hipLaunchKernelGGL(k_order_items<true, true>, grid, block, 0, nullptr, P, C, list.data(), cnt.data());
     } else {
-        launch(k_order_items<false, false>, n_sh * spans, P, C, list.data(), cnt.data());
-        launch(k_order_items<false, true>, n_sh * spans, P, C, list.data(), cnt.data());
+        hipLaunchKernelGGL(k_order_items<false, false>, grid, block, 0, nullptr, P, C, list.data(), cnt.data());
+        hipLaunchKernelGGL(k_order_items<false, true>, grid, block, 0, nullptr, P, C, list.data(), cnt.data());
     }
     const uint32_t cap = C.lo[C.n - 1];
     for (uint32_t sh = 0; sh < n_sh; sh++) {

@@ -1,62 +1,22 @@
 // tools/modulate_host_check.cpp -- the kernels of crt_demodulate / crt_modulate (cudaraytracing_amd/csrc/crt_modulate.h) compiled for the
 // HOST and run against a plain restatement, for AddressSanitizer / UBSan runs without a device.  crt_modulate.h and crt_stages.h (the
-// tone map) are included as they are; this file stands in for what they take from outside, as tools/sample_map_host_check.cpp does.
+// tone map) are included as they are; tools/host_device.h stands in for what they take from outside.
 // The kernels have no cross-lane operation, so a launch is a plain loop over blocks and threads.
 // Every buffer is sized exactly (std::vector of the image's 3 x W x H values), so an access one element out is a report; float4 keeps
 // its 16-byte alignment here, so a 16-byte access through a pointer that is not aligned is a report as well.  The sizes are ragged
 // (3 x W x H is no multiple of four), each is run with aligned bases (the 16-byte path and the scalar tail), with bases one float off
 // (the scalar path on every quad) and with a grid capped to one block (the stride loop).
 //
-//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/modulate_host_check.cpp -o /tmp/modulate_host_check && /tmp/modulate_host_check
-#include <algorithm>
+// tests/test_host_checks.py builds and runs it:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       tools/modulate_host_check.cpp -o /tmp/modulate_host_check && /tmp/modulate_host_check
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
-
-// ---- stand-ins for the device ----
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
-struct Idx { uint32_t x; };
-static Idx blockIdx, threadIdx, gridDim;
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-typedef void* hipStream_t;
-struct alignas(16) float4 { float x, y, z, w; };
-static float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
-static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
-
-template <class K, class P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, P params)
-{
-    gridDim.x = grid.x;
-    for (uint32_t b = 0; b < grid.x; b++)
-        for (uint32_t t = 0; t < block.x; t++) { blockIdx.x = b; threadIdx.x = t; kernel(params); }
-}
-
-// ---- what crt_stages.h takes from crt_path.h / crt_device.h: the same text ----
-namespace crtk {
-using namespace crtdev; // FastDiv, det_powf
-struct F3 { float x, y, z; };
-static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-static float maxf_ref(float x, float y) { return x > y ? x : y; }
-static float minf_ref(float x, float y) { return x < y ? x : y; }
-struct Rad3 { float x, y, z; };
-static Rad3 load_radiance(const Rad3* p) { return *p; }
-static bool slot_to_pixel(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, FastDiv, uint32_t, uint32_t, uint32_t&, uint32_t&) { return false; } // (no slot map here)
-} // namespace crtk
+#include "host_device.h"
 
 #include "crt_stages.h"
 #include "crt_modulate.h"

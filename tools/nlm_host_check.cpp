@@ -1,6 +1,6 @@
 // tools/nlm_host_check.cpp -- the two forms of crt_denoise_nlm (cudaraytracing_amd/csrc/crt_nlm.h) compiled for the HOST, for
-// AddressSanitizer / UBSan runs without a device.  crt_nlm.h and crt_stages.h (the tone map, write_color) are included as they are; this
-// file stands in for what they take from outside, as tools/modulate_host_check.cpp does.
+// AddressSanitizer / UBSan runs without a device.  crt_nlm.h and crt_stages.h (the tone map, write_color) are included as they are;
+// tools/host_device.h stands in for what they take from outside.
 // The shared form's kernel (k_nlm_shared, crt_nlm.hip) is its phases with workgroup barriers in between; here a barrier is "every
 // thread of the workgroup has run the phase": the same sequence as loops over the thread index.  The three LDS arrays are std::vectors of
 // exactly nlm_stage_elems / nlm_d_elems / nlm_row_elems entries (what nlm_lds_bytes hands the launch) and every image plane has exactly
@@ -10,47 +10,16 @@
 // tile, for ragged images of 2 x 2 and more tiles (tiles at all four corners) and for the limits radius 8 / patch 3, the shared order
 // against the direct order on random inputs with zero-variance and zero-depth blocks and NULL guides: mean, RGB and variance bit for bit.
 //
-//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/nlm_host_check.cpp -o /tmp/nlm_host_check && /tmp/nlm_host_check
-#include <algorithm>
+// tests/test_host_checks.py builds and runs it:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       tools/nlm_host_check.cpp -o /tmp/nlm_host_check && /tmp/nlm_host_check
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
-
-// ---- stand-ins for the device ----
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-typedef void* hipStream_t;
-struct alignas(16) float4 { float x, y, z, w; };
-static float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
-static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
-
-// ---- what crt_stages.h takes from crt_path.h / crt_device.h: the same text ----
-namespace crtk {
-using namespace crtdev; // FastDiv, det_powf, det_expf
-struct F3 { float x, y, z; };
-static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-static float maxf_ref(float x, float y) { return x > y ? x : y; }
-static float minf_ref(float x, float y) { return x < y ? x : y; }
-struct Rad3 { float x, y, z; };
-static Rad3 load_radiance(const Rad3* p) { return *p; }
-static bool slot_to_pixel(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, FastDiv, uint32_t, uint32_t, uint32_t&, uint32_t&) { return false; } // (no slot map here)
-} // namespace crtk
+#include "host_device.h"
 
 #include "crt_stages.h"
 #include "crt_nlm.h"

@@ -1,124 +1,22 @@
 // tools/sample_map_host_check.cpp -- the kernels of cudaraytracing_amd/csrc/crt_sample_map.hip and crt_adaptive.hip compiled for the HOST
 // and run against plain restatements, for AddressSanitizer / UBSan runs without a device.  The kernel files and the stages they share
-// (crt_stages.h) are included as they are; this file stands in for what they take from crt_path.h and crt_device.h (the same text) and
-// for the device's launch indices, wave intrinsics and atomics.  A wave is 64 host threads that meet at a barrier in every cross-lane
+// (crt_stages.h) are included as they are; tools/host_device.h stands in for what they take from crt_path.h and crt_device.h and for the
+// device's launch indices, wave intrinsics and atomics.  A wave is 64 host threads that meet at a barrier in every cross-lane
 // operation, so a ballot sees all its lanes' predicates as the hardware's does; a block is run wave after wave.
 // Every buffer is sized exactly (std::vector of the element count the host code allocates), so an access one element out is a report.
 //
-//   g++ -std=c++17 -O1 -g -pthread -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/sample_map_host_check.cpp -o /tmp/sample_map_host_check && /tmp/sample_map_host_check
-#include <algorithm>
-#include <atomic>
+// tests/test_host_checks.py builds and runs it:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       -pthread tools/sample_map_host_check.cpp -o /tmp/sample_map_host_check && /tmp/sample_map_host_check
 #include <cmath>
-#include <condition_variable>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <set>
-#include <thread>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
-
-// ---- stand-ins for the device ----
-#define CRT_INTERNAL_H // (the kernel files' only include: replaced by what follows)
-#define __global__
-#define __device__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
-struct Idx { uint32_t x; };
-static thread_local Idx blockIdx, threadIdx;
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-typedef void* hipStream_t;
-
-struct Wave { // the 64 lanes of the wave that is running
-    std::mutex m;
-    std::condition_variable cv;
-    int waiting = 0;
-    unsigned long gen = 0;
-    std::atomic<unsigned long long> bits{0};
-    int vals[64];
-    void barrier()
-    {
-        std::unique_lock<std::mutex> l(m);
-        const unsigned long g = gen;
-        if (++waiting == 64) { waiting = 0; gen++; cv.notify_all(); }
-        else cv.wait(l, [&] { return gen != g; });
-    }
-};
-static Wave g_wave;
-static unsigned long long __ballot(bool p)
-{
-    const int lane = threadIdx.x & 63;
-    if (p) g_wave.bits.fetch_or(1ull << lane);
-    g_wave.barrier();
-    const unsigned long long m = g_wave.bits.load();
-    g_wave.barrier();
-    if (lane == 0) g_wave.bits.store(0);
-    g_wave.barrier();
-    return m;
-}
-static int __builtin_amdgcn_readlane(int v, int lane_from)
-{
-    g_wave.vals[threadIdx.x & 63] = v;
-    g_wave.barrier();
-    const int r = g_wave.vals[lane_from];
-    g_wave.barrier();
-    return r;
-}
-static int __ffsll(long long v) { return __builtin_ffsll(v); }
-static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-#define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
-using std::max;
-using std::min;
-static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
-static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
-
-// a launch: block after block, wave after wave, 64 threads each
-template <class K, class... P> static void hipLaunchKernelGGL(K kernel, dim3 grid, dim3 block, int, hipStream_t, P... params)
-{
-    for (uint32_t b = 0; b < grid.x; b++)
-        for (uint32_t w0 = 0; w0 < block.x; w0 += 64) {
-            std::vector<std::thread> lanes;
-            for (uint32_t l = 0; l < 64; l++)
-                lanes.emplace_back([=] { blockIdx.x = b; threadIdx.x = w0 + l; kernel(params...); });
-            for (std::thread& t : lanes) t.join();
-        }
-}
-
-// ---- what the kernels and crt_stages.h take from crt_path.h / crt_device.h: the same text ----
-namespace crtk {
-using namespace crtdev; // FastDiv, make_fastdiv, det_powf
-static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
-{
-    const uint32_t t = (uint32_t)(((uint64_t)m * n) >> 32);
-    return (t + ((n - t) >> (sh & 255u))) >> (sh >> 8);
-}
-struct F3 { float x, y, z; };
-static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-static float maxf_ref(float x, float y) { return x > y ? x : y; }
-static float minf_ref(float x, float y) { return x < y ? x : y; }
-struct Rad3 { float x, y, z; };
-static Rad3 load_radiance(const Rad3* p) { return *p; }
-static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t n_tiles, uint32_t tiles_x, FastDiv tiles_x_div, uint32_t width, uint32_t height,
-                          uint32_t& i, uint32_t& j)
-{
-    uint32_t tile = (slot >> 6) * world + rank;
-    uint32_t pix = slot & 63u;
-    if (tile >= n_tiles) return false;
-    uint32_t ty = fast_div(tile, tiles_x_div.m, tiles_x_div.sh), tx = tile - ty * tiles_x;
-    i = tx * CRT_TILE + (pix & 7u);
-    j = ty * CRT_TILE + (pix >> 3);
-    return i < width && j < height;
-}
-} // namespace crtk
+#define CRT_INTERNAL_H // (the kernel files' only include: replaced by host_device.h)
+#define CRT_HOST_WAVES
+#include "host_device.h"
 
 #include "crt_stages.h"
 #include "crt_adaptive.hip"

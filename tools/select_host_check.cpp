@@ -1,7 +1,7 @@
 // tools/select_host_check.cpp -- the two kernels of crt_filter_select (cudaraytracing_amd/csrc/crt_select.h) compiled for the HOST and run over
 // the cases of a job file, for AddressSanitizer / UBSan runs without a device and for a bit comparison with the numpy restatement of
-// include/crt.h (tests/test_filter_select.py).  crt_select.h and crt_stages.h (the tone map, write_color) are included as they are; this
-// file stands in for what they take from outside, as tools/upsample_host_check.cpp does.  The kernels (k_select_choose, k_select_blend,
+// include/crt.h (tests/test_filter_select.py).  crt_select.h and crt_stages.h (the tone map, write_color) are included as they are;
+// tools/host_device.h stands in for what they take from outside.  The kernels (k_select_choose, k_select_blend,
 // crt_select.hip) are their phases with a workgroup barrier in between; here a barrier is "every thread of the workgroup has run the
 // phase": the same sequence as loops over the thread index.  The LDS arrays are std::vectors of exactly select_choose_lds_bytes /
 // select_blend_lds_bytes, filled with NaN (0xff bytes) before a workgroup runs, and every image has exactly its entries: a staging, tap
@@ -13,44 +13,15 @@
 //   OUT: per case mean (w h 3 f32), rgb (w h 3 u8), choice (w h u8), error (w h f32), chosen (4 u64); an output that was not asked for
 //        keeps its fill (0x5a bytes)
 //
-//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/select_host_check.cpp -o /tmp/select_host_check
+// tests/test_filter_select.py builds it plain (-O2) and sanitised and runs both:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       tools/select_host_check.cpp -o /tmp/select_host_check
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
-
-// ---- stand-ins for the device ----
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-typedef void* hipStream_t;
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
-static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
-
-// ---- what crt_stages.h takes from crt_path.h / crt_device.h: the same text ----
-namespace crtk {
-using namespace crtdev; // FastDiv, det_powf
-struct F3 { float x, y, z; };
-static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-static float maxf_ref(float x, float y) { return x > y ? x : y; }
-static float minf_ref(float x, float y) { return x < y ? x : y; }
-struct Rad3 { float x, y, z; };
-static Rad3 load_radiance(const Rad3* p) { return *p; }
-static bool slot_to_pixel(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, FastDiv, uint32_t, uint32_t, uint32_t&, uint32_t&) { return false; } // (no slot map here)
-} // namespace crtk
+#include "host_device.h"
 
 #include "crt_stages.h"
 #include "crt_select.h"

@@ -1,7 +1,7 @@
 // tools/upsample_host_check.cpp -- the two forms of crt_upsample (cudaraytracing_amd/csrc/crt_upsample.h) compiled for the HOST and run
 // against a scalar restatement of include/crt.h, for AddressSanitizer / UBSan runs without a device.  crt_upsample.h and crt_stages.h
-// (the tone map, write_color) are included as they are; this file stands in for what they take from outside, as
-// tools/nlm_host_check.cpp does.  The kernel (k_upsample, crt_upsample.hip) is its two phases with a workgroup barrier in between; here
+// (the tone map, write_color) are included as they are; tools/host_device.h stands in for what they take from
+// outside.  The kernel (k_upsample, crt_upsample.hip) is its two phases with a workgroup barrier in between; here
 // the barrier is "every thread of the workgroup has run the phase": the same sequence as loops over the thread index.  The LDS array is
 // a std::vector of exactly kUpsamplePlanes x upsample_stage_cap entries (what upsample_lds_bytes hands the launch), filled with NaN
 // before a workgroup runs, and every image plane has exactly its image's entries: a staging, tap or output index one element out is a
@@ -11,46 +11,16 @@
 // window, one pixel in a second wave, a single tap, equal sizes -- and the widest tile (radius 4 at equal sizes), each with every
 // combination of guide pairs, with and without a variance, with one output at a time, and with NaN, +-inf and -0 in every buffer.
 //
-//   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
-//       -I cudaraytracing_amd/csrc tools/upsample_host_check.cpp -o /tmp/upsample_host_check && /tmp/upsample_host_check
-#include <algorithm>
+// tests/test_host_checks.py builds and runs it:
+//   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all \
+//       tools/upsample_host_check.cpp -o /tmp/upsample_host_check && /tmp/upsample_host_check
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <limits>
 #include <vector>
 
-#include "crt_detmath.h"
-#include "crt_fastdiv.h"
-
-// ---- stand-ins for the device ----
-#define __global__
-#define __device__
-#define __host__
-#define __forceinline__ inline
-#define __launch_bounds__(n)
-#define CRT_TILE 8
-struct dim3 { uint32_t x; dim3(uint32_t x_ = 1) : x(x_) {} };
-typedef void* hipStream_t;
-#define __HIP_MEMORY_SCOPE_AGENT 0
-#define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
-#define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
-static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
-static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
-
-// ---- what crt_stages.h takes from crt_path.h / crt_device.h: the same text ----
-namespace crtk {
-using namespace crtdev; // FastDiv, det_powf, det_expf
-struct F3 { float x, y, z; };
-static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
-static float maxf_ref(float x, float y) { return x > y ? x : y; }
-static float minf_ref(float x, float y) { return x < y ? x : y; }
-struct Rad3 { float x, y, z; };
-static Rad3 load_radiance(const Rad3* p) { return *p; }
-static bool slot_to_pixel(uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, FastDiv, uint32_t, uint32_t, uint32_t&, uint32_t&) { return false; } // (no slot map here)
-} // namespace crtk
+#include "host_device.h"
 
 #include "crt_stages.h"
 #include "crt_upsample.h"
