@@ -163,6 +163,24 @@ class NlmParams(C.Structure):
                 ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float)]
 
 
+REGRESS_NORMAL, REGRESS_ALBEDO, REGRESS_DEPTH, REGRESS_POSITION = 1, 2, 4, 8  # include/crt.h: CRT_REGRESS_*
+
+
+class RegressParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("radius", C.c_uint32), ("patch", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float),
+                ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float), ("sigma_position", C.c_float), ("ridge", C.c_float),
+                ("features", C.c_uint32)]
+
+
+class RegressInputs(C.Structure):
+    _fields_ = [("color", C.c_void_p), ("variance", C.c_void_p), ("weight_color", C.c_void_p), ("weight_variance", C.c_void_p), ("albedo", C.c_void_p),
+                ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class RegressInfo(InfoStruct):
+    _fields_ = [("total_ms", C.c_float), ("fallback_pixels", C.c_uint64)]
+
+
 class DenoiseInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("passes", C.c_uint32)]
 
@@ -312,7 +330,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_item_order", "crt_aov_specular_defaults", "crt_render_aov_specular", "crt_render_aov_specular_device",
            "crt_render_aov_shading", "crt_render_aov_shading_device", "crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate",
            "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device", "crt_half_buffers", "crt_half_buffers_device",
-           "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device"]
+           "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device",
+           "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device"]
 
 _lib = None
 
@@ -393,6 +412,11 @@ def lib():
                                   C.POINTER(DenoiseInfo)]
     L.crt_denoise_nlm_device.argtypes = [C.c_int, C.POINTER(NlmParams), C.POINTER(DenoiseVarInputs), C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(DenoiseInfo)]
+    L.crt_denoise_regress_defaults.argtypes = [C.POINTER(RegressParams)]
+    L.crt_denoise_regress_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.crt_denoise_regress.argtypes = [C.c_int, C.POINTER(RegressParams), C.POINTER(RegressInputs), C.c_void_p, C.c_void_p, C.POINTER(RegressInfo)]
+    L.crt_denoise_regress_device.argtypes = [C.c_int, C.POINTER(RegressParams), C.POINTER(RegressInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.POINTER(RegressInfo)]
     L.crt_temporal_defaults.argtypes = [C.POINTER(TemporalParams)]
     L.crt_temporal.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalFrame), C.POINTER(TemporalHistory), C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_void_p, C.POINTER(TemporalInfo)]

@@ -563,7 +563,7 @@ class Render:
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
                           sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
-                          demodulate=False, albedo_floor=None, nlm=None):
+                          demodulate=False, albedo_floor=None, nlm=None, regress=None):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
@@ -571,6 +571,9 @@ class Render:
         nlm: True, or a dict of denoise_nlm's settings (radius, patch, k, alpha): render with want_variance and filter with crt_denoise_nlm
         instead of the a-trous filter; the sigma_normal, sigma_albedo and sigma_depth arguments go to it.  It composes with specular_guides
         and demodulate as variance_guided does, and excludes variance_guided, iterations and sigma_color (ValueError).
+        regress: True, or a dict of denoise_regress's settings: render with want_variance and filter with crt_denoise_regress; composes
+        and excludes as nlm does, and excludes nlm.  The sigma arguments scale its features.  With demodulate the albedo feature is
+        dropped from the mask: irradiance does not follow the albedo.  self.denoise_info then holds total_ms and fallback_pixels.
         specular_guides: the albedo guide is guide_albedo of run_view_aov_specular (max_bounces) -- what a mirror reflects instead of the
         mirror; normal and depth stay first-hit.
         demodulate: the filter runs on irradiance.  The shading AOVs (self.shading_buffers: emission, diffuse_albedo) come from the same
@@ -588,7 +591,21 @@ class Render:
             for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
                 if v is not None:
                     nlm_settings[name] = v
-        with_variance = variance_guided or nlm_settings is not None
+        regress_settings = None
+        if regress is not None and regress is not False:
+            if nlm_settings is not None or variance_guided or iterations is not None or sigma_color is not None:
+                raise ValueError("run_view_denoised: regress excludes nlm, variance_guided, iterations and sigma_color")
+            regress_settings = {} if regress is True else dict(regress)
+            unknown = sorted(set(regress_settings) - set(_REGRESS_SETTINGS))
+            if unknown:
+                raise ValueError("run_view_denoised: unknown regress settings %r" % (unknown,))
+            for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
+                if v is not None:
+                    regress_settings[name] = v
+            if demodulate:
+                mask = regress_settings.get("features")
+                regress_settings["features"] = (denoise_regress_defaults()["features"] if mask is None else int(mask)) & ~capi.REGRESS_ALBEDO
+        with_variance = variance_guided or nlm_settings is not None or regress_settings is not None
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=with_variance)
         guides = ("albedo", "normal", "depth")
         if demodulate:
@@ -610,6 +627,9 @@ class Render:
         if nlm_settings is not None:
             rgb, mean, self.denoise_info = denoise_nlm(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **nlm_settings,
                                                        **self.aov_buffers)
+        elif regress_settings is not None:
+            rgb, mean, self.denoise_info = denoise_regress(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **regress_settings,
+                                                           **self.aov_buffers)
         elif variance_guided:
             rgb, mean, self.denoise_info = denoise_var(color, var, **settings, **self.aov_buffers)
         else:
@@ -623,8 +643,9 @@ class Render:
         half frame is smallest (crt_filter_select, contract: include/crt.h).  Renders with want_halves, takes the guides of run_view_aov,
         runs every candidate on each half -- "none" (the half as it is), "atrous" (denoise), "var" (denoise_var) or "nlm" (denoise_nlm),
         each with its own defaults; the variance-taking ones get 2 x the frame's variance, the variance of one half's mean -- and calls
-        filter_select.  Returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32).  Kept: the noisy frame in self.frame_buffer /
-        self.mean_buffer, the guides in self.aov_buffers, self.select_buffers (choice (H, W) uint8, error (H, W) float32, half_a, half_b,
+        filter_select.  "reg" (denoise_regress) filters each half with weights from the OTHER half (weight_color; weight_variance is the
+        half variance), so that a half's weights do not follow its own noise.  Returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32).
+        Kept: the noisy frame in self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, self.select_buffers (choice (H, W) uint8, error (H, W) float32, half_a, half_b,
         half_variance, filtered_a, filtered_b) and self.select_info (total_ms, chosen)."""
         names = tuple(candidates)
         unknown = [n for n in names if n not in _SELECT_CANDIDATES]
@@ -635,8 +656,8 @@ class Render:
         guides = self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
         a, b = self.half_a_buffer, self.half_b_buffer
         half_var = np.float32(2.0) * self.variance_buffer
-        fa = [_select_candidate(n, a, half_var, guides, self.device) for n in names]
-        fb = [_select_candidate(n, b, half_var, guides, self.device) for n in names]
+        fa = [_select_candidate(n, a, half_var, guides, self.device, other=b) for n in names]
+        fb = [_select_candidate(n, b, half_var, guides, self.device, other=a) for n in names]
         rgb, mean, choice, error, self.select_info = filter_select(a, b, half_var, fa, fb, error_radius=error_radius, blend_radius=blend_radius,
                                                                    device=self.device, return_info=True)
         self.select_buffers = {"choice": choice, "error": error, "half_a": a, "half_b": b, "half_variance": half_var, "filtered_a": fa, "filtered_b": fb}
@@ -1173,6 +1194,76 @@ def denoise_nlm_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out
                                out_variance_ptr, scratch_ptr, scratch_bytes, device, stream, want_info)
 
 
+_REGRESS_SETTINGS = ("radius", "patch", "k", "alpha", "sigma_normal", "sigma_albedo", "sigma_depth", "sigma_position", "ridge", "features")
+_REGRESS_GUIDE_BITS = (("normal", capi.REGRESS_NORMAL), ("albedo", capi.REGRESS_ALBEDO), ("depth", capi.REGRESS_DEPTH))
+
+
+def denoise_regress_defaults():
+    """crt_denoise_regress_defaults as a dict: radius, patch, k, alpha, the four sigmas, ridge and the features mask."""
+    return _settings(_defaults(capi.RegressParams, "crt_denoise_regress_defaults"), _REGRESS_SETTINGS)
+
+
+def _regress_params(who, width, height, settings, given):
+    """settings: the caller's, None or absent = crt_denoise_regress_defaults'; given: the guides that are there -- a `features` of None
+    is the default mask without the bits of guides that are not given (an explicit mask goes to the library as it is)"""
+    unknown = sorted(set(settings) - set(_REGRESS_SETTINGS))
+    if unknown:
+        raise ValueError("%s: unknown settings %r" % (who, unknown))
+    for name in ("radius", "patch", "features"):
+        v = settings.get(name)
+        if v is not None and (int(v) != v or not 0 <= int(v) < 2 ** 32):
+            raise ValueError("%s: %s must be a non-negative integer, got %r" % (who, name, v))
+    p = _defaults(capi.RegressParams, "crt_denoise_regress_defaults", width, height, **settings)
+    if settings.get("features") is None:
+        for name, bit in _REGRESS_GUIDE_BITS:
+            if name not in given:
+                p.features &= ~bit
+    return p
+
+
+def denoise_regress_scratch_bytes(width, height):
+    n = C.c_uint64()
+    capi.check(capi.lib().crt_denoise_regress_scratch_bytes(width, height, C.byref(n)), "crt_denoise_regress_scratch_bytes")
+    return int(n.value)
+
+
+def denoise_regress(color, variance, albedo=None, normal=None, depth=None, weight_color=None, weight_variance=None, device=0, want_rgb=True,
+                    want_mean=True, return_info=False, **settings):
+    """First-order feature regression with non-local-means weights (crt_denoise_regress, contract: include/crt.h): `variance` is the
+    (H, W, 3) buffer of Render.variance(); weight_color / weight_variance: the image the weights come from (None: color / variance).
+    settings: radius, patch, k, alpha, sigma_normal, sigma_albedo, sigma_depth, sigma_position, ridge, features (REGRESS_* bits); None or
+    absent takes crt_denoise_regress_defaults, and a features of None is the default mask less the guides that are not given.  Returns
+    (rgb, mean) -- None for the one that is not wanted --, with return_info also the crt_regress_info dict (total_ms, fallback_pixels)."""
+    inputs = capi.RegressInputs()
+    keep = _image_inputs("denoise_regress", "an (H, W, 3) colour image",
+                         (("color", color, 3), ("variance", variance, 3), ("weight_color", weight_color, 3), ("weight_variance", weight_variance, 3),
+                          ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1)), inputs, needs=("variance", "the variance buffer (Render.variance)"))
+    h, w = keep[0].shape[:2]
+    given = {n for n, a in (("albedo", albedo), ("normal", normal), ("depth", depth)) if a is not None}
+    prm = _regress_params("denoise_regress", w, h, settings, given)
+    mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.RegressInfo()
+    capi.check(capi.lib().crt_denoise_regress(device, C.byref(prm), C.byref(inputs), capi.ptr(mean), capi.ptr(rgb), C.byref(info)), "crt_denoise_regress")
+    return (rgb, mean, info.as_dict()) if return_info else (rgb, mean)
+
+
+def denoise_regress_device(width, height, color_ptr, variance_ptr, out_mean_ptr, out_rgb_ptr, scratch_ptr, scratch_bytes, albedo_ptr=None,
+                           normal_ptr=None, depth_ptr=None, weight_color_ptr=None, weight_variance_ptr=None, device=0, stream=None, want_info=True,
+                           **settings):
+    """Enqueues the regression filter with everything in device memory (raw device pointers, crt_denoise_regress_device); the caller owns
+    the scratch (denoise_regress_scratch_bytes).  settings as denoise_regress.  With want_info the call synchronizes the stream and
+    returns the crt_regress_info dict, else None."""
+    inputs = capi.RegressInputs(color_ptr or None, variance_ptr or None, weight_color_ptr or None, weight_variance_ptr or None, albedo_ptr or None,
+                                normal_ptr or None, depth_ptr or None)
+    given = {n for n, a in (("albedo", albedo_ptr), ("normal", normal_ptr), ("depth", depth_ptr)) if a}
+    prm = _regress_params("denoise_regress_device", width, height, settings, given)
+    info = capi.RegressInfo()
+    capi.check(capi.lib().crt_denoise_regress_device(device, C.byref(prm), C.byref(inputs), _vp(out_mean_ptr), _vp(out_rgb_ptr), _vp(scratch_ptr),
+                                                     int(scratch_bytes), _vp(stream), C.byref(info) if want_info else None), "crt_denoise_regress_device")
+    return info.as_dict() if want_info else None
+
+
 def modulate_defaults():
     """crt_modulate_defaults as a dict: albedo_floor."""
     return _settings(_defaults(capi.ModulateParams, "crt_modulate_defaults"))
@@ -1325,17 +1416,20 @@ def upsample_device(width, height, low_width, low_height, low_ptrs, out_color_pt
 
 
 _SELECT_SETTINGS = ("error_radius", "blend_radius")
-_SELECT_CANDIDATES = ("none", "atrous", "var", "nlm")
+_SELECT_CANDIDATES = ("none", "atrous", "var", "nlm", "reg")
 
 
-def _select_candidate(name, half, half_variance, guides, device):
-    """Candidate filter `name` of run_view_selected applied to one half frame, with its own defaults"""
+def _select_candidate(name, half, half_variance, guides, device, other=None):
+    """Candidate filter `name` of run_view_selected applied to one half frame, with its own defaults; other: the other half frame, where
+    "reg" takes its weights"""
     if name == "none":
         return half
     if name == "atrous":
         return denoise(half, device=device, want_rgb=False, **guides)[1]
     if name == "var":
         return denoise_var(half, half_variance, device=device, want_rgb=False, **guides)[1]
+    if name == "reg":
+        return denoise_regress(half, half_variance, weight_color=other, weight_variance=half_variance, device=device, want_rgb=False, **guides)[1]
     return denoise_nlm(half, half_variance, device=device, want_rgb=False, **guides)[1]
 
 

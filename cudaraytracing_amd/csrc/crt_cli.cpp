@@ -8,7 +8,7 @@
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]
 //           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
-//           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]
+//           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K] [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
@@ -42,8 +42,11 @@
 // its own defaults; --denoise-iterations / --denoise-sigma override them as well).  --denoise-nlm makes --denoise use the non-local-means
 // filter (crt_denoise_nlm, its own defaults); --denoise-nlm-params sets its radius, patch and k, --denoise-sigma its three guide sigmas (the
 // colour value is ignored: the filter has no colour sigma).  Not with --denoise-variance or --denoise-iterations.
+// --denoise-regress makes --denoise use the first-order feature-regression filter (crt_denoise_regress, its own defaults, every feature;
+// with --demodulate without the albedo feature); --denoise-regress-params sets its radius, patch, k and ridge, --denoise-sigma the scales
+// of its normal, albedo and depth features.  Not with --denoise-nlm, --denoise-variance or --denoise-iterations.
 // --denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]] makes --denoise pick, per pixel, the one of the filters in LIST -- none, atrous, var,
-// nlm, joined by + (1 .. 4 of them), each with its own defaults -- whose error estimated against the other half frame is smallest
+// nlm, reg, joined by + (1 .. 4 of them), each with its own defaults, reg with its weights from the other half frame -- whose error estimated against the other half frame is smallest
 // (CRT_FLAG_HALF_BUFFERS, crt_half_buffers, crt_filter_select; the radii default to crt_filter_select_defaults').  --denoise-choice PATH
 // writes the choice map as a PNG (candidate k of K as the grey 255 k / max(K - 1, 1)).  Not with the other --denoise-* options or --demodulate.
 // --denoise PATH renders as usual, then filters the frame with the AOV-guided a-trous denoiser (crt_denoise, one device) and writes the
@@ -78,7 +81,8 @@ int main(int argc, char** argv)
                              "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
-                             "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm joined by +)\n"
+                             "       [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]\n"
+                             "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm, reg joined by +)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n"
@@ -99,6 +103,9 @@ int main(int argc, char** argv)
         bool denoise_nlm = false, nlm_params = false;
         crt_nlm_params nlm; // --denoise-nlm: the filter's defaults with the overrides
         crt_denoise_nlm_defaults(&nlm);
+        bool denoise_regress = false, regress_params = false;
+        crt_regress_params reg; // --denoise-regress: the filter's defaults with the overrides
+        crt_denoise_regress_defaults(&reg);
         std::vector<int> select_candidates; // --denoise-select: crt::Render::SELECT_* of LIST
         crt_filter_select_params sel;       // ... and the selection's defaults with the radii given
         crt_filter_select_defaults(&sel);
@@ -211,6 +218,21 @@ int main(int argc, char** argv)
                 if (!good || radius < 0 || patch < 0) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm-params needs three comma-separated values: RADIUS,PATCH,K");
                 nlm.radius = (uint32_t)radius; nlm.patch = (uint32_t)patch;
             }
+            else if (a == "--denoise-regress") denoise_regress = true;
+            else if (a == "--denoise-regress-params") {
+                need(i, 1);
+                regress_params = true;
+                const char* q = argv[++i];
+                char* end = nullptr;
+                const long radius = std::strtol(q, &end, 10);
+                bool good = end != q && *end == ',';
+                long patch = 0;
+                if (good) { q = end + 1; patch = std::strtol(q, &end, 10); good = end != q && *end == ','; }
+                if (good) { q = end + 1; reg.k = std::strtof(q, &end); good = end != q && *end == ','; }
+                if (good) { q = end + 1; reg.ridge = std::strtof(q, &end); good = end != q && *end == 0; }
+                if (!good || radius < 0 || patch < 0) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress-params needs four comma-separated values: RADIUS,PATCH,K,RIDGE");
+                reg.radius = (uint32_t)radius; reg.patch = (uint32_t)patch;
+            }
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
             else if (a == "--adaptive") { need(i, 1); ad.threshold = std::strtof(argv[++i], nullptr); adaptive = true; }
             else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
@@ -278,7 +300,7 @@ int main(int argc, char** argv)
                     const size_t plus = std::min(list.find('+', at), list.size());
                     const std::string name = list.substr(at, plus - at);
                     const int id = name == "none" ? crt::Render::SELECT_NONE : name == "atrous" ? crt::Render::SELECT_ATROUS : name == "var" ? crt::Render::SELECT_VAR
-                                 : name == "nlm" ? crt::Render::SELECT_NLM : -1;
+                                 : name == "nlm" ? crt::Render::SELECT_NLM : name == "reg" ? crt::Render::SELECT_REG : -1;
                     good = id >= 0 && select_candidates.size() < CRT_SELECT_MAX_CANDIDATES;
                     select_candidates.push_back(id);
                     at = plus + 1;
@@ -293,7 +315,7 @@ int main(int argc, char** argv)
                     if (*end == 0) break;
                     q = end + 1;
                 }
-                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs LIST[,ERROR_RADIUS[,BLEND_RADIUS]]: LIST 1 .. 4 of none, atrous, var, nlm joined by +, ERROR_RADIUS 0 .. 8, BLEND_RADIUS 0 .. 4");
+                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs LIST[,ERROR_RADIUS[,BLEND_RADIUS]]: LIST 1 .. 4 of none, atrous, var, nlm, reg joined by +, ERROR_RADIUS 0 .. 8, BLEND_RADIUS 0 .. 4");
             }
             else if (a == "--denoise-iterations") { need(i, 1); dn.iterations = (uint32_t)std::atoi(argv[++i]); dn_iterations = true; }
             else if (a == "--denoise-sigma") {
@@ -331,7 +353,7 @@ int main(int argc, char** argv)
             {!aov_shading.empty(), "--aov-shading renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
             {!variance.empty(), "--variance reads one device's buffer"}, {denoise_var, "--denoise-variance filters on one device"},
             {adaptive, "--adaptive renders on one device"}, {temporal != 0, "--temporal accumulates on one device"}, {upsample != 0, "--upsample runs on one device"},
-            {denoise_nlm, "--denoise-nlm filters on one device"}};
+            {denoise_nlm, "--denoise-nlm filters on one device"}, {denoise_regress, "--denoise-regress filters on one device"}};
         size_t row = 0;
         auto refuse_on_many = [&](size_t count) {
             for (; count-- > 0; row++)
@@ -356,13 +378,19 @@ int main(int argc, char** argv)
         if (denoise_nlm && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is a filter of its own (not with --denoise-variance)");
         if (denoise_nlm && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is one pass (not with --denoise-iterations)");
         if (denoise_nlm && dn_sigma) { nlm.sigma_normal = dn.sigma_normal; nlm.sigma_albedo = dn.sigma_albedo; nlm.sigma_depth = dn.sigma_depth; }
+        refuse_on_many(1);
+        if (denoise_regress && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress needs --denoise PATH");
+        if (regress_params && !denoise_regress) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress-params needs --denoise-regress");
+        if (denoise_regress && (denoise_var || denoise_nlm)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress is a filter of its own (not with --denoise-variance or --denoise-nlm)");
+        if (denoise_regress && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress is one pass (not with --denoise-iterations)");
+        if (denoise_regress && dn_sigma) { reg.sigma_normal = dn.sigma_normal; reg.sigma_albedo = dn.sigma_albedo; reg.sigma_depth = dn.sigma_depth; }
         const bool denoise_select = !select_candidates.empty();
         if (denoise_select && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs --denoise PATH");
         if (!denoise_choice.empty() && !denoise_select) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-choice needs --denoise-select LIST");
-        if (denoise_select && (denoise_var || denoise_nlm || dn_iterations || dn_sigma || denoise_specular || demodulate))
+        if (denoise_select && (denoise_var || denoise_nlm || denoise_regress || dn_iterations || dn_sigma || denoise_specular || demodulate))
             throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select runs every filter with its own defaults on radiance (not with the other --denoise-* options or --demodulate)");
         if (denoise_select && (adaptive || temporal)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs the half buffers of a uniformly sampled frame (not with --adaptive or --temporal)");
-        const bool want_var = !variance.empty() || denoise_var || denoise_nlm || (temporal > 0 && !temporal_moments);
+        const bool want_var = !variance.empty() || denoise_var || denoise_nlm || denoise_regress || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
         crt_denoise_var_defaults(&tdn);
         if (dn_iterations) tdn.iterations = dn.iterations;
@@ -492,7 +520,7 @@ int main(int argc, char** argv)
                 write_files("choice map", {{denoise_choice, 0, grey.data()}});
             }
         } else if (!denoise.empty()) {
-            if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
+            if (denoise_regress) render.run_denoise_regress(reg); else if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
             const crt_denoise_info& di = render.last_denoise_info();
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);
             render.save_denoised_buffer(denoise.c_str());

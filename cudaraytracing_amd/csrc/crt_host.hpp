@@ -258,11 +258,16 @@ public:
     void run_denoise_var(const crt_denoise_params& prm);
     // the same with the non-local-means filter (crt_denoise_nlm; prm: crt_denoise_nlm_defaults with overrides), CRT_FLAG_VARIANCE likewise
     void run_denoise_nlm(const crt_nlm_params& prm);
+    // the same with the feature-regression filter (crt_denoise_regress; prm: crt_denoise_regress_defaults with overrides), CRT_FLAG_VARIANCE
+    // likewise; with set_demodulate the albedo feature is taken off the mask.  last_regress_info(): its timer and fallback pixels
+    void run_denoise_regress(const crt_regress_params& prm);
+    const crt_regress_info& last_regress_info() const { return regress_info_; }
     // Error-estimated filter selection (crt_half_buffers, crt_filter_select): the last run_view must have had CRT_FLAG_HALF_BUFFERS
-    // (set_flags).  candidates: 1 .. 4 of SELECT_NONE / _ATROUS / _VAR / _NLM, each run with its own defaults on either half frame, the
-    // variance-taking ones with 2 x variance(); prm: crt_filter_select_defaults with overrides, its sizes and n_candidates are set here.
+    // (set_flags).  candidates: 1 .. 4 of SELECT_NONE / _ATROUS / _VAR / _NLM / _REG, each run with its own defaults on either half frame,
+    // the variance-taking ones with 2 x variance(), _REG with its weights from the other half frame; prm: crt_filter_select_defaults with
+    // overrides, its sizes and n_candidates are set here.
     // The result is the denoised buffer; the choice map is get_choice_buffer().  Not with set_demodulate.
-    enum { SELECT_NONE = 0, SELECT_ATROUS = 1, SELECT_VAR = 2, SELECT_NLM = 3 };
+    enum { SELECT_NONE = 0, SELECT_ATROUS = 1, SELECT_VAR = 2, SELECT_NLM = 3, SELECT_REG = 4 };
     void run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm);
     const crt_filter_select_info& last_select_info() const { return select_info_; }
     const std::vector<unsigned char>& get_choice_buffer() const { return choice_buffer_; }
@@ -372,6 +377,7 @@ private:
     template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);
     int device_ = 0;
     crt_denoise_info denoise_info_{};
+    crt_regress_info regress_info_{};
     crt_filter_select_info select_info_{};
     std::vector<unsigned char> choice_buffer_;
     crt_stats stats_{};

@@ -300,6 +300,31 @@ void Render::run_denoise_nlm(const crt_nlm_params& prm)
     denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
 }
 
+void Render::run_denoise_regress(const crt_regress_params& prm)
+{
+    const char* who = "Render::run_denoise_regress";
+    one_device(who, "the denoiser");
+    need_guides(who);
+    const size_t n = scene_->get_pixels();
+    crt_regress_params p = prm;
+    p.width = scene_->get_width(); p.height = scene_->get_height();
+    const float* color = mean_buffer_.data();
+    const float* var = variance();
+    std::vector<float> irradiance, irradiance_variance;
+    if (demodulate_) {
+        demodulate_of(who, color, var, irradiance, irradiance_variance);
+        color = irradiance.data(); var = irradiance_variance.data();
+        p.features &= ~CRT_REGRESS_ALBEDO; // (irradiance does not follow the albedo)
+    }
+    crt_regress_inputs in{};
+    in.color = color; in.variance = var;
+    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
+    check(crt_denoise_regress(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &regress_info_), who);
+    denoise_info_.total_ms = regress_info_.total_ms; denoise_info_.passes = 1;
+    if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
+}
+
 void Render::run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm)
 {
     const char* who = "Render::run_denoise_select";
@@ -314,10 +339,20 @@ void Render::run_denoise_select(const std::vector<int>& candidates, const crt_fi
     for (size_t i = 0; i < 3 * n; i++) half_variance[i] = 2.0f * var[i];
     const uint32_t w = scene_->get_width(), h = scene_->get_height();
     // one candidate on one half frame, with its own defaults and the guides of the last run_aov
-    auto filter = [&](int candidate, const float* image, float* out) {
+    // (other: the other half frame, where the regression filter takes its weights)
+    auto filter = [&](int candidate, const float* image, const float* other, float* out) {
         crt_denoise_var_inputs vin{};
         vin.color = image; vin.variance = half_variance.data();
         vin.albedo = albedo_buffer_.data(); vin.normal = normal_buffer_.data(); vin.depth = depth_buffer_.data();
+        if (candidate == SELECT_REG) {
+            crt_regress_params p;
+            crt_denoise_regress_defaults(&p);
+            p.width = w; p.height = h;
+            crt_regress_inputs rin{};
+            rin.color = image; rin.variance = vin.variance; rin.weight_color = other; rin.weight_variance = vin.variance;
+            rin.albedo = vin.albedo; rin.normal = vin.normal; rin.depth = vin.depth;
+            return crt_denoise_regress(device_, &p, &rin, out, nullptr, nullptr);
+        }
         if (candidate == SELECT_NLM) {
             crt_nlm_params p;
             crt_denoise_nlm_defaults(&p);
@@ -342,7 +377,7 @@ void Render::run_denoise_select(const std::vector<int>& candidates, const crt_fi
             const float* image = half[side].data();
             if (candidates[k] != SELECT_NONE) {
                 filtered[side][k].assign(3 * n, 0.0f);
-                check(filter(candidates[k], image, filtered[side][k].data()), who);
+                check(filter(candidates[k], image, half[1 - side].data(), filtered[side][k].data()), who);
                 image = filtered[side][k].data();
             }
             (side == 0 ? in.filtered_a : in.filtered_b)[k] = image;

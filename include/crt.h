@@ -633,6 +633,84 @@ int crt_denoise_nlm(int device, const crt_nlm_params* params, const crt_denoise_
 int crt_denoise_nlm_device(int device, const crt_nlm_params* params, const crt_denoise_var_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
                            void* d_out_variance, void* d_scratch, uint64_t scratch_bytes, void* hip_stream, crt_denoise_info* info);
 
+/* First-order feature regression with non-local-means weights (Moon et al. 2014; Bitterli et al. 2016, "NFOR"): in the window around a
+ * pixel the colour is fitted as a linear function of the guides -- weighted least squares, the weight of a tap crt_denoise_nlm's patch
+ * term -- and the output is the fit's value at the pixel.  Where the three filters above take a weighted mean, which cannot follow a
+ * gradient, this one follows whatever is linear in the enabled features.  The weights may come from another image than the one that is
+ * fitted (weight_color / weight_variance: with the half frames of crt_half_buffers, half B for half A and the reverse, weight and noise
+ * are independent).  An image operation: row-major, no scene handle; buffers as crt_denoise_var's (3 floats per pixel, depth 1).
+ * Inputs: color and variance required; weight_color NULL = color, weight_variance NULL = variance (with both given `variance` itself is
+ * not read); albedo / normal / depth are read only where `features` enables them.  Outputs: out_mean and / or out_rgb (the frame's tone
+ * map of the mean), not both NULL.  There is no out_variance (see below).
+ *   wc, wv = weight_color, weight_variance;  k2 = k * k;  F = the regressors enabled in `features`, M = F + 1
+ * For pixel p and window offset o = (ox, oy), oy = -radius..radius outer, ox = -radius..radius inner, q = p + o; a q outside the image
+ * is skipped:
+ *   e_p = crt_denoise_nlm's e_p of (p, o), to the bit: its v, g (the 3x3 Gaussian of the summed wv), pair term d, row sums in its order,
+ *         its skipping rule, n, Dm = D / (float)n and the clamp Dm < 0 ? 0 : Dm -- evaluated on wc and wv with this call's patch, k, alpha
+ *   w   = exp(-e_p)                                  (det_expf; crt_denoise_nlm's guide terms e_n, e_a, e_d are NOT in the weight)
+ *   x(q): M entries, the enabled ones of the following in this order, then the constant 1 LAST:
+ *     CRT_REGRESS_NORMAL    (normal(q).c - normal(p).c) / sigma_normal                    c = x, y, z
+ *     CRT_REGRESS_ALBEDO    (albedo(q).c - albedo(p).c) / sigma_albedo                    c = x, y, z
+ *     CRT_REGRESS_DEPTH     m = depth(p) > depth(q) ? depth(p) : depth(q);   m > 0 ? (depth(q) - depth(p)) / (sigma_depth * m) : 0
+ *     CRT_REGRESS_POSITION  (float)ox / (sigma_position * (float)radius),   (float)oy / (sigma_position * (float)radius)
+ *   for i = 0..F:   wx = w * x_i;   A[i][j] = A[i][j] + wx * x_j  for j = i..F;   B[i][c] = B[i][c] + wx * color(q).c  for c = r, g, b
+ * Every entry of x is centred on p, so the fit's value at p is the coefficient of the constant.  After the window:
+ *   S = A[F][F] (the sum of the weights),  Z_c = B[F][c]
+ *   A[i][i] = A[i][i] + ridge * S                    for i < F
+ *   for k = 0..F-1:  d = A[k][k];  !(d > 0): fall back
+ *     for i = k+1..F:  f = A[k][i] / d;   A[i][j] = A[i][j] - f * A[k][j]  for j = i..F;   B[i][c] = B[i][c] - f * B[k][c]
+ *   d = A[F][F];  !(d > 0): fall back;   out_mean(p).c = B[F][c] / d
+ *   fall back:  out_mean(p).c = Z_c / S              (the zero-order result: the weighted mean of the window)
+ * Gaussian elimination of the symmetric system on its upper triangle, without pivoting and without back-substitution: only the last
+ * unknown is wanted.  All sums start at +0.0f and run in window order; fp32 with one IEEE operation per symbol (no FMA, no reciprocal
+ * multiply).  A NaN pivot falls back by the !(d > 0) test; non-finite inputs are otherwise not special-cased.  info->fallback_pixels
+ * counts the pixels that fell back.  With features = 0 the filter is the zero-order one (M = 1: B[0] / A[0][0] = Z / S) and no pixel
+ * falls back unless S is not > 0.
+ * A disabled feature has no row and no column: the library instantiates its kernel per mask (csrc/crt_regress.hip), so a smaller mask
+ * runs the smaller system and a disabled feature's buffer may be NULL or not, with the same bits.  An enabled feature with a NULL buffer
+ * is CRT_ERR_INVALID_ARG.  The sigmas here scale the features (and with them what `ridge` means): each > 0 and not NaN; sigma_position is
+ * in units of radius.  ridge >= 0 and finite; radius 1 .. 8, patch 0 .. 3, k > 0 and finite, alpha >= 0 and finite as crt_denoise_nlm;
+ * a null params, inputs, color or variance, a size of 0, unknown mask bits, two NULL outputs, a negative device or a scratch buffer that
+ * is missing, too small or not 16-byte aligned is CRT_ERR_INVALID_ARG, checked before any device call.  (A side longer than 2^24
+ * pixels: CRT_ERR_UNSUPPORTED.)  Scratch: 64 B per pixel (crt_denoise_regress_scratch_bytes: four float4 planes -- (weight colour, g),
+ * (normal, depth), (albedo, -), (colour, 0)).  The kernel has one form, the shared one (k_nlm_shared's staging and phases).
+ * Not done: the variance left after the fit (it needs the fit's equivalent kernel, a second pass), second-order fits, iterating the
+ * filter or pre-filtering the features, specular guides as regressors, temporal inputs, per-channel variances.
+ * crt_denoise_regress_defaults fills radius 5, patch 1, k 0.6, alpha 1, sigma_normal 0.5, sigma_albedo 0.1, sigma_depth 0.05,
+ * sigma_position 2, ridge 0.4 and every feature: the set with the smallest summed error relative to crt_denoise_var's defaults on the
+ * 160x120 spp 8 and spp 32 frames of cornell-box, veach-mis and the textured cornell-box (docs/experiments.md, "The feature-regression
+ * filter"). */
+#define CRT_REGRESS_NORMAL 1u
+#define CRT_REGRESS_ALBEDO 2u
+#define CRT_REGRESS_DEPTH 4u
+#define CRT_REGRESS_POSITION 8u
+typedef struct {
+    uint32_t width, height;
+    uint32_t radius;      /* window (2 radius + 1)^2: 1 .. 8 */
+    uint32_t patch;       /* patches of (2 patch + 1)^2: 0 .. 3 */
+    float k, alpha;       /* as crt_nlm_params */
+    float sigma_normal, sigma_albedo, sigma_depth;   /* the scales of the features: > 0, not NaN */
+    float sigma_position; /* in units of radius: > 0, not NaN */
+    float ridge;          /* >= 0, finite: added to the features' diagonal, times the sum of the weights */
+    uint32_t features;    /* CRT_REGRESS_* bits; 0: the zero-order filter */
+} crt_regress_params;
+typedef struct {
+    const float* color; const float* variance;
+    const float* weight_color;      /* NULL: color */
+    const float* weight_variance;   /* NULL: variance */
+    const float* albedo; const float* normal; const float* depth;
+} crt_regress_inputs;
+typedef struct {
+    float total_ms;
+    uint64_t fallback_pixels;  /* pixels that took Z / S */
+} crt_regress_info;
+int crt_denoise_regress_defaults(crt_regress_params* params);
+int crt_denoise_regress_scratch_bytes(uint32_t width, uint32_t height, uint64_t* bytes);
+int crt_denoise_regress(int device, const crt_regress_params* params, const crt_regress_inputs* host_in, float* out_mean, uint8_t* out_rgb,
+                        crt_regress_info* info);
+int crt_denoise_regress_device(int device, const crt_regress_params* params, const crt_regress_inputs* dev_in, void* d_out_mean, void* d_out_rgb,
+                               void* d_scratch, uint64_t scratch_bytes, void* hip_stream, crt_regress_info* info);
+
 /* Albedo demodulation: filter irradiance, not radiance.  crt_demodulate takes the emission off a frame and divides it by the albedo,
  * crt_modulate puts both back, so that crt_denoise* and crt_temporal* in between see neither the surfaces' colour nor the lights
  * (SVGF, Schied et al. 2017, section 4).  With emission and diffuse_albedo of crt_render_aov_shading the factorisation is exact for this

@@ -34,6 +34,17 @@ of crt_denoise, crt_denoise_var and crt_denoise_nlm (their defaults, first-hit g
 
   python tools/denoise_probe.py --nlm [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--nlm-params 5,1,0.7]
   python tools/denoise_probe.py --nlm --error --ref-seed 7
+
+--regress times crt_denoise_regress_device (its defaults or --regress-params RADIUS,PATCH,K,RIDGE; the full mask, the position feature
+alone and no feature) at --sizes beside one a-trous pass (crt_denoise_device, 1 iteration) and crt_denoise_nlm_device in one process, the
+calls taking turns, HIP events, the median of --calls calls.  With --error it lists, per scene (cornell-box-textured as above) at spp 8
+and spp 32, the error of the unfiltered frame, of crt_denoise_var, crt_denoise_nlm and crt_denoise_regress on radiance and on irradiance,
+and of the selection among {var, nlm}, {var, nlm, reg} and {var, reg} (Render.run_view_selected, radiance).  --sweep lists the error of
+crt_denoise_regress for every combination of the --sweep-* values instead, by its sum relative to crt_denoise_var's defaults.
+
+  python tools/denoise_probe.py --regress [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--regress-params 5,1,0.6,0.4]
+  python tools/denoise_probe.py --regress --error --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
+  python tools/denoise_probe.py --regress --error --sweep --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
 """
 import argparse
 import json
@@ -232,6 +243,131 @@ def nlm_times(a):
     print(json.dumps(out), flush=True)
 
 
+def regress_settings(a):
+    if not a.regress_params:
+        return {}
+    radius, patch, k, ridge = a.regress_params.split(",")
+    return {"radius": int(radius), "patch": int(patch), "k": float(k), "ridge": float(ridge)}
+
+
+def regress_times(a):
+    """--regress: one a-trous pass (crt_denoise_device, 1 iteration), crt_denoise_nlm_device (its default form) and
+    crt_denoise_regress_device at the full mask, with the position feature alone and with no feature, the five calls taking turns"""
+    t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
+    iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+    fov = crt.fov_to_radians(t.fov_y)
+    out = {"scene": a.scene, "spp": a.spp, "calls": a.calls, "warmup": a.warmup, "regress": dict(crt.denoise_regress_defaults(), **regress_settings(a)), "runs": []}
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+        r.run_view(t.eye_pos, iv, fov, want_variance=True)
+        host = dict(r.run_view_aov(t.eye_pos, iv, fov, want=("albedo", "normal", "depth")), color=r.mean_buffer, variance=r.variance_buffer)
+        r.free()
+        scratch_bytes = max(crt.denoise_scratch_bytes(w, h), crt.denoise_nlm_scratch_bytes(w, h), crt.denoise_regress_scratch_bytes(w, h))
+        dev = hipmem.DeviceBuffers({**host, "out_mean": w * h * 12, "out_rgb": w * h * 3, "out_var": w * h * 4, "scratch": scratch_bytes})
+        ptrs = dev.ptrs
+        common = dict(albedo_ptr=ptrs["albedo"], normal_ptr=ptrs["normal"], depth_ptr=ptrs["depth"])
+        args = (w, h, ptrs["color"], ptrs["variance"], ptrs["out_mean"], ptrs["out_rgb"])
+
+        def call_regress(features):
+            return crt.denoise_regress_device(*args, ptrs["scratch"], scratch_bytes, features=features, **common, **regress_settings(a))["total_ms"]
+
+        calls = {"atrous_1_pass": lambda: crt.denoise_device(w, h, ptrs["color"], ptrs["out_mean"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes, iterations=1,
+                                                             **common)["total_ms"],
+                 "nlm": lambda: crt.denoise_nlm_device(*args, ptrs["out_var"], ptrs["scratch"], scratch_bytes, **common)["total_ms"],
+                 "regress_all": lambda: call_regress(15), "regress_position": lambda: call_regress(crt.REGRESS_POSITION), "regress_none": lambda: call_regress(0)}
+        ms = {k: [] for k in calls}
+        for _ in range(a.warmup + a.calls):
+            for k, f in calls.items():
+                ms[k].append(f())
+        run = {"width": w, "height": h}
+        for k, v in ms.items():
+            run[k + "_ms_median"] = round(statistics.median(v[a.warmup:]), 4)
+            run[k + "_ms_best"] = round(min(v[a.warmup:]), 4)
+        run["regress_over_nlm"] = round(run["regress_all_ms_median"] / run["nlm_ms_median"], 3)
+        run["regress_over_atrous_pass"] = round(run["regress_all_ms_median"] / run["atrous_1_pass_ms_median"], 3)
+        out["runs"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        dev.free()
+    print(json.dumps(out), flush=True)
+
+
+def regress_error_table(a):
+    """--regress --error: per scene (cornell-box-textured as in --demodulate), spp 8 and 32, on radiance and on irradiance: the error of
+    the unfiltered frame, of crt_denoise_var, crt_denoise_nlm and crt_denoise_regress (their defaults, or --regress-params), and on radiance
+    of the selection among {var, nlm} and among {var, nlm, reg} (Render.run_view_selected), against --ref-spp samples of --ref-seed.
+    --sweep instead lists, for every combination of --sweep-* values, the error of crt_denoise_regress on the six radiance frames and
+    their sum relative to crt_denoise_var's defaults, the smallest sum first."""
+    import itertools
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "ref_spp": a.ref_spp, "ref_seed": a.ref_seed, "regress": dict(crt.denoise_regress_defaults(), **regress_settings(a)), "rows": []}
+    frames = []
+    for name in a.scenes.split(","):
+        textured = name == "cornell-box-textured"
+        t = crt.Task(os.path.join(ROOT, "scenes", "cornell-box" if textured else name, "config.json"), base_dir=ROOT)
+        view = (t.eye_pos, crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up), crt.fov_to_radians(t.fov_y))
+        if textured:
+            import tempfile
+            sys.path.insert(0, os.path.join(ROOT, "scenes"))
+            import gen_cornell_box
+            with tempfile.TemporaryDirectory(prefix="crt_textured_") as d:
+                obj, mtl_dir, _ = gen_cornell_box.write_textured_variant(d, a.cells)
+                scene = crt.Scene(w, h)
+                scene.add_obj(obj, mtl_dir)
+                scene.set_BVH(t.bvh_thresh_n)
+        else:
+            scene = crt.Scene.from_task(t, w, h)
+        r = crt.Render(scene, a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = a.ref_seed
+        ref = r.run_view(*view).astype(np.float64)
+        r.seed = 0
+
+        def mse(x, ref=ref):
+            return round(float(np.mean((x.astype(np.float64) - ref) ** 2)), 1)
+
+        for spp in (8, 32):
+            r.set_spp(spp)
+            noisy_rgb = r.run_view(*view, want_variance=True).copy()
+            mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+            g = r.run_view_aov_shading(*view, first=("albedo", "normal", "depth"))
+            E, A = g["emission"], g["diffuse_albedo"]
+            guides = {k: g[k] for k in ("albedo", "normal", "depth")}
+            irr, ivar = crt.demodulate(mean, A, E, var)
+            frames.append({"scene": name, "spp": spp, "mse": mse, "mean": mean, "var": var, "guides": guides, "irr": irr, "ivar": ivar, "A": A, "E": E,
+                           "var_default": mse(crt.denoise_var(mean, var, **guides)[0])})
+            if a.sweep:
+                continue
+            no_albedo = crt.denoise_regress_defaults()["features"] & ~crt.REGRESS_ALBEDO
+            row = {"scene": name, "spp": spp, "unfiltered": mse(noisy_rgb), "var": frames[-1]["var_default"], "nlm": mse(crt.denoise_nlm(mean, var, **guides)[0]),
+                   "reg": mse(crt.denoise_regress(mean, var, **regress_settings(a), **guides)[0]),
+                   "selected_var_nlm": mse(r.run_view_selected(*view, candidates=("var", "nlm"))[0]),
+                   "selected_var_nlm_reg": mse(r.run_view_selected(*view, candidates=("var", "nlm", "reg"))[0]),
+                   "selected_var_reg": mse(r.run_view_selected(*view, candidates=("var", "reg"))[0]),
+                   "demodulated_var": mse(crt.modulate(crt.denoise_var(irr, ivar, want_rgb=False, **guides)[1], A, E)[0]),
+                   "demodulated_nlm": mse(crt.modulate(crt.denoise_nlm(irr, ivar, want_rgb=False, **guides)[1], A, E)[0]),
+                   "demodulated_reg": mse(crt.modulate(crt.denoise_regress(irr, ivar, want_rgb=False, features=no_albedo, **regress_settings(a), **guides)[1], A, E)[0])}
+            info = crt.denoise_regress(mean, var, return_info=True, **regress_settings(a), **guides)[2]
+            row["reg_fallback_pixels"] = info["fallback_pixels"]
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        r.free()
+    if a.sweep:
+        grid = {"radius": [int(v) for v in a.sweep_radius.split(",")], "patch": [int(v) for v in a.sweep_patch.split(",")],
+                "k": [float(v) for v in a.sweep_k.split(",")], "ridge": [float(v) for v in a.sweep_ridge.split(",")],
+                "sigma_position": [float(v) for v in a.sweep_sigma_position.split(",")], "features": [int(v) for v in a.sweep_features.split(",")]}
+        for combo in itertools.product(*grid.values()):
+            s = dict(zip(grid.keys(), combo))
+            errs = [f["mse"](crt.denoise_regress(f["mean"], f["var"], **s, **f["guides"])[0]) for f in frames]
+            rel = sum(e / f["var_default"] for e, f in zip(errs, frames))
+            out["rows"].append(dict(s, errors=errs, relative_sum=round(rel, 4)))
+        out["rows"].sort(key=lambda row: row["relative_sum"])
+        out["frames"] = [{"scene": f["scene"], "spp": f["spp"], "var": f["var_default"]} for f in frames]
+        for row in out["rows"][:20]:
+            print(json.dumps(row), file=sys.stderr, flush=True)
+    print(json.dumps(out), flush=True)
+
+
 def error_table(a):
     import numpy as np
     w, h = (int(v) for v in a.error_size.split("x"))
@@ -291,9 +427,20 @@ def main():
     ap.add_argument("--ref-seed", type=int, default=999, help="--error --demodulate: the seed of the converged frame")
     ap.add_argument("--nlm", action="store_true", help="time crt_denoise_nlm_device (both forms) beside crt_denoise_var_device; with --error: the error rows at spp 8 and 32")
     ap.add_argument("--nlm-params", default="", help="--nlm: RADIUS,PATCH,K instead of the filter's defaults")
+    ap.add_argument("--regress", action="store_true", help="time crt_denoise_regress_device beside crt_denoise_nlm_device and one a-trous pass; with --error: the error rows")
+    ap.add_argument("--regress-params", default="", help="--regress: RADIUS,PATCH,K,RIDGE instead of the filter's defaults")
+    ap.add_argument("--sweep", action="store_true", help="--regress --error: the error for every combination of the --sweep-* values")
+    ap.add_argument("--sweep-radius", default="3,5,7")
+    ap.add_argument("--sweep-patch", default="1,2")
+    ap.add_argument("--sweep-k", default="0.5,0.7,1.0")
+    ap.add_argument("--sweep-ridge", default="0.001,0.01,0.1")
+    ap.add_argument("--sweep-sigma-position", default="0.5,1,2")
+    ap.add_argument("--sweep-features", default="15,13,12,8,7", help="masks of the REGRESS_* bits (normal 1, albedo 2, depth 4, position 8)")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
+    if a.regress:
+        return regress_error_table(a) if a.error else regress_times(a)
     if a.error:
         return nlm_error_table(a) if a.nlm else demodulated_error_table(a) if a.demodulate else error_table(a)
     if a.nlm:
