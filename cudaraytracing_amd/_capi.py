@@ -245,6 +245,19 @@ class UpsampleInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("fallback_pixels", C.c_uint64)]
 
 
+class PyramidParams(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("low_width", C.c_uint32), ("low_height", C.c_uint32)]
+
+
+class PyramidPlanes(C.Structure):
+    """crt_pyramid_planes and crt_pyramid_out_planes: the same five pointers"""
+    _fields_ = [("color", C.c_void_p), ("variance", C.c_void_p), ("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class PyramidInfo(InfoStruct):
+    _fields_ = [("total_ms", C.c_float)]
+
+
 SELECT_MAX_CANDIDATES = 4
 
 
@@ -331,7 +344,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_render_aov_shading", "crt_render_aov_shading_device", "crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate",
            "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device", "crt_half_buffers", "crt_half_buffers_device",
            "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device",
-           "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device"]
+           "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device",
+           "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device"]
 
 _lib = None
 
@@ -439,6 +453,13 @@ def lib():
                                         C.POINTER(VarianceEstimateInfo)]
     L.crt_variance_estimate_device.argtypes = [C.c_int, C.POINTER(VarianceEstimateParams), C.POINTER(VarianceEstimateInputs), C.c_void_p, C.c_void_p,
                                                C.POINTER(VarianceEstimateInfo)]
+    L.crt_pyramid_size.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.crt_pyramid_down.argtypes = [C.c_int, C.POINTER(PyramidParams), C.POINTER(PyramidPlanes), C.POINTER(PyramidPlanes), C.POINTER(PyramidInfo)]
+    L.crt_pyramid_down_device.argtypes = [C.c_int, C.POINTER(PyramidParams), C.POINTER(PyramidPlanes), C.POINTER(PyramidPlanes), C.c_void_p,
+                                          C.POINTER(PyramidInfo)]
+    L.crt_pyramid_merge.argtypes = [C.c_int, C.POINTER(PyramidParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PyramidInfo)]
+    L.crt_pyramid_merge_device.argtypes = [C.c_int, C.POINTER(PyramidParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(PyramidInfo)]
     L.crt_upsample_defaults.argtypes = [C.POINTER(UpsampleParams)]
     L.crt_upsample.argtypes = [C.c_int, C.POINTER(UpsampleParams), C.POINTER(UpsampleLow), C.POINTER(UpsampleGuides), C.c_void_p, C.c_void_p, C.c_void_p,
                                C.POINTER(UpsampleInfo)]

@@ -563,7 +563,7 @@ class Render:
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
                           sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
-                          demodulate=False, albedo_floor=None, nlm=None, regress=None):
+                          demodulate=False, albedo_floor=None, nlm=None, regress=None, scales=None):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
@@ -578,8 +578,15 @@ class Render:
         mirror; normal and depth stay first-hit.
         demodulate: the filter runs on irradiance.  The shading AOVs (self.shading_buffers: emission, diffuse_albedo) come from the same
         pass as the guides, the frame (and, variance_guided, its variance) goes through demodulate(albedo_floor), is filtered with the
-        caller's sigmas -- the albedo guide is still passed; sigma_albedo=float("inf") drops it -- and comes back through modulate()."""
+        caller's sigmas -- the albedo guide is still passed; sigma_albedo=float("inf") drops it -- and comes back through modulate().
+        scales: None or 1 is the single filter call; 2 .. 4 runs the filter as denoise_multiscale does, a Laplacian pyramid of that many
+        scales with the same settings at each, where the single call stands (so it composes with demodulate and specular_guides).  It
+        needs variance_guided, nlm or regress (ValueError); self.denoise_info is then denoise_multiscale's dict."""
         self._handle("run_view_denoised")
+        if scales is not None:
+            scales = _check_scales("run_view_denoised", scales)
+            if scales > 1 and not (variance_guided or (nlm is not None and nlm is not False) or (regress is not None and regress is not False)):
+                raise ValueError("run_view_denoised: scales needs variance_guided, nlm or regress (the pyramid reduces the variance with the frame)")
         nlm_settings = None
         if nlm is not None and nlm is not False:
             if variance_guided or iterations is not None or sigma_color is not None:
@@ -624,7 +631,12 @@ class Render:
             color, var = got if with_variance else (got, None)
         settings = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
                         device=self.device, want_rgb=not demodulate, return_info=True)
-        if nlm_settings is not None:
+        if scales is not None and scales > 1:
+            name, chosen = (("nlm", nlm_settings) if nlm_settings is not None else ("reg", regress_settings) if regress_settings is not None
+                            else ("var", {k: v for k, v in settings.items() if k in ("iterations", "sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth")}))
+            rgb, mean, self.denoise_info = denoise_multiscale(color, var, filter=name, scales=scales, device=self.device, want_rgb=not demodulate,
+                                                              return_info=True, **chosen, **self.aov_buffers)
+        elif nlm_settings is not None:
             rgb, mean, self.denoise_info = denoise_nlm(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **nlm_settings,
                                                        **self.aov_buffers)
         elif regress_settings is not None:
@@ -1413,6 +1425,135 @@ def upsample_device(width, height, low_width, low_height, low_ptrs, out_color_pt
                                               _vp(out_variance_ptr), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
                "crt_upsample_device")
     return info.as_dict() if want_info else None
+
+
+_PYRAMID_PLANES = (("color", 3), ("variance", 3), ("albedo", 3), ("normal", 3), ("depth", 1))
+MAX_SCALES = 4
+
+
+def pyramid_size(width, height):
+    """(low_width, low_height) of the next coarser scale: ((width + 1) // 2, (height + 1) // 2) (crt_pyramid_size)."""
+    lw, lh = C.c_uint32(), C.c_uint32()
+    capi.check(capi.lib().crt_pyramid_size(int(width), int(height), C.byref(lw), C.byref(lh)), "crt_pyramid_size")
+    return int(lw.value), int(lh.value)
+
+
+def _pyramid_params(width, height):
+    p = capi.PyramidParams()
+    p.width, p.height = int(width), int(height)
+    p.low_width, p.low_height = (p.width + 1) // 2, (p.height + 1) // 2
+    return p
+
+
+def pyramid_down(color, variance=None, albedo=None, normal=None, depth=None, device=0, return_info=False):
+    """The variance-aware 2 x reduction of a frame and its guides (crt_pyramid_down, contract: include/crt.h): color (H, W, 3) float32;
+    variance, albedo, normal (H, W, 3) and depth (H, W) are optional.  Returns a dict of the planes that were given at
+    ((H + 1) // 2, (W + 1) // 2); with return_info the pair (dict, crt_pyramid_info dict)."""
+    inputs, outputs = capi.PyramidPlanes(), capi.PyramidPlanes()
+    keep = _image_inputs("pyramid_down", "an (H, W, 3) colour image", (("color", color, 3), ("variance", variance, 3), ("albedo", albedo, 3),
+                                                                      ("normal", normal, 3), ("depth", depth, 1)), inputs)
+    h, w = keep[0].shape[:2]
+    prm = _pyramid_params(w, h)
+    out = {}
+    for (name, channels), a in zip(_PYRAMID_PLANES, keep):
+        if a is not None:
+            out[name] = np.zeros((prm.low_height, prm.low_width, 3) if channels == 3 else (prm.low_height, prm.low_width), dtype=np.float32)
+            setattr(outputs, name, out[name].ctypes.data)
+    info = capi.PyramidInfo()
+    capi.check(capi.lib().crt_pyramid_down(device, C.byref(prm), C.byref(inputs), C.byref(outputs), C.byref(info)), "crt_pyramid_down")
+    return (out, info.as_dict()) if return_info else out
+
+
+def pyramid_down_device(width, height, in_ptrs, out_ptrs, device=0, stream=None, want_info=True):
+    """Enqueues crt_pyramid_down_device with everything in device memory: in_ptrs / out_ptrs = {name: raw device pointer} with the names
+    color, variance, albedo, normal, depth; the outputs have ((height + 1) // 2) x ((width + 1) // 2) pixels.  With want_info the call
+    synchronizes the stream and returns the crt_pyramid_info dict, else None."""
+    def fill(ptrs):
+        struct = capi.PyramidPlanes()
+        for name, p in ptrs.items():
+            if name not in dict(_PYRAMID_PLANES):
+                raise ValueError("pyramid_down_device: unknown buffer %r" % name)
+            setattr(struct, name, int(p) if p else None)
+        return struct
+    prm = _pyramid_params(width, height)
+    info = capi.PyramidInfo()
+    capi.check(capi.lib().crt_pyramid_down_device(device, C.byref(prm), C.byref(fill(in_ptrs)), C.byref(fill(out_ptrs)), _vp(stream),
+                                                  C.byref(info) if want_info else None), "crt_pyramid_down_device")
+    return info.as_dict() if want_info else None
+
+
+def pyramid_merge(fine, coarse, device=0, want_rgb=True, want_mean=True, return_info=False):
+    """The pyramid's merge (crt_pyramid_merge, contract: include/crt.h): `fine` (H, W, 3), the filtered fine scale, with its low
+    frequencies replaced by `coarse` ((H + 1) // 2, (W + 1) // 2, 3), the finished result of the coarser scale.  Returns (rgb, mean) --
+    None for the one that is not wanted --, with return_info also the crt_pyramid_info dict.  There is no variance of the result."""
+    f = np.ascontiguousarray(fine, dtype=np.float32)
+    if f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError("pyramid_merge needs an (H, W, 3) fine image, got %r" % (f.shape,))
+    h, w = f.shape[:2]
+    prm = _pyramid_params(w, h)
+    c = np.ascontiguousarray(coarse, dtype=np.float32)
+    if c.shape != (prm.low_height, prm.low_width, 3):
+        raise ValueError("pyramid_merge: the coarse image has shape %r, expected %r" % (c.shape, (prm.low_height, prm.low_width, 3)))
+    mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+    rgb = np.zeros((h, w, 3), dtype=np.uint8) if want_rgb else None
+    info = capi.PyramidInfo()
+    capi.check(capi.lib().crt_pyramid_merge(device, C.byref(prm), capi.ptr(f), capi.ptr(c), capi.ptr(mean), capi.ptr(rgb), C.byref(info)),
+               "crt_pyramid_merge")
+    return (rgb, mean, info.as_dict()) if return_info else (rgb, mean)
+
+
+def pyramid_merge_device(width, height, fine_ptr, coarse_ptr, out_color_ptr, out_rgb_ptr=None, device=0, stream=None, want_info=True):
+    """Enqueues crt_pyramid_merge_device on raw device pointers; out_color_ptr or out_rgb_ptr may be None, not both.  want_info as
+    pyramid_down_device."""
+    prm = _pyramid_params(width, height)
+    info = capi.PyramidInfo()
+    capi.check(capi.lib().crt_pyramid_merge_device(device, C.byref(prm), _vp(fine_ptr), _vp(coarse_ptr), _vp(out_color_ptr), _vp(out_rgb_ptr),
+                                                   _vp(stream), C.byref(info) if want_info else None), "crt_pyramid_merge_device")
+    return info.as_dict() if want_info else None
+
+
+def _check_scales(who, scales):
+    if isinstance(scales, bool) or int(scales) != scales or not 1 <= int(scales) <= MAX_SCALES:
+        raise ValueError("%s: scales must be an integer 1 .. %d, got %r" % (who, MAX_SCALES, scales))
+    return int(scales)
+
+
+def denoise_multiscale(color, variance, albedo=None, normal=None, depth=None, filter="var", scales=2, device=0, want_rgb=True, return_info=False,
+                       **settings):
+    """A Laplacian pyramid over one of the single-scale filters: the frame and its guides are reduced scales - 1 times (pyramid_down), the
+    filter `filter` -- "var" (denoise_var), "nlm" (denoise_nlm) or "reg" (denoise_regress) -- runs with the same `settings` at every
+    scale, and the results are merged from the coarsest scale up (pyramid_merge).  scales is 1 .. 4; scales=1 is the filter's own call.
+    Returns (rgb, mean); with return_info also a dict: total_ms (the sum of the calls' timers) and calls (a list of (name, width,
+    height, total_ms))."""
+    who = "denoise_multiscale"
+    calls = {"var": denoise_var, "nlm": denoise_nlm, "reg": denoise_regress}
+    if filter not in calls:
+        raise ValueError("%s: filter must be one of %r, got %r" % (who, sorted(calls), filter))
+    scales = _check_scales(who, scales)
+    log = []
+    level = {"color": color, "variance": variance, "albedo": albedo, "normal": normal, "depth": depth}
+    if variance is None:
+        raise ValueError("%s needs the variance buffer (Render.variance)" % who)
+    levels = [level]
+    for _ in range(scales - 1):
+        h, w = np.shape(levels[-1]["color"])[:2]
+        low, info = pyramid_down(device=device, return_info=True, **levels[-1])
+        log.append(("pyramid_down", w, h, info["total_ms"]))
+        levels.append({name: low.get(name) for name, _ in _PYRAMID_PLANES})
+    result = None
+    for k in range(scales - 1, -1, -1):
+        lv = levels[k]
+        h, w = np.shape(lv["color"])[:2]
+        last = k == 0
+        rgb, mean, info = calls[filter](lv["color"], lv["variance"], albedo=lv["albedo"], normal=lv["normal"], depth=lv["depth"], device=device,
+                                        want_rgb=want_rgb and last and result is None, return_info=True, **settings)
+        log.append(("denoise_" + filter, w, h, info["total_ms"]))
+        if result is not None:
+            rgb, mean, info = pyramid_merge(mean, result, device=device, want_rgb=want_rgb and last, return_info=True)
+            log.append(("pyramid_merge", w, h, info["total_ms"]))
+        result = mean
+    out = (rgb, result)
+    return out + ({"total_ms": float(sum(c[3] for c in log)), "calls": log},) if return_info else out
 
 
 _SELECT_SETTINGS = ("error_radius", "blend_radius")

@@ -8,7 +8,7 @@
 //           [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]
 //           [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]
 //           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
-//           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K] [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]
+//           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K] [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE] [--denoise-scales N]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
@@ -45,6 +45,9 @@
 // --denoise-regress makes --denoise use the first-order feature-regression filter (crt_denoise_regress, its own defaults, every feature;
 // with --demodulate without the albedo feature); --denoise-regress-params sets its radius, patch, k and ridge, --denoise-sigma the scales
 // of its normal, albedo and depth features.  Not with --denoise-nlm, --denoise-variance or --denoise-iterations.
+// --denoise-scales N (1 .. 4) runs the filter of --denoise-variance, --denoise-nlm or --denoise-regress at N scales of a Laplacian pyramid
+// (crt_pyramid_down, crt_pyramid_merge; Render::set_denoise_scales), with the same settings at every scale; it needs one of the three and
+// is not for --denoise-select.
 // --denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]] makes --denoise pick, per pixel, the one of the filters in LIST -- none, atrous, var,
 // nlm, reg, joined by + (1 .. 4 of them), each with its own defaults, reg with its weights from the other half frame -- whose error estimated against the other half frame is smallest
 // (CRT_FLAG_HALF_BUFFERS, crt_half_buffers, crt_filter_select; the radii default to crt_filter_select_defaults').  --denoise-choice PATH
@@ -82,6 +85,7 @@ int main(int argc, char** argv)
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
                              "       [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]\n"
+                             "       [--denoise-scales N]  (1 .. 4 scales of a pyramid over --denoise-variance, --denoise-nlm or --denoise-regress)\n"
                              "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm, reg joined by +)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
@@ -104,6 +108,7 @@ int main(int argc, char** argv)
         crt_nlm_params nlm; // --denoise-nlm: the filter's defaults with the overrides
         crt_denoise_nlm_defaults(&nlm);
         bool denoise_regress = false, regress_params = false;
+        long denoise_scales = 0; // --denoise-scales N; 0: not given
         crt_regress_params reg; // --denoise-regress: the filter's defaults with the overrides
         crt_denoise_regress_defaults(&reg);
         std::vector<int> select_candidates; // --denoise-select: crt::Render::SELECT_* of LIST
@@ -232,6 +237,13 @@ int main(int argc, char** argv)
                 if (good) { q = end + 1; reg.ridge = std::strtof(q, &end); good = end != q && *end == 0; }
                 if (!good || radius < 0 || patch < 0) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress-params needs four comma-separated values: RADIUS,PATCH,K,RIDGE");
                 reg.radius = (uint32_t)radius; reg.patch = (uint32_t)patch;
+            }
+            else if (a == "--denoise-scales") {
+                need(i, 1);
+                char* end = nullptr;
+                const char* q = argv[++i];
+                denoise_scales = std::strtol(q, &end, 10);
+                if (end == q || *end != 0 || denoise_scales < 1 || denoise_scales > 4) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales needs a number of scales 1 .. 4");
             }
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
             else if (a == "--adaptive") { need(i, 1); ad.threshold = std::strtof(argv[++i], nullptr); adaptive = true; }
@@ -389,6 +401,9 @@ int main(int argc, char** argv)
         if (!denoise_choice.empty() && !denoise_select) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-choice needs --denoise-select LIST");
         if (denoise_select && (denoise_var || denoise_nlm || denoise_regress || dn_iterations || dn_sigma || denoise_specular || demodulate))
             throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select runs every filter with its own defaults on radiance (not with the other --denoise-* options or --demodulate)");
+        if (denoise_scales && denoise_select) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales is not for --denoise-select (the half frames are filtered at one scale)");
+        if (denoise_scales && !(denoise_var || denoise_nlm || denoise_regress))
+            throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales needs --denoise-variance, --denoise-nlm or --denoise-regress (the pyramid reduces the variance with the frame)");
         if (denoise_select && (adaptive || temporal)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs the half buffers of a uniformly sampled frame (not with --adaptive or --temporal)");
         const bool want_var = !variance.empty() || denoise_var || denoise_nlm || denoise_regress || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
@@ -520,6 +535,7 @@ int main(int argc, char** argv)
                 write_files("choice map", {{denoise_choice, 0, grey.data()}});
             }
         } else if (!denoise.empty()) {
+            if (denoise_scales) render.set_denoise_scales((unsigned)denoise_scales);
             if (denoise_regress) render.run_denoise_regress(reg); else if (denoise_nlm) render.run_denoise_nlm(nlm); else if (denoise_var) render.run_denoise_var(dn); else render.run_denoise(dn);
             const crt_denoise_info& di = render.last_denoise_info();
             std::printf("denoise: %u passes, device %.3f ms\n", di.passes, di.total_ms);

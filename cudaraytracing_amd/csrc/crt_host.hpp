@@ -17,6 +17,7 @@
 #include "../../include/crt.h"
 
 #include <cstdint>
+#include <functional>
 #include <stdexcept>
 #include <map>
 #include <string>
@@ -262,6 +263,11 @@ public:
     // likewise; with set_demodulate the albedo feature is taken off the mask.  last_regress_info(): its timer and fallback pixels
     void run_denoise_regress(const crt_regress_params& prm);
     const crt_regress_info& last_regress_info() const { return regress_info_; }
+    // Multi-scale denoising: run_denoise_var, run_denoise_nlm and run_denoise_regress run their filter at n scales of a Laplacian pyramid
+    // (crt_pyramid_down of the frame, its variance and the guides n - 1 times, the filter with the same settings at every scale,
+    // crt_pyramid_merge from the coarsest scale up), where the single call stands: it composes with set_demodulate.  n is 1 .. 4; 1 (the
+    // default) is the single call.  last_denoise_info() then holds the sum of the calls' timers, last_regress_info() the finest scale's.
+    void set_denoise_scales(unsigned n);
     // Error-estimated filter selection (crt_half_buffers, crt_filter_select): the last run_view must have had CRT_FLAG_HALF_BUFFERS
     // (set_flags).  candidates: 1 .. 4 of SELECT_NONE / _ATROUS / _VAR / _NLM / _REG, each run with its own defaults on either half frame,
     // the variance-taking ones with 2 x variance(), _REG with its weights from the other half frame; prm: crt_filter_select_defaults with
@@ -362,7 +368,11 @@ private:
     bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
     crt_variance_estimate_info estimate_info_{};
     void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance = false,
-                        const crt_nlm_params* nlm = nullptr); // nlm: crt_denoise_nlm with these settings instead (prm unused)
+                        const crt_nlm_params* nlm = nullptr, unsigned scales = 1); // nlm: crt_denoise_nlm with these settings instead (prm unused)
+    unsigned denoise_scales_ = 1;                    // set_denoise_scales
+    using ScaleFilter = std::function<int(uint32_t, uint32_t, const crt_pyramid_planes&, float*, unsigned char*)>;
+    __attribute__((visibility("hidden"))) void filter_scales(const char* who, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean,
+                                                             unsigned char* out_rgb, const ScaleFilter& filter);
     // set_aov_shading / set_demodulate
     bool aov_shading_ = false, demodulate_ = false;
     float albedo_floor_ = 0.0f;

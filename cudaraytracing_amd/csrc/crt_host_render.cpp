@@ -79,6 +79,11 @@ void Render::free()
     if (device_scene_) { crt_scene_destroy(device_scene_); device_scene_ = nullptr; }
     if (multi_) { crt_multi_destroy(multi_); multi_ = nullptr; }
 }
+void Render::set_denoise_scales(unsigned n)
+{
+    if (n < 1 || n > 4) throw Error(CRT_ERR_INVALID_ARG, "Render::set_denoise_scales: 1 .. 4 scales");
+    denoise_scales_ = n;
+}
 void Render::set_width(const unsigned& w)
 {
     scene_->set_width(w);
@@ -258,31 +263,91 @@ const float* Render::variance()
     return variance_buffer_.data();
 }
 
-// crt_denoise_var of a colour and its variance with the guides of the last run_aov
+// `filter` once per scale of a Laplacian pyramid of `scales` scales over the planes `in` of a w x h frame, from the coarsest scale up
+// (crt_pyramid_down, crt_pyramid_merge: the chain of denoise_multiscale in api.py); scales 1: the one call.  filter(w, h, planes, out_mean,
+// out_rgb) is the single-scale call with its settings at that size: it returns its status and leaves its timer in denoise_info_, which
+// holds the sum of every call's timer and of the filter's passes afterwards.
+void Render::filter_scales(const char* who, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean, unsigned char* out_rgb,
+                           const ScaleFilter& filter)
+{
+    if (scales <= 1) {
+        check(filter(w, h, in, out_mean, out_rgb), who);
+        return;
+    }
+    struct Level {
+        uint32_t w, h;
+        std::vector<float> color, variance, albedo, normal, depth;
+        crt_pyramid_planes planes;
+    };
+    std::vector<Level> levels(scales); // level 0: the caller's planes
+    levels[0].w = w; levels[0].h = h; levels[0].planes = in;
+    float total_ms = 0.0f;
+    uint32_t passes = 0;
+    crt_pyramid_info pinfo{};
+    for (unsigned k = 1; k < scales; k++) {
+        const Level& f = levels[k - 1];
+        Level& c = levels[k];
+        crt_pyramid_params pp{f.w, f.h, (f.w + 1) / 2, (f.h + 1) / 2};
+        c.w = pp.low_width; c.h = pp.low_height;
+        const size_t n = (size_t)c.w * c.h;
+        c.color.assign(3 * n, 0.0f);
+        if (f.planes.variance) c.variance.assign(3 * n, 0.0f);
+        if (f.planes.albedo) c.albedo.assign(3 * n, 0.0f);
+        if (f.planes.normal) c.normal.assign(3 * n, 0.0f);
+        if (f.planes.depth) c.depth.assign(n, 0.0f);
+        auto ptr = [](std::vector<float>& v) { return v.empty() ? nullptr : v.data(); };
+        crt_pyramid_out_planes out{ptr(c.color), ptr(c.variance), ptr(c.albedo), ptr(c.normal), ptr(c.depth)};
+        check(crt_pyramid_down(device_, &pp, &f.planes, &out, &pinfo), who);
+        total_ms += pinfo.total_ms;
+        c.planes = crt_pyramid_planes{out.color, out.variance, out.albedo, out.normal, out.depth};
+    }
+    std::vector<float> result, filtered, merged;
+    for (unsigned k = scales; k-- > 0;) {
+        const Level& l = levels[k];
+        const size_t n = (size_t)l.w * l.h;
+        std::vector<float>& dst = k + 1 == scales ? result : filtered;
+        dst.assign(3 * n, 0.0f);
+        check(filter(l.w, l.h, l.planes, dst.data(), nullptr), who);
+        total_ms += denoise_info_.total_ms; passes += denoise_info_.passes;
+        if (k + 1 == scales) continue;
+        crt_pyramid_params pp{l.w, l.h, (l.w + 1) / 2, (l.h + 1) / 2};
+        if (k == 0) check(crt_pyramid_merge(device_, &pp, filtered.data(), result.data(), out_mean, out_rgb, &pinfo), who);
+        else {
+            merged.assign(3 * n, 0.0f);
+            check(crt_pyramid_merge(device_, &pp, filtered.data(), result.data(), merged.data(), nullptr, &pinfo), who);
+            result.swap(merged);
+        }
+        total_ms += pinfo.total_ms;
+    }
+    denoise_info_.total_ms = total_ms; denoise_info_.passes = passes;
+}
+
+// crt_denoise_var of a colour and its variance with the guides of the last run_aov, at `scales` scales
 // (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
 void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance,
-                            const crt_nlm_params* nlm)
+                            const crt_nlm_params* nlm, unsigned scales)
 {
     const size_t n = scene_->get_pixels();
-    crt_denoise_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
     std::vector<float> irradiance, irradiance_variance;
     if (demodulate_ && !is_irradiance) {
         demodulate_of(who, color, variance, irradiance, irradiance_variance);
         color = irradiance.data(); variance = irradiance_variance.data();
     }
-    crt_denoise_var_inputs in{};
-    in.color = color; in.variance = variance;
-    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    const crt_pyramid_planes planes{color, variance, albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    unsigned char* const call_rgb = demodulate_ ? nullptr : denoised_buffer_.data();
-    int rc;
-    if (nlm) {
-        crt_nlm_params q = *nlm;
-        q.width = p.width; q.height = p.height;
-        rc = crt_denoise_nlm(device_, &q, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
-    } else rc = crt_denoise_var(device_, &p, &in, denoised_mean_buffer_.data(), call_rgb, nullptr, &denoise_info_);
-    check(rc, who);
+    filter_scales(who, scales, scene_->get_width(), scene_->get_height(), planes, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(),
+                  [&](uint32_t w, uint32_t h, const crt_pyramid_planes& l, float* out_mean, unsigned char* out_rgb) {
+                      crt_denoise_var_inputs in{};
+                      in.color = l.color; in.variance = l.variance; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
+                      if (nlm) {
+                          crt_nlm_params q = *nlm;
+                          q.width = w; q.height = h;
+                          return crt_denoise_nlm(device_, &q, &in, out_mean, out_rgb, nullptr, &denoise_info_);
+                      }
+                      crt_denoise_params p = prm;
+                      p.width = w; p.height = h;
+                      return crt_denoise_var(device_, &p, &in, out_mean, out_rgb, nullptr, &denoise_info_);
+                  });
     if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
 }
 
@@ -290,14 +355,14 @@ void Render::run_denoise_var(const crt_denoise_params& prm)
 {
     one_device("Render::run_denoise_var", "the denoiser");
     need_guides("Render::run_denoise_var");
-    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm);
+    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm, false, nullptr, denoise_scales_);
 }
 
 void Render::run_denoise_nlm(const crt_nlm_params& prm)
 {
     one_device("Render::run_denoise_nlm", "the denoiser");
     need_guides("Render::run_denoise_nlm");
-    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm);
+    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm, denoise_scales_);
 }
 
 void Render::run_denoise_regress(const crt_regress_params& prm)
@@ -307,7 +372,6 @@ void Render::run_denoise_regress(const crt_regress_params& prm)
     need_guides(who);
     const size_t n = scene_->get_pixels();
     crt_regress_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
     const float* color = mean_buffer_.data();
     const float* var = variance();
     std::vector<float> irradiance, irradiance_variance;
@@ -316,12 +380,19 @@ void Render::run_denoise_regress(const crt_regress_params& prm)
         color = irradiance.data(); var = irradiance_variance.data();
         p.features &= ~CRT_REGRESS_ALBEDO; // (irradiance does not follow the albedo)
     }
-    crt_regress_inputs in{};
-    in.color = color; in.variance = var;
-    in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
+    const crt_pyramid_planes planes{color, var, albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    check(crt_denoise_regress(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &regress_info_), who);
-    denoise_info_.total_ms = regress_info_.total_ms; denoise_info_.passes = 1;
+    filter_scales(who, denoise_scales_, scene_->get_width(), scene_->get_height(), planes, denoised_mean_buffer_.data(),
+                  demodulate_ ? nullptr : denoised_buffer_.data(),
+                  [&](uint32_t w, uint32_t h, const crt_pyramid_planes& l, float* out_mean, unsigned char* out_rgb) {
+                      crt_regress_params q = p;
+                      q.width = w; q.height = h;
+                      crt_regress_inputs in{};
+                      in.color = l.color; in.variance = l.variance; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
+                      const int rc = crt_denoise_regress(device_, &q, &in, out_mean, out_rgb, &regress_info_); // (the finest scale's call is the last)
+                      denoise_info_.total_ms = regress_info_.total_ms; denoise_info_.passes = 1;
+                      return rc;
+                  });
     if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
 }
 

@@ -998,6 +998,61 @@ int crt_upsample(int device, const crt_upsample_params* params, const crt_upsamp
 int crt_upsample_device(int device, const crt_upsample_params* params, const crt_upsample_low* dev_low, const crt_upsample_guides* dev_guides,
                         void* d_out_color, void* d_out_variance, void* d_out_rgb, void* hip_stream, crt_upsample_info* info);
 
+/* Multi-scale denoising: the two image operations of a Laplacian pyramid over crt_denoise_var, crt_denoise_nlm and crt_denoise_regress
+ * (Rousselle et al. 2012; Delbracio et al. 2014; the last stage of NFOR).  A single-scale filter sees one window, so noise coarser than
+ * the window stays; the pyramid filters the frame at every scale and replaces the low frequencies of a finer result with the coarser
+ * scale's result.  crt_pyramid_down halves a frame and its guides, crt_pyramid_merge puts a finished coarser result into a filtered
+ * finer one.  Image operations: no scene handle, no scratch; row-major images; color, variance, albedo and normal 3 floats per pixel,
+ * depth 1.  The fine image is width x height, the coarse one low_width x low_height with
+ *   low_width = (width + 1) / 2        low_height = (height + 1) / 2                            (crt_pyramid_size; a scale may be 1 x 1)
+ * crt_pyramid_down, per coarse pixel (X, Y): the taps are the fine pixels (2X, 2Y), (2X + 1, 2Y), (2X, 2Y + 1), (2X + 1, 2Y + 1), in that
+ * order; a tap outside the fine image is skipped; n = the number of taps taken, as a float (4, 2 or 1).  Every sum starts at +0.0f and
+ * runs in that order:
+ *   color, albedo, normal (per channel):   out = sum / n
+ *   variance (per channel):                out = sum / (n * n)                 (the variance of the mean of n independent pixels)
+ *   depth:  sum and the count nd run over the taps with depth > 0 only (false for NaN);  out = nd > 0 ? sum / nd : 0.0f
+ *           (a miss does not pull a surface's depth towards the eye)
+ * color is required; every other plane is optional, as an input / output pair.
+ * crt_pyramid_merge, with `fine` the filtered fine scale and `coarse` the finished result of the coarser scale:
+ *   d(Q)   = coarse(Q) - D(fine)(Q)       per channel and coarse pixel Q; D: exactly crt_pyramid_down's colour line
+ *   out(p) = fine(p) + U(d)(p)            per channel and fine pixel p
+ * U is crt_upsample's interpolation without guides at radius 1 from low_width x low_height: its sx, sy, u, v, x0, y0, wx, wy, hw lines, its
+ * taps in its order (ty = y0, y0 + 1 outer, tx = x0, x0 + 1 inner, a tap outside the coarse image skipped),
+ *   snum = snum + d(q) * hw      sden = sden + hw      U(d)(p) = snum / sden
+ * out_rgb = the frame's tone map of out (the bits crt_render writes for that mean).  With coarse = D(fine) every d is +-0 and out has
+ * fine's values.  There is NO variance output: the fine and the coarse result come from the same samples and are correlated, so the
+ * variance of their combination is not the sum the filters' own estimates would give.
+ * In both operations every * + - / is one IEEE fp32 operation (no FMA, no reciprocal multiply); non-finite inputs are not special-cased:
+ * the arithmetic defines the result.  The library has two forms of the merge kernel (csrc/crt_pyramid.h: `staged` computes each d once
+ * per workgroup into LDS, `direct` once per tap); the environment variable CRT_PYRAMID_FORM=direct|staged, read per call, selects one (for
+ * tests; any other value is CRT_ERR_INVALID_ARG), and both give the same bits.
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null params (down: inputs, outputs, either colour buffer; merge: fine or coarse);
+ * a size of 0; low sizes that are not ((width + 1) / 2, (height + 1) / 2); down: one of a plane's input / output pair without the other;
+ * merge: neither out_color nor out_rgb; a negative device index.  A side longer than 2^24 pixels or more than 2^31 thread blocks
+ * (down: 64 x 4 coarse pixels, merge: 32 x 8 pixels): CRT_ERR_UNSUPPORTED.
+ * Not done: a guide-aware U, a variance of the merged result, per-scale filter settings. */
+typedef struct {
+    uint32_t width, height;          /* the fine image */
+    uint32_t low_width, low_height;  /* the coarse image: ((width + 1) / 2, (height + 1) / 2) */
+} crt_pyramid_params;
+typedef struct { const float* color; const float* variance; const float* albedo; const float* normal; const float* depth; } crt_pyramid_planes;  /* width x height */
+typedef struct { float* color; float* variance; float* albedo; float* normal; float* depth; } crt_pyramid_out_planes;                            /* low_width x low_height */
+typedef struct {
+    float total_ms;            /* HIP-event time of the call's kernel on its stream */
+} crt_pyramid_info;
+int crt_pyramid_size(uint32_t width, uint32_t height, uint32_t* low_width, uint32_t* low_height);
+/* host buffers; allocates and frees its own device memory on `device`; info optional */
+int crt_pyramid_down(int device, const crt_pyramid_params* params, const crt_pyramid_planes* host_in, const crt_pyramid_out_planes* host_out,
+                     crt_pyramid_info* info);
+int crt_pyramid_merge(int device, const crt_pyramid_params* params, const float* fine, const float* coarse, float* out_color, uint8_t* out_rgb,
+                      crt_pyramid_info* info);
+/* Everything in device memory on `device`; enqueued on hip_stream (NULL = default stream) without synchronizing, unless info != NULL
+ * (the call then synchronizes the stream to read the timer).  Outputs must not overlap inputs. */
+int crt_pyramid_down_device(int device, const crt_pyramid_params* params, const crt_pyramid_planes* dev_in, const crt_pyramid_out_planes* dev_out,
+                            void* hip_stream, crt_pyramid_info* info);
+int crt_pyramid_merge_device(int device, const crt_pyramid_params* params, const void* d_fine, const void* d_coarse, void* d_out_color, void* d_out_rgb,
+                             void* hip_stream, crt_pyramid_info* info);
+
 /* Error-estimated filter selection: per pixel, the one of K filtered candidates whose error, estimated against an independent half
  * frame, is smallest (Rousselle et al. 2012).  The caller renders with CRT_FLAG_HALF_BUFFERS, applies every candidate filter k to half
  * A and to half B (crt_half_buffers), and passes the halves, the variance of ONE half's mean (2 x crt_variance) and the 2 K filtered

@@ -45,6 +45,17 @@ crt_denoise_regress for every combination of the --sweep-* values instead, by it
   python tools/denoise_probe.py --regress [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--regress-params 5,1,0.6,0.4]
   python tools/denoise_probe.py --regress --error --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
   python tools/denoise_probe.py --regress --error --sweep --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
+
+--scales times the two operations of the pyramid (crt_pyramid_down_device with every plane; crt_pyramid_merge_device in both forms,
+CRT_PYRAMID_FORM=direct|staged, read per call) at --sizes beside one a-trous pass, and, per filter (var, nlm, reg, their defaults), the
+single call and the whole chain of denoise_multiscale at 2 and 3 scales made of the *_device calls: all in one process, the calls
+taking turns, HIP events (a chain: the sum of its calls' timers), the median of --calls calls.  With --error it lists, per scene
+(cornell-box-textured as above) and --error-spps, the error of the unfiltered frame and of var, nlm, reg and nlm at radius 3 at 1 ..
+--max-scales scales (denoise_multiscale) against --ref-spp samples of --ref-seed, at --error-size.
+
+  python tools/denoise_probe.py --scales [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5]
+  python tools/denoise_probe.py --scales --error --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
+  python tools/denoise_probe.py --scales --error --ref-seed 7 --error-size 800x600 --ref-spp 2048 --error-spps 8 --max-scales 4
 """
 import argparse
 import json
@@ -368,6 +379,145 @@ def regress_error_table(a):
     print(json.dumps(out), flush=True)
 
 
+def _probe_scene(name, w, h, cells):
+    """(task, view, scene) of a scene name of --scenes; cornell-box-textured is generated into a temporary directory"""
+    textured = name == "cornell-box-textured"
+    t = crt.Task(os.path.join(ROOT, "scenes", "cornell-box" if textured else name, "config.json"), base_dir=ROOT)
+    view = (t.eye_pos, crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up), crt.fov_to_radians(t.fov_y))
+    if not textured:
+        return t, view, crt.Scene.from_task(t, w, h)
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "scenes"))
+    import gen_cornell_box
+    with tempfile.TemporaryDirectory(prefix="crt_textured_") as d:  # (the loader reads the files in add_obj and keeps nothing of them open)
+        obj, mtl_dir, _ = gen_cornell_box.write_textured_variant(d, cells)
+        scene = crt.Scene(w, h)
+        scene.add_obj(obj, mtl_dir)
+        scene.set_BVH(t.bvh_thresh_n)
+    return t, view, scene
+
+
+SCALE_FILTERS = (("var", "var", {}), ("nlm", "nlm", {}), ("reg", "reg", {}), ("nlm_r3", "nlm", {"radius": 3}))
+
+
+def scales_error_table(a):
+    """--scales --error: per scene and sample count, every filter of SCALE_FILTERS at 1 .. --max-scales scales"""
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "ref_spp": a.ref_spp, "ref_seed": a.ref_seed, "rows": []}
+    for name in a.scenes.split(","):
+        t, view, scene = _probe_scene(name, w, h, a.cells)
+        r = crt.Render(scene, a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = a.ref_seed
+        ref = r.run_view(*view).astype(np.float64)
+        r.seed = 0
+        for spp in [int(v) for v in a.error_spps.split(",")]:
+            r.set_spp(spp)
+            noisy_rgb = r.run_view(*view, want_variance=True).copy()
+            mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
+            g = r.run_view_aov(*view, want=("albedo", "normal", "depth"))
+            row = {"scene": name, "spp": spp, "unfiltered": round(float(np.mean((noisy_rgb.astype(np.float64) - ref) ** 2)), 1)}
+            for label, filt, settings in SCALE_FILTERS:
+                row[label] = [round(float(np.mean((crt.denoise_multiscale(mean, var, filter=filt, scales=n, **settings, **g)[0].astype(np.float64) - ref) ** 2)), 1)
+                              for n in range(1, a.max_scales + 1)]
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        r.free()
+    print(json.dumps(out), flush=True)
+
+
+def scales_times(a):
+    """--scales: the pyramid's two operations, one a-trous pass, and per filter the single call and the chains at 2 and 3 scales"""
+    t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
+    view = (t.eye_pos, crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up), crt.fov_to_radians(t.fov_y))
+    out = {"scene": a.scene, "spp": a.spp, "calls": a.calls, "warmup": a.warmup, "runs": []}
+    before = os.environ.get("CRT_PYRAMID_FORM")
+    planes = (("color", 12), ("variance", 12), ("albedo", 12), ("normal", 12), ("depth", 4))
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+        r.run_view(*view, want_variance=True)
+        host = dict(r.run_view_aov(*view, want=("albedo", "normal", "depth")), color=r.mean_buffer, variance=r.variance_buffer)
+        r.free()
+        sizes = [(w, h)]
+        for _ in range(2):
+            sizes.append(crt.pyramid_size(*sizes[-1]))
+        scratch_bytes = max(crt.denoise_scratch_bytes(w, h), crt.denoise_nlm_scratch_bytes(w, h), crt.denoise_regress_scratch_bytes(w, h))
+        buffers = {n + "0": host[n] for n, _ in planes}
+        for k, (lw, lh) in enumerate(sizes):
+            if k:
+                buffers.update({n + str(k): lw * lh * b for n, b in planes})
+            buffers.update({"f%d" % k: lw * lh * 12, "m%d" % k: lw * lh * 12})
+        buffers.update(out_rgb=w * h * 3, out_var=w * h * 4, scratch=scratch_bytes)
+        dev = hipmem.DeviceBuffers(buffers)
+        ptrs = dev.ptrs
+
+        def level(k):
+            return {n: ptrs[n + str(k)] for n, _ in planes}
+
+        def down(k):  # level k - 1 -> level k
+            return crt.pyramid_down_device(*sizes[k - 1], level(k - 1), level(k))["total_ms"]
+
+        def merge(k, coarse, rgb, form=None):  # f<k> and the coarser result -> m<k>
+            if form is None:
+                os.environ.pop("CRT_PYRAMID_FORM", None)
+            else:
+                os.environ["CRT_PYRAMID_FORM"] = form
+            return crt.pyramid_merge_device(*sizes[k], ptrs["f%d" % k], coarse, ptrs["m%d" % k], ptrs["out_rgb"] if rgb else None)["total_ms"]
+
+        def filt(name, k, rgb):  # level k -> f<k>
+            lw, lh = sizes[k]
+            p = level(k)
+            guides = dict(albedo_ptr=p["albedo"], normal_ptr=p["normal"], depth_ptr=p["depth"])
+            rgb_ptr = ptrs["out_rgb"] if rgb else None
+            if name == "reg":
+                return crt.denoise_regress_device(lw, lh, p["color"], p["variance"], ptrs["f%d" % k], rgb_ptr, ptrs["scratch"], scratch_bytes, **guides)["total_ms"]
+            call = crt.denoise_var_device if name == "var" else crt.denoise_nlm_device
+            return call(lw, lh, p["color"], p["variance"], ptrs["f%d" % k], rgb_ptr, None, ptrs["scratch"], scratch_bytes, **guides)["total_ms"]
+
+        def chain(name, scales):
+            ms = sum(down(k) for k in range(1, scales))
+            result = None
+            for k in range(scales - 1, -1, -1):
+                ms += filt(name, k, rgb=scales == 1)
+                if result is None:
+                    result = ptrs["f%d" % k]
+                else:
+                    ms += merge(k, result, rgb=k == 0)
+                    result = ptrs["m%d" % k]
+            return ms
+
+        down(1)  # (level 1 holds a reduced frame for the merges timed alone)
+        calls = {"atrous_1": lambda: crt.denoise_device(w, h, ptrs["color0"], ptrs["f0"], ptrs["out_rgb"], ptrs["scratch"], scratch_bytes, albedo_ptr=ptrs["albedo0"],
+                                                        normal_ptr=ptrs["normal0"], depth_ptr=ptrs["depth0"], iterations=1)["total_ms"],
+                 "pyramid_down": lambda: down(1),
+                 "pyramid_merge_direct": lambda: merge(0, ptrs["color1"], True, "direct"),
+                 "pyramid_merge_staged": lambda: merge(0, ptrs["color1"], True, "staged")}
+        for name in ("var", "nlm", "reg"):
+            for scales in (1, 2, 3):
+                calls["%s_%d" % (name, scales)] = lambda name=name, scales=scales: chain(name, scales)
+        ms = {k: [] for k in calls}
+        for _ in range(a.warmup + a.calls):
+            for k, f in calls.items():
+                ms[k].append(f())
+        run = {"width": w, "height": h}
+        for k, v in ms.items():
+            run[k + "_ms_median"] = round(statistics.median(v[a.warmup:]), 4)
+            run[k + "_ms_best"] = round(min(v[a.warmup:]), 4)
+        run["staged_over_direct"] = round(run["pyramid_merge_staged_ms_median"] / run["pyramid_merge_direct_ms_median"], 4)
+        for name in ("var", "nlm", "reg"):
+            for scales in (2, 3):
+                run["%s_%d_over_1" % (name, scales)] = round(run["%s_%d_ms_median" % (name, scales)] / run[name + "_1_ms_median"], 4)
+        out["runs"].append(run)
+        print(json.dumps(run), file=sys.stderr, flush=True)
+        dev.free()
+    if before is None:
+        os.environ.pop("CRT_PYRAMID_FORM", None)
+    else:
+        os.environ["CRT_PYRAMID_FORM"] = before
+    print(json.dumps(out), flush=True)
+
+
 def error_table(a):
     import numpy as np
     w, h = (int(v) for v in a.error_size.split("x"))
@@ -436,9 +586,14 @@ def main():
     ap.add_argument("--sweep-ridge", default="0.001,0.01,0.1")
     ap.add_argument("--sweep-sigma-position", default="0.5,1,2")
     ap.add_argument("--sweep-features", default="15,13,12,8,7", help="masks of the REGRESS_* bits (normal 1, albedo 2, depth 4, position 8)")
+    ap.add_argument("--scales", action="store_true", help="time crt_pyramid_down_device / crt_pyramid_merge_device and the multi-scale chains; with --error: the error rows")
+    ap.add_argument("--max-scales", type=int, default=3, help="--scales --error: the most scales of a row (1 .. 4)")
+    ap.add_argument("--error-spps", default="8,32", help="--scales --error: the sample counts of the rows")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
+    if a.scales:
+        return scales_error_table(a) if a.error else scales_times(a)
     if a.regress:
         return regress_error_table(a) if a.error else regress_times(a)
     if a.error:
