@@ -583,36 +583,10 @@ class Render:
         scales with the same settings at each, where the single call stands (so it composes with demodulate and specular_guides).  It
         needs variance_guided, nlm or regress (ValueError); self.denoise_info is then denoise_multiscale's dict."""
         self._handle("run_view_denoised")
-        if scales is not None:
-            scales = _check_scales("run_view_denoised", scales)
-            if scales > 1 and not (variance_guided or (nlm is not None and nlm is not False) or (regress is not None and regress is not False)):
-                raise ValueError("run_view_denoised: scales needs variance_guided, nlm or regress (the pyramid reduces the variance with the frame)")
-        nlm_settings = None
-        if nlm is not None and nlm is not False:
-            if variance_guided or iterations is not None or sigma_color is not None:
-                raise ValueError("run_view_denoised: nlm excludes variance_guided, iterations and sigma_color (the a-trous filter's)")
-            nlm_settings = {} if nlm is True else dict(nlm)
-            unknown = sorted(set(nlm_settings) - set(_NLM_SETTINGS))
-            if unknown:
-                raise ValueError("run_view_denoised: unknown nlm settings %r" % (unknown,))
-            for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
-                if v is not None:
-                    nlm_settings[name] = v
-        regress_settings = None
-        if regress is not None and regress is not False:
-            if nlm_settings is not None or variance_guided or iterations is not None or sigma_color is not None:
-                raise ValueError("run_view_denoised: regress excludes nlm, variance_guided, iterations and sigma_color")
-            regress_settings = {} if regress is True else dict(regress)
-            unknown = sorted(set(regress_settings) - set(_REGRESS_SETTINGS))
-            if unknown:
-                raise ValueError("run_view_denoised: unknown regress settings %r" % (unknown,))
-            for name, v in (("sigma_normal", sigma_normal), ("sigma_albedo", sigma_albedo), ("sigma_depth", sigma_depth)):
-                if v is not None:
-                    regress_settings[name] = v
-            if demodulate:
-                mask = regress_settings.get("features")
-                regress_settings["features"] = (denoise_regress_defaults()["features"] if mask is None else int(mask)) & ~capi.REGRESS_ALBEDO
-        with_variance = variance_guided or nlm_settings is not None or regress_settings is not None
+        scales = 1 if scales is None else _check_scales("run_view_denoised", scales)
+        name, settings = _legacy_filter("run_view_denoised", variance_guided, iterations, sigma_color,
+                                        dict(sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth), nlm, regress, scales, demodulate)
+        with_variance = _FILTERS[name][2]
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=with_variance)
         guides = ("albedo", "normal", "depth")
         if demodulate:
@@ -629,23 +603,11 @@ class Render:
             sh = self.shading_buffers
             got = _demodulate(color, sh["diffuse_albedo"], sh["emission"], variance=var, albedo_floor=albedo_floor, device=self.device)
             color, var = got if with_variance else (got, None)
-        settings = dict(iterations=iterations, sigma_color=sigma_color, sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth,
-                        device=self.device, want_rgb=not demodulate, return_info=True)
-        if scales is not None and scales > 1:
-            name, chosen = (("nlm", nlm_settings) if nlm_settings is not None else ("reg", regress_settings) if regress_settings is not None
-                            else ("var", {k: v for k, v in settings.items() if k in ("iterations", "sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth")}))
+        if scales > 1:
             rgb, mean, self.denoise_info = denoise_multiscale(color, var, filter=name, scales=scales, device=self.device, want_rgb=not demodulate,
-                                                              return_info=True, **chosen, **self.aov_buffers)
-        elif nlm_settings is not None:
-            rgb, mean, self.denoise_info = denoise_nlm(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **nlm_settings,
-                                                       **self.aov_buffers)
-        elif regress_settings is not None:
-            rgb, mean, self.denoise_info = denoise_regress(color, var, device=self.device, want_rgb=not demodulate, return_info=True, **regress_settings,
-                                                           **self.aov_buffers)
-        elif variance_guided:
-            rgb, mean, self.denoise_info = denoise_var(color, var, **settings, **self.aov_buffers)
+                                                              return_info=True, **settings, **self.aov_buffers)
         else:
-            rgb, mean, self.denoise_info = denoise(color, **settings, **self.aov_buffers)
+            rgb, mean, self.denoise_info = _run_filter(name, color, var, self.aov_buffers, settings, self.device, not demodulate)
         if demodulate:
             rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
         return rgb, mean
@@ -714,7 +676,7 @@ class Render:
             color, var = _demodulate(color, low["diffuse_albedo"], low["emission"], variance=var, albedo_floor=albedo_floor, device=self.device)
         low_guides = {k: low[k] for k in guides}
         if filter_low:
-            color = denoise_var(color, var, device=self.device, want_rgb=False, **low_guides)[1]
+            color = _run_filter("var", color, var, low_guides, {}, self.device, False)[1]
         rgb, mean, self.upsampled_variance, self.upsample_info = upsample(dict(low_guides, color=color, variance=var), w, h, guides=self.aov_buffers,
                                                                           device=self.device, want_rgb=not demodulate, return_info=True,
                                                                           **upsample_settings)
@@ -791,7 +753,7 @@ class Render:
         """What run_view_temporal returns of the accumulated frame (mean, var): filtered with denoise, and back from irradiance with
         demodulate."""
         if denoise:
-            rgb, mean, self.denoise_info = denoise_var(mean, var, device=self.device, want_rgb=not demodulate, return_info=True, **self.aov_buffers)
+            rgb, mean, self.denoise_info = _run_filter("var", mean, var, self.aov_buffers, {}, self.device, not demodulate)
         if demodulate:
             sh = self.shading_buffers
             rgb, mean = _modulate(mean, sh["diffuse_albedo"], sh["emission"], albedo_floor=albedo_floor, device=self.device)
@@ -1518,6 +1480,46 @@ def _check_scales(who, scales):
     return int(scales)
 
 
+_ATROUS_SETTINGS = ("iterations", "sigma_color", "sigma_normal", "sigma_albedo", "sigma_depth")
+# the single-frame filters: name: (the host call, the settings it accepts, whether it takes a variance, whether it can take its weights from
+# another image)
+_FILTERS = {"atrous": (denoise, _ATROUS_SETTINGS, False, False), "var": (denoise_var, _ATROUS_SETTINGS, True, False),
+            "nlm": (denoise_nlm, _NLM_SETTINGS, True, False), "reg": (denoise_regress, _REGRESS_SETTINGS, True, True)}
+
+
+def _run_filter(name, color, variance, guides, settings, device, want_rgb, weights=None):
+    """Filter `name` of _FILTERS on a frame: returns (rgb, mean, info), rgb None without want_rgb.  guides: albedo, normal, depth as
+    keywords; settings: the filter's own (None or absent: its default); weights: the image a filter that can takes its weights from,
+    with `variance` as that image's variance.  The one place that knows how the calls' argument lists differ."""
+    call, _, takes_variance, takes_weights = _FILTERS[name]
+    if takes_weights and weights is not None:
+        settings = dict(settings, weight_color=weights, weight_variance=variance)
+    return call(*((color, variance) if takes_variance else (color,)), device=device, want_rgb=want_rgb, return_info=True, **guides, **settings)
+
+
+def _legacy_filter(who, variance_guided, iterations, sigma_color, sigmas, nlm, regress, scales, demodulate):
+    """run_view_denoised's way of choosing a filter as (name, settings) of _FILTERS.  nlm, regress: None or False = not chosen, True =
+    its defaults, or a dict of its settings; sigmas: the three guide sigmas, which go to whichever filter is chosen."""
+    own = [(key, arg, given, excludes) for key, arg, given, excludes in
+           (("nlm", "nlm", nlm, "variance_guided, iterations and sigma_color (the a-trous filter's)"),
+            ("reg", "regress", regress, "nlm, variance_guided, iterations and sigma_color")) if given is not None and given is not False]
+    if scales > 1 and not (variance_guided or own):
+        raise ValueError("%s: scales needs variance_guided, nlm or regress (the pyramid reduces the variance with the frame)" % who)
+    name, settings = "var" if variance_guided else "atrous", dict(sigmas, iterations=iterations, sigma_color=sigma_color)
+    for key, arg, given, excludes in own:
+        if name != "atrous" or iterations is not None or sigma_color is not None:
+            raise ValueError("%s: %s excludes %s" % (who, arg, excludes))
+        name, settings = key, {} if given is True else dict(given)
+        unknown = sorted(set(settings) - set(_FILTERS[key][1]))
+        if unknown:
+            raise ValueError("%s: unknown %s settings %r" % (who, arg, unknown))
+        settings.update({k: v for k, v in sigmas.items() if v is not None})
+    if name == "reg" and demodulate:  # irradiance does not follow the albedo: the feature goes, from an explicit mask too
+        mask = settings.get("features")
+        settings["features"] = (denoise_regress_defaults()["features"] if mask is None else int(mask)) & ~capi.REGRESS_ALBEDO
+    return name, settings
+
+
 def denoise_multiscale(color, variance, albedo=None, normal=None, depth=None, filter="var", scales=2, device=0, want_rgb=True, return_info=False,
                        **settings):
     """A Laplacian pyramid over one of the single-scale filters: the frame and its guides are reduced scales - 1 times (pyramid_down), the
@@ -1526,9 +1528,9 @@ def denoise_multiscale(color, variance, albedo=None, normal=None, depth=None, fi
     Returns (rgb, mean); with return_info also a dict: total_ms (the sum of the calls' timers) and calls (a list of (name, width,
     height, total_ms))."""
     who = "denoise_multiscale"
-    calls = {"var": denoise_var, "nlm": denoise_nlm, "reg": denoise_regress}
-    if filter not in calls:
-        raise ValueError("%s: filter must be one of %r, got %r" % (who, sorted(calls), filter))
+    names = sorted(n for n in _FILTERS if _FILTERS[n][2])  # (the pyramid reduces the variance with the frame)
+    if filter not in names:
+        raise ValueError("%s: filter must be one of %r, got %r" % (who, names, filter))
     scales = _check_scales(who, scales)
     log = []
     level = {"color": color, "variance": variance, "albedo": albedo, "normal": normal, "depth": depth}
@@ -1545,8 +1547,8 @@ def denoise_multiscale(color, variance, albedo=None, normal=None, depth=None, fi
         lv = levels[k]
         h, w = np.shape(lv["color"])[:2]
         last = k == 0
-        rgb, mean, info = calls[filter](lv["color"], lv["variance"], albedo=lv["albedo"], normal=lv["normal"], depth=lv["depth"], device=device,
-                                        want_rgb=want_rgb and last and result is None, return_info=True, **settings)
+        rgb, mean, info = _run_filter(filter, lv["color"], lv["variance"], {g: lv[g] for g in ("albedo", "normal", "depth")}, settings, device,
+                                      want_rgb and last and result is None)
         log.append(("denoise_" + filter, w, h, info["total_ms"]))
         if result is not None:
             rgb, mean, info = pyramid_merge(mean, result, device=device, want_rgb=want_rgb and last, return_info=True)
@@ -1563,15 +1565,7 @@ _SELECT_CANDIDATES = ("none", "atrous", "var", "nlm", "reg")
 def _select_candidate(name, half, half_variance, guides, device, other=None):
     """Candidate filter `name` of run_view_selected applied to one half frame, with its own defaults; other: the other half frame, where
     "reg" takes its weights"""
-    if name == "none":
-        return half
-    if name == "atrous":
-        return denoise(half, device=device, want_rgb=False, **guides)[1]
-    if name == "var":
-        return denoise_var(half, half_variance, device=device, want_rgb=False, **guides)[1]
-    if name == "reg":
-        return denoise_regress(half, half_variance, weight_color=other, weight_variance=half_variance, device=device, want_rgb=False, **guides)[1]
-    return denoise_nlm(half, half_variance, device=device, want_rgb=False, **guides)[1]
+    return half if name == "none" else _run_filter(name, half, half_variance, guides, {}, device, False, weights=other)[1]
 
 
 def filter_select_defaults():

@@ -384,18 +384,18 @@ int main(int argc, char** argv)
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
-        refuse_on_many(1);
-        if (denoise_nlm && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm needs --denoise PATH");
-        if (nlm_params && !denoise_nlm) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm-params needs --denoise-nlm");
-        if (denoise_nlm && denoise_var) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is a filter of its own (not with --denoise-variance)");
-        if (denoise_nlm && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-nlm is one pass (not with --denoise-iterations)");
-        if (denoise_nlm && dn_sigma) { nlm.sigma_normal = dn.sigma_normal; nlm.sigma_albedo = dn.sigma_albedo; nlm.sigma_depth = dn.sigma_depth; }
-        refuse_on_many(1);
-        if (denoise_regress && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress needs --denoise PATH");
-        if (regress_params && !denoise_regress) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress-params needs --denoise-regress");
-        if (denoise_regress && (denoise_var || denoise_nlm)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress is a filter of its own (not with --denoise-variance or --denoise-nlm)");
-        if (denoise_regress && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-regress is one pass (not with --denoise-iterations)");
-        if (denoise_regress && dn_sigma) { reg.sigma_normal = dn.sigma_normal; reg.sigma_albedo = dn.sigma_albedo; reg.sigma_depth = dn.sigma_depth; }
+        // --denoise-nlm and --denoise-regress: filters of their own with the same rules; --denoise-sigma's guide sigmas go to their settings
+        const struct { std::string flag; bool on, params, others; const char* not_with; float* sigmas[3]; } own_filters[] = {
+            {"--denoise-nlm", denoise_nlm, nlm_params, denoise_var, "--denoise-variance", {&nlm.sigma_normal, &nlm.sigma_albedo, &nlm.sigma_depth}},
+            {"--denoise-regress", denoise_regress, regress_params, denoise_var || denoise_nlm, "--denoise-variance or --denoise-nlm", {&reg.sigma_normal, &reg.sigma_albedo, &reg.sigma_depth}}};
+        for (const auto& f : own_filters) {
+            refuse_on_many(1);
+            if (f.on && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, f.flag + " needs --denoise PATH");
+            if (f.params && !f.on) throw crt::Error(CRT_ERR_INVALID_ARG, f.flag + "-params needs " + f.flag);
+            if (f.on && f.others) throw crt::Error(CRT_ERR_INVALID_ARG, f.flag + " is a filter of its own (not with " + f.not_with + ")");
+            if (f.on && dn_iterations) throw crt::Error(CRT_ERR_INVALID_ARG, f.flag + " is one pass (not with --denoise-iterations)");
+            if (f.on && dn_sigma) { *f.sigmas[0] = dn.sigma_normal; *f.sigmas[1] = dn.sigma_albedo; *f.sigmas[2] = dn.sigma_depth; }
+        }
         const bool denoise_select = !select_candidates.empty();
         if (denoise_select && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs --denoise PATH");
         if (!denoise_choice.empty() && !denoise_select) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-choice needs --denoise-select LIST");

@@ -17,7 +17,6 @@
 #include "../../include/crt.h"
 
 #include <cstdint>
-#include <functional>
 #include <stdexcept>
 #include <map>
 #include <string>
@@ -367,12 +366,19 @@ private:
     std::vector<float> temporal_m1_, temporal_m2_;   // run_temporal_moments: the history's moment planes
     bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
     crt_variance_estimate_info estimate_info_{};
-    void denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance = false,
-                        const crt_nlm_params* nlm = nullptr, unsigned scales = 1); // nlm: crt_denoise_nlm with these settings instead (prm unused)
     unsigned denoise_scales_ = 1;                    // set_denoise_scales
-    using ScaleFilter = std::function<int(uint32_t, uint32_t, const crt_pyramid_planes&, float*, unsigned char*)>;
-    __attribute__((visibility("hidden"))) void filter_scales(const char* who, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean,
-                                                             unsigned char* out_rgb, const ScaleFilter& filter);
+    // a single-frame filter with its settings: kind is SELECT_ATROUS .. SELECT_REG, and the settings of that kind are the ones that count
+    struct Filter {
+        int kind;
+        crt_denoise_params dn{};                     // SELECT_ATROUS, SELECT_VAR
+        crt_nlm_params nlm{};
+        crt_regress_params reg{};
+    };
+    static Filter default_filter(int kind);          // every kind's settings as the library's defaults fill them
+    int apply_filter(const Filter& f, uint32_t w, uint32_t h, const crt_pyramid_planes& in, const float* weights, float* out_mean, unsigned char* out_rgb,
+                     crt_denoise_info* info);
+    void filter_scales(const char* who, const Filter& f, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean, unsigned char* out_rgb);
+    void denoise_of(const char* who, Filter f, const float* color, const float* variance, bool is_irradiance, unsigned scales);
     // set_aov_shading / set_demodulate
     bool aov_shading_ = false, demodulate_ = false;
     float albedo_floor_ = 0.0f;

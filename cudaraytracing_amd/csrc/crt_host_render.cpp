@@ -20,6 +20,12 @@ void save_rgb8(const char* who, const char* save_path, const Scene& scene, const
 {
     check(crt_write_png(save_path, scene.get_width(), scene.get_height(), rgb.data()), who);
 }
+// a filter's settings at a frame size
+template <class Params> Params sized(Params p, uint32_t w, uint32_t h)
+{
+    p.width = w; p.height = h;
+    return p;
+}
 // one frame of a temporal sequence as the library takes it, and the buffers of the history it makes (Render::temporal_frame)
 struct TemporalStep {
     crt_temporal_params p;
@@ -233,25 +239,6 @@ void Render::run_aov_specular(const float eye_pos[3], const float inv_view_mat[9
     if (as_albedo_guide) albedo_buffer_ = guide_albedo_buffer_;
 }
 
-void Render::run_denoise(const crt_denoise_params& prm)
-{
-    one_device("Render::run_denoise", "the denoiser");
-    const size_t n = scene_->get_pixels();
-    need_guides("Render::run_denoise");
-    crt_denoise_params p = prm;
-    p.width = scene_->get_width(); p.height = scene_->get_height();
-    crt_denoise_inputs in{};
-    in.color = mean_buffer_.data(); in.albedo = albedo_buffer_.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    std::vector<float> irradiance, none;
-    if (demodulate_) {
-        demodulate_of("Render::run_denoise", mean_buffer_.data(), nullptr, irradiance, none);
-        in.color = irradiance.data();
-    }
-    check(crt_denoise(device_, &p, &in, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(), &denoise_info_), "Render::run_denoise");
-    if (demodulate_) modulate_of("Render::run_denoise", denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
-}
-
 const float* Render::variance()
 {
     one_device("Render::variance", "the variance buffer");
@@ -263,15 +250,49 @@ const float* Render::variance()
     return variance_buffer_.data();
 }
 
-// `filter` once per scale of a Laplacian pyramid of `scales` scales over the planes `in` of a w x h frame, from the coarsest scale up
-// (crt_pyramid_down, crt_pyramid_merge: the chain of denoise_multiscale in api.py); scales 1: the one call.  filter(w, h, planes, out_mean,
-// out_rgb) is the single-scale call with its settings at that size: it returns its status and leaves its timer in denoise_info_, which
-// holds the sum of every call's timer and of the filter's passes afterwards.
-void Render::filter_scales(const char* who, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean, unsigned char* out_rgb,
-                           const ScaleFilter& filter)
+Render::Filter Render::default_filter(int kind)
+{
+    Filter f{kind};
+    if (kind == SELECT_VAR) crt_denoise_var_defaults(&f.dn); else crt_denoise_defaults(&f.dn);
+    crt_denoise_nlm_defaults(&f.nlm); crt_denoise_regress_defaults(&f.reg);
+    return f;
+}
+
+// The library call of `f` on the planes `l` of a w x h frame, with f's settings at that size: the one place that knows how the four
+// calls differ.  The caller's pointers go to the library as they are.  weights: the image the regression filter takes its weights
+// from, with l.variance as its variance (nullptr: the frame's own).  Returns the status.  info may be null; the regression filter has
+// an info of its own, which with an `info` goes to regress_info_ and gives `info` its timer and its one pass.
+int Render::apply_filter(const Filter& f, uint32_t w, uint32_t h, const crt_pyramid_planes& l, const float* weights, float* out_mean, unsigned char* out_rgb,
+                         crt_denoise_info* info)
+{
+    if (f.kind == SELECT_ATROUS) {
+        const crt_denoise_params p = sized(f.dn, w, h);
+        const crt_denoise_inputs in{l.color, l.albedo, l.normal, l.depth};
+        return crt_denoise(device_, &p, &in, out_mean, out_rgb, info);
+    }
+    if (f.kind == SELECT_REG) {
+        const crt_regress_params p = sized(f.reg, w, h);
+        const crt_regress_inputs in{l.color, l.variance, weights, weights ? l.variance : nullptr, l.albedo, l.normal, l.depth};
+        const int rc = crt_denoise_regress(device_, &p, &in, out_mean, out_rgb, info ? &regress_info_ : nullptr);
+        if (info) { info->total_ms = regress_info_.total_ms; info->passes = 1; }
+        return rc;
+    }
+    const crt_denoise_var_inputs in{l.color, l.variance, l.albedo, l.normal, l.depth};
+    if (f.kind == SELECT_NLM) {
+        const crt_nlm_params p = sized(f.nlm, w, h);
+        return crt_denoise_nlm(device_, &p, &in, out_mean, out_rgb, nullptr, info);
+    }
+    const crt_denoise_params p = sized(f.dn, w, h);
+    return crt_denoise_var(device_, &p, &in, out_mean, out_rgb, nullptr, info);
+}
+
+// `f` once per scale of a Laplacian pyramid of `scales` scales over the planes `in` of a w x h frame, from the coarsest scale up
+// (crt_pyramid_down, crt_pyramid_merge: the chain of denoise_multiscale in api.py); scales 1: the one call.  denoise_info_ holds the sum
+// of every call's timer and of the filter's passes afterwards, regress_info_ the finest scale's call, which is the last.
+void Render::filter_scales(const char* who, const Filter& f, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean, unsigned char* out_rgb)
 {
     if (scales <= 1) {
-        check(filter(w, h, in, out_mean, out_rgb), who);
+        check(apply_filter(f, w, h, in, nullptr, out_mean, out_rgb, &denoise_info_), who);
         return;
     }
     struct Level {
@@ -285,19 +306,19 @@ void Render::filter_scales(const char* who, unsigned scales, uint32_t w, uint32_
     uint32_t passes = 0;
     crt_pyramid_info pinfo{};
     for (unsigned k = 1; k < scales; k++) {
-        const Level& f = levels[k - 1];
+        const Level& fine = levels[k - 1];
         Level& c = levels[k];
-        crt_pyramid_params pp{f.w, f.h, (f.w + 1) / 2, (f.h + 1) / 2};
+        crt_pyramid_params pp{fine.w, fine.h, (fine.w + 1) / 2, (fine.h + 1) / 2};
         c.w = pp.low_width; c.h = pp.low_height;
         const size_t n = (size_t)c.w * c.h;
         c.color.assign(3 * n, 0.0f);
-        if (f.planes.variance) c.variance.assign(3 * n, 0.0f);
-        if (f.planes.albedo) c.albedo.assign(3 * n, 0.0f);
-        if (f.planes.normal) c.normal.assign(3 * n, 0.0f);
-        if (f.planes.depth) c.depth.assign(n, 0.0f);
+        if (fine.planes.variance) c.variance.assign(3 * n, 0.0f);
+        if (fine.planes.albedo) c.albedo.assign(3 * n, 0.0f);
+        if (fine.planes.normal) c.normal.assign(3 * n, 0.0f);
+        if (fine.planes.depth) c.depth.assign(n, 0.0f);
         auto ptr = [](std::vector<float>& v) { return v.empty() ? nullptr : v.data(); };
         crt_pyramid_out_planes out{ptr(c.color), ptr(c.variance), ptr(c.albedo), ptr(c.normal), ptr(c.depth)};
-        check(crt_pyramid_down(device_, &pp, &f.planes, &out, &pinfo), who);
+        check(crt_pyramid_down(device_, &pp, &fine.planes, &out, &pinfo), who);
         total_ms += pinfo.total_ms;
         c.planes = crt_pyramid_planes{out.color, out.variance, out.albedo, out.normal, out.depth};
     }
@@ -307,7 +328,7 @@ void Render::filter_scales(const char* who, unsigned scales, uint32_t w, uint32_
         const size_t n = (size_t)l.w * l.h;
         std::vector<float>& dst = k + 1 == scales ? result : filtered;
         dst.assign(3 * n, 0.0f);
-        check(filter(l.w, l.h, l.planes, dst.data(), nullptr), who);
+        check(apply_filter(f, l.w, l.h, l.planes, nullptr, dst.data(), nullptr, &denoise_info_), who);
         total_ms += denoise_info_.total_ms; passes += denoise_info_.passes;
         if (k + 1 == scales) continue;
         crt_pyramid_params pp{l.w, l.h, (l.w + 1) / 2, (l.h + 1) / 2};
@@ -322,78 +343,53 @@ void Render::filter_scales(const char* who, unsigned scales, uint32_t w, uint32_
     denoise_info_.total_ms = total_ms; denoise_info_.passes = passes;
 }
 
-// crt_denoise_var of a colour and its variance with the guides of the last run_aov, at `scales` scales
-// (set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already -- and modulated after)
-void Render::denoise_var_of(const char* who, const float* color, const float* variance, const crt_denoise_params& prm, bool is_irradiance,
-                            const crt_nlm_params* nlm, unsigned scales)
+// `f` of a colour and its variance (nullptr: a-trous takes none) with the guides of the last run_aov, at `scales` scales, into the
+// denoised buffers.  set_demodulate: on irradiance -- the colour and variance are demodulated first unless they are irradiance already,
+// the regression filter loses its albedo feature, which irradiance does not follow -- and modulated after: the filter then writes no
+// RGB8, the tone map comes from crt_modulate.
+void Render::denoise_of(const char* who, Filter f, const float* color, const float* variance, bool is_irradiance, unsigned scales)
 {
     const size_t n = scene_->get_pixels();
     std::vector<float> irradiance, irradiance_variance;
     if (demodulate_ && !is_irradiance) {
         demodulate_of(who, color, variance, irradiance, irradiance_variance);
-        color = irradiance.data(); variance = irradiance_variance.data();
+        color = irradiance.data();
+        if (variance) variance = irradiance_variance.data();
     }
+    if (demodulate_ && f.kind == SELECT_REG) f.reg.features &= ~CRT_REGRESS_ALBEDO;
     const crt_pyramid_planes planes{color, variance, albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
     denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    filter_scales(who, scales, scene_->get_width(), scene_->get_height(), planes, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data(),
-                  [&](uint32_t w, uint32_t h, const crt_pyramid_planes& l, float* out_mean, unsigned char* out_rgb) {
-                      crt_denoise_var_inputs in{};
-                      in.color = l.color; in.variance = l.variance; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
-                      if (nlm) {
-                          crt_nlm_params q = *nlm;
-                          q.width = w; q.height = h;
-                          return crt_denoise_nlm(device_, &q, &in, out_mean, out_rgb, nullptr, &denoise_info_);
-                      }
-                      crt_denoise_params p = prm;
-                      p.width = w; p.height = h;
-                      return crt_denoise_var(device_, &p, &in, out_mean, out_rgb, nullptr, &denoise_info_);
-                  });
+    filter_scales(who, f, scales, scene_->get_width(), scene_->get_height(), planes, denoised_mean_buffer_.data(), demodulate_ ? nullptr : denoised_buffer_.data());
     if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
+}
+
+// the frame of the last run_view through one filter.  (run_denoise has one scale whatever set_denoise_scales says: no variance to reduce)
+void Render::run_denoise(const crt_denoise_params& prm)
+{
+    one_device("Render::run_denoise", "the denoiser");
+    need_guides("Render::run_denoise");
+    denoise_of("Render::run_denoise", Filter{SELECT_ATROUS, prm}, mean_buffer_.data(), nullptr, false, 1);
 }
 
 void Render::run_denoise_var(const crt_denoise_params& prm)
 {
     one_device("Render::run_denoise_var", "the denoiser");
     need_guides("Render::run_denoise_var");
-    denoise_var_of("Render::run_denoise_var", mean_buffer_.data(), variance(), prm, false, nullptr, denoise_scales_);
+    denoise_of("Render::run_denoise_var", Filter{SELECT_VAR, prm}, mean_buffer_.data(), variance(), false, denoise_scales_);
 }
 
 void Render::run_denoise_nlm(const crt_nlm_params& prm)
 {
     one_device("Render::run_denoise_nlm", "the denoiser");
     need_guides("Render::run_denoise_nlm");
-    denoise_var_of("Render::run_denoise_nlm", mean_buffer_.data(), variance(), crt_denoise_params{}, false, &prm, denoise_scales_);
+    denoise_of("Render::run_denoise_nlm", Filter{SELECT_NLM, {}, prm}, mean_buffer_.data(), variance(), false, denoise_scales_);
 }
 
 void Render::run_denoise_regress(const crt_regress_params& prm)
 {
-    const char* who = "Render::run_denoise_regress";
-    one_device(who, "the denoiser");
-    need_guides(who);
-    const size_t n = scene_->get_pixels();
-    crt_regress_params p = prm;
-    const float* color = mean_buffer_.data();
-    const float* var = variance();
-    std::vector<float> irradiance, irradiance_variance;
-    if (demodulate_) {
-        demodulate_of(who, color, var, irradiance, irradiance_variance);
-        color = irradiance.data(); var = irradiance_variance.data();
-        p.features &= ~CRT_REGRESS_ALBEDO; // (irradiance does not follow the albedo)
-    }
-    const crt_pyramid_planes planes{color, var, albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
-    denoised_buffer_.assign(3 * n, 0); denoised_mean_buffer_.assign(3 * n, 0.0f);
-    filter_scales(who, denoise_scales_, scene_->get_width(), scene_->get_height(), planes, denoised_mean_buffer_.data(),
-                  demodulate_ ? nullptr : denoised_buffer_.data(),
-                  [&](uint32_t w, uint32_t h, const crt_pyramid_planes& l, float* out_mean, unsigned char* out_rgb) {
-                      crt_regress_params q = p;
-                      q.width = w; q.height = h;
-                      crt_regress_inputs in{};
-                      in.color = l.color; in.variance = l.variance; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
-                      const int rc = crt_denoise_regress(device_, &q, &in, out_mean, out_rgb, &regress_info_); // (the finest scale's call is the last)
-                      denoise_info_.total_ms = regress_info_.total_ms; denoise_info_.passes = 1;
-                      return rc;
-                  });
-    if (demodulate_) modulate_of(who, denoised_mean_buffer_.data(), denoised_mean_buffer_.data(), denoised_buffer_.data());
+    one_device("Render::run_denoise_regress", "the denoiser");
+    need_guides("Render::run_denoise_regress");
+    denoise_of("Render::run_denoise_regress", Filter{SELECT_REG, {}, {}, prm}, mean_buffer_.data(), variance(), false, denoise_scales_);
 }
 
 void Render::run_denoise_select(const std::vector<int>& candidates, const crt_filter_select_params& prm)
@@ -409,36 +405,6 @@ void Render::run_denoise_select(const std::vector<int>& candidates, const crt_fi
     const float* var = variance();
     for (size_t i = 0; i < 3 * n; i++) half_variance[i] = 2.0f * var[i];
     const uint32_t w = scene_->get_width(), h = scene_->get_height();
-    // one candidate on one half frame, with its own defaults and the guides of the last run_aov
-    // (other: the other half frame, where the regression filter takes its weights)
-    auto filter = [&](int candidate, const float* image, const float* other, float* out) {
-        crt_denoise_var_inputs vin{};
-        vin.color = image; vin.variance = half_variance.data();
-        vin.albedo = albedo_buffer_.data(); vin.normal = normal_buffer_.data(); vin.depth = depth_buffer_.data();
-        if (candidate == SELECT_REG) {
-            crt_regress_params p;
-            crt_denoise_regress_defaults(&p);
-            p.width = w; p.height = h;
-            crt_regress_inputs rin{};
-            rin.color = image; rin.variance = vin.variance; rin.weight_color = other; rin.weight_variance = vin.variance;
-            rin.albedo = vin.albedo; rin.normal = vin.normal; rin.depth = vin.depth;
-            return crt_denoise_regress(device_, &p, &rin, out, nullptr, nullptr);
-        }
-        if (candidate == SELECT_NLM) {
-            crt_nlm_params p;
-            crt_denoise_nlm_defaults(&p);
-            p.width = w; p.height = h;
-            return crt_denoise_nlm(device_, &p, &vin, out, nullptr, nullptr, nullptr);
-        }
-        if (candidate != SELECT_ATROUS && candidate != SELECT_VAR) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": unknown candidate");
-        crt_denoise_params p;
-        if (candidate == SELECT_VAR) crt_denoise_var_defaults(&p); else crt_denoise_defaults(&p);
-        p.width = w; p.height = h;
-        if (candidate == SELECT_VAR) return crt_denoise_var(device_, &p, &vin, out, nullptr, nullptr, nullptr);
-        crt_denoise_inputs din{};
-        din.color = vin.color; din.albedo = vin.albedo; din.normal = vin.normal; din.depth = vin.depth;
-        return crt_denoise(device_, &p, &din, out, nullptr, nullptr);
-    };
     std::vector<std::vector<float>> filtered[2];
     crt_filter_select_inputs in{};
     in.half_a = half[0].data(); in.half_b = half[1].data(); in.half_variance = half_variance.data();
@@ -446,9 +412,11 @@ void Render::run_denoise_select(const std::vector<int>& candidates, const crt_fi
         filtered[side].resize(candidates.size());
         for (size_t k = 0; k < candidates.size(); k++) {
             const float* image = half[side].data();
-            if (candidates[k] != SELECT_NONE) {
+            if (candidates[k] != SELECT_NONE) { // the filter with its own defaults and the guides of the last run_aov; weights from the other half
+                if (candidates[k] < SELECT_ATROUS || candidates[k] > SELECT_REG) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + ": unknown candidate");
                 filtered[side][k].assign(3 * n, 0.0f);
-                check(filter(candidates[k], image, half[1 - side].data(), filtered[side][k].data()), who);
+                const crt_pyramid_planes planes{image, half_variance.data(), albedo_buffer_.data(), normal_buffer_.data(), depth_buffer_.data()};
+                check(apply_filter(default_filter(candidates[k]), w, h, planes, half[1 - side].data(), filtered[side][k].data(), nullptr, nullptr), who);
                 image = filtered[side][k].data();
             }
             (side == 0 ? in.filtered_a : in.filtered_b)[k] = image;
@@ -551,7 +519,7 @@ void Render::run_denoise_temporal(const crt_denoise_params& prm)
     if (!temporal_valid_ || temporal_color_.size() != (size_t)3 * scene_->get_pixels())
         throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal needs run_temporal of this frame size first");
     if (temporal_demodulated_ != demodulate_) throw Error(CRT_ERR_INVALID_ARG, "Render::run_denoise_temporal: set_demodulate changed since run_temporal");
-    denoise_var_of("Render::run_denoise_temporal", temporal_color_.data(), temporal_variance_.data(), prm, temporal_demodulated_);
+    denoise_of("Render::run_denoise_temporal", Filter{SELECT_VAR, prm}, temporal_color_.data(), temporal_variance_.data(), temporal_demodulated_, 1);
 }
 
 void Render::run_view_upsampled(const float eye_pos[3], const float inv_view_mat[9], float fovY, unsigned factor, const crt_upsample_params& prm, unsigned guide_spp)

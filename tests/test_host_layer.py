@@ -330,7 +330,10 @@ def test_render_class_map_frames_refusals_and_temporal_history(tmp_path):
     """tools/render_host_check.cpp: what crt_cli never asks of crt::Render.  run_view_map against crt_render_map, the text and status
     of every refusal the class makes itself (several devices, after free(), a missing earlier step, a bad factor, an unwritable path),
     and two frames each of run_temporal, run_temporal with a clamp, run_temporal_moments and run_temporal again against the library
-    calls they are made of -- bit for bit, with no history carried from one kind to the other."""
+    calls they are made of -- bit for bit, with no history carried from one kind to the other.  And the filters' dispatch at 30 x 22:
+    run_denoise, _var, _nlm and _regress with settings of their own, set_demodulate off and on, 1 and 3 scales, and run_denoise_select
+    over all five candidates, each against crt_demodulate, crt_pyramid_down, the filter, crt_pyramid_merge and crt_modulate called by
+    hand; the passes in last_denoise_info(), which run_denoise_select leaves alone."""
     from cudaraytracing_amd import build as b
     exe = b.build_render_check()
     r = subprocess.run([exe, util.SCENES["cornell-box"], util.ROOT, str(tmp_path / "no_such_directory")], capture_output=True, text=True, timeout=120)

@@ -1,7 +1,8 @@
 // tools/render_host_check.cpp -- crt::Render (cudaraytracing_amd/csrc/crt_host.hpp) where crt_cli does not reach it: run_view_map, the
-// refusals of the class itself, and the history run_temporal / run_temporal_moments keep between calls.  Needs a GPU.  cornell-box at
-// 32 x 24, spp 4, seed 0; every result is compared bit for bit with the same library calls made directly on a second scene handle, every
-// refusal with the text and status written out below.  Exits 1 at the first mismatch with one line that names the comparison.
+// refusals of the class itself, the history run_temporal / run_temporal_moments keep between calls, and what run_denoise* and
+// run_denoise_select make of their filter, set_demodulate and set_denoise_scales.  Needs a GPU.  cornell-box at 32 x 24 (the filters: 30 x 22,
+// whose halves are odd), spp 4, seed 0; every result is compared bit for bit with the same library calls made directly on a second scene
+// handle, every refusal with the text and status written out below.  Exits 1 at the first mismatch with one line that names the comparison.
 //
 //   cudaraytracing_amd/build.py builds it beside crt_cli, as lib/render_host_check
 //   render_host_check scenes/cornell-box/config.json <base dir of the OBJ paths> <a directory that does not exist>
@@ -99,12 +100,13 @@ std::vector<Call> single_device_calls(crt::Render& r, const View& v, const uint3
     static crt_adaptive_params ad;
     static crt_denoise_params dn, dv;
     static crt_nlm_params nlm;
+    static crt_regress_params reg;
     static crt_filter_select_params sel;
     static crt_temporal_params tp;
     static crt_variance_estimate_params est;
     static crt_upsample_params up;
     crt_adaptive_defaults(&ad); crt_denoise_defaults(&dn); crt_denoise_var_defaults(&dv); crt_denoise_nlm_defaults(&nlm);
-    crt_filter_select_defaults(&sel); crt_temporal_defaults(&tp); crt_variance_estimate_defaults(&est); crt_upsample_defaults(&up);
+    crt_denoise_regress_defaults(&reg); crt_filter_select_defaults(&sel); crt_temporal_defaults(&tp); crt_variance_estimate_defaults(&est); crt_upsample_defaults(&up);
     crt::Render* q = &r;
     return {
         {"Render::run_view_adaptive", ": a single-device interface", [=] { q->run_view_adaptive(v.eye, v.inv_view, v.fov_y, ad); }},
@@ -116,6 +118,7 @@ std::vector<Call> single_device_calls(crt::Render& r, const View& v, const uint3
         {"Render::variance", ": the variance buffer is a single-device interface", [=] { q->variance(); }},
         {"Render::run_denoise_var", ": the denoiser is a single-device interface", [=] { q->run_denoise_var(dv); }},
         {"Render::run_denoise_nlm", ": the denoiser is a single-device interface", [=] { q->run_denoise_nlm(nlm); }},
+        {"Render::run_denoise_regress", ": the denoiser is a single-device interface", [=] { q->run_denoise_regress(reg); }},
         {"Render::run_denoise_select", ": filter selection is a single-device interface", [=] { q->run_denoise_select({crt::Render::SELECT_VAR}, sel); }},
         {"Render::run_temporal", ": temporal accumulation is a single-device interface", [=] { q->run_temporal(v.eye, v.inv_view, v.fov_y, tp); }},
         {"Render::run_temporal_moments", ": temporal accumulation is a single-device interface", [=] { q->run_temporal_moments(v.eye, v.inv_view, v.fov_y, tp, nullptr, est); }},
@@ -129,11 +132,12 @@ void check_refusals(crt::Scene& scene, const crt_task& task, const View& v, cons
     const std::string first = " needs run_view and run_aov of this frame size first", bad_png = no_such_dir + "/x.png", io = "cannot open for writing: " + bad_png;
     crt_denoise_params dn, dv;
     crt_nlm_params nlm;
+    crt_regress_params reg;
     crt_filter_select_params sel;
     crt_temporal_params tp;
     crt_upsample_params up;
-    crt_denoise_defaults(&dn); crt_denoise_var_defaults(&dv); crt_denoise_nlm_defaults(&nlm); crt_filter_select_defaults(&sel); crt_temporal_defaults(&tp);
-    crt_upsample_defaults(&up);
+    crt_denoise_defaults(&dn); crt_denoise_var_defaults(&dv); crt_denoise_nlm_defaults(&nlm); crt_denoise_regress_defaults(&reg); crt_filter_select_defaults(&sel);
+    crt_temporal_defaults(&tp); crt_upsample_defaults(&up);
     {   // two ranks on one device: none of these methods has a form for it.  (No flag is set, the factor is 1: the refusal that
         // names several devices comes before the method's other ones.)
         crt::Render many(&scene, S, task.p_rr, task.light_sample_n, std::vector<int>{0, 0}, CRT_GATHER_COPY);
@@ -149,6 +153,7 @@ void check_refusals(crt::Scene& scene, const crt_task& task, const View& v, cons
     refused("run_denoise before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise" + first, [&] { r.run_denoise(dn); });
     refused("run_denoise_var before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_var" + first, [&] { r.run_denoise_var(dv); });
     refused("run_denoise_nlm before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_nlm" + first, [&] { r.run_denoise_nlm(nlm); });
+    refused("run_denoise_regress before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_regress" + first, [&] { r.run_denoise_regress(reg); });
     refused("run_denoise_select before run_aov", CRT_ERR_INVALID_ARG, "Render::run_denoise_select" + first, [&] { r.run_denoise_select({crt::Render::SELECT_VAR}, sel); });
     refused("run_denoise_select without candidates", CRT_ERR_INVALID_ARG, "Render::run_denoise_select needs 1 .. 4 candidates", [&] { r.run_denoise_select({}, sel); });
     r.set_demodulate(true);
@@ -294,6 +299,195 @@ void check_temporal(crt::Render& r, crt_scene* direct, const crt_task& task)
     }
 }
 
+// ---- 4. run_denoise* and run_denoise_select against the chain of library calls they are made of ----
+const uint32_t FW = 30, FH = 22; // the coarser scales are 15 x 11 and 8 x 6: halves that are odd
+const size_t FN = (size_t)FW * FH;
+enum Filter { ATROUS, VAR, NLM, REG };
+struct Settings {
+    crt_denoise_params atrous, var;
+    crt_nlm_params nlm;
+    crt_regress_params reg;
+};
+Settings default_settings()
+{
+    Settings s;
+    crt_denoise_defaults(&s.atrous); crt_denoise_var_defaults(&s.var); crt_denoise_nlm_defaults(&s.nlm); crt_denoise_regress_defaults(&s.reg);
+    return s;
+}
+
+// one call of filter f on the planes of a w x h frame; weight: the image the regression filter takes its weights from (nullptr: the
+// frame itself).  Returns the passes the call made.
+uint32_t direct_filter(Filter f, const Settings& s, uint32_t w, uint32_t h, const crt_pyramid_planes& l, const float* weight, float* out_mean, uint8_t* out_rgb)
+{
+    crt_denoise_info info{};
+    crt_denoise_var_inputs vin{};
+    vin.color = l.color; vin.variance = l.variance; vin.albedo = l.albedo; vin.normal = l.normal; vin.depth = l.depth;
+    if (f == ATROUS) {
+        crt_denoise_params p = s.atrous;
+        p.width = w; p.height = h;
+        crt_denoise_inputs in{};
+        in.color = l.color; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
+        ok(crt_denoise(0, &p, &in, out_mean, out_rgb, &info), "crt_denoise");
+    } else if (f == VAR) {
+        crt_denoise_params p = s.var;
+        p.width = w; p.height = h;
+        ok(crt_denoise_var(0, &p, &vin, out_mean, out_rgb, nullptr, &info), "crt_denoise_var");
+    } else if (f == NLM) {
+        crt_nlm_params p = s.nlm;
+        p.width = w; p.height = h;
+        ok(crt_denoise_nlm(0, &p, &vin, out_mean, out_rgb, nullptr, &info), "crt_denoise_nlm");
+    } else {
+        crt_regress_params p = s.reg;
+        p.width = w; p.height = h;
+        crt_regress_inputs in{};
+        in.color = l.color; in.variance = l.variance; in.albedo = l.albedo; in.normal = l.normal; in.depth = l.depth;
+        in.weight_color = weight; in.weight_variance = weight ? l.variance : nullptr;
+        ok(crt_denoise_regress(0, &p, &in, out_mean, out_rgb, nullptr), "crt_denoise_regress");
+        info.passes = 1;
+    }
+    return info.passes;
+}
+
+// the pyramid, written from the top down: the frame at `scales` scales is the filtered frame merged with the result of the halved
+// planes at scales - 1.  Returns the passes of all its filter calls.
+uint32_t direct_scales(Filter f, const Settings& s, unsigned scales, uint32_t w, uint32_t h, const crt_pyramid_planes& in, float* out_mean, uint8_t* out_rgb)
+{
+    if (scales == 1) return direct_filter(f, s, w, h, in, nullptr, out_mean, out_rgb);
+    const crt_pyramid_params pp{w, h, (w + 1) / 2, (h + 1) / 2};
+    const size_t n = (size_t)w * h, nl = (size_t)pp.low_width * pp.low_height;
+    std::vector<float> color(3 * nl), variance(in.variance ? 3 * nl : 0), albedo(3 * nl), normal(3 * nl), depth(nl), coarse(3 * nl), fine(3 * n);
+    const crt_pyramid_out_planes out{color.data(), in.variance ? variance.data() : nullptr, albedo.data(), normal.data(), depth.data()};
+    ok(crt_pyramid_down(0, &pp, &in, &out, nullptr), "crt_pyramid_down");
+    const crt_pyramid_planes low{out.color, out.variance, out.albedo, out.normal, out.depth};
+    uint32_t passes = direct_scales(f, s, scales - 1, pp.low_width, pp.low_height, low, coarse.data(), nullptr);
+    passes += direct_filter(f, s, w, h, in, nullptr, fine.data(), nullptr);
+    ok(crt_pyramid_merge(0, &pp, fine.data(), coarse.data(), out_mean, out_rgb, nullptr), "crt_pyramid_merge");
+    return passes;
+}
+
+// what run_denoise* of filter f makes of the frame and the buffers `r` holds.  drop_albedo: the regression filter on irradiance runs
+// without its albedo feature.
+uint32_t direct_denoise(crt::Render& r, Filter f, Settings s, bool demodulate, float albedo_floor, unsigned scales, bool drop_albedo, std::vector<float>& mean,
+                        std::vector<uint8_t>& rgb)
+{
+    const float* color = r.get_mean_buffer();
+    const float* var = f == ATROUS ? nullptr : r.variance();
+    crt_modulate_params m;
+    crt_modulate_defaults(&m);
+    m.width = FW; m.height = FH; m.albedo_floor = albedo_floor;
+    std::vector<float> irradiance(3 * FN), irradiance_variance(3 * FN);
+    if (demodulate) {
+        ok(crt_demodulate(0, &m, color, r.get_diffuse_albedo_buffer(), r.get_emission_buffer(), var, irradiance.data(), var ? irradiance_variance.data() : nullptr, nullptr),
+           "crt_demodulate");
+        color = irradiance.data();
+        if (var) var = irradiance_variance.data();
+        if (drop_albedo) s.reg.features &= ~CRT_REGRESS_ALBEDO;
+    }
+    const crt_pyramid_planes planes{color, var, r.get_albedo_buffer(), r.get_normal_buffer(), r.get_depth_buffer()};
+    mean.assign(3 * FN, 0.0f); rgb.assign(3 * FN, 0);
+    const uint32_t passes = direct_scales(f, s, f == ATROUS ? 1 : scales, FW, FH, planes, mean.data(), demodulate ? nullptr : rgb.data()); // (a-trous: one scale always)
+    if (demodulate) {
+        std::vector<float> radiance(3 * FN);
+        ok(crt_modulate(0, &m, mean.data(), r.get_diffuse_albedo_buffer(), r.get_emission_buffer(), radiance.data(), rgb.data(), nullptr), "crt_modulate");
+        mean.swap(radiance);
+    }
+    return passes;
+}
+
+// `scene` is FW x FH, `direct` a handle of it
+void check_filters(crt::Scene& scene, crt_scene* direct, const crt_task& task, const View& v)
+{
+    crt::Render r(&scene, S, task.p_rr, task.light_sample_n, 0);
+    r.set_flags(CRT_FLAG_VARIANCE);
+    r.set_aov_shading(true);
+    r.run_view(v.eye, v.inv_view, v.fov_y);
+    r.run_aov(v.eye, v.inv_view, v.fov_y);
+    Settings s = default_settings(); // and none of them left as it is where a method could lose it
+    s.atrous.iterations = 2; s.atrous.sigma_color = 3.0f; s.atrous.sigma_normal = 0.4f; s.atrous.sigma_albedo = 0.2f; s.atrous.sigma_depth = 0.1f;
+    s.var.iterations = 4; s.var.sigma_color = 5.0f; s.var.sigma_normal = 0.3f; s.var.sigma_albedo = 0.15f; s.var.sigma_depth = 0.08f;
+    s.nlm.radius = 3; s.nlm.patch = 2; s.nlm.k = 0.9f; s.nlm.alpha = 0.5f; s.nlm.sigma_normal = 0.4f; s.nlm.sigma_albedo = 0.2f; s.nlm.sigma_depth = 0.1f;
+    s.reg.radius = 4; s.reg.patch = 0; s.reg.k = 0.8f; s.reg.alpha = 0.5f; s.reg.sigma_normal = 0.4f; s.reg.sigma_albedo = 0.2f; s.reg.sigma_depth = 0.1f;
+    s.reg.sigma_position = 1.5f; s.reg.ridge = 0.1f;
+    const char* const names[] = {"run_denoise", "run_denoise_var", "run_denoise_nlm", "run_denoise_regress"};
+    const float albedo_floor = 0.02f;
+    std::vector<float> mean, one_scale_mean;
+    std::vector<uint8_t> rgb, one_scale_rgb;
+    for (int f = ATROUS; f <= REG; f++)
+        for (int demodulate = 0; demodulate < 2; demodulate++)
+            for (unsigned scales = 1; scales <= 3; scales += 2) {
+                r.set_demodulate(demodulate != 0, albedo_floor);
+                r.set_denoise_scales(scales);
+                if (f == ATROUS) r.run_denoise(s.atrous); else if (f == VAR) r.run_denoise_var(s.var); else if (f == NLM) r.run_denoise_nlm(s.nlm); else r.run_denoise_regress(s.reg);
+                const std::string what = std::string(names[f]) + (demodulate ? " with set_demodulate" : "") + " at " + std::to_string(scales) + " scales: ";
+                const uint32_t passes = direct_denoise(r, (Filter)f, s, demodulate != 0, albedo_floor, scales, true, mean, rgb);
+                same(what + "mean", r.get_denoised_mean_buffer(), mean.data(), 3 * FN);
+                same(what + "RGB8", r.get_denoised_buffer(), (const unsigned char*)rgb.data(), 3 * FN);
+                if (r.last_denoise_info().passes != passes)
+                    fail(what + std::to_string(r.last_denoise_info().passes) + " passes in last_denoise_info, " + std::to_string(passes) + " in the direct calls");
+                if (f == ATROUS && scales == 1) { one_scale_mean = mean; one_scale_rgb = rgb; }
+                if (f == ATROUS && scales == 3) { // (no variance to reduce: run_denoise has one scale whatever set_denoise_scales says)
+                    same(what + "mean against one scale", r.get_denoised_mean_buffer(), one_scale_mean.data(), 3 * FN);
+                    same(what + "RGB8 against one scale", r.get_denoised_buffer(), (const unsigned char*)one_scale_rgb.data(), 3 * FN);
+                }
+                if (f == REG && demodulate) { // the call that matched is the one without the albedo feature: with it the result is another
+                    direct_denoise(r, REG, s, true, albedo_floor, scales, false, mean, rgb);
+                    if (std::memcmp(r.get_denoised_mean_buffer(), mean.data(), 3 * FN * sizeof(float)) == 0) fail(what + "the albedo feature makes no difference to the direct call");
+                }
+            }
+    // run_denoise_select: every candidate with its own defaults on either half frame, at one scale, and no word in last_denoise_info
+    // or last_regress_info
+    r.set_demodulate(false);
+    r.set_flags(CRT_FLAG_HALF_BUFFERS);
+    r.run_view(v.eye, v.inv_view, v.fov_y);
+    crt_camera cam;
+    crt_params p;
+    direct_args(task, v, 0, CRT_FLAG_HALF_BUFFERS, cam, p);
+    p.width = FW; p.height = FH;
+    std::vector<uint8_t> frame(3 * FN);
+    std::vector<float> frame_mean(3 * FN), half[2] = {std::vector<float>(3 * FN), std::vector<float>(3 * FN)}, half_variance(3 * FN);
+    crt_stats stats;
+    ok(crt_render(direct, &cam, &p, frame.data(), frame_mean.data(), &stats), "crt_render");
+    same("the frame with half buffers", r.get_mean_buffer(), frame_mean.data(), 3 * FN);
+    ok(crt_half_buffers(direct, half[0].data(), half[1].data(), nullptr), "crt_half_buffers");
+    ok(crt_variance(direct, half_variance.data(), nullptr), "crt_variance");
+    for (float& x : half_variance) x = 2.0f * x;
+    crt_filter_select_params sel;
+    crt_filter_select_defaults(&sel);
+    sel.error_radius = 2; sel.blend_radius = 2;
+    const Settings defaults = default_settings();
+    const std::vector<int> lists[] = {{crt::Render::SELECT_NONE, crt::Render::SELECT_ATROUS, crt::Render::SELECT_VAR, crt::Render::SELECT_NLM}, {crt::Render::SELECT_REG}};
+    for (const std::vector<int>& candidates : lists) {
+        const std::string what = "run_denoise_select of " + std::to_string(candidates.size()) + (candidates.size() == 1 ? " candidate: " : " candidates: ");
+        const crt_denoise_info denoise_before = r.last_denoise_info();
+        const crt_regress_info regress_before = r.last_regress_info();
+        r.run_denoise_select(candidates, sel);
+        if (std::memcmp(&denoise_before, &r.last_denoise_info(), sizeof(denoise_before)) != 0) fail(what + "last_denoise_info changed");
+        if (regress_before.fallback_pixels != r.last_regress_info().fallback_pixels || std::memcmp(&regress_before.total_ms, &r.last_regress_info().total_ms, sizeof(float)) != 0)
+            fail(what + "last_regress_info changed");
+        std::vector<std::vector<float>> filtered[2];
+        crt_filter_select_inputs in{};
+        in.half_a = half[0].data(); in.half_b = half[1].data(); in.half_variance = half_variance.data();
+        for (int side = 0; side < 2; side++) {
+            const crt_pyramid_planes planes{half[side].data(), half_variance.data(), r.get_albedo_buffer(), r.get_normal_buffer(), r.get_depth_buffer()};
+            for (size_t k = 0; k < candidates.size(); k++) {
+                filtered[side].emplace_back(candidates[k] == crt::Render::SELECT_NONE ? half[side] : std::vector<float>(3 * FN));
+                if (candidates[k] != crt::Render::SELECT_NONE) // (SELECT_ATROUS .. SELECT_REG - 1 = ATROUS .. REG)
+                    direct_filter((Filter)(candidates[k] - 1), defaults, FW, FH, planes, half[1 - side].data(), filtered[side][k].data(), nullptr);
+            }
+            for (size_t k = 0; k < candidates.size(); k++) (side == 0 ? in.filtered_a : in.filtered_b)[k] = filtered[side][k].data();
+        }
+        sel.width = FW; sel.height = FH; sel.n_candidates = (uint32_t)candidates.size();
+        std::vector<uint8_t> choice(FN);
+        crt_filter_select_info info{};
+        mean.assign(3 * FN, 0.0f); rgb.assign(3 * FN, 0);
+        ok(crt_filter_select(0, &sel, &in, mean.data(), rgb.data(), choice.data(), nullptr, &info), "crt_filter_select");
+        same(what + "mean", r.get_denoised_mean_buffer(), mean.data(), 3 * FN);
+        same(what + "RGB8", r.get_denoised_buffer(), (const unsigned char*)rgb.data(), 3 * FN);
+        same(what + "choice", r.get_choice_buffer().data(), (const unsigned char*)choice.data(), FN);
+        if (std::memcmp(info.chosen, r.last_select_info().chosen, sizeof(info.chosen)) != 0) fail(what + "last_select_info().chosen differs");
+    }
+}
+
 } // namespace
 
 int main(int argc, char** argv)
@@ -321,6 +515,12 @@ int main(int argc, char** argv)
             check_temporal(r, direct, task);
         }
         check_refusals(scene, task, v, argv[3]);
+        crt_scene_destroy(direct);
+        crt::Scene filter_scene(FW, FH);
+        crt::load_task_scene(task, filter_scene, argv[2], &all_objs);
+        filter_scene.set_BVH(task.bvh_thresh_n);
+        ok(crt_scene_create(&filter_scene.flat(), 0, &direct), "crt_scene_create");
+        check_filters(filter_scene, direct, task, v);
         crt_scene_destroy(direct);
     } catch (const crt::Error& e) {
         fail(std::string("unexpected error: ") + e.what() + " (" + crt_strerror(e.status) + ")");

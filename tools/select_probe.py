@@ -40,6 +40,7 @@ sys.path.insert(0, ROOT)
 import cudaraytracing_amd as crt  # noqa: E402
 from cudaraytracing_amd import _capi as capi  # noqa: E402
 from cudaraytracing_amd import hipmem  # noqa: E402
+from cudaraytracing_amd.api import _select_candidate as candidate  # noqa: E402  (run_view_selected's: name, half, half variance, guides, device)
 
 F = np.float32
 GUIDES = ("albedo", "normal", "depth")
@@ -53,16 +54,6 @@ def emit(out, key, run):
 def scene_view(name, w, h):
     t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
     return t, crt.Scene.from_task(t, w, h), (t.eye_pos, crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up), crt.fov_to_radians(t.fov_y))
-
-
-def candidate(name, half, half_var, guides):
-    if name == "none":
-        return half
-    if name == "atrous":
-        return crt.denoise(half, want_rgb=False, **guides)[1]
-    if name == "var":
-        return crt.denoise_var(half, half_var, want_rgb=False, **guides)[1]
-    return crt.denoise_nlm(half, half_var, want_rgb=False, **guides)[1]
 
 
 def part_time(a, out):
@@ -80,7 +71,7 @@ def part_time(a, out):
         host.update({g: guides[g] for g in GUIDES})
         for side in ("a", "b"):
             for n in names[1:]:
-                host["f%s_%s" % (side, n)] = candidate(n, half[side], hv, guides)
+                host["f%s_%s" % (side, n)] = candidate(n, half[side], hv, guides, 0)
         sel_scratch, dn_scratch = crt.filter_select_scratch_bytes(w, h), crt.denoise_scratch_bytes(w, h)
         dev = hipmem.DeviceBuffers({**host, "mean": w * h * 12, "rgb": w * h * 3, "choice": w * h, "error": w * h * 4,
                                     "sel_scratch": sel_scratch, "dn_scratch": dn_scratch})
@@ -202,8 +193,8 @@ def part_effect(a, out):
             hv = F(2.0) * var
             g = r.run_view_aov(*cam, want=GUIDES)
             row = {"scene": name, "spp": spp, "noisy": mse(rgb), "var": mse(crt.denoise_var(mean, var, **g)[0]), "nlm": mse(crt.denoise_nlm(mean, var, **g)[0])}
-            fa = {n: candidate(n, ha, hv, g) for n in ("none", "var", "nlm")}
-            fb = {n: candidate(n, hb, hv, g) for n in ("none", "var", "nlm")}
+            fa = {n: candidate(n, ha, hv, g, 0) for n in ("none", "var", "nlm")}
+            fb = {n: candidate(n, hb, hv, g, 0) for n in ("none", "var", "nlm")}
             d = crt.filter_select_defaults()
             for names in (("var", "nlm"), ("none", "var", "nlm")):
                 key = "+".join(names)
