@@ -92,6 +92,19 @@ class MultiInfo(C.Structure):
         return d
 
 
+# crt_multi_buffers: the planes of a gathered multi-device frame in the order of their CRT_MULTI_* bits (plane k: bit 1 << k), each with
+# its values per pixel and its element type
+MULTI_BUFFERS = {"rgb": (3, np.uint8), "mean": (3, np.float32), "variance": (3, np.float32), "half_a": (3, np.float32), "half_b": (3, np.float32),
+                 "albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "coverage": (1, np.float32), "tri": (1, np.int32),
+                 "material": (1, np.int32), "emission": (3, np.float32), "diffuse_albedo": (3, np.float32)}
+MULTI_BITS = {name: 1 << k for k, name in enumerate(MULTI_BUFFERS)}
+MULTI_ALL = (1 << len(MULTI_BUFFERS)) - 1
+
+
+class MultiBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in MULTI_BUFFERS]
+
+
 class InfoStruct(C.Structure):
     """An info struct of plain numbers: as_dict() is its fields by name."""
 
@@ -335,7 +348,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
            "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
-           "crt_multi_render", "crt_multi_frame_device", "crt_intersect",
+           "crt_multi_render", "crt_multi_frame_device", "crt_multi_render_buffers", "crt_multi_buffers_device", "crt_multi_untile_time", "crt_intersect",
            "crt_device_math", "crt_device_fn", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
            "crt_host_scene_object", "crt_inverse_view", "crt_task_load", "crt_image_load", "crt_write_png", "crt_write_pfm",
@@ -478,6 +491,10 @@ def lib():
     L.crt_multi_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_void_p, C.c_void_p, C.POINTER(Stats),
                                    C.POINTER(MultiInfo)]
     L.crt_multi_frame_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
+    L.crt_multi_render_buffers.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.c_uint32, C.POINTER(MultiBuffers), C.POINTER(Stats),
+                                           C.POINTER(MultiInfo)]
+    L.crt_multi_buffers_device.argtypes = [C.c_void_p, C.POINTER(MultiBuffers), C.POINTER(C.c_int)]
+    L.crt_multi_untile_time.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
     L.crt_intersect.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
     L.crt_device_math.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.crt_device_fn.argtypes = [C.c_int, C.c_char_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]

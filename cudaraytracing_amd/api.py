@@ -583,9 +583,8 @@ class Render:
         scales with the same settings at each, where the single call stands (so it composes with demodulate and specular_guides).  It
         needs variance_guided, nlm or regress (ValueError); self.denoise_info is then denoise_multiscale's dict."""
         self._handle("run_view_denoised")
-        scales = 1 if scales is None else _check_scales("run_view_denoised", scales)
-        name, settings = _legacy_filter("run_view_denoised", variance_guided, iterations, sigma_color,
-                                        dict(sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth), nlm, regress, scales, demodulate)
+        name, settings, scales = _denoise_request("run_view_denoised", variance_guided, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth,
+                                                  nlm, regress, scales, demodulate)
         with_variance = _FILTERS[name][2]
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=with_variance)
         guides = ("albedo", "normal", "depth")
@@ -598,6 +597,13 @@ class Render:
         if specular_guides:
             self.aov_buffers["albedo"] = self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=max_bounces, want=("guide_albedo",),
                                                                     width=width, height=height)["guide_albedo"]
+        return self._filter_frame(name, settings, scales, demodulate, albedo_floor)
+
+    def _filter_frame(self, name, settings, scales, demodulate, albedo_floor):
+        """What run_view_denoised -- and MultiRender.run_view_gathered_denoised -- does once the frame's buffers exist: filter `name` of
+        _FILTERS with `settings` on self.mean_buffer (and self.variance_buffer) with the guides in self.aov_buffers, at `scales` scales,
+        between demodulate() and modulate() with self.shading_buffers when `demodulate`.  Returns (rgb, mean); sets self.denoise_info."""
+        with_variance = _FILTERS[name][2]
         color, var = self.mean_buffer, self.variance_buffer if with_variance else None
         if demodulate:
             sh = self.shading_buffers
@@ -621,13 +627,17 @@ class Render:
         half variance), so that a half's weights do not follow its own noise.  Returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32).
         Kept: the noisy frame in self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, self.select_buffers (choice (H, W) uint8, error (H, W) float32, half_a, half_b,
         half_variance, filtered_a, filtered_b) and self.select_info (total_ms, chosen)."""
-        names = tuple(candidates)
-        unknown = [n for n in names if n not in _SELECT_CANDIDATES]
-        if unknown or not 1 <= len(names) <= capi.SELECT_MAX_CANDIDATES:
-            raise ValueError("run_view_selected: candidates must be 1 .. %d of %r, got %r" % (capi.SELECT_MAX_CANDIDATES, _SELECT_CANDIDATES, names))
+        names = _select_request("run_view_selected", candidates)
         self._handle("run_view_selected")
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_halves=True)
-        guides = self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        self.aov_buffers = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=("albedo", "normal", "depth"), width=width, height=height)
+        return self._select_frame(names, error_radius, blend_radius)
+
+    def _select_frame(self, names, error_radius, blend_radius):
+        """What run_view_selected -- and MultiRender.run_view_gathered_selected -- does once the halves (self.half_a_buffer,
+        self.half_b_buffer), the frame's variance and the guides in self.aov_buffers exist: the candidates `names` on each half, then
+        filter_select.  Returns (rgb, mean); sets self.select_buffers and self.select_info."""
+        guides = self.aov_buffers
         a, b = self.half_a_buffer, self.half_b_buffer
         half_var = np.float32(2.0) * self.variance_buffer
         fa = [_select_candidate(n, a, half_var, guides, self.device, other=b) for n in names]
@@ -853,6 +863,10 @@ class MultiRender(Render):
         self.stats = None
         self.rank_stats = None
         self.info = None
+        # run_view_gathered and its filtered forms: as Render's
+        self.variance_buffer = self.half_a_buffer = self.half_b_buffer = None
+        self.aov_buffers = self.shading_buffers = None
+        self.denoise_info = self.select_buffers = self.select_info = None
 
     def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, to_host=True, want_variance=False,
                  want_halves=False):
@@ -871,6 +885,13 @@ class MultiRender(Render):
         info = capi.MultiInfo()
         capi.check(capi.lib().crt_multi_render(self._mh, C.byref(cam), C.byref(prm), capi.ptr(rgb), capi.ptr(mean), st,
                                                C.byref(info)), "crt_multi_render")
+        self._rank_totals(st, info)
+        if to_host:
+            self.frame_buffer, self.mean_buffer = rgb, mean
+        return rgb
+
+    def _rank_totals(self, st, info):
+        """self.rank_stats, self.info and self.stats (the ranks' counters summed, their times' maximum) of a frame"""
         self.rank_stats = [s.as_dict() for s in st]
         self.info = info.as_dict()
         tot = dict(self.rank_stats[0])
@@ -880,9 +901,77 @@ class MultiRender(Render):
             for k in ("kernel_ms", "total_ms"):
                 tot[k] = max(tot[k], o[k])
         self.stats = tot
-        if to_host:
-            self.frame_buffer, self.mean_buffer = rgb, mean
-        return rgb
+
+    def run_view_gathered(self, eye_pos, inv_view_mat, fovY, want=("rgb", "mean", "variance", "albedo", "normal", "depth"), width=None, height=None,
+                          to_host=True, stats=False):
+        """The frame of run_view with the buffers the image filters take, gathered from all ranks (crt_multi_render_buffers, contract:
+        include/crt.h).  want: names of capi.MULTI_BUFFERS -- rgb, mean, variance, half_a, half_b, the six of run_view_aov, emission,
+        diffuse_albedo --; every plane has the bits of the single-device call it is named after.  Returns {name: array} ((H, W, 3) or
+        (H, W), of the plane's type) and fills, as Render does, self.frame_buffer, self.mean_buffer, self.variance_buffer,
+        self.half_a_buffer / self.half_b_buffer, self.aov_buffers and self.shading_buffers (dicts of the wanted names; None where nothing
+        of the kind is wanted), self.info, self.rank_stats and self.stats.  to_host=False: nothing is copied and None is returned; the
+        planes stay on rank 0's device (gathered_device()) and the host-side attributes are left as they were."""
+        names = tuple(want)
+        unknown = [n for n in names if n not in capi.MULTI_BUFFERS]
+        if unknown:
+            raise ValueError("run_view_gathered: unknown buffer(s) %r; the names are %r" % (unknown, tuple(capi.MULTI_BUFFERS)))
+        if not self._mh:
+            raise RuntimeError("MultiRender.run_view_gathered after free()")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | self.extra_flags, width=width, height=height)
+        w, h = prm.width, prm.height
+        mask, out, bufs = 0, {}, capi.MultiBuffers()
+        for name in names:
+            mask |= capi.MULTI_BITS[name]
+            if to_host:
+                ch, dt = capi.MULTI_BUFFERS[name]
+                out[name] = np.zeros((h, w, 3) if ch == 3 else (h, w), dtype=dt)
+                setattr(bufs, name, out[name].ctypes.data)
+        st = (capi.Stats * len(self.devices))()
+        info = capi.MultiInfo()
+        capi.check(capi.lib().crt_multi_render_buffers(self._mh, C.byref(cam), C.byref(prm), mask, C.byref(bufs) if to_host else None, st, C.byref(info)),
+                   "crt_multi_render_buffers")
+        self._rank_totals(st, info)
+        if not to_host:
+            return None
+        self.frame_buffer, self.mean_buffer, self.variance_buffer = out.get("rgb"), out.get("mean"), out.get("variance")
+        self.half_a_buffer, self.half_b_buffer = out.get("half_a"), out.get("half_b")
+        self.aov_buffers = {k: out[k] for k in capi.AOV_BUFFERS if k in out} or None
+        self.shading_buffers = {k: out[k] for k in capi.AOV_SHADING_BUFFERS if k in out} or None
+        return out
+
+    def gathered_device(self):
+        """({name: raw device pointer of the row-major plane, or None for a plane the last frame did not make}, device index) of the last
+        frame on this handle (crt_multi_buffers_device) -- for the *_device forms of the filters, with no host round trip.  Valid until
+        the next frame."""
+        if not self._mh:
+            raise RuntimeError("MultiRender.gathered_device after free()")
+        bufs, dev = capi.MultiBuffers(), C.c_int(-1)
+        capi.check(capi.lib().crt_multi_buffers_device(self._mh, C.byref(bufs), C.byref(dev)), "crt_multi_buffers_device")
+        return {name: getattr(bufs, name) for name in capi.MULTI_BUFFERS}, dev.value
+
+    def run_view_gathered_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
+                                   sigma_depth=None, width=None, height=None, variance_guided=False, demodulate=False, albedo_floor=None, nlm=None,
+                                   regress=None, scales=None):
+        """Render.run_view_denoised on a frame rendered over all ranks: the arguments are its own (without specular_guides / max_bounces:
+        there is no gather of the specular AOVs), the frame, its variance, the guides and -- demodulate -- the shading AOVs come from ONE
+        run_view_gathered, and everything after that is the very function the single-device method runs on rank 0's device.  Returns
+        (rgb, mean) with the single-device call's bits; the attributes are filled as there."""
+        name, settings, scales = _denoise_request("run_view_gathered_denoised", variance_guided, iterations, sigma_color, sigma_normal, sigma_albedo,
+                                                  sigma_depth, nlm, regress, scales, demodulate)
+        want = ("rgb", "mean", "albedo", "normal", "depth") + (("variance",) if _FILTERS[name][2] else ()) + (tuple(capi.AOV_SHADING_BUFFERS) if demodulate else ())
+        self.run_view_gathered(eye_pos, inv_view_mat, fovY, want=want, width=width, height=height)
+        return self._filter_frame(name, settings, scales, demodulate, albedo_floor)
+
+    def run_view_gathered_selected(self, eye_pos, inv_view_mat, fovY, candidates=("var", "nlm"), error_radius=None, blend_radius=None, width=None,
+                                   height=None):
+        """Render.run_view_selected on a frame rendered over all ranks: the halves, the variance and the guides come from ONE
+        run_view_gathered, the candidates and filter_select are the very function the single-device method runs.  Returns (rgb, mean)
+        with the single-device call's bits; self.select_buffers and self.select_info as there."""
+        names = _select_request("run_view_gathered_selected", candidates)
+        self.run_view_gathered(eye_pos, inv_view_mat, fovY, want=("rgb", "mean", "variance", "half_a", "half_b", "albedo", "normal", "depth"),
+                               width=width, height=height)
+        return self._select_frame(names, error_radius, blend_radius)
 
     def free(self):
         if self._mh:
@@ -1495,6 +1584,23 @@ def _run_filter(name, color, variance, guides, settings, device, want_rgb, weigh
     if takes_weights and weights is not None:
         settings = dict(settings, weight_color=weights, weight_variance=variance)
     return call(*((color, variance) if takes_variance else (color,)), device=device, want_rgb=want_rgb, return_info=True, **guides, **settings)
+
+
+def _select_request(who, candidates):
+    """the candidate names of a run_view_selected form, checked"""
+    names = tuple(candidates)
+    unknown = [n for n in names if n not in _SELECT_CANDIDATES]
+    if unknown or not 1 <= len(names) <= capi.SELECT_MAX_CANDIDATES:
+        raise ValueError("%s: candidates must be 1 .. %d of %r, got %r" % (who, capi.SELECT_MAX_CANDIDATES, _SELECT_CANDIDATES, names))
+    return names
+
+
+def _denoise_request(who, variance_guided, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth, nlm, regress, scales, demodulate):
+    """(filter name of _FILTERS, its settings, scales) of the filter arguments of a run_view_denoised form, checked"""
+    scales = 1 if scales is None else _check_scales(who, scales)
+    name, settings = _legacy_filter(who, variance_guided, iterations, sigma_color,
+                                    dict(sigma_normal=sigma_normal, sigma_albedo=sigma_albedo, sigma_depth=sigma_depth), nlm, regress, scales, demodulate)
+    return name, settings, scales
 
 
 def _legacy_filter(who, variance_guided, iterations, sigma_color, sigmas, nlm, regress, scales, demodulate):

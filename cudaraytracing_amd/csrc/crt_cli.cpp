@@ -12,7 +12,11 @@
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
-//           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]
+//           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]] [--gathered PREFIX[,NAME,...]]
+// --gathered PREFIX[,NAME,...] (only with --gpus / --devices) renders the frame with the buffers the image filters take gathered from all
+// ranks (crt_multi_render_buffers) and writes each float plane asked for as PREFIX.<NAME>.pfm (3 channels; depth and coverage: 1): NAME
+// is mean, variance, half_a, half_b, albedo, normal, depth, coverage, emission or diffuse_albedo; the default is mean, variance, albedo,
+// normal, depth.  Every file holds the floats the single-device options write: --variance's, --aov's depth, --aov-shading's two.
 // --upsample FACTOR[,RADIUS] --upsample-out PATH also renders the frame with resolution scaling (one device) and writes it as a PNG to PATH:
 // the paths at (W / FACTOR, H / FACTOR), the shading AOVs with albedo, normal and depth at that size and at (W, H) -- there with
 // --upsample-guide-spp samples per pixel (default: --spp) --, the low frame demodulated, upsampled along the two sets of guides
@@ -90,7 +94,9 @@ int main(int argc, char** argv)
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n"
-                             "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n", argv[0]);
+                             "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n"
+                             "       [--gathered PREFIX[,NAME,...]]  (with --gpus / --devices; NAME: mean, variance, half_a, half_b, albedo, normal, depth, coverage,\n"
+                             "                                        emission, diffuse_albedo; default: mean, variance, albedo, normal, depth)\n", argv[0]);
         return 2;
     }
     try {
@@ -135,6 +141,13 @@ int main(int argc, char** argv)
         bool reference = false, exact = false, fast = false, bounded = false;
         std::vector<int> devices;
         uint32_t gather = CRT_GATHER_AUTO;
+        // --gathered: the float planes of crt_multi_buffers by name, the prefix, and the planes asked for in the order given
+        const struct { const char* name; uint32_t bit, channels; } gathered_planes[] = {
+            {"mean", CRT_MULTI_MEAN, 3}, {"variance", CRT_MULTI_VARIANCE, 3}, {"half_a", CRT_MULTI_HALF_A, 3}, {"half_b", CRT_MULTI_HALF_B, 3},
+            {"albedo", CRT_MULTI_ALBEDO, 3}, {"normal", CRT_MULTI_NORMAL, 3}, {"depth", CRT_MULTI_DEPTH, 1}, {"coverage", CRT_MULTI_COVERAGE, 1},
+            {"emission", CRT_MULTI_EMISSION, 3}, {"diffuse_albedo", CRT_MULTI_DIFFUSE_ALBEDO, 3}};
+        std::string gathered;
+        std::vector<size_t> gathered_rows;
         auto need = [&](int i, int n) { if (i + n >= argc) throw crt::Error(CRT_ERR_INVALID_ARG, std::string("missing value after ") + argv[i]); };
         for (int i = 2; i < argc; i++) {
             std::string a = argv[i];
@@ -167,6 +180,25 @@ int main(int argc, char** argv)
                 const std::string g = argv[++i];
                 if (g == "auto") gather = CRT_GATHER_AUTO; else if (g == "rccl") gather = CRT_GATHER_RCCL; else if (g == "copy") gather = CRT_GATHER_COPY;
                 else throw crt::Error(CRT_ERR_INVALID_ARG, "--gather must be auto, rccl or copy");
+            }
+            else if (a == "--gathered") {
+                need(i, 1);
+                const std::string v = argv[++i];
+                size_t at = std::min(v.find(','), v.size());
+                gathered = v.substr(0, at);
+                if (gathered.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--gathered needs a PREFIX");
+                gathered_rows.clear();
+                while (at < v.size()) {
+                    const size_t end = std::min(v.find(',', at + 1), v.size());
+                    const std::string name = v.substr(at + 1, end - at - 1);
+                    size_t row = 0;
+                    while (row < sizeof(gathered_planes) / sizeof(gathered_planes[0]) && name != gathered_planes[row].name) row++;
+                    if (row == sizeof(gathered_planes) / sizeof(gathered_planes[0]))
+                        throw crt::Error(CRT_ERR_INVALID_ARG, "--gathered PREFIX[,NAME,...]: NAME is mean, variance, half_a, half_b, albedo, normal, depth, coverage, emission or diffuse_albedo, not '" + name + "'");
+                    gathered_rows.push_back(row);
+                    at = end;
+                }
+                if (gathered_rows.empty()) gathered_rows = {0, 1, 4, 5, 6}; // mean, variance, albedo, normal, depth
             }
             else if (a == "--base-dir") { need(i, 1); base_dir = argv[++i]; }
             else if (a == "--aov") { need(i, 1); aov = argv[++i]; }
@@ -405,6 +437,7 @@ int main(int argc, char** argv)
         if (denoise_scales && !(denoise_var || denoise_nlm || denoise_regress))
             throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales needs --denoise-variance, --denoise-nlm or --denoise-regress (the pyramid reduces the variance with the frame)");
         if (denoise_select && (adaptive || temporal)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs the half buffers of a uniformly sampled frame (not with --adaptive or --temporal)");
+        if (!gathered.empty() && !multi) throw crt::Error(CRT_ERR_INVALID_ARG, "--gathered gathers the buffers of a multi-device frame (only with --gpus / --devices)");
         const bool want_var = !variance.empty() || denoise_var || denoise_nlm || denoise_regress || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
         crt_denoise_var_defaults(&tdn);
@@ -463,6 +496,11 @@ int main(int argc, char** argv)
         }
         else if (adaptive && planned) render.run_view_planned(task.eye_pos, inv_view, fov_y, ad, want_var);
         else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
+        else if (!gathered.empty()) {
+            uint32_t want = 0;
+            for (size_t r : gathered_rows) want |= gathered_planes[r].bit;
+            render.run_view_gathered(task.eye_pos, inv_view, fov_y, want);
+        }
         else render.run_view(task.eye_pos, inv_view, fov_y);
         std::chrono::duration<double> dt = std::chrono::high_resolution_clock::now() - t0;
         if (adaptive && planned) {
@@ -487,6 +525,8 @@ int main(int argc, char** argv)
         }
         render.save_frame_buffer(out.c_str());
         std::printf("%s\n", out.c_str());
+        for (size_t r : gathered_rows) // (one at a time: their number is the caller's)
+            write_files("gathered plane", {{gathered + "." + gathered_planes[r].name + ".pfm", gathered_planes[r].channels, render.get_gathered_buffer(gathered_planes[r].bit)}});
         if (!variance.empty()) write_files("variance file", {{variance, 3, render.variance()}});
         if (!adaptive_samples.empty()) {
             std::vector<float> ns((size_t)task.width * task.height);

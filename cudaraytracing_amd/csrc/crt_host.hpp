@@ -214,6 +214,13 @@ public:
     Render& operator=(const Render&) = delete;
     // run_view(eye_pos, inv_view_mat, fovY): inv_view column-major, fovY in radians
     void run_view(const float eye_pos[3], const float inv_view_mat[9], float fovY);
+    // run_view on a multi-device Render with more of the frame's buffers, gathered from all ranks on the way (crt_multi_render_buffers):
+    // want names the planes (CRT_MULTI_* bits; RGB and MEAN are always made).  Frame and mean buffers as run_view leaves them, albedo,
+    // normal, depth, emission and diffuse_albedo in the buffers of run_aov; get_gathered_buffer(CRT_MULTI_x) is plane x of the last call --
+    // W x H pixels of its type, row 0 = image top -- or nullptr if that call did not make it (or run_view has run since).  The
+    // single-device methods keep refusing a multi-device Render; a single-device Render refuses this one (CRT_ERR_UNSUPPORTED).
+    void run_view_gathered(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t want);
+    const void* get_gathered_buffer(uint32_t plane) const;
     // the adaptive frame of crt_render_adaptive (ap: crt_adaptive_defaults with overrides) in place of run_view's: frame and mean buffers as
     // run_view leaves them, the samples per pixel in get_samples_buffer, and with want_variance the variance of the mean in variance();
     // CRT_FLAG_STATS / _BOUNDED_RADIANCE do not apply; one device only
@@ -354,6 +361,10 @@ private:
     std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame (run_view_adaptive fills it itself)
     std::vector<uint32_t> samples_buffer_;
     std::vector<int32_t> material_buffer_; // run_aov
+    uint32_t gathered_ = 0;                // run_view_gathered: the planes the last call made
+    std::vector<float> half_a_buffer_, half_b_buffer_, coverage_buffer_;
+    std::vector<int32_t> tri_buffer_;
+    void sum_rank_stats();
     // run_temporal: the accumulated frame = the next call's history, with the guides and the camera it was made with
     std::vector<float> temporal_color_, temporal_variance_, temporal_history_, temporal_depth_, temporal_normal_;
     std::vector<int32_t> temporal_id_;

@@ -124,18 +124,72 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     variance_buffer_.clear();
     int rc;
     if (multi_) {
+        gathered_ = 0;
         rc = crt_multi_render(multi_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), rank_stats_.data(), &multi_info_);
-        if (rc == CRT_OK) { // totals over the ranks; times of the slowest one
-            stats_ = rank_stats_[0];
-            for (size_t r = 1; r < rank_stats_.size(); r++) {
-                const crt_stats& o = rank_stats_[r];
-                stats_.paths += o.paths; stats_.rays += o.rays; stats_.shadow_rays += o.shadow_rays; stats_.probe_rays += o.probe_rays;
-                stats_.rays_untraced += o.rays_untraced;
-                stats_.kernel_ms = std::max(stats_.kernel_ms, o.kernel_ms); stats_.total_ms = std::max(stats_.total_ms, o.total_ms);
-            }
-        }
+        if (rc == CRT_OK) sum_rank_stats();
     } else rc = crt_render(device_scene_, &cam, &p, frame_buffer_.data(), mean_buffer_.data(), &stats_);
     check(rc, "Render::run_view");
+}
+// totals over the ranks; times of the slowest one
+void Render::sum_rank_stats()
+{
+    stats_ = rank_stats_[0];
+    for (size_t r = 1; r < rank_stats_.size(); r++) {
+        const crt_stats& o = rank_stats_[r];
+        stats_.paths += o.paths; stats_.rays += o.rays; stats_.shadow_rays += o.shadow_rays; stats_.probe_rays += o.probe_rays;
+        stats_.rays_untraced += o.rays_untraced;
+        stats_.kernel_ms = std::max(stats_.kernel_ms, o.kernel_ms); stats_.total_ms = std::max(stats_.total_ms, o.total_ms);
+    }
+}
+
+// The frame of run_view with more of its buffers, gathered from all ranks (crt_multi_render_buffers): frame and mean buffers as run_view
+// leaves them, every other plane of `want` in the buffer its single-device call fills here.
+void Render::run_view_gathered(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t want)
+{
+    alive("Render::run_view_gathered");
+    if (!multi_) throw Error(CRT_ERR_UNSUPPORTED, "Render::run_view_gathered gathers the buffers of a multi-device Render: on one device run_view, variance and run_aov make them");
+    if (want & ~(uint32_t)CRT_MULTI_ALL) throw Error(CRT_ERR_INVALID_ARG, "Render::run_view_gathered: want holds a bit that is no CRT_MULTI_* plane");
+    want |= CRT_MULTI_RGB | CRT_MULTI_MEAN;
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE), cam, p);
+    const size_t n = scene_->get_pixels();
+    gathered_ = 0;
+    auto plane = [&](uint32_t bit, auto& v, size_t per_pixel) {
+        if (want & bit) v.assign(per_pixel * n, 0); else v.clear();
+        return (want & bit) ? v.data() : nullptr;
+    };
+    crt_multi_buffers out{};
+    out.rgb = frame_buffer_.data(); out.mean = mean_buffer_.data();
+    out.variance = plane(CRT_MULTI_VARIANCE, variance_buffer_, 3);
+    out.half_a = plane(CRT_MULTI_HALF_A, half_a_buffer_, 3); out.half_b = plane(CRT_MULTI_HALF_B, half_b_buffer_, 3);
+    out.albedo = plane(CRT_MULTI_ALBEDO, albedo_buffer_, 3); out.normal = plane(CRT_MULTI_NORMAL, normal_buffer_, 3);
+    out.depth = plane(CRT_MULTI_DEPTH, depth_buffer_, 1); out.coverage = plane(CRT_MULTI_COVERAGE, coverage_buffer_, 1);
+    out.tri = plane(CRT_MULTI_TRI, tri_buffer_, 1); out.material = plane(CRT_MULTI_MATERIAL, material_buffer_, 1);
+    out.emission = plane(CRT_MULTI_EMISSION, emission_buffer_, 3); out.diffuse_albedo = plane(CRT_MULTI_DIFFUSE_ALBEDO, diffuse_albedo_buffer_, 3);
+    check(crt_multi_render_buffers(multi_, &cam, &p, want, &out, rank_stats_.data(), &multi_info_), "Render::run_view_gathered");
+    sum_rank_stats();
+    gathered_ = want;
+}
+const void* Render::get_gathered_buffer(uint32_t plane) const
+{
+    if (!(gathered_ & plane)) return nullptr;
+    switch (plane) {
+    case CRT_MULTI_RGB: return frame_buffer_.data();
+    case CRT_MULTI_MEAN: return mean_buffer_.data();
+    case CRT_MULTI_VARIANCE: return variance_buffer_.data();
+    case CRT_MULTI_HALF_A: return half_a_buffer_.data();
+    case CRT_MULTI_HALF_B: return half_b_buffer_.data();
+    case CRT_MULTI_ALBEDO: return albedo_buffer_.data();
+    case CRT_MULTI_NORMAL: return normal_buffer_.data();
+    case CRT_MULTI_DEPTH: return depth_buffer_.data();
+    case CRT_MULTI_COVERAGE: return coverage_buffer_.data();
+    case CRT_MULTI_TRI: return tri_buffer_.data();
+    case CRT_MULTI_MATERIAL: return material_buffer_.data();
+    case CRT_MULTI_EMISSION: return emission_buffer_.data();
+    case CRT_MULTI_DIFFUSE_ALBEDO: return diffuse_albedo_buffer_.data();
+    default: return nullptr;
+    }
 }
 
 // the arguments and buffers run_view_adaptive, run_view_map and run_view_planned share: `render` makes the library call on them

@@ -7,6 +7,9 @@
 // renders all shards concurrently (one host thread per device drives its own HIP stream), exchanges the
 // compact tile buffers with ONE collective -- ncclAllGather over RCCL / xGMI, every link carries each
 // peer's slice once -- and de-interleaves the gathered tiles into the row-major frame on rank 0.
+// A frame is a set of planes (crt_multi_render_buffers: RGB8, the mean, the variance, the half buffers, the first-hit and the shading
+// AOVs): a rank's block holds its tiles of every wanted plane, so the exchange stays ONE collective and the de-interleave ONE launch
+// (crt_untile.h).  crt_multi_render is the frame of RGB8 and the mean; render_planes below is the one implementation of both.
 //
 // RCCL is bound at run time (dlopen "librccl.so.1"): libcrt.so stays loadable on a box without it, and a
 // process that has already loaded PyTorch's RCCL shares that copy instead of mapping a second one.
@@ -132,25 +135,50 @@ struct NcclErr {
         if (r_ != ncclSuccess) throw NcclErr{r_, #call};    \
     } while (0)
 
-// Gathered tile buffers -> row-major frame.  Rank r stores its k-th tile (global tile k * world + r) at slots
-// [64 k, 64 k + 64) of its block; a block is `stride` bytes: RGB8 of `slots` pixels, padded to 16 B, then (optionally) the
-// float mean of the same pixels.
-__global__ __launch_bounds__(256) void k_untile(const uint8_t* gathered, uint32_t world, uint64_t stride, uint64_t mean_off, uint32_t width,
-                                                uint32_t height, uint32_t tiles_x, uint8_t* out_rgb, float* out_mean)
+} // namespace
+
+// Gathered tile blocks -> row-major planes on rank 0: the index arithmetic and k_untile_planes
+#include "crt_untile.h"
+
+namespace {
+
+// The planes a frame can be gathered as, in the order of their CRT_MULTI_* bits -- which is their order in a rank's block and the
+// order of crt_multi_buffers' members.
+struct PlaneKind { uint32_t bit, per_pixel, elem; };
+const PlaneKind kPlanes[crtk::kUntileMaxPlanes] = {
+    {CRT_MULTI_RGB, 3, 1},      {CRT_MULTI_MEAN, 3, 4},     {CRT_MULTI_VARIANCE, 3, 4}, {CRT_MULTI_HALF_A, 3, 4},   {CRT_MULTI_HALF_B, 3, 4},
+    {CRT_MULTI_ALBEDO, 3, 4},   {CRT_MULTI_NORMAL, 3, 4},   {CRT_MULTI_DEPTH, 1, 4},    {CRT_MULTI_COVERAGE, 1, 4}, {CRT_MULTI_TRI, 1, 4},
+    {CRT_MULTI_MATERIAL, 1, 4}, {CRT_MULTI_EMISSION, 3, 4}, {CRT_MULTI_DIFFUSE_ALBEDO, 3, 4}};
+enum { P_RGB, P_MEAN, P_VARIANCE, P_HALF_A, P_HALF_B, P_ALBEDO, P_NORMAL, P_DEPTH, P_COVERAGE, P_TRI, P_MATERIAL, P_EMISSION, P_DIFFUSE_ALBEDO };
+const uint32_t kFirstHitPlanes = CRT_MULTI_ALBEDO | CRT_MULTI_NORMAL | CRT_MULTI_DEPTH | CRT_MULTI_COVERAGE | CRT_MULTI_TRI | CRT_MULTI_MATERIAL;
+const uint32_t kShadingPlanes = CRT_MULTI_EMISSION | CRT_MULTI_DIFFUSE_ALBEDO;
+
+void* plane_of(const crt_multi_buffers& b, uint32_t k)
 {
-    const uint32_t i = blockIdx.x * 32u + (threadIdx.x & 31u);
-    const uint32_t j = blockIdx.y * 8u + (threadIdx.x >> 5);
-    if (i >= width || j >= height) return;
-    const uint32_t tile = (j >> 3) * tiles_x + (i >> 3);
-    const uint32_t r = tile % world, k = tile / world;
-    const uint64_t slot = (uint64_t)k * 64u + (j & 7u) * 8u + (i & 7u);
-    const uint8_t* block = gathered + (uint64_t)r * stride;
-    const uint64_t o = ((uint64_t)j * width + i) * 3u;
-    out_rgb[o] = block[slot * 3]; out_rgb[o + 1] = block[slot * 3 + 1]; out_rgb[o + 2] = block[slot * 3 + 2];
-    if (out_mean) {
-        const float* m = (const float*)(block + mean_off) + slot * 3;
-        out_mean[o] = m[0]; out_mean[o + 1] = m[1]; out_mean[o + 2] = m[2];
+    void* const p[crtk::kUntileMaxPlanes] = {b.rgb, b.mean, b.variance, b.half_a, b.half_b, b.albedo, b.normal, b.depth, b.coverage, b.tri, b.material,
+                                             b.emission, b.diffuse_albedo};
+    return p[k];
+}
+crt_multi_buffers buffers_of(void* const* p)
+{
+    return crt_multi_buffers{(uint8_t*)p[P_RGB], (float*)p[P_MEAN], (float*)p[P_VARIANCE], (float*)p[P_HALF_A], (float*)p[P_HALF_B], (float*)p[P_ALBEDO],
+                             (float*)p[P_NORMAL], (float*)p[P_DEPTH], (float*)p[P_COVERAGE], (int32_t*)p[P_TRI], (int32_t*)p[P_MATERIAL],
+                             (float*)p[P_EMISSION], (float*)p[P_DIFFUSE_ALBEDO]};
+}
+
+// A rank's block for a request mask: the wanted planes one after the other, each from a 16-byte boundary; 64-bit byte offsets
+struct BlockLayout {
+    uint64_t off[crtk::kUntileMaxPlanes]; // of a wanted plane
+    uint64_t stride = 0;
+};
+BlockLayout block_layout(uint32_t want, uint64_t slots)
+{
+    BlockLayout L;
+    for (uint32_t k = 0; k < crtk::kUntileMaxPlanes; k++) {
+        L.off[k] = L.stride;
+        if (want & kPlanes[k].bit) L.stride += crtk::untile_plane_bytes(slots, kPlanes[k].per_pixel, kPlanes[k].elem);
     }
+    return L;
 }
 
 struct Rank {
@@ -160,7 +188,8 @@ struct Rank {
     hipEvent_t done = nullptr;
     uint8_t* local = nullptr;    // this rank's block (stride bytes)
     uint8_t* gathered = nullptr; // world blocks (RCCL: every rank; COPY: rank 0 only)
-    size_t local_cap = 0, gathered_cap = 0;
+    uint8_t* rgb_scratch = nullptr; // the shard's RGB8 tiles of a frame whose RGB plane is not wanted (crt_render_device always writes them)
+    size_t local_cap = 0, gathered_cap = 0, rgb_scratch_cap = 0;
     ncclComm_t comm = nullptr;
 };
 
@@ -171,10 +200,10 @@ struct crt_multi {
     uint32_t gather = CRT_GATHER_COPY; // what runs
     int rccl_version = 0;
     int rccl_ranks = 0;
-    uint8_t* frame = nullptr;  // rank 0: row-major RGB8
-    float* mean = nullptr;     // rank 0: row-major mean
-    size_t frame_cap = 0, mean_cap = 0;
-    bool last_had_mean = false; // the last crt_multi_render wrote `mean`
+    uint8_t* plane[crtk::kUntileMaxPlanes] = {}; // rank 0: the row-major planes, in kPlanes' order (RGB8 first, then the mean)
+    size_t plane_cap[crtk::kUntileMaxPlanes] = {};
+    uint32_t last_want = 0;     // the planes the last render wrote (0: none yet, or it failed)
+    crtk::UntileParams last_untile{}; // ... and the de-interleave that wrote them (crt_multi_untile_time)
     std::string fallback_reason; // CRT_GATHER_AUTO only: why RCCL was not used although the devices are distinct (empty: no fallback happened)
 };
 
@@ -198,12 +227,13 @@ void destroy(crt_multi* m)
         if (rk.scene) (void)crt_scene_destroy(rk.scene);
         if (rk.local) (void)hipFree(rk.local);
         if (rk.gathered) (void)hipFree(rk.gathered);
+        if (rk.rgb_scratch) (void)hipFree(rk.rgb_scratch);
         if (rk.done) (void)hipEventDestroy(rk.done);
         if (rk.stream) (void)hipStreamDestroy(rk.stream);
     }
     if (!m->ranks.empty()) (void)hipSetDevice(m->ranks[0].device);
-    if (m->frame) (void)hipFree(m->frame);
-    if (m->mean) (void)hipFree(m->mean);
+    for (uint8_t* p : m->plane)
+        if (p) (void)hipFree(p);
     delete m;
 }
 
@@ -324,14 +354,18 @@ int crt_multi_destroy(crt_multi* m)
     return CRT_OK;
 }
 
-int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm, uint8_t* out_rgb, float* out_mean, crt_stats* stats,
-                     crt_multi_info* info)
+} // extern "C"
+
+namespace {
+
+// The one implementation of a multi-device frame: every rank renders its tiles of the wanted planes into its block, one exchange,
+// rank 0 de-interleaves.  `who` names the entry point in messages; its argument checks have run.
+int render_planes(const char* who_, crt_multi* m, const crt_camera* cam, const crt_params* prm, const uint32_t want, const crt_multi_buffers& host_out,
+                  crt_stats* stats, crt_multi_info* info)
 {
-    if (!m || !cam || !prm) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: null argument");
-    if (prm->width == 0 || prm->height == 0) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: width and height must be positive");
-    if (out_mean && !out_rgb) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: out_mean without out_rgb");
+    const std::string who = who_;
     const uint32_t world = (uint32_t)m->ranks.size();
-    const bool want_mean = out_mean != nullptr;
+    const bool want_sums = (want & CRT_MULTI_VARIANCE) != 0, want_halves = (want & (CRT_MULTI_HALF_A | CRT_MULTI_HALF_B)) != 0;
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     DeviceGuard guard;
@@ -340,30 +374,25 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
         for (Rank& rk : m->ranks)
             if (hipSetDevice(rk.device) == hipSuccess && rk.stream) (void)hipStreamSynchronize(rk.stream);
     };
-    m->last_had_mean = false;
+    m->last_want = 0;
     try {
         uint64_t slots = 0;
         int rc = crt_shard_slots(prm->width, prm->height, 0, world, &slots);
         if (rc != CRT_OK) return rc;
-        const uint64_t mean_off = (slots * 3 + 15) & ~15ull;
-        const uint64_t stride = want_mean ? mean_off + slots * 12 : mean_off;
+        const BlockLayout L = block_layout(want, slots);
+        const uint64_t stride = L.stride;
         for (uint32_t r = 0; r < world; r++) {
             Rank& rk = m->ranks[r];
             MHIP(hipSetDevice(rk.device));
             ensure(rk.local, rk.local_cap, stride);
+            if (!(want & CRT_MULTI_RGB)) ensure(rk.rgb_scratch, rk.rgb_scratch_cap, slots * 3);
             if (m->gather == CRT_GATHER_RCCL || r == 0) ensure(rk.gathered, rk.gathered_cap, stride * world);
         }
         MHIP(hipSetDevice(m->ranks[0].device));
-        {
-            size_t fb = (size_t)prm->width * prm->height * 3;
-            ensure(m->frame, m->frame_cap, fb);
-            if (want_mean) { // (through a local: the member must never hold a freed pointer if the allocation throws)
-                uint8_t* p = (uint8_t*)m->mean;
-                m->mean = nullptr;
-                ensure(p, m->mean_cap, fb * 4);
-                m->mean = (float*)p;
-            }
-        }
+        const uint64_t pixels = (uint64_t)prm->width * prm->height;
+        auto plane_bytes = [&](uint32_t k) { return (size_t)(pixels * kPlanes[k].per_pixel * kPlanes[k].elem); };
+        for (uint32_t k = 0; k < crtk::kUntileMaxPlanes; k++)
+            if ((want & kPlanes[k].bit) || k == P_RGB) ensure(m->plane[k], m->plane_cap[k], plane_bytes(k)); // (RGB: crt_multi_frame_device has always had a frame to report)
         // ---- every rank renders its tiles: one host thread per device, each on its own stream ----
         std::vector<int> rcs(world, CRT_OK);
         std::vector<std::string> errs(world);
@@ -373,10 +402,38 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
             crt_params p = *prm;
             p.rank = r; p.world = world;
             p.flags |= CRT_FLAG_TILED_OUTPUT;
-            p.flags &= ~(uint32_t)(CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS); // (there is no gather for the variance buffer or the halves: crt_variance and crt_half_buffers are single-device interfaces)
+            // the sums of crt_variance and crt_half_buffers are kept exactly when a plane needs them (a frame of RGB and the mean: never)
+            p.flags &= ~(uint32_t)(CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS);
+            if (want_sums) p.flags |= CRT_FLAG_VARIANCE;
+            if (want_halves) p.flags |= CRT_FLAG_HALF_BUFFERS;
+            auto at = [&](uint32_t k) -> uint8_t* { return (want & kPlanes[k].bit) ? rk.local + L.off[k] : nullptr; };
+            auto step = [&](int status) {
+                rcs[r] = status;
+                if (status != CRT_OK) errs[r] = crt_last_error();
+                return status == CRT_OK;
+            };
             if (hipSetDevice(rk.device) != hipSuccess) { rcs[r] = CRT_ERR_HIP; errs[r] = "hipSetDevice failed"; return; }
-            rcs[r] = crt_render_device(rk.scene, cam, &p, rk.local, want_mean ? rk.local + mean_off : nullptr, rk.stream, &st[r]);
-            if (rcs[r] != CRT_OK) errs[r] = crt_last_error();
+            if (!step(crt_render_device(rk.scene, cam, &p, (want & CRT_MULTI_RGB) ? at(P_RGB) : rk.rgb_scratch, at(P_MEAN), rk.stream, &st[r]))) return;
+            bool enqueued = false; // work behind the render, which crt_render_device has waited for
+            if (want_sums) {
+                if (!step(crt_variance_device(rk.scene, at(P_VARIANCE), rk.stream, nullptr))) return;
+                enqueued = true;
+            }
+            if (want_halves) {
+                if (!step(crt_half_buffers_device(rk.scene, at(P_HALF_A), at(P_HALF_B), rk.stream, nullptr))) return;
+                enqueued = true;
+            }
+            if (want & (kFirstHitPlanes | kShadingPlanes)) { // ONE trace of the frame's camera rays for all of them
+                const crt_aov_buffers first{(float*)at(P_ALBEDO), (float*)at(P_NORMAL), (float*)at(P_DEPTH), (float*)at(P_COVERAGE), (int32_t*)at(P_TRI),
+                                            (int32_t*)at(P_MATERIAL)};
+                const crt_aov_shading_buffers shading{(float*)at(P_EMISSION), (float*)at(P_DIFFUSE_ALBEDO)};
+                const int status = (want & kShadingPlanes)
+                                       ? crt_render_aov_shading_device(rk.scene, cam, &p, (want & kFirstHitPlanes) ? &first : nullptr, &shading, rk.stream, nullptr)
+                                       : crt_render_aov_device(rk.scene, cam, &p, &first, rk.stream, nullptr);
+                if (!step(status)) return;
+                enqueued = true;
+            }
+            if (enqueued && hipStreamSynchronize(rk.stream) != hipSuccess) { rcs[r] = CRT_ERR_HIP; errs[r] = "hipStreamSynchronize failed"; } // (render_ms: until every shard is complete)
         };
         if (world == 1) work(0);
         else {
@@ -385,7 +442,7 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
             for (std::thread& t : th) t.join();
         }
         for (uint32_t r = 0; r < world; r++)
-            if (rcs[r] != CRT_OK) { drain(); return mfail(rcs[r], "crt_multi_render: rank " + std::to_string(r) + ": " + errs[r]); }
+            if (rcs[r] != CRT_OK) { drain(); return mfail(rcs[r], who + ": rank " + std::to_string(r) + ": " + errs[r]); }
         const auto t1 = clk::now();
         // ---- one exchange: all-gather of the compact tile blocks ----
         if (m->gather == CRT_GATHER_RCCL) {
@@ -408,24 +465,29 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
             MHIP(hipSetDevice(r0.device));
             for (uint32_t r = 1; r < world; r++) MHIP(hipStreamWaitEvent(r0.stream, m->ranks[r].done, 0));
         }
-        // ---- rank 0 de-interleaves the tiles into the frame ----
+        // ---- rank 0 de-interleaves the tiles of every wanted plane with one launch ----
+        crtk::UntileParams U{};
         {
             Rank& r0 = m->ranks[0];
             MHIP(hipSetDevice(r0.device));
-            const uint32_t tiles_x = (prm->width + 7) / 8;
-            dim3 grid((prm->width + 31) / 32, (prm->height + 7) / 8);
-            hipLaunchKernelGGL(k_untile, grid, dim3(256), 0, r0.stream, r0.gathered, world, stride, mean_off, prm->width, prm->height, tiles_x, m->frame,
-                               want_mean ? m->mean : nullptr);
+            U.gathered = r0.gathered; U.stride = stride; U.world = world; U.width = prm->width; U.height = prm->height;
+            U.tiles_x = crtk::untile_tiles_x(prm->width); U.chunks = crtk::untile_chunks(prm->width);
+            for (uint32_t k = 0; k < crtk::kUntileMaxPlanes; k++)
+                if (want & kPlanes[k].bit) U.plane[U.n_planes++] = crtk::UntilePlane{L.off[k], m->plane[k], kPlanes[k].per_pixel, kPlanes[k].elem};
+            const uint64_t grid = crtk::untile_grid(U);
+            if (grid > 0x7fffffffull) { drain(); return mfail(CRT_ERR_INVALID_ARG, who + ": the frame is too large for one de-interleave launch"); }
+            hipLaunchKernelGGL(crtk::k_untile_planes, dim3((uint32_t)grid), dim3(crtk::kUntileBlock), 0, r0.stream, U);
             MHIP(hipGetLastError());
-            if (out_rgb) MHIP(hipMemcpyAsync(out_rgb, m->frame, (size_t)prm->width * prm->height * 3, hipMemcpyDeviceToHost, r0.stream)); // Render.cuh:464
-            if (out_mean) MHIP(hipMemcpyAsync(out_mean, m->mean, (size_t)prm->width * prm->height * 12, hipMemcpyDeviceToHost, r0.stream));
+            for (uint32_t k = 0; k < crtk::kUntileMaxPlanes; k++) // (RGB8: Render.cuh:464)
+                if ((want & kPlanes[k].bit) && plane_of(host_out, k)) MHIP(hipMemcpyAsync(plane_of(host_out, k), m->plane[k], plane_bytes(k), hipMemcpyDeviceToHost, r0.stream));
         }
         for (uint32_t r = 0; r < world; r++) {
             MHIP(hipSetDevice(m->ranks[r].device));
             MHIP(hipStreamSynchronize(m->ranks[r].stream));
         }
         const auto t2 = clk::now();
-        m->last_had_mean = want_mean;
+        m->last_want = want;
+        m->last_untile = U;
         if (stats) std::memcpy(stats, st.data(), sizeof(crt_stats) * world);
         if (info) {
             std::memset(info, 0, sizeof(*info));
@@ -446,21 +508,86 @@ int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm,
         return CRT_OK;
     } catch (const HipErr& f) {
         drain();
-        return mfail(CRT_ERR_HIP, std::string("crt_multi_render: ") + f.what + ": " + hipGetErrorString(f.e));
+        return mfail(CRT_ERR_HIP, who + ": " + f.what + ": " + hipGetErrorString(f.e));
     } catch (const NcclErr& f) {
         drain();
-        return mfail(CRT_ERR_HIP, std::string("crt_multi_render: ") + f.what + ": " + rccl().GetErrorString(f.r));
+        return mfail(CRT_ERR_HIP, who + ": " + f.what + ": " + rccl().GetErrorString(f.r));
     } catch (const std::bad_alloc&) {
         drain();
-        return mfail(CRT_ERR_OOM, "crt_multi_render: out of host memory");
+        return mfail(CRT_ERR_OOM, who + ": out of host memory");
     }
+}
+
+} // namespace
+
+extern "C" {
+
+int crt_multi_render(crt_multi* m, const crt_camera* cam, const crt_params* prm, uint8_t* out_rgb, float* out_mean, crt_stats* stats,
+                     crt_multi_info* info)
+{
+    if (!m || !cam || !prm) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: null argument");
+    if (prm->width == 0 || prm->height == 0) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: width and height must be positive");
+    if (out_mean && !out_rgb) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render: out_mean without out_rgb");
+    crt_multi_buffers host{};
+    host.rgb = out_rgb; host.mean = out_mean;
+    return render_planes("crt_multi_render", m, cam, prm, CRT_MULTI_RGB | (out_mean ? CRT_MULTI_MEAN : 0u), host, stats, info);
+}
+
+int crt_multi_render_buffers(crt_multi* m, const crt_camera* cam, const crt_params* prm, uint32_t want, const crt_multi_buffers* host_out, crt_stats* stats,
+                             crt_multi_info* info)
+{
+    if (!m || !cam || !prm) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render_buffers: null argument");
+    if (prm->width == 0 || prm->height == 0) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render_buffers: width and height must be positive");
+    if (want == 0 || (want & ~(uint32_t)CRT_MULTI_ALL)) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render_buffers: want must name at least one plane and only CRT_MULTI_* bits");
+    if ((want & (CRT_MULTI_VARIANCE | CRT_MULTI_HALF_A | CRT_MULTI_HALF_B)) && prm->spp < 2)
+        return mfail(CRT_ERR_INVALID_ARG, "crt_multi_render_buffers: the variance and the half planes need spp >= 2");
+    const crt_multi_buffers none{};
+    return render_planes("crt_multi_render_buffers", m, cam, prm, want, host_out ? *host_out : none, stats, info);
 }
 
 int crt_multi_frame_device(crt_multi* m, void** d_rgb, void** d_mean, int* device)
 {
     if (!m) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_frame_device: null argument");
-    if (d_rgb) *d_rgb = m->frame;
-    if (d_mean) *d_mean = m->last_had_mean ? m->mean : nullptr;
+    if (d_rgb) *d_rgb = (m->last_want == 0 || (m->last_want & CRT_MULTI_RGB)) ? m->plane[P_RGB] : nullptr;
+    if (d_mean) *d_mean = (m->last_want & CRT_MULTI_MEAN) ? m->plane[P_MEAN] : nullptr;
+    if (device) *device = m->ranks[0].device;
+    return CRT_OK;
+}
+
+int crt_multi_untile_time(crt_multi* m, uint32_t calls, float* ms)
+{
+    if (!m || !ms || calls == 0) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_untile_time: null argument or no calls");
+    if (m->last_want == 0) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_untile_time: no frame on the handle");
+    DeviceGuard guard;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    try {
+        Rank& r0 = m->ranks[0];
+        MHIP(hipSetDevice(r0.device));
+        MHIP(hipEventCreate(&e0));
+        MHIP(hipEventCreate(&e1));
+        for (uint32_t c = 0; c < calls; c++) {
+            MHIP(hipEventRecord(e0, r0.stream));
+            hipLaunchKernelGGL(crtk::k_untile_planes, dim3((uint32_t)crtk::untile_grid(m->last_untile)), dim3(crtk::kUntileBlock), 0, r0.stream, m->last_untile);
+            MHIP(hipGetLastError());
+            MHIP(hipEventRecord(e1, r0.stream));
+            MHIP(hipEventSynchronize(e1));
+            MHIP(hipEventElapsedTime(&ms[c], e0, e1));
+        }
+        (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        return CRT_OK;
+    } catch (const HipErr& f) {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        return mfail(CRT_ERR_HIP, std::string("crt_multi_untile_time: ") + f.what + ": " + hipGetErrorString(f.e));
+    }
+}
+
+int crt_multi_buffers_device(crt_multi* m, crt_multi_buffers* dev, int* device)
+{
+    if (!m || !dev) return mfail(CRT_ERR_INVALID_ARG, "crt_multi_buffers_device: null argument");
+    void* p[crtk::kUntileMaxPlanes];
+    for (uint32_t k = 0; k < crtk::kUntileMaxPlanes; k++) p[k] = (m->last_want & kPlanes[k].bit) ? m->plane[k] : nullptr;
+    *dev = buffers_of(p);
     if (device) *device = m->ranks[0].device;
     return CRT_OK;
 }

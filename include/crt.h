@@ -139,7 +139,8 @@ enum {
     CRT_FLAG_VARIANCE = 32u,     /* keep, beside the frame's sum, the per-pixel sum of squares of the samples on the scene handle:
                                     crt_variance reads the variance of the frame's mean from it.  The frame is bit for bit the frame without
                                     the flag.  Switches the commit ring of CRT_FLAG_BOUNDED_RADIANCE (and of the CRT_COMMIT_RING_LOG2 test
-                                    hook) off for the call, as CRT_FLAG_STATS does.  Cleared by crt_multi_render (no gather for the buffer) */
+                                    hook) off for the call, as CRT_FLAG_STATS does.  Cleared by crt_multi_render (it gathers no
+                                    variance; crt_multi_render_buffers sets the flag itself when the VARIANCE plane is wanted) */
     CRT_FLAG_HALF_BUFFERS = 64u  /* keep, beside c and q, the sums of the even and of the odd samples of every pixel on the scene handle:
                                     crt_half_buffers reads two independent half-sample frames from them.  Implies CRT_FLAG_VARIANCE: the call
                                     behaves as if both were set (commit ring off included); frame, c and q are bit for bit those of
@@ -1145,8 +1146,64 @@ int crt_multi_destroy(crt_multi* multi);
  * (needs out_rgb); stats: NULL or n_devices entries, one per rank; info optional. */
 int crt_multi_render(crt_multi* multi, const crt_camera* cam, const crt_params* params, uint8_t* out_rgb, float* out_mean,
                      crt_stats* stats, crt_multi_info* info);
-/* device pointers of the last frame on rank 0's device (d_mean: NULL unless the last call asked for the mean) */
+/* device pointers of the last frame on rank 0's device (d_mean: NULL unless the last call asked for the mean; d_rgb: NULL after a
+ * crt_multi_render_buffers that did not ask for RGB) */
 int crt_multi_frame_device(crt_multi* multi, void** d_rgb, void** d_mean, int* device);
+
+/* The buffers of a multi-device frame: what the image operations of this header (crt_denoise*, crt_demodulate / crt_modulate,
+ * crt_filter_select, crt_pyramid_*, crt_temporal*, crt_upsample) take, gathered row-major on rank 0's device.  One bit per plane; the
+ * bits' order is the order of the planes in a rank's block and of crt_multi_buffers' members. */
+enum {
+    CRT_MULTI_RGB = 1u,              /* 3 x u8   crt_render's out_rgb */
+    CRT_MULTI_MEAN = 2u,             /* 3 x f32  crt_render's out_mean */
+    CRT_MULTI_VARIANCE = 4u,         /* 3 x f32  crt_variance */
+    CRT_MULTI_HALF_A = 8u,           /* 3 x f32  crt_half_buffers' out_a */
+    CRT_MULTI_HALF_B = 16u,          /* 3 x f32  crt_half_buffers' out_b */
+    CRT_MULTI_ALBEDO = 32u,          /* 3 x f32  crt_render_aov */
+    CRT_MULTI_NORMAL = 64u,          /* 3 x f32 */
+    CRT_MULTI_DEPTH = 128u,          /* f32 */
+    CRT_MULTI_COVERAGE = 256u,       /* f32 */
+    CRT_MULTI_TRI = 512u,            /* i32 */
+    CRT_MULTI_MATERIAL = 1024u,      /* i32 */
+    CRT_MULTI_EMISSION = 2048u,      /* 3 x f32  crt_render_aov_shading */
+    CRT_MULTI_DIFFUSE_ALBEDO = 4096u,/* 3 x f32 */
+    CRT_MULTI_ALL = 8191u
+};
+typedef struct {
+    uint8_t* rgb;
+    float* mean; float* variance; float* half_a; float* half_b;
+    float* albedo; float* normal; float* depth; float* coverage;
+    int32_t* tri; int32_t* material;
+    float* emission; float* diffuse_albedo;
+} crt_multi_buffers;
+/* Renders the frame over all ranks as crt_multi_render does and gathers every plane of `want` (CRT_MULTI_* bits): afterwards each is
+ * row-major (W x H pixels, row 0 = image top) on rank 0's device, and is copied to the matching pointer of host_out where that is not
+ * NULL (host_out itself may be NULL; pointers of planes that are not wanted are ignored).  Every plane has the bits of the
+ * single-device call named beside its bit above, on the same scene, camera and params, whatever the number of ranks.
+ * Per rank, on the rank's own thread and stream, in this order: crt_render_device with CRT_FLAG_TILED_OUTPUT -- CRT_FLAG_VARIANCE set
+ * exactly when VARIANCE is wanted, CRT_FLAG_HALF_BUFFERS exactly when a half is, both cleared otherwise whatever params->flags says --;
+ * crt_variance_device / crt_half_buffers_device into the rank's block; then at most ONE trace of the frame's camera rays:
+ * crt_render_aov_shading_device when EMISSION or DIFFUSE_ALBEDO is wanted (its `first` names the wanted first-hit planes, NULL when
+ * there is none), crt_render_aov_device when only first-hit planes are, nothing when no AOV plane is.
+ * A rank's block is its wanted planes one after the other in the bits' order, each from a 16-byte boundary, of `slots` pixels each
+ * (crt_shard_slots; padding slots as the calls above define them), with 64-bit byte offsets.  The blocks travel in ONE ncclAllGather
+ * (or the peer copies of CRT_GATHER_COPY), crt_multi_info.bytes_per_rank is a block's size, and ONE kernel launch on rank 0
+ * de-interleaves all planes (csrc/crt_untile.h).  An all-gather delivers every plane to every rank although only rank 0 uses them.
+ * render_ms ends when every rank's passes are complete; gather_ms is the exchange, the de-interleave and the copies to the host.
+ * CRT_ERR_INVALID_ARG, checked before any device call: a null handle, camera or params; want == 0 or a bit outside CRT_MULTI_ALL;
+ * VARIANCE, HALF_A or HALF_B with params->spp < 2; a width or height of 0.  A refused or failed call leaves the handle usable.
+ * crt_multi_render IS this call with RGB (and MEAN when out_mean is given): one implementation, the same results, info and
+ * bytes_per_rank as before.  stats, info: as crt_multi_render's. */
+int crt_multi_render_buffers(crt_multi* multi, const crt_camera* cam, const crt_params* params, uint32_t want,
+                             const crt_multi_buffers* host_out /* may be NULL */, crt_stats* stats, crt_multi_info* info);
+/* The device pointers, on rank 0's device (*device, optional), of the planes the last render on the handle made -- crt_multi_render
+ * makes RGB and, asked for, MEAN --; a plane that call did not make is NULL, as is every plane after a call that failed on a device (a refused call leaves them as they were).  Valid until the
+ * next render on the handle.  For the *_device forms of the image operations: no host round trip. */
+int crt_multi_buffers_device(crt_multi* multi, crt_multi_buffers* dev, int* device);
+/* Measurement hook (tools/gather_probe.py): launches the de-interleave of the last frame on the handle again, `calls` times, each
+ * between two HIP events on rank 0's stream; ms[c] receives the time of launch c.  The gathered blocks are still in place, so the
+ * planes are rewritten with their own values.  CRT_ERR_INVALID_ARG: a null argument, calls == 0, no frame on the handle. */
+int crt_multi_untile_time(crt_multi* multi, uint32_t calls, float* ms);
 
 /* Closest-hit query for n rays (device-side DeviceBVH::intersect,
  * DeviceBVH.cuh:128-170), host buffers. dirs are normalised as Ray's
