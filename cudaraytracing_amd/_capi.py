@@ -224,6 +224,19 @@ class TemporalClampInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float), ("reprojected", C.c_uint64), ("clamped", C.c_uint64)]
 
 
+class TemporalDual(C.Structure):
+    _fields_ = [("radius", C.c_uint32), ("min_bounces", C.c_float)]
+
+
+class TemporalSpecularPlanes(C.Structure):
+    _fields_ = [("path_depth", C.c_void_p), ("bounces", C.c_void_p), ("last_normal", C.c_void_p)]
+
+
+class TemporalDualInfo(InfoStruct):
+    _fields_ = [("total_ms", C.c_float), ("reprojected", C.c_uint64), ("clamped", C.c_uint64), ("virtual_tried", C.c_uint64),
+                ("virtual_taken", C.c_uint64)]
+
+
 class TemporalMomentPlanes(C.Structure):
     _fields_ = [("m1", C.c_void_p), ("m2", C.c_void_p)]
 
@@ -347,7 +360,7 @@ ABI_VERSION = 5  # include/crt.h: CRT_ABI_VERSION
 
 # every symbol include/crt.h declares
 EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_count", "crt_scene_create",
-           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
+           "crt_scene_accel_info", "crt_scene_destroy", "crt_task_obj", "crt_shard_slots", "crt_render", "crt_render_device", "crt_render_range", "crt_render_range_device", "crt_last_launch_ms", "crt_radiance_storage", "crt_preview", "crt_preview_device", "crt_variance", "crt_variance_device", "crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device", "crt_render_aov", "crt_render_aov_device", "crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device", "crt_denoise_nlm_defaults", "crt_denoise_nlm_scratch_bytes", "crt_denoise_nlm", "crt_denoise_nlm_device", "crt_temporal_defaults", "crt_temporal", "crt_temporal_device", "crt_temporal_clamp_defaults", "crt_temporal_clamped", "crt_temporal_clamped_device", "crt_temporal_moments", "crt_temporal_moments_device", "crt_temporal_dual_defaults", "crt_temporal_dual", "crt_temporal_dual_device", "crt_variance_estimate_defaults", "crt_variance_estimate", "crt_variance_estimate_device", "crt_multi_create", "crt_multi_destroy",
            "crt_multi_render", "crt_multi_frame_device", "crt_multi_render_buffers", "crt_multi_buffers_device", "crt_multi_untile_time", "crt_intersect",
            "crt_device_math", "crt_device_fn", "crt_device_philox", "crt_device_rcp_check", "crt_scene_export", "crt_host_scene_create", "crt_host_scene_destroy",
            "crt_host_scene_add_obj", "crt_host_scene_set_bvh", "crt_host_scene_set_bvh_device", "crt_host_scene_desc", "crt_host_scene_num_objects",
@@ -461,6 +474,13 @@ def lib():
     L.crt_temporal_moments_device.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalFrame),
                                               C.POINTER(TemporalHistory), C.POINTER(TemporalMomentPlanes), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalClampInfo)]
+    L.crt_temporal_dual_defaults.argtypes = [C.POINTER(TemporalDual)]
+    L.crt_temporal_dual.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalDual), C.POINTER(TemporalFrame),
+                                    C.POINTER(TemporalSpecularPlanes), C.POINTER(TemporalHistory), C.POINTER(TemporalSpecularPlanes), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalDualInfo)]
+    L.crt_temporal_dual_device.argtypes = [C.c_int, C.POINTER(TemporalParams), C.POINTER(TemporalClamp), C.POINTER(TemporalDual), C.POINTER(TemporalFrame),
+                                           C.POINTER(TemporalSpecularPlanes), C.POINTER(TemporalHistory), C.POINTER(TemporalSpecularPlanes), C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(TemporalDualInfo)]
     L.crt_variance_estimate_defaults.argtypes = [C.POINTER(VarianceEstimateParams)]
     L.crt_variance_estimate.argtypes = [C.c_int, C.POINTER(VarianceEstimateParams), C.POINTER(VarianceEstimateInputs), C.c_void_p,
                                         C.POINTER(VarianceEstimateInfo)]

@@ -695,7 +695,7 @@ class Render:
         return rgb, mean
 
     def run_view_temporal(self, eye_pos, inv_view_mat, fovY, denoise=False, seed=None, width=None, height=None, clamp=None, variance="samples",
-                          demodulate=False, albedo_floor=None, **overrides):
+                          demodulate=False, albedo_floor=None, specular=False, **overrides):
         """One frame of a temporally accumulated sequence (crt_temporal, contract: include/crt.h): renders with want_variance, runs the
         AOV pass (albedo, normal, depth, material) and blends the frame into the history this object keeps -- colour, variance, history
         length, depth, normal, material ID and camera of the previous call; the unfiltered result is the next call's history.
@@ -714,18 +714,34 @@ class Render:
         its guides; the frame and its variance go through demodulate(albedo_floor) before the blend, so the history -- and with it the
         clamp's neighbourhood, the moments and self.variance_buffer -- holds irradiance and its variance.  What is returned (and, with
         denoise=True, filtered first, on irradiance) goes through modulate() with the CURRENT frame's buffers.  A change of `demodulate`
-        starts a history."""
+        starts a history.
+        specular: False, True or a dict of max_bounces / radius / min_bounces -- crt_temporal_dual: each frame also runs
+        run_view_aov_specular (max_bounces), its path_depth, bounces and last_normal are kept with the history, and a mirror pixel also
+        tries the history its virtual image points at (temporal(dual=dict(radius=, min_bounces=))); self.temporal_info gains `clamped`
+        (0 without a clamp), `virtual_tried` and `virtual_taken`.  It composes with clamp, denoise and demodulate and excludes
+        variance="moments" (ValueError).  A change of `specular` between False and not starts a history."""
         if variance not in ("samples", "moments"):
             raise ValueError("run_view_temporal: variance must be 'samples' or 'moments', got %r" % (variance,))
+        dual = max_bounces = None
+        if specular is not False:
+            if specular is not True and (not isinstance(specular, dict) or set(specular) - {"max_bounces", "radius", "min_bounces"}):
+                raise ValueError("run_view_temporal: specular must be False, True or a dict of max_bounces / radius / min_bounces, got %r" % (specular,))
+            if variance == "moments":
+                raise ValueError("run_view_temporal: specular and variance='moments' cannot be combined (crt_temporal_moments has no dual form)")
+            settings = {} if specular is True else specular
+            max_bounces = settings.get("max_bounces")
+            dual = {k: settings[k] for k in ("radius", "min_bounces") if k in settings} or True
         self._handle("run_view_temporal")
         demodulate = bool(demodulate)
         if self._temporal is not None and self._temporal.get("demodulate", False) != demodulate:
+            self._temporal = None
+        if self._temporal is not None and ("path_depth" in self._temporal["prev"]) != (dual is not None):
             self._temporal = None
         if variance == "moments":
             return self._run_view_temporal_moments(eye_pos, inv_view_mat, fovY, denoise, seed, width, height, clamp, overrides, demodulate, albedo_floor)
         if self._temporal is not None and "m1" in self._temporal:
             self._temporal = None
-        aov = self._temporal_frame(eye_pos, inv_view_mat, fovY, seed, width, height, True, demodulate)
+        aov = self._temporal_frame(eye_pos, inv_view_mat, fovY, seed, width, height, True, demodulate, specular=(max_bounces,) if dual is not None else None)
         h, w = self.mean_buffer.shape[:2]
         cam = (np.array(eye_pos, dtype=np.float32), np.array(inv_view_mat, dtype=np.float32).reshape(9), np.float32(fovY))
         cur = {"color": self.mean_buffer, "variance": self.variance_buffer, "depth": aov["depth"], "normal": aov["normal"], "id": aov["material"]}
@@ -733,6 +749,9 @@ class Render:
             sh = self.shading_buffers
             cur["color"], cur["variance"] = _demodulate(self.mean_buffer, sh["diffuse_albedo"], sh["emission"], variance=self.variance_buffer,
                                                         albedo_floor=albedo_floor, device=self.device)
+        if dual is not None:
+            cur.update({k: aov[k] for k in _SPECULAR_PLANES})
+            overrides = dict(overrides, dual=dual)
         t = self._temporal if (self._temporal is not None and self._temporal["size"] == (w, h)) else None
         rgb, mean, var, hist, info = temporal(cur, cam, prev=t["prev"] if t else None, prev_camera=t["camera"] if t else None, device=self.device,
                                               return_info=True, clamp=clamp, want_rgb=not demodulate, **overrides)
@@ -741,9 +760,10 @@ class Render:
         self.variance_buffer, self.temporal_history_buffer, self.temporal_info = var, hist, info
         return self._temporal_result(rgb, mean, var, denoise, demodulate, albedo_floor)
 
-    def _temporal_frame(self, eye_pos, inv_view_mat, fovY, seed, width, height, want_variance, demodulate):
+    def _temporal_frame(self, eye_pos, inv_view_mat, fovY, seed, width, height, want_variance, demodulate, specular=None):
         """Renders a frame of run_view_temporal with its seed and runs the pass of its guides (self.aov_buffers) and, demodulate, of its
-        shading AOVs (self.shading_buffers); returns the first-hit buffers the blend takes."""
+        shading AOVs (self.shading_buffers); returns the first-hit buffers the blend takes.  specular: None or (max_bounces,) -- the
+        specular AOV pass runs with the frame's seed too, and its three planes are returned with the others."""
         names = ("albedo", "normal", "depth", "material")
         keep_seed = self.seed
         self.seed = keep_seed + self._temporal_frames if seed is None else int(seed)
@@ -754,6 +774,9 @@ class Render:
                 self.shading_buffers = {k: aov[k] for k in capi.AOV_SHADING_BUFFERS}
             else:
                 aov = self.run_view_aov(eye_pos, inv_view_mat, fovY, want=names, width=width, height=height)
+            if specular is not None:
+                aov = dict(aov, **self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=specular[0], want=_SPECULAR_PLANES, width=width,
+                                                             height=height))
         finally:
             self.seed = keep_seed
         self.aov_buffers = {k: aov[k] for k in ("albedo", "normal", "depth")}
@@ -1783,6 +1806,53 @@ def _temporal_clamp(clamp):
     return c
 
 
+def temporal_dual_defaults():
+    """crt_temporal_dual_defaults as a dict: radius, min_bounces."""
+    return _settings(_defaults(capi.TemporalDual, "crt_temporal_dual_defaults"))
+
+
+_SPECULAR_PLANES = ("path_depth", "bounces", "last_normal")
+
+
+def _temporal_dual(dual):
+    """dual=True (the defaults) or a dict of radius / min_bounces -> crt_temporal_dual"""
+    d = _defaults(capi.TemporalDual, "crt_temporal_dual_defaults")
+    if dual is True:
+        return d
+    if not isinstance(dual, dict) or set(dual) - {"radius", "min_bounces"}:
+        raise ValueError("temporal: dual must be None, True or a dict of radius / min_bounces, got %r" % (dual,))
+    if dual.get("radius") is not None:
+        r = int(dual["radius"])
+        if r != dual["radius"] or not 0 <= r < 2 ** 32:
+            raise ValueError("temporal: the dual reprojection's radius must be an integer 1 .. 3, got %r" % (dual["radius"],))
+        d.radius = r
+    if dual.get("min_bounces") is not None:
+        d.min_bounces = float(dual["min_bounces"])
+    return d
+
+
+def _split_specular(buffers):
+    """a frame's dict -> (the dict without the specular planes, the specular planes)"""
+    if buffers is None:
+        return None, None
+    return ({k: v for k, v in buffers.items() if k not in _SPECULAR_PLANES}, {k: v for k, v in buffers.items() if k in _SPECULAR_PLANES})
+
+
+def _specular_struct(planes, h, w, keep):
+    """the specular planes of a frame's dict (host arrays) -> crt_temporal_specular_planes"""
+    s = capi.TemporalSpecularPlanes()
+    for name in _SPECULAR_PLANES:
+        a = planes.get(name)
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.shape != ((h, w, 3) if name == "last_normal" else (h, w)):
+            raise ValueError("temporal: %s has shape %r for a %d x %d frame" % (name, a.shape, w, h))
+        keep.append(a)
+        setattr(s, name, a.ctypes.data)
+    return s
+
+
 def _temporal_params(width, height, camera, prev_camera, depth_tolerance, normal_tolerance, alpha_min):
     p = _defaults(capi.TemporalParams, "crt_temporal_defaults", width, height, depth_tolerance=depth_tolerance, normal_tolerance=normal_tolerance,
                   alpha_min=alpha_min)
@@ -1828,7 +1898,7 @@ def _moment_planes(moments, h, w, keep):
 
 
 def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, want_rgb=True,
-             return_info=False, clamp=None, moments=None):
+             return_info=False, clamp=None, moments=None, dual=None):
     """Temporal accumulation with reprojection (crt_temporal, contract: include/crt.h).  cur: dict of the current frame -- color
     (H, W, 3), depth (H, W), optionally variance, normal (H, W, 3) and id (H, W) int32; prev: dict of the history -- color, history,
     depth, and variance / normal / id as cur has them -- or None for a first frame; camera, prev_camera: (eye, inv_view, fov_y) of the
@@ -1838,7 +1908,17 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
     with these values: the history is clamped to its neighbourhood in the current frame, and the info dict gains `clamped`).
     moments: None, or -- crt_temporal_moments -- the dict(m1=, m2=) of the history's moment planes (True for a first frame, where there is
     no history): the call then returns (rgb, color, variance, history, m1, m2), the info dict has `clamped` (0 without a clamp), and
-    m1 / m2 / history are what variance_estimate takes."""
+    m1 / m2 / history are what variance_estimate takes.
+    dual: None, or -- crt_temporal_dual -- True or a dict of radius / min_bounces: cur and prev then also hold path_depth and bounces
+    (H, W) and optionally last_normal (H, W, 3) as Render.run_view_aov_specular returns them, a mirror pixel also tries the history its
+    virtual image points at, and the info dict gains `clamped` (0 without a clamp), `virtual_tried` and `virtual_taken`.  Not with
+    moments (ValueError)."""
+    if dual is not None and moments is not None:
+        raise ValueError("temporal: dual and moments cannot be combined (crt_temporal_moments has no dual form)")
+    if dual is not None:
+        dual = _temporal_dual(dual)
+        cur, cur_spec = _split_specular(cur)
+        prev, prev_spec = _split_specular(prev)
     c = np.ascontiguousarray(cur["color"], dtype=np.float32)
     if c.ndim != 3 or c.shape[2] != 3:
         raise ValueError("temporal needs an (H, W, 3) colour image, got %r" % (c.shape,))
@@ -1865,7 +1945,15 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
                                                    C.byref(info)), "crt_temporal_moments")
         out = (rgb, color, var, hist, m1, m2)
         return out + (info.as_dict(),) if return_info else out
-    if clamp is None:
+    if dual is not None:
+        sc = _specular_struct(cur_spec, h, w, keep)
+        sp = _specular_struct(prev_spec, h, w, keep) if prev is not None else None
+        info = capi.TemporalDualInfo()
+        capi.check(capi.lib().crt_temporal_dual(device, C.byref(prm), C.byref(_temporal_clamp(clamp)) if clamp is not None else None, C.byref(dual),
+                                                C.byref(fc), C.byref(sc), C.byref(fp) if fp is not None else None,
+                                                C.byref(sp) if sp is not None else None, capi.ptr(color), capi.ptr(var), capi.ptr(hist), capi.ptr(rgb),
+                                                C.byref(info)), "crt_temporal_dual")
+    elif clamp is None:
         info = capi.TemporalInfo()
         capi.check(capi.lib().crt_temporal(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, capi.ptr(color), capi.ptr(var),
                                            capi.ptr(hist), capi.ptr(rgb), C.byref(info)), "crt_temporal")
@@ -1879,11 +1967,19 @@ def temporal(cur, camera, prev=None, prev_camera=None, depth_tolerance=None, nor
 
 def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_ptr, out_variance_ptr=None, out_rgb_ptr=None, prev_ptrs=None,
                     prev_camera=None, depth_tolerance=None, normal_tolerance=None, alpha_min=None, device=0, stream=None, want_info=True, clamp=None,
-                    moments=None):
+                    moments=None, dual=None):
     """Enqueues crt_temporal_device with everything in device memory: cur_ptrs / prev_ptrs = {name: raw device pointer} with the names of
     temporal()'s dicts (prev_ptrs None: no history).  With want_info the call synchronizes the stream and returns the crt_temporal_info
     dict, else None.  clamp: as temporal() (crt_temporal_clamped_device; the dict gains `clamped`).  moments: None, or
-    dict(out_m1=, out_m2=) of raw device pointers and, with a history, m1= and m2= of its planes (crt_temporal_moments_device)."""
+    dict(out_m1=, out_m2=) of raw device pointers and, with a history, m1= and m2= of its planes (crt_temporal_moments_device).
+    dual: as temporal() (crt_temporal_dual_device): cur_ptrs / prev_ptrs then also hold path_depth, bounces and optionally last_normal."""
+    if dual is not None and moments is not None:
+        raise ValueError("temporal_device: dual and moments cannot be combined (crt_temporal_moments has no dual form)")
+    if dual is not None:
+        dual = _temporal_dual(dual)
+        cur_ptrs, cur_spec = _split_specular(cur_ptrs)
+        prev_ptrs, prev_spec = _split_specular(prev_ptrs)
+
     def fill(struct, ptrs):
         for name, p in ptrs.items():
             if name not in {n for n, _ in struct._fields_}:
@@ -1906,7 +2002,16 @@ def temporal_device(width, height, camera, cur_ptrs, out_color_ptr, out_history_
                                                           _vp(moments.get("out_m2")), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
                    "crt_temporal_moments_device")
         return info.as_dict() if want_info else None
-    if clamp is None:
+    if dual is not None:
+        sc = capi.TemporalSpecularPlanes(**{k: int(v) if v else None for k, v in cur_spec.items()})
+        sp = capi.TemporalSpecularPlanes(**{k: int(v) if v else None for k, v in prev_spec.items()}) if prev_ptrs is not None else None
+        info = capi.TemporalDualInfo()
+        capi.check(capi.lib().crt_temporal_dual_device(device, C.byref(prm), C.byref(_temporal_clamp(clamp)) if clamp is not None else None,
+                                                       C.byref(dual), C.byref(fc), C.byref(sc), C.byref(fp) if fp is not None else None,
+                                                       C.byref(sp) if sp is not None else None, _vp(out_color_ptr), _vp(out_variance_ptr),
+                                                       _vp(out_history_ptr), _vp(out_rgb_ptr), _vp(stream), C.byref(info) if want_info else None),
+                   "crt_temporal_dual_device")
+    elif clamp is None:
         info = capi.TemporalInfo()
         capi.check(capi.lib().crt_temporal_device(device, C.byref(prm), C.byref(fc), C.byref(fp) if fp is not None else None, _vp(out_color_ptr),
                                                   _vp(out_variance_ptr), _vp(out_history_ptr), _vp(out_rgb_ptr), _vp(stream),

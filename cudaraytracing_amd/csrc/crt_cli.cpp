@@ -11,7 +11,8 @@
 //           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K] [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE] [--denoise-scales N]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
-//           [--temporal-variance samples|moments[,MIN_HISTORY]] [--aov-shading PREFIX] [--demodulate]
+//           [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]
+//           [--aov-shading PREFIX] [--demodulate]
 //           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]] [--gathered PREFIX[,NAME,...]]
 // --gathered PREFIX[,NAME,...] (only with --gpus / --devices) renders the frame with the buffers the image filters take gathered from all
 // ranks (crt_multi_render_buffers) and writes each float plane asked for as PREFIX.<NAME>.pfm (3 channels; depth and coverage: 1): NAME
@@ -32,6 +33,9 @@
 // / --denoise-sigma overrides) of the accumulated frame and its accumulated variance to --temporal-out instead.  --variance, --denoise and
 // --aov work on the last frame as rendered.  --temporal-clamp GAMMA[,RADIUS] clamps the history to mean +- GAMMA deviations of the
 // (2 RADIUS + 1)^2 current pixels around each pixel (crt_temporal_clamped; RADIUS 1 .. 3, default: crt_temporal_clamp_defaults').
+// --temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]] also reprojects what mirrors show through its virtual image (crt_temporal_dual:
+// each frame runs the specular AOV pass with MAX_BOUNCES, default crt_aov_specular_defaults'; MIN_BOUNCES > 0 and RADIUS 1 .. 3 default
+// to crt_temporal_dual_defaults'); it composes with --temporal-clamp, --temporal-denoise and --demodulate, not with --temporal-variance moments.
 // --temporal-variance moments[,MIN_HISTORY] measures the variance --temporal-denoise filters with from the temporal moments of each pixel
 // (crt_temporal_moments, crt_variance_estimate with its defaults, of_mean 1 and MIN_HISTORY) instead of carrying the per-sample variance
 // along: the frames are then rendered without CRT_FLAG_VARIANCE and --spp 1 works.  samples (the default) is the carried variance.
@@ -93,7 +97,7 @@ int main(int argc, char** argv)
                              "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm, reg joined by +)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
-                             "       [--temporal-variance samples|moments[,MIN_HISTORY]]\n"
+                             "       [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]\n"
                              "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n"
                              "       [--gathered PREFIX[,NAME,...]]  (with --gpus / --devices; NAME: mean, variance, half_a, half_b, albedo, normal, depth, coverage,\n"
                              "                                        emission, diffuse_albedo; default: mean, variance, albedo, normal, depth)\n", argv[0]);
@@ -129,6 +133,10 @@ int main(int argc, char** argv)
         tvar.of_mean = 1; // (the variance of the accumulated mean, which is what the filter is handed: docs/experiments.md)
         crt_temporal_clamp tclamp;
         crt_temporal_clamp_defaults(&tclamp);
+        bool temporal_specular = false;
+        crt_temporal_dual_params tdual;
+        crt_temporal_dual_defaults(&tdual);
+        uint32_t temporal_max_bounces = 0; // 0: crt_aov_specular_defaults'
         float temporal_step[3] = {0.0f, 0.0f, 0.0f};
         std::string temporal_out;
         unsigned upsample = 0, upsample_guide_spp = 0; // --upsample: the factor; 0 samples = the frame's
@@ -316,6 +324,30 @@ int main(int argc, char** argv)
                 }
                 if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-clamp needs GAMMA[,RADIUS]: GAMMA >= 0, RADIUS 1 .. 3");
             }
+            else if (a == "--temporal-specular") {
+                temporal_specular = temporal_option = true;
+                // (the value is optional: the next argument is one unless it is another option; "-1" is a value, and a bad one)
+                const char* nx = i + 1 < argc ? argv[i + 1] : nullptr;
+                if (nx && (nx[0] != '-' || (nx[1] >= '0' && nx[1] <= '9') || nx[1] == '.')) {
+                    const char* q = argv[++i];
+                    char* end = nullptr;
+                    tdual.min_bounces = std::strtof(q, &end);
+                    bool good = end != q && (*end == 0 || *end == ',') && tdual.min_bounces > 0.0f; // (false for NaN)
+                    if (good && *end == ',') {
+                        q = end + 1;
+                        const long r = std::strtol(q, &end, 10);
+                        good = end != q && (*end == 0 || *end == ',') && r >= 1 && r <= 3;
+                        tdual.radius = (uint32_t)r;
+                        if (good && *end == ',') {
+                            q = end + 1;
+                            const long b = std::strtol(q, &end, 10);
+                            good = end != q && *end == 0 && b >= 1 && b <= 8;
+                            temporal_max_bounces = (uint32_t)b;
+                        }
+                    }
+                    if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-specular takes [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]: MIN_BOUNCES > 0, RADIUS 1 .. 3, MAX_BOUNCES 1 .. 8");
+                }
+            }
             else if (a == "--temporal-variance") {
                 need(i, 1);
                 temporal_option = true;
@@ -412,7 +444,8 @@ int main(int argc, char** argv)
         if (upsample && (task.width % upsample || task.height % upsample))
             throw crt::Error(CRT_ERR_INVALID_ARG, "--upsample: FACTOR must divide --width and --height");
         if (adaptive && temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal accumulates uniformly sampled frames (not with --adaptive)");
-        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp and --temporal-variance need --temporal N");
+        if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp, --temporal-variance and --temporal-specular need --temporal N");
+        if (temporal_specular && temporal_moments) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-specular cannot be combined with --temporal-variance moments (crt_temporal_moments has no dual form)");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
@@ -484,11 +517,15 @@ int main(int argc, char** argv)
                 crt::get_inverse_view_matrix(task.eye_pos, task.lookat, task.up, inv_view);
                 render.set_seed(seed + (uint64_t)f);
                 if (temporal_moments) render.run_temporal_moments(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr, tvar);
+                else if (temporal_specular) render.run_temporal_specular(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr, tdual, temporal_max_bounces);
                 else render.run_temporal(task.eye_pos, inv_view, fov_y, tp, temporal_clamp ? &tclamp : nullptr);
                 std::printf("temporal frame %d: %llu of %llu pixels reprojected, device %.3f ms\n", f, (unsigned long long)render.last_temporal_info().reprojected,
                             (unsigned long long)task.width * task.height, render.last_temporal_info().total_ms);
                 if (temporal_clamp) std::printf("temporal frame %d: %llu histories clamped (gamma %g, radius %u)\n", f, (unsigned long long)render.last_temporal_clamped(),
                                                 (double)tclamp.gamma, tclamp.radius);
+                if (temporal_specular) std::printf("temporal frame %d: %llu pixels tried their virtual image, %llu took it (min_bounces %g, radius %u)\n", f,
+                                                   (unsigned long long)render.last_temporal_dual_info().virtual_tried,
+                                                   (unsigned long long)render.last_temporal_dual_info().virtual_taken, (double)tdual.min_bounces, tdual.radius);
                 if (temporal_moments) std::printf("temporal frame %d: variance of %llu pixels from their neighbourhood (history below %u), device %.3f ms\n", f,
                                                   (unsigned long long)render.last_variance_estimate_info().spatial, tvar.min_history,
                                                   render.last_variance_estimate_info().total_ms);

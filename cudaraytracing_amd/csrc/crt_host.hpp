@@ -293,6 +293,13 @@ public:
     // with another seed (set_seed).  frame and mean buffers hold the frame as rendered; one device only.  clamp != nullptr: the history is
     // clamped to its neighbourhood (crt_temporal_clamped); last_temporal_clamped() is then the count of pixels it moved
     void run_temporal(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp = nullptr);
+    // run_temporal with a second reprojection for what mirrors show (crt_temporal_dual; dual: crt_temporal_dual_defaults with overrides): each
+    // frame also runs run_aov_specular(max_bounces; 0: its default) -- not as the albedo guide --, its path_depth, bounces and last_normal
+    // are kept with the history, and last_temporal_dual_info() has the four counts (last_temporal_info() and last_temporal_clamped() are
+    // filled from it).  A history made by run_temporal is not continued, nor the other way round.
+    void run_temporal_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
+                               const crt_temporal_dual_params& dual, uint32_t max_bounces = 0);
+    const crt_temporal_dual_info& last_temporal_dual_info() const { return temporal_dual_info_; }
     // run_temporal with the variance measured instead of carried: the frame needs no CRT_FLAG_VARIANCE (one sample per pixel works), the
     // history also keeps the moment planes of crt_temporal_moments, and get_temporal_variance_buffer() -- what run_denoise_temporal
     // filters with -- is crt_variance_estimate of them with the frame's normal and depth (est: crt_variance_estimate_defaults with
@@ -376,6 +383,9 @@ private:
     uint64_t temporal_clamped_ = 0;
     std::vector<float> temporal_m1_, temporal_m2_;   // run_temporal_moments: the history's moment planes
     bool temporal_moments_ = false;                  // the history was made by run_temporal_moments
+    std::vector<float> temporal_path_depth_, temporal_bounces_, temporal_last_normal_;   // run_temporal_specular: the history's specular planes
+    bool temporal_specular_ = false;                 // the history was made by run_temporal_specular
+    crt_temporal_dual_info temporal_dual_info_{};
     crt_variance_estimate_info estimate_info_{};
     unsigned denoise_scales_ = 1;                    // set_denoise_scales
     // a single-frame filter with its settings: kind is SELECT_ATROUS .. SELECT_REG, and the settings of that kind are the ones that count
@@ -419,7 +429,7 @@ private:
     __attribute__((visibility("hidden"))) void one_device(const char* who, const char* noun) const;
     __attribute__((visibility("hidden"))) void need_guides(const std::string& who) const;
     template <class Blend> void temporal_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, bool moments,
-                                               const float* var, Blend blend);
+                                               const float* var, Blend blend, bool specular);
 };
 
 } // namespace crt

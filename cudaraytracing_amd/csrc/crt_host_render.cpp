@@ -482,12 +482,13 @@ void Render::run_denoise_select(const std::vector<int>& candidates, const crt_fi
     check(crt_filter_select(device_, &p, &in, denoised_mean_buffer_.data(), denoised_buffer_.data(), choice_buffer_.data(), nullptr, &select_info_), who);
 }
 
-// What run_temporal and run_temporal_moments share, around the library calls `blend` makes on the step.  Before them: the size and the
-// cameras, whether the history is continued (one with moment planes is not continued without them, nor the other way round), the frame
+// What run_temporal, run_temporal_specular and run_temporal_moments share, around the library calls `blend` makes on the step.  Before them:
+// the size and the cameras, whether the history is continued (one with moment planes or with specular planes is not continued without them,
+// nor the other way round; `specular`: the step keeps the planes run_aov_specular has just written with the history), the frame
 // with `var`, the variance of its mean (nullptr: none is carried), or its irradiance, and the history.  After them: a failure drops the
 // history; otherwise the step's buffers become it, with the frame's guides, camera and size.
 template <class Blend> void Render::temporal_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm,
-                                                   bool moments, const float* var, Blend blend)
+                                                   bool moments, const float* var, Blend blend, bool specular)
 {
     TemporalStep s{};
     s.p = prm;
@@ -495,7 +496,8 @@ template <class Blend> void Render::temporal_frame(const char* who, const float 
     std::memcpy(s.p.cur.eye, eye_pos, sizeof(s.p.cur.eye));
     std::memcpy(s.p.cur.inv_view, inv_view_mat, sizeof(s.p.cur.inv_view));
     s.p.cur.fov_y = fovY;
-    const bool have = temporal_valid_ && temporal_moments_ == moments && temporal_demodulated_ == demodulate_ && temporal_width_ == s.p.width && temporal_height_ == s.p.height;
+    const bool have = temporal_valid_ && temporal_moments_ == moments && temporal_specular_ == specular && temporal_demodulated_ == demodulate_ &&
+                      temporal_width_ == s.p.width && temporal_height_ == s.p.height;
     s.p.prev = have ? temporal_cam_ : s.p.cur;
     const size_t n = scene_->get_pixels();
     s.cur.color = mean_buffer_.data(); s.cur.variance = var; s.cur.depth = depth_buffer_.data(); s.cur.normal = normal_buffer_.data(); s.cur.id = material_buffer_.data();
@@ -521,6 +523,8 @@ template <class Blend> void Render::temporal_frame(const char* who, const float 
     temporal_color_.swap(s.color); temporal_variance_.swap(s.variance); temporal_history_.swap(s.history);
     if (moments) { temporal_m1_.swap(s.m1); temporal_m2_.swap(s.m2); }
     temporal_depth_ = depth_buffer_; temporal_normal_ = normal_buffer_; temporal_id_ = material_buffer_;
+    if (specular) { temporal_path_depth_ = path_depth_buffer_; temporal_bounces_ = bounces_buffer_; temporal_last_normal_ = last_normal_buffer_; }
+    temporal_specular_ = specular;
     temporal_cam_ = s.p.cur; temporal_width_ = s.p.width; temporal_height_ = s.p.height;
     temporal_valid_ = true;
     temporal_moments_ = moments;
@@ -542,7 +546,28 @@ void Render::run_temporal(const float eye_pos[3], const float inv_view_mat[9], f
         temporal_info_.total_ms = ci.total_ms; temporal_info_.reprojected = ci.reprojected;
         temporal_clamped_ = ci.clamped;
         return rc;
-    });
+    }, false);
+}
+
+void Render::run_temporal_specular(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
+                                   const crt_temporal_dual_params& dual, uint32_t max_bounces)
+{
+    const char* who = "Render::run_temporal_specular";
+    one_device(who, "temporal accumulation");
+    if (!(flags_ & CRT_FLAG_VARIANCE)) throw Error(CRT_ERR_INVALID_ARG, std::string(who) + " needs set_flags(CRT_FLAG_VARIANCE)");
+    run_view(eye_pos, inv_view_mat, fovY);
+    const float* var = variance();
+    run_aov(eye_pos, inv_view_mat, fovY);
+    run_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces, false);
+    temporal_frame(who, eye_pos, inv_view_mat, fovY, prm, false, var, [&](TemporalStep& s) {
+        const crt_temporal_specular_planes cur_spec = {path_depth_buffer_.data(), bounces_buffer_.data(), last_normal_buffer_.data()};
+        const crt_temporal_specular_planes prev_spec = {temporal_path_depth_.data(), temporal_bounces_.data(), temporal_last_normal_.data()};
+        const int rc = crt_temporal_dual(device_, &s.p, clamp, &dual, &s.cur, &cur_spec, s.prev, s.prev ? &prev_spec : nullptr, s.color.data(), s.variance.data(),
+                                         s.history.data(), s.rgb, &temporal_dual_info_);
+        temporal_info_.total_ms = temporal_dual_info_.total_ms; temporal_info_.reprojected = temporal_dual_info_.reprojected;
+        temporal_clamped_ = temporal_dual_info_.clamped;
+        return rc;
+    }, true);
 }
 
 void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_temporal_params& prm, const crt_temporal_clamp* clamp,
@@ -565,7 +590,7 @@ void Render::run_temporal_moments(const float eye_pos[3], const float inv_view_m
         crt_variance_estimate_inputs in{};
         in.m1 = s.m1.data(); in.m2 = s.m2.data(); in.history = s.history.data(); in.normal = normal_buffer_.data(); in.depth = depth_buffer_.data();
         return crt_variance_estimate(device_, &e, &in, s.variance.data(), &estimate_info_);
-    });
+    }, false);
 }
 
 void Render::run_denoise_temporal(const crt_denoise_params& prm)

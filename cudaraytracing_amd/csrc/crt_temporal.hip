@@ -16,51 +16,18 @@
 // colour: their taps ride on the predicates and the weight b of the colour's taps (24 B more per tap that counts), their blend on n, a
 // and k, and 24 B more are stored per pixel.  <false, false> and <true, false> are the kernels of the older entry points, instruction
 // for instruction what they were before the third parameter (the new fields of TpParams stand at its end).
+//
+// k_temporal_dual<CLAMP> (crt_temporal_dual) is a sibling, not a third parameter, so that those four keep their instructions: per pixel a
+// second candidate history, fetched through the virtual image of what a mirror pixel shows (path_depth along its ray), and the choice
+// between the two (crt_temporal.h has the arithmetic; tools/temporal_host_check.cpp runs that text on the host).  A wave in which no lane
+// tries the second candidate skips it as one scalar branch.  TpParams and history_channel live in crt_temporal.h.
 #include "crt_filter_host.h"
+#include "crt_temporal.h"
 
 #include <cstring>
 #include <string>
 
 namespace crtk {
-
-struct TpParams {
-    uint32_t width, height, tiles_x;
-    float eye[3], iv[9], scale, ar;           // current camera; scale / ar as camera_scale_ar (crt_render.hip)
-    float peye[3], piv[9], pscale;            // the camera the history was made with
-    float depth_tol, normal_tol2, alpha_min;  // normal_tol2 = normal_tolerance * normal_tolerance
-    const float* color; const float* variance; const float* depth; const float* normal; const int32_t* id;          // current frame
-    const float* pcolor; const float* pvariance; const float* phistory; const float* pdepth; const float* pnormal; const int32_t* pid;
-    float* out_mean;                          // out_color (write_color's names)
-    uint8_t* out_rgb;
-    float* out_variance;
-    float* out_history;
-    unsigned long long* count;                // [0] pixels that took the history, [1] of those: moved by the clamp (null: not counted)
-    int radius;                               // k_temporal<true, *> only: crt_temporal_clamp
-    float gamma;
-    const float* pm1; const float* pm2;       // k_temporal<*, true> only: the history's moment planes (null without a history)
-    float* out_m1; float* out_m2;
-};
-
-// One channel of the interpolated history, hc / ws; with CLAMP clamped into [mu - gamma sd, mu + gamma sd] of the neighbourhood sums
-// (`moved` is set if that changed it).  A NaN in the history or in the box fails both comparisons and the history passes through.
-template <bool CLAMP>
-__device__ __forceinline__ float history_channel(float hc, float ws, float s1, float s2, float cnt, float gamma, bool& moved)
-{
-    float h = hc / ws;
-    if (CLAMP) {
-        const float mu = s1 / cnt;
-        float e = s2 / cnt - mu * mu;
-        e = e < 0.0f ? 0.0f : e;
-        const float w = gamma * sqrt_f(e);
-        const float lo = mu - w, hi = mu + w;
-        const bool below = h < lo;
-        h = below ? lo : h;
-        const bool above = h > hi;
-        h = above ? hi : h;
-        moved |= below | above;
-    }
-    return h;
-}
 
 template <bool CLAMP, bool MOMENTS>
 __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
@@ -205,6 +172,41 @@ __global__ __launch_bounds__(256) void k_temporal(const TpParams P)
     }
 }
 
+// crt_temporal_dual: the launch shape and the counting of k_temporal, the per-pixel work of crt_temporal.h.  The ballot between the two
+// halves is held by every lane of the wave (lanes outside the image vote false), so its result is a scalar and the branch on it in
+// temporal_dual_finish a scalar branch.
+template <bool CLAMP>
+__global__ __launch_bounds__(256) void k_temporal_dual(const TpDualParams P)
+{
+    const uint32_t by = blockIdx.x / P.tiles_x, bx = blockIdx.x - by * P.tiles_x;
+    const int x = (int)(bx * 64u + (threadIdx.x & 63u)), y = (int)(by * 4u + (threadIdx.x >> 6));
+    const bool inside = x < (int)P.width && y < (int)P.height;
+    TpDualState st;
+    st.tries = false;
+    if (inside && P.pcolor) st = temporal_dual_begin(P, x, y);
+    const unsigned long long tmask = __ballot(st.tries);
+    const bool any_tries = tmask != 0ull;
+    TpDualFlags fl;
+    fl.took = false; fl.clamped = false; fl.tried = false; fl.took_V = false;
+    if (inside) fl = temporal_dual_finish<CLAMP>(P, x, y, st, any_tries);
+    if (!P.count) return;
+    // (a pixel can try V and take no history at all: the tried count comes before the wave leaves)
+    if (any_tries && (int)(threadIdx.x & 63u) == __ffsll((long long)tmask) - 1)
+        __hip_atomic_fetch_add(P.count + 2, (unsigned long long)__popcll(tmask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long mask = __ballot(fl.took);
+    if (mask == 0ull) return;
+    const bool first = (int)(threadIdx.x & 63u) == __ffsll((long long)mask) - 1;
+    if (first) __hip_atomic_fetch_add(P.count, (unsigned long long)__popcll(mask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (CLAMP) { // (a clamped pixel took the history: the wave is still here, and `first` is one of its lanes)
+        const unsigned long long cmask = __ballot(fl.clamped);
+        if (cmask != 0ull && first)
+            __hip_atomic_fetch_add(P.count + 1, (unsigned long long)__popcll(cmask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const unsigned long long vmask = __ballot(fl.took_V);
+    if (vmask != 0ull && first)
+        __hip_atomic_fetch_add(P.count + 3, (unsigned long long)__popcll(vmask), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 } // namespace crtk
 
 using namespace crtk;
@@ -253,6 +255,22 @@ int temporal_check(const char* who, const crt_temporal_params* prm, const crt_te
     return size_supported(w, prm->width, prm->height, 64, 4);
 }
 
+// crt_temporal_dual / _device: what they refuse beyond temporal_check, before any device call
+int temporal_dual_check(const std::string& w, const crt_temporal_dual_params* dual, const crt_temporal_history* prev, const crt_temporal_specular_planes* cur_spec,
+                        const crt_temporal_specular_planes* prev_spec)
+{
+    if (!dual || !cur_spec) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
+    if (dual->radius < 1 || dual->radius > 3) return fail(CRT_ERR_INVALID_ARG, w + ": the dual reprojection's radius must be 1 .. 3");
+    if (!(dual->min_bounces > 0.0f)) return fail(CRT_ERR_INVALID_ARG, w + ": min_bounces must be > 0 (+inf never tries)"); // (false for NaN)
+    if ((prev != nullptr) != (prev_spec != nullptr))
+        return fail(CRT_ERR_INVALID_ARG, w + ": a history and its specular planes go together");
+    if (!cur_spec->path_depth || !cur_spec->bounces || (prev_spec && (!prev_spec->path_depth || !prev_spec->bounces)))
+        return fail(CRT_ERR_INVALID_ARG, w + ": the specular planes need path_depth and bounces");
+    if (prev_spec && (cur_spec->last_normal != nullptr) != (prev_spec->last_normal != nullptr))
+        return fail(CRT_ERR_INVALID_ARG, w + ": last normals must be given in both frames or in neither");
+    return CRT_OK;
+}
+
 void set_camera(const crt_camera& cam, float* eye, float* iv, float& scale)
 {
     std::memcpy(eye, cam.eye, sizeof(cam.eye));
@@ -261,16 +279,12 @@ void set_camera(const crt_camera& cam, float* eye, float* iv, float& scale)
 }
 
 // what crt_temporal_info and crt_temporal_clamp_info are filled from
-struct TemporalCounts { float total_ms; unsigned long long reprojected, clamped; };
+struct TemporalCounts { float total_ms; unsigned long long reprojected, clamped, tried, taken; };
 
-int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
-                  const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st,
-                  TemporalCounts* info, const MomentArgs* mom = nullptr)
+// the fields of TpParams every form of the pass fills from its arguments (the block is zeroed before)
+void fill_params(TpParams& P, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur, const crt_temporal_history* prev,
+                 void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb)
 {
-    const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, mom);
-    if (rc != CRT_OK) return rc;
-    TpParams P;
-    std::memset(&P, 0, sizeof(P));
     P.width = prm->width; P.height = prm->height;
     P.tiles_x = (prm->width + 63) / 64;
     set_camera(prm->cur, P.eye, P.iv, P.scale);
@@ -288,6 +302,17 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
     P.out_mean = (float*)d_out_color; P.out_rgb = (uint8_t*)d_out_rgb;
     P.out_variance = (float*)d_out_variance; P.out_history = (float*)d_out_history;
     if (clamp) { P.radius = (int)clamp->radius; P.gamma = clamp->gamma; }
+}
+
+int temporal_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_frame* cur,
+                  const crt_temporal_history* prev, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb, hipStream_t st,
+                  TemporalCounts* info, const MomentArgs* mom = nullptr)
+{
+    const int rc = temporal_check(who, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, mom);
+    if (rc != CRT_OK) return rc;
+    TpParams P;
+    std::memset(&P, 0, sizeof(P));
+    fill_params(P, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, d_out_rgb);
     if (mom) {
         if (mom->prev) { P.pm1 = mom->prev->m1; P.pm2 = mom->prev->m2; }
         P.out_m1 = (float*)mom->out_m1; P.out_m2 = (float*)mom->out_m2;
@@ -306,7 +331,32 @@ int temporal_impl(const char* who, int device, const crt_temporal_params* prm, c
     return status;
 }
 
-// the two info structs, filled from the counts of a call that succeeded
+// crt_temporal_dual / _device on device buffers (the checks made)
+int temporal_dual_impl(const char* who, int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                       const crt_temporal_frame* cur, const crt_temporal_specular_planes* cur_spec, const crt_temporal_history* prev,
+                       const crt_temporal_specular_planes* prev_spec, void* d_out_color, void* d_out_variance, void* d_out_history, void* d_out_rgb,
+                       hipStream_t st, TemporalCounts* info)
+{
+    TpDualParams P;
+    std::memset(&P, 0, sizeof(P));
+    fill_params(P, prm, clamp, cur, prev, d_out_color, d_out_variance, d_out_history, d_out_rgb);
+    P.dual_radius = (int)dual->radius; P.min_bounces = dual->min_bounces;
+    if (prev) { // (without a history nothing reads the specular planes)
+        P.path_depth = cur_spec->path_depth; P.bounces = cur_spec->bounces; P.last_normal = cur_spec->last_normal;
+        P.ppath_depth = prev_spec->path_depth; P.pbounces = prev_spec->bounces; P.plast_normal = prev_spec->last_normal;
+    }
+    unsigned long long n[4] = {0, 0, 0, 0};
+    const int status = timed_launch(who, device, st, info, n, 4, [&](unsigned long long* d_count) {
+        P.count = d_count;
+        const dim3 grid(P.tiles_x * ((prm->height + 3) / 4));
+        if (clamp) hipLaunchKernelGGL((k_temporal_dual<true>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((k_temporal_dual<false>), grid, dim3(256), 0, st, P);
+    });
+    if (status == CRT_OK && info) { info->reprojected = n[0]; info->clamped = n[1]; info->tried = n[2]; info->taken = n[3]; }
+    return status;
+}
+
+// the info structs, filled from the counts of a call that succeeded
 void fill_info(crt_temporal_info* info, const TemporalCounts& n)
 {
     std::memset(info, 0, sizeof(*info));
@@ -316,6 +366,13 @@ void fill_info(crt_temporal_clamp_info* info, const TemporalCounts& n)
 {
     std::memset(info, 0, sizeof(*info));
     info->total_ms = n.total_ms; info->reprojected = n.reprojected; info->clamped = n.clamped;
+}
+
+void fill_info(crt_temporal_dual_info* info, const TemporalCounts& n)
+{
+    std::memset(info, 0, sizeof(*info));
+    info->total_ms = n.total_ms; info->reprojected = n.reprojected; info->clamped = n.clamped;
+    info->virtual_tried = n.tried; info->virtual_taken = n.taken;
 }
 
 template <class Info>
@@ -374,6 +431,17 @@ int temporal_host_form(const char* who, int device, const crt_temporal_params* p
     });
     if (rc == CRT_OK && info) fill_info(info, n);
     return rc;
+}
+
+// every refusal of crt_temporal_dual / _device, crt_temporal_clamped's first
+int temporal_dual_checks(const char* who, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                         const crt_temporal_frame* cur, const crt_temporal_specular_planes* cur_spec, const crt_temporal_history* prev,
+                         const crt_temporal_specular_planes* prev_spec, const void* out_color, const void* out_variance, const void* out_history)
+{
+    // (the dual arguments first: temporal_check ends with the sizes the launch cannot cover)
+    if (prm && cur)
+        if (const int rc = temporal_dual_check(who, dual, prev, cur_spec, prev_spec)) return rc;
+    return temporal_check(who, prm, clamp, cur, prev, out_color, out_variance, out_history, nullptr);
 }
 
 } // namespace
@@ -439,6 +507,71 @@ int crt_temporal_moments(int device, const crt_temporal_params* prm, const crt_t
 {
     const MomentArgs mom = {host_prev_moments, out_m1, out_m2};
     return temporal_host_form("crt_temporal_moments", device, prm, clamp, host_cur, host_prev, out_color, out_variance, out_history, out_rgb, info, &mom);
+}
+
+int crt_temporal_dual_defaults(crt_temporal_dual_params* dual)
+{
+    if (!dual) return fail(CRT_ERR_INVALID_ARG, "crt_temporal_dual_defaults: null argument");
+    std::memset(dual, 0, sizeof(*dual));
+    dual->radius = 1; dual->min_bounces = 0.5f; // tuned on nothing (include/crt.h)
+    return CRT_OK;
+}
+
+int crt_temporal_dual_device(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                             const crt_temporal_frame* dev_cur, const crt_temporal_specular_planes* dev_cur_spec, const crt_temporal_history* dev_prev,
+                             const crt_temporal_specular_planes* dev_prev_spec, void* d_out_color, void* d_out_variance, void* d_out_history,
+                             void* d_out_rgb, void* stream, crt_temporal_dual_info* info)
+{
+    const char* who = "crt_temporal_dual_device";
+    const int rc0 = temporal_dual_checks(who, prm, clamp, dual, dev_cur, dev_cur_spec, dev_prev, dev_prev_spec, d_out_color, d_out_variance, d_out_history);
+    if (rc0 != CRT_OK) return rc0;
+    TemporalCounts n{};
+    const int rc = temporal_dual_impl(who, device, prm, clamp, dual, dev_cur, dev_cur_spec, dev_prev, dev_prev_spec, d_out_color, d_out_variance,
+                                      d_out_history, d_out_rgb, (hipStream_t)stream, info ? &n : nullptr);
+    if (rc == CRT_OK && info) fill_info(info, n);
+    return rc;
+}
+
+int crt_temporal_dual(int device, const crt_temporal_params* prm, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                      const crt_temporal_frame* cur, const crt_temporal_specular_planes* cur_spec, const crt_temporal_history* prev,
+                      const crt_temporal_specular_planes* prev_spec, float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb,
+                      crt_temporal_dual_info* info)
+{
+    const char* who = "crt_temporal_dual";
+    const int rc0 = temporal_dual_checks(who, prm, clamp, dual, cur, cur_spec, prev, prev_spec, out_color, out_variance, out_history);
+    if (rc0 != CRT_OK) return rc0;
+    const uint64_t npix = (uint64_t)prm->width * prm->height;
+    TemporalCounts n{};
+    const int rc = host_form(who, device, [&](HostCopies& c) {
+        crt_temporal_frame dc{};
+        crt_temporal_history dp{};
+        crt_temporal_specular_planes dcs{}, dps{};
+        dc.color = c.in(cur->color, npix * 3);
+        dc.variance = c.in(cur->variance, npix * 3);
+        dc.depth = c.in(cur->depth, npix);
+        dc.normal = c.in(cur->normal, npix * 3);
+        dc.id = c.in(cur->id, npix);
+        dcs.path_depth = c.in(cur_spec->path_depth, npix);
+        dcs.bounces = c.in(cur_spec->bounces, npix);
+        dcs.last_normal = c.in(cur_spec->last_normal, npix * 3);
+        if (prev) {
+            dp.color = c.in(prev->color, npix * 3);
+            dp.variance = c.in(prev->variance, npix * 3);
+            dp.history = c.in(prev->history, npix);
+            dp.depth = c.in(prev->depth, npix);
+            dp.normal = c.in(prev->normal, npix * 3);
+            dp.id = c.in(prev->id, npix);
+            dps.path_depth = c.in(prev_spec->path_depth, npix);
+            dps.bounces = c.in(prev_spec->bounces, npix);
+            dps.last_normal = c.in(prev_spec->last_normal, npix * 3);
+        }
+        float *o_color = c.out(out_color, npix * 3), *o_hist = c.out(out_history, npix), *o_var = c.out(out_variance, npix * 3);
+        uint8_t* o_rgb = c.out(out_rgb, npix * 3);
+        return temporal_dual_impl(who, device, prm, clamp, dual, &dc, &dcs, prev ? &dp : nullptr, prev ? &dps : nullptr, o_color, o_var, o_hist, o_rgb,
+                                  nullptr, info ? &n : nullptr);
+    });
+    if (rc == CRT_OK && info) fill_info(info, n);
+    return rc;
 }
 
 } // extern "C"

@@ -899,6 +899,76 @@ int crt_temporal_moments_device(int device, const crt_temporal_params* params, c
                                 void* d_out_variance, void* d_out_history, void* d_out_m1, void* d_out_m2, void* d_out_rgb, void* hip_stream,
                                 crt_temporal_clamp_info* info);
 
+/* crt_temporal_clamped with two reprojections per mirror pixel (the "virtual motion" of real-time denoisers).  A pixel of a planar mirror
+ * shows two things at once: its own diffuse shading, which moves with the surface, and the mirrored scene, which moves rigidly with its
+ * VIRTUAL IMAGE -- the point at path_depth along the pixel's camera ray (crt_render_aov_specular: the length of the mirror chain).
+ * crt_temporal reprojects through the first hit alone, so a reflection that moves across a still plate is accumulated as if it stood
+ * still.  This call fetches a history through each point and blends the one that agrees with what the pixel shows now.
+ * Two more planes per frame, three with last_normal (cur_spec, prev_spec: crt_render_aov_specular's path_depth, bounces and last_normal as
+ * they are, row-major; path_depth, bounces 1 float per pixel, last_normal 3); the caller keeps the current frame's with the rest of the
+ * history, as it keeps depth, normal and id.  Everything is IEEE fp32, every * + - / and sqrt one operation (no FMA, no reciprocal
+ * multiply), sums left to right as written.  Per pixel p = (x, y) of a call with a history:
+ * 1. Surface candidate S: crt_temporal's definition, unchanged, up to and including the tap loop: hc_S, hv_S, hn_S, ws_S;
+ *      valid_S = ok && ws_S > 0.015625f
+ * 2. Virtual candidate V, tried iff  cur.bounces(p) >= min_bounces  (a NaN: false)  &&  cur.path_depth(p) > 0:
+ *      Pv = eye + d * cur.path_depth(p)           d: crt_temporal's pixel-centre ray
+ *      v, cx, cy, cz, tp, fx, fy, x0, wx, y0, wy: exactly as crt_temporal computes them from P, here from Pv
+ *      ok_V = cur.path_depth(p) > 0 && cz > 0 && fx > -1 && fx < W && fy > -1 && fy < H           (a NaN anywhere: false)
+ *      taps q = (x0 + i, y0 + j), j outer, i inner; a tap counts iff it is inside the image
+ *           && prev.bounces(q) >= min_bounces && prev.path_depth(q) > 0
+ *           && |prev.path_depth(q) - tp| <= depth_tolerance * tp
+ *           && (last normals given: crt_temporal's normal test on cur.last_normal(p) and prev.last_normal(q))
+ *           && (ids given: id(p) == prev.id(q)             -- the FIRST-hit id: the same mirror)
+ *      for a tap that counts, with the same b:  hc_V, hv_V, hn_V, ws_V as in crt_temporal
+ *      valid_V = ok_V && ws_V > 0.015625f
+ * 3. Choice, made only when valid_V; r = dual.radius:
+ *      s1 = +0.0f per channel; cnt = +0.0f;  taps t = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r inner, a tap outside the image
+ *      is skipped:  s1 = s1 + color(t);  cnt = cnt + 1            (crt_temporal_clamped's loop)        mu = s1 / cnt
+ *      for each valid candidate:  H = hc / ws per channel;  dx = H.x - mu.x, dy = H.y - mu.y, dz = H.z - mu.z;  e = dx*dx + (dy*dy + dz*dz)
+ *      V is taken iff  !valid_S || e_V < e_S        a tie keeps S; a NaN in either e makes the comparison false and keeps S; with S
+ *      invalid V is taken whatever e_V is
+ * 4. Blend: the chosen candidate's hc, hv, hn, ws go on through crt_temporal_clamped's text from `hc = hc / ws` to the end, the clamp (if
+ *    any: clamp may be NULL) on the chosen H with the clamp's own radius.  Neither candidate valid: the pixel resets.
+ * 5. Counts (info): virtual_tried = pixels for which V was tried (step 2's condition, whatever became of it), virtual_taken = pixels
+ *    that took V; reprojected (pixels that took either history) and clamped as in crt_temporal_clamped.
+ * Without a history every pixel resets, nothing is tried and no specular plane is read.  Two consequences:
+ *   - with min_bounces = +inf (finite bounces), or with cur.bounces zero everywhere, no pixel tries V and the call writes
+ *     crt_temporal_clamped's bits and counts (crt_temporal's with clamp == NULL);
+ *   - crt_temporal, crt_temporal_clamped and crt_temporal_moments are what they were: their kernels are not the ones of this call.
+ * The choice compares single interpolated colours with a mean of (2r+1)^2 noisy ones: at low sample counts it is itself noisy, and where
+ * both histories lie equally far from the mean it keeps S.  crt_temporal_dual_defaults (into a crt_temporal_dual_params) fills radius 1, min_bounces 0.5: tuned on
+ * nothing (docs/experiments.md, "Dual reprojection", has a small sweep; the defaults were set before it and stayed).
+ * CRT_ERR_INVALID_ARG, checked before any device call: everything crt_temporal_clamped refuses, a NULL dual, a radius outside 1 .. 3, a
+ * min_bounces that is not > 0 (NaN included; +inf is allowed), a NULL cur_spec, a missing path_depth or bounces, last_normal given in
+ * one frame only, prev_spec without prev or prev without prev_spec.
+ * Not done here: curved mirrors (the virtual point is then only an approximation: the reflection does not move rigidly), rough plates
+ * (path_depth follows mirror bounces only), refraction, the moments form (crt_temporal_moments with two candidates), splitting the
+ * radiance into a surface layer and a reflected layer with a history each, blending the two histories, tiled shards and crt_multi. */
+typedef struct {
+    uint32_t radius;       /* neighbourhood of the choice: (2*radius+1)^2 pixels of the CURRENT frame's colour; 1 .. 3 */
+    float    min_bounces;  /* share of reflected samples from which a pixel (and a tap) counts as a mirror; > 0, not NaN, +inf allowed (never tries) */
+} crt_temporal_dual_params;
+typedef struct { const float* path_depth; const float* bounces; const float* last_normal; } crt_temporal_specular_planes;
+    /* path_depth, bounces: 1 float per pixel, required; last_normal: 3 floats per pixel, in both frames or in neither */
+typedef struct {
+    float total_ms;          /* as crt_temporal_info */
+    uint64_t reprojected;    /* pixels that took a history, S or V */
+    uint64_t clamped;        /* as crt_temporal_clamp_info */
+    uint64_t virtual_tried;  /* pixels for which the virtual candidate was tried */
+    uint64_t virtual_taken;  /* pixels that took it */
+} crt_temporal_dual_info;
+int crt_temporal_dual_defaults(crt_temporal_dual_params* dual);
+/* host buffers, as crt_temporal_clamped; clamp may be NULL; host_prev_spec is NULL iff host_prev is NULL; info optional */
+int crt_temporal_dual(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                      const crt_temporal_frame* host_cur, const crt_temporal_specular_planes* host_cur_spec,
+                      const crt_temporal_history* host_prev /* may be NULL */, const crt_temporal_specular_planes* host_prev_spec,
+                      float* out_color, float* out_variance, float* out_history, uint8_t* out_rgb, crt_temporal_dual_info* info);
+/* device buffers on hip_stream, as crt_temporal_clamped_device (info != NULL: counts all four, synchronizes the stream) */
+int crt_temporal_dual_device(int device, const crt_temporal_params* params, const crt_temporal_clamp* clamp, const crt_temporal_dual_params* dual,
+                             const crt_temporal_frame* dev_cur, const crt_temporal_specular_planes* dev_cur_spec,
+                             const crt_temporal_history* dev_prev, const crt_temporal_specular_planes* dev_prev_spec, void* d_out_color,
+                             void* d_out_variance, void* d_out_history, void* d_out_rgb, void* hip_stream, crt_temporal_dual_info* info);
+
 /* Variance from temporal moments (SVGF, Schied et al. 2017, section 4.2): what crt_denoise_var takes as `variance`, estimated from what
  * each pixel was actually seen to do over its history instead of carried along with it.  An image operation: no scene handle, no scratch.
  * m1, m2, history: what crt_temporal_moments wrote (required); normal, depth: the current frame's AOVs (either may be NULL: its term is

@@ -54,6 +54,14 @@ static uint32_t fast_div(uint32_t n, uint32_t m, uint32_t sh)
 // crt_device.h: F3, f3
 struct F3 { float x, y, z; };
 static F3 f3(float x, float y, float z) { return F3{x, y, z}; }
+// crt_device.h: dot3, unit3 (there the quotient is built from a reciprocal and corrected to the rounded one: the same value)
+static float dot3(F3 a, F3 b) { return a.x * b.x + (a.y * b.y + a.z * b.z); }
+static F3 unit3(F3 a)
+{
+    const float z = dot3(a, a);
+    if (z > 0.0f) { const float s = sqrt_f(z); return f3(a.x / s, a.y / s, a.z / s); }
+    return a;
+}
 // crt_device.h: maxf_ref, minf_ref
 static float maxf_ref(float x, float y) { return x > y ? x : y; }
 static float minf_ref(float x, float y) { return x < y ? x : y; }

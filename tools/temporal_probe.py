@@ -32,10 +32,17 @@ under crt_denoise.
 clamp, accumulated as radiance and as irradiance; per combination the accumulated error and that of its variance-guided filter (with
 the filter's sigma_albedo and with +inf), which on irradiance runs before the accumulated frame is modulated.
 
+--specular: dual reprojection (crt_temporal_dual).  Cost: at each size, on veach-mis inputs (a third of the pixels try their virtual
+image) and on cornell-box inputs (none does), crt_temporal_dual_device and crt_temporal_clamped_device with the default clamp, and the
+two without a clamp, taking turns in one loop; medians, spreads, ratios, the shares of pixels that tried and took V.  Effect: the four
+sequences and a fifth, veach-mis with eye and lookat point moving sideways past the plates by (0, 0, 0.5) per frame: the accumulated
+error plain / with the default clamp / dual / dual + clamp, the same four under crt_denoise_var, the shares of tried and taken pixels
+in the last frame; then min_bounces 0.25 / 0.5 / 1 x radius 1 / 2 on the two moving veach-mis sequences.
+
 One JSON line per figure on stderr, one JSON document on stdout.
 
   python tools/temporal_probe.py [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5] [--spp 4] [--error-size 160x120] [--alpha-min 0.05,0.1,0.2]
-                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments] [--demodulate]
+                                 [--clamp] [--clamp-gammas 0.5,1,1.5,2,3,inf] [--moments] [--demodulate] [--specular]
 """
 import argparse
 import json
@@ -63,8 +70,14 @@ def camera_at(t, scene, f):
     return eye, crt.get_inverse_view_matrix(eye, t.lookat + s if with_lookat else t.lookat, t.up), crt.fov_to_radians(t.fov_y)
 
 
-def render_frame(r, cam, spp, seed, variance=True):
-    """(the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth}); variance=False: rendered without the flag (spp 1)"""
+SPECULAR_PLANES = ("path_depth", "bounces", "last_normal")
+# --specular: the fifth sequence, eye and lookat point moving by this per frame (the camera looks down -x: sideways past the plates)
+SIDEWAYS = (0.0, 0.0, 0.5)
+
+
+def render_frame(r, cam, spp, seed, variance=True, specular=False):
+    """(the dict crt.temporal takes as `cur`, rgb, {albedo, normal, depth}); variance=False: rendered without the flag (spp 1);
+    specular: the dict also has the three planes crt_temporal_dual takes"""
     r.set_spp(spp)
     r.seed = seed
     rgb = r.run_view(*cam, want_variance=variance).copy()
@@ -72,6 +85,8 @@ def render_frame(r, cam, spp, seed, variance=True):
     cur = {"color": r.mean_buffer.copy(), "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
     if variance:
         cur["variance"] = r.variance_buffer.copy()
+    if specular:
+        cur.update(r.run_view_aov_specular(*cam, want=SPECULAR_PLANES))
     return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
 
 
@@ -335,6 +350,93 @@ def demodulate_effect(a, out):
         r.free()
 
 
+def specular_cost(a, out):
+    for size in a.sizes.split(","):
+        w, h = (int(v) for v in size.split("x"))
+        for scene in ("veach-mis", "cornell-box"):
+            t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+            r = crt.Render(crt.Scene.from_task(t, w, h), a.spp, t.P_RR, t.light_sample_n)
+            cams = [camera_at(t, scene, f) for f in (0, 1)]
+            (c0, _, _), (c1, _, _) = (render_frame(r, cams[f], a.spp, f, specular=True) for f in (0, 1))
+            r.free()
+            prev = dict(c0, history=np.ones((h, w), dtype=F))
+            host = {"cur_" + k: v for k, v in c1.items()}
+            host.update({"prev_" + k: v for k, v in prev.items()})
+            dev = hipmem.DeviceBuffers({**host, "out_color": w * h * 12, "out_var": w * h * 12, "out_hist": w * h * 4, "out_rgb": w * h * 3})
+            ptrs = dev.ptrs
+
+            def call(clamp, dual):
+                keep = lambda f, pre: {k: ptrs[pre + k] for k in f if dual or k not in SPECULAR_PLANES}
+                return crt.temporal_device(w, h, cams[1], keep(c1, "cur_"), ptrs["out_color"], ptrs["out_hist"], out_variance_ptr=ptrs["out_var"],
+                                           out_rgb_ptr=ptrs["out_rgb"], prev_ptrs=keep(prev, "prev_"), prev_camera=cams[0], clamp=clamp, dual=dual)
+
+            kinds = (("clamped", True, None), ("dual_clamped", True, True), ("plain", None, None), ("dual", None, True))
+            ms, info = {k: [] for k, _, _ in kinds}, {}
+            for _ in range(a.warmup + a.calls):
+                for key, clamp, dual in kinds:
+                    info[key] = call(clamp, dual)
+                    ms[key].append(info[key]["total_ms"])
+            run = {"scene": scene, "width": w, "height": h}
+            for key, _, _ in kinds:
+                v = ms[key][a.warmup:]
+                run[key + "_ms_median_best_worst"] = [round(statistics.median(v), 4), round(min(v), 4), round(max(v), 4)]
+            med = {k: statistics.median(v[a.warmup:]) for k, v in ms.items()}
+            run.update({"dual_clamped_over_clamped": round(med["dual_clamped"] / med["clamped"], 4), "dual_over_plain": round(med["dual"] / med["plain"], 4),
+                        "tried_fraction": round(info["dual"]["virtual_tried"] / (w * h), 4), "taken_fraction": round(info["dual"]["virtual_taken"] / (w * h), 4),
+                        "reprojected_fraction": round(info["dual"]["reprojected"] / (w * h), 4)})
+            out["specular_cost"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+            dev.free()
+
+
+def specular_effect(a, out):
+    w, h = (int(v) for v in a.error_size.split("x"))
+    for scene in ("cornell-box", "veach-mis"):
+        t = crt.Task(os.path.join(ROOT, "scenes", scene, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 8, t.P_RR, t.light_sample_n)
+        for camera in ("static", "moving") + (("sideways",) if scene == "veach-mis" else ()):
+            if camera == "sideways":
+                cams = []
+                for f in range(8):
+                    s = F(f) * np.asarray(SIDEWAYS, dtype=F)
+                    cams.append((t.eye_pos + s, crt.get_inverse_view_matrix(t.eye_pos + s, t.lookat + s, t.up), crt.fov_to_radians(t.fov_y)))
+            else:
+                cams = [camera_at(t, scene, f if camera == "moving" else 0) for f in range(8)]
+            frames = [render_frame(r, cams[f], 8, 100 + f, specular=True) + (cams[f],) for f in range(8)]
+            r.set_spp(256)
+            r.seed = 7
+            ref = r.run_view(*cams[-1]).copy()
+            cur, noisy_rgb, g, _ = frames[-1]
+            run = {"scene": scene, "camera": camera, "width": w, "height": h, "mse_last_frame": round(mse(noisy_rgb, ref), 1),
+                   "mse_last_frame_denoise_var": round(mse(crt.denoise_var(cur["color"], cur["variance"], **g)[0], ref), 1)}
+
+            def accumulate(clamp, dual):
+                prev = pcam = None
+                for cur, _, g, cam in frames:
+                    c = cur if dual is not None else {k: v for k, v in cur.items() if k not in SPECULAR_PLANES}
+                    rgb, color, var, hist, info = crt.temporal(c, cam, prev=prev, prev_camera=pcam, return_info=True, clamp=clamp, dual=dual)
+                    prev, pcam = dict(c, color=color, variance=var, history=hist), cam
+                return round(mse(rgb, ref), 1), round(mse(crt.denoise_var(color, var, **g)[0], ref), 1), info
+
+            for tag, clamp, dual in (("plain", None, None), ("clamp", True, None), ("dual", None, True), ("dual_clamp", True, True)):
+                run[tag + "_mse_accumulated"], run[tag + "_mse_accumulated_denoise_var"], info = accumulate(clamp, dual)
+                if dual:
+                    run[tag + "_tried_taken_last"] = [round(info["virtual_tried"] / (w * h), 4), round(info["virtual_taken"] / (w * h), 4)]
+            out["specular_effect"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+            if scene != "veach-mis" or camera == "static":
+                continue
+            for min_bounces in (0.25, 0.5, 1.0):
+                for radius in (1, 2):
+                    row = {"scene": scene, "camera": camera, "min_bounces": min_bounces, "radius": radius}
+                    for tag, clamp in (("dual", None), ("dual_clamp", True)):
+                        row[tag + "_mse_accumulated"], row[tag + "_mse_accumulated_denoise_var"], info = accumulate(clamp, {"radius": radius, "min_bounces": min_bounces})
+                        row[tag + "_tried_taken_last"] = [round(info["virtual_tried"] / (w * h), 4), round(info["virtual_taken"] / (w * h), 4)]
+                    out["specular_sweep"].append(row)
+                    print(json.dumps(row), file=sys.stderr, flush=True)
+        r.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="800x600,3840x2160")
@@ -347,6 +449,7 @@ def main():
     ap.add_argument("--clamp-gammas", default="0.5,1,1.5,2,3,inf")
     ap.add_argument("--moments", action="store_true")
     ap.add_argument("--demodulate", action="store_true", help="the sequences accumulated as irradiance beside radiance")
+    ap.add_argument("--specular", action="store_true", help="dual reprojection (crt_temporal_dual): its cost beside the clamped call, and the sequences with it")
     ap.add_argument("--skip-cost", action="store_true")
     ap.add_argument("--skip-effect", action="store_true")
     a = ap.parse_args()
@@ -354,6 +457,14 @@ def main():
         raise SystemExit("temporal_probe: no HIP device")
     out = {"calls": a.calls, "warmup": a.warmup, "spp": a.spp, "cost": [], "effect": [], "clamp_cost": [], "clamp_effect": [], "moments_cost": [],
            "moments_effect": []}
+    if a.specular:                                           # (its own tables only)
+        out.update({"specular_cost": [], "specular_effect": [], "specular_sweep": []})
+        if not a.skip_cost:
+            specular_cost(a, out)
+        if not a.skip_effect:
+            specular_effect(a, out)
+        print(json.dumps(out), flush=True)
+        return
     if a.demodulate:                                         # (its own table only)
         out["demodulate_effect"] = []
         demodulate_effect(a, out)
