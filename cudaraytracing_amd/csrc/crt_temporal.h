@@ -1,11 +1,22 @@
-// cudaraytracing_amd/csrc/crt_temporal.h -- the parameter blocks of the temporal pass and the per-pixel arithmetic of its dual-reprojection
-// form (crt_temporal_dual, contract: include/crt.h; kernels and host code: crt_temporal.hip).  A pixel of a planar mirror shows two things:
-// its own shading, which moves with the surface, and the mirrored scene, which moves with its virtual image -- the point at path_depth
-// along the pixel's camera ray.  The pass fetches a history through each (candidate S: crt_temporal's taps; candidate V: the same taps
-// keyed on the specular planes) and blends the one that lies nearer the mean of the current frame's colours around the pixel.
-//   temporal_dual_begin    the pixel's ray, candidate S, and whether the pixel tries V
-//   temporal_dual_finish   candidate V and the choice (behind the caller's wave-uniform `any lane tries`), the clamp, the blend, the outputs
-// Between the two the kernel holds one ballot; a caller without waves passes the pixel's own `tries`.
+// cudaraytracing_amd/csrc/crt_temporal.h -- the parameter blocks of the temporal pass and its whole per-pixel arithmetic (crt_temporal,
+// crt_temporal_clamped, crt_temporal_moments, crt_temporal_dual; contract: include/crt.h; kernels and host code: crt_temporal.hip).  The
+// pass is one operation with optional parts: reproject the pixel, gather four taps of the history, optionally fetch and choose a second
+// candidate, optionally clamp, blend.  Every expression of the contract stands here once:
+//   temporal_ray, temporal_project   the pixel's camera ray, and a point along it seen from the previous camera
+//   temporal_gather                  the tap loop: surface taps, virtual taps, and the moment planes riding on either
+//   temporal_box, history_channel    the neighbourhood sums and the clamp
+//   temporal_reset, temporal_blend, temporal_write   what a pixel writes without a history, with one, and the stores
+// and the two forms of a pixel are made of them:
+//   temporal_single<CLAMP, MOMENTS>  one candidate (k_temporal)
+//   temporal_dual_begin              the pixel's ray, candidate S, and whether the pixel tries V
+//   temporal_dual_finish<CLAMP>      candidate V and the choice (behind the caller's wave-uniform `any lane tries`), then the same blend
+// The dual form: a pixel of a planar mirror shows two things, its own shading, which moves with the surface, and the mirrored scene, which
+// moves with its virtual image -- the point at path_depth along the pixel's camera ray.  The pass fetches a history through each
+// (candidate S: crt_temporal's taps; candidate V: the same taps keyed on the specular planes) and blends the one that lies nearer the mean
+// of the current frame's colours around the pixel.  Between begin and finish k_temporal_dual holds one ballot; a caller without waves
+// passes the pixel's own `tries`.
+// p is a pixel's index and p3 = 3 p its offset in a plane of three floats: the forms make the product once and hand it on, because a
+// function that forms it itself is compiled to a multiply of its own that the inlined kernel then keeps (docs/experiments.md).
 // Like crt_select.h this file includes nothing, so that tools/temporal_host_check.cpp can compile this very text for the host behind
 // stand-ins for what it takes from outside: F3 / f3 / dot3 / unit3 (crt_device.h), sqrt_f (crt_detmath.h), write_color (crt_stages.h), floorf / fabsf.
 #ifndef CRT_TEMPORAL_H
@@ -25,9 +36,9 @@ struct TpParams {
     float* out_variance;
     float* out_history;
     unsigned long long* count;                // [0] pixels that took the history, [1] of those: moved by the clamp (null: not counted)
-    int radius;                               // k_temporal<true, *> only: crt_temporal_clamp
+    int radius;                               // CLAMP only: crt_temporal_clamp
     float gamma;
-    const float* pm1; const float* pm2;       // k_temporal<*, true> only: the history's moment planes (null without a history)
+    const float* pm1; const float* pm2;       // MOMENTS only: the history's moment planes (null without a history)
     float* out_m1; float* out_m2;
 };
 
@@ -45,8 +56,12 @@ struct TpDualParams : TpParams {
 struct TpProj { float tp, fx, fy; bool ok; };
 // The interpolated history of one candidate, before the division by ws
 struct TpTaps { F3 hc, hv; float hn, ws; };
+// The history's moment planes over the same taps (crt_temporal_moments' sums of m1 and m2)
+struct TpMoments { F3 h1, h2; };
 // The sums of the current colour around a pixel (crt_temporal_clamped's s1, s2, cnt)
 struct TpBox { F3 s1, s2; float cnt; };
+// A pixel's current colour and variance, and what it writes: the reset's values until temporal_blend replaces them
+struct TpPixel { F3 c, v, oc, ov, o1, o2; float oh; };
 // What temporal_dual_begin hands to temporal_dual_finish
 struct TpDualState {
     F3 d;          // the pixel-centre camera ray
@@ -54,8 +69,8 @@ struct TpDualState {
     bool valid_S;  // ok && ws_S > 0.015625f
     bool tries;    // a history is given, bounces(p) >= min_bounces and path_depth(p) > 0
 };
-// What a pixel did, for the counts
-struct TpDualFlags { bool took, clamped, tried, took_V; };
+// What a pixel did, for the counts (tried, took_V: the dual form's)
+struct TpFlags { bool took, clamped, tried, took_V; };
 
 // the pixel-centre ray of the current camera (camera_dir without the jitter)
 __device__ __forceinline__ F3 temporal_ray(const TpParams& P, const int x, const int y)
@@ -87,27 +102,27 @@ __device__ __forceinline__ TpProj temporal_project(const TpParams& P, const F3 d
     return r;
 }
 
-// The four bilinear taps of a projection that is ok.  VIRTUAL false: crt_temporal's tap test (first-hit depth, normal, id).  VIRTUAL true:
-// the tap must itself be a mirror pixel (bounces >= min_bounces, path_depth > 0), its path_depth must agree with tp, its last normal
-// (if given) with the pixel's, and its first-hit id (if given) must be the pixel's: the same mirror.  Every tap is tested against the
-// image before anything is read at it.
-template <bool VIRTUAL>
-__device__ __forceinline__ TpTaps temporal_gather(const TpDualParams& P, const size_t p, const TpProj& pr)
+// The four bilinear taps of a projection that is ok.  VIRTUAL false: crt_temporal's tap test (first-hit depth, normal, id).  VIRTUAL true
+// (PB: TpDualParams): the tap must itself be a mirror pixel (bounces >= min_bounces, path_depth > 0), its path_depth must agree with tp,
+// its last normal (if given) with the pixel's, and its first-hit id (if given) must be the pixel's: the same mirror.  MOMENTS: m takes the
+// moment planes on the predicates and the weight of the colour's taps.  Every tap is tested against the image before anything is read at it.
+template <bool VIRTUAL, bool MOMENTS, class PB>
+__device__ __forceinline__ TpTaps temporal_gather(const PB& P, const size_t p, const size_t p3, const TpProj& pr, TpMoments& m)
 {
     const int W = (int)P.width, H = (int)P.height;
-    TpTaps t;
-    t.hc = f3(0.0f, 0.0f, 0.0f); t.hv = f3(0.0f, 0.0f, 0.0f);
-    t.hn = 0.0f; t.ws = 0.0f;
     const float flx = floorf(pr.fx), fly = floorf(pr.fy);
     const float wx = pr.fx - flx, wy = pr.fy - fly;
     const int x0 = (int)flx, y0 = (int)fly; // -1 .. W - 1, -1 .. H - 1
     const float tol = P.depth_tol * pr.tp;
-    const float* const cn = VIRTUAL ? P.last_normal : P.normal;
-    const float* const pn = VIRTUAL ? P.plast_normal : P.pnormal;
-    const float* const pdist = VIRTUAL ? P.ppath_depth : P.pdepth;
+    const float* cn; const float* pn; const float* pdist;
+    if constexpr (VIRTUAL) { cn = P.last_normal; pn = P.plast_normal; pdist = P.ppath_depth; }
+    else { cn = P.normal; pn = P.pnormal; pdist = P.pdepth; }
     F3 n = f3(0.0f, 0.0f, 0.0f);
-    if (cn) n = f3(cn[p * 3], cn[p * 3 + 1], cn[p * 3 + 2]);
+    if (cn) n = f3(cn[p3], cn[p3 + 1], cn[p3 + 2]);
     const int32_t idp = P.id ? P.id[p] : 0;
+    TpTaps t;
+    t.hc = f3(0.0f, 0.0f, 0.0f); t.hv = f3(0.0f, 0.0f, 0.0f); m.h1 = f3(0.0f, 0.0f, 0.0f); m.h2 = f3(0.0f, 0.0f, 0.0f);
+    t.hn = 0.0f; t.ws = 0.0f;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
         const int qy = y0 + j;
@@ -117,7 +132,8 @@ __device__ __forceinline__ TpTaps temporal_gather(const TpDualParams& P, const s
             const int qx = x0 + i;
             if (qx < 0 || qx >= W) continue;
             const size_t q = (size_t)qy * P.width + (size_t)qx;
-            if (VIRTUAL && !(P.pbounces[q] >= P.min_bounces)) continue;
+            if constexpr (VIRTUAL)
+                if (!(P.pbounces[q] >= P.min_bounces)) continue;
             const float pd = pdist[q];
             if (!(pd > 0.0f)) continue;
             if (!(fabsf(pd - pr.tp) <= tol)) continue;
@@ -135,6 +151,14 @@ __device__ __forceinline__ TpTaps temporal_gather(const TpDualParams& P, const s
                 t.hv.y = t.hv.y + P.pvariance[q * 3 + 1] * b;
                 t.hv.z = t.hv.z + P.pvariance[q * 3 + 2] * b;
             }
+            if (MOMENTS) {
+                m.h1.x = m.h1.x + P.pm1[q * 3] * b;
+                m.h1.y = m.h1.y + P.pm1[q * 3 + 1] * b;
+                m.h1.z = m.h1.z + P.pm1[q * 3 + 2] * b;
+                m.h2.x = m.h2.x + P.pm2[q * 3] * b;
+                m.h2.y = m.h2.y + P.pm2[q * 3 + 1] * b;
+                m.h2.z = m.h2.z + P.pm2[q * 3 + 2] * b;
+            }
             t.hn = t.hn + P.phistory[q] * b;
             t.ws = t.ws + b;
         }
@@ -142,13 +166,20 @@ __device__ __forceinline__ TpTaps temporal_gather(const TpDualParams& P, const s
     return t;
 }
 
+// no sums yet
+__device__ __forceinline__ TpBox temporal_no_box()
+{
+    TpBox b;
+    b.s1 = f3(0.0f, 0.0f, 0.0f); b.s2 = f3(0.0f, 0.0f, 0.0f);
+    b.cnt = 0.0f;
+    return b;
+}
+
 // sums of the current colour and its squares around (x, y); every tap is tested against the image, so every read is inside it
 __device__ __forceinline__ TpBox temporal_box(const TpParams& P, const int x, const int y, const int radius)
 {
     const int W = (int)P.width, H = (int)P.height;
-    TpBox b;
-    b.s1 = f3(0.0f, 0.0f, 0.0f); b.s2 = f3(0.0f, 0.0f, 0.0f);
-    b.cnt = 0.0f;
+    TpBox b = temporal_no_box();
     for (int dy = -radius; dy <= radius; dy++) {
         const int ty = y + dy;
         if (ty < 0 || ty >= H) continue;
@@ -200,16 +231,97 @@ __device__ __forceinline__ float history_channel(float hc, float ws, float s1, f
     return h;
 }
 
+// The current colour and variance of the pixel at p3, and the outputs of a pixel that takes no history
+template <bool MOMENTS>
+__device__ __forceinline__ TpPixel temporal_reset(const TpParams& P, const size_t p3)
+{
+    TpPixel o;
+    o.c = f3(P.color[p3], P.color[p3 + 1], P.color[p3 + 2]);
+    o.v = f3(0.0f, 0.0f, 0.0f);
+    if (P.variance) o.v = f3(P.variance[p3], P.variance[p3 + 1], P.variance[p3 + 2]);
+    o.oc = o.c; o.ov = o.v;
+    o.oh = 1.0f;
+    o.o1 = o.c; o.o2 = f3(0.0f, 0.0f, 0.0f);
+    if (MOMENTS) o.o2 = f3(o.c.x * o.c.x, o.c.y * o.c.y, o.c.z * o.c.z);
+    return o;
+}
+
+// The blend of pixel (x, y) with the history T it takes (T.ws > 0.015625f).  CLAMP: have_box says that box holds the sums of the clamp's
+// radius already, else they are summed here; `clamped` is set if the clamp moved a channel.  MOMENTS: m's planes, never clamped --
+// m1 is the running mean of what the pixel was seen to show.
+template <bool CLAMP, bool MOMENTS>
+__device__ __forceinline__ void temporal_blend(const TpParams& P, const int x, const int y, const TpTaps& T, const TpMoments& m, TpBox box, const bool have_box,
+                                               TpPixel& o, bool& clamped)
+{
+    const float hn = T.hn / T.ws;
+    o.oh = hn + 1;
+    float a = 1 / o.oh;
+    a = a < P.alpha_min ? P.alpha_min : a;
+    const float k = 1 - a;
+    if (CLAMP) {
+        if (!have_box) box = temporal_box(P, x, y, P.radius);
+    }
+    o.oc = f3(history_channel<CLAMP>(T.hc.x, T.ws, box.s1.x, box.s2.x, box.cnt, P.gamma, clamped) * k + o.c.x * a,
+              history_channel<CLAMP>(T.hc.y, T.ws, box.s1.y, box.s2.y, box.cnt, P.gamma, clamped) * k + o.c.y * a,
+              history_channel<CLAMP>(T.hc.z, T.ws, box.s1.z, box.s2.z, box.cnt, P.gamma, clamped) * k + o.c.z * a);
+    if (P.variance) {
+        const float kk = k * k, aa = a * a;
+        o.ov = f3((T.hv.x / T.ws) * kk + o.v.x * aa, (T.hv.y / T.ws) * kk + o.v.y * aa, (T.hv.z / T.ws) * kk + o.v.z * aa);
+    }
+    if (MOMENTS) {
+        o.o1 = f3((m.h1.x / T.ws) * k + o.c.x * a, (m.h1.y / T.ws) * k + o.c.y * a, (m.h1.z / T.ws) * k + o.c.z * a);
+        o.o2 = f3((m.h2.x / T.ws) * k + o.o2.x * a, (m.h2.y / T.ws) * k + o.o2.y * a, (m.h2.z / T.ws) * k + o.o2.z * a);
+    }
+}
+
+// the pixel's stores
+template <bool MOMENTS>
+__device__ __forceinline__ void temporal_write(const TpParams& P, const size_t p, const size_t p3, const TpPixel& o)
+{
+    write_color(P, p, true, o.oc);
+    if (P.out_variance) { P.out_variance[p3] = o.ov.x; P.out_variance[p3 + 1] = o.ov.y; P.out_variance[p3 + 2] = o.ov.z; }
+    P.out_history[p] = o.oh;
+    if (MOMENTS) {
+        P.out_m1[p3] = o.o1.x; P.out_m1[p3 + 1] = o.o1.y; P.out_m1[p3 + 2] = o.o1.z;
+        P.out_m2[p3] = o.o2.x; P.out_m2[p3 + 1] = o.o2.y; P.out_m2[p3 + 2] = o.o2.z;
+    }
+}
+
+// Pixel (x, y), inside the image: the whole single-candidate form.  The neighbourhood sums run INSIDE the branch of the pixels that take
+// the history, not before it: see docs/experiments.md.
+template <bool CLAMP, bool MOMENTS>
+__device__ __forceinline__ TpFlags temporal_single(const TpParams& P, const int x, const int y)
+{
+    const size_t p = (size_t)y * P.width + (size_t)x, p3 = p * 3;
+    TpFlags fl = {};
+    TpPixel o = temporal_reset<MOMENTS>(P, p3);
+    if (P.pcolor) {
+        const float dp = P.depth[p];
+        const TpProj pr = temporal_project(P, temporal_ray(P, x, y), dp);
+        if (pr.ok) {
+            TpMoments m;
+            const TpTaps T = temporal_gather<false, MOMENTS>(P, p, p3, pr, m);
+            if (T.ws > 0.015625f) {
+                fl.took = true;
+                temporal_blend<CLAMP, MOMENTS>(P, x, y, T, m, temporal_no_box(), false, o, fl.clamped);
+            }
+        }
+    }
+    temporal_write<MOMENTS>(P, p, p3, o);
+    return fl;
+}
+
 // Pixel (x, y), inside the image, of a call with a history: its ray, candidate S, whether it tries V
 __device__ __forceinline__ TpDualState temporal_dual_begin(const TpDualParams& P, const int x, const int y)
 {
-    const size_t p = (size_t)y * P.width + (size_t)x;
+    const size_t p = (size_t)y * P.width + (size_t)x, p3 = p * 3;
     TpDualState st;
     st.d = temporal_ray(P, x, y);
     st.S.hc = f3(0.0f, 0.0f, 0.0f); st.S.hv = f3(0.0f, 0.0f, 0.0f);
     st.S.hn = 0.0f; st.S.ws = 0.0f;
     const TpProj pr = temporal_project(P, st.d, P.depth[p]);
-    if (pr.ok) st.S = temporal_gather<false>(P, p, pr);
+    TpMoments none;
+    if (pr.ok) st.S = temporal_gather<false, false>(P, p, p3, pr, none);
     st.valid_S = pr.ok && st.S.ws > 0.015625f;
     st.tries = P.bounces[p] >= P.min_bounces && P.path_depth[p] > 0.0f; // (false for NaN)
     return st;
@@ -218,29 +330,24 @@ __device__ __forceinline__ TpDualState temporal_dual_begin(const TpDualParams& P
 // Pixel (x, y), inside the image: everything after the ballot.  any_tries: some lane of the pixel's wave tries V (wave-uniform; a wave in
 // which none does skips the second gather and the choice as one branch).  st is read only in a call with a history.
 template <bool CLAMP>
-__device__ __forceinline__ TpDualFlags temporal_dual_finish(const TpDualParams& P, const int x, const int y, const TpDualState& st, const bool any_tries)
+__device__ __forceinline__ TpFlags temporal_dual_finish(const TpDualParams& P, const int x, const int y, const TpDualState& st, const bool any_tries)
 {
-    const size_t p = (size_t)y * P.width + (size_t)x;
-    TpDualFlags fl;
-    fl.took = false; fl.clamped = false; fl.tried = false; fl.took_V = false;
-    const F3 c = f3(P.color[p * 3], P.color[p * 3 + 1], P.color[p * 3 + 2]);
-    F3 v = f3(0.0f, 0.0f, 0.0f);
-    if (P.variance) v = f3(P.variance[p * 3], P.variance[p * 3 + 1], P.variance[p * 3 + 2]);
-    F3 oc = c, ov = v;
-    float oh = 1.0f;
+    const size_t p = (size_t)y * P.width + (size_t)x, p3 = p * 3;
+    TpFlags fl = {};
+    TpPixel o = temporal_reset<false>(P, p3);
     if (P.pcolor) {
         TpTaps T = st.S;
         bool valid = st.valid_S;
-        TpBox box;
-        box.s1 = f3(0.0f, 0.0f, 0.0f); box.s2 = f3(0.0f, 0.0f, 0.0f);
-        box.cnt = 0.0f;
+        TpMoments none;
+        none.h1 = f3(0.0f, 0.0f, 0.0f); none.h2 = f3(0.0f, 0.0f, 0.0f);
+        TpBox box = temporal_no_box();
         int box_radius = 0; // the radius `box` holds the sums of (0: none yet)
         if (any_tries) {
             if (st.tries) {
                 fl.tried = true;
                 const TpProj pr = temporal_project(P, st.d, P.path_depth[p]);
                 if (pr.ok) {
-                    const TpTaps V = temporal_gather<true>(P, p, pr);
+                    const TpTaps V = temporal_gather<true, false>(P, p, p3, pr, none);
                     if (V.ws > 0.015625f) {
                         box = temporal_box(P, x, y, P.dual_radius);
                         box_radius = P.dual_radius;
@@ -251,26 +358,10 @@ __device__ __forceinline__ TpDualFlags temporal_dual_finish(const TpDualParams& 
         }
         if (valid) {
             fl.took = true;
-            const float hn = T.hn / T.ws;
-            oh = hn + 1;
-            float a = 1 / oh;
-            a = a < P.alpha_min ? P.alpha_min : a;
-            const float k = 1 - a;
-            if (CLAMP) {
-                if (box_radius != P.radius) box = temporal_box(P, x, y, P.radius); // (the same sums, bit for bit, when the radii agree)
-            }
-            oc = f3(history_channel<CLAMP>(T.hc.x, T.ws, box.s1.x, box.s2.x, box.cnt, P.gamma, fl.clamped) * k + c.x * a,
-                    history_channel<CLAMP>(T.hc.y, T.ws, box.s1.y, box.s2.y, box.cnt, P.gamma, fl.clamped) * k + c.y * a,
-                    history_channel<CLAMP>(T.hc.z, T.ws, box.s1.z, box.s2.z, box.cnt, P.gamma, fl.clamped) * k + c.z * a);
-            if (P.variance) {
-                const float kk = k * k, aa = a * a;
-                ov = f3((T.hv.x / T.ws) * kk + v.x * aa, (T.hv.y / T.ws) * kk + v.y * aa, (T.hv.z / T.ws) * kk + v.z * aa);
-            }
+            temporal_blend<CLAMP, false>(P, x, y, T, none, box, box_radius == P.radius, o, fl.clamped); // (the same sums, bit for bit, when the radii agree)
         }
     }
-    write_color(P, p, true, oc);
-    if (P.out_variance) { P.out_variance[p * 3] = ov.x; P.out_variance[p * 3 + 1] = ov.y; P.out_variance[p * 3 + 2] = ov.z; }
-    P.out_history[p] = oh;
+    temporal_write<false>(P, p, p3, o);
     return fl;
 }
 

@@ -278,8 +278,8 @@ def host_check_run(tmp_path_factory):
 
 
 def test_kernel_text_on_the_host_passes_its_checks(host_check_run):
-    """csrc/crt_temporal.h as it is, compiled with g++ -ffp-contract=off, against the program's own scalar restatement of the contract:
-    70 x 19, 5 x 3 and 1 x 1; radius 1 and 3; with and without a clamp; min_bounces 0.5 and +inf; finite inputs, NaN and +-inf in the
+    """csrc/crt_temporal.h as it is -- the per-pixel text of k_temporal_dual and of the four k_temporal kernels -- compiled with g++
+    -ffp-contract=off, against the program's own scalar restatement of the contract: 70 x 19, 5 x 3 and 1 x 1; radius 1 and 3; with and without a clamp; min_bounces 0.5 and +inf; finite inputs, NaN and +-inf in the
     colours, path_depth and bounces, and frames without variance, normals and ids; no history; then the mirror scene of
     test_restatement_reprojects_a_mirror_image with its bounds.  The summary line carries the case count."""
     rc, raw, printed = host_check_run[0]

@@ -1,9 +1,11 @@
-// tools/temporal_host_check.cpp -- the per-pixel text of crt_temporal_dual (cudaraytracing_amd/csrc/crt_temporal.h) compiled for the HOST
-// and run against a plain restatement of include/crt.h written here, scalar and straight down the contract's lines, for AddressSanitizer /
-// UBSan runs without a device.  crt_temporal.h and crt_stages.h (the tone map, write_color) are included as they are; tools/host_device.h
-// stands in for what they take from outside.  k_temporal_dual (crt_temporal.hip) is temporal_dual_begin, one ballot, temporal_dual_finish;
-// here every pixel runs twice, once with its own `tries` as the ballot's result and once with `true` (a wave in which another lane
-// tries), and both must write the restatement's bits.  Every image has exactly its entries, so a tap one element out is a report.
+// tools/temporal_host_check.cpp -- the per-pixel text of all six temporal kernels (cudaraytracing_amd/csrc/crt_temporal.h) compiled for
+// the HOST and run against a plain restatement of include/crt.h written here, scalar and straight down the contract's lines, for
+// AddressSanitizer / UBSan runs without a device.  crt_temporal.h and crt_stages.h (the tone map, write_color) are included as they are;
+// tools/host_device.h stands in for what they take from outside.  k_temporal_dual (crt_temporal.hip) is temporal_dual_begin, one ballot,
+// temporal_dual_finish; here every pixel runs twice, once with its own `tries` as the ballot's result and once with `true` (a wave in
+// which another lane tries), and both must write the restatement's bits.  k_temporal<CLAMP, MOMENTS> is temporal_single; every case also
+// runs its four instantiations, with and without the clamp and the moment planes, against the restatement of a pixel that does not try V,
+// plus crt_temporal_moments' two lines.  Every image has exactly its entries, so a tap one element out is a report.
 //
 // Cases: 70 x 19, 5 x 3 and 1 x 1; the choice's radius 1 and 3; with and without a clamp; min_bounces 0.5 and +inf; finite inputs and
 // inputs with NaN and +-inf planted in the colours, in path_depth and in bounces of both frames (a bounces of +inf reaches a min_bounces of
@@ -51,7 +53,7 @@ struct Camera { float eye[3], iv[9], fov; };
 
 // one frame with its specular planes, and the history's extra plane
 struct Frame {
-    std::vector<float> color, variance, depth, normal, path_depth, bounces, last_normal, history;
+    std::vector<float> color, variance, depth, normal, path_depth, bounces, last_normal, history, m1, m2; // (m1, m2: a history's moment planes)
     std::vector<int32_t> id;
 };
 
@@ -62,18 +64,19 @@ struct Case {
     bool clamp; int clamp_radius; float gamma;
     int radius; float min_bounces;
     bool with_history, with_normals, with_ids, with_variance, with_last_normals;
+    bool with_moments = false; // prev has m1 and m2: the single-candidate form also runs with them
     Frame cur, prev;
 };
 
 struct Outputs {
-    std::vector<float> color, variance, history;
+    std::vector<float> color, variance, history, m1, m2;
     std::vector<uint8_t> rgb;
     unsigned long long took = 0, clamped = 0, tried = 0, took_V = 0, ties = 0, v_only = 0, s_kept = 0;
 };
 
 // ------------------------------------------------------------------------------------------------ the contract, restated --
 
-struct RefCand { float hc[3], hv[3], hn, ws; bool valid; };
+struct RefCand { float hc[3], hv[3], h1[3], h2[3], hn, ws; bool valid; };
 
 static void ref_unit3(float* a)
 {
@@ -100,7 +103,7 @@ static RefCand ref_candidate(const Case& c, const int x, const int y, const floa
     const float fx = (((((-cx) / cz) / (pscale * ar)) + 1) * W) / 2 - 0.5f, fy = (((1 - (cy / cz) / pscale) * H) / 2) - 0.5f;
     const bool ok = dist > 0 && cz > 0 && fx > -1 && fx < W && fy > -1 && fy < H;
     RefCand r;
-    for (int k = 0; k < 3; k++) r.hc[k] = r.hv[k] = 0.0f;
+    for (int k = 0; k < 3; k++) r.hc[k] = r.hv[k] = r.h1[k] = r.h2[k] = 0.0f;
     r.hn = 0.0f; r.ws = 0.0f; r.valid = false;
     if (!ok) return r;
     const float x0f = std::floor(fx), y0f = std::floor(fy), wx = fx - x0f, wy = fy - y0f;
@@ -127,6 +130,7 @@ static RefCand ref_candidate(const Case& c, const int x, const int y, const floa
             for (int k = 0; k < 3; k++) {
                 r.hc[k] = r.hc[k] + c.prev.color.at(q * 3 + k) * b;
                 if (c.with_variance) r.hv[k] = r.hv[k] + c.prev.variance.at(q * 3 + k) * b;
+                if (c.with_moments) { r.h1[k] = r.h1[k] + c.prev.m1.at(q * 3 + k) * b; r.h2[k] = r.h2[k] + c.prev.m2.at(q * 3 + k) * b; }
             }
             r.hn = r.hn + c.prev.history.at(q) * b;
             r.ws = r.ws + b;
@@ -167,19 +171,24 @@ static uint8_t ref_tonemap(const float v)
     return (uint8_t)t;
 }
 
-static void ref_run(const Case& c, Outputs& o)
+// dual false: no pixel tries V (crt_temporal, crt_temporal_clamped, crt_temporal_moments); clamp: the case's, or the caller's
+static void ref_run(const Case& c, Outputs& o, const bool dual, const bool clamp)
 {
     const size_t n = (size_t)c.w * c.h;
-    o.color.assign(n * 3, 0); o.variance.assign(n * 3, 0); o.history.assign(n, 0); o.rgb.assign(n * 3, 0);
+    o.color.assign(n * 3, 0); o.variance.assign(n * 3, 0); o.history.assign(n, 0); o.rgb.assign(n * 3, 0); o.m1.assign(n * 3, 0); o.m2.assign(n * 3, 0);
     for (int y = 0; y < c.h; y++)
         for (int x = 0; x < c.w; x++) {
             const size_t p = (size_t)y * c.w + x;
-            float oc[3], ov[3] = {0, 0, 0}, oh = 1.0f;
-            for (int k = 0; k < 3; k++) { oc[k] = c.cur.color.at(p * 3 + k); if (c.with_variance) ov[k] = c.cur.variance.at(p * 3 + k); }
+            float oc[3], ov[3] = {0, 0, 0}, o1[3], o2[3], oh = 1.0f;
+            for (int k = 0; k < 3; k++) {
+                oc[k] = o1[k] = c.cur.color.at(p * 3 + k);
+                o2[k] = oc[k] * oc[k];
+                if (c.with_variance) ov[k] = c.cur.variance.at(p * 3 + k);
+            }
             if (c.with_history) {
                 const RefCand S = ref_candidate(c, x, y, c.cur.depth.at(p), false);
                 RefCand T = S;
-                const bool tries = c.cur.bounces.at(p) >= c.min_bounces && c.cur.path_depth.at(p) > 0;
+                const bool tries = dual && c.cur.bounces.at(p) >= c.min_bounces && c.cur.path_depth.at(p) > 0;
                 if (tries) {
                     o.tried++;
                     const RefCand V = ref_candidate(c, x, y, c.cur.path_depth.at(p), true);
@@ -204,11 +213,11 @@ static void ref_run(const Case& c, Outputs& o)
                     a = a < c.alpha_min ? c.alpha_min : a;
                     const float k1 = 1 - a;
                     float s1[3], s2[3], cnt = 0;
-                    if (c.clamp) ref_box(c, x, y, c.clamp_radius, s1, s2, cnt);
+                    if (clamp) ref_box(c, x, y, c.clamp_radius, s1, s2, cnt);
                     bool moved = false;
                     for (int k = 0; k < 3; k++) {
                         float Hc = T.hc[k] / T.ws;
-                        if (c.clamp) {
+                        if (clamp) {
                             const float mu = s1[k] / cnt;
                             float e = s2[k] / cnt - mu * mu;
                             e = e < 0 ? 0 : e;
@@ -218,21 +227,29 @@ static void ref_run(const Case& c, Outputs& o)
                         }
                         oc[k] = Hc * k1 + c.cur.color.at(p * 3 + k) * a;
                         if (c.with_variance) ov[k] = (T.hv[k] / T.ws) * (k1 * k1) + c.cur.variance.at(p * 3 + k) * (a * a);
+                        const float cc = c.cur.color.at(p * 3 + k);
+                        o1[k] = (T.h1[k] / T.ws) * k1 + cc * a;      // (never clamped; the planes of S: compared only where no pixel tries V)
+                        o2[k] = (T.h2[k] / T.ws) * k1 + (cc * cc) * a;
                     }
                     if (moved) o.clamped++;
                 }
             }
-            for (int k = 0; k < 3; k++) { o.color[p * 3 + k] = oc[k]; o.variance[p * 3 + k] = ov[k]; o.rgb[p * 3 + k] = ref_tonemap(oc[k]); }
+            for (int k = 0; k < 3; k++) {
+                o.color[p * 3 + k] = oc[k]; o.variance[p * 3 + k] = ov[k]; o.rgb[p * 3 + k] = ref_tonemap(oc[k]);
+                o.m1[p * 3 + k] = o1[k]; o.m2[p * 3 + k] = o2[k];
+            }
             o.history[p] = oh;
         }
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel's text --
 
-template <bool CLAMP> static void text_run(const Case& c, const bool every_wave_tries, Outputs& o)
+// the parameter block of a case as crt_temporal.hip's fill_params fills it, on the outputs of o (filled with what no pixel writes)
+static TpDualParams text_params(const Case& c, const bool clamp, const bool moments, Outputs& o)
 {
     const size_t n = (size_t)c.w * c.h;
     o.color.assign(n * 3, QNAN); o.variance.assign(n * 3, QNAN); o.history.assign(n, QNAN); o.rgb.assign(n * 3, 0x5a);
+    o.m1.assign(moments ? n * 3 : 0, QNAN); o.m2.assign(moments ? n * 3 : 0, QNAN);
     TpDualParams P;
     std::memset(&P, 0, sizeof(P));
     P.width = (uint32_t)c.w; P.height = (uint32_t)c.h; P.tiles_x = ((uint32_t)c.w + 63) / 64;
@@ -242,7 +259,7 @@ template <bool CLAMP> static void text_run(const Case& c, const bool every_wave_
     P.depth_tol = c.depth_tol; P.normal_tol2 = c.normal_tol * c.normal_tol; P.alpha_min = c.alpha_min;
     P.color = c.cur.color.data(); P.depth = c.cur.depth.data();
     if (c.with_variance) P.variance = c.cur.variance.data();
-    if (c.with_history) { // (as temporal_dual_impl fills the block: without a history no guide and no specular plane)
+    if (c.with_history) { // (without a history no guide and no specular plane)
         if (c.with_normals) { P.normal = c.cur.normal.data(); P.pnormal = c.prev.normal.data(); }
         if (c.with_ids) { P.id = c.cur.id.data(); P.pid = c.prev.id.data(); }
         P.pcolor = c.prev.color.data(); P.phistory = c.prev.history.data(); P.pdepth = c.prev.depth.data();
@@ -253,17 +270,40 @@ template <bool CLAMP> static void text_run(const Case& c, const bool every_wave_
     }
     P.out_mean = o.color.data(); P.out_rgb = o.rgb.data(); P.out_history = o.history.data();
     if (c.with_variance) P.out_variance = o.variance.data();
-    if (c.clamp) { P.radius = c.clamp_radius; P.gamma = c.gamma; }
+    if (clamp) { P.radius = c.clamp_radius; P.gamma = c.gamma; }
     P.dual_radius = c.radius; P.min_bounces = c.min_bounces;
+    if (moments) {
+        if (c.with_history) { P.pm1 = c.prev.m1.data(); P.pm2 = c.prev.m2.data(); }
+        P.out_m1 = o.m1.data(); P.out_m2 = o.m2.data();
+    }
+    return P;
+}
+
+// k_temporal_dual<CLAMP>'s pixels
+template <bool CLAMP> static void text_run(const Case& c, const bool every_wave_tries, Outputs& o)
+{
+    const TpDualParams P = text_params(c, CLAMP, false, o);
     for (int y = 0; y < c.h; y++)
         for (int x = 0; x < c.w; x++) {
             TpDualState st;
             std::memset(&st, 0, sizeof(st));
             if (P.pcolor) st = temporal_dual_begin(P, x, y);
-            const TpDualFlags fl = temporal_dual_finish<CLAMP>(P, x, y, st, every_wave_tries || st.tries);
+            const TpFlags fl = temporal_dual_finish<CLAMP>(P, x, y, st, every_wave_tries || st.tries);
             o.took += fl.took; o.clamped += fl.clamped; o.tried += fl.tried; o.took_V += fl.took_V;
         }
-    if (!c.with_variance) o.variance.assign(n * 3, 0);
+    if (!c.with_variance) o.variance.assign((size_t)c.w * c.h * 3, 0);
+}
+
+// k_temporal<CLAMP, MOMENTS>'s pixels: the base of the block alone, as the kernel takes it
+template <bool CLAMP, bool MOMENTS> static void text_single(const Case& c, Outputs& o)
+{
+    const TpParams P = text_params(c, CLAMP, MOMENTS, o);
+    for (int y = 0; y < c.h; y++)
+        for (int x = 0; x < c.w; x++) {
+            const TpFlags fl = temporal_single<CLAMP, MOMENTS>(P, x, y);
+            o.took += fl.took; o.clamped += fl.clamped; o.tried += fl.tried; o.took_V += fl.took_V;
+        }
+    if (!c.with_variance) o.variance.assign((size_t)c.w * c.h * 3, 0);
 }
 
 static bool same_bits(const std::vector<float>& a, const std::vector<float>& b, size_t& at)
@@ -282,10 +322,39 @@ static void compare(const Case& c, const Outputs& want, const Outputs& got, cons
     CHECK(same_bits(want.variance, got.variance, at), "case %d (%s): variance differs at %zu", index, what, at);
     CHECK(same_bits(want.history, got.history, at), "case %d (%s): history differs at %zu: %g, expected %g", index, what, at, got.history[at], want.history[at]);
     CHECK(want.rgb == got.rgb, "case %d (%s): rgb differs", index, what);
+    if (!got.m1.empty()) { // (a run with the moment planes)
+        CHECK(same_bits(want.m1, got.m1, at), "case %d (%s): m1 differs at %zu: %g, expected %g", index, what, at, got.m1[at], want.m1[at]);
+        CHECK(same_bits(want.m2, got.m2, at), "case %d (%s): m2 differs at %zu: %g, expected %g", index, what, at, got.m2[at], want.m2[at]);
+    }
     CHECK(want.took == got.took && want.clamped == got.clamped && want.tried == got.tried && want.took_V == got.took_V,
           "case %d (%s): counts %llu %llu %llu %llu, expected %llu %llu %llu %llu", index, what, got.took, got.clamped, got.tried, got.took_V, want.took,
           want.clamped, want.tried, want.took_V);
     (void)c;
+}
+
+// The four single-candidate kernels on a case, each against the restatement in which no pixel tries V; the moment planes where the case
+// has them.  Adds the pixels that took a history and of those the clamped ones, over the runs; out: takes the bytes they wrote.
+static void single_runs(const Case& c, const int index, unsigned long long& took, unsigned long long& clamped, std::FILE* out)
+{
+    Outputs want[2], got[4];
+    ref_run(c, want[0], false, false);
+    ref_run(c, want[1], false, true);
+    text_single<false, false>(c, got[0]);
+    text_single<true, false>(c, got[1]);
+    compare(c, want[0], got[0], "one candidate", index);
+    compare(c, want[1], got[1], "one candidate, clamped", index);
+    if (c.with_moments) {
+        text_single<false, true>(c, got[2]);
+        text_single<true, true>(c, got[3]);
+        compare(c, want[0], got[2], "one candidate, moments", index);
+        compare(c, want[1], got[3], "one candidate, clamped, moments", index);
+    }
+    for (int r = 0; r < (c.with_moments ? 4 : 2); r++) {
+        took += got[r].took; clamped += got[r].clamped;
+        if (!out) continue;
+        std::fwrite(got[r].color.data(), 4, got[r].color.size(), out); std::fwrite(got[r].history.data(), 4, got[r].history.size(), out);
+        if (r >= 2) { std::fwrite(got[r].m1.data(), 4, got[r].m1.size(), out); std::fwrite(got[r].m2.data(), 4, got[r].m2.size(), out); }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ the cases --
@@ -348,8 +417,15 @@ static Case synthetic(const int w, const int h, const uint64_t seed, const bool 
                 for (int k = 0; k < 3; k++) f->last_normal[p * 3 + k] = f->normal[p * 3 + k];
             }
         }
+    // the history's moment planes, from a sequence of their own (the other planes are what they were without them)
+    Rng mrng{seed * 7919u + 13u};
+    c.with_moments = true;
+    c.prev.m1.resize((size_t)w * h * 3); c.prev.m2.resize((size_t)w * h * 3);
+    for (size_t i = 0; i < c.prev.m1.size(); i++) { c.prev.m1[i] = mrng.uniform() * 100; c.prev.m2[i] = mrng.uniform() * 10000; }
     if (non_finite) {
         const float bad[3] = {QNAN, INF, -INF};
+        for (std::vector<float>* plane : {&c.prev.m1, &c.prev.m2})
+            for (int k = 0; k < 9; k++) (*plane)[(size_t)(mrng.next() % (uint32_t)plane->size())] = bad[k % 3];
         int i = 0;
         for (std::vector<float>* plane : {&c.cur.color, &c.prev.color, &c.cur.path_depth, &c.prev.path_depth, &c.cur.bounces, &c.prev.bounces, &c.cur.depth,
                                           &c.prev.depth, &c.prev.history, &c.prev.variance})
@@ -400,8 +476,10 @@ static double mirror_error(const int w, const int h, const float* move, const fl
     mirror_frame(c.prev, c.pcam, w, h, true);
     text_run<false>(c, false, out);
     Outputs want;
-    ref_run(c, want);
+    ref_run(c, want, true, false);
     compare(c, want, out, "mirror", -1);
+    unsigned long long took = 0, clamped = 0;
+    single_runs(c, -1, took, clamped, nullptr);
     const double scale = std::tan((double)c.pcam.fov / 2), ar = (double)w / h;
     double worst = 0;
     inside = 0;
@@ -428,7 +506,7 @@ int main(int argc, char** argv)
     std::FILE* out = argc == 3 ? std::fopen(argv[2], "wb") : nullptr;
     if (argc == 3 && !out) { std::fprintf(stderr, "temporal_host_check: cannot open the output file\n"); return 2; }
     int cases = 0;
-    unsigned long long ties = 0, v_only = 0, s_kept = 0, took_V = 0, non_finite_out = 0;
+    unsigned long long ties = 0, v_only = 0, s_kept = 0, took_V = 0, non_finite_out = 0, single_took = 0, single_clamped = 0;
     const int sizes[3][2] = {{70, 19}, {5, 3}, {1, 1}};
     for (int s = 0; s < 3; s++)
         for (int radius : {1, 3})
@@ -440,7 +518,7 @@ int main(int argc, char** argv)
                         c.clamp = clamp != 0; c.clamp_radius = radius == 1 ? 1 : 2; // (the clamp's radius equal to the choice's, and not)
                         if (kind == 2) c.with_variance = c.with_normals = c.with_last_normals = c.with_ids = false;
                         Outputs want, got, got2;
-                        ref_run(c, want);
+                        ref_run(c, want, true, c.clamp);
                         if (c.clamp) { text_run<true>(c, false, got); text_run<true>(c, true, got2); }
                         else { text_run<false>(c, false, got); text_run<false>(c, true, got2); }
                         compare(c, want, got, "the pixel's own ballot", cases);
@@ -449,6 +527,7 @@ int main(int argc, char** argv)
                         ties += want.ties; v_only += want.v_only; s_kept += want.s_kept; took_V += want.took_V;
                         for (float v : want.color) non_finite_out += !(v - v == 0);
                         if (out) { std::fwrite(got.color.data(), 4, got.color.size(), out); std::fwrite(got.history.data(), 4, got.history.size(), out); std::fwrite(got.rgb.data(), 1, got.rgb.size(), out); }
+                        single_runs(c, cases, single_took, single_clamped, out);
                         cases++;
                     }
     for (int s = 0; s < 3; s++) { // without a history: every pixel resets, no plane of the history or of the specular AOVs is read
@@ -457,15 +536,20 @@ int main(int argc, char** argv)
         c.prev = Frame();
         c.cur.path_depth.clear(); c.cur.bounces.clear(); c.cur.last_normal.clear();
         Outputs want, got;
-        ref_run(c, want);
+        ref_run(c, want, true, true);
         text_run<true>(c, true, got);
         compare(c, want, got, "no history", cases);
         CHECK(want.took == 0 && want.tried == 0, "case %d: a call without a history took one", cases);
+        unsigned long long took = 0, clamped = 0;
+        single_runs(c, cases, took, clamped, out);
+        CHECK(took == 0 && clamped == 0, "case %d: a single-candidate call without a history took one", cases);
         cases++;
     }
     CHECK(ties >= 20 && v_only >= 20 && s_kept >= 20 && took_V >= 100 && non_finite_out >= 20,
           "the cases do not reach every branch: %llu ties, %llu V with S invalid, %llu S kept, %llu V taken, %llu non-finite outputs", ties, v_only, s_kept, took_V,
           non_finite_out);
+    CHECK(single_took >= 1000 && single_clamped >= 100 && single_took - single_clamped >= 1000,
+          "the single-candidate runs do not reach every branch: %llu pixels took the history, %llu of them were clamped", single_took, single_clamped);
     // the mirror scene
     const float moves[4][3] = {{10, 0, 0}, {7.3f, -4.1f, 0}, {3, 2, 15}, {0, 0, -20}};
     double worst_dual = 0, least_surface = 1e30;
