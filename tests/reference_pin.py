@@ -110,7 +110,7 @@ class SceneSpec:
                 self.obj_paths = [(self.files[0], d)]
                 eye, lookat, fov = [4.0, 2.5, -6.0], [4.0, 1.0, 4.0], 60.0
             elif name == "room":
-                from test_gpu_parity import _write_box_scene
+                from scene_files import _write_box_scene
                 obj, mtl = _write_box_scene(d)
                 self.files = [obj, os.path.join(d, "room.mtl")]
                 self.obj_paths = [(obj, mtl)]

@@ -1,5 +1,5 @@
-"""The contract of crt_temporal_dual (include/crt.h) restated in numpy float32 on the restatements that exist: test_temporal.restated
-is the statement of a candidate's taps, test_temporal_clamp.restated_clamped of the clamp and the blend, test_temporal_clamp.history_colour
+"""The contract of crt_temporal_dual (include/crt.h) restated in numpy float32 on the restatements that exist: temporal_restated.restated
+is the statement of a candidate's taps, temporal_clamp_restated.restated_clamped of the clamp and the blend, temporal_clamp_restated.history_colour
 reads H = hc / ws out of the former.  What is written here is what the dual pass adds:
 
   candidate V is candidate S of other inputs -- the pixel's path_depth in the place of its depth, its last normal in the place of its normal,
@@ -12,8 +12,8 @@ The blend of the chosen candidate is restated_clamped's of that candidate's inpu
 its results.  Every ufunc below is one IEEE fp32 operation per element."""
 import numpy as np
 
-import test_temporal as T
-import test_temporal_clamp as TC
+import temporal_clamp_restated as TC
+import temporal_restated as T
 
 F = np.float32
 SPECULAR = ("path_depth", "bounces", "last_normal")
@@ -93,8 +93,8 @@ def counts(masks):
 # ---- inputs ----
 
 def mirror_scene(W, H, eye, zm=100.0, zq=-50.0):
-    """A camera at `eye` looking along +z at a mirror in the plane z = zm (test_temporal.plane_setup's plane); behind the camera the plane
-    z = zq, parallel to it, coloured by test_temporal.plane_colour of world x and y.  A pixel shows the point of that plane its
+    """A camera at `eye` looking along +z at a mirror in the plane z = zm (temporal_restated.plane_setup's plane); behind the camera the plane
+    z = zq, parallel to it, coloured by temporal_restated.plane_colour of world x and y.  A pixel shows the point of that plane its
     reflected ray reaches: the point of the virtual plane z = 2 zm - zq on the straight pixel ray, mirrored in z -- the same x and y.
     Returns (camera, the frame's dict in float64 -- depth to the mirror, path_depth = that + the way on to the plane, bounces 1, one id,
     the colour of the reflected point --, the virtual points)."""

@@ -13,8 +13,7 @@ import cudaraytracing_amd as crt
 import oracle_lib as O
 import tree_check as TC
 import util
-from test_gpu_parity import _write_box_scene, _write_soup_scene
-from test_tree_invariants import write_signed_zero_scene
+from scene_files import _write_box_scene, _write_soup_scene, write_signed_zero_scene
 
 pytestmark = pytest.mark.gpu
 REPORT = os.path.join(util.ROOT, "gpurun_out", "sah_build_report.jsonl")

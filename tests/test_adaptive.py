@@ -2,7 +2,7 @@
 Render.run_view_adaptive and adaptive_defaults in Python, crt_cli --adaptive.
 
 The expected values come from the oracle's per-path radiance (OracleScene.render(want_L=True) -> (h, w, S, 3)): the contract of
-include/crt.h is restated below in numpy float32, one ufunc per IEEE operation -- the warm-up sums of util.restated_sums, the stop
+include/crt.h is restated in variance_restated.py in numpy float32, one ufunc per IEEE operation -- the warm-up sums of util.restated_sums, the stop
 criterion, the masked steps, the outputs -- and the device result must match it on uint32 views (NaN matches NaN), the RGB frame the
 oracle's tone map of the restated mean.
 
@@ -22,66 +22,19 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
-import oracle_lib as O
 import util
-from util import assert_bits, restated_sums
+from adaptive_frames import AD, H, S, W, gpu_adaptive
+from frames import oracle_frame, renders  # noqa: F401
+from util import assert_bits
+from variance_restated import restated_adaptive
 
 F = np.float32
 SCENES = ["cornell-box", "veach-mis"]
 ADAPTIVE_EXPORTS = ("crt_adaptive_defaults", "crt_render_adaptive", "crt_render_adaptive_device")
-W, H, S = 37, 27, 29
-AD = dict(min_samples=4, step_samples=6, threshold=0.2, mean_floor=0.01)
+RENDER_SPP = S     # (what frames.renders creates the handles with)
 STOPS = (4, 10, 16, 22, 28, 29)
 EXPECTED = {"cornell-box": ((427, 107, 96, 52, 35, 282), [572, 465, 369, 317, 282]),
             "veach-mis": ((440, 281, 128, 61, 27, 62), [559, 278, 150, 89, 62])}
-
-
-def variance_of_sums(c, q, fn, r):
-    """crt_variance's formula; fn, r: float32 scalars or (h, w, 1) arrays"""
-    d = fn * q - c * c
-    d = np.where(d < F(0.0), F(0.0), d)
-    return ((r * r) * d) / (fn - F(1.0))
-
-
-def restated_adaptive(L, S, min_samples, step_samples, threshold, mean_floor):
-    """The contract of crt_render_adaptive on per-path radiance L (h, w, S, 3): dict of samples (h, w) uint32, mean, variance
-    (h, w, 3) float32, rgb, pass_pixels, passes, paths."""
-    thr, floor, fs = F(threshold), F(mean_floor), F(S)
-    with np.errstate(all="ignore"):
-        c, q = restated_sums(L, S, min_samples)
-        n = min_samples
-        nsamp = np.full(L.shape[:2], n, dtype=np.uint32)
-        active = np.ones(L.shape[:2], dtype=bool)
-        pass_pixels = []
-        while n < S:
-            fn = F(n)
-            r = fs / fn
-            var = variance_of_sums(c, q, fn, r)
-            p = c * r
-            v = (var[..., 0] + var[..., 1]) + var[..., 2]
-            m = (p[..., 0] + p[..., 1]) + p[..., 2]
-            t = thr * (m + floor)
-            stop = v <= t * t
-            active = active & ~stop
-            if not active.any():
-                break
-            pass_pixels.append(int(active.sum()))
-            ns = min(step_samples, S - n)
-            a3 = active[..., None]
-            for k in range(n, n + ns):
-                x = L[:, :, k, :] / fs
-                c = np.where(a3, c + x, c)
-                q = np.where(a3, q + x * x, q)
-            n += ns
-            nsamp[active] = n
-        fn = nsamp.astype(F)[..., None]
-        r = fs / fn
-        mean = c * r
-        var = variance_of_sums(c, q, fn, r)
-    for a in (c, q, mean, var, v):
-        assert a.dtype == F
-    return dict(samples=nsamp, mean=mean, variance=var, rgb=O.tonemap(mean), pass_pixels=pass_pixels, passes=1 + len(pass_pixels),
-                paths=int(nsamp.astype(np.uint64).sum()), c=c)
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU --
@@ -215,35 +168,11 @@ def test_restatement_stops_at_the_relative_standard_error():
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in SCENES:
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(name):
-    """(rgb, mean, L (H, W, S, 3)) of the oracle at the tests' shape with the scene's own P_RR and light_sample_n, seed 0"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, W, H, S, t.P_RR, t.light_sample_n, want_L=True)
-    c, _ = restated_sums(L, S, S)
-    assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
-    for a in (rgb, mean, L):
-        a.flags.writeable = False
-    return rgb, mean, L
-
-
 @functools.lru_cache(maxsize=None)
 def restated(name, **kw):
     """The restated adaptive frame of a scene at the tests' shape (kw overrides AD), computed once; with the default settings it must
     be the frame recorded at the top of this file -- if not, the inputs are wrong, not the kernel."""
-    _, _, L = oracle_frame(name)
+    _, _, L = oracle_frame(name, W, H, S)
     got = restated_adaptive(L, S, **dict(AD, **kw))
     if not kw:
         counts = tuple(int((got["samples"] == n).sum()) for n in STOPS)
@@ -254,17 +183,6 @@ def restated(name, **kw):
         if isinstance(a, np.ndarray):
             a.flags.writeable = False
     return got
-
-
-def gpu_adaptive(r, name, traversal=crt.TRAVERSAL_EXACT, want_variance=True, **kw):
-    eye, iv, fov = util.camera(name)
-    r.set_spp(S)
-    r.seed, r.traversal = 0, traversal
-    try:
-        rgb = r.run_view_adaptive(eye, iv, fov, want_variance=want_variance, width=W, height=H, **dict(AD, **kw))
-    finally:
-        r.traversal = crt.TRAVERSAL_EXACT
-    return dict(rgb=rgb, mean=r.mean_buffer, samples=r.samples_buffer, variance=r.variance_buffer, info=r.adaptive_info)
 
 
 def check_frame(got, want, where):
@@ -352,7 +270,7 @@ def test_adaptive_shards_are_the_full_frame_at_their_pixels(renders, name):
 def test_adaptive_limits(renders, name):
     r = renders[name]
     eye, iv, fov = util.camera(name)
-    orgb, omean, L = oracle_frame(name)
+    orgb, omean, L = oracle_frame(name, W, H, S)
     r.set_spp(S)
     rgb_u = r.run_view(eye, iv, fov, width=W, height=H, want_variance=True).copy()
     mean_u, var_u = r.mean_buffer.copy(), r.variance_buffer.copy()
@@ -416,7 +334,7 @@ def test_adaptive_leaves_no_frame_in_flight(monkeypatch):
     r = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)   # a fresh handle
     try:
         eye, iv, fov = util.camera(name)
-        orgb, omean, L = oracle_frame(name)
+        orgb, omean, L = oracle_frame(name, W, H, S)
         kw = dict(width=W, height=H)
         want = restated(name)
 

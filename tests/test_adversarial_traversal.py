@@ -14,88 +14,18 @@ import numpy as np
 import pytest
 
 import cudaraytracing_amd as crt
-import oracle_lib as O
+import parity_cases as PC
 import util
-from test_gpu_parity import _write_box_scene, _write_soup_scene
+from blocked_restated import _oracle_blocked
+from parity_cases import _check_rays, _grazing_rays, _load
+from scene_files import _write_box_scene, _write_soup_scene
 
 pytestmark = pytest.mark.gpu
 
 
-def _load(obj, mtl, thresh, w=48, h=36):
-    scene = crt.Scene(w, h)
-    scene.add_obj(obj, mtl)
-    scene.set_BVH(thresh)
-    osc = O.OracleScene([(obj, mtl)], thresh)
-    assert scene.nodes().tobytes() == osc.nodes().tobytes()
-    return scene, osc
-
-
-def _check_rays(r, osc, o, d):
-    otri, ot, _ = osc.intersect(o, d)
-    out = {}
-    for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
-        tri, t = r.intersect(o, d, traversal=mode)
-        out[mode] = (tri, t)
-        bad = np.nonzero((tri != otri) | (util.bits(t) != util.bits(ot)))[0]
-        assert bad.size == 0, (mode, bad[:8], tri[bad[:8]], otri[bad[:8]], t[bad[:8]], ot[bad[:8]])
-    return otri, ot
-
-
-def _grazing_rays(tris, rng, n_per, angles):
-    """Rays that cross triangle planes at the given (tiny) angles, aimed at a point inside the triangle, from both sides,
-    from near and far; plus rays lying exactly in the plane (determinant exactly or nearly zero)."""
-    o_list, d_list = [], []
-    for v in tris:
-        e1, e2 = v[1] - v[0], v[2] - v[0]
-        n = np.cross(e1, e2)
-        ln = np.linalg.norm(n)
-        if ln == 0:
-            continue
-        n /= ln
-        for _ in range(n_per):
-            a, b = rng.uniform(0.05, 0.9), rng.uniform(0.05, 0.9)
-            if a + b > 0.95:
-                a, b = 0.3, 0.3
-            p = v[0] + a * e1 + b * e2
-            tdir = np.cos(rng.uniform(0, 2 * np.pi)) * e1 / np.linalg.norm(e1) + np.sin(rng.uniform(0, 2 * np.pi)) * np.cross(n, e1) / np.linalg.norm(e1)
-            tdir /= np.linalg.norm(tdir)
-            for th in angles:
-                for sgn in (1.0, -1.0):
-                    d = np.cos(th) * tdir + sgn * np.sin(th) * n
-                    s = rng.choice([0.01, 0.5, 3.0, 40.0])
-                    o_list.append(p - s * d)
-                    d_list.append(d)
-    return np.asarray(o_list, dtype=np.float32), np.asarray(d_list, dtype=np.float32)
-
-
-def _soup_triangles(obj):
-    vs, fs = [], []
-    for line in open(obj):
-        t = line.split()
-        if not t:
-            continue
-        if t[0] == "v":
-            vs.append([float(x) for x in t[1:4]])
-        elif t[0] == "f":
-            fs.append([int(x.split("/")[0]) - 1 for x in t[1:4]])
-    vs = np.asarray(vs, dtype=np.float64)
-    return [vs[f] for f in fs]
-
-
 @pytest.mark.parametrize("thresh", [1, 2, 4])
 def test_rays_grazing_triangle_planes(tmp_path, thresh):
-    obj, mtl = _write_soup_scene(str(tmp_path), n=300, dup=30, degenerate=10)
-    scene, osc = _load(obj, mtl, thresh)
-    r = crt.Render(scene, 1, 0.6, 1)
-    try:
-        rng = np.random.RandomState(7)
-        tris = _soup_triangles(obj)
-        pick = [tris[i] for i in rng.choice(len(tris), 160, replace=False)]
-        o, d = _grazing_rays(pick, rng, 3, [0.0, 1e-7, 1e-6, 1e-5, 1e-4, 1e-3, 1e-2])
-        otri, ot = _check_rays(r, osc, o, d)
-        assert (otri >= 0).sum() > o.shape[0] // 4  # the probes do hit things
-    finally:
-        r.free()
+    PC.rays_grazing_triangle_planes_match_oracle(tmp_path, thresh)
 
 
 def _write_sliver_scene(d, n=500, seed=5):
@@ -341,47 +271,9 @@ def test_the_c3_ray_that_the_old_pruning_bound_lost():
         r.free()
 
 
-def _oracle_blocked(osc, o, d, lim):
-    """blocked() of Render.cuh:19-27 from the oracle's closest hit (t = FLT_MAX on a miss)"""
-    _, ot, _ = osc.intersect(o, d)
-    with np.errstate(invalid="ignore", over="ignore"):
-        return (lim.astype(np.float32) - ot) > np.float32(0.00001)
-
-
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
 def test_visibility_queries(name):
-    """crt_intersect with CRT_INTERSECT_VISIBILITY is blocked() of the reference (Render.cuh:19-27, :272) in every traversal mode:
-    rays from surface points towards points on other surfaces, limits around the true distance, and the limits the reference's
-    t_to_light = dist.x / dir.x can produce (0, negative, infinite, NaN)."""
-    t = util.task(name)
-    osc = util.oracle_scene(name)
-    r = crt.Render(util.host_scene(name), 1, t.P_RR, t.light_sample_n)
-    try:
-        rng = np.random.RandomState(11)
-        tr = osc.tris()
-        n = 20000
-        def surface_points(k):
-            i = rng.randint(0, tr["v1"].shape[0], k)
-            a, b = rng.rand(k, 1).astype(np.float32), rng.rand(k, 1).astype(np.float32)
-            flip = (a + b) > 1
-            a, b = np.where(flip, 1 - a, a), np.where(flip, 1 - b, b)
-            return (tr["v1"][i] + a * (tr["v2"][i] - tr["v1"][i]) + b * (tr["v3"][i] - tr["v1"][i])).astype(np.float32)
-        o, p = surface_points(n), surface_points(n)
-        d = p - o
-        dist = np.linalg.norm(d, axis=1).astype(np.float32)
-        lim = dist * rng.choice(np.array([1.0, 1.0, 0.5, 0.999999, 1.000001, 1.00001, 2.0, 1e-3], dtype=np.float32), n)
-        lim[:64] = np.tile(np.array([0.0, -1.0, np.inf, -np.inf, np.nan, 3.0e38, 1.0e-5, 2.0e-5], dtype=np.float32), 8)
-        ob = _oracle_blocked(osc, o, d, lim)
-        assert 0.2 < ob.mean() < 0.95  # both answers are well represented
-        for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_FAST | crt.INTERSECT_FORCE_EXACT, crt.TRAVERSAL_EXACT,
-                     crt.TRAVERSAL_EXACT | crt.INTERSECT_FORCE_EXACT):
-            blk, tri = r.blocked(o, d, lim, traversal=mode)
-            bad = np.nonzero(blk != ob)[0]
-            assert bad.size == 0, (mode, bad[:8], lim[bad[:8]])
-            assert np.all(tri[~blk] == -1)
-            assert np.all(tri[blk & np.isfinite(lim)] >= 0)
-    finally:
-        r.free()
+    PC.visibility_queries_match_blocked(name)
 
 
 # Next-event samples of full C5 frames (seeds 4 and 5) whose blocker CRT_TRAVERSAL_FAST loses: the ray lies in the plane of a small

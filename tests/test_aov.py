@@ -1,7 +1,7 @@
 """First-hit AOV pass (crt_render_aov / crt_render_aov_device, include/crt.h; Render.run_view_aov in Python; crt_cli --aov) and the
 PFM writer.
 
-The expected buffers come from the oracle: orc_render with p_rr = 0 under the ray log; the closest-hit rays that leave the eye are
+The expected buffers come from the oracle (aov_expected.py): orc_render with p_rr = 0 under the ray log; the closest-hit rays that leave the eye are
 the primary rays of the frame's paths, logged pixel by pixel, sample by sample.  Their hits are folded in numpy float32 exactly as
 the contract says (a = a + kd / S over the hits in sample order, ...), and every buffer must match bit for bit.
 """
@@ -15,8 +15,9 @@ import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
+from aov_expected import NAMES, expected_aov, primary_rays, run_aov
+from frames import renders  # noqa: F401
 
-NAMES = ("albedo", "normal", "depth", "coverage", "tri", "material")
 AOV_EXPORTS = ("crt_render_aov", "crt_render_aov_device", "crt_write_pfm")
 
 
@@ -127,65 +128,6 @@ def test_write_pfm_round_trips(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-def primary_rays(name, width, height, spp, crop=None, seed=0):
-    """The oracle's primary rays of a render (crop of a width x height frame): (origins, directions, t, tri) as (pixels, spp, ...)
-    arrays in pixel order, then sample order."""
-    eye, iv, fov = util.camera(name)
-    o, d, t, tri, (ch, cw) = util.primary_rays_of(util.oracle_scene(name), eye, iv, fov, util.task(name).light_sample_n, width, height, spp, crop, seed)
-    p = cw * ch
-    return o.reshape(p, spp, 3), d.reshape(p, spp, 3), t.reshape(p, spp), tri.reshape(p, spp), (ch, cw)
-
-
-def expected_aov(name, width, height, spp, crop=None, seed=0):
-    """The contract of include/crt.h, restated in numpy float32 on the oracle's primary rays."""
-    _, _, t, tri, (ch, cw) = primary_rays(name, width, height, spp, crop, seed)
-    tris = util.oracle_scene(name).tris()
-    mat = util.host_scene(name).triangles()["material"].astype(np.int32)
-    p = tri.shape[0]
-    a = np.zeros((p, 3), dtype=np.float32)
-    nrm = np.zeros((p, 3), dtype=np.float32)
-    d = np.zeros(p, dtype=np.float32)
-    hits = np.zeros(p, dtype=np.int64)
-    fs = np.float32(spp)
-    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
-        for k in range(spp):
-            hit = tri[:, k] >= 0
-            ti = np.where(hit, tri[:, k], 0)
-            a = np.where(hit[:, None], a + tris["kd"][ti].astype(np.float32) / fs, a)
-            nrm = np.where(hit[:, None], nrm + tris["normal"][ti].astype(np.float32) / fs, nrm)
-            d = np.where(hit, d + t[:, k], d)
-            hits += hit
-        depth = np.where(hits > 0, d / hits.astype(np.float32), np.float32(0.0)).astype(np.float32)
-    cov = (hits.astype(np.float32) / fs).astype(np.float32)
-    tri0 = tri[:, 0]
-    mat0 = np.where(tri0 >= 0, mat[np.maximum(tri0, 0)], -1).astype(np.int32)
-    return {"albedo": a.reshape(ch, cw, 3), "normal": nrm.reshape(ch, cw, 3), "depth": depth.reshape(ch, cw),
-            "coverage": cov.reshape(ch, cw), "tri": tri0.reshape(ch, cw), "material": mat0.reshape(ch, cw)}
-
-
-def run_aov(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0):
-    eye, iv, fov = util.camera(name)
-    r.set_spp(spp)
-    r.seed = seed
-    r.traversal = traversal
-    try:
-        return r.run_view_aov(eye, iv, fov, width=width, height=height)
-    finally:
-        r.traversal = crt.TRAVERSAL_EXACT
-        r.seed = 0
-
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])

@@ -1,7 +1,7 @@
 """Shading AOVs (crt_render_aov_shading / crt_render_aov_shading_device, include/crt.h; Render.run_view_aov_shading in Python; crt_cli
 --aov-shading): the emission and the non-emitter albedo that the frame's radiance factors into.
 
-The expected buffers come from the oracle's primary rays (test_aov.primary_rays), folded in numpy float32 exactly as the contract says:
+The expected buffers come from the oracle's primary rays (aov_expected.primary_rays), folded in numpy float32 exactly as the contract says:
 e = e + ke / S over the hits on emitters, b = b + kd / S over the other hits, in sample order.  Every buffer must match bit for bit.
 The CPU tests check the factorisation itself on the oracle's frames: frame = E + sum_k kd(m_k) * I_k / S.
 """
@@ -15,8 +15,9 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
-import test_aov as aov
+import aov_expected as aov
 import util
+from frames import renders  # noqa: F401
 
 F = np.float32
 NAMES = ("emission", "diffuse_albedo")
@@ -150,17 +151,6 @@ def test_radiance_factors_into_emission_and_albedo_on_the_oracle(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in SCENE_NAMES:
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
 
 def run_shading(r, name, spp, width=None, height=None, traversal=crt.TRAVERSAL_EXACT, seed=0, **kw):
     eye, iv, fov = util.camera(name)

@@ -18,6 +18,7 @@ from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
+from frames import renders  # noqa: F401
 
 F = np.float32
 NAMES = ("guide_albedo", "last_normal", "path_depth", "bounces", "last_tri")
@@ -27,7 +28,7 @@ SPECULAR = 1  # crt_material.mode / the oracle's mode of a SPECULAR material (th
 
 # -------------------------------------------------------------------------------------------------------- restatement --
 
-def unit3(v):
+def unit_rows(v):
     """Ray's constructor: v / sqrt(x x + (y y + z z)) per component, v itself if the sum is not positive"""
     z = v[:, 0] * v[:, 0] + (v[:, 1] * v[:, 1] + v[:, 2] * v[:, 2])
     s = np.sqrt(z)
@@ -65,7 +66,7 @@ def chains(osc, o, d, t, tri, max_bounces):
                 break
             ntri, nt, _ = osc.intersect(P, r)
             more = ntri >= 0
-            act, co, cd, ct, ctri = g[more], P[more], unit3(r)[more], nt[more].astype(F), ntri[more]
+            act, co, cd, ct, ctri = g[more], P[more], unit_rows(r)[more], nt[more].astype(F), ntri[more]
     return hit, length, B, thr, last
 
 
@@ -225,16 +226,6 @@ def test_mirror_scene_has_every_kind_of_chain(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
 
 
 def run_spec(r, name, spp, width=None, height=None, max_bounces=None, traversal=crt.TRAVERSAL_EXACT, seed=0, want=NAMES):

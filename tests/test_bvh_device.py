@@ -13,7 +13,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 import util
-from test_gpu_parity import _write_box_scene, _write_soup_scene
+from scene_files import _write_box_scene, _write_soup_scene
 
 pytestmark = pytest.mark.gpu
 REPORT = os.path.join(util.ROOT, "gpurun_out", "bvh_build_report.jsonl")

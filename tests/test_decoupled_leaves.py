@@ -3,14 +3,12 @@ the cases where its differences from the coupled form could show: the tie rule a
 over (distance, ~triangle) instead of the order of the visits (DeviceBVH.cuh:34-41,144; csrc/crt_trace.h), leaves of many records
 are resolved inside one queue entry, rays on the reference-arithmetic path hand their leaves over one by one, a scene that is one
 leaf has no inner node at all, and the commit ring shares the smaller pool.  Everything is compared with the oracle, bit for bit,
-through the C ABI -- the cases themselves are the ones of test_gpu_parity.py / test_adversarial_traversal.py / test_commit_ring.py."""
+through the C ABI -- the cases themselves are the ones of test_gpu_parity.py / test_adversarial_traversal.py / test_commit_ring.py, stated in parity_cases.py."""
 import numpy as np
 import pytest
 
 import cudaraytracing_amd as crt
-import test_adversarial_traversal as A
-import test_commit_ring as R
-import test_gpu_parity as P
+import parity_cases as PC
 import util
 
 pytestmark = pytest.mark.gpu
@@ -26,46 +24,46 @@ def form(monkeypatch, request):
 
 @pytest.mark.parametrize("thresh", [1, 2, 4])
 def test_ties_across_leaves_and_degenerate_triangles(tmp_path, thresh):
-    P.test_triangle_soup_with_ties_and_degenerate_triangles(tmp_path, thresh)
+    PC.soup_with_ties_and_degenerate_triangles_matches_oracle(tmp_path, thresh)
 
 
 @pytest.mark.parametrize("thresh", [1, 3, 20, 200])
 def test_leaf_sizes(tmp_path, thresh):
-    P.test_other_leaf_sizes(tmp_path, thresh)
+    PC.room_matches_oracle_at_leaf_size(tmp_path, thresh)
 
 
 def test_one_leaf_of_150_records(tmp_path):
-    P.test_leaf_of_300_triangles(tmp_path)
+    PC.room_that_is_one_leaf_of_300_triangles_matches_oracle(tmp_path)
 
 
 def test_180000_triangles_with_32_bit_stack_entries(tmp_path):
     """60 000 four-wide nodes: beyond the 16-bit layout, three 32-bit levels in LDS and the rest in the spill area."""
-    P.test_room_of_180000_triangles(tmp_path)
+    PC.room_of_180000_triangles_matches_oracle(tmp_path)
 
 
 @pytest.mark.parametrize("specular", [False, True])
 def test_reference_arithmetic_rays(tmp_path, specular):
-    P.test_rays_with_non_finite_operands_take_the_reference_arithmetic(tmp_path, specular)
+    PC.room_with_every_ray_on_the_reference_arithmetic_matches_oracle(tmp_path, specular)
 
 
 @pytest.mark.parametrize("scale", [1e-12, 1e17])
 def test_extreme_scales(tmp_path, scale):
-    P.test_extreme_coordinate_scales(tmp_path, scale)
+    PC.scaled_soup_matches_oracle(tmp_path, scale)
 
 
 @pytest.mark.parametrize("thresh", [1, 2, 4])
 def test_grazing_rays(tmp_path, thresh):
-    A.test_rays_grazing_triangle_planes(tmp_path, thresh)
+    PC.rays_grazing_triangle_planes_match_oracle(tmp_path, thresh)
 
 
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
 def test_visibility_queries(name):
-    A.test_visibility_queries(name)
+    PC.visibility_queries_match_blocked(name)
 
 
 def test_commit_ring_on_the_smaller_pool():
-    R.test_tiny_rings_reproduce_the_frame("cornell-box", 203, 149, 48, 2)
-    R.test_a_shard_of_the_frame_through_the_ring()
+    PC.tiny_ring_reproduces_the_frame("cornell-box", 203, 149, 48, 2)
+    PC.shard_through_the_ring_is_the_shard_without_it()
 
 
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])

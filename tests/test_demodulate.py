@@ -14,8 +14,9 @@ import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
-import test_temporal as T
+import temporal_restated as T
 import util
+from frames import GUIDES, cached_frame, renders  # noqa: F401
 
 F = np.float32
 MODULATE_EXPORTS = ("crt_modulate_defaults", "crt_demodulate", "crt_demodulate_device", "crt_modulate", "crt_modulate_device")
@@ -184,38 +185,11 @@ def test_restatement_round_trip(albedo_floor):
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-GUIDES = ("albedo", "normal", "depth")
-_frames = {}
-
-
 def frame_of(renders, name, width, height, spp, seed=0, cam=None, variance=True):
-    """A GPU render (with its variance) and the shading pass with the guides from the same trace, rendered once per module:
+    """A GPU render (with its variance) and the shading pass with the guides from the same trace, rendered once:
     {rgb, color, variance, emission, diffuse_albedo, albedo, normal, depth, material}"""
-    key = (name, width, height, spp, seed, None if cam is None else tuple(np.asarray(cam[0], dtype=F)), variance)
-    if key not in _frames:
-        r = renders[name]
-        cam_ = cam if cam is not None else util.camera(name)
-        r.set_spp(spp)
-        r.seed = seed
-        try:
-            rgb = r.run_view(*cam_, width=width, height=height, want_variance=variance).copy()
-            out = {"rgb": rgb, "color": r.mean_buffer.copy(), "variance": r.variance_buffer.copy() if variance else None}
-            out.update(r.run_view_aov_shading(*cam_, first=GUIDES + ("material",), width=width, height=height))
-        finally:
-            r.seed = 0
-        _frames[key] = out
-    return _frames[key]
+    f = cached_frame(renders, name, width, height, spp, seed=seed, cam=cam, want_variance=variance, shading=GUIDES + ("material",))
+    return dict(f, color=f["mean"])
 
 
 def check_pair(color, albedo, emission, variance, albedo_floor, where):

@@ -17,6 +17,7 @@ from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
+from frames import GUIDES, gpu_frame, renders  # noqa: F401
 
 DENOISE_EXPORTS = ("crt_denoise_defaults", "crt_denoise_scratch_bytes", "crt_denoise", "crt_denoise_device")
 DEFAULTS = {"iterations": 3, "sigma_color": 4.0, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
@@ -161,29 +162,10 @@ def test_denoise_arguments_are_checked_before_any_device_call():
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
 def frame_and_guides(r, name, width, height, spp, seed=0):
     """(rgb, mean, {albedo, normal, depth}) of a GPU render and its AOV pass"""
-    eye, iv, fov = util.camera(name)
-    r.set_spp(spp)
-    r.seed = seed
-    try:
-        rgb = r.run_view(eye, iv, fov, width=width, height=height).copy()
-        mean = r.mean_buffer.copy()
-        g = r.run_view_aov(eye, iv, fov, want=("albedo", "normal", "depth"), width=width, height=height)
-    finally:
-        r.seed = 0
-    return rgb, mean, g
+    f = gpu_frame(r, name, width, height, spp, seed=seed, aov=GUIDES)
+    return f["rgb"], f["mean"], {k: f[k] for k in GUIDES}
 
 
 @pytest.mark.gpu

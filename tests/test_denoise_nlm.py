@@ -17,6 +17,7 @@ from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
+from frames import GUIDES, gpu_frame, renders  # noqa: F401
 
 DEFAULTS = {"radius": 5, "patch": 1, "k": 0.7, "alpha": 1.0, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
 K3 = np.array([1.0 / 4, 1.0 / 2, 1.0 / 4], dtype=np.float32)
@@ -250,29 +251,10 @@ def test_restatement_gives_no_weight_across_a_step(radius, patch, k):
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
 def frame_and_guides(r, name, width, height, spp, seed=0):
     """(rgb, mean, variance, {albedo, normal, depth}) of a GPU render with the flag and its AOV pass"""
-    eye, iv, fov = util.camera(name)
-    r.set_spp(spp)
-    r.seed = seed
-    try:
-        rgb = r.run_view(eye, iv, fov, width=width, height=height, want_variance=True).copy()
-        mean, var = r.mean_buffer.copy(), r.variance_buffer.copy()
-        g = r.run_view_aov(eye, iv, fov, want=("albedo", "normal", "depth"), width=width, height=height)
-    finally:
-        r.seed = 0
-    return rgb, mean, var, g
+    f = gpu_frame(r, name, width, height, spp, seed=seed, want_variance=True, aov=GUIDES)
+    return f["rgb"], f["mean"], f["variance"], {k: f[k] for k in GUIDES}
 
 
 @pytest.mark.gpu

@@ -17,7 +17,7 @@ import pytest
 
 import cudaraytracing_amd as crt
 import oracle_lib as O
-import test_commit_ring as R
+import parity_cases as PC
 import util
 
 pytestmark = pytest.mark.gpu
@@ -29,7 +29,7 @@ def test_first_frames_of_fresh_renders_after_other_work():
     eye, iv, fov = util.camera(name)
     _, omean, _, _ = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n)
     for rep in range(6):
-        R.test_the_flag_picks_a_ring_and_one_launch()   # other renders of the same scene: sizes, flags and traversal modes of their own
+        PC.flag_picks_a_ring_and_one_launch()   # other renders of the same scene: sizes, flags and traversal modes of their own
         r = crt.Render(util.host_scene(name), spp, t.P_RR, t.light_sample_n, device=0)
         try:
             for frame in range(2):

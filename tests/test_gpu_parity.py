@@ -10,22 +10,14 @@ import pytest
 
 import cudaraytracing_amd as crt
 import oracle_lib as O
+import parity_cases as PC
 import util
+from frames import renders  # noqa: F401
+from parity_cases import _compare_room
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5  # north-star tolerance on the float radiance buffer
-
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
 
 
 def test_device_present():
@@ -314,206 +306,32 @@ def test_errors_are_reported_not_printed(renders):
 # Edge cases the reference's data model allows: other leaf sizes (bvh_thresh_n), no / several NEE
 # samples, paths that run into the 64-vertex bounce cap, one-leaf trees, every pipeline variant.
 # ----------------------------------------------------------------------------------------------
-def _write_box_scene(d, n_side=6, specular=False, light=True):
-    """A small closed room with an emissive quad and a tessellated floor (2 * n_side^2 + 12 triangles)."""
-    import os
-    v, f = [], []
-
-    def quad(a, b, c, e, mtl):
-        i = len(v)
-        v.extend([a, b, c, e])
-        f.append((mtl, i + 1, i + 2, i + 3))
-        f.append((mtl, i + 1, i + 3, i + 4))
-    S = 10.0
-    step = S / n_side
-    for i in range(n_side):
-        for j in range(n_side):
-            x0, z0 = i * step, j * step
-            quad((x0, 0, z0), (x0, 0, z0 + step), (x0 + step, 0, z0 + step), (x0 + step, 0, z0), "floor")
-    quad((0, S, 0), (S, S, 0), (S, S, S), (0, S, S), "wall")             # ceiling (faces down)
-    quad((0, 0, S), (0, S, S), (S, S, S), (S, 0, S), "wall")             # back wall, faces -z
-    quad((0, 0, 0), (S, 0, 0), (S, S, 0), (0, S, 0), "wall")             # front wall behind the camera, faces +z
-    quad((0, 0, 0), (0, S, 0), (0, S, S), (0, 0, S), "wall")             # x = 0, faces +x
-    quad((S, 0, 0), (S, 0, S), (S, S, S), (S, S, 0), "plate" if specular else "wall")  # x = S, faces -x
-    if light:
-        quad((4, S - 0.01, 4), (6, S - 0.01, 4), (6, S - 0.01, 6), (4, S - 0.01, 6), "light")
-    with open(os.path.join(d, "room.mtl"), "w") as m:
-        m.write("newmtl floor\nKd 0.7 0.6 0.5\nNs 1\nnewmtl wall\nKd 0.5 0.5 0.7\nNs 1\n"
-                "newmtl plate\nKd 0.1 0.2 0.3\nNs 500\nnewmtl light\nKe 30 25 20\nKd 0 0 0\nNs 1\n")
-    with open(os.path.join(d, "room.obj"), "w") as o:
-        o.write("mtllib room.mtl\n")
-        for p in v:
-            o.write("v %g %g %g\nvn 0 1 0\nvt 0 0\n" % p)
-        cur = None
-        for mtl, a, b, c in f:
-            if mtl != cur:
-                o.write("usemtl %s\n" % mtl)
-                cur = mtl
-            o.write("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (a, a, a, b, b, b, c, c, c))
-    return os.path.join(d, "room.obj"), d
-
-
-def _compare_room(tmp_path, thresh, lsn, p_rr, spp, specular=False, w=48, h=36, seed=3, n_side=6, extra_flags=0, light=True):
-    obj, mtl = _write_box_scene(str(tmp_path), n_side=n_side, specular=specular, light=light)
-    scene = crt.Scene(w, h)
-    scene.add_obj(obj, mtl)
-    scene.set_BVH(thresh)
-    osc = O.OracleScene([(obj, mtl)], thresh)
-    assert scene.nodes().tobytes() == osc.nodes().tobytes()
-    eye = np.array([5.0, 5.0, 0.5], dtype=np.float32)
-    iv = crt.get_inverse_view_matrix(eye, [5.0, 4.0, 9.0], [0.0, 1.0, 0.0])
-    fov = crt.fov_to_radians(70.0)
-    r = crt.Render(scene, spp, p_rr, lsn)
-    r.seed = seed
-    r.extra_flags = extra_flags
-    orgb, omean, _, st = osc.render(eye, iv, fov, w, h, spp, p_rr, lsn, seed=seed)
-    try:
-        for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
-            r.traversal = mode
-            rgb = r.run_view(eye, iv, fov)
-            assert np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), (thresh, lsn, p_rr, mode)
-            assert np.array_equal(rgb, orgb)
-            assert r.stats["rays"] == st["rays"] and r.stats["probe_rays"] == st["probe_rays"]
-    finally:
-        r.free()
-    return st
-
-
 @pytest.mark.parametrize("thresh", [1, 2, 3, 5, 20, 200])
 def test_other_leaf_sizes(tmp_path, thresh):
-    """bvh_thresh_n other than 2: leaves with 1, 3..5, more than 15 triangles, and a tree that is one leaf."""
-    st = _compare_room(tmp_path, thresh, lsn=1, p_rr=0.6, spp=3)
-    assert st["rays"] > 5000
+    PC.room_matches_oracle_at_leaf_size(tmp_path, thresh)
 
 
 def test_leaf_of_300_triangles(tmp_path):
-    """The whole 300-triangle room as ONE leaf (150 triangle-pair records, best-triangle offsets beyond 8 bits)."""
-    st = _compare_room(tmp_path, 400, lsn=1, p_rr=0.6, spp=2, n_side=12)
-    assert st["rays"] > 5000
+    PC.room_that_is_one_leaf_of_300_triangles_matches_oracle(tmp_path)
 
 
 def test_room_of_180000_triangles(tmp_path):
-    """A floor tessellated into 180 000 triangles (node / triangle indices beyond 16 bits, an 18-level reference tree,
-    traversal stacks far beyond the three LDS levels)."""
-    st = _compare_room(tmp_path, 2, lsn=1, p_rr=0.6, spp=1, n_side=300, w=40, h=30)
-    assert st["rays"] > 3000
-
-
-def _write_soup_scene(d, n=400, dup=60, degenerate=20, seed=11):
-    """A closed room with a light and, inside it, a soup of random triangles: `dup` of them twice with identical vertices (equal
-    hit distances in different leaves: the reference's tie rule), `degenerate` with zero area (determinant 0: the division by it
-    is the IEEE one, not the short reciprocal), and coplanar overlapping quads."""
-    import os
-    rng = np.random.RandomState(seed)
-    obj, mtl = _write_box_scene(d, n_side=4)
-    tris = []
-    for _ in range(n):
-        c = rng.uniform(1.5, 8.5, 3)
-        tris.append(c + rng.uniform(-0.9, 0.9, (3, 3)))
-    for i in rng.choice(n, dup, replace=False):
-        tris.append(tris[i].copy())                       # exact duplicates
-    for _ in range(degenerate):
-        p, q = rng.uniform(2, 8, 3), rng.uniform(2, 8, 3)
-        tris.append(np.stack([p, q, p + 0.5 * (q - p)]))  # collinear vertices
-    for z in (3.0, 3.0, 6.0):                             # coplanar overlapping quads (two of them in the same plane)
-        x0, y0 = rng.uniform(2, 5, 2)
-        tris.append(np.array([[x0, y0, z], [x0 + 3, y0, z], [x0 + 3, y0 + 3, z]]))
-        tris.append(np.array([[x0, y0, z], [x0 + 3, y0 + 3, z], [x0, y0 + 3, z]]))
-    with open(obj) as f:
-        nv = sum(1 for line in f if line.startswith("v "))
-    with open(obj, "a") as o:
-        o.write("usemtl floor\n")
-        for t in tris:
-            for v in t.astype(np.float32):
-                o.write("v %.9g %.9g %.9g\nvn 0 1 0\nvt 0 0\n" % tuple(v))
-            o.write("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % (nv + 1, nv + 1, nv + 1, nv + 2, nv + 2, nv + 2, nv + 3, nv + 3, nv + 3))
-            nv += 3
-    return obj, mtl
+    PC.room_of_180000_triangles_matches_oracle(tmp_path)
 
 
 @pytest.mark.parametrize("thresh", [1, 2, 4])
 def test_triangle_soup_with_ties_and_degenerate_triangles(tmp_path, thresh):
-    obj, mtl = _write_soup_scene(str(tmp_path))
-    w, h, spp = 64, 48, 2
-    scene = crt.Scene(w, h)
-    scene.add_obj(obj, mtl)
-    scene.set_BVH(thresh)
-    osc = O.OracleScene([(obj, mtl)], thresh)
-    assert scene.nodes().tobytes() == osc.nodes().tobytes()
-    eye = np.array([5.0, 5.0, 0.5], dtype=np.float32)
-    iv = crt.get_inverse_view_matrix(eye, [5.0, 4.5, 9.0], [0.0, 1.0, 0.0])
-    fov = crt.fov_to_radians(75.0)
-    r = crt.Render(scene, spp, 0.6, 2)
-    r.seed = 5
-    orgb, omean, _, st = osc.render(eye, iv, fov, w, h, spp, 0.6, 2, seed=5)
-    try:
-        for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
-            r.traversal = mode
-            rgb = r.run_view(eye, iv, fov)
-            assert np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), mode
-            assert np.array_equal(rgb, orgb)
-            assert r.stats["rays"] == st["rays"]
-        # closest-hit queries straight at the duplicated / coplanar triangles: triangle ids must agree, not only distances
-        n = 4096
-        rng = np.random.RandomState(1)
-        o = np.tile(eye, (n, 1)).astype(np.float32)
-        dd = (rng.uniform([1.5, 1.5, 9.0], [8.5, 8.5, 9.0], (n, 3)) - eye).astype(np.float32)
-        for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
-            tri, t = r.intersect(o, dd, traversal=mode)
-            otri, ot, _ = osc.intersect(o, dd)
-            assert np.array_equal(tri, otri) and np.array_equal(util.bits(t), util.bits(ot)), mode
-    finally:
-        r.free()
-
-
-def _write_scaled_soup_scene(d, scale):
-    """The smaller soup scene with every vertex coordinate multiplied by `scale` (rounded to float32)"""
-    obj, mtl = _write_soup_scene(d, n=200, dup=20, degenerate=10)
-    lines = open(obj).read().split("\n")
-    with open(obj, "w") as f:
-        for line in lines:
-            if line.startswith("v "):
-                x, y, z = (np.float32(float(v) * scale) for v in line.split()[1:4])
-                line = "v %.9g %.9g %.9g" % (x, y, z)
-            f.write(line + "\n")
-    return obj, mtl
+    PC.soup_with_ties_and_degenerate_triangles_matches_oracle(tmp_path, thresh)
 
 
 @pytest.mark.parametrize("scale", [1e-12, 1e12, 1e17])
 def test_extreme_coordinate_scales(tmp_path, scale):
-    """The soup scene with every coordinate scaled: products underflow to denormals / overflow to inf, NaNs appear in the
-    radiance (1e12) -- kernel and oracle must still agree bit for bit (the NaNs included), in both traversal modes."""
-    obj, mtl = _write_scaled_soup_scene(str(tmp_path), scale)
-    w, h, spp = 48, 36, 2
-    scene = crt.Scene(w, h)
-    scene.add_obj(obj, mtl)
-    scene.set_BVH(2)
-    osc = O.OracleScene([(obj, mtl)], 2)
-    assert scene.nodes().tobytes() == osc.nodes().tobytes()
-    eye = (np.array([5.0, 5.0, 0.5]) * scale).astype(np.float32)
-    iv = crt.get_inverse_view_matrix(eye, (np.array([5.0, 4.5, 9.0]) * scale).astype(np.float32), [0.0, 1.0, 0.0])
-    fov = crt.fov_to_radians(75.0)
-    r = crt.Render(scene, spp, 0.6, 2)
-    r.seed = 5
-    orgb, omean, _, st = osc.render(eye, iv, fov, w, h, spp, 0.6, 2, seed=5)
-    try:
-        for mode in (crt.TRAVERSAL_REFERENCE, crt.TRAVERSAL_FAST, crt.TRAVERSAL_EXACT):
-            r.traversal = mode
-            rgb = r.run_view(eye, iv, fov)
-            assert np.array_equal(util.bits(r.mean_buffer), util.bits(omean)), (scale, mode)
-            assert np.array_equal(rgb, orgb)
-            assert r.stats["rays"] == st["rays"]
-    finally:
-        r.free()
+    PC.scaled_soup_matches_oracle(tmp_path, scale)
 
 
 @pytest.mark.parametrize("specular", [False, True])
 def test_rays_with_non_finite_operands_take_the_reference_arithmetic(tmp_path, specular):
-    """CRT_FLAG_FORCE_EXACT sends every ray of the FAST traversal down the path that rays with a zero / denormal direction
-    component take: reference box arithmetic (sign-selected planes, NaN-aware comparisons) on the reference topology, still
-    pruned and any-hit.  Nothing changes."""
-    st = _compare_room(tmp_path, 2, lsn=2, p_rr=0.7, spp=3, specular=specular, extra_flags=crt.FLAG_FORCE_EXACT)
-    assert st["rays"] > 5000
+    PC.room_with_every_ray_on_the_reference_arithmetic_matches_oracle(tmp_path, specular)
 
 
 def test_scene_without_emitters(tmp_path):

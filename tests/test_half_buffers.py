@@ -6,7 +6,6 @@ include/crt.h is restated below in numpy float32, operation by operation, in the
 match it on uint32 views.  37 x 21 is ragged against the 8 x 8 tiles in both directions (15 tiles, 960 pixel slots).
 """
 import ctypes as C
-import functools
 import inspect
 
 import numpy as np
@@ -16,7 +15,8 @@ import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import util
-from util import assert_bits, restated_sums
+from frames import gpu_frame, oracle_frame, renders  # noqa: F401
+from util import assert_bits
 
 F = np.float32
 W, H = 37, 21
@@ -105,40 +105,16 @@ def test_restated_halves_are_the_float64_half_means():
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in SCENES:
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(name, spp):
-    """(rgb, mean, L (H, W, spp, 3)) of the oracle with the scene's own P_RR and light_sample_n; computed once per scene and spp"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, W, H, spp, t.P_RR, t.light_sample_n, seed=0, want_L=True)
-    c, _ = restated_sums(L, spp, spp)
-    assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
-    return rgb, mean, L
-
-
 def gpu_halves(r, name, spp, want_halves=True, want_variance=False):
-    eye, iv, fov = util.camera(name)
-    r.set_spp(spp)
-    rgb = r.run_view(eye, iv, fov, width=W, height=H, want_halves=want_halves, want_variance=want_variance).copy()
-    return rgb, r.mean_buffer.copy(), r.variance_buffer, r.half_a_buffer, r.half_b_buffer
+    f = gpu_frame(r, name, W, H, spp, want_halves=want_halves, want_variance=want_variance)
+    return f["rgb"], f["mean"], f["variance"], f["half_a"], f["half_b"]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", SCENES)
 @pytest.mark.parametrize("spp", [8, 7, 2])
 def test_halves_match_the_restatement_on_the_oracles_radiance(renders, name, spp):
-    orgb, omean, L = oracle_frame(name, spp)
+    orgb, omean, L = oracle_frame(name, W, H, spp)
     want_a, want_b = restated_halves(L, spp)
     assert (want_a > 0).any() and (want_b > 0).any() and not np.array_equal(want_a, want_b)
     rgb, mean, var, a, b = gpu_halves(renders[name], name, spp)
@@ -169,7 +145,7 @@ def test_halves_of_a_progressive_render_keep_the_frames_parity(pipeline, monkeyp
     r = crt.Render(util.host_scene(name), spp, t.P_RR, t.light_sample_n)   # a fresh handle
     try:
         eye, iv, fov = util.camera(name)
-        orgb, omean, L = oracle_frame(name, spp)
+        orgb, omean, L = oracle_frame(name, W, H, spp)
         kw = dict(width=W, height=H)
         with pytest.raises(crt.CrtError) as e:
             r.half_buffers(**kw)                                            # no render with the flag yet
@@ -205,7 +181,7 @@ def test_halves_of_a_progressive_render_keep_the_frames_parity(pipeline, monkeyp
 @pytest.mark.parametrize("name", SCENES)
 def test_halves_are_the_same_across_chunks_and_pipelines(renders, name, monkeypatch):
     spp = 7
-    orgb, omean, L = oracle_frame(name, spp)
+    orgb, omean, L = oracle_frame(name, W, H, spp)
     want_a, want_b = restated_halves(L, spp)
 
     def check(where):
@@ -233,7 +209,7 @@ def test_halves_of_a_tiled_shard(renders):
     """Rank 1 of 3 with CRT_FLAG_TILED_OUTPUT: the shard's compact tiles, padding slots +0"""
     name, spp, rank, world = "veach-mis", 7, 1, 3
     r = renders[name]
-    _, _, L = oracle_frame(name, spp)
+    _, _, L = oracle_frame(name, W, H, spp)
     want = restated_halves(L, spp)
     eye, iv, fov = util.camera(name)
     cam = r._cam(eye, iv, fov)
@@ -265,7 +241,7 @@ def test_halves_of_a_tiled_shard(renders):
 def test_halves_device_form_on_a_stream(renders):
     name, spp = "cornell-box", 7
     r = renders[name]
-    orgb, omean, L = oracle_frame(name, spp)
+    orgb, omean, L = oracle_frame(name, W, H, spp)
     want_a, want_b = restated_halves(L, spp)
     eye, iv, fov = util.camera(name)
     table = {"rgb": (3, np.uint8), "mean": (3, F), "a": (3, F), "b": (3, F)}

@@ -9,7 +9,6 @@ float32 operation by operation as the header states the contract:
 Every comparison is on uint32 views (NaN matches NaN) or on the RGB bytes.
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -19,6 +18,8 @@ from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
+from frames import fresh_render, oracle_frame, renders  # noqa: F401
+from scene_files import _write_scaled_soup_scene
 from util import assert_bits, restated_sums
 
 F = np.float32
@@ -70,35 +71,6 @@ def test_restatement_is_the_mean_of_the_samples_so_far():
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in SCENES:
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-def fresh_render(name, spp):
-    t = util.task(name)
-    return crt.Render(util.host_scene(name), spp, t.P_RR, t.light_sample_n)
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(name, w, h, spp):
-    """(rgb, mean, L (h, w, spp, 3)) of the oracle with the scene's own P_RR and light_sample_n, seed 0"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n, want_L=True)
-    c, _ = restated_sums(L, spp, spp)
-    assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
-    assert np.array_equal(O.tonemap(c), rgb)
-    for a in (rgb, mean, L):
-        a.flags.writeable = False
-    return rgb, mean, L
 
 
 def check_preview(r, L, S, n, w, h, where, times=1):
@@ -350,7 +322,6 @@ SOUP = dict(scale=1e12, w=48, h=36, S=4, n=2, seed=5, p_rr=0.6, lsn=2)
 
 
 def soup_scene(d):
-    from test_gpu_parity import _write_scaled_soup_scene
     obj, mtl = _write_scaled_soup_scene(str(d), SOUP["scale"])
     eye = (np.array([5.0, 5.0, 0.5]) * SOUP["scale"]).astype(F)
     iv = crt.get_inverse_view_matrix(eye, (np.array([5.0, 4.5, 9.0]) * SOUP["scale"]).astype(F), [0.0, 1.0, 0.0])

@@ -8,7 +8,6 @@ between chunks would show.
 The frame: cornell-box 44 x 20 (6 x 3 tiles of 8 x 8, ragged in both directions: 1 152 pixel slots for 880 pixels) at spp 5.
 """
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
@@ -16,9 +15,9 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 import util
-from util import assert_bits, restated_sums
-from test_adaptive import restated_adaptive
-from test_variance import restated_variance
+from frames import oracle_render
+from util import assert_bits
+from variance_restated import restated_adaptive, restated_variance
 
 F = np.float32
 NAME, W, H, SPP = "cornell-box", 44, 20, 5
@@ -26,23 +25,6 @@ NSLOTS = 6 * 3 * 64
 COUNTERS = ("paths", "rays", "shadow_rays", "probe_rays")
 MODES = [crt.TRAVERSAL_EXACT, crt.TRAVERSAL_REFERENCE]
 PIPELINES = ["4", "2"]   # CRT_PIPELINE: the megakernel, the wavefront fallback
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(name=NAME, w=W, h=H, spp=SPP, crop=None):
-    """(rgb, mean, L (h, w, spp, 3) or None for a crop, stats) of the oracle with the scene's own P_RR and light_sample_n, seed 0"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    if crop:
-        rgb, mean, L, st = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n, seed=0, crop=crop)
-    else:
-        rgb, mean, L, st = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n, seed=0, want_L=True)
-        c, _ = restated_sums(L, spp, spp)
-        assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
-    for a in (rgb, mean, L):
-        if a is not None:
-            a.flags.writeable = False
-    return rgb, mean, L, st
 
 
 @pytest.fixture(scope="module")
@@ -70,13 +52,13 @@ def frame(r, stats=False, want_variance=False, w=W, h=H):
 
 
 def check_frame(rgb, mean, where, want=None):
-    orgb, omean = (want or oracle_frame())[:2]
+    orgb, omean = (want or oracle_render(NAME, W, H, SPP))[:2]
     assert_bits(mean, omean, where + ": mean")
     assert np.array_equal(rgb, orgb), where + ": RGB8"
 
 
 def check_counters(st, where, want=None):
-    ost = want or oracle_frame()[3]
+    ost = want or oracle_render(NAME, W, H, SPP)[3]
     for k in COUNTERS:
         assert st[k] == ost[k], (where, k, st[k], ost[k])
 
@@ -93,7 +75,7 @@ def test_ragged_frame_whole_and_as_a_shard(render, mode, pipeline, monkeypatch):
     check_frame(rgb, mean, where)
     check_counters(st, where)
     # rank 1 of 3, tiled: local tile lt is tile 3 lt + 1 of the frame's 18; every slot against the oracle's pixel, padding slots +0 / 0
-    orgb, omean = oracle_frame()[:2]
+    orgb, omean = oracle_render(NAME, W, H, SPP)[:2]
     eye, iv, fov = util.camera(NAME)
     rank, world = 1, 3
     slots = crt.shard_slots(W, H, rank, world)
@@ -146,7 +128,7 @@ def test_variance_sums_and_an_adaptive_pass(render, monkeypatch):
     """fold_samples' VAR arm (k_accumulate_var, the adaptive accumulate): expected values restated in numpy float32 on the oracle's
     per-path radiance, as tests/test_variance.py and tests/test_adaptive.py do"""
     r = render
-    L = oracle_frame()[2]
+    L = oracle_render(NAME, W, H, SPP)[2]
     want_var = restated_variance(L, SPP)
     assert (want_var > 0).any()
     for chunk_log2 in (None, "11"):
@@ -215,7 +197,7 @@ def test_render_intersect_render_on_one_handle(mode):
 
         r.set_spp(1)
         rgb, mean, _ = frame(r, w=8, h=8)
-        check_frame(rgb, mean, "8 x 8 spp 1", want=oracle_frame(NAME, 8, 8, 1))
+        check_frame(rgb, mean, "8 x 8 spp 1", want=oracle_render(NAME, 8, 8, 1))
         assert r.radiance_storage()[0] == 12 * 64
         rays("after the tiny frame")
         r.set_spp(SPP)
@@ -247,7 +229,7 @@ def test_deep_paths_through_specular_vertices(mode):
     1 748 probe rays in the crop), so the backward recursion reads cosines and the records of the incoming directions together"""
     name, spp, crop = "veach-mis", 8, (368, 268, 32, 24)
     t = util.task(name)
-    orgb, omean, _, ost = oracle_frame(name, t.width, t.height, spp, crop)
+    orgb, omean, _, ost = oracle_render(name, t.width, t.height, spp, crop=crop)
     assert ost["probe_rays"] > 1000 and ost["rays"] > 7 * ost["paths"]
     eye, iv, fov = util.camera(name)
     r = crt.Render(util.host_scene(name), spp, t.P_RR, t.light_sample_n)

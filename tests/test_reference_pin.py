@@ -26,7 +26,7 @@ import pytest
 import cudaraytracing_amd as crt
 import reference_pin as RP
 import util
-from test_adversarial_traversal import _oracle_blocked
+from blocked_restated import _oracle_blocked
 
 META = RP.load_meta()
 SCENE_IDS = [c[0] for c in RP.SCENE_CASES]
@@ -69,7 +69,7 @@ def case_of(cid):
     return [c for c in RP.FRAME_CASES if c["id"] == cid][0]
 
 
-def oracle_frame(cid, tmp):
+def case_frame(cid, tmp):
     """the oracle's frame of a case with its draw log: computed once, shared, never changed"""
     if cid not in _frames:
         case = case_of(cid)
@@ -120,7 +120,7 @@ def test_oracle_regenerates_tapes_rays_and_flags(cid, tmp):
     on the way back per vertex the triangle pick, alpha, beta of every next-event sample and the probe's two uniforms.  The probe
     consumed exactly these words in exactly this order when the fixtures were made (it fails when a tape runs out, and the number it
     consumed is compared below), so an oracle that draws another number of words, or in another order, regenerates another tape."""
-    g, of = gold("frame_" + cid), oracle_frame(cid, tmp)
+    g, of = gold("frame_" + cid), case_frame(cid, tmp)
     assert np.array_equal(of["lens"], g["lens"]), "words per path"
     assert np.array_equal(of["words"], g["words"]), "tape"
     assert np.array_equal(of["flags"], g["flags"]), "emitter-probe flags"
@@ -130,13 +130,13 @@ def test_oracle_regenerates_tapes_rays_and_flags(cid, tmp):
 
 
 def test_a_path_reaches_the_bounce_stack_cap(tmp):
-    assert oracle_frame("room-cap-spp1-rr1-lsn1", tmp)["stats"]["max_depth"] == 63   # BOUNCE_STACK_SIZE - 1: the stack is full (Render.cuh:210)
+    assert case_frame("room-cap-spp1-rr1-lsn1", tmp)["stats"]["max_depth"] == 63   # BOUNCE_STACK_SIZE - 1: the stack is full (Render.cuh:210)
 
 
 # ------------------------------------------------------------------------------------------------ paths and frames
 @pytest.mark.parametrize("cid", RP.FRAME_IDS)
 def test_oracle_path_radiance_is_cast_ray_v2s(cid, tmp):
-    g, of = gold("frame_" + cid), oracle_frame(cid, tmp)
+    g, of = gold("frame_" + cid), case_frame(cid, tmp)
     oL = of["L"].reshape(-1, 3)
     excl = excluded_paths(cid)
     same = same_bits(oL, g["L"]).all(axis=1)
@@ -152,7 +152,7 @@ def test_oracle_path_radiance_is_cast_ray_v2s(cid, tmp):
 
 @pytest.mark.parametrize("cid", RP.FRAME_IDS)
 def test_oracle_frame_bytes_are_view_render_kernels(cid, tmp):
-    g, of, case = gold("frame_" + cid), oracle_frame(cid, tmp), case_of(cid)
+    g, of, case = gold("frame_" + cid), case_frame(cid, tmp), case_of(cid)
     excl_px = excluded_paths(cid).reshape(-1, case["spp"]).any(axis=1).reshape(case["h"], case["w"])
     same = (of["rgb"] == g["rgb"]).all(axis=2)
     assert same[~excl_px].all(), "%d pixels differ from the reference" % (~same[~excl_px]).sum()
@@ -297,7 +297,7 @@ def _set_kernel(monkeypatch, kernel):
 
 
 @pytest.fixture(scope="module")
-def renders(tmp):
+def pinned_renders(tmp):
     out = {}
     for name in ("cornell-box", "veach-mis"):
         out[name] = crt.Render(util.host_scene(name), 1, 0.6, 1)
@@ -311,12 +311,12 @@ def renders(tmp):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kernel", list(KERNELS))
 @pytest.mark.parametrize("name", [c[0] for c in RP.INTERSECT_CASES])
-def test_gpu_intersect_gives_the_references_hits(renders, name, kernel, monkeypatch):
+def test_gpu_intersect_gives_the_references_hits(pinned_renders, name, kernel, monkeypatch):
     """crt_intersect against DeviceBVH::intersect's recorded hit (triangle, t on its bits) and blocked()'s recorded verdict, in the
     three traversal modes"""
     g = gold("intersect_" + name)
     _set_kernel(monkeypatch, kernel)
-    r = renders[name]
+    r = pinned_renders[name]
     for mode in MODES:
         tri, t = r.intersect(g["origin"], g["dir"], traversal=mode)
         assert np.array_equal(tri, g["tri"]), (kernel, mode)
@@ -328,7 +328,7 @@ def test_gpu_intersect_gives_the_references_hits(renders, name, kernel, monkeypa
 @pytest.mark.gpu
 @pytest.mark.parametrize("kernel", list(KERNELS))
 @pytest.mark.parametrize("cid", RP.FRAME_IDS)
-def test_gpu_frames_are_the_references(renders, cid, kernel, monkeypatch):
+def test_gpu_frames_are_the_references(pinned_renders, cid, kernel, monkeypatch):
     """Render.run_view: mean_buffer against util.restated_sums of the reference's recorded per-path radiance, RGB against the
     reference's recorded bytes.  A flagged path takes its radiance, a pixel that holds one its bytes, from the unoptimised build's
     record (see the module docstring): every path and every pixel is compared."""
@@ -339,7 +339,7 @@ def test_gpu_frames_are_the_references(renders, cid, kernel, monkeypatch):
         rgb_ref.reshape(-1, 3)[g["flagged_pixels"]] = g["flagged_rgb_unopt"]
     want, _ = util.restated_sums(L.reshape(case["h"], case["w"], case["spp"], 3), case["spp"], case["spp"])
     _set_kernel(monkeypatch, kernel)
-    r = renders[case["scene"]]
+    r = pinned_renders[case["scene"]]
     r.set_spp(case["spp"]); r.set_P_RR(case["p_rr"]); r.set_light_sample_n(case["lsn"])
     r.seed = case["seed"]
     if case["scene"] == "room":

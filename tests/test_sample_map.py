@@ -24,14 +24,18 @@ import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
+import adaptive_frames as TA
 import util
+from frames import oracle_frame, renders  # noqa: F401
 from util import assert_bits, restated_sums
+from variance_restated import restated_adaptive, variance_of_sums
 
 F = np.float32
 SCENES = ["cornell-box", "veach-mis"]
 MAP_EXPORTS = ("crt_render_map", "crt_render_map_device", "crt_sample_plan", "crt_sample_plan_device", "crt_render_planned",
                "crt_render_planned_device")
 W, H, S = 37, 27, 29
+RENDER_SPP = S     # (what frames.renders creates the handles with)
 PLAN = dict(min_samples=4, threshold=0.2, mean_floor=0.01)
 # pixels at n_p = min_samples, pixels at the cap, fewest pixels at any value between, paths
 EXPECTED = {"cornell-box": (427, 198, 6, 12781), "veach-mis": (440, 30, 5, 8683)}
@@ -48,13 +52,6 @@ def ragged_map():
 def counts_of(m, sample_begin=0):
     """n_p = min(max(map[p], max(sample_begin, 1)), S)"""
     return np.minimum(np.maximum(np.asarray(m, dtype=np.uint32), np.uint32(max(sample_begin, 1))), np.uint32(S))
-
-
-def variance_of_sums(c, q, fn, r):
-    """crt_variance's formula; fn, r: float32 scalars or (h, w, 1) arrays"""
-    d = fn * q - c * c
-    d = np.where(d < F(0.0), F(0.0), d)
-    return ((r * r) * d) / (fn - F(1.0))
 
 
 def restated_map(L, n_p, sample_begin=0):
@@ -172,21 +169,10 @@ def test_map_refusals_come_before_any_device_call():
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_frame(name):
-    """(rgb, mean, L (H, W, S, 3)) of the oracle at the tests' shape with the scene's own P_RR and light_sample_n, seed 0"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, W, H, S, t.P_RR, t.light_sample_n, want_L=True)
-    for a in (rgb, mean, L):
-        a.flags.writeable = False
-    return rgb, mean, L
-
-
-@functools.lru_cache(maxsize=None)
 def restated(name, kind, **kw):
     """Restated frames, computed once: kind "ragged" (the ragged map from sample 0), "floor4" (max(ragged map, 4)), "planned" (kw
     overrides PLAN: range + plan + map)"""
-    _, _, L = oracle_frame(name)
+    _, _, L = oracle_frame(name, W, H, S)
     if kind == "ragged":
         got = restated_map(L, counts_of(ragged_map()))
     elif kind == "floor4":
@@ -204,7 +190,7 @@ def restated(name, kind, **kw):
 
 @pytest.mark.parametrize("name", SCENES)
 def test_restated_map_at_the_cap_is_the_oracles_mean(name):
-    orgb, omean, L = oracle_frame(name)
+    orgb, omean, L = oracle_frame(name, W, H, S)
     got = restated_map(L, np.full((H, W), S, dtype=np.uint32))
     assert_bits(got["mean"], omean, "map == S")
     assert np.array_equal(got["rgb"], orgb) and got["paths"] == W * H * S
@@ -215,7 +201,7 @@ def test_restated_map_at_the_cap_is_the_oracles_mean(name):
 @pytest.mark.parametrize("name", SCENES)
 def test_restated_plan_is_the_recorded_distribution(name):
     """If this fails the inputs are wrong, not the kernel."""
-    _, _, L = oracle_frame(name)
+    _, _, L = oracle_frame(name, W, H, S)
     n_p, w = restated_plan(L, PLAN["min_samples"], PLAN["threshold"], PLAN["mean_floor"])
     assert np.isfinite(w).all(), "the NaN / inf arm is covered by the two threshold limits, not by these frames"
     at_min, at_cap, fewest, paths = EXPECTED[name]
@@ -233,10 +219,9 @@ def test_restated_plan_is_the_recorded_distribution(name):
 def test_restated_map_of_the_adaptive_counts_is_the_adaptive_frame(name):
     """An adaptive frame is the map frame of its own sample counts: both fold samples 0 .. n_p - 1 of a pixel in order.  If this fails
     the inputs are wrong, not the kernels."""
-    import test_adaptive as TA
     assert (TA.W, TA.H, TA.S) == (W, H, S)
-    _, _, L = oracle_frame(name)
-    ad = TA.restated_adaptive(L, S, **TA.AD)
+    _, _, L = oracle_frame(name, W, H, S)
+    ad = restated_adaptive(L, S, **TA.AD)
     got = restated_map(L, ad["samples"])
     assert np.array_equal(got["samples"], ad["samples"]) and got["paths"] == ad["paths"]
     assert_bits(got["mean"], ad["mean"], "map of the adaptive counts: mean")
@@ -244,16 +229,6 @@ def test_restated_map_of_the_adaptive_counts_is_the_adaptive_frame(name):
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in SCENES:
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
 
 
 def result(r, rgb):
@@ -315,7 +290,7 @@ def test_map_frame_in_chunks_gives_the_same_bits(renders, name, monkeypatch):
     assert r.last_launch_ms()[1] == math.ceil(int(want["samples"].max()) / 3) == 10
     # a map whose largest count is no multiple of three and below the cap: the chunks beyond it are not launched
     m = np.minimum(ragged_map(), 14)
-    _, _, L = oracle_frame(name)
+    _, _, L = oracle_frame(name, W, H, S)
     check_frame(gpu_map(r, name, m), restated_map(L, counts_of(m)), name + ", small chunks, largest count 14", launches=5)
     assert r.last_launch_ms()[1] == 5
 
@@ -325,7 +300,7 @@ def test_map_frame_in_chunks_gives_the_same_bits(renders, name, monkeypatch):
 def test_uniform_maps_are_the_uniform_frame_and_the_first_sample(renders, name):
     r = renders[name]
     eye, iv, fov = util.camera(name)
-    orgb, omean, L = oracle_frame(name)
+    orgb, omean, L = oracle_frame(name, W, H, S)
     r.set_spp(S)
     rgb_u = r.run_view(eye, iv, fov, width=W, height=H, want_variance=True).copy()
     mean_u, var_u = r.mean_buffer.copy(), r.variance_buffer.copy()
@@ -348,7 +323,7 @@ def test_uniform_maps_are_the_uniform_frame_and_the_first_sample(renders, name):
 def test_map_continues_a_range_with_the_variance_sums(renders, name):
     r = renders[name]
     eye, iv, fov = util.camera(name)
-    orgb, omean, _ = oracle_frame(name)
+    orgb, omean, _ = oracle_frame(name, W, H, S)
     kw = dict(width=W, height=H)
     m = ragged_map()
     want = restated(name, "floor4")
@@ -382,7 +357,6 @@ def test_map_continues_a_range_with_the_variance_sums(renders, name):
 def test_map_of_the_adaptive_frames_samples_is_the_adaptive_frame(renders, name, chunk_log2, monkeypatch):
     """crt_render_adaptive's out_samples fed to crt_render_map from sample 0: the same frame, bit for bit -- the passes and the map's
     chunks fold through one kernel.  Once more with both calls in chunks of three samples."""
-    import test_adaptive as TA
     if chunk_log2:
         monkeypatch.setenv("CRT_CHUNK_LOG2", chunk_log2)
     r = renders[name]
@@ -465,7 +439,7 @@ def test_map_device_form_on_a_stream_matches_host_form(renders):
 def test_sample_plan_matches_restatement(renders, name):
     r = renders[name]
     eye, iv, fov = util.camera(name)
-    _, _, L = oracle_frame(name)
+    _, _, L = oracle_frame(name, W, H, S)
     kw = dict(width=W, height=H)
     r.set_spp(S)
     assert r.run_view_range(eye, iv, fov, 0, 4, want_variance=True, **kw) is None
@@ -500,7 +474,7 @@ def test_planned_frame_matches_range_plan_map_restated(name, monkeypatch):
     r = crt.Render(util.host_scene(name), S, t.P_RR, t.light_sample_n)   # a fresh handle
     try:
         eye, iv, fov = util.camera(name)
-        orgb, omean, L = oracle_frame(name)
+        orgb, omean, L = oracle_frame(name, W, H, S)
         kw = dict(width=W, height=H)
         want = restated(name, "planned")
         assert np.array_equal(want["plan"], want["samples"])

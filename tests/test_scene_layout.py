@@ -13,8 +13,7 @@ from cudaraytracing_amd import _capi as capi
 import host_program as HP
 import tree_check as TC
 import util
-from test_gpu_parity import _write_box_scene, _write_soup_scene
-from test_tree_invariants import _scene, write_signed_zero_scene
+from scene_files import _scene, _write_box_scene, _write_soup_scene, write_signed_zero_scene
 
 COUNTS = ["n_leaves", "n_nodes2", "n_nodes4", "depth2", "depth4", "index_splits", "layout_caps"]   # crt_accel_info without its clocks
 

@@ -19,9 +19,10 @@ from cudaraytracing_amd.hipmem import DeviceBuffers
 import host_program as HP
 import oracle_lib as O
 import temporal_dual_restated as D
-import test_temporal as T
-import test_temporal_clamp as TC
+import temporal_clamp_restated as TC
+import temporal_restated as T
 import util
+from frames import renders  # noqa: F401
 from util import assert_bits
 
 F = np.float32
@@ -299,9 +300,6 @@ def test_kernel_text_is_clean_under_the_sanitizers(host_check_run):
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-from test_temporal import renders  # noqa: E402,F401  (the module-scoped fixture: one Render per scene)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("radius", [1, 2, 3])
 @pytest.mark.parametrize("w,h", [(130, 9), (61, 47)])
@@ -372,7 +370,7 @@ def test_dual_non_finite_pixels():
 
 
 def spec_frames(renders, name, width, height, n, seed0, cameras=None):
-    """test_temporal.frames with the three specular planes of each frame in its dict (the pass runs with the frame's spp and seed)"""
+    """temporal_restated.frames with the three specular planes of each frame in its dict (the pass runs with the frame's spp and seed)"""
     fr = T.frames(renders, name, width, height, n, seed0) if cameras is None else [
         T.render_frame(renders[name], cam, width, height, 4, seed0 + f) + (cam,) for f, cam in enumerate(cameras)]
     out = []
@@ -405,7 +403,7 @@ def chain(fr, clamp, dual, where, check=True):
 @pytest.mark.parametrize("clamp", [None, (1, 1.0)], ids=["no clamp", "the clamp's defaults"])
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])
 def test_dual_rendered_chains_match_restatement(renders, name, clamp):
-    """Four chained frames of a moving camera (64 x 48, spp 4, seeds 100 .. 103, test_temporal's moves): an output is the next frame's
+    """Four chained frames of a moving camera (64 x 48, spp 4, seeds 100 .. 103, temporal_restated's moves): an output is the next frame's
     history, compared after every frame.  On the CPU oracle's frames (the device's, bit for bit) through the restatements, with the
     clamp's defaults, the last call on veach-mis tries V on 1055 pixels and takes it on 327 of the 3072 (10.6 %; the plates cover a
     third of the view); cornell-box has no mirror, tries nothing, and writes crt_temporal_clamped's bits."""

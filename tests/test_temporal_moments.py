@@ -2,9 +2,9 @@
 and temporal_device, variance_estimate, variance_estimate_device and Render.run_view_temporal(variance="moments") in Python; crt_cli
 --temporal-variance).
 
-The two contracts are restated in numpy float32.  crt_temporal_moments stands on test_temporal_clamp.restated_clamped, which stays the
+The two contracts are restated in numpy float32.  crt_temporal_moments stands on temporal_clamp_restated.restated_clamped, which stays the
 statement of everything the call shares with crt_temporal_clamped; the interpolated moments h1 / ws and h2 / ws are read out of
-test_temporal.restated by test_temporal_clamp.history_colour with a moment plane in the place of the history colour, and only the two
+temporal_restated.restated by temporal_clamp_restated.history_colour with a moment plane in the place of the history colour, and only the two
 blends are written here.  crt_variance_estimate is written out in full, with the oracle's det_expf.  The device results must match bit
 for bit, counts included.
 """
@@ -18,9 +18,10 @@ import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
-import test_temporal as T
-import test_temporal_clamp as TC
+import temporal_clamp_restated as TC
+import temporal_restated as T
 import util
+from frames import renders  # noqa: F401
 from util import assert_bits
 
 F = np.float32
@@ -520,9 +521,6 @@ def test_cli_refuses_a_variance_source_without_a_sequence_or_with_a_malformed_va
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
-
-from test_temporal import renders  # noqa: E402,F401  (the module-scoped fixture: one Render per scene)
-
 # The frame of the rendered chains on which the estimate is checked, and its min_history, picked with the restatement on the CPU
 # oracle's frames (the device's, bit for bit): with the library's clamp the last of the eight frames has 1012 (cornell-box) / 360
 # (veach-mis) of its 3072 pixels in the spatial branch at min_history 4 -- background, newly seen and rejected pixels -- and the rest
@@ -597,7 +595,7 @@ def test_estimate_on_rendered_chains_matches_restatement(renders, name, of_mean,
 
 
 def synthetic_moments(w, h, seed):
-    """test_temporal.synthetic with moment planes for its history; on a frame too small for its blocks of misses, none"""
+    """temporal_restated.synthetic with moment planes for its history; on a frame too small for its blocks of misses, none"""
     cur, cam, prev, pcam = T.synthetic(w, h, seed)
     if w < 32 or h < 24:
         cur["depth"][:] = 40.0
@@ -756,16 +754,7 @@ def test_moments_device_forms_on_a_stream_match_host_forms(renders):
 
 def render_frame_without_variance(r, cam, width, height, spp, seed):
     """A GPU render WITHOUT the variance flag (one sample per pixel has no per-sample variance) and its AOV pass"""
-    r.set_spp(spp)
-    r.seed = seed
-    try:
-        rgb = r.run_view(*cam, width=width, height=height).copy()
-        mean = r.mean_buffer.copy()
-        g = r.run_view_aov(*cam, want=("albedo", "normal", "depth", "material"), width=width, height=height)
-    finally:
-        r.seed = 0
-    cur = {"color": mean, "depth": g["depth"], "normal": g["normal"], "id": g["material"]}
-    return cur, rgb, {k: g[k] for k in ("albedo", "normal", "depth")}
+    return T.render_frame(r, cam, width, height, spp, seed, want_variance=False)
 
 
 def by_hand_at_spp1(renders, name, w, h, n, seed0, clamp=None, **estimate):

@@ -16,7 +16,7 @@ from cudaraytracing_amd import _capi as capi
 import oracle_lib as O
 import tree_check as TC
 import util
-from test_gpu_parity import _write_box_scene, _write_soup_scene
+from scene_files import _scene, _write_box_scene, _write_scaled_soup_scene, _write_soup_scene, write_signed_zero_scene
 
 sys.path.insert(0, os.path.join(util.ROOT, "scenes"))
 import gen_cornell_box  # noqa: E402
@@ -29,13 +29,6 @@ def _check(scene, render, stats=None):
     info = render.accel_info()
     v = TC.check_trees(ex, info, scene.nodes(), scene.root, scene.triangles(), stats)
     return ex, info, v
-
-
-def _scene(obj, mtl, thresh, w=32, h=24):
-    s = crt.Scene(w, h)
-    s.add_obj(obj, mtl)
-    s.set_BVH(thresh)
-    return s
 
 
 def _leaf_sizes(scene):
@@ -337,22 +330,10 @@ def test_trees_of_a_room_that_is_one_leaf(tmp_path):
         r.free()
 
 
-def _scaled_soup(d, scale):
-    obj, mtl = _write_soup_scene(d, n=200, dup=20, degenerate=10)
-    lines = open(obj).read().split("\n")
-    with open(obj, "w") as f:
-        for line in lines:
-            if line.startswith("v "):
-                x, y, z = (np.float32(float(v) * scale) for v in line.split()[1:4])
-                line = "v %.9g %.9g %.9g" % (x, y, z)
-            f.write(line + "\n")
-    return obj, mtl
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("scale", [1e-12, 1e12, 1e17])
 def test_trees_at_extreme_coordinate_scales(tmp_path, scale):
-    obj, mtl = _scaled_soup(str(tmp_path), scale)
+    obj, mtl = _write_scaled_soup_scene(str(tmp_path), scale)
     scene = _scene(obj, mtl, 2)
     r = crt.Render(scene, 1, 0.6, 1)
     try:
@@ -360,27 +341,6 @@ def test_trees_at_extreme_coordinate_scales(tmp_path, scale):
         assert v == [], v
     finally:
         r.free()
-
-
-def write_signed_zero_scene(d, n=240, seed=5, denormals=True):
-    """Triangles whose coordinates are +0.0, -0.0, denormals and small normals (and, per triangle, two coordinates from [2, 3], so that
-    no two leaves share a centroid): box planes at both zeros and at denormals, unions over +-0 (the sign the builders give them), and
-    nodes4i nudges that cross zero."""
-    rng = np.random.RandomState(seed)
-    vals = [0.0, -0.0, 0.25, 0.5, 1.0] + ([1e-45, 3e-42, 1e-39, 1.1754944e-38] if denormals else [])   # (lo planes at +0.0 nudged down cross zero)
-    vals = np.array(vals, np.float32)
-    with open(os.path.join(d, "zeros.mtl"), "w") as m:
-        m.write("newmtl floor\nKd 0.7 0.6 0.5\nNs 1\n")
-    with open(os.path.join(d, "zeros.obj"), "w") as o:
-        o.write("mtllib zeros.mtl\nusemtl floor\n")
-        for i in range(n):
-            t = vals[rng.randint(0, len(vals), (3, 3))]
-            t[1, rng.randint(0, 3)] = np.float32(rng.uniform(2.0, 3.0))
-            t[2, rng.randint(0, 3)] = np.float32(rng.uniform(2.0, 3.0))
-            for p in t:
-                o.write("v %.9g %.9g %.9g\nvn 0 1 0\nvt 0 0\n" % tuple(float(c) for c in p))
-            o.write("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % ((3 * i + 1,) * 3 + (3 * i + 2,) * 3 + (3 * i + 3,) * 3))
-    return os.path.join(d, "zeros.obj"), d
 
 
 @pytest.mark.gpu

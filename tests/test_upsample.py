@@ -17,11 +17,11 @@ from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
 import oracle_lib as O
 import util
+from frames import GUIDES, cached_frame, renders  # noqa: F401
 
 F = np.float32
 UPSAMPLE_EXPORTS = ("crt_upsample_defaults", "crt_upsample", "crt_upsample_device")
 DEFAULTS = {"radius": 1, "min_weight": 1.0 / 64, "sigma_normal": 0.5, "sigma_albedo": 0.1, "sigma_depth": 0.05}
-GUIDES = ("albedo", "normal", "depth")
 assert_bits = util.assert_bits
 
 
@@ -289,39 +289,9 @@ DROPS = [(), ("albedo",), ("normal",), ("depth",), GUIDES]
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-_frames = {}
-
-
 def frame_of(renders, name, width, height, spp, seed=0, variance=True):
-    """A GPU render (with its variance) and the shading pass with the guides from the same trace, rendered once per module"""
-    key = (name, width, height, spp, seed, variance)
-    if key not in _frames:
-        r = renders[name]
-        cam = util.camera(name)
-        r.set_spp(spp)
-        r.seed = seed
-        try:
-            if variance:
-                rgb = r.run_view(*cam, width=width, height=height, want_variance=True).copy()
-                out = {"rgb": rgb, "mean": r.mean_buffer.copy(), "variance": r.variance_buffer.copy()}
-            else:
-                out = {}
-            out.update(r.run_view_aov_shading(*cam, first=GUIDES, width=width, height=height))
-        finally:
-            r.seed = 0
-        _frames[key] = out
-    return _frames[key]
+    """A GPU render (with its variance) and the shading pass with the guides from the same trace, rendered once"""
+    return cached_frame(renders, name, width, height, spp, seed=seed, render=variance, want_variance=variance, shading=GUIDES)
 
 
 @pytest.mark.gpu

@@ -2,11 +2,10 @@
 Render.variance in Python; crt_cli --variance).
 
 The expected values come from the oracle's per-path radiance (OracleScene.render(want_L=True) -> (h, w, spp, 3)): the contract of
-include/crt.h is restated below in numpy float32, operation by operation -- first the frame's own sum, which must reproduce the oracle's
+include/crt.h is restated in variance_restated.py in numpy float32, operation by operation -- first the frame's own sum, which must reproduce the oracle's
 mean bit for bit, then the same loop with the sum of squares -- and the device result must match it on uint32 views (NaN matches NaN).
 """
 import ctypes as C
-import functools
 import subprocess
 
 import numpy as np
@@ -15,24 +14,14 @@ import pytest
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
 from cudaraytracing_amd.hipmem import DeviceBuffers
+import frames
 import util
-from util import assert_bits, restated_sums
+from frames import oracle_frame, renders  # noqa: F401
+from util import assert_bits
+from variance_restated import restated_variance
 
 F = np.float32
 VARIANCE_EXPORTS = ("crt_variance", "crt_variance_device", "crt_denoise_var_defaults", "crt_denoise_var", "crt_denoise_var_device")
-
-
-def restated_variance(L, S, n=None):
-    n = S if n is None else n
-    c, q = restated_sums(L, S, n)
-    fn, fs = F(n), F(S)
-    with np.errstate(all="ignore"):
-        d = fn * q - c * c
-        d = np.where(d < F(0.0), F(0.0), d)
-        r = fs / fn
-        var = ((r * r) * d) / (fn - F(1.0))
-    assert var.dtype == F
-    return var
 
 
 # ------------------------------------------------------------------------------------------------------------------ CPU --
@@ -84,38 +73,10 @@ def test_restatement_is_the_sample_variance_of_the_mean():
 
 # ------------------------------------------------------------------------------------------------------------------ GPU --
 
-@pytest.fixture(scope="module")
-def renders():
-    out = {}
-    for name in ("cornell-box", "veach-mis"):
-        t = util.task(name)
-        out[name] = crt.Render(util.host_scene(name), t.spp, t.P_RR, t.light_sample_n)
-    yield out
-    for r in out.values():
-        r.free()
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(name, w, h, spp, seed=0):
-    """(rgb, mean, L (h, w, spp, 3)) of the oracle with the scene's own P_RR and light_sample_n"""
-    t = util.task(name)
-    eye, iv, fov = util.camera(name)
-    rgb, mean, L, _ = util.oracle_scene(name).render(eye, iv, fov, w, h, spp, t.P_RR, t.light_sample_n, seed=seed, want_L=True)
-    c, _ = restated_sums(L, spp, spp)
-    assert np.array_equal(c.view(np.uint32), mean.view(np.uint32)), "summing L / S in numpy does not give the oracle's own mean"
-    return rgb, mean, L
-
-
-def gpu_frame(r, name, w, h, spp, seed=0, traversal=crt.TRAVERSAL_EXACT, want_variance=True, flags=0, stats=False):
+def gpu_frame(r, name, w, h, spp, want_variance=True, **kw):
     """(rgb, mean, variance or None) of a GPU render"""
-    eye, iv, fov = util.camera(name)
-    r.set_spp(spp)
-    r.seed, r.traversal, r.extra_flags = seed, traversal, flags
-    try:
-        rgb = r.run_view(eye, iv, fov, width=w, height=h, want_variance=want_variance, stats=stats).copy()
-        return rgb, r.mean_buffer.copy(), r.variance_buffer
-    finally:
-        r.seed, r.traversal, r.extra_flags = 0, crt.TRAVERSAL_EXACT, 0
+    f = frames.gpu_frame(r, name, w, h, spp, want_variance=want_variance, **kw)
+    return f["rgb"], f["mean"], f["variance"]
 
 
 @pytest.mark.gpu
