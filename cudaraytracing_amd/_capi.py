@@ -19,6 +19,9 @@ FLAG_TRACE_ALL = 8
 FLAG_BOUNDED_RADIANCE = 16
 FLAG_VARIANCE = 32
 FLAG_HALF_BUFFERS = 64   # implies FLAG_VARIANCE
+FLAG_PIXEL_FILTER = 128  # keep the sums of the handle's pixel reconstruction filter (crt_set_pixel_filter, crt_filtered_frame)
+PIXEL_FILTER_BOX, PIXEL_FILTER_TENT, PIXEL_FILTER_MITCHELL = 0, 1, 2
+PIXEL_FILTER_KINDS = {"box": PIXEL_FILTER_BOX, "tent": PIXEL_FILTER_TENT, "mitchell": PIXEL_FILTER_MITCHELL}
 GATHER_AUTO, GATHER_RCCL, GATHER_COPY = 0, 1, 2
 INTERSECT_RAW_DIRECTIONS, INTERSECT_FORCE_EXACT, INTERSECT_VISIBILITY = 0x100, 0x200, 0x400
 TILE = 8
@@ -284,6 +287,10 @@ class PyramidInfo(InfoStruct):
     _fields_ = [("total_ms", C.c_float)]
 
 
+class PixelFilter(InfoStruct):
+    _fields_ = [("kind", C.c_uint32), ("radius", C.c_float)]
+
+
 SELECT_MAX_CANDIDATES = 4
 
 
@@ -371,7 +378,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_modulate_device", "crt_upsample_defaults", "crt_upsample", "crt_upsample_device", "crt_half_buffers", "crt_half_buffers_device",
            "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device",
            "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device",
-           "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device"]
+           "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device",
+           "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device"]
 
 _lib = None
 
@@ -546,6 +554,11 @@ def lib():
                                      C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
     L.crt_render_planned_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AdaptiveParams), C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MapInfo)]
+    if hasattr(L, "crt_set_pixel_filter"):  # (likewise: the entry points came without a new ABI version)
+        L.crt_pixel_filter_defaults.argtypes = [C.POINTER(PixelFilter)]
+        L.crt_set_pixel_filter.argtypes = [C.c_void_p, C.POINTER(PixelFilter)]
+        L.crt_filtered_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        L.crt_filtered_frame_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "crt_item_order"):  # (a CRT_LIB_PATH library of this ABI version from before the entry point was appended has none)
         L.crt_item_order.argtypes = [C.c_void_p, C.POINTER(ItemOrderInfo)]
     _lib = L

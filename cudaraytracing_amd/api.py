@@ -190,7 +190,9 @@ class Render:
         self.upsample_info = None
         self.half_a_buffer = None        # run_view(want_halves=True): the means of the even and of the odd samples
         self.half_b_buffer = None
-        self.select_buffers = None       # run_view_selected: choice, error, the halves, their variance and the filtered candidates
+        self.filtered_rgb = None         # run_view(pixel_filter=True): the frame under the handle's pixel reconstruction filter
+        self.filtered_mean = None
+        self.select_buffers = None      # run_view_selected: choice, error, the halves, their variance and the filtered candidates
         self.select_info = None
         self.temporal_history_buffer = None
         self._temporal = None        # run_view_temporal: the history (temporal()'s `prev` dict), its camera and size
@@ -254,16 +256,39 @@ class Render:
         return self._params(rank=rank, world=world, flags=(capi.FLAG_TILED_OUTPUT if (tiled or world > 1) else 0) | self.extra_flags,
                             width=width, height=height)
 
-    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False, want_halves=False):
+    def set_pixel_filter(self, spec):
+        """The handle's pixel reconstruction filter (crt_set_pixel_filter, contract: include/crt.h): None for none, "box" (radius 0.5:
+        the frame's own filter), "tent" (radius 1), "mitchell" (radius 2), or dict(kind=, radius=).  A setting the library does not
+        allow raises CrtError and the handle keeps its old filter."""
+        h_ = self._handle("set_pixel_filter")
+        capi.check(capi.lib().crt_set_pixel_filter(h_, C.byref(_pixel_filter(spec)) if spec is not None else None), "crt_set_pixel_filter")
+
+    def filtered(self, want_mean=True, width=None, height=None):
+        """(rgb (H, W, 3), mean (H, W, 3) float32 or None, samples done) of crt_filtered_frame: the frame under the handle's pixel
+        filter from the sums a render with pixel_filter=True keeps on the handle -- after the frame, or between the ranges of a
+        progressive one.  Reads only."""
+        h_ = self._handle("filtered")
+        w, h = width or self.scene.width, height or self.scene.height
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+        done = C.c_uint32(0)
+        capi.check(capi.lib().crt_filtered_frame(h_, capi.ptr(rgb), capi.ptr(mean), C.byref(done)), "crt_filtered_frame")
+        return rgb, mean, int(done.value)
+
+    def run_view(self, eye_pos, inv_view_mat, fovY, stats=False, want_mean=True, width=None, height=None, want_variance=False, want_halves=False,
+                 pixel_filter=False):
         """Renders the whole frame; returns the RGB8 frame buffer (H, W, 3).  want_variance: render with FLAG_VARIANCE (the frame is
         the same bits) and leave the per-pixel variance of the mean, (H, W, 3) float32 (crt_variance), in self.variance_buffer.
         want_halves: render with FLAG_HALF_BUFFERS (which implies FLAG_VARIANCE; the same bits again) and leave the means of the even
-        and of the odd samples (crt_half_buffers) in self.half_a_buffer / self.half_b_buffer beside the variance."""
+        and of the odd samples (crt_half_buffers) in self.half_a_buffer / self.half_b_buffer beside the variance.  pixel_filter: render
+        with FLAG_PIXEL_FILTER (the same bits again; set_pixel_filter first) and leave the frame under the handle's filter
+        (crt_filtered_frame) in self.filtered_rgb / self.filtered_mean."""
         if not self._h:
             raise RuntimeError("Render.run_view after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
         prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) |
-                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | self.extra_flags, width=width, height=height)
+                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | (capi.FLAG_PIXEL_FILTER if pixel_filter else 0) | self.extra_flags,
+                           width=width, height=height)
         w, h = prm.width, prm.height
         rgb = np.zeros((h, w, 3), dtype=np.uint8)
         mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
@@ -273,6 +298,7 @@ class Render:
         self.frame_buffer, self.mean_buffer, self.stats = rgb, mean, st.as_dict()
         self.variance_buffer = self.variance(width=w, height=h)[0] if (want_variance or want_halves) else None
         self.half_a_buffer, self.half_b_buffer = self.half_buffers(width=w, height=h)[:2] if want_halves else (None, None)
+        self.filtered_rgb, self.filtered_mean = self.filtered(width=w, height=h)[:2] if pixel_filter else (None, None)
         return rgb
 
     def half_buffers(self, width=None, height=None):
@@ -400,17 +426,19 @@ class Render:
             h_, C.byref(cam), C.byref(prm), C.byref(ap), rgb, mean, samples, var, st, info), ptrs, stream, want_info)
 
     def run_view_range(self, eye_pos, inv_view_mat, fovY, sample_begin, sample_count, want_mean=True, width=None, height=None,
-                       want_variance=False, stats=False, want_halves=False):
+                       want_variance=False, stats=False, want_halves=False, pixel_filter=False):
         """Progressive rendering: adds samples [sample_begin, sample_begin + sample_count) of the spp samples per pixel to the
         accumulator of the device scene; ranges go in ascending order from 0.  Returns the RGB8 frame once the range that ends
         at spp has been rendered (bit-identical to run_view), None before.  A range with sample_begin > 0 that does not continue
         the frame in flight on the handle (samples so far, spp, size) raises CrtError.  want_halves: the range goes with
-        FLAG_HALF_BUFFERS (half_buffers() reads the halves between the ranges and after the last)."""
+        FLAG_HALF_BUFFERS (half_buffers() reads the halves between the ranges and after the last).  pixel_filter: the range goes
+        with FLAG_PIXEL_FILTER (filtered() reads the filtered frame between the ranges and after the last)."""
         if not self._h:
             raise RuntimeError("Render.run_view_range after free()")
         cam = self._cam(eye_pos, inv_view_mat, fovY)
         prm = self._params(flags=(capi.FLAG_STATS if stats else 0) | (capi.FLAG_VARIANCE if want_variance else 0) |
-                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | self.extra_flags, width=width, height=height)
+                           (capi.FLAG_HALF_BUFFERS if want_halves else 0) | (capi.FLAG_PIXEL_FILTER if pixel_filter else 0) | self.extra_flags,
+                           width=width, height=height)
         w, h = prm.width, prm.height
         last = sample_begin + sample_count == self.spp
         rgb = np.zeros((h, w, 3), dtype=np.uint8) if last else None
@@ -1503,6 +1531,32 @@ def upsample_device(width, height, low_width, low_height, low_ptrs, out_color_pt
 
 _PYRAMID_PLANES = (("color", 3), ("variance", 3), ("albedo", 3), ("normal", 3), ("depth", 1))
 MAX_SCALES = 4
+
+
+def pixel_filter_defaults():
+    """crt_pixel_filter_defaults as a dict: kind ("tent") and radius (1)."""
+    p = capi.PixelFilter()
+    capi.check(capi.lib().crt_pixel_filter_defaults(C.byref(p)), "crt_pixel_filter_defaults")
+    return {"kind": {v: k for k, v in capi.PIXEL_FILTER_KINDS.items()}[int(p.kind)], "radius": float(p.radius)}
+
+
+def _pixel_filter(spec):
+    """"box" | "tent" | "mitchell" | dict(kind=, radius=) -> crt_pixel_filter; a kind alone takes the radius the contract ties to it
+    (box 0.5: the frame's own filter, tent 1, mitchell 2).  kind may be a name or a CRT_PIXEL_FILTER_* number."""
+    if isinstance(spec, str):
+        spec = {"kind": spec}
+    unknown = set(spec) - {"kind", "radius"}
+    if unknown or "kind" not in spec:
+        raise ValueError("set_pixel_filter: a filter is a kind name or dict(kind=, radius=), got %r" % (spec,))
+    kind = spec["kind"]
+    if isinstance(kind, str):
+        if kind not in capi.PIXEL_FILTER_KINDS:
+            raise ValueError("set_pixel_filter: unknown kind %r (one of %s)" % (kind, ", ".join(capi.PIXEL_FILTER_KINDS)))
+        kind = capi.PIXEL_FILTER_KINDS[kind]
+    radius = spec.get("radius")
+    if radius is None:
+        radius = {capi.PIXEL_FILTER_BOX: 0.5, capi.PIXEL_FILTER_TENT: 1.0}.get(int(kind), 2.0)
+    return capi.PixelFilter(int(kind), float(radius))
 
 
 def pyramid_size(width, height):

@@ -14,6 +14,11 @@
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]
 //           [--aov-shading PREFIX] [--demodulate]
 //           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]] [--gathered PREFIX[,NAME,...]]
+//           [--pixel-filter KIND[,RADIUS] --pixel-filter-out PATH]
+// --pixel-filter KIND[,RADIUS] --pixel-filter-out PATH also writes the frame under a pixel reconstruction filter (one device;
+// crt_set_pixel_filter, CRT_FLAG_PIXEL_FILTER, crt_filtered_frame): KIND is box, tent or mitchell, RADIUS defaults to 0.5, 1 and 2; every
+// sample then counts for the pixels around its jittered position.  PATH gets a PNG, or with the ending .pfm the 3-channel mean.  -o stays
+// the plain (box-filtered) frame of the same paths.  Not with --adaptive, --temporal or --gpus / --devices.
 // --gathered PREFIX[,NAME,...] (only with --gpus / --devices) renders the frame with the buffers the image filters take gathered from all
 // ranks (crt_multi_render_buffers) and writes each float plane asked for as PREFIX.<NAME>.pfm (3 channels; depth and coverage: 1): NAME
 // is mean, variance, half_a, half_b, albedo, normal, depth, coverage, emission or diffuse_albedo; the default is mean, variance, albedo,
@@ -99,6 +104,7 @@ int main(int argc, char** argv)
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]\n"
                              "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n"
+                             "       [--pixel-filter KIND[,RADIUS] --pixel-filter-out PATH]  (KIND: box, tent, mitchell)\n"
                              "       [--gathered PREFIX[,NAME,...]]  (with --gpus / --devices; NAME: mean, variance, half_a, half_b, albedo, normal, depth, coverage,\n"
                              "                                        emission, diffuse_albedo; default: mean, variance, albedo, normal, depth)\n", argv[0]);
         return 2;
@@ -106,7 +112,9 @@ int main(int argc, char** argv)
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, denoise, variance, adaptive_samples;
+        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, denoise, variance, adaptive_samples, pixel_filter_out;
+        crt_pixel_filter pixel_filter; // --pixel-filter
+        bool pixel_filter_on = false;
         bool demodulate = false;
         crt_adaptive_params ad;
         crt_adaptive_defaults(&ad);
@@ -286,6 +294,24 @@ int main(int argc, char** argv)
                 if (end == q || *end != 0 || denoise_scales < 1 || denoise_scales > 4) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales needs a number of scales 1 .. 4");
             }
             else if (a == "--variance") { need(i, 1); variance = argv[++i]; }
+            else if (a == "--pixel-filter-out") { need(i, 1); pixel_filter_out = argv[++i]; }
+            else if (a == "--pixel-filter") {
+                need(i, 1);
+                const std::string v = argv[++i];
+                const size_t comma = v.find(',');
+                const std::string kind = v.substr(0, comma);
+                bool good = kind == "box" || kind == "tent" || kind == "mitchell";
+                pixel_filter.kind = kind == "box" ? CRT_PIXEL_FILTER_BOX : kind == "tent" ? CRT_PIXEL_FILTER_TENT : CRT_PIXEL_FILTER_MITCHELL;
+                pixel_filter.radius = kind == "box" ? 0.5f : kind == "tent" ? 1.0f : 2.0f;
+                if (good && comma != std::string::npos) {
+                    const char* q = v.c_str() + comma + 1;
+                    char* end = nullptr;
+                    pixel_filter.radius = std::strtof(q, &end);
+                    good = end != q && *end == 0;
+                }
+                if (!good) throw crt::Error(CRT_ERR_INVALID_ARG, "--pixel-filter needs KIND[,RADIUS]: KIND box, tent or mitchell");
+                pixel_filter_on = true;
+            }
             else if (a == "--adaptive") { need(i, 1); ad.threshold = std::strtof(argv[++i], nullptr); adaptive = true; }
             else if (a == "--adaptive-min") { need(i, 1); ad.min_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-step") { need(i, 1); ad.step_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
@@ -470,6 +496,9 @@ int main(int argc, char** argv)
         if (denoise_scales && !(denoise_var || denoise_nlm || denoise_regress))
             throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-scales needs --denoise-variance, --denoise-nlm or --denoise-regress (the pyramid reduces the variance with the frame)");
         if (denoise_select && (adaptive || temporal)) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-select needs the half buffers of a uniformly sampled frame (not with --adaptive or --temporal)");
+        if (pixel_filter_on != !pixel_filter_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--pixel-filter KIND[,RADIUS] and --pixel-filter-out PATH go together");
+        if (pixel_filter_on && (multi || adaptive || temporal))
+            throw crt::Error(CRT_ERR_INVALID_ARG, "--pixel-filter filters the uniformly sampled frame of one device (not with --gpus / --devices, --adaptive or --temporal)");
         if (!gathered.empty() && !multi) throw crt::Error(CRT_ERR_INVALID_ARG, "--gathered gathers the buffers of a multi-device frame (only with --gpus / --devices)");
         const bool want_var = !variance.empty() || denoise_var || denoise_nlm || denoise_regress || (temporal > 0 && !temporal_moments);
         crt_denoise_params tdn; // --temporal-denoise: the variance-guided filter's defaults with the overrides
@@ -488,7 +517,9 @@ int main(int argc, char** argv)
         crt::Render& render = render_one_or_many;
         render.set_seed(seed);
         render.set_traversal(reference ? CRT_TRAVERSAL_REFERENCE : (fast && !exact) ? CRT_TRAVERSAL_FAST : CRT_TRAVERSAL_EXACT);
-        render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u) | (denoise_select ? CRT_FLAG_HALF_BUFFERS : 0u));
+        render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u) | (denoise_select ? CRT_FLAG_HALF_BUFFERS : 0u) |
+                         (pixel_filter_on ? CRT_FLAG_PIXEL_FILTER : 0u));
+        if (pixel_filter_on) render.set_pixel_filter(&pixel_filter);
         render.set_aov_shading(!aov_shading.empty());
         if (demodulate) render.set_demodulate(true);
         // One output's files -- a PFM of 1 or 3 channels of floats, or with channels 0 a PNG of RGB8 -- are written, then their paths printed
@@ -565,6 +596,12 @@ int main(int argc, char** argv)
         for (size_t r : gathered_rows) // (one at a time: their number is the caller's)
             write_files("gathered plane", {{gathered + "." + gathered_planes[r].name + ".pfm", gathered_planes[r].channels, render.get_gathered_buffer(gathered_planes[r].bit)}});
         if (!variance.empty()) write_files("variance file", {{variance, 3, render.variance()}});
+        if (pixel_filter_on) { // (before the calls below that render again: it reads the sums of the frame just rendered)
+            render.filtered_frame();
+            const bool pfm = pixel_filter_out.size() >= 4 && pixel_filter_out.compare(pixel_filter_out.size() - 4, 4, ".pfm") == 0;
+            if (pfm) write_files("filtered frame", {{pixel_filter_out, 3, render.get_filtered_mean_buffer()}});
+            else { render.save_filtered_buffer(pixel_filter_out.c_str()); std::printf("%s\n", pixel_filter_out.c_str()); }
+        }
         if (!adaptive_samples.empty()) {
             std::vector<float> ns((size_t)task.width * task.height);
             for (size_t k = 0; k < ns.size(); k++) ns[k] = (float)render.get_samples_buffer()[k];

@@ -286,6 +286,14 @@ public:
     // per-pixel variance of the mean of the last run_view (crt_variance; needs set_flags(CRT_FLAG_VARIANCE) before it): W x H x 3,
     // fetched from the device on the first call after a frame; one device only
     const float* variance();
+    // Pixel reconstruction filters (crt_set_pixel_filter, crt_filtered_frame): the filter of this Render's handle -- nullptr: none -- and,
+    // after a run_view with set_flags(CRT_FLAG_PIXEL_FILTER), the frame under it: get_filtered_buffer (W x H x 3 RGB8) and
+    // get_filtered_mean_buffer (W x H x 3).  One device only.
+    void set_pixel_filter(const crt_pixel_filter* filter);
+    void filtered_frame();
+    const unsigned char* get_filtered_buffer() const { return filtered_buffer_.data(); }
+    const float* get_filtered_mean_buffer() const { return filtered_mean_buffer_.data(); }
+    void save_filtered_buffer(const char* save_path) const;
     // One frame of a temporally accumulated sequence (crt_temporal; prm: crt_temporal_defaults with overrides, its sizes and cameras are set
     // here): run_view (needs set_flags(CRT_FLAG_VARIANCE)), variance, run_aov, then the frame is blended into the history this object keeps
     // -- colour, variance, history length, depth, normal, material ID and camera of the previous call -- and the unfiltered result becomes
@@ -341,7 +349,7 @@ public:
     void set_light_sample_n(const int& n) { light_sample_n_ = (unsigned)n; }
     void set_seed(uint64_t s) { seed_ = s; }
     void set_traversal(uint32_t t) { traversal_ = t; }
-    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE, CRT_FLAG_VARIANCE, CRT_FLAG_HALF_BUFFERS
+    void set_flags(uint32_t f) { flags_ = f; } // CRT_FLAG_* of crt_params that a caller may choose: CRT_FLAG_TRACE_ALL, CRT_FLAG_BOUNDED_RADIANCE, CRT_FLAG_VARIANCE, CRT_FLAG_HALF_BUFFERS, CRT_FLAG_PIXEL_FILTER
     void set_width(const unsigned& w);
     void set_height(const unsigned& h);
     const crt_stats& last_stats() const { return stats_; }
@@ -367,6 +375,8 @@ private:
     std::vector<float> denoised_mean_buffer_;
     std::vector<float> variance_buffer_; // empty until variance() has fetched it for the last frame (run_view_adaptive fills it itself)
     std::vector<uint32_t> samples_buffer_;
+    std::vector<unsigned char> filtered_buffer_; // filtered_frame
+    std::vector<float> filtered_mean_buffer_;
     std::vector<int32_t> material_buffer_; // run_aov
     uint32_t gathered_ = 0;                // run_view_gathered: the planes the last call made
     std::vector<float> half_a_buffer_, half_b_buffer_, coverage_buffer_;

@@ -120,7 +120,7 @@ void Render::run_view(const float eye_pos[3], const float inv_view_mat[9], float
     alive("Render::run_view");
     crt_camera cam;
     crt_params p;
-    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS), cam, p);
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & (CRT_FLAG_TRACE_ALL | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS | CRT_FLAG_PIXEL_FILTER), cam, p);
     variance_buffer_.clear();
     int rc;
     if (multi_) {
@@ -302,6 +302,20 @@ const float* Render::variance()
         variance_buffer_.swap(v);
     }
     return variance_buffer_.data();
+}
+
+void Render::set_pixel_filter(const crt_pixel_filter* filter)
+{
+    one_device("Render::set_pixel_filter", "the pixel filter");
+    check(crt_set_pixel_filter(device_scene_, filter), "Render::set_pixel_filter");
+}
+void Render::filtered_frame()
+{
+    one_device("Render::filtered_frame", "the filtered frame");
+    std::vector<unsigned char> rgb(3 * scene_->get_pixels(), 0);
+    std::vector<float> mean(3 * scene_->get_pixels(), 0.0f);
+    check(crt_filtered_frame(device_scene_, rgb.data(), mean.data(), nullptr), "Render::filtered_frame");
+    filtered_buffer_.swap(rgb); filtered_mean_buffer_.swap(mean);
 }
 
 Render::Filter Render::default_filter(int kind)
@@ -668,6 +682,12 @@ void Render::save_denoised_buffer(const char* save_path) const
 {
     if (denoised_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_denoised_buffer before run_denoise");
     save_rgb8("save_denoised_buffer", save_path, *scene_, denoised_buffer_);
+}
+
+void Render::save_filtered_buffer(const char* save_path) const
+{
+    if (filtered_buffer_.empty()) throw Error(CRT_ERR_INVALID_ARG, "save_filtered_buffer before filtered_frame");
+    save_rgb8("save_filtered_buffer", save_path, *scene_, filtered_buffer_);
 }
 
 void Render::save_frame_buffer(const char* save_path) const { save_rgb8("save_frame_buffer", save_path, *scene_, frame_buffer_); }

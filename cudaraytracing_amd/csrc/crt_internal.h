@@ -128,6 +128,8 @@ void launch_accumulate_half(const AParams& A, float* qacc, float* hacc, uint32_t
 void launch_half_buffers(const AParams& A, const float* hacc, float* out_a, float* out_b, float scale_a, float scale_b, hipStream_t st); // crt_half_buffers
 void launch_variance(const AParams& A, const float* qacc, float fn, float fs, hipStream_t st); // crt_variance: A.accum, qacc -> A.out_mean
 void launch_preview(const AParams& A, float scale, hipStream_t st);
+// pixel reconstruction filters (crt_pixel_filter.hip): the chunk A describes into the four planes of filter pf's sums; s0: the chunk's first sample in the frame
+void launch_pixel_filter(const AParams& A, const crt_pixel_filter& pf, float* planes, uint64_t seed, uint32_t s0, hipStream_t st);
 void launch_fill_rays(const Pool& pool, uint32_t n, const float* o, const float* d, bool raw_dir, const float* limits);
 void launch_math(int fn, uint32_t n, const float* a, const float* b, float* out);
 void launch_philox(uint32_t n, const uint32_t* ctr, const uint32_t* key, uint32_t* out);

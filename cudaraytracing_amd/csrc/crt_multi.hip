@@ -403,7 +403,7 @@ int render_planes(const char* who_, crt_multi* m, const crt_camera* cam, const c
             p.rank = r; p.world = world;
             p.flags |= CRT_FLAG_TILED_OUTPUT;
             // the sums of crt_variance and crt_half_buffers are kept exactly when a plane needs them (a frame of RGB and the mean: never)
-            p.flags &= ~(uint32_t)(CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS);
+            p.flags &= ~(uint32_t)(CRT_FLAG_VARIANCE | CRT_FLAG_HALF_BUFFERS | CRT_FLAG_PIXEL_FILTER); // (a shard keeps no filter sums: it does not hold its pixels' neighbours)
             if (want_sums) p.flags |= CRT_FLAG_VARIANCE;
             if (want_halves) p.flags |= CRT_FLAG_HALF_BUFFERS;
             auto at = [&](uint32_t k) -> uint8_t* { return (want & kPlanes[k].bit) ? rk.local + L.off[k] : nullptr; };

@@ -244,6 +244,7 @@ struct Frame {
     Rad3* L;        // the chunk's radiance, cap entries (null with the ring, whose entries are crt_scene::ring_L)
     RingPlan ring;
     bool want_stats, tiled, want_var, var_frame, want_half, half_frame;
+    bool pf_frame; // CRT_FLAG_PIXEL_FILTER on a frame that has had it since sample 0: every chunk also goes into the filter's sums
     AParams A;
     const ItemSource* src; // null: every pixel slot takes every sample of the range
     bool open;             // the frame is resolved by the caller, not by the range that ends at spp
@@ -288,13 +289,20 @@ void accumulate_chunk(Frame& f, uint32_t s0, uint32_t ns)
     A.first_chunk = s0 == 0; A.last_chunk = !f.open && s0 + ns >= f.prm->spp;
     if (f.ring.samples) { A.chunk_samples = 0; A.first_chunk = 0; } // the sum is in the accumulator already: tone mapping only
     if (!f.ring.samples || A.last_chunk) {
+        // The filtered frame's read-out takes c where a pixel's W is not positive, and k_accumulate alone does not store c with the last
+        // chunk: with the filter it folds that chunk as one that is not the last, and k_preview at scale 1 (c * 1.0f: c's bits) writes the frame.
+        const bool keep_c = f.pf_frame && !f.want_var && A.last_chunk;
+        if (keep_c) A.last_chunk = 0;
         if (f.src) f.src->fold(A, s0, ns, f.st);
         else if (f.want_half) launch_accumulate_half(A, sc->accum_q.p, sc->accum_h.p, s0 & 1u, f.st);
         else if (f.want_var) launch_accumulate_var(A, sc->accum_q.p, f.st);
         else launch_accumulate(A, f.st);
+        if (keep_c) { A.last_chunk = 1; launch_preview(A, 1.0f, f.st); }
+        if (f.pf_frame) launch_pixel_filter(A, sc->pf, sc->accum_pf.p, f.prm->seed, s0, f.st);
         HIP_CHECK(hipGetLastError());
         if (f.var_frame) { sc->var.valid = true; sc->var.set(f.prm, s0 + ns, f.tiled); }
         if (f.half_frame) { sc->half.valid = true; sc->half.set(f.prm, s0 + ns, f.tiled); }
+        if (f.pf_frame) { sc->pf_mark.valid = true; sc->pf_mark.set(f.prm, s0 + ns, f.tiled); sc->pf_frame = sc->pf; }
     }
     sc->acc.set(f.prm, A.last_chunk ? 0u : s0 + ns, f.tiled);
 }
@@ -336,7 +344,7 @@ RingPlan plan_ring(const crt_scene* sc, const crt_params* prm, const Shard& sh, 
 {
     RingPlan ring;
     std::memset(&ring, 0, sizeof(ring));
-    if (!mega || want_stats || want_var) return ring; // (CRT_FLAG_VARIANCE squares the per-path radiance, which the ring does not keep)
+    if (!mega || want_stats || want_var) return ring; // (CRT_FLAG_VARIANCE squares the per-path radiance, which the ring does not keep; want_var: or CRT_FLAG_PIXEL_FILTER, which reads it too)
     // cursor shards: the commits of a shard are a serial chain (one wave, a memory round trip per 256 pixel slots), so a ring
     // launch has more and smaller shards than the 64 of a launch without: about 1 024 pixel slots each, at most 1 024 shards
     uint32_t shards = ITEM_SHARDS;
@@ -693,6 +701,24 @@ int params_check(const char* who, const crt_params* prm, bool camera_rays_only)
     return CRT_OK;
 }
 
+// CRT_FLAG_PIXEL_FILTER: whether a range that begins at sample s_begin continues a frame whose filter sums are on the handle
+static bool pixel_filter_continues(const crt_scene* sc, const crt_params* prm, uint32_t s_begin)
+{
+    return s_begin > 0 && sc->pf_mark.valid && continues_frame(sc->pf_mark, prm, s_begin, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0);
+}
+// What a render call with CRT_FLAG_PIXEL_FILTER refuses (contract: include/crt.h), before any device call -- the host forms ask before
+// they stage their buffers, render_impl asks again
+static int pixel_filter_check(const crt_scene* sc, const crt_params* prm, uint32_t s_begin)
+{
+    if (!sc->pf_set) return fail(CRT_ERR_INVALID_ARG, "crt_render: CRT_FLAG_PIXEL_FILTER with no filter on the handle (crt_set_pixel_filter)");
+    if (prm->world > 1) return fail(CRT_ERR_UNSUPPORTED, "crt_render: CRT_FLAG_PIXEL_FILTER with world > 1 (a shard does not hold its pixels' neighbours)");
+    if (pixel_filter_continues(sc, prm, s_begin) && (sc->pf_frame.kind != sc->pf.kind || std::memcmp(&sc->pf_frame.radius, &sc->pf.radius, sizeof(float)) != 0))
+        return fail(CRT_ERR_INVALID_ARG, "crt_render_range: a range with sample_begin " + std::to_string(s_begin) + " and CRT_FLAG_PIXEL_FILTER must keep the filter of the frame "
+                                         "in flight (kind " + std::to_string(sc->pf_frame.kind) + ", radius " + std::to_string(sc->pf_frame.radius) + "); the handle's is kind " +
+                                         std::to_string(sc->pf.kind) + ", radius " + std::to_string(sc->pf.radius));
+    return CRT_OK;
+}
+
 // Renders samples [s_begin, s_begin + s_count) of the prm->spp samples per pixel into the scene's accumulator
 // (temp_color += L_k / spp in sample order, Render.cuh:348); the range that ends at spp also tone-maps and writes the frame.
 // src, open: crt_render.h.
@@ -720,6 +746,11 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
     f.want_var = (prm->flags & CRT_FLAG_VARIANCE) != 0;
     f.want_half = (prm->flags & CRT_FLAG_HALF_BUFFERS) != 0 && !src; // (a sparse frame keeps no halves)
     if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) return fail(CRT_ERR_UNSUPPORTED, "crt_render: more than 65535 next-event samples per vertex");
+    // CRT_FLAG_PIXEL_FILTER (a sparse frame keeps no filter sums: crt_sparse.hip clears the flag)
+    const bool want_pf = (prm->flags & CRT_FLAG_PIXEL_FILTER) != 0 && !src;
+    const int rc_pf = want_pf ? pixel_filter_check(sc, prm, s_begin) : CRT_OK;
+    if (rc_pf != CRT_OK) return rc_pf;
+    const bool pf_continues = want_pf && pixel_filter_continues(sc, prm, s_begin);
     // a range that does not start a frame adds to the accumulator: it must hold exactly the samples before the range, of this frame
     if (s_begin > 0 && !continues_frame(sc->acc, prm, s_begin, f.tiled)) {
         const std::string have = sc->acc.in_flight(" at " + std::to_string(sc->acc.width) + " x " + std::to_string(sc->acc.height) + ", rank " + std::to_string(sc->acc.rank) +
@@ -733,7 +764,7 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         f.chunk = chunk_samples(f.sh.nslots, s_count);
         f.cap = (uint64_t)f.chunk * f.sh.nslots;
         const bool mega = choose_pipeline(sc) == 4;
-        f.ring = plan_ring(sc, prm, f.sh, s_count, mega, f.want_stats, f.want_var);
+        f.ring = plan_ring(sc, prm, f.sh, s_count, mega, f.want_stats, f.want_var || want_pf);
         if (f.ring.samples) {
             f.chunk = s_count;
             f.cap = (uint64_t)f.ring.samples * f.ring.spsh * f.ring.shards;
@@ -751,6 +782,10 @@ int render_impl(crt_scene* sc, const crt_camera* cam, const crt_params* prm, voi
         f.half_frame = f.want_half && (s_begin == 0 || (sc->half.valid && continues_frame(sc->half, prm, s_begin, f.tiled)));
         sc->half.valid = false;
         if (f.want_half) sc->accum_h.ensure_uncached((size_t)f.sh.nslots * 6);
+        // the filter's sums: by the same rule
+        f.pf_frame = want_pf && (s_begin == 0 || pf_continues);
+        sc->pf_mark.valid = false;
+        if (f.pf_frame) sc->accum_pf.ensure_uncached((size_t)f.sh.nslots * 4);
         FrameMark frame;
         frame.set(prm, 0, f.tiled);
         f.A = frame_aparams(sc, frame, f.sh);
@@ -777,6 +812,10 @@ int crt_render(crt_scene* sc, const crt_camera* cam, const crt_params* prm, uint
 {
     if (!sc || !prm || !out_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_render: null argument");
     if (prm->world == 0 || prm->rank >= prm->world || prm->width == 0 || prm->height == 0) return fail(CRT_ERR_INVALID_ARG, "crt_render: bad shard or size");
+    if (prm->flags & CRT_FLAG_PIXEL_FILTER) {
+        const int rc_pf = pixel_filter_check(sc, prm, 0);
+        if (rc_pf != CRT_OK) return rc_pf;
+    }
     return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0), true, out_mean != nullptr);
@@ -803,6 +842,10 @@ int crt_render_range(crt_scene* sc, const crt_camera* cam, const crt_params* prm
         return fail(CRT_ERR_INVALID_ARG, "crt_render_range: sample range outside [0, spp)");
     const bool last = sample_begin + sample_count == prm->spp;
     if (last && !out_rgb) return fail(CRT_ERR_INVALID_ARG, "crt_render_range: the range that ends at spp needs a frame buffer");
+    if (prm->flags & CRT_FLAG_PIXEL_FILTER) {
+        const int rc_pf = pixel_filter_check(sc, prm, sample_begin);
+        if (rc_pf != CRT_OK) return rc_pf;
+    }
     return hip_guard([&]() -> int {
         HIP_CHECK(hipSetDevice(sc->device));
         Staging s(out_pixels(prm->width, prm->height, prm->world, (prm->flags & CRT_FLAG_TILED_OUTPUT) != 0), last, last && out_mean);

@@ -108,6 +108,13 @@ struct crt_scene {
     // what they hold (crt_half_buffers), by var's rules: valid = the last render call had the flag, and so had every range since sample 0
     crtk::DevBuf<float> accum_h;
     FrameMark half;
+    // CRT_FLAG_PIXEL_FILTER: the handle's filter (crt_set_pixel_filter), the sums a and W (4 planes of nslots, allocated when the flag is
+    // first used), what they hold (crt_filtered_frame), by var's rules, and the filter they were made with
+    crt_pixel_filter pf{};
+    bool pf_set = false;
+    crtk::DevBuf<float> accum_pf;
+    FrameMark pf_mark;
+    crt_pixel_filter pf_frame{};
     // crt_render_adaptive: per pixel slot its sample count, the compacted list of the slots that take the next pass and its counter
     // (uncached, agent-scope atomics only: crt_adaptive.hip), and the pinned word the counter is copied to once per pass
     crtk::DevBuf<uint32_t> ad_nsamp, ad_list;

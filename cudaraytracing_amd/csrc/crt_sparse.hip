@@ -86,10 +86,10 @@ struct SparseCall {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     SparseCall(crt_scene* sc_, const crt_params* prm, hipStream_t st_, bool timed_) : sc(sc_), st(st_), timed(timed_), p(*prm)
     {
-        p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_HALF_BUFFERS); // (a sparse frame keeps no halves)
+        p.flags = (p.flags | CRT_FLAG_VARIANCE) & ~(uint32_t)(CRT_FLAG_STATS | CRT_FLAG_BOUNDED_RADIANCE | CRT_FLAG_HALF_BUFFERS | CRT_FLAG_PIXEL_FILTER); // (a sparse frame keeps no halves and no filter sums)
         sh = make_shard(p.width, p.height, p.world);
     }
-    ~SparseCall() { sc->acc.samples = 0; sc->var.valid = false; sc->half.valid = false; }
+    ~SparseCall() { sc->acc.samples = 0; sc->var.valid = false; sc->half.valid = false; sc->pf_mark.valid = false; }
     void begin()
     {
         HIP_CHECK(hipSetDevice(sc->device));

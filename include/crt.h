@@ -141,10 +141,16 @@ enum {
                                     the flag.  Switches the commit ring of CRT_FLAG_BOUNDED_RADIANCE (and of the CRT_COMMIT_RING_LOG2 test
                                     hook) off for the call, as CRT_FLAG_STATS does.  Cleared by crt_multi_render (it gathers no
                                     variance; crt_multi_render_buffers sets the flag itself when the VARIANCE plane is wanted) */
-    CRT_FLAG_HALF_BUFFERS = 64u  /* keep, beside c and q, the sums of the even and of the odd samples of every pixel on the scene handle:
+    CRT_FLAG_HALF_BUFFERS = 64u, /* keep, beside c and q, the sums of the even and of the odd samples of every pixel on the scene handle:
                                     crt_half_buffers reads two independent half-sample frames from them.  Implies CRT_FLAG_VARIANCE: the call
                                     behaves as if both were set (commit ring off included); frame, c and q are bit for bit those of
                                     CRT_FLAG_VARIANCE alone.  Cleared by crt_multi_render, as CRT_FLAG_VARIANCE is */
+    CRT_FLAG_PIXEL_FILTER = 128u /* keep, beside whatever else the call keeps, the sums of the handle's pixel reconstruction filter
+                                    (crt_set_pixel_filter): crt_filtered_frame reads the filtered frame from them.  The frame, c, q and the
+                                    halves of the call are bit for bit those without the flag.  Switches the commit ring off for the call, as
+                                    CRT_FLAG_VARIANCE does; implies no other flag.  One device only (world == 1).  Cleared by
+                                    crt_multi_render and crt_multi_render_buffers; ignored by crt_render_adaptive, crt_render_map and
+                                    crt_render_planned */
 };
 
 typedef struct {
@@ -332,6 +338,58 @@ int crt_variance_device(crt_scene* scene, void* d_var, void* hip_stream, uint32_
 int crt_half_buffers(crt_scene* scene, float* out_a, float* out_b, uint32_t* samples_done);
 /* d_a, d_b: device buffers on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
 int crt_half_buffers_device(crt_scene* scene, void* d_a, void* d_b, void* hip_stream, uint32_t* samples_done);
+
+/* Pixel reconstruction filters (CRT_FLAG_PIXEL_FILTER): the frame in which every radiance sample counts for the pixels around its
+ * jittered position, weighted by a box, tent or Mitchell-Netravali filter, made from the very paths of the box-filtered frame (the
+ * reference's, Render.cuh:348, which stays the default: sample k of pixel p counts for p with weight 1 and for nobody else).
+ * crt_set_pixel_filter puts a filter on the handle (NULL: none).  Allowed: BOX with 0.5 <= radius <= 2, TENT with 1 <= radius <= 2,
+ * MITCHELL (B = C = 1/3) with radius exactly 2; anything else, NaN included, is CRT_ERR_INVALID_ARG and the handle keeps its old filter.
+ * With the flag, crt_render, crt_render_device, crt_render_range and crt_render_range_device keep four more planes per pixel slot on
+ * the scene handle, beside whatever they keep without it: a (three planes) and W (uncached, allocated when the flag is first used,
+ * carried across chunks and progressive ranges as q is).  The frame, c, q and the halves of the same call are bit for bit what they
+ * are without the flag.
+ * Tap weight.  For sample k (its index in the frame) of pixel q = (i', j') and output pixel p = (i, j), with S = params->spp and R the
+ * radius:
+ *   ux = rng_uniform(rj.x), uy = rng_uniform(rj.y) of rj = rng_draw(seed, j' * width + i', k, 0, RNG_JITTER, 0): the very values in
+ *        (0, 1] that placed the path's camera ray in its pixel
+ *   dx = ((float)(i' - i) + ux) - 0.5f          dy = ((float)(j' - j) + uy) - 0.5f
+ *   f(d) = 0 unless d > -R && d <= R (half open, so that BOX with R = 0.5 is a partition: u lies in (0, 1]); inside the support
+ *     BOX       f = 1
+ *     TENT      f = 1 - |d| / R
+ *     MITCHELL  x = |d|;  x < 1: f = ((((21 * x - 36) * x) * x) + 16) / 18;  otherwise f = ((((-7 * x + 36) * x - 60) * x) + 32) / 18
+ *   w = f(dx) * f(dy)
+ * every operation one IEEE fp32 operation, no FMA, no reciprocal.
+ * Sums.  a (per channel) and W of every pixel p start from +0.0f; the samples come in frame order k = 0, 1, ...; within a sample the
+ * pixels q around p in row-major order, j' - j = -reach .. reach outer, i' - i inner, reach = ceil(R - 0.5).  Pixels q outside the
+ * frame and taps with w == 0.0f are skipped: nothing is added for them.  For every other tap
+ *   x = L_{q,k} / (float)S (the frame's own quotient)          a = a + w * x   per channel          W = W + w
+ * Read-out (crt_filtered_frame), n = samples accumulated so far (n = S after the range that ends at spp; the sums stay readable until
+ * the next render call on the handle):
+ *   out_mean = a * ((float)S / W)              where W > 0
+ *   out_mean = c * ((float)S / (float)n)       elsewhere, a NaN W included: crt_preview's value
+ *   out_rgb  = the frame's tone map of out_mean
+ * in the layout of the render's outputs (row-major, or the compact tiles with CRT_FLAG_TILED_OUTPUT; padding slots RGB 0 and +0.0f).
+ * So BOX with R = 0.5 gives crt_preview's bits and, at n = S, the frame's own out_mean and RGB.  Either output may be NULL, not both.
+ * Reads the sums only.  *samples_done (optional) receives n.
+ * Refused before any device call, the handle untouched, crt_last_error naming the call: the flag with no filter set
+ * (CRT_ERR_INVALID_ARG); the flag with world > 1 -- a shard does not hold its neighbours -- (CRT_ERR_UNSUPPORTED); a range with
+ * sample_begin > 0 whose filter differs from the filter of the frame in flight (CRT_ERR_INVALID_ARG: the frame in flight can still be
+ * read and continued with its own filter).  crt_filtered_frame: CRT_ERR_INVALID_ARG with no render with the flag on the handle yet;
+ * after a frame any of whose ranges, from sample 0 on, went without the flag; after crt_render_adaptive, crt_render_map or
+ * crt_render_planned, which ignore the flag; with a null scene or both outputs NULL.
+ * Not provided: a Gaussian filter (it needs exp: the three kinds keep the contract polynomial); a variance of the filtered frame, and
+ * with it the filtered frame as a denoiser's input (its noise is correlated between neighbouring pixels); shards and crt_multi; sparse
+ * frames; the sums inside the commit ring. */
+enum { CRT_PIXEL_FILTER_BOX = 0, CRT_PIXEL_FILTER_TENT = 1, CRT_PIXEL_FILTER_MITCHELL = 2 };
+typedef struct {
+    uint32_t kind;   /* CRT_PIXEL_FILTER_* */
+    float radius;    /* in pixels */
+} crt_pixel_filter;
+int crt_pixel_filter_defaults(crt_pixel_filter* out);                        /* TENT, radius 1 */
+int crt_set_pixel_filter(crt_scene* scene, const crt_pixel_filter* filter);  /* NULL: none */
+int crt_filtered_frame(crt_scene* scene, uint8_t* out_rgb, float* out_mean, uint32_t* samples_done);
+/* d_rgb, d_mean: device buffers on the scene's device; enqueued on hip_stream (NULL = default stream) without synchronizing */
+int crt_filtered_frame_device(crt_scene* scene, void* d_rgb, void* d_mean, void* hip_stream, uint32_t* samples_done);
 
 /* Variance-driven adaptive sampling: one frame in which pixel p receives samples 0 .. n_p - 1 of its S = params->spp samples, n_p chosen
  * per pixel by a stop criterion on the running sums of the crt_variance contract.  Sample k of pixel p is the path it is in crt_render's
