@@ -164,7 +164,8 @@ __device__ __forceinline__ wmask visit_front(const DevScene& sc, const MParams3&
     // pushed: the loser of (2,3), then the loser of the final, then the loser of (0,1) -- which is popped first
     V.l3 = sp; V.l2 = add_mask(V.l3, V.pd); V.l1 = add_mask(V.l2, V.pg); V.sp_new = add_mask(V.l1, V.pb);
     constexpr int LV = LDS::LV;
-    if (STATS && (uint32_t)V.sp_new > max_sp) max_sp = (uint32_t)V.sp_new;
+    // (of the lanes whose visit counts: a lane outside the batch carries the depth byte of slot 0, which is whatever LDS held if that slot has had no ray yet)
+    if (STATS && lanes(EFF) && (uint32_t)V.sp_new > max_sp) max_sp = (uint32_t)V.sp_new;
     // the nearest inner child next; without one (nothing was pushed either: the top is the one read when the visit began) the stack's top, or the end
     const wmask NF = EFF & ~IF;
     const wmask POP = NF & bal(V.sp_new > 0);

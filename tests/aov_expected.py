@@ -20,8 +20,18 @@ def primary_rays(name, width, height, spp, crop=None, seed=0):
 def expected_aov(name, width, height, spp, crop=None, seed=0):
     """The contract of include/crt.h, restated in numpy float32 on the oracle's primary rays."""
     _, _, t, tri, (ch, cw) = primary_rays(name, width, height, spp, crop, seed)
-    tris = util.oracle_scene(name).tris()
-    mat = util.host_scene(name).triangles()["material"].astype(np.int32)
+    return fold_aov(t, tri, ch, cw, util.oracle_scene(name).tris(), util.host_scene(name).triangles()["material"].astype(np.int32))
+
+
+def expected_aov_of(osc, scene, view, light_sample_n, width, height, spp, seed=0):
+    """The same for a scene of a test's own: osc and scene are its oracle and host forms, view = (eye, inverse view matrix, fov)."""
+    _, _, t, tri, (ch, cw) = util.primary_rays_of(osc, *view, light_sample_n, width, height, spp, None, seed)
+    return fold_aov(t.reshape(ch * cw, spp), tri.reshape(ch * cw, spp), ch, cw, osc.tris(), scene.triangles()["material"].astype(np.int32))
+
+
+def fold_aov(t, tri, ch, cw, tris, mat):
+    """The buffers from the primary rays' answers t, tri: (pixels, spp); tris: the oracle's triangles; mat: material index per triangle"""
+    spp = tri.shape[1]
     p = tri.shape[0]
     a = np.zeros((p, 3), dtype=np.float32)
     nrm = np.zeros((p, 3), dtype=np.float32)

@@ -91,6 +91,75 @@ def _write_scaled_soup_scene(d, scale):
     return obj, mtl
 
 
+def geometric_chain_triangles(E, ratio=1.2, row=1):
+    """The triangles of write_geometric_chain_scene as an (n, 3, 3) float64 array, in file order (position by position, then along y)"""
+    tris = []
+    x = 2.0 ** -E
+    while x < 2.0 ** E:
+        s = x * (ratio - 1.0) / 2.0
+        w = s / row
+        for k in range(row):
+            tris.append([[x, k * w, 0.0], [x + s, (k + 1) * w, 0.0], [x, k * w, s]])
+        x *= ratio
+    return np.array(tris, dtype=np.float64)
+
+
+def write_geometric_chain_scene(d, E, ratio=1.2, row=1):
+    """geo(E, ratio): a row of triangles in geometric progression along x, from 2^-E up to 2^E -- at position x the triangle (x, 0, 0),
+    (x + s, s, 0), (x, 0, s) with s = x (ratio - 1) / 2, then x *= ratio.  The SAH builder's 32 centroid bins peel such a row a few
+    leaves at a time, so the tree is a chain about as deep as the row is long (the re-insertion pass and the 4-wide collapse keep it).
+    row > 1: `row` triangles side by side in y at each position, each 1 / row of the width -- an inner subtree hangs off every position
+    of the chain.  All grey but the last, which is the light."""
+    tris = geometric_chain_triangles(E, ratio, row)
+    with open(os.path.join(d, "chain.mtl"), "w") as m:
+        m.write("newmtl grey\nKd 0.6 0.6 0.6\nNs 1\nnewmtl light\nKe 20 20 20\nKd 0 0 0\nNs 1\n")
+    with open(os.path.join(d, "chain.obj"), "w") as o:
+        o.write("mtllib chain.mtl\nusemtl grey\n")
+        for i, t in enumerate(tris):
+            if i == len(tris) - 1:
+                o.write("usemtl light\n")
+            for p in t:
+                o.write("v %.9g %.9g %.9g\nvn 0 1 0\nvt 0 0\n" % tuple(p))
+            o.write("f %d/%d/%d %d/%d/%d %d/%d/%d\n" % ((3 * i + 1,) * 3 + (3 * i + 2,) * 3 + (3 * i + 3,) * 3))
+    return os.path.join(d, "chain.obj"), d
+
+
+def geometric_chain_rays(E, ratio=1.2, row=1, n=4096, seed=7):
+    """Rays for geo(E, ratio): (origins, directions, the slice of the first group), a third of the n rays in each of three groups.
+    Along +-x with y = z drawn log-uniformly over the scene's scales, from before the small end and from beyond the large end (from the
+    small end towards the large one the inner child is the nearest and its siblings are still ahead: the stack grows); from
+    log-uniform points towards random points on random triangles; random origins and directions."""
+    rng = np.random.RandomState(seed)
+    tris = geometric_chain_triangles(E, ratio, row)
+    lo, hi = -float(E), float(E)
+    k = n // 3
+
+    def log_uniform(shape):
+        return 2.0 ** rng.uniform(lo, hi, shape)
+
+    o = np.zeros((n, 3))
+    d = np.zeros((n, 3))
+    # the width at position x is s = 0.1 x for ratio 1.2: y = z = c lies inside the triangles from x = 2 c / (ratio - 1) * 2 on
+    c = log_uniform(k) * (ratio - 1.0) / 8.0
+    fwd = rng.rand(k) < 0.75
+    o[:k, 0] = np.where(fwd, -(2.0 ** -E), 2.0 ** (E + 1))
+    o[:k, 1] = c / row
+    o[:k, 2] = c
+    d[:k, 0] = np.where(fwd, 1.0, -1.0)
+    # aimed: from a log-uniform point (either sign per coordinate) at a random point of a random triangle
+    t = tris[rng.randint(0, len(tris), k)]
+    a, b = rng.rand(k, 1), rng.rand(k, 1)
+    flip = (a + b) > 1
+    a, b = np.where(flip, 1 - a, a), np.where(flip, 1 - b, b)
+    p = t[:, 0] + a * (t[:, 1] - t[:, 0]) + b * (t[:, 2] - t[:, 0])
+    o[k:2 * k] = log_uniform((k, 3)) * rng.choice([-1.0, 1.0], (k, 3))
+    d[k:2 * k] = p - o[k:2 * k]
+    # random
+    o[2 * k:] = log_uniform((n - 2 * k, 3)) * rng.choice([-1.0, 1.0], (n - 2 * k, 3))
+    d[2 * k:] = rng.normal(size=(n - 2 * k, 3))
+    return o.astype(np.float32), d.astype(np.float32), slice(0, k)
+
+
 def _scene(obj, mtl, thresh, w=32, h=24):
     s = crt.Scene(w, h)
     s.add_obj(obj, mtl)

@@ -11,9 +11,9 @@ import pytest
 
 import cudaraytracing_amd as crt
 import oracle_lib as O
-import tree_check as TC
 import util
 from scene_files import _write_box_scene, _write_soup_scene, write_signed_zero_scene
+from traversal_trees import _checked_export, _same_trees
 
 pytestmark = pytest.mark.gpu
 REPORT = os.path.join(util.ROOT, "gpurun_out", "sah_build_report.jsonl")
@@ -28,24 +28,6 @@ def _pair(scene, spp, p_rr, lsn, monkeypatch):
     monkeypatch.delenv("CRT_SAH_HOST", raising=False)
     dev.free()
     return dev2, host
-
-
-TREE_ARRAYS = ("nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo_i", "rec_map")
-
-
-def _checked_export(r, scene):
-    """The trees of a handle (Render.export_trees), after tests/tree_check.py found no violation in them."""
-    ex = r.export_trees()
-    v = TC.check_trees(ex, r.accel_info(), scene.nodes(), scene.root, scene.triangles())
-    assert v == [], v
-    return ex
-
-
-def _same_trees(a, b):
-    for k in TREE_ARRAYS:
-        assert a[k].tobytes() == b[k].tobytes(), k
-    for k in ("root4", "root4i", "n_mixed4i", "coord_max", "stack_cap"):
-        assert a[k] == b[k], k
 
 
 def _report(name, a, b):

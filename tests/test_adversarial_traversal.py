@@ -19,6 +19,7 @@ import util
 from blocked_restated import _oracle_blocked
 from parity_cases import _check_rays, _grazing_rays, _load
 from scene_files import _write_box_scene, _write_soup_scene
+from traversal_trees import LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
@@ -342,17 +343,6 @@ def test_raw_directions_with_infinite_components():
             assert np.array_equal(tri_r, tri_f) and np.array_equal(util.bits(t_r), util.bits(t_f)), mode
     finally:
         r.free()
-
-
-LAYOUTS = {  # environment of each form of k_mega3's pool (csrc/crt_render.hip: use_dec, use_ref16, use_impl)
-    "coupled-16": {"CRT_DEC": "0"},
-    "coupled-32": {"CRT_DEC": "0", "CRT_REF16": "0"},
-    "decoupled-16": {"CRT_DEC": "1"},                       # (on the tree without its rows of refs where the scene offers it: both shipped scenes do)
-    "decoupled-16, rows of refs": {"CRT_DEC": "1", "CRT_IMPL": "0"},
-    "decoupled-32": {"CRT_DEC": "1", "CRT_REF32": "1"},
-    "default": {},  # decoupled-16 for CRT_TRAVERSAL_EXACT on a scene of up to about 160 000 triangles, coupled-16 for the other modes
-    "default, leaf records beyond 16 bits": {"CRT_REF16": "0"},  # a scene of 50 000 - 160 000 triangles: coupled-32 for the other modes
-}
 
 
 @pytest.mark.parametrize("name", ["cornell-box", "veach-mis"])

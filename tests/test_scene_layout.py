@@ -2,25 +2,22 @@
 plain C++; tools/scene_layout_dump.cpp, compiled here with g++ and the library's host flags, runs it on a scene description and writes the
 arrays of crt_scene_export.  On the CPU the invariants of the exactness proof (tests/tree_check.py, I1-I9) hold on the dump of every scene
 below; on the GPU the arrays read back from device memory (Render.export_trees) equal the dump byte for byte."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import cudaraytracing_amd as crt
 from cudaraytracing_amd import _capi as capi
-import host_program as HP
 import tree_check as TC
 import util
 from scene_files import _scene, _write_box_scene, _write_soup_scene, write_signed_zero_scene
+from traversal_trees import _dump, build_dump_tool
 
 COUNTS = ["n_leaves", "n_nodes2", "n_nodes4", "depth2", "depth4", "index_splits", "layout_caps"]   # crt_accel_info without its clocks
 
 
 @pytest.fixture(scope="module")
 def tool(tmp_path_factory):
-    return HP.build("scene_layout_dump.cpp", str(tmp_path_factory.mktemp("layout_tool") / "scene_layout_dump"), extra=["-pthread", "-fno-fast-math"])
+    return build_dump_tool(tmp_path_factory.mktemp("layout_tool"))
 
 
 def _make(name, d):
@@ -31,23 +28,6 @@ def _make(name, d):
     if name == "one-leaf":
         return _scene(*_write_box_scene(d, n_side=12), 400)
     return _scene(*write_signed_zero_scene(d), 2)
-
-
-def _dump(tool, scene, d):
-    """The tool's arrays and scalars in the dict shape of Render.export_trees(), and its crt_accel_info as accel_info() gives it."""
-    for name, a in (("nodes", scene.nodes()), ("tris", scene.triangles()), ("light_tris", scene.light_triangles()),
-                    ("materials", scene.materials()), ("lights", scene.lights())):
-        a.tofile(os.path.join(d, "desc_%s.bin" % name))
-    subprocess.run([tool, d, str(scene.root)], check=True, timeout=300)
-    ex = {}
-    for name, dt in crt.Render.EXPORT_ARRAYS.items():
-        a = np.fromfile(os.path.join(d, name + ".bin"), dtype=dt)
-        ex[name] = a.reshape(-1, 4) if dt is np.float32 else a
-    with open(os.path.join(d, "scalars.bin"), "rb") as f:
-        ex.update(capi.TreeScalars.from_buffer_copy(f.read()).as_dict())
-    with open(os.path.join(d, "accel.bin"), "rb") as f:
-        info = capi.AccelInfo.from_buffer_copy(f.read()).as_dict()
-    return ex, info
 
 
 @pytest.mark.parametrize("name", ["veach-mis", "cornell-box", "soup2", "soup5", "one-leaf", "zeros"])
