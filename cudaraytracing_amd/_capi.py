@@ -144,6 +144,10 @@ class AovShadingBuffers(C.Structure):
     _fields_ = [("emission", C.c_void_p), ("diffuse_albedo", C.c_void_p)]
 
 
+class AovDirectBuffers(C.Structure):
+    _fields_ = [("direct", C.c_void_p), ("unshadowed", C.c_void_p), ("direct_variance", C.c_void_p), ("visibility", C.c_void_p)]
+
+
 class ModulateParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("albedo_floor", C.c_float)]
 
@@ -344,6 +348,8 @@ AOV_SPECULAR_BUFFERS = {"guide_albedo": (3, np.float32), "last_normal": (3, np.f
                         "bounces": (1, np.float32), "last_tri": (1, np.int32)}
 # the buffers of crt_aov_shading_buffers
 AOV_SHADING_BUFFERS = {"emission": (3, np.float32), "diffuse_albedo": (3, np.float32)}
+# the buffers of crt_aov_direct_buffers
+AOV_DIRECT_BUFFERS = {"direct": (3, np.float32), "unshadowed": (3, np.float32), "direct_variance": (3, np.float32), "visibility": (1, np.float32)}
 
 
 class Task(C.Structure):
@@ -379,7 +385,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_filter_select_defaults", "crt_filter_select_scratch_bytes", "crt_filter_select", "crt_filter_select_device",
            "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device",
            "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device",
-           "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device"]
+           "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device",
+           "crt_render_aov_direct", "crt_render_aov_direct_device"]
 
 _lib = None
 
@@ -436,6 +443,9 @@ def lib():
                                          C.POINTER(AovInfo)]
     L.crt_render_aov_shading_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovBuffers), C.POINTER(AovShadingBuffers),
                                                 C.c_void_p, C.POINTER(AovInfo)]
+    L.crt_render_aov_direct.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovDirectBuffers), C.POINTER(AovInfo)]
+    L.crt_render_aov_direct_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovDirectBuffers), C.c_void_p,
+                                               C.POINTER(AovInfo)]
     L.crt_modulate_defaults.argtypes = [C.POINTER(ModulateParams)]
     L.crt_demodulate.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(ModulateInfo)]

@@ -176,7 +176,9 @@ class Render:
         self.stats = None
         self.aov_info = None
         self.aov_specular_info = None
+        self.aov_direct_info = None
         self.aov_buffers = None
+        self.direct_buffers = None  # run_view_denoised with split_direct: direct and direct_variance of the frame
         self.shading_buffers = None  # run_view_denoised / run_view_temporal with demodulate: emission and diffuse_albedo of the frame
         self.denoise_info = None
         self.variance_buffer = None
@@ -573,6 +575,22 @@ class Render:
                                 [(first_ptrs, capi.AOV_BUFFERS, capi.AovBuffers, True), (ptrs, capi.AOV_SHADING_BUFFERS, capi.AovShadingBuffers, False)],
                                 "aov_info", stream, want_info)
 
+    def run_view_aov_direct(self, eye_pos, inv_view_mat, fovY, want=tuple(capi.AOV_DIRECT_BUFFERS), width=None, height=None):
+        """Direct-light AOVs (crt_render_aov_direct, contract: include/crt.h): the first-vertex next-event term of the very paths
+        run_view traces with the same camera and settings, recomputed sample for sample.  Returns {name: array} for the names in `want`
+        (direct, unshadowed, direct_variance: (H, W, 3) float32; visibility: (H, W) float32).  light_sample_n is the frame's; p_rr is
+        not read.  self.aov_direct_info gets rays (camera and traced shadow rays), chunks (sub-batches), total_ms."""
+        return self._aov_host("crt_render_aov_direct", (eye_pos, inv_view_mat, fovY), width, height,
+                              [(want, capi.AOV_DIRECT_BUFFERS, capi.AovDirectBuffers, False)], "aov_direct_info")
+
+    def run_view_aov_direct_device(self, eye_pos, inv_view_mat, fovY, ptrs, stream=None, rank=0, world=1, tiled=False, want_info=True,
+                                   width=None, height=None):
+        """The same with outputs in device memory: ptrs = {name: raw device pointer}, layout as run_view_aov_device.  The call
+        synchronizes the stream once per sub-batch (and once more with want_info, which sets self.aov_direct_info)."""
+        return self._aov_device("crt_render_aov_direct_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
+                                [(ptrs, capi.AOV_DIRECT_BUFFERS, capi.AovDirectBuffers, False)], "aov_direct_info", stream, want_info,
+                                kind="direct-light AOV")
+
     def run_view_aov_specular(self, eye_pos, inv_view_mat, fovY, max_bounces=None, want=tuple(capi.AOV_SPECULAR_BUFFERS), width=None, height=None):
         """AOVs that follow perfect-mirror bounces from the first hit (crt_render_aov_specular, contract: include/crt.h): returns
         {name: array} for the names in `want` (guide_albedo, last_normal: (H, W, 3) float32; path_depth, bounces: (H, W) float32;
@@ -591,7 +609,7 @@ class Render:
 
     def run_view_denoised(self, eye_pos, inv_view_mat, fovY, iterations=None, sigma_color=None, sigma_normal=None, sigma_albedo=None,
                           sigma_depth=None, width=None, height=None, variance_guided=False, specular_guides=False, max_bounces=None,
-                          demodulate=False, albedo_floor=None, nlm=None, regress=None, scales=None):
+                          demodulate=False, albedo_floor=None, nlm=None, regress=None, scales=None, split_direct=False):
         """The frame of run_view, filtered by the AOV-guided a-trous denoiser (crt_denoise) with the albedo, normal and depth of
         run_view_aov as guides: returns (rgb (H, W, 3) uint8, mean (H, W, 3) float32) of the denoised frame.  The noisy frame stays in
         self.frame_buffer / self.mean_buffer, the guides in self.aov_buffers, the filter's timer in self.denoise_info.
@@ -609,11 +627,18 @@ class Render:
         caller's sigmas -- the albedo guide is still passed; sigma_albedo=float("inf") drops it -- and comes back through modulate().
         scales: None or 1 is the single filter call; 2 .. 4 runs the filter as denoise_multiscale does, a Laplacian pyramid of that many
         scales with the same settings at each, where the single call stands (so it composes with demodulate and specular_guides).  It
-        needs variance_guided, nlm or regress (ValueError); self.denoise_info is then denoise_multiscale's dict."""
+        needs variance_guided, nlm or regress (ValueError); self.denoise_info is then denoise_multiscale's dict.
+        split_direct: direct and indirect light are filtered separately (SVGF's split) -- `direct` of run_view_aov_direct, with its
+        direct_variance, and mean - direct, with the frame's variance (which overstates it), through the same filter with the same
+        settings; the two results are added (crt_modulate with a zero albedo: a + b, and the frame's tone map).  With the plain and the
+        variance-guided filter, one scale, no demodulate (ValueError otherwise).  self.direct_buffers keeps direct and direct_variance,
+        self.denoise_info the info of the indirect part's call."""
         self._handle("run_view_denoised")
         name, settings, scales = _denoise_request("run_view_denoised", variance_guided, iterations, sigma_color, sigma_normal, sigma_albedo, sigma_depth,
                                                   nlm, regress, scales, demodulate)
         with_variance = _FILTERS[name][2]
+        if split_direct and (name not in ("atrous", "var") or scales > 1 or demodulate):
+            raise ValueError("run_view_denoised: split_direct works with the plain and the variance-guided filter at one scale, without demodulate")
         self.run_view(eye_pos, inv_view_mat, fovY, width=width, height=height, want_variance=with_variance)
         guides = ("albedo", "normal", "depth")
         if demodulate:
@@ -625,6 +650,13 @@ class Render:
         if specular_guides:
             self.aov_buffers["albedo"] = self.run_view_aov_specular(eye_pos, inv_view_mat, fovY, max_bounces=max_bounces, want=("guide_albedo",),
                                                                     width=width, height=height)["guide_albedo"]
+        if split_direct:
+            self.direct_buffers = self.run_view_aov_direct(eye_pos, inv_view_mat, fovY, want=("direct", "direct_variance"), width=width, height=height)
+            direct, dvar = self.direct_buffers["direct"], self.direct_buffers["direct_variance"]
+            a = _run_filter(name, direct, dvar if with_variance else None, self.aov_buffers, settings, self.device, False)[1]
+            _, b, self.denoise_info = _run_filter(name, self.mean_buffer - direct, self.variance_buffer if with_variance else None, self.aov_buffers,
+                                                  settings, self.device, False)
+            return _modulate(a, np.zeros_like(a), b, device=self.device)
         return self._filter_frame(name, settings, scales, demodulate, albedo_floor)
 
     def _filter_frame(self, name, settings, scales, demodulate, albedo_floor):
@@ -1049,6 +1081,8 @@ _MULTI_REFUSALS = {
     "run_view_aov_device": "the AOV pass is a single-device interface (crt_render_aov_device)",
     "run_view_aov_shading": "the AOV pass is a single-device interface (crt_render_aov_shading)",
     "run_view_aov_shading_device": "the AOV pass is a single-device interface (crt_render_aov_shading_device)",
+    "run_view_aov_direct": "the AOV pass is a single-device interface (crt_render_aov_direct)",
+    "run_view_aov_direct_device": "the AOV pass is a single-device interface (crt_render_aov_direct_device)",
     "run_view_aov_specular": "the AOV pass is a single-device interface (crt_render_aov_specular)",
     "run_view_aov_specular_device": "the AOV pass is a single-device interface (crt_render_aov_specular_device)",
     "run_view_denoised": "the denoiser is a single-device interface (crt_denoise): gather the frame first",

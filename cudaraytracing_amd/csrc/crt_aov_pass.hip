@@ -1,10 +1,12 @@
-// cudaraytracing_amd/csrc/crt_aov_pass.hip -- the host side of crt_aov.hip: the AOV passes (first hit, shading, mirror bounces) and their
+// cudaraytracing_amd/csrc/crt_aov_pass.hip -- the host side of crt_aov.hip and crt_aov_direct.hip: the AOV passes (first hit, shading, mirror bounces, direct light) and their
 // entry points in the C ABI of include/crt.h (crt_render_aov*, crt_aov_specular_defaults).  Every pass is the camera rays of samples
 // 0 .. spp-1 of every pixel slot of the shard, in chunks of whole samples of at most kAovChunkRays rays (32 B of query pool + 16 B of
 // results per ray: 1.6 GB), each traced by trace_queries (crt_render.hip, through crt_render.h) and folded into the per-slot running sums
 // in sample order.  Uses the handle's query pool and trace buffers, as crt_intersect does; the accumulator of a progressive render
-// (accum, acc) is not touched.  What the three passes share is stated once: aov_check, aov_pass, aov_host_form.
+// (accum, acc) is not touched.  What the passes share is stated once: aov_check, aov_pass, aov_host_form.
 #include "crt_render.h"
+
+#include "crt_aov_direct.h"
 
 #include <algorithm>
 #include <cstring>
@@ -21,17 +23,19 @@ const uint32_t kAovChunkRays = 1u << 25;
 bool any_buffer(const crt_aov_buffers* o) { return o && (o->albedo || o->normal || o->depth || o->coverage || o->tri || o->material); }
 bool any_buffer(const crt_aov_shading_buffers* o) { return o && (o->emission || o->diffuse_albedo); }
 bool any_buffer(const crt_aov_specular_buffers* o) { return o && (o->guide_albedo || o->last_normal || o->path_depth || o->bounces || o->last_tri); }
+bool any_buffer(const crt_aov_direct_buffers* o) { return o && (o->direct || o->unshadowed || o->direct_variance || o->visibility); }
 
-// The argument check of all six entry points (`who`: the entry's base name), before any device call.  missing: a pointer its form requires
-// is null; unnamed: what to say when its structs name no output buffer (null: they name one); sp: the specular form's settings.
+// The argument check of all eight entry points (`who`: the entry's base name), before any device call.  missing: a pointer its form requires
+// is null; unnamed: what to say when its structs name no output buffer (null: they name one); sp: the specular form's settings;
+// camera_rays_only: false for the direct-light pass, which takes next-event samples and checks light_sample_n as a render does.
 int aov_check(const char* who, const crt_scene* sc, const crt_camera* cam, const crt_params* prm, bool missing, const char* unnamed,
-              const crt_aov_specular_params* sp = nullptr)
+              const crt_aov_specular_params* sp = nullptr, bool camera_rays_only = true)
 {
     const std::string w(who);
     if (!sc || !cam || !prm || missing) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (unnamed) return fail(CRT_ERR_INVALID_ARG, w + ": " + unnamed);
     if (sp && (sp->max_bounces < 1 || sp->max_bounces > 8)) return fail(CRT_ERR_INVALID_ARG, w + ": max_bounces must be in [1, 8]");
-    const int rc = params_check(who, prm, true);
+    const int rc = params_check(who, prm, camera_rays_only);
     if (rc != CRT_OK) return rc;
     if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
         return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 pixel slots in a shard");
@@ -171,6 +175,88 @@ int specular_pass(crt_scene* sc, const crt_camera* cam, const crt_params* prm, c
         });
 }
 
+// crt_render_aov_direct: the first-vertex next-event term of the frame's own paths (kernels: crt_aov_direct.hip).  After a chunk's
+// camera rays are traced, k_aov_direct_vertex copies what the later stages need out of their answers -- on the megakernel pipeline
+// trace_queries returns the handle's one answer array, which the next trace overwrites.  The chunk's (sample, q) entries are then walked in
+// sub-batches of at most kAovChunkRays plane entries (CRT_AOV_DIRECT_BATCH: a test's smaller number): the set-up kernel writes the
+// contributions and compacts the traced shadow rays into the query pool behind the camera rays, the host reads their count -- one 4-byte
+// copy into pinned memory and one synchronization per sub-batch, as the specular pass per bounce --, traces that many, the answer kernel
+// clears the blocked flags and the resolve folds the sub-batch into the slots' running sums.  batches: the sub-batches of the call.
+int direct_pass(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_direct_buffers* out, hipStream_t st, crt_aov_info* info)
+{
+    if ((uint64_t)sc->dev.n_lights * (uint64_t)prm->light_sample_n > 0xffffu) // (as crt_render)
+        return fail(CRT_ERR_UNSUPPORTED, "crt_render_aov_direct: more than 65535 next-event samples per vertex");
+    AovDirectParams D;
+    std::memset(&D, 0, sizeof(D));
+    const uint32_t n_q = (uint32_t)sc->dev.n_lights * (uint32_t)prm->light_sample_n;
+    size_t second = 0;        // where in the query pool the shadow rays go: behind the camera rays of the largest chunk
+    uint64_t batch_pairs = 1; // (sample, q) entries of a sub-batch
+    uint32_t batches = 0;
+    const int rc = aov_pass(sc, cam, prm, st, info,
+        [&](uint64_t max_rays, AovParams& A) {
+            batch_pairs = std::max<uint64_t>(1, env_u32("CRT_AOV_DIRECT_BATCH", kAovChunkRays) / A.nslots);
+            batch_pairs = std::min<uint64_t>(batch_pairs, std::max<uint64_t>(1, max_rays / A.nslots * n_q)); // (no more than a chunk has)
+            const uint64_t cap = batch_pairs * A.nslots;
+            // every buffer at its final size before the first launch: growing one later would drop what a stage has left in it
+            sc->p_ro.ensure(max_rays + cap); sc->p_rd.ensure(max_rays + cap); sc->p_res.ensure(max_rays + cap);
+            sc->aovs_item.ensure(cap); sc->aovd_plane.ensure(cap); sc->aovd_vert.ensure(max_rays);
+            if (choose_pipeline(sc) == 4) (void)sc->L.answers(std::max(max_rays, cap));
+            sc->aov_acc.ensure((size_t)A.nslots * kAovDirectAccRows);
+            sc->aovs_count.ensure_uncached(1);
+            if (!sc->h_aovs_count) HIP_CHECK(hipHostMalloc((void**)&sc->h_aovs_count, sizeof(unsigned int), hipHostMallocDefault));
+            second = max_rays;
+            D.seed = prm->seed; D.spp = prm->spp;
+            D.tri_nm = sc->dev.tri_nm; D.mats = sc->dev.mats; D.ltri = sc->dev.ltri; D.lights = sc->dev.lights;
+            D.n_q = n_q; D.lsn = prm->light_sample_n; D.inv_lsn_pow2 = inv_if_pow2(prm->light_sample_n);
+            D.lsn_div = make_fastdiv((uint32_t)std::max(1, prm->light_sample_n));
+            D.reference_mode = prm->traversal == CRT_TRAVERSAL_REFERENCE ? 1u : 0u;
+            D.vert = sc->aovd_vert.p; D.plane = sc->aovd_plane.p; D.count = sc->aovs_count.p; D.acc = sc->aov_acc.p;
+            D.out_ro = sc->p_ro.p + second; D.out_rd = sc->p_rd.p + second; D.out_res = sc->p_res.p + second; D.out_idx = sc->aovs_item.p;
+            D.direct = out->direct; D.unshadowed = out->unshadowed; D.direct_variance = out->direct_variance; D.visibility = out->visibility;
+        },
+        [&](AovParams& A) -> uint64_t {
+            static_cast<SlotMap&>(D) = A;
+            D.sample_begin = A.sample_begin; D.n_samples = A.n_samples;
+            D.cam_ro = A.pool.ro; D.cam_rd = A.pool.rd; D.res = A.res; D.res_stride = A.res_stride;
+            const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
+            const uint64_t total = (uint64_t)A.n_samples * n_q;
+            uint64_t rays = 0;
+            if (total == 0) { // no next-event samples: the last chunk writes the outputs of sums that never started
+                if (!A.last_chunk) return 0;
+                D.s_first = D.q_first = D.e_count = 0; D.first_batch = D.last_batch = 1;
+                launch_aov_direct_resolve(D, st);
+                batches++;
+                return 0;
+            }
+            launch_aov_direct_vertex(D, st); // (before the first shadow trace: it overwrites the camera answers)
+            HIP_CHECK(hipGetLastError());
+            for (uint64_t e0 = 0; e0 < total; e0 += batch_pairs) {
+                const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch_pairs, total - e0);
+                D.s_first = (uint32_t)(e0 / n_q); D.q_first = (uint32_t)(e0 % n_q); D.e_count = cnt;
+                D.first_batch = A.first_chunk && e0 == 0; D.last_batch = A.last_chunk && e0 + cnt == total;
+                HIP_CHECK(hipMemsetAsync(sc->aovs_count.p, 0, sizeof(unsigned int), st));
+                launch_aov_direct_setup(D, st);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipMemcpyAsync(sc->h_aovs_count, sc->aovs_count.p, sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+                HIP_CHECK(hipStreamSynchronize(st)); // the one synchronization of a sub-batch: how many shadow rays are traced
+                const uint32_t n = (uint32_t)std::min<uint64_t>(*sc->h_aovs_count, (uint64_t)cnt * A.nslots);
+                if (n > 0) {
+                    D.ans = trace_queries(sc, n, prm->traversal, force_exact, st, D.ans_stride, second);
+                    D.n_traced = n;
+                    launch_aov_direct_answer(D, st);
+                    HIP_CHECK(hipGetLastError());
+                    rays += n;
+                }
+                launch_aov_direct_resolve(D, st);
+                HIP_CHECK(hipGetLastError());
+                batches++;
+            }
+            return rays;
+        });
+    if (rc == CRT_OK && info) info->chunks = batches;
+    return rc;
+}
+
 // The host-buffer form of an entry: a device buffer for every plane whose host pointer is given, the pass on them (pass(d): d[i] the
 // device pointer of plane i, null where the host's is), then a synchronization and the copies back.
 struct HostPlane {
@@ -267,6 +353,25 @@ int crt_render_aov_specular(crt_scene* sc, const crt_camera* cam, const crt_para
     return aov_host_form(sc, prm, {{h.guide_albedo, 3}, {h.last_normal, 3}, {h.path_depth, 1}, {h.bounces, 1}, {h.last_tri, 1}}, [&](float* const* d) {
         const crt_aov_specular_buffers dev{d[0], d[1], d[2], d[3], (int32_t*)d[4]};
         return specular_pass(sc, cam, prm, sp, &dev, nullptr, info);
+    });
+}
+
+int crt_render_aov_direct_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_direct_buffers* dev_out, void* stream,
+                                 crt_aov_info* info)
+{
+    const int rc = aov_check("crt_render_aov_direct", sc, cam, prm, !dev_out, any_buffer(dev_out) ? nullptr : "no output buffer", nullptr, false);
+    if (rc != CRT_OK) return rc;
+    return direct_pass(sc, cam, prm, dev_out, (hipStream_t)stream, info);
+}
+
+int crt_render_aov_direct(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_direct_buffers* host_out, crt_aov_info* info)
+{
+    const int rc = aov_check("crt_render_aov_direct", sc, cam, prm, !host_out, any_buffer(host_out) ? nullptr : "no output buffer", nullptr, false);
+    if (rc != CRT_OK) return rc;
+    const crt_aov_direct_buffers& h = *host_out;
+    return aov_host_form(sc, prm, {{h.direct, 3}, {h.unshadowed, 3}, {h.direct_variance, 3}, {h.visibility, 1}}, [&](float* const* d) {
+        const crt_aov_direct_buffers dev{d[0], d[1], d[2], d[3]};
+        return direct_pass(sc, cam, prm, &dev, nullptr, info);
     });
 }
 

@@ -12,7 +12,7 @@
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]
-//           [--aov-shading PREFIX] [--demodulate]
+//           [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX]
 //           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]] [--gathered PREFIX[,NAME,...]]
 //           [--pixel-filter KIND[,RADIUS] --pixel-filter-out PATH]
 // --pixel-filter KIND[,RADIUS] --pixel-filter-out PATH also writes the frame under a pixel reconstruction filter (one device;
@@ -28,6 +28,8 @@
 // --upsample-guide-spp samples per pixel (default: --spp) --, the low frame demodulated, upsampled along the two sets of guides
 // (crt_upsample, its defaults; RADIUS 1 .. 4) and modulated with the full-resolution buffers.  FACTOR is 2 .. 8 and must divide --width and
 // --height.  -o stays the plain frame at full size.  It runs last: --aov and --aov-shading write the buffers of the plain frame.
+// --aov-direct PREFIX writes the direct-light AOVs of the frame (crt_render_aov_direct, one device): PREFIX_direct.pfm, PREFIX_unshadowed.pfm,
+// PREFIX_direct_variance.pfm (3 channels) and PREFIX_visibility.pfm (1 channel).
 // --aov-shading PREFIX writes the shading AOVs of the frame (crt_render_aov_shading, one device, the trace of --aov): PREFIX.emission.pfm
 // and PREFIX.diffuse_albedo.pfm (3 channels).  --demodulate makes --denoise and --temporal work on irradiance: the frame (and its
 // variance) goes through crt_demodulate with those two buffers before the filter or the blend and the result through crt_modulate, so
@@ -94,7 +96,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
-                             "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate]\n"
+                             "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
                              "       [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]\n"
@@ -112,7 +114,7 @@ int main(int argc, char** argv)
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, denoise, variance, adaptive_samples, pixel_filter_out;
+        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, aov_direct, denoise, variance, adaptive_samples, pixel_filter_out;
         crt_pixel_filter pixel_filter; // --pixel-filter
         bool pixel_filter_on = false;
         bool demodulate = false;
@@ -230,6 +232,7 @@ int main(int argc, char** argv)
                 }
                 if (aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular needs a PREFIX");
             }
+            else if (a == "--aov-direct") { need(i, 1); aov_direct = argv[++i]; if (aov_direct.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-direct needs a PREFIX"); }
             else if (a == "--aov-shading") { need(i, 1); aov_shading = argv[++i]; if (aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading needs a PREFIX"); }
             else if (a == "--demodulate") demodulate = true;
             else if (a == "--upsample") {
@@ -452,7 +455,7 @@ int main(int argc, char** argv)
         // the refusals and refuse_on_many takes the next `count` of them where theirs stood among the other checks.
         const struct { bool present; const char* what; } one_device[] = {
             {!aov.empty(), "--aov renders on one device"}, {!aov_specular.empty(), "--aov-specular renders on one device"},
-            {!aov_shading.empty(), "--aov-shading renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
+            {!aov_shading.empty(), "--aov-shading renders on one device"}, {!aov_direct.empty(), "--aov-direct renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
             {!variance.empty(), "--variance reads one device's buffer"}, {denoise_var, "--denoise-variance filters on one device"},
             {adaptive, "--adaptive renders on one device"}, {temporal != 0, "--temporal accumulates on one device"}, {upsample != 0, "--upsample runs on one device"},
             {denoise_nlm, "--denoise-nlm filters on one device"}, {denoise_regress, "--denoise-regress filters on one device"}};
@@ -461,7 +464,7 @@ int main(int argc, char** argv)
             for (; count-- > 0; row++)
                 if (multi && one_device[row].present) throw crt::Error(CRT_ERR_INVALID_ARG, std::string(one_device[row].what) + " (not with --gpus / --devices)");
         };
-        refuse_on_many(3);
+        refuse_on_many(4);
         if (demodulate && denoise.empty() && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--demodulate needs --denoise PATH or --temporal N");
         if (denoise_specular && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-specular needs --denoise PATH");
         refuse_on_many(6);
@@ -626,6 +629,14 @@ int main(int argc, char** argv)
                 normal[k] = to_u8(255.0f * unit_clamp((render.get_normal_buffer()[k] + 1.0f) / 2.0f));
             }
             write_files("AOV files", {{aov + "_albedo.png", 0, albedo.data()}, {aov + "_normal.png", 0, normal.data()}, {aov + "_depth.pfm", 1, render.get_depth_buffer()}});
+        }
+        if (!aov_direct.empty()) {
+            render.run_view_aov_direct(task.eye_pos, inv_view, fov_y);
+            const crt_aov_info& ai = render.last_aov_direct_info();
+            std::printf("aov-direct: %llu rays in %u sub-batches, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
+            write_files("direct-light AOV files", {{aov_direct + "_direct.pfm", 3, render.get_direct_buffer()}, {aov_direct + "_unshadowed.pfm", 3, render.get_unshadowed_buffer()},
+                                                   {aov_direct + "_direct_variance.pfm", 3, render.get_direct_variance_buffer()},
+                                                   {aov_direct + "_visibility.pfm", 1, render.get_visibility_buffer()}});
         }
         if (!aov_specular.empty() || denoise_specular) { // (after --aov's files: as the guide it replaces the first-hit albedo)
             render.run_aov_specular(task.eye_pos, inv_view, fov_y, specular_bounces, denoise_specular);

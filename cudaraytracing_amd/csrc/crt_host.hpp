@@ -242,6 +242,14 @@ public:
     void set_aov_shading(bool on) { aov_shading_ = on; }
     const float* get_emission_buffer() const { return emission_buffer_.data(); }
     const float* get_diffuse_albedo_buffer() const { return diffuse_albedo_buffer_.data(); }
+    // the direct-light AOVs of the frame run_view draws with the same camera and settings (crt_render_aov_direct): the first-vertex
+    // next-event term of the frame's own paths, its unshadowed form, its variance and the visible fraction of its samples; one device only
+    void run_view_aov_direct(const float eye_pos[3], const float inv_view_mat[9], float fovY);
+    const float* get_direct_buffer() const { return direct_buffer_.data(); }                   // W x H x 3, row 0 = image top
+    const float* get_unshadowed_buffer() const { return unshadowed_buffer_.data(); }           // W x H x 3
+    const float* get_direct_variance_buffer() const { return direct_variance_buffer_.data(); } // W x H x 3
+    const float* get_visibility_buffer() const { return visibility_buffer_.data(); }           // W x H
+    const crt_aov_info& last_aov_direct_info() const { return aov_direct_info_; }
     // on: the filters and the temporal pass work on irradiance (crt_demodulate / crt_modulate with albedo_floor and the shading AOVs of
     // the last run_aov, which set_demodulate therefore switches on).  run_denoise / run_denoise_var demodulate the frame (and its
     // variance), filter, and modulate the result.  run_temporal / run_temporal_moments demodulate each frame before the blend, so the
@@ -431,6 +439,8 @@ private:
     crt_aov_info aov_info_{};
     std::vector<float> guide_albedo_buffer_, last_normal_buffer_, path_depth_buffer_, bounces_buffer_; // run_aov_specular
     crt_aov_info aov_specular_info_{};
+    std::vector<float> direct_buffer_, unshadowed_buffer_, direct_variance_buffer_, visibility_buffer_; // run_view_aov_direct
+    crt_aov_info aov_direct_info_{};
     std::vector<unsigned char> upsampled_buffer_;    // run_view_upsampled
     std::vector<float> upsampled_mean_buffer_;
     crt_upsample_info upsample_info_{};

@@ -247,6 +247,18 @@ void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float 
     check(rc, "Render::run_aov");
 }
 
+void Render::run_view_aov_direct(const float eye_pos[3], const float inv_view_mat[9], float fovY)
+{
+    one_device("Render::run_view_aov_direct", "the AOV pass");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
+    const size_t n = scene_->get_pixels();
+    direct_buffer_.assign(3 * n, 0.0f); unshadowed_buffer_.assign(3 * n, 0.0f); direct_variance_buffer_.assign(3 * n, 0.0f); visibility_buffer_.assign(n, 0.0f);
+    const crt_aov_direct_buffers out{direct_buffer_.data(), unshadowed_buffer_.data(), direct_variance_buffer_.data(), visibility_buffer_.data()};
+    check(crt_render_aov_direct(device_scene_, &cam, &p, &out, &aov_direct_info_), "Render::run_view_aov_direct");
+}
+
 crt_modulate_params Render::modulate_params(const char* who) const
 {
     if (emission_buffer_.size() != (size_t)3 * scene_->get_pixels() || diffuse_albedo_buffer_.size() != emission_buffer_.size())

@@ -27,6 +27,8 @@ bool continues_frame(const FrameMark& f, const crt_params* prm, uint32_t s_begin
 AParams frame_aparams(const crt_scene* sc, const FrameMark& f, const Shard& sh);
 void ensure_events(crt_scene* sc);
 void camera_scale_ar(const crt_camera* cam, const crt_params* prm, float& scale, float& ar);
+// 1 / n for n a power of two (exactly representable), else 0: LParams::inv_lsn_pow2 of a frame and of the direct-light AOV pass
+inline float inv_if_pow2(int32_t n) { return (n > 0 && (n & (n - 1)) == 0) ? 1.0f / (float)n : 0.0f; }
 // The n query rays in the handle's query pool, from `first` on, traced on st: the answers stay on the device, `stride` floats apart
 const float* trace_queries(crt_scene* sc, uint32_t n, uint32_t traversal, bool force_exact, hipStream_t st, uint32_t& stride, size_t first = 0);
 // src: the range's item source.  open: the range belongs to a frame its caller resolves (every range of a sparse frame, its uniform

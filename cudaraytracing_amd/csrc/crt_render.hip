@@ -37,9 +37,6 @@ const size_t kCountersBytes = (size_t)CNT_SHARDS * CNT_STRIDE * sizeof(unsigned 
 
 struct RingPlan { uint32_t samples, spsh, shards; }; // commit ring of a launch: samples held (0 = one radiance per work item), pixel slots per cursor shard
 
-// 1 / n for n a power of two (exactly representable), else 0
-float inv_if_pow2(int32_t n) { return (n > 0 && (n & (n - 1)) == 0) ? 1.0f / (float)n : 0.0f; }
-
 // The decoupled-leaves form (Pool4LdsT) of a launch: CRT_TRAVERSAL_EXACT on a scene whose four-wide nodes fit the 16-bit entries of
 // its stack (inner nodes only: up to about 160 000 triangles) and whose leaf records fit a queue entry.  Since the traversal steps
 // alternate without the scheduler (crt_mega3.hip, CHAIN_MIN) it is the faster form on every scene measured (stand-in cornell-box

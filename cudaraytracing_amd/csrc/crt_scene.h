@@ -73,7 +73,11 @@ struct crt_scene {
     crtk::DevBuf<uint32_t> aovs_item;
     crtk::DevBuf<unsigned int> aovs_count;
     unsigned int* h_aovs_count = nullptr;
-    crtk::DevBuf<unsigned long long> counters;      // [CNT_SHARDS][CNT_STRIDE]
+    // crt_render_aov_direct: per camera ray of a chunk its first vertex (pos.xyz, triangle or -1), and the contribution plane of a
+    // sub-batch (c.xyz, flags per (sample, q, slot) entry); the plane entries of its traced rays are aovs_item, their counter aovs_count,
+    // its running sums aov_acc (kAovDirectAccRows per slot, crt_aov_direct.h)
+    crtk::DevBuf<float4> aovd_vert, aovd_plane;
+    crtk::DevBuf<unsigned long long> counters;     // [CNT_SHARDS][CNT_STRIDE]
     crtk::DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
     crtk::DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)
     crtk::DevBuf<unsigned int> ring_done, ring_state; // commit ring: finished items per (shard, sample), shard words

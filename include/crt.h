@@ -558,6 +558,48 @@ int crt_render_aov_specular(crt_scene* scene, const crt_camera* cam, const crt_p
 int crt_render_aov_specular_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_specular_params* specular,
                                    const crt_aov_specular_buffers* dev_out, void* hip_stream, crt_aov_info* info);
 
+/* Direct-light AOVs: what lights the first hit.  The renderer's draws are addressed by (seed, pixel, sample, depth, purpose, index), so the
+ * next-event samples of a path's first vertex depend on the camera ray's hit alone -- not on p_rr, not on anything later in the path --
+ * and this pass recomputes, sample for sample, the first-vertex direct light L_dir of the very paths the frame traces (Render.cuh:262-284).
+ * fp32, one IEEE operation per symbol, no FMA, no reciprocal multiply.  Per pixel, for the samples k = 0 .. S-1 (S = params->spp) in order:
+ *   camera ray and first hit: crt_render_aov's (origin o = eye, unit direction d, distance t, triangle tri).  A miss, or a hit on an
+ *     emitter (crt_material.has_emit != 0), contributes nothing to any sum: Ld_k = U_k = +0, nothing traced.
+ *   vertex: pos = o + t * d (one multiply, then one add); n = crt_triangle.normal of tri as stored; f_r = kd(m) / pi, the BSDF row of the
+ *     material m of tri that the render kernel reads.
+ *   for q = 0 .. n_lights * light_sample_n - 1 (light q / light_sample_n, repetition q % light_sample_n): the draw r = (seed, pixel, k, 0,
+ *     next-event, q); the light's triangle r.x % count; alpha = u(r.y), beta = u(r.z) * (1 - alpha), gamma = 1 - alpha - beta;
+ *     lpos = (alpha * v1 + beta * v2) + gamma * v3; dist = lpos - pos; dir = normalized(dist); the ray leaves pos along normalized(dir)
+ *     with the limit tl = dist.x / dir.x; len = norm(dist); cos = max(dot(dir, n), 0), cos' = max(-dot(dir, n_light), 0) (a NaN: 0);
+ *     c_q = ((((((ke_light * f_r) * cos) * cos') * area_of_obj) / (len * len)) / light_sample_n  -- the last division is the
+ *     multiplication by 2^-j when light_sample_n = 2^j (the same bits).
+ *   sample q is TRACED when !(c.x == 0 && c.y == 0 && c.z == 0) -- a NaN contribution is traced -- and a sample that is not traced adds
+ *     nothing.  A traced sample is BLOCKED by the reference's blocked() (Render.cuh:19-27) evaluated as the render kernel of
+ *     params->traversal evaluates it: tl - t_hit > 1e-5 with t_hit = FLT_MAX when nothing was hit (REFERENCE: the closest hit; EXACT and
+ *     FAST: any hit that satisfies it).
+ *   Ld_k = sum over q of c_q over the traced, unblocked samples;  U_k = the same over all traced samples; both from +0, in q order.
+ * Outputs (any may be NULL, not all four), from +0.0f, in sample order:
+ *   direct           3 floats  d = d + Ld_k / S
+ *   unshadowed       3 floats  u = u + U_k / S
+ *   direct_variance  3 floats  crt_variance's statistic of the S values Ld_k / S (misses and emitter hits included, as +0):
+ *                              c = c + x, q = q + x * x, then max(S * q - c * c, 0) / (S - 1) per channel; +0 when S = 1
+ *   visibility       float     (float)lit / (float)traced over the pixel's traced samples, lit = those not blocked; 1.0f when none was traced
+ * Consequence: at p_rr = 0 the frame's paths end at their first vertex, so at a pixel none of whose samples hits an emitter `direct` is
+ * crt_render's out_mean bit for bit; at any p_rr it is the first-vertex next-event term of the frame's own paths.
+ * p_rr is not read.  light_sample_n is checked as crt_render checks it (0 .. 4096, at most 65535 samples per vertex); with 0, or a scene
+ * without lights, direct, unshadowed and direct_variance are 0 and visibility is 1.  The other refusals, the layout (row-major, or the
+ * tiled shard with CRT_FLAG_TILED_OUTPUT; padding slots 0), the ignored flags, the chunks of camera rays and the frame in flight on the
+ * handle (left alone) are crt_render_aov's.  Inside a chunk the (sample, q) entries are walked in sub-batches of at most 2^25 entries
+ * x pixel slots (16 B of contribution plane and 44 B of query buffers each; a sub-batch may begin and end inside a sample).
+ * info->rays = camera rays (as crt_render_aov's) + traced shadow rays; info->chunks = sub-batches. */
+typedef struct { float* direct; float* unshadowed; float* direct_variance; float* visibility; } crt_aov_direct_buffers;   /* 3, 3, 3, 1 floats per pixel */
+/* host buffers (W*H or slots elements of 3 or 1 values each); info optional */
+int crt_render_aov_direct(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_direct_buffers* host_out, crt_aov_info* info);
+/* device buffers on the scene's device, work enqueued on hip_stream (NULL = default stream).  Like crt_render_aov_specular_device the
+ * call is not asynchronous: per sub-batch the host reads how many shadow rays are traced -- one 4-byte copy into pinned memory and one
+ * synchronization of the stream.  The outputs are enqueued after the last without a further synchronization, unless info != NULL. */
+int crt_render_aov_direct_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_direct_buffers* dev_out,
+                                 void* hip_stream, crt_aov_info* info);
+
 /* AOV-guided edge-avoiding denoiser: an a-trous ("with holes") wavelet filter with edge-stopping weights on colour, normal, albedo and
  * depth (Dammertz et al. 2010), run as `iterations` passes over a frame's pre-tone-map mean radiance (out_mean of crt_render), guided by
  * the buffers crt_render_aov returns.  An image operation: no scene handle.  Row-major images of width x height; color, albedo, normal

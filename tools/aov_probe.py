@@ -18,6 +18,14 @@ crt_render_aov_device in one process, the two taking turns: the HIP-event time o
 (default 64).
 
   python tools/aov_probe.py --shading [--spp 64] [--reps 20]
+
+--direct times the direct-light pass (crt_render_aov_direct_device, its four buffers) beside crt_render_aov_device and beside a frame at
+p_rr = 0 -- which traces the same camera and shadow rays inside the render kernel -- in one process, the three taking turns: the
+host-clock time around each call plus a synchronize, median and best of --reps, at --spp (default 64).  Also the pass's rays (camera,
+traced shadow rays, samples not traced), its sub-batches = host synchronizations per call, and the frame's own counts from one call with
+statistics.
+
+  python tools/aov_probe.py --direct [--spp 64] [--reps 20]
 """
 import argparse
 import json
@@ -127,9 +135,53 @@ def shading(a):
     print(json.dumps(out), flush=True)
 
 
+def direct(a):
+    """--direct: see the module's text."""
+    w, h = a.width, a.height
+    first, second, frame = image_buffers(a, capi.AOV_BUFFERS), image_buffers(a, capi.AOV_DIRECT_BUFFERS), hipmem.DeviceBuffers({"rgb": w * h * 3})
+    out = {"width": w, "height": h, "reps": a.reps, "runs": []}
+    spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 1, 0.0, t.light_sample_n)  # (p_rr = 0: every path of the frame ends at its first vertex)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        calls = (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, first.ptrs, want_info=False)),
+                 ("direct", lambda: r.run_view_aov_direct_device(t.eye_pos, iv, fov, second.ptrs, want_info=False)),
+                 ("frame", lambda: r.run_view_device(t.eye_pos, iv, fov, frame.ptrs["rgb"], want_stats=False)))
+        for spp in spps:
+            r.set_spp(spp)
+            ms = {k: [] for k, _ in calls}
+            for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
+                for key, fn in calls:
+                    hipmem.device_synchronize()
+                    t0 = time.perf_counter()
+                    fn()
+                    hipmem.device_synchronize()
+                    if i >= 2:
+                        ms[key].append((time.perf_counter() - t0) * 1e3)
+            info = r.run_view_aov_direct_device(t.eye_pos, iv, fov, second.ptrs)
+            camera_rays = r.run_view_aov_device(t.eye_pos, iv, fov, first.ptrs)["rays"]
+            st = r.run_view_device(t.eye_pos, iv, fov, frame.ptrs["rgb"], want_stats=True)
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            run = {"scene": name, "spp": spp, "light_sample_n": t.light_sample_n, "sub_batches": info["chunks"], "syncs_per_call": info["chunks"],
+                   "camera_rays": camera_rays, "shadow_rays_traced": info["rays"] - camera_rays, "direct_event_ms": round(info["total_ms"], 4),
+                   "frame_rays": st["rays"], "frame_shadow_rays": st["shadow_rays"], "frame_rays_untraced": st["rays_untraced"],
+                   "aov_ms": round(med["aov"], 4), "aov_ms_best": round(min(ms["aov"]), 4),
+                   "direct_ms": round(med["direct"], 4), "direct_ms_best": round(min(ms["direct"]), 4),
+                   "frame_p_rr_0_ms": round(med["frame"], 4), "frame_p_rr_0_ms_best": round(min(ms["frame"]), 4),
+                   "direct_over_frame": round(med["direct"] / med["frame"], 4), "direct_over_aov": round(med["direct"] / med["aov"], 4)}
+            out["runs"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+    for b in (first, second, frame):
+        b.free()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--spp", default=None, help="comma-separated; default 16,64,512, with --specular / --shading 64")
+    ap.add_argument("--spp", default=None, help="comma-separated; default 16,64,512, with --specular / --shading / --direct 64")
     ap.add_argument("--scenes", default="cornell-box,veach-mis")
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--height", type=int, default=600)
@@ -137,12 +189,15 @@ def main():
     ap.add_argument("--specular", action="store_true", help="time crt_render_aov_specular_device beside crt_render_aov_device")
     ap.add_argument("--bounces", default="1,2", help="--specular: the max_bounces values")
     ap.add_argument("--shading", action="store_true", help="time crt_render_aov_shading_device beside crt_render_aov_device")
+    ap.add_argument("--direct", action="store_true", help="time crt_render_aov_direct_device beside crt_render_aov_device and a frame at p_rr = 0")
     a = ap.parse_args()
     w, h = a.width, a.height
     if a.specular:
         return specular(a)
     if a.shading:
         return shading(a)
+    if a.direct:
+        return direct(a)
     frame, aovs = hipmem.DeviceBuffers({"rgb": w * h * 3}), image_buffers(a, capi.AOV_BUFFERS)
     rgb, ptrs = frame.ptrs["rgb"], aovs.ptrs
     out = {"width": w, "height": h, "reps": a.reps, "runs": []}

@@ -56,6 +56,12 @@ taking turns, HIP events (a chain: the sum of its calls' timers), the median of 
   python tools/denoise_probe.py --scales [--sizes 800x600,3840x2160] [--calls 50] [--warmup 5]
   python tools/denoise_probe.py --scales --error --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
   python tools/denoise_probe.py --scales --error --ref-seed 7 --error-size 800x600 --ref-spp 2048 --error-spps 8 --max-scales 4
+
+--error --split-direct lists, per scene and --error-spps, the error of crt_denoise and crt_denoise_var on the frame beside the same filters
+on direct and indirect light separately (Render.run_view_denoised(split_direct=True): crt_render_aov_direct supplies the split), on the
+whole frame and on the pixels in shadow.
+
+  python tools/denoise_probe.py --error --split-direct --ref-seed 7 --scenes cornell-box,veach-mis,cornell-box-textured
 """
 import argparse
 import json
@@ -426,6 +432,39 @@ def scales_error_table(a):
     print(json.dumps(out), flush=True)
 
 
+def split_direct_error_table(a):
+    """--error --split-direct: per scene (cornell-box-textured as in --demodulate) and --error-spps, the error of the unfiltered frame, of
+    crt_denoise and crt_denoise_var on the frame, and of the same two with direct and indirect light filtered separately
+    (Render.run_view_denoised(split_direct=True)), against --ref-spp samples of --ref-seed at --error-size; and the same errors on the
+    shadowed pixels alone -- those whose visibility AOV is below 1 -- where the split has something to keep."""
+    import numpy as np
+    w, h = (int(v) for v in a.error_size.split("x"))
+    out = {"width": w, "height": h, "ref_spp": a.ref_spp, "ref_seed": a.ref_seed, "rows": []}
+    for name in a.scenes.split(","):
+        t, view, scene = _probe_scene(name, w, h, a.cells)
+        r = crt.Render(scene, a.ref_spp, t.P_RR, t.light_sample_n)
+        r.seed = a.ref_seed
+        ref = r.run_view(*view).astype(np.float64)
+        r.seed = 0
+        for spp in [int(v) for v in a.error_spps.split(",")]:
+            r.set_spp(spp)
+            shadowed = r.run_view_aov_direct(*view, want=("visibility",))["visibility"] < 1
+
+            def mse(x, mask=None):
+                d = (x.astype(np.float64) - ref) ** 2
+                return round(float(np.mean(d if mask is None else d[mask])), 1)
+
+            row = {"scene": name, "spp": spp, "shadowed_pixels": int(shadowed.sum()), "unfiltered": mse(r.run_view(*view))}
+            for label, vg in (("atrous", False), ("var", True)):
+                whole = r.run_view_denoised(*view, variance_guided=vg)[0]
+                split = r.run_view_denoised(*view, variance_guided=vg, split_direct=True)[0]
+                row.update({label: mse(whole), label + "_split": mse(split), label + "_shadowed": mse(whole, shadowed), label + "_split_shadowed": mse(split, shadowed)})
+            out["rows"].append(row)
+            print(json.dumps(row), file=sys.stderr, flush=True)
+        r.free()
+    print(json.dumps(out), flush=True)
+
+
 def scales_times(a):
     """--scales: the pyramid's two operations, one a-trous pass, and per filter the single call and the chains at 2 and 3 scales"""
     t = crt.Task(os.path.join(ROOT, "scenes", a.scene, "config.json"), base_dir=ROOT)
@@ -589,9 +628,12 @@ def main():
     ap.add_argument("--scales", action="store_true", help="time crt_pyramid_down_device / crt_pyramid_merge_device and the multi-scale chains; with --error: the error rows")
     ap.add_argument("--max-scales", type=int, default=3, help="--scales --error: the most scales of a row (1 .. 4)")
     ap.add_argument("--error-spps", default="8,32", help="--scales --error: the sample counts of the rows")
+    ap.add_argument("--split-direct", action="store_true", help="--error: direct and indirect light filtered separately beside the unsplit filters")
     a = ap.parse_args()
     if crt.device_count() < 1:
         raise SystemExit("denoise_probe: no HIP device")
+    if a.error and a.split_direct:
+        return split_direct_error_table(a)
     if a.scales:
         return scales_error_table(a) if a.error else scales_times(a)
     if a.regress:

@@ -4,6 +4,8 @@
 // types, the atomics and bit casts, the few definitions of crt_device.h / crt_path.h it uses, and the launch with its indices.
 // A program that defines CRT_HOST_WAVES before the include gets a wave of 64 host threads with the cross-lane operations (and needs
 // -pthread); without it a launch is a plain loop over blocks and threads, for kernels that have no cross-lane operation.
+// A program that defines CRT_HOST_PATH before the include also gets what kernel text takes from the path code (crt_aov_direct.h): the
+// remaining vector types and bit casts, F3's other operations, the triangle row's material word, the ray kinds and shadow_blocked.
 //
 // Every program builds with one line (tests/host_program.py; the threaded ones add -pthread):
 //   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow \
@@ -83,6 +85,37 @@ static bool slot_to_pixel(uint32_t slot, uint32_t rank, uint32_t world, uint32_t
 }
 } // namespace crtk
 
+#ifdef CRT_HOST_PATH
+#include <cfloat>
+struct alignas(8) float2 { float x, y; };
+static float2 make_float2(float x, float y) { return float2{x, y}; }
+struct alignas(16) uint4 { uint32_t x, y, z, w; };
+static int __float_as_int(float f) { int i; std::memcpy(&i, &f, 4); return i; }
+static float __int_as_float(int i) { float f; std::memcpy(&f, &i, 4); return f; }
+// crt_device.h: the triangle row's material word, the reference's epsilon
+#define TNM_MAT(w_) ((w_) & 0x3fffffffu)
+#define TNM_EMITTER(w_) (((w_) >> 30) & 1u)
+#define TNM_SPECULAR(w_) ((w_) >> 31)
+#define CRT_EPSILON 0.00001f
+namespace crtk {
+// crt_device.h: F3's other operations (there div3 is built from a reciprocal and corrected to the rounded quotients: the same values)
+static F3 add3(F3 a, F3 b) { return f3(a.x + b.x, a.y + b.y, a.z + b.z); }
+static F3 sub3(F3 a, F3 b) { return f3(a.x - b.x, a.y - b.y, a.z - b.z); }
+static F3 mul3(F3 a, F3 b) { return f3(a.x * b.x, a.y * b.y, a.z * b.z); }
+static F3 scale3(F3 a, float s) { return f3(a.x * s, a.y * s, a.z * s); }
+static F3 scalel3(float s, F3 a) { return f3(s * a.x, s * a.y, s * a.z); }
+static F3 div3(F3 a, float s) { return f3(a.x / s, a.y / s, a.z / s); }
+static float norm3(F3 a) { return sqrt_f(dot3(a, a)); }
+// crt_path.h: the ray kinds, shadow_blocked
+enum { RAY_NONE = 0, RAY_CLOSEST = 1, RAY_SHADOW = 2 };
+template <int MODE> static bool shadow_blocked(float tl, float T, int tri)
+{
+    if (MODE != 1) return tri >= 0 || tl - FLT_MAX > CRT_EPSILON;
+    return tl - T > CRT_EPSILON;
+}
+} // namespace crtk
+#endif
+
 // ---- the launch: its indices, and with CRT_HOST_WAVES the wave ----
 struct Idx { uint32_t x; };
 static thread_local Idx blockIdx, threadIdx, gridDim;
@@ -128,6 +161,7 @@ static int __builtin_amdgcn_readlane(int v, int lane_from)
     g_wave.barrier(v);
     return g_wave.vals[lane_from];
 }
+static int __builtin_amdgcn_readfirstlane(int v) { return __builtin_amdgcn_readlane(v, 0); } // (called with every lane active)
 static int __ffsll(long long v) { return __builtin_ffsll(v); }
 static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 
