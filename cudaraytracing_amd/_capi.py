@@ -148,6 +148,14 @@ class AovDirectBuffers(C.Structure):
     _fields_ = [("direct", C.c_void_p), ("unshadowed", C.c_void_p), ("direct_variance", C.c_void_p), ("visibility", C.c_void_p)]
 
 
+class AovAoParams(C.Structure):
+    _fields_ = [("ao_samples", C.c_uint32), ("max_distance", C.c_float)]
+
+
+class AovAoBuffers(C.Structure):
+    _fields_ = [("ao", C.c_void_p), ("openness", C.c_void_p), ("bent_normal", C.c_void_p)]
+
+
 class ModulateParams(C.Structure):
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("albedo_floor", C.c_float)]
 
@@ -350,6 +358,8 @@ AOV_SPECULAR_BUFFERS = {"guide_albedo": (3, np.float32), "last_normal": (3, np.f
 AOV_SHADING_BUFFERS = {"emission": (3, np.float32), "diffuse_albedo": (3, np.float32)}
 # the buffers of crt_aov_direct_buffers
 AOV_DIRECT_BUFFERS = {"direct": (3, np.float32), "unshadowed": (3, np.float32), "direct_variance": (3, np.float32), "visibility": (1, np.float32)}
+# the buffers of crt_aov_ao_buffers
+AOV_AO_BUFFERS = {"ao": (1, np.float32), "openness": (1, np.float32), "bent_normal": (3, np.float32)}
 
 
 class Task(C.Structure):
@@ -386,7 +396,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_denoise_regress_defaults", "crt_denoise_regress_scratch_bytes", "crt_denoise_regress", "crt_denoise_regress_device",
            "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device",
            "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device",
-           "crt_render_aov_direct", "crt_render_aov_direct_device"]
+           "crt_render_aov_direct", "crt_render_aov_direct_device",
+           "crt_aov_ao_defaults", "crt_render_aov_ao", "crt_render_aov_ao_device"]
 
 _lib = None
 
@@ -446,6 +457,10 @@ def lib():
     L.crt_render_aov_direct.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovDirectBuffers), C.POINTER(AovInfo)]
     L.crt_render_aov_direct_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovDirectBuffers), C.c_void_p,
                                                C.POINTER(AovInfo)]
+    L.crt_aov_ao_defaults.argtypes = [C.c_void_p, C.POINTER(AovAoParams)]
+    L.crt_render_aov_ao.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovAoParams), C.POINTER(AovAoBuffers), C.POINTER(AovInfo)]
+    L.crt_render_aov_ao_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(AovAoParams), C.POINTER(AovAoBuffers), C.c_void_p,
+                                           C.POINTER(AovInfo)]
     L.crt_modulate_defaults.argtypes = [C.POINTER(ModulateParams)]
     L.crt_demodulate.argtypes = [C.c_int, C.POINTER(ModulateParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.POINTER(ModulateInfo)]

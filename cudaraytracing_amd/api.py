@@ -177,6 +177,7 @@ class Render:
         self.aov_info = None
         self.aov_specular_info = None
         self.aov_direct_info = None
+        self.aov_ao_info = None
         self.aov_buffers = None
         self.direct_buffers = None  # run_view_denoised with split_direct: direct and direct_variance of the frame
         self.shading_buffers = None  # run_view_denoised / run_view_temporal with demodulate: emission and diffuse_albedo of the frame
@@ -503,8 +504,8 @@ class Render:
 
     def _aov_host(self, fn, view, width, height, groups, info_attr, sp=None):
         """The host form `fn` of an AOV pass for view = (eye_pos, inv_view_mat, fovY).  groups: per buffer struct of the C call, in its
-        order, (names wanted, buffer table, ctypes struct, pass NULL when no name is given); sp: the AovSpecularParams of the specular
-        form.  Returns {name: zeroed array the pass has filled}; self.<info_attr> gets the crt_aov_info dict."""
+        order, (names wanted, buffer table, ctypes struct, pass NULL when no name is given); sp: the settings struct of the forms that
+        take one (AovSpecularParams, AovAoParams).  Returns {name: zeroed array the pass has filled}; self.<info_attr> gets the crt_aov_info dict."""
         h_ = self._handle("run_view" + fn[len("crt_render"):])
         cam = self._cam(*view)
         prm = self._params(flags=self.extra_flags, width=width, height=height)
@@ -590,6 +591,33 @@ class Render:
         return self._aov_device("crt_render_aov_direct_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
                                 [(ptrs, capi.AOV_DIRECT_BUFFERS, capi.AovDirectBuffers, False)], "aov_direct_info", stream, want_info,
                                 kind="direct-light AOV")
+
+    def aov_ao_defaults(self):
+        """crt_aov_ao_defaults of this scene as a dict: ao_samples 4, max_distance a quarter of the diagonal of the scene's root box.
+        Both are tuned on nothing."""
+        p = capi.AovAoParams()
+        capi.check(capi.lib().crt_aov_ao_defaults(self._handle("aov_ao_defaults"), C.byref(p)), "crt_aov_ao_defaults")
+        return {"ao_samples": int(p.ao_samples), "max_distance": float(p.max_distance)}
+
+    def _aov_ao_params(self, ao_samples, max_distance):
+        d = self.aov_ao_defaults()
+        return capi.AovAoParams(d["ao_samples"] if ao_samples is None else int(ao_samples), d["max_distance"] if max_distance is None else float(max_distance))
+
+    def run_view_aov_ao(self, eye_pos, inv_view_mat, fovY, ao_samples=None, max_distance=None, want=tuple(capi.AOV_AO_BUFFERS), width=None, height=None):
+        """Ambient-occlusion AOVs (crt_render_aov_ao, contract: include/crt.h): per camera ray's hit, ao_samples rays of at most
+        max_distance over the hemisphere of the facing normal.  Returns {name: array} for the names in `want` (ao, openness: (H, W)
+        float32; bent_normal: (H, W, 3) float32).  None: aov_ao_defaults'.  p_rr and light_sample_n are not read.  self.aov_ao_info
+        gets rays (camera and occlusion rays), chunks (sub-batches), total_ms."""
+        return self._aov_host("crt_render_aov_ao", (eye_pos, inv_view_mat, fovY), width, height,
+                              [(want, capi.AOV_AO_BUFFERS, capi.AovAoBuffers, False)], "aov_ao_info", sp=self._aov_ao_params(ao_samples, max_distance))
+
+    def run_view_aov_ao_device(self, eye_pos, inv_view_mat, fovY, ptrs, ao_samples=None, max_distance=None, stream=None, rank=0, world=1, tiled=False,
+                               want_info=True, width=None, height=None):
+        """The same with outputs in device memory: ptrs = {name: raw device pointer}, layout as run_view_aov_device.  The call only
+        enqueues; with want_info it synchronizes the stream once, at the end, and sets self.aov_ao_info."""
+        return self._aov_device("crt_render_aov_ao_device", (eye_pos, inv_view_mat, fovY), (rank, world, tiled, width, height),
+                                [(ptrs, capi.AOV_AO_BUFFERS, capi.AovAoBuffers, False)], "aov_ao_info", stream, want_info,
+                                sp=self._aov_ao_params(ao_samples, max_distance), kind="ambient-occlusion AOV")
 
     def run_view_aov_specular(self, eye_pos, inv_view_mat, fovY, max_bounces=None, want=tuple(capi.AOV_SPECULAR_BUFFERS), width=None, height=None):
         """AOVs that follow perfect-mirror bounces from the first hit (crt_render_aov_specular, contract: include/crt.h): returns
@@ -1083,6 +1111,9 @@ _MULTI_REFUSALS = {
     "run_view_aov_shading_device": "the AOV pass is a single-device interface (crt_render_aov_shading_device)",
     "run_view_aov_direct": "the AOV pass is a single-device interface (crt_render_aov_direct)",
     "run_view_aov_direct_device": "the AOV pass is a single-device interface (crt_render_aov_direct_device)",
+    "run_view_aov_ao": "the AOV pass is a single-device interface (crt_render_aov_ao)",
+    "run_view_aov_ao_device": "the AOV pass is a single-device interface (crt_render_aov_ao_device)",
+    "aov_ao_defaults": "the AOV pass is a single-device interface (crt_aov_ao_defaults)",
     "run_view_aov_specular": "the AOV pass is a single-device interface (crt_render_aov_specular)",
     "run_view_aov_specular_device": "the AOV pass is a single-device interface (crt_render_aov_specular_device)",
     "run_view_denoised": "the denoiser is a single-device interface (crt_denoise): gather the frame first",

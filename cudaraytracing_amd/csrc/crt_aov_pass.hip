@@ -1,5 +1,5 @@
-// cudaraytracing_amd/csrc/crt_aov_pass.hip -- the host side of crt_aov.hip and crt_aov_direct.hip: the AOV passes (first hit, shading, mirror bounces, direct light) and their
-// entry points in the C ABI of include/crt.h (crt_render_aov*, crt_aov_specular_defaults).  Every pass is the camera rays of samples
+// cudaraytracing_amd/csrc/crt_aov_pass.hip -- the host side of crt_aov.hip, crt_aov_direct.hip and crt_aov_ao.hip: the AOV passes (first hit, shading, mirror bounces, direct light,
+// ambient occlusion) and their entry points in the C ABI of include/crt.h (crt_render_aov*, crt_aov_specular_defaults, crt_aov_ao_defaults).  Every pass is the camera rays of samples
 // 0 .. spp-1 of every pixel slot of the shard, in chunks of whole samples of at most kAovChunkRays rays (32 B of query pool + 16 B of
 // results per ray: 1.6 GB), each traced by trace_queries (crt_render.hip, through crt_render.h) and folded into the per-slot running sums
 // in sample order.  Uses the handle's query pool and trace buffers, as crt_intersect does; the accumulator of a progressive render
@@ -7,8 +7,10 @@
 #include "crt_render.h"
 
 #include "crt_aov_direct.h"
+#include "crt_aov_ao.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <initializer_list>
 #include <string>
@@ -24,21 +26,27 @@ bool any_buffer(const crt_aov_buffers* o) { return o && (o->albedo || o->normal 
 bool any_buffer(const crt_aov_shading_buffers* o) { return o && (o->emission || o->diffuse_albedo); }
 bool any_buffer(const crt_aov_specular_buffers* o) { return o && (o->guide_albedo || o->last_normal || o->path_depth || o->bounces || o->last_tri); }
 bool any_buffer(const crt_aov_direct_buffers* o) { return o && (o->direct || o->unshadowed || o->direct_variance || o->visibility); }
+bool any_buffer(const crt_aov_ao_buffers* o) { return o && (o->ao || o->openness || o->bent_normal); }
 
-// The argument check of all eight entry points (`who`: the entry's base name), before any device call.  missing: a pointer its form requires
+// The argument check of all ten entry points (`who`: the entry's base name), before any device call.  missing: a pointer its form requires
 // is null; unnamed: what to say when its structs name no output buffer (null: they name one); sp: the specular form's settings;
-// camera_rays_only: false for the direct-light pass, which takes next-event samples and checks light_sample_n as a render does.
+// camera_rays_only: false for the direct-light pass, which takes next-event samples and checks light_sample_n as a render does; ao: the
+// ambient-occlusion form's settings.
 int aov_check(const char* who, const crt_scene* sc, const crt_camera* cam, const crt_params* prm, bool missing, const char* unnamed,
-              const crt_aov_specular_params* sp = nullptr, bool camera_rays_only = true)
+              const crt_aov_specular_params* sp = nullptr, bool camera_rays_only = true, const crt_aov_ao_params* ao = nullptr)
 {
     const std::string w(who);
     if (!sc || !cam || !prm || missing) return fail(CRT_ERR_INVALID_ARG, w + ": null argument");
     if (unnamed) return fail(CRT_ERR_INVALID_ARG, w + ": " + unnamed);
     if (sp && (sp->max_bounces < 1 || sp->max_bounces > 8)) return fail(CRT_ERR_INVALID_ARG, w + ": max_bounces must be in [1, 8]");
+    if (ao && (ao->ao_samples < 1 || ao->ao_samples > 256)) return fail(CRT_ERR_INVALID_ARG, w + ": ao_samples must be in [1, 256]");
+    if (ao && !(ao->max_distance > 0.0f && ao->max_distance <= FLT_MAX)) // (a NaN fails the first comparison)
+        return fail(CRT_ERR_INVALID_ARG, w + ": max_distance must be finite and > 0");
     const int rc = params_check(who, prm, camera_rays_only);
     if (rc != CRT_OK) return rc;
     if ((uint64_t)make_shard(prm->width, prm->height, prm->world).local_tiles * 64u > 0x7fffffffull)
         return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^31 pixel slots in a shard");
+    if (ao && (uint64_t)prm->spp * ao->ao_samples > 0xffffffffull) return fail(CRT_ERR_UNSUPPORTED, w + ": more than 2^32 occlusion rays per pixel");
     return CRT_OK;
 }
 // crt_render_aov_shading: `first` may be null (a struct that is given must name a buffer, as crt_render_aov's), `shading` not
@@ -257,6 +265,74 @@ int direct_pass(crt_scene* sc, const crt_camera* cam, const crt_params* prm, con
     return rc;
 }
 
+// crt_render_aov_ao: occlusion rays over the hemisphere of the first hit (kernels: crt_aov_ao.hip).  After a chunk's camera rays are
+// traced, k_aov_ao_vertex copies what the later stages need out of their answers (as the direct-light pass: the next trace overwrites
+// them).  The chunk's (sample, q) entries are then walked in sub-batches of at most kAovChunkRays plane entries (CRT_AOV_AO_BATCH: a
+// test's smaller number): the set-up kernel writes every entry's direction and cosine and its ray into the query pool behind the camera
+// rays, at the entry's own index; all of them are traced, and the resolve folds entries and answers into the slots' running sums.
+// Every ray is traced, so the host knows each launch's size and reads nothing back: the pass only enqueues (a buffer that has to grow
+// is freed first, which waits for the device).  The sum of the occlusion rays of the call stays on the device unless info is asked for.
+int ao_pass(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_ao_params* ap, const crt_aov_ao_buffers* out, hipStream_t st,
+            crt_aov_info* info)
+{
+    AovAoParams D;
+    std::memset(&D, 0, sizeof(D));
+    const uint32_t n_q = ap->ao_samples;
+    size_t second = 0;        // where in the query pool the occlusion rays go: behind the camera rays of the largest chunk
+    uint64_t batch_pairs = 1; // (sample, q) entries of a sub-batch
+    uint32_t batches = 0;
+    const int rc = aov_pass(sc, cam, prm, st, info,
+        [&](uint64_t max_rays, AovParams& A) {
+            batch_pairs = std::max<uint64_t>(1, env_u32("CRT_AOV_AO_BATCH", kAovChunkRays) / A.nslots);
+            batch_pairs = std::min<uint64_t>(batch_pairs, std::max<uint64_t>(1, max_rays / A.nslots * n_q)); // (no more than a chunk has)
+            const uint64_t cap = batch_pairs * A.nslots;
+            // every buffer at its final size before the first launch: growing one later would drop what a stage has left in it
+            sc->p_ro.ensure(max_rays + cap); sc->p_rd.ensure(max_rays + cap); sc->p_res.ensure(max_rays + cap);
+            sc->aovd_plane.ensure(cap); sc->aovd_vert.ensure(2 * max_rays);
+            if (choose_pipeline(sc) == 4) (void)sc->L.answers(std::max(max_rays, cap));
+            sc->aov_acc.ensure((size_t)A.nslots * kAovAoAccRows);
+            sc->aovao_rays.ensure(1);
+            HIP_CHECK(hipMemsetAsync(sc->aovao_rays.p, 0, sizeof(unsigned long long), st));
+            second = max_rays;
+            D.seed = prm->seed; D.spp = prm->spp;
+            D.n_q = n_q; D.max_distance = ap->max_distance;
+            D.reference_mode = prm->traversal == CRT_TRAVERSAL_REFERENCE ? 1u : 0u;
+            D.tri_nm = sc->dev.tri_nm;
+            D.vert = sc->aovd_vert.p; D.vnf = sc->aovd_vert.p + max_rays; D.plane = sc->aovd_plane.p; D.acc = sc->aov_acc.p;
+            D.out_ro = sc->p_ro.p + second; D.out_rd = sc->p_rd.p + second; D.out_res = sc->p_res.p + second;
+            D.ray_total = sc->aovao_rays.p;
+            D.ao = out->ao; D.openness = out->openness; D.bent_normal = out->bent_normal;
+        },
+        [&](AovParams& A) -> uint64_t {
+            static_cast<SlotMap&>(D) = A;
+            D.sample_begin = A.sample_begin; D.n_samples = A.n_samples;
+            D.cam_ro = A.pool.ro; D.cam_rd = A.pool.rd; D.res = A.res; D.res_stride = A.res_stride;
+            const bool force_exact = (prm->flags & CRT_FLAG_FORCE_EXACT) != 0;
+            const uint64_t total = (uint64_t)A.n_samples * n_q;
+            launch_aov_ao_vertex(D, st); // (before the first occlusion trace: it overwrites the camera answers)
+            HIP_CHECK(hipGetLastError());
+            for (uint64_t e0 = 0; e0 < total; e0 += batch_pairs) {
+                const uint32_t cnt = (uint32_t)std::min<uint64_t>(batch_pairs, total - e0);
+                D.s_first = (uint32_t)(e0 / n_q); D.q_first = (uint32_t)(e0 % n_q); D.e_count = cnt;
+                D.first_batch = A.first_chunk && e0 == 0; D.last_batch = A.last_chunk && e0 + cnt == total;
+                launch_aov_ao_setup(D, st);
+                HIP_CHECK(hipGetLastError());
+                D.ans = trace_queries(sc, cnt * A.nslots, prm->traversal, force_exact, st, D.ans_stride, second);
+                launch_aov_ao_resolve(D, st);
+                HIP_CHECK(hipGetLastError());
+                batches++;
+            }
+            return 0; // (the occlusion rays with a vertex are counted on the device)
+        });
+    if (rc != CRT_OK || !info) return rc;
+    return hip_guard([&]() -> int {
+        unsigned long long n = 0;
+        HIP_CHECK(hipMemcpy(&n, sc->aovao_rays.p, sizeof(n), hipMemcpyDeviceToHost)); // (aov_pass has synchronized the stream for the info)
+        info->rays += n; info->chunks = batches;
+        return CRT_OK;
+    });
+}
+
 // The host-buffer form of an entry: a device buffer for every plane whose host pointer is given, the pass on them (pass(d): d[i] the
 // device pointer of plane i, null where the host's is), then a synchronization and the copies back.
 struct HostPlane {
@@ -372,6 +448,37 @@ int crt_render_aov_direct(crt_scene* sc, const crt_camera* cam, const crt_params
     return aov_host_form(sc, prm, {{h.direct, 3}, {h.unshadowed, 3}, {h.direct_variance, 3}, {h.visibility, 1}}, [&](float* const* d) {
         const crt_aov_direct_buffers dev{d[0], d[1], d[2], d[3]};
         return direct_pass(sc, cam, prm, &dev, nullptr, info);
+    });
+}
+
+int crt_aov_ao_defaults(const crt_scene* sc, crt_aov_ao_params* p)
+{
+    if (!sc || !p) return fail(CRT_ERR_INVALID_ARG, "crt_aov_ao_defaults: null argument");
+    double d2 = 0.0;
+    for (int a = 0; a < 3; a++) d2 += ((double)sc->root_bb[a] - (double)sc->root_aa[a]) * ((double)sc->root_bb[a] - (double)sc->root_aa[a]);
+    const float quarter = (float)(0.25 * std::sqrt(d2));
+    p->ao_samples = 4;
+    p->max_distance = (quarter > 0.0f && quarter <= FLT_MAX) ? quarter : 1.0f; // (a root box that is a point, or not finite)
+    return CRT_OK;
+}
+
+int crt_render_aov_ao_device(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_ao_params* ao, const crt_aov_ao_buffers* dev_out,
+                             void* stream, crt_aov_info* info)
+{
+    const int rc = aov_check("crt_render_aov_ao", sc, cam, prm, !ao || !dev_out, any_buffer(dev_out) ? nullptr : "no output buffer", nullptr, true, ao);
+    if (rc != CRT_OK) return rc;
+    return ao_pass(sc, cam, prm, ao, dev_out, (hipStream_t)stream, info);
+}
+
+int crt_render_aov_ao(crt_scene* sc, const crt_camera* cam, const crt_params* prm, const crt_aov_ao_params* ao, const crt_aov_ao_buffers* host_out,
+                      crt_aov_info* info)
+{
+    const int rc = aov_check("crt_render_aov_ao", sc, cam, prm, !ao || !host_out, any_buffer(host_out) ? nullptr : "no output buffer", nullptr, true, ao);
+    if (rc != CRT_OK) return rc;
+    const crt_aov_ao_buffers& h = *host_out;
+    return aov_host_form(sc, prm, {{h.ao, 1}, {h.openness, 1}, {h.bent_normal, 3}}, [&](float* const* d) {
+        const crt_aov_ao_buffers dev{d[0], d[1], d[2]};
+        return ao_pass(sc, cam, prm, ao, &dev, nullptr, info);
     });
 }
 

@@ -12,7 +12,7 @@
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]
-//           [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX]
+//           [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX] [--aov-ao PREFIX[,SAMPLES[,DISTANCE]]]
 //           [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]] [--gathered PREFIX[,NAME,...]]
 //           [--pixel-filter KIND[,RADIUS] --pixel-filter-out PATH]
 // --pixel-filter KIND[,RADIUS] --pixel-filter-out PATH also writes the frame under a pixel reconstruction filter (one device;
@@ -30,6 +30,9 @@
 // --height.  -o stays the plain frame at full size.  It runs last: --aov and --aov-shading write the buffers of the plain frame.
 // --aov-direct PREFIX writes the direct-light AOVs of the frame (crt_render_aov_direct, one device): PREFIX_direct.pfm, PREFIX_unshadowed.pfm,
 // PREFIX_direct_variance.pfm (3 channels) and PREFIX_visibility.pfm (1 channel).
+// --aov-ao PREFIX[,SAMPLES[,DISTANCE]] writes the ambient-occlusion AOVs of the frame (crt_render_aov_ao, one device): PREFIX_ao.pfm,
+// PREFIX_openness.pfm (1 channel) and PREFIX_bent.pfm (3 channels); SAMPLES 1 .. 256 rays per hit of at most DISTANCE > 0, either
+// left out: crt_aov_ao_defaults'.
 // --aov-shading PREFIX writes the shading AOVs of the frame (crt_render_aov_shading, one device, the trace of --aov): PREFIX.emission.pfm
 // and PREFIX.diffuse_albedo.pfm (3 channels).  --demodulate makes --denoise and --temporal work on irradiance: the frame (and its
 // variance) goes through crt_demodulate with those two buffers before the filter or the blend and the result through crt_modulate, so
@@ -97,6 +100,7 @@ int main(int argc, char** argv)
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
                              "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX]\n"
+                             "       [--aov-ao PREFIX[,SAMPLES[,DISTANCE]]]\n"
                              "       [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]\n"
                              "       [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K]  (--denoise-sigma: its colour value is ignored with --denoise-nlm)\n"
                              "       [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE]\n"
@@ -114,7 +118,7 @@ int main(int argc, char** argv)
     try {
         crt::TaskObjs all_objs;
         crt_task task = crt::load_task(argv[1], &all_objs);
-        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, aov_direct, denoise, variance, adaptive_samples, pixel_filter_out;
+        std::string out = "out.png", base_dir = ".", aov, aov_specular, aov_shading, aov_direct, aov_ao, denoise, variance, adaptive_samples, pixel_filter_out;
         crt_pixel_filter pixel_filter; // --pixel-filter
         bool pixel_filter_on = false;
         bool demodulate = false;
@@ -136,6 +140,8 @@ int main(int argc, char** argv)
         crt_filter_select_defaults(&sel);
         std::string denoise_choice;
         uint32_t specular_bounces = 0; // 0: crt_aov_specular_defaults'
+        uint32_t ao_samples = 0;       // --aov-ao; 0: crt_aov_ao_defaults', as is a distance of 0
+        float ao_distance = 0.0f;
         int temporal = 0;
         bool temporal_option = false, temporal_denoise = false, temporal_clamp = false, temporal_moments = false;
         crt_variance_estimate_params tvar; // --temporal-variance moments: the estimate's defaults with of_mean 1 and MIN_HISTORY
@@ -233,6 +239,24 @@ int main(int argc, char** argv)
                 if (aov_specular.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-specular needs a PREFIX");
             }
             else if (a == "--aov-direct") { need(i, 1); aov_direct = argv[++i]; if (aov_direct.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-direct needs a PREFIX"); }
+            else if (a == "--aov-ao") {
+                need(i, 1);
+                aov_ao = argv[++i];
+                const size_t c1 = aov_ao.find(',');
+                if (c1 != std::string::npos) {
+                    const std::string rest = aov_ao.substr(c1 + 1);
+                    aov_ao.resize(c1);
+                    const size_t c2 = rest.find(',');
+                    const int n = std::atoi(rest.substr(0, c2).c_str());
+                    if (n < 1 || n > 256) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-ao PREFIX[,SAMPLES[,DISTANCE]] needs SAMPLES in 1 .. 256");
+                    ao_samples = (uint32_t)n;
+                    if (c2 != std::string::npos) {
+                        ao_distance = (float)std::atof(rest.c_str() + c2 + 1);
+                        if (!(ao_distance > 0.0f && ao_distance <= 3.402823466e38f)) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-ao PREFIX[,SAMPLES[,DISTANCE]] needs a finite DISTANCE > 0");
+                    }
+                }
+                if (aov_ao.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-ao needs a PREFIX");
+            }
             else if (a == "--aov-shading") { need(i, 1); aov_shading = argv[++i]; if (aov_shading.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--aov-shading needs a PREFIX"); }
             else if (a == "--demodulate") demodulate = true;
             else if (a == "--upsample") {
@@ -455,7 +479,7 @@ int main(int argc, char** argv)
         // the refusals and refuse_on_many takes the next `count` of them where theirs stood among the other checks.
         const struct { bool present; const char* what; } one_device[] = {
             {!aov.empty(), "--aov renders on one device"}, {!aov_specular.empty(), "--aov-specular renders on one device"},
-            {!aov_shading.empty(), "--aov-shading renders on one device"}, {!aov_direct.empty(), "--aov-direct renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
+            {!aov_shading.empty(), "--aov-shading renders on one device"}, {!aov_direct.empty(), "--aov-direct renders on one device"}, {!aov_ao.empty(), "--aov-ao renders on one device"}, {!denoise.empty(), "--denoise filters on one device"},
             {!variance.empty(), "--variance reads one device's buffer"}, {denoise_var, "--denoise-variance filters on one device"},
             {adaptive, "--adaptive renders on one device"}, {temporal != 0, "--temporal accumulates on one device"}, {upsample != 0, "--upsample runs on one device"},
             {denoise_nlm, "--denoise-nlm filters on one device"}, {denoise_regress, "--denoise-regress filters on one device"}};
@@ -464,7 +488,7 @@ int main(int argc, char** argv)
             for (; count-- > 0; row++)
                 if (multi && one_device[row].present) throw crt::Error(CRT_ERR_INVALID_ARG, std::string(one_device[row].what) + " (not with --gpus / --devices)");
         };
-        refuse_on_many(4);
+        refuse_on_many(5);
         if (demodulate && denoise.empty() && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--demodulate needs --denoise PATH or --temporal N");
         if (denoise_specular && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-specular needs --denoise PATH");
         refuse_on_many(6);
@@ -637,6 +661,13 @@ int main(int argc, char** argv)
             write_files("direct-light AOV files", {{aov_direct + "_direct.pfm", 3, render.get_direct_buffer()}, {aov_direct + "_unshadowed.pfm", 3, render.get_unshadowed_buffer()},
                                                    {aov_direct + "_direct_variance.pfm", 3, render.get_direct_variance_buffer()},
                                                    {aov_direct + "_visibility.pfm", 1, render.get_visibility_buffer()}});
+        }
+        if (!aov_ao.empty()) {
+            render.run_view_aov_ao(task.eye_pos, inv_view, fov_y, ao_samples, ao_distance);
+            const crt_aov_info& ai = render.last_aov_ao_info();
+            std::printf("aov-ao: %llu rays in %u sub-batches, device %.3f ms\n", (unsigned long long)ai.rays, ai.chunks, ai.total_ms);
+            write_files("ambient-occlusion AOV files", {{aov_ao + "_ao.pfm", 1, render.get_ao_buffer()}, {aov_ao + "_openness.pfm", 1, render.get_openness_buffer()},
+                                                        {aov_ao + "_bent.pfm", 3, render.get_bent_normal_buffer()}});
         }
         if (!aov_specular.empty() || denoise_specular) { // (after --aov's files: as the guide it replaces the first-hit albedo)
             render.run_aov_specular(task.eye_pos, inv_view, fov_y, specular_bounces, denoise_specular);

@@ -205,7 +205,7 @@ CRT_HD float det_powf(float x, float y)
 
 // ---- Philox4x32-10 (Salmon et al., SC'11) with explicit draw addressing ----
 // key = {pixel_index, seed_lo}; counter = {sample_k, depth | purpose << 16, idx, seed_hi}
-enum { RNG_JITTER = 0, RNG_BOUNCE = 1, RNG_NEE = 2, RNG_PROBE = 3 };
+enum { RNG_JITTER = 0, RNG_BOUNCE = 1, RNG_NEE = 2, RNG_PROBE = 3, RNG_AO = 4 }; // (RNG_AO: the occlusion rays of crt_render_aov_ao; no path draws it)
 struct U4 { uint32_t x, y, z, w; };
 CRT_HD U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1)
 {

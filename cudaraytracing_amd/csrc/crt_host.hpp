@@ -250,6 +250,13 @@ public:
     const float* get_direct_variance_buffer() const { return direct_variance_buffer_.data(); } // W x H x 3
     const float* get_visibility_buffer() const { return visibility_buffer_.data(); }           // W x H
     const crt_aov_info& last_aov_direct_info() const { return aov_direct_info_; }
+    // the ambient-occlusion AOVs of the frame run_view draws with the same camera and settings (crt_render_aov_ao): ao_samples rays of
+    // at most max_distance over the hemisphere of every first hit; 0 takes crt_aov_ao_defaults' value for either; one device only
+    void run_view_aov_ao(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t ao_samples = 0, float max_distance = 0.0f);
+    const float* get_ao_buffer() const { return ao_buffer_.data(); }                   // W x H, row 0 = image top
+    const float* get_openness_buffer() const { return openness_buffer_.data(); }       // W x H
+    const float* get_bent_normal_buffer() const { return bent_normal_buffer_.data(); } // W x H x 3
+    const crt_aov_info& last_aov_ao_info() const { return aov_ao_info_; }
     // on: the filters and the temporal pass work on irradiance (crt_demodulate / crt_modulate with albedo_floor and the shading AOVs of
     // the last run_aov, which set_demodulate therefore switches on).  run_denoise / run_denoise_var demodulate the frame (and its
     // variance), filter, and modulate the result.  run_temporal / run_temporal_moments demodulate each frame before the blend, so the
@@ -441,6 +448,8 @@ private:
     crt_aov_info aov_specular_info_{};
     std::vector<float> direct_buffer_, unshadowed_buffer_, direct_variance_buffer_, visibility_buffer_; // run_view_aov_direct
     crt_aov_info aov_direct_info_{};
+    std::vector<float> ao_buffer_, openness_buffer_, bent_normal_buffer_; // run_view_aov_ao
+    crt_aov_info aov_ao_info_{};
     std::vector<unsigned char> upsampled_buffer_;    // run_view_upsampled
     std::vector<float> upsampled_mean_buffer_;
     crt_upsample_info upsample_info_{};

@@ -259,6 +259,22 @@ void Render::run_view_aov_direct(const float eye_pos[3], const float inv_view_ma
     check(crt_render_aov_direct(device_scene_, &cam, &p, &out, &aov_direct_info_), "Render::run_view_aov_direct");
 }
 
+void Render::run_view_aov_ao(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t ao_samples, float max_distance)
+{
+    one_device("Render::run_view_aov_ao", "the AOV pass");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, 0, cam, p);
+    crt_aov_ao_params ao;
+    check(crt_aov_ao_defaults(device_scene_, &ao), "Render::run_view_aov_ao");
+    if (ao_samples != 0) ao.ao_samples = ao_samples;
+    if (max_distance != 0.0f) ao.max_distance = max_distance;
+    const size_t n = scene_->get_pixels();
+    ao_buffer_.assign(n, 0.0f); openness_buffer_.assign(n, 0.0f); bent_normal_buffer_.assign(3 * n, 0.0f);
+    const crt_aov_ao_buffers out{ao_buffer_.data(), openness_buffer_.data(), bent_normal_buffer_.data()};
+    check(crt_render_aov_ao(device_scene_, &cam, &p, &ao, &out, &aov_ao_info_), "Render::run_view_aov_ao");
+}
+
 crt_modulate_params Render::modulate_params(const char* who) const
 {
     if (emission_buffer_.size() != (size_t)3 * scene_->get_pixels() || diffuse_albedo_buffer_.size() != emission_buffer_.size())

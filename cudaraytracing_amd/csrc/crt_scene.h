@@ -77,6 +77,11 @@ struct crt_scene {
     // sub-batch (c.xyz, flags per (sample, q, slot) entry); the plane entries of its traced rays are aovs_item, their counter aovs_count,
     // its running sums aov_acc (kAovDirectAccRows per slot, crt_aov_direct.h)
     crtk::DevBuf<float4> aovd_vert, aovd_plane;
+    // crt_render_aov_ao uses the same two (per camera ray pos and facing normal: aovd_vert at twice the rays; the entry plane: aovd_plane),
+    // aov_acc (kAovAoAccRows per slot, crt_aov_ao.h) and the sum of a call's occlusion rays, read only when crt_aov_info is asked for.
+    // root_aa / root_bb: the box of the scene description's root node (crt_aov_ao_defaults)
+    crtk::DevBuf<unsigned long long> aovao_rays;
+    float root_aa[3] = {0.0f, 0.0f, 0.0f}, root_bb[3] = {0.0f, 0.0f, 0.0f};
     crtk::DevBuf<unsigned long long> counters;     // [CNT_SHARDS][CNT_STRIDE]
     crtk::DevBuf<unsigned int> item_next;           // [ITEM_SHARDS][ITEM_STRIDE]
     crtk::DevBuf<uint32_t> item_list;               // k_order_items: the order of the work items of a launch (small launches only)

@@ -127,6 +127,8 @@ int crt_scene_create(const crt_scene_desc* d, int device, crt_scene** out)
         sc->dev.n_lights = (int32_t)d->n_lights;
         sc->n_tris = d->n_tris;
         sc->n_mats = d->n_materials;
+        std::memcpy(sc->root_aa, d->nodes[d->root].aa, sizeof(sc->root_aa));
+        std::memcpy(sc->root_bb, d->nodes[d->root].bb, sizeof(sc->root_bb));
         create_frame_resources(sc);
         *out = sc;
         return CRT_OK;

@@ -600,6 +600,52 @@ int crt_render_aov_direct(crt_scene* scene, const crt_camera* cam, const crt_par
 int crt_render_aov_direct_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_direct_buffers* dev_out,
                                  void* hip_stream, crt_aov_info* info);
 
+/* Ambient-occlusion AOVs: the geometry around the first hit.  Per camera ray's hit the pass sends ao_samples rays of at most max_distance
+ * over the hemisphere of the hit's facing normal and returns the cosine-weighted open fraction, the plain open fraction and the mean
+ * open direction.  The draws have a purpose of their own (4, "ambient occlusion", beside jitter 0, bounce 1, next-event 2, probe 3): no
+ * path consumes them, and no path's draws move.  fp32, one IEEE operation per symbol, no FMA, no reciprocal multiply.  Per pixel, for the
+ * samples k = 0 .. S-1 (S = params->spp) in order:
+ *   camera ray and first hit: crt_render_aov's (origin o = eye, unit direction d, distance t, triangle tri).  A miss contributes nothing
+ *     to any sum.  Every hit is a vertex, a hit on an emitter too.
+ *   vertex: pos = o + t * d (one multiply, then one add); n = crt_triangle.normal of tri as stored; nf = dot(d, n) > 0 ? -n : n (a NaN
+ *     dot keeps n).
+ *   for q = 0 .. ao_samples - 1: the draw r = (seed, pixel, k, 0, ambient occlusion, q); dir = bounce_dir(nf, r), the function the
+ *     path's bounce uses: normalized(sample_hemisphere(nf, u(r.y), u(r.z))), a uniform hemisphere (Render.cuh:214, Ray.cuh:13);
+ *     w = max(dot(dir, nf), 0) (a NaN: 0).  The ray leaves pos along dir -- the query is handed dir itself, as the path's bounce ray is;
+ *     the reference's Ray would get sample_hemisphere's vector and normalise it once -- with the limit tl = max_distance, and is BLOCKED
+ *     by the reference's blocked() (Render.cuh:19-27) evaluated as the render kernel of params->traversal evaluates it: tl - t_hit > 1e-5
+ *     with t_hit = FLT_MAX when nothing was hit (REFERENCE: the closest hit; EXACT and FAST: any hit that satisfies it) -- what
+ *     crt_render_aov_direct does with its shadow rays.  Every ray is traced: there is no "untraced" class.
+ *   sums, from +0 in (k, q) order: A = A + w;  V = V + w over the unblocked rays;  the integer counts rays and open (unblocked);
+ *     b = b + dir per component over the unblocked rays.
+ * Outputs (any may be NULL, not all three):
+ *   ao           float     V / A, and 1.0f when A == 0 (no hit, or every cosine zero)
+ *   openness     float     (float)open / (float)rays, and 1.0f when rays == 0
+ *   bent_normal  3 floats  normalized(b) -- b / sqrt(dot(b, b)) when dot(b, b) > 0, else b as it is --, and (+0, +0, +0) when open == 0
+ * A mean distance of the open rays is deliberately not provided: an any-hit query knows no distance of a ray that is open.
+ * ao_samples is 1 .. 256.  max_distance must be finite and > 0: with +inf, inf - FLT_MAX would block every ray that escapes, so +inf and
+ * NaN are CRT_ERR_INVALID_ARG like 0 and negative values.  crt_aov_ao_defaults gives ao_samples 4 and max_distance = a quarter of the
+ * diagonal of the box of the scene's root node (1 when that is not a positive finite number); BOTH DEFAULTS ARE TUNED ON NOTHING --
+ * they are a starting point that no measurement stands behind.
+ * p_rr and light_sample_n are not read.  The refusals, the layout (row-major, or the tiled shard with CRT_FLAG_TILED_OUTPUT), the ignored
+ * flags, the chunks of camera rays and the frame in flight on the handle (left alone) are crt_render_aov's; spp x ao_samples above
+ * 2^32 - 1 is CRT_ERR_UNSUPPORTED.  A padding slot of a tiled shard gets what a pixel that only misses gets: ao 1.0f, openness 1.0f,
+ * bent_normal +0.  Inside a chunk the (sample, q) entries are walked in sub-batches of at most 2^25 entries x pixel slots (16 B of entry
+ * plane and 56 B of query buffers and answers each; a sub-batch may begin and end inside a sample).
+ * info->rays = camera rays (as crt_render_aov's) + occlusion rays (hits x ao_samples); info->chunks = sub-batches. */
+typedef struct { uint32_t ao_samples; float max_distance; } crt_aov_ao_params;
+typedef struct { float* ao; float* openness; float* bent_normal; } crt_aov_ao_buffers;   /* 1, 1, 3 floats per pixel */
+int crt_aov_ao_defaults(const crt_scene* scene, crt_aov_ao_params* out);
+/* host buffers (W*H or slots elements of 1 or 3 values each); info optional */
+int crt_render_aov_ao(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_ao_params* ao, const crt_aov_ao_buffers* host_out,
+                      crt_aov_info* info);
+/* device buffers on the scene's device, work enqueued on hip_stream (NULL = default stream).  Every ray is traced, so the host knows the
+ * size of each launch in advance: the call reads nothing back and enqueues its whole work without synchronizing the stream, unless
+ * info != NULL (one synchronization at the end, then an 8-byte copy of the ray count).  Like every pass on a handle it may have to grow
+ * the handle's buffers first, and freeing a device buffer waits for the device: the first call at a size is not asynchronous. */
+int crt_render_aov_ao_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_aov_ao_params* ao, const crt_aov_ao_buffers* dev_out,
+                             void* hip_stream, crt_aov_info* info);
+
 /* AOV-guided edge-avoiding denoiser: an a-trous ("with holes") wavelet filter with edge-stopping weights on colour, normal, albedo and
  * depth (Dammertz et al. 2010), run as `iterations` passes over a frame's pre-tone-map mean radiance (out_mean of crt_render), guided by
  * the buffers crt_render_aov returns.  An image operation: no scene handle.  Row-major images of width x height; color, albedo, normal

@@ -26,6 +26,13 @@ traced shadow rays, samples not traced), its sub-batches = host synchronizations
 statistics.
 
   python tools/aov_probe.py --direct [--spp 64] [--reps 20]
+
+--ao times the ambient-occlusion pass (crt_render_aov_ao_device, its three buffers, crt_aov_ao_defaults' settings) beside
+crt_render_aov_device and crt_render_aov_direct_device in one process, the three taking turns: the HIP-event time of each call (its
+info), median and best of --reps, at --spp (default 64), and each call's rays -- so also the time per occlusion ray beside the direct
+pass's time per shadow ray, both with the time of crt_render_aov, which traces the same camera rays, taken off.
+
+  python tools/aov_probe.py --ao [--spp 64] [--reps 20]
 """
 import argparse
 import json
@@ -179,9 +186,51 @@ def direct(a):
     print(json.dumps(out), flush=True)
 
 
+def ao(a):
+    """--ao: see the module's text."""
+    w, h = a.width, a.height
+    first, second, third = image_buffers(a, capi.AOV_BUFFERS), image_buffers(a, capi.AOV_DIRECT_BUFFERS), image_buffers(a, capi.AOV_AO_BUFFERS)
+    out = {"width": w, "height": h, "reps": a.reps, "runs": []}
+    spps = [int(s) for s in a.spp.split(",")] if a.spp is not None else [64]
+    for name in a.scenes.split(","):
+        t = crt.Task(os.path.join(ROOT, "scenes", name, "config.json"), base_dir=ROOT)
+        r = crt.Render(crt.Scene.from_task(t, w, h), 1, t.P_RR, t.light_sample_n)
+        iv = crt.get_inverse_view_matrix(t.eye_pos, t.lookat, t.up)
+        fov = crt.fov_to_radians(t.fov_y)
+        calls = (("aov", lambda: r.run_view_aov_device(t.eye_pos, iv, fov, first.ptrs)),
+                 ("direct", lambda: r.run_view_aov_direct_device(t.eye_pos, iv, fov, second.ptrs)),
+                 ("ao", lambda: r.run_view_aov_ao_device(t.eye_pos, iv, fov, third.ptrs)))
+        for spp in spps:
+            r.set_spp(spp)
+            ms = {k: [] for k, _ in calls}
+            info = {}
+            for i in range(a.reps + 2):  # (the first two rounds warm up: allocations, code objects)
+                for key, fn in calls:
+                    info[key] = dict(fn())
+                    if i >= 2:
+                        ms[key].append(info[key]["total_ms"])
+            med = {k: statistics.median(v) for k, v in ms.items()}
+            camera_rays = info["aov"]["rays"]
+            shadow_rays, ao_rays = info["direct"]["rays"] - camera_rays, info["ao"]["rays"] - camera_rays
+            ns_shadow = (med["direct"] - med["aov"]) * 1e6 / max(1, shadow_rays)
+            ns_ao = (med["ao"] - med["aov"]) * 1e6 / max(1, ao_rays)
+            run = {"scene": name, "spp": spp, **r.aov_ao_defaults(), "camera_rays": camera_rays, "shadow_rays": shadow_rays, "ao_rays": ao_rays,
+                   "ao_sub_batches": info["ao"]["chunks"], "direct_sub_batches": info["direct"]["chunks"],
+                   "aov_ms": round(med["aov"], 4), "aov_ms_best": round(min(ms["aov"]), 4),
+                   "direct_ms": round(med["direct"], 4), "direct_ms_best": round(min(ms["direct"]), 4),
+                   "ao_ms": round(med["ao"], 4), "ao_ms_best": round(min(ms["ao"]), 4),
+                   "ns_per_shadow_ray": round(ns_shadow, 4), "ns_per_ao_ray": round(ns_ao, 4), "ao_over_direct_per_ray": round(ns_ao / ns_shadow, 3) if ns_shadow > 0 else None}
+            out["runs"].append(run)
+            print(json.dumps(run), file=sys.stderr, flush=True)
+        r.free()
+    for b in (first, second, third):
+        b.free()
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--spp", default=None, help="comma-separated; default 16,64,512, with --specular / --shading / --direct 64")
+    ap.add_argument("--spp", default=None, help="comma-separated; default 16,64,512, with --specular / --shading / --direct / --ao 64")
     ap.add_argument("--scenes", default="cornell-box,veach-mis")
     ap.add_argument("--width", type=int, default=800)
     ap.add_argument("--height", type=int, default=600)
@@ -190,8 +239,11 @@ def main():
     ap.add_argument("--bounces", default="1,2", help="--specular: the max_bounces values")
     ap.add_argument("--shading", action="store_true", help="time crt_render_aov_shading_device beside crt_render_aov_device")
     ap.add_argument("--direct", action="store_true", help="time crt_render_aov_direct_device beside crt_render_aov_device and a frame at p_rr = 0")
+    ap.add_argument("--ao", action="store_true", help="time crt_render_aov_ao_device beside crt_render_aov_device and crt_render_aov_direct_device")
     a = ap.parse_args()
     w, h = a.width, a.height
+    if a.ao:
+        return ao(a)
     if a.specular:
         return specular(a)
     if a.shading:

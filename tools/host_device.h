@@ -4,8 +4,9 @@
 // types, the atomics and bit casts, the few definitions of crt_device.h / crt_path.h it uses, and the launch with its indices.
 // A program that defines CRT_HOST_WAVES before the include gets a wave of 64 host threads with the cross-lane operations (and needs
 // -pthread); without it a launch is a plain loop over blocks and threads, for kernels that have no cross-lane operation.
-// A program that defines CRT_HOST_PATH before the include also gets what kernel text takes from the path code (crt_aov_direct.h): the
-// remaining vector types and bit casts, F3's other operations, the triangle row's material word, the ray kinds and shadow_blocked.
+// A program that defines CRT_HOST_PATH before the include also gets what kernel text takes from the path code (crt_aov_direct.h, crt_aov_ao.h): the
+// remaining vector types and bit casts, F3's other operations, the triangle row's material word, the ray kinds, shadow_blocked and
+// bounce_dir with the samplers under it.
 //
 // Every program builds with one line (tests/host_program.py; the threaded ones add -pthread):
 //   g++ -std=c++17 -ffp-contract=off -I cudaraytracing_amd/csrc -O1 -g -fsanitize=address,undefined,float-cast-overflow \
@@ -113,6 +114,31 @@ template <int MODE> static bool shadow_blocked(float tl, float T, int tri)
     if (MODE != 1) return tri >= 0 || tl - FLT_MAX > CRT_EPSILON;
     return tl - T > CRT_EPSILON;
 }
+// crt_device.h: cross3; crt_trace.h: to_world, sample_hemisphere; crt_path.h: bounce_dir (crt_aov_ao.h's directions) -- the same text
+static F3 cross3(F3 a, F3 b) { return f3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+static F3 to_world(F3 a, F3 N)
+{
+    F3 C;
+    if (absf(N.x) > absf(N.y)) {
+        float invLen = 1.0f / sqrt_f(N.x * N.x + N.z * N.z);
+        C = f3(N.z * invLen, 0.0f, -N.x * invLen);
+    } else {
+        float invLen = 1.0f / sqrt_f(N.y * N.y + N.z * N.z);
+        C = f3(0.0f, N.z * invLen, -N.y * invLen);
+    }
+    F3 B = cross3(C, N);
+    return add3(add3(scalel3(a.x, B), scalel3(a.y, C)), scalel3(a.z, N));
+}
+static F3 sample_hemisphere(F3 N, float x_1, float x_2)
+{
+    float z = absf(1.0f - 2.0f * x_1);
+    float r = sqrt_f(1.0f - z * z);
+    float phi = (float)(2 * 3.14159265358979323846 * (double)x_2);
+    float sn, cs;
+    det_sincosf(phi, &sn, &cs);
+    return to_world(f3(r * cs, r * sn, z), N);
+}
+static F3 bounce_dir(const F3 n, const U4 rb) { return unit3(sample_hemisphere(n, rng_uniform(rb.y), rng_uniform(rb.z))); }
 } // namespace crtk
 #endif
 
