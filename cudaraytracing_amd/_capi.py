@@ -348,6 +348,35 @@ class PlanInfo(InfoStruct):
     _fields_ = [("samples", C.c_uint32), ("spp", C.c_uint32)]
 
 
+class FrameErrorInfo(C.Structure):
+    _fields_ = [("samples_done", C.c_uint32), ("spp", C.c_uint32), ("pixels", C.c_uint64), ("nan_pixels", C.c_uint64), ("above", C.c_uint64),
+                ("hist", C.c_uint64 * 16), ("sum_variance", C.c_double), ("sum_mean", C.c_double)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "hist"}
+        d["hist"] = [int(x) for x in self.hist]
+        return d
+
+
+class UntilParams(C.Structure):
+    _fields_ = [("min_samples", C.c_uint32), ("step_samples", C.c_uint32), ("threshold", C.c_float), ("mean_floor", C.c_float), ("max_above", C.c_uint64)]
+
+
+UNTIL_CHECKS_REPORTED = 64
+
+
+class UntilInfo(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("checks", C.c_uint32), ("samples_done", C.c_uint32), ("reserved_", C.c_uint32),
+                ("above", C.c_uint64 * UNTIL_CHECKS_REPORTED), ("paths", C.c_uint64), ("kernel_ms", C.c_float), ("total_ms", C.c_float),
+                ("last", FrameErrorInfo)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in ("passes", "checks", "samples_done", "paths", "kernel_ms", "total_ms")}
+        d["above"] = [int(x) for x in self.above[:min(self.checks, UNTIL_CHECKS_REPORTED)]]
+        d["last"] = self.last.as_dict()
+        return d
+
+
 # the buffers of crt_aov_buffers: name -> (values per pixel, numpy type)
 AOV_BUFFERS = {"albedo": (3, np.float32), "normal": (3, np.float32), "depth": (1, np.float32), "coverage": (1, np.float32),
                "tri": (1, np.int32), "material": (1, np.int32)}
@@ -397,7 +426,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_pyramid_size", "crt_pyramid_down", "crt_pyramid_down_device", "crt_pyramid_merge", "crt_pyramid_merge_device",
            "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device",
            "crt_render_aov_direct", "crt_render_aov_direct_device",
-           "crt_aov_ao_defaults", "crt_render_aov_ao", "crt_render_aov_ao_device"]
+           "crt_aov_ao_defaults", "crt_render_aov_ao", "crt_render_aov_ao_device",
+           "crt_frame_error_defaults", "crt_frame_error", "crt_frame_error_device", "crt_until_defaults", "crt_render_until", "crt_render_until_device"]
 
 _lib = None
 
@@ -586,6 +616,15 @@ def lib():
         L.crt_filtered_frame_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
     if hasattr(L, "crt_item_order"):  # (a CRT_LIB_PATH library of this ABI version from before the entry point was appended has none)
         L.crt_item_order.argtypes = [C.c_void_p, C.POINTER(ItemOrderInfo)]
+    if hasattr(L, "crt_frame_error"):  # (likewise)
+        L.crt_frame_error_defaults.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.crt_frame_error.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(FrameErrorInfo)]
+        L.crt_frame_error_device.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
+        L.crt_until_defaults.argtypes = [C.POINTER(UntilParams)]
+        L.crt_render_until.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(UntilParams), C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(UntilInfo)]
+        L.crt_render_until_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(UntilParams), C.c_uint32, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(UntilInfo)]
     _lib = L
     return L
 

@@ -185,6 +185,7 @@ class Render:
         self.variance_buffer = None
         self.samples_buffer = None
         self.adaptive_info = None
+        self.until_info = None
         self.map_info = None
         self.temporal_info = None
         self.variance_estimate_info = None
@@ -398,6 +399,80 @@ class Render:
         info = capi.PlanInfo()
         capi.check(capi.lib().crt_sample_plan(h_, ap.threshold, ap.mean_floor, capi.ptr(m), C.byref(info)), "crt_sample_plan")
         return m, int(info.samples)
+
+    def frame_error(self, threshold=None, mean_floor=None):
+        """The error of the frame in flight (or of the last finished frame) as a FrameError (crt_frame_error, contract: include/crt.h):
+        the sums a render with want_variance keeps on the handle, reduced on the device over the shard's pixels against the adaptive
+        call's target, standard error <= threshold x (mean + mean_floor).  Reads only.  None settings take crt_frame_error_defaults."""
+        h_ = self._handle("frame_error")
+        thr, floor = _frame_error_settings(threshold, mean_floor)
+        info = capi.FrameErrorInfo()
+        capi.check(capi.lib().crt_frame_error(h_, thr, floor, C.byref(info)), "crt_frame_error")
+        return FrameError(info.as_dict(), thr, floor)
+
+    def frame_error_device(self, d_out_ptr, threshold=None, mean_floor=None, stream=None):
+        """crt_frame_error_device: the crt_frame_error_info into the device buffer d_out_ptr (capi.FrameErrorInfo's layout), enqueued on
+        `stream` without synchronizing."""
+        h_ = self._handle("frame_error_device")
+        thr, floor = _frame_error_settings(threshold, mean_floor)
+        capi.check(capi.lib().crt_frame_error_device(h_, thr, floor, C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), "crt_frame_error_device")
+
+    def _until_params(self, prm, min_samples, step_samples, threshold, mean_floor, max_above):
+        """crt_until_params from the settings (None: crt_until_defaults'); max_above: a pixel count (int) or a fraction of the shard's
+        pixels (float below 1)"""
+        up = capi.UntilParams()
+        capi.check(capi.lib().crt_until_defaults(C.byref(up)), "crt_until_defaults")
+        for name, v in (("min_samples", min_samples), ("step_samples", step_samples), ("threshold", threshold), ("mean_floor", mean_floor)):
+            if v is not None:
+                setattr(up, name, int(v) if name.endswith("samples") else float(v))
+        if max_above is not None:
+            if isinstance(max_above, (float, np.floating)):
+                if not 0.0 <= max_above < 1.0:
+                    raise ValueError("run_view_until: a fractional max_above must be in [0, 1), got %r" % (max_above,))
+                max_above = int(float(max_above) * shard_pixels(prm.width, prm.height, prm.rank, prm.world))
+            up.max_above = int(max_above)
+        return up
+
+    def run_view_until(self, eye_pos, inv_view_mat, fovY, min_samples=None, step_samples=None, threshold=None, mean_floor=None, max_above=None,
+                       sample_begin=0, want_variance=False, want_mean=True, want_halves=False, width=None, height=None):
+        """A uniform frame rendered until it is clean enough (crt_render_until, contract: include/crt.h): min_samples samples of every
+        pixel, then step_samples more per range until at most max_above pixels (an int, or a fraction of the pixels as a float) have a
+        standard error above threshold x (mean + mean_floor), or all self.spp samples are in.  None settings take crt_until_defaults.
+        Returns the RGB8 frame (H, W, 3): run_view's bits when the frame ran to spp, else preview()'s at the samples done -- and then
+        the frame STAYS IN FLIGHT: run_view_range or run_view_until(sample_begin=samples done) continues it.  self.mean_buffer
+        (want_mean) and self.variance_buffer (want_variance) go with it; self.until_info is the crt_until_info dict, its "last" a
+        FrameError.  want_halves: the ranges go with FLAG_HALF_BUFFERS."""
+        h_ = self._handle("run_view_until")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._params(flags=(capi.FLAG_HALF_BUFFERS if want_halves else 0) | self.extra_flags, width=width, height=height)
+        up = self._until_params(prm, min_samples, step_samples, threshold, mean_floor, max_above)
+        w, h = prm.width, prm.height
+        rgb = np.zeros((h, w, 3), dtype=np.uint8)
+        mean = np.zeros((h, w, 3), dtype=np.float32) if want_mean else None
+        var = np.zeros((h, w, 3), dtype=np.float32) if want_variance else None
+        info = capi.UntilInfo()
+        capi.check(capi.lib().crt_render_until(h_, C.byref(cam), C.byref(prm), C.byref(up), int(sample_begin), capi.ptr(rgb), capi.ptr(mean), capi.ptr(var),
+                                               C.byref(info)), "crt_render_until")
+        self.frame_buffer, self.mean_buffer, self.variance_buffer = rgb, mean, var
+        self.until_info = _until_info(info, up)
+        return rgb
+
+    def run_view_until_device(self, eye_pos, inv_view_mat, fovY, ptrs, min_samples=None, step_samples=None, threshold=None, mean_floor=None,
+                              max_above=None, sample_begin=0, stream=None, rank=0, world=1, tiled=False, want_info=True, width=None, height=None):
+        """crt_render_until_device: ptrs = {"rgb", "mean", "variance": raw device pointer or None} (row-major, or the shard's compact
+        tiles with tiled / world > 1), work enqueued on `stream`.  The call synchronizes the stream once per check (once more with
+        want_info, which sets self.until_info)."""
+        h_ = self._handle("run_view_until_device")
+        cam = self._cam(eye_pos, inv_view_mat, fovY)
+        prm = self._device_params(rank, world, tiled, width, height)
+        up = self._until_params(prm, min_samples, step_samples, threshold, mean_floor, max_above)
+        info = capi.UntilInfo()
+        out = [C.c_void_p(ptrs[n]) if ptrs.get(n) else None for n in ("rgb", "mean", "variance")]
+        capi.check(capi.lib().crt_render_until_device(h_, C.byref(cam), C.byref(prm), C.byref(up), int(sample_begin), *out,
+                                                      C.c_void_p(stream) if stream else None, C.byref(info) if want_info else None), "crt_render_until_device")
+        if want_info:
+            self.until_info = _until_info(info, up)
+        return self.until_info if want_info else None
 
     def _map_device(self, what, call, ptrs, stream, want_info):
         info = capi.MapInfo()
@@ -1099,6 +1174,10 @@ _MULTI_REFUSALS = {
     "run_view_planned": "planned adaptive frames are a single-device interface (crt_render_planned)",
     "run_view_planned_device": "planned adaptive frames are a single-device interface (crt_render_planned_device)",
     "sample_plan": "the sample plan is a single-device interface (crt_sample_plan)",
+    "frame_error": "the frame's error summary is a single-device interface (crt_frame_error)",
+    "frame_error_device": "the frame's error summary is a single-device interface (crt_frame_error_device)",
+    "run_view_until": "rendering to an error target is a single-device interface (crt_render_until)",
+    "run_view_until_device": "rendering to an error target is a single-device interface (crt_render_until_device)",
     "preview": "previews are a single-device interface (crt_preview)",
     "variance": "the variance buffer is a single-device interface (crt_variance)",
     "half_buffers": "the half buffers are a single-device interface (crt_half_buffers)",
@@ -1162,6 +1241,78 @@ def adaptive_defaults():
     p = capi.AdaptiveParams()
     capi.check(capi.lib().crt_adaptive_defaults(C.byref(p)), "crt_adaptive_defaults")
     return {n: getattr(p, n) for n, _ in p._fields_}
+
+
+def until_defaults():
+    """crt_until_defaults as a dict: min_samples, step_samples, threshold, mean_floor, max_above."""
+    p = capi.UntilParams()
+    capi.check(capi.lib().crt_until_defaults(C.byref(p)), "crt_until_defaults")
+    return {n: getattr(p, n) for n, _ in p._fields_}
+
+
+def frame_error_defaults():
+    """crt_frame_error_defaults as a dict: threshold, mean_floor."""
+    thr, floor = _frame_error_settings(None, None)
+    return {"threshold": thr, "mean_floor": floor}
+
+
+def _frame_error_settings(threshold, mean_floor):
+    thr, floor = C.c_float(), C.c_float()
+    capi.check(capi.lib().crt_frame_error_defaults(C.byref(thr), C.byref(floor)), "crt_frame_error_defaults")
+    return (thr.value if threshold is None else float(threshold)), (floor.value if mean_floor is None else float(mean_floor))
+
+
+def shard_pixels(width, height, rank=0, world=1):
+    """The pixels of shard `rank` of `world` of a width x height frame: its 8 x 8 tiles rank, rank + world, ... clipped to the frame."""
+    tx, ty = (width + 7) // 8, (height + 7) // 8
+    n = 0
+    for tile in range(rank, tx * ty, world):
+        x, y = tile % tx, tile // tx
+        n += min(8, width - 8 * x) * min(8, height - 8 * y)
+    return n
+
+
+class FrameError:
+    """crt_frame_error_info (include/crt.h) with what a caller reads from it.  The fields: samples_done, spp, pixels, nan_pixels, above,
+    hist (16 bins), sum_variance, sum_mean; threshold and mean_floor are the target's."""
+
+    def __init__(self, fields, threshold, mean_floor):
+        self.__dict__.update(fields)
+        self.threshold, self.mean_floor = threshold, mean_floor
+
+    def as_dict(self):
+        return {k: v for k, v in self.__dict__.items()}
+
+    @property
+    def fraction_above(self):
+        return self.above / self.pixels if self.pixels else 0.0
+
+    @property
+    def rel_rmse(self):
+        """The root of the mean variance over the mean of the channel-summed means (plus mean_floor): the frame's relative noise"""
+        if not self.pixels:
+            return 0.0
+        return float(np.sqrt(self.sum_variance / self.pixels) / (self.sum_mean / self.pixels + self.mean_floor))
+
+    def percentile_ratio(self, p):
+        """The smallest bin edge 4^k, k in -7 .. 7, such that at least p percent of the pixels have a variance within 4^k times the
+        target's (their standard error within 2^k times the threshold's); inf when the last bin or the NaN pixels are needed."""
+        need = np.ceil(self.pixels * float(p) / 100.0)
+        have = 0
+        for b in range(15):
+            have += self.hist[b]
+            if have >= need:
+                return 4.0 ** (b - 7)
+        return float("inf")
+
+    def __repr__(self):
+        return "FrameError(%s)" % ", ".join("%s=%r" % kv for kv in self.as_dict().items())
+
+
+def _until_info(info, up):
+    d = info.as_dict()
+    d["last"] = FrameError(d["last"], float(up.threshold), float(up.mean_floor))
+    return d
 
 
 def _adaptive_params(min_samples=None, step_samples=None, threshold=None, mean_floor=None):

@@ -4,6 +4,7 @@
   lib/crt_cli     headless config.json -> PNG command line     (hipcc, links libcrt.so)
   lib/render_host_check   tools/render_host_check.cpp, a GPU test's program   (likewise)
   lib/temporal_specular_host_check   tools/temporal_specular_host_check.cpp, a GPU test's program   (likewise)
+  lib/until_host_check   tools/until_host_check.cpp, a GPU test's program   (likewise)
 
 The flags matter for bit parity with the CPU oracle: no FMA contraction, no
 fast-math, correctly rounded fp32 divide / sqrt on the device.
@@ -22,11 +23,11 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"] + os.environ.get("CRT_EXTRA_CXXFLAGS", "").split()
 DEVICE = ["--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 
-LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_aov_direct.hip", "crt_aov_ao.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_regress.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_pyramid.hip", "crt_pixel_filter.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp", "crt_host_render.cpp", "crt_host_capi.cpp"]
-LIB_DEPS = LIB_SOURCES + ["crt_path.h", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_item_order.h", "crt_internal.h", "crt_stages.h", "crt_aov_direct.h", "crt_aov_ao.h", "crt_filter_host.h", "crt_modulate.h", "crt_nlm.h", "crt_regress.h", "crt_temporal.h", "crt_upsample.h", "crt_pyramid.h", "crt_pixel_filter.h", "crt_untile.h", "crt_select.h", "crt_render.h", "crt_scene.h", "crt_scene_layout.h", "crt_fastdiv.h", "crt_device.h", "crt_trace.h", "crt_accel.h", "crt_detmath.h", "crt_host.hpp", "crt_png.h", "crt_jpeg.h", "crt_formats.h", "crt_image.h", "crt_bvh_build.h",
+LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_aov_direct.hip", "crt_aov_ao.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_regress.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_pyramid.hip", "crt_pixel_filter.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp", "crt_host_render.cpp", "crt_host_capi.cpp"]
+LIB_DEPS = LIB_SOURCES + ["crt_path.h", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_item_order.h", "crt_internal.h", "crt_stages.h", "crt_aov_direct.h", "crt_aov_ao.h", "crt_frame_error.h", "crt_filter_host.h", "crt_modulate.h", "crt_nlm.h", "crt_regress.h", "crt_temporal.h", "crt_upsample.h", "crt_pyramid.h", "crt_pixel_filter.h", "crt_untile.h", "crt_select.h", "crt_render.h", "crt_scene.h", "crt_scene_layout.h", "crt_fastdiv.h", "crt_device.h", "crt_trace.h", "crt_accel.h", "crt_detmath.h", "crt_host.hpp", "crt_png.h", "crt_jpeg.h", "crt_formats.h", "crt_image.h", "crt_bvh_build.h",
                           os.path.join("..", "..", "include", "crt.h")]
 # the units that see the render kernel's headers (crt_mega3.h / crt_path.h): a variant build with a -D that changes a shared layout compiles all of these (tools/ab_build.sh)
-KERNEL_HEADER_UNITS = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_render.hip", "crt_sparse.hip", "crt_scene.hip"]
+KERNEL_HEADER_UNITS = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_scene.hip"]
 FLAGS_FILE = os.path.join(LIBDIR, "libcrt.flags")  # the flag string libcrt.so was built with (a variant build is stale for a default run)
 
 
@@ -188,11 +189,18 @@ def build_temporal_specular_check(force=False, verbose=False):
                           verbose)
 
 
+def build_until_check(force=False, verbose=False):
+    """tools/until_host_check.cpp: crt::Render::run_view_until and frame_error against the library calls they are made of
+    (tests/test_frame_error.py runs it on a GPU)"""
+    return _build_program(os.path.join(HERE, "..", "tools", "until_host_check.cpp"), os.path.join(LIBDIR, "until_host_check"), force, verbose)
+
+
 def build_all(force=False, verbose=False):
     build_lib(force, verbose)
     build_cli(force, verbose)
     build_render_check(force, verbose)
     build_temporal_specular_check(force, verbose)
+    build_until_check(force, verbose)
 
 
 if __name__ == "__main__":

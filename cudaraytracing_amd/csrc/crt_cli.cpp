@@ -10,6 +10,7 @@
 //           [--denoise-specular] [--denoise PATH] [--denoise-iterations N] [--denoise-sigma c,n,a,d] [--denoise-variance] [--variance PATH]
 //           [--denoise-nlm] [--denoise-nlm-params RADIUS,PATCH,K] [--denoise-regress] [--denoise-regress-params RADIUS,PATCH,K,RIDGE] [--denoise-scales N]
 //           [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]
+//           [--until THRESHOLD[,FRACTION[,MIN[,STEP]]]]
 //           [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]
 //           [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]
 //           [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX] [--aov-ao PREFIX[,SAMPLES[,DISTANCE]]]
@@ -55,6 +56,11 @@
 // --variance, --denoise and --aov work on the adaptive frame as on the uniform one.  --adaptive-planned renders it in two launches
 // instead (crt_render_planned): the warm-up, then every pixel's remaining samples as planned from the warm-up's variance; --adaptive-step
 // does not apply.
+// --until THRESHOLD[,FRACTION[,MIN[,STEP]]] renders the uniform frame until it is clean enough (crt_render_until, one device): MIN
+// samples of every pixel, then STEP more per range (crt_until_defaults' where not given) until at most FRACTION of the pixels (default
+// 0) have a standard error above THRESHOLD x (mean + floor), or all --spp samples are in.  Prints the samples done and the last summary
+// (crt_frame_error_info); the frame written is the preview at the samples done.  --variance, --denoise and --aov work on it as on the
+// uniform frame.  Not with --adaptive, --temporal, --upsample, --pixel-filter, --denoise-select or --gpus / --devices.
 // --variance PATH renders with CRT_FLAG_VARIANCE (the frame is the same bits) and writes the per-pixel variance of the mean
 // (crt_variance, one device) as a 3-channel PFM.  --denoise-variance makes --denoise use the variance-guided filter (crt_denoise_var,
 // its own defaults; --denoise-iterations / --denoise-sigma override them as well).  --denoise-nlm makes --denoise use the non-local-means
@@ -107,6 +113,7 @@ int main(int argc, char** argv)
                              "       [--denoise-scales N]  (1 .. 4 scales of a pyramid over --denoise-variance, --denoise-nlm or --denoise-regress)\n"
                              "       [--denoise-select LIST[,ERROR_RADIUS[,BLEND_RADIUS]]] [--denoise-choice PATH]  (LIST: none, atrous, var, nlm, reg joined by +)\n"
                              "       [--adaptive THRESHOLD] [--adaptive-min N] [--adaptive-step N] [--adaptive-samples PATH] [--adaptive-planned]\n"
+                             "       [--until THRESHOLD[,FRACTION[,MIN[,STEP]]]]\n"
                              "       [--temporal N] [--temporal-step x,y,z] [--temporal-out PATH] [--temporal-denoise] [--temporal-clamp GAMMA[,RADIUS]]\n"
                              "       [--temporal-variance samples|moments[,MIN_HISTORY]] [--temporal-specular [MIN_BOUNCES[,RADIUS[,MAX_BOUNCES]]]]\n"
                              "       [--upsample FACTOR[,RADIUS] --upsample-out PATH [--upsample-guide-spp N]]  (FACTOR 2 .. 8 divides --width and --height)\n"
@@ -125,6 +132,10 @@ int main(int argc, char** argv)
         crt_adaptive_params ad;
         crt_adaptive_defaults(&ad);
         bool adaptive = false, ad_option = false, planned = false;
+        crt_until_params un;
+        crt_until_defaults(&un);
+        bool until = false;
+        double until_fraction = 0.0;
         crt_denoise_params dn; // the overrides: 0 = take the default of the filter chosen
         std::memset(&dn, 0, sizeof(dn));
         bool dn_iterations = false, dn_sigma = false, denoise_var = false, denoise_specular = false;
@@ -344,6 +355,19 @@ int main(int argc, char** argv)
             else if (a == "--adaptive-step") { need(i, 1); ad.step_samples = (uint32_t)std::atoi(argv[++i]); ad_option = true; }
             else if (a == "--adaptive-samples") { need(i, 1); adaptive_samples = argv[++i]; ad_option = true; }
             else if (a == "--adaptive-planned") { planned = true; ad_option = true; }
+            else if (a == "--until") {
+                need(i, 1);
+                const char* q = argv[++i];
+                char* end = nullptr;
+                bool good = true;
+                un.threshold = std::strtof(q, &end);
+                good = end != q;
+                if (good && *end == ',') { q = end + 1; until_fraction = std::strtod(q, &end); good = end != q && until_fraction >= 0.0 && until_fraction < 1.0; }
+                if (good && *end == ',') { q = end + 1; const long n = std::strtol(q, &end, 10); good = end != q && n >= 2; un.min_samples = (uint32_t)n; }
+                if (good && *end == ',') { q = end + 1; const long n = std::strtol(q, &end, 10); good = end != q && n >= 1; un.step_samples = (uint32_t)n; }
+                if (!good || *end != 0) throw crt::Error(CRT_ERR_INVALID_ARG, "--until needs THRESHOLD[,FRACTION[,MIN[,STEP]]]: FRACTION in [0, 1), MIN >= 2, STEP >= 1");
+                until = true;
+            }
             else if (a == "--temporal") {
                 need(i, 1);
                 temporal = std::atoi(argv[++i]);
@@ -500,6 +524,9 @@ int main(int argc, char** argv)
         if (temporal_option && !temporal) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-step, --temporal-out, --temporal-denoise, --temporal-clamp, --temporal-variance and --temporal-specular need --temporal N");
         if (temporal_specular && temporal_moments) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-specular cannot be combined with --temporal-variance moments (crt_temporal_moments has no dual form)");
         if (temporal_denoise && temporal_out.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--temporal-denoise needs --temporal-out PATH");
+        if (until && multi) throw crt::Error(CRT_ERR_INVALID_ARG, "--until renders on one device (not with --gpus / --devices)");
+        if (until && (adaptive || temporal || upsample || pixel_filter_on || !select_candidates.empty()))
+            throw crt::Error(CRT_ERR_INVALID_ARG, "--until renders the uniformly sampled frame in ranges (not with --adaptive, --temporal, --upsample, --pixel-filter or --denoise-select)");
         if (ad_option && !adaptive) throw crt::Error(CRT_ERR_INVALID_ARG, "--adaptive-min, --adaptive-step, --adaptive-samples and --adaptive-planned need --adaptive THRESHOLD");
         if (denoise_var && denoise.empty()) throw crt::Error(CRT_ERR_INVALID_ARG, "--denoise-variance needs --denoise PATH");
         // --denoise-nlm and --denoise-regress: filters of their own with the same rules; --denoise-sigma's guide sigmas go to their settings
@@ -591,6 +618,10 @@ int main(int argc, char** argv)
         }
         else if (adaptive && planned) render.run_view_planned(task.eye_pos, inv_view, fov_y, ad, want_var);
         else if (adaptive) render.run_view_adaptive(task.eye_pos, inv_view, fov_y, ad, want_var);
+        else if (until) {
+            un.max_above = (uint64_t)(until_fraction * (double)((uint64_t)task.width * task.height));
+            render.run_view_until(task.eye_pos, inv_view, fov_y, un, 0, want_var);
+        }
         else if (!gathered.empty()) {
             uint32_t want = 0;
             for (size_t r : gathered_rows) want |= gathered_planes[r].bit;
@@ -602,6 +633,15 @@ int main(int argc, char** argv)
             const crt_map_info& mi = render.last_map_info();
             std::printf("render cost: %.6f seconds (device %.3f ms, planned: %u launches, %llu of %llu paths)\n", dt.count(), mi.total_ms, mi.launches,
                         (unsigned long long)mi.paths, (unsigned long long)mi.paths_uniform);
+        } else if (until) {
+            const crt_until_info& ui = render.last_until_info();
+            const crt_frame_error_info& e = ui.last;
+            std::printf("render cost: %.6f seconds (device %.3f ms, until: %u of %u samples in %u ranges, %u checks, %llu paths)\n", dt.count(), ui.total_ms,
+                        ui.samples_done, e.spp, ui.passes, ui.checks, (unsigned long long)ui.paths);
+            std::printf("until: %llu of %llu pixels above the target (%llu allowed, %llu NaN), sum_variance %.17g, sum_mean %.17g\nuntil: hist", (unsigned long long)e.above,
+                        (unsigned long long)e.pixels, (unsigned long long)un.max_above, (unsigned long long)e.nan_pixels, e.sum_variance, e.sum_mean);
+            for (int b = 0; b < 16; b++) std::printf(" %llu", (unsigned long long)e.hist[b]);
+            std::printf("\n");
         } else if (adaptive) {
             const crt_adaptive_info& ai = render.last_adaptive_info();
             std::printf("render cost: %.6f seconds (device %.3f ms, adaptive: %u passes, %llu of %llu paths)\n", dt.count(), ai.total_ms, ai.passes,

@@ -230,6 +230,13 @@ public:
     void run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin = 0, bool want_variance = false);
     void run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance = false);
     const crt_map_info& last_map_info() const { return map_info_; }
+    // the error of the frame in flight, or of the last finished frame, against the adaptive call's target (crt_frame_error): reads only
+    crt_frame_error_info frame_error(float threshold, float mean_floor);
+    // a uniform frame rendered until it is clean enough (crt_render_until; up: crt_until_defaults with overrides): frame and mean buffers
+    // as run_view leaves them when the frame ran to spp, else the preview's at last_until_info().samples_done, and then the frame stays
+    // in flight: run_view_until with sample_begin = samples_done continues it.  want_variance: the variance of that mean in variance()
+    void run_view_until(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_until_params& up, uint32_t sample_begin = 0, bool want_variance = false);
+    const crt_until_info& last_until_info() const { return until_info_; }
     const uint32_t* get_samples_buffer() const { return samples_buffer_.data(); } // W x H, after run_view_adaptive / _map / _planned
     const crt_adaptive_info& last_adaptive_info() const { return adaptive_info_; }
     // first-hit albedo, normal and depth of the frame run_view draws with the same camera and settings (crt_render_aov); one device only
@@ -435,6 +442,7 @@ private:
     void modulate_of(const char* who, const float* irradiance, float* out_mean, unsigned char* out_rgb) const;
     crt_adaptive_info adaptive_info_{};
     crt_map_info map_info_{};
+    crt_until_info until_info_{};
     void view_args(const float eye_pos[3], const float inv_view_mat[9], float fovY, uint32_t flags, crt_camera& cam, crt_params& p) const;
     template <class Call> void sampled_frame(const char* who, const float eye_pos[3], const float inv_view_mat[9], float fovY, bool want_variance, Call render);
     int device_ = 0;

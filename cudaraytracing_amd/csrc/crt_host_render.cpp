@@ -228,6 +228,27 @@ void Render::run_view_planned(const float eye_pos[3], const float inv_view_mat[9
     });
 }
 
+crt_frame_error_info Render::frame_error(float threshold, float mean_floor)
+{
+    one_device("Render::frame_error", "the frame's error summary");
+    crt_frame_error_info e{};
+    check(crt_frame_error(device_scene_, threshold, mean_floor, &e), "Render::frame_error");
+    return e;
+}
+
+void Render::run_view_until(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_until_params& up, uint32_t sample_begin, bool want_variance)
+{
+    one_device("Render::run_view_until", "rendering to an error target");
+    crt_camera cam;
+    crt_params p;
+    view_args(eye_pos, inv_view_mat, fovY, flags_ & CRT_FLAG_TRACE_ALL, cam, p);
+    variance_buffer_.clear();
+    std::vector<float> v(want_variance ? 3 * scene_->get_pixels() : 0, 0.0f);
+    check(crt_render_until(device_scene_, &cam, &p, &up, sample_begin, frame_buffer_.data(), mean_buffer_.data(), want_variance ? v.data() : nullptr, &until_info_),
+          "Render::run_view_until");
+    variance_buffer_.swap(v);
+}
+
 void Render::run_aov(const float eye_pos[3], const float inv_view_mat[9], float fovY)
 {
     one_device("Render::run_aov", "the AOV pass");

@@ -135,6 +135,12 @@ struct crt_scene {
     crtk::DevBuf<unsigned int> map_hist, map_cursor;
     unsigned int* h_map = nullptr;
     size_t h_map_words = 0;
+    // crt_frame_error: the blocks' partials of the two fp64 sums and of the counts (crt_frame_error.h: FrameErrorParams), the summary of
+    // the host form and of crt_render_until's checks, and the pinned copy a check's `above` is read through
+    crtk::DevBuf<double> fe_sum;
+    crtk::DevBuf<uint32_t> fe_cnt;
+    crtk::DevBuf<crt_frame_error_info> fe_info;
+    crt_frame_error_info* h_fe = nullptr;
     std::vector<hipEvent_t> ev;
     std::vector<hipEvent_t> ev_chunk; // a timed megakernel frame: (before, after) the launch of chunk i at [2 i], [2 i + 1]
     ~crt_scene()
@@ -150,6 +156,7 @@ struct crt_scene {
         if (h_ad_count) (void)hipHostFree(h_ad_count);
         if (h_aovs_count) (void)hipHostFree(h_aovs_count);
         if (h_map) (void)hipHostFree(h_map);
+        if (h_fe) (void)hipHostFree(h_fe);
     }
 };
 

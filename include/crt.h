@@ -1634,6 +1634,93 @@ int crt_render_planned(crt_scene* scene, const crt_camera* cam, const crt_params
 int crt_render_planned_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_adaptive_params* adaptive,
                               void* d_rgb, void* d_mean, void* d_samples, void* d_variance, void* hip_stream, crt_map_info* info);
 
+/* The error of the frame in flight in one small struct: the sums c and q of the crt_variance contract, reduced on the device over the
+ * shard's VALID pixel slots (padding slots of a tiled shard count for nothing).  Accepts the state crt_variance accepts -- a frame in
+ * flight or the last finished frame, rendered with CRT_FLAG_VARIANCE, n >= 2 samples in the sums -- and changes nothing on the handle:
+ * a call between two ranges changes no later bit.  With S = the frame's spp, fn = (float)n, fs = (float)S, per valid slot, every
+ * operation one IEEE fp32 operation, no FMA (crt_render_adaptive's criterion):
+ *   r = fs / fn;  rr = r * r
+ *   per channel  d = fn * q - c * c;  d = d < 0.0f ? 0.0f : d;  var = (rr * d) / (fn - 1.0f);   p = c * r
+ *   v = (var.x + var.y) + var.z;   m = (p.x + p.y) + p.z;   t = threshold * (m + mean_floor);   tt = t * t
+ *   nan_pixels  slots where v or tt is NaN
+ *   above       slots with !(v <= tt): the pixels crt_render_adaptive would send on, NaN slots included
+ *   hist[b]     the other slots by b = the number of j in 0 .. 14 with v > tt * e_j, e_j = 4^(j - 7) (an exact fp32 constant, the product
+ *               one fp32 multiply).  e_7 = 1, so above == hist[8] + ... + hist[15] + nan_pixels, and the sum of hist + nan_pixels ==
+ *               pixels.  Bin b <= 7 holds the pixels whose v is within 4^(b - 7) times the target, bin 8 + k those beyond it by up to 4^(k + 1).
+ *   sum_variance, sum_mean   fp64 sums of (double)v and (double)m over the valid slots that are not NaN slots; every other slot
+ *               contributes +0.0.  Every add is one IEEE fp64 add and their order is part of the contract, so that the bits do not
+ *               depend on how the reduction is launched:
+ *     1. slots are taken in blocks of 256 consecutive slot indices (the last block filled up with +0.0), in a block in groups of 64
+ *     2. in a group, for s = 32, 16, 8, 4, 2, 1:  x[t] += x[t + s] for every t < s; the group's sum is x[0]: w0 .. w3 of the block
+ *     3. the block's partial is ((w0 + w1) + w2) + w3
+ *     4. with P[0 .. nb) the blocks' partials: lane l of ONE group of 64 adds P[l], P[l + 64], ... in ascending order to +0.0
+ *     5. the 64 lane sums are folded by the tree of step 2
+ * The counts are integers: exact in any order.
+ * CRT_ERR_INVALID_ARG, before any device call, the handle untouched: what crt_variance refuses (a null scene; no valid variance sums
+ * on the handle; n < 2); a null output; a threshold that is negative or NaN; a mean_floor that is negative or not finite.
+ * crt_frame_error_defaults gives threshold 0.05 and mean_floor 0.01, crt_adaptive_defaults' values (untuned). */
+typedef struct {
+    uint32_t samples_done;  /* n: the samples in the sums */
+    uint32_t spp;           /* S */
+    uint64_t pixels;        /* the shard's valid pixel slots */
+    uint64_t nan_pixels;
+    uint64_t above;
+    uint64_t hist[16];
+    double sum_variance;
+    double sum_mean;
+} crt_frame_error_info;
+int crt_frame_error_defaults(float* threshold, float* mean_floor);
+/* returns the struct; synchronizes once */
+int crt_frame_error(crt_scene* scene, float threshold, float mean_floor, crt_frame_error_info* out);
+/* d_out: sizeof(crt_frame_error_info) bytes on the scene's device, 8-byte aligned; enqueued on hip_stream (NULL = default stream)
+ * without synchronizing.  The partial sums live in a scratch buffer on the handle: one summary of a handle at a time. */
+int crt_frame_error_device(crt_scene* scene, float threshold, float mean_floor, void* d_out, void* hip_stream);
+
+/* A uniform frame rendered until it is clean enough, and left in flight.  CRT_FLAG_VARIANCE is implied; every other flag means what it
+ * means to crt_render_range.  In terms of the calls above, S = params->spp:
+ *   1. sample_begin == 0: crt_render_range(0, min_samples); n = min_samples.
+ *      sample_begin > 0: the frame in flight must hold exactly samples [0, sample_begin) of every pixel with CRT_FLAG_VARIANCE from
+ *      sample 0 on, at the same spp, size, shard and layout.  sample_begin < min_samples: crt_render_range(sample_begin, min_samples -
+ *      sample_begin), n = min_samples; else n = sample_begin and nothing is rendered yet.
+ *   2. E = crt_frame_error(threshold, mean_floor) at n; E.above is recorded.  E.above <= max_above or n == S: stop.
+ *   3. ns = min(step_samples, S - n); crt_render_range(n, ns); n += ns; step 2.
+ * n == S: the last range wrote the frame: out_rgb / out_mean are crt_render's bits, out_variance crt_variance's, the frame is finished.
+ * n < S: out_rgb / out_mean are crt_preview's bits at n, out_variance crt_variance's at n, and THE FRAME STAYS IN FLIGHT at n: a later
+ * crt_render_range(n, ...) or crt_render_until(sample_begin = n) with a stricter target continues it, and run to S it ends with
+ * crt_render's bits.  out_rgb is required; out_mean, out_variance and info are optional.
+ * CRT_ERR_INVALID_ARG, before any device call, the handle as it was: a null scene, camera, params, until params or out_rgb;
+ * min_samples < 2 or > spp; step_samples == 0; threshold / mean_floor as crt_frame_error; a sample_begin that does not continue the
+ * frame in flight; whatever crt_render_range with CRT_FLAG_VARIANCE refuses, refused as it refuses it.  crt_multi has no such call.
+ * crt_until_defaults fills min_samples 16, step_samples 64 (crt_adaptive_defaults' values: every range is a launch of the render
+ * kernel with its tail), threshold 0.05, mean_floor 0.01, max_above 0. */
+typedef struct {
+    uint32_t min_samples;   /* the first check is made at max(min_samples, sample_begin) samples; >= 2, <= spp */
+    uint32_t step_samples;  /* samples per range after it; >= 1 */
+    float threshold;
+    float mean_floor;
+    uint64_t max_above;     /* pixels that may stay above the target */
+} crt_until_params;
+#define CRT_UNTIL_CHECKS_REPORTED 64
+typedef struct {
+    uint32_t passes;        /* ranges this call rendered */
+    uint32_t checks;        /* summaries it read */
+    uint32_t samples_done;  /* n at the end */
+    uint32_t reserved_;
+    uint64_t above[CRT_UNTIL_CHECKS_REPORTED]; /* E.above of check 0, 1, ... (checks beyond 64 are not recorded) */
+    uint64_t paths;         /* pixels x samples this call rendered */
+    float kernel_ms;        /* the render kernel's launches (0 on the fallback pipeline) */
+    float total_ms;
+    crt_frame_error_info last; /* the summary of the last check */
+} crt_until_info;
+int crt_until_defaults(crt_until_params* params);
+int crt_render_until(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_until_params* until, uint32_t sample_begin,
+                     uint8_t* out_rgb, float* out_mean, float* out_variance, crt_until_info* info);
+/* d_rgb / d_mean / d_variance: device buffers in the layout of crt_render_device's, enqueued on hip_stream (NULL = default stream).
+ * SYNCHRONIZES hip_stream once per check, as crt_render_adaptive_device per pass, to read E.above: one 8-byte copy into pinned memory;
+ * once more at the end when info != NULL (the last summary and the timers). */
+int crt_render_until_device(crt_scene* scene, const crt_camera* cam, const crt_params* params, const crt_until_params* until, uint32_t sample_begin,
+                            void* d_rgb, void* d_mean, void* d_variance, void* hip_stream, crt_until_info* info);
+
 /* The order in which the render kernel hands out the last work items of a launch (the paths the roulette draws will let run longest
  * first: it shortens the end of a launch, where every wave runs its pool dry, and cannot change a result).  The order is a list on the
  * handle that depends on the seed, the sample range, the size and shard of the frame, p_rr and the stream -- not on the camera or the

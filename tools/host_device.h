@@ -3,7 +3,8 @@
 // plain restatements under AddressSanitizer / UBSan; this header supplies what that text takes from outside: the HIP qualifiers and
 // types, the atomics and bit casts, the few definitions of crt_device.h / crt_path.h it uses, and the launch with its indices.
 // A program that defines CRT_HOST_WAVES before the include gets a wave of 64 host threads with the cross-lane operations (and needs
-// -pthread); without it a launch is a plain loop over blocks and threads, for kernels that have no cross-lane operation.
+// -pthread), an 8-byte __shfl_down and LDS; without it a launch is a plain loop over blocks and threads, for kernels that have no
+// cross-lane operation.
 // A program that defines CRT_HOST_PATH before the include also gets what kernel text takes from the path code (crt_aov_direct.h, crt_aov_ao.h): the
 // remaining vector types and bit casts, F3's other operations, the triangle row's material word, the ray kinds, shadow_blocked and
 // bounce_dir with the samplers under it.
@@ -162,10 +163,10 @@ struct Wave { // the 64 lanes of the wave that is running
     std::condition_variable cv;
     int waiting = 0;
     unsigned long gen = 0;
-    int in[64], vals[64];
+    long long in[64], vals[64];
     // The barrier: every lane hands in a value and returns when all 64 have, with the 64 values in vals.  (vals is written again by
     // the last lane to reach the NEXT barrier, so after every lane has read it.)
-    void barrier(int v = 0)
+    void barrier(long long v = 0)
     {
         std::unique_lock<std::mutex> l(m);
         in[threadIdx.x & 63] = v;
@@ -185,9 +186,25 @@ static unsigned long long __ballot(bool p)
 static int __builtin_amdgcn_readlane(int v, int lane_from)
 {
     g_wave.barrier(v);
-    return g_wave.vals[lane_from];
+    return (int)g_wave.vals[lane_from];
 }
 static int __builtin_amdgcn_readfirstlane(int v) { return __builtin_amdgcn_readlane(v, 0); } // (called with every lane active)
+// the shuffle of an 8-byte value (double, unsigned long long): lane + delta's, a lane's own where that is beyond the wave
+template <class T> static T __shfl_down(T v, unsigned int delta)
+{
+    static_assert(sizeof(T) == sizeof(long long), "an 8-byte value");
+    long long bits;
+    std::memcpy(&bits, &v, sizeof(bits));
+    g_wave.barrier(bits);
+    const unsigned int lane = threadIdx.x & 63u, from = lane + delta < 64u ? lane + delta : lane;
+    bits = g_wave.vals[from];
+    std::memcpy(&v, &bits, sizeof(bits));
+    return v;
+}
+// LDS: one static array, which the waves of a block -- run one after another here -- all see; so the block-wide barrier is the
+// wave's own, and is right for kernel text in which only the block's LAST wave reads what the others wrote (crt_frame_error.h)
+#define __shared__ static
+static void __syncthreads() { g_wave.barrier(); }
 static int __ffsll(long long v) { return __builtin_ffsll(v); }
 static int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 
