@@ -131,6 +131,17 @@ class TreeScalars(InfoStruct):
                 ("stack_cap", C.c_uint32), ("node4i_f4", C.c_uint32)]
 
 
+class RefitInfo(InfoStruct):
+    _fields_ = [("n_tris", C.c_uint32), ("n_light_tris", C.c_uint32), ("leaves", C.c_uint32), ("boxes_written", C.c_uint32), ("launches", C.c_uint32),
+                ("form", C.c_uint32), ("root_aa", C.c_float * 3), ("root_bb", C.c_float * 3), ("coord_max", C.c_float), ("prepare_ms", C.c_float),
+                ("device_ms", C.c_float)]
+
+    def as_dict(self):
+        d = super().as_dict()
+        d["root_aa"], d["root_bb"] = [float(x) for x in self.root_aa], [float(x) for x in self.root_bb]
+        return d
+
+
 class AovBuffers(C.Structure):
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("depth", C.c_void_p), ("coverage", C.c_void_p), ("tri", C.c_void_p),
                 ("material", C.c_void_p)]
@@ -427,7 +438,8 @@ EXPORTS = ["crt_strerror", "crt_last_error", "crt_abi_version", "crt_device_coun
            "crt_pixel_filter_defaults", "crt_set_pixel_filter", "crt_filtered_frame", "crt_filtered_frame_device",
            "crt_render_aov_direct", "crt_render_aov_direct_device",
            "crt_aov_ao_defaults", "crt_render_aov_ao", "crt_render_aov_ao_device",
-           "crt_frame_error_defaults", "crt_frame_error", "crt_frame_error_device", "crt_until_defaults", "crt_render_until", "crt_render_until_device"]
+           "crt_frame_error_defaults", "crt_frame_error", "crt_frame_error_device", "crt_until_defaults", "crt_render_until", "crt_render_until_device",
+           "crt_scene_refit", "crt_scene_refit_device", "crt_host_scene_transform_object"]
 
 _lib = None
 
@@ -625,6 +637,10 @@ def lib():
                                        C.c_void_p, C.POINTER(UntilInfo)]
         L.crt_render_until_device.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(Params), C.POINTER(UntilParams), C.c_uint32, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.POINTER(UntilInfo)]
+    if hasattr(L, "crt_scene_refit"):  # (likewise)
+        L.crt_scene_refit.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(RefitInfo)]
+        L.crt_scene_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(RefitInfo)]
+        L.crt_host_scene_transform_object.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
     _lib = L
     return L
 

@@ -87,6 +87,14 @@ class Scene:
             self.bvh_build_info = info.as_dict()
         self._desc = None
 
+    def transform_object(self, index, m):
+        """Moves object `index` (objects()' order) by the 3 x 4 affine map m (12 values, row-major), keeping the BVH's topology and
+        refitting its boxes (crt_host_scene_transform_object); desc(), nodes(), triangles() ... then give the moved description, which
+        Render.refit() pushes into a scene handle."""
+        a = np.ascontiguousarray(m, dtype=np.float32).reshape(12)
+        capi.check(capi.lib().crt_host_scene_transform_object(self._h, int(index), a.ctypes.data_as(C.POINTER(C.c_float))), "crt_host_scene_transform_object")
+        self._desc = None
+
     def desc(self):
         if self._desc is None:
             d = capi.SceneDesc()
@@ -186,6 +194,7 @@ class Render:
         self.samples_buffer = None
         self.adaptive_info = None
         self.until_info = None
+        self.refit_info = None
         self.map_info = None
         self.temporal_info = None
         self.variance_estimate_info = None
@@ -238,6 +247,43 @@ class Render:
         assert n.value == C.sizeof(s)
         out.update(s.as_dict())
         return out
+
+    def export_array(self, name):
+        """Test hook: one array of crt_scene_export by name -- those of EXPORT_ARRAYS, and "ltri" (the light triangles' rows) -- as
+        export_trees() returns them."""
+        h = self._handle("export_array")
+        dt = self.EXPORT_ARRAYS.get(name, np.float32)
+        n = C.c_size_t()
+        capi.check(capi.lib().crt_scene_export(h, name.encode(), None, 0, C.byref(n)), "crt_scene_export")
+        a = np.zeros(n.value // np.dtype(dt).itemsize, dtype=dt)
+        if n.value:
+            capi.check(capi.lib().crt_scene_export(h, name.encode(), capi.ptr(a), a.nbytes, C.byref(n)), "crt_scene_export")
+        return a.reshape(-1, 4) if dt is np.float32 else a
+
+    def refit(self, tris=None, light_tris=None):
+        """Moves the handle's triangles without rebuilding it (crt_scene_refit): tris / light_tris are arrays of capi.TRI_DTYPE in the
+        handle's BVH order / shape order, by default the scene's current ones (after Scene.transform_object).  Ends the frame in
+        flight.  Returns crt_refit_info as a dict, also kept in self.refit_info."""
+        h = self._handle("refit")
+        t = np.ascontiguousarray(self.scene.triangles() if tris is None else tris, dtype=capi.TRI_DTYPE)
+        l = np.ascontiguousarray(self.scene.light_triangles() if light_tris is None else light_tris, dtype=capi.TRI_DTYPE)
+        info = capi.RefitInfo()
+        capi.check(capi.lib().crt_scene_refit(h, capi.ptr(t), len(t), capi.ptr(l) if len(l) else None, len(l), C.byref(info)), "crt_scene_refit")
+        self.refit_info = info.as_dict()
+        return self.refit_info
+
+    def refit_device(self, d_tris_ptr, d_light_tris_ptr, stream=None, n_tris=None, n_light_tris=None):
+        """crt_scene_refit_device: the two arrays of crt_triangle (60 bytes each) are device pointers, e.g. tensor.data_ptr(); the work is
+        enqueued on `stream` (a HIP stream handle as an integer; None: the null stream), which is synchronized once.  The counts default
+        to the scene's."""
+        h = self._handle("refit_device")
+        nt = len(self.scene.triangles()) if n_tris is None else int(n_tris)
+        nl = len(self.scene.light_triangles()) if n_light_tris is None else int(n_light_tris)
+        info = capi.RefitInfo()
+        capi.check(capi.lib().crt_scene_refit_device(h, C.c_void_p(d_tris_ptr), nt, C.c_void_p(d_light_tris_ptr) if d_light_tris_ptr else None, nl,
+                                                     C.c_void_p(stream) if stream else None, C.byref(info)), "crt_scene_refit_device")
+        self.refit_info = info.as_dict()
+        return self.refit_info
 
     def set_spp(self, spp):
         self.spp = int(spp)

@@ -23,11 +23,11 @@ HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math"] + os.environ.get("CRT_EXTRA_CXXFLAGS", "").split()
 DEVICE = ["--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt"]
 
-LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_aov_direct.hip", "crt_aov_ao.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_regress.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_pyramid.hip", "crt_pixel_filter.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp", "crt_host_render.cpp", "crt_host_capi.cpp"]
-LIB_DEPS = LIB_SOURCES + ["crt_path.h", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_item_order.h", "crt_internal.h", "crt_stages.h", "crt_aov_direct.h", "crt_aov_ao.h", "crt_frame_error.h", "crt_filter_host.h", "crt_modulate.h", "crt_nlm.h", "crt_regress.h", "crt_temporal.h", "crt_upsample.h", "crt_pyramid.h", "crt_pixel_filter.h", "crt_untile.h", "crt_select.h", "crt_render.h", "crt_scene.h", "crt_scene_layout.h", "crt_fastdiv.h", "crt_device.h", "crt_trace.h", "crt_accel.h", "crt_detmath.h", "crt_host.hpp", "crt_png.h", "crt_jpeg.h", "crt_formats.h", "crt_image.h", "crt_bvh_build.h",
+LIB_SOURCES = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_aov.hip", "crt_aov_direct.hip", "crt_aov_ao.hip", "crt_denoise.hip", "crt_nlm.hip", "crt_regress.hip", "crt_modulate.hip", "crt_temporal.hip", "crt_variance_estimate.hip", "crt_upsample.hip", "crt_pyramid.hip", "crt_pixel_filter.hip", "crt_select.hip", "crt_device_fn.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_aov_pass.hip", "crt_scene.hip", "crt_refit.hip", "crt_multi.hip", "crt_bvh_build.hip", "crt_accel_build.hip", "crt_host.cpp", "crt_host_render.cpp", "crt_host_capi.cpp"]
+LIB_DEPS = LIB_SOURCES + ["crt_path.h", "crt_mega3.h", "crt_mega3_math.h", "crt_mega3_wave.h", "crt_mega3_logic.h", "crt_mega3_coupled.h", "crt_mega3_decoupled.h", "crt_item_order.h", "crt_internal.h", "crt_stages.h", "crt_aov_direct.h", "crt_aov_ao.h", "crt_frame_error.h", "crt_refit.h", "crt_filter_host.h", "crt_modulate.h", "crt_nlm.h", "crt_regress.h", "crt_temporal.h", "crt_upsample.h", "crt_pyramid.h", "crt_pixel_filter.h", "crt_untile.h", "crt_select.h", "crt_render.h", "crt_scene.h", "crt_scene_layout.h", "crt_fastdiv.h", "crt_device.h", "crt_trace.h", "crt_accel.h", "crt_detmath.h", "crt_host.hpp", "crt_png.h", "crt_jpeg.h", "crt_formats.h", "crt_image.h", "crt_bvh_build.h",
                           os.path.join("..", "..", "include", "crt.h")]
 # the units that see the render kernel's headers (crt_mega3.h / crt_path.h): a variant build with a -D that changes a shared layout compiles all of these (tools/ab_build.sh)
-KERNEL_HEADER_UNITS = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_scene.hip"]
+KERNEL_HEADER_UNITS = ["crt_mega3.hip", "crt_wavefront.hip", "crt_frame.hip", "crt_adaptive.hip", "crt_sample_map.hip", "crt_render.hip", "crt_sparse.hip", "crt_frame_error.hip", "crt_scene.hip", "crt_refit.hip"]
 FLAGS_FILE = os.path.join(LIBDIR, "libcrt.flags")  # the flag string libcrt.so was built with (a variant build is stale for a default run)
 
 

@@ -103,6 +103,7 @@ int main(int argc, char** argv)
 {
     if (argc < 2) {
         std::fprintf(stderr, "usage: %s <config.json> [-o out.png] [--spp N] [--p-rr X] [--lsn N] [--seed S] [--width W] [--height H]\n"
+                             "       [--move-object INDEX,dx,dy,dz]...  (translates one object and refits the scene handle, once per use, before the frame)\n"
                              "       [--eye x y z] [--lookat x y z] [--up x y z] [--reference | --exact | --fast] [--bounded-radiance] [--base-dir DIR] [--device N]\n"
                              "       [--gpus N | --devices a,b,...] [--gather auto|rccl|copy] [--aov PREFIX] [--aov-specular PREFIX[,MAX_BOUNCES]]\n"
                              "       [--denoise-specular] [--aov-shading PREFIX] [--demodulate] [--aov-direct PREFIX]\n"
@@ -183,6 +184,8 @@ int main(int argc, char** argv)
             {"emission", CRT_MULTI_EMISSION, 3}, {"diffuse_albedo", CRT_MULTI_DIFFUSE_ALBEDO, 3}};
         std::string gathered;
         std::vector<size_t> gathered_rows;
+        struct MoveObject { uint32_t index; float d[3]; };
+        std::vector<MoveObject> moves; // --move-object, in the order given
         auto need = [&](int i, int n) { if (i + n >= argc) throw crt::Error(CRT_ERR_INVALID_ARG, std::string("missing value after ") + argv[i]); };
         for (int i = 2; i < argc; i++) {
             std::string a = argv[i];
@@ -483,6 +486,20 @@ int main(int argc, char** argv)
                     q = end + 1;
                 }
             }
+            else if (a == "--move-object") {
+                need(i, 1);
+                const char* q = argv[++i];
+                char* e = nullptr;
+                MoveObject mo;
+                mo.index = (uint32_t)std::strtoul(q, &e, 10);
+                bool good = e != q;
+                for (int k = 0; k < 3 && good; k++) {
+                    good = *e == ',';
+                    if (good) { q = e + 1; mo.d[k] = std::strtof(q, &e); good = e != q; }
+                }
+                if (!good || *e) throw crt::Error(CRT_ERR_INVALID_ARG, "--move-object needs INDEX,dx,dy,dz");
+                moves.push_back(mo);
+            }
             else if (a == "--reference") reference = true;
             else if (a == "--exact") exact = true;
             else if (a == "--fast") fast = true;
@@ -574,6 +591,14 @@ int main(int argc, char** argv)
         render.set_flags((bounded ? CRT_FLAG_BOUNDED_RADIANCE : 0u) | (want_var ? CRT_FLAG_VARIANCE : 0u) | (denoise_select ? CRT_FLAG_HALF_BUFFERS : 0u) |
                          (pixel_filter_on ? CRT_FLAG_PIXEL_FILTER : 0u));
         if (pixel_filter_on) render.set_pixel_filter(&pixel_filter);
+        if (!moves.empty() && multi) throw crt::Error(CRT_ERR_INVALID_ARG, "--move-object refits one device's scene handle (not with --gpus / --devices)");
+        for (const MoveObject& mo : moves) { // the handle was made from the scene as loaded: each move is one refit of it
+            const float m[12] = {1.0f, 0.0f, 0.0f, mo.d[0], 0.0f, 1.0f, 0.0f, mo.d[1], 0.0f, 0.0f, 1.0f, mo.d[2]};
+            scene.transform_object(mo.index, m);
+            const crt_refit_info ri = render.refit();
+            std::printf("moved object %u by (%g, %g, %g): refit %.3f ms on the device (tables %.3f ms), %u launches\n", mo.index, mo.d[0], mo.d[1], mo.d[2], ri.device_ms,
+                        ri.prepare_ms, ri.launches);
+        }
         render.set_aov_shading(!aov_shading.empty());
         if (demodulate) render.set_demodulate(true);
         // One output's files -- a PFM of 1 or 3 channels of floats, or with channels 0 a PNG of RGB8 -- are written, then their paths printed

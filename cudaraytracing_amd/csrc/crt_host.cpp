@@ -157,6 +157,32 @@ BVH::BVH(unsigned thresh_n, std::vector<Triangle>& triangles, int device, crt_bv
     if (info) *info = bi;
 }
 
+void BVH::refit()
+{
+    auto lt = [](float x, float y) { return x < y || (x == y && std::signbit(x) && !std::signbit(y)); }; // (crtaccel::Box::ord_lt)
+    auto grow = [&](BVHNode& n, Vec3 p) {
+        if (lt(p.x, n.AA.x)) n.AA.x = p.x;
+        if (lt(p.y, n.AA.y)) n.AA.y = p.y;
+        if (lt(p.z, n.AA.z)) n.AA.z = p.z;
+        if (lt(n.BB.x, p.x)) n.BB.x = p.x;
+        if (lt(n.BB.y, p.y)) n.BB.y = p.y;
+        if (lt(n.BB.z, p.z)) n.BB.z = p.z;
+    };
+    for (BVHNode& n : nodes_) { // post-order: children precede their parent
+        if (n.lc < 0 && n.rc < 0) {
+            n.AA = n.BB = triangles_[(size_t)n.it].get_v1();
+            for (unsigned k = 0; k < n.n; k++) {
+                const Triangle& t = triangles_[(size_t)n.it + k];
+                grow(n, t.get_v1()); grow(n, t.get_v2()); grow(n, t.get_v3());
+            }
+        } else {
+            const BVHNode &l = nodes_[(size_t)n.lc], &r = nodes_[(size_t)n.rc];
+            n.AA = l.AA; n.BB = l.BB;
+            grow(n, r.AA); grow(n, r.BB);
+        }
+    }
+}
+
 int BVH::build_node(std::vector<Key>& keys, int l, int r, unsigned depth)
 {
     if (l >= r) return -1;
@@ -196,6 +222,7 @@ Scene::~Scene() { free(); }
 
 void Scene::add_light_obj(Object& obj)
 {
+    for (Triangle& t : obj.get_triangles()) t.set_object((uint32_t)objects_.size());
     triangles_.insert(triangles_.end(), obj.get_triangles().begin(), obj.get_triangles().end()); // Scene.h:38-42
     light_objs_.push_back(obj);
     objects_.push_back(std::make_pair(true, obj));
@@ -203,6 +230,7 @@ void Scene::add_light_obj(Object& obj)
 }
 void Scene::add_normal_obj(Object& obj)
 {
+    for (Triangle& t : obj.get_triangles()) t.set_object((uint32_t)objects_.size());
     triangles_.insert(triangles_.end(), obj.get_triangles().begin(), obj.get_triangles().end()); // Scene.h:44-48
     objects_.push_back(std::make_pair(false, obj));
     flat_valid_ = false;
@@ -221,6 +249,44 @@ void Scene::set_BVH_device(unsigned thresh_n, int device, crt_bvh_build_info* in
     delete bvh_;
     bvh_ = nullptr;
     bvh_ = new BVH(thresh_n, triangles_, device, info);
+    flat_valid_ = false;
+}
+void Scene::transform_object(unsigned index, const float m[12])
+{
+    if (index >= objects_.size()) throw Error(CRT_ERR_INVALID_ARG, "Scene::transform_object: no such object");
+    if (!bvh_) throw Error(CRT_ERR_INVALID_ARG, "Scene::transform_object before set_BVH");
+    for (int k = 0; k < 12; k++)
+        if (!(std::fabs(m[k]) <= FLT_MAX)) throw Error(CRT_ERR_INVALID_ARG, "Scene::transform_object: a matrix entry is not finite");
+    auto map = [&](Vec3 p) {
+        float o[3];
+        const float v[3] = {p.x, p.y, p.z};
+        for (int r = 0; r < 3; r++) {
+            bool any = false;
+            float a = 0.0f;
+            for (int c = 0; c < 3; c++)
+                if (m[4 * r + c] != 0.0f) { const float t = m[4 * r + c] * v[c]; a = any ? a + t : t; any = true; }
+            if (m[4 * r + 3] != 0.0f) { a = any ? a + m[4 * r + 3] : m[4 * r + 3]; any = true; }
+            o[r] = any ? a : 0.0f;
+        }
+        return mk(o[0], o[1], o[2]);
+    };
+    auto moved = [&](const Triangle& t) {
+        Triangle n(map(t.get_v1()), map(t.get_v2()), map(t.get_v3()), t.get_material());
+        n.set_object(t.get_object());
+        return n;
+    };
+    std::vector<Triangle> ts;
+    for (const Triangle& t : objects_[index].second.get_triangles()) ts.push_back(moved(t));
+    const Object obj(ts); // the object's area, summed in its own order (Object.h:16-23)
+    if (objects_[index].first) {
+        size_t light = 0;
+        for (unsigned i = 0; i < index; i++) light += objects_[i].first ? 1 : 0;
+        light_objs_[light] = obj;
+    }
+    objects_[index].second = obj;
+    for (Triangle& t : triangles_)
+        if (t.get_object() == index) { t = moved(t); t.set_area_of_obj(obj.get_area()); }
+    bvh_->refit();
     flat_valid_ = false;
 }
 void Scene::free()

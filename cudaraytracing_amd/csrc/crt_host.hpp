@@ -69,11 +69,15 @@ public:
     const Material& get_material() const { return material_; }
     Vec3 get_min() const { return lo_; }
     Vec3 get_max() const { return hi_; }
+    // the object of the scene the triangle came with (Scene::add_*_obj numbers them; Scene::transform_object finds its triangles by it)
+    uint32_t get_object() const { return object_; }
+    void set_object(uint32_t o) { object_ = o; }
 
 private:
     Vec3 v1_, v2_, v3_, center_, normal_, lo_, hi_;
     Material material_;
     float area_ = 0.0f, area_of_obj_ = 0.0f;
+    uint32_t object_ = 0;
 };
 
 // reference: include/Object.h:7-31
@@ -111,6 +115,9 @@ public:
     const std::vector<Triangle>& get_triangles() const { return triangles_; }
     size_t get_triangles_size() const { return triangles_.size(); }
     unsigned max_depth() const { return max_depth_; }
+    // The boxes of the tree as it stands from the triangles as they now are (crt_scene_refit's rule, include/crt.h): a leaf's from the
+    // nine coordinates of each of its triangles, an inner node's as the union of its children's, in the order in which -0 < +0
+    void refit();
 
 private:
     struct Key { float c[3]; uint32_t idx; };
@@ -133,6 +140,11 @@ public:
     void add_normal_obj(Object& obj);
     void set_BVH(unsigned thresh_n);
     void set_BVH_device(unsigned thresh_n, int device, crt_bvh_build_info* info = nullptr);
+    // A 3 x 4 affine map (row-major: x' = m[0] x + m[1] y + m[2] z + m[3], ...) on the vertices of object `index` (get_objects' order),
+    // in the scene's triangles and in the light's own copies.  A term whose coefficient is 0 is left out, so the identity keeps every
+    // bit, -0 included.  normal, area and area_of_obj are recomputed as the loader computes them (Triangle, Object); the BVH keeps its
+    // topology and triangle order, and its boxes are refitted (BVH::refit).  set_BVH afterwards builds a new tree as ever.
+    void transform_object(unsigned index, const float m[12]);
     void free();
     unsigned get_height() const { return height_; }
     unsigned get_width() const { return width_; }
@@ -230,6 +242,9 @@ public:
     void run_view_map(const float eye_pos[3], const float inv_view_mat[9], float fovY, const uint32_t* sample_map, uint32_t sample_begin = 0, bool want_variance = false);
     void run_view_planned(const float eye_pos[3], const float inv_view_mat[9], float fovY, const crt_adaptive_params& ap, bool want_variance = false);
     const crt_map_info& last_map_info() const { return map_info_; }
+    // the host scene's current triangles into the device handle without rebuilding it (crt_scene_refit): after Scene::transform_object.
+    // Ends the frame in flight; one device only
+    crt_refit_info refit();
     // the error of the frame in flight, or of the last finished frame, against the adaptive call's target (crt_frame_error): reads only
     crt_frame_error_info frame_error(float threshold, float mean_floor);
     // a uniform frame rendered until it is clean enough (crt_render_until; up: crt_until_defaults with overrides): frame and mean buffers

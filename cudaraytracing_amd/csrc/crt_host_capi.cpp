@@ -83,6 +83,11 @@ int crt_host_scene_desc(const crt_host_scene* s, crt_scene_desc* out)
     if (!s || !out) { g_last_error = "crt_host_scene_desc: null argument"; return CRT_ERR_INVALID_ARG; }
     CRT_HOST_TRY(*out = const_cast<crt_host_scene*>(s)->scene.flat());
 }
+int crt_host_scene_transform_object(crt_host_scene* s, uint32_t index, const float m[12])
+{
+    if (!s || !m) { g_last_error = "crt_host_scene_transform_object: null argument"; return CRT_ERR_INVALID_ARG; }
+    CRT_HOST_TRY(s->scene.transform_object(index, m));
+}
 int crt_host_scene_num_objects(const crt_host_scene* s, uint32_t* n)
 {
     if (!s || !n) { g_last_error = "crt_host_scene_num_objects: null argument"; return CRT_ERR_INVALID_ARG; }

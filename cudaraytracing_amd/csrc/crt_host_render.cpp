@@ -228,6 +228,15 @@ void Render::run_view_planned(const float eye_pos[3], const float inv_view_mat[9
     });
 }
 
+crt_refit_info Render::refit()
+{
+    one_device("Render::refit", "a refit of the scene handle");
+    const crt_scene_desc& d = scene_->flat();
+    crt_refit_info r{};
+    check(crt_scene_refit(device_scene_, d.tris, d.n_tris, d.light_tris, d.n_light_tris, &r), "Render::refit");
+    return r;
+}
+
 crt_frame_error_info Render::frame_error(float threshold, float mean_floor)
 {
     one_device("Render::frame_error", "the frame's error summary");

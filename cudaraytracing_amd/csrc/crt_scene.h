@@ -50,6 +50,9 @@ struct ItemResults {
 // the shading form, whose six extra sums fill the two spare floats of row 2 and a fourth row
 const size_t kAovAccRows = 3, kAovAccRowsShading = 4;
 
+struct RefitState;
+void refit_release(RefitState* r); // crt_refit.hip
+
 struct crt_scene {
     int device = 0;
     crtk::DevBuf<float4> nodes, tri_geo, mats, ltri, nodes3, leaf_geo, tri_nm, nodes4, nodes4i, leaf_geo_i;
@@ -141,10 +144,15 @@ struct crt_scene {
     crtk::DevBuf<uint32_t> fe_cnt;
     crtk::DevBuf<crt_frame_error_info> fe_info;
     crt_frame_error_info* h_fe = nullptr;
+    // crt_scene_refit: the materials of the light triangles (the device keeps their emission only; the host form's check), and what
+    // the handle's first refit makes: tables, scratch, events (crt_refit.hip)
+    std::vector<int32_t> ltri_mat;
+    struct RefitState* refit = nullptr;
     std::vector<hipEvent_t> ev;
     std::vector<hipEvent_t> ev_chunk; // a timed megakernel frame: (before, after) the launch of chunk i at [2 i], [2 i + 1]
     ~crt_scene()
     {
+        refit_release(refit);
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
         if (ev_k0) (void)hipEventDestroy(ev_k0);

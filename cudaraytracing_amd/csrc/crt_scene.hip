@@ -127,6 +127,8 @@ int crt_scene_create(const crt_scene_desc* d, int device, crt_scene** out)
         sc->dev.n_lights = (int32_t)d->n_lights;
         sc->n_tris = d->n_tris;
         sc->n_mats = d->n_materials;
+        sc->ltri_mat.resize(d->n_light_tris);
+        for (uint32_t i = 0; i < d->n_light_tris; i++) sc->ltri_mat[i] = d->light_tris[i].material;
         std::memcpy(sc->root_aa, d->nodes[d->root].aa, sizeof(sc->root_aa));
         std::memcpy(sc->root_bb, d->nodes[d->root].bb, sizeof(sc->root_bb));
         create_frame_resources(sc);
@@ -151,9 +153,9 @@ int crt_scene_accel_info(crt_scene* sc, crt_accel_info* out)
 int crt_scene_export(crt_scene* sc, const char* name, void* dst, size_t capacity, size_t* bytes)
 {
     if (!bytes) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: null bytes");
-    static const char* names[] = {"nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo", "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", "scalars"};
+    static const char* names[] = {"nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo", "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", "scalars", "ltri"};
     int id = -1;
-    for (int i = 0; name && i < 11; i++)
+    for (int i = 0; name && i < 12; i++)
         if (std::strcmp(name, names[i]) == 0) id = i;
     if (id < 0) return fail(CRT_ERR_INVALID_ARG, std::string("crt_scene_export: unknown array ") + (name ? name : "(null)"));
     if (!sc) return fail(CRT_ERR_INVALID_ARG, "crt_scene_export: null scene");
@@ -179,6 +181,7 @@ int crt_scene_export(crt_scene* sc, const char* name, void* dst, size_t capacity
     case 6: arr(sc->rec_map, impl); break;
     case 7: arr(sc->tri_geo, true); break;
     case 8: arr(sc->leaf_count, true); break;
+    case 11: arr(sc->ltri, !sc->ltri_mat.empty()); break;
     default: arr(sc->tri_nm, true); break;
     }
     *bytes = n;

@@ -1460,7 +1460,7 @@ int crt_device_fn(int device, const char* name, uint32_t n, const uint32_t* in, 
 int crt_device_rcp_check(int device, uint64_t* mismatches, uint64_t* outside);
 /* Test-only export of the traversal trees a scene handle holds, copied from DEVICE memory (what the kernels read; layouts:
  * csrc/crt_device.h, csrc/crt_scene_layout.h).  `name` is one of the arrays "nodes", "nodes3", "nodes4", "nodes4i", "leaf_geo",
- * "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", or "scalars" (one crt_tree_scalars).  *bytes receives the array's
+ * "leaf_geo_i", "rec_map", "tri_geo", "leaf_count", "tri_nm", "ltri", or "scalars" (one crt_tree_scalars).  *bytes receives the array's
  * size (0 for an array the scene does not have: "nodes" / "nodes3" when the tree is one leaf, the nodes4i set when layout_caps
  * bit 3 is clear); dst == NULL asks for the size only.  An unknown name, a null `bytes`, a null scene or a capacity below the size
  * is CRT_ERR_INVALID_ARG (the name and `bytes` are checked first, so a null scene reports those). */
@@ -1472,6 +1472,60 @@ typedef struct {
     uint32_t node4i_f4;                          /* float4 per node of nodes4i (NODE4I_F4) */
 } crt_tree_scalars;
 int crt_scene_export(crt_scene* scene, const char* name, void* dst, size_t capacity, size_t* bytes);
+/* "ltri": the light triangles' rows (four float4 each: v1, v2, v3, normal, ke, area_of_obj), 0 bytes for a scene without lights. */
+
+/* Refit: new coordinates for the triangles of a scene handle, without rebuilding it.  `tris` are in the handle's BVH order and
+ * `light_tris` in its shape order -- the arrays and the layout of crt_scene_desc -- and the counts must equal the handle's.  Materials,
+ * lights, the leaves' triangle ranges [it, it + n) and every topology the handle holds stay: the reference tree and the SAH tree in
+ * `nodes` / `nodes3`, the collapsed tree in `nodes4`, its copy without refs `nodes4i`, the leaf records and `rec_map`.  Only
+ * coordinates are rewritten, and afterwards the handle renders, bit for bit, what a fresh handle renders from the description with the
+ * same topology and the refitted boxes (a frame depends on the triangles, the leaves' own boxes and on inner boxes being supersets:
+ * DESIGN.md 4).  Operation by operation (names: crt_scene_export; csrc/crt_scene_layout.h builds the same rows at crt_scene_create):
+ *   1. Rows.  e1 = v2 - v1, e2 = v3 - v1 in fp32.  tri_geo row 3 i .. 3 i + 2 = (v1.xyz, e1.x) (e1.yz, e2.xy) (e2.z, normal.xyz);
+ *      tri_nm[i] = (normal.xyz, the word it had: material and flags stay); both lanes of the dense leaf_geo records (the second lane
+ *      of an odd tail repeats the first) and their copies in leaf_geo_i at rec_map[record]; ltri row 4 j .. 4 j + 3 =
+ *      (v1.xyz, v2.x) (v2.yz, v3.xy) (v3.z, normal.xyz) (ke as it was, area_of_obj).  `area` is not stored anywhere.
+ *   2. Leaf boxes.  Per axis lo = the minimum and hi = the maximum of the nine vertex coordinates of each of the leaf's triangles, in
+ *      the order x < y, or x == y with x = -0 and y = +0: the bits do not depend on the order of evaluation.
+ *   3. Inner boxes.  Each is the union of its children's boxes under the same order, in every tree; every stored plane of nodes (both
+ *      ranges), nodes3, nodes4 and nodes4i is the plane of the child's box.  Empty slots and the empty nodes stay.
+ *   4. In nodes4i the six planes of child 0 of a mixed node (an inner child) keep their low 12 mantissa bits: each is the nearest value
+ *      outwards of the refitted plane that has the bits the plane had.  Leaf planes are exact.
+ *   5. Scalars.  crt_tree_scalars.coord_max = the largest |plane| of the used children of nodes4 and nodes4i (0 when the scene is one
+ *      leaf); the root box crt_aov_ao_defaults reads = the box of the reference tree's root.  Every other field of crt_tree_scalars,
+ *      crt_accel_info (layout_caps, depths) and the stack capacity are unchanged.
+ * Refusals, each CRT_ERR_INVALID_ARG, and each leaves the handle byte for byte as it was: a NULL scene or triangle array (light_tris
+ * may be NULL only when the handle has none), counts other than the handle's, any vertex coordinate that is not finite or has
+ * |x| > 2^126 (so step 4 cannot leave the finite floats and layout_caps cannot change; the check of ALL coordinates completes on the
+ * device before the first array is written), and -- host form only -- a triangle whose `material` differs from the handle's.  The
+ * device form does not read `material` or `area`.  `normal` and `area_of_obj` are taken as given: they are stored as they come and are
+ * not checked, in either form.
+ * A refit ends the frame in flight: the sums of crt_render_range, CRT_FLAG_VARIANCE, CRT_FLAG_HALF_BUFFERS and CRT_FLAG_PIXEL_FILTER
+ * are as after a new frame's start (a range with sample_begin > 0, crt_variance, ... are refused until a frame starts at sample 0).
+ * The order of the work items (crt_item_order) stays: the scene is not in it.
+ * crt_scene_refit_device reads two device arrays of crt_triangle on `hip_stream`, enqueues everything there and synchronizes that
+ * stream ONCE, to read one 32-byte result (the count of refused coordinates, coord_max, the root box) through pinned memory;
+ * crt_scene_refit uploads the two arrays and calls it on the null stream.  The tables the kernels walk (one entry per leaf and per
+ * inner node of every tree) are made at the handle's FIRST refit from the arrays the handle holds -- crt_scene_create does nothing
+ * for a refit -- and the time is reported in prepare_ms (0 on later calls).
+ * The inner boxes have two forms with the same bytes: CRT_REFIT_FORM=levels (one launch per node height) | walk (one launch: the
+ * last thread to arrive at a node computes it); read per call -- the calls of one handle may take either form in any order --
+ * another value is CRT_ERR_INVALID_ARG; unset: the faster one
+ * (docs/experiments.md, "Refitting a scene"). */
+typedef struct {
+    uint32_t n_tris, n_light_tris;
+    uint32_t leaves;           /* leaf boxes computed */
+    uint32_t boxes_written;    /* child boxes stored in nodes, nodes3, nodes4 and nodes4i together */
+    uint32_t launches;         /* kernel launches of the call */
+    uint32_t form;             /* 0: levels, 1: walk */
+    float root_aa[3], root_bb[3], coord_max;   /* the scalars of step 5 as the handle now holds them */
+    float prepare_ms;          /* host clock: the tables (the first refit of a handle; 0 afterwards) */
+    float device_ms;           /* HIP events around the call's launches */
+} crt_refit_info;
+int crt_scene_refit(crt_scene* scene, const crt_triangle* tris, uint32_t n_tris, const crt_triangle* light_tris, uint32_t n_light_tris,
+                    crt_refit_info* info /* may be NULL */);
+int crt_scene_refit_device(crt_scene* scene, const void* d_tris, uint32_t n_tris, const void* d_light_tris, uint32_t n_light_tris,
+                           void* hip_stream, crt_refit_info* info /* may be NULL */);
 
 /* ------------------------------------------------------------------------
  * Host layer: scene ingestion and BVH build on the CPU (north star: "C++ host
@@ -1513,6 +1567,16 @@ int crt_host_scene_num_objects(const crt_host_scene* scene, uint32_t* n);
 /* Object area as printed by the reference (Object.h:25) and whether it is a light */
 int crt_host_scene_object(const crt_host_scene* scene, uint32_t index, float* area, int32_t* is_light,
                           uint32_t* n_tris);
+
+/* Moves one object of a scene whose BVH is built: the 3 x 4 affine map m (row-major: x' = m[0] x + m[1] y + m[2] z + m[3], ...; fp32,
+ * terms in that order, a term whose coefficient is 0 left out, so the identity keeps every bit) on the vertices of object `index`
+ * (crt_host_scene_object's order), in its triangles and, for a light, in its light triangles.  normal, area and area_of_obj are
+ * recomputed with the loader's formulas (Triangle.h:27,39; Object.h:15-23).  The BVH keeps its topology and its triangle order; its
+ * boxes are refitted by crt_scene_refit's rule (leaf: minimum and maximum of its triangles' vertices, inner: the union of its
+ * children, -0 < +0), so crt_host_scene_desc then returns the moved description, whose triangle arrays crt_scene_refit takes.
+ * crt_host_scene_set_bvh afterwards builds a new tree as before.  A bad index, a matrix entry that is not finite or a scene
+ * without a BVH is CRT_ERR_INVALID_ARG. */
+int crt_host_scene_transform_object(crt_host_scene* scene, uint32_t index, const float m[12]);
 
 /* get_inverse_view_matrix (Camera.h:9-36); out = 9 floats column-major */
 int crt_inverse_view(const float eye[3], const float lookat[3], const float up[3], float out[9]);

@@ -41,6 +41,13 @@ static float4 make_float4(float x, float y, float z, float w) { return float4{x,
 #define __hip_atomic_load(p, order, scope) __atomic_load_n(p, order)
 #define __hip_atomic_store(p, v, order, scope) __atomic_store_n(p, v, order)
 #define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
+template <class T> static T __hip_atomic_fetch_max(T* p, T v, int, int) // (a compare-and-swap loop: gcc has no fetch-max)
+{
+    T seen = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (seen < v && !__atomic_compare_exchange_n(p, &seen, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return seen;
+}
+#define __builtin_amdgcn_fence(order, scope) __atomic_thread_fence(order) // crt_refit.h: the fences around an arrival
 static float __uint_as_float(unsigned int u) { float f; std::memcpy(&f, &u, 4); return f; }
 static unsigned int __float_as_uint(float f) { unsigned int u; std::memcpy(&u, &f, 4); return u; }
 using std::max;
